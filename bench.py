@@ -7,8 +7,13 @@ over +-45 deg) x ~10 top-edge samples x 2 configurations over ~400 line segments
 With --gpus N every rank runs its own batch (frames are independent units: no data-path collective,
 weak scaling); value = frames of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant kernel (score_kernel),
-"cpu_baseline" = the CPU oracle timed on a bounded sample of the same workload (rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the line: the headline
+(`value`, `ms_per_step`) and "roofline" for the dominant kernel (score_kernel) from the run's own kernel events.
+--full adds everything else the script measures: the steady state, the BA path ("ba"), the distance-map front end, image in,
+the roll/pitch stress variant, single-call latency, the line producer, the rocprofv3 counter passes behind roofline.traffic and
+roofline.valu_issue, and "cpu_baseline" = the CPU oracle timed on a bounded sample of the same workload with the timed records
+checked against it (rank 0, N=1 only).
+--dump-outputs DIR writes the cuboid records of the last timed step (every frame of its batch) as DIR/<field>.npy, float64.
 """
 from __future__ import annotations
 
@@ -110,7 +115,43 @@ def measure_traffic_live(args, n_unique):
     return avg["FETCH_SIZE"] * 1024 * 2 + avg["WRITE_SIZE"] * 1024
 
 
-def main():
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(bat, out_dir):
+    """What a caller of the timed path receives from one step -- Batch.cuboids(f) of every frame of the batch -- as DIR/<name>.npy, float64:
+    counts [frames, boxes] (records per box), index [n, 3] (frame, box, rank of the record within its box) and one array per record field,
+    row i of each belonging to index[i].  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the frames is written (frames.npy names them)."""
+    import numpy as np
+    n_frames, n_boxes = bat.n_frames, max(1, bat.max_boxes)
+    counts = bat._counts[:n_frames * n_boxes].reshape(n_frames, n_boxes).astype(np.float64)
+    per_record = 8 * (3 + 3 + 1 + 2 + 16 + 24 + 4 + 7 + 3)
+    frames = np.arange(n_frames)
+    budget = DUMP_LIMIT_BYTES - (64 << 10)      # (the .npy headers)
+    if counts.sum() * per_record + counts.nbytes > budget:
+        keep = int(n_frames * budget / (counts.sum() * per_record + counts.nbytes))
+        frames = np.sort(np.random.default_rng(0).choice(n_frames, max(1, keep), replace=False))
+    index, fields = [], {}
+    for f in frames:
+        for b, recs in enumerate(bat.cuboids(int(f))):
+            for k, rec in enumerate(recs):
+                index.append((f, b, k))
+                for name, v in rec.items():
+                    fields.setdefault(name, []).append(np.asarray(v, dtype=np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"frames": frames.astype(np.float64), "counts": counts[frames], "index": np.array(index, dtype=np.float64).reshape(-1, 3)}
+    arrays.update({name: np.stack(v) for name, v in fields.items()})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+# what a plain run (no --full) sets the options of the legs beside the headline to, and the options that only matter inside those legs
+PLAIN_LEGS = {"steady_steps": 0, "rp_frames": 0, "image_in_steps": 0, "latency_calls": 0, "lines_images": 0, "ba": "none", "no_edge": True,
+              "no_cpu_baseline": True, "no_measure_traffic": True}
+LEG_ONLY_OPTIONS = ("cpu_seconds", "ba_iters", "shard_probe", "rp_inflight")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
@@ -137,7 +178,27 @@ def main():
     ap.add_argument("--no-measure-traffic", action="store_true", help="do not collect roofline.traffic in this run (two rocprofv3 --pmc passes -- FETCH_SIZE, WRITE_SIZE; "
                     "kernel-trace only -- over a short child run of the same workload, ~20 s at N = 1); report the figure of the last tools/profile_round.sh "
                     "(profiles/pmc_traffic.json) instead, which is also the fallback when rocprofv3 is missing or a pass fails")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline (steady state, BA, front end, image in, roll/pitch stress, latency, "
+                    "line producer, counter passes, CPU baseline and the oracle check of the timed records); without it the options of those legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the cuboid records of the last timed step (every frame of its batch) to DIR/<field>.npy, float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does what the headline needs and nothing else: every other leg is off, whatever its own option says -- and an option
+        # that asked for one of those legs is named on stderr
+        ignored = [k for k, v in PLAIN_LEGS.items() if getattr(args, k) != v and getattr(args, k) != ap.get_default(k)]
+        ignored += [k for k in LEG_ONLY_OPTIONS if getattr(args, k) != ap.get_default(k)]
+        if ignored:
+            print("bench.py: without --full the legs beside the headline do not run; ignored: %s" % ", ".join("--" + k.replace("_", "-") for k in ignored),
+                  file=sys.stderr)
+        for k, v in PLAIN_LEGS.items():
+            setattr(args, k, v)
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -307,6 +368,8 @@ def main():
     # parity of the TIMED region's own output: the records the last timed step wrote, kept before any later leg reuses the batch
     N_PARITY = min(16, args.frames)
     timed_records = [last_collected[0].cuboids(f) for f in range(N_PARITY)] if (rank == 0 and last_collected[0] is not None) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_collected[0], args.dump_outputs)
     host_cpu = None
     if cg0 and cg1:      # how much CPU the timed region took and whether the container's quota throttled it (a throttled period stalls every thread)
         host_cpu = {"granted_cpus": granted if quota else None, "host_threads_per_pipeline": host_threads, "cpu_seconds_per_wall_second": (cg1[0] - cg0[0]) * 1e-6 / max(elapsed, 1e-9),
@@ -1037,12 +1100,12 @@ def main():
             wl = pt["workload"]
             if wl["frames_per_batch"] == args.frames and wl["unique"] == n_unique and world == 1:
                 traffic = pt["kernels"]["score_kernel"]["hbm_bytes_per_launch"]
-                traffic_source = "profiles/pmc_traffic.json: the same passes run by tools/profile_round.sh on this workload (not collected in this run: --no-measure-traffic, N > 1, or rocprofv3 unavailable)"
+                traffic_source = "profiles/pmc_traffic.json: the same passes run by tools/profile_round.sh on this workload (not collected in this run: no --full, --no-measure-traffic, N > 1, or rocprofv3 unavailable)"
         except (OSError, KeyError, ValueError):
             pass
         out = {
             "metric": "frames/sec detect_cuboid", "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup,
+            "warmup": args.warmup, "full": args.full,
             # what really ran before the clock started: every batch alone (sizes its buffers; the isolated kernel timings), then all pipelines side by side
             "warmup_untimed_steps": {"total": warm_alone_runs + warm_concurrent_steps, "each_batch_alone": warm_alone_runs, "all_pipelines_side_by_side": warm_concurrent_steps,
                                      "what": "--warmup W = %d: W runs of each of the %d batches alone, then max(W, batches) x %s steps driven exactly like the timed steps" % (args.warmup, inflight * depth, os.environ.get("CS_BENCH_WARMUP_ROUNDS", "4"))},

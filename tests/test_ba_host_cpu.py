@@ -64,7 +64,8 @@ H.close()
 
 
 def _run(shim, threads):
-    env = dict(os.environ, LD_PRELOAD=str(shim), CS_BA_UPLOAD_KERNEL="0")     # (kernels do not run under the shim: the tables go up by per-table copies)
+    # (kernels do not run under the shim: the tables go up by per-table copies; whatever the environment already preloads stays preloaded)
+    env = dict(os.environ, LD_PRELOAD=":".join(p for p in (str(shim), os.environ.get("LD_PRELOAD", "")) if p), CS_BA_UPLOAD_KERNEL="0")
     env.pop("CS_BA_STRUCT_THREADS", None)
     if threads:
         env["CS_BA_STRUCT_THREADS"] = str(threads)

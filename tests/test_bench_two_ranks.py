@@ -11,7 +11,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QUICK = ["--steps", "4", "--warmup", "1", "--steady-steps", "0", "--latency-calls", "0", "--lines-images", "0", "--rp-frames", "0", "--no-edge", "--no-measure-traffic",
+QUICK = ["--full", "--steps", "4", "--warmup", "1", "--steady-steps", "0", "--latency-calls", "0", "--lines-images", "0", "--rp-frames", "0", "--no-edge", "--no-measure-traffic",
          "--no-cpu-baseline", "--frames", "200", "--unique", "20"]
 
 

@@ -44,12 +44,13 @@ def test_no_product_file_references_the_oracle():
                 assert "oracle/" not in txt and "import oracle" not in txt and "from oracle" not in txt, os.path.join(d, f)
 
 
-def test_bench_traffic_passes_fall_back_without_a_device():
+def test_bench_traffic_passes_fall_back_without_a_device(monkeypatch):
     """bench.py collects roofline.traffic with two rocprofv3 child passes; when they cannot run (here: no HIP device, so the child
     exits at once; on a box without rocprofv3: not found) the function must return None -- the caller then reports the tracked
     figure -- and must not raise."""
     import importlib.util
     import types
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")      # no HIP device for the child passes, on a GPU machine too
     spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)

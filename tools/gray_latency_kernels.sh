@@ -1,10 +1,10 @@
-# kernels of ONE cs_detect_cuboids_gray call (one KITTI-shaped frame, 8 ROIs): durations from a kernel trace of the bench's latency leg (run on the GPU box)
-export TMPDIR=/tmp; R=$(pwd); cd /tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/kt_gray -o kt -- python $R/bench.py --steps 1 --warmup 0 --ba none --no-cpu-baseline --rp-frames 0 --latency-calls 60 --lines-images 0 --no-measure-traffic > $R/gpurun_out/kt_gray.log 2>&1
+# kernels of ONE cs_detect_cuboids_gray call (one KITTI-shaped frame, 8 ROIs): durations from a kernel trace of the bench's latency leg (run on a GPU machine; results under $OUT, default out/)
+export TMPDIR=/tmp; R=$(pwd); OUT=${OUT:-$R/out}; mkdir -p $OUT; cd /tmp
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_gray -o kt -- python $R/bench.py --full --steps 1 --warmup 0 --ba none --no-cpu-baseline --rp-frames 0 --latency-calls 60 --lines-images 0 --no-measure-traffic > $OUT/kt_gray.log 2>&1
 cd $R
 python - <<PY
 import csv, glob, collections
-f = glob.glob("gpurun_out/kt_gray/**/kt_kernel_trace.csv", recursive=True)[0]
+f = glob.glob("$OUT/kt_gray/**/kt_kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last gray call: find the last edge_canny launch with a small grid and print the kernels from there to the next record_kernel
