@@ -2663,15 +2663,14 @@ void ba_launch_chi2(const BaView& v, int nb_proj, hipStream_t st) {
 // ev_pre (optional): an event ALREADY recorded on st at the point from which the state no longer changes -- the side streams then start from
 // there instead of from this call (a speculated linearisation: the numeric-Jacobian edges run beside the chi2 kernels of the trial before it)
 void ba_launch_linearize(const BaView& v, hipStream_t st, hipStream_t st2, hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t st3, hipEvent_t ev_join3, hipEvent_t ev_pre) {
-  const bool side = st2 != nullptr && v.n_cub > 0;
+  const bool side = v.n_cub > 0;
   const bool lin_pt = v.np > 0 && !v.fuse_lin;       // (fuse_lin: the Schur kernels of this iteration's trials linearise the landmark side themselves)
-  const bool side3 = st3 != nullptr && ev_join3 != nullptr && lin_pt && (v.n_proj > 0 || v.nc > 0);
+  const bool side3 = lin_pt && (v.n_proj > 0 || v.nc > 0);
   hipStream_t se = side ? st2 : st;
   if ((side || side3) && !ev_pre) (void)hipEventRecord(ev_fork, st);
   if (ev_pre) ev_fork = ev_pre;
   if (side) (void)hipStreamWaitEvent(st2, ev_fork, 0);
-  static const bool odom_own_launch = getenv("CS_BA_ODOM_OWN_LAUNCH") != nullptr;      // (the former form: A / B)
-  const int ob = (!odom_own_launch && v.n_cub3 > 0 && v.n_odom > 0) ? (v.n_odom + 7) / 8 : 0;      // the odometry edges as the cuboid launch's first workgroups
+  const int ob = (v.n_cub3 > 0 && v.n_odom > 0) ? (v.n_odom + 7) / 8 : 0;      // the odometry edges as the cuboid launch's first workgroups
   if (v.n_cub3 > 0) hipLaunchKernelGGL(ba_cub_edge_kernel<true>, dim3((v.n_cub3 + 3) / 4 + ob), dim3(128), 0, se, v, ob);
   if (v.n_cub > v.n_cub3) hipLaunchKernelGGL(ba_cub_edge_kernel<false>, dim3((v.n_cub - v.n_cub3 + 3) / 4), dim3(128), 0, se, v, 0);
   // (the odometry edges: a single short wave per four edges, 38 us of latency -- beside the cuboid edges on the main stream, not behind

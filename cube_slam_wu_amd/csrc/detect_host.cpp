@@ -57,15 +57,17 @@ void launch_rp_save_fallback(const DetectDeviceView& v, const RpSaveView& s, hip
 struct EdgeRoi { int l, t, w, h; long long img_off, cls_off, map_off; };
 struct CopySeg { const void* src; void* dst; unsigned long long bytes; };
 struct CopySegs { CopySeg s[16]; int n; };
+// appends the copy of cnt elements of from's buffer to to's (nothing when cnt is 0)
+template <class To, class From> inline void add_copy(CopySegs& cp, const To& to, const From& from, long long cnt) {
+  if (cnt > 0) { cp.s[cp.n].src = from.p; cp.s[cp.n].dst = to.p; cp.s[cp.n].bytes = sizeof(*from.p) * (unsigned long long)cnt; cp.n++; }
+}
 void launch_multi_copy(const CopySegs& segs, hipStream_t st);
 void launch_edge_maps(const unsigned char* gray, int W, int H, const EdgeRoi* rois, int n_rois, unsigned char* cls_pool, float* map_pool, int max_w, long long max_px, int low, int high,
                       hipStream_t st);
 void launch_line_setup(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order = nullptr, hipStream_t st_crowded = nullptr,
-                       hipEvent_t fork = nullptr, hipEvent_t join = nullptr);
+                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st);
 void launch_line_setup_listed(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                              double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded,
-                              hipStream_t st_mid = nullptr, hipEvent_t join_mid = nullptr);
+                              double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded);
 int line_setup_capacity();
 void launch_gather_ranges(const DetectDeviceView& v, const long long* src_off, const int* count, const long long* dst_off, int n_ranges,
                           double* o_dist, double* o_angle, double* o_skew, int* o_flag, long long* o_slot, hipStream_t st);
@@ -384,7 +386,7 @@ struct cs_detector {
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;   // tie-break re-ranking fetches of the previous chunk, concurrent with the next chunk's sweep
   hipStream_t stream3 = nullptr;   // line setup of the crowded ROIs, beside the line setup of all the others
-  hipStream_t stream4 = nullptr;   // ... of the ROIs of 129 .. 256 segments (their own, smaller instance)
+  hipStream_t stream4 = nullptr;   // runs nothing: streams take hardware queues in creation order, and without it the contract run was 4 % slower (450-470 k against 478-489 k frames/s)
   hipStream_t stream_hi = nullptr; // high priority: the small fetches of the tie boxes, which the host waits for while another batch's sweep owns the device
   hipEvent_t ev[12] = {};
   int n_threads = 1;
@@ -443,12 +445,12 @@ struct PipeSlot {
   PinBuf<unsigned char> h_tab_arena;
   bool merged_io = false;                // this slot's call went through the block: its results are unpacked from h_tab_arena in pipe_finish
   size_t o_jobs = 0, o_rec = 0, o_wc = 0, o_fb = 0, o_jv = 0, o_cb = 0, o_end = 0;
-  DevBuf<long long> slot_prefix, job_cbase, c_slot, fb_src, fb_dst, fb_slot, win_slots;
-  DevBuf<int> vp_prefix, top_x, flag, job_valid, c_flag, box_job0, box_njobs, win_count, fallback, fb_cnt, fb_flag;
+  DevBuf<long long> slot_prefix, job_cbase, c_slot, fb_slot;
+  DevBuf<int> vp_prefix, top_x, flag, job_valid, c_flag, box_job0, box_njobs, win_count, fallback, fb_flag;
   DevBuf<double> bound3;
   DevBuf<int> ls_order, blk_info, ls_crowded;
   PinBuf<int> h_ls_order;
-  DevBuf<double> mid_x, mid_y, ang, yaw, yaw_c, yaw_s, vp, bound, corners, c_dist, c_angle, c_skew, fb_dist, fb_angle, fb_skew, win_corners;
+  DevBuf<double> mid_x, mid_y, ang, yaw, yaw_c, yaw_s, vp, bound, c_dist, c_angle, c_skew, fb_dist, fb_angle, fb_skew;
   DevBuf<cs::RankWinner> winners;
   DevBuf<cs_cuboid> records;        // the winners' records of the device-ranked boxes (record_kernel)
   PinBuf<cs_cuboid> h_records;
@@ -473,24 +475,23 @@ struct PipeSlot {
   PinBuf<long long> h_slot_prefix, h_job_cbase;
   PinBuf<int> h_vp_prefix, h_top_x, h_box_job0, h_box_njobs, h_win_count, h_fallback, h_job_valid;
   PinBuf<double> h_yaw, h_yaw_c, h_yaw_s;
-  PinBuf<cs::RankWinner> h_winners;
   PinBuf<long long> h_fb_src, h_fb_dst, h_fb_slot, h_win_slots;
   PinBuf<int> h_fb_cnt, h_fb_flag;
   PinBuf<double> h_fb_dist, h_fb_angle, h_fb_skew, h_win_corners;
-  hipEvent_t done = nullptr, ev[14] = {};   // 0-6: phase marks on the main stream; 7: inputs resident; 8-11: second stream (corner construction); 12: line setup of the crowded ROIs done (third stream)
+  hipEvent_t done = nullptr, ev[13] = {};   // 0-6: phase marks on the main stream; 7: inputs resident; 8-11: second stream (corner construction); 12: line setup of the crowded ROIs done (third stream)
   cs::DetectDeviceView view{};
   int f0 = 0, f1 = 0, vp_total = 0;
   size_t nj = 0, nb = 0;
   long long slot_total = 0;
   bool in_flight = false;
   void release() {
-    jobs.release(); slot_prefix.release(); job_cbase.release(); c_slot.release(); fb_src.release(); fb_dst.release(); fb_slot.release(); win_slots.release();
+    jobs.release(); slot_prefix.release(); job_cbase.release(); c_slot.release(); fb_slot.release();
     vp_prefix.release(); top_x.release(); flag.release(); job_valid.release(); c_flag.release(); box_job0.release(); box_njobs.release(); win_count.release();
-    fallback.release(); fb_cnt.release(); fb_flag.release(); mid_x.release(); mid_y.release(); ang.release(); yaw.release(); yaw_c.release(); yaw_s.release();
-    vp.release(); bound.release(); bound3.release(); ls_order.release(); blk_info.release(); ls_crowded.release(); h_ls_order.release(); corners.release(); c_dist.release(); c_angle.release(); c_skew.release(); fb_dist.release(); fb_angle.release(); fb_skew.release();
-    win_corners.release(); winners.release(); records.release(); h_records.release(); rp_trip_cnt.release(); rp_cur_idx.release(); rp_tab_count.release(); rp_maps.release(); rp_last_slot.release(); rp_box_base.release(); rp_pool_used.release(); rp_raw_euler.release(); h_rp_tab_count.release(); h_rp_maps.release(); h_rp_raw_euler.release(); h_rp_last_slot.release(); h_rp_box_base.release(); h_rp_pool_used.release(); h_jobs_in.release(); h_jobs_out.release(); h_slot_prefix.release(); h_job_cbase.release(); h_vp_prefix.release();
+    fallback.release(); fb_flag.release(); mid_x.release(); mid_y.release(); ang.release(); yaw.release(); yaw_c.release(); yaw_s.release();
+    vp.release(); bound.release(); bound3.release(); ls_order.release(); blk_info.release(); ls_crowded.release(); h_ls_order.release(); c_dist.release(); c_angle.release(); c_skew.release(); fb_dist.release(); fb_angle.release(); fb_skew.release();
+    winners.release(); records.release(); h_records.release(); rp_trip_cnt.release(); rp_cur_idx.release(); rp_tab_count.release(); rp_maps.release(); rp_last_slot.release(); rp_box_base.release(); rp_pool_used.release(); rp_raw_euler.release(); h_rp_tab_count.release(); h_rp_maps.release(); h_rp_raw_euler.release(); h_rp_last_slot.release(); h_rp_box_base.release(); h_rp_pool_used.release(); h_jobs_in.release(); h_jobs_out.release(); h_slot_prefix.release(); h_job_cbase.release(); h_vp_prefix.release();
     h_top_x.release(); h_box_job0.release(); h_box_njobs.release(); h_win_count.release(); h_fallback.release(); h_job_valid.release(); h_yaw.release();
-    h_yaw_c.release(); h_yaw_s.release(); h_winners.release();
+    h_yaw_c.release(); h_yaw_s.release();
     h_fb_src.release(); h_fb_dst.release(); h_fb_slot.release(); h_win_slots.release(); h_fb_cnt.release(); h_fb_flag.release(); h_fb_dist.release(); h_fb_angle.release();
     h_fb_skew.release(); h_win_corners.release();
     if (done) (void)hipEventDestroy(done);
@@ -1102,8 +1103,6 @@ namespace {
 static double g_mark[16];
 static int g_runs = 0;
 static const bool g_prof = getenv("CS_DETECT_PROF") != nullptr;   // diagnostics: host phase clock of the lean path
-static const bool g_split_candidates = getenv("CS_DETECT_SPLIT_CANDIDATES") != nullptr;   // vp_points + candidate + scan + compact as separate kernels (the form before round 6) instead of candidate_compact_kernel
-static const bool g_dma_tables = getenv("CS_DETECT_DMA_TABLES") != nullptr;   // a batch's tables / results through hipMemcpyAsync (the form before round 6) instead of multi_copy_kernel
 #define MARK(k, t_ref) do { if (g_prof) { double t_now = now_ms(); g_mark[k] += t_now - (t_ref); (t_ref) = t_now; } } while (0)
 
 int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
@@ -1217,13 +1216,11 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   PENS(S.ls_order, nj); PENS(S.jobs, nj); PENS(S.slot_prefix, nj + 1); PENS(S.vp_prefix, nj + 1); PENS(S.job_valid, nj); PENS(S.job_cbase, nj + 1);
   PENS(S.mid_x, n_lines + 1); PENS(S.mid_y, n_lines + 1); PENS(S.ang, n_lines + 1); PENS(S.yaw, n_yaw + 1); PENS(S.yaw_c, n_yaw + 1); PENS(S.yaw_s, n_yaw + 1);
   PENS(S.top_x, n_top + 1); PENS(S.vp, 6 * (size_t)S.vp_total + 6); PENS(S.bound, 6 * (size_t)S.vp_total + 6); PENS(S.bound3, nj * (size_t)cs::vp3_table_doubles_per_job());
-  if (g_split_candidates) PENS(S.flag, slot_total + 1); else PENS(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4);
-  PENS(S.ls_crowded, 2 * (nj + 1) + 2);
+  PENS(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4); PENS(S.ls_crowded, 2 * (nj + 1) + 2);
   PENS(S.c_slot, slot_total + 1); PENS(S.c_flag, slot_total + 1); PENS(S.c_dist, slot_total + 1);
   PENS(S.c_angle, slot_total + 1); PENS(S.c_skew, slot_total + 1); PENS(S.box_job0, nb + 1); PENS(S.box_njobs, nb + 1); PENS(S.win_count, nb + 1);
   PENS(S.fallback, nb + 1); PENS(S.winners, nb * KMAX + 1); PENS(S.records, nb * KMAX + 1); PENS(S.h_records, nb * KMAX + 1);
-  PENS(S.h_winners, nb * KMAX + 1); PENS(S.h_win_count, nb + 1); PENS(S.h_fallback, nb + 1); PENS(S.h_job_valid, nj); PENS(S.h_job_cbase, nj + 1); PENS(S.h_jobs_out, nj);
-#define PH2D(dst, src, n) HIP_TRY(hipMemcpyAsync((dst).p, (src).p, sizeof(*(src).p) * (n), hipMemcpyHostToDevice, st))
+  PENS(S.h_win_count, nb + 1); PENS(S.h_fallback, nb + 1); PENS(S.h_job_valid, nj); PENS(S.h_job_cbase, nj + 1); PENS(S.h_jobs_out, nj);
   // the tables' device addresses: the slot's own buffers, or -- a call of a frame or two, where ten copies of a few hundred bytes cost ten
   // launch latencies (~150 us of a 0.46 ms call) -- pieces of ONE block that goes up in one copy
   int* p_ls_order = S.ls_order.p; cs::JobDesc* p_jobs = S.jobs.p; long long* p_slot_prefix = S.slot_prefix.p; int* p_vp_prefix = S.vp_prefix.p;
@@ -1256,54 +1253,34 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   } else {
     // a batch's tables: one kernel reads all ten out of the pinned staging pools (no copy-engine ring in the sweep: see multi_copy_kernel)
     cs::CopySegs cp{};
-#define SEG(to_, from_, cnt_) do { if ((cnt_) > 0) { cp.s[cp.n].src = (from_).p; cp.s[cp.n].dst = (to_).p; cp.s[cp.n].bytes = sizeof(*(from_).p) * (unsigned long long)(cnt_); cp.n++; } } while (0)
-    if (g_dma_tables) {
-      PH2D(S.ls_order, S.h_ls_order, nj); PH2D(S.jobs, S.h_jobs_in, nj); PH2D(S.slot_prefix, S.h_slot_prefix, nj + 1); PH2D(S.vp_prefix, S.h_vp_prefix, nj + 1);
-      if (n_yaw) { PH2D(S.yaw, S.h_yaw, n_yaw); PH2D(S.yaw_c, S.h_yaw_c, n_yaw); PH2D(S.yaw_s, S.h_yaw_s, n_yaw); }
-      if (n_top) PH2D(S.top_x, S.h_top_x, n_top);
-      if (nb) { PH2D(S.box_job0, S.h_box_job0, nb); PH2D(S.box_njobs, S.h_box_njobs, nb); }
-    } else {
-      SEG(S.ls_order, S.h_ls_order, nj); SEG(S.jobs, S.h_jobs_in, nj); SEG(S.slot_prefix, S.h_slot_prefix, nj + 1); SEG(S.vp_prefix, S.h_vp_prefix, nj + 1);
-      SEG(S.yaw, S.h_yaw, n_yaw); SEG(S.yaw_c, S.h_yaw_c, n_yaw); SEG(S.yaw_s, S.h_yaw_s, n_yaw); SEG(S.top_x, S.h_top_x, n_top);
-      SEG(S.box_job0, S.h_box_job0, nb); SEG(S.box_njobs, S.h_box_njobs, nb);
-      cs::launch_multi_copy(cp, st);
-    }
+    cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, S.jobs, S.h_jobs_in, nj); cs::add_copy(cp, S.slot_prefix, S.h_slot_prefix, nj + 1);
+    cs::add_copy(cp, S.vp_prefix, S.h_vp_prefix, nj + 1); cs::add_copy(cp, S.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, S.yaw_c, S.h_yaw_c, n_yaw);
+    cs::add_copy(cp, S.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, S.top_x, S.h_top_x, n_top); cs::add_copy(cp, S.box_job0, S.h_box_job0, nb);
+    cs::add_copy(cp, S.box_njobs, S.h_box_njobs, nb);
+    cs::launch_multi_copy(cp, st);
   }
-  if (g_split_candidates) HIP_TRY(hipMemsetAsync(p_job_valid, 0, sizeof(int) * nj, st));      // (candidate_kernel counts with atomics; the fused kernel writes every job's count)
   cs::DetectDeviceView& v = S.view;
   v = cs::DetectDeviceView{};
   v.jobs = p_jobs; v.n_jobs = (int)nj; v.slot_prefix = p_slot_prefix; v.vp_prefix = p_vp_prefix; v.maps = b->d_maps.p;
   v.mid_x = S.mid_x.p; v.mid_y = S.mid_y.p; v.line_angle = S.ang.p; v.yaw = p_yaw; v.yaw_cos = p_yaw_c; v.yaw_sin = p_yaw_s; v.top_x = p_top_x;
-  v.rp = b->d_rp.p; v.invK = b->d_invK.p; v.vp = S.vp.p; v.bound = S.bound.p; v.bound3 = S.bound3.p; v.flag = S.flag.p; v.job_valid = p_job_valid;
+  v.rp = b->d_rp.p; v.invK = b->d_invK.p; v.vp = S.vp.p; v.bound = S.bound.p; v.bound3 = S.bound3.p; v.job_valid = p_job_valid;
   v.job_cbase = p_job_cbase; v.c_slot = S.c_slot.p; v.c_flag = S.c_flag.p; v.c_dist = S.c_dist.p; v.c_angle = S.c_angle.p; v.c_skew = S.c_skew.p;
   // The corner construction needs the vanishing points but not the segments: it runs on the second stream beside line
   // setup + VP support (a latency-bound and an ALU-bound kernel), and the scorer waits for both.
   hipStream_t stB = d->stream2;
-  HIP_TRY(hipEventRecord(S.ev[7], st));                      // inputs resident, job_valid zeroed
+  HIP_TRY(hipEventRecord(S.ev[7], st));                      // inputs resident
   HIP_TRY(hipStreamWaitEvent(stB, S.ev[7], 0));
   HIP_TRY(hipEventRecord(S.ev[8], stB));
-  if (g_split_candidates) {
-    cs::launch_vp_points(v, S.vp_total, stB);
-    cs::launch_candidates(v, C.sp, slot_total, stB);
-    HIP_TRY(hipEventRecord(S.ev[9], stB));
-    cs::launch_scan_compact(v, stB);
-  } else {
-    // vanishing points, corner construction and ordered compaction of a job in one workgroup (candidate_compact_kernel); the compacted rows
-    // of job j start at slot_prefix[j]: no scan over all jobs between this kernel and the scorer
-    v.blk_info = S.blk_info.p;
-    HIP_TRY(hipMemsetAsync(S.blk_info.p, 0, sizeof(int), stB));
-    cs::launch_candidate_compact(v, C.sp, stB);
-    HIP_TRY(hipEventRecord(S.ev[9], stB));
-  }
+  // vanishing points, corner construction and ordered compaction of a job in one workgroup (candidate_compact_kernel); the compacted rows
+  // of job j start at slot_prefix[j]: no scan over all jobs between this kernel and the scorer
+  v.blk_info = S.blk_info.p;
+  HIP_TRY(hipMemsetAsync(S.blk_info.p, 0, sizeof(int), stB));
+  cs::launch_candidate_compact(v, C.sp, stB);
+  HIP_TRY(hipEventRecord(S.ev[9], stB));
   HIP_TRY(hipEventRecord(S.ev[10], stB));
   HIP_TRY(hipEventRecord(S.ev[0], st));
-  static const bool ls_unlisted = getenv("CS_DETECT_LS_UNLISTED") != nullptr;      // (the former form: a workgroup of the crowded instance per job -- A / B)
-  if (!ls_unlisted && d->stream3)
-    cs::launch_line_setup_listed(p_jobs, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
-                                 d->stream3, S.ev[0], S.ev[12], S.ls_crowded.p, d->stream4, S.ev[13]);
-  else
-    cs::launch_line_setup(p_jobs, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
-                          d->stream3, S.ev[0], S.ev[12]);
+  cs::launch_line_setup_listed(p_jobs, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
+                               d->stream3, S.ev[0], S.ev[12], S.ls_crowded.p);
   HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::launch_vp_support_only(v, C.sp, S.vp_total, st, 1);      // (this path's jobs have one roll/pitch sample: jd.RP = 1 above)
   HIP_TRY(hipEventRecord(S.ev[2], st));
@@ -1320,23 +1297,11 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   HIP_TRY(hipGetLastError());
   if (S.merged_io) {
     HIP_TRY(hipMemcpyAsync(S.h_tab_arena.p + S.o_jobs, S.tab_arena.p + S.o_jobs, S.o_end - S.o_jobs, hipMemcpyDeviceToHost, st));   // unpacked in pipe_finish
-  } else {
-    if (g_dma_tables) {
-      if (nb) {
-        HIP_TRY(hipMemcpyAsync(S.h_records.p, S.records.p, sizeof(cs_cuboid) * nb * KMAX, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(S.h_win_count.p, S.win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(S.h_fallback.p, S.fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-      }
-      HIP_TRY(hipMemcpyAsync(S.h_job_valid.p, S.job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(S.h_job_cbase.p, S.job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(S.h_jobs_out.p, p_jobs, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
-    } else {   // the results: written to the pinned host pools by one kernel
-      cs::CopySegs cp{};
-      SEG(S.h_records, S.records, nb * KMAX); SEG(S.h_win_count, S.win_count, nb); SEG(S.h_fallback, S.fallback, nb);
-      SEG(S.h_job_valid, S.job_valid, nj); SEG(S.h_job_cbase, S.job_cbase, nj + 1);      // (the job table itself is not read back: pipe_finish works from the host's own copy)
-      cs::launch_multi_copy(cp, st);
-    }
-#undef SEG
+  } else {   // the results: written to the pinned host pools by one kernel
+    cs::CopySegs cp{};
+    cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, S.h_win_count, S.win_count, nb); cs::add_copy(cp, S.h_fallback, S.fallback, nb);
+    cs::add_copy(cp, S.h_job_valid, S.job_valid, nj); cs::add_copy(cp, S.h_job_cbase, S.job_cbase, nj + 1);      // (the job table itself is not read back: pipe_finish works from the host's own copy)
+    cs::launch_multi_copy(cp, st);
   }
   HIP_TRY(hipEventRecord(S.done, st));
   S.in_flight = true;
@@ -1374,9 +1339,8 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     long long n_valid = 0;      // (the capacity layout has no running total: job_cbase[j] = slot_prefix[j])
     for (size_t j = 0; j < nj; j++) n_valid += S.h_job_valid.p[j];
     tm.n_valid += n_valid;
-    // algorithmic bytes of the corner construction: the vanishing points it writes (48 B each) + what leaves it per slot -- a 4-byte flag per
-    // slot in the four-kernel form, 12 bytes (slot id, flag) per VALID proposal from candidate_compact_kernel
-    tm.cand_kernel_bytes += g_split_candidates ? 48LL * S.vp_total + 4LL * S.slot_total : 48LL * S.vp_total + 12LL * n_valid;
+    // algorithmic bytes of the corner construction: the vanishing points it writes (48 B each) + 12 bytes (slot id, flag) per VALID proposal
+    tm.cand_kernel_bytes += 48LL * S.vp_total + 12LL * n_valid;
     long long sbytes = 96LL * S.vp_total + (28LL + 8LL + 4LL) * n_valid;
     for (size_t j = 0; j < nj; j++) if (S.h_jobs_in.p[j].Y > 0 && S.h_jobs_in.p[j].T > 0) sbytes += 4LL * S.h_jobs_in.p[j].map_w * (S.h_jobs_in.p[j].g.eb - S.h_jobs_in.p[j].g.et);
     tm.score_kernel_bytes += sbytes;
@@ -1401,28 +1365,13 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   int rc;
   if (!fb_src.empty()) {
     size_t nr = fb_src.size();
-    PENS(S.fb_src, nr); PENS(S.fb_dst, nr); PENS(S.fb_cnt, nr); PENS(S.h_fb_src, nr); PENS(S.h_fb_dst, nr); PENS(S.h_fb_cnt, nr);
-    PENS(S.fb_dist, tot + 1); PENS(S.fb_angle, tot + 1); PENS(S.fb_skew, tot + 1); PENS(S.fb_flag, tot + 1); PENS(S.fb_slot, tot + 1);
+    PENS(S.h_fb_src, nr); PENS(S.h_fb_dst, nr); PENS(S.h_fb_cnt, nr);
     PENS(S.h_fb_dist, tot + 1); PENS(S.h_fb_angle, tot + 1); PENS(S.h_fb_skew, tot + 1); PENS(S.h_fb_flag, tot + 1); PENS(S.h_fb_slot, tot + 1);
     std::copy(fb_src.begin(), fb_src.end(), S.h_fb_src.p); std::copy(fb_dst.begin(), fb_dst.end(), S.h_fb_dst.p); std::copy(fb_cnt.begin(), fb_cnt.end(), S.h_fb_cnt.p);
-    if (g_dma_tables) {
-      HIP_TRY(hipMemcpyAsync(S.fb_src.p, S.h_fb_src.p, 8 * nr, hipMemcpyHostToDevice, st2));
-      HIP_TRY(hipMemcpyAsync(S.fb_dst.p, S.h_fb_dst.p, 8 * nr, hipMemcpyHostToDevice, st2));
-      HIP_TRY(hipMemcpyAsync(S.fb_cnt.p, S.h_fb_cnt.p, 4 * nr, hipMemcpyHostToDevice, st2));
-      cs::launch_gather_ranges(S.view, S.fb_src.p, S.fb_cnt.p, S.fb_dst.p, (int)nr, S.fb_dist.p, S.fb_angle.p, S.fb_skew.p, S.fb_flag.p, S.fb_slot.p, st2);
-      if (tot) {
-        HIP_TRY(hipMemcpyAsync(S.h_fb_dist.p, S.fb_dist.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st2));
-        HIP_TRY(hipMemcpyAsync(S.h_fb_angle.p, S.fb_angle.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st2));
-        HIP_TRY(hipMemcpyAsync(S.h_fb_skew.p, S.fb_skew.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st2));
-        HIP_TRY(hipMemcpyAsync(S.h_fb_flag.p, S.fb_flag.p, 4 * (size_t)tot, hipMemcpyDeviceToHost, st2));
-        HIP_TRY(hipMemcpyAsync(S.h_fb_slot.p, S.fb_slot.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st2));
-      }
-    } else {
-      // the range lists are read from, and the columns written to, the pinned host pools by the gather kernel itself (coalesced rows; no
-      // copy engine between the device and a host that is waiting for a few kilobytes)
-      cs::launch_gather_ranges(S.view, S.h_fb_src.p, S.h_fb_cnt.p, S.h_fb_dst.p, (int)nr, S.h_fb_dist.p, S.h_fb_angle.p, S.h_fb_skew.p, S.h_fb_flag.p, S.h_fb_slot.p, st2);
-      HIP_TRY(hipGetLastError());
-    }
+    // the range lists are read from, and the columns written to, the pinned host pools by the gather kernel itself (coalesced rows; no
+    // copy engine between the device and a host that is waiting for a few kilobytes)
+    cs::launch_gather_ranges(S.view, S.h_fb_src.p, S.h_fb_cnt.p, S.h_fb_dst.p, (int)nr, S.h_fb_dist.p, S.h_fb_angle.p, S.h_fb_skew.p, S.h_fb_flag.p, S.h_fb_slot.p, st2);
+    HIP_TRY(hipGetLastError());
   }
   MARK(5, tq);   // tie lists + gather enqueue
   // ---- records of the winners.  The boxes the device ranked are written while the tie boxes' columns travel.
@@ -1501,8 +1450,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     }
     C.out_counts[(size_t)f * MB + bi] = nw;
   };
-  static const bool tie_separate = getenv("CS_TIE_SEPARATE_PASS") != nullptr;   // diagnostics: always the two-pass order
-  if (fbq.size() <= 64 && !tie_separate) {
+  if (fbq.size() <= 64) {
     // a handful of tie boxes (the usual case): their columns are a few kilobytes and already here; their exact ranking
     // (tens of microseconds each) rides in the same parallel pass as the records of the other boxes, first in the queue
     if (!fb_src.empty()) HIP_TRY(hipStreamSynchronize(st2));
@@ -1527,15 +1475,9 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     std::vector<long long> ws;
     for (int q : fbq) for (auto& w : fb_winners[q]) ws.push_back(w.slot);
     if (!ws.empty()) {
-      PENS(S.win_slots, ws.size()); PENS(S.win_corners, 16 * ws.size()); PENS(S.h_win_slots, ws.size()); PENS(S.h_win_corners, 16 * ws.size());
+      PENS(S.h_win_slots, ws.size()); PENS(S.h_win_corners, 16 * ws.size());
       std::copy(ws.begin(), ws.end(), S.h_win_slots.p);
-      if (g_dma_tables) {
-        HIP_TRY(hipMemcpyAsync(S.win_slots.p, S.h_win_slots.p, 8 * ws.size(), hipMemcpyHostToDevice, st2));
-        cs::launch_gather_corners(S.view, C.sp, S.win_slots.p, (int)ws.size(), S.win_corners.p, st2);
-        HIP_TRY(hipMemcpyAsync(S.h_win_corners.p, S.win_corners.p, 8 * 16 * ws.size(), hipMemcpyDeviceToHost, st2));
-      } else {
-        cs::launch_gather_corners(S.view, C.sp, S.h_win_slots.p, (int)ws.size(), S.h_win_corners.p, st2);     // (pinned host memory on both sides)
-      }
+      cs::launch_gather_corners(S.view, C.sp, S.h_win_slots.p, (int)ws.size(), S.h_win_corners.p, st2);     // (pinned host memory on both sides)
       HIP_TRY(hipStreamSynchronize(st2));
       const double* hc = S.h_win_corners.p;
       size_t z = 0;
@@ -1550,7 +1492,6 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   return CS_OK;
 }
 #undef PENS
-#undef PH2D
 
 // ================================================================== lean roll/pitch path =========
 // whether_sample_cam_roll_pitch = 1 (the reference class's default; main_obj.cpp:623 uses it from the second frame on).  The boxes of a
@@ -1691,33 +1632,21 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   PENS(S.rp_box_base, nb + 1); PENS(S.rp_pool_used, 1); PENS(S.h_rp_box_base, nb + 1); PENS(S.h_rp_pool_used, 1); PENS(S.h_rp_last_slot, nb + 1); PENS(S.h_job_valid, nj + 1); PENS(S.h_jobs_out, nj + 1);
   HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
   PENS(S.rp_cur_idx, (size_t)NF + 1); PENS(S.rp_tab_count, (size_t)NF * NT + 1); PENS(S.rp_maps, 3 * (size_t)MB * NF + 1); PENS(S.rp_raw_euler, 3 * (size_t)NF + 1);
-#define PH2D(dst, src, n) HIP_TRY(hipMemcpyAsync((dst).p, (src).p, sizeof(*(src).p) * (n), hipMemcpyHostToDevice, st))
-#define SEG(to_, from_, cnt_) do { if ((cnt_) > 0) { cp.s[cp.n].src = (from_).p; cp.s[cp.n].dst = (to_).p; cp.s[cp.n].bytes = sizeof(*(from_).p) * (unsigned long long)(cnt_); cp.n++; } } while (0)
-  if (g_dma_tables) {
-    PH2D(S.ls_order, S.h_ls_order, nj); PH2D(S.jobs, S.h_jobs_in, nj); PH2D(S.slot_prefix, S.h_slot_prefix, nj + MB); PH2D(S.vp_prefix, S.h_vp_prefix, nj + MB);
-    PH2D(S.yaw, S.h_yaw, n_yaw); PH2D(S.yaw_c, S.h_yaw_c, n_yaw); PH2D(S.yaw_s, S.h_yaw_s, n_yaw);
-    if (n_top) PH2D(S.top_x, S.h_top_x, n_top);
-    PH2D(S.box_job0, S.h_box_job0, nb); PH2D(S.box_njobs, S.h_box_njobs, nb);
-    PH2D(S.rp_tab_count, S.h_rp_tab_count, (size_t)NF * NT); PH2D(S.rp_maps, S.h_rp_maps, 3 * (size_t)MB * NF); PH2D(S.rp_raw_euler, S.h_rp_raw_euler, 3 * (size_t)NF);
-  } else {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
+  {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
     cs::CopySegs cp{};
-    SEG(S.ls_order, S.h_ls_order, nj); SEG(S.jobs, S.h_jobs_in, nj); SEG(S.slot_prefix, S.h_slot_prefix, nj + MB); SEG(S.vp_prefix, S.h_vp_prefix, nj + MB);
-    SEG(S.yaw, S.h_yaw, n_yaw); SEG(S.yaw_c, S.h_yaw_c, n_yaw); SEG(S.yaw_s, S.h_yaw_s, n_yaw); SEG(S.top_x, S.h_top_x, n_top);
-    SEG(S.box_job0, S.h_box_job0, nb); SEG(S.box_njobs, S.h_box_njobs, nb);
-    SEG(S.rp_tab_count, S.h_rp_tab_count, (size_t)NF * NT); SEG(S.rp_maps, S.h_rp_maps, 3 * (size_t)MB * NF); SEG(S.rp_raw_euler, S.h_rp_raw_euler, 3 * (size_t)NF);
+    cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, S.jobs, S.h_jobs_in, nj); cs::add_copy(cp, S.slot_prefix, S.h_slot_prefix, nj + MB);
+    cs::add_copy(cp, S.vp_prefix, S.h_vp_prefix, nj + MB); cs::add_copy(cp, S.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, S.yaw_c, S.h_yaw_c, n_yaw);
+    cs::add_copy(cp, S.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, S.top_x, S.h_top_x, n_top); cs::add_copy(cp, S.box_job0, S.h_box_job0, nb);
+    cs::add_copy(cp, S.box_njobs, S.h_box_njobs, nb); cs::add_copy(cp, S.rp_tab_count, S.h_rp_tab_count, (long long)NF * NT);
+    cs::add_copy(cp, S.rp_maps, S.h_rp_maps, 3LL * MB * NF); cs::add_copy(cp, S.rp_raw_euler, S.h_rp_raw_euler, 3LL * NF);
     cs::launch_multi_copy(cp, st);
   }
   HIP_TRY(hipMemsetAsync(S.job_valid.p, 0, sizeof(int) * nj, st));
   HIP_TRY(hipMemsetAsync(S.rp_cur_idx.p, 0, sizeof(int) * NF, st));
   HIP_TRY(hipEventRecord(S.ev[0], st));
   // ---- line setup of every job of the batch at once (it depends on the box and the frame's segments only)
-  static const bool ls_unlisted = getenv("CS_DETECT_LS_UNLISTED") != nullptr;
-  if (!ls_unlisted && d->stream3)
-    cs::launch_line_setup_listed(S.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
-                                 d->stream3, S.ev[0], S.ev[12], S.ls_crowded.p, d->stream4, S.ev[13]);
-  else
-    cs::launch_line_setup(S.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
-                          d->stream3, S.ev[0], S.ev[12]);
+  cs::launch_line_setup_listed(S.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
+                               d->stream3, S.ev[0], S.ev[12], S.ls_crowded.p);
   HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
   while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
@@ -1767,24 +1696,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(S.ev[6], st));
-  if (g_dma_tables) {
-    HIP_TRY(hipMemcpyAsync(S.h_records.p, S.records.p, sizeof(cs_cuboid) * nb * KMAX, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_win_count.p, S.win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_fallback.p, S.fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_job_cbase.p, S.job_cbase.p, sizeof(long long) * (nj + MB), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_job_valid.p, S.job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_jobs_out.p, S.jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_rp_last_slot.p, S.rp_last_slot.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_rp_box_base.p, S.rp_box_base.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(S.h_rp_pool_used.p, S.rp_pool_used.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  } else {
+  {
     cs::CopySegs cp{};
-    SEG(S.h_records, S.records, nb * KMAX); SEG(S.h_win_count, S.win_count, nb); SEG(S.h_fallback, S.fallback, nb); SEG(S.h_job_cbase, S.job_cbase, nj + MB);
-    SEG(S.h_job_valid, S.job_valid, nj); SEG(S.h_jobs_out, S.jobs, nj); SEG(S.h_rp_last_slot, S.rp_last_slot, nb); SEG(S.h_rp_box_base, S.rp_box_base, nb);
-    SEG(S.h_rp_pool_used, S.rp_pool_used, 1);
+    cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, S.h_win_count, S.win_count, nb); cs::add_copy(cp, S.h_fallback, S.fallback, nb);
+    cs::add_copy(cp, S.h_job_cbase, S.job_cbase, nj + MB); cs::add_copy(cp, S.h_job_valid, S.job_valid, nj); cs::add_copy(cp, S.h_jobs_out, S.jobs, nj);
+    cs::add_copy(cp, S.h_rp_last_slot, S.rp_last_slot, nb); cs::add_copy(cp, S.h_rp_box_base, S.rp_box_base, nb); cs::add_copy(cp, S.h_rp_pool_used, S.rp_pool_used, 1);
     cs::launch_multi_copy(cp, st);
   }
-#undef SEG
   HIP_TRY(hipEventRecord(S.done, st));
   S.in_flight = true;
   return CS_OK;
@@ -1831,21 +1749,11 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
 #define PENS(buf, n) do { rc = (buf).ensure(n); if (rc) return rc; } while (0)
     PENS(S.h_fb_dist, used + 1); PENS(S.h_fb_angle, used + 1); PENS(S.h_fb_skew, used + 1); PENS(S.h_fb_flag, used + 1); PENS(S.h_fb_slot, used + 1);
 #undef PENS
-    if (used && !g_dma_tables) {
+    if (used) {
       cs::CopySegs cp{};
-      const void* srcs[5] = {S.fb_dist.p, S.fb_angle.p, S.fb_skew.p, S.fb_flag.p, S.fb_slot.p};
-      void* dsts[5] = {S.h_fb_dist.p, S.h_fb_angle.p, S.h_fb_skew.p, S.h_fb_flag.p, S.h_fb_slot.p};
-      const unsigned long long widths[5] = {8, 8, 8, 4, 8};
-      for (int z = 0; z < 5; z++) { cp.s[z].src = srcs[z]; cp.s[z].dst = dsts[z]; cp.s[z].bytes = widths[z] * used; }
-      cp.n = 5;
+      cs::add_copy(cp, S.h_fb_dist, S.fb_dist, used); cs::add_copy(cp, S.h_fb_angle, S.fb_angle, used); cs::add_copy(cp, S.h_fb_skew, S.fb_skew, used);
+      cs::add_copy(cp, S.h_fb_flag, S.fb_flag, used); cs::add_copy(cp, S.h_fb_slot, S.fb_slot, used);
       cs::launch_multi_copy(cp, st2);
-      HIP_TRY(hipStreamSynchronize(st2));
-    } else if (used) {
-      HIP_TRY(hipMemcpyAsync(S.h_fb_dist.p, S.fb_dist.p, 8 * used, hipMemcpyDeviceToHost, st2));
-      HIP_TRY(hipMemcpyAsync(S.h_fb_angle.p, S.fb_angle.p, 8 * used, hipMemcpyDeviceToHost, st2));
-      HIP_TRY(hipMemcpyAsync(S.h_fb_skew.p, S.fb_skew.p, 8 * used, hipMemcpyDeviceToHost, st2));
-      HIP_TRY(hipMemcpyAsync(S.h_fb_flag.p, S.fb_flag.p, 4 * used, hipMemcpyDeviceToHost, st2));
-      HIP_TRY(hipMemcpyAsync(S.h_fb_slot.p, S.fb_slot.p, 8 * used, hipMemcpyDeviceToHost, st2));
       HIP_TRY(hipStreamSynchronize(st2));
     }
     const std::vector<std::vector<CamCache>>& cam_rp = *C.cam_rp_all;
@@ -1983,7 +1891,6 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   return CS_OK;
 }
 #undef PENS
-#undef PH2D
 
 }  // namespace
 
@@ -2145,8 +2052,7 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
   {
     int max_rp = 0;
     for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)cam_rp[f].size());
-    static const bool rp_rounds_forced = getenv("CS_DETECT_RP_ROUNDS") != nullptr;   // diagnostics: always the round-by-round path
-    if (sample_rp && !b->debug && !b->force_host_rank && !b->force_host_setup && !b->force_no_pipeline && !b->force_round_path && !rp_rounds_forced && b->device_setup &&
+    if (sample_rp && !b->debug && !b->force_host_rank && !b->force_host_setup && !b->force_no_pipeline && !b->force_round_path && b->device_setup &&
         KMAX <= cs::RANK_KMAX && MB > 0 && max_rp <= cs::vp3_table_doubles_per_job() / 2) {
       rs->C = PipeCtx{d, b, out, out_counts, &rs->cam_raw, &rs->rp_off, sp, &rs->tm, &rs->cam_rp};
       int rc = rp_launch(rs->C, b->pipe[0], rs->cam_rp);

@@ -1722,8 +1722,6 @@ __global__ __launch_bounds__(64) void line_setup_small_kernel(JobDesc* jobs, int
   if (lane == 0) jobs[j].m = kept;
 }
 
-// st_crowded (with the two events): the few crowded ROIs -- long, low-occupancy workgroups -- run on their own stream beside the
-// others; `fork` must already be recorded on st, `join` is recorded here and st waits for it.
 // diagnostics: CS_DETECT_SKIP=<names> leaves the named kernels out of the sweep, to measure their marginal cost in the saturated
 // pipeline (the results are then meaningless; never set outside a timing experiment)
 // Compiled in only with -DCS_DIAG (make DIAG=1): the shipped library has no switch that changes results, cs_diag_build() says which
@@ -1736,48 +1734,36 @@ static bool skip_kernel(const char* name) {
 #else
 static constexpr bool skip_kernel(const char*) { return false; }
 #endif
+// the round path's form: a workgroup of each instance per job, all on st
 void launch_line_setup(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join) {
+                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st) {
   if (skip_kernel("line_setup")) return;
   if (n_jobs <= 0) return;
   LineSetupParams lp{dist_thre, angle_thre_deg / 180.0 * CS_PI, len_thre, sqrt_lt_bound(dist_thre), sqrt_le_bound(len_thre)};
-  const bool beside = st_crowded && fork && join;
-  hipStream_t sc = beside ? st_crowded : st;
-  if (beside) (void)hipStreamWaitEvent(sc, fork, 0);
-  hipLaunchKernelGGL((line_setup_kernel<LS_CAP, LS_CROWDED_THREADS>), dim3(n_jobs), dim3(LS_CROWDED_THREADS), 0, sc, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, order);
-  if (beside) (void)hipEventRecord(join, sc);
-  hipLaunchKernelGGL(line_setup_small_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, order);
-  if (beside) (void)hipStreamWaitEvent(st, join, 0);
+  hipLaunchKernelGGL((line_setup_kernel<LS_CAP, LS_CROWDED_THREADS>), dim3(n_jobs), dim3(LS_CROWDED_THREADS), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, nullptr);
+  hipLaunchKernelGGL(line_setup_small_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, nullptr);
 }
-// the lean path's form: the crowded ROIs from line_classify_kernel's list (crowded: n_jobs + 1 ints of scratch), the others as above
+// the lean paths' form: the crowded ROIs from line_classify_kernel's list, the others in `order`.  crowded: 2 (n_jobs + 1) ints of scratch --
+// the list of the ROIs of up to LS_MID rows, behind it the list of the larger ones.  The crowded ROIs -- long, low-occupancy workgroups --
+// run on st_crowded beside the others, the mid-size instance behind the large one (on a stream of its own it cost 7 % of the sweep's
+// rate); `fork` and `join` are recorded here and st waits for `join`.
 void launch_line_setup_listed(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                              double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded,
-                              hipStream_t st_mid, hipEvent_t join_mid) {
+                              double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded) {
   if (skip_kernel("line_setup")) return;
   if (n_jobs <= 0) return;
   LineSetupParams lp{dist_thre, angle_thre_deg / 180.0 * CS_PI, len_thre, sqrt_lt_bound(dist_thre), sqrt_le_bound(len_thre)};
-  // crowded: 2 (n_jobs + 1) ints -- the list of the ROIs of up to LS_MID rows, behind it the list of the larger ones (one list when there is no second stream)
-  static const bool one_list = getenv("CS_DETECT_LS_ONE_LIST") != nullptr;
-  const bool two = st_mid && join_mid && !one_list;
-  int* big = two ? crowded + n_jobs + 1 : nullptr;
+  int* big = crowded + n_jobs + 1;
   (void)hipMemsetAsync(crowded, 0, sizeof(int), st);
-  if (two) (void)hipMemsetAsync(big, 0, sizeof(int), st);
+  (void)hipMemsetAsync(big, 0, sizeof(int), st);
   hipLaunchKernelGGL(line_classify_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, crowded, big);
   (void)hipEventRecord(fork, st);
   const int grid = n_jobs < 1024 ? n_jobs : 1024;      // (more crowded ROIs than workgroups: a workgroup takes several)
   (void)hipStreamWaitEvent(st_crowded, fork, 0);
-  hipLaunchKernelGGL((line_setup_listed_kernel<LS_CAP, LS_CROWDED_THREADS>), dim3(grid), dim3(LS_CROWDED_THREADS), 0, st_crowded, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, two ? big : crowded);
+  hipLaunchKernelGGL((line_setup_listed_kernel<LS_CAP, LS_CROWDED_THREADS>), dim3(grid), dim3(LS_CROWDED_THREADS), 0, st_crowded, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, big);
+  hipLaunchKernelGGL((line_setup_listed_kernel<LS_MID, LS_CROWDED_THREADS>), dim3(grid), dim3(LS_CROWDED_THREADS), 0, st_crowded, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, crowded);
   (void)hipEventRecord(join, st_crowded);
-  if (two) {
-    static const bool mid_own_stream = getenv("CS_DETECT_LS_MID_STREAM") != nullptr;
-    hipStream_t sm = mid_own_stream ? st_mid : st_crowded;       // (behind the large ROIs' instance on ITS stream: a fourth stream per detector cost 7 % of the sweep's rate)
-    if (mid_own_stream) (void)hipStreamWaitEvent(st_mid, fork, 0);
-    hipLaunchKernelGGL((line_setup_listed_kernel<LS_MID, LS_CROWDED_THREADS>), dim3(grid), dim3(LS_CROWDED_THREADS), 0, sm, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, crowded);
-    (void)hipEventRecord(join_mid, sm);
-  }
   hipLaunchKernelGGL(line_setup_small_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, order);
   (void)hipStreamWaitEvent(st, join, 0);
-  if (two) (void)hipStreamWaitEvent(st, join_mid, 0);
 }
 int line_setup_capacity() { return LS_CAP; }
 
@@ -1881,8 +1867,7 @@ void launch_vp_support(const DetectDeviceView& v, const SweepParams& sp, int vp_
 void launch_vp_support_only(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st, int rp_max) {
   if (skip_kernel("vp_support")) return;
   if (vp_total <= 0) return;
-  static const bool sparse = getenv("CS_DETECT_VP3_SPARSE") != nullptr;      // (VP3_RPCAP lanes per job whatever the jobs hold: the form until round 6's end -- A / B)
-  const int stride = (!sparse && rp_max >= 1 && rp_max <= (int)VP3_RPCAP) ? rp_max : (int)VP3_RPCAP;
+  const int stride = (rp_max >= 1 && rp_max <= (int)VP3_RPCAP) ? rp_max : (int)VP3_RPCAP;
   hipLaunchKernelGGL(vp3_support_kernel, dim3((unsigned)(((long long)v.n_jobs * stride + 63) / 64)), dim3(64), 0, st, v, sp, stride);
   vp_support_kernel<1><<<dim3(grid8(vp_total, 256)), dim3(256), 0, st>>>(v, sp, vp_total);
 }
