@@ -6,8 +6,8 @@ loading fails loudly when the HIP library has not been built (run __graft_entry_
 from __future__ import annotations
 
 import os as _os
-# (six streams per detector, one of them idle: with the ROCm runtime's default of four hardware queues they share queues and serialise -- INTEGRATION.md; only effective
-# when nothing has initialised HIP yet, and a value already in the environment wins)
+# (the library sizes its set of working streams by this value and gives every detector streams of its own for the three roles of a sweep when there are eight
+# queues or more -- INTEGRATION.md; only effective when nothing has initialised HIP yet, and a value already in the environment wins)
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import ctypes as C
 import os

@@ -4,9 +4,10 @@
 //   setup   (host, threaded)  per frame: camera cache (box_proposal_detail.cpp:45-56); per box and height sample: integer
 //                             box/ROI geometry (:143-256), yaw / top-edge / roll-pitch sample lists (:180-184, :212-219,
 //                             :344-355)  ->  JobDesc + pooled SoA arrays in pinned memory, one H2D copy;
-//   sweep   (HIP, 3 streams)  line setup (ROI filter + merge_break_lines) and VP support on one stream, vanishing points +
-//                             corner construction + ordered compaction on a second, the crowded ROIs' line setup on a
-//                             third; the scorer joins them (detect_kernels.hip);
+//   sweep   (HIP)             line setup (ROI filter + merge_break_lines) and VP support, vanishing points + corner
+//                             construction + ordered compaction, the crowded ROIs' line setup; the scorer joins them
+//                             (detect_kernels.hip).  On three streams of the process's stream set with eight hardware
+//                             queues or more, on one stream per detector with fewer (StreamSet below);
 //   rank    (HIP)             fuse_normalize_scores_v2 (object_3d_util.cpp:726-837) and the final skew-weighted ranking
 //                             (box_proposal_detail.cpp:766-838) on the compacted (dist, angle, skew) columns; only the
 //                             winners come back;
@@ -377,16 +378,124 @@ void fuse_scores(const double* dist, const double* angle, int n, double w_angle,
   }
 }
 
+// ---- the working streams of all detectors of a process on one device ---------------------------------------------------------
+// The ROCm runtime multiplexes a process's normal-priority streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless the environment
+// says otherwise) and a queue hands its packets out in order.  With six streams of their own per detector, WHICH roles of which detectors
+// shared a queue followed from the order the streams were created in (profiles/stream_queue_map_per_detector_streams_4_queues.txt: one
+// detector's chain had a queue to itself, the three others' chains shared one).  Now the library owns one set of streams per device,
+// sized by the queue count, and a detector borrows the streams of a SLOT of the set (the lowest free one; more detectors than slots
+// share slots):
+//   fewer than 8 queues   a slot is ONE stream and there are as many slots as queues: a batch's whole sweep -- tables, corner construction,
+//                         line setup, VP support, scorer, ranking, records, results -- runs on it in order, beside the other slots' sweeps.
+//                         Measured against every split by role that four queues allow: the device is kept busy by
+//                         the OTHER pipelines' kernels, and a role stream shared between pipelines makes a ready kernel wait behind one
+//                         whose inputs are not there yet.  A detector whose sweep finds the device to ITSELF (the usual integration, a
+//                         single-frame call: no other detector's kernels fill its batch's holes) runs the corner construction and the crowded
+//                         line setup on two of the idle slots' streams, as a batch alone wants them: decided per enqueue block by whether
+//                         another detector has a sweep in flight (sweep_side_streams).
+//   8 queues or more      the set holds no streams: every detector has streams of its OWN for the chain, the corner construction and the crowded
+//                         line setup, a fourth that runs nothing and a high-priority one, created in that order when the detector is -- with
+//                         queues to spare a batch's own roles side by side pay, and this is the form that was measured fastest there.  WHICH
+//                         streams then share a queue is the runtime's choice by creation order (the fourth stream is part of that order:
+//                         profiles/stream_queue_map_per_detector_streams_8_queues.txt -- four chains on queues of their own, a detector's
+//                         corner construction with its neighbour's crowded line setup).  Set-owned slots of three streams that land on the
+//                         queues in the same way were 5-9 % slower, so nothing is shared here and no lock is taken.
+// With fewer than 8 queues the tie boxes' fetches run on a high-priority stream per slot (the runtime keeps hardware queues per priority class: they take none
+// from the sweep, and a host thread that synchronises its slot's stream waits for its own slot's fetches only); an image-input batch's upload
+// stream has the lowest priority for the same reason and stays the batch's own.
+// Several host threads may enqueue into one stream: HIP's stream calls are thread safe, every call in an enqueue block is asynchronous,
+// and an event is waited for only after the call that recorded it has returned -- in the order the runtime saw the calls every operation
+// depends on earlier ones only, so no interleaving can deadlock and no detector ever waits for another one's host thread.  ONE lock,
+// `enqueue_mu`, is held around a batch's enqueue block (pipe_launch, rp_launch) all the same: the batch's launches then sit back to back
+// in a shared stream (no other batch's big kernel between two of its small ones, and the per-stage events of timing() bracket this batch's
+// kernels only).  Nothing that waits for the device or for another thread happens under it, no allocation, and no second lock is taken inside.
+struct StreamSet {
+  enum { MAX_SLOTS = 16 };
+  int device = 0, refs = 0, n_queues = 4, n_slots = 0;
+  std::atomic<int> busy{0};                        // sweeps queued and not yet collected, all detectors of the device (sweep_side_streams)
+  bool own_streams = false;                        // 8 queues or more: the detectors create their streams themselves
+  hipStream_t chain[MAX_SLOTS] = {};
+  int users[MAX_SLOTS] = {};
+  hipStream_t hi[MAX_SLOTS] = {};
+  std::mutex enqueue_mu;
+};
+std::mutex g_sets_mu;
+std::vector<StreamSet*> g_sets;      // one per device in use
+
+// What the runtime will use: read, never set.  The runtime latches the variable when HIP initialises; the set reads it when a device's first
+// detector is created and ASSUMES that nobody changed it in between (a host that sets it after its first HIP call gets a set sized for a
+// queue count the runtime does not have -- more streams than queues, which share queues as the runtime pleases).
+int hw_queue_count() {
+  const char* e = getenv("GPU_MAX_HW_QUEUES");
+  const int n = e ? atoi(e) : 4;
+  return n < 1 ? 4 : std::min(n, 32);
+}
+
+void stream_set_destroy(StreamSet* s) {
+  for (hipStream_t st : s->chain) if (st) (void)hipStreamDestroy(st);
+  for (hipStream_t st : s->hi) if (st) (void)hipStreamDestroy(st);
+  delete s;
+}
+
+// the device's set, created on first use (the caller has made `device` current); nullptr + *err on a HIP error
+StreamSet* stream_set_acquire(int device, hipError_t* err) {
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  *err = hipSuccess;
+  for (StreamSet* s : g_sets) if (s->device == device) { s->refs++; return s; }
+  StreamSet* s = new StreamSet();
+  s->device = device; s->n_queues = hw_queue_count();
+  s->own_streams = s->n_queues >= 8;
+  s->n_slots = s->own_streams ? 0 : s->n_queues;
+  for (int i = 0; i < s->n_slots && *err == hipSuccess; i++) *err = hipStreamCreateWithFlags(&s->chain[i], hipStreamNonBlocking);
+  if (*err == hipSuccess && s->n_slots > 0) {
+    int prio_low = 0, prio_high = 0;   // (numerically lowest = greatest priority)
+    *err = hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
+    for (int i = 0; i < s->n_slots && *err == hipSuccess; i++) *err = hipStreamCreateWithPriority(&s->hi[i], hipStreamNonBlocking, prio_high);
+  }
+  if (*err != hipSuccess) { stream_set_destroy(s); return nullptr; }
+  s->refs = 1;
+  g_sets.push_back(s);
+  return s;
+}
+
+// a new detector's slot: the one the fewest live detectors hold (the lowest of them); out: chain, corner construction, crowded line setup, tie fetches
+// (not with own_streams: -1, nothing borrowed)
+int stream_set_borrow(StreamSet* s, hipStream_t out[4]) {
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  if (s->own_streams) return -1;
+  int i = 0;
+  for (int k = 1; k < s->n_slots; k++) if (s->users[k] < s->users[i]) i = k;
+  s->users[i]++;
+  out[0] = s->chain[i];
+  out[1] = out[0];
+  out[2] = out[0];
+  out[3] = s->hi[i];
+  return i;
+}
+
+// the detector's slot goes back; the last detector of a device takes the set with it (its streams are idle: a detector is destroyed after its batches)
+void stream_set_release(StreamSet* s, int slot) {
+  std::lock_guard<std::mutex> lk(g_sets_mu);
+  if (slot >= 0 && slot < s->n_slots) s->users[slot]--;
+  if (--s->refs > 0) return;
+  g_sets.erase(std::find(g_sets.begin(), g_sets.end(), s));
+  stream_set_destroy(s);
+}
+
 }  // namespace
 
 // ================================================================== handles ======================
 struct cs_detector {
   cs_detect_params prm;
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;   // tie-break re-ranking fetches of the previous chunk, concurrent with the next chunk's sweep
-  hipStream_t stream3 = nullptr;   // line setup of the crowded ROIs, beside the line setup of all the others
-  hipStream_t stream4 = nullptr;   // runs nothing: streams take hardware queues in creation order, and without it the contract run was 4 % slower (450-470 k against 478-489 k frames/s)
+  // borrowed from the device's StreamSet (above), shared with the other detectors of the process
+  StreamSet* streams = nullptr;
+  int stream_slot = -1;
+  std::atomic<int> busy{0};        // this detector's sweeps queued and not yet COLLECTED by the host (not: still on the device -- a finished sweep counts until cs_batch_collect)
+  hipStream_t stream_idle = nullptr;   // own_streams only: runs nothing, holds the fourth place in the order the runtime assigns queues by
+  hipStream_t stream = nullptr;    // a batch's chain (and everything outside the sweep: front end, segment producers, the round path)
+  hipStream_t stream2 = nullptr;   // vanishing points + corner construction: beside the line setup, or -- few queues -- the chain's stream
+  hipStream_t stream3 = nullptr;   // line setup of the crowded ROIs: beside the line setup of all the others, or the chain's stream
   hipStream_t stream_hi = nullptr; // high priority: the small fetches of the tie boxes, which the host waits for while another batch's sweep owns the device
   hipEvent_t ev[12] = {};
   int n_threads = 1;
@@ -403,6 +512,19 @@ struct cs_detector {
   void (*lsd_free)(void*) = nullptr;
   std::mutex lines_mu;
 };
+
+// The side streams of one enqueue block (call it under enqueue_mu): the detector's own; or, with one stream per slot and no OTHER detector's
+// sweep in flight on the device, the streams of two other slots -- nobody else's kernels fill this batch's holes, so it runs corner
+// construction, crowded line setup and chain side by side on three queues.  Batches own their buffers and events, so another detector's
+// sweep that arrives while such a batch is in flight changes nothing for it.
+static void sweep_side_streams(const cs_detector* d, hipStream_t* corners, hipStream_t* crowded) {
+  const StreamSet* s = d->streams;
+  *corners = d->stream2; *crowded = d->stream3;
+  if (!s->own_streams && s->n_slots >= 3 && s->busy.load() == d->busy.load()) {
+    *corners = s->chain[(d->stream_slot + 1) % s->n_slots];
+    *crowded = s->chain[(d->stream_slot + 2) % s->n_slots];
+  }
+}
 
 struct FrameIn {
   double K[9], invK[9], R[9], t[3];
@@ -484,6 +606,7 @@ struct PipeSlot {
   size_t nj = 0, nb = 0;
   long long slot_total = 0;
   bool in_flight = false;
+  bool counted_busy = false;      // this sweep is in the detector's and the stream set's `busy` counts
   void release() {
     jobs.release(); slot_prefix.release(); job_cbase.release(); c_slot.release(); fb_slot.release();
     vp_prefix.release(); top_x.release(); flag.release(); job_valid.release(); c_flag.release(); box_job0.release(); box_njobs.release(); win_count.release();
@@ -669,14 +792,23 @@ int cs_detector_create(const cs_detect_params* params, int device, cs_detector**
   if (d->prm.max_cuboid_num < 1 || !(d->prm.yaw_step_deg > 0) || !(d->prm.yaw_range_deg >= 0)) { set_err("bad params"); return CS_ERR_INVALID_ARG; }
   d->device = device;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&d->stream3, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&d->stream4, hipStreamNonBlocking));
   {
-    int prio_low = 0, prio_high = 0;   // (numerically lowest = greatest priority)
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-    HIP_TRY(hipStreamCreateWithPriority(&d->stream_hi, hipStreamNonBlocking, prio_high));
+    hipError_t se = hipSuccess;
+    d->streams = stream_set_acquire(device, &se);
+    HIP_TRY(se);
+    if (d->streams->own_streams) {
+      HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+      HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
+      HIP_TRY(hipStreamCreateWithFlags(&d->stream3, hipStreamNonBlocking));
+      HIP_TRY(hipStreamCreateWithFlags(&d->stream_idle, hipStreamNonBlocking));
+      int prio_low = 0, prio_high = 0;   // (numerically lowest = greatest priority)
+      HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+      HIP_TRY(hipStreamCreateWithPriority(&d->stream_hi, hipStreamNonBlocking, prio_high));
+    } else {
+      hipStream_t st4[4];
+      d->stream_slot = stream_set_borrow(d->streams, st4);
+      d->stream = st4[0]; d->stream2 = st4[1]; d->stream3 = st4[2]; d->stream_hi = st4[3];
+    }
   }
   for (auto& e : d->ev) HIP_TRY(hipEventCreate(&e));
   int hc = (int)std::thread::hardware_concurrency();
@@ -708,11 +840,13 @@ void cs_detector_destroy(cs_detector* d) {
   if (d->lines_scratch && d->lines_free) { d->lines_free(d->lines_scratch); d->lines_scratch = nullptr; }
   if (d->lsd_scratch && d->lsd_free) { d->lsd_free(d->lsd_scratch); d->lsd_scratch = nullptr; }
   for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
-  if (d->stream2) (void)hipStreamDestroy(d->stream2);
-  if (d->stream3) (void)hipStreamDestroy(d->stream3);
-  if (d->stream4) (void)hipStreamDestroy(d->stream4);
-  if (d->stream_hi) (void)hipStreamDestroy(d->stream_hi);
+  if (d->streams) {
+    // (the streams are shared: what this detector queued outside a batch -- a front end, a segment producer's tail -- is waited for here)
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    if (d->streams->own_streams)
+      for (hipStream_t st : {d->stream, d->stream2, d->stream3, d->stream_idle, d->stream_hi}) if (st) (void)hipStreamDestroy(st);
+    stream_set_release(d->streams, d->stream_slot);
+  }
   delete d;
 }
 
@@ -982,6 +1116,7 @@ void cs_batch_destroy(cs_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->det->device);
   if (b->run_state) { (void)hipDeviceSynchronize(); batch_drop_run_state(b); }   // a submitted sweep that was never collected
+  for (PipeSlot& S : b->pipe) if (S.counted_busy) { S.counted_busy = false; b->det->busy.fetch_sub(1); b->det->streams->busy.fetch_sub(1); }
   release_batch_buffers(b);
   delete b;
 }
@@ -1227,6 +1362,9 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   double *p_yaw = S.yaw.p, *p_yaw_c = S.yaw_c.p, *p_yaw_s = S.yaw_s.p;
   int *p_top_x = S.top_x.p, *p_box_job0 = S.box_job0.p, *p_box_njobs = S.box_njobs.p;
   cs_cuboid* p_records = S.records.p; int *p_win_count = S.win_count.p, *p_fallback = S.fallback.p, *p_job_valid = S.job_valid.p; long long* p_job_cbase = S.job_cbase.p;
+  // from the first launch to the `done` record: this batch's launches, back to back in the shared streams (StreamSet::enqueue_mu; asynchronous
+  // calls only)
+  std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);
   S.merged_io = nj <= 256;
   if (S.merged_io) {
     // layout: [inputs | the job table (in and out) | outputs] -- one copy up ([0, end of the job table)), one copy back (from the job table on)
@@ -1244,6 +1382,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     if (n_yaw) { memcpy(hb + o_y, S.h_yaw.p, 8 * n_yaw); memcpy(hb + o_yc, S.h_yaw_c.p, 8 * n_yaw); memcpy(hb + o_ys, S.h_yaw_s.p, 8 * n_yaw); }
     if (n_top) memcpy(hb + o_tx, S.h_top_x.p, sizeof(int) * n_top);
     if (nb) { memcpy(hb + o_b0, S.h_box_job0.p, sizeof(int) * nb); memcpy(hb + o_bn, S.h_box_njobs.p, sizeof(int) * nb); }
+    if (!d->streams->own_streams) enqueue.lock();
     HIP_TRY(hipMemcpyAsync(db, hb, in_end, hipMemcpyHostToDevice, st));
     p_ls_order = reinterpret_cast<int*>(db + o_ls); p_jobs = reinterpret_cast<cs::JobDesc*>(db + o_jobs); p_slot_prefix = reinterpret_cast<long long*>(db + o_sp);
     p_vp_prefix = reinterpret_cast<int*>(db + o_vp); p_yaw = reinterpret_cast<double*>(db + o_y); p_yaw_c = reinterpret_cast<double*>(db + o_yc); p_yaw_s = reinterpret_cast<double*>(db + o_ys);
@@ -1257,6 +1396,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     cs::add_copy(cp, S.vp_prefix, S.h_vp_prefix, nj + 1); cs::add_copy(cp, S.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, S.yaw_c, S.h_yaw_c, n_yaw);
     cs::add_copy(cp, S.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, S.top_x, S.h_top_x, n_top); cs::add_copy(cp, S.box_job0, S.h_box_job0, nb);
     cs::add_copy(cp, S.box_njobs, S.h_box_njobs, nb);
+    if (!d->streams->own_streams) enqueue.lock();
     cs::launch_multi_copy(cp, st);
   }
   cs::DetectDeviceView& v = S.view;
@@ -1265,11 +1405,15 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   v.mid_x = S.mid_x.p; v.mid_y = S.mid_y.p; v.line_angle = S.ang.p; v.yaw = p_yaw; v.yaw_cos = p_yaw_c; v.yaw_sin = p_yaw_s; v.top_x = p_top_x;
   v.rp = b->d_rp.p; v.invK = b->d_invK.p; v.vp = S.vp.p; v.bound = S.bound.p; v.bound3 = S.bound3.p; v.job_valid = p_job_valid;
   v.job_cbase = p_job_cbase; v.c_slot = S.c_slot.p; v.c_flag = S.c_flag.p; v.c_dist = S.c_dist.p; v.c_angle = S.c_angle.p; v.c_skew = S.c_skew.p;
-  // The corner construction needs the vanishing points but not the segments: it runs on the second stream beside line
+  // The corner construction needs the vanishing points but not the segments: it runs on the second stream (where this block has one:
+  // otherwise stB == st and the cross-stream waits are not enqueued) beside line
   // setup + VP support (a latency-bound and an ALU-bound kernel), and the scorer waits for both.
-  hipStream_t stB = d->stream2;
-  HIP_TRY(hipEventRecord(S.ev[7], st));                      // inputs resident
-  HIP_TRY(hipStreamWaitEvent(stB, S.ev[7], 0));
+  hipStream_t stB = nullptr, stC = nullptr;
+  sweep_side_streams(d, &stB, &stC);
+  if (stB != st) {
+    HIP_TRY(hipEventRecord(S.ev[7], st));                      // inputs resident
+    HIP_TRY(hipStreamWaitEvent(stB, S.ev[7], 0));
+  }
   HIP_TRY(hipEventRecord(S.ev[8], stB));
   // vanishing points, corner construction and ordered compaction of a job in one workgroup (candidate_compact_kernel); the compacted rows
   // of job j start at slot_prefix[j]: no scan over all jobs between this kernel and the scorer
@@ -1280,11 +1424,11 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   HIP_TRY(hipEventRecord(S.ev[10], stB));
   HIP_TRY(hipEventRecord(S.ev[0], st));
   cs::launch_line_setup_listed(p_jobs, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
-                               d->stream3, S.ev[0], S.ev[12], S.ls_crowded.p);
+                               stC, S.ev[0], S.ev[12], S.ls_crowded.p);
   HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::launch_vp_support_only(v, C.sp, S.vp_total, st, 1);      // (this path's jobs have one roll/pitch sample: jd.RP = 1 above)
   HIP_TRY(hipEventRecord(S.ev[2], st));
-  HIP_TRY(hipStreamWaitEvent(st, S.ev[10], 0));
+  if (stB != st) HIP_TRY(hipStreamWaitEvent(st, S.ev[10], 0));
   HIP_TRY(hipEventRecord(S.ev[4], st));
   cs::launch_score(v, C.sp, slot_total, slot_total, st);
   HIP_TRY(hipEventRecord(S.ev[5], st));
@@ -1305,6 +1449,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   }
   HIP_TRY(hipEventRecord(S.done, st));
   S.in_flight = true;
+  S.counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
   MARK(3, tq);   // allocations + enqueue of copies and kernels
   return CS_OK;
 }
@@ -1315,6 +1460,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
   cs_detect_timing& tm = *C.tm;
   double tw = now_ms(), tq = tw;
+  if (S.counted_busy) { S.counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); }      // (before the wait: an error return must not leave the counts up)
   HIP_TRY(hipEventSynchronize(S.done));
   tm.d2h_ms += now_ms() - tw;   // time the host actually waited for the GPU
   S.in_flight = false;
@@ -1630,8 +1776,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   PENS(S.fb_dist, (size_t)S.rp_pool_cap + 1); PENS(S.fb_angle, (size_t)S.rp_pool_cap + 1); PENS(S.fb_skew, (size_t)S.rp_pool_cap + 1); PENS(S.fb_flag, (size_t)S.rp_pool_cap + 1); PENS(S.fb_slot, (size_t)S.rp_pool_cap + 1);
   PENS(S.ls_crowded, 2 * (nj + 1) + 2);
   PENS(S.rp_box_base, nb + 1); PENS(S.rp_pool_used, 1); PENS(S.h_rp_box_base, nb + 1); PENS(S.h_rp_pool_used, 1); PENS(S.h_rp_last_slot, nb + 1); PENS(S.h_job_valid, nj + 1); PENS(S.h_jobs_out, nj + 1);
-  HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
   PENS(S.rp_cur_idx, (size_t)NF + 1); PENS(S.rp_tab_count, (size_t)NF * NT + 1); PENS(S.rp_maps, 3 * (size_t)MB * NF + 1); PENS(S.rp_raw_euler, 3 * (size_t)NF + 1);
+  while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
+  std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);      // all rounds of this batch back to back in the shared streams (see pipe_launch)
+  if (!d->streams->own_streams) enqueue.lock();
+  hipStream_t stB_unused = nullptr, stC = nullptr;
+  sweep_side_streams(d, &stB_unused, &stC);
+  HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
   {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
     cs::CopySegs cp{};
     cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, S.jobs, S.h_jobs_in, nj); cs::add_copy(cp, S.slot_prefix, S.h_slot_prefix, nj + MB);
@@ -1646,10 +1797,9 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   HIP_TRY(hipEventRecord(S.ev[0], st));
   // ---- line setup of every job of the batch at once (it depends on the box and the frame's segments only)
   cs::launch_line_setup_listed(S.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
-                               d->stream3, S.ev[0], S.ev[12], S.ls_crowded.p);
+                               stC, S.ev[0], S.ev[12], S.ls_crowded.p);
   HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
-  while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
   for (int r = 0; r < MB; r++) {
     const PipeSlot::RpRound& Rr = S.rp_rounds[r];
     if (Rr.nj == 0) continue;
@@ -1705,6 +1855,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   }
   HIP_TRY(hipEventRecord(S.done, st));
   S.in_flight = true;
+  S.counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
   return CS_OK;
 }
 
@@ -1714,6 +1865,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   const int KMAX = P.max_cuboid_num, MB = b->max_boxes, NF = b->n_frames;
   cs_detect_timing& tm = *C.tm;
   double tw = now_ms();
+  if (S.counted_busy) { S.counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); }      // (before the wait: an error return must not leave the counts up)
   HIP_TRY(hipEventSynchronize(S.done));
   tm.d2h_ms += now_ms() - tw;
   S.in_flight = false;

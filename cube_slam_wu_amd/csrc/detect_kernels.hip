@@ -1758,12 +1758,12 @@ void launch_line_setup_listed(JobDesc* jobs, int n_jobs, const double* frame_lin
   hipLaunchKernelGGL(line_classify_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, crowded, big);
   (void)hipEventRecord(fork, st);
   const int grid = n_jobs < 1024 ? n_jobs : 1024;      // (more crowded ROIs than workgroups: a workgroup takes several)
-  (void)hipStreamWaitEvent(st_crowded, fork, 0);
+  if (st_crowded != st) (void)hipStreamWaitEvent(st_crowded, fork, 0);      // (one stream for both: stream order)
   hipLaunchKernelGGL((line_setup_listed_kernel<LS_CAP, LS_CROWDED_THREADS>), dim3(grid), dim3(LS_CROWDED_THREADS), 0, st_crowded, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, big);
   hipLaunchKernelGGL((line_setup_listed_kernel<LS_MID, LS_CROWDED_THREADS>), dim3(grid), dim3(LS_CROWDED_THREADS), 0, st_crowded, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, crowded);
   (void)hipEventRecord(join, st_crowded);
   hipLaunchKernelGGL(line_setup_small_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, n_jobs, frame_lines, frame_line_ptr, mid_x, mid_y, line_angle, lp, order);
-  (void)hipStreamWaitEvent(st, join, 0);
+  if (st_crowded != st) (void)hipStreamWaitEvent(st, join, 0);
 }
 int line_setup_capacity() { return LS_CAP; }
 
