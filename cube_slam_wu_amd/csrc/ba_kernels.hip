@@ -407,7 +407,7 @@ __global__ __launch_bounds__(128, 3) void ba_cub_edge_kernel(BaView v, int odom_
     // Two phases.  (1) The unperturbed error: min_log_error's four yaw candidates on four lanes (h = 0 .. 3) instead of a loop on one;
     // the norms meet through lane exchanges, the winner by the reference's rule (first minimum, strict <; g2o_Object.h:76-114).
     // (2) The 30 perturbed evaluations: a 1e-9 step moves a candidate's norm by ~1e-7 at most, so where the winner leads the runner-up
-    // by more than 1e-3 (1 + norm) every perturbed evaluation has the same winner and computes THAT candidate only -- the same
+    // by more than CUBE_CLEAR_LEAD (1e-3) (1 + norm) every perturbed evaluation has the same winner and computes THAT candidate only -- the same
     // instructions on the same operands as the loop would run for it, hence the same bits; otherwise (a near tie: yaw near 45 degrees
     // off with a square footprint) the full loop.  Two candidate evaluations per wavefront instead of four: 135 -> ~80 us at C4.
     Cube esti0;
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(128, 3) void ba_cub_edge_kernel(BaView v, int odom_
     for (int i = 1; i < 4; i++) if (n4[i] < best_n) { best_n = n4[i]; win = i; }
     bool clear = best_n == best_n;               // (a NaN leader: the loop decides)
 #pragma unroll
-    for (int i = 0; i < 4; i++) if (i != win && !(n4[i] - best_n > 1e-3 * (1.0 + best_n))) clear = false;
+    for (int i = 0; i < 4; i++) if (i != win && !(n4[i] - best_n > CUBE_CLEAR_LEAD * (1.0 + best_n))) clear = false;
     // the unperturbed error: the winner's, fetched from the lane that holds it (every lane takes part in the exchange: an inactive
     // source lane would read as zero)
 #pragma unroll

@@ -217,6 +217,9 @@ CS_HD void cube_min_log_error(const Cube& self, const Cube& other, double* res) 
     }
   }
 }
+// The lead (over the runner-up's norm, relative to 1 + the winner's norm) above which ba_cub_edge_kernel's perturbed evaluations compute the
+// unperturbed winner only; at or below it they run the full four-candidate loop.  tests/edge_blocks_ref.py reads the value from this line.
+constexpr double CUBE_CLEAR_LEAD = 1e-3;
 // one candidate of min_log_error: the error against `other` turned by yaw (i - 1) pi / 2, and its norm -- the loop body above, for callers
 // that know which candidate wins (ba_cub_edge_kernel: the perturbed evaluations of a numeric Jacobian take the unperturbed winner when
 // its lead over the runner-up is a hundred thousand times what a 1e-9 step can move a norm)

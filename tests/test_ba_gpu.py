@@ -5,6 +5,8 @@ g2o's edge-order accumulation) and sin/cos/acos/tan come from ocml vs glibc, so 
 BASELINE.json states: states within 1e-5 relative after the same number of LM iterations, with the same
 accept/reject sequence.  Intermediate quantities are held to tighter bounds where they are analytic
 (1e-9 relative to the matrix scale) and to 1e-5 where they go through 1e-9-step numeric Jacobians.
+Those 1e-5 bounds are whole-matrix bounds (relative to the largest entry of H_pp); the numeric-Jacobian edges' blocks are held per block,
+relative to the block itself, by tests/test_ba_edge_blocks_gpu.py against an exact-quotient fixture.
 """
 import os
 
