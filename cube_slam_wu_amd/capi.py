@@ -849,3 +849,83 @@ def cam_rank(cam, n_cams, n_ranks):
 def shard_frames(n_frames, rank, world):
     """Path A multi-GPU: frames are independent units, dealt round-robin; returns this rank's frame indices."""
     return list(range(int(rank), int(n_frames), int(world)))
+
+
+# ------------------------------------------------------------------ motion-only pose optimisation, batched ----------
+class CsPoseParams(C.Structure):
+    _fields_ = [("n_rounds", C.c_int), ("iterations", C.c_int * 8), ("robust_rounds", C.c_int), ("restart_each_round", C.c_int),
+                ("huber_mono", C.c_double), ("huber_stereo", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double)]
+
+
+DECLARED_SYMBOLS += ["cs_pose_default_params", "cs_pose_optimize_batch", "cs_pose_batch_create", "cs_pose_batch_destroy", "cs_pose_batch_optimize", "cs_pose_batch_last_timing"]
+
+
+def pose_default_params(**kw):
+    """cs_pose_default_params with overrides; `iterations` takes a list of n_rounds counts."""
+    p = CsPoseParams()
+    lib().cs_pose_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k == "iterations":
+            for r, n in enumerate(v):
+                p.iterations[r] = int(n)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _pose_call(fn, head, batch, params):
+    """Marshals a batch dict (synth_pose.synth_pose_batch layout: Tcw, intr, obs_ptr, Xw, meas, info, is_stereo) into one C call."""
+    p = params if params is not None else pose_default_params()
+    T = _f64(batch["Tcw"], (-1, 7)); n = len(T)
+    intr, ptr = _f64(batch["intr"], (n, 5)), _i32(batch["obs_ptr"])
+    if len(ptr) != n + 1:
+        raise ValueError("obs_ptr must hold n_frames + 1 entries")
+    N = int(ptr[-1]) if n else 0
+    X, m, W = _f64(batch["Xw"], (N, 3)), _f64(batch["meas"], (N, 3)), _f64(batch["info"], (N, 9))
+    st = np.ascontiguousarray(np.asarray(batch["is_stereo"]).ravel().astype(np.uint8))
+    if len(st) != N:
+        raise ValueError("is_stereo must hold one entry per observation")
+    T_out, inl = np.zeros((n, 7)), np.zeros(N, np.uint8)
+    chi2, iters = np.zeros((n, p.n_rounds)), np.zeros((n, p.n_rounds), np.int32)
+    ub = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte))
+    rc = fn(*head, C.byref(p), n, _dp(T), _dp(intr), _ip(ptr), _dp(X), _dp(m), _dp(W), ub(st), _dp(T_out), ub(inl), _dp(chi2), _ip(iters))
+    return rc, dict(Tcw=T_out, inlier=inl, chi2=chi2, iterations=iters)
+
+
+class PoseBatch:
+    """cs_pose_batch handle: keeps its stream and device buffers between optimize() calls."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _chk(lib().cs_pose_batch_create(int(device), C.byref(self.h)), "cs_pose_batch_create")
+
+    def optimize(self, batch, params=None):
+        """-> dict: Tcw (n, 7), inlier (N, uint8), chi2 and iterations (n, n_rounds)."""
+        rc, out = _pose_call(lib().cs_pose_batch_optimize, (self.h,), batch, params)
+        _chk(rc, "cs_pose_batch_optimize")
+        return out
+
+    def timing(self):
+        k, h = C.c_double(), C.c_double()
+        _chk(lib().cs_pose_batch_last_timing(self.h, C.byref(k), C.byref(h)), "cs_pose_batch_last_timing")
+        return {"kernel_ms": k.value, "host_ms": h.value}
+
+    def close(self):
+        if self.h:
+            lib().cs_pose_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pose_optimize_batch(batch, params=None, device=0):
+    """cs_pose_optimize_batch: the one-shot form."""
+    rc, out = _pose_call(lib().cs_pose_optimize_batch, (int(device),), batch, params)
+    _chk(rc, "cs_pose_optimize_batch")
+    return out

@@ -1,0 +1,319 @@
+// pose_kernels.hip -- motion-only pose optimisation, many frames per launch (include/cubeslam_hip.h: cs_pose_*).
+//
+// One frame is a g2o graph of ONE free VertexSE3Expmap and the frame's unary edges
+//   EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose   object_slam/Thirdparty/g2o/g2o/types/types_six_dof_expmap.h:208-267
+//   computeError / cam_project / linearizeOplus                   types/types_six_dof_expmap.cpp:311-408
+//   constructQuadraticForm (rho' weights Omega and -Omega e)      core/base_unary_edge.hpp:42-72
+//   RobustKernelHuber with its single-precision delta^2           cs_robust.h
+//   VertexSE3Expmap::oplusImpl (exp(update) * estimate)           types_six_dof_expmap.h:73-76, cs_se3.h
+// driven round by round through SparseOptimizer::optimize (core/sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg
+// (core/optimization_algorithm_levenberg.cpp:61-189); the 6 x 6 system goes through an LDL^T without pivoting whose "all pivots positive"
+// test is LinearSolverDense's isPositive() (solvers/linear_solver_dense.h:104-111).
+//
+// Shape: one wavefront per frame, the whole optimisation -- every round, iteration and trial -- inside one launch.  Lane l owns the frame's
+// observations l, l + 64, ...: it keeps their share of the 21 upper entries of H, of b and of chi2 in registers; the 64 shares are summed
+// by a butterfly over the lanes (lane ^ 32, ^ 16, ... ^ 1: a fixed order, and -- both partners add the same two numbers -- the same bits in
+// every lane).  Every lane therefore holds the same H and b, and every lane runs the 6 x 6 factorisation on them: on a SIMD machine that
+// costs what one lane costs, and the increment needs no broadcast.  All LM scalars are wave-uniform, so the control flow never diverges.
+// A frame's result depends on its own data only: the same bits at any position in any batch.  FP64, -ffp-contract=off.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+
+#include "cs_robust.h"
+#include "pose_types.h"
+
+namespace cs {
+namespace {
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+struct Obs {
+  double X[3], m[3], W[9];
+  bool stereo;
+};
+
+__device__ __forceinline__ Obs obs_load(const double* __restrict__ rec) {
+  // 128 bytes, 16-byte aligned (the host packs the records behind a 256-byte aligned base)
+  const double2* p = reinterpret_cast<const double2*>(rec);
+  double v[POSE_OBS_DOUBLES];
+#pragma unroll
+  for (int k = 0; k < POSE_OBS_DOUBLES / 2; k++) { const double2 t = p[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
+  Obs o;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { o.X[k] = v[k]; o.m[k] = v[3 + k]; }
+#pragma unroll
+  for (int k = 0; k < 9; k++) o.W[k] = v[6 + k];
+  o.stereo = v[15] != 0.0;
+  return o;
+}
+
+// computeError of the two edges (types_six_dof_expmap.h:218-222, :249-253) with their cam_project (.cpp:335-351).  The stereo edge's
+// cam_project holds 1 / z in a `const float` (.cpp:345; the division itself is a double one, its operand being a double); its bf is the
+// double member.  A mono edge's third component is 0.
+__device__ __forceinline__ void obs_error(const Pose& T, const double* intr, const Obs& o, double* e, double* pc) {
+  pose_map(T, o.X, pc);
+  if (o.stereo) {
+    const double invz = (double)(float)(1.0 / pc[2]);
+    const double u = pc[0] * invz * intr[0] + intr[2];
+    e[0] = o.m[0] - u;
+    e[1] = o.m[1] - (pc[1] * invz * intr[1] + intr[3]);
+    e[2] = o.m[2] - (u - intr[4] * invz);
+  } else {
+    e[0] = o.m[0] - (pc[0] / pc[2] * intr[0] + intr[2]);      // project2d, then * fx + cx
+    e[1] = o.m[1] - (pc[1] / pc[2] * intr[1] + intr[3]);
+    e[2] = 0.0;
+  }
+}
+
+// e^T Omega e (BaseEdge::chi2) and Omega e
+__device__ __forceinline__ double obs_chi2(const Obs& o, const double* e, double* We) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) We[i] = (o.W[3 * i] * e[0] + o.W[3 * i + 1] * e[1]) + o.W[3 * i + 2] * e[2];
+  return (e[0] * We[0] + e[1] * We[1]) + e[2] * We[2];
+}
+
+struct Frame {
+  const double* obs;            // the frame's first record
+  unsigned char* level;         // 1 = level 0 (optimised), 0 = level 1 (left out), per observation of the frame
+  int n;
+  double intr[5];
+  double huber_mono, huber_stereo;
+};
+
+// activeRobustChi2 at pose T over the frame's level-0 observations (sparse_optimizer.cpp:100-114)
+__device__ __forceinline__ double frame_chi2(const Frame& F, const Pose& T, bool robust, int lane) {
+  double acc = 0.0;
+  for (int i = lane; i < F.n; i += 64) {
+    if (!F.level[i]) continue;
+    const Obs o = obs_load(F.obs + (size_t)i * POSE_OBS_DOUBLES);
+    double e[3], pc[3], We[3];
+    obs_error(T, F.intr, o, e, pc);
+    const double c = obs_chi2(o, e, We);
+    double r0, r1;
+    huber_rho(c, robust ? (o.stereo ? F.huber_stereo : F.huber_mono) : 0.0, r0, r1);
+    acc += r0;
+  }
+  return wave_sum(acc);
+}
+
+// computeActiveErrors + linearizeOplus + constructQuadraticForm of every level-0 edge: H (21 upper entries, row by row), b, chi2
+__device__ __forceinline__ void frame_linearize(const Frame& F, const Pose& T, bool robust, int lane, double* H, double* b, double& chi) {
+  double h[21], g[6], acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < 21; k++) h[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) g[k] = 0.0;
+  for (int i = lane; i < F.n; i += 64) {
+    if (!F.level[i]) continue;
+    const Obs o = obs_load(F.obs + (size_t)i * POSE_OBS_DOUBLES);
+    double e[3], pc[3], We[3];
+    obs_error(T, F.intr, o, e, pc);
+    const double c = obs_chi2(o, e, We);
+    double r0, r1;
+    huber_rho(c, robust ? (o.stereo ? F.huber_stereo : F.huber_mono) : 0.0, r0, r1);
+    acc += r0;
+    // linearizeOplus (.cpp:311-333, :380-409)
+    const double fx = F.intr[0], fy = F.intr[1], bf = F.intr[4];
+    const double x = pc[0], y = pc[1], invz = 1.0 / pc[2], invz_2 = invz * invz;
+    double J[18];
+    J[0] = x * y * invz_2 * fx;
+    J[1] = -(1 + (x * x * invz_2)) * fx;
+    J[2] = y * invz * fx;
+    J[3] = -invz * fx;
+    J[4] = 0;
+    J[5] = x * invz_2 * fx;
+    J[6] = (1 + y * y * invz_2) * fy;
+    J[7] = -x * y * invz_2 * fy;
+    J[8] = -x * invz * fy;
+    J[9] = 0;
+    J[10] = -invz * fy;
+    J[11] = y * invz_2 * fy;
+    if (o.stereo) {
+      J[12] = J[0] - bf * y * invz_2;
+      J[13] = J[1] + bf * x * invz_2;
+      J[14] = J[2];
+      J[15] = J[3];
+      J[16] = 0;
+      J[17] = J[5] - bf * invz_2;
+    } else {
+#pragma unroll
+      for (int k = 12; k < 18; k++) J[k] = 0.0;
+    }
+    // b -= rho' A^T Omega e;  A += A^T (rho' Omega) A   (base_unary_edge.hpp:56-66; without a kernel rho' = 1)
+    double WJ[18];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int a = 0; a < 6; a++) WJ[6 * r + a] = r1 * ((o.W[3 * r] * J[a] + o.W[3 * r + 1] * J[6 + a]) + o.W[3 * r + 2] * J[12 + a]);
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      g[a] -= r1 * ((J[a] * We[0] + J[6 + a] * We[1]) + J[12 + a] * We[2]);
+#pragma unroll
+      for (int c2 = a; c2 < 6; c2++, k++) h[k] += (J[a] * WJ[c2] + J[6 + a] * WJ[6 + c2]) + J[12 + a] * WJ[12 + c2];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 21; k++) H[k] = wave_sum(h[k]);
+#pragma unroll
+  for (int k = 0; k < 6; k++) b[k] = wave_sum(g[k]);
+  chi = wave_sum(acc);
+}
+
+// (H + lambda I) x = b by LDL^T without pivoting; false when a pivot is not positive
+__device__ __forceinline__ bool solve6(const double* H, double lambda, const double* b, double* x) {
+  double A[36], D[6], y[6];
+  {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = i; j < 6; j++, k++) { A[6 * i + j] = H[k]; A[6 * j + i] = H[k]; }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) A[7 * i] += lambda;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    double d = A[7 * j];
+#pragma unroll
+    for (int k = 0; k < j; k++) d -= A[6 * j + k] * A[6 * j + k] * D[k];
+    if (!(d > 0)) ok = false;
+    D[j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = A[6 * i + j];
+#pragma unroll
+      for (int k = 0; k < j; k++) s -= A[6 * i + k] * A[6 * j + k] * D[k];
+      A[6 * i + j] = s / d;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double s = b[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) s -= A[6 * i + k] * y[k];
+    y[i] = s;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) y[i] /= D[i];
+#pragma unroll
+  for (int i = 5; i >= 0; i--) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; k++) s -= A[6 * k + i] * x[k];
+    x[i] = s;
+  }
+  return ok;
+}
+
+__global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(const PoseLaunch a) {
+  const int lane = threadIdx.x & 63;
+  const int f = blockIdx.x * POSE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  if (f >= a.n_frames) return;                       // (a whole wavefront leaves: there is no barrier in this kernel)
+  Frame F;
+  const int o0 = a.obs_ptr[f];
+  F.n = a.obs_ptr[f + 1] - o0;
+  F.obs = a.obs + (size_t)o0 * POSE_OBS_DOUBLES;
+  F.level = a.inlier + o0;
+#pragma unroll
+  for (int k = 0; k < 5; k++) F.intr[k] = a.intr[5 * f + k];
+  F.huber_mono = a.huber_mono; F.huber_stereo = a.huber_stereo;
+  Pose T0 = pose_load(a.T0 + 7 * f);
+  pose_normalize(T0);                                // SE3Quat(const Vector7d&) normalises (types/se3quat.h:67-70)
+  Pose T = T0;
+  // every edge starts at level 0.  A lane reads back only what it wrote itself (observation i belongs to lane i & 63 throughout).
+  for (int i = lane; i < F.n; i += 64) F.level[i] = 1;
+
+  for (int r = 0; r < a.n_rounds; r++) {
+    if (a.restart_each_round) T = T0;
+    const bool robust = r < a.robust_rounds;
+    int n_act = 0;
+    for (int i = lane; i < F.n; i += 64) n_act += F.level[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) n_act += __shfl_xor(n_act, m, 64);
+    int done = 0;
+    double currentChi = 0.0;
+    if (n_act > 0) {
+      const int iterations = a.iterations[r];
+      if (iterations <= 0) currentChi = frame_chi2(F, T, robust, lane);
+      double lambda = 0.0, ni = 2.0;
+      int nBad = 0;
+      for (int it = 0; it < iterations; it++) {
+        double H[21], b[6];
+        frame_linearize(F, T, robust, lane, H, b, currentChi);
+        if (it == 0) {                               // computeLambdaInit (:166-180): tau * max |H_jj|, tau = 1e-5
+          double md = 0.0;
+          int k = 0;
+#pragma unroll
+          for (int j = 0; j < 6; k += 6 - j, j++) md = fmax(fabs(H[k]), md);
+          lambda = 1e-5 * md;
+          ni = 2.0; nBad = 0;
+        }
+        const double iniChi = currentChi;
+        double rho = 0.0;
+        int qmax = 0;
+        do {
+          double x[6];
+          const bool ok2 = solve6(H, lambda, b, x);
+          double tempChi = DBL_MAX, scale = 0.0;
+          Pose Tn = T;
+          if (ok2) {
+            Tn = cam_oplus(T, x);
+            tempChi = frame_chi2(F, Tn, robust, lane);
+#pragma unroll
+            for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);      // computeScale (:182-189)
+          }
+          rho = currentChi - tempChi;
+          scale += 1e-3;
+          rho /= scale;
+          if (rho > 0 && isfinite(tempChi)) {
+            double alpha = 1. - pow(2 * rho - 1, 3.0);
+            alpha = fmin(alpha, 2. / 3.);
+            lambda *= fmax(1. / 3., alpha);
+            ni = 2.0;
+            currentChi = tempChi;
+            T = Tn;
+          } else {
+            lambda *= ni;
+            ni *= 2;
+          }
+          qmax++;
+        } while (rho < 0 && qmax < 10);
+        done++;
+        if (qmax == 10 || rho == 0) break;
+        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
+        if (nBad >= 3) break;
+      }
+    }
+    if (lane == 0) {
+      a.iters_out[f * a.n_rounds + r] = done;
+      a.chi2_out[f * a.n_rounds + r] = currentChi;
+    }
+    // the caller's classification between two optimize() calls: every observation, current outliers included, by its plain chi2
+    for (int i = lane; i < F.n; i += 64) {
+      const Obs o = obs_load(F.obs + (size_t)i * POSE_OBS_DOUBLES);
+      double e[3], pc[3], We[3];
+      obs_error(T, F.intr, o, e, pc);
+      const double c = obs_chi2(o, e, We);
+      const double thr = o.stereo ? a.chi2_stereo : a.chi2_mono;
+      F.level[i] = (thr > 0 && c > thr) ? 0 : 1;
+    }
+  }
+  if (lane == 0) pose_store(T, a.T_out + 7 * f);
+}
+
+}  // namespace
+
+void pose_launch(const PoseLaunch& a, hipStream_t st) {
+  if (a.n_frames <= 0) return;
+  const int blocks = (a.n_frames + POSE_WAVES_PER_BLOCK - 1) / POSE_WAVES_PER_BLOCK;
+  hipLaunchKernelGGL(pose_batch_kernel, dim3(blocks), dim3(64 * POSE_WAVES_PER_BLOCK), 0, st, a);
+}
+
+}  // namespace cs

@@ -1,0 +1,29 @@
+// pose_types.h -- what pose_host.cpp hands to pose_kernels.hip (motion-only pose optimisation, include/cubeslam_hip.h: cs_pose_*).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace cs {
+
+// One observation as the kernel reads it: 16 doubles = 128 bytes, one cache line per lane.
+//   [0..2] Xw   [3..5] measurement (u, v, u_r; mono: u, v, 0)   [6..14] information, row-major 3 x 3 (mono: the upper-left 2 x 2, zeros elsewhere)
+//   [15] 1.0 = EdgeStereoSE3ProjectXYZOnlyPose, 0.0 = EdgeSE3ProjectXYZOnlyPose
+enum { POSE_OBS_DOUBLES = 16, POSE_MAX_ROUNDS = 8, POSE_WAVES_PER_BLOCK = 4 };
+
+struct PoseLaunch {
+  int n_frames, n_rounds;
+  int iterations[POSE_MAX_ROUNDS];
+  int robust_rounds, restart_each_round;
+  double huber_mono, huber_stereo, chi2_mono, chi2_stereo;
+  const double* T0;        // n_frames x 7
+  const double* intr;      // n_frames x 5: fx fy cx cy bf
+  const int* obs_ptr;      // n_frames + 1
+  const double* obs;       // obs_ptr[n_frames] x POSE_OBS_DOUBLES
+  double* T_out;           // n_frames x 7
+  double* chi2_out;        // n_frames x n_rounds
+  int* iters_out;          // n_frames x n_rounds
+  unsigned char* inlier;   // obs_ptr[n_frames]: the level of every observation between the rounds, and the result
+};
+
+void pose_launch(const PoseLaunch& a, hipStream_t st);
+
+}  // namespace cs

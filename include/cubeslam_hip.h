@@ -479,6 +479,63 @@ int cs_ba_check_finite(cs_ba* ba, int* n_bad, char* report, int report_cap);
 int cs_ba_dump(cs_ba* ba, const char* path);
 int cs_ba_load(const char* path, int device, cs_ba** out);
 
+/* ------------------------------------------------------------------ Path B': motion-only pose optimisation, batched -- */
+/* Replaces, for many frames at once, what a tracking thread built on ORB-SLAM2 does once per frame with g2o: a graph of ONE free
+ * VertexSE3Expmap (types/types_six_dof_expmap.h:59-77) and the frame's unary edges
+ *   EdgeSE3ProjectXYZOnlyPose          types_six_dof_expmap.h:208-236   (computeError :218-222, linearizeOplus .cpp:311-333, cam_project .cpp:335-341)
+ *   EdgeStereoSE3ProjectXYZOnlyPose    types_six_dof_expmap.h:239-267   (computeError :249-253, linearizeOplus .cpp:380-409, cam_project .cpp:344-351)
+ * optimised in a few rounds -- each one SparseOptimizer::optimize(iterations[r]) (core/sparse_optimizer.cpp:354-419) with
+ * OptimizationAlgorithmLevenberg (core/optimization_algorithm_levenberg.cpp:61-189: lambda initialised from tau * max |H_jj| in every
+ * round, rho, the accept / reject updates, at most 10 trials, the stopping rules) -- with the caller's inlier / outlier classification
+ * between the rounds (Edge::setLevel(1) on an outlier, initializeOptimization(0) before the next round).  There are no marginalised
+ * vertices, hence no Schur complement: the 6 x 6 system H + lambda I is solved by an LDL^T without pivoting, and a pivot that is not
+ * positive makes the trial a failed one (LinearSolverDense, solvers/linear_solver_dense.h:104-111).  The quadratic form and the rho'
+ * weighting are BaseUnaryEdge::constructQuadraticForm's (core/base_unary_edge.hpp:42-72), the kernel is RobustKernelHuber with its
+ * single-precision delta^2 (core/robust_kernel_impl.h:86), the update is VertexSE3Expmap::oplusImpl (exp(update) * estimate).
+ * In the stereo edge bf is the double member it is there (the float cast of bf belongs to the binary EdgeStereoSE3ProjectXYZ, .cpp:195,
+ * which is not part of this library); its cam_project keeps 1 / z in a `const float` (.cpp:345) and so does this library.
+ * All frames of a call are optimised by ONE kernel launch, one wavefront per frame; a frame's result does not
+ * depend on its position in the batch or on the batch's size.
+ *
+ * The round schedule and the classification are the caller's code in the reference's lineage, not g2o's; cs_pose_default_params() fills
+ * ORB-SLAM2's Optimizer::PoseOptimization values, which are NOT IN THE REFERENCE: 4 rounds of 10 iterations, Huber kernel in the first 3,
+ * every round restarted from the frame's initial pose, deltas sqrt(5.991) / sqrt(7.815), thresholds 5.991 / 7.815.                  */
+typedef struct cs_pose_params {
+  int    n_rounds;                 /* optimize() calls per frame, 1..8                                  */
+  int    iterations[8];            /* LM iterations of round r                                          */
+  int    robust_rounds;            /* the Huber kernel is on in rounds r < robust_rounds                */
+  int    restart_each_round;       /* 1: every round starts from the frame's initial pose               */
+  double huber_mono, huber_stereo; /* RobustKernelHuber::delta per class, <= 0: no kernel               */
+  double chi2_mono, chi2_stereo;   /* after each round an observation whose e^T Omega e exceeds it is   */
+                                   /* left out of the next round (edge level 1); <= 0: never classify   */
+} cs_pose_params;
+void cs_pose_default_params(cs_pose_params* p);
+/* Frame f owns observations obs_ptr[f] .. obs_ptr[f + 1] - 1 (obs_ptr[0] = 0, non-decreasing).  Per observation: Xw3 the fixed map point
+ * (the edge's Xw member), meas3 = u v u_r, info9 = row-major 3 x 3 information, is_stereo != 0 = the stereo edge; a mono observation uses
+ * meas3[0..1] and the upper-left 2 x 2 of info9 (entries 0 1 3 4).  Poses are world-to-camera, 7 doubles in SE3Quat::toVector order.
+ * Outputs: Tcw7_out n_frames x 7, the pose the last round ended on; inlier_out one byte per observation, 1 = at or under its threshold
+ * at that pose; chi2_out and iterations_done n_frames x n_rounds (either may be NULL): activeRobustChi2 over the round's level-0
+ * observations at the pose round r ended on, and what optimize() returned for round r.  Classification after a round tests every
+ * observation of the frame, current outliers included, by its plain (not robustified) chi2.  A round without a level-0 observation leaves
+ * the pose as it is and reports 0 iterations.                                                                                     */
+int cs_pose_optimize_batch(int device, const cs_pose_params* p, int n_frames,
+      const double* Tcw7_in,        /* n_frames x 7, world-to-camera, SE3Quat::toVector order            */
+      const double* intr5,          /* n_frames x 5: fx fy cx cy bf                                      */
+      const int* obs_ptr,           /* n_frames + 1: frame f owns observations obs_ptr[f]..obs_ptr[f+1]  */
+      const double* Xw3, const double* meas3, const double* info9, const unsigned char* is_stereo,
+      double* Tcw7_out, unsigned char* inlier_out, double* chi2_out, int* iterations_done /* n_frames x n_rounds */);
+/* The same with a handle that keeps its stream and its device / pinned buffers between calls (they grow on demand and never shrink): what
+ * a tracking loop calls every frame.  Same arguments, same bits as the one-shot form.  Calls on one handle must not overlap.        */
+typedef struct cs_pose_batch cs_pose_batch;
+int cs_pose_batch_create(int device, cs_pose_batch** out);
+void cs_pose_batch_destroy(cs_pose_batch* b);
+int cs_pose_batch_optimize(cs_pose_batch* b, const cs_pose_params* p, int n_frames, const double* Tcw7_in, const double* intr5, const int* obs_ptr,
+      const double* Xw3, const double* meas3, const double* info9, const unsigned char* is_stereo,
+      double* Tcw7_out, unsigned char* inlier_out, double* chi2_out, int* iterations_done);
+/* Of the handle's last call: kernel_ms = the one kernel, from hipEvents on the handle's stream; host_ms = the whole call on a monotonic
+ * clock (packing, the two copies and the kernel included).                                                                          */
+int cs_pose_batch_last_timing(const cs_pose_batch* b, double* kernel_ms, double* host_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,298 @@
+"""Float64 numpy statement of g2o's motion-only pose optimisation: TEST INFRASTRUCTURE, shares no code with the product.
+
+Written from the reference's lines:
+  EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose   Thirdparty/g2o/g2o/types/types_six_dof_expmap.h:208-267
+  their linearizeOplus and cam_project                          types/types_six_dof_expmap.cpp:311-408
+  BaseUnaryEdge::constructQuadraticForm (rho' weighting)        core/base_unary_edge.hpp:42-72
+  RobustKernelHuber (float dsqr)                                core/robust_kernel_impl.cpp:65-91, robust_kernel_impl.h:86
+  OptimizationAlgorithmLevenberg::solve / computeLambdaInit / computeScale   core/optimization_algorithm_levenberg.cpp:61-189
+  SparseOptimizer::optimize                                     core/sparse_optimizer.cpp:354-419
+  LinearSolverDense (LDL^T, isPositive)                         solvers/linear_solver_dense.h:104-111
+  SE3Quat exp / operator* / map / normalizeRotation             types/se3quat.h:67-70, 110-116, 274-323, 346-351
+  VertexSE3Expmap::oplusImpl                                    types/types_six_dof_expmap.h:73-76
+The round schedule and the classification between the rounds are the caller's (ORB-SLAM2's Optimizer::PoseOptimization pattern): after
+each round every observation -- current outliers included -- is tested by its plain chi2 at the round's final pose.
+
+optimize_frame() also records what the tests' condition on the inputs needs: every LM trial's rho and, at every classification point,
+how close any observation's chi2 came to its threshold.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+DEFAULTS = dict(n_rounds=4, iterations=[10, 10, 10, 10], robust_rounds=3, restart_each_round=1,
+                huber_mono=np.sqrt(5.991), huber_stereo=np.sqrt(7.815), chi2_mono=5.991, chi2_stereo=7.815)
+
+
+# ---- SE3Quat: 7-vector x y z qx qy qz qw
+def _qmul(a, b):
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx,
+                     aw * bw - ax * bx - ay * by - az * bz])
+
+
+def _normalize(q):
+    if q[3] < 0:
+        q = -q
+    return q / np.sqrt(q @ q)
+
+
+def _rot(q):
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def _quat_from_rot(R):
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    if t > 0:
+        s = np.sqrt(t + 1.0)
+        w = 0.5 * s
+        s = 0.5 / s
+        return np.array([(R[2, 1] - R[1, 2]) * s, (R[0, 2] - R[2, 0]) * s, (R[1, 0] - R[0, 1]) * s, w])
+    i = 0
+    if R[1, 1] > R[0, 0]:
+        i = 1
+    if R[2, 2] > R[i, i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    s = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+    q = np.zeros(4)
+    q[i] = 0.5 * s
+    s = 0.5 / s
+    q[3] = (R[k, j] - R[j, k]) * s
+    q[j] = (R[j, i] + R[i, j]) * s
+    q[k] = (R[k, i] + R[i, k]) * s
+    return q
+
+
+def _skew(v):
+    return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+
+
+def se3_exp(u):
+    """SE3Quat::exp, update = [omega, upsilon] (se3quat.h:280-323)."""
+    omega, ups = u[:3], u[3:]
+    theta = np.sqrt(omega @ omega)
+    Om = _skew(omega)
+    Om2 = Om @ Om
+    if theta < 0.00001:
+        R = np.eye(3) + Om + Om2
+        V = R
+    else:
+        R = np.eye(3) + np.sin(theta) / theta * Om + (1 - np.cos(theta)) / (theta * theta) * Om2
+        V = np.eye(3) + (1 - np.cos(theta)) / (theta * theta) * Om + (theta - np.sin(theta)) / (theta ** 3) * Om2
+    return np.concatenate([V @ ups, _normalize(_quat_from_rot(R))])
+
+
+def se3_mul(a, b):
+    """SE3Quat::operator* with normalizeRotation (se3quat.h:110-116)."""
+    return np.concatenate([a[:3] + _rot(a[3:]) @ b[:3], _normalize(_qmul(a[3:], b[3:]))])
+
+
+def se3_from_vector(v):
+    v = np.asarray(v, np.float64)
+    return np.concatenate([v[:3], _normalize(v[3:].copy())])
+
+
+# ---- the two edges, all observations of a frame at once
+def errors(T, intr, Xw, meas, stereo):
+    """computeError of both classes: (n, 3) errors (a mono row's third entry is 0) and the points in the camera frame."""
+    fx, fy, cx, cy, bf = intr
+    pc = Xw @ _rot(T[3:]).T + T[:3]
+    e = np.zeros((len(Xw), 3))
+    m = ~stereo
+    # EdgeSE3ProjectXYZOnlyPose::cam_project: project2d, then * f + c
+    e[m, 0] = meas[m, 0] - (pc[m, 0] / pc[m, 2] * fx + cx)
+    e[m, 1] = meas[m, 1] - (pc[m, 1] / pc[m, 2] * fy + cy)
+    # EdgeStereoSE3ProjectXYZOnlyPose::cam_project: `const float invz = 1.0f / trans_xyz[2]`, bf the double member
+    s = stereo
+    invz = (1.0 / pc[s, 2]).astype(np.float32).astype(np.float64)
+    u = pc[s, 0] * invz * fx + cx
+    e[s, 0] = meas[s, 0] - u
+    e[s, 1] = meas[s, 1] - (pc[s, 1] * invz * fy + cy)
+    e[s, 2] = meas[s, 2] - (u - bf * invz)
+    return e, pc
+
+
+def jacobians(pc, intr, stereo):
+    """linearizeOplus of both classes: (n, 3, 6); a mono edge's third row is 0."""
+    fx, fy, _, _, bf = intr
+    x, y = pc[:, 0], pc[:, 1]
+    invz = 1.0 / pc[:, 2]
+    invz_2 = invz * invz
+    J = np.zeros((len(pc), 3, 6))
+    J[:, 0, 0] = x * y * invz_2 * fx
+    J[:, 0, 1] = -(1 + (x * x * invz_2)) * fx
+    J[:, 0, 2] = y * invz * fx
+    J[:, 0, 3] = -invz * fx
+    J[:, 0, 5] = x * invz_2 * fx
+    J[:, 1, 0] = (1 + y * y * invz_2) * fy
+    J[:, 1, 1] = -x * y * invz_2 * fy
+    J[:, 1, 2] = -x * invz * fy
+    J[:, 1, 4] = -invz * fy
+    J[:, 1, 5] = y * invz_2 * fy
+    s = stereo
+    J[s, 2, 0] = J[s, 0, 0] - bf * y[s] * invz_2[s]
+    J[s, 2, 1] = J[s, 0, 1] + bf * x[s] * invz_2[s]
+    J[s, 2, 2] = J[s, 0, 2]
+    J[s, 2, 3] = J[s, 0, 3]
+    J[s, 2, 5] = J[s, 0, 5] - bf * invz_2[s]
+    return J
+
+
+def omega3(info9, stereo):
+    """(n, 3, 3) information: the stereo edge's 3 x 3, the mono edge's 2 x 2 in the upper-left corner."""
+    W = np.asarray(info9, np.float64).reshape(-1, 3, 3).copy()
+    W[~stereo, 2, :] = 0
+    W[~stereo, :, 2] = 0
+    return W
+
+
+def huber(e2, delta):
+    """RobustKernelHuber::robustify: rho and rho' of the squared errors e2 (delta per edge; <= 0 = no kernel)."""
+    delta = np.broadcast_to(np.asarray(delta, np.float64), e2.shape)
+    dsqr = (delta * delta).astype(np.float32).astype(np.float64)
+    on = (delta > 0) & (e2 > dsqr)
+    sq = np.sqrt(np.where(on, e2, 1.0))
+    return np.where(on, 2 * sq * delta - dsqr, e2), np.where(on, delta / sq, 1.0)
+
+
+def ldlt_solve(A, b):
+    """LDL^T without pivoting; None when a pivot is not positive (LDLT::isPositive)."""
+    n = len(b)
+    L = np.eye(n)
+    D = np.zeros(n)
+    for j in range(n):
+        d = A[j, j] - (L[j, :j] * L[j, :j]) @ D[:j]
+        if not d > 0:
+            return None
+        D[j] = d
+        for i in range(j + 1, n):
+            L[i, j] = (A[i, j] - (L[i, :j] * L[j, :j]) @ D[:j]) / d
+    y = np.zeros(n)
+    for i in range(n):
+        y[i] = b[i] - L[i, :i] @ y[:i]
+    y /= D
+    x = np.zeros(n)
+    for i in range(n - 1, -1, -1):
+        x[i] = y[i] - L[i + 1:, i] @ x[i + 1:]
+    return x
+
+
+class _Graph:
+    """One free VertexSE3Expmap and the level-0 edges of a frame."""
+
+    def __init__(self, intr, Xw, meas, W, stereo, delta):
+        self.intr, self.Xw, self.meas, self.W, self.stereo, self.delta = intr, Xw, meas, W, stereo, delta
+
+    def chi2_each(self, T):
+        e, pc = errors(T, self.intr, self.Xw, self.meas, self.stereo)
+        We = np.einsum("nij,nj->ni", self.W, e)
+        return np.einsum("ni,ni->n", e, We), e, We, pc
+
+    def robust_chi2(self, T):
+        c, _, _, _ = self.chi2_each(T)
+        return huber(c, self.delta)[0].sum()
+
+    def linearize(self, T):
+        c, e, We, pc = self.chi2_each(T)
+        rho0, rho1 = huber(c, self.delta)
+        J = jacobians(pc, self.intr, self.stereo)
+        b = -np.einsum("n,nia,ni->a", rho1, J, We)
+        H = np.einsum("n,nia,nij,njb->ab", rho1, J, self.W, J)
+        return H, b, rho0.sum()
+
+
+def lm_optimize(G, T, iterations, log):
+    """SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg; returns (pose, iterations done, final chi2, trials per iteration)."""
+    lam, ni, n_bad, done, trials = 0.0, 2.0, 0, 0, []
+    current = G.robust_chi2(T)
+    for it in range(iterations):
+        H, b, current = G.linearize(T)
+        if it == 0:
+            lam = 1e-5 * np.abs(np.diag(H)).max()
+            ni, n_bad = 2.0, 0
+        ini = current
+        rho, qmax = 0.0, 0
+        while True:
+            x = ldlt_solve(H + lam * np.eye(6), b)
+            if x is not None:
+                Tn = se3_mul(se3_exp(x), T)
+                temp = G.robust_chi2(Tn)
+                scale = float(x @ (lam * x + b))
+            else:
+                log["not_pd_trials"] += 1
+                Tn, temp, scale = T, np.finfo(np.float64).max, 0.0
+            rho = (current - temp) / (scale + 1e-3)
+            log["rho"].append(rho)
+            if rho > 0 and np.isfinite(temp):
+                alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
+                lam *= max(1.0 / 3.0, alpha)
+                ni = 2.0
+                current, T = temp, Tn
+            else:
+                lam *= ni
+                ni *= 2
+            qmax += 1
+            if not (rho < 0 and qmax < 10):
+                break
+        trials.append(qmax)
+        done += 1
+        if qmax == 10 or rho == 0:
+            break
+        n_bad = n_bad + 1 if (ini - current) * 1e3 < ini else 0
+        if n_bad >= 3:
+            break
+    return T, done, current, trials
+
+
+def optimize_frame(T0, intr, Xw, meas, info9, stereo, params=None):
+    """All rounds of one frame.  Returns a dict: pose (7), inlier (n, bool), chi2 / iterations (n_rounds), trials (list per round),
+    rho (every LM trial's rho), margin (smallest |chi2 / threshold - 1| met at a classification point), not_pd_trials."""
+    p = dict(DEFAULTS, **(params or {}))
+    Xw = np.asarray(Xw, np.float64).reshape(-1, 3)
+    meas = np.asarray(meas, np.float64).reshape(-1, 3)
+    stereo = np.asarray(stereo).astype(bool).ravel()
+    intr = np.asarray(intr, np.float64)
+    W = omega3(info9, stereo)
+    n = len(Xw)
+    thr = np.where(stereo, p["chi2_stereo"], p["chi2_mono"])
+    T0 = se3_from_vector(T0)
+    T = T0
+    level0 = np.ones(n, bool)
+    log = dict(rho=[], not_pd_trials=0)
+    chi2, iters, trials, margin = [], [], [], np.inf
+    for r in range(p["n_rounds"]):
+        if p["restart_each_round"]:
+            T = T0
+        delta = np.where(stereo, p["huber_stereo"], p["huber_mono"]) if r < p["robust_rounds"] else np.zeros(n)
+        a = level0
+        if a.any():
+            G = _Graph(intr, Xw[a], meas[a], W[a], stereo[a], delta[a])
+            T, done, c, tr = lm_optimize(G, T, p["iterations"][r], log)
+        else:
+            done, c, tr = 0, 0.0, []
+        chi2.append(c); iters.append(done); trials.append(tr)
+        if n:
+            each = _Graph(intr, Xw, meas, W, stereo, np.zeros(n)).chi2_each(T)[0]
+            on = thr > 0
+            if on.any():
+                margin = min(margin, np.abs(each[on] / thr[on] - 1).min())
+            level0 = ~(on & (each > thr))
+    return dict(pose=T, inlier=level0, chi2=np.array(chi2), iterations=np.array(iters, np.int32), trials=trials,
+                rho=np.array(log["rho"]), margin=margin, not_pd_trials=log["not_pd_trials"])
+
+
+def optimize_batch(batch, params=None):
+    """optimize_frame over a batch dict (cube_slam_wu_amd.synth_pose layout); a list of per-frame results."""
+    out = []
+    ptr = batch["obs_ptr"]
+    for f in range(len(batch["Tcw"])):
+        s = slice(ptr[f], ptr[f + 1])
+        out.append(optimize_frame(batch["Tcw"][f], batch["intr"][f], batch["Xw"][s], batch["meas"][s], batch["info"][s], batch["is_stereo"][s], params))
+    return out
