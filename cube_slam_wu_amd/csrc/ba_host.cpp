@@ -32,67 +32,19 @@
 
 #include "../../include/cubeslam_hip.h"
 #include "ba_types.h"
-
-namespace cs {
-int ba_chi2_blocks(int n_proj);
-void ba_launch_chi2(const BaView& v, int nb_proj, hipStream_t st);
-void ba_launch_fill_rows4(double* dst, const double* rec4, long long rows, hipStream_t st);
-void ba_launch_linearize(const BaView& v, hipStream_t st, hipStream_t st2, hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t st3, hipEvent_t ev_join3, hipEvent_t ev_pre = nullptr);
-void ba_launch_reduce(const BaView& v, const double* lambda_dev, hipStream_t st, hipStream_t st2, hipEvent_t ev_fork, hipEvent_t ev_join, const BaSidePrologue* sp = nullptr);
-void ba_launch_gather_rows(const double* src, const int* idx, int n, int width, double* dst, hipStream_t st);
-void ba_launch_backsub(const BaView& v, hipStream_t st);
-int ba_scale_blocks();
-void ba_launch_scale(const BaView& v, const double* lambda_dev, double* partial, hipStream_t st);
-void ba_launch_update(const BaView& v, hipStream_t st, double* bak_cams = nullptr, double* bak_points = nullptr, double* bak_cubes = nullptr);
-void ba_launch_scale_update(const BaView& v, const double* lambda_dev, double* partial, hipStream_t st, double* bak_cams, double* bak_points, double* bak_cubes);
-void ba_launch_band_cholesky(double* Sb, double* work, int n, int LD, double* rhs, int* info, bool solve, hipStream_t st, bool one_sided = false);
-void ba_launch_sep_reduce(const double* S, int LD, const double* Linv, int ci, int ni, int zl, int wl, int zr, int wr, double* Y, const double* rhs, double* msg, int wm, hipStream_t st);
-void ba_launch_sep_assemble(const double* msgs, size_t msg_doubles, int wm, int R, const int* sep_off, int n, int LDs, double* Ssep, double* rsep, hipStream_t st);
-void ba_launch_sep_scatter(const double* xsep, int n, int R, const int* sep_off, const int* sep_col, double* x, hipStream_t st);
-void ba_launch_sep_backsolve(double* S, int LD, double* work, int ci, int ni, int zl, int wl, int zr, int wr, double* Y, double* rhs, int* info, hipStream_t st);
-void ba_launch_fail_flag(const int* a, const int* b, const int* c, double* out, hipStream_t st);
-size_t ba_band_workspace_doubles(int n, int LD);
-int ba_band_team(int LD, int* rw_out);
-bool ba_band_fits_device(int n, int LD, bool one_sided = false);
-bool ba_bcr_ok(int n, int LD);
-double ba_bcr_estimate_ms(int n);
-size_t ba_bcr_workspace_doubles(int n, int Bv);
-void ba_launch_bcr(const double* Sb, double* work, int n, int LD, int Bv, double* rhs, int* info, hipStream_t st);
-bool ba_bcr_sep_ok(int wm, int R);
-size_t ba_bcr_sep_workspace_doubles(int R);
-void ba_launch_bcr_sep(const double* msgs, size_t msg_doubles, int wm, int R, const int* sep_off, const int* sep_col, int ns, double* work, double* x, int* info, hipStream_t st);
-void ba_launch_sum2(const double* a, int na, const double* b, int nb, double* out, hipStream_t st);
-void ba_launch_multi_zero(const std::pair<void*, size_t>* list, int n, hipStream_t st);
-void ba_launch_multi_copy(const BaCopyItem* list, int n, hipStream_t st);
-void ba_launch_sum2_flag(const double* a, int na, const double* b, int nb, const int* f0, const int* f1, double* out, hipStream_t st, double* host_out = nullptr, double seq = 0.0);
-void ba_launch_max_diag(const BaView& v, double* out, hipStream_t st);
-void ba_launch_trial_prologue(double* d_lam, double lam0, double lam1, int* info24, int* elim_fail, double* S, size_t n_clear, hipStream_t st);
-void ba_launch_ext_add(const BaView& v, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3, hipStream_t st);
-void ba_launch_ext_offdiag(const BaView& v, int n_groups, const int* gptr, const int* order, const int* e4, const double* Hij, hipStream_t st);
-void ba_launch_scan_finite(const double* p, long long n, int* out, hipStream_t st);
-void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st);
-}  // namespace cs
-
-extern "C" const char* cs_last_error(void);
-void cs_set_error_ba(const std::string& s);
+#include "cs_hip_util.h"
 
 namespace {
 
-#define BA_TRY(expr)                                                           \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cs_set_error_ba(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
+using cs::now_ms;
+
 // a phase mark on the handle's stream -- only while the stage split is asked for (cs_ba_set_stage_timing)
-#define BA_MARK(B, e) do { if ((B)->stage_timing) BA_TRY(hipEventRecord((e), (B)->st)); } while (0)
+#define BA_MARK(B, e) do { if ((B)->stage_timing) CS_HIP_TRY(hipEventRecord((e), (B)->st)); } while (0)
 #define BA_NCCL(expr)                                                          \
   do {                                                                         \
     ncclResult_t _r = (expr);                                                  \
     if (_r != ncclSuccess) {                                                   \
-      cs_set_error_ba(std::string(#expr) + ": " + ncclGetErrorString(_r));     \
+      cs_set_error(std::string(#expr) + ": " + ncclGetErrorString(_r));     \
       return CS_ERR_HIP;                                                       \
     }                                                                          \
   } while (0)
@@ -100,18 +52,10 @@ namespace {
   do {                                                                         \
     rocblas_status _s = (expr);                                                \
     if (_s != rocblas_status_success) {                                        \
-      cs_set_error_ba(std::string(#expr) + ": rocblas status " + std::to_string((int)_s)); \
+      cs_set_error(std::string(#expr) + ": rocblas status " + std::to_string((int)_s)); \
       return CS_ERR_HIP;                                                       \
     }                                                                          \
   } while (0)
-
-// no C++ exception crosses the C boundary
-#define BA_GUARD_BEGIN try {
-#define BA_GUARD_END(fn_name)                                                                                                   \
-  } catch (const std::bad_alloc&) { cs_set_error_ba(std::string(fn_name) + ": out of host memory"); return CS_ERR_CAPACITY; }   \
-    catch (const std::exception& ex) { cs_set_error_ba(std::string(fn_name) + ": " + ex.what()); return CS_ERR_CAPACITY; }
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Pinned staging for the structure phase's many small uploads: a blocking hipMemcpy from pageable memory costs ~40 us whatever its
 // size, and the phase makes a few dozen; through this arena they are queued on the handle's stream and waited for once.
@@ -129,7 +73,7 @@ struct StageArena {
     if (p && cap >= want) return CS_OK;
     if (p) (void)hipHostFree(p);
     p = nullptr; cap = 0;
-    BA_TRY(hipHostMalloc((void**)&p, want));
+    CS_HIP_TRY(hipHostMalloc((void**)&p, want));
     cap = want;
     return CS_OK;
   }
@@ -150,14 +94,14 @@ struct DBuf {
     const size_t want = p ? count + count / 4 + 64 : count;
     g_dbuf_reallocs++;
     if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    BA_TRY(hipMalloc((void**)&p, want * sizeof(T)));
+    CS_HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
     cap = want;
     return CS_OK;
   }
   int upload_ptr(const T* h, size_t count) {   // from the caller's memory
     int rc = reserve(count); if (rc) return rc;
     n = count;
-    if (n) BA_TRY(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
+    if (n) CS_HIP_TRY(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
     return CS_OK;
   }
   int append_ptr(const T* h, size_t count) {   // the old contents stay where they are on the device, `count` new entries follow
@@ -165,12 +109,12 @@ struct DBuf {
     if (!p || n + count > cap) {               // (with head room: the next frames append in place)
       const size_t want = std::max(n + count, cap + cap / 2 + 16);
       T* q = nullptr;
-      BA_TRY(hipMalloc((void**)&q, want * sizeof(T)));
-      if (n) BA_TRY(hipMemcpy(q, p, n * sizeof(T), hipMemcpyDeviceToDevice));
+      CS_HIP_TRY(hipMalloc((void**)&q, want * sizeof(T)));
+      if (n) CS_HIP_TRY(hipMemcpy(q, p, n * sizeof(T), hipMemcpyDeviceToDevice));
       if (p) (void)hipFree(p);
       p = q; cap = want;
     }
-    BA_TRY(hipMemcpy(p + n, h, count * sizeof(T), hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(p + n, h, count * sizeof(T), hipMemcpyHostToDevice));
     n += count;
     return CS_OK;
   }
@@ -181,11 +125,11 @@ struct DBuf {
     const size_t bytes = count * sizeof(T);
     void* pin = (p && n + count <= cap && bytes <= (256u << 10)) ? stage.take(bytes) : nullptr;
     if (!pin) {                                   // growing (the old contents are copied: nothing may still be writing them) or no room
-      BA_TRY(hipStreamSynchronize(st));
+      CS_HIP_TRY(hipStreamSynchronize(st));
       return append_ptr(h, count);
     }
     std::memcpy(pin, h, bytes);
-    BA_TRY(hipMemcpyAsync(p + n, pin, bytes, hipMemcpyHostToDevice, st));
+    CS_HIP_TRY(hipMemcpyAsync(p + n, pin, bytes, hipMemcpyHostToDevice, st));
     n += count;
     return CS_OK;
   }
@@ -198,7 +142,7 @@ struct DBuf {
     int rc = reserve(count); if (rc) return rc;
     n = count;
     std::memcpy(pin, h, bytes);
-    BA_TRY(hipMemcpyAsync(p, pin, bytes, hipMemcpyHostToDevice, st));
+    CS_HIP_TRY(hipMemcpyAsync(p, pin, bytes, hipMemcpyHostToDevice, st));
     return CS_OK;
   }
   // like upload_ptr_staged, but the copy itself is left to the caller's batched launch (cs::ba_launch_multi_copy): destination, staged
@@ -219,8 +163,8 @@ struct DBuf {
   int alloc(size_t count, hipStream_t st = nullptr) {   // zeroed; st: queued on that stream instead of a blocking call per buffer
     int rc = reserve(count); if (rc) return rc;
     n = count;
-    if (st) BA_TRY(hipMemsetAsync(p, 0, std::max<size_t>(1, n) * sizeof(T), st));
-    else BA_TRY(hipMemset(p, 0, std::max<size_t>(1, n) * sizeof(T)));
+    if (st) CS_HIP_TRY(hipMemsetAsync(p, 0, std::max<size_t>(1, n) * sizeof(T), st));
+    else CS_HIP_TRY(hipMemset(p, 0, std::max<size_t>(1, n) * sizeof(T)));
     return CS_OK;
   }
   // zeroed like alloc(), but the fill is left to the caller's batched launch (cs::ba_launch_multi_zero): ptr / bytes are appended to the list
@@ -523,8 +467,8 @@ void landmark_owners(int n_ranks, int n_cams, int n_points, int n_proj, const in
 
 int finalize_structure(cs_ba* B) {
   if (!B->structure_dirty) return CS_OK;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));             // nothing of an earlier call may still read the buffers (or the staging arena) reused below
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));             // nothing of an earlier call may still read the buffers (or the staging arena) reused below
   { const int rc0 = B->stage.begin((size_t)8 << 20); if (rc0) return rc0; }
   static const bool prof = getenv("CS_BA_PROF") != nullptr;   // diagnostics: host phase clock of the structure phase
   double t_ph = now_ms();
@@ -548,7 +492,7 @@ int finalize_structure(cs_ba* B) {
   // gorder: free landmarks with >= 1 edge sorted by (number of cameras, camera list); run_first: where each distinct set starts
   // (edges that an earlier phase of this handle has seen were checked then, and append only raises nc / np)
   for (int k = std::min(B->st_lists_edges, B->n_proj); k < B->n_proj; k++)
-    if (B->e_pt[k] < 0 || B->e_pt[k] >= np || B->e_cam[k] < 0 || B->e_cam[k] >= nc) { cs_set_error_ba("projection edge index out of range"); return CS_ERR_INVALID_ARG; }
+    if (B->e_pt[k] < 0 || B->e_pt[k] >= np || B->e_cam[k] < 0 || B->e_cam[k] >= nc) { cs_set_error("projection edge index out of range"); return CS_ERR_INVALID_ARG; }
   mark("  checks, index mapping");
   std::vector<int> cam_cnt(np + 1, 0), gorder, run_first;
   // edges grouped by landmark: camera (sorted by id) and caller edge index
@@ -645,7 +589,7 @@ int finalize_structure(cs_ba* B) {
     mark("  camera lists (count, fill, sort)");
     for (int p = 0; p < np; p++) {
       for (int a = cam_cnt[p] + 1; a < cam_cnt[p + 1]; a++)
-        if (cams_of[a] == cams_of[a - 1]) { cs_set_error_ba("two projection edges between the same point and camera"); return CS_ERR_INVALID_ARG; }
+        if (cams_of[a] == cams_of[a - 1]) { cs_set_error("two projection edges between the same point and camera"); return CS_ERR_INVALID_ARG; }
       if (!B->pt_fixed[p] && cam_cnt[p + 1] > cam_cnt[p]) gorder.push_back(p);
     }
     mark("  duplicate check");
@@ -726,9 +670,9 @@ int finalize_structure(cs_ba* B) {
   mark("camera sets");
   // ---- cuboid / odometry edge indices are used below: check them first
   for (int k = 0; k < B->n_cub; k++)
-    if (B->ce_cam[k] < 0 || B->ce_cam[k] >= nc || B->ce_cub[k] < 0 || B->ce_cub[k] >= no) { cs_set_error_ba("cuboid edge index out of range"); return CS_ERR_INVALID_ARG; }
+    if (B->ce_cam[k] < 0 || B->ce_cam[k] >= nc || B->ce_cub[k] < 0 || B->ce_cub[k] >= no) { cs_set_error("cuboid edge index out of range"); return CS_ERR_INVALID_ARG; }
   for (int k = 0; k < B->n_odom; k++)
-    if (B->oe_i[k] < 0 || B->oe_i[k] >= nc || B->oe_j[k] < 0 || B->oe_j[k] >= nc) { cs_set_error_ba("odometry edge index out of range"); return CS_ERR_INVALID_ARG; }
+    if (B->oe_i[k] < 0 || B->oe_i[k] >= nc || B->oe_j[k] < 0 || B->oe_j[k] >= nc) { cs_set_error("odometry edge index out of range"); return CS_ERR_INVALID_ARG; }
   // ---- solver ordering of the pose vertices: reverse Cuthill-McKee on the block graph of the reduced system
   // (camera-camera through shared landmarks and odometry edges, camera-cuboid through cuboid edges), so that S is
   // banded for trajectory-shaped graphs.  The ordering only permutes the linear system; g2o's order is kept for x/b
@@ -748,12 +692,12 @@ int finalize_structure(cs_ba* B) {
   for (int k = 0; k < B->ext_n; k++) {
     const int ci = B->ext_e4[4 * k], ii = B->ext_e4[4 * k + 1], cj = B->ext_e4[4 * k + 2], ij = B->ext_e4[4 * k + 3];
     auto bad = [&](int c, int i) { return c < 0 || c > 2 || i < 0 || i >= (c == 0 ? nc : c == 1 ? no : np); };
-    if (bad(ci, ii) || (ij >= 0 && bad(cj, ij))) { cs_set_error_ba("external edge: vertex class / index out of range"); return CS_ERR_INVALID_ARG; }
-    if (ij >= 0 && (ci == 2 || cj == 2)) { cs_set_error_ba("external edge: a binary edge may join cameras and cuboids only (a marginalised point takes unary terms only: its coupling to a pose would change the Schur structure)"); return CS_ERR_INVALID_ARG; }
-    if (ij >= 0 && ci == cj && ii == ij) { cs_set_error_ba("external edge: both ends are the same vertex"); return CS_ERR_INVALID_ARG; }
+    if (bad(ci, ii) || (ij >= 0 && bad(cj, ij))) { cs_set_error("external edge: vertex class / index out of range"); return CS_ERR_INVALID_ARG; }
+    if (ij >= 0 && (ci == 2 || cj == 2)) { cs_set_error("external edge: a binary edge may join cameras and cuboids only (a marginalised point takes unary terms only: its coupling to a pose would change the Schur structure)"); return CS_ERR_INVALID_ARG; }
+    if (ij >= 0 && ci == cj && ii == ij) { cs_set_error("external edge: both ends are the same vertex"); return CS_ERR_INVALID_ARG; }
     if (ij >= 0 && (ci == 1 || cj == 1)) ext_binary_on_cuboid = true;
   }
-  if (B->shard_n > 1 && (B->ext_n > 0 || B->ext_fn || B->ext_terms_set)) { cs_set_error_ba("external (host-evaluated) edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
+  if (B->shard_n > 1 && (B->ext_n > 0 || B->ext_fn || B->ext_terms_set)) { cs_set_error("external (host-evaluated) edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
   std::vector<std::vector<int>> cub_cams(no);     // free cameras observing a free cuboid, distinct, by camera id
   int max_slots = 0, n_free_cub = 0;
   for (int k = 0; k < B->n_cub; k++) if (!B->cub_fixed[B->ce_cub[k]] && !B->cam_fixed[B->ce_cam[k]]) cub_cams[B->ce_cub[k]].push_back(B->ce_cam[k]);
@@ -1000,7 +944,7 @@ int finalize_structure(cs_ba* B) {
     if (!all && copy_list.size() < 24 && bytes < ((size_t)2 << 20)) return CS_OK;
     for (size_t i = 0; i < copy_list.size(); i += 48) cs::ba_launch_multi_copy(copy_list.data() + i, (int)std::min<size_t>(48, copy_list.size() - i), B->st);
     copy_list.clear();
-    BA_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
     return CS_OK;
   };
 #define UP(buf, vec) do { rc = upload_kernel ? (buf).upload_ptr_deferred((vec).data(), (vec).size(), B->stage, copy_list, B->st) : (buf).upload_staged(vec, B->stage, B->st); if (!rc) rc = cflush(false); if (rc) return rc; } while (0)
@@ -1010,7 +954,7 @@ int finalize_structure(cs_ba* B) {
   auto zflush = [&]() -> int {
     for (size_t i = 0; i < zero_list.size(); i += 48) cs::ba_launch_multi_zero(zero_list.data() + i, (int)std::min<size_t>(48, zero_list.size() - i), B->st);
     zero_list.clear();
-    BA_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
     return CS_OK;
   };
 #define AL(buf, n) do { rc = (buf).alloc_deferred(n, zero_list); if (rc) return rc; } while (0)
@@ -1090,7 +1034,7 @@ int finalize_structure(cs_ba* B) {
   int edge_rc = CS_OK;
   std::thread edge_th([&]() {
     edge_rc = [&]() -> int {
-      BA_TRY(hipSetDevice(B->device));
+      CS_HIP_TRY(hipSetDevice(B->device));
       int r;
       const size_t Ez = (size_t)E;
 #define ER(call) do { r = (call); if (r) return r; } while (0)
@@ -1108,7 +1052,7 @@ int finalize_structure(cs_ba* B) {
       if (per_info) cs::ba_launch_gather_rows(B->pm_info.p, B->cm_pm.p, E, 4, B->cm_info.p, B->st);
       if (per_intr) cs::ba_launch_gather_rows(B->pm_intr.p, B->cm_pm.p, E, 4, B->cm_intr.p, B->st);
       cs::ba_launch_gather_rows(B->pm_huber.p, B->cm_pm.p, E, 1, B->cm_huber.p, B->st);
-      BA_TRY(hipGetLastError());
+      CS_HIP_TRY(hipGetLastError());
       ER(B->pm_pt.upload_ptr(pm_pt.data(), Ez)); ER(B->pm_cam.upload_ptr(pm_cam.data(), Ez)); ER(B->cm_pt.upload_ptr(cm_pt.data(), Ez));
 #undef ER
       return CS_OK;
@@ -1467,7 +1411,7 @@ int finalize_structure(cs_ba* B) {
       if (B->h_scalars) (void)hipHostFree(B->h_scalars);
       B->h_scalars = nullptr;
       const size_t want = need + need / 4 + 256;
-      BA_TRY(hipHostMalloc((void**)&B->h_scalars, want * sizeof(double)));
+      CS_HIP_TRY(hipHostMalloc((void**)&B->h_scalars, want * sizeof(double)));
       B->scalars_cap = want;
     }
   }
@@ -1514,7 +1458,7 @@ int finalize_structure(cs_ba* B) {
   // the allocations above are zeroed on B->st (one batched fill, one wait here); uploads went through blocking copies
   ZFLUSH();
   rc = cflush(true); if (rc) return rc;
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   B->append_stage.off = 0;           // (the appended rows have arrived)
   B->st_lists_edges = B->n_proj; B->st_cam_cnt = std::move(cam_cnt); B->st_cur = st_nb;   // (for a grown graph's next phase)
   mark("pose edges + allocations");
@@ -1530,10 +1474,10 @@ namespace {
 
 int chi2_device(cs_ba* B, double* chi) {
   cs::ba_launch_chi2(B->view, B->nb_chi, B->st);
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   std::vector<double> part(B->n_chi_partials);
-  BA_TRY(hipMemcpyAsync(part.data(), B->chi_partial.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipMemcpyAsync(part.data(), B->chi_partial.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   double s = 0;
   for (double p : part) s += p;  // fixed order
   *chi = s;
@@ -1544,10 +1488,10 @@ int chi2_device(cs_ba* B, double* chi) {
 int fetch_b(cs_ba* B) {
   B->h_b.assign(B->n_pose + 3 * (size_t)B->n_lm, 0.0);
   std::vector<double> bc(6 * (size_t)B->nc), bo(9 * (size_t)B->no), bl(3 * (size_t)B->np);
-  if (B->nc) BA_TRY(hipMemcpyAsync(bc.data(), B->bcam.p, 8 * bc.size(), hipMemcpyDeviceToHost, B->st));
-  if (B->no) BA_TRY(hipMemcpyAsync(bo.data(), B->bcub.p, 8 * bo.size(), hipMemcpyDeviceToHost, B->st));
-  if (B->np) BA_TRY(hipMemcpyAsync(bl.data(), B->bl.p, 8 * bl.size(), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(bc.data(), B->bcam.p, 8 * bc.size(), hipMemcpyDeviceToHost, B->st));
+  if (B->no) CS_HIP_TRY(hipMemcpyAsync(bo.data(), B->bcub.p, 8 * bo.size(), hipMemcpyDeviceToHost, B->st));
+  if (B->np) CS_HIP_TRY(hipMemcpyAsync(bl.data(), B->bl.p, 8 * bl.size(), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   for (int i = 0; i < B->nc; i++) if (B->cam_col[i] >= 0) std::memcpy(&B->h_b[B->cam_col[i]], &bc[6 * (size_t)i], 48);
   for (int i = 0; i < B->no; i++) if (B->cub_col[i] >= 0) std::memcpy(&B->h_b[B->cub_col[i]], &bo[9 * (size_t)i], 72);
   for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) std::memcpy(&B->h_b[B->n_pose + 3 * (size_t)B->pt_lm[i]], &bl[3 * (size_t)i], 24);
@@ -1557,9 +1501,9 @@ int fetch_b(cs_ba* B) {
 int fetch_x(cs_ba* B) {
   B->h_x.assign(B->n_pose + 3 * (size_t)B->n_lm, 0.0);
   std::vector<double> xl(3 * (size_t)B->np);
-  if (B->n_pose) BA_TRY(hipMemcpyAsync(B->h_x.data(), B->view.rhs, 8 * (size_t)B->n_pose, hipMemcpyDeviceToHost, B->st));
-  if (B->np) BA_TRY(hipMemcpyAsync(xl.data(), B->xl.p, 8 * xl.size(), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  if (B->n_pose) CS_HIP_TRY(hipMemcpyAsync(B->h_x.data(), B->view.rhs, 8 * (size_t)B->n_pose, hipMemcpyDeviceToHost, B->st));
+  if (B->np) CS_HIP_TRY(hipMemcpyAsync(xl.data(), B->xl.p, 8 * xl.size(), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) std::memcpy(&B->h_x[B->n_pose + 3 * (size_t)B->pt_lm[i]], &xl[3 * (size_t)i], 24);
   return CS_OK;
 }
@@ -1569,7 +1513,7 @@ int collect_lin_time(cs_ba* B) {
   if (!B->stage_timing) { B->lin_pending = false; return CS_OK; }
   if (!B->lin_pending) return CS_OK;
   float ms = 0;
-  BA_TRY(hipEventElapsedTime(&ms, B->ev[0], B->ev[1]));
+  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[0], B->ev[1]));
   B->tm.linearize_ms += ms;
   B->lin_pending = false;
   return CS_OK;
@@ -1579,11 +1523,11 @@ int build_system_device(cs_ba* B, hipEvent_t ev_pre = nullptr) {
   BA_MARK(B, B->ev[0]);
   cs::ba_launch_linearize(B->view, B->st, B->st2, B->ev_fork, B->ev_join, B->st3, B->ev_join3, ev_pre);
   if (B->ext_terms_set) {
-    if (B->ext_cam36.n != 36 * (size_t)B->nc || B->ext_cub81.n != 81 * (size_t)B->no || B->ext_pt9.n != 9 * (size_t)B->np) { cs_set_error_ba("external terms were set for a graph of another size: call cs_ba_set_external_terms again"); return CS_ERR_INVALID_ARG; }
+    if (B->ext_cam36.n != 36 * (size_t)B->nc || B->ext_cub81.n != 81 * (size_t)B->no || B->ext_pt9.n != 9 * (size_t)B->np) { cs_set_error("external terms were set for a graph of another size: call cs_ba_set_external_terms again"); return CS_ERR_INVALID_ARG; }
     cs::ba_launch_ext_add(B->view, B->ext_has_cam ? B->ext_cam36.p : nullptr, B->ext_cam6.p, B->ext_has_cub ? B->ext_cub81.p : nullptr, B->ext_cub9.p,
                           B->ext_has_pt ? B->ext_pt9.p : nullptr, B->ext_pt3.p, B->st);
   }
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->ev[1]);
   B->lin_pending = true;
   B->tm.n_linearizations++;
@@ -1606,12 +1550,12 @@ static std::atomic<int> g_comm_handles{0};
 int collect_solve_times(cs_ba* B) {
   if (!B->stage_timing) { B->lin_pending = false; return CS_OK; }
   float ms = 0;
-  BA_TRY(hipEventElapsedTime(&ms, B->ev[2], B->ev[3])); B->tm.reduce_ms += ms;
-  BA_TRY(hipEventElapsedTime(&ms, B->ev[3], B->ev[4])); B->tm.factor_ms += ms;
-  BA_TRY(hipEventElapsedTime(&ms, B->ev[4], B->ev[5])); B->tm.backsub_ms += ms;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[2], B->ev[3])); B->tm.reduce_ms += ms;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[3], B->ev[4])); B->tm.factor_ms += ms;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[4], B->ev[5])); B->tm.backsub_ms += ms;
   if (B->sep_mode && B->shard_n > 1) {
     hipEvent_t seq[6] = {B->ev[3], B->sev[0], B->sev[1], B->sev[2], B->sev[3], B->ev[4]};
-    for (int i = 0; i < 5; i++) { BA_TRY(hipEventElapsedTime(&ms, seq[i], seq[i + 1])); B->sep_ms[i] += ms; }
+    for (int i = 0; i < 5; i++) { CS_HIP_TRY(hipEventElapsedTime(&ms, seq[i], seq[i + 1])); B->sep_ms[i] += ms; }
   }
   return collect_lin_time(B);
 }
@@ -1623,8 +1567,8 @@ int share_cuboid_increments(cs_ba* B, cs_allreduce_fn fn, void* ctx) {
   double* xo = B->view.rhs + B->n_red;
   const size_t n = (size_t)(B->n_pose - B->n_red);
   if (fn) {
-    BA_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, xo, n, 1, 0) != 0) { cs_set_error_ba("all-reduce callback failed"); return CS_ERR_HIP; }
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
+    if (fn(ctx, xo, n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
   } else if (B->comm) {
     BA_NCCL(ncclAllReduce(xo, xo, n, ncclDouble, ncclSum, B->comm, B->st));
   }
@@ -1638,7 +1582,7 @@ int share_cuboid_increments(cs_ba* B, cs_allreduce_fn fn, void* ctx) {
 int put_lambda(cs_ba* B, double lambda) {
   B->h_lam[0] = lambda;
   B->h_lam[1] = B->shard_rank == 0 ? lambda : 0.0;      // x^T (lambda x + b): the poses' lambda x^2 is counted once, on rank 0
-  BA_TRY(hipMemcpyAsync(B->d_lam.p, B->h_lam, 2 * sizeof(double), hipMemcpyHostToDevice, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->d_lam.p, B->h_lam, 2 * sizeof(double), hipMemcpyHostToDevice, B->st));
   return CS_OK;
 }
 int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void* ctx, std::unique_lock<std::mutex>* defer);
@@ -1672,23 +1616,23 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
     } else if (B->sparse && B->sp_S_clean) {
       // (sparse path: S was cleared by the structure phase and only the plan's pattern is ever written -- the pattern and the right-hand side)
       cs::launch_sparse_zero_pattern(sparse_view(B), B->S.p, B->st);
-      BA_TRY(hipMemsetAsync(B->S.p + B->s_doubles, 0, sizeof(double) * B->n_pose, B->st));
+      CS_HIP_TRY(hipMemsetAsync(B->S.p + B->s_doubles, 0, sizeof(double) * B->n_pose, B->st));
     } else {
-      BA_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
+      CS_HIP_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
       B->sp_S_clean = B->sparse;
     }
-    if (!lean_head) BA_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
+    if (!lean_head) CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
     cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join, pro_in_reduce ? &side_pro : nullptr);
     if (B->ext_n > 0 && B->ext_terms_set) cs::ba_launch_ext_offdiag(B->view, B->ext_groups, B->d_ext_gptr.p, B->d_ext_order.p, B->d_ext_e4.p, B->ext_Hij.p, B->st);
     // (block cyclic reduction in a deferred trial: no kernel of it waits for another -- no time-out word to read --, and the two failure words
     // reach the host folded into the trial's scalars by the caller's sum kernel: the two 4-byte copies, a blit launch each, stay away)
     const bool status_in_scalars = defer != nullptr && B->band_ld > 0 && B->use_bcr;
     if (status_in_scalars) { B->h_status[0] = 0; B->h_status[1] = 0; }
-    else BA_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-    BA_TRY(hipGetLastError());
+    else CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+    CS_HIP_TRY(hipGetLastError());
     if (fn && B->shard_n > 1) {  // sum the ranks' partial reduced systems: [S | rhs] in one message
-      BA_TRY(hipStreamSynchronize(B->st));
-      if (fn(ctx, B->S.p, B->s_doubles + B->n_pose, 1, 0) != 0) { cs_set_error_ba("all-reduce callback failed"); return CS_ERR_HIP; }
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
+      if (fn(ctx, B->S.p, B->s_doubles + B->n_pose, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
     } else if (!fn && B->comm) {  // RCCL, queued on this stream behind the kernels that produced the partial system: no host round trip
       BA_NCCL(ncclAllReduce(B->S.p, B->S.p, B->s_doubles + B->n_pose, ncclDouble, ncclSum, B->comm, B->st));
     }
@@ -1700,66 +1644,66 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
       std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
       if (B->use_bcr) cs::ba_launch_bcr(B->S.p, B->band_linv.p, n, B->band_ld, 128, B->view.rhs, B->d_band_info.p, B->st);
       else cs::ba_launch_band_cholesky(B->S.p, B->band_linv.p, n, B->band_ld, B->view.rhs, B->d_band_info.p, true, B->st);
-      BA_TRY(hipGetLastError());
+      CS_HIP_TRY(hipGetLastError());
       BA_MARK(B, B->ev[4]);
       // (Round 5 tried clearing the band for the NEXT trial on the side stream here -- block cyclic reduction is done with it after its first
       // level -- to take the 10 us fill off the head of a trial: the event record / wait / fill / record sequence stalled the host's enqueue of the
       // kernels behind it by 35-60 us each, profiles/r5_ba_timeline_prezero.txt; the fill stays at the head.)
       cs::ba_launch_backsub(B->view, B->st);
-      BA_TRY(hipGetLastError());
+      CS_HIP_TRY(hipGetLastError());
       if (fn && B->elim && B->shard_n > 1) {   // the callback waits for the other ranks: the persistent kernel's turn must be free by then
-        BA_TRY(hipStreamSynchronize(B->st));
+        CS_HIP_TRY(hipStreamSynchronize(B->st));
         coop_turn.unlock();
       }
       { int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
       BA_MARK(B, B->ev[5]);
-      if (!status_in_scalars) BA_TRY(hipMemcpyAsync(B->h_status, B->d_band_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+      if (!status_in_scalars) CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_band_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
       if (defer) { *defer = std::move(coop_turn); B->tm.n_solves++; return CS_OK; }   // (the caller's sum kernel folds the two status words into the trial's scalars)
       cs::ba_launch_fail_flag(B->d_band_info.p, B->d_elim_fail.p, nullptr, B->d_scalars.p + 2, B->st);
-      BA_TRY(hipStreamSynchronize(B->st));
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
       if (*B->h_status == 0x7fffffff) {   // a workgroup waited ~1 s for its team: the device is shared with another persistent kernel
-        cs_set_error_ba("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device");
+        cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device");
         return CS_ERR_HIP;
       }
       if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
     } else if (B->sparse) {
       // general sparse: the pattern's blocks are gathered from the dense S by the factorisation itself (sparse_kernels.hip)
       std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-      BA_TRY(hipMemsetAsync(B->sp_info.p, 0, 2 * sizeof(int), B->st));
+      CS_HIP_TRY(hipMemsetAsync(B->sp_info.p, 0, 2 * sizeof(int), B->st));
       const cs::SparseView SV = sparse_view(B);
-      if (!cs::launch_sparse_cholesky(SV, cs::sparse_max_panel_doubles(), B->sp_grids, B->st)) { cs_set_error_ba("sparse solver: the factorisation could not be launched (grid " + std::to_string(B->sp_grids.chol) + " for " + std::to_string(SV.N) + " vertices)"); return CS_ERR_HIP; }
-      BA_TRY(hipMemsetAsync(B->d_info.p, 0, sizeof(int), B->st));
+      if (!cs::launch_sparse_cholesky(SV, cs::sparse_max_panel_doubles(), B->sp_grids, B->st)) { cs_set_error("sparse solver: the factorisation could not be launched (grid " + std::to_string(B->sp_grids.chol) + " for " + std::to_string(SV.N) + " vertices)"); return CS_ERR_HIP; }
+      CS_HIP_TRY(hipMemsetAsync(B->d_info.p, 0, sizeof(int), B->st));
       if (SV.n_tail > 0) {   // the top of the elimination tree as one dense block (same storage convention as the dense path's S)
         BA_ROC(rocsolver_dpotrf(B->blas, rocblas_fill_upper, SV.n_tail, SV.T, SV.n_tail, B->d_info.p));
         BA_ROC(rocsolver_dpotrs(B->blas, rocblas_fill_upper, SV.n_tail, 1, SV.T, SV.n_tail, SV.rhs_t, SV.n_tail));
       }
-      if (!cs::launch_sparse_backsolve(SV, B->sp_grids, B->st)) { cs_set_error_ba("sparse solver: the substitution could not be launched (grid " + std::to_string(B->sp_grids.back) + " for " + std::to_string(SV.N) + " vertices)"); return CS_ERR_HIP; }
+      if (!cs::launch_sparse_backsolve(SV, B->sp_grids, B->st)) { cs_set_error("sparse solver: the substitution could not be launched (grid " + std::to_string(B->sp_grids.back) + " for " + std::to_string(SV.N) + " vertices)"); return CS_ERR_HIP; }
       BA_MARK(B, B->ev[4]);
       cs::ba_launch_backsub(B->view, B->st);
-      BA_TRY(hipGetLastError());
+      CS_HIP_TRY(hipGetLastError());
       { int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
       BA_MARK(B, B->ev[5]);
-      BA_TRY(hipMemcpyAsync(B->h_status, B->sp_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-      BA_TRY(hipMemcpyAsync(B->h_status + 2, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-      BA_TRY(hipStreamSynchronize(B->st));
+      CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->sp_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+      CS_HIP_TRY(hipMemcpyAsync(B->h_status + 2, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
       if (B->h_status[2] != 0 && B->h_status[0] == 0) B->h_status[0] = B->h_status[2];     // (the dense tail's pivot)
       if (*B->h_status == 0x7fffffff) {
-        cs_set_error_ba("sparse solver: grid not co-resident (wait timed out); set CS_BA_SPARSE=0 on a shared device");
+        cs_set_error("sparse solver: grid not co-resident (wait timed out); set CS_BA_SPARSE=0 on a shared device");
         return CS_ERR_HIP;
       }
       if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
     } else {
       // dense: the lower triangle of the row-major S is the upper triangle of the column-major matrix rocSOLVER sees
       BA_ROC(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, B->S.p, n, B->d_info.p));
-      BA_TRY(hipMemcpyAsync(B->h_status, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-      BA_TRY(hipStreamSynchronize(B->st));
+      CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
       if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
       else BA_ROC(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, 1, B->S.p, n, B->view.rhs, n));
       BA_MARK(B, B->ev[4]);
       // (sharded: the collective is issued whether or not THIS rank's factorisation went through -- the ranks decide together, below)
-      if (*ok || B->shard_n > 1) { cs::ba_launch_backsub(B->view, B->st); BA_TRY(hipGetLastError()); int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
+      if (*ok || B->shard_n > 1) { cs::ba_launch_backsub(B->view, B->st); CS_HIP_TRY(hipGetLastError()); int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
       BA_MARK(B, B->ev[5]);
-      BA_TRY(hipStreamSynchronize(B->st));
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
     }
     int rc = collect_solve_times(B); if (rc) return rc;
   }
@@ -1772,8 +1716,8 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
 // host-synchronous: the stream is drained first)
 int coll_allreduce(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* d, size_t n) {
   if (fn) {
-    BA_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, d, n, 1, 0) != 0) { cs_set_error_ba("all-reduce callback failed"); return CS_ERR_HIP; }
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
+    if (fn(ctx, d, n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
   } else if (B->comm) {
     BA_NCCL(ncclAllReduce(d, d, n, ncclDouble, ncclSum, B->comm, B->st));
   }
@@ -1783,8 +1727,8 @@ int coll_allreduce(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* d, size_t n)
 // (the caller zeroes the other ranks' slots first).
 int coll_allgather(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* buf, size_t per_rank) {
   if (fn) {
-    BA_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, buf, per_rank * (size_t)B->shard_n, 1, 0) != 0) { cs_set_error_ba("all-reduce callback failed"); return CS_ERR_HIP; }
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
+    if (fn(ctx, buf, per_rank * (size_t)B->shard_n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
   } else if (B->comm) {
     BA_NCCL(ncclAllGather(buf + (size_t)B->shard_rank * per_rank, buf, per_rank, ncclDouble, B->comm, B->st));
   }
@@ -1801,32 +1745,32 @@ int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void
   // Without a collective the separator system would be assembled from the other ranks' stale / zero messages and "solve" to a
   // meaningless x that reports positive_definite = 1 (the low-level path cs_ba_solve -> solve_device has neither callback nor, possibly,
   // a communicator).  A sharded handle solves only through cs_ba_optimize_sharded or after cs_ba_comm_init.
-  if (!fn && !B->comm) { cs_set_error_ba("sharded handle in separator mode: the damped solve needs the ranks' separator messages -- use cs_ba_optimize_sharded (callback) or cs_ba_comm_init (RCCL); cs_ba_solve alone cannot"); return CS_ERR_INVALID_ARG; }
+  if (!fn && !B->comm) { cs_set_error("sharded handle in separator mode: the damped solve needs the ranks' separator messages -- use cs_ba_optimize_sharded (callback) or cs_ba_comm_init (RCCL); cs_ba_solve alone cannot"); return CS_ERR_INVALID_ARG; }
   const int R = B->shard_n, LD = B->band_ld, ns = B->n_sep;
   double* rhs = B->view.rhs;
   const int LDs = 2 * B->w_max;
   double* rsep = B->sepS.p + (size_t)ns * LDs;
   { int rcl = put_lambda(B, lambda); if (rcl) return rcl; }
   BA_MARK(B, B->ev[2]);
-  BA_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
-  BA_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
-  if (fn) BA_TRY(hipMemsetAsync(B->sep_msgs.p, 0, sizeof(double) * B->msg_doubles * (size_t)R, B->st));
+  CS_HIP_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
+  CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
+  if (fn) CS_HIP_TRY(hipMemsetAsync(B->sep_msgs.p, 0, sizeof(double) * B->msg_doubles * (size_t)R, B->st));
   cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join);
-  BA_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->ev[3]);
   std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-  BA_TRY(hipMemsetAsync(B->d_int_info.p, 0, 24 * sizeof(int), B->st));
+  CS_HIP_TRY(hipMemsetAsync(B->d_int_info.p, 0, 24 * sizeof(int), B->st));
   // the interior: L L^T = S(I, I), y = L^-1 b_I in place (one-sided order, right-hand side riding along)
   cs::ba_launch_band_cholesky(B->S.p + (size_t)B->int_c * LD, B->int_work.p, B->int_n, LD, rhs + B->int_c, B->d_int_info.p, false, B->st, true);
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->sev[0]);
   if (fn) {   // the callback waits for the other ranks (threads of this process in the tests): the persistent kernel's turn must be free by then
-    BA_TRY(hipStreamSynchronize(B->st));
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
     coop_turn.unlock();
   }
   cs::ba_launch_sep_reduce(B->S.p, LD, B->int_work.p, B->int_c, B->int_n, B->zl, B->wl, B->zr, B->wr, B->sepY.p, rhs, B->sep_msgs.p + (size_t)B->shard_rank * B->msg_doubles, B->w_max, B->st);
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->sev[1]);
   { int rc = coll_allgather(B, fn, ctx, B->sep_msgs.p, B->msg_doubles); if (rc) return rc; }
   BA_MARK(B, B->sev[2]);
@@ -1834,46 +1778,46 @@ int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void
   // 2 w_max: the persistent banded Cholesky again (two fronts at 7 separators: 18 dependent steps)
   if (cs::ba_bcr_sep_ok(B->w_max, R)) {
     // ... by block cyclic reduction, straight from the messages' blocks (bcr_kernels.hip): 7 separators = 3 levels instead of 18 dependent steps
-    BA_TRY(hipMemsetAsync(B->d_sep_info.p, 0, 24 * sizeof(int), B->st));
+    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, 24 * sizeof(int), B->st));
     cs::ba_launch_bcr_sep(B->sep_msgs.p, B->msg_doubles, B->w_max, R, B->d_sep_off.p, B->d_sep_col.p, ns, B->sep_work.p, rhs, B->d_sep_info.p, B->st);
-    BA_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
   } else {
     cs::ba_launch_sep_assemble(B->sep_msgs.p, B->msg_doubles, B->w_max, R, B->d_sep_off.p, ns, LDs, B->sepS.p, rsep, B->st);
-    BA_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
     if (!coop_turn.owns_lock()) coop_turn.lock();
-    BA_TRY(hipMemsetAsync(B->d_sep_info.p, 0, 24 * sizeof(int), B->st));
+    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, 24 * sizeof(int), B->st));
     cs::ba_launch_band_cholesky(B->sepS.p, B->sep_work.p, ns, LDs, rsep, B->d_sep_info.p, true, B->st);
-    BA_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
     if (fn) {
-      BA_TRY(hipStreamSynchronize(B->st));
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
       coop_turn.unlock();
     }
     cs::ba_launch_sep_scatter(rsep, ns, R, B->d_sep_off.p, B->d_sep_col.p, rhs, B->st);
   }
   BA_MARK(B, B->sev[3]);
   cs::ba_launch_sep_backsolve(B->S.p, LD, B->int_work.p, B->int_c, B->int_n, B->zl, B->wl, B->zr, B->wr, B->sepY.p, rhs, B->d_int_info.p, B->st);
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->ev[4]);
   cs::ba_launch_backsub(B->view, B->st);   // this rank's landmarks and cuboids see its own columns and the next separator only
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   // the solution vector: every rank contributes ITS columns (its separator as it solved it, its interior) and its cuboids' increments
   // behind the reduced system, zeros elsewhere -- every entry then has one source, so all ranks end with the same bits
-  if (B->zl > 0) BA_TRY(hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)B->zl, B->st));
-  if (B->int_c + B->int_n < B->n_red) BA_TRY(hipMemsetAsync(rhs + B->int_c + B->int_n, 0, sizeof(double) * (size_t)(B->n_red - B->int_c - B->int_n), B->st));
+  if (B->zl > 0) CS_HIP_TRY(hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)B->zl, B->st));
+  if (B->int_c + B->int_n < B->n_red) CS_HIP_TRY(hipMemsetAsync(rhs + B->int_c + B->int_n, 0, sizeof(double) * (size_t)(B->n_red - B->int_c - B->int_n), B->st));
   { int rc = coll_allreduce(B, fn, ctx, rhs, (size_t)B->n_pose); if (rc) return rc; }
   BA_MARK(B, B->ev[5]);
   cs::ba_launch_fail_flag(B->d_int_info.p, B->d_elim_fail.p, B->d_sep_info.p, B->d_scalars.p + 2, B->st);
   // both persistent factorisations of the trial report their own time-out (a team that was not co-resident): the interior's and the
   // separator system's -- the latter must not be mistaken for "not positive definite" (LM would raise lambda and retry, ~1 s a trial)
-  BA_TRY(hipMemcpyAsync(B->h_status, B->d_int_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipMemcpyAsync(B->h_status + 2, B->d_sep_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_int_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status + 2, B->d_sep_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipGetLastError());
   B->tm.n_solves++;
   if (defer) { if (coop_turn.owns_lock()) *defer = std::move(coop_turn); return CS_OK; }
-  BA_TRY(hipMemcpyAsync(B->h_scalars + 2, B->d_scalars.p + 2, sizeof(double), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_scalars + 2, B->d_scalars.p + 2, sizeof(double), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (coop_turn.owns_lock()) coop_turn.unlock();
-  if (B->h_status[0] == 0x7fffffff || B->h_status[2] == 0x7fffffff) { cs_set_error_ba("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
+  if (B->h_status[0] == 0x7fffffff || B->h_status[2] == 0x7fffffff) { cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
   if (B->h_scalars[2] != 0.0) *ok = false;
   return collect_solve_times(B);
 }
@@ -1886,36 +1830,36 @@ int cs_ba_create(int device, cs_ba** out) {
   if (!out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error_ba("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { cs_set_error_ba("device index out of range"); return CS_ERR_INVALID_ARG; }
-  BA_GUARD_BEGIN
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
+  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
+  CS_GUARD_BEGIN
   struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{new cs_ba()};   // freed on every early return
   cs_ba* B = g.b;
   B->device = device;
   { const char* e = getenv("CS_BA_FORCE_DENSE"); B->force_dense = (e && atoi(e)) ? 1 : 0; }  // diagnostics: rocSOLVER dense path
-  BA_TRY(hipSetDevice(device));
-  BA_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
-  BA_TRY(hipStreamCreateWithFlags(&B->st2, hipStreamNonBlocking));   // (a high-priority side stream was measured in round 5: no effect on the kernels that run beside a device-filling one)
-  BA_TRY(hipEventCreateWithFlags(&B->ev_fork, hipEventDisableTiming));
-  BA_TRY(hipEventCreateWithFlags(&B->ev_join, hipEventDisableTiming));
-  BA_TRY(hipStreamCreateWithFlags(&B->st3, hipStreamNonBlocking));
-  BA_TRY(hipEventCreateWithFlags(&B->ev_join3, hipEventDisableTiming));
-  BA_TRY(hipEventCreateWithFlags(&B->ev_upd, hipEventDisableTiming));
-  for (auto& e : B->ev) BA_TRY(hipEventCreate(&e));
-  for (auto& e : B->sev) BA_TRY(hipEventCreate(&e));
-  BA_TRY(hipHostMalloc((void**)&B->h_lam, 2 * sizeof(double)));
+  CS_HIP_TRY(hipSetDevice(device));
+  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
+  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st2, hipStreamNonBlocking));   // (a high-priority side stream was measured in round 5: no effect on the kernels that run beside a device-filling one)
+  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_fork, hipEventDisableTiming));
+  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_join, hipEventDisableTiming));
+  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st3, hipStreamNonBlocking));
+  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_join3, hipEventDisableTiming));
+  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_upd, hipEventDisableTiming));
+  for (auto& e : B->ev) CS_HIP_TRY(hipEventCreate(&e));
+  for (auto& e : B->sev) CS_HIP_TRY(hipEventCreate(&e));
+  CS_HIP_TRY(hipHostMalloc((void**)&B->h_lam, 2 * sizeof(double)));
   B->h_lam[0] = B->h_lam[1] = 0.0;
   { int rc0 = B->d_lam.alloc(2); if (rc0) return rc0; }
-  BA_TRY(hipHostMalloc((void**)&B->h_trial, 8 * sizeof(double)));
+  CS_HIP_TRY(hipHostMalloc((void**)&B->h_trial, 8 * sizeof(double)));
   for (int i = 0; i < 8; i++) B->h_trial[i] = 0.0;
-  BA_TRY(hipHostMalloc((void**)&B->h_status, 3 * sizeof(int)));   // [factorisation status, a cuboid block failed, separator system's status]
+  CS_HIP_TRY(hipHostMalloc((void**)&B->h_status, 3 * sizeof(int)));   // [factorisation status, a cuboid block failed, separator system's status]
   B->h_status[0] = B->h_status[1] = B->h_status[2] = 0;
   BA_ROC(rocblas_create_handle(&B->blas));
   BA_ROC(rocblas_set_stream(B->blas, B->st));
   *out = B;
   g.b = nullptr;
   return CS_OK;
-  BA_GUARD_END("cs_ba_create")
+  CS_GUARD_END("cs_ba_create")
 }
 
 void cs_ba_destroy(cs_ba* B) {
@@ -1959,8 +1903,8 @@ void cs_ba_destroy(cs_ba* B) {
 static int cs_ba_set_vertices_impl(cs_ba* B, const double* cams7, const int* cam_fixed, int nc, const double* cuboids10, const int* cub_fixed, int no,
                        const double* points3, const int* pt_fixed, int np, int cuboids_first) {
   if (!B || nc < 0 || no < 0 || np < 0 || (nc && (!cams7 || !cam_fixed)) || (no && (!cuboids10 || !cub_fixed)) || (np && (!points3 || !pt_fixed))) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way: cs_ba_append_* queues them on st)
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way: cs_ba_append_* queues them on st)
   B->nc = nc; B->no = no; B->np = np; B->cuboids_first = cuboids_first;
   proj_edge_lists_invalidate(B);
   B->cam_fixed.assign(cam_fixed, cam_fixed + nc); B->cub_fixed.assign(cub_fixed, cub_fixed + no); B->pt_fixed.assign(pt_fixed, pt_fixed + np);
@@ -1975,9 +1919,9 @@ static int cs_ba_set_vertices_impl(cs_ba* B, const double* cams7, const int* cam
 }
 int cs_ba_set_vertices(cs_ba* B, const double* cams7, const int* cam_fixed, int nc, const double* cuboids10, const int* cub_fixed, int no,
                        const double* points3, const int* pt_fixed, int np, int cuboids_first) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_vertices_impl(B, cams7, cam_fixed, nc, cuboids10, cub_fixed, no, points3, pt_fixed, np, cuboids_first);
-  BA_GUARD_END("cs_ba_set_vertices")
+  CS_GUARD_END("cs_ba_set_vertices")
 }
 
 // ---- growing graphs (the reference's pattern: main_obj.cpp:802-803 adds a frame and calls optimize(5); g2o's seam is
@@ -1992,8 +1936,8 @@ static int append_arena(cs_ba* B) {
 static int cs_ba_append_vertices_impl(cs_ba* B, const double* cams7, const int* cam_fixed, int n_cams, const double* cuboids10, const int* cub_fixed, int n_cub,
                                       const double* points3, const int* pt_fixed, int n_pts) {
   if (!B || n_cams < 0 || n_cub < 0 || n_pts < 0 || (n_cams && (!cams7 || !cam_fixed)) || (n_cub && (!cuboids10 || !cub_fixed)) || (n_pts && (!points3 || !pt_fixed))) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   std::vector<double> c(cams7, cams7 + 7 * (size_t)n_cams);
   for (int i = 0; i < n_cams; i++) { cs::Pose p = cs::pose_load(&c[7 * (size_t)i]); cs::pose_normalize(p); cs::pose_store(p, &c[7 * (size_t)i]); }
   int rc;
@@ -2009,9 +1953,9 @@ static int cs_ba_append_vertices_impl(cs_ba* B, const double* cams7, const int* 
 }
 int cs_ba_append_vertices(cs_ba* B, const double* cams7, const int* cam_fixed, int n_cams, const double* cuboids10, const int* cub_fixed, int n_cub,
                           const double* points3, const int* pt_fixed, int n_pts) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_append_vertices_impl(B, cams7, cam_fixed, n_cams, cuboids10, cub_fixed, n_cub, points3, pt_fixed, n_pts);
-  BA_GUARD_END("cs_ba_append_vertices")
+  CS_GUARD_END("cs_ba_append_vertices")
 }
 // are the n new records all equal to the handle's reference record (the first record ever set)?  A few threads over the caller's arrays.
 static void scan_uniform_records(cs_ba* B, bool first, const double* info4, const double* intr4, int n) {
@@ -2041,11 +1985,11 @@ static void scan_uniform_records(cs_ba* B, bool first, const double* info4, cons
 }
 int cs_ba_append_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
   if (!B || n < 0 || (n && (!pt || !cam || !uv || !info4 || !intr4))) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   if (n == 0) return CS_OK;
-  if (B->n_proj > 0 && (huber != nullptr) != B->have_huber) { cs_set_error_ba("cs_ba_append_edges_proj: Huber deltas must be given for all projection edges or for none"); return CS_ERR_INVALID_ARG; }
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
+  if (B->n_proj > 0 && (huber != nullptr) != B->have_huber) { cs_set_error("cs_ba_append_edges_proj: Huber deltas must be given for all projection edges or for none"); return CS_ERR_INVALID_ARG; }
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   int rc;
   const bool first_edges = B->n_proj == 0;
   scan_uniform_records(B, first_edges, info4, intr4, n);
@@ -2055,7 +1999,7 @@ int cs_ba_append_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, cons
     int r = raw.reserve(4 * (size_t)(B->n_proj + n));
     if (r) return r;
     cs::ba_launch_fill_rows4(raw.p, rec4, B->n_proj, B->st);
-    BA_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
     raw.n = 4 * (size_t)B->n_proj;
     is_virtual = false;
     return CS_OK;
@@ -2073,32 +2017,32 @@ int cs_ba_append_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, cons
   B->n_proj += n;
   B->structure_dirty = true;
   return CS_OK;
-  BA_GUARD_END("cs_ba_append_edges_proj")
+  CS_GUARD_END("cs_ba_append_edges_proj")
 }
 int cs_ba_append_edges_cuboid(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
   if (!B || n < 0 || (n && (!cam || !cub || !meas10 || !info81))) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   B->u3_cam.insert(B->u3_cam.end(), cam, cam + n); B->u3_cub.insert(B->u3_cub.end(), cub, cub + n);
   if (!B->rk_cub3.empty()) { B->rk_cub3.resize(B->u3_cam.size(), 0); B->rd_cub3.resize(B->u3_cam.size(), 0.0); }
   B->h_ce_meas.insert(B->h_ce_meas.end(), meas10, meas10 + 10 * (size_t)n); B->h_ce_info.insert(B->h_ce_info.end(), info81, info81 + 81 * (size_t)n);
   B->structure_dirty = true;
   return CS_OK;
-  BA_GUARD_END("cs_ba_append_edges_cuboid")
+  CS_GUARD_END("cs_ba_append_edges_cuboid")
 }
 int cs_ba_append_edges_cuboid_proj(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
   if (!B || n < 0 || (n && (!cam || !cub || !meas4 || !info16 || !K9))) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   B->up_cam.insert(B->up_cam.end(), cam, cam + n); B->up_cub.insert(B->up_cub.end(), cub, cub + n);
   if (!B->rk_cproj.empty()) { B->rk_cproj.resize(B->up_cam.size(), 0); B->rd_cproj.resize(B->up_cam.size(), 0.0); }
   B->h_pe_meas.insert(B->h_pe_meas.end(), meas4, meas4 + 4 * (size_t)n); B->h_pe_info.insert(B->h_pe_info.end(), info16, info16 + 16 * (size_t)n);
   B->h_pe_K.insert(B->h_pe_K.end(), K9, K9 + 9 * (size_t)n);
   B->structure_dirty = true;
   return CS_OK;
-  BA_GUARD_END("cs_ba_append_edges_cuboid_proj")
+  CS_GUARD_END("cs_ba_append_edges_cuboid_proj")
 }
 int cs_ba_append_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const double* meas7, const double* info36) {
   if (!B || n < 0 || (n && (!ci || !cj || !meas7 || !info36))) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   B->oe_i.insert(B->oe_i.end(), ci, ci + n); B->oe_j.insert(B->oe_j.end(), cj, cj + n);
   const size_t m0 = B->h_oe_meas.size();
   B->h_oe_meas.insert(B->h_oe_meas.end(), meas7, meas7 + 7 * (size_t)n);
@@ -2108,27 +2052,27 @@ int cs_ba_append_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const
   if (!B->rk_odom.empty()) { B->rk_odom.resize(B->n_odom, 0); B->rd_odom.resize(B->n_odom, 0.0); }
   B->structure_dirty = true;
   return CS_OK;
-  BA_GUARD_END("cs_ba_append_edges_odom")
+  CS_GUARD_END("cs_ba_append_edges_odom")
 }
 
 static int cs_ba_set_estimates_impl(cs_ba* B, const double* cams7, const double* cuboids10, const double* points3) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
   if (cams7 && B->nc) {
     std::vector<double> c(cams7, cams7 + 7 * (size_t)B->nc);
     for (int i = 0; i < B->nc; i++) { cs::Pose p = cs::pose_load(&c[7 * (size_t)i]); cs::pose_normalize(p); cs::pose_store(p, &c[7 * (size_t)i]); }
-    BA_TRY(hipMemcpy(B->cams.p, c.data(), 56 * (size_t)B->nc, hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(B->cams.p, c.data(), 56 * (size_t)B->nc, hipMemcpyHostToDevice));
   }
-  if (cuboids10 && B->no) BA_TRY(hipMemcpy(B->cubes.p, cuboids10, 80 * (size_t)B->no, hipMemcpyHostToDevice));
-  if (points3 && B->np) BA_TRY(hipMemcpy(B->points.p, points3, 24 * (size_t)B->np, hipMemcpyHostToDevice));
+  if (cuboids10 && B->no) CS_HIP_TRY(hipMemcpy(B->cubes.p, cuboids10, 80 * (size_t)B->no, hipMemcpyHostToDevice));
+  if (points3 && B->np) CS_HIP_TRY(hipMemcpy(B->points.p, points3, 24 * (size_t)B->np, hipMemcpyHostToDevice));
   B->have_system = false;
   return CS_OK;
 }
 int cs_ba_set_estimates(cs_ba* B, const double* cams7, const double* cuboids10, const double* points3) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_estimates_impl(B, cams7, cuboids10, points3);
-  BA_GUARD_END("cs_ba_set_estimates")
+  CS_GUARD_END("cs_ba_set_estimates")
 }
 
 static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
@@ -2136,8 +2080,8 @@ static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* 
   B->n_proj = n;
   proj_edge_lists_invalidate(B);
   B->e_pt.assign(pt, pt + n); B->e_cam.assign(cam, cam + n);
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
   int rc;
   scan_uniform_records(B, true, info4, intr4, n);
   if ((rc = B->raw_uv.upload_ptr(uv, 2 * (size_t)n))) return rc;
@@ -2151,9 +2095,9 @@ static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* 
   return CS_OK;
 }
 int cs_ba_set_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_edges_proj_impl(B, n, pt, cam, uv, info4, intr4, huber);
-  BA_GUARD_END("cs_ba_set_edges_proj")
+  CS_GUARD_END("cs_ba_set_edges_proj")
 }
 
 static int cs_ba_set_edges_cuboid_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
@@ -2165,9 +2109,9 @@ static int cs_ba_set_edges_cuboid_impl(cs_ba* B, int n, const int* cam, const in
   return CS_OK;
 }
 int cs_ba_set_edges_cuboid(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_edges_cuboid_impl(B, n, cam, cub, meas10, info81);
-  BA_GUARD_END("cs_ba_set_edges_cuboid")
+  CS_GUARD_END("cs_ba_set_edges_cuboid")
 }
 
 static int cs_ba_set_edges_cuboid_proj_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
@@ -2179,9 +2123,9 @@ static int cs_ba_set_edges_cuboid_proj_impl(cs_ba* B, int n, const int* cam, con
   return CS_OK;
 }
 int cs_ba_set_edges_cuboid_proj(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_edges_cuboid_proj_impl(B, n, cam, cub, meas4, info16, K9);
-  BA_GUARD_END("cs_ba_set_edges_cuboid_proj")
+  CS_GUARD_END("cs_ba_set_edges_cuboid_proj")
 }
 
 static int cs_ba_set_edges_odom_impl(cs_ba* B, int n, const int* ci, const int* cj, const double* meas7, const double* info36) {
@@ -2196,9 +2140,9 @@ static int cs_ba_set_edges_odom_impl(cs_ba* B, int n, const int* ci, const int* 
   return CS_OK;
 }
 int cs_ba_set_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const double* meas7, const double* info36) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_edges_odom_impl(B, n, ci, cj, meas7, info36);
-  BA_GUARD_END("cs_ba_set_edges_odom")
+  CS_GUARD_END("cs_ba_set_edges_odom")
 }
 
 // ---- external (host-evaluated) edges: the CPU path for edge types the library does not evaluate.  The caller runs such an edge through
@@ -2206,30 +2150,30 @@ int cs_ba_set_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const do
 // base_unary_edge.hpp:42-123) -- and hands over what they accumulate.
 int cs_ba_set_external_edges(cs_ba* B, int n, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j) {
   if (!B || n < 0 || (n && (!class_i || !idx_i || !class_j || !idx_j))) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   // an edge whose two ends are the same vertex has no off-diagonal block (its whole quadratic form belongs to the vertex's diagonal terms,
   // cs_ba_set_external_terms' cam36 / cub81 / pt9): the off-diagonal kernel would address the upper triangle of a diagonal block
   for (int k = 0; k < n; k++)
-    if (class_i[k] == class_j[k] && idx_i[k] == idx_j[k]) { cs_set_error_ba("cs_ba_set_external_edges: edge " + std::to_string(k) + " joins a vertex to itself; add its terms to the vertex's diagonal block instead"); return CS_ERR_INVALID_ARG; }
+    if (class_i[k] == class_j[k] && idx_i[k] == idx_j[k]) { cs_set_error("cs_ba_set_external_edges: edge " + std::to_string(k) + " joins a vertex to itself; add its terms to the vertex's diagonal block instead"); return CS_ERR_INVALID_ARG; }
   B->ext_n = n;
   B->ext_e4.resize(4 * (size_t)n);
   for (int k = 0; k < n; k++) { B->ext_e4[4 * k] = class_i[k]; B->ext_e4[4 * k + 1] = idx_i[k]; B->ext_e4[4 * k + 2] = class_j[k]; B->ext_e4[4 * k + 3] = idx_j[k]; }
   B->ext_terms_set = false;
   B->structure_dirty = true;
   return CS_OK;
-  BA_GUARD_END("cs_ba_set_external_edges")
+  CS_GUARD_END("cs_ba_set_external_edges")
 }
 static int cs_ba_set_external_terms_impl(cs_ba* B, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3,
                                          const double* Hij81, double chi2) {
   if (!B || (cam36 && !cam6) || (cub81 && !cub9) || (pt9 && !pt3) || (B->ext_n > 0 && !Hij81)) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));     // the previous linearisation may still read the buffers
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));     // the previous linearisation may still read the buffers
   int rc;
   auto put = [&](DBuf<double>& d, const double* h, size_t n) -> int { return h ? d.upload_ptr(h, n) : d.alloc(n, B->st); };
   if ((rc = put(B->ext_cam36, cam36, 36 * (size_t)B->nc)) || (rc = put(B->ext_cam6, cam6, 6 * (size_t)B->nc)) || (rc = put(B->ext_cub81, cub81, 81 * (size_t)B->no)) ||
       (rc = put(B->ext_cub9, cub9, 9 * (size_t)B->no)) || (rc = put(B->ext_pt9, pt9, 9 * (size_t)B->np)) || (rc = put(B->ext_pt3, pt3, 3 * (size_t)B->np)) ||
       (rc = put(B->ext_Hij, Hij81, 81 * (size_t)B->ext_n))) return rc;
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   B->ext_has_cam = cam36 != nullptr; B->ext_has_cub = cub81 != nullptr; B->ext_has_pt = pt9 != nullptr;
   if (Hij81) B->h_ext_Hij.assign(Hij81, Hij81 + 81 * (size_t)B->ext_n); else B->h_ext_Hij.clear();
   B->ext_chi2 = chi2;
@@ -2239,13 +2183,13 @@ static int cs_ba_set_external_terms_impl(cs_ba* B, const double* cam36, const do
 }
 int cs_ba_set_external_terms(cs_ba* B, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3,
                              const double* Hij81, double chi2) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_external_terms_impl(B, cam36, cam6, cub81, cub9, pt9, pt3, Hij81, chi2);
-  BA_GUARD_END("cs_ba_set_external_terms")
+  CS_GUARD_END("cs_ba_set_external_terms")
 }
 int cs_ba_set_external_chi2(cs_ba* B, double chi2) {
   if (!B) return CS_ERR_INVALID_ARG;
-  if (!B->ext_terms_set) { cs_set_error_ba("cs_ba_set_external_chi2: call cs_ba_set_external_terms first"); return CS_ERR_NOT_RUN; }
+  if (!B->ext_terms_set) { cs_set_error("cs_ba_set_external_chi2: call cs_ba_set_external_terms first"); return CS_ERR_NOT_RUN; }
   B->ext_chi2 = chi2;
   return CS_OK;
 }
@@ -2261,18 +2205,18 @@ static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const 
   if (!B || n < 0 || (n && kind && !delta)) return CS_ERR_INVALID_ARG;
   const int have = edge_class == CS_EDGE_PROJ ? B->n_proj : edge_class == CS_EDGE_CUBOID ? (int)B->u3_cam.size() : edge_class == CS_EDGE_CUBOID_PROJ ? (int)B->up_cam.size()
                  : edge_class == CS_EDGE_ODOM ? B->n_odom : -1;
-  if (have < 0) { cs_set_error_ba("cs_ba_set_robust_kernels: unknown edge class"); return CS_ERR_INVALID_ARG; }
+  if (have < 0) { cs_set_error("cs_ba_set_robust_kernels: unknown edge class"); return CS_ERR_INVALID_ARG; }
   if (!kind) n = have;         // removing the class's kernels: the count is the library's own (n is ignored)
-  if (n != have) { cs_set_error_ba("cs_ba_set_robust_kernels: n must equal the number of edges of the class (set the edges first)"); return CS_ERR_INVALID_ARG; }
+  if (n != have) { cs_set_error("cs_ba_set_robust_kernels: n must equal the number of edges of the class (set the edges first)"); return CS_ERR_INVALID_ARG; }
   std::vector<int> kk(n, 0); std::vector<double> dd(n, 0.0);
   for (int k = 0; k < n && kind; k++) {
-    if (kind[k] < 0 || kind[k] >= cs::RK_KINDS) { cs_set_error_ba("cs_ba_set_robust_kernels: unknown kernel kind"); return CS_ERR_INVALID_ARG; }
-    if (kind[k] != cs::RK_NONE && !(delta[k] > 0)) { cs_set_error_ba("cs_ba_set_robust_kernels: a kernel needs delta > 0"); return CS_ERR_INVALID_ARG; }
+    if (kind[k] < 0 || kind[k] >= cs::RK_KINDS) { cs_set_error("cs_ba_set_robust_kernels: unknown kernel kind"); return CS_ERR_INVALID_ARG; }
+    if (kind[k] != cs::RK_NONE && !(delta[k] > 0)) { cs_set_error("cs_ba_set_robust_kernels: a kernel needs delta > 0"); return CS_ERR_INVALID_ARG; }
     kk[k] = kind[k]; dd[k] = kind[k] != cs::RK_NONE ? delta[k] : 0.0;
   }
   if (edge_class == CS_EDGE_PROJ) {
-    BA_TRY(hipSetDevice(B->device));
-    BA_TRY(hipStreamSynchronize(B->st));
+    CS_HIP_TRY(hipSetDevice(B->device));
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
     int rc = B->raw_huber.upload_ptr(dd.data(), (size_t)n); if (rc) return rc;    // delta per edge, 0 = none
     B->have_huber = true;
     B->rk_proj = kk;
@@ -2283,14 +2227,14 @@ static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const 
   return CS_OK;
 }
 int cs_ba_set_robust_kernels(cs_ba* B, int edge_class, int n, const int* kind, const double* delta) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_set_robust_kernels_impl(B, edge_class, n, kind, delta);
-  BA_GUARD_END("cs_ba_set_robust_kernels")
+  CS_GUARD_END("cs_ba_set_robust_kernels")
 }
 
 static int cs_ba_compute_errors_impl(cs_ba* B, double* chi2) {
   if (!B || !chi2) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
   double t0 = now_ms();
   rc = chi2_device(B, chi2);
@@ -2299,14 +2243,14 @@ static int cs_ba_compute_errors_impl(cs_ba* B, double* chi2) {
   return rc;
 }
 int cs_ba_compute_errors(cs_ba* B, double* chi2) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_compute_errors_impl(B, chi2);
-  BA_GUARD_END("cs_ba_compute_errors")
+  CS_GUARD_END("cs_ba_compute_errors")
 }
 
 static int cs_ba_build_system_impl(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
   rc = build_system_device(B); if (rc) return rc;
   rc = fetch_b(B); if (rc) return rc;
@@ -2314,15 +2258,15 @@ static int cs_ba_build_system_impl(cs_ba* B) {
   return CS_OK;
 }
 int cs_ba_build_system(cs_ba* B) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_build_system_impl(B);
-  BA_GUARD_END("cs_ba_build_system")
+  CS_GUARD_END("cs_ba_build_system")
 }
 
 static int cs_ba_solve_impl(cs_ba* B, double lambda, int* pd) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
-  if (B->structure_dirty || !B->have_system) { cs_set_error_ba("cs_ba_solve: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  CS_HIP_TRY(hipSetDevice(B->device));
+  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_solve: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
   bool ok = false;
   int rc = solve_device(B, lambda, &ok); if (rc) return rc;
   if (ok) debug_nan_scan(B, "after cs_ba_solve");
@@ -2330,48 +2274,48 @@ static int cs_ba_solve_impl(cs_ba* B, double lambda, int* pd) {
   return ok ? fetch_x(B) : CS_OK;
 }
 int cs_ba_solve(cs_ba* B, double lambda, int* pd) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_solve_impl(B, lambda, pd);
-  BA_GUARD_END("cs_ba_solve")
+  CS_GUARD_END("cs_ba_solve")
 }
 
 int cs_ba_update(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
-  if (B->structure_dirty || !B->have_system) { cs_set_error_ba("cs_ba_update: no solution to apply (call cs_ba_build_system and cs_ba_solve first)"); return CS_ERR_NOT_RUN; }
-  BA_TRY(hipSetDevice(B->device));
+  CS_GUARD_BEGIN
+  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_update: no solution to apply (call cs_ba_build_system and cs_ba_solve first)"); return CS_ERR_NOT_RUN; }
+  CS_HIP_TRY(hipSetDevice(B->device));
   double t0 = now_ms();
   cs::ba_launch_update(B->view, B->st);
-  BA_TRY(hipGetLastError());
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   B->tm.update_ms += now_ms() - t0;
   debug_nan_scan(B, "after cs_ba_update");
   return CS_OK;
-  BA_GUARD_END("cs_ba_update")
+  CS_GUARD_END("cs_ba_update")
 }
 
 int cs_ba_push(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
-  BA_TRY(hipSetDevice(B->device));
+  CS_GUARD_BEGIN
+  CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
-  if (B->nc) BA_TRY(hipMemcpyAsync(B->cams_bak.p, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
-  if (B->np) BA_TRY(hipMemcpyAsync(B->points_bak.p, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
-  if (B->no) BA_TRY(hipMemcpyAsync(B->cubes_bak.p, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
+  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams_bak.p, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
+  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points_bak.p, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
+  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes_bak.p, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
   return CS_OK;
-  BA_GUARD_END("cs_ba_push")
+  CS_GUARD_END("cs_ba_push")
 }
 
 int cs_ba_pop(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
-  if (B->structure_dirty) { cs_set_error_ba("cs_ba_pop: nothing was pushed since the graph changed"); return CS_ERR_NOT_RUN; }
-  BA_TRY(hipSetDevice(B->device));
-  if (B->nc) BA_TRY(hipMemcpyAsync(B->cams.p, B->cams_bak.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
-  if (B->np) BA_TRY(hipMemcpyAsync(B->points.p, B->points_bak.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
-  if (B->no) BA_TRY(hipMemcpyAsync(B->cubes.p, B->cubes_bak.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
+  CS_GUARD_BEGIN
+  if (B->structure_dirty) { cs_set_error("cs_ba_pop: nothing was pushed since the graph changed"); return CS_ERR_NOT_RUN; }
+  CS_HIP_TRY(hipSetDevice(B->device));
+  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams.p, B->cams_bak.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
+  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points.p, B->points_bak.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
+  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes.p, B->cubes_bak.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
   return CS_OK;
-  BA_GUARD_END("cs_ba_pop")
+  CS_GUARD_END("cs_ba_pop")
 }
 
 // optimization_algorithm_levenberg.cpp:61-163 + sparse_optimizer.cpp:354-419
@@ -2396,10 +2340,10 @@ int cs_ba_optimize(cs_ba* B, int iterations, int* iterations_done, double* chi_h
 
 static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap) {
   if (!B || iterations < 0) return CS_ERR_INVALID_ARG;
-  if (B->shard_n > 1 && !fn && !B->comm) { cs_set_error_ba("sharded problem needs cs_ba_comm_init() (RCCL) or an all-reduce callback"); return CS_ERR_INVALID_ARG; }
+  if (B->shard_n > 1 && !fn && !B->comm) { cs_set_error("sharded problem needs cs_ba_comm_init() (RCCL) or an all-reduce callback"); return CS_ERR_INVALID_ARG; }
   const bool cb = fn && B->shard_n > 1;          // collectives through the caller's callback (CPU / gloo tests, ranks as threads)
   const bool rccl = !fn && B->comm != nullptr;   // collectives issued here, on this handle's stream
-  BA_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
   // host scalars: sum / max over the ranks
   auto reduce_host = [&](double* v, size_t n, int op) -> int {
@@ -2425,19 +2369,19 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     const double q[5] = {(double)B->n_red, (double)B->band_ld, B->elim ? 1.0 : 0.0, B->sep_mode ? 1.0 : 0.0, (double)B->n_sep};
     double v[10];
     for (int i = 0; i < 5; i++) { v[i] = q[i]; v[5 + i] = -q[i]; }
-    if (reduce_host(v, 10, 1)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+    if (reduce_host(v, 10, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
     for (int i = 0; i < 5; i++)
-      if (v[i] != q[i] || v[5 + i] != -q[i]) { cs_set_error_ba("sharded BA: the ranks disagree on the solver layout (reduced size / bandwidth / cuboid elimination / separator mode); check CS_BA_* environment variables and devices"); return CS_ERR_INVALID_ARG; }
+      if (v[i] != q[i] || v[5 + i] != -q[i]) { cs_set_error("sharded BA: the ranks disagree on the solver layout (reduced size / bandwidth / cuboid elimination / separator mode); check CS_BA_* environment variables and devices"); return CS_ERR_INVALID_ARG; }
   }
   // external (host-evaluated) edges: their terms depend on the state, so the caller's callback re-evaluates them before every
   // linearisation (want_system = 1: cs_ba_set_external_terms) and after every trial's update (want_system = 0: cs_ba_set_external_chi2)
   const bool ext_active = B->ext_n > 0 || B->ext_terms_set || B->ext_fn;
-  if (ext_active && !B->ext_fn) { cs_set_error_ba("cs_ba_optimize: the graph has external (host-evaluated) edges but no cs_ba_set_external_callback; drive the stepwise calls instead"); return CS_ERR_NOT_RUN; }
+  if (ext_active && !B->ext_fn) { cs_set_error("cs_ba_optimize: the graph has external (host-evaluated) edges but no cs_ba_set_external_callback; drive the stepwise calls instead"); return CS_ERR_NOT_RUN; }
   auto ext_refresh = [&](int want_system) -> int {
     if (!ext_active) return CS_OK;
-    BA_TRY(hipStreamSynchronize(B->st));
-    if (B->ext_fn(B->ext_ctx, B, want_system) != 0) { cs_set_error_ba("external-edge callback failed"); return CS_ERR_INVALID_ARG; }
-    if (!B->ext_terms_set) { cs_set_error_ba("external-edge callback did not call cs_ba_set_external_terms"); return CS_ERR_NOT_RUN; }
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
+    if (B->ext_fn(B->ext_ctx, B, want_system) != 0) { cs_set_error("external-edge callback failed"); return CS_ERR_INVALID_ARG; }
+    if (!B->ext_terms_set) { cs_set_error("external-edge callback did not call cs_ba_set_external_terms"); return CS_ERR_NOT_RUN; }
     return CS_OK;
   };
   const bool fuse_lin_env = [] { const char* e = getenv("CS_BA_FUSE_LIN"); return !e || atoi(e) != 0; }();     // (read per call: the tests hold the two paths to each other in one process)
@@ -2460,8 +2404,8 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     unsigned spins = 0;
     while (h[3] != seq) {
       if ((++spins & 0xfffu) == 0 && now_ms() - t_w > 5000.0) {      // five seconds without the word: ask the runtime what happened
-        BA_TRY(hipStreamSynchronize(B->st));
-        if (h[3] != seq) { cs_set_error_ba("cs_ba_optimize: the trial's scalars never arrived in pinned memory"); return CS_ERR_HIP; }
+        CS_HIP_TRY(hipStreamSynchronize(B->st));
+        if (h[3] != seq) { cs_set_error("cs_ba_optimize: the trial's scalars never arrived in pinned memory"); return CS_ERR_HIP; }
         break;
       }
 #if defined(__x86_64__)
@@ -2487,7 +2431,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     } else {
       rc = chi2_device(B, &currentChi); if (rc) return rc;
       if (ext_active) currentChi += B->ext_chi2;
-      if (reduce_host(&currentChi, 1, 0)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+      if (reduce_host(&currentChi, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
       B->tm.errors_ms += now_ms() - t0;
     }
     double tempChi = currentChi, iniChi = currentChi;
@@ -2501,28 +2445,28 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     if (it == 0 && B->shard_n == 1) {  // computeLambdaInit (:166-180): tau * max |H_jj| over all non-fixed vertices, landmarks included
       // one rank: the maximum is taken where the blocks are (ba_max_diag_kernel) and eight bytes come back, instead of every H_cc / H_oo / H_ll
       // block (14 MB at C4, 0.6 ms of every cs_ba_optimize call)
-      BA_TRY(hipMemsetAsync(B->d_scalars.p, 0, sizeof(double), B->st));
+      CS_HIP_TRY(hipMemsetAsync(B->d_scalars.p, 0, sizeof(double), B->st));
       cs::ba_launch_max_diag(B->view, B->d_scalars.p, B->st);
-      BA_TRY(hipGetLastError());
-      BA_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, sizeof(double), hipMemcpyDeviceToHost, B->st));
-      BA_TRY(hipStreamSynchronize(B->st));
+      CS_HIP_TRY(hipGetLastError());
+      CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, sizeof(double), hipMemcpyDeviceToHost, B->st));
+      CS_HIP_TRY(hipStreamSynchronize(B->st));
       lambda = B->user_lambda_init > 0 ? B->user_lambda_init : 1e-5 * B->h_scalars[0];      // (:168-169: a user value wins)
       ni = 2; nBad = 0;
     } else if (it == 0) {
-      BA_TRY(hipStreamSynchronize(B->st));   // the copies below run on the NULL stream, which B->st does not order with
+      CS_HIP_TRY(hipStreamSynchronize(B->st));   // the copies below run on the NULL stream, which B->st does not order with
       std::vector<double> hc(36 * (size_t)B->nc), ho(81 * (size_t)B->no), hl(9 * (size_t)B->np);
-      if (B->nc) BA_TRY(hipMemcpy(hc.data(), B->Hcam.p, 8 * hc.size(), hipMemcpyDeviceToHost));
-      if (B->no) BA_TRY(hipMemcpy(ho.data(), B->Hcub.p, 8 * ho.size(), hipMemcpyDeviceToHost));
-      if (B->np) BA_TRY(hipMemcpy(hl.data(), B->Hll.p, 8 * hl.size(), hipMemcpyDeviceToHost));
+      if (B->nc) CS_HIP_TRY(hipMemcpy(hc.data(), B->Hcam.p, 8 * hc.size(), hipMemcpyDeviceToHost));
+      if (B->no) CS_HIP_TRY(hipMemcpy(ho.data(), B->Hcub.p, 8 * ho.size(), hipMemcpyDeviceToHost));
+      if (B->np) CS_HIP_TRY(hipMemcpy(hl.data(), B->Hll.p, 8 * hl.size(), hipMemcpyDeviceToHost));
       // pose diagonals are partial sums on every rank: sum them before taking the maximum
       std::vector<double> pd(std::max(1, B->n_pose), 0.0);
       for (int i = 0; i < B->nc; i++) if (B->cam_col[i] >= 0) for (int d = 0; d < 6; d++) pd[B->cam_col[i] + d] = hc[36 * (size_t)i + 7 * d];
       for (int i = 0; i < B->no; i++) if (B->cub_col[i] >= 0) for (int d = 0; d < 9; d++) pd[B->cub_col[i] + d] = ho[81 * (size_t)i + 10 * d];
-      if (reduce_host(pd.data(), pd.size(), 0)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+      if (reduce_host(pd.data(), pd.size(), 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
       double md = 0;
       for (int i = 0; i < B->n_pose; i++) md = std::max(std::fabs(pd[i]), md);
       for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) for (int d = 0; d < 3; d++) md = std::max(std::fabs(hl[9 * (size_t)i + 4 * d]), md);
-      if (reduce_host(&md, 1, 1)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+      if (reduce_host(&md, 1, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
       lambda = B->user_lambda_init > 0 ? B->user_lambda_init : 1e-5 * md;
       ni = 2; nBad = 0;
     }
@@ -2543,15 +2487,15 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
           bool okq = true;
           int rq = solve_device(B, lambda, &okq, nullptr, nullptr, t); if (rq) return rq;
           cs::ba_launch_scale_update(B->view, B->d_lam.p, B->scale_partial.p, B->st, B->cams_bak.p, B->points_bak.p, B->cubes_bak.p);
-          if (spec_now) BA_TRY(hipEventRecord(B->ev_upd, B->st));      // the state the next linearisation reads is final from here
+          if (spec_now) CS_HIP_TRY(hipEventRecord(B->ev_upd, B->st));      // the state the next linearisation reads is final from here
           BA_MARK(B, B->ev[6]);
           cs::ba_launch_chi2(B->view, B->nb_chi, B->st);
           if (B->sep_mode && B->shard_n > 1) cs::ba_launch_sum2(B->chi_partial.p, B->n_chi_partials, B->scale_partial.p, cs::ba_scale_blocks(), B->d_scalars.p, B->st);   // (separator mode set its flag itself: three status words)
           else cs::ba_launch_sum2_flag(B->chi_partial.p, B->n_chi_partials, B->scale_partial.p, cs::ba_scale_blocks(), B->d_band_info.p, B->d_elim_fail.p, B->d_scalars.p, B->st,
                                        direct_scalars ? B->h_trial : nullptr, direct_scalars ? (B->trial_seq += 1.0) : 0.0);
-          BA_TRY(hipGetLastError());
+          CS_HIP_TRY(hipGetLastError());
           if (rccl) BA_NCCL(ncclAllReduce(B->d_scalars.p, B->d_scalars.p, 3, ncclDouble, ncclSum, B->comm, B->st));
-          if (!direct_scalars) BA_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, 3 * sizeof(double), hipMemcpyDeviceToHost, B->st));
+          if (!direct_scalars) CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, 3 * sizeof(double), hipMemcpyDeviceToHost, B->st));
           BA_MARK(B, B->ev[7]);
           return CS_OK;
         };
@@ -2569,41 +2513,41 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
         }
         const double* hs = B->h_scalars;
         if (direct_scalars) { rc = wait_trial(B->trial_seq); if (rc) return rc; hs = B->h_trial; }
-        else BA_TRY(hipStreamSynchronize(B->st));
+        else CS_HIP_TRY(hipStreamSynchronize(B->st));
         turn.unlock();
-        if (B->h_status[0] == 0x7fffffff || (B->sep_mode && B->shard_n > 1 && B->h_status[2] == 0x7fffffff)) { cs_set_error_ba("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
+        if (B->h_status[0] == 0x7fffffff || (B->sep_mode && B->shard_n > 1 && B->h_status[2] == 0x7fffffff)) { cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
         ok2 = hs[2] == 0.0;
         tempChi = hs[0];
         scale = ok2 ? hs[1] : 0.0;
         if (B->stage_timing) {
-          if (direct_scalars) BA_TRY(hipStreamSynchronize(B->st));     // (the phase marks are read below: the last one must have passed)
+          if (direct_scalars) CS_HIP_TRY(hipStreamSynchronize(B->st));     // (the phase marks are read below: the last one must have passed)
           rc = collect_solve_times(B); if (rc) return rc;
           float ms = 0;
-          BA_TRY(hipEventElapsedTime(&ms, B->ev[6], B->ev[7])); B->tm.errors_ms += ms;
+          CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[6], B->ev[7])); B->tm.errors_ms += ms;
         }
         if (ext_active && ok2) { rc = ext_refresh(0); if (rc) return rc; tempChi += B->ext_chi2; }
       } else {
         rc = solve_device(B, lambda, &ok2, fn, ctx); if (rc) return rc;
         if (B->shard_n > 1) {   // a failed factorisation on one rank is everybody's rejected trial
           double ff = ok2 ? 0.0 : 1.0;
-          if (reduce_host(&ff, 1, 1)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+          if (reduce_host(&ff, 1, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
           ok2 = ff == 0.0;
         }
         if (ok2) {
           const int nsb = cs::ba_scale_blocks();
           std::vector<double> sp(nsb);
           cs::ba_launch_scale(B->view, B->d_lam.p, B->scale_partial.p, B->st);     // (d_lam still holds this trial's lambda: put_lambda in solve_device)
-          BA_TRY(hipGetLastError());
-          BA_TRY(hipMemcpyAsync(sp.data(), B->scale_partial.p, sizeof(double) * nsb, hipMemcpyDeviceToHost, B->st));
+          CS_HIP_TRY(hipGetLastError());
+          CS_HIP_TRY(hipMemcpyAsync(sp.data(), B->scale_partial.p, sizeof(double) * nsb, hipMemcpyDeviceToHost, B->st));
           rc = cs_ba_update(B); if (rc) return rc;   // synchronises the stream
           for (double p : sp) scale += p;
         }
         t0 = now_ms();
         rc = chi2_device(B, &tempChi); if (rc) return rc;
         if (ext_active && ok2) { rc = ext_refresh(0); if (rc) return rc; tempChi += B->ext_chi2; }
-        if (reduce_host(&tempChi, 1, 0)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+        if (reduce_host(&tempChi, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
         B->tm.errors_ms += now_ms() - t0;
-        if (reduce_host(&scale, 1, 0)) { cs_set_error_ba("all-reduce failed"); return CS_ERR_HIP; }
+        if (reduce_host(&scale, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
       }
       if (ok2) debug_nan_scan(B, "cs_ba_optimize: after a trial's solve + update");
       if (!ok2) tempChi = std::numeric_limits<double>::max();
@@ -2627,7 +2571,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
       }
       qmax++;
     } while (rho < 0 && qmax < B->max_trials_after_failure);
-    if (!spec_lin) BA_TRY(hipStreamSynchronize(B->st));
+    if (!spec_lin) CS_HIP_TRY(hipStreamSynchronize(B->st));
     if (done < cap) {
       if (chi_hist) chi_hist[done] = currentChi;
       if (lambda_hist) lambda_hist[done] = lambda;
@@ -2639,15 +2583,15 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
     if (nBad >= 3) break;
   }
-  if (spec_lin) BA_TRY(hipStreamSynchronize(B->st));      // (a stopping rule ended the loop behind an accepted trial: its speculated system is the current state's)
+  if (spec_lin) CS_HIP_TRY(hipStreamSynchronize(B->st));      // (a stopping rule ended the loop behind an accepted trial: its speculated system is the current state's)
   if (iterations_done) *iterations_done = done;
   B->tm.total_ms += now_ms() - t_begin;
   return CS_OK;
 }
 int cs_ba_optimize_sharded(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_optimize_sharded_impl(B, iterations, fn, ctx, iterations_done, chi_hist, lambda_hist, trials_hist, cap);
-  BA_GUARD_END("cs_ba_optimize_sharded")
+  CS_GUARD_END("cs_ba_optimize_sharded")
 }
 
 // ---- RCCL: one process per GPU, the library issues the collectives itself (ncclAllReduce on the handle's stream)
@@ -2662,9 +2606,9 @@ int cs_ba_comm_unique_id(unsigned char id128[128]) {
 
 int cs_ba_comm_init(cs_ba* B, int rank, int n_ranks, const unsigned char id128[128]) {
   if (!B || !id128 || n_ranks < 1 || rank < 0 || rank >= n_ranks) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipSetDevice(B->device));
   if (B->comm) { (void)ncclCommDestroy(B->comm); B->comm = nullptr; g_comm_handles--; }
-  if (g_comm_handles.load() > 0) { cs_set_error_ba("cs_ba_comm_init: this process already holds a communicator handle (one process per GPU)"); return CS_ERR_INVALID_ARG; }
+  if (g_comm_handles.load() > 0) { cs_set_error("cs_ba_comm_init: this process already holds a communicator handle (one process per GPU)"); return CS_ERR_INVALID_ARG; }
   ncclUniqueId id;
   std::memcpy(id.internal, id128, 128);
   BA_NCCL(ncclCommInitRank(&B->comm, n_ranks, id, rank));
@@ -2676,7 +2620,7 @@ int cs_ba_comm_init(cs_ba* B, int rank, int n_ranks, const unsigned char id128[1
 // the separator system; the bytes this rank contributes to the collectives of one LM trial, and what the all-reduce would be.
 int cs_ba_shard_info(cs_ba* B, int* sep_mode, int* n_sep, int* w_max, long long* bytes_per_trial, long long* bytes_per_trial_allreduce, int* interior_n) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
   if (sep_mode) *sep_mode = B->sep_mode ? 1 : 0;
   if (n_sep) *n_sep = B->n_sep;
@@ -2685,7 +2629,7 @@ int cs_ba_shard_info(cs_ba* B, int* sep_mode, int* n_sep, int* w_max, long long*
   if (bytes_per_trial_allreduce) *bytes_per_trial_allreduce = B->bytes_per_trial_allreduce;
   if (interior_n) *interior_n = B->sep_mode ? B->int_n : B->n_red;
   return CS_OK;
-  BA_GUARD_END("cs_ba_shard_info")
+  CS_GUARD_END("cs_ba_shard_info")
 }
 // Accumulated stage times of the separator-mode solves (ms; divide by cs_ba_timing::n_solves): interior factorisation, separator
 // message (Y = B L^-T, T, t), gather of the messages (through a callback this includes the host round trip), separator system
@@ -2698,23 +2642,23 @@ int cs_ba_shard_timing(cs_ba* B, double out5[5]) {
 // The rank that owns each landmark under the rule in force (separator mode: by the lowest column of its free cameras).
 int cs_ba_get_landmark_owners(cs_ba* B, int* owner_out) {
   if (!B || (B->np && !owner_out)) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
   std::copy(B->lm_owner.begin(), B->lm_owner.end(), owner_out);
   return CS_OK;
-  BA_GUARD_END("cs_ba_get_landmark_owners")
+  CS_GUARD_END("cs_ba_get_landmark_owners")
 }
 
 int cs_ba_get_state(cs_ba* B, double* cams7, double* cuboids10, double* points3) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
-  if (cams7 && B->nc) BA_TRY(hipMemcpy(cams7, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToHost));
-  if (cuboids10 && B->no) BA_TRY(hipMemcpy(cuboids10, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToHost));
-  if (points3 && B->np) BA_TRY(hipMemcpy(points3, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToHost));
+  CS_GUARD_BEGIN
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
+  if (cams7 && B->nc) CS_HIP_TRY(hipMemcpy(cams7, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToHost));
+  if (cuboids10 && B->no) CS_HIP_TRY(hipMemcpy(cuboids10, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToHost));
+  if (points3 && B->np) CS_HIP_TRY(hipMemcpy(points3, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToHost));
   return CS_OK;
-  BA_GUARD_END("cs_ba_get_state")
+  CS_GUARD_END("cs_ba_get_state")
 }
 
 static int cs_ba_sizes_impl(cs_ba* B, int* size_pose, int* size_lm) {
@@ -2725,9 +2669,9 @@ static int cs_ba_sizes_impl(cs_ba* B, int* size_pose, int* size_lm) {
   return CS_OK;
 }
 int cs_ba_sizes(cs_ba* B, int* size_pose, int* size_lm) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_sizes_impl(B, size_pose, size_lm);
-  BA_GUARD_END("cs_ba_sizes")
+  CS_GUARD_END("cs_ba_sizes")
 }
 
 static int cs_ba_solver_layout_impl(cs_ba* B, int* band_ld, int* team) {
@@ -2739,23 +2683,23 @@ static int cs_ba_solver_layout_impl(cs_ba* B, int* band_ld, int* team) {
   return CS_OK;
 }
 int cs_ba_solver_layout(cs_ba* B, int* band_ld, int* team) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_solver_layout_impl(B, band_ld, team);
-  BA_GUARD_END("cs_ba_solver_layout")
+  CS_GUARD_END("cs_ba_solver_layout")
 }
 
 static int cs_ba_get_system_impl(cs_ba* B, double* Hpp, double* Hll9, double* Hpl18, double* b, double* x) {
   if (!B) return CS_ERR_INVALID_ARG;
   if (B->structure_dirty || !B->have_system) return CS_ERR_NOT_RUN;
-  BA_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipSetDevice(B->device));
   const int n = B->n_pose;
   if (Hpp) {
     std::memset(Hpp, 0, sizeof(double) * (size_t)n * n);
     std::vector<double> hc(36 * (size_t)B->nc), ho(81 * (size_t)B->no), hco(54 * (size_t)B->n_cub), hij(36 * (size_t)B->n_odom);
-    if (B->nc) BA_TRY(hipMemcpy(hc.data(), B->Hcam.p, 8 * hc.size(), hipMemcpyDeviceToHost));
-    if (B->no) BA_TRY(hipMemcpy(ho.data(), B->Hcub.p, 8 * ho.size(), hipMemcpyDeviceToHost));
-    if (B->n_cub) BA_TRY(hipMemcpy(hco.data(), B->ce_Hco.p, 8 * hco.size(), hipMemcpyDeviceToHost));
-    if (B->n_odom) BA_TRY(hipMemcpy(hij.data(), B->oe_Hij.p, 8 * hij.size(), hipMemcpyDeviceToHost));
+    if (B->nc) CS_HIP_TRY(hipMemcpy(hc.data(), B->Hcam.p, 8 * hc.size(), hipMemcpyDeviceToHost));
+    if (B->no) CS_HIP_TRY(hipMemcpy(ho.data(), B->Hcub.p, 8 * ho.size(), hipMemcpyDeviceToHost));
+    if (B->n_cub) CS_HIP_TRY(hipMemcpy(hco.data(), B->ce_Hco.p, 8 * hco.size(), hipMemcpyDeviceToHost));
+    if (B->n_odom) CS_HIP_TRY(hipMemcpy(hij.data(), B->oe_Hij.p, 8 * hij.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < B->nc; i++) { int c = B->cam_col_ref[i]; if (c < 0) continue; for (int r = 0; r < 6; r++) for (int q = 0; q < 6; q++) Hpp[(size_t)(c + r) * n + c + q] = hc[36 * (size_t)i + 6 * r + q]; }
     for (int i = 0; i < B->no; i++) { int c = B->cub_col_ref[i]; if (c < 0) continue; for (int r = 0; r < 9; r++) for (int q = 0; q < 9; q++) Hpp[(size_t)(c + r) * n + c + q] = ho[81 * (size_t)i + 9 * r + q]; }
     for (int k = 0; k < B->n_cub; k++) {
@@ -2778,12 +2722,12 @@ static int cs_ba_get_system_impl(cs_ba* B, double* Hpp, double* Hll9, double* Hp
   }
   if (Hll9) {
     std::vector<double> hl(9 * (size_t)B->np);
-    if (B->np) BA_TRY(hipMemcpy(hl.data(), B->Hll.p, 8 * hl.size(), hipMemcpyDeviceToHost));
+    if (B->np) CS_HIP_TRY(hipMemcpy(hl.data(), B->Hll.p, 8 * hl.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) std::memcpy(Hll9 + 9 * (size_t)B->pt_lm[i], &hl[9 * (size_t)i], 72);
   }
   if (Hpl18) {
     std::vector<double> w(18 * (size_t)B->slot_src_n);
-    if (!w.empty()) BA_TRY(hipMemcpy(w.data(), B->W.p, 8 * w.size(), hipMemcpyDeviceToHost));
+    if (!w.empty()) CS_HIP_TRY(hipMemcpy(w.data(), B->W.p, 8 * w.size(), hipMemcpyDeviceToHost));
     std::memset(Hpl18, 0, 144 * (size_t)B->n_proj);      // (an edge owned by another rank stays zero)
     for (int sl = 0; sl < B->slot_src_n; sl++) std::memcpy(Hpl18 + 18 * (size_t)B->slot_src[sl], &w[18 * (size_t)sl], 144);
   }
@@ -2797,9 +2741,9 @@ static int cs_ba_get_system_impl(cs_ba* B, double* Hpp, double* Hll9, double* Hp
   return CS_OK;
 }
 int cs_ba_get_system(cs_ba* B, double* Hpp, double* Hll9, double* Hpl18, double* b, double* x) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_get_system_impl(B, Hpp, Hll9, Hpl18, b, x);
-  BA_GUARD_END("cs_ba_get_system")
+  CS_GUARD_END("cs_ba_get_system")
 }
 
 // Solver::computeMarginals (core/block_solver.hpp:488-499): LinearSolver::solvePattern(spinv, blockIndices, *_Hpp) -- blocks of the INVERSE of
@@ -2812,12 +2756,12 @@ int cs_ba_get_system(cs_ba* B, double* Hpp, double* Hll9, double* Hpl18, double*
 static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite) {
   if (!B || n_pairs < 0 || (n_pairs && (!class_i || !idx_i || !class_j || !idx_j || !out))) return CS_ERR_INVALID_ARG;
   if (positive_definite) *positive_definite = 1;
-  if (B->structure_dirty || !B->have_system) { cs_set_error_ba("cs_ba_pose_marginals: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
-  if (B->shard_n > 1) { cs_set_error_ba("cs_ba_pose_marginals: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
+  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_pose_marginals: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  if (B->shard_n > 1) { cs_set_error("cs_ba_pose_marginals: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
   if (n_pairs == 0) return CS_OK;
   const int n = B->n_pose;
-  if (n <= 0) { cs_set_error_ba("cs_ba_pose_marginals: the graph has no free camera or cuboid"); return CS_ERR_INVALID_ARG; }
-  if ((long long)n * n > (1ll << 28)) { cs_set_error_ba("cs_ba_pose_marginals: the dense pose Hessian would exceed 2 GB"); return CS_ERR_CAPACITY; }
+  if (n <= 0) { cs_set_error("cs_ba_pose_marginals: the graph has no free camera or cuboid"); return CS_ERR_INVALID_ARG; }
+  if ((long long)n * n > (1ll << 28)) { cs_set_error("cs_ba_pose_marginals: the dense pose Hessian would exceed 2 GB"); return CS_ERR_CAPACITY; }
   auto col_of = [&](int cls, int idx, int& dim) -> int {
     if (cls == CS_VERTEX_CAM) { dim = 6; return (idx >= 0 && idx < B->nc) ? B->cam_col_ref[idx] : -1; }
     if (cls == CS_VERTEX_CUBOID) { dim = 9; return (idx >= 0 && idx < B->no) ? B->cub_col_ref[idx] : -1; }
@@ -2830,13 +2774,13 @@ static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, 
   for (int k = 0; k < n_pairs; k++) {
     int di, dj;
     const int ci = col_of(class_i[k], idx_i[k], di), cj = col_of(class_j[k], idx_j[k], dj);
-    if (ci < 0 || cj < 0) { cs_set_error_ba("cs_ba_pose_marginals: pair " + std::to_string(k) + " names a fixed vertex, a point or an index out of range"); return CS_ERR_INVALID_ARG; }
+    if (ci < 0 || cj < 0) { cs_set_error("cs_ba_pose_marginals: pair " + std::to_string(k) + " names a fixed vertex, a point or an index out of range"); return CS_ERR_INVALID_ARG; }
     auto it = rhs_at.find(cj);
     if (it == rhs_at.end()) { it = rhs_at.emplace(cj, m).first; col_base.push_back(cj); col_dim.push_back(dj); m += dj; }
     rhs_of_pair[k] = it->second;
   }
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   std::vector<double> H((size_t)n * n);
   { const int rc = cs_ba_get_system_impl(B, H.data(), nullptr, nullptr, nullptr, nullptr); if (rc) return rc; }
   std::vector<double> E((size_t)n * m, 0.0);      // column-major n x m: unit vectors
@@ -2847,17 +2791,17 @@ static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, 
   struct Rel { DBuf<double>&a, &b; DBuf<int>& c; ~Rel() { a.release(); b.release(); c.release(); } } rel{dH, dE, dinfo};
   int rc;
   if ((rc = dH.reserve((size_t)n * n)) || (rc = dE.reserve((size_t)n * m)) || (rc = dinfo.reserve(1))) return rc;
-  BA_TRY(hipMemcpyAsync(dH.p, H.data(), 8 * H.size(), hipMemcpyHostToDevice, B->st));
-  BA_TRY(hipMemcpyAsync(dE.p, E.data(), 8 * E.size(), hipMemcpyHostToDevice, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(dH.p, H.data(), 8 * H.size(), hipMemcpyHostToDevice, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(dE.p, E.data(), 8 * E.size(), hipMemcpyHostToDevice, B->st));
   BA_ROC(rocblas_set_stream(B->blas, B->st));
   BA_ROC(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, dH.p, n, dinfo.p));      // (symmetric: row- and column-major are the same matrix)
   int info = 0;
-  BA_TRY(hipMemcpyAsync(&info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipMemcpyAsync(&info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (info != 0) { if (positive_definite) *positive_definite = 0; return CS_OK; }
   BA_ROC(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, m, dH.p, n, dE.p, n));
-  BA_TRY(hipMemcpyAsync(E.data(), dE.p, 8 * E.size(), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipMemcpyAsync(E.data(), dE.p, 8 * E.size(), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   size_t o = 0;
   for (int k = 0; k < n_pairs; k++) {
     int di, dj;
@@ -2868,9 +2812,9 @@ static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, 
   return CS_OK;
 }
 int cs_ba_pose_marginals(cs_ba* B, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_pose_marginals_impl(B, n_pairs, class_i, idx_i, class_j, idx_j, out, positive_definite);
-  BA_GUARD_END("cs_ba_pose_marginals")
+  CS_GUARD_END("cs_ba_pose_marginals")
 }
 
 // Inspection for parity tests: the damped reduced system exactly as the solver is about to factorise it -- dense symmetric n_red x n_red
@@ -2879,22 +2823,22 @@ int cs_ba_pose_marginals(cs_ba* B, int n_pairs, const int* class_i, const int* i
 // (block_solver.hpp:373-439) at `lambda` on the current linearisation; no factorisation.
 static int cs_ba_get_reduced_system_impl(cs_ba* B, double lambda, double* S_dense, double* rhs, int* cam_col, int* cub_col) {
   if (!B) return CS_ERR_INVALID_ARG;
-  if (B->structure_dirty || !B->have_system) { cs_set_error_ba("cs_ba_get_reduced_system: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
-  if (B->shard_n > 1) { cs_set_error_ba("cs_ba_get_reduced_system: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
-  BA_TRY(hipSetDevice(B->device));
+  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_get_reduced_system: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  if (B->shard_n > 1) { cs_set_error("cs_ba_get_reduced_system: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
+  CS_HIP_TRY(hipSetDevice(B->device));
   const int n = B->n_red;
   if (cam_col) std::copy(B->cam_col.begin(), B->cam_col.end(), cam_col);
   if (cub_col) std::copy(B->cub_col.begin(), B->cub_col.end(), cub_col);
   if (n <= 0) return CS_OK;
   { int rcl = put_lambda(B, lambda); if (rcl) return rcl; }
-  BA_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
-  BA_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
+  CS_HIP_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
+  CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
   cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join);
   if (B->ext_n > 0 && B->ext_terms_set) cs::ba_launch_ext_offdiag(B->view, B->ext_groups, B->d_ext_gptr.p, B->d_ext_order.p, B->d_ext_e4.p, B->ext_Hij.p, B->st);
-  BA_TRY(hipGetLastError());
+  CS_HIP_TRY(hipGetLastError());
   std::vector<double> h(B->s_doubles + B->n_pose);
-  BA_TRY(hipMemcpyAsync(h.data(), B->S.p, 8 * h.size(), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipMemcpyAsync(h.data(), B->S.p, 8 * h.size(), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (rhs) std::copy(h.begin() + B->s_doubles, h.begin() + B->s_doubles + n, rhs);
   if (S_dense) {
     std::memset(S_dense, 0, sizeof(double) * (size_t)n * n);
@@ -2908,52 +2852,52 @@ static int cs_ba_get_reduced_system_impl(cs_ba* B, double lambda, double* S_dens
   return CS_OK;
 }
 int cs_ba_get_reduced_system(cs_ba* B, double lambda, double* S_dense, double* rhs, int* cam_col, int* cub_col) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_get_reduced_system_impl(B, lambda, S_dense, rhs, cam_col, cub_col);
-  BA_GUARD_END("cs_ba_get_reduced_system")
+  CS_GUARD_END("cs_ba_get_reduced_system")
 }
 
 int cs_ba_reduced_size(cs_ba* B, int* n_reduced, int* cuboids_eliminated) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
   if (n_reduced) *n_reduced = B->n_red;
   if (cuboids_eliminated) *cuboids_eliminated = B->elim ? 1 : 0;
   return CS_OK;
-  BA_GUARD_END("cs_ba_reduced_size")
+  CS_GUARD_END("cs_ba_reduced_size")
 }
 
 int cs_ba_band_order(cs_ba* B, int* block_cyclic_reduction, int* levels) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
   const bool bcr = B->band_ld > 0 && B->use_bcr;
   if (block_cyclic_reduction) *block_cyclic_reduction = bcr ? 1 : 0;
   if (levels) { int L = 0; for (int N = (B->n_red + 127) / 128; bcr && N >= 1; N /= 2) L++; *levels = L; }
   return CS_OK;
-  BA_GUARD_END("cs_ba_band_order")
+  CS_GUARD_END("cs_ba_band_order")
 }
 int cs_ba_solver_path(cs_ba* B, int* path, int* bandwidth, double* sparse_fill) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
   if (path) *path = B->band_ld ? CS_BA_PATH_BAND : (B->sparse ? CS_BA_PATH_SPARSE : CS_BA_PATH_DENSE);
   if (bandwidth) *bandwidth = B->band_ld ? B->band_ld - 1 : 0;
   if (sparse_fill) *sparse_fill = B->sparse ? (double)B->sp_plan.nvals / (0.5 * (double)B->n_red * (double)B->n_red) : 0.0;
   return CS_OK;
-  BA_GUARD_END("cs_ba_solver_path")
+  CS_GUARD_END("cs_ba_solver_path")
 }
 
 int cs_ba_schur_layout(cs_ba* B, int* fused, int* n_segments, int* n_partial_blocks, int* n_blocks) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
   if (fused) *fused = B->fused ? 1 : 0;
   if (n_segments) *n_segments = B->n_seg;
   if (n_partial_blocks) *n_partial_blocks = (int)(B->part_tiles.n / 36);
   if (n_blocks) *n_blocks = B->fused ? B->n_gpairs : B->n_pairs;
   return CS_OK;
-  BA_GUARD_END("cs_ba_schur_layout")
+  CS_GUARD_END("cs_ba_schur_layout")
 }
 
 // Inspection for tests: a fingerprint of every index table the structure phase leaves on the device (edge orders, per-vertex lists,
@@ -2961,10 +2905,10 @@ int cs_ba_schur_layout(cs_ba* B, int* fused, int* n_segments, int* n_partial_blo
 // threaded loops and CS_BA_STRUCT_THREADS=1, an appended graph and the same graph set up at once -- must agree table by table.
 int cs_ba_structure_digest(cs_ba* B, unsigned long long* out, int cap, int* n_tables) {
   if (!B || !n_tables || cap < 0 || (cap && !out)) return CS_ERR_INVALID_ARG;
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   int rc = finalize_structure(B); if (rc) return rc;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   const DBuf<int>* tabs[] = {&B->d_cam_col, &B->d_cub_col, &B->d_pt_free, &B->pm_pt, &B->pm_cam, &B->pt_ptr, &B->cm_pm, &B->cm_pt, &B->cam_ptr, &B->d_src,
                              &B->d_run_lm, &B->d_seg_ptr, &B->d_seg_k, &B->d_seg_tile, &B->d_seg_slot, &B->d_gp_ptr, &B->d_gp_i1, &B->d_gp_i2, &B->d_gtile, &B->d_gcam_ptr, &B->d_gslot,
                              &B->pair_ptr, &B->pair_i1, &B->pair_i2, &B->ent_a, &B->ent_b, &B->d_cubS_ptr, &B->d_cubS_cam, &B->d_ce_slot, &B->d_cub_tile, &B->d_cub_coef,
@@ -2975,13 +2919,13 @@ int cs_ba_structure_digest(cs_ba* B, unsigned long long* out, int cap, int* n_ta
   std::vector<int> h;
   for (int t = 0; t < nt && t < cap; t++) {
     h.resize(tabs[t]->n);
-    if (tabs[t]->n) BA_TRY(hipMemcpy(h.data(), tabs[t]->p, sizeof(int) * tabs[t]->n, hipMemcpyDeviceToHost));
+    if (tabs[t]->n) CS_HIP_TRY(hipMemcpy(h.data(), tabs[t]->p, sizeof(int) * tabs[t]->n, hipMemcpyDeviceToHost));
     unsigned long long f = 1469598103934665603ull ^ (unsigned long long)tabs[t]->n;
     for (int v : h) { f ^= (unsigned)v; f *= 1099511628211ull; }
     out[t] = f;
   }
   return CS_OK;
-  BA_GUARD_END("cs_ba_structure_digest")
+  CS_GUARD_END("cs_ba_structure_digest")
 }
 
 // The diagonal Hessian blocks g2o keeps mapped into its vertices (BaseVertex::_hessian, core/base_vertex.hpp:30,52-54; mapped by
@@ -2989,19 +2933,19 @@ int cs_ba_structure_digest(cs_ba* B, unsigned long long* out, int cap, int* n_ta
 // (optimization_algorithm_levenberg.cpp:166-180): A_ii of every vertex, caller's vertex order, zeros for fixed vertices.
 int cs_ba_get_vertex_hessians(cs_ba* B, double* cam36, double* cub81, double* pt9) {
   if (!B) return CS_ERR_INVALID_ARG;
-  if (B->structure_dirty || !B->have_system) { cs_set_error_ba("cs_ba_get_vertex_hessians: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
+  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_get_vertex_hessians: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (cam36 && B->nc) {
-    BA_TRY(hipMemcpy(cam36, B->Hcam.p, 8 * 36 * (size_t)B->nc, hipMemcpyDeviceToHost));
+    CS_HIP_TRY(hipMemcpy(cam36, B->Hcam.p, 8 * 36 * (size_t)B->nc, hipMemcpyDeviceToHost));
     for (int i = 0; i < B->nc; i++) if (B->cam_fixed[i]) std::memset(cam36 + 36 * (size_t)i, 0, 288);
   }
   if (cub81 && B->no) {
-    BA_TRY(hipMemcpy(cub81, B->Hcub.p, 8 * 81 * (size_t)B->no, hipMemcpyDeviceToHost));
+    CS_HIP_TRY(hipMemcpy(cub81, B->Hcub.p, 8 * 81 * (size_t)B->no, hipMemcpyDeviceToHost));
     for (int i = 0; i < B->no; i++) if (B->cub_fixed[i]) std::memset(cub81 + 81 * (size_t)i, 0, 648);
   }
   if (pt9 && B->np) {
-    BA_TRY(hipMemcpy(pt9, B->Hll.p, 8 * 9 * (size_t)B->np, hipMemcpyDeviceToHost));
+    CS_HIP_TRY(hipMemcpy(pt9, B->Hll.p, 8 * 9 * (size_t)B->np, hipMemcpyDeviceToHost));
     for (int i = 0; i < B->np; i++) if (B->pt_fixed[i]) std::memset(pt9 + 9 * (size_t)i, 0, 72);
   }
   return CS_OK;
@@ -3039,7 +2983,7 @@ int cs_ba_last_timing(cs_ba* B, cs_ba_timing* t) {
 // prints what it finds to stderr.
 static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_out) {
   if (!B) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
   const cs::BaView& v = B->view;
   const int E = v.n_proj, n_edges = E + B->n_cub + B->n_odom;
@@ -3073,9 +3017,9 @@ static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_
   for (size_t t = 0; t < arrs.size(); t++) { h[2 * t] = 0; h[2 * t + 1] = 0x7fffffff; }
   if ((rc = out.upload(h))) return rc;
   for (size_t t = 0; t < arrs.size(); t++) cs::ba_launch_scan_finite(arrs[t].p, arrs[t].n, out.p + 2 * t, B->st);
-  BA_TRY(hipGetLastError());
-  BA_TRY(hipMemcpyAsync(h.data(), out.p, sizeof(int) * h.size(), hipMemcpyDeviceToHost, B->st));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipMemcpyAsync(h.data(), out.p, sizeof(int) * h.size(), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   long long total = 0;
   std::string rep;
   for (size_t t = 0; t < arrs.size(); t++) {
@@ -3092,9 +3036,9 @@ static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_
   return CS_OK;
 }
 int cs_ba_check_finite(cs_ba* B, int* n_bad, char* report, int report_cap) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return check_finite_impl(B, report, report_cap, n_bad);
-  BA_GUARD_END("cs_ba_check_finite")
+  CS_GUARD_END("cs_ba_check_finite")
 }
 static bool debug_nan_enabled() { static const bool on = [] { const char* e = getenv("CS_BA_DEBUG_NAN"); return e && atoi(e) != 0; }(); return on; }
 static void debug_nan_scan(cs_ba* B, const char* where) {
@@ -3114,18 +3058,18 @@ template <class T> bool rd(FILE* f, std::vector<T>& a, size_t n) { a.resize(n); 
 }  // namespace
 static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   if (!B || !path) return CS_ERR_INVALID_ARG;
-  BA_TRY(hipSetDevice(B->device));
-  BA_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   const int np_e = B->n_proj, n3 = (int)B->u3_cam.size(), n4 = (int)B->up_cam.size(), n6 = B->n_odom;
   std::vector<double> cams(7 * (size_t)B->nc), cubs(10 * (size_t)B->no), pts(3 * (size_t)B->np), uv(2 * (size_t)np_e), info(4 * (size_t)np_e), intr(4 * (size_t)np_e), hub(B->have_huber ? np_e : 0);
-  auto d2h = [&](std::vector<double>& h, const double* d) -> int { if (!h.empty()) BA_TRY(hipMemcpy(h.data(), d, 8 * h.size(), hipMemcpyDeviceToHost)); return CS_OK; };
+  auto d2h = [&](std::vector<double>& h, const double* d) -> int { if (!h.empty()) CS_HIP_TRY(hipMemcpy(h.data(), d, 8 * h.size(), hipMemcpyDeviceToHost)); return CS_OK; };
   int rc;
   if ((rc = d2h(cams, B->cams.p)) || (rc = d2h(cubs, B->cubes.p)) || (rc = d2h(pts, B->points.p)) || (rc = d2h(uv, B->raw_uv.p)) || (rc = d2h(hub, B->raw_huber.p))) return rc;
   // (records that were never stored -- every edge carries the reference record -- are written out here)
   if (B->raw_info_virtual) { for (int k = 0; k < np_e; k++) std::memcpy(&info[4 * (size_t)k], B->uni8, 32); } else if ((rc = d2h(info, B->raw_info.p))) return rc;
   if (B->raw_intr_virtual) { for (int k = 0; k < np_e; k++) std::memcpy(&intr[4 * (size_t)k], B->uni8 + 4, 32); } else if ((rc = d2h(intr, B->raw_intr.p))) return rc;
   FILE* f = fopen(path, "wb");
-  if (!f) { cs_set_error_ba(std::string("cs_ba_dump: cannot open ") + path); return CS_ERR_INVALID_ARG; }
+  if (!f) { cs_set_error(std::string("cs_ba_dump: cannot open ") + path); return CS_ERR_INVALID_ARG; }
   DumpHeader H{};
   std::memcpy(H.magic, "CSBA0002", 8);
   const int counts[16] = {B->nc, B->no, B->np, B->cuboids_first, np_e, B->have_huber ? 1 : 0, (int)B->rk_proj.size(), n3, (int)B->rk_cub3.size(), n4, (int)B->rk_cproj.size(), n6, (int)B->rk_odom.size(), 0, 0, 0};
@@ -3137,23 +3081,23 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   ok = ok && wr(f, B->up_cam) && wr(f, B->up_cub) && wr(f, B->h_pe_meas) && wr(f, B->h_pe_info) && wr(f, B->h_pe_K) && wr(f, B->rk_cproj) && wr(f, B->rd_cproj);
   ok = ok && wr(f, B->oe_i) && wr(f, B->oe_j) && wr(f, B->h_oe_meas) && wr(f, B->h_oe_info) && wr(f, B->rk_odom) && wr(f, B->rd_odom);
   ok = (fclose(f) == 0) && ok;
-  if (!ok) { cs_set_error_ba(std::string("cs_ba_dump: write to ") + path + " failed"); return CS_ERR_INVALID_ARG; }
+  if (!ok) { cs_set_error(std::string("cs_ba_dump: write to ") + path + " failed"); return CS_ERR_INVALID_ARG; }
   return CS_OK;
 }
 int cs_ba_dump(cs_ba* B, const char* path) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_dump_impl(B, path);
-  BA_GUARD_END("cs_ba_dump")
+  CS_GUARD_END("cs_ba_dump")
 }
 static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   if (!path || !out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
   FILE* f = fopen(path, "rb");
-  if (!f) { cs_set_error_ba(std::string("cs_ba_load: cannot open ") + path); return CS_ERR_INVALID_ARG; }
+  if (!f) { cs_set_error(std::string("cs_ba_load: cannot open ") + path); return CS_ERR_INVALID_ARG; }
   struct Close { FILE* f; ~Close() { fclose(f); } } cl{f};
   DumpHeader H;
-  if (fread(&H, sizeof(H), 1, f) != 1 || std::memcmp(H.magic, "CSBA0002", 8) != 0) { cs_set_error_ba("cs_ba_load: not a cs_ba dump (magic CSBA0002)"); return CS_ERR_INVALID_ARG; }
-  for (int i = 0; i < 13; i++) if (H.v[i] < 0) { cs_set_error_ba("cs_ba_load: corrupt header"); return CS_ERR_INVALID_ARG; }
+  if (fread(&H, sizeof(H), 1, f) != 1 || std::memcmp(H.magic, "CSBA0002", 8) != 0) { cs_set_error("cs_ba_load: not a cs_ba dump (magic CSBA0002)"); return CS_ERR_INVALID_ARG; }
+  for (int i = 0; i < 13; i++) if (H.v[i] < 0) { cs_set_error("cs_ba_load: corrupt header"); return CS_ERR_INVALID_ARG; }
   const int nc = H.v[0], no = H.v[1], np = H.v[2], cf = H.v[3], npe = H.v[4], hh = H.v[5], nrk = H.v[6], n3 = H.v[7], nrk3 = H.v[8], n4 = H.v[9], nrk4 = H.v[10], n6 = H.v[11], nrk6 = H.v[12];
   std::vector<double> cams, cubs, pts, uv, info, intr, hub, m10, i81, rd3, m4, i16, k9, rd4, m7, i36, rd6;
   std::vector<int> camf, cubf, ptf, ept, ecam, rkp, c3, o3, rk3, c4, o4, rk4, oi, oj, rk6;
@@ -3162,13 +3106,13 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   ok = ok && rd(f, c3, n3) && rd(f, o3, n3) && rd(f, m10, 10 * (size_t)n3) && rd(f, i81, 81 * (size_t)n3) && rd(f, rk3, nrk3) && rd(f, rd3, nrk3);
   ok = ok && rd(f, c4, n4) && rd(f, o4, n4) && rd(f, m4, 4 * (size_t)n4) && rd(f, i16, 16 * (size_t)n4) && rd(f, k9, 9 * (size_t)n4) && rd(f, rk4, nrk4) && rd(f, rd4, nrk4);
   ok = ok && rd(f, oi, n6) && rd(f, oj, n6) && rd(f, m7, 7 * (size_t)n6) && rd(f, i36, 36 * (size_t)n6) && rd(f, rk6, nrk6) && rd(f, rd6, nrk6);
-  if (!ok || (nrk && nrk != npe) || (nrk3 && nrk3 != n3) || (nrk4 && nrk4 != n4) || (nrk6 && nrk6 != n6)) { cs_set_error_ba("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
+  if (!ok || (nrk && nrk != npe) || (nrk3 && nrk3 != n3) || (nrk4 && nrk4 != n4) || (nrk6 && nrk6 != n6)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
   cs_ba* B = nullptr;
   int rc = cs_ba_create(device, &B); if (rc) return rc;
   struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{B};
   if ((rc = cs_ba_set_vertices(B, cams.data(), camf.data(), nc, cubs.data(), cubf.data(), no, pts.data(), ptf.data(), np, cf))) return rc;
   // (the setters normalise quaternions; the dumped ones are normalised already and must come back with their exact bits)
-  if (nc) BA_TRY(hipMemcpy(B->cams.p, cams.data(), 56 * (size_t)nc, hipMemcpyHostToDevice));
+  if (nc) CS_HIP_TRY(hipMemcpy(B->cams.p, cams.data(), 56 * (size_t)nc, hipMemcpyHostToDevice));
   if (npe && (rc = cs_ba_set_edges_proj(B, npe, ept.data(), ecam.data(), uv.data(), info.data(), intr.data(), hh ? hub.data() : nullptr))) return rc;
   if (nrk && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_PROJ, npe, rkp.data(), hub.data()))) return rc;
   if (n3 && (rc = cs_ba_set_edges_cuboid(B, n3, c3.data(), o3.data(), m10.data(), i81.data()))) return rc;
@@ -3183,7 +3127,7 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   return CS_OK;
 }
 int cs_ba_load(const char* path, int device, cs_ba** out) {
-  BA_GUARD_BEGIN
+  CS_GUARD_BEGIN
   return cs_ba_load_impl(path, device, out);
-  BA_GUARD_END("cs_ba_load")
+  CS_GUARD_END("cs_ba_load")
 }

@@ -2690,7 +2690,6 @@ void ba_launch_linearize(const BaView& v, hipStream_t st, hipStream_t st2, hipEv
   if (side3) (void)hipStreamWaitEvent(st, ev_join3, 0);
   hipLaunchKernelGGL(ba_accum_pose_kernel, dim3(v.nc + v.no), dim3(128), 0, st, v, 0);
 }
-void ba_launch_trial_prologue(double* d_lam, double lam0, double lam1, int* info24, int* elim_fail, double* S, size_t n_clear, hipStream_t st);
 void ba_launch_reduce(const BaView& v, const double* lambda, hipStream_t st, hipStream_t st2, hipEvent_t ev_fork, hipEvent_t ev_join, const BaSidePrologue* sp) {   // lambda: device, [lambda, lambda of the pose diagonals in the scale term]
   // sp (optional): the trial's prologue has NOT been launched yet -- it goes to the side stream when there is one and the landmark segments can take
   // lambda by value (the fused-linearisation kernels, no long-track segments), else in front of everything on the main stream

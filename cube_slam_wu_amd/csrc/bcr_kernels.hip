@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "ba_types.h"
 #include "band_potf2.h"
 #include "cs_hip_util.h"
 

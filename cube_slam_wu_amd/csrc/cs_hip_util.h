@@ -1,10 +1,68 @@
-// cs_hip_util.h -- small host-side HIP helpers shared by the kernel files.
+// cs_hip_util.h -- small host-side HIP helpers shared by the kernel files and the host stages.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
+#include <new>
+#include <stdexcept>
+#include <string>
+
+#include "../../include/cubeslam_hip.h"
+
+// the calling thread's message behind cs_last_error() (g_cs_err, detect_host.cpp; shared by every path)
+void cs_set_error(const std::string& s);
+
+#define CS_HIP_TRY(expr)                                                       \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) {                                                    \
+      cs_set_error(std::string(#expr) + ": " + hipGetErrorString(_e));         \
+      return CS_ERR_HIP;                                                       \
+    }                                                                          \
+  } while (0)
+
+// No C++ exception may cross the C boundary (std::bad_alloc / std::length_error from a host buffer would terminate the caller).
+#define CS_GUARD_BEGIN try {
+#define CS_GUARD_END(fn_name)                                                                                                \
+  } catch (const std::bad_alloc&) { cs_set_error(std::string(fn_name) + ": out of host memory"); return CS_ERR_CAPACITY; }   \
+    catch (const std::exception& ex) { cs_set_error(std::string(fn_name) + ": " + ex.what()); return CS_ERR_CAPACITY; }
 
 namespace cs {
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// Grow-only device / pinned buffers.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  int ensure(size_t n) {
+    if (n <= cap) return CS_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    size_t want = n + n / 8 + 64;
+    CS_HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
+    cap = want;
+    return CS_OK;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  int ensure(size_t n) {
+    if (n <= cap) return CS_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    size_t want = n + n / 8 + 64;
+    CS_HIP_TRY(hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault));
+    cap = want;
+    return CS_OK;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device's instance of a kernel: a handle on a second GPU of the
 // same process (cs_ba_create(device = 1), sharded ranks as threads on several devices) needs its own call.  One table per kernel, a

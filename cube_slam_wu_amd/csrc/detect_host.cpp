@@ -38,61 +38,19 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "cs_hip_util.h"
+#include "detect_hooks.h"
 #include "detect_types.h"
+#include "edge_types.h"
 
-namespace cs {
-void launch_vp_support(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st);
-void launch_vp_support_only(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st, int rp_max = 0);      // rp_max: the jobs' largest roll/pitch sample count (0: unknown)
-void launch_vp_points(const DetectDeviceView& v, int vp_total, hipStream_t st);
-int vp3_table_doubles_per_job();
-void launch_candidates(const DetectDeviceView& v, const SweepParams& sp, long long slot_total, hipStream_t st);
-void launch_candidate_compact(const DetectDeviceView& v, const SweepParams& sp, hipStream_t st);
-void launch_scan_compact(const DetectDeviceView& v, hipStream_t st);
-void launch_scan_compact_trips(const DetectDeviceView& v, int* cnt, int max_trips, hipStream_t st);
-void launch_score(const DetectDeviceView& v, const SweepParams& sp, long long n_valid_bound, long long slot_total, hipStream_t st);
-void launch_gather_corners(const DetectDeviceView& v, const SweepParams& sp, const long long* slots, int n, double* out, hipStream_t st);
-void launch_rank(const DetectDeviceView& v, const RankView& rv, const RankParams& rp, hipStream_t st, long long max_slots_per_box = 0, bool with_corners = true);
-void launch_records(const DetectDeviceView& v, const RankView& rv, int kmax, cs_cuboid* out, hipStream_t st, const double* raw_euler = nullptr, double rebuild_short_sq_bound = -1.0);
-void launch_rp_carry(const RpCarryView& c, JobDesc* jobs, hipStream_t st);
-void launch_rp_save_fallback(const DetectDeviceView& v, const RpSaveView& s, hipStream_t st);
-struct EdgeRoi { int l, t, w, h; long long img_off, cls_off, map_off; };
-struct CopySeg { const void* src; void* dst; unsigned long long bytes; };
-struct CopySegs { CopySeg s[16]; int n; };
-// appends the copy of cnt elements of from's buffer to to's (nothing when cnt is 0)
-template <class To, class From> inline void add_copy(CopySegs& cp, const To& to, const From& from, long long cnt) {
-  if (cnt > 0) { cp.s[cp.n].src = from.p; cp.s[cp.n].dst = to.p; cp.s[cp.n].bytes = sizeof(*from.p) * (unsigned long long)cnt; cp.n++; }
-}
-void launch_multi_copy(const CopySegs& segs, hipStream_t st);
-void launch_edge_maps(const unsigned char* gray, int W, int H, const EdgeRoi* rois, int n_rois, unsigned char* cls_pool, float* map_pool, int max_w, long long max_px, int low, int high,
-                      hipStream_t st);
-void launch_line_setup(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st);
-void launch_line_setup_listed(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                              double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded);
-int line_setup_capacity();
-void launch_gather_ranges(const DetectDeviceView& v, const long long* src_off, const int* count, const long long* dst_off, int n_ranges,
-                          double* o_dist, double* o_angle, double* o_skew, int* o_flag, long long* o_slot, hipStream_t st);
-}  // namespace cs
-
-thread_local std::string g_cs_err;  // shared by both paths (ba_host.cpp reports through cs_set_error_ba)
-void cs_set_error_ba(const std::string& s) { g_cs_err = s; }
+thread_local std::string g_cs_err;  // shared by every path (cs_hip_util.h: cs_set_error)
+void cs_set_error(const std::string& s) { g_cs_err = s; }
 
 namespace {
 
-void set_err(const std::string& s) { g_cs_err = s; }
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      set_err(std::string(#expr) + ": " + hipGetErrorString(_e));                             \
-      return CS_ERR_HIP;                                                                      \
-    }                                                                                         \
-  } while (0)
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+using cs::DevBuf;
+using cs::PinBuf;
+using cs::now_ms;
 
 // Persistent worker pool for the host stages (one per detector; the calling thread takes part).
 class WorkerPool {
@@ -153,38 +111,6 @@ class WorkerPool {
   int n_ = 0, pending_ = 0, limit_ = 0x7fffffff;
   unsigned long long gen_ = 0;
   bool stop_ = false;
-};
-
-// Grow-only device / pinned buffers.
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t n) {
-    if (n <= cap) return CS_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    size_t want = n + n / 8 + 64;
-    HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
-    cap = want;
-    return CS_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-template <class T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t n) {
-    if (n <= cap) return CS_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    size_t want = n + n / 8 + 64;
-    HIP_TRY(hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault));
-    cap = want;
-    return CS_OK;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
 // sin and cos stay two libm calls (the reference's default Debug build makes two calls; glibc's fused
@@ -698,12 +624,6 @@ static bool box_inside_image(const double* box5, int img_w, int img_h) {
   return left >= 0 && top >= 0 && w > 0 && h > 0 && right <= img_w - 1 && bottom <= img_h - 1;
 }
 
-// No C++ exception may cross the C boundary (std::bad_alloc / std::length_error from a host buffer would terminate the caller).
-#define CS_GUARD_BEGIN try {
-#define CS_GUARD_END(fn_name)                                                                      \
-  } catch (const std::bad_alloc&) { set_err(std::string(fn_name) + ": out of host memory"); return CS_ERR_CAPACITY; } \
-    catch (const std::exception& ex) { set_err(std::string(fn_name) + ": " + ex.what()); return CS_ERR_CAPACITY; }
-
 extern "C" {
 
 const char* cs_last_error(void) { return g_cs_err.c_str(); }
@@ -781,36 +701,36 @@ int cs_detector_create(const cs_detect_params* params, int device, cs_detector**
   *out = nullptr;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    set_err("no HIP device visible; libcubeslam_hip has no CPU fallback");
+    cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback");
     return CS_ERR_NO_DEVICE;
   }
-  if (device < 0 || device >= n) { set_err("device index out of range"); return CS_ERR_INVALID_ARG; }
+  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
   CS_GUARD_BEGIN
   struct Guard { cs_detector* d; ~Guard() { if (d) cs_detector_destroy(d); } } g{new cs_detector()};   // freed on every early return
   cs_detector* d = g.d;
   if (params) d->prm = *params; else cs_detect_default_params(&d->prm);
-  if (d->prm.max_cuboid_num < 1 || !(d->prm.yaw_step_deg > 0) || !(d->prm.yaw_range_deg >= 0)) { set_err("bad params"); return CS_ERR_INVALID_ARG; }
+  if (d->prm.max_cuboid_num < 1 || !(d->prm.yaw_step_deg > 0) || !(d->prm.yaw_range_deg >= 0)) { cs_set_error("bad params"); return CS_ERR_INVALID_ARG; }
   d->device = device;
-  HIP_TRY(hipSetDevice(device));
+  CS_HIP_TRY(hipSetDevice(device));
   {
     hipError_t se = hipSuccess;
     d->streams = stream_set_acquire(device, &se);
-    HIP_TRY(se);
+    CS_HIP_TRY(se);
     if (d->streams->own_streams) {
-      HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-      HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
-      HIP_TRY(hipStreamCreateWithFlags(&d->stream3, hipStreamNonBlocking));
-      HIP_TRY(hipStreamCreateWithFlags(&d->stream_idle, hipStreamNonBlocking));
+      CS_HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+      CS_HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
+      CS_HIP_TRY(hipStreamCreateWithFlags(&d->stream3, hipStreamNonBlocking));
+      CS_HIP_TRY(hipStreamCreateWithFlags(&d->stream_idle, hipStreamNonBlocking));
       int prio_low = 0, prio_high = 0;   // (numerically lowest = greatest priority)
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-      HIP_TRY(hipStreamCreateWithPriority(&d->stream_hi, hipStreamNonBlocking, prio_high));
+      CS_HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+      CS_HIP_TRY(hipStreamCreateWithPriority(&d->stream_hi, hipStreamNonBlocking, prio_high));
     } else {
       hipStream_t st4[4];
       d->stream_slot = stream_set_borrow(d->streams, st4);
       d->stream = st4[0]; d->stream2 = st4[1]; d->stream3 = st4[2]; d->stream_hi = st4[3];
     }
   }
-  for (auto& e : d->ev) HIP_TRY(hipEventCreate(&e));
+  for (auto& e : d->ev) CS_HIP_TRY(hipEventCreate(&e));
   int hc = (int)std::thread::hardware_concurrency();
   // default worker count: 64 on an unrestricted 256-thread EPYC (beats 32 and 128); under a cgroup CPU quota three threads
   // per granted CPU (measured under a 16-CPU quota: 48 threads 187 k frames/s, 32: 184 k, 64: 171-181 k, 16: 166-172 k --
@@ -865,7 +785,7 @@ static int batch_create_impl(cs_detector* d, const cs_frame_desc* fr, const unsi
   if (!d || !out || (!fr && n_frames) || n_frames < 0) return CS_ERR_INVALID_ARG;
   *out = nullptr;
   CS_GUARD_BEGIN
-  HIP_TRY(hipSetDevice(d->device));
+  CS_HIP_TRY(hipSetDevice(d->device));
   struct Guard { cs_batch* b; ~Guard() { if (b) cs_batch_destroy(b); } } g{new cs_batch()};   // freed on every early return
   g.b->det = d;
   int rc = batch_fill(d, g.b, fr, grays, n_frames);
@@ -888,12 +808,12 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
     const cs_frame_desc& s = fr[f];
     FrameIn& F = b->frames[f];
     if (!s.K || !s.T_wc || s.n_boxes < 0 || s.n_lines < 0 || (s.n_boxes && (!s.boxes || (!grays && !s.dist_maps))) || (s.n_lines && !s.lines) || (grays && !grays[f])) {
-      set_err("bad frame descriptor"); return CS_ERR_INVALID_ARG;
+      cs_set_error("bad frame descriptor"); return CS_ERR_INVALID_ARG;
     }
     for (int i = 0; i < s.n_boxes; i++)
-      if (!box_inside_image(s.boxes + 5 * (size_t)i, s.img_w, s.img_h)) { set_err("2D box outside the image (need 0 <= x, 0 <= y, x + w <= img_w - 1, y + h <= img_h - 1)"); return CS_ERR_INVALID_ARG; }
+      if (!box_inside_image(s.boxes + 5 * (size_t)i, s.img_w, s.img_h)) { cs_set_error("2D box outside the image (need 0 <= x, 0 <= y, x + w <= img_w - 1, y + h <= img_h - 1)"); return CS_ERR_INVALID_ARG; }
     if (s.T_wc[12] != 0 || s.T_wc[13] != 0 || s.T_wc[14] != 0 || s.T_wc[15] != 1) {
-      set_err("T_wc must have last row 0 0 0 1"); return CS_ERR_INVALID_ARG;
+      cs_set_error("T_wc must have last row 0 0 0 1"); return CS_ERR_INVALID_ARG;
     }
     std::memcpy(F.K, s.K, sizeof(F.K));
     inv3(F.K, F.invK);  // set_calibration (box_proposal_detail.cpp:38-42)
@@ -917,7 +837,7 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
       F.n_heights[i] = nh;
       for (int k = 0; k < nh; k++) {
         const cs_roi& r = F.rois[3 * i + k];
-        if (r.width <= 0 || r.height <= 0 || (!grays && !s.dist_maps[3 * i + k])) { set_err("missing distance map / empty ROI"); return CS_ERR_INVALID_ARG; }
+        if (r.width <= 0 || r.height <= 0 || (!grays && !s.dist_maps[3 * i + k])) { cs_set_error("missing distance map / empty ROI"); return CS_ERR_INVALID_ARG; }
         F.map_offs[3 * i + k] = (long long)map_floats;
         map_floats += (size_t)r.width * r.height + r.width + 1;  // + one row + one float of zero padding
       }
@@ -944,8 +864,8 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
             std::memcpy(&stage[F.map_offs[3 * i + k]], fr[f].dist_maps[3 * i + k], sizeof(float) * (size_t)r.width * r.height);
           }
       }
-      if (pinned) HIP_TRY(hipMemcpyAsync(b->d_maps.p, stage, sizeof(float) * (map_floats + 1), hipMemcpyHostToDevice, d->stream));   // the sweep follows on the same stream
-      else HIP_TRY(hipMemcpy(b->d_maps.p, stage, sizeof(float) * (map_floats + 1), hipMemcpyHostToDevice));
+      if (pinned) CS_HIP_TRY(hipMemcpyAsync(b->d_maps.p, stage, sizeof(float) * (map_floats + 1), hipMemcpyHostToDevice, d->stream));   // the sweep follows on the same stream
+      else CS_HIP_TRY(hipMemcpy(b->d_maps.p, stage, sizeof(float) * (map_floats + 1), hipMemcpyHostToDevice));
     } else {
       // image in: upload the gray images, produce every job's map in place in the pool (Canny + distance transform on the
       // device, box_proposal_detail.cpp:320-327); the padding between the maps stays zero.  All frames share one size.
@@ -955,11 +875,11 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
       int max_w = 1;
       for (int f = 0; f < n_frames; f++) {
         FrameIn& F = b->frames[f];
-        if (F.img_w != W || F.img_h != H) { set_err("cs_batch_create_gray: all frames must have the same image size"); return CS_ERR_INVALID_ARG; }
+        if (F.img_w != W || F.img_h != H) { cs_set_error("cs_batch_create_gray: all frames must have the same image size"); return CS_ERR_INVALID_ARG; }
         for (int i = 0; i < F.n_boxes; i++)
           for (int k = 0; k < F.n_heights[i]; k++) {
             const cs_roi& r = F.rois[3 * i + k];
-            if (r.left < 0 || r.top < 0 || r.left + r.width > W || r.top + r.height > H) { set_err("ROI outside the image"); return CS_ERR_INVALID_ARG; }
+            if (r.left < 0 || r.top < 0 || r.left + r.width > W || r.top + r.height > H) { cs_set_error("ROI outside the image"); return CS_ERR_INVALID_ARG; }
             er.push_back(cs::EdgeRoi{r.left, r.top, r.width, r.height, (long long)f * W * H, cls_tot, F.map_offs[3 * i + k]});
             cls_tot += (long long)r.width * r.height;
             max_w = std::max(max_w, r.width); max_px = std::max(max_px, 4LL * ((r.width + 5) / 4) * (r.height + 2));
@@ -970,15 +890,15 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
       if ((rc = d_gray.ensure((size_t)W * H * std::max(1, n_frames))) || (rc = d_cls.ensure((size_t)cls_tot + 8)) || (rc = d_rois.ensure(er.size() + 1))) { return rc; }
       hipStream_t st = d->stream;
       b->gray_batch = true; b->gray_w = W; b->gray_h = H; b->edge_n_rois = (int)er.size(); b->edge_max_w = max_w; b->edge_max_px = max_px; b->gray_cur = 0;
-      HIP_TRY(hipMemsetAsync(b->d_maps.p, 0, sizeof(float) * (map_floats + 1), st));
-      for (int f = 0; f < n_frames; f++) HIP_TRY(hipMemcpyAsync(d_gray.p + (size_t)f * W * H, grays[f], (size_t)W * H, hipMemcpyHostToDevice, st));
+      CS_HIP_TRY(hipMemsetAsync(b->d_maps.p, 0, sizeof(float) * (map_floats + 1), st));
+      for (int f = 0; f < n_frames; f++) CS_HIP_TRY(hipMemcpyAsync(d_gray.p + (size_t)f * W * H, grays[f], (size_t)W * H, hipMemcpyHostToDevice, st));
       if (!er.empty()) {
         edge_rois_largest_first(er);
-        HIP_TRY(hipMemcpyAsync(d_rois.p, er.data(), sizeof(cs::EdgeRoi) * er.size(), hipMemcpyHostToDevice, st));
+        CS_HIP_TRY(hipMemcpyAsync(d_rois.p, er.data(), sizeof(cs::EdgeRoi) * er.size(), hipMemcpyHostToDevice, st));
         cs::launch_edge_maps(d_gray.p, W, H, d_rois.p, (int)er.size(), d_cls.p, b->d_maps.p, max_w, max_px, 80, 200, st);
-        HIP_TRY(hipGetLastError());
+        CS_HIP_TRY(hipGetLastError());
       }
-      HIP_TRY(hipStreamSynchronize(st));      // (the host arrays `grays` and `er` are read by the copies above)
+      CS_HIP_TRY(hipStreamSynchronize(st));      // (the host arrays `grays` and `er` are read by the copies above)
     }
   }
   return batch_layout(d, b);
@@ -992,7 +912,7 @@ static int batch_layout(cs_detector* d, cs_batch* b) {
     for (int f = 0; f < n_frames; f++) std::memcpy(&ik[9 * f], b->frames[f].invK, 9 * sizeof(double));
     rc = b->d_invK.ensure(ik.size());
     if (rc) { return rc; }
-    HIP_TRY(hipMemcpy(b->d_invK.p, ik.data(), sizeof(double) * ik.size(), hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(b->d_invK.p, ik.data(), sizeof(double) * ik.size(), hipMemcpyHostToDevice));
     // line segments (already left-to-right aligned), pooled, for the device-side line setup
     std::vector<int> lp(n_frames + 1, 0);
     b->device_setup = true;
@@ -1001,8 +921,8 @@ static int batch_layout(cs_detector* d, cs_batch* b) {
     for (int f = 0; f < n_frames; f++) if (b->frames[f].n_lines) std::memcpy(&fl[4 * (size_t)lp[f]], b->frames[f].lines.data(), 32 * (size_t)b->frames[f].n_lines);
     rc = b->d_frame_lines.ensure(fl.size()); if (rc) { return rc; }
     rc = b->d_frame_line_ptr.ensure(lp.size()); if (rc) { return rc; }
-    HIP_TRY(hipMemcpy(b->d_frame_lines.p, fl.data(), 8 * fl.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_frame_line_ptr.p, lp.data(), 4 * lp.size(), hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(b->d_frame_lines.p, fl.data(), 8 * fl.size(), hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(b->d_frame_line_ptr.p, lp.data(), 4 * lp.size(), hipMemcpyHostToDevice));
   }
   {
     b->job_base.assign(n_frames + 1, 0); b->box_base.assign(n_frames + 1, 0); b->line_base.assign(n_frames + 1, 0);
@@ -1041,24 +961,24 @@ int cs_batch_create_gray(cs_detector* d, const cs_frame_desc* fr, const unsigned
 // + sweep) runs beside an upload.  Returns at once.
 int cs_batch_refill_gray(cs_detector* d, cs_batch* b, const unsigned char* const* grays) {
   if (!d || !b || !grays || b->det != d) return CS_ERR_INVALID_ARG;
-  if (!b->gray_batch) { set_err("cs_batch_refill_gray: the batch was not created by cs_batch_create_gray"); return CS_ERR_INVALID_ARG; }
+  if (!b->gray_batch) { cs_set_error("cs_batch_refill_gray: the batch was not created by cs_batch_create_gray"); return CS_ERR_INVALID_ARG; }
   CS_GUARD_BEGIN
-  HIP_TRY(hipSetDevice(d->device));
+  CS_HIP_TRY(hipSetDevice(d->device));
   const size_t px = (size_t)b->gray_w * b->gray_h;
   const int n = b->n_frames;
   if (n <= 0 || px == 0) return CS_OK;
   int rc;
   if ((rc = b->d_gray2.ensure(px * (size_t)n))) return rc;
-  if (b->n_refill == 2) { set_err("cs_batch_refill_gray: two uploads are queued already (one per image buffer); cs_batch_submit / cs_batch_run takes the older one"); return CS_ERR_INVALID_ARG; }
+  if (b->n_refill == 2) { cs_set_error("cs_batch_refill_gray: two uploads are queued already (one per image buffer); cs_batch_submit / cs_batch_run takes the older one"); return CS_ERR_INVALID_ARG; }
   if (!b->copy_stream) {
     // (lowest priority: bulk traffic, and a hardware queue of its own)
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    HIP_TRY(hipStreamCreateWithPriority(&b->copy_stream, hipStreamNonBlocking, prio_least));
-    for (auto& e : b->ev_copied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : b->ev_edge_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->ev_edge_done[0], d->stream));      // buffer 0's reader so far: the front end of cs_batch_create_gray (finished)
-    HIP_TRY(hipEventRecord(b->ev_edge_done[1], d->stream));
+    CS_HIP_TRY(hipStreamCreateWithPriority(&b->copy_stream, hipStreamNonBlocking, prio_least));
+    for (auto& e : b->ev_copied) CS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : b->ev_edge_done) CS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    CS_HIP_TRY(hipEventRecord(b->ev_edge_done[0], d->stream));      // buffer 0's reader so far: the front end of cs_batch_create_gray (finished)
+    CS_HIP_TRY(hipEventRecord(b->ev_edge_done[1], d->stream));
   }
   // Which buffer: the one that is neither being read (gray_cur, or -- with an upload already queued -- that upload's target, which the next
   // submit's front end reads) ...  With one upload queued the new one goes BEHIND it on the copy stream into the buffer of the current maps:
@@ -1066,7 +986,7 @@ int cs_batch_refill_gray(cs_detector* d, cs_batch* b, const unsigned char* const
   const int nxt = b->n_refill == 1 ? 1 - b->refill_q[0] : 1 - b->gray_cur;
   unsigned char* dst = nxt ? b->d_gray2.p : b->d_gray.p;
   // the buffer's last reader -- the front end queued when it became current -- must be through before it is overwritten
-  HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_edge_done[nxt], 0));
+  CS_HIP_TRY(hipStreamWaitEvent(b->copy_stream, b->ev_edge_done[nxt], 0));
   // images that follow each other in host memory go up as one copy (a batch decoded into one pinned block: a single DMA)
   for (int f = 0; f < n;) {
     int g = f + 1;
@@ -1074,10 +994,10 @@ int cs_batch_refill_gray(cs_detector* d, cs_batch* b, const unsigned char* const
     // The copy engine, not the shader cores: a kernel that reads pinned host memory keeps hundreds of PCIe reads in flight through the same
     // request queues the other kernels' HBM traffic takes -- with it beside them the distance transform ran 0.8 -> 7.7 ms and Canny
     // 2.4 -> 7.5 ms (profiles/r6_image_in_timeline.txt); the engine's 8.3 ms for 467 MB is the same and costs the kernels nothing.
-    HIP_TRY(hipMemcpyAsync(dst + (size_t)f * px, grays[f], px * (size_t)(g - f), hipMemcpyHostToDevice, b->copy_stream));
+    CS_HIP_TRY(hipMemcpyAsync(dst + (size_t)f * px, grays[f], px * (size_t)(g - f), hipMemcpyHostToDevice, b->copy_stream));
     f = g;
   }
-  HIP_TRY(hipEventRecord(b->ev_copied[nxt], b->copy_stream));
+  CS_HIP_TRY(hipEventRecord(b->ev_copied[nxt], b->copy_stream));
   b->refill_q[b->n_refill++] = nxt;
   return CS_OK;
   CS_GUARD_END("cs_batch_refill_gray")
@@ -1089,13 +1009,13 @@ int cs_batch_refill_gray(cs_detector* d, cs_batch* b, const unsigned char* const
 static int batch_flush_refill(cs_detector* d, cs_batch* b) {
   if (b->n_refill == 0) return CS_OK;
   const int nxt = b->refill_q[0];
-  HIP_TRY(hipEventSynchronize(b->ev_copied[nxt]));
+  CS_HIP_TRY(hipEventSynchronize(b->ev_copied[nxt]));
   hipStream_t st = d->stream;
   if (b->edge_n_rois > 0) {
     cs::launch_edge_maps(nxt ? b->d_gray2.p : b->d_gray.p, b->gray_w, b->gray_h, b->d_edge_rois.p, b->edge_n_rois, b->d_cls.p, b->d_maps.p, b->edge_max_w, b->edge_max_px, 80, 200, st);
-    HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(b->ev_edge_done[nxt], st));
+  CS_HIP_TRY(hipEventRecord(b->ev_edge_done[nxt], st));
   b->gray_cur = nxt;
   b->refill_q[0] = b->refill_q[1]; b->refill_q[1] = -1; b->n_refill--;
   return CS_OK;
@@ -1104,8 +1024,8 @@ static int batch_flush_refill(cs_detector* d, cs_batch* b) {
 int cs_batch_refill_wait(cs_batch* b) {
   if (!b) return CS_ERR_INVALID_ARG;
   if (!b->copy_stream) return CS_OK;
-  HIP_TRY(hipSetDevice(b->det->device));
-  HIP_TRY(hipStreamSynchronize(b->copy_stream));
+  CS_HIP_TRY(hipSetDevice(b->det->device));
+  CS_HIP_TRY(hipStreamSynchronize(b->copy_stream));
   return CS_OK;
 }
 
@@ -1246,7 +1166,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   hipStream_t st = d->stream;
   const int KMAX = P.max_cuboid_num;
   double t0 = now_ms(), tq = t0;
-  if (!S.done) { HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) HIP_TRY(hipEventCreate(&e)); }
+  if (!S.done) { CS_HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) CS_HIP_TRY(hipEventCreate(&e)); }
   S.f0 = f0; S.f1 = f1;
   const int nf = f1 - f0;
   // ---- per frame, in parallel and straight into the pinned staging pools: job descriptors + sample lists (everything
@@ -1258,9 +1178,9 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   const size_t nj = (size_t)(b->job_base[f1] - jb0), n_lines = (size_t)(b->line_base[f1] - ln0);
   const int YCAP = (int)(2.0 * P.yaw_range_deg / std::max(1e-9, P.yaw_step_deg)) + 3;
   const size_t n_yaw = (size_t)nf * YCAP, n_top = (size_t)(b->top_base[b->box_base[f1]] - tp0);
-  if ((long long)nj * 1 > 0x7fffffffLL || (long long)n_lines > 0x7fffffffLL) { set_err("chunk too large"); return CS_ERR_CAPACITY; }
+  if ((long long)nj * 1 > 0x7fffffffLL || (long long)n_lines > 0x7fffffffLL) { cs_set_error("chunk too large"); return CS_ERR_CAPACITY; }
   S.nj = nj;
-  if (nj == 0) { S.nb = 0; S.slot_total = 0; S.vp_total = 0; S.in_flight = true; C.tm->setup_host_ms += now_ms() - t0; HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
+  if (nj == 0) { S.nb = 0; S.slot_total = 0; S.vp_total = 0; S.in_flight = true; C.tm->setup_host_ms += now_ms() - t0; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
   int rc;
 #define PENS(buf, n) do { rc = (buf).ensure(n); if (rc) return rc; } while (0)
   PENS(S.h_jobs_in, nj); PENS(S.h_slot_prefix, nj + 1); PENS(S.h_vp_prefix, nj + 1); PENS(S.h_yaw, n_yaw + 1); PENS(S.h_yaw_c, n_yaw + 1); PENS(S.h_yaw_s, n_yaw + 1);
@@ -1307,7 +1227,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
       }
     }
   });
-  if (overflow) { set_err("yaw sample list exceeds its capacity"); return CS_ERR_CAPACITY; }
+  if (overflow) { cs_set_error("yaw sample list exceeds its capacity"); return CS_ERR_CAPACITY; }
   MARK(0, tq);   // per-frame jobs + sample lists
   // ---- slot / vanishing-point prefixes and the box table: one serial pass over the jobs
   size_t nb = 0;
@@ -1339,7 +1259,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
       for (int q = 0; q < NBK; q++) cnt[q + 1] += cnt[q];
       for (size_t j = 0; j < nj; j++) S.h_ls_order.p[cnt[bucket(S.h_jobs_in.p[j])]++] = (int)j;
     }
-    if (vo > 0x7fffffffLL) { set_err("too many yaw samples in one chunk"); return CS_ERR_CAPACITY; }
+    if (vo > 0x7fffffffLL) { cs_set_error("too many yaw samples in one chunk"); return CS_ERR_CAPACITY; }
   }
   S.nb = nb;
   MARK(1, tq);   // prefixes + box table
@@ -1383,7 +1303,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     if (n_top) memcpy(hb + o_tx, S.h_top_x.p, sizeof(int) * n_top);
     if (nb) { memcpy(hb + o_b0, S.h_box_job0.p, sizeof(int) * nb); memcpy(hb + o_bn, S.h_box_njobs.p, sizeof(int) * nb); }
     if (!d->streams->own_streams) enqueue.lock();
-    HIP_TRY(hipMemcpyAsync(db, hb, in_end, hipMemcpyHostToDevice, st));
+    CS_HIP_TRY(hipMemcpyAsync(db, hb, in_end, hipMemcpyHostToDevice, st));
     p_ls_order = reinterpret_cast<int*>(db + o_ls); p_jobs = reinterpret_cast<cs::JobDesc*>(db + o_jobs); p_slot_prefix = reinterpret_cast<long long*>(db + o_sp);
     p_vp_prefix = reinterpret_cast<int*>(db + o_vp); p_yaw = reinterpret_cast<double*>(db + o_y); p_yaw_c = reinterpret_cast<double*>(db + o_yc); p_yaw_s = reinterpret_cast<double*>(db + o_ys);
     p_top_x = reinterpret_cast<int*>(db + o_tx); p_box_job0 = reinterpret_cast<int*>(db + o_b0); p_box_njobs = reinterpret_cast<int*>(db + o_bn);
@@ -1411,43 +1331,43 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   hipStream_t stB = nullptr, stC = nullptr;
   sweep_side_streams(d, &stB, &stC);
   if (stB != st) {
-    HIP_TRY(hipEventRecord(S.ev[7], st));                      // inputs resident
-    HIP_TRY(hipStreamWaitEvent(stB, S.ev[7], 0));
+    CS_HIP_TRY(hipEventRecord(S.ev[7], st));                      // inputs resident
+    CS_HIP_TRY(hipStreamWaitEvent(stB, S.ev[7], 0));
   }
-  HIP_TRY(hipEventRecord(S.ev[8], stB));
+  CS_HIP_TRY(hipEventRecord(S.ev[8], stB));
   // vanishing points, corner construction and ordered compaction of a job in one workgroup (candidate_compact_kernel); the compacted rows
   // of job j start at slot_prefix[j]: no scan over all jobs between this kernel and the scorer
   v.blk_info = S.blk_info.p;
-  HIP_TRY(hipMemsetAsync(S.blk_info.p, 0, sizeof(int), stB));
+  CS_HIP_TRY(hipMemsetAsync(S.blk_info.p, 0, sizeof(int), stB));
   cs::launch_candidate_compact(v, C.sp, stB);
-  HIP_TRY(hipEventRecord(S.ev[9], stB));
-  HIP_TRY(hipEventRecord(S.ev[10], stB));
-  HIP_TRY(hipEventRecord(S.ev[0], st));
+  CS_HIP_TRY(hipEventRecord(S.ev[9], stB));
+  CS_HIP_TRY(hipEventRecord(S.ev[10], stB));
+  CS_HIP_TRY(hipEventRecord(S.ev[0], st));
   cs::launch_line_setup_listed(p_jobs, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
                                stC, S.ev[0], S.ev[12], S.ls_crowded.p);
-  HIP_TRY(hipEventRecord(S.ev[1], st));
+  CS_HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::launch_vp_support_only(v, C.sp, S.vp_total, st, 1);      // (this path's jobs have one roll/pitch sample: jd.RP = 1 above)
-  HIP_TRY(hipEventRecord(S.ev[2], st));
-  if (stB != st) HIP_TRY(hipStreamWaitEvent(st, S.ev[10], 0));
-  HIP_TRY(hipEventRecord(S.ev[4], st));
+  CS_HIP_TRY(hipEventRecord(S.ev[2], st));
+  if (stB != st) CS_HIP_TRY(hipStreamWaitEvent(st, S.ev[10], 0));
+  CS_HIP_TRY(hipEventRecord(S.ev[4], st));
   cs::launch_score(v, C.sp, slot_total, slot_total, st);
-  HIP_TRY(hipEventRecord(S.ev[5], st));
+  CS_HIP_TRY(hipEventRecord(S.ev[5], st));
   cs::RankView rv{};
   rv.box_job0 = p_box_job0; rv.box_njobs = p_box_njobs; rv.n_boxes = (int)nb; rv.winners = S.winners.p; rv.win_count = p_win_count; rv.fallback = p_fallback;
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
   cs::launch_rank(v, rv, rkp, st, 0, false);          // (the host reads no winner of the device: record_kernel rebuilds their corners)
   cs::launch_records(v, rv, KMAX, p_records, st, nullptr, rkp.short_sq_bound);     // the records of the boxes the device ranked: only they come back
-  HIP_TRY(hipEventRecord(S.ev[6], st));
-  HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipEventRecord(S.ev[6], st));
+  CS_HIP_TRY(hipGetLastError());
   if (S.merged_io) {
-    HIP_TRY(hipMemcpyAsync(S.h_tab_arena.p + S.o_jobs, S.tab_arena.p + S.o_jobs, S.o_end - S.o_jobs, hipMemcpyDeviceToHost, st));   // unpacked in pipe_finish
+    CS_HIP_TRY(hipMemcpyAsync(S.h_tab_arena.p + S.o_jobs, S.tab_arena.p + S.o_jobs, S.o_end - S.o_jobs, hipMemcpyDeviceToHost, st));   // unpacked in pipe_finish
   } else {   // the results: written to the pinned host pools by one kernel
     cs::CopySegs cp{};
     cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, S.h_win_count, S.win_count, nb); cs::add_copy(cp, S.h_fallback, S.fallback, nb);
     cs::add_copy(cp, S.h_job_valid, S.job_valid, nj); cs::add_copy(cp, S.h_job_cbase, S.job_cbase, nj + 1);      // (the job table itself is not read back: pipe_finish works from the host's own copy)
     cs::launch_multi_copy(cp, st);
   }
-  HIP_TRY(hipEventRecord(S.done, st));
+  CS_HIP_TRY(hipEventRecord(S.done, st));
   S.in_flight = true;
   S.counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
   MARK(3, tq);   // allocations + enqueue of copies and kernels
@@ -1461,7 +1381,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   cs_detect_timing& tm = *C.tm;
   double tw = now_ms(), tq = tw;
   if (S.counted_busy) { S.counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); }      // (before the wait: an error return must not leave the counts up)
-  HIP_TRY(hipEventSynchronize(S.done));
+  CS_HIP_TRY(hipEventSynchronize(S.done));
   tm.d2h_ms += now_ms() - tw;   // time the host actually waited for the GPU
   S.in_flight = false;
   const size_t nj = S.nj, nb = S.nb;
@@ -1475,12 +1395,12 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   double t0 = now_ms();
   {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[1], S.ev[2])); tm.vp_kernel_ms += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[8], S.ev[9])); tm.cand_kernel_ms += ms;    // second stream: vanishing points + corners
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[9], S.ev[10])); tm.compact_ms += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[4], S.ev[5])); tm.score_kernel_ms += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[5], S.ev[6])); tm.rank_kernel_ms += ms;
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[1], S.ev[2])); tm.vp_kernel_ms += ms;
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[8], S.ev[9])); tm.cand_kernel_ms += ms;    // second stream: vanishing points + corners
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[9], S.ev[10])); tm.compact_ms += ms;
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[4], S.ev[5])); tm.score_kernel_ms += ms;
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[5], S.ev[6])); tm.rank_kernel_ms += ms;
     tm.cand_kernel_launches += 1;
     long long n_valid = 0;      // (the capacity layout has no running total: job_cbase[j] = slot_prefix[j])
     for (size_t j = 0; j < nj; j++) n_valid += S.h_job_valid.p[j];
@@ -1517,7 +1437,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     // the range lists are read from, and the columns written to, the pinned host pools by the gather kernel itself (coalesced rows; no
     // copy engine between the device and a host that is waiting for a few kilobytes)
     cs::launch_gather_ranges(S.view, S.h_fb_src.p, S.h_fb_cnt.p, S.h_fb_dst.p, (int)nr, S.h_fb_dist.p, S.h_fb_angle.p, S.h_fb_skew.p, S.h_fb_flag.p, S.h_fb_slot.p, st2);
-    HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipGetLastError());
   }
   MARK(5, tq);   // tie lists + gather enqueue
   // ---- records of the winners.  The boxes the device ranked are written while the tie boxes' columns travel.
@@ -1599,7 +1519,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   if (fbq.size() <= 64) {
     // a handful of tie boxes (the usual case): their columns are a few kilobytes and already here; their exact ranking
     // (tens of microseconds each) rides in the same parallel pass as the records of the other boxes, first in the queue
-    if (!fb_src.empty()) HIP_TRY(hipStreamSynchronize(st2));
+    if (!fb_src.empty()) CS_HIP_TRY(hipStreamSynchronize(st2));
     MARK(7, tq);   // wait for the tie columns
     const int nfb = (int)fbq.size();
     constexpr int RCH = 256;           // records are a 400-byte copy each: hand them out in chunks
@@ -1612,7 +1532,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   } else {
     d->pool->run((int)nb, records);
     MARK(6, tq);   // records of the device-ranked boxes, written while the tie boxes' columns travel
-    if (!fb_src.empty()) HIP_TRY(hipStreamSynchronize(st2));
+    if (!fb_src.empty()) CS_HIP_TRY(hipStreamSynchronize(st2));
     MARK(7, tq);   // wait for the tie columns
     d->pool->run((int)fbq.size(), [&](int z) { rank_on_host((size_t)fbq[z]); });
   }
@@ -1624,7 +1544,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
       PENS(S.h_win_slots, ws.size()); PENS(S.h_win_corners, 16 * ws.size());
       std::copy(ws.begin(), ws.end(), S.h_win_slots.p);
       cs::launch_gather_corners(S.view, C.sp, S.h_win_slots.p, (int)ws.size(), S.h_win_corners.p, st2);     // (pinned host memory on both sides)
-      HIP_TRY(hipStreamSynchronize(st2));
+      CS_HIP_TRY(hipStreamSynchronize(st2));
       const double* hc = S.h_win_corners.p;
       size_t z = 0;
       for (int q : fbq) for (auto& w : fb_winners[q]) { std::memcpy(w.corners, &hc[16 * z], 128); z++; }
@@ -1655,7 +1575,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   hipStream_t st = d->stream;
   const int KMAX = P.max_cuboid_num, NF = b->n_frames, MB = b->max_boxes;
   double t0 = now_ms();
-  if (!S.done) { HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) HIP_TRY(hipEventCreate(&e)); }
+  if (!S.done) { CS_HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) CS_HIP_TRY(hipEventCreate(&e)); }
   S.rp_mode = true;
   S.f0 = 0; S.f1 = NF;
   int rc;
@@ -1666,7 +1586,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   const int NT = 1 + max_rp;
   const int YCAP = (int)(2.0 * P.yaw_range_deg / std::max(1e-9, P.yaw_step_deg)) + 3;
   const size_t n_yaw = (size_t)NF * NT * YCAP;
-  if (n_yaw > 0x7fffffffULL) { set_err("too many yaw samples"); return CS_ERR_CAPACITY; }
+  if (n_yaw > 0x7fffffffULL) { cs_set_error("too many yaw samples"); return CS_ERR_CAPACITY; }
   PENS(S.h_yaw, n_yaw + 1); PENS(S.h_yaw_c, n_yaw + 1); PENS(S.h_yaw_s, n_yaw + 1); PENS(S.h_rp_tab_count, (size_t)NF * NT + 1); PENS(S.h_rp_raw_euler, 3 * (size_t)NF + 1);
   std::atomic<int> overflow{0};
   std::vector<int> ycap_f(NF, 0);     // longest list of the frame: its boxes' slots are laid out for it
@@ -1685,7 +1605,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     for (size_t y = 0; y < yl.size(); y++) { yw[y] = yl[y]; yc[y] = h_cos(yl[y]); ys[y] = h_sin(yl[y]); }
     *cnt = (int)yl.size();
   });
-  if (overflow) { set_err("yaw sample list exceeds its capacity"); return CS_ERR_CAPACITY; }
+  if (overflow) { cs_set_error("yaw sample list exceeds its capacity"); return CS_ERR_CAPACITY; }
   for (int f = 0; f < NF; f++) {
     for (int i = 0; i < NT; i++) ycap_f[f] = std::max(ycap_f[f], S.h_rp_tab_count.p[(size_t)f * NT + i]);
     for (int e = 0; e < 3; e++) S.h_rp_raw_euler.p[3 * f + e] = (*C.cam_raw)[f].euler[e];
@@ -1750,17 +1670,17 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     }
     Rr.nj = ji - Rr.j0; Rr.nb = nb_tot - Rr.b0; Rr.slot_cap = so; Rr.vp_cap = (int)vo;
     S.h_slot_prefix.p[ji + r] = so; S.h_vp_prefix.p[ji + r] = (int)vo;
-    if (vo > 0x7fffffffLL || so > 0x7fffffff00LL) { set_err("too many samples in one round"); return CS_ERR_CAPACITY; }
+    if (vo > 0x7fffffffLL || so > 0x7fffffff00LL) { cs_set_error("too many samples in one round"); return CS_ERR_CAPACITY; }
     slot_cap_max = std::max(slot_cap_max, so); vp_cap_max = std::max(vp_cap_max, (int)vo); nj_round_max = std::max(nj_round_max, Rr.nj);
     slots_all += so;
   }
   const size_t nj = ji, nb = nb_tot;
   S.nj = nj; S.nb = nb; S.slot_total = slots_all; S.vp_total = vp_cap_max;
-  if (n_lines > 0x7fffffffLL) { set_err("chunk too large"); return CS_ERR_CAPACITY; }
+  if (n_lines > 0x7fffffffLL) { cs_set_error("chunk too large"); return CS_ERR_CAPACITY; }
   for (size_t j = 0; j < nj; j++) S.h_ls_order.p[j] = (int)j;
   C.tm->setup_host_ms += now_ms() - t0;
   C.tm->n_jobs += (long long)nj;
-  if (nj == 0) { S.in_flight = true; HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
+  if (nj == 0) { S.in_flight = true; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
   // ---- device buffers; the per-round arrays are sized for the largest round and reused from round to round (one stream: in order)
   PENS(S.ls_order, nj); PENS(S.jobs, nj); PENS(S.slot_prefix, nj + MB + 1); PENS(S.vp_prefix, nj + MB + 1); PENS(S.job_valid, nj); PENS(S.job_cbase, nj + MB + 1);
   const int max_trips = (int)std::min<long long>((max_job_slots + 4095) / 4096, 1 << 20);      // compaction trips of the largest job (4096 slots each)
@@ -1777,12 +1697,12 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   PENS(S.ls_crowded, 2 * (nj + 1) + 2);
   PENS(S.rp_box_base, nb + 1); PENS(S.rp_pool_used, 1); PENS(S.h_rp_box_base, nb + 1); PENS(S.h_rp_pool_used, 1); PENS(S.h_rp_last_slot, nb + 1); PENS(S.h_job_valid, nj + 1); PENS(S.h_jobs_out, nj + 1);
   PENS(S.rp_cur_idx, (size_t)NF + 1); PENS(S.rp_tab_count, (size_t)NF * NT + 1); PENS(S.rp_maps, 3 * (size_t)MB * NF + 1); PENS(S.rp_raw_euler, 3 * (size_t)NF + 1);
-  while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
+  while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; CS_HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
   std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);      // all rounds of this batch back to back in the shared streams (see pipe_launch)
   if (!d->streams->own_streams) enqueue.lock();
   hipStream_t stB_unused = nullptr, stC = nullptr;
   sweep_side_streams(d, &stB_unused, &stC);
-  HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
+  CS_HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
   {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
     cs::CopySegs cp{};
     cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, S.jobs, S.h_jobs_in, nj); cs::add_copy(cp, S.slot_prefix, S.h_slot_prefix, nj + MB);
@@ -1792,13 +1712,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     cs::add_copy(cp, S.rp_maps, S.h_rp_maps, 3LL * MB * NF); cs::add_copy(cp, S.rp_raw_euler, S.h_rp_raw_euler, 3LL * NF);
     cs::launch_multi_copy(cp, st);
   }
-  HIP_TRY(hipMemsetAsync(S.job_valid.p, 0, sizeof(int) * nj, st));
-  HIP_TRY(hipMemsetAsync(S.rp_cur_idx.p, 0, sizeof(int) * NF, st));
-  HIP_TRY(hipEventRecord(S.ev[0], st));
+  CS_HIP_TRY(hipMemsetAsync(S.job_valid.p, 0, sizeof(int) * nj, st));
+  CS_HIP_TRY(hipMemsetAsync(S.rp_cur_idx.p, 0, sizeof(int) * NF, st));
+  CS_HIP_TRY(hipEventRecord(S.ev[0], st));
   // ---- line setup of every job of the batch at once (it depends on the box and the frame's segments only)
   cs::launch_line_setup_listed(S.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
                                stC, S.ev[0], S.ev[12], S.ls_crowded.p);
-  HIP_TRY(hipEventRecord(S.ev[1], st));
+  CS_HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
   for (int r = 0; r < MB; r++) {
     const PipeSlot::RpRound& Rr = S.rp_rounds[r];
@@ -1822,15 +1742,15 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       c.tab_count = S.rp_tab_count.p; c.cur_idx = S.rp_cur_idx.p;
       cs::launch_rp_carry(c, S.jobs.p + Rr.j0, st);
     }
-    HIP_TRY(hipEventRecord(re[0], st));
+    CS_HIP_TRY(hipEventRecord(re[0], st));
     cs::launch_vp_points(v, Rr.vp_cap, st);
     cs::launch_candidates(v, C.sp, Rr.slot_cap, st);
     cs::launch_scan_compact_trips(v, S.rp_trip_cnt.p, max_trips, st);
-    HIP_TRY(hipEventRecord(re[1], st));
+    CS_HIP_TRY(hipEventRecord(re[1], st));
     cs::launch_vp_support_only(v, C.sp, Rr.vp_cap, st);
-    HIP_TRY(hipEventRecord(re[2], st));
+    CS_HIP_TRY(hipEventRecord(re[2], st));
     cs::launch_score(v, C.sp, Rr.slot_cap, Rr.slot_cap, st);
-    HIP_TRY(hipEventRecord(re[3], st));
+    CS_HIP_TRY(hipEventRecord(re[3], st));
     cs::RankView rv{};
     rv.box_job0 = S.box_job0.p + Rr.b0; rv.box_njobs = S.box_njobs.p + Rr.b0; rv.n_boxes = (int)Rr.nb; rv.winners = S.winners.p + Rr.b0 * KMAX;
     rv.win_count = S.win_count.p + Rr.b0; rv.fallback = S.fallback.p + Rr.b0; rv.last_slot = S.rp_last_slot.p + Rr.b0;
@@ -1842,10 +1762,10 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       sv.box_base = S.rp_box_base.p + Rr.b0; sv.p_dist = S.fb_dist.p; sv.p_angle = S.fb_angle.p; sv.p_skew = S.fb_skew.p; sv.p_flag = S.fb_flag.p; sv.p_slot = S.fb_slot.p;
       cs::launch_rp_save_fallback(v, sv, st);
     }
-    HIP_TRY(hipEventRecord(re[4], st));
-    HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipEventRecord(re[4], st));
+    CS_HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(S.ev[6], st));
+  CS_HIP_TRY(hipEventRecord(S.ev[6], st));
   {
     cs::CopySegs cp{};
     cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, S.h_win_count, S.win_count, nb); cs::add_copy(cp, S.h_fallback, S.fallback, nb);
@@ -1853,7 +1773,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     cs::add_copy(cp, S.h_rp_last_slot, S.rp_last_slot, nb); cs::add_copy(cp, S.h_rp_box_base, S.rp_box_base, nb); cs::add_copy(cp, S.h_rp_pool_used, S.rp_pool_used, 1);
     cs::launch_multi_copy(cp, st);
   }
-  HIP_TRY(hipEventRecord(S.done, st));
+  CS_HIP_TRY(hipEventRecord(S.done, st));
   S.in_flight = true;
   S.counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
   return CS_OK;
@@ -1866,21 +1786,21 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   cs_detect_timing& tm = *C.tm;
   double tw = now_ms();
   if (S.counted_busy) { S.counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); }      // (before the wait: an error return must not leave the counts up)
-  HIP_TRY(hipEventSynchronize(S.done));
+  CS_HIP_TRY(hipEventSynchronize(S.done));
   tm.d2h_ms += now_ms() - tw;
   S.in_flight = false;
   if (S.nj == 0) return CS_OK;
   double t0 = now_ms();
   {
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
+    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
     for (int r = 0; r < MB; r++) {
       if (S.rp_rounds[r].nj == 0) continue;
       hipEvent_t* re = &S.rp_ev[5 * (size_t)r];
-      HIP_TRY(hipEventElapsedTime(&ms, re[0], re[1])); tm.cand_kernel_ms += ms;      // vanishing points, corners, compaction
-      HIP_TRY(hipEventElapsedTime(&ms, re[1], re[2])); tm.vp_kernel_ms += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, re[2], re[3])); tm.score_kernel_ms += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, re[3], re[4])); tm.rank_kernel_ms += ms;      // ranking, records, the flagged boxes' columns
+      CS_HIP_TRY(hipEventElapsedTime(&ms, re[0], re[1])); tm.cand_kernel_ms += ms;      // vanishing points, corners, compaction
+      CS_HIP_TRY(hipEventElapsedTime(&ms, re[1], re[2])); tm.vp_kernel_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, re[2], re[3])); tm.score_kernel_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, re[3], re[4])); tm.rank_kernel_ms += ms;      // ranking, records, the flagged boxes' columns
       tm.cand_kernel_launches += 1;
     }
     tm.n_slots += S.slot_total;
@@ -1906,7 +1826,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
       cs::add_copy(cp, S.h_fb_dist, S.fb_dist, used); cs::add_copy(cp, S.h_fb_angle, S.fb_angle, used); cs::add_copy(cp, S.h_fb_skew, S.fb_skew, used);
       cs::add_copy(cp, S.h_fb_flag, S.fb_flag, used); cs::add_copy(cp, S.h_fb_slot, S.fb_slot, used);
       cs::launch_multi_copy(cp, st2);
-      HIP_TRY(hipStreamSynchronize(st2));
+      CS_HIP_TRY(hipStreamSynchronize(st2));
     }
     const std::vector<std::vector<CamCache>>& cam_rp = *C.cam_rp_all;
     // boxes of a frame in round order
@@ -2079,7 +1999,7 @@ static int batch_collect_impl(cs_detector* d, cs_batch* b) {
   std::unique_ptr<BatchRunState> rs(b->run_state);
   b->run_state = nullptr;
   if (!rs->deferred) return CS_OK;
-  HIP_TRY(hipSetDevice(d->device));
+  CS_HIP_TRY(hipSetDevice(d->device));
   int rc = rs->rp_lean ? rp_finish(rs->C, b->pipe[0]) : pipe_finish(rs->C, b->pipe[0], rs->cam_rp);
   if (rc) return rc;
   rs->tm.total_ms = now_ms() - rs->t_begin;
@@ -2095,8 +2015,8 @@ static int batch_collect_impl(cs_detector* d, cs_batch* b) {
 }
 static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_counts, bool defer) {
   if (!d || !b || b->det != d || !out || !out_counts) return CS_ERR_INVALID_ARG;
-  if (b->run_state) { set_err("cs_batch_submit: the previous submit of this batch has not been collected"); return CS_ERR_INVALID_ARG; }
-  HIP_TRY(hipSetDevice(d->device));
+  if (b->run_state) { cs_set_error("cs_batch_submit: the previous submit of this batch has not been collected"); return CS_ERR_INVALID_ARG; }
+  CS_HIP_TRY(hipSetDevice(d->device));
   { const int rcf = batch_flush_refill(d, b); if (rcf) return rcf; }      // (cs_batch_refill_gray: the new images' maps, in front of this sweep)
   std::unique_ptr<BatchRunState> rs_owner(new BatchRunState());
   BatchRunState* rs = rs_owner.get();
@@ -2160,7 +2080,7 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
       for (size_t k = 0; k < cam_rp[f].size(); k++) b->h_rp.p[rp_off[f] + k] = cam_rp[f][k].pose;
     rc = b->d_rp.ensure(np_);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(b->d_rp.p, b->h_rp.p, sizeof(cs::RpPose) * np_, hipMemcpyHostToDevice, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->d_rp.p, b->h_rp.p, sizeof(cs::RpPose) * np_, hipMemcpyHostToDevice, st));
   }
   tm.setup_host_ms += now_ms() - t0;
 
@@ -2300,7 +2220,7 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     }
     const size_t nj = f_job[NF], n_lines = f_line[NF], n_yaw = f_yaw[NF], n_top = f_top[NF];
     if (nj == 0) { tm.setup_host_ms += now_ms() - t0; continue; }
-    if (f_vp[NF] > 0x7fffffffLL) { set_err("too many (roll,pitch,yaw) samples in one round"); return CS_ERR_CAPACITY; }
+    if (f_vp[NF] > 0x7fffffffLL) { cs_set_error("too many (roll,pitch,yaw) samples in one round"); return CS_ERR_CAPACITY; }
     std::vector<cs::JobDesc> jobs(nj);
     std::vector<long long> slot_prefix(nj + 1);
     std::vector<int> vp_prefix(nj + 1);
@@ -2359,14 +2279,14 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
       ENS(b->h_tables, need + 64);
       unsigned char* hb = b->h_tables.p;
 #define H2DP(dst, vec, off) do { if (!(vec).empty()) { memcpy(hb + (off), (vec).data(), sizeof((vec)[0]) * (vec).size()); \
-                                   HIP_TRY(hipMemcpyAsync((dst).p, hb + (off), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st)); } } while (0)
+                                   CS_HIP_TRY(hipMemcpyAsync((dst).p, hb + (off), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st)); } } while (0)
       H2DP(b->d_jobs, jobs, o_jobs); H2DP(b->d_slot_prefix, slot_prefix, o_sp); H2DP(b->d_vp_prefix, vp_prefix, o_vp);
       if (n_lines && !dev_setup) { H2DP(b->d_mid_x, mid_x, o_mx); H2DP(b->d_mid_y, mid_y, o_my); H2DP(b->d_ang, ang, o_an); }
       if (n_yaw) { H2DP(b->d_yaw, yaw, o_y); H2DP(b->d_yaw_c, yaw_c, o_yc); H2DP(b->d_yaw_s, yaw_s, o_ys); }
       if (n_top) H2DP(b->d_top_x, top_x, o_tx);
     }
-#define H2D(dst, vec) HIP_TRY(hipMemcpyAsync((dst).p, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st))
-    HIP_TRY(hipMemsetAsync(b->d_job_valid.p, 0, sizeof(int) * nj, st));
+#define H2D(dst, vec) CS_HIP_TRY(hipMemcpyAsync((dst).p, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st))
+    CS_HIP_TRY(hipMemsetAsync(b->d_job_valid.p, 0, sizeof(int) * nj, st));
     tm.h2d_ms += now_ms() - t0;
 
     // ------------------------------------------------------------------ sweep (HIP) ----------
@@ -2376,23 +2296,23 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     v.yaw = b->d_yaw.p; v.yaw_cos = b->d_yaw_c.p; v.yaw_sin = b->d_yaw_s.p; v.top_x = b->d_top_x.p; v.rp = b->d_rp.p; v.invK = b->d_invK.p;
     v.vp = b->d_vp.p; v.bound = b->d_bound.p; v.flag = b->d_flag.p;
     v.job_valid = b->d_job_valid.p; v.job_cbase = b->d_job_cbase.p;
-    HIP_TRY(hipEventRecord(d->ev[6], st));
+    CS_HIP_TRY(hipEventRecord(d->ev[6], st));
     if (dev_setup) {
       cs::launch_line_setup(b->d_jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, b->d_mid_x.p, b->d_mid_y.p, b->d_ang.p,
                             P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st);
     }
-    HIP_TRY(hipEventRecord(d->ev[7], st));
+    CS_HIP_TRY(hipEventRecord(d->ev[7], st));
     if (dev_setup) {
       // the merged segment counts come back with the results (byte accounting, debug getters)
       ENS(b->h_jobs, nj);
-      HIP_TRY(hipMemcpyAsync(b->h_jobs.p, b->d_jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_jobs.p, b->d_jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipEventRecord(d->ev[0], st));
+    CS_HIP_TRY(hipEventRecord(d->ev[0], st));
     cs::launch_vp_support(v, sp, vp_total, st);
-    HIP_TRY(hipEventRecord(d->ev[1], st));
+    CS_HIP_TRY(hipEventRecord(d->ev[1], st));
     cs::launch_candidates(v, sp, slot_total, st);
-    HIP_TRY(hipEventRecord(d->ev[2], st));
-    HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipEventRecord(d->ev[2], st));
+    CS_HIP_TRY(hipGetLastError());
 
     // ------------------------------------------------------------------ rank on the device --------
     // (no roll/pitch sampling: boxes are independent, so nothing has to come back to the host before the ranking)
@@ -2400,11 +2320,11 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     if (device_rank) {
       ENS(b->d_c_slot, slot_total + 1); ENS(b->d_c_flag, slot_total + 1); ENS(b->d_c_dist, slot_total + 1); ENS(b->d_c_angle, slot_total + 1); ENS(b->d_c_skew, slot_total + 1);
       v.c_slot = b->d_c_slot.p; v.c_flag = b->d_c_flag.p; v.c_dist = b->d_c_dist.p; v.c_angle = b->d_c_angle.p; v.c_skew = b->d_c_skew.p;
-      HIP_TRY(hipEventRecord(d->ev[3], st));
+      CS_HIP_TRY(hipEventRecord(d->ev[3], st));
       cs::launch_scan_compact(v, st);
-      HIP_TRY(hipEventRecord(d->ev[8], st));
+      CS_HIP_TRY(hipEventRecord(d->ev[8], st));
       cs::launch_score(v, sp, slot_total, slot_total, st);   // the exact number of valid proposals stays on the device
-      HIP_TRY(hipEventRecord(d->ev[4], st));
+      CS_HIP_TRY(hipEventRecord(d->ev[4], st));
       std::vector<int> box_job0, box_njobs;
       for (size_t j = 0; j < nj; j++)
         if (jobs[j].hid == 0) { box_job0.push_back((int)j); box_njobs.push_back(b->frames[jobs[j].frame].n_heights[jobs[j].box]); }
@@ -2423,28 +2343,28 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
       if (sample_rp) { ENS(b->d_last_slot, nb); ENS(b->h_last_slot, nb); rv.last_slot = b->d_last_slot.p; }
       cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, sp.short_sq_bound};
       cs::launch_rank(v, rv, rkp, st);
-      HIP_TRY(hipEventRecord(d->ev[5], st));
-      HIP_TRY(hipGetLastError());
+      CS_HIP_TRY(hipEventRecord(d->ev[5], st));
+      CS_HIP_TRY(hipGetLastError());
       double t_d2h = now_ms();
-      HIP_TRY(hipMemcpyAsync(b->h_winners.p, b->d_winners.p, sizeof(cs::RankWinner) * nb * KMAX, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_win_count.p, b->d_win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_fallback.p, b->d_fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-      if (sample_rp) HIP_TRY(hipMemcpyAsync(b->h_last_slot.p, b->d_last_slot.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_job_cbase.p, b->d_job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_winners.p, b->d_winners.p, sizeof(cs::RankWinner) * nb * KMAX, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_win_count.p, b->d_win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_fallback.p, b->d_fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+      if (sample_rp) CS_HIP_TRY(hipMemcpyAsync(b->h_last_slot.p, b->d_last_slot.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_job_cbase.p, b->d_job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipStreamSynchronize(st));
       tm.d2h_ms += now_ms() - t_d2h;
       if (dev_setup) for (size_t j = 0; j < nj; j++) jobs[j].m = b->h_jobs.p[j].m;
       const long long n_valid = b->h_job_cbase.p[nj];
       tm.n_valid += n_valid;
       {
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[4], d->ev[5])); tm.rank_kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
+        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
+        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
+        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
+        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
+        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[4], d->ev[5])); tm.rank_kernel_ms += ms;
+        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
         tm.cand_kernel_launches += 1;
         // algorithmic bytes: geometry kernel = vanishing points read once per (job, rp, yaw) + one flag per slot
         // (the corners stay in registers); scoring kernel = each distance map once + the vanishing points and the VP support table
@@ -2491,13 +2411,13 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
           cs::launch_gather_ranges(v, b->d_fb_src.p, b->d_fb_cnt.p, b->d_fb_dst.p, (int)nr, b->d_fb_dist.p, b->d_fb_angle.p, b->d_fb_skew.p, b->d_fb_flag.p, b->d_fb_slot.p, st);
           fb_dist.resize(tot); fb_angle.resize(tot); fb_skew.resize(tot); fb_flag.resize(tot); fb_slot.resize(tot);
           if (tot) {
-            HIP_TRY(hipMemcpyAsync(fb_dist.data(), b->d_fb_dist.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(fb_angle.data(), b->d_fb_angle.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(fb_skew.data(), b->d_fb_skew.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(fb_flag.data(), b->d_fb_flag.p, 4 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(fb_slot.data(), b->d_fb_slot.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+            CS_HIP_TRY(hipMemcpyAsync(fb_dist.data(), b->d_fb_dist.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+            CS_HIP_TRY(hipMemcpyAsync(fb_angle.data(), b->d_fb_angle.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+            CS_HIP_TRY(hipMemcpyAsync(fb_skew.data(), b->d_fb_skew.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+            CS_HIP_TRY(hipMemcpyAsync(fb_flag.data(), b->d_fb_flag.p, 4 * (size_t)tot, hipMemcpyDeviceToHost, st));
+            CS_HIP_TRY(hipMemcpyAsync(fb_slot.data(), b->d_fb_slot.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
           }
-          HIP_TRY(hipStreamSynchronize(st));
+          CS_HIP_TRY(hipStreamSynchronize(st));
         }
       }
       std::vector<std::vector<cs::RankWinner>> fb_winners(nb);
@@ -2586,8 +2506,8 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
           ENS(b->d_win_slots, ws.size()); ENS(b->d_win_corners, 16 * ws.size()); ENS(b->h_win_corners, 16 * ws.size());
           H2D(b->d_win_slots, ws);
           cs::launch_gather_corners(v, sp, b->d_win_slots.p, (int)ws.size(), b->d_win_corners.p, st);
-          HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * ws.size(), hipMemcpyDeviceToHost, st));
-          HIP_TRY(hipStreamSynchronize(st));
+          CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * ws.size(), hipMemcpyDeviceToHost, st));
+          CS_HIP_TRY(hipStreamSynchronize(st));
           size_t z = 0;
           for (size_t q = 0; q < nb; q++)
             if (b->h_fallback.p[q])
@@ -2601,8 +2521,8 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     }
     // valid counts -> host -> size the compact arrays
     ENS(b->h_job_valid, nj); ENS(b->h_job_cbase, nj + 1);
-    HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipStreamSynchronize(st));
     if (dev_setup) for (size_t j = 0; j < nj; j++) jobs[j].m = b->h_jobs.p[j].m;
     long long n_valid = 0;
     for (size_t j = 0; j < nj; j++) { b->h_job_cbase.p[j] = n_valid; n_valid += b->h_job_valid.p[j]; }
@@ -2610,30 +2530,30 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     tm.n_valid += n_valid;
     ENS(b->d_c_slot, n_valid + 1); ENS(b->d_c_flag, n_valid + 1); ENS(b->d_c_dist, n_valid + 1); ENS(b->d_c_angle, n_valid + 1); ENS(b->d_c_skew, n_valid + 1);
     v.c_slot = b->d_c_slot.p; v.c_flag = b->d_c_flag.p; v.c_dist = b->d_c_dist.p; v.c_angle = b->d_c_angle.p; v.c_skew = b->d_c_skew.p;
-    HIP_TRY(hipEventRecord(d->ev[3], st));
+    CS_HIP_TRY(hipEventRecord(d->ev[3], st));
     cs::launch_scan_compact(v, st);
-    HIP_TRY(hipEventRecord(d->ev[8], st));
+    CS_HIP_TRY(hipEventRecord(d->ev[8], st));
     cs::launch_score(v, sp, n_valid, slot_total, st);
-    HIP_TRY(hipEventRecord(d->ev[4], st));
-    HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipEventRecord(d->ev[4], st));
+    CS_HIP_TRY(hipGetLastError());
     ENS(b->h_c_slot, n_valid + 1); ENS(b->h_c_flag, n_valid + 1); ENS(b->h_c_dist, n_valid + 1); ENS(b->h_c_angle, n_valid + 1); ENS(b->h_c_skew, n_valid + 1);
     double t_d2h = now_ms();
     if (n_valid) {
-      HIP_TRY(hipMemcpyAsync(b->h_c_slot.p, b->d_c_slot.p, sizeof(long long) * n_valid, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_c_flag.p, b->d_c_flag.p, sizeof(int) * n_valid, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_c_dist.p, b->d_c_dist.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_c_angle.p, b->d_c_angle.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(b->h_c_skew.p, b->d_c_skew.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_c_slot.p, b->d_c_slot.p, sizeof(long long) * n_valid, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_c_flag.p, b->d_c_flag.p, sizeof(int) * n_valid, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_c_dist.p, b->d_c_dist.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_c_angle.p, b->d_c_angle.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_c_skew.p, b->d_c_skew.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipStreamSynchronize(st));
+    CS_HIP_TRY(hipStreamSynchronize(st));
     tm.d2h_ms += now_ms() - t_d2h;
     {
       float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
+      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
       tm.cand_kernel_launches += 1;
       // algorithmic bytes of the candidate kernel: maps + line arrays + vp/bound read once,
       // 200 B written per valid proposal, 4 B flag per slot
@@ -2737,10 +2657,10 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     if (b->debug) wslots.insert(wslots.end(), b->h_c_slot.p, b->h_c_slot.p + n_valid);
     if (n_gather) {
       ENS(b->d_win_slots, n_gather); ENS(b->d_win_corners, 16 * n_gather); ENS(b->h_win_corners, 16 * n_gather);
-      HIP_TRY(hipMemcpyAsync(b->d_win_slots.p, wslots.data(), sizeof(long long) * n_gather, hipMemcpyHostToDevice, st));
+      CS_HIP_TRY(hipMemcpyAsync(b->d_win_slots.p, wslots.data(), sizeof(long long) * n_gather, hipMemcpyHostToDevice, st));
       cs::launch_gather_corners(v, sp, b->d_win_slots.p, (int)n_gather, b->d_win_corners.p, st);
-      HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * n_gather, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
+      CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * n_gather, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipStreamSynchronize(st));
     }
     for (size_t i = 0; i < nw; i++) {
       const Winner& w = winners[w0 + i];
@@ -2787,7 +2707,7 @@ int cs_batch_debug_candidates(cs_batch* b, int frame, int box, int k, int cap, d
   int n = std::min(cap, R.n_valid);
   if (rows9) std::memcpy(rows9, R.rows9.data(), sizeof(double) * 9 * (size_t)n);
   if (corners16) {
-    if (R.corners.size() < 16 * (size_t)R.n_valid) { set_err("corners not retained: call cs_batch_set_debug(b,1) before cs_batch_run"); return CS_ERR_NOT_RUN; }
+    if (R.corners.size() < 16 * (size_t)R.n_valid) { cs_set_error("corners not retained: call cs_batch_set_debug(b,1) before cs_batch_run"); return CS_ERR_NOT_RUN; }
     std::memcpy(corners16, R.corners.data(), sizeof(double) * 16 * (size_t)n);
   }
   return R.n_valid;
@@ -2816,7 +2736,7 @@ int cs_edge_distance_maps_multi(cs_detector* d, const unsigned char* const* gray
                                 int n_rois, float* const* out_maps, double* kernel_ms) {
   if (!d || n_images <= 0 || !grays || img_w <= 0 || img_h <= 0 || n_rois < 0 || (n_rois && (!rois || !roi_image))) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
-  HIP_TRY(hipSetDevice(d->device));
+  CS_HIP_TRY(hipSetDevice(d->device));
   if (kernel_ms) *kernel_ms = 0;
   if (n_rois == 0) return CS_OK;
   const size_t img_px = (size_t)img_w * img_h;
@@ -2827,7 +2747,7 @@ int cs_edge_distance_maps_multi(cs_detector* d, const unsigned char* const* gray
     const cs_roi& r = rois[k];
     if (r.width <= 0 || r.height <= 0 || r.left < 0 || r.top < 0 || r.left + r.width > img_w || r.top + r.height > img_h || roi_image[k] < 0 || roi_image[k] >= n_images ||
         (out_maps && !out_maps[k])) {
-      set_err("cs_edge_distance_maps: ROI outside the image");
+      cs_set_error("cs_edge_distance_maps: ROI outside the image");
       return CS_ERR_INVALID_ARG;
     }
     er[k] = cs::EdgeRoi{r.left, r.top, r.width, r.height, (long long)(roi_image[k] * img_px), tot, tot};
@@ -2841,22 +2761,22 @@ int cs_edge_distance_maps_multi(cs_detector* d, const unsigned char* const* gray
   if ((rc = d_gray.ensure(img_px * n_images)) || (rc = d_cls.ensure((size_t)tot + 8)) || (rc = d_rois.ensure((size_t)n_rois)) || (rc = d_map.ensure((size_t)tot))) return rc;
   hipStream_t st = d->stream;
   for (int i = 0; i < n_images; i++) {
-    if (!grays[i]) { set_err("cs_edge_distance_maps: null image"); return CS_ERR_INVALID_ARG; }
-    HIP_TRY(hipMemcpyAsync(d_gray.p + img_px * i, grays[i], img_px, hipMemcpyHostToDevice, st));
+    if (!grays[i]) { cs_set_error("cs_edge_distance_maps: null image"); return CS_ERR_INVALID_ARG; }
+    CS_HIP_TRY(hipMemcpyAsync(d_gray.p + img_px * i, grays[i], img_px, hipMemcpyHostToDevice, st));
   }
   std::vector<cs::EdgeRoi> er_launch(er.begin(), er.end());      // (er keeps the caller's order for the copies back)
   edge_rois_largest_first(er_launch);
-  HIP_TRY(hipMemcpyAsync(d_rois.p, er_launch.data(), sizeof(cs::EdgeRoi) * n_rois, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(d->ev[0], st));
+  CS_HIP_TRY(hipMemcpyAsync(d_rois.p, er_launch.data(), sizeof(cs::EdgeRoi) * n_rois, hipMemcpyHostToDevice, st));
+  CS_HIP_TRY(hipEventRecord(d->ev[0], st));
   // cv::Canny(gray_img(object_bbox), im_canny, 80, 200): the thresholds are literals of the reference (:324)
   cs::launch_edge_maps(d_gray.p, img_w, img_h, d_rois.p, n_rois, d_cls.p, d_map.p, max_w, max_px, 80, 200, st);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(d->ev[1], st));
+  CS_HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipEventRecord(d->ev[1], st));
   if (out_maps)
     for (int k = 0; k < n_rois; k++)
-      HIP_TRY(hipMemcpyAsync(out_maps[k], d_map.p + er[k].map_off, sizeof(float) * (size_t)er[k].w * er[k].h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (kernel_ms) { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); *kernel_ms = ms; }
+      CS_HIP_TRY(hipMemcpyAsync(out_maps[k], d_map.p + er[k].map_off, sizeof(float) * (size_t)er[k].w * er[k].h, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipStreamSynchronize(st));
+  if (kernel_ms) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); *kernel_ms = ms; }
   d_gray.release(); d_cls.release(); d_rois.release(); d_map.release();
   return CS_OK;
   CS_GUARD_END("cs_edge_distance_maps")
@@ -2874,7 +2794,7 @@ static int detect_single(cs_detector* d, const cs_frame_desc* frame, const unsig
   if (!d || !frame || !out || !out_counts) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
   std::lock_guard<std::mutex> lk(d->single_mu);
-  HIP_TRY(hipSetDevice(d->device));
+  CS_HIP_TRY(hipSetDevice(d->device));
   if (!d->single) { d->single = new cs_batch(); d->single->det = d; }
   int rc = batch_fill(d, d->single, frame, gray ? &gray : nullptr, 1);
   if (rc) return rc;

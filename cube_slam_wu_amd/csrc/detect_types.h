@@ -1,8 +1,11 @@
-// detect_types.h -- device data layout of the proposal sweep (shared by detect_kernels.hip and
-// detect_host.cpp).  See DESIGN.md "Path A: data layout in HBM".
+// detect_types.h -- what detect_host.cpp hands to detect_kernels.hip: the device data layout of the proposal sweep
+// (see DESIGN.md "Path A: data layout in HBM") and the launchers.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
 
+#include "../../include/cubeslam_hip.h"
 #include "cs_geom.h"
 
 namespace cs {
@@ -120,5 +123,28 @@ struct RpCarryView {
   const int* tab_count;             // [n_frames * NT] yaw samples of list i of frame f
   int* cur_idx;                     // [n_frames] list in force
 };
+
+// ---- launchers (detect_kernels.hip)
+void launch_vp_support(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st);
+void launch_vp_support_only(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st, int rp_max = 0);      // rp_max: the jobs' largest roll/pitch sample count (0: unknown)
+void launch_vp_points(const DetectDeviceView& v, int vp_total, hipStream_t st);
+int vp3_table_doubles_per_job();
+void launch_candidates(const DetectDeviceView& v, const SweepParams& sp, long long slot_total, hipStream_t st);
+void launch_candidate_compact(const DetectDeviceView& v, const SweepParams& sp, hipStream_t st);
+void launch_scan_compact(const DetectDeviceView& v, hipStream_t st);
+void launch_scan_compact_trips(const DetectDeviceView& v, int* cnt, int max_trips, hipStream_t st);
+void launch_score(const DetectDeviceView& v, const SweepParams& sp, long long n_valid_bound, long long slot_total, hipStream_t st);
+void launch_gather_corners(const DetectDeviceView& v, const SweepParams& sp, const long long* slots, int n, double* out, hipStream_t st);
+void launch_rank(const DetectDeviceView& v, const RankView& rv, const RankParams& rp, hipStream_t st, long long max_slots_per_box = 0, bool with_corners = true);
+void launch_records(const DetectDeviceView& v, const RankView& rv, int kmax, cs_cuboid* out, hipStream_t st, const double* raw_euler = nullptr, double rebuild_short_sq_bound = -1.0);
+void launch_rp_carry(const RpCarryView& c, JobDesc* jobs, hipStream_t st);
+void launch_rp_save_fallback(const DetectDeviceView& v, const RpSaveView& s, hipStream_t st);
+void launch_line_setup(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
+                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st);
+void launch_line_setup_listed(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
+                              double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded);
+int line_setup_capacity();
+void launch_gather_ranges(const DetectDeviceView& v, const long long* src_off, const int* count, const long long* dst_off, int n_ranges,
+                          double* o_dist, double* o_angle, double* o_skew, int* o_flag, long long* o_slot, hipStream_t st);
 
 }  // namespace cs

@@ -6,19 +6,13 @@
 // integer arithmetic (bit-reproducible on any host).  One workgroup per ROI.
 #include <hip/hip_runtime.h>
 #include "cs_hip_util.h"
+#include "edge_types.h"
 
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
 namespace cs {
-
-struct EdgeRoi {
-  int l, t, w, h;            // ROI inside the gray image
-  long long img_off;         // -> first pixel of the ROI's image in the gray pool
-  long long cls_off;         // -> class bytes (w * h)
-  long long map_off;         // -> output floats (w * h)
-};
 
 __device__ __forceinline__ int edge_px(const unsigned char* __restrict__ g, int W, int H, int x, int y) {
   x = min(max(x, 0), W - 1); y = min(max(y, 0), H - 1);   // BORDER_REPLICATE at the image border; the ROI is not isolated
@@ -740,11 +734,7 @@ __global__ __launch_bounds__(64) void edge_dt_kernel(const EdgeRoi* __restrict__
   if (bits) edge_dt_dispatch<true>(A, R.w); else edge_dt_dispatch<false>(A, R.w);
 }
 
-// A handful of tables between PINNED host memory and device memory in ONE launch (either direction; the host side is addressed through the
-// unified address space).  Why not one hipMemcpyAsync each: ten small copies are ten trips through a copy-engine ring (~0.3 ms of latency in
-// front of a sweep, ~0.15 ms behind it), and a ring that holds a bulk upload (cs_batch_refill_gray) makes every one of them wait for it.
-struct CopySeg { const void* src; void* dst; unsigned long long bytes; };
-struct CopySegs { CopySeg s[16]; int n; };
+// the batched table copy (CopySegs, edge_types.h)
 __global__ __launch_bounds__(256) void multi_copy_kernel(CopySegs segs) {
   const CopySeg sg = segs.s[blockIdx.y];
   const size_t n16 = ((reinterpret_cast<uintptr_t>(sg.src) | reinterpret_cast<uintptr_t>(sg.dst)) & 15) ? 0 : sg.bytes / 16;

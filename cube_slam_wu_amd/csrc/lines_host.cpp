@@ -16,7 +16,6 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -24,31 +23,12 @@
 
 #include "../../include/cubeslam_hip.h"
 #include "batch_gate.h"
+#include "cs_hip_util.h"
 #include "cs_nfa.h"
-
-void cs_set_error_ba(const std::string& s);
-extern "C" void* cs_internal_detector_stream(cs_detector* d);
-extern "C" int cs_internal_detector_device(cs_detector* d);
-extern "C" void** cs_internal_detector_lines_slot(cs_detector* d, void (*deleter)(void*));
-extern "C" void* cs_internal_detector_lines_mutex(cs_detector* d);
-extern "C" void cs_internal_detector_parallel(cs_detector* d, int n, void (*fn)(int, void*), void* ctx);
-extern "C" void cs_internal_detector_parallel_long(cs_detector* d, int n, void (*fn)(int, void*), void* ctx);
-
-namespace cs {
-struct LineMaps { unsigned char* p3; };
-void launch_lines_maps(const unsigned char* gray, int W, int H, const LineMaps& m, const int k[3], int grad_thr, int anchor_thr, int scan, hipStream_t st, int n_images);
-}  // namespace cs
+#include "detect_hooks.h"
+#include "lines_types.h"
 
 namespace {
-
-#define LN_TRY(expr)                                                           \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cs_set_error_ba(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
 
 // EDLineDetector() :1515-1526 and BinaryDescriptor::Params() :110-117
 struct EdParams { int grad_thr = 80, anchor_thr = 8, scan = 2, min_len = 15, try_time = 6, skip = 2, max_outlier = 3; double fit_err = 1.6; };
@@ -256,10 +236,10 @@ struct Extractor {
 // Resident scratch of a detector's line producer: device maps and pinned host copies for `cap_images` images of `cap_pixels` pixels
 // (grows only).  A call used to pay three hipMalloc / hipFree pairs and five copies into pageable vectors.
 struct LinesScratch {
-  unsigned char* d_gray = nullptr; unsigned char* d_pk = nullptr;
-  unsigned char* h_pin = nullptr;  // per image: the packed map, 3 bytes per pixel (+ 4 bytes of pad behind the last image)
-  unsigned char* h_in = nullptr;   // pinned: the batch's images side by side (one upload)
-  size_t cap = 0;                  // pixels x images
+  cs::DevBuf<unsigned char> d_gray, d_pk;
+  cs::PinBuf<unsigned char> h_pin;   // per image: the packed map, 3 bytes per pixel (+ 4 bytes of pad behind the last image)
+  cs::PinBuf<unsigned char> h_in;    // the batch's images side by side (one upload)
+  size_t cap = 0;                    // pixels x images the four hold (they grow together)
   cs::ChunkEvents chunks;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double device_ms = 0, host_ms = 0, total_ms = 0;
@@ -268,10 +248,7 @@ struct LinesScratch {
 void lines_scratch_free(void* p) {
   LinesScratch* S = (LinesScratch*)p;
   if (!S) return;
-  if (S->d_gray) (void)hipFree(S->d_gray);
-  if (S->d_pk) (void)hipFree(S->d_pk);
-  if (S->h_pin) (void)hipHostFree(S->h_pin);
-  if (S->h_in) (void)hipHostFree(S->h_in);
+  S->d_gray.release(); S->d_pk.release(); S->h_pin.release(); S->h_in.release();
   S->chunks.release();
   if (S->ev0) (void)hipEventDestroy(S->ev0);
   if (S->ev1) (void)hipEventDestroy(S->ev1);
@@ -298,7 +275,7 @@ int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, floa
     for (int x = 1; x < img_w - 1; x += P.scan)
       if ((row[3 * x] >> 3) & 1) { grid_at.push_back((unsigned)((size_t)y * img_w + x)); col_at[(size_t)x + 1]++; }
   }
-  if (grid_at.size() > N / 5) { cs_set_error_ba("cs_detect_lines_gray: more anchors than the reference's arrays hold"); return CS_ERR_CAPACITY; }
+  if (grid_at.size() > N / 5) { cs_set_error("cs_detect_lines_gray: more anchors than the reference's arrays hold"); return CS_ERR_CAPACITY; }
   for (int x = 0; x < img_w; x++) col_at[(size_t)x + 1] += col_at[x];
   std::vector<unsigned> anchors(grid_at.size());
   for (const unsigned at : grid_at) anchors[col_at[at % (unsigned)img_w]++] = at;
@@ -330,7 +307,7 @@ int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, floa
     if (dir >= -0.25 * M_PI && dir < 0.25 * M_PI) flip = flip || ex < 0;
     if (dir >= 0.25 * M_PI && dir < 0.75 * M_PI) flip = flip || ey < 0;
     if ((dir >= 0.75 * M_PI && dir < M_PI) || (dir >= -M_PI && dir < -0.75 * M_PI)) flip = flip || ex > 0;
-    if (n >= cap) { cs_set_error_ba("cs_detect_lines_gray: more segments than `cap`"); return CS_ERR_CAPACITY; }
+    if (n >= cap) { cs_set_error("cs_detect_lines_gray: more segments than `cap`"); return CS_ERR_CAPACITY; }
     float* o = lines4 + 4 * (size_t)n;
     if (flip) { o[0] = s.x2; o[1] = s.y2; o[2] = s.x1; o[3] = s.y1; } else { o[0] = s.x1; o[1] = s.y1; o[2] = s.x2; o[3] = s.y2; }
     n++;
@@ -338,8 +315,6 @@ int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, floa
   *n_lines = n;
   return CS_OK;
 }
-
-double ln_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
 
@@ -354,27 +329,24 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
     for (int i = 0; i < n_images; i++) n_lines[i] = 0;
     if (n_images == 0) return CS_OK;
     std::lock_guard<std::mutex> lk(*(std::mutex*)cs_internal_detector_lines_mutex(d));
-    LN_TRY(hipSetDevice(cs_internal_detector_device(d)));
+    CS_HIP_TRY(hipSetDevice(cs_internal_detector_device(d)));
     hipStream_t st = (hipStream_t)cs_internal_detector_stream(d);
     void** slot = cs_internal_detector_lines_slot(d, lines_scratch_free);
     if (!*slot) *slot = new LinesScratch();
     LinesScratch& S = *(LinesScratch*)*slot;
-    const double t_begin = ln_now_ms();
+    const double t_begin = cs::now_ms();
     const EdParams P;
     const size_t N = (size_t)img_w * img_h, need = N * (size_t)n_images;
     if (need > S.cap) {
-      if (S.d_gray) (void)hipFree(S.d_gray);
-      if (S.d_pk) (void)hipFree(S.d_pk);
-      if (S.h_pin) (void)hipHostFree(S.h_pin);
-      if (S.h_in) (void)hipHostFree(S.h_in);
-      S.d_gray = nullptr; S.d_pk = nullptr; S.h_pin = nullptr; S.h_in = nullptr; S.cap = 0;
-      LN_TRY(hipMalloc((void**)&S.d_gray, need));
-      LN_TRY(hipMalloc((void**)&S.d_pk, 3 * need + 4));
-      LN_TRY(hipHostMalloc((void**)&S.h_pin, 3 * need + 4));
-      LN_TRY(hipHostMalloc((void**)&S.h_in, need));
+      S.cap = 0;
+      int rc = S.d_gray.ensure(need);
+      if (!rc) rc = S.d_pk.ensure(3 * need + 4);
+      if (!rc) rc = S.h_pin.ensure(3 * need + 4);
+      if (!rc) rc = S.h_in.ensure(need);
+      if (rc) return rc;
       S.cap = need;
     }
-    if (!S.ev0) { LN_TRY(hipEventCreate(&S.ev0)); LN_TRY(hipEventCreate(&S.ev1)); }
+    if (!S.ev0) { CS_HIP_TRY(hipEventCreate(&S.ev0)); CS_HIP_TRY(hipEventCreate(&S.ev1)); }
     // getGaussianKernel(5, 1.0, CV_32F) rounded to 8-bit fixed point, as createSeparableLinearFilter does for 8-bit images
     int k[3];
     {
@@ -383,12 +355,12 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
       sum = 1. / sum;
       for (int i = 0; i < 3; i++) k[i] = (int)std::nearbyint((double)(float)(cf[i] * sum) * 256.0);
     }
-    const cs::LineMaps dm{S.d_pk};
+    const cs::LineMaps dm{S.d_pk.p};
     struct Ctx {
       const unsigned char* h_pk; int W, H; size_t N; const EdParams* P; double thr; float* const* lines4; int cap; int* n_lines; std::vector<int> rc;
       cs::ChunkGate gate; int device; const hipEvent_t* done; int n_chunks, n_images;
       const unsigned char* const* grays; unsigned char* h_in;
-    } ctx{S.h_pin, img_w, img_h, N, &P, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in};
+    } ctx{S.h_pin.p, img_w, img_h, N, &P, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in.p};
     auto one = [](int i, void* vp) {
       Ctx& c = *(Ctx*)vp;
       Maps M; M.W = c.W; M.H = c.H; M.grad_thr = c.P->grad_thr; M.p3 = c.h_pk + 3 * c.N * (size_t)i;
@@ -397,37 +369,37 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
     };
     double t_host;
     if (n_images == 1) {
-      LN_TRY(hipMemcpyAsync(S.d_gray, grays[0], N, hipMemcpyHostToDevice, st));
-      LN_TRY(hipEventRecord(S.ev0, st));
-      cs::launch_lines_maps(S.d_gray, img_w, img_h, dm, k, P.grad_thr, P.anchor_thr, P.scan, st, 1);
-      LN_TRY(hipGetLastError());
-      LN_TRY(hipEventRecord(S.ev1, st));
-      LN_TRY(hipMemcpyAsync(S.h_pin, S.d_pk, 3 * N, hipMemcpyDeviceToHost, st));
-      LN_TRY(hipStreamSynchronize(st));
+      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, grays[0], N, hipMemcpyHostToDevice, st));
+      CS_HIP_TRY(hipEventRecord(S.ev0, st));
+      cs::launch_lines_maps(S.d_gray.p, img_w, img_h, dm, k, P.grad_thr, P.anchor_thr, P.scan, st, 1);
+      CS_HIP_TRY(hipGetLastError());
+      CS_HIP_TRY(hipEventRecord(S.ev1, st));
+      CS_HIP_TRY(hipMemcpyAsync(S.h_pin.p, S.d_pk.p, 3 * N, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipStreamSynchronize(st));
       float ms = 0;
-      LN_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
+      CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
       S.device_ms = ms;
-      t_host = ln_now_ms();
+      t_host = cs::now_ms();
       one(0, &ctx);
     } else {
       // a batch: the images gathered into pinned memory by the pool (the caller's buffers are pageable), one upload, then chunk by chunk
       // [kernel | copy back | event], all queued before the pool starts on the first chunk's images (batch_gate.h)
       cs_internal_detector_parallel(d, n_images, [](int i, void* vp) { Ctx& c = *(Ctx*)vp; std::memcpy(c.h_in + c.N * (size_t)i, c.grays[i], c.N); }, &ctx);
       const int CH = cs::BATCH_CHUNK, n_chunks = (n_images + CH - 1) / CH;
-      LN_TRY(S.chunks.reserve(n_chunks));
-      LN_TRY(hipMemcpyAsync(S.d_gray, S.h_in, N * (size_t)n_images, hipMemcpyHostToDevice, st));
+      CS_HIP_TRY(S.chunks.reserve(n_chunks));
+      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, S.h_in.p, N * (size_t)n_images, hipMemcpyHostToDevice, st));
       for (int c = 0; c < n_chunks; c++) {
         const int i0 = c * CH, ni = std::min(CH, n_images - i0);
         const cs::LineMaps mi{dm.p3 + 3 * (size_t)i0 * N};
-        LN_TRY(hipEventRecord(S.chunks.k0[c], st));
-        cs::launch_lines_maps(S.d_gray + (size_t)i0 * N, img_w, img_h, mi, k, P.grad_thr, P.anchor_thr, P.scan, st, ni);
-        LN_TRY(hipGetLastError());
-        LN_TRY(hipEventRecord(S.chunks.k1[c], st));
-        LN_TRY(hipMemcpyAsync(S.h_pin + 3 * N * (size_t)i0, S.d_pk + 3 * N * (size_t)i0, 3 * N * (size_t)ni, hipMemcpyDeviceToHost, st));
-        LN_TRY(hipEventRecord(S.chunks.done[c], st));
+        CS_HIP_TRY(hipEventRecord(S.chunks.k0[c], st));
+        cs::launch_lines_maps(S.d_gray.p + (size_t)i0 * N, img_w, img_h, mi, k, P.grad_thr, P.anchor_thr, P.scan, st, ni);
+        CS_HIP_TRY(hipGetLastError());
+        CS_HIP_TRY(hipEventRecord(S.chunks.k1[c], st));
+        CS_HIP_TRY(hipMemcpyAsync(S.h_pin.p + 3 * N * (size_t)i0, S.d_pk.p + 3 * N * (size_t)i0, 3 * N * (size_t)ni, hipMemcpyDeviceToHost, st));
+        CS_HIP_TRY(hipEventRecord(S.chunks.done[c], st));
       }
       ctx.done = S.chunks.done.data(); ctx.n_chunks = n_chunks;
-      t_host = ln_now_ms();
+      t_host = cs::now_ms();
       cs_internal_detector_parallel_long(d, n_images + 1, [](int t, void* vp) {
         Ctx& c = *(Ctx*)vp;
         if (t == 0) { c.gate.watch(c.device, c.done, c.n_chunks, cs::BATCH_CHUNK, c.n_images); return; }
@@ -437,16 +409,16 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
         try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i]); }
         catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
       }, &ctx);
-      LN_TRY(hipStreamSynchronize(st));
+      CS_HIP_TRY(hipStreamSynchronize(st));
       double dev = 0;
-      for (int c = 0; c < n_chunks; c++) { float ms = 0; LN_TRY(hipEventElapsedTime(&ms, S.chunks.k0[c], S.chunks.k1[c])); dev += ms; }
+      for (int c = 0; c < n_chunks; c++) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, S.chunks.k0[c], S.chunks.k1[c])); dev += ms; }
       S.device_ms = dev;
     }
-    S.host_ms = ln_now_ms() - t_host; S.total_ms = ln_now_ms() - t_begin; S.n_images = n_images;
+    S.host_ms = cs::now_ms() - t_host; S.total_ms = cs::now_ms() - t_begin; S.n_images = n_images;
     for (int r : ctx.rc) if (r) return r;
     return CS_OK;
   } catch (const std::exception& ex) {
-    cs_set_error_ba(std::string("cs_detect_lines_batch: ") + ex.what());
+    cs_set_error(std::string("cs_detect_lines_batch: ") + ex.what());
     return CS_ERR_CAPACITY;
   }
 }

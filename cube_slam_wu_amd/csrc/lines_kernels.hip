@@ -13,16 +13,9 @@
 
 #include <cstdint>
 
-namespace cs {
+#include "lines_types.h"
 
-// What goes back to the host, THREE bytes per pixel (round 6; a 32-bit word until then -- the copy back is the batch's longest stage): the Sobel
-// derivatives (dxImg_, dyImg_; |.| <= 4 x 255 = 1020: eleven bits each) and the anchor flag, little endian,
-//   bits 0..10  dx (two's complement)        bit 11  anchor        bits 12..22  dy (two's complement)        bit 23  0
-// i.e. bits 11..22 are 2 dy + anchor as before.  The thresholded gradient / 4 (gImg_) and the direction map (dirImg_: |dx| < |dy| = horizontal) are
-// functions of dx and dy that the host stage evaluates where it reads them (lines_host.cpp, Maps).  Image i's map starts at p3 + 3 N i.
-struct LineMaps {
-  unsigned char* p3;
-};
+namespace cs {
 
 __device__ __forceinline__ int lines_reflect101(int p, int n) {
   if (n == 1) return 0;

@@ -16,7 +16,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -27,32 +26,12 @@
 #include "../../include/cubeslam_hip.h"
 #include "batch_gate.h"
 #include "cs_fast_atan.h"
+#include "cs_hip_util.h"
 #include "cs_nfa.h"
-
-void cs_set_error_ba(const std::string& s);
-extern "C" void* cs_internal_detector_stream(cs_detector* d);
-extern "C" int cs_internal_detector_device(cs_detector* d);
-extern "C" void** cs_internal_detector_lsd_slot(cs_detector* d, void (*deleter)(void*));
-extern "C" void* cs_internal_detector_lines_mutex(cs_detector* d);
-extern "C" void cs_internal_detector_parallel(cs_detector* d, int n, void (*fn)(int, void*), void* ctx);
-extern "C" void cs_internal_detector_parallel_long(cs_detector* d, int n, void (*fn)(int, void*), void* ctx);
-
-namespace cs {
-struct LsdGauss { double k[7]; };
-struct LsdScaleTab { const int* xo; const float* xa; const int* yo; const float* ya; };
-void launch_lsd_maps(const unsigned char* gray, int W, int H, int Ws, int Hs, const LsdGauss& G, const LsdScaleTab& T, double rho, double* blur, char* out, size_t out_stride, hipStream_t st, int n_images);
-}  // namespace cs
+#include "detect_hooks.h"
+#include "lsd_types.h"
 
 namespace {
-
-#define LSD_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cs_set_error_ba(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
 
 // createLineSegmentDetector(LSD_REFINE_ADV) defaults (lsd.cpp:185-187) and the constants of :53-64
 constexpr double kScale = 0.8, kSigmaScale = 0.6, kQuant = 2.0, kAngTh = 22.5, kLogEps = 0.0, kDensityTh = 0.7;
@@ -467,7 +446,7 @@ int lsd_host_stage(int img_w, int img_h, int Ws, int Hs, const float* deg, const
       if ((e[0] < border && e[2] < border) || (e[0] > img_w - border && e[2] > img_w - border) || (e[1] < border && e[3] < border) || (e[1] > img_h - border && e[3] > img_h - border)) continue;
       const float len = (float)std::sqrt(std::pow(e[0] - e[2], 2) + std::pow(e[1] - e[3], 2));
       if (!(len > (float)length_thres)) continue;
-      if (n >= cap) { cs_set_error_ba("cs_detect_lsd_gray: more segments than `cap`"); return CS_ERR_CAPACITY; }
+      if (n >= cap) { cs_set_error("cs_detect_lsd_gray: more segments than `cap`"); return CS_ERR_CAPACITY; }
       std::memcpy(lines4 + 4 * (size_t)n, e, sizeof(e));
       n++;
     }
@@ -477,10 +456,10 @@ int lsd_host_stage(int img_w, int img_h, int Ws, int Hs, const float* deg, const
 
 // Resident scratch of a detector's LSD producer (grows only)
 struct LsdScratch {
-  unsigned char* d_gray = nullptr; double* d_blur = nullptr; char* d_out = nullptr; char* d_tab = nullptr;
-  char* h_out = nullptr;            // pinned: per image [modulus (double) | angle (float degrees)]
-  unsigned char* h_in = nullptr;    // pinned: the batch's images side by side (one upload)
-  size_t cap_in = 0, cap_out = 0;   // input pixels x images; bytes of the planes
+  cs::DevBuf<unsigned char> d_gray; cs::DevBuf<double> d_blur; cs::DevBuf<char> d_out, d_tab;
+  cs::PinBuf<char> h_out;           // per image [modulus (double) | angle (float degrees)]
+  cs::PinBuf<unsigned char> h_in;   // the batch's images side by side (one upload)
+  size_t cap_in = 0, cap_out = 0;   // input pixels x images (d_gray, d_blur, h_in grow together); bytes of the planes (d_out, h_out)
   cs::ChunkEvents chunks;
   int tab_w = 0, tab_h = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -489,19 +468,12 @@ struct LsdScratch {
 void lsd_scratch_free(void* p) {
   LsdScratch* S = (LsdScratch*)p;
   if (!S) return;
-  if (S->d_gray) (void)hipFree(S->d_gray);
-  if (S->d_blur) (void)hipFree(S->d_blur);
-  if (S->d_out) (void)hipFree(S->d_out);
-  if (S->d_tab) (void)hipFree(S->d_tab);
-  if (S->h_out) (void)hipHostFree(S->h_out);
-  if (S->h_in) (void)hipHostFree(S->h_in);
+  S->d_gray.release(); S->d_blur.release(); S->d_out.release(); S->d_tab.release(); S->h_out.release(); S->h_in.release();
   S->chunks.release();
   if (S->ev0) (void)hipEventDestroy(S->ev0);
   if (S->ev1) (void)hipEventDestroy(S->ev1);
   delete S;
 }
-
-double lsd_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
 
@@ -513,35 +485,32 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
     for (int i = 0; i < n_images; i++) n_lines[i] = 0;
     if (n_images == 0) return CS_OK;
     std::lock_guard<std::mutex> lk(*(std::mutex*)cs_internal_detector_lines_mutex(d));
-    LSD_TRY(hipSetDevice(cs_internal_detector_device(d)));
+    CS_HIP_TRY(hipSetDevice(cs_internal_detector_device(d)));
     hipStream_t st = (hipStream_t)cs_internal_detector_stream(d);
     void** slot = cs_internal_detector_lsd_slot(d, lsd_scratch_free);
     if (!*slot) *slot = new LsdScratch();
     LsdScratch& S = *(LsdScratch*)*slot;
-    const double t_begin = lsd_now_ms();
+    const double t_begin = cs::now_ms();
     // the scaled size: resize(..., Size(), 0.8, 0.8) rounds (saturate_cast<int>)
     const int Ws = (int)std::lrint(img_w * kScale), Hs = (int)std::lrint(img_h * kScale);
     const size_t N = (size_t)img_w * img_h, Ns = (size_t)Ws * Hs;
     const size_t out_stride = 8 * Ns + 4 * ((Ns + 1) & ~(size_t)1);       // per image: Ns doubles, Ns floats (padded to a multiple of 8 bytes)
     if (N * (size_t)n_images > S.cap_in) {
-      if (S.d_gray) (void)hipFree(S.d_gray);
-      if (S.d_blur) (void)hipFree(S.d_blur);
-      if (S.h_in) (void)hipHostFree(S.h_in);
-      S.d_gray = nullptr; S.d_blur = nullptr; S.h_in = nullptr; S.cap_in = 0;
-      LSD_TRY(hipMalloc((void**)&S.d_gray, N * (size_t)n_images));
-      LSD_TRY(hipHostMalloc((void**)&S.h_in, N * (size_t)n_images));
-      LSD_TRY(hipMalloc((void**)&S.d_blur, N * (size_t)n_images * sizeof(double)));
+      S.cap_in = 0;
+      int rc = S.d_gray.ensure(N * (size_t)n_images);
+      if (!rc) rc = S.h_in.ensure(N * (size_t)n_images);
+      if (!rc) rc = S.d_blur.ensure(N * (size_t)n_images);
+      if (rc) return rc;
       S.cap_in = N * (size_t)n_images;
     }
     if (out_stride * (size_t)n_images > S.cap_out) {
-      if (S.d_out) (void)hipFree(S.d_out);
-      if (S.h_out) (void)hipHostFree(S.h_out);
-      S.d_out = nullptr; S.h_out = nullptr; S.cap_out = 0;
-      LSD_TRY(hipMalloc((void**)&S.d_out, out_stride * (size_t)n_images));
-      LSD_TRY(hipHostMalloc((void**)&S.h_out, out_stride * (size_t)n_images));
+      S.cap_out = 0;
+      int rc = S.d_out.ensure(out_stride * (size_t)n_images);
+      if (!rc) rc = S.h_out.ensure(out_stride * (size_t)n_images);
+      if (rc) return rc;
       S.cap_out = out_stride * (size_t)n_images;
     }
-    if (!S.ev0) { LSD_TRY(hipEventCreate(&S.ev0)); LSD_TRY(hipEventCreate(&S.ev1)); }
+    if (!S.ev0) { CS_HIP_TRY(hipEventCreate(&S.ev0)); CS_HIP_TRY(hipEventCreate(&S.ev1)); }
     // resize's tables for this size: source offset and the two float weights per scaled column / row (pixel centres, INTER_LINEAR)
     const size_t tab_bytes = (size_t)(Ws + Hs) * (sizeof(int) + 2 * sizeof(float));
     if (S.tab_w != img_w || S.tab_h != img_h) {
@@ -565,19 +534,19 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
         f -= s;
         yo[i] = s; ya[2 * i] = 1.f - f; ya[2 * i + 1] = f;
       }
-      if (S.d_tab) (void)hipFree(S.d_tab);
-      S.d_tab = nullptr; S.tab_w = S.tab_h = 0;
-      LSD_TRY(hipMalloc((void**)&S.d_tab, tab_bytes));
-      LSD_TRY(hipMemcpy(S.d_tab, host.data(), tab_bytes, hipMemcpyHostToDevice));
+      S.tab_w = S.tab_h = 0;
+      const int rc = S.d_tab.ensure(tab_bytes);
+      if (rc) return rc;
+      CS_HIP_TRY(hipMemcpy(S.d_tab.p, host.data(), tab_bytes, hipMemcpyHostToDevice));
       S.tab_w = img_w; S.tab_h = img_h;
     }
     cs::LsdScaleTab T;
-    T.xo = (const int*)S.d_tab; T.yo = T.xo + Ws; T.xa = (const float*)(T.yo + Hs); T.ya = T.xa + 2 * (size_t)Ws;
+    T.xo = (const int*)S.d_tab.p; T.yo = T.xo + Ws; T.xa = (const float*)(T.yo + Hs); T.ya = T.xa + 2 * (size_t)Ws;
     // getGaussianKernel(7, 0.6 / 0.8, CV_64F): the window is 1 + 2 ceil(sigma sqrt(2 * 3 ln 10)) = 7 for these parameters (:452-456)
     cs::LsdGauss G;
     {
       const double sigma = kSigmaScale / kScale;
-      if (1 + 2 * (int)std::ceil(sigma * std::sqrt(2 * 3 * std::log(10.0))) != 7) { cs_set_error_ba("cs_detect_lsd_batch: window"); return CS_ERR_INVALID_ARG; }
+      if (1 + 2 * (int)std::ceil(sigma * std::sqrt(2 * 3 * std::log(10.0))) != 7) { cs_set_error("cs_detect_lsd_batch: window"); return CS_ERR_INVALID_ARG; }
       double sum = 0;
       for (int i = 0; i < 7; i++) { const double x = i - 3.0; G.k[i] = std::exp(-0.5 / (sigma * sigma) * x * x); sum += G.k[i]; }
       sum = 1. / sum;
@@ -588,7 +557,7 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
       const char* h; size_t out_stride; int w, h0, Ws, Hs; size_t Ns; double thr; float* const* lines4; int cap; int* n_lines; std::vector<int> rc;
       cs::ChunkGate gate; int device; const hipEvent_t* done; int n_chunks, n_images;
       const unsigned char* const* grays; unsigned char* h_in; size_t N;
-    } ctx{S.h_out, out_stride, img_w, img_h, Ws, Hs, Ns, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in, N};
+    } ctx{S.h_out.p, out_stride, img_w, img_h, Ws, Hs, Ns, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in.p, N};
     auto one = [](int i, void* vp) {
       Ctx& c = *(Ctx*)vp;
       const double* mod = (const double*)(c.h + c.out_stride * (size_t)i);
@@ -597,36 +566,36 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
     };
     double t_host;
     if (n_images == 1) {
-      LSD_TRY(hipMemcpyAsync(S.d_gray, grays[0], N, hipMemcpyHostToDevice, st));
-      LSD_TRY(hipEventRecord(S.ev0, st));
-      cs::launch_lsd_maps(S.d_gray, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur, S.d_out, out_stride, st, 1);
-      LSD_TRY(hipGetLastError());
-      LSD_TRY(hipEventRecord(S.ev1, st));
-      LSD_TRY(hipMemcpyAsync(S.h_out, S.d_out, out_stride, hipMemcpyDeviceToHost, st));
-      LSD_TRY(hipStreamSynchronize(st));
+      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, grays[0], N, hipMemcpyHostToDevice, st));
+      CS_HIP_TRY(hipEventRecord(S.ev0, st));
+      cs::launch_lsd_maps(S.d_gray.p, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur.p, S.d_out.p, out_stride, st, 1);
+      CS_HIP_TRY(hipGetLastError());
+      CS_HIP_TRY(hipEventRecord(S.ev1, st));
+      CS_HIP_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, out_stride, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipStreamSynchronize(st));
       float ms = 0;
-      LSD_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
+      CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
       S.device_ms = ms;
-      t_host = lsd_now_ms();
+      t_host = cs::now_ms();
       one(0, &ctx);
     } else {
       // a batch: the images gathered into pinned memory by the pool (the caller's buffers are pageable: 64 staged copies otherwise), one
       // upload, then chunk by chunk [kernels | copy back | event] -- all queued before the pool starts on the first chunk (batch_gate.h)
       cs_internal_detector_parallel(d, n_images, [](int i, void* vp) { Ctx& c = *(Ctx*)vp; std::memcpy(c.h_in + c.N * (size_t)i, c.grays[i], c.N); }, &ctx);
       const int CH = cs::BATCH_CHUNK, n_chunks = (n_images + CH - 1) / CH;
-      LSD_TRY(S.chunks.reserve(n_chunks));
-      LSD_TRY(hipMemcpyAsync(S.d_gray, S.h_in, N * (size_t)n_images, hipMemcpyHostToDevice, st));
+      CS_HIP_TRY(S.chunks.reserve(n_chunks));
+      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, S.h_in.p, N * (size_t)n_images, hipMemcpyHostToDevice, st));
       for (int c = 0; c < n_chunks; c++) {
         const int i0 = c * CH, ni = std::min(CH, n_images - i0);
-        LSD_TRY(hipEventRecord(S.chunks.k0[c], st));
-        cs::launch_lsd_maps(S.d_gray + (size_t)i0 * N, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur + (size_t)i0 * N, S.d_out + out_stride * (size_t)i0, out_stride, st, ni);
-        LSD_TRY(hipGetLastError());
-        LSD_TRY(hipEventRecord(S.chunks.k1[c], st));
-        LSD_TRY(hipMemcpyAsync(S.h_out + out_stride * (size_t)i0, S.d_out + out_stride * (size_t)i0, out_stride * (size_t)ni, hipMemcpyDeviceToHost, st));
-        LSD_TRY(hipEventRecord(S.chunks.done[c], st));
+        CS_HIP_TRY(hipEventRecord(S.chunks.k0[c], st));
+        cs::launch_lsd_maps(S.d_gray.p + (size_t)i0 * N, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur.p + (size_t)i0 * N, S.d_out.p + out_stride * (size_t)i0, out_stride, st, ni);
+        CS_HIP_TRY(hipGetLastError());
+        CS_HIP_TRY(hipEventRecord(S.chunks.k1[c], st));
+        CS_HIP_TRY(hipMemcpyAsync(S.h_out.p + out_stride * (size_t)i0, S.d_out.p + out_stride * (size_t)i0, out_stride * (size_t)ni, hipMemcpyDeviceToHost, st));
+        CS_HIP_TRY(hipEventRecord(S.chunks.done[c], st));
       }
       ctx.done = S.chunks.done.data(); ctx.n_chunks = n_chunks;
-      t_host = lsd_now_ms();
+      t_host = cs::now_ms();
       cs_internal_detector_parallel_long(d, n_images + 1, [](int t, void* vp) {
         Ctx& c = *(Ctx*)vp;
         if (t == 0) { c.gate.watch(c.device, c.done, c.n_chunks, cs::BATCH_CHUNK, c.n_images); return; }
@@ -636,16 +605,16 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
         try { c.rc[i] = lsd_host_stage(c.w, c.h0, c.Ws, c.Hs, (const float*)(mod + c.Ns), mod, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i]); }
         catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
       }, &ctx);
-      LSD_TRY(hipStreamSynchronize(st));          // (every chunk's event has been waited for; this also surfaces a late error)
+      CS_HIP_TRY(hipStreamSynchronize(st));          // (every chunk's event has been waited for; this also surfaces a late error)
       double dev = 0;
-      for (int c = 0; c < n_chunks; c++) { float ms = 0; LSD_TRY(hipEventElapsedTime(&ms, S.chunks.k0[c], S.chunks.k1[c])); dev += ms; }
+      for (int c = 0; c < n_chunks; c++) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, S.chunks.k0[c], S.chunks.k1[c])); dev += ms; }
       S.device_ms = dev;
     }
-    S.host_ms = lsd_now_ms() - t_host; S.total_ms = lsd_now_ms() - t_begin;
+    S.host_ms = cs::now_ms() - t_host; S.total_ms = cs::now_ms() - t_begin;
     for (int r : ctx.rc) if (r) return r;
     return CS_OK;
   } catch (const std::exception& ex) {
-    cs_set_error_ba(std::string("cs_detect_lsd_batch: ") + ex.what());
+    cs_set_error(std::string("cs_detect_lsd_batch: ") + ex.what());
     return CS_ERR_CAPACITY;
   }
 }

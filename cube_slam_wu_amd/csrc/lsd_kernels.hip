@@ -12,13 +12,9 @@
 #include <cfloat>
 #include <cstdint>
 
-namespace cs {
+#include "lsd_types.h"
 
-struct LsdGauss { double k[7]; };                  // getGaussianKernel(7, 0.75, CV_64F)
-struct LsdScaleTab {                               // resize's per-column / per-row source offsets and weights (computed on the host)
-  const int* xo; const float* xa;                  // W_s offsets, 2 W_s weights
-  const int* yo; const float* ya;                  // H_s offsets, 2 H_s weights
-};
+namespace cs {
 
 #define LSD_NOTDEF (-1024.0)
 

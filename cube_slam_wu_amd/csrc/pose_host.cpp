@@ -7,7 +7,6 @@
 // There is no CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -15,57 +14,28 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "cs_hip_util.h"
 #include "pose_types.h"
-
-void cs_set_error_ba(const std::string& s);
-
-#define POSE_TRY(expr)                                                         \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cs_set_error_ba(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
 
 struct cs_pose_batch {
   int device = 0;
   hipStream_t st = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  unsigned char* d_in = nullptr; size_t in_cap = 0;      // [T0 | intr | records | obs_ptr], one upload
-  unsigned char* d_out = nullptr; size_t out_cap = 0;    // [T_out | chi2 | iterations | inlier], one download
-  unsigned char* h_in = nullptr; size_t h_in_cap = 0;    // pinned staging of the two
-  unsigned char* h_out = nullptr; size_t h_out_cap = 0;
+  cs::DevBuf<unsigned char> d_in;      // [T0 | intr | records | obs_ptr], one upload
+  cs::DevBuf<unsigned char> d_out;     // [T_out | chi2 | iterations | inlier], one download
+  cs::PinBuf<unsigned char> h_in, h_out;     // pinned staging of the two
   double kernel_ms = 0, host_ms = 0;
   bool ran = false;
 };
 
 namespace {
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-int grow_dev(unsigned char** p, size_t* cap, size_t need) {
-  if (need <= *cap) return CS_OK;
-  if (*p) { POSE_TRY(hipFree(*p)); *p = nullptr; *cap = 0; }
-  const size_t n = align256(need + need / 4);
-  POSE_TRY(hipMalloc((void**)p, n));
-  *cap = n;
-  return CS_OK;
-}
-int grow_host(unsigned char** p, size_t* cap, size_t need) {
-  if (need <= *cap) return CS_OK;
-  if (*p) { POSE_TRY(hipHostFree(*p)); *p = nullptr; *cap = 0; }
-  const size_t n = align256(need + need / 4);
-  POSE_TRY(hipHostMalloc((void**)p, n));
-  *cap = n;
-  return CS_OK;
-}
-
 int check_params(const cs_pose_params* p) {
-  if (!p || p->n_rounds < 1 || p->n_rounds > cs::POSE_MAX_ROUNDS) { cs_set_error_ba("cs_pose: n_rounds must be 1..8"); return CS_ERR_INVALID_ARG; }
+  if (!p || p->n_rounds < 1 || p->n_rounds > cs::POSE_MAX_ROUNDS) { cs_set_error("cs_pose: n_rounds must be 1..8"); return CS_ERR_INVALID_ARG; }
   for (int r = 0; r < p->n_rounds; r++)
-    if (p->iterations[r] < 0) { cs_set_error_ba("cs_pose: negative iteration count"); return CS_ERR_INVALID_ARG; }
+    if (p->iterations[r] < 0) { cs_set_error("cs_pose: negative iteration count"); return CS_ERR_INVALID_ARG; }
   return CS_OK;
 }
 
@@ -88,16 +58,16 @@ int cs_pose_batch_create(int device, cs_pose_batch** out) {
   if (!out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error_ba("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { cs_set_error_ba("device index out of range"); return CS_ERR_INVALID_ARG; }
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
+  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
   cs_pose_batch* B = new (std::nothrow) cs_pose_batch();
   if (!B) return CS_ERR_CAPACITY;
   struct Guard { cs_pose_batch* b; ~Guard() { if (b) cs_pose_batch_destroy(b); } } g{B};
   B->device = device;
-  POSE_TRY(hipSetDevice(device));
-  POSE_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
-  POSE_TRY(hipEventCreate(&B->ev0));
-  POSE_TRY(hipEventCreate(&B->ev1));
+  CS_HIP_TRY(hipSetDevice(device));
+  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
+  CS_HIP_TRY(hipEventCreate(&B->ev0));
+  CS_HIP_TRY(hipEventCreate(&B->ev1));
   g.b = nullptr;
   *out = B;
   return CS_OK;
@@ -107,10 +77,7 @@ void cs_pose_batch_destroy(cs_pose_batch* B) {
   if (!B) return;
   (void)hipSetDevice(B->device);
   if (B->st) (void)hipStreamSynchronize(B->st);
-  if (B->d_in) (void)hipFree(B->d_in);
-  if (B->d_out) (void)hipFree(B->d_out);
-  if (B->h_in) (void)hipHostFree(B->h_in);
-  if (B->h_out) (void)hipHostFree(B->h_out);
+  B->d_in.release(); B->d_out.release(); B->h_in.release(); B->h_out.release();
   if (B->ev0) (void)hipEventDestroy(B->ev0);
   if (B->ev1) (void)hipEventDestroy(B->ev1);
   if (B->st) (void)hipStreamDestroy(B->st);
@@ -124,31 +91,31 @@ int cs_pose_batch_optimize(cs_pose_batch* B, const cs_pose_params* p, int n_fram
   int rc = check_params(p); if (rc) return rc;
   B->ran = false;
   if (n_frames == 0) { B->kernel_ms = B->host_ms = 0; B->ran = true; return CS_OK; }
-  if (!Tcw7_in || !intr5 || !obs_ptr || !Tcw7_out) { cs_set_error_ba("cs_pose_batch_optimize: NULL argument"); return CS_ERR_INVALID_ARG; }
-  const double t_begin = now_ms();
+  if (!Tcw7_in || !intr5 || !obs_ptr || !Tcw7_out) { cs_set_error("cs_pose_batch_optimize: NULL argument"); return CS_ERR_INVALID_ARG; }
+  const double t_begin = cs::now_ms();
   // the kernel indexes the records by obs_ptr alone: it must be a non-decreasing partition of [0, n_obs)
-  if (obs_ptr[0] != 0) { cs_set_error_ba("cs_pose_batch_optimize: obs_ptr[0] must be 0"); return CS_ERR_INVALID_ARG; }
+  if (obs_ptr[0] != 0) { cs_set_error("cs_pose_batch_optimize: obs_ptr[0] must be 0"); return CS_ERR_INVALID_ARG; }
   for (int f = 0; f < n_frames; f++)
-    if (obs_ptr[f + 1] < obs_ptr[f]) { cs_set_error_ba("cs_pose_batch_optimize: obs_ptr must not decrease"); return CS_ERR_INVALID_ARG; }
+    if (obs_ptr[f + 1] < obs_ptr[f]) { cs_set_error("cs_pose_batch_optimize: obs_ptr must not decrease"); return CS_ERR_INVALID_ARG; }
   const size_t n_obs = (size_t)obs_ptr[n_frames];
-  if (n_obs > 0 && (!Xw3 || !meas3 || !info9 || !is_stereo || !inlier_out)) { cs_set_error_ba("cs_pose_batch_optimize: NULL observation array"); return CS_ERR_INVALID_ARG; }
+  if (n_obs > 0 && (!Xw3 || !meas3 || !info9 || !is_stereo || !inlier_out)) { cs_set_error("cs_pose_batch_optimize: NULL observation array"); return CS_ERR_INVALID_ARG; }
   const size_t R = (size_t)p->n_rounds, nf = (size_t)n_frames;
 
   // ---- layout of the two buffers (every part 256-byte aligned)
   const size_t in_T = 0, in_intr = align256(in_T + 7 * nf * 8), in_obs = align256(in_intr + 5 * nf * 8), in_ptr = align256(in_obs + n_obs * cs::POSE_OBS_DOUBLES * 8),
                in_bytes = align256(in_ptr + (nf + 1) * 4);
   const size_t out_T = 0, out_chi = align256(out_T + 7 * nf * 8), out_it = align256(out_chi + nf * R * 8), out_lv = align256(out_it + nf * R * 4), out_bytes = align256(out_lv + n_obs);
-  POSE_TRY(hipSetDevice(B->device));
-  rc = grow_dev(&B->d_in, &B->in_cap, in_bytes); if (rc) return rc;
-  rc = grow_dev(&B->d_out, &B->out_cap, out_bytes); if (rc) return rc;
-  rc = grow_host(&B->h_in, &B->h_in_cap, in_bytes); if (rc) return rc;
-  rc = grow_host(&B->h_out, &B->h_out_cap, out_bytes); if (rc) return rc;
+  CS_HIP_TRY(hipSetDevice(B->device));
+  rc = B->d_in.ensure(in_bytes); if (rc) return rc;
+  rc = B->d_out.ensure(out_bytes); if (rc) return rc;
+  rc = B->h_in.ensure(in_bytes); if (rc) return rc;
+  rc = B->h_out.ensure(out_bytes); if (rc) return rc;
 
   // ---- pack
-  std::memcpy(B->h_in + in_T, Tcw7_in, 7 * nf * 8);
-  std::memcpy(B->h_in + in_intr, intr5, 5 * nf * 8);
-  std::memcpy(B->h_in + in_ptr, obs_ptr, (nf + 1) * 4);
-  double* rec = reinterpret_cast<double*>(B->h_in + in_obs);
+  std::memcpy(B->h_in.p + in_T, Tcw7_in, 7 * nf * 8);
+  std::memcpy(B->h_in.p + in_intr, intr5, 5 * nf * 8);
+  std::memcpy(B->h_in.p + in_ptr, obs_ptr, (nf + 1) * 4);
+  double* rec = reinterpret_cast<double*>(B->h_in.p + in_obs);
   for (size_t i = 0; i < n_obs; i++, rec += cs::POSE_OBS_DOUBLES) {
     const double *X = Xw3 + 3 * i, *m = meas3 + 3 * i, *W = info9 + 9 * i;
     rec[0] = X[0]; rec[1] = X[1]; rec[2] = X[2];
@@ -168,31 +135,31 @@ int cs_pose_batch_optimize(cs_pose_batch* B, const cs_pose_params* p, int n_fram
   for (int r = 0; r < cs::POSE_MAX_ROUNDS; r++) a.iterations[r] = r < p->n_rounds ? p->iterations[r] : 0;
   a.robust_rounds = p->robust_rounds; a.restart_each_round = p->restart_each_round ? 1 : 0;
   a.huber_mono = p->huber_mono; a.huber_stereo = p->huber_stereo; a.chi2_mono = p->chi2_mono; a.chi2_stereo = p->chi2_stereo;
-  a.T0 = reinterpret_cast<const double*>(B->d_in + in_T);
-  a.intr = reinterpret_cast<const double*>(B->d_in + in_intr);
-  a.obs = reinterpret_cast<const double*>(B->d_in + in_obs);
-  a.obs_ptr = reinterpret_cast<const int*>(B->d_in + in_ptr);
-  a.T_out = reinterpret_cast<double*>(B->d_out + out_T);
-  a.chi2_out = reinterpret_cast<double*>(B->d_out + out_chi);
-  a.iters_out = reinterpret_cast<int*>(B->d_out + out_it);
-  a.inlier = B->d_out + out_lv;
+  a.T0 = reinterpret_cast<const double*>(B->d_in.p + in_T);
+  a.intr = reinterpret_cast<const double*>(B->d_in.p + in_intr);
+  a.obs = reinterpret_cast<const double*>(B->d_in.p + in_obs);
+  a.obs_ptr = reinterpret_cast<const int*>(B->d_in.p + in_ptr);
+  a.T_out = reinterpret_cast<double*>(B->d_out.p + out_T);
+  a.chi2_out = reinterpret_cast<double*>(B->d_out.p + out_chi);
+  a.iters_out = reinterpret_cast<int*>(B->d_out.p + out_it);
+  a.inlier = B->d_out.p + out_lv;
 
-  POSE_TRY(hipMemcpyAsync(B->d_in, B->h_in, in_bytes, hipMemcpyHostToDevice, B->st));
-  POSE_TRY(hipEventRecord(B->ev0, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->d_in.p, B->h_in.p, in_bytes, hipMemcpyHostToDevice, B->st));
+  CS_HIP_TRY(hipEventRecord(B->ev0, B->st));
   cs::pose_launch(a, B->st);
-  POSE_TRY(hipGetLastError());
-  POSE_TRY(hipEventRecord(B->ev1, B->st));
-  POSE_TRY(hipMemcpyAsync(B->h_out, B->d_out, out_bytes, hipMemcpyDeviceToHost, B->st));
-  POSE_TRY(hipStreamSynchronize(B->st));
+  CS_HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipEventRecord(B->ev1, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_out.p, B->d_out.p, out_bytes, hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
   float ms = 0;
-  POSE_TRY(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev0, B->ev1));
 
-  std::memcpy(Tcw7_out, B->h_out + out_T, 7 * nf * 8);
-  if (chi2_out) std::memcpy(chi2_out, B->h_out + out_chi, nf * R * 8);
-  if (iterations_done) std::memcpy(iterations_done, B->h_out + out_it, nf * R * 4);
-  if (n_obs) std::memcpy(inlier_out, B->h_out + out_lv, n_obs);
+  std::memcpy(Tcw7_out, B->h_out.p + out_T, 7 * nf * 8);
+  if (chi2_out) std::memcpy(chi2_out, B->h_out.p + out_chi, nf * R * 8);
+  if (iterations_done) std::memcpy(iterations_done, B->h_out.p + out_it, nf * R * 4);
+  if (n_obs) std::memcpy(inlier_out, B->h_out.p + out_lv, n_obs);
   B->kernel_ms = ms;
-  B->host_ms = now_ms() - t_begin;
+  B->host_ms = cs::now_ms() - t_begin;
   B->ran = true;
   return CS_OK;
 }

@@ -6,7 +6,7 @@
 
 #include <cstdio>
 
-void cs_set_error_ba(const std::string& s) { fprintf(stderr, "%s\n", s.c_str()); }
+void cs_set_error(const std::string& s) { fprintf(stderr, "%s\n", s.c_str()); }
 extern "C" void* cs_internal_detector_stream(cs_detector*) { return nullptr; }
 extern "C" int cs_internal_detector_device(cs_detector*) { return 0; }
 extern "C" void** cs_internal_detector_lines_slot(cs_detector*, void (*)(void*)) { return nullptr; }

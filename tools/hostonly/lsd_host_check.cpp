@@ -7,7 +7,7 @@
 
 #include <cstdio>
 
-void cs_set_error_ba(const std::string& s) { fprintf(stderr, "%s\n", s.c_str()); }
+void cs_set_error(const std::string& s) { fprintf(stderr, "%s\n", s.c_str()); }
 extern "C" void* cs_internal_detector_stream(cs_detector*) { return nullptr; }
 extern "C" int cs_internal_detector_device(cs_detector*) { return 0; }
 extern "C" void** cs_internal_detector_lsd_slot(cs_detector*, void (*)(void*)) { return nullptr; }
@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
     double* mod;
     oracle_planes_f(gi, w, h, &Ws, &Hs, &deg, &mod);
     double best = 1e30;
-    for (int r = 0; r < reps; r++) { const double t0 = lsd_now_ms(); lsd_host_stage(w, h, Ws, Hs, deg, mod, 15.0, out.data(), 20000, &n); best = std::min(best, lsd_now_ms() - t0); }
+    for (int r = 0; r < reps; r++) { const double t0 = cs::now_ms(); lsd_host_stage(w, h, Ws, Hs, deg, mod, 15.0, out.data(), 20000, &n); best = std::min(best, cs::now_ms() - t0); }
     t_all += best;
     const int nr = lsd_oracle_detect(gi, w, h, 15.0, ref.data(), 20000);
     if (n != nr || memcmp(out.data(), ref.data(), 16 * (size_t)n)) { bad++; printf("image %d differs (%d vs %d segments)\n", i, n, nr); }

@@ -12,12 +12,7 @@
 #include <cstring>
 #include <vector>
 
-namespace cs {
-void ba_launch_band_cholesky(double* Sb, double* work, int n, int LD, double* rhs, int* info, bool solve, hipStream_t st, bool one_sided);
-size_t ba_band_workspace_doubles(int n, int LD);
-void ba_launch_bcr(const double* Sb, double* work, int n, int LD, int Bv, double* rhs, int* info, hipStream_t st);
-size_t ba_bcr_workspace_doubles(int n, int Bv);
-}
+#include "../../cube_slam_wu_amd/csrc/ba_types.h"
 
 int main(int argc, char** argv) {
   int n = argc > 1 ? atoi(argv[1]) : 10494, LD = argc > 2 ? atoi(argv[2]) : 183, reps = argc > 3 ? atoi(argv[3]) : 5;
