@@ -425,6 +425,7 @@ DECLARED_SYMBOLS += [
     "cs_ba_get_state", "cs_ba_sizes", "cs_ba_solver_layout", "cs_ba_get_system", "cs_ba_last_timing", "cs_ba_set_shard", "cs_ba_optimize_sharded",
     "cs_ba_shard_landmark_owners", "cs_ba_get_landmark_owners", "cs_ba_shard_info", "cs_ba_shard_timing", "cs_ba_append_vertices", "cs_ba_append_edges_proj", "cs_ba_append_edges_cuboid", "cs_ba_append_edges_cuboid_proj", "cs_ba_append_edges_odom", "cs_ba_get_vertex_hessians", "cs_ba_schur_layout", "cs_ba_structure_digest", "cs_ba_reduced_size", "cs_ba_solver_path", "cs_ba_band_order", "cs_ba_comm_unique_id", "cs_ba_comm_init", "cs_ba_set_robust_kernels",
     "cs_ba_set_external_edges", "cs_ba_set_external_terms", "cs_ba_set_external_chi2", "cs_ba_set_external_callback", "cs_ba_check_finite", "cs_ba_dump", "cs_ba_load", "cs_ba_get_reduced_system", "cs_ba_set_stage_timing", "cs_ba_set_lm_params", "cs_ba_pose_marginals",
+    "cs_ba_set_edges_proj_stereo", "cs_ba_append_edges_proj_stereo",
 ]
 
 
@@ -465,6 +466,13 @@ class BaProblem:
         _chk(lib().cs_ba_set_edges_proj(self.h, self.n_proj, _ip(pt), _ip(cam), _dp(_f64(uv, (-1, 2))), _dp(_f64(info4, (-1, 4))), _dp(_f64(intr4, (-1, 4))),
                                         _dp(hb) if hb is not None else None), "cs_ba_set_edges_proj")
 
+    def set_edges_proj_stereo(self, pt, cam, uvr3, info9, intr5, huber=None):
+        """EdgeStereoSE3ProjectXYZ: uvr3 = (u_left, v, u_right), info9 row-major 3 x 3, intr5 = fx fy cx cy bf; they follow the mono edges in g2o's order."""
+        pt, cam = _i32(pt), _i32(cam); self.n_stereo = len(pt)
+        hb = _f64(huber, (-1,)) if huber is not None else None
+        _chk(lib().cs_ba_set_edges_proj_stereo(self.h, self.n_stereo, _ip(pt), _ip(cam), _dp(_f64(uvr3, (-1, 3))), _dp(_f64(info9, (-1, 9))), _dp(_f64(intr5, (-1, 5))),
+                                               _dp(hb) if hb is not None else None), "cs_ba_set_edges_proj_stereo")
+
     def set_edges_cuboid(self, cam, cub, meas10, info81):
         cam, cub = _i32(cam), _i32(cub); self.n_cub = len(cam)
         _chk(lib().cs_ba_set_edges_cuboid(self.h, self.n_cub, _ip(cam), _ip(cub), _dp(_f64(meas10, (-1, 10))), _dp(_f64(info81, (-1, 81)))), "cs_ba_set_edges_cuboid")
@@ -481,7 +489,7 @@ class BaProblem:
 
     def set_robust_kernels(self, edge_class, kind, delta):
         """cs_ba_set_robust_kernels: edge_class 0 projection / 1 EdgeSE3Cuboid / 2 EdgeSE3CuboidProj / 3 EdgeSE3Expmap; kind per edge
-        (RK_* below), delta = RobustKernel::delta().  kind None removes the class's kernels."""
+        (RK_* below), delta = RobustKernel::delta(); 4 = the stereo projection edges.  kind None removes the class's kernels."""
         if kind is None:        # (the library counts the class's edges itself: no shadow count here, a handle from Problem.load() has none)
             _chk(lib().cs_ba_set_robust_kernels(self.h, int(edge_class), 0, None, None), "cs_ba_set_robust_kernels")
             return
@@ -530,6 +538,13 @@ class BaProblem:
         _chk(lib().cs_ba_append_edges_proj(self.h, len(pt), _ip(pt), _ip(cam), _dp(_f64(uv, (-1, 2))), _dp(_f64(info4, (-1, 4))), _dp(_f64(intr4, (-1, 4))), _dp(hb) if hb is not None else None), "cs_ba_append_edges_proj")
         self.n_proj = getattr(self, "n_proj", 0) + len(pt)
 
+    def append_edges_proj_stereo(self, pt, cam, uvr3, info9, intr5, huber=None):
+        pt, cam = _i32(pt), _i32(cam)
+        hb = _f64(huber, (-1,)) if huber is not None else None
+        _chk(lib().cs_ba_append_edges_proj_stereo(self.h, len(pt), _ip(pt), _ip(cam), _dp(_f64(uvr3, (-1, 3))), _dp(_f64(info9, (-1, 9))), _dp(_f64(intr5, (-1, 5))),
+                                                  _dp(hb) if hb is not None else None), "cs_ba_append_edges_proj_stereo")
+        self.n_stereo = getattr(self, "n_stereo", 0) + len(pt)
+
     def append_edges_cuboid(self, cam, cub, meas10, info81):
         cam, cub = _i32(cam), _i32(cub)
         _chk(lib().cs_ba_append_edges_cuboid(self.h, len(cam), _ip(cam), _ip(cub), _dp(_f64(meas10, (-1, 10))), _dp(_f64(info81, (-1, 81)))), "cs_ba_append_edges_cuboid")
@@ -551,7 +566,7 @@ class BaProblem:
     def build_system(self, dense_hpp=True):
         _chk(lib().cs_ba_build_system(self.h), "cs_ba_build_system")
         n, nl = self.sizes()
-        Hpp, Hll, Hpl, b = (np.zeros((n, n)) if dense_hpp else None), np.zeros((nl // 3, 9)), np.zeros((self.n_proj, 18)), np.zeros(n + nl)
+        Hpp, Hll, Hpl, b = (np.zeros((n, n)) if dense_hpp else None), np.zeros((nl // 3, 9)), np.zeros((self.n_proj + getattr(self, "n_stereo", 0), 18)), np.zeros(n + nl)
         _chk(lib().cs_ba_get_system(self.h, _dp(Hpp) if dense_hpp else None, _dp(Hll), _dp(Hpl), _dp(b), None), "cs_ba_get_system")
         return Hpp, Hll, Hpl, b
 
@@ -730,7 +745,7 @@ class BaProblem:
 
     @classmethod
     def load(cls, path, sizes, device=0):
-        """cs_ba_load; sizes = (n_cams, n_cuboids, n_points, n_proj) of the dumped problem (the Python wrapper sizes its host arrays with them)."""
+        """cs_ba_load; sizes = (n_cams, n_cuboids, n_points, n_proj) of the dumped problem, n_proj counting mono and stereo projection edges (the Python wrapper sizes its host arrays with them)."""
         P = cls.__new__(cls)
         P.h = C.c_void_p()
         _chk(lib().cs_ba_load(str(path).encode(), int(device), C.byref(P.h)), "cs_ba_load")
@@ -772,7 +787,7 @@ class BaProblem:
 
 
 RK_NONE, RK_HUBER, RK_PSEUDO_HUBER, RK_CAUCHY, RK_SATURATED, RK_DCS, RK_TUKEY = range(7)      # enum cs_robust_kernel
-EDGE_PROJ, EDGE_CUBOID, EDGE_CUBOID_PROJ, EDGE_ODOM = range(4)                                 # enum cs_edge_class
+EDGE_PROJ, EDGE_CUBOID, EDGE_CUBOID_PROJ, EDGE_ODOM, EDGE_PROJ_STEREO = range(5)               # enum cs_edge_class
 
 
 def ba_from_dict(pr, device=0, cuboids_first=False):
@@ -780,6 +795,8 @@ def ba_from_dict(pr, device=0, cuboids_first=False):
     P = BaProblem(pr["cams"], pr["cam_fixed"], pr["cuboids"], pr["cub_fixed"], pr["points"], pr["pt_fixed"], cuboids_first=cuboids_first, device=device)
     if len(pr["e_pt"]):
         P.set_edges_proj(pr["e_pt"], pr["e_cam"], pr["e_uv"], pr["e_info"], pr["e_intr"], pr["e_huber"])
+    if len(pr.get("se_pt", [])):          # (synth_ba.make_stereo_problem)
+        P.set_edges_proj_stereo(pr["se_pt"], pr["se_cam"], pr["se_uvr"], pr["se_info"], pr["se_intr"], pr["se_huber"])
     if len(pr["ce_cam"]):
         P.set_edges_cuboid(pr["ce_cam"], pr["ce_cub"], pr["ce_meas"], pr["ce_info"])
     if len(pr.get("pe_cam", [])):

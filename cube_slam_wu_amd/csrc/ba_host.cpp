@@ -284,7 +284,16 @@ struct cs_ba {
   std::vector<int> u3_cam, u3_cub, up_cam, up_cub;      // the caller's two lists
   std::vector<double> h_pe_meas, h_pe_info, h_pe_K;
   DBuf<double> pe_meas, pe_info, pe_K;
-  std::vector<int> e_pt, e_cam;      // projection edges, caller order
+  std::vector<int> e_pt, e_cam;      // projection edges, caller order: the mono edges [0, n_proj - n_stereo), the stereo edges behind them (g2o's edge order)
+  // stereo projection edges (EdgeStereoSE3ProjectXYZ; cs_ba_set_edges_proj_stereo): counted in n_proj, their payload in the caller's order on the
+  // host until the structure phase puts it beside the mono edges' in the two edge orders
+  int n_stereo = 0;
+  std::vector<double> h_se_uv, h_se_ur, h_se_intr, h_se_sinfo, h_se_huber;   // 2, 1, 4 (fx fy cx cy), 10 (information 3 x 3, bf), 1 (empty: no kernel) per edge
+  std::vector<int> rk_stereo;                                                // kernel kinds (cs_ba_set_robust_kernels), empty: Huber from the deltas
+  bool intr_uniform_all = false, sinfo_uniform = false;                      // decided by the structure phase: BaView::intr_u over both classes, sinfo_u
+  DBuf<double> comb_uv, comb_info, comb_intr, comb_huber;                    // a stereo graph's rows of both classes in e_pt's order (the gathers' source)
+  DBuf<double> d_pm_ur, d_cm_ur, d_pm_sinfo, d_cm_sinfo;
+  DBuf<int> d_pm_kind, d_cm_kind;
   DBuf<int> d_src;                   // device copy of slot_src (the gathers of the structure phase)
   std::unique_ptr<int[]> slot_src;   // point-major slot -> caller edge (uninitialised storage with head room: kept across structure phases)
   size_t slot_src_cap = 0; int slot_src_n = 0;
@@ -1031,6 +1040,20 @@ int finalize_structure(cs_ba* B) {
   // arrays of E ints through blocking copies (0.3-0.4 ms each at a million edges, from pageable memory), the zero-fills and the eight
   // gathers that put the caller's measurement rows into both edge orders.  Everything is queued on B->st; the phase's one wait is
   // at its end.  (The staging arena is this thread's: the helper copies directly.)
+  // stereo edges: which records are the same for every edge (the structure is unsharded here: cs_ba_set_shard refuses a stereo graph, so E = n_proj)
+  const int nS = B->n_stereo, nM = B->n_proj - nS;
+  if (nS > 0) {
+    if (B->shard_n > 1 || E != B->n_proj) { cs_set_error("stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
+    const char* env = getenv("CS_BA_UNIFORM");
+    const bool on = !env || atoi(env) != 0;
+    if (nM == 0) std::memcpy(B->uni8 + 4, B->h_se_intr.data(), 32);      // (no mono edge: the first stereo edge's intrinsics are the reference record)
+    B->intr_uniform_all = nM > 0 ? B->intr_uniform : on;
+    B->sinfo_uniform = on;
+    for (int s = 0; s < nS && (B->intr_uniform_all || B->sinfo_uniform); s++) {
+      if (B->intr_uniform_all && std::memcmp(&B->h_se_intr[4 * (size_t)s], B->uni8 + 4, 32) != 0) B->intr_uniform_all = false;
+      if (B->sinfo_uniform && std::memcmp(&B->h_se_sinfo[10 * (size_t)s], B->h_se_sinfo.data(), 80) != 0) B->sinfo_uniform = false;
+    }
+  }
   int edge_rc = CS_OK;
   std::thread edge_th([&]() {
     edge_rc = [&]() -> int {
@@ -1040,14 +1063,51 @@ int finalize_structure(cs_ba* B) {
 #define ER(call) do { r = (call); if (r) return r; } while (0)
       ER(B->cm_pm.upload_ptr(cm_pm.data(), Ez)); ER(B->d_src.upload_ptr(src_of_slot, Ez));
       // (the information / intrinsics records in the two edge orders only when they differ between edges: BaView::info_u / intr_u otherwise)
-      const bool per_info = !B->info_uniform, per_intr = !B->intr_uniform;
+      bool per_info = !B->info_uniform, per_intr = !B->intr_uniform, have_hub = B->have_huber;
+      const double* src_uv = B->raw_uv.p; const double* src_info = B->raw_info.p; const double* src_intr = B->raw_intr.p; const double* src_huber = B->raw_huber.p;
+      if (nS > 0) {
+        // A stereo graph: the gathers below index rows in e_pt's order -- the mono edges' rows (on the device since they were set), then the stereo
+        // edges' (on the host) -- so the two are put behind each other first.  A mono edge's slot of a stereo-only field stays zero and the reverse.
+        const size_t Mz = (size_t)nM, Sz = (size_t)nS;
+        auto rows = [&](DBuf<double>& comb, int w, const double* mono_dev, const double* mono_rec4, const double* st_host) -> int {
+          int rr = comb.reserve((size_t)w * (Mz + Sz)); if (rr) return rr;
+          comb.n = (size_t)w * (Mz + Sz);
+          if (Mz && mono_dev) CS_HIP_TRY(hipMemcpyAsync(comb.p, mono_dev, 8 * (size_t)w * Mz, hipMemcpyDeviceToDevice, B->st));
+          else if (Mz && mono_rec4) cs::ba_launch_fill_rows4(comb.p, mono_rec4, nM, B->st);
+          else if (Mz) CS_HIP_TRY(hipMemsetAsync(comb.p, 0, 8 * (size_t)w * Mz, B->st));
+          if (st_host) CS_HIP_TRY(hipMemcpy(comb.p + (size_t)w * Mz, st_host, 8 * (size_t)w * Sz, hipMemcpyHostToDevice));
+          else CS_HIP_TRY(hipMemsetAsync(comb.p + (size_t)w * Mz, 0, 8 * (size_t)w * Sz, B->st));
+          return CS_OK;
+        };
+        per_info = nM > 0 && !B->info_uniform; per_intr = !B->intr_uniform_all; have_hub = B->have_huber || !B->h_se_huber.empty();
+        ER(rows(B->comb_uv, 2, B->raw_uv.p, nullptr, B->h_se_uv.data())); src_uv = B->comb_uv.p;
+        if (per_info) { ER(rows(B->comb_info, 4, B->raw_info.p, nullptr, nullptr)); src_info = B->comb_info.p; }
+        if (per_intr) { ER(rows(B->comb_intr, 4, B->raw_intr_virtual ? nullptr : B->raw_intr.p, B->uni8 + 4, B->h_se_intr.data())); src_intr = B->comb_intr.p; }
+        if (have_hub) { ER(rows(B->comb_huber, 1, B->have_huber ? B->raw_huber.p : nullptr, nullptr, B->h_se_huber.empty() ? nullptr : B->h_se_huber.data())); src_huber = B->comb_huber.p; }
+        // the stereo-only fields in both orders, built here from the host rows
+        const bool per_sinfo = !B->sinfo_uniform;
+        std::vector<int> pk(Ez), ck(Ez);
+        std::vector<double> pu(Ez), cu(Ez), ps(per_sinfo ? 10 * Ez : 0), cs10(per_sinfo ? 10 * Ez : 0);
+        for (size_t sl = 0; sl < Ez; sl++) {
+          const int s = src_of_slot[sl] - nM;
+          pk[sl] = s >= 0; pu[sl] = s >= 0 ? B->h_se_ur[s] : 0.0;
+          if (per_sinfo) { if (s >= 0) std::memcpy(&ps[10 * sl], &B->h_se_sinfo[10 * (size_t)s], 80); else std::memset(&ps[10 * sl], 0, 80); }
+        }
+        for (size_t q = 0; q < Ez; q++) {
+          const size_t sl = (size_t)cm_pm[q];
+          ck[q] = pk[sl]; cu[q] = pu[sl];
+          if (per_sinfo) std::memcpy(&cs10[10 * q], &ps[10 * sl], 80);
+        }
+        ER(B->d_pm_kind.upload(pk)); ER(B->d_cm_kind.upload(ck)); ER(B->d_pm_ur.upload(pu)); ER(B->d_cm_ur.upload(cu));
+        if (per_sinfo) { ER(B->d_pm_sinfo.upload(ps)); ER(B->d_cm_sinfo.upload(cs10)); }
+      }
       ER(B->pm_uv.alloc(2 * Ez, B->st)); ER(B->pm_huber.alloc(Ez, B->st)); ER(B->cm_uv.alloc(2 * Ez, B->st)); ER(B->cm_huber.alloc(Ez, B->st));
       if (per_info) { ER(B->pm_info.alloc(4 * Ez, B->st)); ER(B->cm_info.alloc(4 * Ez, B->st)); }
       if (per_intr) { ER(B->pm_intr.alloc(4 * Ez, B->st)); ER(B->cm_intr.alloc(4 * Ez, B->st)); }
-      cs::ba_launch_gather_rows(B->raw_uv.p, B->d_src.p, E, 2, B->pm_uv.p, B->st);
-      if (per_info) cs::ba_launch_gather_rows(B->raw_info.p, B->d_src.p, E, 4, B->pm_info.p, B->st);
-      if (per_intr) cs::ba_launch_gather_rows(B->raw_intr.p, B->d_src.p, E, 4, B->pm_intr.p, B->st);
-      if (B->have_huber) cs::ba_launch_gather_rows(B->raw_huber.p, B->d_src.p, E, 1, B->pm_huber.p, B->st);   // (else: zeros from the allocation)
+      cs::ba_launch_gather_rows(src_uv, B->d_src.p, E, 2, B->pm_uv.p, B->st);
+      if (per_info) cs::ba_launch_gather_rows(src_info, B->d_src.p, E, 4, B->pm_info.p, B->st);
+      if (per_intr) cs::ba_launch_gather_rows(src_intr, B->d_src.p, E, 4, B->pm_intr.p, B->st);
+      if (have_hub) cs::ba_launch_gather_rows(src_huber, B->d_src.p, E, 1, B->pm_huber.p, B->st);   // (else: zeros from the allocation)
       cs::ba_launch_gather_rows(B->pm_uv.p, B->cm_pm.p, E, 2, B->cm_uv.p, B->st);
       if (per_info) cs::ba_launch_gather_rows(B->pm_info.p, B->cm_pm.p, E, 4, B->cm_info.p, B->st);
       if (per_intr) cs::ba_launch_gather_rows(B->pm_intr.p, B->cm_pm.p, E, 4, B->cm_intr.p, B->st);
@@ -1063,7 +1123,21 @@ int finalize_structure(cs_ba* B) {
   {   // kernel kinds of the projection edges in both orders -- only if some edge has a kernel other than Huber
     bool generic = false;
     for (int kd : B->rk_proj) if (kd != cs::RK_NONE && kd != cs::RK_HUBER) { generic = true; break; }
-    if (generic) {
+    for (int kd : B->rk_stereo) if (kd != cs::RK_NONE && kd != cs::RK_HUBER) { generic = true; break; }
+    if (generic && nS > 0) {
+      // (a class without a kind list has Huber wherever its delta is positive: with a kind array on the device every edge is looked up in it)
+      std::vector<double> hub_m;
+      if (B->rk_proj.empty() && B->have_huber && nM > 0) { hub_m.resize((size_t)nM); CS_HIP_TRY(hipMemcpy(hub_m.data(), B->raw_huber.p, 8 * (size_t)nM, hipMemcpyDeviceToHost)); }
+      auto kind_of = [&](int src) -> int {
+        if (src < nM) return !B->rk_proj.empty() ? B->rk_proj[src] : (!hub_m.empty() && hub_m[src] > 0 ? cs::RK_HUBER : cs::RK_NONE);
+        const int s2 = src - nM;
+        return !B->rk_stereo.empty() ? B->rk_stereo[s2] : (!B->h_se_huber.empty() && B->h_se_huber[s2] > 0 ? cs::RK_HUBER : cs::RK_NONE);
+      };
+      std::vector<int> pk(std::max(1, E), 0), ck(std::max(1, E), 0);
+      for (int sl = 0; sl < E; sl++) pk[sl] = kind_of(src_of_slot[sl]);
+      for (int q = 0; q < E; q++) ck[q] = pk[cm_pm[q]];
+      UP(B->d_pm_rk, pk); UP(B->d_cm_rk, ck);
+    } else if (generic) {
       std::vector<int> pk(std::max(1, E), 0), ck(std::max(1, E), 0);
       for (int sl = 0; sl < E; sl++) pk[sl] = B->rk_proj[src_of_slot[sl]];
       for (int q = 0; q < E; q++) ck[q] = pk[cm_pm[q]];
@@ -1416,7 +1490,11 @@ int finalize_structure(cs_ba* B) {
     }
   }
   AL(B->cams_bak, 7 * (size_t)nc); AL(B->points_bak, 3 * (size_t)np); AL(B->cubes_bak, 10 * (size_t)no);
-  { std::vector<double> u8(B->uni8, B->uni8 + 8); UP(B->d_uni, u8); }
+  {
+    std::vector<double> u8(B->uni8, B->uni8 + 8);
+    if (nS > 0) u8.insert(u8.end(), B->h_se_sinfo.begin(), B->h_se_sinfo.begin() + 10);      // (a stereo graph: the stereo edges' reference record behind the mono one)
+    UP(B->d_uni, u8);
+  }
 #undef UP
 #undef AL
 #undef UPB
@@ -1446,6 +1524,13 @@ int finalize_structure(cs_ba* B) {
   {
     v.info_u = B->info_uniform && E > 0 ? B->d_uni.p : nullptr;
     v.intr_u = B->intr_uniform && E > 0 ? B->d_uni.p + 4 : nullptr;
+    v.pm_kind = v.cm_kind = nullptr; v.pm_ur = v.cm_ur = v.pm_sinfo = v.cm_sinfo = v.sinfo_u = nullptr;
+    if (nS > 0) {
+      v.info_u = (B->info_uniform || nM == 0) ? B->d_uni.p : nullptr;
+      v.intr_u = B->intr_uniform_all ? B->d_uni.p + 4 : nullptr;
+      v.pm_kind = B->d_pm_kind.p; v.cm_kind = B->d_cm_kind.p; v.pm_ur = B->d_pm_ur.p; v.cm_ur = B->d_cm_ur.p;
+      if (B->sinfo_uniform) v.sinfo_u = B->d_uni.p + 8; else { v.pm_sinfo = B->d_pm_sinfo.p; v.cm_sinfo = B->d_cm_sinfo.p; }
+    }
   }
   v.Dinv = B->Dinv.p; v.dbl = B->dbl.p; v.S = B->S.p; v.band_ld = B->band_ld; v.lam_lo = B->sep_mode ? B->cut[B->shard_rank] : 0; v.lam_hi = B->sep_mode ? B->cut[B->shard_rank + 1] : (B->shard_rank == 0 ? 0x7fffffff : 0); v.rhs = B->S.p + B->s_doubles; v.xl = B->xl.p;
   v.n_pairs = B->n_pairs; v.pair_ptr = B->pair_ptr.p; v.pair_i1 = B->pair_i1.p; v.pair_i2 = B->pair_i2.p; v.ent_a = B->ent_a.p; v.ent_b = B->ent_b.p;
@@ -1868,7 +1953,7 @@ void cs_ba_destroy(cs_ba* B) {
   DBuf<double>* dd[] = {&B->cams, &B->points, &B->cubes, &B->cams_bak, &B->points_bak, &B->cubes_bak, &B->pm_uv, &B->pm_info, &B->pm_intr, &B->pm_huber,
                         &B->cm_uv, &B->cm_info, &B->cm_intr, &B->cm_huber, &B->ce_meas, &B->ce_info, &B->ce_Hcc, &B->ce_Hoo, &B->ce_Hco, &B->ce_bc, &B->ce_bo,
                         &B->oe_meas, &B->oe_info, &B->oe_Hii, &B->oe_Hjj, &B->oe_Hij, &B->oe_bi, &B->oe_bj, &B->Hcam, &B->bcam, &B->Hcub, &B->bcub, &B->Hll, &B->bl,
-                        &B->W, &B->WD, &B->Dinv, &B->dbl, &B->S, &B->rhs, &B->xl, &B->chi_partial, &B->band_linv, &B->scale_partial, &B->pe_meas, &B->pe_info, &B->pe_K, &B->part_tiles, &B->part_coef, &B->cub_M, &B->cub_Dinv, &B->raw_uv, &B->raw_info, &B->raw_intr, &B->raw_huber, &B->sepY, &B->sep_msgs, &B->sepS, &B->int_work, &B->sep_work, &B->d_ce_rdelta, &B->d_oe_rdelta, &B->ext_cam36, &B->ext_cam6, &B->ext_cub81, &B->ext_cub9, &B->ext_pt9, &B->ext_pt3, &B->ext_Hij, &B->sp_L, &B->sp_xs, &B->sp_T};
+                        &B->W, &B->WD, &B->Dinv, &B->dbl, &B->S, &B->rhs, &B->xl, &B->chi_partial, &B->band_linv, &B->scale_partial, &B->pe_meas, &B->pe_info, &B->pe_K, &B->part_tiles, &B->part_coef, &B->cub_M, &B->cub_Dinv, &B->raw_uv, &B->raw_info, &B->raw_intr, &B->raw_huber, &B->sepY, &B->sep_msgs, &B->sepS, &B->int_work, &B->sep_work, &B->d_ce_rdelta, &B->d_oe_rdelta, &B->ext_cam36, &B->ext_cam6, &B->ext_cub81, &B->ext_cub9, &B->ext_pt9, &B->ext_pt3, &B->ext_Hij, &B->sp_L, &B->sp_xs, &B->sp_T, &B->comb_uv, &B->comb_info, &B->comb_intr, &B->comb_huber, &B->d_pm_ur, &B->d_cm_ur, &B->d_pm_sinfo, &B->d_cm_sinfo};
   for (auto* d : dd) d->release();
   B->stage.release(); B->append_stage.release();
   DBuf<int>* di[] = {&B->d_ce_active, &B->d_oe_active, &B->d_cam_col, &B->d_cub_col, &B->d_pt_free, &B->pm_pt, &B->pm_cam, &B->pt_ptr, &B->cm_pm, &B->cm_pt, &B->cam_ptr, &B->d_ce_cam, &B->d_ce_cub,
@@ -1876,7 +1961,7 @@ void cs_ba_destroy(cs_ba* B) {
                      &B->cub_ce_idx, &B->pair_ptr, &B->pair_i1, &B->pair_i2, &B->ent_a, &B->ent_b, &B->d_run_lm, &B->d_seg_ptr, &B->d_seg_k, &B->d_seg_tile, &B->d_seg_slot, &B->d_run_e0, &B->d_seg_cam,
                      &B->d_gp_ptr, &B->d_gp_i1, &B->d_gp_i2, &B->d_gtile, &B->d_gcam_ptr, &B->d_gslot, &B->d_cubS_ptr, &B->d_cubS_cam, &B->d_ce_slot, &B->d_cub_tile, &B->d_cub_coef,
                      &B->d_elim_fail, &B->d_slotE_ptr, &B->d_slotE_idx, &B->d_cub_mine, &B->d_sep_off, &B->d_sep_col, &B->d_int_info, &B->d_sep_info, &B->d_pm_rk, &B->d_cm_rk, &B->d_ce_rk, &B->d_oe_rk, &B->d_ext_e4, &B->d_ext_order, &B->d_ext_gptr, &B->d_src, &B->sp_ndim, &B->sp_ncol, &B->sp_sptr, &B->sp_srow, &B->sp_sroff, &B->sp_prow, &B->sp_rbase, &B->sp_rent, &B->sp_rptr, &B->sp_rcol, &B->sp_rpos,
-                     &B->sp_order, &B->sp_info, &B->sp_tcol};
+                     &B->sp_order, &B->sp_info, &B->sp_tcol, &B->d_pm_kind, &B->d_cm_kind};
   for (auto* d : di) d->release();
   B->sp_poff.release(); B->sp_done.release(); B->sp_xdone.release();
   B->d_info.release(); B->d_band_info.release();
@@ -1987,20 +2072,21 @@ int cs_ba_append_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, cons
   if (!B || n < 0 || (n && (!pt || !cam || !uv || !info4 || !intr4))) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
   if (n == 0) return CS_OK;
-  if (B->n_proj > 0 && (huber != nullptr) != B->have_huber) { cs_set_error("cs_ba_append_edges_proj: Huber deltas must be given for all projection edges or for none"); return CS_ERR_INVALID_ARG; }
+  const int n_mono = B->n_proj - B->n_stereo;      // (the stereo edges keep their place behind the mono ones)
+  if (n_mono > 0 && (huber != nullptr) != B->have_huber) { cs_set_error("cs_ba_append_edges_proj: Huber deltas must be given for all projection edges or for none"); return CS_ERR_INVALID_ARG; }
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   int rc;
-  const bool first_edges = B->n_proj == 0;
+  const bool first_edges = n_mono == 0;
   scan_uniform_records(B, first_edges, info4, intr4, n);
   if (first_edges) { B->raw_info_virtual = B->info_uniform; B->raw_intr_virtual = B->intr_uniform; B->raw_info.n = 0; B->raw_intr.n = 0; }
   // an appended edge with another record: the records of the edges so far are written out from the reference record, then kept per edge
   auto write_out = [&](DBuf<double>& raw, const double* rec4, bool& is_virtual) -> int {
-    int r = raw.reserve(4 * (size_t)(B->n_proj + n));
+    int r = raw.reserve(4 * (size_t)(n_mono + n));
     if (r) return r;
-    cs::ba_launch_fill_rows4(raw.p, rec4, B->n_proj, B->st);
+    cs::ba_launch_fill_rows4(raw.p, rec4, n_mono, B->st);
     CS_HIP_TRY(hipGetLastError());
-    raw.n = 4 * (size_t)B->n_proj;
+    raw.n = 4 * (size_t)n_mono;
     is_virtual = false;
     return CS_OK;
   };
@@ -2012,7 +2098,8 @@ int cs_ba_append_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, cons
   if (!B->raw_intr_virtual && (rc = B->raw_intr.append_ptr_staged(intr4, 4 * (size_t)n, B->append_stage, B->st))) return rc;
   if (huber) { rc = B->raw_huber.append_ptr_staged(huber, (size_t)n, B->append_stage, B->st); if (rc) return rc; }
   B->have_huber = huber != nullptr;
-  B->e_pt.insert(B->e_pt.end(), pt, pt + n); B->e_cam.insert(B->e_cam.end(), cam, cam + n);
+  B->e_pt.insert(B->e_pt.end() - B->n_stereo, pt, pt + n); B->e_cam.insert(B->e_cam.end() - B->n_stereo, cam, cam + n);
+  if (B->n_stereo > 0) proj_edge_lists_invalidate(B);      // (the stereo edges' indices moved)
   if (!B->rk_proj.empty()) for (int k = 0; k < n; k++) B->rk_proj.push_back((huber && huber[k] > 0) ? cs::RK_HUBER : cs::RK_NONE);
   B->n_proj += n;
   B->structure_dirty = true;
@@ -2077,9 +2164,13 @@ int cs_ba_set_estimates(cs_ba* B, const double* cams7, const double* cuboids10, 
 
 static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
   if (!B || n < 0 || (n && (!pt || !cam || !uv || !info4 || !intr4))) return CS_ERR_INVALID_ARG;
-  B->n_proj = n;
+  {   // the mono edges are replaced; the stereo edges behind them stay
+    const std::vector<int> sp(B->e_pt.end() - B->n_stereo, B->e_pt.end()), sc(B->e_cam.end() - B->n_stereo, B->e_cam.end());
+    B->e_pt.assign(pt, pt + n); B->e_cam.assign(cam, cam + n);
+    B->e_pt.insert(B->e_pt.end(), sp.begin(), sp.end()); B->e_cam.insert(B->e_cam.end(), sc.begin(), sc.end());
+  }
+  B->n_proj = n + B->n_stereo;
   proj_edge_lists_invalidate(B);
-  B->e_pt.assign(pt, pt + n); B->e_cam.assign(cam, cam + n);
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
   int rc;
@@ -2098,6 +2189,42 @@ int cs_ba_set_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, const d
   CS_GUARD_BEGIN
   return cs_ba_set_edges_proj_impl(B, n, pt, cam, uv, info4, intr4, huber);
   CS_GUARD_END("cs_ba_set_edges_proj")
+}
+
+// EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.h:178-206): uvr3 = (u_left, v, u_right), info9 row-major, intr5 = fx fy cx cy bf, huber as
+// cs_ba_set_edges_proj's.  The edges follow the mono projection edges in g2o's edge order and join the same device lists.
+static int stereo_edges_add(cs_ba* B, bool replace, int n, const int* pt, const int* cam, const double* uvr3, const double* info9, const double* intr5, const double* huber) {
+  if (!B || n < 0 || (n && (!pt || !cam || !uvr3 || !info9 || !intr5))) return CS_ERR_INVALID_ARG;
+  if (n > 0 && B->shard_n > 1) { cs_set_error("stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
+  if (!replace && n == 0) return CS_OK;
+  if (!replace && B->n_stereo > 0 && (huber != nullptr) != !B->h_se_huber.empty()) { cs_set_error("cs_ba_append_edges_proj_stereo: Huber deltas must be given for all stereo edges or for none"); return CS_ERR_INVALID_ARG; }
+  if (replace) {
+    B->e_pt.resize(B->e_pt.size() - B->n_stereo); B->e_cam.resize(B->e_cam.size() - B->n_stereo);
+    B->n_proj -= B->n_stereo; B->n_stereo = 0;
+    B->h_se_uv.clear(); B->h_se_ur.clear(); B->h_se_intr.clear(); B->h_se_sinfo.clear(); B->h_se_huber.clear(); B->rk_stereo.clear();
+    proj_edge_lists_invalidate(B);
+  }
+  B->e_pt.insert(B->e_pt.end(), pt, pt + n); B->e_cam.insert(B->e_cam.end(), cam, cam + n);
+  for (int k = 0; k < n; k++) {
+    B->h_se_uv.push_back(uvr3[3 * (size_t)k]); B->h_se_uv.push_back(uvr3[3 * (size_t)k + 1]); B->h_se_ur.push_back(uvr3[3 * (size_t)k + 2]);
+    B->h_se_intr.insert(B->h_se_intr.end(), intr5 + 5 * (size_t)k, intr5 + 5 * (size_t)k + 4);
+    B->h_se_sinfo.insert(B->h_se_sinfo.end(), info9 + 9 * (size_t)k, info9 + 9 * (size_t)k + 9); B->h_se_sinfo.push_back(intr5[5 * (size_t)k + 4]);
+    if (huber) B->h_se_huber.push_back(huber[k]);
+    if (!B->rk_stereo.empty()) B->rk_stereo.push_back((huber && huber[k] > 0) ? cs::RK_HUBER : cs::RK_NONE);
+  }
+  B->n_stereo += n; B->n_proj += n;
+  B->structure_dirty = true;
+  return CS_OK;
+}
+int cs_ba_set_edges_proj_stereo(cs_ba* B, int n, const int* pt, const int* cam, const double* uvr3, const double* info9, const double* intr5, const double* huber) {
+  CS_GUARD_BEGIN
+  return stereo_edges_add(B, true, n, pt, cam, uvr3, info9, intr5, huber);
+  CS_GUARD_END("cs_ba_set_edges_proj_stereo")
+}
+int cs_ba_append_edges_proj_stereo(cs_ba* B, int n, const int* pt, const int* cam, const double* uvr3, const double* info9, const double* intr5, const double* huber) {
+  CS_GUARD_BEGIN
+  return stereo_edges_add(B, false, n, pt, cam, uvr3, info9, intr5, huber);
+  CS_GUARD_END("cs_ba_append_edges_proj_stereo")
 }
 
 static int cs_ba_set_edges_cuboid_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
@@ -2203,7 +2330,7 @@ int cs_ba_set_external_callback(cs_ba* B, cs_external_fn fn, void* ctx) {
 // core/robust_kernel_impl.cpp:78-165).  Replaces the class's kernels; n = the class's edge count.
 static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const int* kind, const double* delta) {
   if (!B || n < 0 || (n && kind && !delta)) return CS_ERR_INVALID_ARG;
-  const int have = edge_class == CS_EDGE_PROJ ? B->n_proj : edge_class == CS_EDGE_CUBOID ? (int)B->u3_cam.size() : edge_class == CS_EDGE_CUBOID_PROJ ? (int)B->up_cam.size()
+  const int have = edge_class == CS_EDGE_PROJ ? B->n_proj - B->n_stereo : edge_class == CS_EDGE_PROJ_STEREO ? B->n_stereo : edge_class == CS_EDGE_CUBOID ? (int)B->u3_cam.size() : edge_class == CS_EDGE_CUBOID_PROJ ? (int)B->up_cam.size()
                  : edge_class == CS_EDGE_ODOM ? B->n_odom : -1;
   if (have < 0) { cs_set_error("cs_ba_set_robust_kernels: unknown edge class"); return CS_ERR_INVALID_ARG; }
   if (!kind) n = have;         // removing the class's kernels: the count is the library's own (n is ignored)
@@ -2220,7 +2347,8 @@ static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const 
     int rc = B->raw_huber.upload_ptr(dd.data(), (size_t)n); if (rc) return rc;    // delta per edge, 0 = none
     B->have_huber = true;
     B->rk_proj = kk;
-  } else if (edge_class == CS_EDGE_CUBOID) { B->rk_cub3 = kk; B->rd_cub3 = dd; }
+  } else if (edge_class == CS_EDGE_PROJ_STEREO) { B->h_se_huber = dd; B->rk_stereo = kk; }
+  else if (edge_class == CS_EDGE_CUBOID) { B->rk_cub3 = kk; B->rd_cub3 = dd; }
   else if (edge_class == CS_EDGE_CUBOID_PROJ) { B->rk_cproj = kk; B->rd_cproj = dd; }
   else { B->rk_odom = kk; B->rd_odom = dd; }
   B->structure_dirty = true;
@@ -2321,6 +2449,7 @@ int cs_ba_pop(cs_ba* B) {
 // optimization_algorithm_levenberg.cpp:61-163 + sparse_optimizer.cpp:354-419
 int cs_ba_set_shard(cs_ba* B, int rank, int n_ranks) {
   if (!B || n_ranks < 1 || rank < 0 || rank >= n_ranks) return CS_ERR_INVALID_ARG;
+  if (B->n_stereo > 0 && n_ranks > 1) { cs_set_error("cs_ba_set_shard: stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
   B->shard_rank = rank; B->shard_n = n_ranks;
   B->structure_dirty = true;
   return CS_OK;
@@ -3060,7 +3189,7 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   if (!B || !path) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
-  const int np_e = B->n_proj, n3 = (int)B->u3_cam.size(), n4 = (int)B->up_cam.size(), n6 = B->n_odom;
+  const int nst = B->n_stereo, np_e = B->n_proj - nst, n3 = (int)B->u3_cam.size(), n4 = (int)B->up_cam.size(), n6 = B->n_odom;
   std::vector<double> cams(7 * (size_t)B->nc), cubs(10 * (size_t)B->no), pts(3 * (size_t)B->np), uv(2 * (size_t)np_e), info(4 * (size_t)np_e), intr(4 * (size_t)np_e), hub(B->have_huber ? np_e : 0);
   auto d2h = [&](std::vector<double>& h, const double* d) -> int { if (!h.empty()) CS_HIP_TRY(hipMemcpy(h.data(), d, 8 * h.size(), hipMemcpyDeviceToHost)); return CS_OK; };
   int rc;
@@ -3072,14 +3201,17 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   if (!f) { cs_set_error(std::string("cs_ba_dump: cannot open ") + path); return CS_ERR_INVALID_ARG; }
   DumpHeader H{};
   std::memcpy(H.magic, "CSBA0002", 8);
-  const int counts[16] = {B->nc, B->no, B->np, B->cuboids_first, np_e, B->have_huber ? 1 : 0, (int)B->rk_proj.size(), n3, (int)B->rk_cub3.size(), n4, (int)B->rk_cproj.size(), n6, (int)B->rk_odom.size(), 0, 0, 0};
+  const int counts[16] = {B->nc, B->no, B->np, B->cuboids_first, np_e, B->have_huber ? 1 : 0, (int)B->rk_proj.size(), n3, (int)B->rk_cub3.size(), n4, (int)B->rk_cproj.size(), n6, (int)B->rk_odom.size(), nst, B->h_se_huber.empty() ? 0 : 1, (int)B->rk_stereo.size()};
   std::memcpy(H.v, counts, sizeof(counts));
   bool ok = fwrite(&H, sizeof(H), 1, f) == 1;
   ok = ok && wr(f, cams) && wr(f, B->cam_fixed) && wr(f, cubs) && wr(f, B->cub_fixed) && wr(f, pts) && wr(f, B->pt_fixed);
-  ok = ok && wr(f, B->e_pt) && wr(f, B->e_cam) && wr(f, uv) && wr(f, info) && wr(f, intr) && wr(f, hub) && wr(f, B->rk_proj);
+  const std::vector<int> m_pt(B->e_pt.begin(), B->e_pt.begin() + np_e), m_cam(B->e_cam.begin(), B->e_cam.begin() + np_e), s_pt(B->e_pt.begin() + np_e, B->e_pt.end()), s_cam(B->e_cam.begin() + np_e, B->e_cam.end());
+  ok = ok && wr(f, m_pt) && wr(f, m_cam) && wr(f, uv) && wr(f, info) && wr(f, intr) && wr(f, hub) && wr(f, B->rk_proj);
   ok = ok && wr(f, B->u3_cam) && wr(f, B->u3_cub) && wr(f, B->h_ce_meas) && wr(f, B->h_ce_info) && wr(f, B->rk_cub3) && wr(f, B->rd_cub3);
   ok = ok && wr(f, B->up_cam) && wr(f, B->up_cub) && wr(f, B->h_pe_meas) && wr(f, B->h_pe_info) && wr(f, B->h_pe_K) && wr(f, B->rk_cproj) && wr(f, B->rd_cproj);
   ok = ok && wr(f, B->oe_i) && wr(f, B->oe_j) && wr(f, B->h_oe_meas) && wr(f, B->h_oe_info) && wr(f, B->rk_odom) && wr(f, B->rd_odom);
+  // (the stereo projection edges last: a graph without one dumps the bytes it always did)
+  ok = ok && wr(f, s_pt) && wr(f, s_cam) && wr(f, B->h_se_uv) && wr(f, B->h_se_ur) && wr(f, B->h_se_intr) && wr(f, B->h_se_sinfo) && wr(f, B->h_se_huber) && wr(f, B->rk_stereo);
   ok = (fclose(f) == 0) && ok;
   if (!ok) { cs_set_error(std::string("cs_ba_dump: write to ") + path + " failed"); return CS_ERR_INVALID_ARG; }
   return CS_OK;
@@ -3097,8 +3229,8 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   struct Close { FILE* f; ~Close() { fclose(f); } } cl{f};
   DumpHeader H;
   if (fread(&H, sizeof(H), 1, f) != 1 || std::memcmp(H.magic, "CSBA0002", 8) != 0) { cs_set_error("cs_ba_load: not a cs_ba dump (magic CSBA0002)"); return CS_ERR_INVALID_ARG; }
-  for (int i = 0; i < 13; i++) if (H.v[i] < 0) { cs_set_error("cs_ba_load: corrupt header"); return CS_ERR_INVALID_ARG; }
-  const int nc = H.v[0], no = H.v[1], np = H.v[2], cf = H.v[3], npe = H.v[4], hh = H.v[5], nrk = H.v[6], n3 = H.v[7], nrk3 = H.v[8], n4 = H.v[9], nrk4 = H.v[10], n6 = H.v[11], nrk6 = H.v[12];
+  for (int i = 0; i < 16; i++) if (H.v[i] < 0) { cs_set_error("cs_ba_load: corrupt header"); return CS_ERR_INVALID_ARG; }
+  const int nc = H.v[0], no = H.v[1], np = H.v[2], cf = H.v[3], npe = H.v[4], hh = H.v[5], nrk = H.v[6], n3 = H.v[7], nrk3 = H.v[8], n4 = H.v[9], nrk4 = H.v[10], n6 = H.v[11], nrk6 = H.v[12], nst = H.v[13], sth = H.v[14], nrks = H.v[15];
   std::vector<double> cams, cubs, pts, uv, info, intr, hub, m10, i81, rd3, m4, i16, k9, rd4, m7, i36, rd6;
   std::vector<int> camf, cubf, ptf, ept, ecam, rkp, c3, o3, rk3, c4, o4, rk4, oi, oj, rk6;
   bool ok = rd(f, cams, 7 * (size_t)nc) && rd(f, camf, nc) && rd(f, cubs, 10 * (size_t)no) && rd(f, cubf, no) && rd(f, pts, 3 * (size_t)np) && rd(f, ptf, np);
@@ -3106,7 +3238,9 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   ok = ok && rd(f, c3, n3) && rd(f, o3, n3) && rd(f, m10, 10 * (size_t)n3) && rd(f, i81, 81 * (size_t)n3) && rd(f, rk3, nrk3) && rd(f, rd3, nrk3);
   ok = ok && rd(f, c4, n4) && rd(f, o4, n4) && rd(f, m4, 4 * (size_t)n4) && rd(f, i16, 16 * (size_t)n4) && rd(f, k9, 9 * (size_t)n4) && rd(f, rk4, nrk4) && rd(f, rd4, nrk4);
   ok = ok && rd(f, oi, n6) && rd(f, oj, n6) && rd(f, m7, 7 * (size_t)n6) && rd(f, i36, 36 * (size_t)n6) && rd(f, rk6, nrk6) && rd(f, rd6, nrk6);
-  if (!ok || (nrk && nrk != npe) || (nrk3 && nrk3 != n3) || (nrk4 && nrk4 != n4) || (nrk6 && nrk6 != n6)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
+  std::vector<int> spt, scam, rks; std::vector<double> suv, sur, sintr, ssinfo, shub;
+  ok = ok && rd(f, spt, nst) && rd(f, scam, nst) && rd(f, suv, 2 * (size_t)nst) && rd(f, sur, nst) && rd(f, sintr, 4 * (size_t)nst) && rd(f, ssinfo, 10 * (size_t)nst) && rd(f, shub, sth ? nst : 0) && rd(f, rks, nrks);
+  if (!ok || (nrks && nrks != nst) || (nrk && nrk != npe) || (nrk3 && nrk3 != n3) || (nrk4 && nrk4 != n4) || (nrk6 && nrk6 != n6)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
   cs_ba* B = nullptr;
   int rc = cs_ba_create(device, &B); if (rc) return rc;
   struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{B};
@@ -3115,6 +3249,15 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   if (nc) CS_HIP_TRY(hipMemcpy(B->cams.p, cams.data(), 56 * (size_t)nc, hipMemcpyHostToDevice));
   if (npe && (rc = cs_ba_set_edges_proj(B, npe, ept.data(), ecam.data(), uv.data(), info.data(), intr.data(), hh ? hub.data() : nullptr))) return rc;
   if (nrk && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_PROJ, npe, rkp.data(), hub.data()))) return rc;
+  if (nst) {
+    std::vector<double> uvr(3 * (size_t)nst), i9(9 * (size_t)nst), k5(5 * (size_t)nst);
+    for (int k = 0; k < nst; k++) {
+      uvr[3 * (size_t)k] = suv[2 * (size_t)k]; uvr[3 * (size_t)k + 1] = suv[2 * (size_t)k + 1]; uvr[3 * (size_t)k + 2] = sur[k];
+      std::memcpy(&i9[9 * (size_t)k], &ssinfo[10 * (size_t)k], 72); std::memcpy(&k5[5 * (size_t)k], &sintr[4 * (size_t)k], 32); k5[5 * (size_t)k + 4] = ssinfo[10 * (size_t)k + 9];
+    }
+    if ((rc = cs_ba_set_edges_proj_stereo(B, nst, spt.data(), scam.data(), uvr.data(), i9.data(), k5.data(), sth ? shub.data() : nullptr))) return rc;
+    if (nrks && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_PROJ_STEREO, nst, rks.data(), shub.data()))) return rc;
+  }
   if (n3 && (rc = cs_ba_set_edges_cuboid(B, n3, c3.data(), o3.data(), m10.data(), i81.data()))) return rc;
   if (nrk3 && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_CUBOID, n3, rk3.data(), rd3.data()))) return rc;
   if (n4 && (rc = cs_ba_set_edges_cuboid_proj(B, n4, c4.data(), o4.data(), m4.data(), i16.data(), k9.data()))) return rc;

@@ -75,12 +75,136 @@ __device__ __forceinline__ void proj_linearize(const Pose& T, const double* R, c
   L.r[1] = -(info[2] * L.e[0] + info[3] * L.e[1]) * rho1;
 }
 
+// ---- stereo projection edges (EdgeStereoSE3ProjectXYZ) ----------------------------------------------------------------------------
+// Every kernel that evaluates a projection edge has a STEREO instantiation, launched for graphs that hold a stereo edge (v.pm_kind != nullptr);
+// a graph without one runs the STEREO = false code, which is the mono code above and nothing else.  Inside a stereo instantiation a lane
+// branches on its edge's kind while it linearises; both kinds then share one set of 3-row products -- a mono edge fills rows 0 and 1 and
+// leaves row 2 (error, Jacobians, information) zero, which adds exact zeros to the sums the mono code forms.
+struct ProjLin3 {
+  double e[3];     // error (u_left, v, u_right)
+  double Jp[9];    // 3x3  d e / d point
+  double Jc[18];   // 3x6  d e / d camera
+  double Wm[9];    // rho' * Omega
+  double r[3];     // -rho' * Omega e
+  double chi;      // rho0
+};
+// a stereo edge's record beyond the mono one: 3 x 3 information + bf, the graph's one record or the edge's own
+__device__ __forceinline__ const double* stereo_rec(const double* sinfo_u, const double* sinfo, size_t k) { return sinfo_u ? sinfo_u : sinfo + 10 * k; }
+__device__ __forceinline__ double quad3(const double* e, const double* info) {
+  return e[0] * ((info[0] * e[0] + info[1] * e[1]) + info[2] * e[2]) + e[1] * ((info[3] * e[0] + info[4] * e[1]) + info[5] * e[2]) + e[2] * ((info[6] * e[0] + info[7] * e[1]) + info[8] * e[2]);
+}
+// Either kind of edge of a stereo graph in the 3-row form, from the fields both kinds have (uv, info: the mono edge's 2 x 2; intr: fx fy cx cy)
+// and the stereo ones (u_right; srec = 3 x 3 information, bf).  What the two kinds share is formed once, in front of the per-lane branch: the
+// camera-frame point and rows 0 and 1 of the camera Jacobian, which both linearizeOplus write alike (types_six_dof_expmap.cpp:171-183, :259-271).
+// Stereo: the error with its single-precision invz / bf (cs_se3.h), the point Jacobian in ITS form (:247-257: -fx R(0,j) / z + fx x R(2,j) / z^2,
+// not the mono edge's -1/z * tmp * R), row 2 of both Jacobians (:255-257, :273-278), all double.  Mono: proj_linearize's arithmetic, row 2 zero.
+// Then the weights of constructQuadraticForm (base_binary_edge.hpp:54-120).
+__device__ __forceinline__ void proj_linearize_any(bool stereo, const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k,
+                                                   double ur, const double* srec, ProjLin3& L) {
+  double pc[3];
+  pose_map(T, X, pc);
+  const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z, fx = intr[0], fy = intr[1];
+  L.Jc[0] = x * y / z_2 * fx; L.Jc[1] = -(1 + (x * x / z_2)) * fx; L.Jc[2] = y / z * fx; L.Jc[3] = -1. / z * fx; L.Jc[4] = 0; L.Jc[5] = x / z_2 * fx;
+  L.Jc[6] = (1 + y * y / z_2) * fy; L.Jc[7] = -x * y / z_2 * fy; L.Jc[8] = -x / z * fy; L.Jc[9] = 0; L.Jc[10] = -1. / z * fy; L.Jc[11] = y / z_2 * fy;
+  double e0, e1, e2, c, W[9], jp[9], jc2[6];
+  if (stereo) {
+    const double bf = srec[9];
+    double e[3];
+    stereo_cam_project_error(pc, uv, ur, intr, bf, e);
+    e0 = e[0]; e1 = e[1]; e2 = e[2];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      jp[j] = -fx * R[j] / z + fx * x * R[6 + j] / z_2;
+      jp[3 + j] = -fy * R[3 + j] / z + fy * y * R[6 + j] / z_2;
+      jp[6 + j] = jp[j] - bf * R[6 + j] / z_2;
+    }
+    jc2[0] = L.Jc[0] - bf * y / z_2; jc2[1] = L.Jc[1] + bf * x / z_2; jc2[2] = L.Jc[2]; jc2[3] = L.Jc[3]; jc2[4] = 0; jc2[5] = L.Jc[5] - bf / z_2;
+#pragma unroll
+    for (int i = 0; i < 9; i++) W[i] = srec[i];
+  } else {
+    e0 = uv[0] - (x / z * fx + intr[2]);
+    e1 = uv[1] - (y / z * fy + intr[3]);
+    e2 = 0;
+    const double tmp[6] = {fx, 0, -x / z * fx, 0, fy, -y / z * fy};
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        double s = 0;
+#pragma unroll
+        for (int q = 0; q < 3; q++) s += (-1. / z * tmp[3 * i + q]) * R[3 * q + j];
+        jp[3 * i + j] = s;
+      }
+    jp[6] = 0; jp[7] = 0; jp[8] = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) jc2[i] = 0;
+    W[0] = info[0]; W[1] = info[1]; W[2] = 0; W[3] = info[2]; W[4] = info[3]; W[5] = 0; W[6] = 0; W[7] = 0; W[8] = 0;
+  }
+  L.e[0] = e0; L.e[1] = e1; L.e[2] = e2;
+#pragma unroll
+  for (int i = 0; i < 9; i++) L.Jp[i] = jp[i];
+#pragma unroll
+  for (int i = 0; i < 6; i++) L.Jc[12 + i] = jc2[i];
+  // (a mono edge: the zeros of row / column 2 add nothing -- e^T Omega e, rho' Omega and -rho' Omega e are the 2 x 2 ones)
+  c = quad3(L.e, W);
+  double rho1;
+  proj_rho(rk, k, huber, c, L.chi, rho1);
+#pragma unroll
+  for (int i = 0; i < 9; i++) L.Wm[i] = rho1 * W[i];
+#pragma unroll
+  for (int i = 0; i < 3; i++) L.r[i] = -((W[3 * i] * L.e[0] + W[3 * i + 1] * L.e[1]) + W[3 * i + 2] * L.e[2]) * rho1;
+}
+// the products of constructQuadraticForm on the 3-row form, written as the mono sites write theirs (row sums left to right)
+__device__ __forceinline__ void lin3_cam_terms(const ProjLin3& L, double* A21, double* b6) {   // A_ii (upper triangle) += J_c^T W J_c, b_i += J_c^T r
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const double jw0 = (L.Jc[i] * L.Wm[0] + L.Jc[6 + i] * L.Wm[3]) + L.Jc[12 + i] * L.Wm[6];
+    const double jw1 = (L.Jc[i] * L.Wm[1] + L.Jc[6 + i] * L.Wm[4]) + L.Jc[12 + i] * L.Wm[7];
+    const double jw2 = (L.Jc[i] * L.Wm[2] + L.Jc[6 + i] * L.Wm[5]) + L.Jc[12 + i] * L.Wm[8];
+#pragma unroll
+    for (int j = i; j < 6; j++) A21[q++] += (jw0 * L.Jc[j] + jw1 * L.Jc[6 + j]) + jw2 * L.Jc[12 + j];
+    b6[i] += (L.Jc[i] * L.r[0] + L.Jc[6 + i] * L.r[1]) + L.Jc[12 + i] * L.r[2];
+  }
+}
+__device__ __forceinline__ void lin3_point_terms(const ProjLin3& L, double* H6, double* b3) {   // J_p^T W J_p (upper triangle), J_p^T r
+  double pw[9];  // Jp^T W (3x3)
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int d = 0; d < 3; d++) pw[3 * i + d] = (L.Jp[i] * L.Wm[d] + L.Jp[3 + i] * L.Wm[3 + d]) + L.Jp[6 + i] * L.Wm[6 + d];
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+#pragma unroll
+    for (int j = i; j < 3; j++) H6[q++] = (pw[3 * i] * L.Jp[j] + pw[3 * i + 1] * L.Jp[3 + j]) + pw[3 * i + 2] * L.Jp[6 + j];
+    b3[i] = (L.Jp[i] * L.r[0] + L.Jp[3 + i] * L.r[1]) + L.Jp[6 + i] * L.r[2];
+  }
+}
+__device__ __forceinline__ double lin3_hpl(const ProjLin3& L, int i, int j) {   // (J_c^T W J_p)(i, j)
+  const double jw0 = (L.Jc[i] * L.Wm[0] + L.Jc[6 + i] * L.Wm[3]) + L.Jc[12 + i] * L.Wm[6];
+  const double jw1 = (L.Jc[i] * L.Wm[1] + L.Jc[6 + i] * L.Wm[4]) + L.Jc[12 + i] * L.Wm[7];
+  const double jw2 = (L.Jc[i] * L.Wm[2] + L.Jc[6 + i] * L.Wm[5]) + L.Jc[12 + i] * L.Wm[8];
+  return (jw0 * L.Jp[j] + jw1 * L.Jp[3 + j]) + jw2 * L.Jp[6 + j];
+}
+
 // ---------------------------------------------------------------------------------------------------
 // (device bodies with the block index / block count as arguments: ba_chi2_kernel below runs both kinds of block in ONE launch)
+template <bool STEREO>
 __device__ __forceinline__ void chi2_proj_block(const BaView& v, int bid, int nblocks, double* ws) {
   double acc = 0;
   for (int k = bid * 256 + threadIdx.x; k < v.n_proj; k += nblocks * 256) {
     Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
+    if constexpr (STEREO) {
+      if (v.pm_kind[k]) {
+        double e3[3], pc3[3], rho0, rho1;
+        const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
+        stereo_proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.pm_ur[k], v.intr_u ? v.intr_u : v.pm_intr + 4 * k, srec[9], e3, pc3);
+        proj_rho(v.pm_rk, k, v.pm_huber[k], quad3(e3, srec), rho0, rho1);
+        acc += rho0;
+        continue;
+      }
+    }
     double e[2], pc[3];
     proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, e, pc);
     const double* info = v.info_u ? v.info_u : v.pm_info + 4 * k;
@@ -137,6 +261,7 @@ __device__ __forceinline__ void chi2_pose_edges_wave(const BaView& v, int partia
 // chi2 of every active edge in one launch: the blocks of the cuboid / odometry edges FIRST (a wave per 64 edges: few, long -- four SE3 logs
 // per cuboid edge), the projection edges' blocks behind them.  The partial sums keep their places: [0, nb_proj) projection blocks, then one
 // per 64 pose edges -- the same values in the same slots as the two launches this replaces (round 6: one dispatch less on every trial's chain).
+template <bool STEREO>
 __global__ __launch_bounds__(256) void ba_chi2_kernel(BaView v, int nb_proj, int nb_pose) {
   __shared__ double ws[4];
   const int nb4 = (nb_pose + 3) / 4;
@@ -145,7 +270,7 @@ __global__ __launch_bounds__(256) void ba_chi2_kernel(BaView v, int nb_proj, int
     if (pb < nb_pose) chi2_pose_edges_wave(v, nb_proj, pb, threadIdx.x & 63);
     return;
   }
-  chi2_proj_block(v, blockIdx.x - nb4, nb_proj, ws);
+  chi2_proj_block<STEREO>(v, blockIdx.x - nb4, nb_proj, ws);
 }
 
 // x^T (lambda x + b) of the LM gain ratio (optimization_algorithm_levenberg.cpp:117-126, computeScale :182-189) over
@@ -184,6 +309,7 @@ __global__ __launch_bounds__(256) void ba_scale_kernel(BaView v, const double* _
 }
 
 // ---------------------------------------------------------------------------------------------------
+template <bool STEREO>
 __global__ __launch_bounds__(256) void ba_lin_cam_kernel(BaView v) {
   int c = blockIdx.x;
   if (v.cam_col[c] < 0) return;
@@ -198,6 +324,13 @@ __global__ __launch_bounds__(256) void ba_lin_cam_kernel(BaView v) {
   for (int i = 0; i < 6; i++) b[i] = 0;
   int e0 = v.cam_ptr[c], e1 = v.cam_ptr[c + 1];
   for (int k = e0 + threadIdx.x; k < e1; k += 256) {
+    if constexpr (STEREO) {
+      ProjLin3 L3;
+      proj_linearize_any(v.cm_kind[k] != 0, T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k,
+                         v.cm_ur[k], stereo_rec(v.sinfo_u, v.cm_sinfo, (size_t)k), L3);
+      lin3_cam_terms(L3, A, b);
+      continue;
+    }
     ProjLin L;
     proj_linearize(T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k, L);
     // JW = Jc^T W (6x2)
@@ -240,11 +373,25 @@ __global__ __launch_bounds__(256) void ba_lin_cam_kernel(BaView v) {
 // replaces.  Groups with more than LIN_PT_CAP edges (landmarks with very long tracks) walk their edges per landmark instead.
 enum { LIN_PT_GROUP = 48, LIN_PT_CAP = 512 };
 
+template <bool STEREO>
 __device__ __forceinline__ void lin_pt_edge(const BaView& v, int k, bool free_pt, double* H6, double* b3) {
   const int c = v.pm_cam[k];
   Pose T = pose_load(v.cams + 7 * c);
   double R[9];
   pose_rotmat(T, R);
+  if constexpr (STEREO) {
+    ProjLin3 L3;
+    proj_linearize_any(v.pm_kind[k] != 0, T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k,
+                       v.pm_ur[k], stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k), L3);
+    lin3_point_terms(L3, H6, b3);
+    double* Wk3 = v.W + 18 * (size_t)k;
+    const bool both3 = free_pt && v.cam_col[c] >= 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) Wk3[3 * i + j] = both3 ? lin3_hpl(L3, i, j) : 0.0;
+    return;
+  }
   ProjLin L;
   proj_linearize(T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k, L);
   double pw[6];  // Jp^T W (3x2)
@@ -271,6 +418,7 @@ __device__ __forceinline__ void lin_pt_edge(const BaView& v, int k, bool free_pt
   }
 }
 
+template <bool STEREO>
 __global__ __launch_bounds__(256) void ba_lin_pt_kernel(BaView v) {
   __shared__ double part[9][LIN_PT_CAP];     // [term][edge of the group]: consecutive lanes, consecutive words
   const int p0 = blockIdx.x * LIN_PT_GROUP, p1 = min(v.np, p0 + LIN_PT_GROUP);
@@ -280,7 +428,7 @@ __global__ __launch_bounds__(256) void ba_lin_pt_kernel(BaView v) {
   if (staged) {
     for (int k = e0 + threadIdx.x; k < e1; k += 256) {
       double H6[6], b3[3];
-      lin_pt_edge(v, k, v.pt_free[v.pm_pt[k]] != 0, H6, b3);
+      lin_pt_edge<STEREO>(v, k, v.pt_free[v.pm_pt[k]] != 0, H6, b3);
 #pragma unroll
       for (int i = 0; i < 6; i++) part[i][k - e0] = H6[i];
 #pragma unroll
@@ -299,7 +447,7 @@ __global__ __launch_bounds__(256) void ba_lin_pt_kernel(BaView v) {
 #pragma unroll
       for (int i = 0; i < 3; i++) b3[i] = part[6 + i][k - e0];
     } else {
-      lin_pt_edge(v, k, v.pt_free[p] != 0, H6, b3);
+      lin_pt_edge<STEREO>(v, k, v.pt_free[p] != 0, H6, b3);
     }
 #pragma unroll
     for (int i = 0; i < 6; i++) H[i] += H6[i];
@@ -808,7 +956,7 @@ __global__ __launch_bounds__(256) void ba_schur_fused_kernel(BaView v, const dou
 // Used by cs_ba_optimize from the second iteration on (the first needs H_ll for lambda's initial value before any trial), on unsharded
 // graphs without long tracks or host-evaluated edges; the classic pair of kernels serves everything else and the inspection entries.
 enum { LS_PLANES = 18, LS_DCOLS = 16, LS_WAVE_DOUBLES = LS_PLANES * 64 + 12 * LS_DCOLS };   // 10.75 KB per wavefront: three workgroups per CU
-template <int MT>
+template <int MT, bool STEREO>
 __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lambda, int seg, int k, double* lds) {
   const int lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4, rows = 6 * k;
   const int q0 = v.seg_ptr[seg], q1 = v.seg_ptr[seg + 1], n = q1 - q0;
@@ -844,7 +992,9 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
   const int k3 = kk < 3 ? kk : 0;
   // an edge's record (point, measurement, information, intrinsics, kernel width): requested one chunk ahead, with clamped
   // indices -- every load unconditional, so that the requests of the next chunk are in flight under this chunk's products
-  struct EdgeRec { double X[3], uv[2], info[4], intr[4], huber; int p, e; };
+  // (a stereo graph's record adds the edge's kind and u_right; the 3 x 3 information and bf are read where a stereo lane linearises -- ten more
+  // doubles in the record would be held across the chunk's products by every lane, mono ones included)
+  struct EdgeRec { double X[3], uv[2], info[4], intr[4], huber; int p, e; double ur; int kind; };
   auto fetch = [&](int c0) {
     EdgeRec r;
     const int ncl = min(C, n - c0);
@@ -857,6 +1007,7 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
 #pragma unroll
     for (int q = 0; q < 4; q++) { r.info[q] = v.info_u ? v.info_u[q] : v.pm_info[4 * (size_t)r.e + q]; r.intr[q] = v.intr_u ? v.intr_u[q] : v.pm_intr[4 * (size_t)r.e + q]; }
     r.huber = v.pm_huber[r.e];
+    if constexpr (STEREO) { r.ur = v.pm_ur[r.e]; r.kind = v.pm_kind[r.e]; } else { r.ur = 0.0; r.kind = 0; }
     return r;
   };
   EdgeRec rec = fetch(0);
@@ -869,7 +1020,18 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
       const int p = rec.p, e = rec.e;
 #pragma unroll
       for (int q = 0; q < 9; q++) h9[q] = 0.0;
-      if (lc < ncl) {
+      if constexpr (STEREO) {
+        if (lc < ncl) {
+          ProjLin3 L3;
+          proj_linearize_any(rec.kind != 0, T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, rec.ur, stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)e), L3);
+          lin3_point_terms(L3, h9, h9 + 6);
+          const bool both3 = cam_free && v.pt_free[p] != 0;
+#pragma unroll
+          for (int q = 0; q < 6; q++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Wl[3 * q + j][lane] = both3 ? lin3_hpl(L3, q, j) : 0.0;
+        }
+      } else if (lc < ncl) {
         ProjLin L;
         proj_linearize(T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, L);
         double pw[6];  // Jp^T W (3x2)
@@ -986,13 +1148,13 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
         }
       }
 }
-template <int MT>
+template <int MT, bool STEREO>
 __global__ __launch_bounds__(256) void ba_lin_schur_kernel(BaView v, const double* __restrict__ lamp, int seg_begin, int seg_end, double lam_val) {
   __shared__ double lds[4][LS_WAVE_DOUBLES];
   const double lambda = lamp ? lamp[0] : lam_val;      // (by value: the trial's prologue runs beside this kernel, BaSidePrologue)
   const int seg = __builtin_amdgcn_readfirstlane(seg_begin + blockIdx.x * 4 + (threadIdx.x >> 6));
   if (seg >= seg_end) return;
-  ba_lin_schur_segment<MT>(v, lambda, seg, v.seg_k[seg], lds[threadIdx.x >> 6]);
+  ba_lin_schur_segment<MT, STEREO>(v, lambda, seg, v.seg_k[seg], lds[threadIdx.x >> 6]);
 }
 
 // Long tracks (BA_FUSED_KMAX < k <= BA_LONG_KMAX cameras: the tail of a real map, landmarks seen from dozens of key frames): the same
@@ -1286,6 +1448,7 @@ __device__ __forceinline__ void backsub_point(const BaView& v, int p) {
 // The same with H_pl formed on the spot (the fused linearise-in-Schur trials, which never write it): per edge the camera, the point, the
 // measurement -- proj_linearize and the J_c^T (rho' Omega) J_p product exactly as ba_lin_schur_segment / lin_pt_edge form them, then the same
 // sums in the same order as the kernel above: the same x_l bit for bit (tests/test_ba_gpu.py holds the LM run to the classic pair).
+template <bool STEREO>
 __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
   if (p >= v.np) return;
   double cl[3] = {v.bl[3 * p], v.bl[3 * p + 1], v.bl[3 * p + 2]};
@@ -1298,15 +1461,25 @@ __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
     Pose T = pose_load(v.cams + 7 * c);
     double R[9];
     pose_rotmat(T, R);
+    double Wk[18];
+    if constexpr (STEREO) {
+      ProjLin3 L3;
+      proj_linearize_any(v.pm_kind[k] != 0, T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k,
+                         v.pm_ur[k], stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k), L3);
+#pragma unroll
+      for (int q = 0; q < 6; q++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) Wk[3 * q + j] = free_pt ? lin3_hpl(L3, q, j) : 0.0;
+    } else {
     ProjLin L;
     proj_linearize(T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k, L);
-    double Wk[18];
 #pragma unroll
     for (int q = 0; q < 6; q++) {
       const double jw0 = L.Jc[q] * L.Wm[0] + L.Jc[6 + q] * L.Wm[2];
       const double jw1 = L.Jc[q] * L.Wm[1] + L.Jc[6 + q] * L.Wm[3];
 #pragma unroll
       for (int j = 0; j < 3; j++) Wk[3 * q + j] = free_pt ? (jw0 * L.Jp[j] + jw1 * L.Jp[3 + j]) : 0.0;      // (the camera is free here)
+    }
     }
     const double* xp = v.rhs + col;
 #pragma unroll
@@ -1324,7 +1497,7 @@ __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
 
 // Both back-substitutions of a trial in ONE launch: the eliminated cuboids' blocks first (a wave per cuboid: x_o from the cameras' x_p), the
 // landmarks' behind them -- the two read the cameras' increments only and write disjoint outputs.  LIN: H_pl formed on the spot (above).
-template <bool LIN>
+template <bool LIN, bool STEREO>
 __global__ __launch_bounds__(256) void ba_backsub_all_kernel(BaView v, int n_cub_blocks) {
   __shared__ double cl[4][9];
   if ((int)blockIdx.x < n_cub_blocks) {
@@ -1333,7 +1506,7 @@ __global__ __launch_bounds__(256) void ba_backsub_all_kernel(BaView v, int n_cub
     return;
   }
   const int p = (blockIdx.x - n_cub_blocks) * 256 + threadIdx.x;
-  if (LIN) backsub_lin_point(v, p); else backsub_point(v, p);
+  if (LIN) backsub_lin_point<STEREO>(v, p); else backsub_point(v, p);
 }
 
 // bak_*: non-null = the push of the LM trial rides along (OptimizableGraph::push before the update, optimization_algorithm_levenberg.cpp:104-
@@ -2654,7 +2827,8 @@ int ba_chi2_blocks(int n_proj) { int nb = (n_proj + 255) / 256; return nb < 1 ? 
 
 void ba_launch_chi2(const BaView& v, int nb_proj, hipStream_t st) {
   const int ne = v.n_cub + v.n_odom, nb_pose = (ne + 63) / 64;
-  hipLaunchKernelGGL(ba_chi2_kernel, dim3(nb_proj + (nb_pose + 3) / 4), dim3(256), 0, st, v, nb_proj, nb_pose);
+  if (v.pm_kind) hipLaunchKernelGGL(ba_chi2_kernel<true>, dim3(nb_proj + (nb_pose + 3) / 4), dim3(256), 0, st, v, nb_proj, nb_pose);
+  else hipLaunchKernelGGL(ba_chi2_kernel<false>, dim3(nb_proj + (nb_pose + 3) / 4), dim3(256), 0, st, v, nb_proj, nb_pose);
 }
 // the numeric-Jacobian edges (cuboid, odometry: few edges, long dependent chains) run beside the projection edges (many edges, short
 // chains) on a second stream; ba_accum_pose_kernel needs both
@@ -2681,11 +2855,18 @@ void ba_launch_linearize(const BaView& v, hipStream_t st, hipStream_t st2, hipEv
   if (side) (void)hipEventRecord(ev_join, st2);
   if (side3) {
     (void)hipStreamWaitEvent(st3, ev_fork, 0);
-    hipLaunchKernelGGL(ba_lin_pt_kernel, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st3, v);
+    if (v.pm_kind) hipLaunchKernelGGL(ba_lin_pt_kernel<true>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st3, v);
+    else hipLaunchKernelGGL(ba_lin_pt_kernel<false>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st3, v);
     (void)hipEventRecord(ev_join3, st3);
   }
-  if (v.n_proj > 0 || v.nc > 0) hipLaunchKernelGGL(ba_lin_cam_kernel, dim3(v.nc), dim3(256), 0, st, v);
-  if (!side3 && lin_pt) hipLaunchKernelGGL(ba_lin_pt_kernel, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st, v);
+  if (v.n_proj > 0 || v.nc > 0) {
+    if (v.pm_kind) hipLaunchKernelGGL(ba_lin_cam_kernel<true>, dim3(v.nc), dim3(256), 0, st, v);
+    else hipLaunchKernelGGL(ba_lin_cam_kernel<false>, dim3(v.nc), dim3(256), 0, st, v);
+  }
+  if (!side3 && lin_pt) {
+    if (v.pm_kind) hipLaunchKernelGGL(ba_lin_pt_kernel<true>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st, v);
+    else hipLaunchKernelGGL(ba_lin_pt_kernel<false>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st, v);
+  }
   if (side) (void)hipStreamWaitEvent(st, ev_join, 0);
   if (side3) (void)hipStreamWaitEvent(st, ev_join3, 0);
   hipLaunchKernelGGL(ba_accum_pose_kernel, dim3(v.nc + v.no), dim3(128), 0, st, v, 0);
@@ -2722,11 +2903,15 @@ void ba_launch_reduce(const BaView& v, const double* lambda, hipStream_t st, hip
         // (round 6: the one- and two-camera segments ride in the <2> launch -- the same products on the same operands, their second tile idle --
         // instead of a 17 us launch of their own in front of it: the two kernels never overlapped; C4 1 312-1 324 -> 1 336-1 342 LM it/s)
         if (c1 > c0) c0 = 0;
-        if (c0 > 0) hipLaunchKernelGGL(ba_lin_schur_kernel<1>, dim3((c0 + 3) / 4), dim3(256), 0, st, v, lin_lamp, 0, c0, lin_lam);
-        if (c1 > c0) hipLaunchKernelGGL(ba_lin_schur_kernel<2>, dim3((c1 - c0 + 3) / 4), dim3(256), 0, st, v, lin_lamp, c0, c1, lin_lam);
-        if (c2 > c1) hipLaunchKernelGGL(ba_lin_schur_kernel<3>, dim3((c2 - c1 + 3) / 4), dim3(256), 0, st, v, lin_lamp, c1, c2, lin_lam);
-        if (c3 > c2) hipLaunchKernelGGL(ba_lin_schur_kernel<4>, dim3((c3 - c2 + 3) / 4), dim3(256), 0, st, v, lin_lamp, c2, c3, lin_lam);
-        if (c4 > c3) hipLaunchKernelGGL(ba_lin_schur_kernel<5>, dim3((c4 - c3 + 3) / 4), dim3(256), 0, st, v, lin_lamp, c3, c4, lin_lam);
+        const int cb[6] = {0, c0, c1, c2, c3, c4};
+        auto launch = [&](auto kern, int lo, int hi) { if (hi > lo) hipLaunchKernelGGL(kern, dim3((hi - lo + 3) / 4), dim3(256), 0, st, v, lin_lamp, lo, hi, lin_lam); };
+        if (v.pm_kind) {
+          launch(ba_lin_schur_kernel<1, true>, cb[0], cb[1]); launch(ba_lin_schur_kernel<2, true>, cb[1], cb[2]); launch(ba_lin_schur_kernel<3, true>, cb[2], cb[3]);
+          launch(ba_lin_schur_kernel<4, true>, cb[3], cb[4]); launch(ba_lin_schur_kernel<5, true>, cb[4], cb[5]);
+        } else {
+          launch(ba_lin_schur_kernel<1, false>, cb[0], cb[1]); launch(ba_lin_schur_kernel<2, false>, cb[1], cb[2]); launch(ba_lin_schur_kernel<3, false>, cb[2], cb[3]);
+          launch(ba_lin_schur_kernel<4, false>, cb[3], cb[4]); launch(ba_lin_schur_kernel<5, false>, cb[4], cb[5]);
+        }
       } else {
         if (c0 > 0) hipLaunchKernelGGL(ba_schur_fused_kernel<1>, dim3((c0 + 3) / 4), dim3(256), 0, st, v, lambda, 0, c0);
         if (c1 > c0) hipLaunchKernelGGL(ba_schur_fused_kernel<2>, dim3((c1 - c0 + 3) / 4), dim3(256), 0, st, v, lambda, c0, c1);
@@ -2772,10 +2957,20 @@ void ba_launch_scan_finite(const double* p, long long n, int* out, hipStream_t s
 }
 // the edges' (un-robustified) squared errors e^T Omega e, one double per edge: projection edges (point-major order), then the
 // camera-cuboid and the odometry edges -- what a NaN in an error vector turns into
+template <bool STEREO>
 __global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k < v.n_proj) {
     Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
+    if constexpr (STEREO) {
+      if (v.pm_kind[k]) {
+        double e3[3], pc3[3];
+        const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
+        stereo_proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.pm_ur[k], v.intr_u ? v.intr_u : v.pm_intr + 4 * k, srec[9], e3, pc3);
+        out[k] = quad3(e3, srec);
+        return;
+      }
+    }
     double e[2], pc[3];
     proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, e, pc);
     const double* info = v.info_u ? v.info_u : v.pm_info + 4 * k;
@@ -2801,7 +2996,9 @@ __global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out)
 }
 void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st) {
   const int n = v.n_proj + v.n_cub + v.n_odom;
-  if (n > 0) hipLaunchKernelGGL(ba_edge_chi_kernel, dim3((n + 255) / 256), dim3(256), 0, st, v, out);
+  if (n <= 0) return;
+  if (v.pm_kind) hipLaunchKernelGGL(ba_edge_chi_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, v, out);
+  else hipLaunchKernelGGL(ba_edge_chi_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, v, out);
 }
 
 // ---- external (host-evaluated) edges: cs_ba_set_external_edges / cs_ba_set_external_terms ---------------------------------------
@@ -3006,8 +3203,9 @@ void ba_launch_scale(const BaView& v, const double* lambda, double* partial, hip
 void ba_launch_backsub(const BaView& v, hipStream_t st) {
   const int ncb = (v.elim && v.no > 0) ? (v.no + 3) / 4 : 0, npb = (v.np + 255) / 256;
   if (ncb + npb <= 0) return;
-  if (v.fuse_lin) hipLaunchKernelGGL(ba_backsub_all_kernel<true>, dim3(ncb + npb), dim3(256), 0, st, v, ncb);      // (the trial's Schur kernels did not write H_pl)
-  else hipLaunchKernelGGL(ba_backsub_all_kernel<false>, dim3(ncb + npb), dim3(256), 0, st, v, ncb);
+  if (v.fuse_lin && v.pm_kind) hipLaunchKernelGGL((ba_backsub_all_kernel<true, true>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);
+  else if (v.fuse_lin) hipLaunchKernelGGL((ba_backsub_all_kernel<true, false>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);      // (the trial's Schur kernels did not write H_pl)
+  else hipLaunchKernelGGL((ba_backsub_all_kernel<false, false>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);
 }
 void ba_launch_scale_update(const BaView& v, const double* lambda, double* partial, hipStream_t st, double* bak_cams, double* bak_points, double* bak_cubes) {
   const int n = v.np + v.nc + v.no;

@@ -51,6 +51,15 @@ struct BaView {
   // robust kernels (cs_robust.h).  Projection edges: pm_huber / cm_huber hold RobustKernel::delta(); pm_rk / cm_rk the kernel kind, or
   // nullptr when every projection edge has Huber or none (then delta > 0 means Huber -- the common case keeps its 8-byte record)
   const int* pm_rk; const int* cm_rk;
+  // ---- stereo projection edges (EdgeStereoSE3ProjectXYZ: 3-dim error u_left, v, u_right) --------------
+  // They sit in the same two edge lists as the mono edges (the structure phase sees (landmark, camera) only); pm_uv / pm_intr / pm_huber /
+  // pm_rk hold their (u_left, v), (fx fy cx cy), kernel width and kind.  What a mono edge does not have lives in the arrays below, ALL nullptr
+  // in a graph without a stereo edge (the host then launches the kernels' STEREO = false instantiations, which never name them):
+  // kind 1 = stereo; u_right; 10 doubles per edge = the 3 x 3 information (row-major) and bf -- or, where every stereo edge carries the same
+  // ten, pm_sinfo / cm_sinfo = nullptr and the one record sinfo_u (like info_u / intr_u)
+  const int* pm_kind; const int* cm_kind;
+  const double* pm_ur; const double* cm_ur;
+  const double* pm_sinfo; const double* cm_sinfo; const double* sinfo_u;
   // ---- cuboid edges and odometry edges (EdgeSE3Expmap): numeric Jacobians ------------------------------
   // camera-cuboid edges 0 .. n_cub3 - 1 are EdgeSE3Cuboid (9-dim, ce_meas / ce_info), edges n_cub3 .. n_cub - 1 are
   // EdgeSE3CuboidProj (4-dim bounding-box error, pe_meas 4 / pe_info 16 / pe_K 9 per edge, indexed k - n_cub3); both

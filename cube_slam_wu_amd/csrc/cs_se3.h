@@ -181,6 +181,23 @@ CS_HD void proj_error(const Pose& Tcw, const double* X, const double* uv, const 
   r[0] = uv[0] - (pc[0] / pc[2] * intr[0] + intr[2]);
   r[1] = uv[1] - (pc[1] / pc[2] * intr[1] + intr[3]);
 }
+// EdgeStereoSE3ProjectXYZ::computeError (types_six_dof_expmap.h:178-206, .cpp:195-202): obs - cam_project(T.map(X), bf), with the
+// reference's three single-precision roundings -- bf arrives as `const float&`, invz is a `const float` holding the double quotient 1 / z,
+// and bf * invz is a float product -- everything else double (invz is promoted in u and v).  NOT the only-pose stereo edge's projection,
+// which keeps bf double (pose_kernels.hip).  r = (u_left, v, u_right).
+CS_HD void stereo_cam_project_error(const double* pc, const double* uv, double ur, const double* intr, double bf, double* r) {   // pc = T.map(X)
+  const float invz = (float)(1.0 / pc[2]);
+  const float bf32 = (float)bf;
+  const double ul = pc[0] * invz * intr[0] + intr[2];
+  const float disp = bf32 * invz;
+  r[0] = uv[0] - ul;
+  r[1] = uv[1] - (pc[1] * invz * intr[1] + intr[3]);
+  r[2] = ur - (ul - disp);
+}
+CS_HD void stereo_proj_error(const Pose& Tcw, const double* X, const double* uv, double ur, const double* intr, double bf, double* r, double* pc) {
+  pose_map(Tcw, X, pc);
+  stereo_cam_project_error(pc, uv, ur, intr, bf, r);
+}
 // cuboid::cube_log_error (g2o_Object.h:66-73)
 CS_HD void cube_log_error(const Cube& self, const Cube& other, double* res) {
   Pose diff = pose_mul(pose_inv(other.pose), self.pose);

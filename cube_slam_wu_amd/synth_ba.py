@@ -267,3 +267,37 @@ def make_mesh_problem(nx=16, ny=16, n_points=20000, seed=7, spacing=(7.0, 2.5), 
         ce_cam=np.zeros(0, np.int32), ce_cub=np.zeros(0, np.int32), ce_meas=np.zeros((0, 10)), ce_info=np.zeros((0, 81)),
         oe_i=oe_i, oe_j=oe_j, oe_meas=oe_meas, oe_info=np.tile(np.eye(6).ravel(), (len(oe_i), 1)),
         truth=dict(cams=T_cw_true, cuboids=np.zeros((0, 10)), points=pts))
+
+
+BF = 386.1448      # KITTI 00: fx * 0.537 m baseline -- 8 .. 40 m of depth give disparities of 48 .. 10 pixels
+
+
+def stereo_project(T_cw7, X, intr4, bf):
+    """EdgeStereoSE3ProjectXYZ::cam_project (types_six_dof_expmap.cpp:195-202) with its single-precision invz, bf and bf * invz:
+    (u_left, v, u_right) of the points X (n, 3) seen from the poses T_cw7 (n, 7)."""
+    p = quat_rot(T_cw7[..., 3:], X) + T_cw7[..., :3]
+    invz = (1.0 / p[:, 2]).astype(np.float32)
+    ul = p[:, 0] * invz.astype(np.float64) * intr4[:, 0] + intr4[:, 2]
+    v = p[:, 1] * invz.astype(np.float64) * intr4[:, 1] + intr4[:, 3]
+    disp = np.asarray(bf, np.float64).astype(np.float32) * invz
+    return np.stack([ul, v, ul - disp.astype(np.float64)], 1)
+
+
+def make_stereo_problem(stereo_share=0.5, bf=BF, **kw):
+    """make_problem(**kw) with a share of its projection edges turned into EdgeStereoSE3ProjectXYZ edges (a random choice per edge, so the kinds
+    mix inside single tracks; own random stream: the rest of the problem is make_problem's).  A stereo edge's measurement is the edge's own
+    projection of the true point plus N(0, 1) pixel noise on all three coordinates, its information I3.  The mono edges stay under e_*; the
+    stereo edges come as se_pt, se_cam, se_uvr (n, 3), se_info (n, 9), se_intr (n, 5: fx fy cx cy bf), se_huber."""
+    pr = make_problem(**kw)
+    rng = np.random.default_rng(kw.get("seed", 42) + 104729)
+    n_e = len(pr["e_pt"])
+    st = rng.random(n_e) < stereo_share
+    s_pt, s_cam = pr["e_pt"][st], pr["e_cam"][st]
+    intr = pr["e_intr"][st]
+    uvr = stereo_project(pr["truth"]["cams"][s_cam], pr["truth"]["points"][s_pt], intr, np.full(len(s_pt), bf)) + rng.normal(0, 1.0, (len(s_pt), 3))
+    out = dict(pr)
+    for k in ("e_pt", "e_cam", "e_uv", "e_info", "e_intr", "e_huber"):
+        out[k] = pr[k][~st]
+    out.update(se_pt=s_pt, se_cam=s_cam, se_uvr=uvr, se_info=np.tile(np.eye(3).ravel(), (len(s_pt), 1)),
+               se_intr=np.concatenate([intr, np.full((len(s_pt), 1), bf)], 1), se_huber=np.where(pr["e_huber"][st] > 0, np.sqrt(7.815), 0.0))
+    return out

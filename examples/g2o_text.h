@@ -16,6 +16,13 @@
 //                                                           problem, two state lines of this library's own precede the edges they apply to,
 //                                                             CS_INTRINSICS fx fy cx cy        and        CS_ROBUST_HUBER delta     (delta <= 0: none)
 //                                                           -- g2o's loader would skip both as unknown tags, as this one skips any other unknown tag
+//   EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP p c   u_left v u_right  I(0,0) I(0,1) I(0,2) I(1,1) I(1,2) I(2,2)
+//                                                           EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.h:178-206): THREE measurement values and the upper
+//                                                           triangle of the 3 x 3 information.  (The class's own read / write loop over four entries
+//                                                           of its Vector3d measurement, types_six_dof_expmap.cpp:207-231 -- an overrun; not repeated here.)
+//                                                           fx fy cx cy and the kernel come from the same two state lines, bf -- another public member the
+//                                                           class never writes -- from a third,     CS_STEREO_BF bf.     The tag is this library's name.
+//                                                           The stereo edges are written behind the mono ones, their place in g2o's edge order here.
 // The reference's vendored g2o registers NO type with its Factory (no G2O_REGISTER_TYPE under object_slam/Thirdparty/g2o), so its own
 // save() writes nothing for this graph, and EdgeSE3Cuboid::read / write are empty stubs (g2o_Object.h:241-248).  The two SE3 tags are
 // upstream g2o's, as are VERTEX_XYZ and EDGE_SE3_PROJECT_XYZ:EXPMAP [tag names from upstream g2o's G2O_REGISTER_TYPE lines: general knowledge, not in the
@@ -48,6 +55,9 @@ struct Graph {
   std::vector<double> points;
   std::vector<int> pe_pt, pe_cam;
   std::vector<double> pe_uv, pe_info, pe_intr, pe_huber;
+  // stereo camera-point edges (cs_ba_set_edges_proj_stereo: u_left v u_right, information 9 row-major, fx fy cx cy bf, Huber delta or <= 0)
+  std::vector<int> se_pt, se_cam;
+  std::vector<double> se_uvr, se_info, se_intr, se_huber;
 };
 
 inline cs::Cube cuboid_from_minimal(const double* v) {     // cuboid::fromMinimalVector (g2o_Object.h:37-42), zyx_euler_to_quat (matrix_utils.cpp:19-33)
@@ -127,6 +137,23 @@ inline bool save(const std::string& path, const Graph& g, int digits = 17) {
       std::fprintf(f, " "); put(&g.pe_info[4 * k], 2); put(&g.pe_info[4 * k + 3], 1);      // I(0,0) I(0,1) I(1,1)
       std::fprintf(f, "\n");
     }
+    double bf = 0;
+    bool have_bf = false;
+    for (size_t k = 0; k < g.se_pt.size(); k++) {
+      const double* in = &g.se_intr[5 * k];
+      if (!have_intr || in[0] != intr[0] || in[1] != intr[1] || in[2] != intr[2] || in[3] != intr[3]) {
+        std::fprintf(f, "CS_INTRINSICS"); put(in, 4); std::fprintf(f, "\n");
+        for (int q = 0; q < 4; q++) intr[q] = in[q];
+        have_intr = true;
+      }
+      if (!have_bf || in[4] != bf) { std::fprintf(f, "CS_STEREO_BF"); put(in + 4, 1); std::fprintf(f, "\n"); bf = in[4]; have_bf = true; }
+      const double hb = g.se_huber.empty() ? 0.0 : g.se_huber[k];
+      if (!have_huber || hb != huber) { std::fprintf(f, "CS_ROBUST_HUBER"); put(&hb, 1); std::fprintf(f, "\n"); huber = hb; have_huber = true; }
+      std::fprintf(f, "EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP %d %d", g.pt_id[g.se_pt[k]], g.cam_id[g.se_cam[k]]); put(&g.se_uvr[3 * k], 3);
+      std::fprintf(f, " ");
+      for (int r = 0; r < 3; r++) put(&g.se_info[9 * k + 3 * r + r], 3 - r);      // the upper triangle, row by row
+      std::fprintf(f, "\n");
+    }
   }
   const bool ok = std::ferror(f) == 0;
   std::fclose(f);
@@ -141,8 +168,8 @@ inline bool load(const std::string& path, Graph& g, std::string* warnings = null
   g = Graph();
   std::map<int, int> cam_of, cub_of, pt_of;
   std::map<std::string, int> unknown;
-  double cur_intr[4] = {0, 0, 0, 0}, cur_huber = 0;
-  bool have_intr = false;
+  double cur_intr[4] = {0, 0, 0, 0}, cur_huber = 0, cur_bf = 0;
+  bool have_intr = false, have_bf = false;
   auto warn = [&](const std::string& m) { if (warnings) *warnings += m + "\n"; };
   std::string line;
   while (std::getline(f, line)) {
@@ -222,6 +249,19 @@ inline bool load(const std::string& path, Graph& g, std::string* warnings = null
       g.pe_pt.push_back(pt_of[a]); g.pe_cam.push_back(cam_of[b]);
       g.pe_uv.insert(g.pe_uv.end(), uv, uv + 2); g.pe_info.insert(g.pe_info.end(), info, info + 4);
       g.pe_intr.insert(g.pe_intr.end(), cur_intr, cur_intr + 4); g.pe_huber.push_back(cur_huber);
+    } else if (tag == "CS_STEREO_BF") {
+      double v;
+      if (!(ss >> v)) { warn("malformed CS_STEREO_BF line"); continue; }
+      cur_bf = v; have_bf = true;
+    } else if (tag == "EDGE_STEREO_SE3_PROJECT_XYZ:EXPMAP") {
+      int a, b; double uvr[3], info[9];
+      ss >> a >> b >> uvr[0] >> uvr[1] >> uvr[2];
+      for (int r = 0; r < 3; r++) for (int c = r; c < 3; c++) { ss >> info[3 * r + c]; info[3 * c + r] = info[3 * r + c]; }
+      if (!ss || !pt_of.count(a) || !cam_of.count(b)) { warn("Unable to find vertices for edge " + tag + " " + std::to_string(a) + " " + std::to_string(b)); continue; }
+      if (!have_intr || !have_bf) { warn("edge " + tag + " " + std::to_string(a) + " " + std::to_string(b) + " dropped: fx fy cx cy and bf are members the class does not write -- put CS_INTRINSICS and CS_STEREO_BF lines before the edges"); continue; }
+      g.se_pt.push_back(pt_of[a]); g.se_cam.push_back(cam_of[b]);
+      g.se_uvr.insert(g.se_uvr.end(), uvr, uvr + 3); g.se_info.insert(g.se_info.end(), info, info + 9);
+      g.se_intr.insert(g.se_intr.end(), cur_intr, cur_intr + 4); g.se_intr.push_back(cur_bf); g.se_huber.push_back(cur_huber);
     } else if (unknown[tag]++ == 0) {
       warn("unknown type: " + tag);
     }

@@ -123,6 +123,7 @@ static int run_g2o_file(const char* in, const char* out, int iterations, int dig
   if (!warnings.empty()) std::cerr << warnings;
   std::cout << "loaded " << g.cam_id.size() << " cameras, " << g.cub_id.size() << " cuboids, " << g.ce_cam.size() << " camera-cuboid edges, " << g.oe_i.size() << " odometry edges";
   if (!g.pt_id.empty() || !g.pe_pt.empty()) std::cout << ", " << g.pt_id.size() << " points, " << g.pe_pt.size() << " camera-point edges";
+  if (!g.se_pt.empty()) std::cout << ", " << g.se_pt.size() << " stereo camera-point edges";
   std::cout << std::endl;
   if (iterations > 0) {
     // (the handle goes with the scope, whichever CHECK leaves it)
@@ -135,6 +136,7 @@ static int run_g2o_file(const char* in, const char* out, int iterations, int dig
     CHECK(cs_ba_set_vertices(ba.p, g.cam_Tcw.data(), g.cam_fixed.data(), (int)g.cam_id.size(), g.cuboids.data(), g.cub_fixed.data(), (int)g.cub_id.size(),
                              g.points.data(), g.pt_fixed.data(), (int)g.pt_id.size(), cuboids_first));
     if (!g.pe_pt.empty()) CHECK(cs_ba_set_edges_proj(ba.p, (int)g.pe_pt.size(), g.pe_pt.data(), g.pe_cam.data(), g.pe_uv.data(), g.pe_info.data(), g.pe_intr.data(), g.pe_huber.data()));
+    if (!g.se_pt.empty()) CHECK(cs_ba_set_edges_proj_stereo(ba.p, (int)g.se_pt.size(), g.se_pt.data(), g.se_cam.data(), g.se_uvr.data(), g.se_info.data(), g.se_intr.data(), g.se_huber.data()));
     if (!g.ce_cam.empty()) CHECK(cs_ba_set_edges_cuboid(ba.p, (int)g.ce_cam.size(), g.ce_cam.data(), g.ce_cub.data(), g.ce_meas.data(), g.ce_info.data()));
     if (!g.oe_i.empty()) CHECK(cs_ba_set_edges_odom(ba.p, (int)g.oe_i.size(), g.oe_i.data(), g.oe_j.data(), g.oe_meas.data(), g.oe_info.data()));
     int done = 0;

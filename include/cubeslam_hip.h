@@ -270,6 +270,17 @@ int cs_ba_set_estimates(cs_ba* ba, const double* cams7, const double* cuboids10,
  * info4 = 2x2 information, intr4 = fx fy cx cy, huber[k] <= 0 means no robust kernel (NULL: none). */
 int cs_ba_set_edges_proj(cs_ba* ba, int n, const int* point, const int* cam, const double* uv2,
                          const double* info4, const double* intr4, const double* huber);
+/* EdgeStereoSE3ProjectXYZ (types/types_six_dof_expmap.h:178-206, .cpp:195-202, :233-281): vertex 0 = point, vertex 1 = camera; 3-dim
+ * error obs - cam_project(T.map(X), bf) over uvr3 = (u_left, v, u_right); info9 = 3 x 3 information, row-major; intr5 = fx fy cx cy bf;
+ * huber as above.  The error keeps the reference's single-precision roundings (bf is passed as `const float&`, invz = 1 / z is a
+ * `const float`, bf * invz a float product); the analytic Jacobians are all double.  The edges are evaluated on the device like the mono
+ * ones and share their lists, the Schur schedule and every solve path; in g2o's edge order they FOLLOW the mono projection edges -- so
+ * in cs_ba_get_system's Hpl18 (rows n_mono ..), in cs_ba_check_finite's edge indices and in the squared-error scan.  Mono and stereo
+ * edges may observe the same landmark; two projection edges of either kind between the same landmark and camera are refused, as two
+ * mono edges are.  Not available on a sharded handle: cs_ba_set_shard(n_ranks > 1) on a handle that holds stereo edges (and setting them
+ * on a sharded one) returns CS_ERR_INVALID_ARG.  Kernels: class CS_EDGE_PROJ_STEREO of cs_ba_set_robust_kernels.                  */
+int cs_ba_set_edges_proj_stereo(cs_ba* ba, int n, const int* point, const int* cam, const double* uvr3,
+                                const double* info9, const double* intr5, const double* huber);
 /* EdgeSE3Cuboid (g2o_Object.h:235-260): vertex 0 = camera, vertex 1 = cuboid; meas10 = cuboid in the
  * camera frame, info81 = 9x9 information.                                                          */
 int cs_ba_set_edges_cuboid(cs_ba* ba, int n, const int* cam, const int* cuboid, const double* meas10, const double* info81);
@@ -290,7 +301,7 @@ int cs_ba_set_edges_odom(cs_ba* ba, int n, const int* cam_i, const int* cam_j, c
  * edge count; kind == NULL removes the class's kernels (n is then ignored).  cs_ba_set_edges_proj's `huber` argument is shorthand for
  * (CS_RK_HUBER, huber[k]) where huber[k] > 0.  Edges appended later carry no kernel (projection edges: their `huber` value).     */
 enum cs_robust_kernel { CS_RK_NONE = 0, CS_RK_HUBER = 1, CS_RK_PSEUDO_HUBER = 2, CS_RK_CAUCHY = 3, CS_RK_SATURATED = 4, CS_RK_DCS = 5, CS_RK_TUKEY = 6 };
-enum cs_edge_class { CS_EDGE_PROJ = 0, CS_EDGE_CUBOID = 1, CS_EDGE_CUBOID_PROJ = 2, CS_EDGE_ODOM = 3 };
+enum cs_edge_class { CS_EDGE_PROJ = 0, CS_EDGE_CUBOID = 1, CS_EDGE_CUBOID_PROJ = 2, CS_EDGE_ODOM = 3, CS_EDGE_PROJ_STEREO = 4 };
 int cs_ba_set_robust_kernels(cs_ba* ba, int edge_class, int n, const int* kind, const double* delta);
 
 /* External (host-evaluated) edges: the CPU path for edge types the library does not evaluate -- what g2o's BlockSolver does for
@@ -332,6 +343,7 @@ int cs_ba_solve(cs_ba* ba, double lambda, int* positive_definite); /* setLambda 
 int cs_ba_append_vertices(cs_ba* ba, const double* cams7, const int* cam_fixed, int n_cams, const double* cuboids10, const int* cub_fixed, int n_cuboids,
                           const double* points3, const int* pt_fixed, int n_points);
 int cs_ba_append_edges_proj(cs_ba* ba, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber);
+int cs_ba_append_edges_proj_stereo(cs_ba* ba, int n, const int* pt, const int* cam, const double* uvr3, const double* info9, const double* intr5, const double* huber);
 int cs_ba_append_edges_cuboid(cs_ba* ba, int n, const int* cam, const int* cub, const double* meas10, const double* info81);
 int cs_ba_append_edges_cuboid_proj(cs_ba* ba, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9);
 int cs_ba_append_edges_odom(cs_ba* ba, int n, const int* cam_i, const int* cam_j, const double* meas7, const double* info36);
