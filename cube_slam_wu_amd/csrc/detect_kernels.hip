@@ -565,6 +565,78 @@ enum { SCORE_JOBS = 4, SCORE_SUB = 128, SCORE_BINS = SCORE_JOBS * SCORE_SUB };  
 // loads: its 34 words per lane were vector loads of one address) and the three integer divisions by T and Y per proposal are one
 // multiplication each (reciprocals formed once; exact while n d < 2^32, the division itself otherwise -- as in candidate_compact_kernel).
 __device__ __forceinline__ unsigned score_udiv(unsigned n, unsigned d, unsigned inv) { return inv ? __umulhi(n, inv) : n / d; }
+
+// The distance term of score_kernel: the gathers of EU edges are issued before their (sequential, float) accumulation.  One body, three
+// instances by what the wavefront holds after the block's re-sort (it is almost always one configuration):
+//   SCORE_WAVE_MIXED  both configurations: corner ids and weights are nibbles of per-lane words, every sample goes through
+//                     mul, add, select (a lane of configuration 2 keeps its sum over edges 7 and 8);
+//   SCORE_WAVE_CFG1 / SCORE_WAVE_CFG2  one configuration: the tables are constants and the edge number is uniform, so ids and weights
+//                     are scalar work, and what the mul and the select cannot change is not issued.  Identities on the bits, no rounding moves:
+//                     d * 1.0f is d for every float (a NaN's payload reaches the following add either way); `on ? nx : sum` with `on`
+//                     true is nx; with `on` false every sample of the edge keeps sum, which is what not visiting the edge does.
+// The order of the additions -- s = 0..10 within an edge, the edges in table order -- is the same in all three.
+enum { SCORE_WAVE_MIXED = 0, SCORE_WAVE_CFG1 = 1, SCORE_WAVE_CFG2 = 2 };
+template <int MODE>
+__device__ __forceinline__ void score_edge_trip(int e0, int cfg, const double (*CXt)[260], const double (*CYt)[260], int tx, double ox, double oy,
+                                                const float* __restrict__ map, int map_w, float& sum_dist) {
+  // corner ids of the 9 edges, one nibble each (edge 0 lowest): {0,1,2,3,1,2,3,4,4}-{1,2,3,0,5,4,7,7,5} / {0,1,2,3,1,2,4,0,0}-{1,2,3,0,5,4,5,0,0}
+  const bool c2 = MODE == SCORE_WAVE_MIXED ? cfg != 0 : MODE == SCORE_WAVE_CFG2;
+  const unsigned long long EA = c2 ? 0x004213210ull : 0x443213210ull, EB = c2 ? 0x005450321ull : 0x577450321ull;
+  // config 2 reweights edges 4, 5 by 3/2 and edge 6 by 2 (:655-661), one weight nibble per edge in halves.  The reference
+  // computes float(double(d) * 3.0 / 2.0) and float(double(d) * 2.0): both products are exact in double, so the one rounding
+  // to float is the rounding of the float product d * 1.5f (d * 2.0f), and d * 1.0f is d.
+  const unsigned long long EW = c2 ? 0x004332222ull : 0x222222222ull;
+  const int n_edges = c2 ? 7 : 9;
+  constexpr int EU = 3;   // edges per trip: their 11 * EU gathers are in flight together
+  float dv[EU][11];
+#pragma unroll
+  for (int u = 0; u < EU; u++) {
+    const int e = e0 + u;                    // (mixed, beyond the list: nibble 0 = corner 1, a valid address; the sum skips it)
+    if (MODE != SCORE_WAVE_MIXED && e >= n_edges) continue;       // round 4: a wavefront of configuration 2 gathers one edge in its last trip
+    const int a = (int)((EA >> (4 * e)) & 7), b = (int)((EB >> (4 * e)) & 7);
+    const double x1 = CXt[a][tx] - ox, y1 = CYt[a][tx] - oy, x2 = CXt[b][tx] - ox, y2 = CYt[b][tx] - oy;
+#pragma unroll
+    for (int s = 0; s < 11; s++) {
+      // s / 10 * p1 + (1 - s / 10) * p2 (object_3d_util.cpp:645-652).  Round 4: s = 0 and s = 10 ARE the end points (0 * a + 1 * b: the
+      // product with 0 is +-0, the product with 1 exact, and the sum with +-0 leaves b unless b is itself a zero, whose sign the
+      // integer cast drops); s = 5 is (a + b) * 0.5 (both halves are exact, the single rounding happens in the sum either way)
+      double sx, sy;
+      if (s == 0) { sx = x2; sy = y2; }
+      else if (s == 10) { sx = x1; sy = y1; }
+      else if (s == 5) { sx = (x1 + x2) * 0.5; sy = (y1 + y2) * 0.5; }
+      else { const double w = (double)s / 10.0; sx = w * x1 + (1 - w) * x2; sy = w * y1 + (1 - w) * y2; }
+      // samples lie inside the ROI the map covers (corners were tested against it): row * width + column fits 24 x 24 -> 32 bits
+      dv[u][s] = map[(unsigned)(__mul24((int)sy, map_w) + (int)sx)];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < EU; u++) {
+    const int e = e0 + u;
+    const float wt = MODE == SCORE_WAVE_CFG1 ? 1.0f : 0.5f * (float)(int)((EW >> (4 * e)) & 7);
+    const bool on = e < n_edges;
+    if (MODE == SCORE_WAVE_MIXED) {
+#pragma unroll
+      for (int s = 0; s < 11; s++) { const float nx = sum_dist + dv[u][s] * wt; sum_dist = on ? nx : sum_dist; }
+    } else if (!on) {
+    } else if (wt == 1.0f) {               // (e is uniform: branches of the wavefront, not selects)
+#pragma unroll
+      for (int s = 0; s < 11; s++) sum_dist += dv[u][s];
+    } else {
+#pragma unroll
+      for (int s = 0; s < 11; s++) sum_dist += dv[u][s] * wt;
+    }
+  }
+}
+template <int MODE>
+__device__ __forceinline__ float score_edge_sum(int cfg, const double (*CXt)[260], const double (*CYt)[260], int tx, double ox, double oy,
+                                                const float* __restrict__ map, int map_w) {
+  float sum_dist = 0;
+  const int n_edges = MODE == SCORE_WAVE_MIXED ? (cfg ? 7 : 9) : MODE == SCORE_WAVE_CFG2 ? 7 : 9;
+#pragma unroll 1
+  for (int e0 = 0; e0 < n_edges; e0 += 3) score_edge_trip<MODE>(e0, cfg, CXt, CYt, tx, ox, oy, map, map_w, sum_dist);
+  return sum_dist;
+}
+
 template <bool CAP>
 __global__ __launch_bounds__(256) void score_kernel(DetectDeviceView v, long long slot_total, double short_sq_bound) {
   // [coordinate: x0..x7, y0..y7][lane]: every lane keeps its proposal's corners in its own column (LDS because the edge tables index
@@ -668,55 +740,15 @@ __global__ __launch_bounds__(256) void score_kernel(DetectDeviceView v, long lon
 #pragma unroll
     for (int q = 0; q < 6; q++) bnd[q] = bound[q];
   }
-  // ---- distance error: all gathers of an edge are issued before its (sequential, float) accumulation
-  float sum_dist = 0;
-  // corner ids of the 9 edges, one nibble each (edge 0 lowest): {0,1,2,3,1,2,3,4,4}-{1,2,3,0,5,4,7,7,5} / {0,1,2,3,1,2,4,0,0}-{1,2,3,0,5,4,5,0,0}
-  const unsigned long long EA = cfg ? 0x004213210ull : 0x443213210ull, EB = cfg ? 0x005450321ull : 0x577450321ull;
-  // config 2 reweights edges 4, 5 by 3/2 and edge 6 by 2 (:655-661), one weight nibble per edge in halves.  The reference
-  // computes float(double(d) * 3.0 / 2.0) and float(double(d) * 2.0): both products are exact in double, so the one rounding
-  // to float is the rounding of the float product d * 1.5f (d * 2.0f), and d * 1.0f is d.
-  const unsigned long long EW = cfg ? 0x004332222ull : 0x222222222ull;
-  const int n_edges = cfg ? 7 : 9;
+  // ---- distance error (score_edge_sum above).  After the re-sort a wavefront is almost always one configuration: the vote is taken once,
+  // among the lanes that score a proposal (the others have returned), and a one-configuration wavefront takes the instance that issues
+  // nothing for what its configuration fixes
   const int map_w = jd.map_w;
-  constexpr int EU = 3;   // edges per trip: their 11 * EU gathers are in flight together
-  const bool wave_has_cfg1 = __any(cfg == 0);  // round 4: a wavefront of configuration-2 proposals has no edges 7 and 8 (it mostly is one
-                                               // configuration after the re-sort), so its last trip gathers one edge instead of three
-#pragma unroll 1
-  for (int e0 = 0; e0 < n_edges; e0 += EU) {
-    float dv[EU][11];
-#pragma unroll
-    for (int u = 0; u < EU; u++) {
-      const int e = e0 + u;                    // (beyond the list: nibble 0 = corner 1, a valid address; the sum skips it)
-      if (u > 0 && e0 == 6 && !wave_has_cfg1) {
-#pragma unroll
-        for (int s = 0; s < 11; s++) dv[u][s] = 0.0f;
-        continue;
-      }
-      const int a = (int)((EA >> (4 * e)) & 7), b = (int)((EB >> (4 * e)) & 7);
-      const double x1 = CXt[a][tx] - ox, y1 = CYt[a][tx] - oy, x2 = CXt[b][tx] - ox, y2 = CYt[b][tx] - oy;
-#pragma unroll
-      for (int s = 0; s < 11; s++) {
-        // s / 10 * p1 + (1 - s / 10) * p2 (object_3d_util.cpp:645-652).  Round 4: s = 0 and s = 10 ARE the end points (0 * a + 1 * b: the
-        // product with 0 is +-0, the product with 1 exact, and the sum with +-0 leaves b unless b is itself a zero, whose sign the
-        // integer cast drops); s = 5 is (a + b) * 0.5 (both halves are exact, the single rounding happens in the sum either way)
-        double sx, sy;
-        if (s == 0) { sx = x2; sy = y2; }
-        else if (s == 10) { sx = x1; sy = y1; }
-        else if (s == 5) { sx = (x1 + x2) * 0.5; sy = (y1 + y2) * 0.5; }
-        else { const double w = (double)s / 10.0; sx = w * x1 + (1 - w) * x2; sy = w * y1 + (1 - w) * y2; }
-        // samples lie inside the ROI the map covers (corners were tested against it): row * width + column fits 24 x 24 -> 32 bits
-        dv[u][s] = map[(unsigned)(__mul24((int)sy, map_w) + (int)sx)];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < EU; u++) {
-      const int e = e0 + u;
-      const float wt = 0.5f * (float)(int)((EW >> (4 * e)) & 7);
-      const bool on = e < n_edges;
-#pragma unroll
-      for (int s = 0; s < 11; s++) { const float nx = sum_dist + dv[u][s] * wt; sum_dist = on ? nx : sum_dist; }
-    }
-  }
+  const bool u1 = __all(cfg == 0), u2 = __all(cfg == 1);
+  float sum_dist;
+  if (u1) sum_dist = score_edge_sum<SCORE_WAVE_CFG1>(cfg, CXt, CYt, tx, ox, oy, map, map_w);
+  else if (u2) sum_dist = score_edge_sum<SCORE_WAVE_CFG2>(cfg, CXt, CYt, tx, ox, oy, map, map_w);
+  else sum_dist = score_edge_sum<SCORE_WAVE_MIXED>(cfg, CXt, CYt, tx, ox, oy, map, map_w);
   // ---- angle alignment error
   double total = 0;
   const double not_found_penalty = 30.0 / 180.0 * CS_PI * 2;
