@@ -168,7 +168,10 @@ class BlockSolverHIP : public g2o::Solver {
     }
     std::vector<double> blocks(total + 1);
     int pd = 1;
-    if (cs_ba_pose_marginals(ba_, (int)blockIndices.size(), ci.data(), ii.data(), cj.data(), ij.data(), blocks.data(), &pd) != CS_OK) return fail("cs_ba_pose_marginals");
+    // (CS_ERR_NOT_RUN: the handle holds no linear system -- none was built yet, or cs_ba_optimize ran on it since: that call leaves none behind)
+    const int rc = cs_ba_pose_marginals(ba_, (int)blockIndices.size(), ci.data(), ii.data(), cj.data(), ij.data(), blocks.data(), &pd);
+    if (rc == CS_ERR_NOT_RUN) return refuse("computeMarginals: no linear system on the device (after cs_ba_optimize there is none): build the system first -- buildSystem(), i.e. cs_ba_compute_errors + cs_ba_build_system");
+    if (rc != CS_OK) return fail("cs_ba_pose_marginals");
     if (!pd) return false;                                 // (Cholesky failure: the reference's solvePattern returns false)
     spinv = g2o::SparseBlockMatrix<g2o::MatrixXd>(&rbi[0], &rbi[0], (int)rbi.size(), (int)rbi.size(), true);
     size_t o = 0;

@@ -351,7 +351,13 @@ struct cs_ba {
   cs_external_fn ext_fn = nullptr; void* ext_ctx = nullptr;
   // last solution / rhs on the host (for LM's scale term and for inspection)
   std::vector<double> h_b, h_x;
+  // The linear system in device memory is ONE linearisation of the current graph: set by build_system_device, cleared by the structure phase, by new
+  // estimates or external terms, and by every optimize call that ran an iteration (what that leaves behind is blocks of up to three states: H_pl of
+  // its first iteration, pose blocks of the speculated linearisation, landmark blocks of the trial before).
   bool have_system = false;
+  // cams_bak / points_bak / cubes_bak hold what cs_ba_push saved (one level).  Dead after the structure phase, cs_ba_set_estimates, an optimize call
+  // that ran an iteration (its update kernel saves every trial's estimates there) and after cs_ba_pop has restored it.
+  bool backup_live = false;
   cs_ba_timing tm{};
   cs::BaView view{};
 };
@@ -1549,6 +1555,7 @@ int finalize_structure(cs_ba* B) {
   mark("pose edges + allocations");
   B->structure_dirty = false;
   B->have_system = false;
+  B->backup_live = false;
   return CS_OK;
 }
 
@@ -2154,6 +2161,7 @@ static int cs_ba_set_estimates_impl(cs_ba* B, const double* cams7, const double*
   if (cuboids10 && B->no) CS_HIP_TRY(hipMemcpy(B->cubes.p, cuboids10, 80 * (size_t)B->no, hipMemcpyHostToDevice));
   if (points3 && B->np) CS_HIP_TRY(hipMemcpy(B->points.p, points3, 24 * (size_t)B->np, hipMemcpyHostToDevice));
   B->have_system = false;
+  B->backup_live = false;
   return CS_OK;
 }
 int cs_ba_set_estimates(cs_ba* B, const double* cams7, const double* cuboids10, const double* points3) {
@@ -2391,10 +2399,18 @@ int cs_ba_build_system(cs_ba* B) {
   CS_GUARD_END("cs_ba_build_system")
 }
 
+// The guard of every call that reads the linear system (see cs_ba::have_system).
+static int need_system(cs_ba* B, const char* who) {
+  if (!B->structure_dirty && B->have_system) return CS_OK;
+  cs_set_error(std::string(who) + ": no linear system on the handle (none was built, or the graph, the estimates or the external terms changed, or cs_ba_optimize ran "
+               "since): call cs_ba_compute_errors + cs_ba_build_system first");
+  return CS_ERR_NOT_RUN;
+}
+
 static int cs_ba_solve_impl(cs_ba* B, double lambda, int* pd) {
   if (!B) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
-  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_solve: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  if (int rn = need_system(B, "cs_ba_solve")) return rn;
   bool ok = false;
   int rc = solve_device(B, lambda, &ok); if (rc) return rc;
   if (ok) debug_nan_scan(B, "after cs_ba_solve");
@@ -2410,7 +2426,7 @@ int cs_ba_solve(cs_ba* B, double lambda, int* pd) {
 int cs_ba_update(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
-  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_update: no solution to apply (call cs_ba_build_system and cs_ba_solve first)"); return CS_ERR_NOT_RUN; }
+  if (int rn = need_system(B, "cs_ba_update (no solution to apply; cs_ba_solve comes after them)")) return rn;
   CS_HIP_TRY(hipSetDevice(B->device));
   double t0 = now_ms();
   cs::ba_launch_update(B->view, B->st);
@@ -2422,14 +2438,28 @@ int cs_ba_update(cs_ba* B) {
   CS_GUARD_END("cs_ba_update")
 }
 
+// The estimates into / out of the backup buffers, queued on the handle's stream: what cs_ba_push / cs_ba_pop do once their guards have passed, and
+// what cs_ba_optimize's own trials use (its rollback of a rejected trial is not the caller's pop and goes through no guard).
+static int save_estimates(cs_ba* B) {
+  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams_bak.p, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
+  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points_bak.p, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
+  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes_bak.p, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
+  return CS_OK;
+}
+static int restore_estimates(cs_ba* B) {
+  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams.p, B->cams_bak.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
+  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points.p, B->points_bak.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
+  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes.p, B->cubes_bak.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
+  return CS_OK;
+}
+
 int cs_ba_push(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
   CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
-  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams_bak.p, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
-  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points_bak.p, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
-  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes_bak.p, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
+  rc = save_estimates(B); if (rc) return rc;
+  B->backup_live = true;
   return CS_OK;
   CS_GUARD_END("cs_ba_push")
 }
@@ -2437,11 +2467,13 @@ int cs_ba_push(cs_ba* B) {
 int cs_ba_pop(cs_ba* B) {
   if (!B) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
-  if (B->structure_dirty) { cs_set_error("cs_ba_pop: nothing was pushed since the graph changed"); return CS_ERR_NOT_RUN; }
+  if (B->structure_dirty || !B->backup_live) {
+    cs_set_error("cs_ba_pop: no backup to restore (cs_ba_push has not run since the graph changed, since cs_ba_set_estimates, since a cs_ba_optimize call or since the last cs_ba_pop)");
+    return CS_ERR_NOT_RUN;
+  }
   CS_HIP_TRY(hipSetDevice(B->device));
-  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams.p, B->cams_bak.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
-  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points.p, B->points_bak.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
-  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes.p, B->cubes_bak.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
+  int rc = restore_estimates(B); if (rc) return rc;
+  B->backup_live = false;        // (one level, and spent once restored)
   return CS_OK;
   CS_GUARD_END("cs_ba_pop")
 }
@@ -2518,6 +2550,9 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
                            B->n_seg == std::max(std::max(std::max(B->seg_class[0], B->seg_class[1]), std::max(B->seg_class[2], B->seg_class[3])), B->seg_class[4]) &&
                            getenv("CS_BA_DEBUG_NAN") == nullptr;
   struct FuseLinGuard { cs_ba* b; ~FuseLinGuard() { b->view.fuse_lin = 0; } } fuse_lin_guard{B};   // (every other entry point linearises with the classic kernels)
+  // Once an iteration has started, whatever way this call returns: no linear system for the stepwise and inspection calls (see cs_ba::have_system), and
+  // the caller's pushed estimates are gone (the trials below save theirs in the same buffers).  Two host flags: nothing is queued for them.
+  struct LeftoverGuard { cs_ba* b; bool ran; ~LeftoverGuard() { if (ran) { b->have_system = false; b->backup_live = false; } } } leftover_guard{B, false};
   // The NEXT iteration's linearisation is queued right behind a trial, before the host has the trial's verdict: nearly every trial is accepted, and
   // the ~70 us the host needs to read the scalars, decide and queue again then pass while the device linearises (the timeline showed the device
   // idle for exactly that long after every trial).  A rejected trial pops the estimates and linearises the restored state once more -- the same
@@ -2549,6 +2584,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
   double carriedChi = 0;
   bool have_carried = false;     // chi2 of the current state is known from the previous iteration's last trial
   for (int it = 0; it < iterations; it++) {
+    leftover_guard.ran = true;
     double currentChi = 0;
     double t0 = now_ms();
     rc = ext_refresh(1); if (rc) return rc;        // (the terms of this iteration's linearisation, and the chi2 share at the current state)
@@ -2602,7 +2638,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     double rho = 0;
     int qmax = 0;
     do {
-      if (!stream_flow) { rc = cs_ba_push(B); if (rc) return rc; }      // (stream flow: the update kernel below saves the estimates it replaces)
+      if (!stream_flow) { rc = save_estimates(B); if (rc) return rc; }      // (stream flow: the update kernel below saves the estimates it replaces)
       bool ok2 = true;
       bool spec_now = false;
       double scale = 0;
@@ -2693,7 +2729,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
       } else {
         lambda *= ni;
         ni *= 2;
-        rc = cs_ba_pop(B); if (rc) return rc;
+        rc = restore_estimates(B); if (rc) return rc;
         if (spec_now) {            // the speculation linearised the rejected state: the restored one again, as this iteration linearises
           rc = build_system_device(B); if (rc) return rc;
         }
@@ -2819,7 +2855,7 @@ int cs_ba_solver_layout(cs_ba* B, int* band_ld, int* team) {
 
 static int cs_ba_get_system_impl(cs_ba* B, double* Hpp, double* Hll9, double* Hpl18, double* b, double* x) {
   if (!B) return CS_ERR_INVALID_ARG;
-  if (B->structure_dirty || !B->have_system) return CS_ERR_NOT_RUN;
+  if (int rn = need_system(B, "cs_ba_get_system")) return rn;
   CS_HIP_TRY(hipSetDevice(B->device));
   const int n = B->n_pose;
   if (Hpp) {
@@ -2885,7 +2921,7 @@ int cs_ba_get_system(cs_ba* B, double* Hpp, double* Hll9, double* Hpl18, double*
 static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite) {
   if (!B || n_pairs < 0 || (n_pairs && (!class_i || !idx_i || !class_j || !idx_j || !out))) return CS_ERR_INVALID_ARG;
   if (positive_definite) *positive_definite = 1;
-  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_pose_marginals: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  if (int rn = need_system(B, "cs_ba_pose_marginals")) return rn;
   if (B->shard_n > 1) { cs_set_error("cs_ba_pose_marginals: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
   if (n_pairs == 0) return CS_OK;
   const int n = B->n_pose;
@@ -2952,7 +2988,7 @@ int cs_ba_pose_marginals(cs_ba* B, int n_pairs, const int* class_i, const int* i
 // (block_solver.hpp:373-439) at `lambda` on the current linearisation; no factorisation.
 static int cs_ba_get_reduced_system_impl(cs_ba* B, double lambda, double* S_dense, double* rhs, int* cam_col, int* cub_col) {
   if (!B) return CS_ERR_INVALID_ARG;
-  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_get_reduced_system: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  if (int rn = need_system(B, "cs_ba_get_reduced_system")) return rn;
   if (B->shard_n > 1) { cs_set_error("cs_ba_get_reduced_system: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
   CS_HIP_TRY(hipSetDevice(B->device));
   const int n = B->n_red;
@@ -3062,7 +3098,7 @@ int cs_ba_structure_digest(cs_ba* B, unsigned long long* out, int cap, int* n_ta
 // (optimization_algorithm_levenberg.cpp:166-180): A_ii of every vertex, caller's vertex order, zeros for fixed vertices.
 int cs_ba_get_vertex_hessians(cs_ba* B, double* cam36, double* cub81, double* pt9) {
   if (!B) return CS_ERR_INVALID_ARG;
-  if (B->structure_dirty || !B->have_system) { cs_set_error("cs_ba_get_vertex_hessians: call cs_ba_build_system first"); return CS_ERR_NOT_RUN; }
+  if (int rn = need_system(B, "cs_ba_get_vertex_hessians")) return rn;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (cam36 && B->nc) {
@@ -3138,7 +3174,7 @@ static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_
     };
     arrs.insert(arrs.end(), std::begin(sys), std::end(sys));
   }
-  if (B->tm.n_solves > 0) {
+  if (B->have_system && B->tm.n_solves > 0) {      // (an increment belongs to the system it solved)
     arrs.push_back({"pose increment x_p (solver order)", v.rhs, B->n_pose, 1, "column"});
     arrs.push_back({"landmark increment", v.xl, 3LL * B->np, 3, "point"});
   }

@@ -348,11 +348,24 @@ int cs_ba_append_edges_cuboid(cs_ba* ba, int n, const int* cam, const int* cub, 
 int cs_ba_append_edges_cuboid_proj(cs_ba* ba, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9);
 int cs_ba_append_edges_odom(cs_ba* ba, int n, const int* cam_i, const int* cam_j, const double* meas7, const double* info36);
 int cs_ba_update(cs_ba* ba);                                 /* SparseOptimizer::update(x)              */
-int cs_ba_push(cs_ba* ba);                                   /* SparseOptimizer::push / pop / discardTop */
+/* SparseOptimizer::push / pop, ONE level deep (g2o keeps a stack per vertex; LM needs one level): cs_ba_push saves the estimates in a backup on the
+ * device, cs_ba_pop restores them.  cs_ba_pop needs a LIVE backup: only cs_ba_push makes one, and a change of the graph (the structure phase runs
+ * again), cs_ba_set_estimates and every cs_ba_optimize / cs_ba_optimize_sharded call that ran an iteration (its trials save their own estimates in
+ * the same buffers) make it dead; restoring spends it, so a second cs_ba_pop needs a cs_ba_push in between.  Without a live backup cs_ba_pop
+ * returns CS_ERR_NOT_RUN and leaves the estimates untouched.                                                                                    */
+int cs_ba_push(cs_ba* ba);
 int cs_ba_pop(cs_ba* ba);
 
 /* SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg; returns (in *iterations_done)
- * what g2o returns.  History arrays (may be NULL) receive chi2 / lambda / LM trials of every iteration. */
+ * what g2o returns.  History arrays (may be NULL) receive chi2 / lambda / LM trials of every iteration.
+ * AFTER THE CALL THE HANDLE HOLDS NO LINEAR SYSTEM.  Once cs_ba_optimize or cs_ba_optimize_sharded has run at least one iteration (any solver
+ * path, sharded or not), cs_ba_solve, cs_ba_update, cs_ba_get_system, cs_ba_get_reduced_system, cs_ba_get_vertex_hessians and
+ * cs_ba_pose_marginals return CS_ERR_NOT_RUN until cs_ba_compute_errors + cs_ba_build_system have linearised the returned state, and
+ * cs_ba_check_finite scans the estimates and the edges' errors only.  (The loop forms H_pl inside its Schur kernels without storing it and
+ * linearises the next state behind a trial before the trial's verdict: what it leaves in memory is blocks of several states -- not g2o's
+ * leftover either, which is the linearisation of the state before the last step.)  The backup of cs_ba_push is dead as well (above).
+ * cs_ba_get_state, cs_ba_compute_errors, cs_ba_build_system, another cs_ba_optimize, the timing and layout queries and the append calls are not
+ * affected; iterations == 0 changes nothing and keeps whatever system and backup the handle had.                                               */
 int cs_ba_optimize(cs_ba* ba, int iterations, int* iterations_done, double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap);
 
 /* Sharded BA over the GPUs of one node (one process per GPU).  Every rank describes the FULL problem
@@ -437,13 +450,17 @@ int cs_ba_schur_layout(cs_ba* ba, int* fused, int* n_segments, int* n_partial_bl
  * -- threaded and sequential (CS_BA_STRUCT_THREADS=1), appended frame by frame and set up at once -- agree table by table.          */
 int cs_ba_structure_digest(cs_ba* ba, unsigned long long* out, int cap, int* n_tables);
 /* Inspection for parity tests (host copies, caller-sized): dense Hpp (size_pose^2, no lambda), Hll (9 per
- * free point in point order), Hpl (18 per projection edge in the caller's edge order), b, x.            */
+ * free point in point order), Hpl (18 per projection edge in the caller's edge order), b, x.
+ * This and the three inspection calls below (cs_ba_pose_marginals, cs_ba_get_reduced_system, cs_ba_get_vertex_hessians) read the linear system
+ * cs_ba_build_system left: CS_ERR_NOT_RUN when there is none -- before the first cs_ba_build_system, after a change of the graph, of the estimates
+ * (cs_ba_set_estimates) or of the external terms, and after cs_ba_optimize (see there).                                                        */
 int cs_ba_get_system(cs_ba* ba, double* Hpp_dense, double* Hll9, double* Hpl18, double* b, double* x);
 /* Solver::computeMarginals (core/block_solver.hpp:488-499 -> LinearSolver::solvePattern on _Hpp, core/marginal_covariance_cholesky.cpp:154-222):
  * blocks of the inverse of the pose-pose Hessian as cs_ba_build_system left it (no lambda, no Schur complement -- what the reference's call
  * factorises).  Pair k = rows of vertex (class_i[k], idx_i[k]) x columns of vertex (class_j[k], idx_j[k]) (cs_vertex_class: cameras 6, cuboids
  * 9; free vertices only), written row-major one after the other into `out`.  *positive_definite = 0 when H_pp cannot be factorised (g2o
- * returns false there).  A query call (dense rocSOLVER factorisation of H_pp), not a per-iteration path.                                  */
+ * returns false there).  A query call (dense rocSOLVER factorisation of H_pp), not a per-iteration path.  After cs_ba_optimize: CS_ERR_NOT_RUN
+ * until cs_ba_compute_errors + cs_ba_build_system (the marginals of the optimised state need its linearisation).                            */
 int cs_ba_pose_marginals(cs_ba* ba, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite);
 
 /* The damped reduced system as the solver is about to factorise it (the Schur-complement build of block_solver.hpp:373-439 at `lambda`
@@ -479,8 +496,8 @@ int cs_ba_set_lm_params(cs_ba* ba, double user_lambda_init, int max_trials_after
 /* Debug / repro aids (what g2o offers through its debug builds and its text IO).
  * cs_ba_check_finite: scans for NaN / Inf where g2o's debug builds look for them -- the edges' errors (SparseOptimizer::
  * computeActiveErrors, core/sparse_optimizer.cpp:78-86) and Jacobians (BlockSolver::buildSystem, core/block_solver.hpp:533-544) --
- * through what they turn into on the device: every edge's squared error, every block of the linear system (after cs_ba_build_system),
- * the increments (after a solve) and the estimates.  *n_bad = number of non-finite values (0 = clean); report (may be NULL) receives one
+ * through what they turn into on the device: every edge's squared error, every block of the linear system and the increments of a solve
+ * (while the handle holds a system: after cs_ba_build_system, not after cs_ba_optimize) and the estimates.  *n_bad = number of non-finite values (0 = clean); report (may be NULL) receives one
  * line per offending array naming the first offending vertex / edge in the caller's indices.  With CS_BA_DEBUG_NAN=1 in the
  * environment the library runs the scan itself after every linearisation, solve and update and prints the report to stderr.
  * cs_ba_dump / cs_ba_load: the complete problem (vertices with their CURRENT estimates and fixed flags, all four edge lists, robust

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import ba_stepwise
 from cube_slam_wu_amd import capi, synth_ba
 from oracle import ba_oracle_py as O
 
@@ -1253,48 +1254,10 @@ def test_stepwise_abi_driven_like_g2o_levenberg():
     B = capi.ba_from_dict(pr)       # one-shot reference
     n_b = B.optimize(6)
     chi_b, lam_b, tr_b = B.history()
-    cams, cubs, pts = (np.asarray(pr[k], float).copy() for k in ("cams", "cuboids", "points"))
-    lam, ni, n_bad = -1.0, 2.0, 0
-    chis, lams, trials = [], [], []
-    for it in range(6):
-        A.set_estimates(cams, cubs, pts)                 # adapter: upload_estimates() in buildSystem()
-        cur = A.compute_errors()
-        ini = tmp = cur
-        A.build_system()
-        if it == 0:
-            hc, ho, hp = A.vertex_hessians()
-            md = max(np.abs(np.einsum("kii->ki", hc)).max(), np.abs(np.einsum("kii->ki", ho)).max(), np.abs(np.einsum("kii->ki", hp)).max())
-            lam = 1e-5 * md
-            assert np.all(hc[np.asarray(pr["cam_fixed"]) != 0] == 0)      # fixed vertices carry no block
-        rho, q = 0.0, 0
-        while True:
-            A.push()
-            ok, _ = A.solve(lam)
-            b, x = A.system_vectors()
-            A.update()
-            tmp = A.compute_errors()
-            if not ok:
-                tmp = np.finfo(float).max
-            scale = float(np.dot(x, lam * x + b)) + 1e-3
-            rho = (cur - tmp) / scale
-            if rho > 0 and np.isfinite(tmp):
-                lam *= max(1.0 / 3.0, min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0))
-                ni = 2.0
-                cur = tmp
-            else:
-                lam *= ni
-                ni *= 2
-                A.pop()
-            q += 1
-            if not (rho < 0 and q < 10):
-                break
-        cams, cubs, pts = A.state()                      # g2o keeps the estimates on its side between iterations
-        chis.append(cur); lams.append(lam); trials.append(q)
-        if q == 10 or rho == 0:
-            break
-        n_bad = n_bad + 1 if (ini - cur) * 1e3 < ini else 0
-        if n_bad >= 3:
-            break
+    r = ba_stepwise.run(A, 6, (pr["cams"], pr["cuboids"], pr["points"]))
+    chis, lams, trials = r["chi2"], r["lam"], r["trials"]
+    hc, ho, hp = r["first_hessians"]
+    assert np.all(hc[np.asarray(pr["cam_fixed"]) != 0] == 0)      # fixed vertices carry no block
     assert len(chis) == n_b and trials == list(tr_b)
     assert np.allclose(chis, chi_b, rtol=1e-9) and np.allclose(lams, lam_b, rtol=1e-9)
     # (the estimates make a host round trip per iteration -- re-normalised quaternions -- and the cuboid / odometry Jacobians are
