@@ -416,7 +416,15 @@ class Batch:
 # ------------------------------------------------------------------ Path B: bundle adjustment ----------
 class CsBaTiming(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("errors_ms", "linearize_ms", "reduce_ms", "schur_ms", "factor_ms", "backsub_ms", "update_ms", "total_ms")] + \
-               [("n_linearizations", C.c_longlong), ("n_solves", C.c_longlong), ("linearize_bytes", C.c_longlong), ("schur_entries", C.c_longlong)]
+               [("n_linearizations", C.c_longlong), ("n_solves", C.c_longlong), ("linearize_bytes", C.c_longlong), ("schur_entries", C.c_longlong), ("structure_ms", C.c_double)]
+
+
+class CsBaClassify(C.Structure):
+    _fields_ = [("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("depth_positive", C.c_int), ("sticky", C.c_int)]
+
+
+class CsBaRound(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("kernels_enabled", C.c_int), ("classify", CsBaClassify)]
 
 
 DECLARED_SYMBOLS += [
@@ -426,6 +434,7 @@ DECLARED_SYMBOLS += [
     "cs_ba_shard_landmark_owners", "cs_ba_get_landmark_owners", "cs_ba_shard_info", "cs_ba_shard_timing", "cs_ba_append_vertices", "cs_ba_append_edges_proj", "cs_ba_append_edges_cuboid", "cs_ba_append_edges_cuboid_proj", "cs_ba_append_edges_odom", "cs_ba_get_vertex_hessians", "cs_ba_schur_layout", "cs_ba_structure_digest", "cs_ba_reduced_size", "cs_ba_solver_path", "cs_ba_band_order", "cs_ba_comm_unique_id", "cs_ba_comm_init", "cs_ba_set_robust_kernels",
     "cs_ba_set_external_edges", "cs_ba_set_external_terms", "cs_ba_set_external_chi2", "cs_ba_set_external_callback", "cs_ba_check_finite", "cs_ba_dump", "cs_ba_load", "cs_ba_get_reduced_system", "cs_ba_set_stage_timing", "cs_ba_set_lm_params", "cs_ba_pose_marginals",
     "cs_ba_set_edges_proj_stereo", "cs_ba_append_edges_proj_stereo",
+    "cs_ba_set_edge_levels", "cs_ba_get_edge_levels", "cs_ba_set_kernels_enabled", "cs_ba_classify_edges", "cs_ba_optimize_rounds",
 ]
 
 
@@ -495,6 +504,57 @@ class BaProblem:
             return
         kind, delta = _i32(kind), _f64(delta, (-1,))
         _chk(lib().cs_ba_set_robust_kernels(self.h, int(edge_class), len(kind), _ip(kind), _dp(delta)), "cs_ba_set_robust_kernels")
+
+    # ---- edge levels, kernels switched in place, classification, rounds (ORB-SLAM2's LocalBundleAdjustment on the device)
+    def _class_count(self, edge_class):
+        return {EDGE_PROJ: self.n_proj, EDGE_PROJ_STEREO: getattr(self, "n_stereo", 0), EDGE_CUBOID: self.n_cub, EDGE_CUBOID_PROJ: getattr(self, "n_cproj", 0),
+                EDGE_ODOM: self.n_odom}[int(edge_class)]
+
+    def set_edge_levels(self, edge_class, level, n=None):
+        """Edge::setLevel over a class (cs_ba_set_edge_levels): level[k] in {0, 1} in the caller's edge order, None = all 0; n (default: the
+        class's count as this wrapper has seen it) must equal the library's count."""
+        lv = np.ascontiguousarray(np.asarray(level, np.uint8).ravel()) if level is not None else None
+        n = int(n) if n is not None else (len(lv) if lv is not None else self._class_count(edge_class))
+        _chk(lib().cs_ba_set_edge_levels(self.h, int(edge_class), n, lv.ctypes.data_as(C.POINTER(C.c_ubyte)) if lv is not None else None), "cs_ba_set_edge_levels")
+
+    def edge_levels(self, edge_class, n=None):
+        """The class's levels in the caller's edge order (cs_ba_get_edge_levels)."""
+        n = int(n) if n is not None else self._class_count(edge_class)
+        out = np.zeros(max(1, n), np.uint8)
+        _chk(lib().cs_ba_get_edge_levels(self.h, int(edge_class), n, out.ctypes.data_as(C.POINTER(C.c_ubyte))), "cs_ba_get_edge_levels")
+        return out[:n]
+
+    def set_kernels_enabled(self, edge_class, enabled):
+        """setRobustKernel(0) over a class, and back, without forgetting the deltas or touching the structure (cs_ba_set_kernels_enabled)."""
+        _chk(lib().cs_ba_set_kernels_enabled(self.h, int(edge_class), 1 if enabled else 0), "cs_ba_set_kernels_enabled")
+
+    def classify_edges(self, chi2_mono=5.991, chi2_stereo=7.815, depth_positive=True, sticky=False, want_chi2=False):
+        """cs_ba_classify_edges at the current estimates -> (n_outliers mono, stereo) [, chi2 mono, chi2 stereo in the caller's order]."""
+        p = CsBaClassify(float(chi2_mono), float(chi2_stereo), 1 if depth_positive else 0, 1 if sticky else 0)
+        cnt = (C.c_int * 2)()
+        cm = np.zeros(max(1, self.n_proj)) if want_chi2 else None
+        cs_ = np.zeros(max(1, getattr(self, "n_stereo", 0))) if want_chi2 else None
+        _chk(lib().cs_ba_classify_edges(self.h, C.byref(p), cnt, _dp(cm) if want_chi2 else None, _dp(cs_) if want_chi2 else None), "cs_ba_classify_edges")
+        n = (int(cnt[0]), int(cnt[1]))
+        return (n, cm[:self.n_proj], cs_[:getattr(self, "n_stereo", 0)]) if want_chi2 else n
+
+    def optimize_rounds(self, rounds, cap=64):
+        """cs_ba_optimize_rounds: rounds = [(iterations, kernels_enabled, (chi2_mono, chi2_stereo, depth_positive, sticky) or None), ...];
+        -> (iterations done per round, n_outliers (n_rounds, 2)); rounds_history() has the per-round chi2 / lambda / trials."""
+        nr = len(rounds)
+        arr = (CsBaRound * max(1, nr))()
+        for r, (its, ke, cl) in enumerate(rounds):
+            cl = cl if cl is not None else (0.0, 0.0, 0, 0)
+            arr[r] = CsBaRound(int(its), 1 if ke else 0, CsBaClassify(float(cl[0]), float(cl[1]), int(cl[2]), int(cl[3])))
+        done, nout = np.zeros(max(1, nr), np.int32), np.zeros((max(1, nr), 2), np.int32)
+        self._rchi, self._rlam, self._rtr = np.zeros((max(1, nr), cap)), np.zeros((max(1, nr), cap)), np.zeros((max(1, nr), cap), np.int32)
+        _chk(lib().cs_ba_optimize_rounds(self.h, arr, nr, _ip(done), _ip(nout), _dp(self._rchi), _dp(self._rlam), _ip(self._rtr), int(cap)), "cs_ba_optimize_rounds")
+        self._rdone = done[:nr].copy()
+        return self._rdone, nout[:nr].copy()
+
+    def rounds_history(self):
+        """[(chi2, lambda, trials) of round r] after optimize_rounds."""
+        return [(self._rchi[r, :n].copy(), self._rlam[r, :n].copy(), self._rtr[r, :n].copy()) for r, n in enumerate(self._rdone)]
 
     # ---- external (host-evaluated) edges
     def set_external_edges(self, class_i, idx_i, class_j, idx_j):

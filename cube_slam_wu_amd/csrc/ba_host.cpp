@@ -339,6 +339,20 @@ struct cs_ba {
   std::vector<double> rd_cub3, rd_cproj, rd_odom;
   DBuf<int> d_pm_rk, d_cm_rk, d_ce_rk, d_oe_rk;
   DBuf<double> d_ce_rdelta, d_oe_rdelta;
+  int rk_off = 0;                    // cs_ba_set_kernels_enabled: bit (1 << cs_edge_class) set = the class's kernels are switched off (BaView::rk_off)
+  // Edge levels (OptimizableGraph::Edge::setLevel; cs_ba_set_edge_levels / cs_ba_classify_edges).  The master copy per class, in the caller's edge
+  // order; empty = every edge of the class at level 0.  On the device a projection edge's level is the sign of its width record in both edge orders
+  // (ba_kernels.hip: edge_off) plus d_lvl, one byte per edge in e_pt's order (mono edges, then stereo), which exists only once a level may be 1; a
+  // cuboid / odometry edge's level is folded into d_ce_active / d_oe_active (h_ce_shard / h_oe_shard keep the sharding's own words).
+  // lvl_host_stale: cs_ba_classify_edges wrote d_lvl on the device and the host vectors have not been refreshed from it yet.
+  std::vector<unsigned char> lvl_mono, lvl_stereo, lvl_cub3, lvl_cproj, lvl_odom;
+  DBuf<unsigned char> d_lvl;
+  bool lvl_on_device = false, lvl_host_stale = false;
+  int lvl_nM = 0, lvl_nS = 0;        // d_lvl's layout: the class counts of the structure phase that filled it
+  std::vector<int> h_ce_shard, h_oe_shard;
+  DBuf<int> d_pm_cm, d_cls_counts;   // point-major -> camera-major slot (the inverse of cm_pm, built for the first classification of a structure); [mono, stereo] outlier counters
+  bool pm_cm_valid = false;
+  DBuf<double> d_cls_chi;            // the classification's per-edge plain chi2, when the caller asks for it
   // external (host-evaluated) edges: the coupling pattern of the binary ones (structure), the terms of the current linearisation
   int ext_n = 0;
   std::vector<int> ext_e4;                       // (class_i, idx_i, class_j, idx_j) per edge; idx_j < 0: unary
@@ -480,10 +494,46 @@ void landmark_owners(int n_ranks, int n_cams, int n_points, int n_proj, const in
   for (int p = 0; p < n_points; p++) owner[p] = (first[p] == 0x7fffffff) ? 0 : cam_rank(first[p], n_cams, n_ranks);
 }
 
+// the host's level vectors from the device's bytes, after a classification there (the layout is that of the structure phase that filled d_lvl)
+int refresh_levels_host(cs_ba* B) {
+  if (!B->lvl_host_stale) return CS_OK;
+  const size_t nM = (size_t)B->lvl_nM, nS = (size_t)B->lvl_nS;
+  std::vector<unsigned char> all(nM + nS);
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
+  if (!all.empty()) CS_HIP_TRY(hipMemcpy(all.data(), B->d_lvl.p, all.size(), hipMemcpyDeviceToHost));
+  B->lvl_mono.assign(all.begin(), all.begin() + nM);
+  B->lvl_stereo.assign(all.begin() + nM, all.end());
+  B->lvl_host_stale = false;
+  return CS_OK;
+}
+bool any_level(const std::vector<unsigned char>& l) { for (unsigned char c : l) if (c) return true; return false; }
+// the projection edges' levels in e_pt's order (nM mono, nS stereo; a class's vector may be shorter -- appended edges are at level 0 -- or empty)
+bool combined_proj_levels(const cs_ba* B, int nM, int nS, std::vector<unsigned char>& out) {
+  if (!any_level(B->lvl_mono) && !any_level(B->lvl_stereo)) return false;
+  out.assign((size_t)nM + nS, 0);
+  std::copy(B->lvl_mono.begin(), B->lvl_mono.begin() + std::min<size_t>(B->lvl_mono.size(), nM), out.begin());
+  std::copy(B->lvl_stereo.begin(), B->lvl_stereo.begin() + std::min<size_t>(B->lvl_stereo.size(), nS), out.begin() + nM);
+  return true;
+}
+// d_ce_active / d_oe_active = the sharding's words with the levels folded in
+void fold_pose_levels(const cs_ba* B, std::vector<int>& ca, std::vector<int>& oa) {
+  ca = B->h_ce_shard; oa = B->h_oe_shard;
+  for (size_t k = 0; k < ca.size(); k++) {
+    const size_t n3 = (size_t)B->n_cub3;
+    const bool off = k < n3 ? (k < B->lvl_cub3.size() && B->lvl_cub3[k]) : (k - n3 < B->lvl_cproj.size() && B->lvl_cproj[k - n3]);
+    if (off) ca[k] = 0;
+  }
+  for (size_t k = 0; k < oa.size(); k++) if (k < B->lvl_odom.size() && B->lvl_odom[k]) oa[k] = 0;
+}
+
 int finalize_structure(cs_ba* B) {
   if (!B->structure_dirty) return CS_OK;
+  struct Clock { cs_ba* b; double t0; ~Clock() { b->tm.structure_ms += now_ms() - t0; } } clock{B, now_ms()};
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));             // nothing of an earlier call may still read the buffers (or the staging arena) reused below
+  { const int rl = refresh_levels_host(B); if (rl) return rl; }      // (levels a classification left on the device survive this phase through the host's copy)
+  B->pm_cm_valid = false;
   { const int rc0 = B->stage.begin((size_t)8 << 20); if (rc0) return rc0; }
   static const bool prof = getenv("CS_BA_PROF") != nullptr;   // diagnostics: host phase clock of the structure phase
   double t_ph = now_ms();
@@ -1113,7 +1163,15 @@ int finalize_structure(cs_ba* B) {
       cs::ba_launch_gather_rows(src_uv, B->d_src.p, E, 2, B->pm_uv.p, B->st);
       if (per_info) cs::ba_launch_gather_rows(src_info, B->d_src.p, E, 4, B->pm_info.p, B->st);
       if (per_intr) cs::ba_launch_gather_rows(src_intr, B->d_src.p, E, 4, B->pm_intr.p, B->st);
-      if (have_hub) cs::ba_launch_gather_rows(src_huber, B->d_src.p, E, 1, B->pm_huber.p, B->st);   // (else: zeros from the allocation)
+      // the width records: widths <= 0 (no kernel) as +0.0, the sign bit = the edge's level (ba_kernels.hip: edge_off); levels exist -> their
+      // bytes in e_pt's order go up first (the only per-edge upload a level costs, and only here)
+      const unsigned char* lvl_dev = nullptr;
+      {
+        std::vector<unsigned char> lv;
+        B->lvl_on_device = combined_proj_levels(B, nM, nS, lv);
+        if (B->lvl_on_device) { ER(B->d_lvl.upload(lv)); lvl_dev = B->d_lvl.p; B->lvl_nM = nM; B->lvl_nS = nS; }
+      }
+      if (have_hub || lvl_dev) cs::ba_launch_gather_widths(have_hub ? src_huber : nullptr, B->d_src.p, lvl_dev, E, B->pm_huber.p, B->st);   // (else: zeros from the allocation)
       cs::ba_launch_gather_rows(B->pm_uv.p, B->cm_pm.p, E, 2, B->cm_uv.p, B->st);
       if (per_info) cs::ba_launch_gather_rows(B->pm_info.p, B->cm_pm.p, E, 4, B->cm_info.p, B->st);
       if (per_intr) cs::ba_launch_gather_rows(B->pm_intr.p, B->cm_pm.p, E, 4, B->cm_intr.p, B->st);
@@ -1417,6 +1475,9 @@ int finalize_structure(cs_ba* B) {
       for (int o = 0; o < no; o++) mine[o] = cub_owner[o] == B->shard_rank;
       UP(B->d_cub_mine, mine);
     }
+    B->h_ce_shard = ca; B->h_oe_shard = oa;
+    B->lvl_cub3.resize(any_level(B->lvl_cub3) ? (size_t)B->n_cub3 : 0); B->lvl_cproj.resize(any_level(B->lvl_cproj) ? (size_t)(B->n_cub - B->n_cub3) : 0); B->lvl_odom.resize(any_level(B->lvl_odom) ? (size_t)B->n_odom : 0);
+    fold_pose_levels(B, ca, oa);      // (a level-1 edge gives zero blocks and no chi2, like an edge of another rank)
     UP(B->d_ce_active, ca); UP(B->d_oe_active, oa);
   }
   {   // kernels of the camera-cuboid edges (EdgeSE3Cuboid list, then EdgeSE3CuboidProj list) and of the odometry edges
@@ -1516,6 +1577,7 @@ int finalize_structure(cs_ba* B) {
   v.cub_mine = B->d_cub_mine.p;
   v.cub_M = B->cub_M.p; v.cub_Dinv = B->cub_Dinv.p; v.elim_fail = B->d_elim_fail.p; v.slotE_ptr = B->d_slotE_ptr.p; v.slotE_idx = B->d_slotE_idx.p;
   v.n_proj = E; v.pm_pt = B->pm_pt.p; v.pm_cam = B->pm_cam.p; v.pm_uv = B->pm_uv.p; v.pm_info = B->pm_info.p; v.pm_intr = B->pm_intr.p; v.pm_huber = B->pm_huber.p;
+  v.rk_off = B->rk_off;
   v.pm_rk = B->d_pm_rk.p; v.cm_rk = B->d_cm_rk.p; v.ce_rk = B->d_ce_rk.p; v.ce_rdelta = B->d_ce_rdelta.p; v.oe_rk = B->d_oe_rk.p; v.oe_rdelta = B->d_oe_rdelta.p;
   v.pt_ptr = B->pt_ptr.p; v.cm_pm = B->cm_pm.p; v.cm_pt = B->cm_pt.p; v.cm_uv = B->cm_uv.p; v.cm_info = B->cm_info.p; v.cm_intr = B->cm_intr.p; v.cm_huber = B->cm_huber.p; v.cam_ptr = B->cam_ptr.p;
   v.n_cub3 = B->n_cub3; v.pe_meas = B->pe_meas.p; v.pe_info = B->pe_info.p; v.pe_K = B->pe_K.p;
@@ -1970,6 +2032,7 @@ void cs_ba_destroy(cs_ba* B) {
                      &B->d_elim_fail, &B->d_slotE_ptr, &B->d_slotE_idx, &B->d_cub_mine, &B->d_sep_off, &B->d_sep_col, &B->d_int_info, &B->d_sep_info, &B->d_pm_rk, &B->d_cm_rk, &B->d_ce_rk, &B->d_oe_rk, &B->d_ext_e4, &B->d_ext_order, &B->d_ext_gptr, &B->d_src, &B->sp_ndim, &B->sp_ncol, &B->sp_sptr, &B->sp_srow, &B->sp_sroff, &B->sp_prow, &B->sp_rbase, &B->sp_rent, &B->sp_rptr, &B->sp_rcol, &B->sp_rpos,
                      &B->sp_order, &B->sp_info, &B->sp_tcol, &B->d_pm_kind, &B->d_cm_kind};
   for (auto* d : di) d->release();
+  B->d_lvl.release(); B->d_pm_cm.release(); B->d_cls_counts.release(); B->d_cls_chi.release();
   B->sp_poff.release(); B->sp_done.release(); B->sp_xdone.release();
   B->d_info.release(); B->d_band_info.release();
   for (auto& e : B->ev) if (e) (void)hipEventDestroy(e);
@@ -2182,6 +2245,8 @@ static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* 
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
   int rc;
+  if ((rc = refresh_levels_host(B))) return rc;
+  B->lvl_mono.clear();                            // (a new list: every edge at level 0; the stereo edges keep theirs)
   scan_uniform_records(B, true, info4, intr4, n);
   if ((rc = B->raw_uv.upload_ptr(uv, 2 * (size_t)n))) return rc;
   B->raw_info_virtual = B->info_uniform; B->raw_intr_virtual = B->intr_uniform;
@@ -2207,6 +2272,8 @@ static int stereo_edges_add(cs_ba* B, bool replace, int n, const int* pt, const 
   if (!replace && n == 0) return CS_OK;
   if (!replace && B->n_stereo > 0 && (huber != nullptr) != !B->h_se_huber.empty()) { cs_set_error("cs_ba_append_edges_proj_stereo: Huber deltas must be given for all stereo edges or for none"); return CS_ERR_INVALID_ARG; }
   if (replace) {
+    if (int rl = refresh_levels_host(B)) return rl;
+    B->lvl_stereo.clear();
     B->e_pt.resize(B->e_pt.size() - B->n_stereo); B->e_cam.resize(B->e_cam.size() - B->n_stereo);
     B->n_proj -= B->n_stereo; B->n_stereo = 0;
     B->h_se_uv.clear(); B->h_se_ur.clear(); B->h_se_intr.clear(); B->h_se_sinfo.clear(); B->h_se_huber.clear(); B->rk_stereo.clear();
@@ -2238,7 +2305,7 @@ int cs_ba_append_edges_proj_stereo(cs_ba* B, int n, const int* pt, const int* ca
 static int cs_ba_set_edges_cuboid_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
   if (!B || n < 0 || (n && (!cam || !cub || !meas10 || !info81))) return CS_ERR_INVALID_ARG;
   B->u3_cam.assign(cam, cam + n); B->u3_cub.assign(cub, cub + n);
-  B->rk_cub3.clear(); B->rd_cub3.clear();
+  B->rk_cub3.clear(); B->rd_cub3.clear(); B->lvl_cub3.clear();
   B->h_ce_meas.assign(meas10, meas10 + 10 * (size_t)n); B->h_ce_info.assign(info81, info81 + 81 * (size_t)n);
   B->structure_dirty = true;
   return CS_OK;
@@ -2252,7 +2319,7 @@ int cs_ba_set_edges_cuboid(cs_ba* B, int n, const int* cam, const int* cub, cons
 static int cs_ba_set_edges_cuboid_proj_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
   if (!B || n < 0 || (n && (!cam || !cub || !meas4 || !info16 || !K9))) return CS_ERR_INVALID_ARG;
   B->up_cam.assign(cam, cam + n); B->up_cub.assign(cub, cub + n);
-  B->rk_cproj.clear(); B->rd_cproj.clear();
+  B->rk_cproj.clear(); B->rd_cproj.clear(); B->lvl_cproj.clear();
   B->h_pe_meas.assign(meas4, meas4 + 4 * (size_t)n); B->h_pe_info.assign(info16, info16 + 16 * (size_t)n); B->h_pe_K.assign(K9, K9 + 9 * (size_t)n);
   B->structure_dirty = true;
   return CS_OK;
@@ -2267,7 +2334,7 @@ static int cs_ba_set_edges_odom_impl(cs_ba* B, int n, const int* ci, const int* 
   if (!B || n < 0 || (n && (!ci || !cj || !meas7 || !info36))) return CS_ERR_INVALID_ARG;
   B->n_odom = n;
   B->oe_i.assign(ci, ci + n); B->oe_j.assign(cj, cj + n);
-  B->rk_odom.clear(); B->rd_odom.clear();
+  B->rk_odom.clear(); B->rd_odom.clear(); B->lvl_odom.clear();
   B->h_oe_meas.assign(meas7, meas7 + 7 * (size_t)n);
   for (int k = 0; k < n; k++) { cs::Pose p = cs::pose_load(&B->h_oe_meas[7 * (size_t)k]); cs::pose_normalize(p); cs::pose_store(p, &B->h_oe_meas[7 * (size_t)k]); }
   B->h_oe_info.assign(info36, info36 + 36 * (size_t)n);
@@ -2366,6 +2433,145 @@ int cs_ba_set_robust_kernels(cs_ba* B, int edge_class, int n, const int* kind, c
   CS_GUARD_BEGIN
   return cs_ba_set_robust_kernels_impl(B, edge_class, n, kind, delta);
   CS_GUARD_END("cs_ba_set_robust_kernels")
+}
+
+static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap);
+// ---- edge levels, kernels switched in place, classification, rounds: ORB-SLAM2's LocalBundleAdjustment / BundleAdjustment on the device ----------
+static int class_count(const cs_ba* B, int edge_class) {
+  return edge_class == CS_EDGE_PROJ ? B->n_proj - B->n_stereo : edge_class == CS_EDGE_PROJ_STEREO ? B->n_stereo : edge_class == CS_EDGE_CUBOID ? (int)B->u3_cam.size()
+         : edge_class == CS_EDGE_CUBOID_PROJ ? (int)B->up_cam.size() : edge_class == CS_EDGE_ODOM ? B->n_odom : -1;
+}
+static std::vector<unsigned char>* class_levels(cs_ba* B, int edge_class) {
+  return edge_class == CS_EDGE_PROJ ? &B->lvl_mono : edge_class == CS_EDGE_PROJ_STEREO ? &B->lvl_stereo : edge_class == CS_EDGE_CUBOID ? &B->lvl_cub3 : edge_class == CS_EDGE_CUBOID_PROJ ? &B->lvl_cproj : &B->lvl_odom;
+}
+static int levels_refuse_shard(const cs_ba* B, const char* who) {
+  if (B->shard_n <= 1) return CS_OK;
+  cs_set_error(std::string(who) + ": edge levels are not supported on a sharded handle");
+  return CS_ERR_INVALID_ARG;
+}
+// the host's projection levels into a finished structure: the bytes in e_pt's order, the signs of the width records in both edge orders
+static int push_proj_levels(cs_ba* B) {
+  const int nS = B->n_stereo, nM = B->n_proj - nS, E = B->slot_src_n;
+  std::vector<unsigned char> lv;
+  const bool any = combined_proj_levels(B, nM, nS, lv);
+  if (!any && !B->lvl_on_device) return CS_OK;       // (nothing on the device to take back)
+  if (!any) lv.assign((size_t)nM + nS, 0);
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
+  int rc = B->d_lvl.upload(lv); if (rc) return rc;
+  B->lvl_nM = nM; B->lvl_nS = nS;
+  cs::ba_launch_relabel_widths(B->pm_huber.p, B->d_src.p, B->d_lvl.p, E, B->st);
+  cs::ba_launch_gather_rows(B->pm_huber.p, B->cm_pm.p, E, 1, B->cm_huber.p, B->st);
+  CS_HIP_TRY(hipGetLastError());
+  B->lvl_on_device = any;
+  return CS_OK;
+}
+static int push_pose_levels(cs_ba* B) {
+  std::vector<int> ca, oa;
+  fold_pose_levels(B, ca, oa);
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
+  if (!ca.empty()) CS_HIP_TRY(hipMemcpy(B->d_ce_active.p, ca.data(), sizeof(int) * ca.size(), hipMemcpyHostToDevice));
+  if (!oa.empty()) CS_HIP_TRY(hipMemcpy(B->d_oe_active.p, oa.data(), sizeof(int) * oa.size(), hipMemcpyHostToDevice));
+  return CS_OK;
+}
+static int cs_ba_set_edge_levels_impl(cs_ba* B, int edge_class, int n, const unsigned char* level) {
+  if (!B) return CS_ERR_INVALID_ARG;
+  if (int rs = levels_refuse_shard(B, "cs_ba_set_edge_levels")) return rs;
+  const int have = class_count(B, edge_class);
+  if (have < 0) { cs_set_error("cs_ba_set_edge_levels: unknown edge class"); return CS_ERR_INVALID_ARG; }
+  if (n != have) { cs_set_error("cs_ba_set_edge_levels: n must equal the number of edges of the class"); return CS_ERR_INVALID_ARG; }
+  for (int k = 0; k < n && level; k++) if (level[k] > 1) { cs_set_error("cs_ba_set_edge_levels: a level is 0 or 1"); return CS_ERR_INVALID_ARG; }
+  CS_HIP_TRY(hipSetDevice(B->device));
+  int rc = refresh_levels_host(B); if (rc) return rc;
+  std::vector<unsigned char>& l = *class_levels(B, edge_class);
+  if (level) l.assign(level, level + n); else l.clear();
+  B->have_system = false;          // (the system on the device is the old active set's)
+  if (B->structure_dirty) return CS_OK;      // (the structure phase that is due applies them)
+  return (edge_class == CS_EDGE_PROJ || edge_class == CS_EDGE_PROJ_STEREO) ? push_proj_levels(B) : push_pose_levels(B);
+}
+int cs_ba_set_edge_levels(cs_ba* B, int edge_class, int n, const unsigned char* level) {
+  CS_GUARD_BEGIN
+  return cs_ba_set_edge_levels_impl(B, edge_class, n, level);
+  CS_GUARD_END("cs_ba_set_edge_levels")
+}
+int cs_ba_get_edge_levels(cs_ba* B, int edge_class, int n, unsigned char* level) {
+  CS_GUARD_BEGIN
+  if (!B || (n && !level)) return CS_ERR_INVALID_ARG;
+  const int have = class_count(B, edge_class);
+  if (have < 0) { cs_set_error("cs_ba_get_edge_levels: unknown edge class"); return CS_ERR_INVALID_ARG; }
+  if (n != have) { cs_set_error("cs_ba_get_edge_levels: n must equal the number of edges of the class"); return CS_ERR_INVALID_ARG; }
+  int rc = refresh_levels_host(B); if (rc) return rc;
+  const std::vector<unsigned char>& l = *class_levels(B, edge_class);
+  for (int k = 0; k < n; k++) level[k] = (size_t)k < l.size() ? l[k] : 0;
+  return CS_OK;
+  CS_GUARD_END("cs_ba_get_edge_levels")
+}
+int cs_ba_set_kernels_enabled(cs_ba* B, int edge_class, int enabled) {
+  if (!B || class_count(B, edge_class) < 0) return CS_ERR_INVALID_ARG;
+  const int bit = 1 << edge_class, now = enabled ? (B->rk_off & ~bit) : (B->rk_off | bit);
+  if (now != B->rk_off) B->have_system = false;
+  B->rk_off = now;
+  B->view.rk_off = now;            // (a scalar of the kernels' argument block: no upload, no structure phase)
+  return CS_OK;
+}
+static int cs_ba_classify_edges_impl(cs_ba* B, const cs_ba_classify* p, int n_outliers[2], double* chi2_mono, double* chi2_stereo) {
+  if (!B || !p) return CS_ERR_INVALID_ARG;
+  if (int rs = levels_refuse_shard(B, "cs_ba_classify_edges")) return rs;
+  CS_HIP_TRY(hipSetDevice(B->device));
+  int rc = finalize_structure(B); if (rc) return rc;
+  const int nS = B->n_stereo, nM = B->n_proj - nS, E = B->slot_src_n;
+  const bool want_chi = chi2_mono || chi2_stereo;
+  if (!B->lvl_on_device) {      // the first level of this structure: its bytes, all 0
+    if ((rc = B->d_lvl.alloc((size_t)nM + nS, B->st))) return rc;
+    B->lvl_nM = nM; B->lvl_nS = nS; B->lvl_on_device = true;
+  }
+  if (!B->pm_cm_valid) {
+    if ((rc = B->d_pm_cm.reserve((size_t)E))) return rc;
+    B->d_pm_cm.n = (size_t)E;
+    cs::ba_launch_invert_perm(B->cm_pm.p, E, B->d_pm_cm.p, B->st);
+    B->pm_cm_valid = true;
+  }
+  if ((rc = B->d_cls_counts.alloc(2, B->st))) return rc;
+  if (want_chi && (rc = B->d_cls_chi.alloc((size_t)nM + nS, B->st))) return rc;
+  cs::BaClassify a{};
+  a.thr_mono = p->chi2_mono; a.thr_stereo = p->chi2_stereo; a.depth_positive = p->depth_positive; a.sticky = p->sticky;
+  a.pm_huber = B->pm_huber.p; a.cm_huber = B->cm_huber.p; a.pm_cm = B->d_pm_cm.p; a.src = B->d_src.p; a.lvl = B->d_lvl.p; a.n_mono = nM;
+  a.counts = B->d_cls_counts.p; a.chi_out = want_chi ? B->d_cls_chi.p : nullptr;
+  cs::ba_launch_classify(B->view, a, B->st);
+  CS_HIP_TRY(hipGetLastError());
+  int cnt[2] = {0, 0};
+  CS_HIP_TRY(hipMemcpyAsync(cnt, B->d_cls_counts.p, sizeof(cnt), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));
+  if (chi2_mono && nM) CS_HIP_TRY(hipMemcpy(chi2_mono, B->d_cls_chi.p, 8 * (size_t)nM, hipMemcpyDeviceToHost));
+  if (chi2_stereo && nS) CS_HIP_TRY(hipMemcpy(chi2_stereo, B->d_cls_chi.p + nM, 8 * (size_t)nS, hipMemcpyDeviceToHost));
+  if (n_outliers) { n_outliers[0] = cnt[0]; n_outliers[1] = cnt[1]; }
+  if (p->chi2_mono > 0 || p->chi2_stereo > 0) { B->lvl_host_stale = true; B->have_system = false; }
+  return CS_OK;
+}
+int cs_ba_classify_edges(cs_ba* B, const cs_ba_classify* p, int n_outliers[2], double* chi2_mono, double* chi2_stereo) {
+  CS_GUARD_BEGIN
+  return cs_ba_classify_edges_impl(B, p, n_outliers, chi2_mono, chi2_stereo);
+  CS_GUARD_END("cs_ba_classify_edges")
+}
+int cs_ba_optimize_rounds(cs_ba* B, const cs_ba_round* rounds, int n_rounds, int* iterations_done, int* n_outliers, double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap) {
+  CS_GUARD_BEGIN
+  if (!B || n_rounds < 0 || (n_rounds && !rounds) || hist_cap < 0) return CS_ERR_INVALID_ARG;
+  if (int rs = levels_refuse_shard(B, "cs_ba_optimize_rounds")) return rs;
+  for (int r = 0; r < n_rounds; r++) if (rounds[r].iterations < 0) return CS_ERR_INVALID_ARG;
+  for (int r = 0; r < n_rounds; r++) {
+    int rc = cs_ba_set_kernels_enabled(B, CS_EDGE_PROJ, rounds[r].kernels_enabled); if (rc) return rc;
+    if ((rc = cs_ba_set_kernels_enabled(B, CS_EDGE_PROJ_STEREO, rounds[r].kernels_enabled))) return rc;
+    const size_t off = (size_t)r * hist_cap;
+    int done = 0;
+    rc = cs_ba_optimize_sharded_impl(B, rounds[r].iterations, nullptr, nullptr, &done, chi2_hist ? chi2_hist + off : nullptr, lambda_hist ? lambda_hist + off : nullptr,
+                                     trials_hist ? trials_hist + off : nullptr, hist_cap);
+    if (rc) return rc;
+    if (iterations_done) iterations_done[r] = done;
+    int cnt[2] = {-1, -1};
+    if (rounds[r].classify.chi2_mono > 0 || rounds[r].classify.chi2_stereo > 0) { rc = cs_ba_classify_edges_impl(B, &rounds[r].classify, cnt, nullptr, nullptr); if (rc) return rc; }
+    if (n_outliers) { n_outliers[2 * r] = cnt[0]; n_outliers[2 * r + 1] = cnt[1]; }
+  }
+  return CS_OK;
+  CS_GUARD_END("cs_ba_optimize_rounds")
 }
 
 static int cs_ba_compute_errors_impl(cs_ba* B, double* chi2) {
@@ -2482,6 +2688,9 @@ int cs_ba_pop(cs_ba* B) {
 int cs_ba_set_shard(cs_ba* B, int rank, int n_ranks) {
   if (!B || n_ranks < 1 || rank < 0 || rank >= n_ranks) return CS_ERR_INVALID_ARG;
   if (B->n_stereo > 0 && n_ranks > 1) { cs_set_error("cs_ba_set_shard: stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
+  if (n_ranks > 1 && (B->lvl_host_stale || any_level(B->lvl_mono) || any_level(B->lvl_stereo) || any_level(B->lvl_cub3) || any_level(B->lvl_cproj) || any_level(B->lvl_odom))) {
+    cs_set_error("cs_ba_set_shard: edge levels are not supported on a sharded handle"); return CS_ERR_INVALID_ARG;
+  }
   B->shard_rank = rank; B->shard_n = n_ranks;
   B->structure_dirty = true;
   return CS_OK;
@@ -3085,6 +3294,8 @@ int cs_ba_structure_digest(cs_ba* B, unsigned long long* out, int cap, int* n_ta
   for (int t = 0; t < nt && t < cap; t++) {
     h.resize(tabs[t]->n);
     if (tabs[t]->n) CS_HIP_TRY(hipMemcpy(h.data(), tabs[t]->p, sizeof(int) * tabs[t]->n, hipMemcpyDeviceToHost));
+    // (the last two tables are the sharding's activity words: an edge's level is folded into the device's copy and is no part of the structure)
+    if (t >= nt - 2) { const std::vector<int>& sh = t == nt - 2 ? B->h_ce_shard : B->h_oe_shard; std::copy(sh.begin(), sh.begin() + std::min(sh.size(), h.size()), h.begin()); }
     unsigned long long f = 1469598103934665603ull ^ (unsigned long long)tabs[t]->n;
     for (int v : h) { f ^= (unsigned)v; f *= 1099511628211ull; }
     out[t] = f;
@@ -3155,7 +3366,16 @@ static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_
   DBuf<double> chi; DBuf<int> out;
   struct Free { DBuf<double>* a; DBuf<int>* b; ~Free() { a->release(); b->release(); } } guard{&chi, &out};
   if ((rc = chi.alloc(std::max(1, n_edges), B->st))) return rc;
-  cs::ba_launch_edge_chi(v, chi.p, B->st);
+  // (level-0 edges only: a level-1 edge is outside the active set and may well be non-finite)
+  DBuf<unsigned char> lce, loe;
+  struct FreeL { DBuf<unsigned char>* a; DBuf<unsigned char>* b; ~FreeL() { a->release(); b->release(); } } guard_l{&lce, &loe};
+  if (any_level(B->lvl_cub3) || any_level(B->lvl_cproj)) {
+    std::vector<unsigned char> l((size_t)B->n_cub, 0);
+    for (size_t k = 0; k < l.size(); k++) { const size_t n3 = (size_t)B->n_cub3; l[k] = k < n3 ? (k < B->lvl_cub3.size() && B->lvl_cub3[k]) : (k - n3 < B->lvl_cproj.size() && B->lvl_cproj[k - n3]); }
+    if ((rc = lce.upload(l))) return rc;
+  }
+  if (any_level(B->lvl_odom)) { std::vector<unsigned char> l(B->lvl_odom); l.resize((size_t)B->n_odom, 0); if ((rc = loe.upload(l))) return rc; }
+  cs::ba_launch_edge_chi(v, chi.p, B->st, lce.p, loe.p);
   struct Arr { const char* name; const double* p; long long n; int per; const char* owner; };
   std::vector<Arr> arrs = {
     {"squared error of a projection edge", chi.p, E, 1, "projection edge (caller's index)"},
@@ -3218,6 +3438,7 @@ static void debug_nan_scan(cs_ba* B, const char* where) {
 // then the arrays in the order written below, each raw little-endian.  Shard settings and external edges are not part of it.
 namespace {
 struct DumpHeader { char magic[8]; int v[16]; };
+struct LevelTrailer { char magic[8]; int rk_off; int n[5]; };      // optional, behind the arrays: levels of CS_EDGE_PROJ, _PROJ_STEREO, _CUBOID, _CUBOID_PROJ, _ODOM (n[i] = 0: all at level 0)
 template <class T> bool wr(FILE* f, const std::vector<T>& a) { return a.empty() || fwrite(a.data(), sizeof(T), a.size(), f) == a.size(); }
 template <class T> bool rd(FILE* f, std::vector<T>& a, size_t n) { a.resize(n); return n == 0 || fread(a.data(), sizeof(T), n, f) == n; }
 }  // namespace
@@ -3225,6 +3446,7 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   if (!B || !path) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
+  { const int rl = refresh_levels_host(B); if (rl) return rl; }
   const int nst = B->n_stereo, np_e = B->n_proj - nst, n3 = (int)B->u3_cam.size(), n4 = (int)B->up_cam.size(), n6 = B->n_odom;
   std::vector<double> cams(7 * (size_t)B->nc), cubs(10 * (size_t)B->no), pts(3 * (size_t)B->np), uv(2 * (size_t)np_e), info(4 * (size_t)np_e), intr(4 * (size_t)np_e), hub(B->have_huber ? np_e : 0);
   auto d2h = [&](std::vector<double>& h, const double* d) -> int { if (!h.empty()) CS_HIP_TRY(hipMemcpy(h.data(), d, 8 * h.size(), hipMemcpyDeviceToHost)); return CS_OK; };
@@ -3248,6 +3470,24 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   ok = ok && wr(f, B->oe_i) && wr(f, B->oe_j) && wr(f, B->h_oe_meas) && wr(f, B->h_oe_info) && wr(f, B->rk_odom) && wr(f, B->rd_odom);
   // (the stereo projection edges last: a graph without one dumps the bytes it always did)
   ok = ok && wr(f, s_pt) && wr(f, s_cam) && wr(f, B->h_se_uv) && wr(f, B->h_se_ur) && wr(f, B->h_se_intr) && wr(f, B->h_se_sinfo) && wr(f, B->h_se_huber) && wr(f, B->rk_stereo);
+  // (edge levels and kernel switches behind everything else, and only when there is one: a handle without them dumps the bytes it always did)
+  {
+    const int cls[5] = {CS_EDGE_PROJ, CS_EDGE_PROJ_STEREO, CS_EDGE_CUBOID, CS_EDGE_CUBOID_PROJ, CS_EDGE_ODOM};
+    bool any = B->rk_off != 0;
+    for (int c : cls) any = any || any_level(*class_levels(B, c));
+    if (any) {
+      LevelTrailer T{};
+      std::memcpy(T.magic, "CSLV0001", 8);
+      T.rk_off = B->rk_off;
+      std::vector<unsigned char> lv[5];
+      for (int i = 0; i < 5; i++) {
+        if (any_level(*class_levels(B, cls[i]))) { lv[i] = *class_levels(B, cls[i]); lv[i].resize((size_t)class_count(B, cls[i]), 0); }
+        T.n[i] = (int)lv[i].size();
+      }
+      ok = ok && fwrite(&T, sizeof(T), 1, f) == 1;
+      for (int i = 0; i < 5; i++) ok = ok && wr(f, lv[i]);
+    }
+  }
   ok = (fclose(f) == 0) && ok;
   if (!ok) { cs_set_error(std::string("cs_ba_dump: write to ") + path + " failed"); return CS_ERR_INVALID_ARG; }
   return CS_OK;
@@ -3276,6 +3516,15 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   ok = ok && rd(f, oi, n6) && rd(f, oj, n6) && rd(f, m7, 7 * (size_t)n6) && rd(f, i36, 36 * (size_t)n6) && rd(f, rk6, nrk6) && rd(f, rd6, nrk6);
   std::vector<int> spt, scam, rks; std::vector<double> suv, sur, sintr, ssinfo, shub;
   ok = ok && rd(f, spt, nst) && rd(f, scam, nst) && rd(f, suv, 2 * (size_t)nst) && rd(f, sur, nst) && rd(f, sintr, 4 * (size_t)nst) && rd(f, ssinfo, 10 * (size_t)nst) && rd(f, shub, sth ? nst : 0) && rd(f, rks, nrks);
+  LevelTrailer LT{};
+  std::vector<unsigned char> lv[5];
+  bool have_levels = false;
+  if (ok && fread(&LT, sizeof(LT), 1, f) == 1) {
+    have_levels = true;
+    const int cnt5[5] = {npe, nst, n3, n4, n6};
+    ok = std::memcmp(LT.magic, "CSLV0001", 8) == 0;
+    for (int i = 0; i < 5 && ok; i++) ok = (LT.n[i] == 0 || LT.n[i] == cnt5[i]) && rd(f, lv[i], (size_t)LT.n[i]);
+  }
   if (!ok || (nrks && nrks != nst) || (nrk && nrk != npe) || (nrk3 && nrk3 != n3) || (nrk4 && nrk4 != n4) || (nrk6 && nrk6 != n6)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
   cs_ba* B = nullptr;
   int rc = cs_ba_create(device, &B); if (rc) return rc;
@@ -3301,6 +3550,13 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   if (n6 && (rc = cs_ba_set_edges_odom(B, n6, oi.data(), oj.data(), m7.data(), i36.data()))) return rc;
   if (n6) B->h_oe_meas = m7;
   if (nrk6 && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_ODOM, n6, rk6.data(), rd6.data()))) return rc;
+  if (have_levels) {
+    const int cls[5] = {CS_EDGE_PROJ, CS_EDGE_PROJ_STEREO, CS_EDGE_CUBOID, CS_EDGE_CUBOID_PROJ, CS_EDGE_ODOM};
+    for (int i = 0; i < 5; i++) {
+      if (LT.n[i] && (rc = cs_ba_set_edge_levels(B, cls[i], LT.n[i], lv[i].data()))) return rc;
+      if ((LT.rk_off >> cls[i]) & 1) { if ((rc = cs_ba_set_kernels_enabled(B, cls[i], 0))) return rc; }
+    }
+  }
   *out = B;
   g.b = nullptr;
   return CS_OK;

@@ -37,9 +37,23 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // rho, rho' of a projection edge's squared error (cs_robust.h): Huber-or-none from the delta alone, any kernel through the kind array
-__device__ __forceinline__ void proj_rho(const int* rk, int k, double delta, double e, double& rho0, double& rho1) {
-  if (rk) robust_rho(rk[k], delta, e, rho0, rho1); else huber_rho(e, delta, rho0, rho1);
+// (off: the class's kernels are switched off in place, cs_ba_set_kernels_enabled -- the RK_NONE branch, whatever the records hold)
+__device__ __forceinline__ void proj_rho(const int* rk, int k, double delta, bool off, double e, double& rho0, double& rho1) {
+  if (off) { rho0 = e; rho1 = 1.0; }
+  else if (rk) robust_rho(rk[k], delta, e, rho0, rho1);
+  else huber_rho(e, delta, rho0, rho1);
 }
+// An edge's level (OptimizableGraph::Edge::setLevel, core/optimizable_graph.h) rides in the SIGN BIT of its kernel-width record (pm_huber /
+// cm_huber, widths are >= +0.0 otherwise): the kernels already read that record, so a graph without a level-1 edge reads nothing more and computes
+// what it always did.  A level-1 edge is outside the active set: every site that evaluates an edge SELECTS zeros for it before the projection is
+// used -- its point may sit at depth 0 or behind the camera, and 0 * inf must not reach a sum.
+__device__ __forceinline__ bool edge_off(double width_record) { return __double2hiint(width_record) < 0; }
+// The select of the linearising sites (proj_linearize / proj_linearize_any): a level-1 edge's camera-frame point is replaced by (0, 0, 1) BEFORE it is
+// projected, so its error and Jacobians are finite whatever the estimates are, and its rho' and chi2 are then selected to zero -- Omega and -Omega e are
+// weighted by an exact 0 and every product the callers form from the ProjLin is an exact (signed) zero.  Selects, not an early return with a zeroed
+// ProjLin: a second exit made the compiler keep the camera-frame point in scratch memory in every kernel that inlines these functions, and zeroing the
+// error as well cost ba_lin_schur_kernel<1, true> and <5, false> a wavefront of occupancy (169 and 257 registers against the steps at 168 and 256).
+__device__ __forceinline__ void level1_point(bool off, double* pc) { if (off) { pc[0] = 0.0; pc[1] = 0.0; pc[2] = 1.0; } }
 
 struct ProjLin {
   double e[2];     // error
@@ -50,9 +64,14 @@ struct ProjLin {
   double chi;      // rho0
 };
 
-__device__ __forceinline__ void proj_linearize(const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k, ProjLin& L) {
+__device__ __forceinline__ void proj_linearize(const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k, int rk_off, ProjLin& L) {
+  // (proj_error's arithmetic, with the level's select between its two steps)
   double pc[3];
-  proj_error(T, X, uv, intr, L.e, pc);
+  pose_map(T, X, pc);
+  const bool off = edge_off(huber);
+  level1_point(off, pc);
+  L.e[0] = uv[0] - (pc[0] / pc[2] * intr[0] + intr[2]);
+  L.e[1] = uv[1] - (pc[1] / pc[2] * intr[1] + intr[3]);
   double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z, fx = intr[0], fy = intr[1];
   double tmp[6] = {fx, 0, -x / z * fx, 0, fy, -y / z * fy};
 #pragma unroll
@@ -68,7 +87,8 @@ __device__ __forceinline__ void proj_linearize(const Pose& T, const double* R, c
   L.Jc[6] = (1 + y * y / z_2) * fy; L.Jc[7] = -x * y / z_2 * fy; L.Jc[8] = -x / z * fy; L.Jc[9] = 0; L.Jc[10] = -1. / z * fy; L.Jc[11] = y / z_2 * fy;
   double c = L.e[0] * (info[0] * L.e[0] + info[1] * L.e[1]) + L.e[1] * (info[2] * L.e[0] + info[3] * L.e[1]);
   double rho1;
-  proj_rho(rk, k, huber, c, L.chi, rho1);
+  proj_rho(rk, k, huber, (rk_off & RK_OFF_MONO) != 0, c, L.chi, rho1);
+  if (off) { rho1 = 0.0; L.chi = 0.0; }
 #pragma unroll
   for (int i = 0; i < 4; i++) L.Wm[i] = rho1 * info[i];
   L.r[0] = -(info[0] * L.e[0] + info[1] * L.e[1]) * rho1;
@@ -99,10 +119,12 @@ __device__ __forceinline__ double quad3(const double* e, const double* info) {
 // Stereo: the error with its single-precision invz / bf (cs_se3.h), the point Jacobian in ITS form (:247-257: -fx R(0,j) / z + fx x R(2,j) / z^2,
 // not the mono edge's -1/z * tmp * R), row 2 of both Jacobians (:255-257, :273-278), all double.  Mono: proj_linearize's arithmetic, row 2 zero.
 // Then the weights of constructQuadraticForm (base_binary_edge.hpp:54-120).
-__device__ __forceinline__ void proj_linearize_any(bool stereo, const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k,
+__device__ __forceinline__ void proj_linearize_any(bool stereo, const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k, int rk_off,
                                                    double ur, const double* srec, ProjLin3& L) {
   double pc[3];
   pose_map(T, X, pc);
+  const bool off = edge_off(huber);
+  level1_point(off, pc);
   const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z, fx = intr[0], fy = intr[1];
   L.Jc[0] = x * y / z_2 * fx; L.Jc[1] = -(1 + (x * x / z_2)) * fx; L.Jc[2] = y / z * fx; L.Jc[3] = -1. / z * fx; L.Jc[4] = 0; L.Jc[5] = x / z_2 * fx;
   L.Jc[6] = (1 + y * y / z_2) * fy; L.Jc[7] = -x * y / z_2 * fy; L.Jc[8] = -x / z * fy; L.Jc[9] = 0; L.Jc[10] = -1. / z * fy; L.Jc[11] = y / z_2 * fy;
@@ -148,7 +170,8 @@ __device__ __forceinline__ void proj_linearize_any(bool stereo, const Pose& T, c
   // (a mono edge: the zeros of row / column 2 add nothing -- e^T Omega e, rho' Omega and -rho' Omega e are the 2 x 2 ones)
   c = quad3(L.e, W);
   double rho1;
-  proj_rho(rk, k, huber, c, L.chi, rho1);
+  proj_rho(rk, k, huber, (rk_off & (stereo ? RK_OFF_STEREO : RK_OFF_MONO)) != 0, c, L.chi, rho1);
+  if (off) { rho1 = 0.0; L.chi = 0.0; }
 #pragma unroll
   for (int i = 0; i < 9; i++) L.Wm[i] = rho1 * W[i];
 #pragma unroll
@@ -194,13 +217,14 @@ template <bool STEREO>
 __device__ __forceinline__ void chi2_proj_block(const BaView& v, int bid, int nblocks, double* ws) {
   double acc = 0;
   for (int k = bid * 256 + threadIdx.x; k < v.n_proj; k += nblocks * 256) {
+    if (edge_off(v.pm_huber[k])) continue;      // level 1: no share in chi2, its error never formed
     Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
     if constexpr (STEREO) {
       if (v.pm_kind[k]) {
         double e3[3], pc3[3], rho0, rho1;
         const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
         stereo_proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.pm_ur[k], v.intr_u ? v.intr_u : v.pm_intr + 4 * k, srec[9], e3, pc3);
-        proj_rho(v.pm_rk, k, v.pm_huber[k], quad3(e3, srec), rho0, rho1);
+        proj_rho(v.pm_rk, k, v.pm_huber[k], (v.rk_off & RK_OFF_STEREO) != 0, quad3(e3, srec), rho0, rho1);
         acc += rho0;
         continue;
       }
@@ -210,7 +234,7 @@ __device__ __forceinline__ void chi2_proj_block(const BaView& v, int bid, int nb
     const double* info = v.info_u ? v.info_u : v.pm_info + 4 * k;
     double c = e[0] * (info[0] * e[0] + info[1] * e[1]) + e[1] * (info[2] * e[0] + info[3] * e[1]);
     double rho0, rho1;
-    proj_rho(v.pm_rk, k, v.pm_huber[k], c, rho0, rho1);
+    proj_rho(v.pm_rk, k, v.pm_huber[k], (v.rk_off & RK_OFF_MONO) != 0, c, rho0, rho1);
     acc += rho0;
   }
   acc = wave_sum(acc);
@@ -237,14 +261,14 @@ __device__ __forceinline__ void chi2_pose_edges_wave(const BaView& v, int partia
     double e[9];
     if (v.ce_active[k]) cuboid_edge_error(pose_load(v.cams + 7 * v.ce_cam[k]), cube_load(v.cubes + 10 * v.ce_cub[k]), cube_load(v.ce_meas + 10 * k), e);
     if (v.ce_active[k]) c = quad_form(e, v.ce_info + 81 * k, 9);
-    if (v.ce_active[k] && v.ce_rk && v.ce_rk[k]) { double r1; robust_rho(v.ce_rk[k], v.ce_rdelta[k], c, c, r1); }
+    if (v.ce_active[k] && v.ce_rk && v.ce_rk[k] && !(v.rk_off & RK_OFF_CUB3)) { double r1; robust_rho(v.ce_rk[k], v.ce_rdelta[k], c, c, r1); }
   } else if (k < v.n_cub) {
     const int q = k - v.n_cub3;
     double e[4];
     if (v.ce_active[k]) {
       cuboid_proj_error(pose_load(v.cams + 7 * v.ce_cam[k]), cube_load(v.cubes + 10 * v.ce_cub[k]), v.pe_K + 9 * (size_t)q, v.pe_meas + 4 * (size_t)q, e);
       c = quad_form(e, v.pe_info + 16 * (size_t)q, 4);
-      if (v.ce_rk && v.ce_rk[k]) { double r1; robust_rho(v.ce_rk[k], v.ce_rdelta[k], c, c, r1); }
+      if (v.ce_rk && v.ce_rk[k] && !(v.rk_off & RK_OFF_CPROJ)) { double r1; robust_rho(v.ce_rk[k], v.ce_rdelta[k], c, c, r1); }
     }
   } else if (k < v.n_cub + v.n_odom) {
     int q = k - v.n_cub;
@@ -252,7 +276,7 @@ __device__ __forceinline__ void chi2_pose_edges_wave(const BaView& v, int partia
     if (v.oe_active[q]) {
       odom_edge_error(pose_load(v.cams + 7 * v.oe_i[q]), pose_load(v.cams + 7 * v.oe_j[q]), pose_load(v.oe_meas + 7 * q), e);
       c = quad_form(e, v.oe_info + 36 * q, 6);
-      if (v.oe_rk && v.oe_rk[q]) { double r1; robust_rho(v.oe_rk[q], v.oe_rdelta[q], c, c, r1); }
+      if (v.oe_rk && v.oe_rk[q] && !(v.rk_off & RK_OFF_ODOM)) { double r1; robust_rho(v.oe_rk[q], v.oe_rdelta[q], c, c, r1); }
     }
   }
   c = wave_sum(c);
@@ -326,13 +350,13 @@ __global__ __launch_bounds__(256) void ba_lin_cam_kernel(BaView v) {
   for (int k = e0 + threadIdx.x; k < e1; k += 256) {
     if constexpr (STEREO) {
       ProjLin3 L3;
-      proj_linearize_any(v.cm_kind[k] != 0, T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k,
+      proj_linearize_any(v.cm_kind[k] != 0, T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k, v.rk_off,
                          v.cm_ur[k], stereo_rec(v.sinfo_u, v.cm_sinfo, (size_t)k), L3);
       lin3_cam_terms(L3, A, b);
       continue;
     }
     ProjLin L;
-    proj_linearize(T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k, L);
+    proj_linearize(T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k, v.rk_off, L);
     // JW = Jc^T W (6x2)
     int q = 0;
 #pragma unroll
@@ -381,7 +405,7 @@ __device__ __forceinline__ void lin_pt_edge(const BaView& v, int k, bool free_pt
   pose_rotmat(T, R);
   if constexpr (STEREO) {
     ProjLin3 L3;
-    proj_linearize_any(v.pm_kind[k] != 0, T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k,
+    proj_linearize_any(v.pm_kind[k] != 0, T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k, v.rk_off,
                        v.pm_ur[k], stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k), L3);
     lin3_point_terms(L3, H6, b3);
     double* Wk3 = v.W + 18 * (size_t)k;
@@ -393,7 +417,7 @@ __device__ __forceinline__ void lin_pt_edge(const BaView& v, int k, bool free_pt
     return;
   }
   ProjLin L;
-  proj_linearize(T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k, L);
+  proj_linearize(T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k, v.rk_off, L);
   double pw[6];  // Jp^T W (3x2)
 #pragma unroll
   for (int i = 0; i < 3; i++) {
@@ -607,7 +631,7 @@ __global__ __launch_bounds__(128, 3) void ba_cub_edge_kernel(BaView v, int odom_
   }
   __syncthreads();
   double w = 1.0;      // rho' of the edge's kernel at its chi2 (every lane of the edge computes the same value)
-  if (live && sgn == 0 && v.ce_rk && v.ce_rk[k]) {
+  if (live && sgn == 0 && v.ce_rk && v.ce_rk[k] && !(v.rk_off & (is3d ? RK_OFF_CUB3 : RK_OFF_CPROJ))) {
     const double c = is3d ? quad_form(J[sub][15], v.ce_info + 81 * (size_t)k, 9) : quad_form(Jq[15], v.pe_info + 16 * (size_t)(k - v.n_cub3), 4);
     double r0;
     robust_rho(v.ce_rk[k], v.ce_rdelta[k], c, r0, w);
@@ -651,7 +675,7 @@ __device__ __forceinline__ void odom_edge_block(const BaView& v, int blk, int ti
   __syncthreads();
   if (live) {
     double w = 1.0;
-    if (v.oe_rk && v.oe_rk[k]) { double r0; robust_rho(v.oe_rk[k], v.oe_rdelta[k], quad_form(J[sub][15], v.oe_info + 36 * (size_t)k, 6), r0, w); }
+    if (v.oe_rk && v.oe_rk[k] && !(v.rk_off & RK_OFF_ODOM)) { double r0; robust_rho(v.oe_rk[k], v.oe_rdelta[k], quad_form(J[sub][15], v.oe_info + 36 * (size_t)k, 6), r0, w); }
     edge_rows_from_columns<6, 6, 6>(J[sub], J[sub][15], v.oe_info + 36 * (size_t)k, d, v.oe_Hii + 36 * (size_t)k, v.oe_Hjj + 36 * (size_t)k,
                                     v.oe_Hij + 36 * (size_t)k, v.oe_bi + 6 * (size_t)k, v.oe_bj + 6 * (size_t)k, w);
   }
@@ -1023,7 +1047,7 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
       if constexpr (STEREO) {
         if (lc < ncl) {
           ProjLin3 L3;
-          proj_linearize_any(rec.kind != 0, T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, rec.ur, stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)e), L3);
+          proj_linearize_any(rec.kind != 0, T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, v.rk_off, rec.ur, stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)e), L3);
           lin3_point_terms(L3, h9, h9 + 6);
           const bool both3 = cam_free && v.pt_free[p] != 0;
 #pragma unroll
@@ -1033,7 +1057,7 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
         }
       } else if (lc < ncl) {
         ProjLin L;
-        proj_linearize(T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, L);
+        proj_linearize(T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, v.rk_off, L);
         double pw[6];  // Jp^T W (3x2)
 #pragma unroll
         for (int q = 0; q < 3; q++) {
@@ -1464,7 +1488,7 @@ __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
     double Wk[18];
     if constexpr (STEREO) {
       ProjLin3 L3;
-      proj_linearize_any(v.pm_kind[k] != 0, T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k,
+      proj_linearize_any(v.pm_kind[k] != 0, T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k, v.rk_off,
                          v.pm_ur[k], stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k), L3);
 #pragma unroll
       for (int q = 0; q < 6; q++)
@@ -1472,7 +1496,7 @@ __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
         for (int j = 0; j < 3; j++) Wk[3 * q + j] = free_pt ? lin3_hpl(L3, q, j) : 0.0;
     } else {
     ProjLin L;
-    proj_linearize(T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k, L);
+    proj_linearize(T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k, v.rk_off, L);
 #pragma unroll
     for (int q = 0; q < 6; q++) {
       const double jw0 = L.Jc[q] * L.Wm[0] + L.Jc[6 + q] * L.Wm[2];
@@ -2957,10 +2981,13 @@ void ba_launch_scan_finite(const double* p, long long n, int* out, hipStream_t s
 }
 // the edges' (un-robustified) squared errors e^T Omega e, one double per edge: projection edges (point-major order), then the
 // camera-cuboid and the odometry edges -- what a NaN in an error vector turns into
+// (a level-1 edge is not evaluated and reads as 0: projection edges by their width record's sign, the others through lvl_ce / lvl_oe, nullptr
+// while none of them is at level 1)
 template <bool STEREO>
-__global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out) {
+__global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out, const unsigned char* lvl_ce, const unsigned char* lvl_oe) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k < v.n_proj) {
+    if (edge_off(v.pm_huber[k])) { out[k] = 0.0; return; }
     Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
     if constexpr (STEREO) {
       if (v.pm_kind[k]) {
@@ -2978,6 +3005,7 @@ __global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out)
     return;
   }
   const int q = k - v.n_proj;
+  if (q < v.n_cub ? (lvl_ce && lvl_ce[q]) : (q < v.n_cub + v.n_odom && lvl_oe && lvl_oe[q - v.n_cub])) { out[k] = 0.0; return; }
   if (q < v.n_cub3) {
     double e[9];
     cuboid_edge_error(pose_load(v.cams + 7 * v.ce_cam[q]), cube_load(v.cubes + 10 * v.ce_cub[q]), cube_load(v.ce_meas + 10 * q), e);
@@ -2994,11 +3022,99 @@ __global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out)
     out[k] = quad_form(e, v.oe_info + 36 * r, 6);
   }
 }
-void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st) {
+void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st, const unsigned char* lvl_ce, const unsigned char* lvl_oe) {
   const int n = v.n_proj + v.n_cub + v.n_odom;
   if (n <= 0) return;
-  if (v.pm_kind) hipLaunchKernelGGL(ba_edge_chi_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, v, out);
-  else hipLaunchKernelGGL(ba_edge_chi_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, v, out);
+  if (v.pm_kind) hipLaunchKernelGGL(ba_edge_chi_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, v, out, lvl_ce, lvl_oe);
+  else hipLaunchKernelGGL(ba_edge_chi_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, v, out, lvl_ce, lvl_oe);
+}
+
+// ---- edge levels (OptimizableGraph::Edge::setLevel) of the projection edges: see edge_off ------------------------------------------------
+// The structure phase's gather of the width records, point-major from the caller's order: a width <= 0 (no kernel) becomes +0.0, so that the sign
+// bit is free for the level; lvl (caller's order, nullptr: every edge at level 0) sets it.  src == nullptr: no edge has a width.
+__global__ __launch_bounds__(256) void ba_gather_widths_kernel(const double* __restrict__ src, const int* __restrict__ idx, const unsigned char* __restrict__ lvl, int n, double* __restrict__ dst) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int s = idx[k];
+  const double h = src ? src[s] : 0.0;
+  const double w = h > 0 ? h : 0.0;
+  dst[k] = (lvl && lvl[s]) ? -w : w;
+}
+void ba_launch_gather_widths(const double* src, const int* idx, const unsigned char* lvl, int n, double* dst, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ba_gather_widths_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, idx, lvl, n, dst);
+}
+// new levels into the point-major width records of a finished structure (cs_ba_set_edge_levels): the widths stay, the signs follow lvl
+__global__ __launch_bounds__(256) void ba_relabel_widths_kernel(double* __restrict__ pm_huber, const int* __restrict__ idx, const unsigned char* __restrict__ lvl, int n) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const double w = fabs(pm_huber[k]);
+  pm_huber[k] = lvl[idx[k]] ? -w : w;
+}
+void ba_launch_relabel_widths(double* pm_huber, const int* idx, const unsigned char* lvl, int n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ba_relabel_widths_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pm_huber, idx, lvl, n);
+}
+__global__ __launch_bounds__(256) void ba_invert_perm_kernel(const int* __restrict__ perm, int n, int* __restrict__ inv) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k < n) inv[perm[k]] = k;
+}
+void ba_launch_invert_perm(const int* perm, int n, int* inv, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ba_invert_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, perm, n, inv);
+}
+// cs_ba_classify_edges: ORB-SLAM2's outlier test between the rounds of LocalBundleAdjustment / BundleAdjustment (e->chi2() > 5.991 / 7.815 ||
+// !e->isDepthPositive() -> setLevel(1)), one lane per projection edge over the point-major list at the current estimates.  Plain chi2 = e^T Omega e
+// (the stereo error with its single-precision invz / bf: stereo_proj_error); depth = (T.map(X)).z, the test `not > 0` so that a NaN depth is out.
+// sticky: a level-1 edge is not tested (and not evaluated unless its chi2 is asked for).  A changed level is written to the width record's sign
+// in both edge orders and to the caller-order byte array; per class the lanes at level 1 afterwards are counted by ballot, one atomic per wavefront.
+template <bool STEREO>
+__global__ __launch_bounds__(256) void ba_classify_kernel(BaView v, BaClassify a) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  bool stereo = false, out = false;
+  if (k < v.n_proj) {
+    if constexpr (STEREO) stereo = v.pm_kind[k] != 0;
+    const double h = a.pm_huber[k], thr = stereo ? a.thr_stereo : a.thr_mono;
+    const bool was = edge_off(h), test = thr > 0 && !(a.sticky && was);
+    out = was;
+    if (test || a.chi_out) {
+      const Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
+      const double* intr = v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k;
+      double chi, pc[3];
+      if (stereo) {
+        double e3[3];
+        const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
+        stereo_proj_error(T, v.points + 3 * (size_t)v.pm_pt[k], v.pm_uv + 2 * (size_t)k, v.pm_ur[k], intr, srec[9], e3, pc);
+        chi = quad3(e3, srec);
+      } else {
+        double e[2];
+        proj_error(T, v.points + 3 * (size_t)v.pm_pt[k], v.pm_uv + 2 * (size_t)k, intr, e, pc);
+        const double* info = v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k;
+        chi = e[0] * (info[0] * e[0] + info[1] * e[1]) + e[1] * (info[2] * e[0] + info[3] * e[1]);
+      }
+      const int s = a.src[k];
+      if (a.chi_out) a.chi_out[s] = chi;
+      if (test) {
+        out = chi > thr || (a.depth_positive && !(pc[2] > 0));
+        if (out != was) {
+          const double w = fabs(h), hn = out ? -w : w;
+          a.pm_huber[k] = hn;
+          a.cm_huber[a.pm_cm[k]] = hn;
+        }
+        a.lvl[s] = out ? 1 : 0;
+      }
+    }
+  }
+  const unsigned long long bm = __ballot(out && !stereo), bs = __ballot(out && stereo);
+  if ((threadIdx.x & 63) == 0) {
+    if (bm) atomicAdd(a.counts, __popcll(bm));
+    if (bs) atomicAdd(a.counts + 1, __popcll(bs));
+  }
+}
+void ba_launch_classify(const BaView& v, const BaClassify& a, hipStream_t st) {
+  if (v.n_proj <= 0) return;
+  if (v.pm_kind) hipLaunchKernelGGL(ba_classify_kernel<true>, dim3((unsigned)((v.n_proj + 255) / 256)), dim3(256), 0, st, v, a);
+  else hipLaunchKernelGGL(ba_classify_kernel<false>, dim3((unsigned)((v.n_proj + 255) / 256)), dim3(256), 0, st, v, a);
 }
 
 // ---- external (host-evaluated) edges: cs_ba_set_external_edges / cs_ba_set_external_terms ---------------------------------------

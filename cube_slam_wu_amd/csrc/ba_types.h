@@ -51,6 +51,9 @@ struct BaView {
   // robust kernels (cs_robust.h).  Projection edges: pm_huber / cm_huber hold RobustKernel::delta(); pm_rk / cm_rk the kernel kind, or
   // nullptr when every projection edge has Huber or none (then delta > 0 means Huber -- the common case keeps its 8-byte record)
   const int* pm_rk; const int* cm_rk;
+  // a class's kernels switched off in place (cs_ba_set_kernels_enabled: ORB-SLAM2's setRobustKernel(0) over a class): bit RK_OFF_* set -> that
+  // class's edges take the RK_NONE branch whatever their records hold; the records, the structure and the uploads stay as they are
+  int rk_off;
   // ---- stereo projection edges (EdgeStereoSE3ProjectXYZ: 3-dim error u_left, v, u_right) --------------
   // They sit in the same two edge lists as the mono edges (the structure phase sees (landmark, camera) only); pm_uv / pm_intr / pm_huber /
   // pm_rk hold their (u_left, v), (fx fy cx cy), kernel width and kind.  What a mono edge does not have lives in the arrays below, ALL nullptr
@@ -116,6 +119,15 @@ struct BaView {
 // a side stream the prologue runs THERE, in front of it, and the landmark segments' kernel takes lambda by value -- nothing on the main stream
 // reads what the prologue writes before the streams join, so its launch leaves the trial's chain.
 struct BaSidePrologue { double* d_lam; double lam0, lam1; int* info24; int* elim_fail; double* S; size_t n_clear; };
+enum { RK_OFF_MONO = 1 << 0, RK_OFF_CUB3 = 1 << 1, RK_OFF_CPROJ = 1 << 2, RK_OFF_ODOM = 1 << 3, RK_OFF_STEREO = 1 << 4 };   // 1 << cs_edge_class
+// cs_ba_classify_edges on the device (ba_classify_kernel): thresholds on the plain chi2 per projection class (<= 0: the class keeps its levels),
+// the depth test, the sticky rule; the width records in both edge orders, the point-major -> camera-major map, the levels in the caller's order
+// (e_pt's: mono edges, then stereo), the per-class counters [mono, stereo] and the optional plain chi2 per edge in the caller's order
+struct BaClassify {
+  double thr_mono, thr_stereo; int depth_positive, sticky;
+  double* pm_huber; double* cm_huber; const int* pm_cm; const int* src; unsigned char* lvl; int n_mono;
+  int* counts; double* chi_out;
+};
 enum { BA_SEG_LM = 32, BA_FUSED_KMAX = 13, BA_LONG_KMAX = 64, BA_ELIM_MAX_SLOTS = 64 };   // (6 k + 1 <= 80 rows = five tiles: 15 accumulator tiles per wavefront)
 
 CS_HD double* ba_S_at(const BaView& v, int r, int c) {  // requires r >= c (and r - c < band_ld in band mode)
@@ -159,6 +171,10 @@ void ba_launch_trial_prologue(double* d_lam, double lam0, double lam1, int* info
 void ba_launch_ext_add(const BaView& v, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3, hipStream_t st);
 void ba_launch_ext_offdiag(const BaView& v, int n_groups, const int* gptr, const int* order, const int* e4, const double* Hij, hipStream_t st);
 void ba_launch_scan_finite(const double* p, long long n, int* out, hipStream_t st);
-void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st);
+void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st, const unsigned char* lvl_ce = nullptr, const unsigned char* lvl_oe = nullptr);
+void ba_launch_gather_widths(const double* src, const int* idx, const unsigned char* lvl, int n, double* dst, hipStream_t st);
+void ba_launch_relabel_widths(double* pm_huber, const int* idx, const unsigned char* lvl, int n, hipStream_t st);
+void ba_launch_invert_perm(const int* perm, int n, int* inv, hipStream_t st);
+void ba_launch_classify(const BaView& v, const BaClassify& a, hipStream_t st);
 
 }  // namespace cs

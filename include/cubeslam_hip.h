@@ -304,6 +304,47 @@ enum cs_robust_kernel { CS_RK_NONE = 0, CS_RK_HUBER = 1, CS_RK_PSEUDO_HUBER = 2,
 enum cs_edge_class { CS_EDGE_PROJ = 0, CS_EDGE_CUBOID = 1, CS_EDGE_CUBOID_PROJ = 2, CS_EDGE_ODOM = 3, CS_EDGE_PROJ_STEREO = 4 };
 int cs_ba_set_robust_kernels(cs_ba* ba, int edge_class, int n, const int* kind, const double* delta);
 
+/* Edge levels (OptimizableGraph::Edge::setLevel, core/optimizable_graph.h; SparseOptimizer::initializeOptimization(0) then takes the level-0
+ * edges as the active set).  Every edge of a device-evaluated class has a level, 0 or 1.  A level-1 edge has no share in chi2
+ * (activeRobustChi2), in H, b, the H_pl blocks and the Schur products, in computeLambdaInit's maximum and in LM's scale term; it is never
+ * evaluated, so its point may sit at depth 0 or behind its camera.  The STRUCTURE stays the full graph's: levels never run the structure
+ * phase, cs_ba_structure_digest, the orderings, the Schur schedule and the solver path do not change, and a vertex whose edges are all at
+ * level 1 keeps its column, gets lambda I on its diagonal and a zero increment (g2o leaves it out of the active set; it moves as little).
+ * cs_ba_set_edge_levels: level[k] of the class's edges in the caller's order, n = the class's edge count, level == NULL: all 0.
+ * cs_ba_get_edge_levels: the same array back (refreshed from the device after a cs_ba_classify_edges there).  Levels survive
+ * cs_ba_append_* (appended edges are at level 0) and the structure phase that follows; cs_ba_set_edges_* of a class resets that class to 0.
+ * A change of levels leaves no linear system (cs_ba_solve, cs_ba_get_system ... return CS_ERR_NOT_RUN until cs_ba_compute_errors +
+ * cs_ba_build_system).  cs_ba_check_finite scans level-0 edges only; cs_ba_get_system's Hpl18 rows of level-1 edges are zero; cs_ba_dump
+ * stores levels and kernel switches when there is one (a handle without them dumps the bytes it always did).  Host-evaluated external
+ * edges are not touched.  Not available on a sharded handle (CS_ERR_INVALID_ARG, as for stereo edges).                                   */
+int cs_ba_set_edge_levels(cs_ba* ba, int edge_class, int n, const unsigned char* level);
+int cs_ba_get_edge_levels(cs_ba* ba, int edge_class, int n, unsigned char* level);
+/* ORB-SLAM2's `e->setRobustKernel(0)` over a class, and back: enabled = 0 makes every edge of the class take the no-kernel branch (rho = e,
+ * rho' = 1) from the next evaluation on; the deltas and kinds are kept, nothing is uploaded and the structure phase does not run (unlike
+ * cs_ba_set_robust_kernels(class, kind = NULL), which forgets them and rebuilds).  enabled = 1 brings the class's kernels back.          */
+int cs_ba_set_kernels_enabled(cs_ba* ba, int edge_class, int enabled);
+/* The outlier test ORB-SLAM2 runs between and after the rounds of LocalBundleAdjustment / BundleAdjustment (Optimizer.cc: `if (e->chi2() >
+ * 5.991 || !e->isDepthPositive()) e->setLevel(1)`, 7.815 for stereo edges), on the device at the handle's current estimates: a projection edge
+ * goes to level 1 if its plain chi2 = e^T Omega e (no kernel; the stereo error with its single-precision invz / bf) exceeds its class's
+ * threshold, or -- depth_positive != 0 -- if (T.map(X)).z is not > 0; otherwise to level 0.  A threshold <= 0 leaves that class's levels
+ * alone.  sticky = 1: only level-0 edges are tested, an outlier stays out (LocalBundleAdjustment); sticky = 0: every edge is tested and may
+ * return (PoseOptimization's convention, cs_pose_optimize_batch).  n_outliers[0 / 1] (may be NULL) = mono / stereo edges at level 1 after the
+ * call; chi2_mono / chi2_stereo (either may be NULL) receive every edge's plain chi2 in the caller's order -- per-edge data crosses to the
+ * host only when asked for.  Deviation from g2o: e->chi2() after optimize() is the error of the last TRIAL (the returned state whenever that
+ * trial was accepted); here it is always the returned state's.                                                                            */
+typedef struct cs_ba_classify { double chi2_mono, chi2_stereo; int depth_positive; int sticky; } cs_ba_classify;
+int cs_ba_classify_edges(cs_ba* ba, const cs_ba_classify* p, int n_outliers[2], double* chi2_mono, double* chi2_stereo);
+/* Rounds over one graph, ORB-SLAM2's LocalBundleAdjustment in one call: per round cs_ba_set_kernels_enabled(both projection classes,
+ * kernels_enabled), then exactly cs_ba_optimize(iterations) (lambda initialised anew, as SparseOptimizer::optimize does), then
+ * cs_ba_classify_edges(classify) unless both of its thresholds are <= 0.  No structure phase and no per-edge host traffic between the
+ * rounds.  LocalBundleAdjustment (optimize(5) with Huber kernels; setLevel(1) on outliers, setRobustKernel(0); initializeOptimization(0),
+ * optimize(10); final classification) is {5, 1, {5.991, 7.815, 1, 1}}, {10, 0, {5.991, 7.815, 1, 0}}.  iterations_done: n_rounds;
+ * n_outliers: n_rounds x 2 (-1, -1 for a round without classification); the histories: n_rounds x hist_cap each; all may be NULL.  The
+ * kernel switch of the last round stays in force after the call.                                                                         */
+typedef struct cs_ba_round { int iterations; int kernels_enabled; cs_ba_classify classify; } cs_ba_round;
+int cs_ba_optimize_rounds(cs_ba* ba, const cs_ba_round* rounds, int n_rounds, int* iterations_done, int* n_outliers,
+                          double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap);
+
 /* External (host-evaluated) edges: the CPU path for edge types the library does not evaluate -- what g2o's BlockSolver does for
  * EVERY edge, kept for the ones that have no kernel here.  The caller runs such an edge through its own virtuals (computeError,
  * linearizeOplus(JacobianWorkspace&), constructQuadraticForm: core/optimizable_graph.h:394-454; the numeric default of linearizeOplus:
@@ -480,6 +521,7 @@ typedef struct cs_ba_timing {
   long long n_linearizations, n_solves;
   long long linearize_bytes;        /* algorithmic bytes of one linearisation + Schur build */
   long long schur_entries;          /* sum over landmarks of k_j (k_j + 1) / 2                           */
+  double structure_ms;              /* host time of the structure phases run so far (0 more while the graph's structure is final) */
 } cs_ba_timing;
 int cs_ba_last_timing(cs_ba* ba, cs_ba_timing* t);
 /* The stage split above (errors / linearize / reduce / factor / backsub _ms) is g2o's G2OBatchStatistics (core/batch_stats.h:48-62) and, like
