@@ -1006,3 +1006,117 @@ def pose_optimize_batch(batch, params=None, device=0):
     rc, out = _pose_call(lib().cs_pose_optimize_batch, (int(device),), batch, params)
     _chk(rc, "cs_pose_optimize_batch")
     return out
+
+
+DECLARED_SYMBOLS += ["cs_pgo_create", "cs_pgo_destroy", "cs_pgo_set_vertices", "cs_pgo_set_estimates", "cs_pgo_set_edges", "cs_pgo_set_lm_params", "cs_pgo_chi2",
+                     "cs_pgo_linearize_edges", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
+
+
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ubyte)) if a is not None else None
+
+
+class PoseGraph:
+    """cs_pgo handle: Sim(3) keyframe vertices, EdgeSim3 links, Levenberg-Marquardt (Optimizer::OptimizeEssentialGraph's graph).
+    States are qx qy qz qw tx ty tz s, world-to-keyframe."""
+
+    def __init__(self, sim8, fixed=None, fix_scale=None, device=0):
+        self.h = C.c_void_p()
+        _chk(lib().cs_pgo_create(int(device), C.byref(self.h)), "cs_pgo_create")
+        self.nv = self.ne = 0
+        self.hist = None
+        self.set_vertices(sim8, fixed, fix_scale)
+
+    def set_vertices(self, sim8, fixed=None, fix_scale=None):
+        s = _f64(sim8, (-1, 8))
+        fx = np.ascontiguousarray(np.asarray(fixed, np.uint8).ravel()) if fixed is not None else None
+        fs = np.ascontiguousarray(np.asarray(fix_scale, np.uint8).ravel()) if fix_scale is not None else None
+        if (fx is not None and len(fx) != len(s)) or (fs is not None and len(fs) != len(s)):
+            raise ValueError("one flag per vertex")
+        _chk(lib().cs_pgo_set_vertices(self.h, len(s), _dp(s), _u8p(fx), _u8p(fs)), "cs_pgo_set_vertices")
+        self.nv, self.ne = len(s), 0
+
+    def set_estimates(self, sim8):
+        s = _f64(sim8, (self.nv, 8))
+        _chk(lib().cs_pgo_set_estimates(self.h, _dp(s)), "cs_pgo_set_estimates")
+
+    def set_edges(self, vi, vj, meas8, info49=None):
+        vi, vj, m = _i32(vi), _i32(vj), _f64(meas8, (-1, 8))
+        w = _f64(info49, (-1, 49)) if info49 is not None else None
+        if len(vj) != len(vi) or len(m) != len(vi) or (w is not None and len(w) != len(vi)):
+            raise ValueError("one entry per edge")
+        _chk(lib().cs_pgo_set_edges(self.h, len(vi), _ip(vi), _ip(vj), _dp(m), _dp(w) if w is not None else None), "cs_pgo_set_edges")
+        self.ne = len(vi)
+
+    def set_lm_params(self, user_lambda_init=0.0, max_trials_after_failure=10):
+        _chk(lib().cs_pgo_set_lm_params(self.h, C.c_double(user_lambda_init), int(max_trials_after_failure)), "cs_pgo_set_lm_params")
+
+    def chi2(self, each=False):
+        c = C.c_double()
+        e = np.zeros(self.ne) if each else None
+        _chk(lib().cs_pgo_chi2(self.h, C.byref(c), _dp(e) if each else None), "cs_pgo_chi2")
+        return (c.value, e) if each else c.value
+
+    def linearize_edges(self):
+        """err (E, 7), J_i, J_j (E, 7, 7; row = error component) at the current estimates."""
+        e, ji, jj = np.zeros((self.ne, 7)), np.zeros((self.ne, 7, 7)), np.zeros((self.ne, 7, 7))
+        _chk(lib().cs_pgo_linearize_edges(self.h, _dp(e), _dp(ji), _dp(jj)), "cs_pgo_linearize_edges")
+        return e, ji, jj
+
+    def optimize(self, iters, cap=64):
+        done = C.c_int()
+        chi, lam, tr = np.zeros(cap), np.zeros(cap), np.zeros(cap, np.int32)
+        _chk(lib().cs_pgo_optimize(self.h, int(iters), C.byref(done), _dp(chi), _dp(lam), _ip(tr), cap), "cs_pgo_optimize")
+        k = min(done.value, cap)
+        self.hist = (chi[:k], lam[:k], tr[:k])
+        return done.value
+
+    def history(self):
+        """chi2, lambda, LM trials of every iteration of the last optimize()."""
+        return self.hist
+
+    def vertices(self):
+        s = np.zeros((self.nv, 8))
+        _chk(lib().cs_pgo_get_vertices(self.h, _dp(s)), "cs_pgo_get_vertices")
+        return s
+
+    def se3(self):
+        t = np.zeros((self.nv, 7))
+        _chk(lib().cs_pgo_get_se3(self.h, _dp(t)), "cs_pgo_get_se3")
+        return t
+
+    def correct_points(self, ref_vertex, xyz):
+        r, x = _i32(ref_vertex), _f64(xyz, (-1, 3))
+        if len(r) != len(x):
+            raise ValueError("one reference vertex per point")
+        out = np.zeros_like(x)
+        _chk(lib().cs_pgo_correct_points(self.h, len(x), _ip(r), _dp(x), _dp(out)), "cs_pgo_correct_points")
+        return out
+
+    def solver_path(self):
+        p, f = C.c_int(), C.c_double()
+        _chk(lib().cs_pgo_solver_path(self.h, C.byref(p), C.byref(f)), "cs_pgo_solver_path")
+        return {0: "dense", 2: "sparse"}[p.value], f.value
+
+    def timing(self):
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _chk(lib().cs_pgo_last_timing(self.h, C.byref(a), C.byref(b), C.byref(c)), "cs_pgo_last_timing")
+        return dict(linearize_ms=a.value, solve_ms=b.value, total_ms=c.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().cs_pgo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pose_graph_from_dict(g, device=0):
+    """A PoseGraph from synth_pgo.ring()'s dict."""
+    G = PoseGraph(g["sim8"], g["fixed"], g["fix_scale"], device=device)
+    G.set_edges(g["vi"], g["vj"], g["meas8"], g.get("info49"))
+    return G

@@ -1694,7 +1694,7 @@ int build_system_device(cs_ba* B, hipEvent_t ev_pre = nullptr) {
 // The banded factorisation is a persistent kernel whose workgroups wait for each other: all of them must be resident.
 // One such kernel fits many times over, but an unbounded number of concurrent solves (handles on different streams of
 // one process) would not; they take turns.
-static std::mutex g_coop_mutex;
+static std::mutex& g_coop_mutex = cs::coop_mutex();   // (cs_hip_util.h: the pose-graph handle's sparse solve takes the same turn)
 // The turn is held across the collectives of a trial when they are queued on the stream (RCCL): two communicator handles in one
 // process would wait for each other (one holds the turn inside a collective, the other needs the turn to enqueue its side).  One
 // process per GPU is the contract; cs_ba_comm_init enforces it.

@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <mutex>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -29,6 +30,9 @@ void cs_set_error(const std::string& s);
     catch (const std::exception& ex) { cs_set_error(std::string(fn_name) + ": " + ex.what()); return CS_ERR_CAPACITY; }
 
 namespace cs {
+
+// the turn of the persistent solver kernels whose workgroups wait for each other (ba_host.cpp, pgo_host.cpp): one such kernel at a time per process
+inline std::mutex& coop_mutex() { static std::mutex m; return m; }
 
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 

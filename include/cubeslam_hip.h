@@ -607,6 +607,69 @@ int cs_pose_batch_optimize(cs_pose_batch* b, const cs_pose_params* p, int n_fram
  * clock (packing, the two copies and the kernel included).                                                                          */
 int cs_pose_batch_last_timing(const cs_pose_batch* b, double* kernel_ms, double* host_ms);
 
+/* ------------------------------------------------------------------ Path B'': pose-graph optimisation over Sim(3) keyframe vertices -- */
+/* Replaces the g2o graph an ORB-SLAM2-derived pipeline optimises after a loop closure (Optimizer::OptimizeEssentialGraph, NOT IN THE
+ * REFERENCE; the g2o types it uses are): one VertexSim3Expmap per keyframe (types/types_seven_dof_expmap.h:48-94; oplusImpl :60-69:
+ * update[6] = 0 under _fix_scale, estimate = exp(update) * estimate), one EdgeSim3 per spanning-tree / loop / covisibility link
+ * (:99-126; computeError :106-114: log(C S_i S_j^-1)), over Sim3 (types/sim3.h:41-285: exp :70-138, log :144-223, inverse :226-229,
+ * operator* :259-265, map :140 -- quaternion, translation and scale are never renormalised, and neither are they here).  Jacobians are
+ * BaseBinaryEdge::linearizeOplus's numeric default (core/base_binary_edge.hpp:130-205: central differences, delta = 1e-9, through
+ * oplusImpl -- a fix_scale vertex gets an exactly zero seventh column, a fixed vertex no Jacobian), the quadratic form is
+ * BaseBinaryEdge::constructQuadraticForm's without a robust kernel (:55-90), the optimiser OptimizationAlgorithmLevenberg
+ * (core/optimization_algorithm_levenberg.cpp:61-189) as cs_ba_optimize states it.  There are no marginalised vertices: H + lambda I over
+ * the free vertices' 7-blocks is solved directly, by the general sparse Cholesky of cs_ba (CS_BA_PATH_SPARSE) wherever its plan and grid
+ * accept the graph and by rocSOLVER potrf / potrs (CS_BA_PATH_DENSE) otherwise; CS_PGO_FORCE_DENSE=1 (environment, read by
+ * cs_pgo_set_edges) forces the latter.  A factorisation with a non-positive pivot makes the trial a failed one.
+ *
+ * sim3.h:116 / :192 IS KEPT AS IT IS: with |sigma| >= 1e-5 and a small rotation, B = ((0.5 sigma^2 - sigma + 1) s) / sigma^3 grows like
+ * 1 / sigma^3; in log it makes W nearly rank one for an error with a rotation under ~4.5e-3 rad and |log s| >= 1e-5, and the translation
+ * Jacobian of that edge collapses in two directions.  A free-scale graph near convergence goes through it, here as in g2o.
+ *
+ * The system is assembled densely (n x n doubles, n = 7 per free keyframe that has an edge) whichever factorisation takes it: a graph
+ * above 4 GiB of it -- MORE THAN 3 310 FREE KEYFRAMES -- is refused by cs_pgo_set_edges with CS_ERR_CAPACITY.  Two edges between the same
+ * pair of vertices, in either orientation, are refused with CS_ERR_INVALID_ARG (as cs_ba refuses a doubled projection edge): merge them
+ * into one measurement, as OptimizeEssentialGraph's sInsertedEdges does.  Every argument is checked on the host before anything is
+ * launched; no input makes a kernel read out of bounds.  Calls on one handle must not overlap.                                     */
+typedef struct cs_pgo cs_pgo;
+int  cs_pgo_create(int device, cs_pgo** out);
+void cs_pgo_destroy(cs_pgo* g);
+/* optimizer.addVertex(VertexSim3Expmap) for n >= 1 keyframes, ids 0 .. n - 1.  sim8 = qx qy qz qw tx ty tz s (Sim3::operator[] order,
+ * sim3.h:232-257), world-to-keyframe as ORB-SLAM2 stores Scw; s > 0 and every value finite.  fixed / fix_scale: one byte per vertex,
+ * setFixed / _fix_scale (NULL: none).  Drops the edges of an earlier graph.                                                        */
+int  cs_pgo_set_vertices(cs_pgo* g, int n, const double* sim8, const unsigned char* fixed, const unsigned char* fix_scale);
+/* setEstimate on every vertex: same graph, new states; they also become the "initial" states of cs_pgo_correct_points.           */
+int  cs_pgo_set_estimates(cs_pgo* g, const double* sim8);
+/* optimizer.addEdge(EdgeSim3) n >= 1 times, replacing the handle's edges: vertices (vi, vj), setMeasurement(meas8) in the vertices'
+ * layout, setInformation(info49) row-major 7 x 7 (NULL: identity for every edge).  Refused: an index out of range, vi == vj, a repeated
+ * pair, a non-positive or non-finite measurement, a system above the budget.  A vertex without an edge keeps its estimate; an edge
+ * between two fixed vertices counts in chi2 only.                                                                                  */
+int  cs_pgo_set_edges(cs_pgo* g, int n, const int* vi, const int* vj, const double* meas8, const double* info49);
+/* OptimizationAlgorithmLevenberg's two properties, as cs_ba_set_lm_params: ORB-SLAM2 calls setUserLambdaInit(1e-16).               */
+int  cs_pgo_set_lm_params(cs_pgo* g, double user_lambda_init, int max_trials_after_failure);
+/* computeActiveErrors + activeChi2 (sparse_optimizer.cpp:78-86, optimizable_graph.cpp chi2): sum of e^T Omega e; chi2_each (may be NULL)
+ * one value per edge.                                                                                                              */
+int  cs_pgo_chi2(cs_pgo* g, double* chi2, double* chi2_each);
+/* Inspection: every edge's error (n_edges x 7) and Jacobian blocks (n_edges x 49 each, row-major, row = error component) at the current
+ * estimates -- what computeError + linearizeOplus leave in _error, _jacobianOplusXi, _jacobianOplusXj; a zero block for a fixed
+ * vertex.  Any of the three may be NULL.                                                                                           */
+int  cs_pgo_linearize_edges(cs_pgo* g, double* err7, double* Ji49, double* Jj49);
+/* SparseOptimizer::optimize(iterations) (sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg; *iterations_done and the
+ * history arrays as cs_ba_optimize.  CS_ERR_NOT_RUN before cs_pgo_set_edges.                                                       */
+int  cs_pgo_optimize(cs_pgo* g, int iterations, int* iterations_done, double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap);
+int  cs_pgo_get_vertices(cs_pgo* g, double* sim8);
+/* The SE(3) pose OptimizeEssentialGraph recovers from each Sim(3) state: [sR t] -> [R t / s], n x 7 in SE3Quat::toVector order
+ * (tx ty tz qx qy qz qw; se3quat.h:151-163), the rotation as SE3Quat(R, t) holds it (normalised, w >= 0).                          */
+int  cs_pgo_get_se3(cs_pgo* g, double* Tcw7);
+/* ORB-SLAM2's map-point correction: P' = S_opt[ref]^-1 .map( S_init[ref].map(P) ) (sim3.h:140, :226-229) for n points, ref_vertex[p] the
+ * point's reference keyframe; S_init = what cs_pgo_set_vertices / cs_pgo_set_estimates last gave, S_opt = the current estimates.   */
+int  cs_pgo_correct_points(cs_pgo* g, int n, const int* ref_vertex, const double* xyz_in, double* xyz_out);
+/* *path: CS_BA_PATH_SPARSE or CS_BA_PATH_DENSE (cs_ba_solver_path_kind); *sparse_fill: values of the sparse factor / those of the dense
+ * triangle (0 on the dense path).                                                                                                  */
+int  cs_pgo_solver_path(cs_pgo* g, int* path, double* sparse_fill);
+/* Of the last cs_pgo_optimize, on a monotonic host clock: linearize_ms = the edge kernel and chi2 of every iteration, solve_ms = the
+ * trials (assembly, factorisation, substitution, update, chi2 of the new state, the record's copy), total_ms = the call.          */
+int  cs_pgo_last_timing(cs_pgo* g, double* linearize_ms, double* solve_ms, double* total_ms);
+
 #ifdef __cplusplus
 }
 #endif
