@@ -8,9 +8,6 @@
 // system is dense and factorised with rocSOLVER potrf/potrs (the reference's LinearSolverDense uses a dense
 // Eigen::LDLT, solvers/linear_solver_dense.h:104-111).  There is no CPU fallback.
 #include <hip/hip_runtime.h>
-#include <rocsolver/rocsolver.h>
-
-#include "ba_sparse.h"
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -33,6 +30,8 @@
 #include "../../include/cubeslam_hip.h"
 #include "ba_types.h"
 #include "cs_hip_util.h"
+#include "cs_lm.h"
+#include "cs_sparse_solver.h"
 
 namespace {
 
@@ -45,14 +44,6 @@ using cs::now_ms;
     ncclResult_t _r = (expr);                                                  \
     if (_r != ncclSuccess) {                                                   \
       cs_set_error(std::string(#expr) + ": " + ncclGetErrorString(_r));     \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
-#define BA_ROC(expr)                                                           \
-  do {                                                                         \
-    rocblas_status _s = (expr);                                                \
-    if (_s != rocblas_status_success) {                                        \
-      cs_set_error(std::string(#expr) + ": rocblas status " + std::to_string((int)_s)); \
       return CS_ERR_HIP;                                                       \
     }                                                                          \
   } while (0)
@@ -216,7 +207,7 @@ struct cs_ba {
   hipEvent_t sev[4] = {};  // separator mode, inside [3, 4]: interior factorised, separator message formed, messages gathered, separator system solved
   double sep_ms[5] = {0, 0, 0, 0, 0};   // accumulated: interior factorisation, message (Y, T, t), gather, separator solve, interior back-substitution
   bool lin_pending = false;  // ev[0..1] recorded but not yet read
-  int* h_status = nullptr;   // pinned: [status of the (interior's) factorisation, a cuboid block failed, status of the separator system's factorisation]
+  int* h_status = nullptr;   // pinned: [status of the (interior's) factorisation, a cuboid block failed, status of the separator system's factorisation -- sparse: [2], [3] are the solver's two words]
   // sharded BA over RCCL (cs_ba_comm_init): the collectives are issued from here, on this handle's stream
   ncclComm_t comm = nullptr;
   DBuf<double> d_scalars;    // [chi2, LM scale term] of a trial; lambda_0's diagonal on iteration 0
@@ -266,16 +257,10 @@ struct cs_ba {
   int n_red = 0;            // dimension of the system the solver factorises: n_pose, or the cameras' part when the cuboids are eliminated too
   bool elim = false;        // free cuboids eliminated like landmarks (single rank, fused Schur schedule)
   int elim_max_slots = 1;   // observing cameras of the widest free cuboid
-  // general sparse Cholesky of the reduced system (ba_sparse.h): graphs the ordering cannot band
-  bool sparse = false;
-  bool sp_S_clean = false;     // S holds nothing outside the plan's pattern (set by the first trial's full clear)
-  cs::SparsePlan sp_plan;
-  cs::SparseGrids sp_grids{0, 0};   // launch grids of the sparse factorisation / substitution, decided with the plan
-  DBuf<int> sp_ndim, sp_ncol, sp_sptr, sp_srow, sp_sroff, sp_prow, sp_rbase, sp_rent, sp_rptr, sp_rcol, sp_rpos, sp_order, sp_info;
-  DBuf<long long> sp_poff;
-  DBuf<double> sp_L, sp_xs, sp_T;
-  DBuf<int> sp_tcol;
-  DBuf<unsigned> sp_done, sp_xdone;
+  // general sparse Cholesky of the reduced system (cs_sparse_solver.h): graphs the ordering cannot band
+  bool sparse = false;         // this structure's solves go through `solver` (its plan was built, accepted and uploaded)
+  bool S_clean = false;        // sparse: S holds nothing outside the plan's pattern (set by the first trial's full clear)
+  cs::SparseSolver solver;
   DBuf<int> d_cub_mine;     // sharded + eliminated cuboids: 1 = this rank owns the cuboid (holds all its edges)
   DBuf<int> d_cubS_ptr, d_cubS_cam, d_ce_slot, d_cub_tile, d_cub_coef, d_elim_fail, d_slotE_ptr, d_slotE_idx;
   DBuf<double> cub_M, cub_Dinv;
@@ -892,7 +877,7 @@ int finalize_structure(cs_ba* B) {
     // 1.5 ms per Gflop + the dense tail's n^3 / 3 at 3 Tflop/s (rocSOLVER at 1-2 k unknowns) + the dense assembly's extra cost (1 ms + the
     // n x n fill).  The plan (an O(N^2) minimum-degree sweep) is only built when the alternative costs more than 5 ms.  CS_BA_SPARSE=0 never, =1 whenever the plan fits.
     mark("  band fits device");
-    B->sparse = false; B->sp_S_clean = false;
+    B->sparse = false; B->S_clean = false;
     {
       const char* e = getenv("CS_BA_SPARSE");
       const int mode = e ? atoi(e) : -1;
@@ -914,18 +899,14 @@ int finalize_structure(cs_ba* B) {
       if (consider) {
         std::vector<int> dim(nc + no, 0), col(nc + no, 0);
         for (int v : O.free_ids) { dim[v] = v < nc ? 6 : 9; col[v] = v < nc ? O.cam_col[v] : O.cub_col[v - nc]; }
-        cs::SparsePlan plan;
-        cs::SparseGrids sp_grids{0, 0};
-        const bool fits = cs::sparse_plan_build(O.adj, O.free_ids, dim, col, cs::sparse_max_panel_doubles(), 0.35, plan, getenv("CS_BA_SPARSE_NO_TAIL") ? 0 : (getenv("CS_BA_SPARSE_TAIL_MAX") ? atoi(getenv("CS_BA_SPARSE_TAIL_MAX")) : 9000)) && cs::sparse_grids(cs::sparse_max_panel_doubles(), plan.N, &sp_grids);
+        const bool fits = B->solver.build(O.adj, O.free_ids, dim, col, 0.35, getenv("CS_BA_SPARSE_NO_TAIL") ? 0 : (getenv("CS_BA_SPARSE_TAIL_MAX") ? atoi(getenv("CS_BA_SPARSE_TAIL_MAX")) : 9000));
+        const cs::SparsePlan& plan = B->solver.plan;      // (the handle's own: a plan that is not taken is not uploaded, and B->sparse stays false)
         const double nt = (double)plan.n_tail;
         const double est_sparse = 0.025 * plan.levels + 1.5 * plan.flops * 2e-9 + (nt > 0 ? nt * nt * nt / 3.0 / 3e12 * 1e3 + 1.0 : 0.0) + 1.0 + nn * nn * 8.0 / 2e12 * 1e3
                                   + 0.3;   // (the sparse solve is not deferrable: its trials take cs_ba_optimize's synchronising flow -- four more host round trips than the stream flow of the band)
         if (prof && fits) fprintf(stderr, "[ba structure] sparse plan: %d vertices, %d levels, %lld values (%.1f%% of the dense triangle), largest panel %d, %.2f Gflop + a dense tail of %d unknowns; estimates ms: sparse %.1f, band %.1f, dense %.1f\n",
                                   plan.N, plan.levels, plan.nvals, 100.0 * plan.nvals / (0.5 * nn * nn), plan.max_panel, plan.flops * 2e-9, plan.n_tail, est_sparse, est_band < 1e29 ? est_band : -1.0, est_dense);
-        if (fits && (mode == 1 || est_sparse < est_other)) {
-          B->sparse = true; B->band_ld = 0; B->use_bcr = false;
-          B->sp_plan = std::move(plan); B->sp_grids = sp_grids;
-        }
+        if (fits && (mode == 1 || est_sparse < est_other)) { B->sparse = true; B->band_ld = 0; B->use_bcr = false; }
       }
     }
   }
@@ -1517,14 +1498,7 @@ int finalize_structure(cs_ba* B) {
   AL(B->chi_partial, B->n_chi_partials);
   AL(B->scale_partial, (size_t)cs::ba_scale_blocks());
   AL(B->d_info, 1);
-  if (B->sparse) {
-    const cs::SparsePlan& SP = B->sp_plan;
-    UP(B->sp_ndim, SP.ndim); UP(B->sp_ncol, SP.ncol); UP(B->sp_sptr, SP.sptr); UP(B->sp_srow, SP.srow); UP(B->sp_sroff, SP.sroff); UP(B->sp_prow, SP.prow);
-    UP(B->sp_rbase, SP.rbase); UP(B->sp_rent, SP.rent); UP(B->sp_rptr, SP.rptr); UP(B->sp_order, SP.order); UP(B->sp_poff, SP.poff);
-    { std::vector<int> v_rcol(SP.rcol), v_rpos(SP.rpos); if (v_rcol.empty()) { v_rcol.push_back(0); v_rpos.push_back(0); } UP(B->sp_rcol, v_rcol); UP(B->sp_rpos, v_rpos); }
-    UP(B->sp_tcol, SP.tcol); AL(B->sp_T, (size_t)SP.n_tail * SP.n_tail + SP.n_tail + 1);
-    AL(B->sp_L, (size_t)SP.nvals); AL(B->sp_xs, 9 * (size_t)(SP.N + 1)); AL(B->sp_done, (size_t)SP.N + 1); AL(B->sp_xdone, (size_t)SP.N + 2); AL(B->sp_info, 2);
-  }
+  if (B->sparse) { rc = B->solver.upload(B->st); if (rc) return rc; }      // (one queued copy; this phase's closing wait is the one it asks for)
   if (B->sep_mode) {
     AL(B->sepY, (size_t)(B->wl + B->wr) * B->int_n);
     AL(B->sep_msgs, B->msg_doubles * (size_t)R);
@@ -1740,15 +1714,6 @@ int put_lambda(cs_ba* B, double lambda) {
   return CS_OK;
 }
 int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void* ctx, std::unique_lock<std::mutex>* defer);
-static cs::SparseView sparse_view(cs_ba* B) {
-  cs::SparseView SV;
-  SV.N = B->sp_plan.N; SV.n = B->n_red;
-  SV.ndim = B->sp_ndim.p; SV.ncol = B->sp_ncol.p; SV.sptr = B->sp_sptr.p; SV.srow = B->sp_srow.p; SV.sroff = B->sp_sroff.p; SV.prow = B->sp_prow.p;
-  SV.rbase = B->sp_rbase.p; SV.rent = B->sp_rent.p; SV.rptr = B->sp_rptr.p; SV.rcol = B->sp_rcol.p; SV.rpos = B->sp_rpos.p; SV.order = B->sp_order.p; SV.poff = B->sp_poff.p;
-  SV.tcol = B->sp_tcol.p; SV.tail_start = B->sp_plan.tail_start; SV.n_tail = B->sp_plan.n_tail; SV.T = B->sp_T.p; SV.rhs_t = B->sp_T.p + (size_t)SV.n_tail * SV.n_tail;
-  SV.S = B->S.p; SV.rhs = B->view.rhs; SV.L = B->sp_L.p; SV.xs = B->sp_xs.p; SV.done = B->sp_done.p; SV.xdone = B->sp_xdone.p; SV.info = B->sp_info.p;
-  return SV;
-}
 
 int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr, void* ctx = nullptr, std::unique_lock<std::mutex>* defer = nullptr) {
   const int n = B->n_red;
@@ -1767,13 +1732,13 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
     } else { int rcl = put_lambda(B, lambda); if (rcl) return rcl; }
     BA_MARK(B, B->ev[2]);
     if (lean_head) {
-    } else if (B->sparse && B->sp_S_clean) {
+    } else if (B->sparse && B->S_clean) {
       // (sparse path: S was cleared by the structure phase and only the plan's pattern is ever written -- the pattern and the right-hand side)
-      cs::launch_sparse_zero_pattern(sparse_view(B), B->S.p, B->st);
+      cs::launch_sparse_zero_pattern(B->solver.view(B->S.p, B->view.rhs, n), B->S.p, B->st);
       CS_HIP_TRY(hipMemsetAsync(B->S.p + B->s_doubles, 0, sizeof(double) * B->n_pose, B->st));
     } else {
       CS_HIP_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
-      B->sp_S_clean = B->sparse;
+      B->S_clean = B->sparse;
     }
     if (!lean_head) CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
     cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join, pro_in_reduce ? &side_pro : nullptr);
@@ -1823,36 +1788,30 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
     } else if (B->sparse) {
       // general sparse: the pattern's blocks are gathered from the dense S by the factorisation itself (sparse_kernels.hip)
       std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-      CS_HIP_TRY(hipMemsetAsync(B->sp_info.p, 0, 2 * sizeof(int), B->st));
-      const cs::SparseView SV = sparse_view(B);
-      if (!cs::launch_sparse_cholesky(SV, cs::sparse_max_panel_doubles(), B->sp_grids, B->st)) { cs_set_error("sparse solver: the factorisation could not be launched (grid " + std::to_string(B->sp_grids.chol) + " for " + std::to_string(SV.N) + " vertices)"); return CS_ERR_HIP; }
-      CS_HIP_TRY(hipMemsetAsync(B->d_info.p, 0, sizeof(int), B->st));
-      if (SV.n_tail > 0) {   // the top of the elimination tree as one dense block (same storage convention as the dense path's S)
-        BA_ROC(rocsolver_dpotrf(B->blas, rocblas_fill_upper, SV.n_tail, SV.T, SV.n_tail, B->d_info.p));
-        BA_ROC(rocsolver_dpotrs(B->blas, rocblas_fill_upper, SV.n_tail, 1, SV.T, SV.n_tail, SV.rhs_t, SV.n_tail));
-      }
-      if (!cs::launch_sparse_backsolve(SV, B->sp_grids, B->st)) { cs_set_error("sparse solver: the substitution could not be launched (grid " + std::to_string(B->sp_grids.back) + " for " + std::to_string(SV.N) + " vertices)"); return CS_ERR_HIP; }
+      const cs::SparseSolver& sv = B->solver; const int rs = B->solver.solve(B->blas, B->S.p, B->view.rhs, n, B->st);
+      if (rs == cs::SparseSolver::CHOL_NOT_LAUNCHED) { cs_set_error("sparse solver: the factorisation could not be launched (grid " + std::to_string(sv.grids.chol) + " for " + std::to_string(sv.plan.N) + " vertices)"); return CS_ERR_HIP; }
+      if (rs == cs::SparseSolver::BACK_NOT_LAUNCHED) { cs_set_error("sparse solver: the substitution could not be launched (grid " + std::to_string(sv.grids.back) + " for " + std::to_string(sv.plan.N) + " vertices)"); return CS_ERR_HIP; }
+      if (rs) return rs;
       BA_MARK(B, B->ev[4]);
       cs::ba_launch_backsub(B->view, B->st);
       CS_HIP_TRY(hipGetLastError());
       { int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
       BA_MARK(B, B->ev[5]);
-      CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->sp_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-      CS_HIP_TRY(hipMemcpyAsync(B->h_status + 2, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+      { int rc2 = B->solver.queue_status(B->h_status + 2, B->st); if (rc2) return rc2; }
       CS_HIP_TRY(hipStreamSynchronize(B->st));
-      if (B->h_status[2] != 0 && B->h_status[0] == 0) B->h_status[0] = B->h_status[2];     // (the dense tail's pivot)
-      if (*B->h_status == 0x7fffffff) {
+      const cs::SparseVerdict verdict = cs::sparse_verdict(B->h_status + 2);     // (the factorisation's word and the dense tail's pivot)
+      if (verdict == cs::SPARSE_TIMEOUT) {
         cs_set_error("sparse solver: grid not co-resident (wait timed out); set CS_BA_SPARSE=0 on a shared device");
         return CS_ERR_HIP;
       }
-      if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
+      if (verdict != cs::SPARSE_OK || B->h_status[1] != 0) *ok = false;
     } else {
       // dense: the lower triangle of the row-major S is the upper triangle of the column-major matrix rocSOLVER sees
-      BA_ROC(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, B->S.p, n, B->d_info.p));
+      CS_ROC_TRY(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, B->S.p, n, B->d_info.p));
       CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
       CS_HIP_TRY(hipStreamSynchronize(B->st));
       if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
-      else BA_ROC(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, 1, B->S.p, n, B->view.rhs, n));
+      else CS_ROC_TRY(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, 1, B->S.p, n, B->view.rhs, n));
       BA_MARK(B, B->ev[4]);
       // (sharded: the collective is issued whether or not THIS rank's factorisation went through -- the ranks decide together, below)
       if (*ok || B->shard_n > 1) { cs::ba_launch_backsub(B->view, B->st); CS_HIP_TRY(hipGetLastError()); int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
@@ -1983,9 +1942,7 @@ extern "C" {
 int cs_ba_create(int device, cs_ba** out) {
   if (!out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
+  { const int rc = cs::check_device(device); if (rc) return rc; }
   CS_GUARD_BEGIN
   struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{new cs_ba()};   // freed on every early return
   cs_ba* B = g.b;
@@ -2006,10 +1963,10 @@ int cs_ba_create(int device, cs_ba** out) {
   { int rc0 = B->d_lam.alloc(2); if (rc0) return rc0; }
   CS_HIP_TRY(hipHostMalloc((void**)&B->h_trial, 8 * sizeof(double)));
   for (int i = 0; i < 8; i++) B->h_trial[i] = 0.0;
-  CS_HIP_TRY(hipHostMalloc((void**)&B->h_status, 3 * sizeof(int)));   // [factorisation status, a cuboid block failed, separator system's status]
-  B->h_status[0] = B->h_status[1] = B->h_status[2] = 0;
-  BA_ROC(rocblas_create_handle(&B->blas));
-  BA_ROC(rocblas_set_stream(B->blas, B->st));
+  CS_HIP_TRY(hipHostMalloc((void**)&B->h_status, 4 * sizeof(int)));
+  B->h_status[0] = B->h_status[1] = B->h_status[2] = B->h_status[3] = 0;
+  CS_ROC_TRY(rocblas_create_handle(&B->blas));
+  CS_ROC_TRY(rocblas_set_stream(B->blas, B->st));
   *out = B;
   g.b = nullptr;
   return CS_OK;
@@ -2022,18 +1979,17 @@ void cs_ba_destroy(cs_ba* B) {
   DBuf<double>* dd[] = {&B->cams, &B->points, &B->cubes, &B->cams_bak, &B->points_bak, &B->cubes_bak, &B->pm_uv, &B->pm_info, &B->pm_intr, &B->pm_huber,
                         &B->cm_uv, &B->cm_info, &B->cm_intr, &B->cm_huber, &B->ce_meas, &B->ce_info, &B->ce_Hcc, &B->ce_Hoo, &B->ce_Hco, &B->ce_bc, &B->ce_bo,
                         &B->oe_meas, &B->oe_info, &B->oe_Hii, &B->oe_Hjj, &B->oe_Hij, &B->oe_bi, &B->oe_bj, &B->Hcam, &B->bcam, &B->Hcub, &B->bcub, &B->Hll, &B->bl,
-                        &B->W, &B->WD, &B->Dinv, &B->dbl, &B->S, &B->rhs, &B->xl, &B->chi_partial, &B->band_linv, &B->scale_partial, &B->pe_meas, &B->pe_info, &B->pe_K, &B->part_tiles, &B->part_coef, &B->cub_M, &B->cub_Dinv, &B->raw_uv, &B->raw_info, &B->raw_intr, &B->raw_huber, &B->sepY, &B->sep_msgs, &B->sepS, &B->int_work, &B->sep_work, &B->d_ce_rdelta, &B->d_oe_rdelta, &B->ext_cam36, &B->ext_cam6, &B->ext_cub81, &B->ext_cub9, &B->ext_pt9, &B->ext_pt3, &B->ext_Hij, &B->sp_L, &B->sp_xs, &B->sp_T, &B->comb_uv, &B->comb_info, &B->comb_intr, &B->comb_huber, &B->d_pm_ur, &B->d_cm_ur, &B->d_pm_sinfo, &B->d_cm_sinfo};
+                        &B->W, &B->WD, &B->Dinv, &B->dbl, &B->S, &B->rhs, &B->xl, &B->chi_partial, &B->band_linv, &B->scale_partial, &B->pe_meas, &B->pe_info, &B->pe_K, &B->part_tiles, &B->part_coef, &B->cub_M, &B->cub_Dinv, &B->raw_uv, &B->raw_info, &B->raw_intr, &B->raw_huber, &B->sepY, &B->sep_msgs, &B->sepS, &B->int_work, &B->sep_work, &B->d_ce_rdelta, &B->d_oe_rdelta, &B->ext_cam36, &B->ext_cam6, &B->ext_cub81, &B->ext_cub9, &B->ext_pt9, &B->ext_pt3, &B->ext_Hij, &B->comb_uv, &B->comb_info, &B->comb_intr, &B->comb_huber, &B->d_pm_ur, &B->d_cm_ur, &B->d_pm_sinfo, &B->d_cm_sinfo};
   for (auto* d : dd) d->release();
   B->stage.release(); B->append_stage.release();
   DBuf<int>* di[] = {&B->d_ce_active, &B->d_oe_active, &B->d_cam_col, &B->d_cub_col, &B->d_pt_free, &B->pm_pt, &B->pm_cam, &B->pt_ptr, &B->cm_pm, &B->cm_pt, &B->cam_ptr, &B->d_ce_cam, &B->d_ce_cub,
                      &B->d_oe_i, &B->d_oe_j, &B->cam_ce_ptr, &B->cam_ce_idx, &B->cam_oei_ptr, &B->cam_oei_idx, &B->cam_oej_ptr, &B->cam_oej_idx, &B->cub_ce_ptr,
                      &B->cub_ce_idx, &B->pair_ptr, &B->pair_i1, &B->pair_i2, &B->ent_a, &B->ent_b, &B->d_run_lm, &B->d_seg_ptr, &B->d_seg_k, &B->d_seg_tile, &B->d_seg_slot, &B->d_run_e0, &B->d_seg_cam,
                      &B->d_gp_ptr, &B->d_gp_i1, &B->d_gp_i2, &B->d_gtile, &B->d_gcam_ptr, &B->d_gslot, &B->d_cubS_ptr, &B->d_cubS_cam, &B->d_ce_slot, &B->d_cub_tile, &B->d_cub_coef,
-                     &B->d_elim_fail, &B->d_slotE_ptr, &B->d_slotE_idx, &B->d_cub_mine, &B->d_sep_off, &B->d_sep_col, &B->d_int_info, &B->d_sep_info, &B->d_pm_rk, &B->d_cm_rk, &B->d_ce_rk, &B->d_oe_rk, &B->d_ext_e4, &B->d_ext_order, &B->d_ext_gptr, &B->d_src, &B->sp_ndim, &B->sp_ncol, &B->sp_sptr, &B->sp_srow, &B->sp_sroff, &B->sp_prow, &B->sp_rbase, &B->sp_rent, &B->sp_rptr, &B->sp_rcol, &B->sp_rpos,
-                     &B->sp_order, &B->sp_info, &B->sp_tcol, &B->d_pm_kind, &B->d_cm_kind};
+                     &B->d_elim_fail, &B->d_slotE_ptr, &B->d_slotE_idx, &B->d_cub_mine, &B->d_sep_off, &B->d_sep_col, &B->d_int_info, &B->d_sep_info, &B->d_pm_rk, &B->d_cm_rk, &B->d_ce_rk, &B->d_oe_rk, &B->d_ext_e4, &B->d_ext_order, &B->d_ext_gptr, &B->d_src, &B->d_pm_kind, &B->d_cm_kind};
   for (auto* d : di) d->release();
   B->d_lvl.release(); B->d_pm_cm.release(); B->d_cls_counts.release(); B->d_cls_chi.release();
-  B->sp_poff.release(); B->sp_done.release(); B->sp_xdone.release();
+  B->solver.release();
   B->d_info.release(); B->d_band_info.release();
   for (auto& e : B->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : B->sev) if (e) (void)hipEventDestroy(e);
@@ -2788,8 +2744,8 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
     std::atomic_thread_fence(std::memory_order_acquire);
     return CS_OK;
   };
-  double lambda = -1, ni = 2;
-  int nBad = 0, done = 0;
+  cs::LmState lm;      // lambda, ni, the bad-iteration count: the policy is cs_lm.h's (set by the first iteration)
+  int done = 0;
   double carriedChi = 0;
   bool have_carried = false;     // chi2 of the current state is known from the previous iteration's last trial
   for (int it = 0; it < iterations; it++) {
@@ -2824,8 +2780,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
       CS_HIP_TRY(hipGetLastError());
       CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, sizeof(double), hipMemcpyDeviceToHost, B->st));
       CS_HIP_TRY(hipStreamSynchronize(B->st));
-      lambda = B->user_lambda_init > 0 ? B->user_lambda_init : 1e-5 * B->h_scalars[0];      // (:168-169: a user value wins)
-      ni = 2; nBad = 0;
+      cs::lm_begin(lm, B->user_lambda_init, B->h_scalars[0]);
     } else if (it == 0) {
       CS_HIP_TRY(hipStreamSynchronize(B->st));   // the copies below run on the NULL stream, which B->st does not order with
       std::vector<double> hc(36 * (size_t)B->nc), ho(81 * (size_t)B->no), hl(9 * (size_t)B->np);
@@ -2841,8 +2796,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
       for (int i = 0; i < B->n_pose; i++) md = std::max(std::fabs(pd[i]), md);
       for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) for (int d = 0; d < 3; d++) md = std::max(std::fabs(hl[9 * (size_t)i + 4 * d]), md);
       if (reduce_host(&md, 1, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-      lambda = B->user_lambda_init > 0 ? B->user_lambda_init : 1e-5 * md;
-      ni = 2; nBad = 0;
+      cs::lm_begin(lm, B->user_lambda_init, md);
     }
     double rho = 0;
     int qmax = 0;
@@ -2859,7 +2813,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
         // [chi2, scale term, "a factorisation failed somewhere"]: one message; every rank takes the same accept / reject branch.
         auto enqueue_trial = [&](std::unique_lock<std::mutex>* t) -> int {
           bool okq = true;
-          int rq = solve_device(B, lambda, &okq, nullptr, nullptr, t); if (rq) return rq;
+          int rq = solve_device(B, lm.lambda, &okq, nullptr, nullptr, t); if (rq) return rq;
           cs::ba_launch_scale_update(B->view, B->d_lam.p, B->scale_partial.p, B->st, B->cams_bak.p, B->points_bak.p, B->cubes_bak.p);
           if (spec_now) CS_HIP_TRY(hipEventRecord(B->ev_upd, B->st));      // the state the next linearisation reads is final from here
           BA_MARK(B, B->ev[6]);
@@ -2892,7 +2846,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
         if (B->h_status[0] == 0x7fffffff || (B->sep_mode && B->shard_n > 1 && B->h_status[2] == 0x7fffffff)) { cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
         ok2 = hs[2] == 0.0;
         tempChi = hs[0];
-        scale = ok2 ? hs[1] : 0.0;
+        scale = hs[1];
         if (B->stage_timing) {
           if (direct_scalars) CS_HIP_TRY(hipStreamSynchronize(B->st));     // (the phase marks are read below: the last one must have passed)
           rc = collect_solve_times(B); if (rc) return rc;
@@ -2901,7 +2855,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
         }
         if (ext_active && ok2) { rc = ext_refresh(0); if (rc) return rc; tempChi += B->ext_chi2; }
       } else {
-        rc = solve_device(B, lambda, &ok2, fn, ctx); if (rc) return rc;
+        rc = solve_device(B, lm.lambda, &ok2, fn, ctx); if (rc) return rc;
         if (B->shard_n > 1) {   // a failed factorisation on one rank is everybody's rejected trial
           double ff = ok2 ? 0.0 : 1.0;
           if (reduce_host(&ff, 1, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
@@ -2924,38 +2878,25 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
         if (reduce_host(&scale, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
       }
       if (ok2) debug_nan_scan(B, "cs_ba_optimize: after a trial's solve + update");
-      if (!ok2) tempChi = std::numeric_limits<double>::max();
-      rho = currentChi - tempChi;
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - std::pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        lambda *= std::max(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
+      if (cs::lm_trial(lm, currentChi, tempChi, scale, ok2, rho)) {
         spec_lin = spec_now;       // the system of the state this trial left is already on the stream
       } else {
-        lambda *= ni;
-        ni *= 2;
         rc = restore_estimates(B); if (rc) return rc;
         if (spec_now) {            // the speculation linearised the rejected state: the restored one again, as this iteration linearises
           rc = build_system_device(B); if (rc) return rc;
         }
       }
       qmax++;
-    } while (rho < 0 && qmax < B->max_trials_after_failure);
+    } while (cs::lm_again(rho, qmax, B->max_trials_after_failure));
     if (!spec_lin) CS_HIP_TRY(hipStreamSynchronize(B->st));
     if (done < cap) {
       if (chi_hist) chi_hist[done] = currentChi;
-      if (lambda_hist) lambda_hist[done] = lambda;
+      if (lambda_hist) lambda_hist[done] = lm.lambda;
       if (trials_hist) trials_hist[done] = qmax;
     }
     done++;
     carriedChi = currentChi; have_carried = true;
-    if (qmax == B->max_trials_after_failure || rho == 0) break;
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-    if (nBad >= 3) break;
+    if (cs::lm_stop(lm, rho, qmax, B->max_trials_after_failure, iniChi, currentChi)) break;
   }
   if (spec_lin) CS_HIP_TRY(hipStreamSynchronize(B->st));      // (a stopping rule ended the loop behind an accepted trial: its speculated system is the current state's)
   if (iterations_done) *iterations_done = done;
@@ -3167,13 +3108,13 @@ static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, 
   if ((rc = dH.reserve((size_t)n * n)) || (rc = dE.reserve((size_t)n * m)) || (rc = dinfo.reserve(1))) return rc;
   CS_HIP_TRY(hipMemcpyAsync(dH.p, H.data(), 8 * H.size(), hipMemcpyHostToDevice, B->st));
   CS_HIP_TRY(hipMemcpyAsync(dE.p, E.data(), 8 * E.size(), hipMemcpyHostToDevice, B->st));
-  BA_ROC(rocblas_set_stream(B->blas, B->st));
-  BA_ROC(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, dH.p, n, dinfo.p));      // (symmetric: row- and column-major are the same matrix)
+  CS_ROC_TRY(rocblas_set_stream(B->blas, B->st));
+  CS_ROC_TRY(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, dH.p, n, dinfo.p));      // (symmetric: row- and column-major are the same matrix)
   int info = 0;
   CS_HIP_TRY(hipMemcpyAsync(&info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (info != 0) { if (positive_definite) *positive_definite = 0; return CS_OK; }
-  BA_ROC(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, m, dH.p, n, dE.p, n));
+  CS_ROC_TRY(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, m, dH.p, n, dE.p, n));
   CS_HIP_TRY(hipMemcpyAsync(E.data(), dE.p, 8 * E.size(), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   size_t o = 0;
@@ -3257,7 +3198,7 @@ int cs_ba_solver_path(cs_ba* B, int* path, int* bandwidth, double* sparse_fill) 
   int rc = finalize_structure(B); if (rc) return rc;
   if (path) *path = B->band_ld ? CS_BA_PATH_BAND : (B->sparse ? CS_BA_PATH_SPARSE : CS_BA_PATH_DENSE);
   if (bandwidth) *bandwidth = B->band_ld ? B->band_ld - 1 : 0;
-  if (sparse_fill) *sparse_fill = B->sparse ? (double)B->sp_plan.nvals / (0.5 * (double)B->n_red * (double)B->n_red) : 0.0;
+  if (sparse_fill) *sparse_fill = B->sparse ? B->solver.fill(B->n_red) : 0.0;
   return CS_OK;
   CS_GUARD_END("cs_ba_solver_path")
 }

@@ -1,8 +1,9 @@
-// ba_sparse.h -- general sparse Cholesky of the reduced pose system, for graphs reverse Cuthill-McKee cannot band (2-D covisibility
-// meshes, many loop closures): what the reference leaves to Eigen::SimplicialLDLT behind a fill-reducing block ordering
-// (g2o/solvers/linear_solver_eigen.h:94-232, blockOrdering + AMD).  Host side: the SYMBOLIC phase, once per structure --
-//   * minimum-degree elimination of the block graph (vertices = free cameras / cuboids, 6 or 9 unknowns each); eliminating a vertex joins
-//     its remaining neighbours, which at that moment are exactly the rows of its column of L;
+// ba_sparse.h -- general sparse Cholesky of a block system: the bundle adjustment's reduced pose system where reverse Cuthill-McKee cannot
+// band it (2-D covisibility meshes, many loop closures) and the pose graph's H + lambda I (pgo_host.cpp); what the reference leaves to
+// Eigen::SimplicialLDLT behind a fill-reducing block ordering (g2o/solvers/linear_solver_eigen.h:94-232, blockOrdering + AMD).  Here, host
+// only: the SYMBOLIC phase, once per structure (its device state and launch sequence have one owner, cs_sparse_solver.h) --
+//   * minimum-degree elimination of the block graph (vertices = free cameras / cuboids / keyframes, weighted 9 for a 9-block and 6 for any
+//     other); eliminating a vertex joins its remaining neighbours, which at that moment are exactly the rows of its column of L;
 //   * per column j its row structure, per row i the columns k < i that update it (left-looking), a processing order by elimination-tree level;
 //   * storage: column j of L is a dense PANEL, rows = [the diagonal block | the blocks below it | one row for the right-hand side], dj wide.
 // Device side (sparse_kernels.hip): one persistent kernel factorises (a workgroup per column, columns taken in level order, a column waits

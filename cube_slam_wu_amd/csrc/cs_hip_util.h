@@ -34,6 +34,13 @@ namespace cs {
 // the turn of the persistent solver kernels whose workgroups wait for each other (ba_host.cpp, pgo_host.cpp): one such kernel at a time per process
 inline std::mutex& coop_mutex() { static std::mutex m; return m; }
 
+// the first check of every cs_*_create: a device is visible and `device` names one
+inline int check_device(int device) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
+  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
+  return CS_OK;
+}
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Grow-only device / pinned buffers.

@@ -699,12 +699,7 @@ int cs_internal_detector_device(cs_detector* d) { return d->device; }
 int cs_detector_create(const cs_detect_params* params, int device, cs_detector** out) {
   if (!out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback");
-    return CS_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
+  { const int rc = cs::check_device(device); if (rc) return rc; }
   CS_GUARD_BEGIN
   struct Guard { cs_detector* d; ~Guard() { if (d) cs_detector_destroy(d); } } g{new cs_detector()};   // freed on every early return
   cs_detector* d = g.d;

@@ -4,35 +4,24 @@
 // EdgeSim3 per spanning-tree / loop / covisibility link (types/types_seven_dof_expmap.h:48-126 over types/sim3.h), Levenberg-Marquardt
 // (core/optimization_algorithm_levenberg.cpp:61-189).  No vertex is marginalised, so H + lambda I over the free vertices' 7-blocks is
 // solved directly: assembled as a dense lower triangle (ba_types.h's S[r n + c]) and factorised by the general sparse Cholesky
-// (ba_sparse.h, ndim = 7) where its plan and grids accept the graph, by rocSOLVER potrf / potrs otherwise.  The host reads one pinned
+// (cs_sparse_solver.h, ndim = 7) where its plan and grids accept the graph, by rocSOLVER potrf / potrs otherwise.  The host reads one pinned
 // record per trial (chi2, scale term, pivot flags).  There is no CPU fallback.
 #include <hip/hip_runtime.h>
-#include <rocblas/rocblas.h>
-#include <rocsolver/rocsolver.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
-#include "ba_sparse.h"
 #include "cs_hip_util.h"
+#include "cs_lm.h"
+#include "cs_sparse_solver.h"
 #include "pgo_types.h"
-
-#define PGO_ROC(expr)                                                          \
-  do {                                                                         \
-    rocblas_status _s = (expr);                                                \
-    if (_s != rocblas_status_success) {                                        \
-      cs_set_error(std::string(#expr) + ": rocblas status " + std::to_string((int)_s)); \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
 
 // The dense system's budget: n x n doubles, n = 7 per free keyframe with an edge.  4 GiB -> n <= 23 170 -> 3 310 free keyframes.
 static const size_t PGO_DENSE_BUDGET_BYTES = (size_t)4 << 30;
@@ -50,15 +39,10 @@ struct cs_pgo {
   cs::DevBuf<int> vcol, ei, ej, inc_ptr, inc_edge, d_info, io_i;
   cs::DevBuf<unsigned char> d_fix_scale, inc_side;
   cs::PinBuf<double> h_rec;     // [chi2, scale term, max |H_jj|]
-  cs::PinBuf<int> h_status;     // [sparse info, dense info]
-  // general sparse Cholesky (ba_sparse.h)
-  bool sparse = false, S_clean = false;
-  cs::SparsePlan plan;
-  cs::SparseGrids grids{0, 0};
-  cs::DevBuf<int> sp_ndim, sp_ncol, sp_sptr, sp_srow, sp_sroff, sp_prow, sp_rbase, sp_rent, sp_rptr, sp_rcol, sp_rpos, sp_order, sp_tcol, sp_info;
-  cs::DevBuf<long long> sp_poff;
-  cs::DevBuf<double> sp_L, sp_xs, sp_T;
-  cs::DevBuf<unsigned> sp_done, sp_xdone;
+  cs::PinBuf<int> h_status;     // cs::sparse_verdict's two words: the solver's, or [0, rocSOLVER's info] on the dense path
+  // general sparse Cholesky (cs_sparse_solver.h)
+  bool sparse = false, S_clean = false;     // this structure's solves go through `solver`; S holds nothing outside the graph's blocks
+  cs::SparseSolver solver;
   double linearize_ms = 0, solve_ms = 0, total_ms = 0;
 };
 
@@ -74,16 +58,6 @@ cs::PgoView view_of(cs_pgo* G) {
   v.inc_ptr = G->inc_ptr.p; v.inc_edge = G->inc_edge.p; v.inc_side = G->inc_side.p;
   v.S = G->S.p; v.b = G->b.p; v.x = G->x.p; v.diag = G->diag.p; v.rec = G->rec.p;
   return v;
-}
-
-cs::SparseView sparse_view(cs_pgo* G) {
-  cs::SparseView SV;
-  SV.N = G->plan.N; SV.n = G->n;
-  SV.ndim = G->sp_ndim.p; SV.ncol = G->sp_ncol.p; SV.sptr = G->sp_sptr.p; SV.srow = G->sp_srow.p; SV.sroff = G->sp_sroff.p; SV.prow = G->sp_prow.p;
-  SV.rbase = G->sp_rbase.p; SV.rent = G->sp_rent.p; SV.rptr = G->sp_rptr.p; SV.rcol = G->sp_rcol.p; SV.rpos = G->sp_rpos.p; SV.order = G->sp_order.p; SV.poff = G->sp_poff.p;
-  SV.tcol = G->sp_tcol.p; SV.tail_start = G->plan.tail_start; SV.n_tail = G->plan.n_tail; SV.T = G->sp_T.p; SV.rhs_t = G->sp_T.p + (size_t)SV.n_tail * SV.n_tail;
-  SV.S = G->S.p; SV.rhs = G->x.p; SV.L = G->sp_L.p; SV.xs = G->sp_xs.p; SV.done = G->sp_done.p; SV.xdone = G->sp_xdone.p; SV.info = G->sp_info.p;
-  return SV;
 }
 
 template <class T>
@@ -123,21 +97,17 @@ int solve(cs_pgo* G, double lambda, std::unique_lock<std::mutex>* turn) {
   }
   cs::pgo_launch_assemble(v, lambda, G->st);
   CS_HIP_TRY(hipGetLastError());
-  CS_HIP_TRY(hipMemsetAsync(G->d_info.p, 0, sizeof(int), G->st));
-  CS_HIP_TRY(hipMemsetAsync(G->sp_info.p, 0, 2 * sizeof(int), G->st));
   if (G->sparse) {
     *turn = std::unique_lock<std::mutex>(cs::coop_mutex());     // (a persistent kernel whose workgroups wait for each other: one at a time per process)
-    const cs::SparseView SV = sparse_view(G);
-    if (!cs::launch_sparse_cholesky(SV, cs::sparse_max_panel_doubles(), G->grids, G->st)) { cs_set_error("cs_pgo: the sparse factorisation could not be launched"); return CS_ERR_HIP; }
-    if (SV.n_tail > 0) {
-      PGO_ROC(rocsolver_dpotrf(G->blas, rocblas_fill_upper, SV.n_tail, SV.T, SV.n_tail, G->d_info.p));
-      PGO_ROC(rocsolver_dpotrs(G->blas, rocblas_fill_upper, SV.n_tail, 1, SV.T, SV.n_tail, SV.rhs_t, SV.n_tail));
-    }
-    if (!cs::launch_sparse_backsolve(SV, G->grids, G->st)) { cs_set_error("cs_pgo: the sparse substitution could not be launched"); return CS_ERR_HIP; }
+    const int rs = G->solver.solve(G->blas, G->S.p, G->x.p, G->n, G->st);
+    if (rs == cs::SparseSolver::CHOL_NOT_LAUNCHED) { cs_set_error("cs_pgo: the sparse factorisation could not be launched"); return CS_ERR_HIP; }
+    if (rs == cs::SparseSolver::BACK_NOT_LAUNCHED) { cs_set_error("cs_pgo: the sparse substitution could not be launched"); return CS_ERR_HIP; }
+    if (rs) return rs;
   } else {
+    CS_HIP_TRY(hipMemsetAsync(G->d_info.p, 0, sizeof(int), G->st));
     // the lower triangle of the row-major S is the upper triangle of the column-major matrix rocSOLVER sees
-    PGO_ROC(rocsolver_dpotrf(G->blas, rocblas_fill_upper, G->n, G->S.p, G->n, G->d_info.p));
-    PGO_ROC(rocsolver_dpotrs(G->blas, rocblas_fill_upper, G->n, 1, G->S.p, G->n, G->x.p, G->n));
+    CS_ROC_TRY(rocsolver_dpotrf(G->blas, rocblas_fill_upper, G->n, G->S.p, G->n, G->d_info.p));
+    CS_ROC_TRY(rocsolver_dpotrs(G->blas, rocblas_fill_upper, G->n, 1, G->S.p, G->n, G->x.p, G->n));
   }
   return CS_OK;
 }
@@ -145,8 +115,8 @@ int solve(cs_pgo* G, double lambda, std::unique_lock<std::mutex>* turn) {
 // the trial's record comes home: one synchronisation
 int fetch_record(cs_pgo* G) {
   CS_HIP_TRY(hipMemcpyAsync(G->h_rec.p, G->rec.p, 3 * sizeof(double), hipMemcpyDeviceToHost, G->st));
-  CS_HIP_TRY(hipMemcpyAsync(G->h_status.p, G->sp_info.p, sizeof(int), hipMemcpyDeviceToHost, G->st));
-  CS_HIP_TRY(hipMemcpyAsync(G->h_status.p + 1, G->d_info.p, sizeof(int), hipMemcpyDeviceToHost, G->st));
+  if (G->sparse) { const int rc = G->solver.queue_status(G->h_status.p, G->st); if (rc) return rc; }
+  else { G->h_status.p[0] = 0; CS_HIP_TRY(hipMemcpyAsync(G->h_status.p + 1, G->d_info.p, sizeof(int), hipMemcpyDeviceToHost, G->st)); }
   CS_HIP_TRY(hipStreamSynchronize(G->st));
   return CS_OK;
 }
@@ -183,7 +153,7 @@ int build_structure(cs_pgo* G, const std::vector<int>& vi, const std::vector<int
   const size_t E = std::max(ne, 1), N = std::max(n, 1);
   if ((rc = G->err.ensure(7 * E)) || (rc = G->Ji.ensure(49 * E)) || (rc = G->Jj.ensure(49 * E)) || (rc = G->Hii.ensure(49 * E)) || (rc = G->Hij.ensure(49 * E)) ||
       (rc = G->Hjj.ensure(49 * E)) || (rc = G->bi.ensure(7 * E)) || (rc = G->bj.ensure(7 * E)) || (rc = G->chi2_each.ensure(E)) || (rc = G->S.ensure(N * N)) ||
-      (rc = G->b.ensure(N)) || (rc = G->x.ensure(N)) || (rc = G->diag.ensure(N)) || (rc = G->rec.ensure(4)) || (rc = G->d_info.ensure(1)) || (rc = G->sp_info.ensure(2)) ||
+      (rc = G->b.ensure(N)) || (rc = G->x.ensure(N)) || (rc = G->diag.ensure(N)) || (rc = G->rec.ensure(4)) || (rc = G->d_info.ensure(1)) ||
       (rc = G->h_rec.ensure(4)) || (rc = G->h_status.ensure(2))) return rc;
   // ---- which factorisation: the general sparse Cholesky where its plan (fill at most 35 % of the dense triangle, panels within the LDS)
   // and its grid (co-resident on this device) accept the graph; rocSOLVER otherwise.  CS_PGO_FORCE_DENSE=1 (read per call): always rocSOLVER.
@@ -194,22 +164,12 @@ int build_structure(cs_pgo* G, const std::vector<int>& vi, const std::vector<int
     for (int k = 0; k < ne; k++) if (vcol[vi[k]] >= 0 && vcol[vj[k]] >= 0) { adj[vi[k]].push_back(vj[k]); adj[vj[k]].push_back(vi[k]); }
     std::vector<int> dim(nv, 0);
     for (int v : free_ids) dim[v] = 7;
-    cs::SparsePlan plan;
-    cs::SparseGrids grids{0, 0};
-    if (cs::sparse_plan_build(adj, free_ids, dim, vcol, cs::sparse_max_panel_doubles(), 0.35, plan, 9000) && cs::sparse_grids(cs::sparse_max_panel_doubles(), plan.N, &grids)) {
-      G->sparse = true; G->plan = std::move(plan); G->grids = grids;
-      const cs::SparsePlan& SP = G->plan;
-      std::vector<int> v_rcol(SP.rcol), v_rpos(SP.rpos);
-      if (v_rcol.empty()) { v_rcol.push_back(0); v_rpos.push_back(0); }
-      if ((rc = upload(G->sp_ndim, SP.ndim, st)) || (rc = upload(G->sp_ncol, SP.ncol, st)) || (rc = upload(G->sp_sptr, SP.sptr, st)) || (rc = upload(G->sp_srow, SP.srow, st)) ||
-          (rc = upload(G->sp_sroff, SP.sroff, st)) || (rc = upload(G->sp_prow, SP.prow, st)) || (rc = upload(G->sp_rbase, SP.rbase, st)) || (rc = upload(G->sp_rent, SP.rent, st)) ||
-          (rc = upload(G->sp_rptr, SP.rptr, st)) || (rc = upload(G->sp_order, SP.order, st)) || (rc = upload(G->sp_poff, SP.poff, st)) || (rc = upload(G->sp_rcol, v_rcol, st)) ||
-          (rc = upload(G->sp_rpos, v_rpos, st)) || (rc = upload(G->sp_tcol, SP.tcol, st)) || (rc = G->sp_T.ensure((size_t)SP.n_tail * SP.n_tail + SP.n_tail + 1)) ||
-          (rc = G->sp_L.ensure((size_t)SP.nvals)) || (rc = G->sp_xs.ensure(9 * (size_t)(SP.N + 1))) || (rc = G->sp_done.ensure((size_t)SP.N + 1)) ||
-          (rc = G->sp_xdone.ensure((size_t)SP.N + 2))) return rc;
+    if (G->solver.build(adj, free_ids, dim, vcol, 0.35, 9000)) {      // (a plan that is refused is not uploaded, and G->sparse stays false)
+      G->sparse = true;
+      if ((rc = G->solver.upload(st))) return rc;
     }
   }
-  CS_HIP_TRY(hipStreamSynchronize(st));      // (the uploads read host vectors that end with this call)
+  CS_HIP_TRY(hipStreamSynchronize(st));      // (the uploads read host vectors that end with this call; the solver's asks for this wait too)
   return CS_OK;
 }
 
@@ -227,17 +187,15 @@ extern "C" {
 int cs_pgo_create(int device, cs_pgo** out) {
   if (!out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
+  { const int rc = cs::check_device(device); if (rc) return rc; }
   cs_pgo* G = new (std::nothrow) cs_pgo();
   if (!G) return CS_ERR_CAPACITY;
   struct Guard { cs_pgo* g; ~Guard() { if (g) cs_pgo_destroy(g); } } guard{G};
   G->device = device;
   CS_HIP_TRY(hipSetDevice(device));
   CS_HIP_TRY(hipStreamCreateWithFlags(&G->st, hipStreamNonBlocking));
-  PGO_ROC(rocblas_create_handle(&G->blas));
-  PGO_ROC(rocblas_set_stream(G->blas, G->st));
+  CS_ROC_TRY(rocblas_create_handle(&G->blas));
+  CS_ROC_TRY(rocblas_set_stream(G->blas, G->st));
   guard.g = nullptr;
   *out = G;
   return CS_OK;
@@ -249,12 +207,11 @@ void cs_pgo_destroy(cs_pgo* G) {
   if (G->st) (void)hipStreamSynchronize(G->st);
   if (G->blas) (void)rocblas_destroy_handle(G->blas);
   cs::DevBuf<double>* dd[] = {&G->est, &G->est_init, &G->est_bak, &G->meas, &G->info, &G->err, &G->Ji, &G->Jj, &G->Hii, &G->Hij, &G->Hjj, &G->bi, &G->bj, &G->chi2_each,
-                              &G->S, &G->b, &G->x, &G->diag, &G->rec, &G->io, &G->sp_L, &G->sp_xs, &G->sp_T};
+                              &G->S, &G->b, &G->x, &G->diag, &G->rec, &G->io};
   for (auto* d : dd) d->release();
-  cs::DevBuf<int>* di[] = {&G->vcol, &G->ei, &G->ej, &G->inc_ptr, &G->inc_edge, &G->d_info, &G->io_i, &G->sp_ndim, &G->sp_ncol, &G->sp_sptr, &G->sp_srow, &G->sp_sroff, &G->sp_prow,
-                           &G->sp_rbase, &G->sp_rent, &G->sp_rptr, &G->sp_rcol, &G->sp_rpos, &G->sp_order, &G->sp_tcol, &G->sp_info};
+  cs::DevBuf<int>* di[] = {&G->vcol, &G->ei, &G->ej, &G->inc_ptr, &G->inc_edge, &G->d_info, &G->io_i};
   for (auto* d : di) d->release();
-  G->d_fix_scale.release(); G->inc_side.release(); G->sp_poff.release(); G->sp_done.release(); G->sp_xdone.release();
+  G->d_fix_scale.release(); G->inc_side.release(); G->solver.release();
   G->h_rec.release(); G->h_status.release();
   if (G->st) (void)hipStreamDestroy(G->st);
   delete G;
@@ -351,15 +308,15 @@ int cs_pgo_linearize_edges(cs_pgo* G, double* err7, double* Ji49, double* Jj49) 
   return CS_OK;
 }
 
-// optimization_algorithm_levenberg.cpp:61-163 + sparse_optimizer.cpp:354-419, as cs_ba_optimize states them
+// optimization_algorithm_levenberg.cpp:61-163 (the policy: cs_lm.h) + sparse_optimizer.cpp:354-419
 int cs_pgo_optimize(cs_pgo* G, int iterations, int* iterations_done, double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap) {
   int rc = need(G, "cs_pgo_optimize", true); if (rc) return rc;
   if (iterations < 0) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(G->device));
   const double t_begin = now_ms();
   G->linearize_ms = G->solve_ms = 0;
-  int done = 0, nBad = 0;
-  double lambda = 0, ni = 2;
+  int done = 0;
+  cs::LmState lm;
   const cs::PgoView v = view_of(G);
   const size_t est_bytes = 8 * (size_t)G->nv * sizeof(double);
   for (int it = 0; it < iterations && G->n > 0; it++) {
@@ -368,20 +325,17 @@ int cs_pgo_optimize(cs_pgo* G, int iterations, int* iterations_done, double* chi
     if (it == 0 && !(G->user_lambda_init > 0)) { cs::pgo_launch_assemble(v, 0.0, G->st); CS_HIP_TRY(hipGetLastError()); }   // (for max |H_jj|; S is cleared by the first solve)
     rc = fetch_record(G); if (rc) return rc;
     G->linearize_ms += now_ms() - t0;
-    double currentChi = G->h_rec.p[0], tempChi = currentChi;
+    double currentChi = G->h_rec.p[0];
     const double iniChi = currentChi;
-    if (it == 0) {
-      lambda = G->user_lambda_init > 0 ? G->user_lambda_init : 1e-5 * G->h_rec.p[2];     // computeLambdaInit (:166-180), tau = 1e-5
-      ni = 2; nBad = 0;
-    }
+    if (it == 0) cs::lm_begin(lm, G->user_lambda_init, G->h_rec.p[2]);
     double rho = 0;
     int qmax = 0;
     do {
       t0 = now_ms();
       CS_HIP_TRY(hipMemcpyAsync(G->est_bak.p, G->est.p, est_bytes, hipMemcpyDeviceToDevice, G->st));       // push
       std::unique_lock<std::mutex> turn;
-      rc = solve(G, lambda, &turn); if (rc) return rc;
-      cs::pgo_launch_scale(v, lambda, G->st);
+      rc = solve(G, lm.lambda, &turn); if (rc) return rc;
+      cs::pgo_launch_scale(v, lm.lambda, G->st);
       cs::pgo_launch_update(v, G->st);
       cs::pgo_launch_errors(v, G->st);
       cs::pgo_launch_chi2(v, G->st);
@@ -389,36 +343,19 @@ int cs_pgo_optimize(cs_pgo* G, int iterations, int* iterations_done, double* chi
       rc = fetch_record(G); if (rc) return rc;
       if (turn.owns_lock()) turn.unlock();
       G->solve_ms += now_ms() - t0;
-      if (G->h_status.p[0] == 0x7fffffff) { cs_set_error("cs_pgo: sparse solver: grid not co-resident (wait timed out); set CS_PGO_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
-      const bool ok2 = G->h_status.p[0] == 0 && G->h_status.p[1] == 0;      // a non-positive pivot: a failed trial
-      tempChi = G->h_rec.p[0];
-      double scale = G->h_rec.p[1];
-      if (!ok2) { tempChi = std::numeric_limits<double>::max(); scale = 0.0; }    // (x is what the failed factorisation left: its scale term must not turn the sign of rho)
-      rho = currentChi - tempChi;
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - std::pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        lambda *= std::max(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
-      } else {
-        lambda *= ni;
-        ni *= 2;
+      const cs::SparseVerdict verdict = cs::sparse_verdict(G->h_status.p);
+      if (verdict == cs::SPARSE_TIMEOUT) { cs_set_error("cs_pgo: sparse solver: grid not co-resident (wait timed out); set CS_PGO_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
+      if (!cs::lm_trial(lm, currentChi, G->h_rec.p[0], G->h_rec.p[1], verdict == cs::SPARSE_OK, rho))      // (a non-positive pivot: a failed trial)
         CS_HIP_TRY(hipMemcpyAsync(G->est.p, G->est_bak.p, est_bytes, hipMemcpyDeviceToDevice, G->st));     // pop
-      }
       qmax++;
-    } while (rho < 0 && qmax < G->max_trials);
+    } while (cs::lm_again(rho, qmax, G->max_trials));
     if (done < hist_cap) {
       if (chi2_hist) chi2_hist[done] = currentChi;
-      if (lambda_hist) lambda_hist[done] = lambda;
+      if (lambda_hist) lambda_hist[done] = lm.lambda;
       if (trials_hist) trials_hist[done] = qmax;
     }
     done++;
-    if (qmax == G->max_trials || rho == 0) break;
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-    if (nBad >= 3) break;
+    if (cs::lm_stop(lm, rho, qmax, G->max_trials, iniChi, currentChi)) break;
   }
   CS_HIP_TRY(hipStreamSynchronize(G->st));
   if (iterations_done) *iterations_done = done;
@@ -467,7 +404,7 @@ int cs_pgo_correct_points(cs_pgo* G, int n, const int* ref_vertex, const double*
 int cs_pgo_solver_path(cs_pgo* G, int* path, double* sparse_fill) {
   int rc = need(G, "cs_pgo_solver_path", true); if (rc) return rc;
   if (path) *path = G->sparse ? CS_BA_PATH_SPARSE : CS_BA_PATH_DENSE;
-  if (sparse_fill) *sparse_fill = G->sparse ? (double)G->plan.nvals / (0.5 * (double)G->n * (double)G->n) : 0.0;
+  if (sparse_fill) *sparse_fill = G->sparse ? G->solver.fill(G->n) : 0.0;
   return CS_OK;
 }
 

@@ -57,9 +57,7 @@ void cs_pose_default_params(cs_pose_params* p) {
 int cs_pose_batch_create(int device, cs_pose_batch** out) {
   if (!out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { cs_set_error("no HIP device visible; libcubeslam_hip has no CPU fallback"); return CS_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { cs_set_error("device index out of range"); return CS_ERR_INVALID_ARG; }
+  { const int rc = cs::check_device(device); if (rc) return rc; }
   cs_pose_batch* B = new (std::nothrow) cs_pose_batch();
   if (!B) return CS_ERR_CAPACITY;
   struct Guard { cs_pose_batch* b; ~Guard() { if (b) cs_pose_batch_destroy(b); } } g{B};

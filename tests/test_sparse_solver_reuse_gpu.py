@@ -1,0 +1,139 @@
+"""The general sparse Cholesky's solver object (csrc/cs_sparse_solver.h) on handles that are used again.
+
+Its plan tables travel as one packed array and its workspace is grow-only, so what a second structure phase on the same handle could
+break is exactly this: a smaller plan inside a larger buffer, a larger one after a smaller, the sparse path taken again after another
+path, and two handles of different kinds taking turns in one process.  Every comparison is bit for bit against a fresh handle."""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from cube_slam_wu_amd import capi, synth_ba
+import pgo_cases as pc
+
+pytestmark = pytest.mark.gpu
+RING_ITERATIONS = pc.TRAJECTORIES[("free", 0.0)]
+
+
+@functools.lru_cache(maxsize=None)
+def _mesh16():
+    """tests/test_ba_solver_paths_gpu.py's mesh16: 256 cameras on a 16 x 16 grid, a graph no ordering can band."""
+    return synth_ba.make_mesh_problem(16, 16, 20000)
+
+
+def _pgo_result(G, iterations):
+    done = G.optimize(iterations)
+    chi, lam, trials = G.history()
+    return dict(done=done, vertices=G.vertices(), chi=chi.copy(), lam=lam.copy(), trials=trials.copy(), path=G.solver_path()[0])
+
+
+def _set_graph(G, g):
+    G.set_vertices(g["sim8"], g["fixed"], g["fix_scale"])
+    G.set_edges(g["vi"], g["vj"], g["meas8"], g.get("info49"))
+
+
+@functools.lru_cache(maxsize=None)
+def _pgo_alone(name):
+    """The graph on a fresh handle."""
+    G = capi.pose_graph_from_dict(pc.graph(name))
+    try:
+        return _pgo_result(G, pc.LAYOUT_ITERATIONS if name == "layout" else RING_ITERATIONS)
+    finally:
+        G.close()
+
+
+def _same_pgo(got, want, what):
+    assert got["done"] == want["done"], what
+    for k in ("vertices", "chi", "lam", "trials"):
+        assert np.array_equal(got[k], want[k]), (what, k)
+
+
+def _with_sparse(value, fn):
+    old = os.environ.get("CS_BA_SPARSE")
+    os.environ["CS_BA_SPARSE"] = value
+    try:
+        return fn()
+    finally:
+        if old is None:
+            os.environ.pop("CS_BA_SPARSE", None)
+        else:
+            os.environ["CS_BA_SPARSE"] = old
+
+
+def _ba_solve(G):
+    """Structure phase (it reads CS_BA_SPARSE on every run), linearisation, one damped solve -> (path, increment)."""
+    G.compute_errors()
+    G.build_system(dense_hpp=False)
+    ok, x = G.solve(1e-3)
+    assert ok
+    return G.solver_path(), x
+
+
+@functools.lru_cache(maxsize=None)
+def _ba_alone():
+    G = capi.ba_from_dict(_mesh16())
+    try:
+        return _with_sparse("1", lambda: _ba_solve(G))
+    finally:
+        G.close()
+
+
+def test_pgo_larger_plan_after_a_smaller_one():
+    A = _pgo_alone("layout")
+    assert A["path"] == "sparse"
+    B = capi.pose_graph_from_dict(pc.graph("free"))
+    try:
+        _pgo_result(B, RING_ITERATIONS)
+        _set_graph(B, pc.graph("layout"))
+        got = _pgo_result(B, pc.LAYOUT_ITERATIONS)
+    finally:
+        B.close()
+    assert got["path"] == "sparse"
+    _same_pgo(got, A, "layout after the ring")
+
+
+def test_pgo_smaller_plan_inside_a_larger_buffer():
+    A = _pgo_alone("free")
+    B = capi.pose_graph_from_dict(pc.graph("layout"))
+    try:
+        assert _pgo_result(B, pc.LAYOUT_ITERATIONS)["path"] == "sparse"
+        _set_graph(B, pc.graph("free"))
+        got = _pgo_result(B, RING_ITERATIONS)
+    finally:
+        B.close()
+    assert got["path"] == A["path"]
+    _same_pgo(got, A, "the ring after layout")
+
+
+def test_ba_sparse_again_after_another_path():
+    path0, x0 = _ba_alone()
+    assert path0 == "sparse"
+    G = capi.ba_from_dict(_mesh16())
+    try:
+        path1, x1 = _with_sparse("1", lambda: _ba_solve(G))
+        G.set_shard(0, 1)                         # (marks the structure stale: the next call runs the structure phase again)
+        path2, _ = _with_sparse("0", lambda: _ba_solve(G))
+        G.set_shard(0, 1)
+        path3, x3 = _with_sparse("1", lambda: _ba_solve(G))
+    finally:
+        G.close()
+    assert path1 == "sparse" and path2 in ("band", "dense") and path3 == "sparse"
+    assert np.array_equal(x3, x1) and np.array_equal(x3, x0)
+
+
+def test_pgo_and_ba_take_turns_in_one_process():
+    want_p, (want_path, want_x) = _pgo_alone("layout"), _ba_alone()
+    P = capi.pose_graph_from_dict(pc.graph("layout"))
+    B = capi.ba_from_dict(_mesh16())
+    P2 = capi.pose_graph_from_dict(pc.graph("layout"))
+    try:
+        got_p = _pgo_result(P, pc.LAYOUT_ITERATIONS)
+        path, x = _with_sparse("1", lambda: _ba_solve(B))
+        got_p2 = _pgo_result(P2, pc.LAYOUT_ITERATIONS)
+    finally:
+        P.close(); B.close(); P2.close()
+    assert got_p["path"] == "sparse" and path == want_path == "sparse"
+    _same_pgo(got_p, want_p, "the pose graph before the bundle adjustment")
+    assert np.array_equal(x, want_x)
+    _same_pgo(got_p2, want_p, "the pose graph after the bundle adjustment")
