@@ -608,10 +608,18 @@ class BaProblem:
     def append_edges_cuboid(self, cam, cub, meas10, info81):
         cam, cub = _i32(cam), _i32(cub)
         _chk(lib().cs_ba_append_edges_cuboid(self.h, len(cam), _ip(cam), _ip(cub), _dp(_f64(meas10, (-1, 10))), _dp(_f64(info81, (-1, 81)))), "cs_ba_append_edges_cuboid")
+        self.n_cub = getattr(self, "n_cub", 0) + len(cam)
+
+    def append_edges_cuboid_proj(self, cam, cub, meas4, info16, K9):
+        cam, cub = _i32(cam), _i32(cub)
+        _chk(lib().cs_ba_append_edges_cuboid_proj(self.h, len(cam), _ip(cam), _ip(cub), _dp(_f64(meas4, (-1, 4))), _dp(_f64(info16, (-1, 16))), _dp(_f64(K9, (-1, 9)))),
+             "cs_ba_append_edges_cuboid_proj")
+        self.n_cproj = getattr(self, "n_cproj", 0) + len(cam)
 
     def append_edges_odom(self, ci, cj, meas7, info36):
         ci, cj = _i32(ci), _i32(cj)
         _chk(lib().cs_ba_append_edges_odom(self.h, len(ci), _ip(ci), _ip(cj), _dp(_f64(meas7, (-1, 7))), _dp(_f64(info36, (-1, 36)))), "cs_ba_append_edges_odom")
+        self.n_odom = getattr(self, "n_odom", 0) + len(ci)
 
     def compute_errors(self):
         chi = C.c_double()

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "ba_edge_class.h"
 #include "ba_types.h"
 #include "cs_hip_util.h"
 #include "cs_lm.h"
@@ -264,10 +265,13 @@ struct cs_ba {
   DBuf<int> d_cub_mine;     // sharded + eliminated cuboids: 1 = this rank owns the cuboid (holds all its edges)
   DBuf<int> d_cubS_ptr, d_cubS_cam, d_ce_slot, d_cub_tile, d_cub_coef, d_elim_fail, d_slotE_ptr, d_slotE_idx;
   DBuf<double> cub_M, cub_Dinv;
-  int n_proj = 0, n_cub = 0, n_odom = 0;   // n_cub = EdgeSE3Cuboid + EdgeSE3CuboidProj edges (the combined list ce_cam / ce_cub)
+  // The three pose-edge classes as the caller gave them (ba_edge_class.h): endpoints, payload, kernels and levels of EdgeSE3Cuboid,
+  // EdgeSE3CuboidProj and EdgeSE3Expmap, kept until the structure phase puts them on the device.
+  cs::EdgeClassHost ec[3] = {{cs::kPoseEdgeDims[0]}, {cs::kPoseEdgeDims[1]}, {cs::kPoseEdgeDims[2]}};
+  cs::EdgeClassHost& pose_class(int edge_class) { return ec[edge_class - CS_EDGE_CUBOID]; }
+  const cs::EdgeClassHost& pose_class(int edge_class) const { return ec[edge_class - CS_EDGE_CUBOID]; }
+  int n_proj = 0, n_cub = 0, n_odom = 0;   // n_cub = EdgeSE3Cuboid + EdgeSE3CuboidProj edges (the combined list ce_cam / ce_cub); n_cub, n_cub3 and n_odom are written by finalize_structure only
   int n_cub3 = 0;                          // of which EdgeSE3Cuboid (they come first)
-  std::vector<int> u3_cam, u3_cub, up_cam, up_cub;      // the caller's two lists
-  std::vector<double> h_pe_meas, h_pe_info, h_pe_K;
   DBuf<double> pe_meas, pe_info, pe_K;
   std::vector<int> e_pt, e_cam;      // projection edges, caller order: the mono edges [0, n_proj - n_stereo), the stereo edges behind them (g2o's edge order)
   // stereo projection edges (EdgeStereoSE3ProjectXYZ; cs_ba_set_edges_proj_stereo): counted in n_proj, their payload in the caller's order on the
@@ -282,7 +286,7 @@ struct cs_ba {
   DBuf<int> d_src;                   // device copy of slot_src (the gathers of the structure phase)
   std::unique_ptr<int[]> slot_src;   // point-major slot -> caller edge (uninitialised storage with head room: kept across structure phases)
   size_t slot_src_cap = 0; int slot_src_n = 0;
-  std::vector<int> ce_cam, ce_cub, oe_i, oe_j;
+  std::vector<int> ce_cam, ce_cub;
   bool structure_dirty = true;
   // device buffers
   DBuf<double> cams, points, cubes, cams_bak, points_bak, cubes_bak;
@@ -304,8 +308,6 @@ struct cs_ba {
   DBuf<int> d_band_info;
   int n_pairs = 0, nb_chi = 1, n_chi_partials = 1;
   long long schur_entries = 0;
-  // raw edge payloads kept until finalisation
-  std::vector<double> h_ce_meas, h_ce_info, h_oe_meas, h_oe_info;
   // the projection edges' payload (88 bytes per edge) goes straight to the device when the edges are set, in the caller's order;
   // the structure phase permutes it there (ba_gather_rows_kernel)
   DBuf<double> raw_uv, raw_info, raw_intr, raw_huber;
@@ -320,8 +322,7 @@ struct cs_ba {
   bool have_huber = false;
   // robust kernels (cs_ba_set_robust_kernels; cs_robust.h): kinds per edge in the caller's order, empty = none of the class has one.
   // The projection edges' deltas live in raw_huber (Huber is the fast path: kinds all 0 / 1 -> no kind array on the device).
-  std::vector<int> rk_proj, rk_cub3, rk_cproj, rk_odom;
-  std::vector<double> rd_cub3, rd_cproj, rd_odom;
+  std::vector<int> rk_proj;
   DBuf<int> d_pm_rk, d_cm_rk, d_ce_rk, d_oe_rk;
   DBuf<double> d_ce_rdelta, d_oe_rdelta;
   int rk_off = 0;                    // cs_ba_set_kernels_enabled: bit (1 << cs_edge_class) set = the class's kernels are switched off (BaView::rk_off)
@@ -330,7 +331,7 @@ struct cs_ba {
   // (ba_kernels.hip: edge_off) plus d_lvl, one byte per edge in e_pt's order (mono edges, then stereo), which exists only once a level may be 1; a
   // cuboid / odometry edge's level is folded into d_ce_active / d_oe_active (h_ce_shard / h_oe_shard keep the sharding's own words).
   // lvl_host_stale: cs_ba_classify_edges wrote d_lvl on the device and the host vectors have not been refreshed from it yet.
-  std::vector<unsigned char> lvl_mono, lvl_stereo, lvl_cub3, lvl_cproj, lvl_odom;
+  std::vector<unsigned char> lvl_mono, lvl_stereo;      // (the pose classes' levels: ec[].lvl)
   DBuf<unsigned char> d_lvl;
   bool lvl_on_device = false, lvl_host_stale = false;
   int lvl_nM = 0, lvl_nS = 0;        // d_lvl's layout: the class counts of the structure phase that filled it
@@ -501,15 +502,23 @@ bool combined_proj_levels(const cs_ba* B, int nM, int nS, std::vector<unsigned c
   std::copy(B->lvl_stereo.begin(), B->lvl_stereo.begin() + std::min<size_t>(B->lvl_stereo.size(), nS), out.begin() + nM);
   return true;
 }
+// One per-edge attribute (level, kernel kind, kernel delta) of the camera-cuboid edges in ce_cam's order -- the EdgeSE3Cuboid list, then the
+// EdgeSE3CuboidProj list -- from the two classes' vectors; zero where a class's vector is empty or shorter than its list.  At least n_min entries.
+template <class T>
+std::vector<T> combined_cuboid(const cs_ba* B, std::vector<T> cs::EdgeClassHost::*attr, size_t n_min = 0) {
+  const size_t n3 = (size_t)B->n_cub3, np = (size_t)B->n_cub - n3;
+  const std::vector<T>&v3 = B->pose_class(CS_EDGE_CUBOID).*attr, &vp = B->pose_class(CS_EDGE_CUBOID_PROJ).*attr;
+  std::vector<T> out(std::max(n3 + np, n_min), T(0));
+  std::copy_n(v3.begin(), std::min(v3.size(), n3), out.begin());
+  std::copy_n(vp.begin(), std::min(vp.size(), np), out.begin() + n3);
+  return out;
+}
 // d_ce_active / d_oe_active = the sharding's words with the levels folded in
 void fold_pose_levels(const cs_ba* B, std::vector<int>& ca, std::vector<int>& oa) {
   ca = B->h_ce_shard; oa = B->h_oe_shard;
-  for (size_t k = 0; k < ca.size(); k++) {
-    const size_t n3 = (size_t)B->n_cub3;
-    const bool off = k < n3 ? (k < B->lvl_cub3.size() && B->lvl_cub3[k]) : (k - n3 < B->lvl_cproj.size() && B->lvl_cproj[k - n3]);
-    if (off) ca[k] = 0;
-  }
-  for (size_t k = 0; k < oa.size(); k++) if (k < B->lvl_odom.size() && B->lvl_odom[k]) oa[k] = 0;
+  const std::vector<unsigned char> lc = combined_cuboid(B, &cs::EdgeClassHost::lvl), &lo = B->pose_class(CS_EDGE_ODOM).lvl;
+  for (size_t k = 0; k < ca.size(); k++) if (lc[k]) ca[k] = 0;
+  for (size_t k = 0; k < oa.size(); k++) if (k < lo.size() && lo[k]) oa[k] = 0;
 }
 
 int finalize_structure(cs_ba* B) {
@@ -525,10 +534,13 @@ int finalize_structure(cs_ba* B) {
   auto mark = [&](const char* what) { if (prof) { double t = now_ms(); fprintf(stderr, "[ba structure] %-28s %8.2f ms   (%d device allocations so far)\n", what, t - t_ph, g_dbuf_reallocs); t_ph = t; } };
   const int nc = B->nc, no = B->no, np = B->np;
   // camera-cuboid edges of both kinds as one list: EdgeSE3Cuboid first, then EdgeSE3CuboidProj
-  B->ce_cam = B->u3_cam; B->ce_cam.insert(B->ce_cam.end(), B->up_cam.begin(), B->up_cam.end());
-  B->ce_cub = B->u3_cub; B->ce_cub.insert(B->ce_cub.end(), B->up_cub.begin(), B->up_cub.end());
-  B->n_cub3 = (int)B->u3_cam.size();
+  const cs::EdgeClassHost &c3 = B->pose_class(CS_EDGE_CUBOID), &cp = B->pose_class(CS_EDGE_CUBOID_PROJ), &od = B->pose_class(CS_EDGE_ODOM);
+  const std::vector<int>&oe_i = od.a, &oe_j = od.b;
+  B->ce_cam = c3.a; B->ce_cam.insert(B->ce_cam.end(), cp.a.begin(), cp.a.end());
+  B->ce_cub = c3.b; B->ce_cub.insert(B->ce_cub.end(), cp.b.begin(), cp.b.end());
+  B->n_cub3 = c3.size();
   B->n_cub = (int)B->ce_cam.size();
+  B->n_odom = od.size();
   // ---- index mapping (sparse_optimizer.cpp:166-190): non-marginalised vertices by id, then the points
   B->cam_col_ref.assign(nc, -1); B->cub_col_ref.assign(no, -1); B->pt_lm.assign(np, -1);
   {
@@ -722,7 +734,7 @@ int finalize_structure(cs_ba* B) {
   for (int k = 0; k < B->n_cub; k++)
     if (B->ce_cam[k] < 0 || B->ce_cam[k] >= nc || B->ce_cub[k] < 0 || B->ce_cub[k] >= no) { cs_set_error("cuboid edge index out of range"); return CS_ERR_INVALID_ARG; }
   for (int k = 0; k < B->n_odom; k++)
-    if (B->oe_i[k] < 0 || B->oe_i[k] >= nc || B->oe_j[k] < 0 || B->oe_j[k] >= nc) { cs_set_error("odometry edge index out of range"); return CS_ERR_INVALID_ARG; }
+    if (oe_i[k] < 0 || oe_i[k] >= nc || oe_j[k] < 0 || oe_j[k] >= nc) { cs_set_error("odometry edge index out of range"); return CS_ERR_INVALID_ARG; }
   // ---- solver ordering of the pose vertices: reverse Cuthill-McKee on the block graph of the reduced system
   // (camera-camera through shared landmarks and odometry edges, camera-cuboid through cuboid edges), so that S is
   // banded for trajectory-shaped graphs.  The ordering only permutes the linear system; g2o's order is kept for x/b
@@ -793,7 +805,7 @@ int finalize_structure(cs_ba* B) {
       const int p = gorder[run_first[r]];
       for (int a = cam_cnt[p]; a < cam_cnt[p + 1]; a++) for (int b = a + 1; b < cam_cnt[p + 1]; b++) link(cams_of[a], cams_of[b]);
     }
-    for (int k = 0; k < B->n_odom; k++) link(B->oe_i[k], B->oe_j[k]);
+    for (int k = 0; k < B->n_odom; k++) link(oe_i[k], oe_j[k]);
     for (int k = 0; k < B->ext_n; k++) if (B->ext_e4[4 * k + 3] >= 0) link((B->ext_e4[4 * k] ? nc : 0) + B->ext_e4[4 * k + 1], (B->ext_e4[4 * k + 2] ? nc : 0) + B->ext_e4[4 * k + 3]);
     if (!elim) { for (int k = 0; k < B->n_cub; k++) link(B->ce_cam[k], nc + B->ce_cub[k]); }
     else for (int o = 0; o < no; o++) if (!B->cub_fixed[o]) for (size_t a = 0; a < cub_cams[o].size(); a++) for (size_t b = a + 1; b < cub_cams[o].size(); b++) link(cub_cams[o][a], cub_cams[o][b]);
@@ -1411,10 +1423,10 @@ int finalize_structure(cs_ba* B) {
     for (size_t k = 0; k < owner.size(); k++) idx[fill[owner[k]]++] = (int)k;
   };
   std::vector<int> p1, i1, p2, i2, p3, i3, p4, i4;
-  csr(nc, B->ce_cam, p1, i1); csr(nc, B->oe_i, p2, i2); csr(nc, B->oe_j, p3, i3); csr(no, B->ce_cub, p4, i4);
+  csr(nc, B->ce_cam, p1, i1); csr(nc, oe_i, p2, i2); csr(nc, oe_j, p3, i3); csr(no, B->ce_cub, p4, i4);
   UP(B->cam_ce_ptr, p1); UP(B->cam_ce_idx, i1); UP(B->cam_oei_ptr, p2); UP(B->cam_oei_idx, i2);
   UP(B->cam_oej_ptr, p3); UP(B->cam_oej_idx, i3); UP(B->cub_ce_ptr, p4); UP(B->cub_ce_idx, i4);
-  UP(B->d_ce_cam, B->ce_cam); UP(B->d_ce_cub, B->ce_cub); UP(B->d_oe_i, B->oe_i); UP(B->d_oe_j, B->oe_j);
+  UP(B->d_ce_cam, B->ce_cam); UP(B->d_ce_cub, B->ce_cub); UP(B->d_oe_i, oe_i); UP(B->d_oe_j, oe_j);
   {
     std::vector<int> ca(B->n_cub), oa(B->n_odom);
     // cuboid edges: with their camera's rank, or -- cuboids eliminated -- all edges of a cuboid with the rank of its lowest-index camera.
@@ -1440,8 +1452,8 @@ int finalize_structure(cs_ba* B) {
       }
       for (int k = 0; k < B->n_odom; k++) {
         int lo = 0x7fffffff;
-        if (B->cam_col[B->oe_i[k]] >= 0) lo = std::min(lo, B->cam_col[B->oe_i[k]]);
-        if (B->cam_col[B->oe_j[k]] >= 0) lo = std::min(lo, B->cam_col[B->oe_j[k]]);
+        if (B->cam_col[oe_i[k]] >= 0) lo = std::min(lo, B->cam_col[oe_i[k]]);
+        if (B->cam_col[oe_j[k]] >= 0) lo = std::min(lo, B->cam_col[oe_j[k]]);
         oa[k] = (lo == 0x7fffffff ? 0 : rank_of_col(lo)) == B->shard_rank;
       }
     } else {
@@ -1449,7 +1461,7 @@ int finalize_structure(cs_ba* B) {
       for (int k = 0; k < B->n_cub; k++) first[B->ce_cub[k]] = std::min(first[B->ce_cub[k]], B->ce_cam[k]);
       for (int o = 0; o < no; o++) cub_owner[o] = first[o] == 0x7fffffff ? 0 : cam_rank(first[o], nc, B->shard_n);
       for (int k = 0; k < B->n_cub; k++) ca[k] = (B->elim ? cub_owner[B->ce_cub[k]] : cam_rank(B->ce_cam[k], nc, B->shard_n)) == B->shard_rank;
-      for (int k = 0; k < B->n_odom; k++) oa[k] = cam_rank(B->oe_j[k], nc, B->shard_n) == B->shard_rank;
+      for (int k = 0; k < B->n_odom; k++) oa[k] = cam_rank(oe_j[k], nc, B->shard_n) == B->shard_rank;
     }
     {
       std::vector<int> mine(std::max(1, no), 0);
@@ -1457,31 +1469,26 @@ int finalize_structure(cs_ba* B) {
       UP(B->d_cub_mine, mine);
     }
     B->h_ce_shard = ca; B->h_oe_shard = oa;
-    B->lvl_cub3.resize(any_level(B->lvl_cub3) ? (size_t)B->n_cub3 : 0); B->lvl_cproj.resize(any_level(B->lvl_cproj) ? (size_t)(B->n_cub - B->n_cub3) : 0); B->lvl_odom.resize(any_level(B->lvl_odom) ? (size_t)B->n_odom : 0);
+    for (cs::EdgeClassHost& c : B->ec) c.lvl.resize(any_level(c.lvl) ? (size_t)c.size() : 0);
     fold_pose_levels(B, ca, oa);      // (a level-1 edge gives zero blocks and no chi2, like an edge of another rank)
     UP(B->d_ce_active, ca); UP(B->d_oe_active, oa);
   }
   {   // kernels of the camera-cuboid edges (EdgeSE3Cuboid list, then EdgeSE3CuboidProj list) and of the odometry edges
-    bool any = false;
-    for (int kd : B->rk_cub3) any |= kd != 0;
-    for (int kd : B->rk_cproj) any |= kd != 0;
-    if (any) {
-      std::vector<int> kk(std::max(1, B->n_cub), 0); std::vector<double> dd(std::max(1, B->n_cub), 0.0);
-      for (size_t k = 0; k < B->rk_cub3.size() && (int)k < B->n_cub3; k++) { kk[k] = B->rk_cub3[k]; dd[k] = B->rd_cub3[k]; }
-      for (size_t k = 0; k < B->rk_cproj.size() && B->n_cub3 + (int)k < B->n_cub; k++) { kk[B->n_cub3 + k] = B->rk_cproj[k]; dd[B->n_cub3 + k] = B->rd_cproj[k]; }
-      UP(B->d_ce_rk, kk); UP(B->d_ce_rdelta, dd);
+    auto any_kernel = [](const std::vector<int>& kinds) { for (int kd : kinds) if (kd != 0) return true; return false; };
+    const std::vector<int> kc = combined_cuboid(B, &cs::EdgeClassHost::rk, 1);
+    if (any_kernel(kc)) {
+      const std::vector<double> dc = combined_cuboid(B, &cs::EdgeClassHost::rd, 1);
+      UP(B->d_ce_rk, kc); UP(B->d_ce_rdelta, dc);
     } else { B->d_ce_rk.release(); B->d_ce_rdelta.release(); }
-    any = false;
-    for (int kd : B->rk_odom) any |= kd != 0;
-    if (any) {
-      std::vector<int> kk(B->rk_odom); std::vector<double> dd(B->rd_odom);
+    if (any_kernel(od.rk)) {
+      std::vector<int> kk(od.rk); std::vector<double> dd(od.rd);
       kk.resize(std::max(1, B->n_odom), 0); dd.resize(std::max(1, B->n_odom), 0.0);
       UP(B->d_oe_rk, kk); UP(B->d_oe_rdelta, dd);
     } else { B->d_oe_rk.release(); B->d_oe_rdelta.release(); }
   }
   mark("  pose edge lists");
-  UP(B->ce_meas, B->h_ce_meas); UP(B->ce_info, B->h_ce_info); UP(B->oe_meas, B->h_oe_meas); UP(B->oe_info, B->h_oe_info);
-  UP(B->pe_meas, B->h_pe_meas); UP(B->pe_info, B->h_pe_info); UP(B->pe_K, B->h_pe_K);
+  UP(B->ce_meas, c3.meas); UP(B->ce_info, c3.info); UP(B->oe_meas, od.meas); UP(B->oe_info, od.info);
+  UP(B->pe_meas, cp.meas); UP(B->pe_info, cp.info); UP(B->pe_K, cp.extra);
   AL(B->ce_Hcc, 36 * (size_t)B->n_cub); AL(B->ce_Hoo, 81 * (size_t)B->n_cub); AL(B->ce_Hco, 54 * (size_t)B->n_cub); AL(B->ce_bc, 6 * (size_t)B->n_cub); AL(B->ce_bo, 9 * (size_t)B->n_cub);
   AL(B->oe_Hii, 36 * (size_t)B->n_odom); AL(B->oe_Hjj, 36 * (size_t)B->n_odom); AL(B->oe_Hij, 36 * (size_t)B->n_odom); AL(B->oe_bi, 6 * (size_t)B->n_odom); AL(B->oe_bj, 6 * (size_t)B->n_odom);
   mark("  pose edge measurements");
@@ -2132,39 +2139,26 @@ int cs_ba_append_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, cons
   return CS_OK;
   CS_GUARD_END("cs_ba_append_edges_proj")
 }
-int cs_ba_append_edges_cuboid(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
-  if (!B || n < 0 || (n && (!cam || !cub || !meas10 || !info81))) return CS_ERR_INVALID_ARG;
-  CS_GUARD_BEGIN
-  B->u3_cam.insert(B->u3_cam.end(), cam, cam + n); B->u3_cub.insert(B->u3_cub.end(), cub, cub + n);
-  if (!B->rk_cub3.empty()) { B->rk_cub3.resize(B->u3_cam.size(), 0); B->rd_cub3.resize(B->u3_cam.size(), 0.0); }
-  B->h_ce_meas.insert(B->h_ce_meas.end(), meas10, meas10 + 10 * (size_t)n); B->h_ce_info.insert(B->h_ce_info.end(), info81, info81 + 81 * (size_t)n);
+// The six entry points of the pose-edge classes: cs_ba_set_edges_* replaces the class's list (its kernels and levels go with it), cs_ba_append_edges_*
+// extends it (cs::EdgeClassHost::add).
+static int pose_edges_add(cs_ba* B, int edge_class, bool replace, int n, const int* a, const int* b, const double* meas, const double* info, const double* extra) {
+  if (!B || !B->pose_class(edge_class).add(replace, n, a, b, meas, info, extra)) return CS_ERR_INVALID_ARG;
   B->structure_dirty = true;
   return CS_OK;
+}
+int cs_ba_append_edges_cuboid(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
+  CS_GUARD_BEGIN
+  return pose_edges_add(B, CS_EDGE_CUBOID, false, n, cam, cub, meas10, info81, nullptr);
   CS_GUARD_END("cs_ba_append_edges_cuboid")
 }
 int cs_ba_append_edges_cuboid_proj(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
-  if (!B || n < 0 || (n && (!cam || !cub || !meas4 || !info16 || !K9))) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
-  B->up_cam.insert(B->up_cam.end(), cam, cam + n); B->up_cub.insert(B->up_cub.end(), cub, cub + n);
-  if (!B->rk_cproj.empty()) { B->rk_cproj.resize(B->up_cam.size(), 0); B->rd_cproj.resize(B->up_cam.size(), 0.0); }
-  B->h_pe_meas.insert(B->h_pe_meas.end(), meas4, meas4 + 4 * (size_t)n); B->h_pe_info.insert(B->h_pe_info.end(), info16, info16 + 16 * (size_t)n);
-  B->h_pe_K.insert(B->h_pe_K.end(), K9, K9 + 9 * (size_t)n);
-  B->structure_dirty = true;
-  return CS_OK;
+  return pose_edges_add(B, CS_EDGE_CUBOID_PROJ, false, n, cam, cub, meas4, info16, K9);
   CS_GUARD_END("cs_ba_append_edges_cuboid_proj")
 }
 int cs_ba_append_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const double* meas7, const double* info36) {
-  if (!B || n < 0 || (n && (!ci || !cj || !meas7 || !info36))) return CS_ERR_INVALID_ARG;
   CS_GUARD_BEGIN
-  B->oe_i.insert(B->oe_i.end(), ci, ci + n); B->oe_j.insert(B->oe_j.end(), cj, cj + n);
-  const size_t m0 = B->h_oe_meas.size();
-  B->h_oe_meas.insert(B->h_oe_meas.end(), meas7, meas7 + 7 * (size_t)n);
-  for (int k = 0; k < n; k++) { cs::Pose p = cs::pose_load(&B->h_oe_meas[m0 + 7 * (size_t)k]); cs::pose_normalize(p); cs::pose_store(p, &B->h_oe_meas[m0 + 7 * (size_t)k]); }
-  B->h_oe_info.insert(B->h_oe_info.end(), info36, info36 + 36 * (size_t)n);
-  B->n_odom += n;
-  if (!B->rk_odom.empty()) { B->rk_odom.resize(B->n_odom, 0); B->rd_odom.resize(B->n_odom, 0.0); }
-  B->structure_dirty = true;
-  return CS_OK;
+  return pose_edges_add(B, CS_EDGE_ODOM, false, n, ci, cj, meas7, info36, nullptr);
   CS_GUARD_END("cs_ba_append_edges_odom")
 }
 
@@ -2258,48 +2252,19 @@ int cs_ba_append_edges_proj_stereo(cs_ba* B, int n, const int* pt, const int* ca
   CS_GUARD_END("cs_ba_append_edges_proj_stereo")
 }
 
-static int cs_ba_set_edges_cuboid_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
-  if (!B || n < 0 || (n && (!cam || !cub || !meas10 || !info81))) return CS_ERR_INVALID_ARG;
-  B->u3_cam.assign(cam, cam + n); B->u3_cub.assign(cub, cub + n);
-  B->rk_cub3.clear(); B->rd_cub3.clear(); B->lvl_cub3.clear();
-  B->h_ce_meas.assign(meas10, meas10 + 10 * (size_t)n); B->h_ce_info.assign(info81, info81 + 81 * (size_t)n);
-  B->structure_dirty = true;
-  return CS_OK;
-}
 int cs_ba_set_edges_cuboid(cs_ba* B, int n, const int* cam, const int* cub, const double* meas10, const double* info81) {
   CS_GUARD_BEGIN
-  return cs_ba_set_edges_cuboid_impl(B, n, cam, cub, meas10, info81);
+  return pose_edges_add(B, CS_EDGE_CUBOID, true, n, cam, cub, meas10, info81, nullptr);
   CS_GUARD_END("cs_ba_set_edges_cuboid")
-}
-
-static int cs_ba_set_edges_cuboid_proj_impl(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
-  if (!B || n < 0 || (n && (!cam || !cub || !meas4 || !info16 || !K9))) return CS_ERR_INVALID_ARG;
-  B->up_cam.assign(cam, cam + n); B->up_cub.assign(cub, cub + n);
-  B->rk_cproj.clear(); B->rd_cproj.clear(); B->lvl_cproj.clear();
-  B->h_pe_meas.assign(meas4, meas4 + 4 * (size_t)n); B->h_pe_info.assign(info16, info16 + 16 * (size_t)n); B->h_pe_K.assign(K9, K9 + 9 * (size_t)n);
-  B->structure_dirty = true;
-  return CS_OK;
 }
 int cs_ba_set_edges_cuboid_proj(cs_ba* B, int n, const int* cam, const int* cub, const double* meas4, const double* info16, const double* K9) {
   CS_GUARD_BEGIN
-  return cs_ba_set_edges_cuboid_proj_impl(B, n, cam, cub, meas4, info16, K9);
+  return pose_edges_add(B, CS_EDGE_CUBOID_PROJ, true, n, cam, cub, meas4, info16, K9);
   CS_GUARD_END("cs_ba_set_edges_cuboid_proj")
-}
-
-static int cs_ba_set_edges_odom_impl(cs_ba* B, int n, const int* ci, const int* cj, const double* meas7, const double* info36) {
-  if (!B || n < 0 || (n && (!ci || !cj || !meas7 || !info36))) return CS_ERR_INVALID_ARG;
-  B->n_odom = n;
-  B->oe_i.assign(ci, ci + n); B->oe_j.assign(cj, cj + n);
-  B->rk_odom.clear(); B->rd_odom.clear(); B->lvl_odom.clear();
-  B->h_oe_meas.assign(meas7, meas7 + 7 * (size_t)n);
-  for (int k = 0; k < n; k++) { cs::Pose p = cs::pose_load(&B->h_oe_meas[7 * (size_t)k]); cs::pose_normalize(p); cs::pose_store(p, &B->h_oe_meas[7 * (size_t)k]); }
-  B->h_oe_info.assign(info36, info36 + 36 * (size_t)n);
-  B->structure_dirty = true;
-  return CS_OK;
 }
 int cs_ba_set_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const double* meas7, const double* info36) {
   CS_GUARD_BEGIN
-  return cs_ba_set_edges_odom_impl(B, n, ci, cj, meas7, info36);
+  return pose_edges_add(B, CS_EDGE_ODOM, true, n, ci, cj, meas7, info36, nullptr);
   CS_GUARD_END("cs_ba_set_edges_odom")
 }
 
@@ -2357,31 +2322,41 @@ int cs_ba_set_external_callback(cs_ba* B, cs_external_fn fn, void* ctx) {
   return CS_OK;
 }
 
+// What the handle keeps per edge class, whichever way the class stores it: the caller's edge count (-1: no such class), the levels, the kernel
+// kinds and the kernel deltas (nullptr: the mono projection edges', which live on the device in raw_huber).
+struct EdgeClassRef { int count; std::vector<unsigned char>* levels; std::vector<int>* kinds; std::vector<double>* deltas; };
+static EdgeClassRef edge_class_ref(cs_ba* B, int edge_class) {
+  switch (edge_class) {
+    case CS_EDGE_PROJ: return {B->n_proj - B->n_stereo, &B->lvl_mono, &B->rk_proj, nullptr};
+    case CS_EDGE_PROJ_STEREO: return {B->n_stereo, &B->lvl_stereo, &B->rk_stereo, &B->h_se_huber};
+    case CS_EDGE_CUBOID: case CS_EDGE_CUBOID_PROJ: case CS_EDGE_ODOM: { cs::EdgeClassHost& c = B->pose_class(edge_class); return {c.size(), &c.lvl, &c.rk, &c.rd}; }
+    default: return {-1, nullptr, nullptr, nullptr};
+  }
+}
+static const int kEdgeClasses[5] = {CS_EDGE_PROJ, CS_EDGE_PROJ_STEREO, CS_EDGE_CUBOID, CS_EDGE_CUBOID_PROJ, CS_EDGE_ODOM};      // (in the order of the dump's level trailer)
+static bool any_class_level(cs_ba* B) { for (int c : kEdgeClasses) if (any_level(*edge_class_ref(B, c).levels)) return true; return false; }
+
 // Robust kernels of one edge class (OptimizableGraph::Edge::setRobustKernel, core/optimizable_graph.h:419-423; the kernels:
 // core/robust_kernel_impl.cpp:78-165).  Replaces the class's kernels; n = the class's edge count.
 static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const int* kind, const double* delta) {
   if (!B || n < 0 || (n && kind && !delta)) return CS_ERR_INVALID_ARG;
-  const int have = edge_class == CS_EDGE_PROJ ? B->n_proj - B->n_stereo : edge_class == CS_EDGE_PROJ_STEREO ? B->n_stereo : edge_class == CS_EDGE_CUBOID ? (int)B->u3_cam.size() : edge_class == CS_EDGE_CUBOID_PROJ ? (int)B->up_cam.size()
-                 : edge_class == CS_EDGE_ODOM ? B->n_odom : -1;
-  if (have < 0) { cs_set_error("cs_ba_set_robust_kernels: unknown edge class"); return CS_ERR_INVALID_ARG; }
-  if (!kind) n = have;         // removing the class's kernels: the count is the library's own (n is ignored)
-  if (n != have) { cs_set_error("cs_ba_set_robust_kernels: n must equal the number of edges of the class (set the edges first)"); return CS_ERR_INVALID_ARG; }
+  const EdgeClassRef cls = edge_class_ref(B, edge_class);
+  if (cls.count < 0) { cs_set_error("cs_ba_set_robust_kernels: unknown edge class"); return CS_ERR_INVALID_ARG; }
+  if (!kind) n = cls.count;         // removing the class's kernels: the count is the library's own (n is ignored)
+  if (n != cls.count) { cs_set_error("cs_ba_set_robust_kernels: n must equal the number of edges of the class (set the edges first)"); return CS_ERR_INVALID_ARG; }
   std::vector<int> kk(n, 0); std::vector<double> dd(n, 0.0);
   for (int k = 0; k < n && kind; k++) {
     if (kind[k] < 0 || kind[k] >= cs::RK_KINDS) { cs_set_error("cs_ba_set_robust_kernels: unknown kernel kind"); return CS_ERR_INVALID_ARG; }
     if (kind[k] != cs::RK_NONE && !(delta[k] > 0)) { cs_set_error("cs_ba_set_robust_kernels: a kernel needs delta > 0"); return CS_ERR_INVALID_ARG; }
     kk[k] = kind[k]; dd[k] = kind[k] != cs::RK_NONE ? delta[k] : 0.0;
   }
-  if (edge_class == CS_EDGE_PROJ) {
+  if (edge_class == CS_EDGE_PROJ) {      // the mono projection edges' deltas live on the device
     CS_HIP_TRY(hipSetDevice(B->device));
     CS_HIP_TRY(hipStreamSynchronize(B->st));
     int rc = B->raw_huber.upload_ptr(dd.data(), (size_t)n); if (rc) return rc;    // delta per edge, 0 = none
     B->have_huber = true;
-    B->rk_proj = kk;
-  } else if (edge_class == CS_EDGE_PROJ_STEREO) { B->h_se_huber = dd; B->rk_stereo = kk; }
-  else if (edge_class == CS_EDGE_CUBOID) { B->rk_cub3 = kk; B->rd_cub3 = dd; }
-  else if (edge_class == CS_EDGE_CUBOID_PROJ) { B->rk_cproj = kk; B->rd_cproj = dd; }
-  else { B->rk_odom = kk; B->rd_odom = dd; }
+  } else *cls.deltas = dd;
+  *cls.kinds = kk;
   B->structure_dirty = true;
   return CS_OK;
 }
@@ -2393,13 +2368,6 @@ int cs_ba_set_robust_kernels(cs_ba* B, int edge_class, int n, const int* kind, c
 
 static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap);
 // ---- edge levels, kernels switched in place, classification, rounds: ORB-SLAM2's LocalBundleAdjustment / BundleAdjustment on the device ----------
-static int class_count(const cs_ba* B, int edge_class) {
-  return edge_class == CS_EDGE_PROJ ? B->n_proj - B->n_stereo : edge_class == CS_EDGE_PROJ_STEREO ? B->n_stereo : edge_class == CS_EDGE_CUBOID ? (int)B->u3_cam.size()
-         : edge_class == CS_EDGE_CUBOID_PROJ ? (int)B->up_cam.size() : edge_class == CS_EDGE_ODOM ? B->n_odom : -1;
-}
-static std::vector<unsigned char>* class_levels(cs_ba* B, int edge_class) {
-  return edge_class == CS_EDGE_PROJ ? &B->lvl_mono : edge_class == CS_EDGE_PROJ_STEREO ? &B->lvl_stereo : edge_class == CS_EDGE_CUBOID ? &B->lvl_cub3 : edge_class == CS_EDGE_CUBOID_PROJ ? &B->lvl_cproj : &B->lvl_odom;
-}
 static int levels_refuse_shard(const cs_ba* B, const char* who) {
   if (B->shard_n <= 1) return CS_OK;
   cs_set_error(std::string(who) + ": edge levels are not supported on a sharded handle");
@@ -2432,13 +2400,13 @@ static int push_pose_levels(cs_ba* B) {
 static int cs_ba_set_edge_levels_impl(cs_ba* B, int edge_class, int n, const unsigned char* level) {
   if (!B) return CS_ERR_INVALID_ARG;
   if (int rs = levels_refuse_shard(B, "cs_ba_set_edge_levels")) return rs;
-  const int have = class_count(B, edge_class);
-  if (have < 0) { cs_set_error("cs_ba_set_edge_levels: unknown edge class"); return CS_ERR_INVALID_ARG; }
-  if (n != have) { cs_set_error("cs_ba_set_edge_levels: n must equal the number of edges of the class"); return CS_ERR_INVALID_ARG; }
+  const EdgeClassRef cls = edge_class_ref(B, edge_class);
+  if (cls.count < 0) { cs_set_error("cs_ba_set_edge_levels: unknown edge class"); return CS_ERR_INVALID_ARG; }
+  if (n != cls.count) { cs_set_error("cs_ba_set_edge_levels: n must equal the number of edges of the class"); return CS_ERR_INVALID_ARG; }
   for (int k = 0; k < n && level; k++) if (level[k] > 1) { cs_set_error("cs_ba_set_edge_levels: a level is 0 or 1"); return CS_ERR_INVALID_ARG; }
   CS_HIP_TRY(hipSetDevice(B->device));
   int rc = refresh_levels_host(B); if (rc) return rc;
-  std::vector<unsigned char>& l = *class_levels(B, edge_class);
+  std::vector<unsigned char>& l = *cls.levels;
   if (level) l.assign(level, level + n); else l.clear();
   B->have_system = false;          // (the system on the device is the old active set's)
   if (B->structure_dirty) return CS_OK;      // (the structure phase that is due applies them)
@@ -2452,17 +2420,17 @@ int cs_ba_set_edge_levels(cs_ba* B, int edge_class, int n, const unsigned char* 
 int cs_ba_get_edge_levels(cs_ba* B, int edge_class, int n, unsigned char* level) {
   CS_GUARD_BEGIN
   if (!B || (n && !level)) return CS_ERR_INVALID_ARG;
-  const int have = class_count(B, edge_class);
-  if (have < 0) { cs_set_error("cs_ba_get_edge_levels: unknown edge class"); return CS_ERR_INVALID_ARG; }
-  if (n != have) { cs_set_error("cs_ba_get_edge_levels: n must equal the number of edges of the class"); return CS_ERR_INVALID_ARG; }
+  const EdgeClassRef cls = edge_class_ref(B, edge_class);
+  if (cls.count < 0) { cs_set_error("cs_ba_get_edge_levels: unknown edge class"); return CS_ERR_INVALID_ARG; }
+  if (n != cls.count) { cs_set_error("cs_ba_get_edge_levels: n must equal the number of edges of the class"); return CS_ERR_INVALID_ARG; }
   int rc = refresh_levels_host(B); if (rc) return rc;
-  const std::vector<unsigned char>& l = *class_levels(B, edge_class);
+  const std::vector<unsigned char>& l = *cls.levels;
   for (int k = 0; k < n; k++) level[k] = (size_t)k < l.size() ? l[k] : 0;
   return CS_OK;
   CS_GUARD_END("cs_ba_get_edge_levels")
 }
 int cs_ba_set_kernels_enabled(cs_ba* B, int edge_class, int enabled) {
-  if (!B || class_count(B, edge_class) < 0) return CS_ERR_INVALID_ARG;
+  if (!B || edge_class_ref(B, edge_class).count < 0) return CS_ERR_INVALID_ARG;
   const int bit = 1 << edge_class, now = enabled ? (B->rk_off & ~bit) : (B->rk_off | bit);
   if (now != B->rk_off) B->have_system = false;
   B->rk_off = now;
@@ -2644,7 +2612,7 @@ int cs_ba_pop(cs_ba* B) {
 int cs_ba_set_shard(cs_ba* B, int rank, int n_ranks) {
   if (!B || n_ranks < 1 || rank < 0 || rank >= n_ranks) return CS_ERR_INVALID_ARG;
   if (B->n_stereo > 0 && n_ranks > 1) { cs_set_error("cs_ba_set_shard: stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
-  if (n_ranks > 1 && (B->lvl_host_stale || any_level(B->lvl_mono) || any_level(B->lvl_stereo) || any_level(B->lvl_cub3) || any_level(B->lvl_cproj) || any_level(B->lvl_odom))) {
+  if (n_ranks > 1 && (B->lvl_host_stale || any_class_level(B))) {
     cs_set_error("cs_ba_set_shard: edge levels are not supported on a sharded handle"); return CS_ERR_INVALID_ARG;
   }
   B->shard_rank = rank; B->shard_n = n_ranks;
@@ -3022,8 +2990,9 @@ static int cs_ba_get_system_impl(cs_ba* B, double* Hpp, double* Hll9, double* Hp
       if (ca < 0 || cb < 0) continue;
       for (int r = 0; r < 6; r++) for (int q = 0; q < 9; q++) { double val = hco[54 * (size_t)k + 9 * r + q]; Hpp[(size_t)(ca + r) * n + cb + q] += val; Hpp[(size_t)(cb + q) * n + ca + r] += val; }
     }
+    const cs::EdgeClassHost& od = B->pose_class(CS_EDGE_ODOM);
     for (int k = 0; k < B->n_odom; k++) {
-      int ca = B->cam_col_ref[B->oe_i[k]], cb = B->cam_col_ref[B->oe_j[k]];
+      int ca = B->cam_col_ref[od.a[k]], cb = B->cam_col_ref[od.b[k]];
       if (ca < 0 || cb < 0) continue;
       for (int r = 0; r < 6; r++) for (int q = 0; q < 6; q++) { double val = hij[36 * (size_t)k + 6 * r + q]; Hpp[(size_t)(ca + r) * n + cb + q] += val; Hpp[(size_t)(cb + q) * n + ca + r] += val; }
     }
@@ -3310,12 +3279,8 @@ static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_
   // (level-0 edges only: a level-1 edge is outside the active set and may well be non-finite)
   DBuf<unsigned char> lce, loe;
   struct FreeL { DBuf<unsigned char>* a; DBuf<unsigned char>* b; ~FreeL() { a->release(); b->release(); } } guard_l{&lce, &loe};
-  if (any_level(B->lvl_cub3) || any_level(B->lvl_cproj)) {
-    std::vector<unsigned char> l((size_t)B->n_cub, 0);
-    for (size_t k = 0; k < l.size(); k++) { const size_t n3 = (size_t)B->n_cub3; l[k] = k < n3 ? (k < B->lvl_cub3.size() && B->lvl_cub3[k]) : (k - n3 < B->lvl_cproj.size() && B->lvl_cproj[k - n3]); }
-    if ((rc = lce.upload(l))) return rc;
-  }
-  if (any_level(B->lvl_odom)) { std::vector<unsigned char> l(B->lvl_odom); l.resize((size_t)B->n_odom, 0); if ((rc = loe.upload(l))) return rc; }
+  { const std::vector<unsigned char> l = combined_cuboid(B, &cs::EdgeClassHost::lvl); if (any_level(l) && (rc = lce.upload(l))) return rc; }
+  if (any_level(B->pose_class(CS_EDGE_ODOM).lvl)) { std::vector<unsigned char> l(B->pose_class(CS_EDGE_ODOM).lvl); l.resize((size_t)B->n_odom, 0); if ((rc = loe.upload(l))) return rc; }
   cs::ba_launch_edge_chi(v, chi.p, B->st, lce.p, loe.p);
   struct Arr { const char* name; const double* p; long long n; int per; const char* owner; };
   std::vector<Arr> arrs = {
@@ -3379,6 +3344,7 @@ static void debug_nan_scan(cs_ba* B, const char* where) {
 // then the arrays in the order written below, each raw little-endian.  Shard settings and external edges are not part of it.
 namespace {
 struct DumpHeader { char magic[8]; int v[16]; };
+constexpr int kDumpPoseCounts = 7, kDumpStereoCounts = 13;      // v[7 + 2 i], v[8 + 2 i]: edges and kernels of pose-edge class i (cs_ba::ec); v[13 .. 15]: the stereo class
 struct LevelTrailer { char magic[8]; int rk_off; int n[5]; };      // optional, behind the arrays: levels of CS_EDGE_PROJ, _PROJ_STEREO, _CUBOID, _CUBOID_PROJ, _ODOM (n[i] = 0: all at level 0)
 template <class T> bool wr(FILE* f, const std::vector<T>& a) { return a.empty() || fwrite(a.data(), sizeof(T), a.size(), f) == a.size(); }
 template <class T> bool rd(FILE* f, std::vector<T>& a, size_t n) { a.resize(n); return n == 0 || fread(a.data(), sizeof(T), n, f) == n; }
@@ -3388,7 +3354,7 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   { const int rl = refresh_levels_host(B); if (rl) return rl; }
-  const int nst = B->n_stereo, np_e = B->n_proj - nst, n3 = (int)B->u3_cam.size(), n4 = (int)B->up_cam.size(), n6 = B->n_odom;
+  const int nst = B->n_stereo, np_e = B->n_proj - nst;
   std::vector<double> cams(7 * (size_t)B->nc), cubs(10 * (size_t)B->no), pts(3 * (size_t)B->np), uv(2 * (size_t)np_e), info(4 * (size_t)np_e), intr(4 * (size_t)np_e), hub(B->have_huber ? np_e : 0);
   auto d2h = [&](std::vector<double>& h, const double* d) -> int { if (!h.empty()) CS_HIP_TRY(hipMemcpy(h.data(), d, 8 * h.size(), hipMemcpyDeviceToHost)); return CS_OK; };
   int rc;
@@ -3400,34 +3366,29 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   if (!f) { cs_set_error(std::string("cs_ba_dump: cannot open ") + path); return CS_ERR_INVALID_ARG; }
   DumpHeader H{};
   std::memcpy(H.magic, "CSBA0002", 8);
-  const int counts[16] = {B->nc, B->no, B->np, B->cuboids_first, np_e, B->have_huber ? 1 : 0, (int)B->rk_proj.size(), n3, (int)B->rk_cub3.size(), n4, (int)B->rk_cproj.size(), n6, (int)B->rk_odom.size(), nst, B->h_se_huber.empty() ? 0 : 1, (int)B->rk_stereo.size()};
-  std::memcpy(H.v, counts, sizeof(counts));
+  const int head[7] = {B->nc, B->no, B->np, B->cuboids_first, np_e, B->have_huber ? 1 : 0, (int)B->rk_proj.size()}, tail[3] = {nst, B->h_se_huber.empty() ? 0 : 1, (int)B->rk_stereo.size()};
+  std::memcpy(H.v, head, sizeof(head)); std::memcpy(H.v + kDumpStereoCounts, tail, sizeof(tail));
+  for (int i = 0; i < 3; i++) { H.v[kDumpPoseCounts + 2 * i] = B->ec[i].size(); H.v[kDumpPoseCounts + 2 * i + 1] = (int)B->ec[i].rk.size(); }
   bool ok = fwrite(&H, sizeof(H), 1, f) == 1;
   ok = ok && wr(f, cams) && wr(f, B->cam_fixed) && wr(f, cubs) && wr(f, B->cub_fixed) && wr(f, pts) && wr(f, B->pt_fixed);
   const std::vector<int> m_pt(B->e_pt.begin(), B->e_pt.begin() + np_e), m_cam(B->e_cam.begin(), B->e_cam.begin() + np_e), s_pt(B->e_pt.begin() + np_e, B->e_pt.end()), s_cam(B->e_cam.begin() + np_e, B->e_cam.end());
   ok = ok && wr(f, m_pt) && wr(f, m_cam) && wr(f, uv) && wr(f, info) && wr(f, intr) && wr(f, hub) && wr(f, B->rk_proj);
-  ok = ok && wr(f, B->u3_cam) && wr(f, B->u3_cub) && wr(f, B->h_ce_meas) && wr(f, B->h_ce_info) && wr(f, B->rk_cub3) && wr(f, B->rd_cub3);
-  ok = ok && wr(f, B->up_cam) && wr(f, B->up_cub) && wr(f, B->h_pe_meas) && wr(f, B->h_pe_info) && wr(f, B->h_pe_K) && wr(f, B->rk_cproj) && wr(f, B->rd_cproj);
-  ok = ok && wr(f, B->oe_i) && wr(f, B->oe_j) && wr(f, B->h_oe_meas) && wr(f, B->h_oe_info) && wr(f, B->rk_odom) && wr(f, B->rd_odom);
+  for (const cs::EdgeClassHost& c : B->ec) ok = ok && wr(f, c.a) && wr(f, c.b) && wr(f, c.meas) && wr(f, c.info) && wr(f, c.extra) && wr(f, c.rk) && wr(f, c.rd);
   // (the stereo projection edges last: a graph without one dumps the bytes it always did)
   ok = ok && wr(f, s_pt) && wr(f, s_cam) && wr(f, B->h_se_uv) && wr(f, B->h_se_ur) && wr(f, B->h_se_intr) && wr(f, B->h_se_sinfo) && wr(f, B->h_se_huber) && wr(f, B->rk_stereo);
   // (edge levels and kernel switches behind everything else, and only when there is one: a handle without them dumps the bytes it always did)
-  {
-    const int cls[5] = {CS_EDGE_PROJ, CS_EDGE_PROJ_STEREO, CS_EDGE_CUBOID, CS_EDGE_CUBOID_PROJ, CS_EDGE_ODOM};
-    bool any = B->rk_off != 0;
-    for (int c : cls) any = any || any_level(*class_levels(B, c));
-    if (any) {
-      LevelTrailer T{};
-      std::memcpy(T.magic, "CSLV0001", 8);
-      T.rk_off = B->rk_off;
-      std::vector<unsigned char> lv[5];
-      for (int i = 0; i < 5; i++) {
-        if (any_level(*class_levels(B, cls[i]))) { lv[i] = *class_levels(B, cls[i]); lv[i].resize((size_t)class_count(B, cls[i]), 0); }
-        T.n[i] = (int)lv[i].size();
-      }
-      ok = ok && fwrite(&T, sizeof(T), 1, f) == 1;
-      for (int i = 0; i < 5; i++) ok = ok && wr(f, lv[i]);
+  if (B->rk_off != 0 || any_class_level(B)) {
+    LevelTrailer T{};
+    std::memcpy(T.magic, "CSLV0001", 8);
+    T.rk_off = B->rk_off;
+    std::vector<unsigned char> lv[5];
+    for (int i = 0; i < 5; i++) {
+      const EdgeClassRef c = edge_class_ref(B, kEdgeClasses[i]);
+      if (any_level(*c.levels)) { lv[i] = *c.levels; lv[i].resize((size_t)c.count, 0); }
+      T.n[i] = (int)lv[i].size();
     }
+    ok = ok && fwrite(&T, sizeof(T), 1, f) == 1;
+    for (int i = 0; i < 5; i++) ok = ok && wr(f, lv[i]);
   }
   ok = (fclose(f) == 0) && ok;
   if (!ok) { cs_set_error(std::string("cs_ba_dump: write to ") + path + " failed"); return CS_ERR_INVALID_ARG; }
@@ -3447,14 +3408,17 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   DumpHeader H;
   if (fread(&H, sizeof(H), 1, f) != 1 || std::memcmp(H.magic, "CSBA0002", 8) != 0) { cs_set_error("cs_ba_load: not a cs_ba dump (magic CSBA0002)"); return CS_ERR_INVALID_ARG; }
   for (int i = 0; i < 16; i++) if (H.v[i] < 0) { cs_set_error("cs_ba_load: corrupt header"); return CS_ERR_INVALID_ARG; }
-  const int nc = H.v[0], no = H.v[1], np = H.v[2], cf = H.v[3], npe = H.v[4], hh = H.v[5], nrk = H.v[6], n3 = H.v[7], nrk3 = H.v[8], n4 = H.v[9], nrk4 = H.v[10], n6 = H.v[11], nrk6 = H.v[12], nst = H.v[13], sth = H.v[14], nrks = H.v[15];
-  std::vector<double> cams, cubs, pts, uv, info, intr, hub, m10, i81, rd3, m4, i16, k9, rd4, m7, i36, rd6;
-  std::vector<int> camf, cubf, ptf, ept, ecam, rkp, c3, o3, rk3, c4, o4, rk4, oi, oj, rk6;
+  const int nc = H.v[0], no = H.v[1], np = H.v[2], cf = H.v[3], npe = H.v[4], hh = H.v[5], nrk = H.v[6], nst = H.v[13], sth = H.v[14], nrks = H.v[15];
+  std::vector<double> cams, cubs, pts, uv, info, intr, hub;
+  std::vector<int> camf, cubf, ptf, ept, ecam, rkp;
+  cs::EdgeClassHost pe[3] = {{cs::kPoseEdgeDims[0]}, {cs::kPoseEdgeDims[1]}, {cs::kPoseEdgeDims[2]}};      // the pose-edge classes as the file has them
   bool ok = rd(f, cams, 7 * (size_t)nc) && rd(f, camf, nc) && rd(f, cubs, 10 * (size_t)no) && rd(f, cubf, no) && rd(f, pts, 3 * (size_t)np) && rd(f, ptf, np);
   ok = ok && rd(f, ept, npe) && rd(f, ecam, npe) && rd(f, uv, 2 * (size_t)npe) && rd(f, info, 4 * (size_t)npe) && rd(f, intr, 4 * (size_t)npe) && rd(f, hub, hh ? npe : 0) && rd(f, rkp, nrk);
-  ok = ok && rd(f, c3, n3) && rd(f, o3, n3) && rd(f, m10, 10 * (size_t)n3) && rd(f, i81, 81 * (size_t)n3) && rd(f, rk3, nrk3) && rd(f, rd3, nrk3);
-  ok = ok && rd(f, c4, n4) && rd(f, o4, n4) && rd(f, m4, 4 * (size_t)n4) && rd(f, i16, 16 * (size_t)n4) && rd(f, k9, 9 * (size_t)n4) && rd(f, rk4, nrk4) && rd(f, rd4, nrk4);
-  ok = ok && rd(f, oi, n6) && rd(f, oj, n6) && rd(f, m7, 7 * (size_t)n6) && rd(f, i36, 36 * (size_t)n6) && rd(f, rk6, nrk6) && rd(f, rd6, nrk6);
+  for (int i = 0; i < 3; i++) {
+    cs::EdgeClassHost& c = pe[i];
+    const size_t n = (size_t)H.v[kDumpPoseCounts + 2 * i], nk = (size_t)H.v[kDumpPoseCounts + 2 * i + 1];
+    ok = ok && rd(f, c.a, n) && rd(f, c.b, n) && rd(f, c.meas, c.d.meas * n) && rd(f, c.info, c.d.info * n) && rd(f, c.extra, c.d.extra * n) && rd(f, c.rk, nk) && rd(f, c.rd, nk) && (nk == 0 || nk == n);
+  }
   std::vector<int> spt, scam, rks; std::vector<double> suv, sur, sintr, ssinfo, shub;
   ok = ok && rd(f, spt, nst) && rd(f, scam, nst) && rd(f, suv, 2 * (size_t)nst) && rd(f, sur, nst) && rd(f, sintr, 4 * (size_t)nst) && rd(f, ssinfo, 10 * (size_t)nst) && rd(f, shub, sth ? nst : 0) && rd(f, rks, nrks);
   LevelTrailer LT{};
@@ -3462,11 +3426,11 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   bool have_levels = false;
   if (ok && fread(&LT, sizeof(LT), 1, f) == 1) {
     have_levels = true;
-    const int cnt5[5] = {npe, nst, n3, n4, n6};
+    const int cnt5[5] = {npe, nst, H.v[kDumpPoseCounts], H.v[kDumpPoseCounts + 2], H.v[kDumpPoseCounts + 4]};
     ok = std::memcmp(LT.magic, "CSLV0001", 8) == 0;
     for (int i = 0; i < 5 && ok; i++) ok = (LT.n[i] == 0 || LT.n[i] == cnt5[i]) && rd(f, lv[i], (size_t)LT.n[i]);
   }
-  if (!ok || (nrks && nrks != nst) || (nrk && nrk != npe) || (nrk3 && nrk3 != n3) || (nrk4 && nrk4 != n4) || (nrk6 && nrk6 != n6)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
+  if (!ok || (nrks && nrks != nst) || (nrk && nrk != npe)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
   cs_ba* B = nullptr;
   int rc = cs_ba_create(device, &B); if (rc) return rc;
   struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{B};
@@ -3484,18 +3448,16 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
     if ((rc = cs_ba_set_edges_proj_stereo(B, nst, spt.data(), scam.data(), uvr.data(), i9.data(), k5.data(), sth ? shub.data() : nullptr))) return rc;
     if (nrks && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_PROJ_STEREO, nst, rks.data(), shub.data()))) return rc;
   }
-  if (n3 && (rc = cs_ba_set_edges_cuboid(B, n3, c3.data(), o3.data(), m10.data(), i81.data()))) return rc;
-  if (nrk3 && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_CUBOID, n3, rk3.data(), rd3.data()))) return rc;
-  if (n4 && (rc = cs_ba_set_edges_cuboid_proj(B, n4, c4.data(), o4.data(), m4.data(), i16.data(), k9.data()))) return rc;
-  if (nrk4 && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_CUBOID_PROJ, n4, rk4.data(), rd4.data()))) return rc;
-  if (n6 && (rc = cs_ba_set_edges_odom(B, n6, oi.data(), oj.data(), m7.data(), i36.data()))) return rc;
-  if (n6) B->h_oe_meas = m7;
-  if (nrk6 && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_ODOM, n6, rk6.data(), rd6.data()))) return rc;
+  for (int i = 0; i < 3; i++) {
+    const cs::EdgeClassHost& c = pe[i];
+    if (c.size() && (rc = pose_edges_add(B, CS_EDGE_CUBOID + i, true, c.size(), c.a.data(), c.b.data(), c.meas.data(), c.info.data(), c.extra.data()))) return rc;
+    if (c.size() && c.d.meas_is_pose) B->ec[i].meas = c.meas;      // (the dumped quaternions come back with their exact bits, as the cameras' above)
+    if (!c.rk.empty() && (rc = cs_ba_set_robust_kernels(B, CS_EDGE_CUBOID + i, c.size(), c.rk.data(), c.rd.data()))) return rc;
+  }
   if (have_levels) {
-    const int cls[5] = {CS_EDGE_PROJ, CS_EDGE_PROJ_STEREO, CS_EDGE_CUBOID, CS_EDGE_CUBOID_PROJ, CS_EDGE_ODOM};
     for (int i = 0; i < 5; i++) {
-      if (LT.n[i] && (rc = cs_ba_set_edge_levels(B, cls[i], LT.n[i], lv[i].data()))) return rc;
-      if ((LT.rk_off >> cls[i]) & 1) { if ((rc = cs_ba_set_kernels_enabled(B, cls[i], 0))) return rc; }
+      if (LT.n[i] && (rc = cs_ba_set_edge_levels(B, kEdgeClasses[i], LT.n[i], lv[i].data()))) return rc;
+      if ((LT.rk_off >> kEdgeClasses[i]) & 1) { if ((rc = cs_ba_set_kernels_enabled(B, kEdgeClasses[i], 0))) return rc; }
     }
   }
   *out = B;

@@ -1503,6 +1503,36 @@ def test_growing_graph_append_equals_rebuild_every_frame():
     G.close()
 
 
+def test_pose_edge_classes_grown_by_append_equal_set_at_once_bitwise():
+    """The three pose-edge classes (48 EdgeSE3Cuboid, 48 EdgeSE3CuboidProj, 11 odometry edges of a 12-camera graph) set at once, and grown: a prefix
+    of each class set, one structure phase, the rest appended (cs_ba_append_edges_cuboid, _cuboid_proj -- a single-edge tail --, _odom).  Same vertices,
+    same estimates, and the same tables and payloads on the device, so the kernels see the same input: chi2, every array of the linear system and
+    three LM iterations are equal bit for bit."""
+    pr = synth_ba.make_problem(n_cams=12, n_points=300, n_cuboids=4, bbox_edges=True)
+    classes = ((("ce_cam", "ce_cub", "ce_meas", "ce_info"), 20), (("pe_cam", "pe_cub", "pe_meas", "pe_info", "pe_K"), 47), (("oe_i", "oe_j", "oe_meas", "oe_info"), 5))
+    assert [len(pr[k[0]]) for k, _ in classes] == [48, 48, 11]
+    A = capi.ba_from_dict(pr)
+    B = capi.BaProblem(pr["cams"], pr["cam_fixed"], pr["cuboids"], pr["cub_fixed"], pr["points"], pr["pt_fixed"])
+    B.set_edges_proj(pr["e_pt"], pr["e_cam"], pr["e_uv"], pr["e_info"], pr["e_intr"], pr["e_huber"])
+    for f, (keys, cut) in zip((B.set_edges_cuboid, B.set_edges_cuboid_proj, B.set_edges_odom), classes):
+        f(*[pr[k][:cut] for k in keys])
+    chi_prefix = B.compute_errors()
+    for f, (keys, cut) in zip((B.append_edges_cuboid, B.append_edges_cuboid_proj, B.append_edges_odom), classes):
+        f(*[pr[k][cut:] for k in keys])
+    assert (B.n_cub, B.n_cproj, B.n_odom) == (A.n_cub, A.n_cproj, A.n_odom) == (48, 48, 11)
+    chi_a, chi_b = A.compute_errors(), B.compute_errors()
+    assert chi_a == chi_b and chi_prefix < chi_a          # (the appended edges count)
+    for x, y in zip(A.build_system(), B.build_system()):
+        assert x.shape == y.shape and np.array_equal(x, y)
+    n_a, n_b = A.optimize(3), B.optimize(3)
+    assert n_a == n_b >= 1
+    for x, y in zip(A.history(), B.history()):
+        assert np.array_equal(x, y)
+    for x, y in zip(A.state(), B.state()):
+        assert np.array_equal(x, y)
+    A.close(); B.close()
+
+
 def test_general_sparse_reduced_solve_on_a_covisibility_mesh():
     """A survey-flight graph (cameras on a 2-D grid looking down: synth_ba.make_mesh_problem): the cameras' covisibility graph is a mesh
     that reverse Cuthill-McKee cannot band narrowly.  The general sparse path (CS_BA_SPARSE=1: minimum-degree block ordering + symbolic
