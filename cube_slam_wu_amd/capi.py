@@ -67,6 +67,7 @@ DECLARED_SYMBOLS = [
     "cs_last_error", "cs_device_count", "cs_diag_build", "cs_detect_default_params", "cs_box_rois", "cs_cam_euler_zyx", "cs_detector_create",
     "cs_detector_destroy", "cs_detect_cuboids", "cs_batch_create", "cs_batch_max_boxes", "cs_batch_run", "cs_batch_submit", "cs_batch_collect",
     "cs_bgr_to_gray", "cs_edge_distance_maps", "cs_edge_distance_maps_multi", "cs_detect_cuboids_gray", "cs_batch_create_gray", "cs_batch_refill_gray", "cs_batch_refill_wait", "cs_batch_destroy", "cs_batch_last_timing", "cs_batch_debug_candidates", "cs_batch_debug_kept", "cs_batch_set_debug", "cs_batch_set_pipeline_chunks", "cs_detect_lines_gray", "cs_detect_lines_batch", "cs_detect_lines_last_timing", "cs_detect_lsd_gray", "cs_detect_lsd_batch", "cs_detect_lsd_last_timing",
+    "cs_check_score_atan2",
 ]
 
 _lib = None
@@ -103,6 +104,18 @@ def default_params(**kw):
             raise KeyError(k)
         setattr(p, k, v)
     return p
+
+
+def check_score_atan2(y, x):
+    """The scorer's atan2 call sequence on the device, one pair per lane: (values, accepted flags of the lean evaluation)."""
+    y, x = np.ascontiguousarray(y, np.float64), np.ascontiguousarray(x, np.float64)
+    if y.shape != x.shape or y.ndim != 1:
+        raise ValueError("y and x must be 1-D arrays of the same length")
+    out, acc = np.zeros(len(y)), np.zeros(len(y), np.int32)
+    rc = lib().cs_check_score_atan2(_dp(y), _dp(x), len(y), _dp(out), acc.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        raise RuntimeError("cs_check_score_atan2 failed (%d): %s" % (rc, last_error()))
+    return out, acc.astype(bool)
 
 
 def box_rois(box5, img_w, img_h, sample_height=False):

@@ -642,6 +642,30 @@ int cs_diag_build(void) {
 #endif
 }
 
+int cs_check_score_atan2(const double* y, const double* x, int n, double* out, int* accepted) {
+  if (n < 0 || (n > 0 && (!y || !x || !out || !accepted))) { cs_set_error("cs_check_score_atan2: null array"); return CS_ERR_INVALID_ARG; }
+  if (n > (1 << 30)) { cs_set_error("cs_check_score_atan2: more than 2^30 pairs"); return CS_ERR_CAPACITY; }
+  if (int rc = cs::check_device(0)) return rc;
+  if (n == 0) return CS_OK;
+  CS_HIP_TRY(hipSetDevice(0));
+  DevBuf<double> d;       // y, x, out
+  DevBuf<int> a;
+  int rc = d.ensure(3 * (size_t)n);
+  if (rc == CS_OK) rc = a.ensure((size_t)n);
+  auto run = [&]() -> int {
+    CS_HIP_TRY(hipMemcpy(d.p, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(d.p + n, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    cs::launch_score_atan2_check(d.p, d.p + n, n, d.p + 2 * (size_t)n, a.p, nullptr);
+    CS_HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipMemcpy(out, d.p + 2 * (size_t)n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    CS_HIP_TRY(hipMemcpy(accepted, a.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    return CS_OK;
+  };
+  if (rc == CS_OK) rc = run();
+  d.release(); a.release();
+  return rc;
+}
+
 void cs_detect_default_params(cs_detect_params* p) {
   if (!p) return;
   p->consider_config_1 = 1; p->consider_config_2 = 1;

@@ -29,6 +29,7 @@
 
 #include "../../include/cubeslam_hip.h"
 #include "detect_types.h"
+#include "cs_atan2_lean.h"
 
 namespace cs {
 
@@ -637,6 +638,35 @@ __device__ __forceinline__ float score_edge_sum(int cfg, const double (*CXt)[260
   return sum_dist;
 }
 
+// The scorer's atan2 (six edges per proposal): cs_atan2_lean, and cs_atan2 for the lanes it declined -- a special argument pair
+// or, for about 4e-5 of the ordinary ones, a value too close to a rounding boundary.  The vote keeps every part of cs_atan2
+// off the path of a wavefront without a declined lane; wherever the lean function accepts it returns cs_atan2's bits
+// (cs_atan2_lean.h), so the value is cs_atan2's in every lane.  cs_atan2 stays inlined behind the vote, its double-double
+// evaluation being the only call: a wrapper function around it would not be a leaf, and the frame of a non-leaf function
+// would be the kernel's only scratch memory.
+__device__ __forceinline__ double score_atan2(double dy, double dx, bool* accepted = nullptr) {
+  double a;                                                // (every lane gets a value: from the lean function where it accepts, from cs_atan2 below where not)
+  const bool ok = cs_atan2_lean(dy, dx, &a);
+  if (__builtin_amdgcn_ballot_w64(!ok) != 0) {        // (the vote: __any(!ok) as a ballot)
+    if (!ok) a = cs_atan2(dy, dx);
+  }
+  if (accepted) *accepted = ok;
+  return a;
+}
+
+// cs_check_score_atan2: score_atan2 over n argument pairs, one per lane, in wavefronts of 64 as score_kernel's
+__global__ __launch_bounds__(256) void score_atan2_check_kernel(const double* __restrict__ y, const double* __restrict__ x, int n, double* __restrict__ out, int* __restrict__ accepted) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  bool ok;
+  out[i] = score_atan2(y[i], x[i], &ok);
+  accepted[i] = ok ? 1 : 0;
+}
+void launch_score_atan2_check(const double* y, const double* x, int n, double* out, int* accepted, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(score_atan2_check_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y, x, n, out, accepted);
+}
+
 template <bool CAP>
 __global__ __launch_bounds__(256) void score_kernel(DetectDeviceView v, long long slot_total, double short_sq_bound) {
   // [coordinate: x0..x7, y0..y7][lane]: every lane keeps its proposal's corners in its own column (LDS because the edge tables index
@@ -761,7 +791,7 @@ __global__ __launch_bounds__(256) void score_kernel(DetectDeviceView v, long lon
 #pragma unroll
       for (int ee = 0; ee < 2; ee++) {
         int pa = sel(cfg, ID1[k][2 * ee], ID2[k][2 * ee]), pb = sel(cfg, ID1[k][2 * ee + 1], ID2[k][2 * ee + 1]);
-        double ang = normalize_to_pi(cs_atan2(CYt[pb][tx] - CYt[pa][tx], CXt[pb][tx] - CXt[pa][tx]));
+        double ang = normalize_to_pi(score_atan2(CYt[pb][tx] - CYt[pa][tx], CXt[pb][tx] - CXt[pa][tx]));
         double best = 100;
         if (v0) { double t = dabs(ang - b0); t = dmin(t, CS_PI - t); if (t < best) best = t; }
         if (v1) { double t = dabs(ang - b1); t = dmin(t, CS_PI - t); if (t < best) best = t; }

@@ -239,6 +239,11 @@ int cs_batch_debug_candidates(cs_batch* b, int frame, int box, int k, int cap, d
 /* good_proposal_ids / normalized_score of fuse_normalize_scores_v2 (object_3d_util.cpp:726-837). */
 int cs_batch_debug_kept(cs_batch* b, int frame, int box, int k, int cap, int* keep_ids, double* scores);
 
+/* A check of the scorer's angle evaluation on its own: for each of n argument pairs, one per lane in wavefronts of 64 as in the
+ * scorer, out[i] = the value the scorer computes for atan2(y[i], x[i]) -- the lean evaluation, then the exact one for the lanes
+ * it declined -- and accepted[i] = 1 where the lean evaluation accepted the pair, 0 where it declined.  Runs on device 0. */
+int cs_check_score_atan2(const double* y, const double* x, int n, double* out, int* accepted);
+
 
 /* ------------------------------------------------------------------ Path B: g2o bundle adjustment -- */
 /* Replaces, for graphs made of VertexSE3Expmap / VertexSBAPointXYZ / VertexCuboid and EdgeSE3ProjectXYZ /
