@@ -67,7 +67,7 @@ DECLARED_SYMBOLS = [
     "cs_last_error", "cs_device_count", "cs_diag_build", "cs_detect_default_params", "cs_box_rois", "cs_cam_euler_zyx", "cs_detector_create",
     "cs_detector_destroy", "cs_detect_cuboids", "cs_batch_create", "cs_batch_max_boxes", "cs_batch_run", "cs_batch_submit", "cs_batch_collect",
     "cs_bgr_to_gray", "cs_edge_distance_maps", "cs_edge_distance_maps_multi", "cs_detect_cuboids_gray", "cs_batch_create_gray", "cs_batch_refill_gray", "cs_batch_refill_wait", "cs_batch_destroy", "cs_batch_last_timing", "cs_batch_debug_candidates", "cs_batch_debug_kept", "cs_batch_set_debug", "cs_batch_set_pipeline_chunks", "cs_detect_lines_gray", "cs_detect_lines_batch", "cs_detect_lines_last_timing", "cs_detect_lsd_gray", "cs_detect_lsd_batch", "cs_detect_lsd_last_timing",
-    "cs_check_score_atan2",
+    "cs_check_score_atan2", "cs_check_score_sample_index",
 ]
 
 _lib = None
@@ -116,6 +116,21 @@ def check_score_atan2(y, x):
     if rc != 0:
         raise RuntimeError("cs_check_score_atan2 failed (%d): %s" % (rc, last_error()))
     return out, acc.astype(bool)
+
+
+def check_score_sample_index(sy, sx, map_w, a, b):
+    """The scorer's distance-map index on the device, one sample per lane, and the double-precision sum a + b the same lane forms right
+    behind it: (indices, sums)."""
+    sy, sx, a, b = (np.ascontiguousarray(t, np.float64) for t in (sy, sx, a, b))
+    map_w = np.ascontiguousarray(map_w, np.int32)
+    if sy.ndim != 1 or any(t.shape != sy.shape for t in (sx, map_w, a, b)):
+        raise ValueError("sy, sx, map_w, a and b must be 1-D arrays of the same length")
+    idx, probe = np.zeros(len(sy), np.int32), np.zeros(len(sy))
+    ip = C.POINTER(C.c_int)
+    rc = lib().cs_check_score_sample_index(_dp(sy), _dp(sx), map_w.ctypes.data_as(ip), _dp(a), _dp(b), len(sy), idx.ctypes.data_as(ip), _dp(probe))
+    if rc != 0:
+        raise RuntimeError("cs_check_score_sample_index failed (%d): %s" % (rc, last_error()))
+    return idx, probe
 
 
 def box_rois(box5, img_w, img_h, sample_height=False):

@@ -114,13 +114,23 @@ struct BoxGeom {
   int left, top, right, down;          // raw box, bottom already expanded by the height sample
   int el, et, er, eb;                  // expanded ROI, inclusive bounds
 };
+// The same bounds as the doubles build_corners compares and computes with.  int -> double is exact, so converting once (a caller that
+// runs many proposals of one job: candidate_compact_kernel) or at every use (BoxGeom) gives the same bits.
+struct BoxGeomD {
+  double left, top, right, down;
+  double el, et, er, eb;
+};
+CS_HD BoxGeomD box_geom_d(const BoxGeom& g) {
+  return BoxGeomD{(double)g.left, (double)g.top, (double)g.right, (double)g.down, (double)g.el, (double)g.et, (double)g.er, (double)g.eb};
+}
 
 // The eight 2D corners of one proposal (box_proposal_detail.cpp:413-625).
 // Returns 0 when the proposal is rejected, else vp_1_position (1 = left, 2 = right).
 // The reference rejects edges with sqrt(dx^2 + dy^2) < shorted_edge_thre.  The IEEE square root is monotone, so that test is
 // d2 < short_sq_bound with short_sq_bound = the smallest double whose rounded square root reaches the threshold (computed once
 // on the host, sqrt_lt_bound() in detect_host.cpp): the same decision for every d2 including NaN / inf, without the 13 roots.
-CS_HD int build_corners(const BoxGeom& g, V2 vp1, V2 vp2, V2 vp3, double top_x, int config_id, double short_sq_bound, V2 c[8]) {
+template <class Geom>      // BoxGeom or BoxGeomD
+CS_HD int build_corners(const Geom& g, V2 vp1, V2 vp2, V2 vp3, double top_x, int config_id, double short_sq_bound, V2 c[8]) {
   V2 c1 = v2(top_x, (double)g.top);
   int vp1_pos = 0;
   V2 c2 = ray_hit_vertical(vp1, c1, (double)g.right, (double)g.top, (double)g.down);

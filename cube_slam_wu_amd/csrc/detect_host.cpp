@@ -666,6 +666,32 @@ int cs_check_score_atan2(const double* y, const double* x, int n, double* out, i
   return rc;
 }
 
+int cs_check_score_sample_index(const double* sy, const double* sx, const int* map_w, const double* a, const double* b, int n, int* index, double* probe) {
+  if (n < 0 || (n > 0 && (!sy || !sx || !map_w || !a || !b || !index || !probe))) { cs_set_error("cs_check_score_sample_index: null array"); return CS_ERR_INVALID_ARG; }
+  if (n > (1 << 28)) { cs_set_error("cs_check_score_sample_index: more than 2^28 samples"); return CS_ERR_CAPACITY; }
+  if (int rc = cs::check_device(0)) return rc;
+  if (n == 0) return CS_OK;
+  CS_HIP_TRY(hipSetDevice(0));
+  DevBuf<double> d;       // sy, sx, a, b, probe
+  DevBuf<int> w;          // map_w, index
+  const size_t N = (size_t)n;
+  int rc = d.ensure(5 * N);
+  if (rc == CS_OK) rc = w.ensure(2 * N);
+  auto run = [&]() -> int {
+    const double* in[4] = {sy, sx, a, b};
+    for (int q = 0; q < 4; q++) CS_HIP_TRY(hipMemcpy(d.p + q * N, in[q], sizeof(double) * N, hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(w.p, map_w, sizeof(int) * N, hipMemcpyHostToDevice));
+    cs::launch_score_sample_index_check(d.p, d.p + N, w.p, d.p + 2 * N, d.p + 3 * N, n, w.p + N, d.p + 4 * N, nullptr);
+    CS_HIP_TRY(hipGetLastError());
+    CS_HIP_TRY(hipMemcpy(index, w.p + N, sizeof(int) * N, hipMemcpyDeviceToHost));
+    CS_HIP_TRY(hipMemcpy(probe, d.p + 4 * N, sizeof(double) * N, hipMemcpyDeviceToHost));
+    return CS_OK;
+  };
+  if (rc == CS_OK) rc = run();
+  d.release(); w.release();
+  return rc;
+}
+
 void cs_detect_default_params(cs_detect_params* p) {
   if (!p) return;
   p->consider_config_1 = 1; p->consider_config_2 = 1;

@@ -41,6 +41,14 @@ __device__ __forceinline__ long long wave_uniform_i64(long long x) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(x & 0xffffffffll)), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(x >> 32));
   return (long long)(((unsigned long long)hi << 32) | lo);
 }
+// a wave-uniform double into a scalar register pair.  (The builtin is folded away where the compiler can see that its operand is uniform,
+// and the value then stays where a vector instruction produced it: two vector registers in every lane.  The instruction written out is not.)
+__device__ __forceinline__ double wave_uniform_f64(double x) {
+  int lo, hi;
+  asm("v_readfirstlane_b32 %0, %1" : "=s"(lo) : "v"(__double2loint(x)));
+  asm("v_readfirstlane_b32 %0, %1" : "=s"(hi) : "v"(__double2hiint(x)));
+  return __hiloint2double(hi, lo);
+}
 template <typename T>
 __device__ __forceinline__ int find_job_wave(const T* __restrict__ prefix, int n, T elem) {
   const T first = sizeof(T) == 8 ? (T)wave_uniform_i64((long long)elem) : (T)wave_uniform_i32((int)elem);   // lane 0 holds the smallest
@@ -423,7 +431,8 @@ __global__ __launch_bounds__(256) void candidate_kernel(DetectDeviceView v, Swee
 }
 
 // Round 6: vanishing points + corner construction + ordered compaction of ONE job per workgroup (the lean path; replaces vp_points_kernel,
-// candidate_kernel, scan_jobs_kernel and compact_kernel there).  The job record is uniform (scalar registers), the decisions of a trip of
+// candidate_kernel, scan_jobs_kernel and compact_kernel there).  The job record is uniform and is read ONCE, into locals, ahead of the kernel's
+// first store (below: why a reference to it is not enough), the decisions of a trip of
 // 4096 slots stay in LDS (a byte each) instead of going through a 4-byte flag per slot in memory, the valid count needs no atomics, and --
 // with the compacted rows of job j starting at slot_prefix[j] (capacity layout, DetectDeviceView::blk_info) -- nothing waits for a scan over
 // all jobs.  Lane -> proposal as in candidate_kernel: a wave runs one configuration (eight passes of 256 top-edge/yaw samples per
@@ -435,17 +444,38 @@ __global__ __launch_bounds__(256) void candidate_compact_kernel(DetectDeviceView
   if (j >= v.n_jobs) return;
   __shared__ unsigned char s_flag[CC_TRIP];
   __shared__ int wsum[4];
-  const JobDesc& jd = v.jobs[j];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  // ---- the job record, once.  v.jobs is memory this kernel may, for all the compiler knows, store into (v.vp, c_slot, c_flag, blk_info
+  // are plain pointers), so a `const JobDesc&` is a scalar load only up to the first store and a vector load of one address after it,
+  // inside every pass of the corner loop, with the box bounds converted to double again behind each.  Locals are values: read here
+  // (scalar loads), and the eight bounds converted here, six of them pinned to scalar registers (wave_uniform_f64: the conversion is a
+  // vector instruction, its result would otherwise occupy two vector registers per lane for one value).  left and right stay in vector
+  // registers: the ray hits SELECT them (hit.x = bx), and a select whose condition is a scalar pair cannot take a second scalar operand
+  // -- from scalar registers each such select paid two moves.
+  int jd_Y, jd_T, jd_rp_off, jd_yaw_off, jd_vp_off, jd_top_off, n_vp;
+  BoxGeomD gd;
+  {
+    const JobDesc& jd = v.jobs[j];
+    jd_Y = jd.Y; jd_T = jd.T; jd_rp_off = jd.rp_off; jd_yaw_off = jd.yaw_off; jd_vp_off = jd.vp_off; jd_top_off = jd.top_off;
+    n_vp = jd.RP * jd.Y;
+    const BoxGeomD g = box_geom_d(jd.g);
+    gd = BoxGeomD{g.left, wave_uniform_f64(g.top), g.right, wave_uniform_f64(g.down),
+                  wave_uniform_f64(g.el), wave_uniform_f64(g.et), wave_uniform_f64(g.er), wave_uniform_f64(g.eb)};
+  }
+  // (where the job's count and base go at the very end: the two addresses wait in vector registers, which this kernel has to spare at its
+  // occupancy (70 of 72), not in scalar ones, of which the nested decisions of build_corners -- a saved mask per level -- leave none: left
+  // to the compiler they were loaded at entry and parked in lanes of a vector register until the end)
+  int* out_valid = v.job_valid + j;
+  long long* out_cbase = v.job_cbase + j;
+  asm volatile("" : "+v"(out_valid), "+v"(out_cbase));
   // ---- getVanishingPoints (object_3d_util.cpp:928-937) of the job's (roll/pitch, yaw) samples: vp_points_kernel's arithmetic
-  const int n_vp = jd.RP * jd.Y;
   for (int e = tid; e < n_vp; e += 256) {
-    const int rp = e / jd.Y, y = e - rp * jd.Y;
-    const RpPose* pose = v.rp + jd.rp_off + rp;
-    const double cy = v.yaw_cos[jd.yaw_off + y], sy = v.yaw_sin[jd.yaw_off + y];
+    const int rp = e / jd_Y, y = e - rp * jd_Y;
+    const RpPose* pose = v.rp + jd_rp_off + rp;
+    const double cy = v.yaw_cos[jd_yaw_off + y], sy = v.yaw_sin[jd_yaw_off + y];
     const double* A = pose->KinvR;
     const double d[3][3] = {{cy, sy, 0.0}, {-sy, cy, 0.0}, {0.0, 0.0, 1.0}};
-    double* vout = v.vp + 6 * (long long)(jd.vp_off + e);
+    double* vout = v.vp + 6 * (long long)(jd_vp_off + e);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       const double h0 = (A[0] * d[k][0] + A[1] * d[k][1]) + A[2] * d[k][2];
@@ -456,17 +486,19 @@ __global__ __launch_bounds__(256) void candidate_compact_kernel(DetectDeviceView
     }
   }
   __syncthreads();        // (one workgroup, one CU: the rows written above are read back below)
-  const unsigned half = (unsigned)n_vp * (unsigned)jd.T;            // proposals per configuration
+  const unsigned half = (unsigned)n_vp * (unsigned)jd_T;            // proposals per configuration
   // rest / T by one multiplication (T is uniform; the generic 32-bit division is ~20 instructions per slot): m = floor(2^32 / T) + 1 gives
   // floor(rest m / 2^32) = floor(rest / T) whenever rest T < 2^32 (the error term rest (m T - 2^32) / (2^32 T) stays below 1 / T);
   // rest < half, so half T < 2^32 decides -- otherwise (never at any image size: n_vp T^2 in the millions) the division itself
-  const unsigned Tu = (unsigned)jd.T;
+  const unsigned Tu = (unsigned)jd_T;
   const bool fast_div = Tu > 1 && (unsigned long long)half * Tu < (1ull << 32);
   const unsigned inv_T = fast_div ? 0xffffffffu / Tu + 1u : 0u;
   const long long base = v.slot_prefix[j];
   long long run = base;
   const unsigned long long below = (1ull << lane) - 1ull;
   const bool en1 = sp.consider_config_1 != 0, en2 = sp.consider_config_2 != 0;
+  const double* job_vp = v.vp + 6 * (long long)jd_vp_off;
+  const int* job_top_x = v.top_x + jd_top_off;
   for (unsigned r0 = 0; r0 < half; r0 += CC_TRIP / 2) {
     // ---- decisions of the trip's proposals
 #pragma unroll 1
@@ -477,9 +509,9 @@ __global__ __launch_bounds__(256) void candidate_compact_kernel(DetectDeviceView
       if (rest < half && (cfg == 1 ? en1 : en2)) {
         const unsigned ryu = fast_div ? __umulhi(rest, inv_T) : rest / Tu;
         const int t = (int)(rest - ryu * Tu);
-        const double* vp = v.vp + 6 * (long long)(jd.vp_off + (int)ryu);
+        const double* vp = job_vp + 6 * (long long)(int)ryu;
         V2 c[8];
-        flag = build_corners(jd.g, v2(vp[0], vp[1]), v2(vp[2], vp[3]), v2(vp[4], vp[5]), (double)v.top_x[jd.top_off + t], cfg, sp.short_sq_bound, c);
+        flag = build_corners(gd, v2(vp[0], vp[1]), v2(vp[2], vp[3]), v2(vp[4], vp[5]), (double)job_top_x[t], cfg, sp.short_sq_bound, c);
       }
       s_flag[2 * rl + (unsigned)(cfg - 1)] = (unsigned char)flag;
     }
@@ -513,7 +545,7 @@ __global__ __launch_bounds__(256) void candidate_compact_kernel(DetectDeviceView
     __syncthreads();                                    // s_flag and wsum are rewritten by the next trip
   }
   const int n_valid = (int)(run - base);
-  if (tid == 0) { v.job_valid[j] = n_valid; v.job_cbase[j] = base; }
+  if (tid == 0) { *out_valid = n_valid; *out_cbase = base; }
   // the scorer's work list: this job's blocks of 256 rows, appended as the job finishes (the list's order is roughly the jobs' order:
   // neighbouring entries read the same distance maps; it does not matter for any result)
   const int nblk = (n_valid + 255) >> 8;
@@ -577,6 +609,9 @@ __device__ __forceinline__ unsigned score_udiv(unsigned n, unsigned d, unsigned 
 //                     true is nx; with `on` false every sample of the edge keeps sum, which is what not visiting the edge does.
 // The order of the additions -- s = 0..10 within an edge, the edges in table order -- is the same in all three.
 enum { SCORE_WAVE_MIXED = 0, SCORE_WAVE_CFG1 = 1, SCORE_WAVE_CFG2 = 2 };
+// The element of the job's distance map under sample (sx, sy), coordinates relative to the map's corner: the reference's integer casts (:653).
+// samples lie inside the ROI the map covers (corners were tested against it): row * width + column fits 24 x 24 -> 32 bits
+__device__ __forceinline__ unsigned score_sample_index(double sy, double sx, int map_w) { return (unsigned)(__mul24((int)sy, map_w) + (int)sx); }
 template <int MODE>
 __device__ __forceinline__ void score_edge_trip(int e0, int cfg, const double (*CXt)[260], const double (*CYt)[260], int tx, double ox, double oy,
                                                 const float* __restrict__ map, int map_w, float& sum_dist) {
@@ -606,8 +641,7 @@ __device__ __forceinline__ void score_edge_trip(int e0, int cfg, const double (*
       else if (s == 10) { sx = x1; sy = y1; }
       else if (s == 5) { sx = (x1 + x2) * 0.5; sy = (y1 + y2) * 0.5; }
       else { const double w = (double)s / 10.0; sx = w * x1 + (1 - w) * x2; sy = w * y1 + (1 - w) * y2; }
-      // samples lie inside the ROI the map covers (corners were tested against it): row * width + column fits 24 x 24 -> 32 bits
-      dv[u][s] = map[(unsigned)(__mul24((int)sy, map_w) + (int)sx)];
+      dv[u][s] = map[score_sample_index(sy, sx, map_w)];
     }
   }
 #pragma unroll
@@ -665,6 +699,25 @@ __global__ __launch_bounds__(256) void score_atan2_check_kernel(const double* __
 void launch_score_atan2_check(const double* y, const double* x, int n, double* out, int* accepted, hipStream_t st) {
   if (n <= 0) return;
   hipLaunchKernelGGL(score_atan2_check_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y, x, n, out, accepted);
+}
+
+// cs_check_score_sample_index: score_sample_index over n samples, one per lane, and right behind it a double-precision sum of two given
+// terms in the same lane (the empty statement ties the sum to the index: it cannot be scheduled ahead of it).  Whatever the index
+// function does to the lane's floating-point mode shows in that sum.
+__global__ __launch_bounds__(256) void score_sample_index_check_kernel(const double* __restrict__ sy, const double* __restrict__ sx, const int* __restrict__ map_w,
+                                                                       const double* __restrict__ a, const double* __restrict__ b, int n, int* __restrict__ index, double* __restrict__ probe) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double pa = a[i];
+  const double pb = b[i];
+  const unsigned k = score_sample_index(sy[i], sx[i], map_w[i]);
+  asm volatile("" : "+v"(pa) : "v"(k));
+  index[i] = (int)k;
+  probe[i] = pa + pb;
+}
+void launch_score_sample_index_check(const double* sy, const double* sx, const int* map_w, const double* a, const double* b, int n, int* index, double* probe, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(score_sample_index_check_kernel, dim3((n + 255) / 256), dim3(256), 0, st, sy, sx, map_w, a, b, n, index, probe);
 }
 
 template <bool CAP>

@@ -243,6 +243,12 @@ int cs_batch_debug_kept(cs_batch* b, int frame, int box, int k, int cap, int* ke
  * scorer, out[i] = the value the scorer computes for atan2(y[i], x[i]) -- the lean evaluation, then the exact one for the lanes
  * it declined -- and accepted[i] = 1 where the lean evaluation accepted the pair, 0 where it declined.  Runs on device 0. */
 int cs_check_score_atan2(const double* y, const double* x, int n, double* out, int* accepted);
+/* A check of the scorer's distance-map index on its own: for each of n samples (sy[i], sx[i]) of a map map_w[i] floats wide, one per
+ * lane in wavefronts of 64 as in the scorer, index[i] = the element the scorer reads, (int)sy * map_w + (int)sx (samples are
+ * finite and >= 0; map_w < 2^23).  Right behind the index the same lane adds a[i] + b[i] in double precision into probe[i]: with
+ * a = 1 and b = 1.5 * 2^-53 the sum is 1 + 2^-52 under round-to-nearest and 1 under round-toward-zero, which tells whether the
+ * lane's rounding mode is what the rest of the scorer's arithmetic assumes.  Runs on device 0. */
+int cs_check_score_sample_index(const double* sy, const double* sx, const int* map_w, const double* a, const double* b, int n, int* index, double* probe);
 
 
 /* ------------------------------------------------------------------ Path B: g2o bundle adjustment -- */
