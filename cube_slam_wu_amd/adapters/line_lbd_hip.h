@@ -4,7 +4,8 @@
 // as called by object_slam/src/main_obj.cpp:502-505,593.  Include this header instead of line_lbd/line_lbd_allclass.h and link
 // -lcubeslam_hip in place of the reference's libline_lbd_lib.  Both detector branches are served: EDLines (use_LSD = false, the one
 // the graph driver selects) by cs_detect_lines_gray, LSD (use_LSD = true, the one whose output the reference ships for its bundled
-// frame) by cs_detect_lsd_gray; descriptors and matching are not on the hot path and stay with the reference library.  Needs OpenCV
+// frame) by cs_detect_lsd_gray.  Descriptors and matching are served by the C ABI directly (cs_detect_descrip_lines_gray, cs_lbd_describe_gray,
+// cs_lbd_match: INTEGRATION.md); this class does not wrap them, because its compile check's OpenCV stand-ins declare no CV_8UC1.  Needs OpenCV
 // for cv::Mat / cvtColor; tests/test_adapters_compile.py compiles it against declaration-only stubs.
 #pragma once
 

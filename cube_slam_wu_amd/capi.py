@@ -67,8 +67,12 @@ DECLARED_SYMBOLS = [
     "cs_last_error", "cs_device_count", "cs_diag_build", "cs_detect_default_params", "cs_box_rois", "cs_cam_euler_zyx", "cs_detector_create",
     "cs_detector_destroy", "cs_detect_cuboids", "cs_batch_create", "cs_batch_max_boxes", "cs_batch_run", "cs_batch_submit", "cs_batch_collect",
     "cs_bgr_to_gray", "cs_edge_distance_maps", "cs_edge_distance_maps_multi", "cs_detect_cuboids_gray", "cs_batch_create_gray", "cs_batch_refill_gray", "cs_batch_refill_wait", "cs_batch_destroy", "cs_batch_last_timing", "cs_batch_debug_candidates", "cs_batch_debug_kept", "cs_batch_set_debug", "cs_batch_set_pipeline_chunks", "cs_detect_lines_gray", "cs_detect_lines_batch", "cs_detect_lines_last_timing", "cs_detect_lsd_gray", "cs_detect_lsd_batch", "cs_detect_lsd_last_timing",
+    "cs_lbd_describe_gray", "cs_detect_descrip_lines_gray", "cs_detect_descrip_lines_batch", "cs_lbd_match", "cs_lbd_match_batch", "cs_lbd_last_timing",
     "cs_check_score_atan2", "cs_check_score_sample_index",
 ]
+
+# cs_keyline (one octave: start / end point, direction, length of the support region in pixels)
+KEYLINE_DTYPE = np.dtype([("sx", np.float32), ("sy", np.float32), ("ex", np.float32), ("ey", np.float32), ("direction", np.float32), ("num_pixels", np.int32)])
 
 _lib = None
 
@@ -228,6 +232,91 @@ class Detector:
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s" % ("cs_detect_lsd_batch" if use_lsd else "cs_detect_lines_batch", rc, last_error()))
         return [out[i, :cnt[i]].copy() for i in range(n)]
+
+    def describe_lines(self, gray, keylines, want_float=False):
+        """cs_lbd_describe_gray: BinaryDescriptor::compute on the caller's keylines (records of KEYLINE_DTYPE, one octave) -> (n, 32) uint8
+        [, (n, 72) float32 with want_float]."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        kl = np.ascontiguousarray(keylines, KEYLINE_DTYPE)
+        n = len(kl)
+        d32 = np.zeros((n, 32), np.uint8)
+        d72 = np.zeros((n, 72), np.float32) if want_float else None
+        rc = lib().cs_lbd_describe_gray(self.h, gray.ctypes.data_as(C.POINTER(C.c_ubyte)), int(gray.shape[1]), int(gray.shape[0]), C.c_void_p(kl.ctypes.data), n,
+                                        C.c_void_p(d32.ctypes.data), C.c_void_p(d72.ctypes.data) if want_float else None)
+        if rc != 0:
+            raise RuntimeError("cs_lbd_describe_gray failed (%d): %s" % (rc, last_error()))
+        return (d32, d72) if want_float else d32
+
+    def detect_descrip_lines(self, gray, length_thres=15.0, cap=20000):
+        """cs_detect_descrip_lines_gray: line_lbd_detect::detect_descrip_lines (EDLines, one octave) -> (keyline records, (n, 32) uint8)."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        kl = np.empty(cap, KEYLINE_DTYPE)
+        d32 = np.empty((cap, 32), np.uint8)
+        n = C.c_int()
+        rc = lib().cs_detect_descrip_lines_gray(self.h, gray.ctypes.data_as(C.POINTER(C.c_ubyte)), int(gray.shape[1]), int(gray.shape[0]), C.c_double(length_thres),
+                                                C.c_void_p(kl.ctypes.data), C.c_void_p(d32.ctypes.data), int(cap), C.byref(n))
+        if rc != 0:
+            raise RuntimeError("cs_detect_descrip_lines_gray failed (%d): %s" % (rc, last_error()))
+        return kl[:n.value].copy(), d32[:n.value].copy()
+
+    def detect_descrip_lines_batch(self, grays, length_thres=15.0, cap=20000):
+        """cs_detect_descrip_lines_batch: images of one size -> list of (keyline records, (n_i, 32) uint8), all lines described in one launch."""
+        grays = [g if (isinstance(g, np.ndarray) and g.dtype == np.uint8 and g.flags.c_contiguous) else np.ascontiguousarray(g, np.uint8) for g in grays]
+        n = len(grays)
+        if n == 0:
+            return []
+        H, W = grays[0].shape
+        if any(g.shape != (H, W) for g in grays):
+            raise ValueError("detect_descrip_lines_batch: the images of a batch have one size")
+        kl = np.empty((n, cap), KEYLINE_DTYPE)
+        d32 = np.empty((n, cap, 32), np.uint8)
+        cnt = np.zeros(n, np.int32)
+        gp = (C.c_void_p * n)(*[g.ctypes.data for g in grays])
+        kp = (C.c_void_p * n)(*[kl.ctypes.data + i * kl.strides[0] for i in range(n)])
+        dp = (C.c_void_p * n)(*[d32.ctypes.data + i * d32.strides[0] for i in range(n)])
+        rc = lib().cs_detect_descrip_lines_batch(self.h, gp, n, int(W), int(H), C.c_double(length_thres), kp, dp, int(cap), cnt.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            raise RuntimeError("cs_detect_descrip_lines_batch failed (%d): %s" % (rc, last_error()))
+        return [(kl[i, :cnt[i]].copy(), d32[i, :cnt[i]].copy()) for i in range(n)]
+
+    def match_lines(self, q, t):
+        """cs_lbd_match: BinaryDescriptorMatcher::match on (nq, 32) / (nt, 32) uint8 descriptors -> (train_idx, dist, dist2) int32 per query row
+        (nearest train row, ties to the lowest; its Hamming distance; the second-smallest distance; -1 where there is none)."""
+        idx, dist, dist2 = self.match_lines_batch([(q, t)])
+        return idx[0], dist[0], dist2[0]
+
+    def match_lines_batch(self, pairs):
+        """cs_lbd_match_batch: [(q, t), ...] matched in one launch -> (list of train_idx, list of dist, list of dist2), one array per pair."""
+        qs = [np.ascontiguousarray(q, np.uint8).reshape(-1, 32) for q, _ in pairs]
+        ts = [np.ascontiguousarray(t, np.uint8).reshape(-1, 32) for _, t in pairs]
+        q_ptr = np.concatenate([[0], np.cumsum([len(q) for q in qs])]).astype(np.int32)
+        t_ptr = np.concatenate([[0], np.cumsum([len(t) for t in ts])]).astype(np.int32)
+        qa = np.ascontiguousarray(np.concatenate(qs)) if qs else np.zeros((0, 32), np.uint8)
+        ta = np.ascontiguousarray(np.concatenate(ts)) if ts else np.zeros((0, 32), np.uint8)
+        nq = int(q_ptr[-1])
+        out = np.zeros((3, max(nq, 1)), np.int32)
+        ip = C.POINTER(C.c_int)
+        rc = lib().cs_lbd_match_batch(self.h, len(pairs), C.c_void_p(qa.ctypes.data), q_ptr.ctypes.data_as(ip), C.c_void_p(ta.ctypes.data), t_ptr.ctypes.data_as(ip),
+                                      out[0].ctypes.data_as(ip), out[1].ctypes.data_as(ip), out[2].ctypes.data_as(ip))
+        if rc != 0:
+            raise RuntimeError("cs_lbd_match_batch failed (%d): %s" % (rc, last_error()))
+        cut = lambda row: [row[q_ptr[p]:q_ptr[p + 1]].copy() for p in range(len(pairs))]
+        return cut(out[0]), cut(out[1]), cut(out[2])
+
+    def match_line_descrip(self, q, t, dist_thres=25.0):
+        """line_lbd_detect::match_line_descrip: the matches with dist < dist_thres (matching_dist_thres, 25 by default) as (query_idx, train_idx, dist)
+        rows, int32."""
+        idx, dist, _ = self.match_lines(q, t)
+        keep = np.nonzero((idx >= 0) & (dist < dist_thres))[0]
+        return np.stack([keep.astype(np.int32), idx[keep], dist[keep]], axis=1).astype(np.int32).reshape(-1, 3)
+
+    def lbd_timing(self):
+        """Device time (ms) of the last descriptor kernel and the last matching kernel of this detector (-1: not run)."""
+        a, b = C.c_double(), C.c_double()
+        rc = lib().cs_lbd_last_timing(self.h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise RuntimeError("cs_lbd_last_timing failed (%d)" % rc)
+        return {"describe_kernel_ms": a.value, "match_kernel_ms": b.value}
 
     def lines_timing(self, use_lsd=False):
         a, b, c = C.c_double(), C.c_double(), C.c_double()

@@ -436,6 +436,8 @@ struct cs_detector {
   void (*lines_free)(void*) = nullptr;
   void* lsd_scratch = nullptr;          // the same for the LSD branch (lsd_host.cpp)
   void (*lsd_free)(void*) = nullptr;
+  void* lbd_scratch = nullptr;          // and for the line descriptors / matching (lbd_host.cpp)
+  void (*lbd_free)(void*) = nullptr;
   std::mutex lines_mu;
 };
 
@@ -740,6 +742,7 @@ void* cs_internal_detector_stream(cs_detector* d) { return (void*)d->stream; }
 // lines_host.cpp: the producer's scratch slot, its lock, and the detector's worker pool
 void** cs_internal_detector_lines_slot(cs_detector* d, void (*deleter)(void*)) { d->lines_free = deleter; return &d->lines_scratch; }
 void** cs_internal_detector_lsd_slot(cs_detector* d, void (*deleter)(void*)) { d->lsd_free = deleter; return &d->lsd_scratch; }
+void** cs_internal_detector_lbd_slot(cs_detector* d, void (*deleter)(void*)) { d->lbd_free = deleter; return &d->lbd_scratch; }
 void* cs_internal_detector_lines_mutex(cs_detector* d) { return (void*)&d->lines_mu; }
 void cs_internal_detector_parallel(cs_detector* d, int n, void (*fn)(int, void*), void* ctx) { d->pool->run(n, [&](int i) { fn(i, ctx); }); }
 // (for the segment producers' image-long items: two threads per granted CPU at most, see cs_detector_create)
@@ -804,6 +807,7 @@ void cs_detector_destroy(cs_detector* d) {
   if (d->single) { cs_batch_destroy(d->single); d->single = nullptr; }
   if (d->lines_scratch && d->lines_free) { d->lines_free(d->lines_scratch); d->lines_scratch = nullptr; }
   if (d->lsd_scratch && d->lsd_free) { d->lsd_free(d->lsd_scratch); d->lsd_scratch = nullptr; }
+  if (d->lbd_scratch && d->lbd_free) { d->lbd_free(d->lbd_scratch); d->lbd_scratch = nullptr; }
   for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
   if (d->streams) {
     // (the streams are shared: what this detector queued outside a batch -- a front end, a segment producer's tail -- is waited for here)

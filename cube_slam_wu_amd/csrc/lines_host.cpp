@@ -129,7 +129,7 @@ struct NormalEq {
 // number of false alarms (descriptor.hpp:650-848): cs_nfa.h, with the log-gamma first term
 double minus_log10_nfa(int n, int k, double p, double logNT) { return cs::minus_log10_nfa(n, k, p, logNT, true); }
 
-struct Segment { float x1, y1, x2, y2, direction; };
+struct Segment { float x1, y1, x2, y2, direction; int n_pixels; };     // n_pixels: chain pixels the fitted line kept (lines_.sId[k + 1] - lines_.sId[k], :2442-2626)
 
 // ---- line extraction from the chains ------------------------------------------------------------------------------------------
 struct Extractor {
@@ -227,6 +227,7 @@ struct Extractor {
         X = lx.back(); Y = ly.back();
         sg.x2 = (float)(p1 * X - p3 * Y - p4); sg.y2 = (float)(p2 * Y - p3 * X - p5);
         sg.direction = direction;
+        sg.n_pixels = (int)lx.size();
         out.push_back(sg);
       }
     }
@@ -256,7 +257,8 @@ void lines_scratch_free(void* p) {
 }
 
 // the sequential half of one image: routing, fitting, validation, end points (all of it independent of the other images)
-int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, float* lines4, int cap, int* n_lines) {
+// extra (optional, cap records): each kept segment's lineDirection_ and numOfPixels (OctaveKeyLines :1081-1082), what the descriptor needs beside the end points
+int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, float* lines4, int cap, int* n_lines, cs::LineExtra* extra = nullptr) {
   const int img_w = M.W, img_h = M.H;
   const size_t N = (size_t)img_w * img_h;
   *n_lines = 0;
@@ -310,6 +312,7 @@ int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, floa
     if (n >= cap) { cs_set_error("cs_detect_lines_gray: more segments than `cap`"); return CS_ERR_CAPACITY; }
     float* o = lines4 + 4 * (size_t)n;
     if (flip) { o[0] = s.x2; o[1] = s.y2; o[2] = s.x1; o[3] = s.y1; } else { o[0] = s.x1; o[1] = s.y1; o[2] = s.x2; o[3] = s.y2; }
+    if (extra) { extra[n].direction = s.direction; extra[n].num_pixels = s.n_pixels; }
     n++;
   }
   *n_lines = n;
@@ -321,8 +324,11 @@ int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, floa
 // n_images gray images of one size: the per-pixel stages of all of them on the device (one kernel per image, queued back to back, the
 // maps copied into pinned staging), then the sequential halves side by side on the detector's worker pool.  lines4[i] receives image
 // i's segments (cap rows of 4), n_lines[i] their number.
-extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const* grays, int n_images, int img_w, int img_h, double length_thres, float* const* lines4, int cap,
-                                     int* n_lines) {
+// The entry behind cs_detect_lines_batch, with two optional extras for the descriptor path (lbd_host.cpp; detect_hooks.h): extra[i] receives image i's
+// per-segment direction / pixel count, and `then` runs after the host stages, still under the producer's lock, with the batch's packed maps resident
+// on the device (image i's at d_p3 + 3 N i) and the detector's stream idle.
+extern "C" int cs_internal_detect_lines_batch(cs_detector* d, const unsigned char* const* grays, int n_images, int img_w, int img_h, double length_thres, float* const* lines4, int cap,
+                                              int* n_lines, cs::LineExtra* const* extra, int (*then)(void* ctx, const unsigned char* d_p3), void* then_ctx) {
   if (!d || n_images < 0 || (n_images && (!grays || !n_lines || (cap && !lines4))) || img_w < 3 || img_h < 3 || cap < 0) return CS_ERR_INVALID_ARG;
   for (int i = 0; i < n_images; i++) if (!grays[i] || (cap && !lines4[i])) return CS_ERR_INVALID_ARG;
   try {
@@ -347,24 +353,18 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
       S.cap = need;
     }
     if (!S.ev0) { CS_HIP_TRY(hipEventCreate(&S.ev0)); CS_HIP_TRY(hipEventCreate(&S.ev1)); }
-    // getGaussianKernel(5, 1.0, CV_32F) rounded to 8-bit fixed point, as createSeparableLinearFilter does for 8-bit images
     int k[3];
-    {
-      float cf[5]; double sum = 0;
-      for (int i = 0; i < 5; i++) { const double x = i - 2.0; cf[i] = (float)std::exp(-0.5 * x * x); sum += cf[i]; }
-      sum = 1. / sum;
-      for (int i = 0; i < 3; i++) k[i] = (int)std::nearbyint((double)(float)(cf[i] * sum) * 256.0);
-    }
+    cs::lines_blur_taps(k);
     const cs::LineMaps dm{S.d_pk.p};
     struct Ctx {
       const unsigned char* h_pk; int W, H; size_t N; const EdParams* P; double thr; float* const* lines4; int cap; int* n_lines; std::vector<int> rc;
       cs::ChunkGate gate; int device; const hipEvent_t* done; int n_chunks, n_images;
-      const unsigned char* const* grays; unsigned char* h_in;
-    } ctx{S.h_pin.p, img_w, img_h, N, &P, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in.p};
+      const unsigned char* const* grays; unsigned char* h_in; cs::LineExtra* const* extra;
+    } ctx{S.h_pin.p, img_w, img_h, N, &P, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in.p, extra};
     auto one = [](int i, void* vp) {
       Ctx& c = *(Ctx*)vp;
       Maps M; M.W = c.W; M.H = c.H; M.grad_thr = c.P->grad_thr; M.p3 = c.h_pk + 3 * c.N * (size_t)i;
-      try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i]); }
+      try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i], c.extra ? c.extra[i] : nullptr); }
       catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
     };
     double t_host;
@@ -406,7 +406,7 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
         const int i = t - 1;
         if (!c.gate.wait_for(i)) { c.rc[i] = CS_ERR_HIP; return; }
         Maps M; M.W = c.W; M.H = c.H; M.grad_thr = c.P->grad_thr; M.p3 = c.h_pk + 3 * c.N * (size_t)i;
-        try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i]); }
+        try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i], c.extra ? c.extra[i] : nullptr); }
         catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
       }, &ctx);
       CS_HIP_TRY(hipStreamSynchronize(st));
@@ -416,11 +416,17 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
     }
     S.host_ms = cs::now_ms() - t_host; S.total_ms = cs::now_ms() - t_begin; S.n_images = n_images;
     for (int r : ctx.rc) if (r) return r;
-    return CS_OK;
+    return then ? then(then_ctx, S.d_pk.p) : CS_OK;
   } catch (const std::exception& ex) {
     cs_set_error(std::string("cs_detect_lines_batch: ") + ex.what());
     return CS_ERR_CAPACITY;
   }
+}
+
+// n_images gray images of one size (see above)
+extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const* grays, int n_images, int img_w, int img_h, double length_thres, float* const* lines4, int cap,
+                                     int* n_lines) {
+  return cs_internal_detect_lines_batch(d, grays, n_images, img_w, img_h, length_thres, lines4, cap, n_lines, nullptr, nullptr, nullptr);
 }
 
 // timing of the last cs_detect_lines_batch / cs_detect_lines_gray of this detector: the device kernels, the host stage (wall), the whole call

@@ -185,6 +185,42 @@ int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* grays, int n
                         float* const* lines4, int cap, int* n_lines);
 int cs_detect_lsd_last_timing(cs_detector* d, double* device_ms, double* host_ms, double* total_ms);
 
+/* ---- line descriptors (LBD) and Hamming matching ------------------------------------------------------------------------------
+ * The rest of `class line_lbd_detect` a line-tracking caller uses (line_lbd/class/line_lbd_allclass.cpp): detect_descrip_lines
+ * (:239-282), get_line_descriptors (:190-197) and match_line_descrip (:352-369), i.e. BinaryDescriptor::compute / computeLBD
+ * (line_lbd/libs/binary_descriptor.cpp:592-795, :1150-1513; default parameters widthOfBand_ = 7, 9 bands) and
+ * BinaryDescriptorMatcher::match.  One octave.  The descriptor is a fixed sequence of single-precision operations, stated in
+ * csrc/cs_lbd.h and reproduced operation for operation; a flat support region gives 72 NaN floats and 32 zero bytes, as in the
+ * reference.                                                                                                                     */
+typedef struct cs_keyline { float sx, sy, ex, ey, direction; int num_pixels; } cs_keyline;   /* one octave: *PointInOctave == *Point */
+/* Replaces BinaryDescriptor::compute(image, keylines, descriptors [, returnFloatDescr]) for octave-0 keylines (what
+ * get_line_descriptors calls on the caller's own segments): desc32 n x 32 bytes, desc72 n x 72 floats or NULL.  gray is blurred and
+ * differentiated on the device (computeSobel :352-402).  direction: the angle of the line (KeyLine::angle / lineDirection_);
+ * num_pixels: the length of the support region (KeyLine::numOfPixels).  CS_ERR_INVALID_ARG for an image side above 32767 (the
+ * reference indexes with short), num_pixels outside [0, 32767], or a non-finite coordinate / direction.  n == 0 is valid.         */
+int cs_lbd_describe_gray(cs_detector* d, const unsigned char* gray, int img_w, int img_h, const cs_keyline* kl, int n, unsigned char* desc32, float* desc72);
+/* Replaces line_lbd_detect::detect_descrip_lines(gray, keylines_out, descrips), EDLines branch: the segments of
+ * cs_detect_lines_gray at the same threshold, in the same order, as keyline records (direction = the detector's lineDirection_,
+ * num_pixels = lines_.sId[k + 1] - lines_.sId[k], binary_descriptor.cpp:1081-1082) with their 32-byte descriptors; kl and desc32
+ * hold cap rows.  length_thres < 0: no length filter (the Mat overload, :239-256).  The descriptor kernel reads the maps the
+ * detector's device stage left resident.                                                                                         */
+int cs_detect_descrip_lines_gray(cs_detector* d, const unsigned char* gray, int img_w, int img_h, double length_thres, cs_keyline* kl, unsigned char* desc32, int cap, int* n_lines);
+/* The same for n_images images of one size; all images' lines are described in one launch after the host stages.                 */
+int cs_detect_descrip_lines_batch(cs_detector* d, const unsigned char* const* grays, int n_images, int img_w, int img_h, double length_thres,
+                                  cs_keyline* const* kl, unsigned char* const* desc32, int cap, int* n_lines);
+/* Replaces BinaryDescriptorMatcher::match(query, train) as match_line_descrip calls it: per query row the nearest train row in
+ * Hamming distance over the 256 bits (brute force; the reference's distances and set of minimisers, ties to the LOWEST train row --
+ * the reference's tie order comes from its hash buckets and is not reproduced).  train_idx[i] = -1 and dist[i] = -1 when nt == 0;
+ * dist2 (may be NULL): the second-smallest distance, -1 when nt < 2.  nq == 0 is valid.  The dist < matching_dist_thres filter of
+ * match_line_descrip is one line on the caller's side.                                                                           */
+int cs_lbd_match(cs_detector* d, const unsigned char* q32, int nq, const unsigned char* t32, int nt, int* train_idx, int* dist, int* dist2);
+/* n_pairs (query set, train set) pairs in one launch: pair p's queries are rows q_ptr[p] .. q_ptr[p + 1] of q32, its train rows
+ * t_ptr[p] .. t_ptr[p + 1] of t32 (q_ptr[0] = t_ptr[0] = 0).  Outputs are indexed like q32's rows; train_idx counts within the pair's
+ * train set.                                                                                                                      */
+int cs_lbd_match_batch(cs_detector* d, int n_pairs, const unsigned char* q32, const int* q_ptr, const unsigned char* t32, const int* t_ptr, int* train_idx, int* dist, int* dist2);
+/* Device time (ms, from events) of this detector's last descriptor kernel and last matching kernel; -1: not run yet.             */
+int cs_lbd_last_timing(cs_detector* d, double* describe_kernel_ms, double* match_kernel_ms);
+
 /* Batched form for throughput: cs_batch_create() copies the frames' inputs into HBM (maps, lines,
  * boxes, cameras); cs_batch_run() is the hot path proper -- resident inputs in, cuboids out.
  * out / out_counts are laid out frame-major with stride max_boxes = max over frames of n_boxes:
