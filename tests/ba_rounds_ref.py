@@ -44,11 +44,14 @@ def make_case(seed, **kw):
 
 def subgraph(f, cams, points, keep_mono=None, keep_stereo=None, huber=None):
     """Graph of f's vertices at the given estimates with the kept edges only (keep_* = boolean per edge of the class, None = all); huber = (delta
-    mono, delta stereo) or None (no kernels)."""
+    mono, delta stereo) or None (no kernels); a delta is one number for the class or an array with every edge's own (kept or not)."""
     def sub(t, keep, delta):
         keep = np.ones(len(t[0]), bool) if keep is None else np.asarray(keep, bool)
         if not keep.any():
             return None
+        if delta is not None and np.ndim(delta) == 1:
+            assert len(delta) == len(keep)
+            delta = np.asarray(delta, float)[keep]
         return tuple(np.asarray(a)[keep] for a in t[:5]) + (np.full(int(keep.sum()), delta if delta is not None else 0.0),)
     return ref.Graph(cams, f["cam_fixed"], points, f["pt_fixed"], sub(f["mono"], keep_mono, huber[0] if huber else None),
                      sub(f["stereo"], keep_stereo, huber[1] if huber else None))
@@ -64,12 +67,12 @@ def classify(G, th=TH, depth_positive=True):
     return out, chi, float(np.abs(chi / t - 1).min())
 
 
-def local_ba(f, iters=(5, 10)):
+def local_ba(f, iters=(5, 10), huber=HUB):
     """The two rounds and the two classifications of LocalBundleAdjustment on f.  Returns a dict: per round `done`, `hist` (chi2, lambda, trials),
     `rho` (every trial's gain ratio); `out1` / `out2` = outliers after round 1 / at the end over ALL edges (mono first), `margin1` / `margin2`,
-    `state1` / `state2` = (cams7, points) after each round, `n_mono`."""
+    `state1` / `state2` = (cams7, points) after each round, `n_mono`.  huber: the first round's deltas, as subgraph() takes them."""
     nm = len(f["mono"][0])
-    G1 = ref.graph_of(f, huber=HUB)
+    G1 = ref.graph_of(f, huber=huber)
     d1 = G1.optimize(iters[0])
     out1, _, margin1 = classify(G1)
     cams1, _, X1 = G1.state()

@@ -117,20 +117,18 @@ def test_lm_trajectory_equals_the_reference(fam):
     P.close()
 
 
-def test_fused_linearisation_equals_the_stepwise_calls():
-    """cs_ba_optimize linearises the landmark side inside the Schur kernels from its second iteration on (the fused schedule, no long track, banded
-    solve: a 60-camera member of the family); the same LM steps driven through compute_errors / build_system / solve / push / update / pop use the classic kernels.  Same states to 1e-9."""
-    f = ref.make_family(seed=2, long_track=False, n_cams=60)      # (60 cameras: the reduced system is banded, which the 24-camera graphs' is not)
-    A = _device(f, huber=HUB)
+def _check_fused_equals_stepwise(f, huber):
+    """The body of test_fused_linearisation_equals_the_stepwise_calls on the graph f with the deltas huber (one per class, or an array per class)."""
+    A = _device(f, huber=huber)
     assert A.optimize(3) == 3
     fused, n_seg, _, _ = A.schur_layout()
     assert fused and n_seg > 0 and A.solver_path() == "band"      # what cs_ba_optimize asks for before it fuses the linearisation
     chi_a, lam_a, tr_a = A.history()
-    G = ref.graph_of(f, huber=HUB)                                  # the fused route against the reference as well
+    G = ref.graph_of(f, huber=huber)                                  # the fused route against the reference as well
     assert G.optimize(3) == 3 and all(abs(r) > 1e-6 for r in G.rho_log)
     assert np.array_equal(G.history()[2], tr_a) and np.allclose(chi_a, G.history()[0], rtol=1e-5)
     assert np.abs(A.state()[2] - G.state()[2]).max() <= 1e-5 * np.abs(G.state()[2]).max()
-    B = _device(f, huber=HUB)
+    B = _device(f, huber=huber)
     lam, ni, chi_b = 0.0, 2.0, []
     for it in range(3):
         cur = B.compute_errors()
@@ -163,7 +161,7 @@ def test_fused_linearisation_equals_the_stepwise_calls():
     # and the classic pair inside cs_ba_optimize itself
     os.environ["CS_BA_FUSE_LIN"] = "0"
     try:
-        Cc = _device(f, huber=HUB)
+        Cc = _device(f, huber=huber)
         assert Cc.optimize(3) == 3
     finally:
         del os.environ["CS_BA_FUSE_LIN"]
@@ -172,6 +170,13 @@ def test_fused_linearisation_equals_the_stepwise_calls():
         if a.size:
             assert np.abs(a - b).max() <= 1e-9 * np.abs(b).max()
     A.close(); B.close(); Cc.close()
+
+
+def test_fused_linearisation_equals_the_stepwise_calls():
+    """cs_ba_optimize linearises the landmark side inside the Schur kernels from its second iteration on (the fused schedule, no long track, banded
+    solve: a 60-camera member of the family); the same LM steps driven through compute_errors / build_system / solve / push / update / pop use the classic kernels.  Same states to 1e-9."""
+    f = ref.make_family(seed=2, long_track=False, n_cams=60)      # (60 cameras: the reduced system is banded, which the 24-camera graphs' is not)
+    _check_fused_equals_stepwise(f, HUB)
 
 
 def test_all_stereo_and_all_mono_graphs():
