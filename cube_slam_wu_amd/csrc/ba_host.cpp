@@ -30,6 +30,7 @@
 #include "../../include/cubeslam_hip.h"
 #include "ba_edge_class.h"
 #include "ba_types.h"
+#include "band_solver.h"
 #include "cs_hip_util.h"
 #include "cs_lm.h"
 #include "cs_sparse_solver.h"
@@ -1498,7 +1499,7 @@ int finalize_structure(cs_ba* B) {
   AL(B->Dinv, 9 * (size_t)np); AL(B->dbl, 3 * (size_t)np); B->s_doubles = (size_t)B->n_red * (B->band_ld ? B->band_ld : B->n_red);
   AL(B->S, B->s_doubles + B->n_pose);   // [S | rhs]: one buffer, one all-reduce in the sharded solve
   AL(B->xl, 3 * (size_t)np);
-  AL(B->d_band_info, 24);  // [first bad pivot + 1, grid-barrier counters, a zero double]
+  AL(B->d_band_info, cs::BAND_INFO_WORDS);  // the solver's status words (band_solver.h)
   AL(B->band_linv, B->band_ld ? std::max(cs::ba_band_workspace_doubles(B->n_red, B->band_ld), B->use_bcr ? cs::ba_bcr_workspace_doubles(B->n_red, 128) : (size_t)1) : 1);   // inverted diagonal blocks (+ the separator's rows in the nested order)
   B->nb_chi = cs::ba_chi2_blocks(E);
   B->n_chi_partials = B->nb_chi + (B->n_cub + B->n_odom + 63) / 64;
@@ -1511,16 +1512,16 @@ int finalize_structure(cs_ba* B) {
     AL(B->sep_msgs, B->msg_doubles * (size_t)R);
     AL(B->sepS, (size_t)B->n_sep * 2 * B->w_max + B->n_sep);   // [S_sep (band of 2 w_max) | rhs_sep]
     AL(B->sep_work, std::max(cs::ba_band_workspace_doubles(B->n_sep, 2 * B->w_max), cs::ba_bcr_sep_ok(B->w_max, B->shard_n) ? cs::ba_bcr_sep_workspace_doubles(B->shard_n) : (size_t)1));
-    AL(B->d_sep_info, 24);
+    AL(B->d_sep_info, cs::BAND_INFO_WORDS);
     AL(B->int_work, cs::ba_band_workspace_doubles(B->int_n, B->band_ld));
-    AL(B->d_int_info, 24);
+    AL(B->d_int_info, cs::BAND_INFO_WORDS);
     std::vector<int> sep_col(R + 1, 0);
     for (int k = 1; k < R; k++) sep_col[k] = B->cut[k];
     UP(B->d_sep_off, B->sep_off); UP(B->d_sep_col, sep_col);
     // what this rank contributes to the collectives of one LM trial: its separator message, the solution vector, three scalars
     B->bytes_per_trial = 8 * ((long long)B->msg_doubles + B->n_pose + 3);
   } else {
-    AL(B->sepY, 1); AL(B->sep_msgs, 1); AL(B->sepS, 1); AL(B->int_work, 1); AL(B->d_int_info, 24); AL(B->sep_work, 1); AL(B->d_sep_info, 24);
+    AL(B->sepY, 1); AL(B->sep_msgs, 1); AL(B->sepS, 1); AL(B->int_work, 1); AL(B->d_int_info, cs::BAND_INFO_WORDS); AL(B->sep_work, 1); AL(B->d_sep_info, cs::BAND_INFO_WORDS);
     std::vector<int> none1(1, 0);
     UP(B->d_sep_off, none1); UP(B->d_sep_col, none1);
     B->bytes_per_trial = R > 1 ? 8 * ((long long)B->s_doubles + B->n_pose + 3 + (B->elim ? B->n_pose - B->n_red : 0)) : 0;
@@ -1695,19 +1696,42 @@ int collect_solve_times(cs_ba* B) {
   return collect_lin_time(B);
 }
 
+// collectives of the sharded solve: RCCL on the handle's stream (queued, no host round trip), or the caller's callback (which is
+// host-synchronous: the stream is drained first)
+int coll_allreduce(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* d, size_t n) {
+  if (fn) {
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
+    if (fn(ctx, d, n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
+  } else if (B->comm) {
+    BA_NCCL(ncclAllReduce(d, d, n, ncclDouble, ncclSum, B->comm, B->st));
+  }
+  return CS_OK;
+}
+// in place: rank r's part sits at buf + r * per_rank.  Through the callback an all-gather is the sum of the zero-padded buffers
+// (the caller zeroes the other ranks' slots first).
+int coll_allgather(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* buf, size_t per_rank) {
+  if (fn) {
+    CS_HIP_TRY(hipStreamSynchronize(B->st));
+    if (fn(ctx, buf, per_rank * (size_t)B->shard_n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
+  } else if (B->comm) {
+    BA_NCCL(ncclAllGather(buf + (size_t)B->shard_rank * per_rank, buf, per_rank, ncclDouble, B->comm, B->st));
+  }
+  return CS_OK;
+}
+
 // Sharded with the cuboids eliminated: a cuboid's increment is computed by the rank that owns it (zero elsewhere); every rank updates
 // all vertices, so the increments (9 doubles per free cuboid, behind the reduced system's in `rhs`) are summed over the ranks.
 int share_cuboid_increments(cs_ba* B, cs_allreduce_fn fn, void* ctx) {
   if (!B->elim || B->shard_n <= 1 || B->n_pose <= B->n_red) return CS_OK;
-  double* xo = B->view.rhs + B->n_red;
-  const size_t n = (size_t)(B->n_pose - B->n_red);
-  if (fn) {
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, xo, n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
-  } else if (B->comm) {
-    BA_NCCL(ncclAllReduce(xo, xo, n, ncclDouble, ncclSum, B->comm, B->st));
-  }
-  return CS_OK;
+  return coll_allreduce(B, fn, ctx, B->view.rhs + B->n_red, (size_t)(B->n_pose - B->n_red));
+}
+
+// A workgroup of a persistent factorisation waited ~1 s for its team (band_wait_ge): the device is shared with another persistent kernel.
+// h_status[0]: the band's / the interior's word; with_sep: h_status[2], the separator system's, counts too.
+int check_band_timeout(const cs_ba* B, bool with_sep) {
+  if (B->h_status[0] != cs::BAND_TIMEOUT_INFO && !(with_sep && B->h_status[2] == cs::BAND_TIMEOUT_INFO)) return CS_OK;
+  cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device");
+  return CS_ERR_HIP;
 }
 
 // defer != nullptr (banded path only): everything is queued and the function returns WITHOUT synchronising; *defer then holds the
@@ -1756,11 +1780,8 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
     if (status_in_scalars) { B->h_status[0] = 0; B->h_status[1] = 0; }
     else CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
     CS_HIP_TRY(hipGetLastError());
-    if (fn && B->shard_n > 1) {  // sum the ranks' partial reduced systems: [S | rhs] in one message
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-      if (fn(ctx, B->S.p, B->s_doubles + B->n_pose, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
-    } else if (!fn && B->comm) {  // RCCL, queued on this stream behind the kernels that produced the partial system: no host round trip
-      BA_NCCL(ncclAllReduce(B->S.p, B->S.p, B->s_doubles + B->n_pose, ncclDouble, ncclSum, B->comm, B->st));
+    if ((fn && B->shard_n > 1) || (!fn && B->comm)) {  // sum the ranks' partial reduced systems: [S | rhs] in one message
+      int rc2 = coll_allreduce(B, fn, ctx, B->S.p, B->s_doubles + B->n_pose); if (rc2) return rc2;
     }
     BA_MARK(B, B->ev[3]);
     if (B->band_ld) {
@@ -1787,10 +1808,7 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
       if (defer) { *defer = std::move(coop_turn); B->tm.n_solves++; return CS_OK; }   // (the caller's sum kernel folds the two status words into the trial's scalars)
       cs::ba_launch_fail_flag(B->d_band_info.p, B->d_elim_fail.p, nullptr, B->d_scalars.p + 2, B->st);
       CS_HIP_TRY(hipStreamSynchronize(B->st));
-      if (*B->h_status == 0x7fffffff) {   // a workgroup waited ~1 s for its team: the device is shared with another persistent kernel
-        cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device");
-        return CS_ERR_HIP;
-      }
+      { int rc2 = check_band_timeout(B, false); if (rc2) return rc2; }
       if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
     } else if (B->sparse) {
       // general sparse: the pattern's blocks are gathered from the dense S by the factorisation itself (sparse_kernels.hip)
@@ -1831,31 +1849,7 @@ int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr
   return CS_OK;
 }
 
-
-// collectives of the sharded solve: RCCL on the handle's stream (queued, no host round trip), or the caller's callback (which is
-// host-synchronous: the stream is drained first)
-int coll_allreduce(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* d, size_t n) {
-  if (fn) {
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, d, n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
-  } else if (B->comm) {
-    BA_NCCL(ncclAllReduce(d, d, n, ncclDouble, ncclSum, B->comm, B->st));
-  }
-  return CS_OK;
-}
-// in place: rank r's part sits at buf + r * per_rank.  Through the callback an all-gather is the sum of the zero-padded buffers
-// (the caller zeroes the other ranks' slots first).
-int coll_allgather(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* buf, size_t per_rank) {
-  if (fn) {
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, buf, per_rank * (size_t)B->shard_n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
-  } else if (B->comm) {
-    BA_NCCL(ncclAllGather(buf + (size_t)B->shard_rank * per_rank, buf, per_rank, ncclDouble, B->comm, B->st));
-  }
-  return CS_OK;
-}
-
-// The damped solve in separator mode (cs_ba::sep_mode; kernels: "sharded reduced solve" in ba_kernels.hip).  What is built here lies
+// The damped solve in separator mode (cs_ba::sep_mode; kernels: "sharded reduced solve" in band_kernels.hip).  What is built here lies
 // in this rank's columns and in the next separator's diagonal block; only the interior is factorised here.  Collectives per solve:
 // one all-gather of the separator messages (3 w^2 + 2 w doubles per rank) and one all-reduce of the solution vector (n_pose doubles:
 // every rank contributes its interior's increments and those of the cuboids it eliminated).  block_solver.hpp:385-485 for what a
@@ -1880,7 +1874,7 @@ int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void
   CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->ev[3]);
   std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-  CS_HIP_TRY(hipMemsetAsync(B->d_int_info.p, 0, 24 * sizeof(int), B->st));
+  CS_HIP_TRY(hipMemsetAsync(B->d_int_info.p, 0, cs::BAND_INFO_WORDS * sizeof(int), B->st));
   // the interior: L L^T = S(I, I), y = L^-1 b_I in place (one-sided order, right-hand side riding along)
   cs::ba_launch_band_cholesky(B->S.p + (size_t)B->int_c * LD, B->int_work.p, B->int_n, LD, rhs + B->int_c, B->d_int_info.p, false, B->st, true);
   CS_HIP_TRY(hipGetLastError());
@@ -1898,14 +1892,14 @@ int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void
   // 2 w_max: the persistent banded Cholesky again (two fronts at 7 separators: 18 dependent steps)
   if (cs::ba_bcr_sep_ok(B->w_max, R)) {
     // ... by block cyclic reduction, straight from the messages' blocks (bcr_kernels.hip): 7 separators = 3 levels instead of 18 dependent steps
-    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, 24 * sizeof(int), B->st));
+    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, cs::BAND_INFO_WORDS * sizeof(int), B->st));
     cs::ba_launch_bcr_sep(B->sep_msgs.p, B->msg_doubles, B->w_max, R, B->d_sep_off.p, B->d_sep_col.p, ns, B->sep_work.p, rhs, B->d_sep_info.p, B->st);
     CS_HIP_TRY(hipGetLastError());
   } else {
     cs::ba_launch_sep_assemble(B->sep_msgs.p, B->msg_doubles, B->w_max, R, B->d_sep_off.p, ns, LDs, B->sepS.p, rsep, B->st);
     CS_HIP_TRY(hipGetLastError());
     if (!coop_turn.owns_lock()) coop_turn.lock();
-    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, 24 * sizeof(int), B->st));
+    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, cs::BAND_INFO_WORDS * sizeof(int), B->st));
     cs::ba_launch_band_cholesky(B->sepS.p, B->sep_work.p, ns, LDs, rsep, B->d_sep_info.p, true, B->st);
     CS_HIP_TRY(hipGetLastError());
     if (fn) {
@@ -1937,7 +1931,7 @@ int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void
   CS_HIP_TRY(hipMemcpyAsync(B->h_scalars + 2, B->d_scalars.p + 2, sizeof(double), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (coop_turn.owns_lock()) coop_turn.unlock();
-  if (B->h_status[0] == 0x7fffffff || B->h_status[2] == 0x7fffffff) { cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
+  { int rc = check_band_timeout(B, true); if (rc) return rc; }
   if (B->h_scalars[2] != 0.0) *ok = false;
   return collect_solve_times(B);
 }
@@ -2811,7 +2805,7 @@ static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn
         if (direct_scalars) { rc = wait_trial(B->trial_seq); if (rc) return rc; hs = B->h_trial; }
         else CS_HIP_TRY(hipStreamSynchronize(B->st));
         turn.unlock();
-        if (B->h_status[0] == 0x7fffffff || (B->sep_mode && B->shard_n > 1 && B->h_status[2] == 0x7fffffff)) { cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device"); return CS_ERR_HIP; }
+        rc = check_band_timeout(B, B->sep_mode && B->shard_n > 1); if (rc) return rc;
         ok2 = hs[2] == 0.0;
         tempChi = hs[0];
         scale = hs[1];

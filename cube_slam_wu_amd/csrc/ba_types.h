@@ -1,5 +1,6 @@
-// ba_types.h -- what ba_host.cpp hands to ba_kernels.hip and bcr_kernels.hip: the device data layout of the bundle-adjustment path
-// (see DESIGN.md "Path B: data layout in HBM") and the launchers.
+// ba_types.h -- what ba_host.cpp hands to ba_kernels.hip: the device data layout of the bundle-adjustment path
+// (see DESIGN.md "Path B: data layout in HBM") and the launchers.  The solvers of the reduced system have seams of their own
+// (band_solver.h, ba_sparse.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -134,7 +135,7 @@ CS_HD double* ba_S_at(const BaView& v, int r, int c) {  // requires r >= c (and 
   return v.band_ld ? v.S + (size_t)c * v.band_ld + (r - c) : v.S + (size_t)r * v.n_red + c;
 }
 
-// ---- launchers (ba_kernels.hip; ba_bcr_* and ba_launch_bcr*: bcr_kernels.hip)
+// ---- launchers (ba_kernels.hip)
 int ba_chi2_blocks(int n_proj);
 void ba_launch_chi2(const BaView& v, int nb_proj, hipStream_t st);
 void ba_launch_fill_rows4(double* dst, const double* rec4, long long rows, hipStream_t st);
@@ -146,22 +147,7 @@ int ba_scale_blocks();
 void ba_launch_scale(const BaView& v, const double* lambda_dev, double* partial, hipStream_t st);
 void ba_launch_update(const BaView& v, hipStream_t st, double* bak_cams = nullptr, double* bak_points = nullptr, double* bak_cubes = nullptr);
 void ba_launch_scale_update(const BaView& v, const double* lambda_dev, double* partial, hipStream_t st, double* bak_cams, double* bak_points, double* bak_cubes);
-void ba_launch_band_cholesky(double* Sb, double* work, int n, int LD, double* rhs, int* info, bool solve, hipStream_t st, bool one_sided = false);
-void ba_launch_sep_reduce(const double* S, int LD, const double* Linv, int ci, int ni, int zl, int wl, int zr, int wr, double* Y, const double* rhs, double* msg, int wm, hipStream_t st);
-void ba_launch_sep_assemble(const double* msgs, size_t msg_doubles, int wm, int R, const int* sep_off, int n, int LDs, double* Ssep, double* rsep, hipStream_t st);
-void ba_launch_sep_scatter(const double* xsep, int n, int R, const int* sep_off, const int* sep_col, double* x, hipStream_t st);
-void ba_launch_sep_backsolve(double* S, int LD, double* work, int ci, int ni, int zl, int wl, int zr, int wr, double* Y, double* rhs, int* info, hipStream_t st);
 void ba_launch_fail_flag(const int* a, const int* b, const int* c, double* out, hipStream_t st);
-size_t ba_band_workspace_doubles(int n, int LD);
-int ba_band_team(int LD, int* rw_out);
-bool ba_band_fits_device(int n, int LD, bool one_sided = false);
-bool ba_bcr_ok(int n, int LD);
-double ba_bcr_estimate_ms(int n);
-size_t ba_bcr_workspace_doubles(int n, int Bv);
-void ba_launch_bcr(const double* Sb, double* work, int n, int LD, int Bv, double* rhs, int* info, hipStream_t st);
-bool ba_bcr_sep_ok(int wm, int R);
-size_t ba_bcr_sep_workspace_doubles(int R);
-void ba_launch_bcr_sep(const double* msgs, size_t msg_doubles, int wm, int R, const int* sep_off, const int* sep_col, int ns, double* work, double* x, int* info, hipStream_t st);
 void ba_launch_sum2(const double* a, int na, const double* b, int nb, double* out, hipStream_t st);
 void ba_launch_multi_zero(const std::pair<void*, size_t>* list, int n, hipStream_t st);
 void ba_launch_multi_copy(const BaCopyItem* list, int n, hipStream_t st);

@@ -1,4 +1,4 @@
-// band_potf2.h -- the diagonal-block routine the reduced-system solvers share (ba_kernels.hip: the persistent banded Cholesky;
+// band_potf2.h -- the diagonal-block routine the reduced-system solvers share (band_kernels.hip: the persistent banded Cholesky;
 // bcr_kernels.hip: block cyclic reduction): Cholesky factor of a 32 x 32 block and the inverse of that factor in one sweep, by one
 // workgroup of 256 threads out of LDS.  Held to a tolerance, not to bit parity (the reference's reduced solve is Eigen's LDLT,
 // object_slam/Thirdparty/g2o/g2o/solvers/linear_solver_dense.h:65-113).

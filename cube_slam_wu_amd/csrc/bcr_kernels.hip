@@ -1,7 +1,7 @@
 // bcr_kernels.hip -- the reduced (pose) system solved by BLOCK CYCLIC REDUCTION, for gfx950 (MI355X).
 //
 // What it replaces: the reduced solve of g2o's BlockSolver (block_solver.hpp:441-453, `_linearSolver->solve(*_Hschur, ...)`; the reference
-// constructs LinearSolverDense, solvers/linear_solver_dense.h:65-113).  The banded Cholesky of ba_kernels.hip eliminates 32 columns per
+// constructs LinearSolverDense, solvers/linear_solver_dense.h:65-113).  The banded Cholesky of band_kernels.hip eliminates 32 columns per
 // dependent step -- 53 steps of ~13 us at C4 (n = 5 994, bandwidth 119), four fronts at once.  The arithmetic (0.2 Gflop) is nothing;
 // the NUMBER of dependent steps is the cost.  Here the band is read as a block-tridiagonal matrix with blocks of Bv >= bandwidth
 // unknowns (padded to B = 128) and eliminated in odd-even (nested dissection) order:
@@ -29,13 +29,13 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "ba_types.h"
+#include "band_solver.h"
 #include "band_potf2.h"
 #include "cs_hip_util.h"
+#include "cs_wave.h"
 
 namespace cs {
 
-typedef double bcr_v4d __attribute__((ext_vector_type(4)));
 enum { BCR_B = 128, BCR_NB = BCR_B / BS, BCR_NT = BCR_B / 16, BCR_NS = BCR_B / 4, BCR_BB = BCR_B * BCR_B, BCR_SLOTS = BCR_NB * (BCR_NB + 1) / 2,
        BCR_MAXLEV = 16, BCR_UPD_SLOTS = BCR_NT * (BCR_NT + 1) / 2 + BCR_NT * BCR_NT + 1 };
 typedef double (*bcr_blk)[BS + 1];
@@ -76,13 +76,13 @@ __device__ __forceinline__ double bcr_b_at(const BcrLevel& P, int k, int r) {
 
 __device__ __forceinline__ double bcr_rowop(bcr_blk M, int t, int s, int lane) { return M[16 * t + (lane & 15)][4 * s + (lane >> 4)]; }
 __device__ __forceinline__ double bcr_colop(bcr_blk M, int s, int t, int lane) { return M[4 * s + (lane >> 4)][16 * t + (lane & 15)]; }
-__device__ __forceinline__ bcr_v4d bcr_ctile_load(bcr_blk M, int ti, int tj, int lane) {
-  bcr_v4d c;
+__device__ __forceinline__ ba_v4d bcr_ctile_load(bcr_blk M, int ti, int tj, int lane) {
+  ba_v4d c;
 #pragma unroll
   for (int g = 0; g < 4; g++) c[g] = M[16 * ti + 4 * g + (lane >> 4)][16 * tj + (lane & 15)];
   return c;
 }
-__device__ __forceinline__ void bcr_ctile_store(bcr_blk M, int ti, int tj, int lane, bcr_v4d c) {
+__device__ __forceinline__ void bcr_ctile_store(bcr_blk M, int ti, int tj, int lane, ba_v4d c) {
 #pragma unroll
   for (int g = 0; g < 4; g++) M[16 * ti + 4 * g + (lane >> 4)][16 * tj + (lane & 15)] = c[g];
 }
@@ -155,7 +155,7 @@ enum { F8_SLOT = BS * (BS + 1), F8_NA = BCR_NB * (BCR_NB + 1) / 2, F8_NL = BCR_N
        BCR_LDS_DOUBLES = (F8_NA + F8_NL) * F8_SLOT + F8_COLBUF + 4 * BCR_B, BCR_FACTOR_THREADS = 512 };
 #define F8_A(i, j) (reinterpret_cast<bcr_blk>(lds + ((i) * ((i) + 1) / 2 + (j)) * F8_SLOT))
 #define F8_L(i, j) (reinterpret_cast<bcr_blk>(lds + (F8_NA + (i) * ((i) - 1) / 2 + (j)) * F8_SLOT))
-#define F8_ZERO (bcr_v4d{0.0, 0.0, 0.0, 0.0})
+#define F8_ZERO (ba_v4d{0.0, 0.0, 0.0, 0.0})
 
 __device__ __forceinline__ void bcr_row8(bcr_blk M, int t, int lane, double (&a)[8]) {
 #pragma unroll
@@ -167,7 +167,7 @@ __device__ __forceinline__ void bcr_col8(bcr_blk M, int t, int lane, double (&b)
 }
 // c (+/-)= rows ti of MA times  BCOL ? columns tj of MB : rows tj of MB transposed,  depth steps [s0, s1) of the 32
 template <bool NEG, bool BCOL>
-__device__ __forceinline__ bcr_v4d f8_mma(bcr_v4d c, bcr_blk MA, int ti, bcr_blk MB, int tj, int lane, int s0, int s1) {
+__device__ __forceinline__ ba_v4d f8_mma(ba_v4d c, bcr_blk MA, int ti, bcr_blk MB, int tj, int lane, int s0, int s1) {
   double a[8], b[8];
   bcr_row8(MA, ti, lane, a);
   if (BCOL) bcr_col8(MB, tj, lane, b); else bcr_row8(MB, tj, lane, b);
@@ -198,7 +198,7 @@ __device__ __forceinline__ void f8_B(double* lds, int K, int j, int ti, int tj, 
 // The M set's products beside a sweep are ISSUED in one interval and STORED at the head of the next: the interval then holds the operand loads
 // and the issue of the eight matrix-core instructions only -- shorter than a round of the sweep, which the set would otherwise hold up at
 // the barrier (measured: 0.7 us per whole product against 0.5 us per round) -- and nothing reads the tile before the barrier after its store.
-struct F8Pend { bcr_v4d c; int off; };      // off: the destination slot's offset in doubles, -1 = nothing pending
+struct F8Pend { ba_v4d c; int off; };      // off: the destination slot's offset in doubles, -1 = nothing pending
 #define F8_OFF_A(i, j) (((i) * ((i) + 1) / 2 + (j)) * F8_SLOT)
 #define F8_OFF_L(i, j) ((F8_NA + (i) * ((i) - 1) / 2 + (j)) * F8_SLOT)
 __device__ __forceinline__ void f8_flush(double* lds, F8Pend& q, int ti, int tj, int lane) {
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(256) void bcr_panel_kernel(BcrLevel P) {
   for (int s = 0; s < 16; s++) a0[s] = TA[(size_t)(m0 * BCR_NS + (s < 4 * (m0 + 1) ? s : 0)) * 64 + lane];
 #pragma unroll
   for (int s = 0; s < BCR_NS; s++) a1[s] = TA[(size_t)(m1 * BCR_NS + (s < 4 * (m1 + 1) ? s : 0)) * 64 + lane];
-  bcr_v4d c0 = bcr_v4d{0.0, 0.0, 0.0, 0.0}, c1 = bcr_v4d{0.0, 0.0, 0.0, 0.0};
+  ba_v4d c0 = ba_v4d{0.0, 0.0, 0.0, 0.0}, c1 = ba_v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int s = 0; s < BCR_NS; s++) {
     if (s < 16 && s < 4 * (m0 + 1)) c0 = BCR_MFMA(a0[s & 15], bop[s], c0);
@@ -524,7 +524,7 @@ __global__ __launch_bounds__(256) void bcr_update_kernel(BcrLevel P) {
     if (w == 0)
 #pragma unroll
       for (int g = 0; g < 4; g++) d[g] = Dr[(16 * a + 4 * g + (lane >> 4)) * BCR_B + 16 * b + (lane & 15)];
-    bcr_v4d acc = bcr_v4d{0.0, 0.0, 0.0, 0.0};
+    ba_v4d acc = ba_v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < 8; q++) acc = BCR_MFMA(pa[q], pb[q], acc);
     if (has_r)
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256) void bcr_update_kernel(BcrLevel P) {
     double pa[8], pb[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) { const int s = 8 * w + q; pa[q] = Aop[((size_t)s * BCR_NT + a) * 64 + lane]; pb[q] = Bop[((size_t)s * BCR_NT + b) * 64 + lane]; }
-    bcr_v4d acc = bcr_v4d{0.0, 0.0, 0.0, 0.0};
+    ba_v4d acc = ba_v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < 8; q++) acc = BCR_MFMA(pa[q], pb[q], acc);
 #pragma unroll
@@ -720,7 +720,7 @@ void ba_launch_bcr(const double* Sb, double* work, int n, int LD, int Bv, double
 }
 
 // ------------------------------------------------------------------------- the sharded solve's separator system, in block form --
-// Separator mode of the sharded BA (ba_kernels.hip, "sharded reduced solve"): after the all-gather every rank holds the R messages
+// Separator mode of the sharded BA (band_kernels.hip, "sharded reduced solve"): after the all-gather every rank holds the R messages
 // [LL | RL | RR | tL | tR] (three wm x wm blocks, two wm-vectors) and solves the block-tridiagonal system of the R - 1 separators:
 //   D_k = LL(rank k + 1) + RR(rank k),   A(k + 1, k) = RL(rank k + 1),   b_k = tL(rank k + 1) + tR(rank k)        (block k = separator Z_(k+1))
 // The blocks (<= 128 wide, padded with the identity) go straight into the level-0 arrays; x comes back as N x 128 padded blocks.

@@ -7,7 +7,7 @@
 //                          LDS), the diagonal block is factorised, the rows below are scaled by L_jj^-T -- the right-hand side's row
 //                          becomes y_j -- and the panel is written through to memory before the column's flag is raised.
 //   sparse_back_kernel     L^T x = y the same way in the reverse order, a wavefront per column.
-// Hand-offs between workgroups follow the banded solver's protocol (ba_kernels.hip): write-through stores, drained, then a flag; the
+// Hand-offs between workgroups follow the banded solver's protocol (band_kernels.hip): write-through stores, drained, then a flag; the
 // consumer polls the flag, takes one agent-scope acquire and reads with plain loads.  Waits are bounded (~1 s): a starved grid fails.
 #include <hip/hip_runtime.h>
 

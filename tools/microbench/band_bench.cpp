@@ -1,5 +1,5 @@
 // band_bench -- standalone timing + residual check of the banded Cholesky kernels (development tool, not shipped).
-//   hipcc --offload-arch=gfx950 -O3 -x hip tools/microbench/band_bench.cpp cube_slam_wu_amd/csrc/ba_kernels.o -o /tmp/band_bench
+//   hipcc --offload-arch=gfx950 -O3 -x hip tools/microbench/band_bench.cpp cube_slam_wu_amd/csrc/band_kernels.o cube_slam_wu_amd/csrc/bcr_kernels.o -o /tmp/band_bench
 //   /tmp/band_bench [n] [LD] [reps] [order: 0 nested / two fronts, 1 one-sided, 2 block cyclic reduction] [Bv of order 2, default 128]
 #include <hip/hip_runtime.h>
 #pragma clang diagnostic ignored "-Wunused-value"
@@ -12,7 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../cube_slam_wu_amd/csrc/ba_types.h"
+#include "../../cube_slam_wu_amd/csrc/band_solver.h"
 
 int main(int argc, char** argv) {
   int n = argc > 1 ? atoi(argv[1]) : 10494, LD = argc > 2 ? atoi(argv[2]) : 183, reps = argc > 3 ? atoi(argv[3]) : 5;
@@ -26,7 +26,7 @@ int main(int argc, char** argv) {
     for (int d = 1; d <= bw && c + d < n; d++) { double v = rnd(); A[(size_t)c * LD + d] = v; diag[c] += std::fabs(v); diag[c + d] += std::fabs(v); }
   for (int c = 0; c < n; c++) { A[(size_t)c * LD] = diag[c]; b[c] = rnd(); }
   double *dS, *dL, *dr; int* dinfo;
-  hipMalloc(&dS, A.size() * 8); hipMalloc(&dL, std::max(cs::ba_band_workspace_doubles(n, LD), cs::ba_bcr_workspace_doubles(n, Bv)) * 8); hipMalloc(&dr, n * 8); hipMalloc(&dinfo, 96);
+  hipMalloc(&dS, A.size() * 8); hipMalloc(&dL, std::max(cs::ba_band_workspace_doubles(n, LD), cs::ba_bcr_workspace_doubles(n, Bv)) * 8); hipMalloc(&dr, n * 8); hipMalloc(&dinfo, cs::BAND_INFO_WORDS * sizeof(int));
   hipStream_t st; hipStreamCreate(&st);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   std::vector<double> x(n);
@@ -35,7 +35,7 @@ int main(int argc, char** argv) {
     if (r > 0) { for (auto& v : A) v *= 1.25; for (int c = 0; c < n; c++) A[(size_t)c * LD] += 0.5 * r; for (auto& v : b) v = rnd(); }
     hipMemcpyAsync(dS, A.data(), A.size() * 8, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(dr, b.data(), n * 8, hipMemcpyHostToDevice, st);
-    hipMemsetAsync(dinfo, 0, 96, st);
+    hipMemsetAsync(dinfo, 0, cs::BAND_INFO_WORDS * sizeof(int), st);
     hipEventRecord(e0, st);
     if (order == 2) cs::ba_launch_bcr(dS, dL, n, LD, Bv, dr, dinfo, st);
     else cs::ba_launch_band_cholesky(dS, dL, n, LD, dr, dinfo, true, st, order == 1);

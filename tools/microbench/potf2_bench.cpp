@@ -5,7 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../../cube_slam_wu_amd/csrc/ba_kernels.hip"
+#include "../../cube_slam_wu_amd/csrc/band_kernels.hip"
 
 
 // the routine's rounds under a stopwatch (a copy of band_potf2_inv4b_impl with clock reads; thread 0's accumulated phase times)

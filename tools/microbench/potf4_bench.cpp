@@ -29,7 +29,7 @@ __global__ __launch_bounds__(512) void potf4_kernel(const double* A, double* Xou
     for (int i0 = 0; i0 < 7; i0++) {
       if (isP) { cs::potf4_post(S, i0, colbuf, lane, ws); cs::potf4_pre(S, i0 + 1, colbuf, lane, ws); }
       else if (busy_m) {   // the other set's kind of work: LDS operand reads + matrix-core products
-        cs::bcr_v4d c = cs::bcr_v4d{0.0, 0.0, 0.0, 0.0};
+        cs::ba_v4d c = cs::ba_v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int s = 0; s < 8; s++) { const double a = U[(lane & 15) + 16 * (ws & 1)][4 * s + (lane >> 4)]; c = BCR_MFMA(a, a + junk, c); }
         junk += c[0];
