@@ -23,6 +23,9 @@ void cs_set_error(const std::string& s);
     }                                                                          \
   } while (0)
 
+// grow a DevBuf / PinBuf (below) inside a function that returns a CS_* code
+#define CS_ENSURE(buf, n) do { if (int _rc = (buf).ensure(n)) return _rc; } while (0)
+
 // No C++ exception may cross the C boundary (std::bad_alloc / std::length_error from a host buffer would terminate the caller).
 #define CS_GUARD_BEGIN try {
 #define CS_GUARD_END(fn_name)                                                                                                \
@@ -43,11 +46,15 @@ inline int check_device(int device) {
 }
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// Grow-only device / pinned buffers.
+// Grow-only device / pinned buffers.  They free themselves (release() is idempotent: a holder may still call it early) and cannot be copied.
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int ensure(size_t n) {
     if (n <= cap) return CS_OK;
     if (p) (void)hipFree(p);
@@ -63,6 +70,10 @@ template <class T>
 struct PinBuf {
   T* p = nullptr;
   size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
   int ensure(size_t n) {
     if (n <= cap) return CS_OK;
     if (p) (void)hipHostFree(p);

@@ -40,11 +40,14 @@
 #include "../../include/cubeslam_hip.h"
 #include "cs_hip_util.h"
 #include "detect_hooks.h"
+#include "detect_rank_host.h"
 #include "detect_types.h"
 #include "edge_types.h"
 
 thread_local std::string g_cs_err;  // shared by every path (cs_hip_util.h: cs_set_error)
 void cs_set_error(const std::string& s) { g_cs_err = s; }
+
+using namespace cs_dh;   // detect_rank_host.h: FrameIn, the slot decode, the exact ranking, the record writers
 
 namespace {
 
@@ -112,11 +115,6 @@ class WorkerPool {
   unsigned long long gen_ = 0;
   bool stop_ = false;
 };
-
-// sin and cos stay two libm calls (the reference's default Debug build makes two calls; glibc's fused
-// sincos() rounds differently in ~1.4e-3 of arguments).  The volatile copy keeps compilers from merging.
-inline double h_sin(double x) { volatile double v = x; return std::sin(v); }
-inline double h_cos(double x) { volatile double v = x; return std::cos(v); }
 
 // ---------------------------------------------------------------- camera cache (set_cam_pose) ---
 struct M3 { double m[9]; };
@@ -252,56 +250,6 @@ void merge_lines(std::vector<double>& L, double dist_thre, double angle_thre_deg
     total = k;
   }
   L.resize(4 * (size_t)total);
-}
-
-// fuse_normalize_scores_v2 (object_3d_util.cpp:726-837)
-void fuse_scores(const double* dist, const double* angle, int n, double w_angle, std::vector<int>& keep, std::vector<double>& score) {
-  keep.clear();
-  if (n > 4) {
-    int bn = (int)std::round(float(n) / 3.0 * 2.0);
-    // std::partial_sort of the ids by value (sort_indexes, matrix_utils.cpp:327-335).  The keys travel with the ids: the
-    // algorithm makes the same comparisons and moves as on a bare id array (so ties resolve identically), without the
-    // indirect loads
-    struct KI { double key; int id; };
-    std::vector<KI> ds(n), as(n);
-    for (int i = 0; i < n; i++) { ds[i] = KI{dist[i], i}; as[i] = KI{angle[i], i}; }
-    auto by_key = [](const KI& a, const KI& b) { return a.key < b.key; };
-    std::partial_sort(ds.begin(), ds.begin() + bn, ds.end(), by_key);
-    std::partial_sort(as.begin(), as.begin() + bn, as.end(), by_key);
-    std::vector<int> di(bn), ai(bn);
-    for (int i = 0; i < bn; i++) { di[i] = ds[i].id; ai[i] = as[i].id; }
-    std::vector<int> dk(di.begin(), di.begin() + bn - 1);
-    if (angle[ai[bn - 1]] > angle[ai[bn - 2]]) {
-      // sort both id lists + set_intersection (:771-776) = the ids present in both, ascending: one pass over a marker array
-      std::vector<unsigned char> in(n, 0);
-      for (int i = 0; i < bn - 1; i++) { in[di[i]] |= 1; in[ai[i]] |= 2; }
-      for (int id = 0; id < n; id++) if (in[id] == 3) keep.push_back(id);
-    } else {
-      keep = dk;
-    }
-  } else {
-    keep.resize(n);
-    std::iota(keep.begin(), keep.end(), 0);
-  }
-  int k = (int)keep.size();
-  double dmin = 1e6, dmax = -1, amin = 1e6, amax = -1;
-  for (int i = 0; i < k; i++) {
-    double d = dist[keep[i]], a = angle[keep[i]];
-    dmin = std::min(dmin, d); dmax = std::max(dmax, d);
-    amin = std::min(amin, a); amax = std::max(amax, a);
-  }
-  score.resize(k);
-  if (k > 1) {
-    bool na = (amax - amin) > 0;
-    for (int i = 0; i < k; i++) {
-      double d = (dist[keep[i]] - dmin) / (dmax - dmin);
-      double a = angle[keep[i]];
-      if (na) a = (a - amin) / (amax - amin);
-      score[i] = (d + w_angle * a) / (1 + w_angle);
-    }
-  } else {
-    for (int i = 0; i < k; i++) score[i] = (dist[keep[i]] + w_angle * angle[keep[i]]) / (1 + w_angle);
-  }
 }
 
 // ---- the working streams of all detectors of a process on one device ---------------------------------------------------------
@@ -454,16 +402,6 @@ static void sweep_side_streams(const cs_detector* d, hipStream_t* corners, hipSt
   }
 }
 
-struct FrameIn {
-  double K[9], invK[9], R[9], t[3];
-  int img_w, img_h, n_boxes, n_lines;
-  std::vector<double> boxes;     // n x 5
-  std::vector<double> lines;     // M x 4, left-to-right aligned (object_3d_util.cpp:246-258)
-  std::vector<long long> map_offs;  // per (box, k): float offset into the device map pool (-1 = absent)
-  std::vector<cs_roi> rois;      // n x 3
-  std::vector<int> n_heights;    // n
-};
-
 struct JobHost {          // host-side companion of a JobDesc of the current round
   int frame, box, hid;
   int yaw_off_local;
@@ -482,13 +420,12 @@ struct JobResult {        // rank-stage products retained for cs_batch_debug_*
   int frame, box, hid, n_valid;
   std::vector<double> rows9;     // V x 9
   std::vector<long long> slots;  // V
-  std::vector<int> rp_idx;       // V: roll/pitch sample of each candidate
   std::vector<int> keep;
   std::vector<double> score;
   std::vector<double> corners;   // V x 16 when debug is on
 };
 
-// One of the two in-flight chunks of the pipelined production path (run_pipelined).
+// One of the two in-flight chunks of the pipelined production path (pipe_launch / pipe_finish).  Its buffers free themselves.
 struct PipeSlot {
   DevBuf<cs::JobDesc> jobs;
   DevBuf<unsigned char> tab_arena;       // a small call's tables in one block: one upload instead of ten (single-frame latency)
@@ -520,7 +457,6 @@ struct PipeSlot {
   long long rp_pool_cap = 0;
   int rp_NT = 0, rp_YCAP = 0;
   std::vector<hipEvent_t> rp_ev;     // 5 per round: start, corners + compaction, VP support, scorer, ranking + records
-  bool rp_mode = false;
   PinBuf<cs::JobDesc> h_jobs_in, h_jobs_out;
   PinBuf<long long> h_slot_prefix, h_job_cbase;
   PinBuf<int> h_vp_prefix, h_top_x, h_box_job0, h_box_njobs, h_win_count, h_fallback, h_job_valid;
@@ -535,21 +471,10 @@ struct PipeSlot {
   long long slot_total = 0;
   bool in_flight = false;
   bool counted_busy = false;      // this sweep is in the detector's and the stream set's `busy` counts
-  void release() {
-    jobs.release(); slot_prefix.release(); job_cbase.release(); c_slot.release(); fb_slot.release();
-    vp_prefix.release(); top_x.release(); flag.release(); job_valid.release(); c_flag.release(); box_job0.release(); box_njobs.release(); win_count.release();
-    fallback.release(); fb_flag.release(); mid_x.release(); mid_y.release(); ang.release(); yaw.release(); yaw_c.release(); yaw_s.release();
-    vp.release(); bound.release(); bound3.release(); ls_order.release(); blk_info.release(); ls_crowded.release(); h_ls_order.release(); c_dist.release(); c_angle.release(); c_skew.release(); fb_dist.release(); fb_angle.release(); fb_skew.release();
-    winners.release(); records.release(); h_records.release(); rp_trip_cnt.release(); rp_cur_idx.release(); rp_tab_count.release(); rp_maps.release(); rp_last_slot.release(); rp_box_base.release(); rp_pool_used.release(); rp_raw_euler.release(); h_rp_tab_count.release(); h_rp_maps.release(); h_rp_raw_euler.release(); h_rp_last_slot.release(); h_rp_box_base.release(); h_rp_pool_used.release(); h_jobs_in.release(); h_jobs_out.release(); h_slot_prefix.release(); h_job_cbase.release(); h_vp_prefix.release();
-    h_top_x.release(); h_box_job0.release(); h_box_njobs.release(); h_win_count.release(); h_fallback.release(); h_job_valid.release(); h_yaw.release();
-    h_yaw_c.release(); h_yaw_s.release();
-    h_fb_src.release(); h_fb_dst.release(); h_fb_slot.release(); h_win_slots.release(); h_fb_cnt.release(); h_fb_flag.release(); h_fb_dist.release(); h_fb_angle.release();
-    h_fb_skew.release(); h_win_corners.release();
+  ~PipeSlot() {
     if (done) (void)hipEventDestroy(done);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : rp_ev) if (e) (void)hipEventDestroy(e);
-    rp_ev.clear();
-    done = nullptr; for (auto& e : ev) e = nullptr;
   }
 };
 
@@ -588,9 +513,8 @@ struct cs_batch {
   DevBuf<cs::JobDesc> d_jobs;
   DevBuf<long long> d_slot_prefix, d_job_cbase, d_c_slot, d_win_slots;
   DevBuf<int> d_vp_prefix, d_top_x, d_flag, d_job_valid, d_c_flag;
-  DevBuf<double> d_mid_x, d_mid_y, d_ang, d_yaw, d_yaw_c, d_yaw_s, d_vp, d_bound, d_dist, d_angle, d_skew, d_corners, d_c_dist, d_c_angle, d_c_skew, d_win_corners;
+  DevBuf<double> d_mid_x, d_mid_y, d_ang, d_yaw, d_yaw_c, d_yaw_s, d_vp, d_bound, d_c_dist, d_c_angle, d_c_skew, d_win_corners;
   DevBuf<cs::RpPose> d_rp;
-  PinBuf<char> h_stage;
   PinBuf<long long> h_c_slot, h_job_cbase;
   PinBuf<int> h_c_flag, h_job_valid;
   PinBuf<double> h_c_dist, h_c_angle, h_c_skew, h_win_corners;
@@ -612,6 +536,13 @@ struct cs_batch {
   std::vector<JobResult> results;             // all jobs of the last run (index via job_index)
   std::vector<int> job_index;                 // (frame*max_boxes + box)*3 + k -> results idx or -1
   cs_detect_timing timing{};
+  // (the caller has made the device current.)  The upload stream first: nothing may still be writing the image buffers when the
+  // members -- every device and pinned buffer above -- free themselves after this body
+  ~cs_batch() {
+    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+    for (auto& e : ev_copied) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_edge_done) if (e) (void)hipEventDestroy(e);
+  }
 };
 
 
@@ -664,7 +595,6 @@ int cs_check_score_atan2(const double* y, const double* x, int n, double* out, i
     return CS_OK;
   };
   if (rc == CS_OK) rc = run();
-  d.release(); a.release();
   return rc;
 }
 
@@ -690,7 +620,6 @@ int cs_check_score_sample_index(const double* sy, const double* sx, const int* m
     return CS_OK;
   };
   if (rc == CS_OK) rc = run();
-  d.release(); w.release();
   return rc;
 }
 
@@ -829,7 +758,6 @@ static void edge_rois_largest_first(std::vector<cs::EdgeRoi>& er) {
 static int batch_layout(cs_detector* d, cs_batch* b);
 static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_counts, bool defer);
 static int batch_flush_refill(cs_detector* d, cs_batch* b);
-static void release_batch_buffers(cs_batch* b);
 static int batch_create_impl(cs_detector* d, const cs_frame_desc* fr, const unsigned char* const* grays, int n_frames, cs_batch** out) {
   if (!d || !out || (!fr && n_frames) || n_frames < 0) return CS_ERR_INVALID_ARG;
   *out = nullptr;
@@ -1086,27 +1014,7 @@ void cs_batch_destroy(cs_batch* b) {
   (void)hipSetDevice(b->det->device);
   if (b->run_state) { (void)hipDeviceSynchronize(); batch_drop_run_state(b); }   // a submitted sweep that was never collected
   for (PipeSlot& S : b->pipe) if (S.counted_busy) { S.counted_busy = false; b->det->busy.fetch_sub(1); b->det->streams->busy.fetch_sub(1); }
-  release_batch_buffers(b);
   delete b;
-}
-static void release_batch_buffers(cs_batch* b) {
-  b->pipe[0].release(); b->pipe[1].release();
-  b->d_maps.release(); b->d_invK.release(); b->d_frame_lines.release(); b->d_frame_line_ptr.release(); b->d_jobs.release(); b->d_slot_prefix.release(); b->d_job_cbase.release();
-  b->d_c_slot.release(); b->d_win_slots.release(); b->d_vp_prefix.release(); b->d_top_x.release(); b->d_flag.release();
-  b->d_job_valid.release(); b->d_c_flag.release(); b->d_mid_x.release(); b->d_mid_y.release(); b->d_ang.release();
-  b->d_yaw.release(); b->d_yaw_c.release(); b->d_yaw_s.release(); b->d_vp.release(); b->d_bound.release(); b->d_dist.release();
-  b->d_angle.release(); b->d_skew.release(); b->d_corners.release(); b->d_c_dist.release(); b->d_c_angle.release();
-  b->d_c_skew.release(); b->d_win_corners.release(); b->d_rp.release(); b->h_rp.release();
-  b->d_gray.release(); b->d_cls.release(); b->d_edge_rois.release(); b->h_maps_stage.release(); b->d_gray2.release();
-  if (b->copy_stream) { (void)hipStreamSynchronize(b->copy_stream); (void)hipStreamDestroy(b->copy_stream); b->copy_stream = nullptr; }
-  for (auto& e : b->ev_copied) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  for (auto& e : b->ev_edge_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  b->h_stage.release(); b->h_c_slot.release(); b->h_job_cbase.release(); b->h_c_flag.release(); b->h_job_valid.release();
-  b->h_c_dist.release(); b->h_c_angle.release(); b->h_c_skew.release(); b->h_win_corners.release();
-  b->d_box_job0.release(); b->d_box_njobs.release(); b->d_win_count.release(); b->d_fallback.release(); b->d_winners.release(); b->d_last_slot.release(); b->h_last_slot.release();
-  b->h_winners.release(); b->h_win_count.release(); b->h_fallback.release(); b->h_jobs.release(); b->h_tables.release(); b->h_tables2.release();
-  b->d_fb_src.release(); b->d_fb_dst.release(); b->d_fb_slot.release(); b->d_fb_cnt.release(); b->d_fb_flag.release();
-  b->d_fb_dist.release(); b->d_fb_angle.release(); b->d_fb_skew.release();
 }
 
 int cs_batch_set_debug(cs_batch* b, int enable) {
@@ -1119,63 +1027,6 @@ int cs_batch_set_debug(cs_batch* b, int enable) {
 }
 
 }  // extern "C"
-
-namespace {
-
-struct Proposal {   // one entry of raw_obj_proposals (box_proposal_detail.cpp:195, :797)
-  int res_idx;      // JobResult index
-  int cand;         // candidate index inside the job (raw_cube_ind)
-  double normalized_error, skew;
-};
-
-struct Winner {
-  int frame, box, rank;
-  int res_idx, cand;
-  double normalized_error, skew;
-};
-
-// Build one cs_cuboid from the winner's corners (box_proposal_detail.cpp:740-798, object_3d_util.cpp:941-1011).
-void finish_cuboid(const FrameIn& F, const cs::RpPose& pose, const double* rows9, const double* corners16, const double raw_euler[3],
-                   bool sample_rp, double normalized_error, cs_cuboid& o) {
-  std::memset(&o, 0, sizeof(o));
-  cs::V2 c[8];
-  for (int i = 0; i < 8; i++) c[i] = cs::v2(corners16[i], corners16[8 + i]);
-  cs::lift_to_3d(c, pose.R, pose.t, F.invK, pose.plane, o.pos, o.scale);
-  o.rotY = rows9[2];
-  o.box_config_type[0] = rows9[0]; o.box_config_type[1] = rows9[1];
-  static const int left_ids[8] = {6, 5, 8, 7, 2, 3, 4, 1}, right_ids[8] = {5, 6, 7, 8, 3, 2, 1, 4};
-  const int* ids = (rows9[1] == 1) ? left_ids : right_ids;
-  for (int i = 0; i < 8; i++) {
-    o.box_corners_2d[i] = (int)corners16[ids[i] - 1];
-    o.box_corners_2d[8 + i] = (int)corners16[8 + ids[i] - 1];
-  }
-  // compute3D_BoxCorner (object_3d_util.cpp:59-73) with similarityTransformation (:15-44)
-  static const double body[3][8] = {{1, 1, -1, -1, 1, 1, -1, -1}, {1, -1, -1, 1, 1, -1, -1, 1}, {-1, -1, -1, -1, 1, 1, 1, 1}};
-  double cr = h_cos(o.rotY), sr = h_sin(o.rotY);
-  double rot[3][3] = {{cr, -sr, 0}, {sr, cr, 0}, {0, 0, 1}};
-  double S[4][4] = {{0}};
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) S[i][j] = rot[i][j] * o.scale[j];
-    S[i][3] = o.pos[i];
-  }
-  S[3][3] = 1;
-  for (int k = 0; k < 8; k++) {
-    double p[4] = {body[0][k], body[1][k], body[2][k], 1.0}, w[4];
-    for (int i = 0; i < 4; i++) w[i] = ((S[i][0] * p[0] + S[i][1] * p[1]) + S[i][2] * p[2]) + S[i][3] * p[3];
-    for (int i = 0; i < 3; i++) o.box_corners_3d_world[8 * i + k] = w[i] / w[3];
-  }
-  o.edge_distance_error = rows9[4];
-  o.edge_angle_error = rows9[5];
-  o.normalized_error = normalized_error;
-  o.skew_ratio = std::max(o.scale[0], o.scale[1]) / std::min(o.scale[0], o.scale[1]);
-  o.down_expand_height = rows9[6];
-  if (sample_rp) {
-    o.camera_roll_delta = rows9[7] - raw_euler[0];
-    o.camera_pitch_delta = rows9[8] - raw_euler[1];
-  }
-}
-
-}  // namespace
 
 
 // ================================================================== pipelined production path =====
@@ -1230,10 +1081,8 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   if ((long long)nj * 1 > 0x7fffffffLL || (long long)n_lines > 0x7fffffffLL) { cs_set_error("chunk too large"); return CS_ERR_CAPACITY; }
   S.nj = nj;
   if (nj == 0) { S.nb = 0; S.slot_total = 0; S.vp_total = 0; S.in_flight = true; C.tm->setup_host_ms += now_ms() - t0; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
-  int rc;
-#define PENS(buf, n) do { rc = (buf).ensure(n); if (rc) return rc; } while (0)
-  PENS(S.h_jobs_in, nj); PENS(S.h_slot_prefix, nj + 1); PENS(S.h_vp_prefix, nj + 1); PENS(S.h_yaw, n_yaw + 1); PENS(S.h_yaw_c, n_yaw + 1); PENS(S.h_yaw_s, n_yaw + 1);
-  PENS(S.h_top_x, n_top + 1); PENS(S.h_box_job0, nj); PENS(S.h_box_njobs, nj); PENS(S.h_ls_order, nj);
+  CS_ENSURE(S.h_jobs_in, nj); CS_ENSURE(S.h_slot_prefix, nj + 1); CS_ENSURE(S.h_vp_prefix, nj + 1); CS_ENSURE(S.h_yaw, n_yaw + 1); CS_ENSURE(S.h_yaw_c, n_yaw + 1); CS_ENSURE(S.h_yaw_s, n_yaw + 1);
+  CS_ENSURE(S.h_top_x, n_top + 1); CS_ENSURE(S.h_box_job0, nj); CS_ENSURE(S.h_box_njobs, nj); CS_ENSURE(S.h_ls_order, nj);
   std::atomic<int> overflow{0};
   d->pool->run(nf, [&](int q) {
     const int f = f0 + q;
@@ -1243,7 +1092,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     int nY = -1, ji = 0;
     for (int bi = 0; bi < F.n_boxes; bi++) {
       const double* bb = &F.boxes[5 * bi];
-      int left = bb[0], top = bb[1], w = bb[2], h = bb[3];
+      int left = bb[0], w = bb[2];
       int right = left + bb[2];
       int res = (int)std::round(std::min(20, w / 10));
       const int tb = b->top_base[b->box_base[f] + bi] - tp0, tcap = b->top_base[b->box_base[f] + bi + 1] - tp0 - tb;
@@ -1261,15 +1110,9 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
         for (int x = left + 5; x <= right - 5 && nT < tcap; x += res) tx[nT++] = x;   // linespace<int> (matrix_utils.cpp:368-380)
       }
       for (int k = 0; k < F.n_heights[bi]; k++) {
-        const cs_roi& roi = F.rois[3 * bi + k];
         cs::JobDesc jd;
-        std::memset(&jd, 0, sizeof(jd));
-        int he = h + roi.down_expand;
-        jd.g.left = left; jd.g.top = top; jd.g.right = right; jd.g.down = top + he;
-        jd.g.el = roi.left; jd.g.et = roi.top; jd.g.er = roi.left + roi.width; jd.g.eb = roi.top + roi.height;
-        jd.map_w = roi.width; jd.Y = (res >= 1) ? std::max(nY, 0) : 0; jd.T = nT; jd.RP = 1; jd.down_expand = roi.down_expand;
-        jd.frame = f; jd.box = bi; jd.hid = k; jd.map_off = F.map_offs[3 * bi + k]; jd.rp_off = (*C.rp_off)[f];
-        jd.diag = std::sqrt(double(w * w + he * he));
+        fill_job_geometry(jd, F, bi, k, (*C.rp_off)[f]);
+        jd.frame = f; jd.Y = (res >= 1) ? std::max(nY, 0) : 0; jd.T = nT; jd.RP = 1;
         jd.yaw_off = q * YCAP; jd.top_off = tb;
         jd.line_off = (int)(b->line_base[f] - ln0) + ji * F.n_lines;
         jout[ji++] = jd;
@@ -1312,19 +1155,18 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   }
   S.nb = nb;
   MARK(1, tq);   // prefixes + box table
-  MARK(2, tq);   // box table
   C.tm->setup_host_ms += now_ms() - t0;
   C.tm->n_jobs += (long long)nj; C.tm->n_slots += real_slots;
   // ---- device buffers, H2D, kernels, D2H: all asynchronous on the detector's stream
   const long long slot_total = S.slot_total;
-  PENS(S.ls_order, nj); PENS(S.jobs, nj); PENS(S.slot_prefix, nj + 1); PENS(S.vp_prefix, nj + 1); PENS(S.job_valid, nj); PENS(S.job_cbase, nj + 1);
-  PENS(S.mid_x, n_lines + 1); PENS(S.mid_y, n_lines + 1); PENS(S.ang, n_lines + 1); PENS(S.yaw, n_yaw + 1); PENS(S.yaw_c, n_yaw + 1); PENS(S.yaw_s, n_yaw + 1);
-  PENS(S.top_x, n_top + 1); PENS(S.vp, 6 * (size_t)S.vp_total + 6); PENS(S.bound, 6 * (size_t)S.vp_total + 6); PENS(S.bound3, nj * (size_t)cs::vp3_table_doubles_per_job());
-  PENS(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4); PENS(S.ls_crowded, 2 * (nj + 1) + 2);
-  PENS(S.c_slot, slot_total + 1); PENS(S.c_flag, slot_total + 1); PENS(S.c_dist, slot_total + 1);
-  PENS(S.c_angle, slot_total + 1); PENS(S.c_skew, slot_total + 1); PENS(S.box_job0, nb + 1); PENS(S.box_njobs, nb + 1); PENS(S.win_count, nb + 1);
-  PENS(S.fallback, nb + 1); PENS(S.winners, nb * KMAX + 1); PENS(S.records, nb * KMAX + 1); PENS(S.h_records, nb * KMAX + 1);
-  PENS(S.h_win_count, nb + 1); PENS(S.h_fallback, nb + 1); PENS(S.h_job_valid, nj); PENS(S.h_job_cbase, nj + 1); PENS(S.h_jobs_out, nj);
+  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.jobs, nj); CS_ENSURE(S.slot_prefix, nj + 1); CS_ENSURE(S.vp_prefix, nj + 1); CS_ENSURE(S.job_valid, nj); CS_ENSURE(S.job_cbase, nj + 1);
+  CS_ENSURE(S.mid_x, n_lines + 1); CS_ENSURE(S.mid_y, n_lines + 1); CS_ENSURE(S.ang, n_lines + 1); CS_ENSURE(S.yaw, n_yaw + 1); CS_ENSURE(S.yaw_c, n_yaw + 1); CS_ENSURE(S.yaw_s, n_yaw + 1);
+  CS_ENSURE(S.top_x, n_top + 1); CS_ENSURE(S.vp, 6 * (size_t)S.vp_total + 6); CS_ENSURE(S.bound, 6 * (size_t)S.vp_total + 6); CS_ENSURE(S.bound3, nj * (size_t)cs::vp3_table_doubles_per_job());
+  CS_ENSURE(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2);
+  CS_ENSURE(S.c_slot, slot_total + 1); CS_ENSURE(S.c_flag, slot_total + 1); CS_ENSURE(S.c_dist, slot_total + 1);
+  CS_ENSURE(S.c_angle, slot_total + 1); CS_ENSURE(S.c_skew, slot_total + 1); CS_ENSURE(S.box_job0, nb + 1); CS_ENSURE(S.box_njobs, nb + 1); CS_ENSURE(S.win_count, nb + 1);
+  CS_ENSURE(S.fallback, nb + 1); CS_ENSURE(S.winners, nb * KMAX + 1); CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1);
+  CS_ENSURE(S.h_win_count, nb + 1); CS_ENSURE(S.h_fallback, nb + 1); CS_ENSURE(S.h_job_valid, nj); CS_ENSURE(S.h_job_cbase, nj + 1); CS_ENSURE(S.h_jobs_out, nj);
   // the tables' device addresses: the slot's own buffers, or -- a call of a frame or two, where ten copies of a few hundred bytes cost ten
   // launch latencies (~150 us of a 0.46 ms call) -- pieces of ONE block that goes up in one copy
   int* p_ls_order = S.ls_order.p; cs::JobDesc* p_jobs = S.jobs.p; long long* p_slot_prefix = S.slot_prefix.p; int* p_vp_prefix = S.vp_prefix.p;
@@ -1344,7 +1186,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     const size_t o_jobs = room(sizeof(cs::JobDesc) * nj), in_end = need;
     S.o_jobs = o_jobs; S.o_rec = room(sizeof(cs_cuboid) * nb * KMAX); S.o_wc = room(sizeof(int) * nb); S.o_fb = room(sizeof(int) * nb); S.o_jv = room(sizeof(int) * nj);
     S.o_cb = room(sizeof(long long) * (nj + 1)); S.o_end = need;
-    PENS(S.tab_arena, need + 256); PENS(S.h_tab_arena, need + 256);
+    CS_ENSURE(S.tab_arena, need + 256); CS_ENSURE(S.h_tab_arena, need + 256);
     unsigned char *hb = S.h_tab_arena.p, *db = S.tab_arena.p;
     memcpy(hb + o_ls, S.h_ls_order.p, sizeof(int) * nj); memcpy(hb + o_jobs, S.h_jobs_in.p, sizeof(cs::JobDesc) * nj);
     memcpy(hb + o_sp, S.h_slot_prefix.p, sizeof(long long) * (nj + 1)); memcpy(hb + o_vp, S.h_vp_prefix.p, sizeof(int) * (nj + 1));
@@ -1435,7 +1277,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   S.in_flight = false;
   const size_t nj = S.nj, nb = S.nb;
   if (nj == 0) return CS_OK;
-  if (S.merged_io) {     // a small call's results came back in one block (pipe_submit): to the places the rest of this function reads
+  if (S.merged_io) {     // a small call's results came back in one block (pipe_launch): to the places the rest of this function reads
     const unsigned char* hb = S.h_tab_arena.p;
     memcpy(S.h_jobs_out.p, hb + S.o_jobs, sizeof(cs::JobDesc) * nj);
     if (nb) { memcpy(S.h_records.p, hb + S.o_rec, sizeof(cs_cuboid) * nb * KMAX); memcpy(S.h_win_count.p, hb + S.o_wc, sizeof(int) * nb); memcpy(S.h_fallback.p, hb + S.o_fb, sizeof(int) * nb); }
@@ -1477,11 +1319,10 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
         fb_src.push_back(S.h_job_cbase.p[j]); fb_cnt.push_back(S.h_job_valid.p[j]); fb_dst.push_back(tot);
         tot += S.h_job_valid.p[j];
       }
-  int rc;
   if (!fb_src.empty()) {
     size_t nr = fb_src.size();
-    PENS(S.h_fb_src, nr); PENS(S.h_fb_dst, nr); PENS(S.h_fb_cnt, nr);
-    PENS(S.h_fb_dist, tot + 1); PENS(S.h_fb_angle, tot + 1); PENS(S.h_fb_skew, tot + 1); PENS(S.h_fb_flag, tot + 1); PENS(S.h_fb_slot, tot + 1);
+    CS_ENSURE(S.h_fb_src, nr); CS_ENSURE(S.h_fb_dst, nr); CS_ENSURE(S.h_fb_cnt, nr);
+    CS_ENSURE(S.h_fb_dist, tot + 1); CS_ENSURE(S.h_fb_angle, tot + 1); CS_ENSURE(S.h_fb_skew, tot + 1); CS_ENSURE(S.h_fb_flag, tot + 1); CS_ENSURE(S.h_fb_slot, tot + 1);
     std::copy(fb_src.begin(), fb_src.end(), S.h_fb_src.p); std::copy(fb_dst.begin(), fb_dst.end(), S.h_fb_dst.p); std::copy(fb_cnt.begin(), fb_cnt.end(), S.h_fb_cnt.p);
     // the range lists are read from, and the columns written to, the pinned host pools by the gather kernel itself (coalesced rows; no
     // copy engine between the device and a host that is waiting for a few kilobytes)
@@ -1490,64 +1331,29 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   }
   MARK(5, tq);   // tie lists + gather enqueue
   // ---- records of the winners.  The boxes the device ranked are written while the tie boxes' columns travel.
-  auto write_box = [&](size_t q, const cs::RankWinner* wl, int nw) {
-    const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q];
-    const int f = jobs[j0].frame, bi = jobs[j0].box;
-    const FrameIn& F = b->frames[f];
-    const double* bb = &F.boxes[5 * bi];
+  std::vector<std::vector<ExactWinner>> fb_winners(nb);
+  std::vector<size_t> fb_corner0(nb, 0);      // first of a tie box's winners in h_win_corners
+  auto write_box = [&](size_t q) {
+    const int j0 = S.h_box_job0.p[q];
+    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = (int)fb_winners[q].size();
     for (int r = 0; r < nw; r++) {
-      const cs::RankWinner& w = wl[r];
-      int h = 0;
-      while (h + 1 < nh && w.slot >= jobs[j0 + h + 1].slot_off) h++;
-      const cs::JobDesc& jd = jobs[j0 + h];
-      long long local = w.slot - jd.slot_off;
-      long long rest = local >> 1;
-      int t = (int)(rest % jd.T), y = (int)(rest / jd.T);
-      const cs::RpPose& pose = cam_rp[f][0].pose;
-      double r9[9] = {(double)((local & 1) + 1), (double)(w.flag & cs::CAND_VP_MASK), S.h_yaw.p[jd.yaw_off + y], (double)t, w.dist_err, w.angle_err,
-                      (double)jd.down_expand, pose.roll, pose.pitch};
-      cs_cuboid& o = C.out[((size_t)f * MB + bi) * KMAX + r];
-      finish_cuboid(F, pose, r9, w.corners, (*C.cam_raw)[f].euler, false, w.normalized_error, o);
-      o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
+      const ExactWinner& w = fb_winners[q][r];
+      const cs::JobDesc& jd = jobs[j0 + w.h];
+      const SlotRef s = decode_slot(jd, w.slot);
+      write_winner_record(b->frames[f], jd, s, w.flag, w.dist, w.angle, S.h_yaw.p[jd.yaw_off + s.y], cam_rp[f][s.rp].pose, S.h_win_corners.p + 16 * (fb_corner0[q] + r),
+                          (*C.cam_raw)[f].euler, false, w.score, C.out[((size_t)f * MB + bi) * KMAX + r]);
     }
     C.out_counts[(size_t)f * MB + bi] = nw;
   };
-  const double* fb_dist = S.h_fb_dist.p; const double* fb_angle = S.h_fb_angle.p; const double* fb_skew = S.h_fb_skew.p;
-  const int* fb_flag = S.h_fb_flag.p; const long long* fb_slot = S.h_fb_slot.p;
-  std::vector<std::vector<cs::RankWinner>> fb_winners(nb);
+  const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
   auto rank_on_host = [&](size_t q) {
     const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q];
-    struct HP { int h, cand; double score, skew; };
-    std::vector<HP> props;
+    HeightCols cols[3];
     for (int h = 0; h < nh; h++) {
-      int j = j0 + h, V = S.h_job_valid.p[j];
-      long long p0 = fb_dst[fb_range_of_job[j]];
-      std::vector<int> keep;
-      std::vector<double> score;
-      fuse_scores(fb_dist + p0, fb_angle + p0, V, P.weight_vp_angle, keep, score);
-      for (size_t z = 0; z < keep.size(); z++) {
-        if (fb_flag[p0 + keep[z]] & cs::CAND_NEG_SCALE) continue;
-        props.push_back(HP{h, keep[z], score[z], fb_skew[p0 + keep[z]]});
-      }
+      const long long p0 = fb_dst[fb_range_of_job[j0 + h]];
+      cols[h] = HeightCols{S.h_fb_dist.p + p0, S.h_fb_angle.p + p0, S.h_fb_skew.p + p0, S.h_fb_flag.p + p0, S.h_fb_slot.p + p0, S.h_job_valid.p[j0 + h]};
     }
-    int n = (int)props.size(), kk = std::min(KMAX, n);
-    std::vector<double> comb(n);
-    for (int i = 0; i < n; i++) {
-      double skew_error = P.weight_skew_error * std::max(props[i].skew - P.nominal_skew_ratio, 0.0);
-      if (props[i].skew > P.max_cut_skew) skew_error = 100;
-      comb[i] = props[i].score + P.weight_skew_error * skew_error;
-    }
-    std::vector<int> idx(n);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::partial_sort(idx.begin(), idx.begin() + kk, idx.end(), [&comb](int a, int c) { return comb[a] < comb[c]; });
-    for (int r = 0; r < kk; r++) {
-      const HP& hp = props[idx[r]];
-      long long p0 = fb_dst[fb_range_of_job[j0 + hp.h]];
-      cs::RankWinner w{};
-      w.slot = fb_slot[p0 + hp.cand]; w.normalized_error = hp.score; w.dist_err = fb_dist[p0 + hp.cand]; w.angle_err = fb_angle[p0 + hp.cand];
-      w.flag = fb_flag[p0 + hp.cand] & cs::CAND_VP_MASK;
-      fb_winners[q].push_back(w);
-    }
+    (void)exact_rank_box(cols, nh, RW, KMAX, fb_winners[q]);
   };
   std::vector<int> fbq;
   for (size_t q = 0; q < nb; q++) if (S.h_fallback.p[q]) fbq.push_back((int)q);
@@ -1557,12 +1363,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     if (S.h_fallback.p[q]) return;
     const int j0 = S.h_box_job0.p[q];
     const int f = jobs[j0].frame, bi = jobs[j0].box, nw = S.h_win_count.p[q];
-    const double* bb = &b->frames[f].boxes[5 * bi];
-    for (int r = 0; r < nw; r++) {
-      cs_cuboid& o = C.out[((size_t)f * MB + bi) * KMAX + r];
-      o = S.h_records.p[q * KMAX + r];
-      o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
-    }
+    for (int r = 0; r < nw; r++) copy_device_record(b->frames[f], bi, S.h_records.p[q * KMAX + r], C.out[((size_t)f * MB + bi) * KMAX + r]);
     C.out_counts[(size_t)f * MB + bi] = nw;
   };
   if (fbq.size() <= 64) {
@@ -1587,26 +1388,22 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   }
   MARK(8, tq);   // exact ranking of the tie boxes
   {
-    std::vector<long long> ws;
-    for (int q : fbq) for (auto& w : fb_winners[q]) ws.push_back(w.slot);
-    if (!ws.empty()) {
-      PENS(S.h_win_slots, ws.size()); PENS(S.h_win_corners, 16 * ws.size());
-      std::copy(ws.begin(), ws.end(), S.h_win_slots.p);
-      cs::launch_gather_corners(S.view, C.sp, S.h_win_slots.p, (int)ws.size(), S.h_win_corners.p, st2);     // (pinned host memory on both sides)
+    size_t nw = 0;
+    for (int q : fbq) { fb_corner0[q] = nw; nw += fb_winners[q].size(); }
+    if (nw) {
+      CS_ENSURE(S.h_win_slots, nw); CS_ENSURE(S.h_win_corners, 16 * nw);
+      for (int q : fbq) for (size_t r = 0; r < fb_winners[q].size(); r++) S.h_win_slots.p[fb_corner0[q] + r] = fb_winners[q][r].slot;
+      cs::launch_gather_corners(S.view, C.sp, S.h_win_slots.p, (int)nw, S.h_win_corners.p, st2);     // (pinned host memory on both sides)
       CS_HIP_TRY(hipStreamSynchronize(st2));
-      const double* hc = S.h_win_corners.p;
-      size_t z = 0;
-      for (int q : fbq) for (auto& w : fb_winners[q]) { std::memcpy(w.corners, &hc[16 * z], 128); z++; }
     }
   }
   MARK(9, tq);   // corners of the tie winners
-  if (fbq.size() <= 24) { for (size_t z = 0; z < fbq.size(); z++) { const size_t q = (size_t)fbq[z]; write_box(q, fb_winners[q].data(), (int)fb_winners[q].size()); } }
-  else d->pool->run((int)fbq.size(), [&](int z) { const size_t q = (size_t)fbq[z]; write_box(q, fb_winners[q].data(), (int)fb_winners[q].size()); });
+  if (fbq.size() <= 24) { for (int q : fbq) write_box((size_t)q); }
+  else d->pool->run((int)fbq.size(), [&](int z) { write_box((size_t)fbq[z]); });
   MARK(10, tq);  // records of the tie boxes
   tm.finalize_ms += now_ms() - t0;
   return CS_OK;
 }
-#undef PENS
 
 // ================================================================== lean roll/pitch path =========
 // whether_sample_cam_roll_pitch = 1 (the reference class's default; main_obj.cpp:623 uses it from the second frame on).  The boxes of a
@@ -1625,10 +1422,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   const int KMAX = P.max_cuboid_num, NF = b->n_frames, MB = b->max_boxes;
   double t0 = now_ms();
   if (!S.done) { CS_HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) CS_HIP_TRY(hipEventCreate(&e)); }
-  S.rp_mode = true;
   S.f0 = 0; S.f1 = NF;
-  int rc;
-#define PENS(buf, n) do { rc = (buf).ensure(n); if (rc) return rc; } while (0)
   // ---- yaw lists: NT = 1 + max RP per frame, YCAP samples each
   int max_rp = 1;
   for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)cam_rp[f].size());
@@ -1636,7 +1430,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   const int YCAP = (int)(2.0 * P.yaw_range_deg / std::max(1e-9, P.yaw_step_deg)) + 3;
   const size_t n_yaw = (size_t)NF * NT * YCAP;
   if (n_yaw > 0x7fffffffULL) { cs_set_error("too many yaw samples"); return CS_ERR_CAPACITY; }
-  PENS(S.h_yaw, n_yaw + 1); PENS(S.h_yaw_c, n_yaw + 1); PENS(S.h_yaw_s, n_yaw + 1); PENS(S.h_rp_tab_count, (size_t)NF * NT + 1); PENS(S.h_rp_raw_euler, 3 * (size_t)NF + 1);
+  CS_ENSURE(S.h_yaw, n_yaw + 1); CS_ENSURE(S.h_yaw_c, n_yaw + 1); CS_ENSURE(S.h_yaw_s, n_yaw + 1); CS_ENSURE(S.h_rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.h_rp_raw_euler, 3 * (size_t)NF + 1);
   std::atomic<int> overflow{0};
   std::vector<int> ycap_f(NF, 0);     // longest list of the frame: its boxes' slots are laid out for it
   d->pool->run(NF * NT, [&](int z) {
@@ -1664,8 +1458,8 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   size_t nj_tot = 0, nb_tot = 0;
   for (int f = 0; f < NF; f++) for (int bi = 0; bi < b->frames[f].n_boxes; bi++) nj_tot += b->frames[f].n_heights[bi];
   const size_t n_top = (size_t)b->top_base[b->box_base[NF]];
-  PENS(S.h_jobs_in, nj_tot + 1); PENS(S.h_slot_prefix, nj_tot + MB + 1); PENS(S.h_vp_prefix, nj_tot + MB + 1); PENS(S.h_top_x, n_top + 1);
-  PENS(S.h_box_job0, nj_tot + 1); PENS(S.h_box_njobs, nj_tot + 1); PENS(S.h_ls_order, nj_tot + 1); PENS(S.h_rp_maps, 3 * (size_t)MB * NF + 1);
+  CS_ENSURE(S.h_jobs_in, nj_tot + 1); CS_ENSURE(S.h_slot_prefix, nj_tot + MB + 1); CS_ENSURE(S.h_vp_prefix, nj_tot + MB + 1); CS_ENSURE(S.h_top_x, n_top + 1);
+  CS_ENSURE(S.h_box_job0, nj_tot + 1); CS_ENSURE(S.h_box_njobs, nj_tot + 1); CS_ENSURE(S.h_ls_order, nj_tot + 1); CS_ENSURE(S.h_rp_maps, 3 * (size_t)MB * NF + 1);
   S.rp_rounds.assign(MB, PipeSlot::RpRound{});
   S.rp_box_frame.clear(); S.rp_box_index.clear();
   size_t ji = 0;
@@ -1683,7 +1477,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       if (r >= F.n_boxes) continue;
       const int bi = r;
       const double* bb = &F.boxes[5 * bi];
-      const int left = bb[0], top = bb[1], w = bb[2], h = bb[3], right = left + bb[2];
+      const int left = bb[0], w = bb[2], right = left + bb[2];
       const int res = (int)std::round(std::min(20, w / 10));
       if (res < 1) continue;              // :215: the box is skipped and leaves the carried yaw alone
       const int tb = b->top_base[b->box_base[f] + bi] - tp0, tcap = b->top_base[b->box_base[f] + bi + 1] - tp0 - tb;
@@ -1696,17 +1490,11 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       S.rp_box_frame.push_back(f); S.rp_box_index.push_back(bi);
       nb_tot++;
       for (int k = 0; k < F.n_heights[bi]; k++) {
-        const cs_roi& roi = F.rois[3 * bi + k];
         cs::JobDesc jd;
-        std::memset(&jd, 0, sizeof(jd));
-        const int he = h + roi.down_expand;
-        jd.g.left = left; jd.g.top = top; jd.g.right = right; jd.g.down = top + he;
-        jd.g.el = roi.left; jd.g.et = roi.top; jd.g.er = roi.left + roi.width; jd.g.eb = roi.top + roi.height;
-        jd.map_w = roi.width; jd.T = nT; jd.RP = nrp; jd.down_expand = roi.down_expand;
+        fill_job_geometry(jd, F, bi, k, (*C.rp_off)[f]);
+        jd.frame = f; jd.T = nT; jd.RP = nrp;
         jd.Y = S.h_rp_tab_count.p[(size_t)f * NT];            // list 0 (the raw pose) until rp_carry_kernel says otherwise
         jd.yaw_off = (int)(((size_t)f * NT) * YCAP);
-        jd.frame = f; jd.box = bi; jd.hid = k; jd.map_off = F.map_offs[3 * bi + k]; jd.rp_off = (*C.rp_off)[f];
-        jd.diag = std::sqrt(double(w * w + he * he));
         jd.top_off = tb;
         jd.line_off = (int)n_lines; n_lines += F.n_lines;
         jd.slot_off = so; jd.vp_off = (int)vo;
@@ -1731,26 +1519,26 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   C.tm->n_jobs += (long long)nj;
   if (nj == 0) { S.in_flight = true; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
   // ---- device buffers; the per-round arrays are sized for the largest round and reused from round to round (one stream: in order)
-  PENS(S.ls_order, nj); PENS(S.jobs, nj); PENS(S.slot_prefix, nj + MB + 1); PENS(S.vp_prefix, nj + MB + 1); PENS(S.job_valid, nj); PENS(S.job_cbase, nj + MB + 1);
+  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.jobs, nj); CS_ENSURE(S.slot_prefix, nj + MB + 1); CS_ENSURE(S.vp_prefix, nj + MB + 1); CS_ENSURE(S.job_valid, nj); CS_ENSURE(S.job_cbase, nj + MB + 1);
   const int max_trips = (int)std::min<long long>((max_job_slots + 4095) / 4096, 1 << 20);      // compaction trips of the largest job (4096 slots each)
-  PENS(S.rp_trip_cnt, (size_t)nj_round_max * (size_t)std::max(1, max_trips) + 1);
-  PENS(S.mid_x, (size_t)n_lines + 1); PENS(S.mid_y, (size_t)n_lines + 1); PENS(S.ang, (size_t)n_lines + 1); PENS(S.yaw, n_yaw + 1); PENS(S.yaw_c, n_yaw + 1); PENS(S.yaw_s, n_yaw + 1);
-  PENS(S.top_x, n_top + 1); PENS(S.vp, 6 * (size_t)vp_cap_max + 6); PENS(S.bound, 6 * (size_t)vp_cap_max + 6); PENS(S.bound3, nj_round_max * (size_t)cs::vp3_table_doubles_per_job() + 1);
-  PENS(S.flag, slot_cap_max + 1); PENS(S.c_slot, slot_cap_max + 1); PENS(S.c_flag, slot_cap_max + 1); PENS(S.c_dist, slot_cap_max + 1); PENS(S.c_angle, slot_cap_max + 1); PENS(S.c_skew, slot_cap_max + 1);
-  PENS(S.box_job0, nb + 1); PENS(S.box_njobs, nb + 1); PENS(S.win_count, nb + 1); PENS(S.fallback, nb + 1); PENS(S.rp_last_slot, nb + 1);
-  PENS(S.winners, nb * KMAX + 1); PENS(S.records, nb * KMAX + 1); PENS(S.h_records, nb * KMAX + 1); PENS(S.h_win_count, nb + 1); PENS(S.h_fallback, nb + 1);
-  PENS(S.h_job_cbase, nj + MB + 1);
+  CS_ENSURE(S.rp_trip_cnt, (size_t)nj_round_max * (size_t)std::max(1, max_trips) + 1);
+  CS_ENSURE(S.mid_x, (size_t)n_lines + 1); CS_ENSURE(S.mid_y, (size_t)n_lines + 1); CS_ENSURE(S.ang, (size_t)n_lines + 1); CS_ENSURE(S.yaw, n_yaw + 1); CS_ENSURE(S.yaw_c, n_yaw + 1); CS_ENSURE(S.yaw_s, n_yaw + 1);
+  CS_ENSURE(S.top_x, n_top + 1); CS_ENSURE(S.vp, 6 * (size_t)vp_cap_max + 6); CS_ENSURE(S.bound, 6 * (size_t)vp_cap_max + 6); CS_ENSURE(S.bound3, nj_round_max * (size_t)cs::vp3_table_doubles_per_job() + 1);
+  CS_ENSURE(S.flag, slot_cap_max + 1); CS_ENSURE(S.c_slot, slot_cap_max + 1); CS_ENSURE(S.c_flag, slot_cap_max + 1); CS_ENSURE(S.c_dist, slot_cap_max + 1); CS_ENSURE(S.c_angle, slot_cap_max + 1); CS_ENSURE(S.c_skew, slot_cap_max + 1);
+  CS_ENSURE(S.box_job0, nb + 1); CS_ENSURE(S.box_njobs, nb + 1); CS_ENSURE(S.win_count, nb + 1); CS_ENSURE(S.fallback, nb + 1); CS_ENSURE(S.rp_last_slot, nb + 1);
+  CS_ENSURE(S.winners, nb * KMAX + 1); CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1); CS_ENSURE(S.h_win_count, nb + 1); CS_ENSURE(S.h_fallback, nb + 1);
+  CS_ENSURE(S.h_job_cbase, nj + MB + 1);
   S.rp_NT = NT; S.rp_YCAP = YCAP;
   S.rp_pool_cap = std::max<long long>(1 << 18, slots_all / 64);        // columns of the flagged boxes (about one box in a hundred)
-  PENS(S.fb_dist, (size_t)S.rp_pool_cap + 1); PENS(S.fb_angle, (size_t)S.rp_pool_cap + 1); PENS(S.fb_skew, (size_t)S.rp_pool_cap + 1); PENS(S.fb_flag, (size_t)S.rp_pool_cap + 1); PENS(S.fb_slot, (size_t)S.rp_pool_cap + 1);
-  PENS(S.ls_crowded, 2 * (nj + 1) + 2);
-  PENS(S.rp_box_base, nb + 1); PENS(S.rp_pool_used, 1); PENS(S.h_rp_box_base, nb + 1); PENS(S.h_rp_pool_used, 1); PENS(S.h_rp_last_slot, nb + 1); PENS(S.h_job_valid, nj + 1); PENS(S.h_jobs_out, nj + 1);
-  PENS(S.rp_cur_idx, (size_t)NF + 1); PENS(S.rp_tab_count, (size_t)NF * NT + 1); PENS(S.rp_maps, 3 * (size_t)MB * NF + 1); PENS(S.rp_raw_euler, 3 * (size_t)NF + 1);
+  CS_ENSURE(S.fb_dist, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_angle, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_skew, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_flag, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_slot, (size_t)S.rp_pool_cap + 1);
+  CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2);
+  CS_ENSURE(S.rp_box_base, nb + 1); CS_ENSURE(S.rp_pool_used, 1); CS_ENSURE(S.h_rp_box_base, nb + 1); CS_ENSURE(S.h_rp_pool_used, 1); CS_ENSURE(S.h_rp_last_slot, nb + 1); CS_ENSURE(S.h_job_valid, nj + 1); CS_ENSURE(S.h_jobs_out, nj + 1);
+  CS_ENSURE(S.rp_cur_idx, (size_t)NF + 1); CS_ENSURE(S.rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.rp_maps, 3 * (size_t)MB * NF + 1); CS_ENSURE(S.rp_raw_euler, 3 * (size_t)NF + 1);
   while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; CS_HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
   std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);      // all rounds of this batch back to back in the shared streams (see pipe_launch)
   if (!d->streams->own_streams) enqueue.lock();
-  hipStream_t stB_unused = nullptr, stC = nullptr;
-  sweep_side_streams(d, &stB_unused, &stC);
+  hipStream_t stB = nullptr, stC = nullptr;      // (corner construction stays on the chain here: stB is not used)
+  sweep_side_streams(d, &stB, &stC);
   CS_HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
   {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
     cs::CopySegs cp{};
@@ -1866,10 +1654,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   if (n_fb) {
     hipStream_t st2 = d->stream_hi;
     const size_t used = (size_t)std::min<unsigned long long>(*S.h_rp_pool_used.p, (unsigned long long)S.rp_pool_cap);
-    int rc;
-#define PENS(buf, n) do { rc = (buf).ensure(n); if (rc) return rc; } while (0)
-    PENS(S.h_fb_dist, used + 1); PENS(S.h_fb_angle, used + 1); PENS(S.h_fb_skew, used + 1); PENS(S.h_fb_flag, used + 1); PENS(S.h_fb_slot, used + 1);
-#undef PENS
+    CS_ENSURE(S.h_fb_dist, used + 1); CS_ENSURE(S.h_fb_angle, used + 1); CS_ENSURE(S.h_fb_skew, used + 1); CS_ENSURE(S.h_fb_flag, used + 1); CS_ENSURE(S.h_fb_slot, used + 1);
     if (used) {
       cs::CopySegs cp{};
       cs::add_copy(cp, S.h_fb_dist, S.fb_dist, used); cs::add_copy(cp, S.h_fb_angle, S.fb_angle, used); cs::add_copy(cp, S.h_fb_skew, S.fb_skew, used);
@@ -1881,7 +1666,8 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
     // boxes of a frame in round order
     std::vector<std::vector<size_t>> boxes_of(NF);
     for (size_t q = 0; q < S.nb; q++) boxes_of[S.rp_box_frame[q]].push_back(q);
-    auto carry_idx = [&](const cs::JobDesc& jl, long long last) { return last < 0 ? jl.RP : 1 + (int)((((last - jl.slot_off) >> 1) / jl.T) / jl.Y); };
+    auto carry_idx = [](const cs::JobDesc& jl, long long last) { return last < 0 ? jl.RP : 1 + decode_slot(jl, last).rp; };
+    const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
     std::vector<int> fb_frames;
     for (int f = 0; f < NF; f++) { bool any = false; for (size_t q : boxes_of[f]) any = any || S.h_fallback.p[q]; if (any) fb_frames.push_back(f); }
     d->pool->run((int)fb_frames.size(), [&](int z) {
@@ -1898,42 +1684,21 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
         const cs::JobDesc* jobs = S.h_jobs_out.p + S.rp_rounds[r].j0;
         const int* jvalid = S.h_job_valid.p + S.rp_rounds[r].j0;
         const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q], bi = S.rp_box_index[q];
-        struct HP { int h, cand; double score, skew; };
-        std::vector<HP> props;
-        std::vector<long long> p0(nh);
-        long long run = base, exact_last = -1;
+        HeightCols cols[3];
+        long long run = base;
         for (int h = 0; h < nh; h++) {
-          const int V = jvalid[j0 + h];
-          p0[h] = run; run += V;
-          std::vector<int> keep;
-          std::vector<double> score;
-          fuse_scores(S.h_fb_dist.p + p0[h], S.h_fb_angle.p + p0[h], V, P.weight_vp_angle, keep, score);
-          if (h == nh - 1) exact_last = keep.empty() ? -1 : S.h_fb_slot.p[p0[h] + keep.back()];
-          for (size_t k = 0; k < keep.size(); k++) {
-            if (S.h_fb_flag.p[p0[h] + keep[k]] & cs::CAND_NEG_SCALE) continue;
-            props.push_back(HP{h, keep[k], score[k], S.h_fb_skew.p[p0[h] + keep[k]]});
-          }
+          cols[h] = HeightCols{S.h_fb_dist.p + run, S.h_fb_angle.p + run, S.h_fb_skew.p + run, S.h_fb_flag.p + run, S.h_fb_slot.p + run, jvalid[j0 + h]};
+          run += jvalid[j0 + h];
         }
-        const int n = (int)props.size(), kk = std::min(KMAX, n);
-        std::vector<double> comb(n);
-        for (int i = 0; i < n; i++) {
-          double skew_error = P.weight_skew_error * std::max(props[i].skew - P.nominal_skew_ratio, 0.0);
-          if (props[i].skew > P.max_cut_skew) skew_error = 100;
-          comb[i] = props[i].score + P.weight_skew_error * skew_error;
-        }
-        std::vector<int> idx(n);
-        std::iota(idx.begin(), idx.end(), 0);
-        std::partial_sort(idx.begin(), idx.begin() + kk, idx.end(), [&comb](int a, int c) { return comb[a] < comb[c]; });
-        const double* bb = &F.boxes[5 * bi];
+        std::vector<ExactWinner> wl;
+        const long long exact_last = exact_rank_box(cols, nh, RW, KMAX, wl);
+        const int kk = (int)wl.size();
         for (int w = 0; w < kk; w++) {
-          const HP& hp = props[idx[w]];
-          const cs::JobDesc& jd = jobs[j0 + hp.h];
-          const long long slot = S.h_fb_slot.p[p0[hp.h] + hp.cand];
-          const long long local = slot - jd.slot_off, rest = local >> 1;
-          const int t = (int)(rest % jd.T), ry = (int)(rest / jd.T), rp = ry / jd.Y, y = ry - rp * jd.Y;
+          const cs::JobDesc& jd = jobs[j0 + wl[w].h];
+          const SlotRef s = decode_slot(jd, wl[w].slot);
           // the winner's corners: the vanishing points (vp_points_kernel's arithmetic) and build_corners, on the host
-          const double* A = cam_rp[f][rp].pose.KinvR;
-          const double cy = S.h_yaw_c.p[jd.yaw_off + y], sy = S.h_yaw_s.p[jd.yaw_off + y];
+          const double* A = cam_rp[f][s.rp].pose.KinvR;
+          const double cy = S.h_yaw_c.p[jd.yaw_off + s.y], sy = S.h_yaw_s.p[jd.yaw_off + s.y];
           const double dd[3][3] = {{cy, sy, 0.0}, {-sy, cy, 0.0}, {0.0, 0.0, 1.0}};
           cs::V2 vp[3];
           for (int k = 0; k < 3; k++) {
@@ -1944,14 +1709,11 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
           }
           cs::V2 c8[8];
           for (auto& c : c8) c = cs::v2(0.0, 0.0);
-          (void)cs::build_corners(jd.g, vp[0], vp[1], vp[2], (double)S.h_top_x.p[jd.top_off + t], (int)(local & 1) + 1, C.sp.short_sq_bound, c8);
+          (void)cs::build_corners(jd.g, vp[0], vp[1], vp[2], (double)S.h_top_x.p[jd.top_off + s.t], s.cfg, C.sp.short_sq_bound, c8);
           double c16[16];
           for (int k = 0; k < 8; k++) { c16[k] = c8[k].x; c16[8 + k] = c8[k].y; }
-          double r9[9] = {(double)((local & 1) + 1), (double)(S.h_fb_flag.p[p0[hp.h] + hp.cand] & cs::CAND_VP_MASK), S.h_yaw.p[jd.yaw_off + y], (double)t,
-                          S.h_fb_dist.p[p0[hp.h] + hp.cand], S.h_fb_angle.p[p0[hp.h] + hp.cand], (double)jd.down_expand, cam_rp[f][rp].pose.roll, cam_rp[f][rp].pose.pitch};
-          cs_cuboid& o = C.out[((size_t)f * MB + bi) * KMAX + w];
-          finish_cuboid(F, cam_rp[f][rp].pose, r9, c16, (*C.cam_raw)[f].euler, true, hp.score, o);
-          o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
+          write_winner_record(F, jd, s, wl[w].flag, wl[w].dist, wl[w].angle, S.h_yaw.p[jd.yaw_off + s.y], cam_rp[f][s.rp].pose, c16, (*C.cam_raw)[f].euler, true, wl[w].score,
+                              C.out[((size_t)f * MB + bi) * KMAX + w]);
         }
         C.out_counts[(size_t)f * MB + bi] = kk;
         host_done[q] = 1;
@@ -1969,12 +1731,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
       const int f = S.rp_box_frame[q], bi = S.rp_box_index[q];
       if (redo[f] || host_done[q]) continue;
       const int nw = S.h_win_count.p[q];
-      const double* bb = &b->frames[f].boxes[5 * bi];
-      for (int r = 0; r < nw; r++) {
-        cs_cuboid& o = C.out[((size_t)f * MB + bi) * KMAX + r];
-        o = S.h_records.p[q * KMAX + r];
-        o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
-      }
+      for (int r = 0; r < nw; r++) copy_device_record(b->frames[f], bi, S.h_records.p[q * KMAX + r], C.out[((size_t)f * MB + bi) * KMAX + r]);
       C.out_counts[(size_t)f * MB + bi] = nw;
     }
   });
@@ -1990,7 +1747,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
     sub.max_boxes = 0;
     for (size_t z = 0; z < ids.size(); z++) { sub.frames[z] = b->frames[ids[z]]; sub.max_boxes = std::max(sub.max_boxes, sub.frames[z].n_boxes); }
     sub.d_maps.p = b->d_maps.p; sub.d_maps.cap = b->d_maps.cap;           // borrowed
-    struct Unborrow { cs_batch* s; ~Unborrow() { s->d_maps.p = nullptr; s->d_maps.cap = 0; release_batch_buffers(s); } } ub{&sub};
+    struct Unborrow { cs_batch* s; ~Unborrow() { s->d_maps.p = nullptr; s->d_maps.cap = 0; } } ub{&sub};      // (destroyed before `sub`)
     int rc = batch_layout(d, &sub);
     if (rc) return rc;
     const int MBs = sub.max_boxes;
@@ -2011,7 +1768,6 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   tm.finalize_ms += now_ms() - t0;
   return CS_OK;
 }
-#undef PENS
 
 }  // namespace
 
@@ -2043,6 +1799,14 @@ extern "C" int cs_batch_collect(cs_detector* d, cs_batch* b) {
   CS_GUARD_END("cs_batch_collect")
 }
 static void batch_drop_run_state(cs_batch* b) { delete b->run_state; b->run_state = nullptr; }
+// CS_DETECT_PROF: the host phase clock of the lean path, every eighth run
+static void prof_report(double total_ms) {
+  if (!g_prof || (++g_runs % 8) != 0) return;
+  const char* nm[11] = {"jobs+samples", "prefix+pack", nullptr, "alloc+enqueue", "gpu wait", "tie lists", "records", "tie wait", "tie rank", "tie corners", "tie records"};
+  fprintf(stderr, "[detect] host ms/run:");
+  for (int k = 0; k < 11; k++) { if (nm[k]) fprintf(stderr, " %s %.3f", nm[k], g_mark[k] / 8); g_mark[k] = 0; }
+  fprintf(stderr, " | pre %.3f total %.3f\n", g_mark[11] / 8, total_ms); g_mark[11] = 0;
+}
 static int batch_collect_impl(cs_detector* d, cs_batch* b) {
   if (!b->run_state) return CS_OK;                        // nothing outstanding (or the sweep ran to completion inside submit)
   std::unique_ptr<BatchRunState> rs(b->run_state);
@@ -2054,14 +1818,555 @@ static int batch_collect_impl(cs_detector* d, cs_batch* b) {
   rs->tm.total_ms = now_ms() - rs->t_begin;
   b->timing = rs->tm;
   b->ran = true;
-  if (g_prof && (++g_runs % 8) == 0) {
-    const char* nm[11] = {"jobs+samples", "prefix+pack", "box table", "alloc+enqueue", "gpu wait", "tie lists", "records", "tie wait", "tie rank", "tie corners", "tie records"};
-    fprintf(stderr, "[detect] host ms/run:");
-    for (int k = 0; k < 11; k++) { fprintf(stderr, " %s %.3f", nm[k], g_mark[k] / 8); g_mark[k] = 0; }
-    fprintf(stderr, " | pre %.3f total %.3f\n", g_mark[11] / 8, rs->tm.total_ms); g_mark[11] = 0;
-  }
+  prof_report(rs->tm.total_ms);
   return CS_OK;
 }
+
+// Per-frame camera caches: raw pose and the roll/pitch sample poses (:78-79, :344-355, :368-377).  The pose pool is the same for every
+// round: uploaded once.
+static int build_camera_caches(cs_detector* d, cs_batch* b, BatchRunState* rs, bool sample_rp) {
+  const int NF = b->n_frames;
+  const double t0 = now_ms();
+  std::vector<CamCache>& cam_raw = rs->cam_raw; cam_raw.resize(NF);
+  std::vector<std::vector<CamCache>>& cam_rp = rs->cam_rp; cam_rp.resize(NF);
+  d->pool->run(NF, [&](int f) {
+    const FrameIn& F = b->frames[f];
+    make_cam(F.K, F.R, F.t, cam_raw[f]);
+    if (sample_rp) {
+      std::vector<double> rolls, pitches;
+      linespace<double>(cam_raw[f].euler[0] - 6.0 / 180.0 * CS_PI, cam_raw[f].euler[0] + 6.0 / 180.0 * CS_PI, 3.0 / 180.0 * CS_PI, rolls);
+      linespace<double>(cam_raw[f].euler[1] - 6.0 / 180.0 * CS_PI, cam_raw[f].euler[1] + 6.0 / 180.0 * CS_PI, 3.0 / 180.0 * CS_PI, pitches);
+      for (double r : rolls)
+        for (double p : pitches) {
+          double Rn[9];
+          euler_to_rot(r, p, cam_raw[f].euler[2], Rn);
+          CamCache c;
+          make_cam(F.K, Rn, F.t, c);
+          c.pose.roll = r; c.pose.pitch = p;  // the row stores the *sample* angles (:686)
+          cam_rp[f].push_back(c);
+        }
+    } else {
+      cam_rp[f].push_back(cam_raw[f]);
+    }
+  });
+  std::vector<int>& rp_off = rs->rp_off; rp_off.assign(NF + 1, 0);
+  for (int f = 0; f < NF; f++) rp_off[f + 1] = rp_off[f] + (int)cam_rp[f].size();
+  // (pinned staging owned by the batch: the copy is queued behind whatever the detector's stream still runs -- another batch's sweep --
+  // and nobody waits for it here)
+  const size_t np_ = (size_t)std::max(1, rp_off[NF]);
+  CS_ENSURE(b->h_rp, np_);
+  for (int f = 0; f < NF; f++)
+    for (size_t k = 0; k < cam_rp[f].size(); k++) b->h_rp.p[rp_off[f] + k] = cam_rp[f][k].pose;
+  CS_ENSURE(b->d_rp, np_);
+  CS_HIP_TRY(hipMemcpyAsync(b->d_rp.p, b->h_rp.p, sizeof(cs::RpPose) * np_, hipMemcpyHostToDevice, d->stream));
+  rs->tm.setup_host_ms += now_ms() - t0;
+  return CS_OK;
+}
+
+// what both lean paths (pipe_launch / pipe_finish, rp_launch / rp_finish) need of a batch: nothing retained for the debug getters, nothing
+// forced to the host, line setup and ranking within the kernels' capacities
+static bool lean_path_allowed(const cs_batch* b, int kmax) {
+  return !b->debug && !b->force_host_rank && !b->force_host_setup && !b->force_no_pipeline && b->device_setup && kmax <= cs::RANK_KMAX && b->max_boxes > 0;
+}
+
+// ================================================================== round-by-round path ==========
+// The general path (debug getters, host ranking / host line setup on request, the lean roll/pitch path's redo of frames with tie
+// boxes): per round setup -> upload -> sweep -> ranking on the device or on the host -> records, the host deciding after every round.
+namespace {
+
+struct RoundTables {      // the job tables of one round and the device view of its sweep
+  std::vector<cs::JobDesc> jobs;
+  std::vector<long long> slot_prefix;
+  std::vector<int> vp_prefix, top_x, box_job0, box_njobs;      // (the round's boxes: first job, height samples -- consecutive jobs)
+  std::vector<double> mid_x, mid_y, ang, yaw, yaw_c, yaw_s;
+  size_t nj = 0, n_lines = 0;      // n_lines: entries of the pooled line tables (mid_x / mid_y / ang hold them only with the host line setup)
+  long long slot_total = 0;
+  int vp_total = 0;
+  cs::DetectDeviceView v{};
+};
+
+struct RoundRun {         // one cs_batch_run through the round path
+  PipeCtx& C;
+  bool sample_rp, dev_setup;
+  std::vector<double> cur_yaw;      // cam_pose.camera_yaw as the next box of a frame will see it (:180)
+};
+
+// cam_pose.camera_yaw as the next box of this frame reads it (:180): the reference's last set_cam_pose() of this box is
+// the one for the last kept proposal of the last height sample (:727-737), or, when nothing was kept, the sweep's last
+// (roll, pitch) sample (:368-377).  jl: the box's last job.  (One box per frame and round: no two workers write the same entry.)
+void carry_yaw(RoundRun& X, const cs::JobDesc& jl, long long last_slot) {
+  const std::vector<CamCache>& rp = (*X.C.cam_rp_all)[jl.frame];
+  X.cur_yaw[jl.frame] = last_slot < 0 ? rp.back().cam_yaw : rp[(size_t)decode_slot(jl, last_slot).rp].cam_yaw;
+}
+
+// the record of winner `rank` of job jd's box
+void round_write_winner(const RoundRun& X, const RoundTables& T, const cs::JobDesc& jd, long long slot, int flag, double dist_err, double angle_err, double normalized_error,
+                        const double* corners16, int rank) {
+  const PipeCtx& C = X.C;
+  const int f = jd.frame;
+  const SlotRef s = decode_slot(jd, slot);
+  write_winner_record(C.b->frames[f], jd, s, flag, dist_err, angle_err, T.yaw[jd.yaw_off + s.y], (*C.cam_rp_all)[f][s.rp].pose, corners16, (*C.cam_raw)[f].euler, X.sample_rp,
+                      normalized_error, C.out[((size_t)f * C.b->max_boxes + jd.box) * C.d->prm.max_cuboid_num + rank]);
+}
+
+// a table to the device: through the pinned block `hb` (asynchronous, back to back with its neighbours), or from where it lies
+template <class T>
+int upload_staged(DevBuf<T>& dst, const std::vector<T>& vec, unsigned char* hb, size_t off, hipStream_t st) {
+  if (vec.empty()) return CS_OK;
+  memcpy(hb + off, vec.data(), sizeof(T) * vec.size());
+  CS_HIP_TRY(hipMemcpyAsync(dst.p, hb + off, sizeof(T) * vec.size(), hipMemcpyHostToDevice, st));
+  return CS_OK;
+}
+template <class T>
+int upload_pageable(DevBuf<T>& dst, const std::vector<T>& vec, hipStream_t st) {
+  CS_HIP_TRY(hipMemcpyAsync(dst.p, vec.data(), sizeof(T) * vec.size(), hipMemcpyHostToDevice, st));
+  return CS_OK;
+}
+
+// ---- setup (host): the round's jobs per frame, then packed into pooled tables
+int round_setup(RoundRun& X, int round, RoundTables& T) {
+  cs_detector* d = X.C.d; cs_batch* b = X.C.b;
+  const cs_detect_params& P = d->prm;
+  const int NF = b->n_frames;
+  const bool sample_rp = X.sample_rp, dev_setup = X.dev_setup;
+  const std::vector<std::vector<CamCache>>& cam_rp = *X.C.cam_rp_all;
+  const std::vector<int>& rp_off = *X.C.rp_off;
+  cs_detect_timing& tm = *X.C.tm;
+  const double t0 = now_ms();
+  std::vector<FrameRound> fr(NF);
+  d->pool->run(NF, [&](int f) {
+    const FrameIn& F = b->frames[f];
+    FrameRound& R = fr[f];
+    int b0 = sample_rp ? round : 0, b1 = sample_rp ? std::min(round + 1, F.n_boxes) : F.n_boxes;
+    int shared_yoff = -1, shared_Y = 0;  // without roll/pitch sampling cam_pose never changes: every box of the frame sweeps the same yaw list (:180-184)
+    for (int bi = b0; bi < b1; bi++) {
+      const double* bb = &F.boxes[5 * bi];
+      int left = bb[0], w = bb[2];
+      int right = left + bb[2];
+      int res = (int)std::round(std::min(20, w / 10));
+      if (res < 1) continue;  // :215 break (same for every height sample)
+      // yaw samples (:180-184)
+      int yoff, nY;
+      if (shared_yoff >= 0) { yoff = shared_yoff; nY = shared_Y; }
+      else {
+        double yaw_init = X.cur_yaw[f] - 90.0 / 180.0 * CS_PI;
+        std::vector<double> yaws;
+        linespace<double>(yaw_init - P.yaw_range_deg / 180.0 * CS_PI, yaw_init + P.yaw_range_deg / 180.0 * CS_PI, P.yaw_step_deg / 180.0 * CS_PI, yaws);
+        yoff = (int)R.yaw.size(); nY = (int)yaws.size();
+        for (double y : yaws) { R.yaw.push_back(y); R.yaw_c.push_back(h_cos(y)); R.yaw_s.push_back(h_sin(y)); }
+        if (!sample_rp) { shared_yoff = yoff; shared_Y = nY; }
+      }
+      std::vector<int> tops;
+      linespace<int>(left + 5, right - 5, res, tops);
+      for (int k = 0; k < F.n_heights[bi]; k++) {
+        cs::JobDesc jd;
+        fill_job_geometry(jd, F, bi, k, rp_off[f]);
+        jd.frame = f; jd.Y = nY; jd.T = (int)tops.size(); jd.RP = (int)cam_rp[f].size();
+        JobHost jh;
+        jh.frame = f; jh.box = bi; jh.hid = k; jh.yaw_off_local = yoff; jh.tops = tops;
+        // ROI line filter (:271-283) + merge (:288-296) + angles/midpoints (:309-315): line_setup_kernel, or here
+        if (dev_setup) { jd.m = 0; jh.line_cap = F.n_lines; R.jobs.push_back(jd); R.jh.push_back(std::move(jh)); continue; }
+        std::vector<double> in;
+        for (int e = 0; e < F.n_lines; e++) {
+          const double* l = &F.lines[4 * e];
+          if (cs::inside_box(cs::v2(l[0], l[1]), jd.g.el, jd.g.et, jd.g.er, jd.g.eb) &&
+              cs::inside_box(cs::v2(l[2], l[3]), jd.g.el, jd.g.et, jd.g.er, jd.g.eb))
+            in.insert(in.end(), l, l + 4);
+        }
+        merge_lines(in, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold);
+        jd.m = (int)(in.size() / 4);
+        for (int i = 0; i < jd.m; i++) {
+          jh.angs.push_back(cs::cs_atan2(in[4 * i + 3] - in[4 * i + 1], in[4 * i + 2] - in[4 * i]));
+          jh.mids_x.push_back((in[4 * i] + in[4 * i + 2]) / 2);
+          jh.mids_y.push_back((in[4 * i + 1] + in[4 * i + 3]) / 2);
+        }
+        jh.line_cap = jd.m;
+        R.jobs.push_back(jd);
+        R.jh.push_back(std::move(jh));
+      }
+    }
+  });
+  // pack: per-frame sizes -> offsets (serial prefix over frames) -> parallel copy into the pooled arrays
+  std::vector<size_t> f_job(NF + 1, 0), f_line(NF + 1, 0), f_yaw(NF + 1, 0), f_top(NF + 1, 0);
+  std::vector<long long> f_slot(NF + 1, 0), f_vp(NF + 1, 0);
+  for (int f = 0; f < NF; f++) {
+    size_t nl = 0, nt = 0;
+    long long ns = 0, nv = 0;
+    for (size_t q = 0; q < fr[f].jobs.size(); q++) {
+      const cs::JobDesc& jd = fr[f].jobs[q];
+      nl += fr[f].jh[q].line_cap; nt += fr[f].jh[q].tops.size();
+      nv += (long long)jd.RP * jd.Y; ns += (long long)jd.RP * jd.Y * jd.T * 2;
+    }
+    f_job[f + 1] = f_job[f] + fr[f].jobs.size(); f_line[f + 1] = f_line[f] + nl; f_yaw[f + 1] = f_yaw[f] + fr[f].yaw.size();
+    f_top[f + 1] = f_top[f] + nt; f_slot[f + 1] = f_slot[f] + ns; f_vp[f + 1] = f_vp[f] + nv;
+  }
+  const size_t nj = f_job[NF];
+  T.nj = nj; T.n_lines = f_line[NF];
+  if (nj == 0) { tm.setup_host_ms += now_ms() - t0; return CS_OK; }
+  if (f_vp[NF] > 0x7fffffffLL) { cs_set_error("too many (roll,pitch,yaw) samples in one round"); return CS_ERR_CAPACITY; }
+  T.jobs.resize(nj); T.slot_prefix.resize(nj + 1); T.vp_prefix.resize(nj + 1);
+  const size_t n_lines_host = dev_setup ? 0 : T.n_lines;  // with the device line setup these tables are only ever written by the kernel
+  T.mid_x.resize(n_lines_host); T.mid_y.resize(n_lines_host); T.ang.resize(n_lines_host);
+  T.yaw.resize(f_yaw[NF]); T.yaw_c.resize(f_yaw[NF]); T.yaw_s.resize(f_yaw[NF]); T.top_x.resize(f_top[NF]);
+  d->pool->run(NF, [&](int f) {
+    FrameRound& R = fr[f];
+    size_t ji = f_job[f], lo = f_line[f], yo = f_yaw[f], to = f_top[f];
+    long long so = f_slot[f], vo = f_vp[f];
+    std::copy(R.yaw.begin(), R.yaw.end(), T.yaw.begin() + yo);
+    std::copy(R.yaw_c.begin(), R.yaw_c.end(), T.yaw_c.begin() + yo);
+    std::copy(R.yaw_s.begin(), R.yaw_s.end(), T.yaw_s.begin() + yo);
+    for (size_t q = 0; q < R.jobs.size(); q++, ji++) {
+      cs::JobDesc& jd = R.jobs[q];
+      const JobHost& jh = R.jh[q];
+      jd.line_off = (int)lo; jd.yaw_off = (int)(yo + jh.yaw_off_local); jd.top_off = (int)to;
+      jd.vp_off = (int)vo; jd.slot_off = so;
+      if (!dev_setup) {
+        std::copy(jh.mids_x.begin(), jh.mids_x.end(), T.mid_x.begin() + lo);
+        std::copy(jh.mids_y.begin(), jh.mids_y.end(), T.mid_y.begin() + lo);
+        std::copy(jh.angs.begin(), jh.angs.end(), T.ang.begin() + lo);
+      }
+      std::copy(jh.tops.begin(), jh.tops.end(), T.top_x.begin() + to);
+      lo += jh.line_cap; to += jh.tops.size();
+      T.slot_prefix[ji] = so; T.vp_prefix[ji] = (int)vo;
+      vo += (long long)jd.RP * jd.Y;
+      so += (long long)jd.RP * jd.Y * jd.T * 2;
+      T.jobs[ji] = jd;
+    }
+  });
+  T.slot_prefix[nj] = f_slot[NF]; T.vp_prefix[nj] = (int)f_vp[NF];
+  T.slot_total = T.slot_prefix[nj]; T.vp_total = T.vp_prefix[nj];
+  for (size_t j = 0; j < nj; j++)
+    if (T.jobs[j].hid == 0) { T.box_job0.push_back((int)j); T.box_njobs.push_back(b->frames[T.jobs[j].frame].n_heights[T.jobs[j].box]); }
+  tm.setup_host_ms += now_ms() - t0;
+  tm.n_jobs += (long long)nj; tm.n_slots += T.slot_total;
+  return CS_OK;
+}
+
+// ---- H2D: the round's tables.  They are small (a frame: ~10 of them, a few KB each).  From the std::vectors every hipMemcpyAsync is a
+// staged, effectively synchronous copy (10-25 us apiece, ~150 us per call); copied first into ONE pinned block they go out back to back
+// and the host does not wait (the round's results are awaited before the block is written again).
+int round_upload(RoundRun& X, RoundTables& T) {
+  cs_batch* b = X.C.b;
+  hipStream_t st = X.C.d->stream;
+  const double t0 = now_ms();
+  const size_t nj = T.nj, n_lines = T.n_lines, n_yaw = T.yaw.size(), n_top = T.top_x.size();
+  CS_ENSURE(b->d_jobs, nj); CS_ENSURE(b->d_slot_prefix, nj + 1); CS_ENSURE(b->d_vp_prefix, nj + 1); CS_ENSURE(b->d_job_valid, nj); CS_ENSURE(b->d_job_cbase, nj + 1);
+  CS_ENSURE(b->d_mid_x, n_lines + 1); CS_ENSURE(b->d_mid_y, n_lines + 1); CS_ENSURE(b->d_ang, n_lines + 1);
+  CS_ENSURE(b->d_yaw, n_yaw + 1); CS_ENSURE(b->d_yaw_c, n_yaw + 1); CS_ENSURE(b->d_yaw_s, n_yaw + 1); CS_ENSURE(b->d_top_x, n_top + 1);
+  CS_ENSURE(b->d_vp, 6 * (size_t)T.vp_total + 6); CS_ENSURE(b->d_bound, 6 * (size_t)T.vp_total + 6);
+  CS_ENSURE(b->d_flag, T.slot_total + 1);
+  size_t need = 0;
+  auto room = [&](size_t bytes) { const size_t at = need; need += (bytes + 63) & ~(size_t)63; return at; };
+  const size_t o_jobs = room(sizeof(cs::JobDesc) * T.jobs.size()), o_sp = room(sizeof(long long) * T.slot_prefix.size()), o_vp = room(sizeof(int) * T.vp_prefix.size());
+  const size_t o_mx = room(8 * T.mid_x.size()), o_my = room(8 * T.mid_y.size()), o_an = room(8 * T.ang.size());
+  const size_t o_y = room(8 * T.yaw.size()), o_yc = room(8 * T.yaw_c.size()), o_ys = room(8 * T.yaw_s.size()), o_tx = room(sizeof(int) * T.top_x.size());
+  CS_ENSURE(b->h_tables, need + 64);
+  unsigned char* hb = b->h_tables.p;
+  int rc;
+  if ((rc = upload_staged(b->d_jobs, T.jobs, hb, o_jobs, st)) || (rc = upload_staged(b->d_slot_prefix, T.slot_prefix, hb, o_sp, st)) || (rc = upload_staged(b->d_vp_prefix, T.vp_prefix, hb, o_vp, st)) ||
+      (rc = upload_staged(b->d_mid_x, T.mid_x, hb, o_mx, st)) || (rc = upload_staged(b->d_mid_y, T.mid_y, hb, o_my, st)) || (rc = upload_staged(b->d_ang, T.ang, hb, o_an, st)) ||
+      (rc = upload_staged(b->d_yaw, T.yaw, hb, o_y, st)) || (rc = upload_staged(b->d_yaw_c, T.yaw_c, hb, o_yc, st)) || (rc = upload_staged(b->d_yaw_s, T.yaw_s, hb, o_ys, st)) ||
+      (rc = upload_staged(b->d_top_x, T.top_x, hb, o_tx, st)))
+    return rc;
+  CS_HIP_TRY(hipMemsetAsync(b->d_job_valid.p, 0, sizeof(int) * nj, st));
+  X.C.tm->h2d_ms += now_ms() - t0;
+  return CS_OK;
+}
+
+// ---- sweep (HIP): line setup, VP support, corner construction
+int round_sweep(RoundRun& X, RoundTables& T) {
+  cs_detector* d = X.C.d; cs_batch* b = X.C.b;
+  const cs_detect_params& P = d->prm;
+  hipStream_t st = d->stream;
+  const size_t nj = T.nj;
+  cs::DetectDeviceView& v = T.v;
+  v.jobs = b->d_jobs.p; v.n_jobs = (int)nj; v.slot_prefix = b->d_slot_prefix.p; v.vp_prefix = b->d_vp_prefix.p;
+  v.maps = b->d_maps.p; v.mid_x = b->d_mid_x.p; v.mid_y = b->d_mid_y.p; v.line_angle = b->d_ang.p;
+  v.yaw = b->d_yaw.p; v.yaw_cos = b->d_yaw_c.p; v.yaw_sin = b->d_yaw_s.p; v.top_x = b->d_top_x.p; v.rp = b->d_rp.p; v.invK = b->d_invK.p;
+  v.vp = b->d_vp.p; v.bound = b->d_bound.p; v.flag = b->d_flag.p;
+  v.job_valid = b->d_job_valid.p; v.job_cbase = b->d_job_cbase.p;
+  CS_HIP_TRY(hipEventRecord(d->ev[6], st));
+  if (X.dev_setup) {
+    cs::launch_line_setup(b->d_jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, b->d_mid_x.p, b->d_mid_y.p, b->d_ang.p,
+                          P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st);
+  }
+  CS_HIP_TRY(hipEventRecord(d->ev[7], st));
+  if (X.dev_setup) {
+    // the merged segment counts come back with the results (byte accounting, debug getters)
+    CS_ENSURE(b->h_jobs, nj);
+    CS_HIP_TRY(hipMemcpyAsync(b->h_jobs.p, b->d_jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
+  }
+  CS_HIP_TRY(hipEventRecord(d->ev[0], st));
+  cs::launch_vp_support(v, X.C.sp, T.vp_total, st);
+  CS_HIP_TRY(hipEventRecord(d->ev[1], st));
+  cs::launch_candidates(v, X.C.sp, T.slot_total, st);
+  CS_HIP_TRY(hipEventRecord(d->ev[2], st));
+  CS_HIP_TRY(hipGetLastError());
+  return CS_OK;
+}
+
+// compaction into the c_* columns (`rows` of them) and the scorer
+int round_compact_score(RoundRun& X, RoundTables& T, long long rows) {
+  cs_detector* d = X.C.d; cs_batch* b = X.C.b;
+  hipStream_t st = d->stream;
+  cs::DetectDeviceView& v = T.v;
+  CS_ENSURE(b->d_c_slot, rows + 1); CS_ENSURE(b->d_c_flag, rows + 1); CS_ENSURE(b->d_c_dist, rows + 1); CS_ENSURE(b->d_c_angle, rows + 1); CS_ENSURE(b->d_c_skew, rows + 1);
+  v.c_slot = b->d_c_slot.p; v.c_flag = b->d_c_flag.p; v.c_dist = b->d_c_dist.p; v.c_angle = b->d_c_angle.p; v.c_skew = b->d_c_skew.p;
+  CS_HIP_TRY(hipEventRecord(d->ev[3], st));
+  cs::launch_scan_compact(v, st);
+  CS_HIP_TRY(hipEventRecord(d->ev[8], st));
+  cs::launch_score(v, X.C.sp, rows, T.slot_total, st);
+  CS_HIP_TRY(hipEventRecord(d->ev[4], st));
+  return CS_OK;
+}
+
+// Kernel times and algorithmic bytes of a finished round: geometry kernel = vanishing points read once per
+// (job, rp, yaw) + one flag per slot (the corners stay in registers); scoring kernel = each distance map once + the vanishing points and
+// the VP support table once per (job, rp, yaw) + per valid proposal 12 B read (slot id, flag) and 28 B of scores written.
+// ranked: the round was ranked on the device (events 4 -> 5).
+int account_sweep(cs_detector* d, cs_detect_timing& tm, const RoundTables& T, long long n_valid, bool ranked) {
+  float ms = 0;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
+  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
+  if (ranked) { CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[4], d->ev[5])); tm.rank_kernel_ms += ms; }
+  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
+  tm.cand_kernel_launches += 1;
+  tm.cand_kernel_bytes += 48LL * T.vp_total + 4LL * T.slot_total;
+  long long sbytes = 96LL * T.vp_total + (28LL + 8LL + 4LL) * n_valid;
+  for (const cs::JobDesc& jd : T.jobs) sbytes += 4LL * jd.map_w * (jd.g.eb - jd.g.et);
+  tm.score_kernel_bytes += sbytes;
+  return CS_OK;
+}
+
+// ---- rank on the device (nothing has to come back to the host before the ranking), records on the host; boxes flagged by the kernel
+// are re-ranked exactly
+int round_rank_device(RoundRun& X, RoundTables& T) {
+  PipeCtx& C = X.C;
+  cs_detector* d = C.d; cs_batch* b = C.b;
+  const cs_detect_params& P = d->prm;
+  const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
+  hipStream_t st = d->stream;
+  cs_detect_timing& tm = *C.tm;
+  const cs::DetectDeviceView& v = T.v;
+  const size_t nj = T.nj, nb = T.box_job0.size();
+  int rc;
+  if ((rc = round_compact_score(X, T, T.slot_total))) return rc;   // the exact number of valid proposals stays on the device
+  CS_ENSURE(b->d_box_job0, nb); CS_ENSURE(b->d_box_njobs, nb); CS_ENSURE(b->d_win_count, nb); CS_ENSURE(b->d_fallback, nb); CS_ENSURE(b->d_winners, nb * KMAX);
+  CS_ENSURE(b->h_winners, nb * KMAX); CS_ENSURE(b->h_win_count, nb); CS_ENSURE(b->h_fallback, nb); CS_ENSURE(b->h_job_valid, nj); CS_ENSURE(b->h_job_cbase, nj + 1);
+  CS_ENSURE(b->h_tables2, 2 * sizeof(int) * nb + 128);
+  if ((rc = upload_staged(b->d_box_job0, T.box_job0, b->h_tables2.p, 0, st)) || (rc = upload_staged(b->d_box_njobs, T.box_njobs, b->h_tables2.p, (sizeof(int) * nb + 63) & ~(size_t)63, st))) return rc;
+  cs::RankView rv{};
+  rv.box_job0 = b->d_box_job0.p; rv.box_njobs = b->d_box_njobs.p; rv.n_boxes = (int)nb;
+  rv.winners = b->d_winners.p; rv.win_count = b->d_win_count.p; rv.fallback = b->d_fallback.p;
+  if (X.sample_rp) { CS_ENSURE(b->d_last_slot, nb); CS_ENSURE(b->h_last_slot, nb); rv.last_slot = b->d_last_slot.p; }
+  cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
+  cs::launch_rank(v, rv, rkp, st);
+  CS_HIP_TRY(hipEventRecord(d->ev[5], st));
+  CS_HIP_TRY(hipGetLastError());
+  double t0 = now_ms();
+  CS_HIP_TRY(hipMemcpyAsync(b->h_winners.p, b->d_winners.p, sizeof(cs::RankWinner) * nb * KMAX, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(b->h_win_count.p, b->d_win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(b->h_fallback.p, b->d_fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+  if (X.sample_rp) CS_HIP_TRY(hipMemcpyAsync(b->h_last_slot.p, b->d_last_slot.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(b->h_job_cbase.p, b->d_job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipStreamSynchronize(st));
+  tm.d2h_ms += now_ms() - t0;
+  if (X.dev_setup) for (size_t j = 0; j < nj; j++) T.jobs[j].m = b->h_jobs.p[j].m;
+  const long long n_valid = b->h_job_cbase.p[nj];
+  tm.n_valid += n_valid;
+  if ((rc = account_sweep(d, tm, T, n_valid, true))) return rc;
+  t0 = now_ms();
+  // columns of every flagged box, fetched with one gather + one copy per column
+  std::vector<long long> fb_src, fb_dst, fb_slot;
+  std::vector<int> fb_cnt, fb_flag, fb_range_of_job(nj, -1);
+  std::vector<double> fb_dist, fb_angle, fb_skew;
+  long long tot = 0;
+  for (size_t q = 0; q < nb; q++)
+    if (b->h_fallback.p[q])
+      for (int h = 0; h < T.box_njobs[q]; h++) {
+        int j = T.box_job0[q] + h;
+        fb_range_of_job[j] = (int)fb_src.size();
+        fb_src.push_back(b->h_job_cbase.p[j]); fb_cnt.push_back(b->h_job_valid.p[j]); fb_dst.push_back(tot);
+        tot += b->h_job_valid.p[j];
+      }
+  if (!fb_src.empty()) {
+    size_t nr = fb_src.size();
+    CS_ENSURE(b->d_fb_src, nr); CS_ENSURE(b->d_fb_dst, nr); CS_ENSURE(b->d_fb_cnt, nr);
+    CS_ENSURE(b->d_fb_dist, tot + 1); CS_ENSURE(b->d_fb_angle, tot + 1); CS_ENSURE(b->d_fb_skew, tot + 1); CS_ENSURE(b->d_fb_flag, tot + 1); CS_ENSURE(b->d_fb_slot, tot + 1);
+    if ((rc = upload_pageable(b->d_fb_src, fb_src, st)) || (rc = upload_pageable(b->d_fb_dst, fb_dst, st)) || (rc = upload_pageable(b->d_fb_cnt, fb_cnt, st))) return rc;
+    cs::launch_gather_ranges(v, b->d_fb_src.p, b->d_fb_cnt.p, b->d_fb_dst.p, (int)nr, b->d_fb_dist.p, b->d_fb_angle.p, b->d_fb_skew.p, b->d_fb_flag.p, b->d_fb_slot.p, st);
+    fb_dist.resize(tot); fb_angle.resize(tot); fb_skew.resize(tot); fb_flag.resize(tot); fb_slot.resize(tot);
+    if (tot) {
+      CS_HIP_TRY(hipMemcpyAsync(fb_dist.data(), b->d_fb_dist.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(fb_angle.data(), b->d_fb_angle.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(fb_skew.data(), b->d_fb_skew.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(fb_flag.data(), b->d_fb_flag.p, 4 * (size_t)tot, hipMemcpyDeviceToHost, st));
+      CS_HIP_TRY(hipMemcpyAsync(fb_slot.data(), b->d_fb_slot.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
+    }
+    CS_HIP_TRY(hipStreamSynchronize(st));
+  }
+  // the boxes the device ranked: their records; the flagged ones: the exact ranking only (their corners are fetched below, in one gather)
+  const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
+  std::vector<std::vector<ExactWinner>> fb_winners(nb);
+  d->pool->run((int)nb, [&](int q) {
+    const int j0 = T.box_job0[q], nh = T.box_njobs[q];
+    const cs::JobDesc* jobs = &T.jobs[j0];
+    if (b->h_fallback.p[q]) {
+      HeightCols cols[3];
+      for (int h = 0; h < nh; h++) {
+        const long long p0 = fb_dst[fb_range_of_job[j0 + h]];
+        cols[h] = HeightCols{fb_dist.data() + p0, fb_angle.data() + p0, fb_skew.data() + p0, fb_flag.data() + p0, fb_slot.data() + p0, b->h_job_valid.p[j0 + h]};
+      }
+      const long long last = exact_rank_box(cols, nh, RW, KMAX, fb_winners[q]);
+      if (X.sample_rp) carry_yaw(X, jobs[nh - 1], last);
+      return;
+    }
+    if (X.sample_rp) carry_yaw(X, jobs[nh - 1], b->h_last_slot.p[q]);
+    const int nw = b->h_win_count.p[q];
+    for (int r = 0; r < nw; r++) {
+      const cs::RankWinner& w = b->h_winners.p[q * KMAX + r];
+      int h = 0;
+      while (h + 1 < nh && w.slot >= jobs[h + 1].slot_off) h++;
+      round_write_winner(X, T, jobs[h], w.slot, w.flag, w.dist_err, w.angle_err, w.normalized_error, w.corners, r);
+    }
+    C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = nw;
+  });
+  std::vector<long long> ws;
+  std::vector<size_t> corner0(nb, 0);      // first of a flagged box's winners in h_win_corners
+  for (size_t q = 0; q < nb; q++)
+    if (b->h_fallback.p[q]) { tm.n_fallback_boxes++; corner0[q] = ws.size(); for (const ExactWinner& w : fb_winners[q]) ws.push_back(w.slot); }
+  if (!ws.empty()) {
+    CS_ENSURE(b->d_win_slots, ws.size()); CS_ENSURE(b->d_win_corners, 16 * ws.size()); CS_ENSURE(b->h_win_corners, 16 * ws.size());
+    if ((rc = upload_pageable(b->d_win_slots, ws, st))) return rc;
+    cs::launch_gather_corners(v, C.sp, b->d_win_slots.p, (int)ws.size(), b->d_win_corners.p, st);
+    CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * ws.size(), hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipStreamSynchronize(st));
+  }
+  d->pool->run((int)nb, [&](int q) {
+    if (!b->h_fallback.p[q]) return;
+    const cs::JobDesc* jobs = &T.jobs[T.box_job0[q]];
+    const int nw = (int)fb_winners[q].size();
+    for (int r = 0; r < nw; r++) {
+      const ExactWinner& w = fb_winners[q][r];
+      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, b->h_win_corners.p + 16 * (corner0[q] + r), r);
+    }
+    C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = nw;
+  });
+  tm.finalize_ms += now_ms() - t0;
+  return CS_OK;
+}
+
+// ---- rank on the host: every column comes back, every box gets the exact ranking; the candidates are retained for cs_batch_debug_*
+int round_rank_host(RoundRun& X, RoundTables& T) {
+  PipeCtx& C = X.C;
+  cs_detector* d = C.d; cs_batch* b = C.b;
+  const cs_detect_params& P = d->prm;
+  const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
+  hipStream_t st = d->stream;
+  cs_detect_timing& tm = *C.tm;
+  const std::vector<std::vector<CamCache>>& cam_rp = *C.cam_rp_all;
+  const size_t nj = T.nj, nb = T.box_job0.size();
+  int rc;
+  // valid counts -> host -> size the compact arrays
+  CS_ENSURE(b->h_job_valid, nj); CS_ENSURE(b->h_job_cbase, nj + 1);
+  CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipStreamSynchronize(st));
+  if (X.dev_setup) for (size_t j = 0; j < nj; j++) T.jobs[j].m = b->h_jobs.p[j].m;
+  long long n_valid = 0;
+  for (size_t j = 0; j < nj; j++) { b->h_job_cbase.p[j] = n_valid; n_valid += b->h_job_valid.p[j]; }
+  b->h_job_cbase.p[nj] = n_valid;
+  tm.n_valid += n_valid;
+  if ((rc = round_compact_score(X, T, n_valid))) return rc;
+  CS_HIP_TRY(hipGetLastError());
+  CS_ENSURE(b->h_c_slot, n_valid + 1); CS_ENSURE(b->h_c_flag, n_valid + 1); CS_ENSURE(b->h_c_dist, n_valid + 1); CS_ENSURE(b->h_c_angle, n_valid + 1); CS_ENSURE(b->h_c_skew, n_valid + 1);
+  double t0 = now_ms();
+  if (n_valid) {
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_slot.p, b->d_c_slot.p, sizeof(long long) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_flag.p, b->d_c_flag.p, sizeof(int) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_dist.p, b->d_c_dist.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_angle.p, b->d_c_angle.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_skew.p, b->d_c_skew.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+  }
+  CS_HIP_TRY(hipStreamSynchronize(st));
+  tm.d2h_ms += now_ms() - t0;
+  if ((rc = account_sweep(d, tm, T, n_valid, false))) return rc;
+
+  // per job: the candidate rows and fuse_normalize_scores_v2, retained
+  t0 = now_ms();
+  const size_t res_base = b->results.size();
+  b->results.resize(res_base + nj);
+  d->pool->run((int)nj, [&](int j) {
+    const cs::JobDesc& jd = T.jobs[j];
+    JobResult& R = b->results[res_base + j];
+    R.frame = jd.frame; R.box = jd.box; R.hid = jd.hid;
+    const long long c0 = b->h_job_cbase.p[j];
+    const int V = b->h_job_valid.p[j];
+    R.n_valid = V;
+    R.rows9.resize(9 * (size_t)V);
+    R.slots.assign(b->h_c_slot.p + c0, b->h_c_slot.p + c0 + V);
+    for (int i = 0; i < V; i++) {
+      const SlotRef s = decode_slot(jd, R.slots[i]);
+      const cs::RpPose& pose = cam_rp[jd.frame][s.rp].pose;
+      candidate_row9(s, b->h_c_flag.p[c0 + i], b->h_c_dist.p[c0 + i], b->h_c_angle.p[c0 + i], T.yaw[jd.yaw_off + s.y], jd.down_expand, pose.roll, pose.pitch, &R.rows9[9 * (size_t)i]);
+    }
+    fuse_scores(b->h_c_dist.p + c0, b->h_c_angle.p + c0, V, P.weight_vp_angle, R.keep, R.score);
+  });
+  for (size_t j = 0; j < nj; j++) b->job_index[((size_t)T.jobs[j].frame * MB + T.jobs[j].box) * 3 + T.jobs[j].hid] = (int)(res_base + j);
+  // per box: proposals over its height samples (in order), final ranking (:804-838)
+  const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
+  std::vector<std::vector<ExactWinner>> win_per_box(nb);
+  d->pool->run((int)nb, [&](int q) {
+    const int j0 = T.box_job0[q], nh = T.box_njobs[q];
+    HeightCols cols[3];
+    for (int h = 0; h < nh; h++) {
+      const long long c0 = b->h_job_cbase.p[j0 + h];
+      const JobResult& R = b->results[res_base + j0 + h];
+      cols[h] = HeightCols{b->h_c_dist.p + c0, b->h_c_angle.p + c0, b->h_c_skew.p + c0, b->h_c_flag.p + c0, b->h_c_slot.p + c0, R.n_valid, &R.keep, &R.score};
+    }
+    const long long last = exact_rank_box(cols, nh, RW, KMAX, win_per_box[q]);
+    if (X.sample_rp) carry_yaw(X, T.jobs[j0 + nh - 1], last);
+  });
+  tm.rank_host_ms += now_ms() - t0;
+
+  // ---- finish: the winners' corners (debug: those of every valid candidate of the round) and the records
+  t0 = now_ms();
+  std::vector<long long> wslots;
+  for (const auto& wl : win_per_box) for (const ExactWinner& w : wl) wslots.push_back(w.slot);
+  const size_t nw = wslots.size();
+  if (b->debug) wslots.insert(wslots.end(), b->h_c_slot.p, b->h_c_slot.p + n_valid);
+  const size_t n_gather = wslots.size();
+  if (n_gather) {
+    CS_ENSURE(b->d_win_slots, n_gather); CS_ENSURE(b->d_win_corners, 16 * n_gather); CS_ENSURE(b->h_win_corners, 16 * n_gather);
+    if ((rc = upload_pageable(b->d_win_slots, wslots, st))) return rc;
+    cs::launch_gather_corners(T.v, C.sp, b->d_win_slots.p, (int)n_gather, b->d_win_corners.p, st);
+    CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * n_gather, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipStreamSynchronize(st));
+  }
+  size_t i = 0;
+  for (size_t q = 0; q < nb; q++) {
+    const cs::JobDesc* jobs = &T.jobs[T.box_job0[q]];
+    for (size_t r = 0; r < win_per_box[q].size(); r++, i++) {
+      const ExactWinner& w = win_per_box[q][r];
+      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, b->h_win_corners.p + 16 * i, (int)r);
+    }
+    C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = (int)win_per_box[q].size();
+  }
+  if (b->debug) {
+    for (size_t j = 0; j < nj; j++) {
+      JobResult& R = b->results[res_base + j];
+      const long long c0 = b->h_job_cbase.p[j];
+      R.corners.assign(b->h_win_corners.p + 16 * (nw + c0), b->h_win_corners.p + 16 * (nw + c0 + R.n_valid));
+    }
+  }
+  tm.finalize_ms += now_ms() - t0;
+  return CS_OK;
+}
+
+}  // namespace
+
 static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_counts, bool defer) {
   if (!d || !b || b->det != d || !out || !out_counts) return CS_ERR_INVALID_ARG;
   if (b->run_state) { cs_set_error("cs_batch_submit: the previous submit of this batch has not been collected"); return CS_ERR_INVALID_ARG; }
@@ -2072,11 +2377,8 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
   const cs_detect_params& P = d->prm;
   const bool sample_rp = P.whether_sample_cam_roll_pitch != 0;
   const int NF = b->n_frames, MB = b->max_boxes, KMAX = P.max_cuboid_num;
-  auto parallel_for = [d](int n, int /*nt*/, const std::function<void(int)>& fn) { d->pool->run(n, fn); };
-  const int NT = d->n_threads;
-  hipStream_t st = d->stream;
   cs_detect_timing& tm = rs->tm;
-  double t_begin = now_ms();
+  const double t_begin = now_ms();
   rs->t_begin = t_begin;
 
   std::fill(out_counts, out_counts + (size_t)NF * std::max(MB, 0), 0);
@@ -2090,58 +2392,17 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
   sp.short_sq_bound = cs::sqrt_lt_bound(P.shorted_edge_thre);
   sp.consider_config_1 = P.consider_config_1; sp.consider_config_2 = P.consider_config_2;
 
-  // ---- per-frame camera caches: raw pose and the roll/pitch sample poses (:78-79, :344-355, :368-377)
-  double t0 = now_ms();
-  std::vector<CamCache>& cam_raw = rs->cam_raw; cam_raw.resize(NF);
-  std::vector<std::vector<CamCache>>& cam_rp = rs->cam_rp; cam_rp.resize(NF);
-  std::vector<double> cur_yaw(NF);  // cam_pose.camera_yaw as the next box will see it (:180)
-  parallel_for(NF, NT, [&](int f) {
-    const FrameIn& F = b->frames[f];
-    make_cam(F.K, F.R, F.t, cam_raw[f]);
-    cur_yaw[f] = cam_raw[f].cam_yaw;
-    if (sample_rp) {
-      std::vector<double> rs, ps;
-      linespace<double>(cam_raw[f].euler[0] - 6.0 / 180.0 * CS_PI, cam_raw[f].euler[0] + 6.0 / 180.0 * CS_PI, 3.0 / 180.0 * CS_PI, rs);
-      linespace<double>(cam_raw[f].euler[1] - 6.0 / 180.0 * CS_PI, cam_raw[f].euler[1] + 6.0 / 180.0 * CS_PI, 3.0 / 180.0 * CS_PI, ps);
-      for (double r : rs)
-        for (double p : ps) {
-          double Rn[9];
-          euler_to_rot(r, p, cam_raw[f].euler[2], Rn);
-          CamCache c;
-          make_cam(F.K, Rn, F.t, c);
-          c.pose.roll = r; c.pose.pitch = p;  // the row stores the *sample* angles (:686)
-          cam_rp[f].push_back(c);
-        }
-    } else {
-      cam_rp[f].push_back(cam_raw[f]);
-    }
-  });
-  // rp pool: identical for every round -> upload once
-  std::vector<int>& rp_off = rs->rp_off; rp_off.assign(NF + 1, 0);
-  for (int f = 0; f < NF; f++) rp_off[f + 1] = rp_off[f] + (int)cam_rp[f].size();
-  {
-    // (pinned staging owned by the batch: the copy is queued behind whatever the detector's stream still runs -- another batch's sweep --
-    // and nobody waits for it here)
-    const size_t np_ = (size_t)std::max(1, rp_off[NF]);
-    int rc = b->h_rp.ensure(np_);
-    if (rc) return rc;
-    for (int f = 0; f < NF; f++)
-      for (size_t k = 0; k < cam_rp[f].size(); k++) b->h_rp.p[rp_off[f] + k] = cam_rp[f][k].pose;
-    rc = b->d_rp.ensure(np_);
-    if (rc) return rc;
-    CS_HIP_TRY(hipMemcpyAsync(b->d_rp.p, b->h_rp.p, sizeof(cs::RpPose) * np_, hipMemcpyHostToDevice, st));
-  }
-  tm.setup_host_ms += now_ms() - t0;
-
+  int rc = build_camera_caches(d, b, rs, sample_rp);
+  if (rc) return rc;
+  rs->C = PipeCtx{d, b, out, out_counts, &rs->cam_raw, &rs->rp_off, sp, &rs->tm, &rs->cam_rp};
+  PipeCtx& C = rs->C;
   if (g_prof) g_mark[11] += now_ms() - t_begin;   // camera caches + pose pool upload
+
   // ---- production path: chunked two-slot pipeline (host packs chunk k+1 / finishes chunk k-1 while the GPU sweeps k)
-  if (!sample_rp && !b->debug && !b->force_host_rank && !b->force_host_setup && !b->force_no_pipeline && b->device_setup && KMAX <= cs::RANK_KMAX && MB > 0) {
-    rs->C = PipeCtx{d, b, out, out_counts, &rs->cam_raw, &rs->rp_off, sp, &rs->tm};
-    PipeCtx& C = rs->C;
+  if (!sample_rp && lean_path_allowed(b, KMAX)) {
     const int n_chunks = std::max(1, std::min(NF, b->pipe_chunks));
     if (n_chunks == 1) {    // the usual shape: one launch, one finish -- the finish may be left to cs_batch_collect
-      int rc = pipe_launch(C, b->pipe[0], 0, NF);
-      if (rc) return rc;
+      if ((rc = pipe_launch(C, b->pipe[0], 0, NF))) return rc;
       rs->deferred = true;
       b->run_state = rs_owner.release();
       return defer ? CS_OK : batch_collect_impl(d, b);
@@ -2149,588 +2410,37 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
     for (int k = 0; k <= n_chunks; k++) {
       if (k < n_chunks) {
         int f0 = (int)((long long)NF * k / n_chunks), f1 = (int)((long long)NF * (k + 1) / n_chunks);
-        int rc = pipe_launch(C, b->pipe[k & 1], f0, f1);
-        if (rc) return rc;
+        if ((rc = pipe_launch(C, b->pipe[k & 1], f0, f1))) return rc;
       }
-      if (k >= 1) {
-        int rc = pipe_finish(C, b->pipe[(k - 1) & 1], cam_rp);
-        if (rc) return rc;
-      }
+      if (k >= 1 && (rc = pipe_finish(C, b->pipe[(k - 1) & 1], rs->cam_rp))) return rc;
     }
     tm.total_ms = now_ms() - t_begin;
     b->timing = tm;
     b->ran = true;
-    if (g_prof && (++g_runs % 8) == 0) {
-      const char* nm[11] = {"jobs+samples", "prefix+pack", "box table", "alloc+enqueue", "gpu wait", "tie lists", "records", "tie wait", "tie rank", "tie corners", "tie records"};
-      fprintf(stderr, "[detect] host ms/run:");
-      for (int k = 0; k < 11; k++) { fprintf(stderr, " %s %.3f", nm[k], g_mark[k] / 8); g_mark[k] = 0; }
-      fprintf(stderr, " | pre %.3f total %.3f\n", g_mark[11] / 8, tm.total_ms); g_mark[11] = 0;
-    }
+    prof_report(tm.total_ms);
     return CS_OK;
   }
 
   // ---- roll/pitch sampling, lean path: every round queued at once, the carried yaw picked on the device
-  {
-    int max_rp = 0;
-    for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)cam_rp[f].size());
-    if (sample_rp && !b->debug && !b->force_host_rank && !b->force_host_setup && !b->force_no_pipeline && !b->force_round_path && b->device_setup &&
-        KMAX <= cs::RANK_KMAX && MB > 0 && max_rp <= cs::vp3_table_doubles_per_job() / 2) {
-      rs->C = PipeCtx{d, b, out, out_counts, &rs->cam_raw, &rs->rp_off, sp, &rs->tm, &rs->cam_rp};
-      int rc = rp_launch(rs->C, b->pipe[0], rs->cam_rp);
-      if (rc) return rc;
-      rs->deferred = true; rs->rp_lean = true;
-      b->run_state = rs_owner.release();
-      return defer ? CS_OK : batch_collect_impl(d, b);
-    }
+  int max_rp = 0;
+  for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)rs->cam_rp[f].size());
+  if (sample_rp && lean_path_allowed(b, KMAX) && !b->force_round_path && max_rp <= cs::vp3_table_doubles_per_job() / 2) {
+    if ((rc = rp_launch(C, b->pipe[0], rs->cam_rp))) return rc;
+    rs->deferred = true; rs->rp_lean = true;
+    b->run_state = rs_owner.release();
+    return defer ? CS_OK : batch_collect_impl(d, b);
   }
-  // proposals per (frame, box) accumulate over height samples inside a round
-  std::vector<Winner> winners;
+
+  // ---- the round path: with roll/pitch sampling round r = box r of every frame, else one round of all boxes
+  RoundRun X{C, sample_rp, b->device_setup && !b->force_host_setup, std::vector<double>(NF)};
+  for (int f = 0; f < NF; f++) X.cur_yaw[f] = rs->cam_raw[f].cam_yaw;
+  const bool device_rank = !b->debug && !b->force_host_rank && KMAX <= cs::RANK_KMAX;
   const int n_rounds = sample_rp ? MB : (MB > 0 ? 1 : 0);
   for (int round = 0; round < n_rounds; round++) {
-    // ------------------------------------------------------------------ setup (host) ---------
-    t0 = now_ms();
-    const bool dev_setup = b->device_setup && !b->force_host_setup;
-    std::vector<FrameRound> fr(NF);
-    parallel_for(NF, NT, [&](int f) {
-      const FrameIn& F = b->frames[f];
-      FrameRound& R = fr[f];
-      int b0 = sample_rp ? round : 0, b1 = sample_rp ? std::min(round + 1, F.n_boxes) : F.n_boxes;
-      int shared_yoff = -1, shared_Y = 0;  // without roll/pitch sampling cam_pose never changes: every box of the frame sweeps the same yaw list (:180-184)
-      for (int bi = b0; bi < b1; bi++) {
-        const double* bb = &F.boxes[5 * bi];
-        int left = bb[0], top = bb[1], w = bb[2], h = bb[3];
-        int right = left + bb[2];
-        int res = (int)std::round(std::min(20, w / 10));
-        if (res < 1) continue;  // :215 break (same for every height sample)
-        // yaw samples (:180-184)
-        int yoff, nY;
-        if (shared_yoff >= 0) { yoff = shared_yoff; nY = shared_Y; }
-        else {
-          double yaw_init = cur_yaw[f] - 90.0 / 180.0 * CS_PI;
-          std::vector<double> yaws;
-          linespace<double>(yaw_init - P.yaw_range_deg / 180.0 * CS_PI, yaw_init + P.yaw_range_deg / 180.0 * CS_PI, P.yaw_step_deg / 180.0 * CS_PI, yaws);
-          yoff = (int)R.yaw.size(); nY = (int)yaws.size();
-          for (double y : yaws) { R.yaw.push_back(y); R.yaw_c.push_back(h_cos(y)); R.yaw_s.push_back(h_sin(y)); }
-          if (!sample_rp) { shared_yoff = yoff; shared_Y = nY; }
-        }
-        std::vector<int> tops;
-        linespace<int>(left + 5, right - 5, res, tops);
-        for (int k = 0; k < F.n_heights[bi]; k++) {
-          const cs_roi& roi = F.rois[3 * bi + k];
-          cs::JobDesc jd;
-          std::memset(&jd, 0, sizeof(jd));
-          int he = h + roi.down_expand;
-          jd.g.left = left; jd.g.top = top; jd.g.right = right; jd.g.down = top + he;
-          jd.g.el = roi.left; jd.g.et = roi.top; jd.g.er = roi.left + roi.width; jd.g.eb = roi.top + roi.height;
-          jd.map_w = roi.width;
-          jd.Y = nY; jd.T = (int)tops.size(); jd.RP = (int)cam_rp[f].size();
-          jd.down_expand = roi.down_expand;
-          jd.frame = f; jd.box = bi; jd.hid = k;
-          jd.map_off = F.map_offs[3 * bi + k];
-          jd.rp_off = rp_off[f];
-          jd.diag = std::sqrt(double(w * w + he * he));
-          JobHost jh;
-          jh.frame = f; jh.box = bi; jh.hid = k; jh.yaw_off_local = yoff; jh.tops = tops;
-          // ROI line filter (:271-283) + merge (:288-296) + angles/midpoints (:309-315): line_setup_kernel, or here
-          if (dev_setup) { jd.m = 0; jh.line_cap = F.n_lines; R.jobs.push_back(jd); R.jh.push_back(std::move(jh)); continue; }
-          std::vector<double> in;
-          for (int e = 0; e < F.n_lines; e++) {
-            const double* l = &F.lines[4 * e];
-            if (cs::inside_box(cs::v2(l[0], l[1]), jd.g.el, jd.g.et, jd.g.er, jd.g.eb) &&
-                cs::inside_box(cs::v2(l[2], l[3]), jd.g.el, jd.g.et, jd.g.er, jd.g.eb))
-              in.insert(in.end(), l, l + 4);
-          }
-          merge_lines(in, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold);
-          jd.m = (int)(in.size() / 4);
-          for (int i = 0; i < jd.m; i++) {
-            jh.angs.push_back(cs::cs_atan2(in[4 * i + 3] - in[4 * i + 1], in[4 * i + 2] - in[4 * i]));
-            jh.mids_x.push_back((in[4 * i] + in[4 * i + 2]) / 2);
-            jh.mids_y.push_back((in[4 * i + 1] + in[4 * i + 3]) / 2);
-          }
-          jh.line_cap = jd.m;
-          R.jobs.push_back(jd);
-          R.jh.push_back(std::move(jh));
-        }
-      }
-    });
-    // pack: per-frame sizes -> offsets (serial prefix over frames) -> parallel copy into the pooled arrays
-    std::vector<size_t> f_job(NF + 1, 0), f_line(NF + 1, 0), f_yaw(NF + 1, 0), f_top(NF + 1, 0);
-    std::vector<long long> f_slot(NF + 1, 0), f_vp(NF + 1, 0);
-    for (int f = 0; f < NF; f++) {
-      size_t nl = 0, nt = 0;
-      long long ns = 0, nv = 0;
-      for (size_t q = 0; q < fr[f].jobs.size(); q++) {
-        const cs::JobDesc& jd = fr[f].jobs[q];
-        nl += fr[f].jh[q].line_cap; nt += fr[f].jh[q].tops.size();
-        nv += (long long)jd.RP * jd.Y; ns += (long long)jd.RP * jd.Y * jd.T * 2;
-      }
-      f_job[f + 1] = f_job[f] + fr[f].jobs.size(); f_line[f + 1] = f_line[f] + nl; f_yaw[f + 1] = f_yaw[f] + fr[f].yaw.size();
-      f_top[f + 1] = f_top[f] + nt; f_slot[f + 1] = f_slot[f] + ns; f_vp[f + 1] = f_vp[f] + nv;
-    }
-    const size_t nj = f_job[NF], n_lines = f_line[NF], n_yaw = f_yaw[NF], n_top = f_top[NF];
-    if (nj == 0) { tm.setup_host_ms += now_ms() - t0; continue; }
-    if (f_vp[NF] > 0x7fffffffLL) { cs_set_error("too many (roll,pitch,yaw) samples in one round"); return CS_ERR_CAPACITY; }
-    std::vector<cs::JobDesc> jobs(nj);
-    std::vector<long long> slot_prefix(nj + 1);
-    std::vector<int> vp_prefix(nj + 1);
-    const size_t n_lines_host = dev_setup ? 0 : n_lines;  // with the device line setup these tables are only ever written by the kernel
-    std::vector<double> mid_x(n_lines_host), mid_y(n_lines_host), ang(n_lines_host), yaw(n_yaw), yaw_c(n_yaw), yaw_s(n_yaw);
-    std::vector<int> top_x(n_top);
-    parallel_for(NF, NT, [&](int f) {
-      FrameRound& R = fr[f];
-      size_t ji = f_job[f], lo = f_line[f], yo = f_yaw[f], to = f_top[f];
-      long long so = f_slot[f], vo = f_vp[f];
-      std::copy(R.yaw.begin(), R.yaw.end(), yaw.begin() + yo);
-      std::copy(R.yaw_c.begin(), R.yaw_c.end(), yaw_c.begin() + yo);
-      std::copy(R.yaw_s.begin(), R.yaw_s.end(), yaw_s.begin() + yo);
-      for (size_t q = 0; q < R.jobs.size(); q++, ji++) {
-        cs::JobDesc& jd = R.jobs[q];
-        const JobHost& jh = R.jh[q];
-        jd.line_off = (int)lo; jd.yaw_off = (int)(yo + jh.yaw_off_local); jd.top_off = (int)to;
-        jd.vp_off = (int)vo; jd.slot_off = so;
-        if (!dev_setup) {
-          std::copy(jh.mids_x.begin(), jh.mids_x.end(), mid_x.begin() + lo);
-          std::copy(jh.mids_y.begin(), jh.mids_y.end(), mid_y.begin() + lo);
-          std::copy(jh.angs.begin(), jh.angs.end(), ang.begin() + lo);
-        }
-        std::copy(jh.tops.begin(), jh.tops.end(), top_x.begin() + to);
-        lo += jh.line_cap; to += jh.tops.size();
-        slot_prefix[ji] = so; vp_prefix[ji] = (int)vo;
-        vo += (long long)jd.RP * jd.Y;
-        so += (long long)jd.RP * jd.Y * jd.T * 2;
-        jobs[ji] = jd;
-      }
-    });
-    slot_prefix[nj] = f_slot[NF]; vp_prefix[nj] = (int)f_vp[NF];
-    const long long slot_total = slot_prefix[nj];
-    const int vp_total = vp_prefix[nj];
-    tm.setup_host_ms += now_ms() - t0;
-    tm.n_jobs += (long long)nj; tm.n_slots += slot_total;
-
-    // ------------------------------------------------------------------ H2D -----------------
-    t0 = now_ms();
-    int rc;
-#define ENS(buf, n) do { rc = (buf).ensure(n); if (rc) return rc; } while (0)
-    ENS(b->d_jobs, nj); ENS(b->d_slot_prefix, nj + 1); ENS(b->d_vp_prefix, nj + 1); ENS(b->d_job_valid, nj); ENS(b->d_job_cbase, nj + 1);
-    ENS(b->d_mid_x, n_lines + 1); ENS(b->d_mid_y, n_lines + 1); ENS(b->d_ang, n_lines + 1);
-    ENS(b->d_yaw, n_yaw + 1); ENS(b->d_yaw_c, n_yaw + 1); ENS(b->d_yaw_s, n_yaw + 1); ENS(b->d_top_x, n_top + 1);
-    ENS(b->d_vp, 6 * (size_t)vp_total + 6); ENS(b->d_bound, 6 * (size_t)vp_total + 6);
-    ENS(b->d_flag, slot_total + 1);
-    // The tables are small (a frame: ~10 of them, a few KB each).  From the std::vectors every hipMemcpyAsync is a staged, effectively
-    // synchronous copy (10-25 us apiece, ~150 us per call); copied first into ONE pinned block they go out back to back and the host
-    // does not wait (the round's results are awaited further down, before the block is written again).
-    {
-      size_t need = 0;
-      auto room = [&](size_t bytes) { const size_t at = need; need += (bytes + 63) & ~(size_t)63; return at; };
-      const size_t o_jobs = room(sizeof(cs::JobDesc) * jobs.size()), o_sp = room(sizeof(long long) * slot_prefix.size()), o_vp = room(sizeof(int) * vp_prefix.size());
-      const size_t o_mx = room(8 * mid_x.size()), o_my = room(8 * mid_y.size()), o_an = room(8 * ang.size());
-      const size_t o_y = room(8 * yaw.size()), o_yc = room(8 * yaw_c.size()), o_ys = room(8 * yaw_s.size()), o_tx = room(sizeof(int) * top_x.size());
-      ENS(b->h_tables, need + 64);
-      unsigned char* hb = b->h_tables.p;
-#define H2DP(dst, vec, off) do { if (!(vec).empty()) { memcpy(hb + (off), (vec).data(), sizeof((vec)[0]) * (vec).size()); \
-                                   CS_HIP_TRY(hipMemcpyAsync((dst).p, hb + (off), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st)); } } while (0)
-      H2DP(b->d_jobs, jobs, o_jobs); H2DP(b->d_slot_prefix, slot_prefix, o_sp); H2DP(b->d_vp_prefix, vp_prefix, o_vp);
-      if (n_lines && !dev_setup) { H2DP(b->d_mid_x, mid_x, o_mx); H2DP(b->d_mid_y, mid_y, o_my); H2DP(b->d_ang, ang, o_an); }
-      if (n_yaw) { H2DP(b->d_yaw, yaw, o_y); H2DP(b->d_yaw_c, yaw_c, o_yc); H2DP(b->d_yaw_s, yaw_s, o_ys); }
-      if (n_top) H2DP(b->d_top_x, top_x, o_tx);
-    }
-#define H2D(dst, vec) CS_HIP_TRY(hipMemcpyAsync((dst).p, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st))
-    CS_HIP_TRY(hipMemsetAsync(b->d_job_valid.p, 0, sizeof(int) * nj, st));
-    tm.h2d_ms += now_ms() - t0;
-
-    // ------------------------------------------------------------------ sweep (HIP) ----------
-    cs::DetectDeviceView v{};
-    v.jobs = b->d_jobs.p; v.n_jobs = (int)nj; v.slot_prefix = b->d_slot_prefix.p; v.vp_prefix = b->d_vp_prefix.p;
-    v.maps = b->d_maps.p; v.mid_x = b->d_mid_x.p; v.mid_y = b->d_mid_y.p; v.line_angle = b->d_ang.p;
-    v.yaw = b->d_yaw.p; v.yaw_cos = b->d_yaw_c.p; v.yaw_sin = b->d_yaw_s.p; v.top_x = b->d_top_x.p; v.rp = b->d_rp.p; v.invK = b->d_invK.p;
-    v.vp = b->d_vp.p; v.bound = b->d_bound.p; v.flag = b->d_flag.p;
-    v.job_valid = b->d_job_valid.p; v.job_cbase = b->d_job_cbase.p;
-    CS_HIP_TRY(hipEventRecord(d->ev[6], st));
-    if (dev_setup) {
-      cs::launch_line_setup(b->d_jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, b->d_mid_x.p, b->d_mid_y.p, b->d_ang.p,
-                            P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st);
-    }
-    CS_HIP_TRY(hipEventRecord(d->ev[7], st));
-    if (dev_setup) {
-      // the merged segment counts come back with the results (byte accounting, debug getters)
-      ENS(b->h_jobs, nj);
-      CS_HIP_TRY(hipMemcpyAsync(b->h_jobs.p, b->d_jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
-    }
-    CS_HIP_TRY(hipEventRecord(d->ev[0], st));
-    cs::launch_vp_support(v, sp, vp_total, st);
-    CS_HIP_TRY(hipEventRecord(d->ev[1], st));
-    cs::launch_candidates(v, sp, slot_total, st);
-    CS_HIP_TRY(hipEventRecord(d->ev[2], st));
-    CS_HIP_TRY(hipGetLastError());
-
-    // ------------------------------------------------------------------ rank on the device --------
-    // (no roll/pitch sampling: boxes are independent, so nothing has to come back to the host before the ranking)
-    const bool device_rank = !b->debug && !b->force_host_rank && KMAX <= cs::RANK_KMAX;
-    if (device_rank) {
-      ENS(b->d_c_slot, slot_total + 1); ENS(b->d_c_flag, slot_total + 1); ENS(b->d_c_dist, slot_total + 1); ENS(b->d_c_angle, slot_total + 1); ENS(b->d_c_skew, slot_total + 1);
-      v.c_slot = b->d_c_slot.p; v.c_flag = b->d_c_flag.p; v.c_dist = b->d_c_dist.p; v.c_angle = b->d_c_angle.p; v.c_skew = b->d_c_skew.p;
-      CS_HIP_TRY(hipEventRecord(d->ev[3], st));
-      cs::launch_scan_compact(v, st);
-      CS_HIP_TRY(hipEventRecord(d->ev[8], st));
-      cs::launch_score(v, sp, slot_total, slot_total, st);   // the exact number of valid proposals stays on the device
-      CS_HIP_TRY(hipEventRecord(d->ev[4], st));
-      std::vector<int> box_job0, box_njobs;
-      for (size_t j = 0; j < nj; j++)
-        if (jobs[j].hid == 0) { box_job0.push_back((int)j); box_njobs.push_back(b->frames[jobs[j].frame].n_heights[jobs[j].box]); }
-      const size_t nb = box_job0.size();
-      ENS(b->d_box_job0, nb); ENS(b->d_box_njobs, nb); ENS(b->d_win_count, nb); ENS(b->d_fallback, nb); ENS(b->d_winners, nb * KMAX);
-      ENS(b->h_winners, nb * KMAX); ENS(b->h_win_count, nb); ENS(b->h_fallback, nb); ENS(b->h_job_valid, nj); ENS(b->h_job_cbase, nj + 1);
-      {
-        ENS(b->h_tables2, 2 * sizeof(int) * nb + 128);
-        unsigned char* hb = b->h_tables2.p;
-        const size_t o1 = (sizeof(int) * nb + 63) & ~(size_t)63;
-        H2DP(b->d_box_job0, box_job0, 0); H2DP(b->d_box_njobs, box_njobs, o1);
-      }
-      cs::RankView rv{};
-      rv.box_job0 = b->d_box_job0.p; rv.box_njobs = b->d_box_njobs.p; rv.n_boxes = (int)nb;
-      rv.winners = b->d_winners.p; rv.win_count = b->d_win_count.p; rv.fallback = b->d_fallback.p;
-      if (sample_rp) { ENS(b->d_last_slot, nb); ENS(b->h_last_slot, nb); rv.last_slot = b->d_last_slot.p; }
-      cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, sp.short_sq_bound};
-      cs::launch_rank(v, rv, rkp, st);
-      CS_HIP_TRY(hipEventRecord(d->ev[5], st));
-      CS_HIP_TRY(hipGetLastError());
-      double t_d2h = now_ms();
-      CS_HIP_TRY(hipMemcpyAsync(b->h_winners.p, b->d_winners.p, sizeof(cs::RankWinner) * nb * KMAX, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_win_count.p, b->d_win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_fallback.p, b->d_fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-      if (sample_rp) CS_HIP_TRY(hipMemcpyAsync(b->h_last_slot.p, b->d_last_slot.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_job_cbase.p, b->d_job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipStreamSynchronize(st));
-      tm.d2h_ms += now_ms() - t_d2h;
-      if (dev_setup) for (size_t j = 0; j < nj; j++) jobs[j].m = b->h_jobs.p[j].m;
-      const long long n_valid = b->h_job_cbase.p[nj];
-      tm.n_valid += n_valid;
-      {
-        float ms = 0;
-        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
-        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
-        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
-        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
-        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[4], d->ev[5])); tm.rank_kernel_ms += ms;
-        CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
-        tm.cand_kernel_launches += 1;
-        // algorithmic bytes: geometry kernel = vanishing points read once per (job, rp, yaw) + one flag per slot
-        // (the corners stay in registers); scoring kernel = each distance map once + the vanishing points and the VP support table
-        // once per (job, rp, yaw) + per valid proposal 12 B read (slot id, flag) and 28 B of scores written
-        tm.cand_kernel_bytes += 48LL * vp_total + 4LL * slot_total;
-        long long sbytes = 96LL * vp_total + (28LL + 8LL + 4LL) * n_valid;
-        for (size_t j = 0; j < nj; j++) sbytes += 4LL * jobs[j].map_w * (jobs[j].g.eb - jobs[j].g.et);
-        tm.score_kernel_bytes += sbytes;
-      }
-      // ---- finish on the host: records of the winners; boxes flagged by the kernel are re-ranked exactly
-      t0 = now_ms();
-      auto rows_of = [&](const cs::JobDesc& jd, long long slot, int flag, double de, double ae, double* r9, int* rp_out) {
-        long long local = slot - jd.slot_off;
-        int cfg = (int)(local & 1) + 1;
-        long long rest = local >> 1;
-        int t = (int)(rest % jd.T);
-        int ry = (int)(rest / jd.T);
-        int rp = ry / jd.Y, y = ry - rp * jd.Y;
-        *rp_out = rp;
-        r9[0] = cfg; r9[1] = flag & cs::CAND_VP_MASK; r9[2] = yaw[jd.yaw_off + y]; r9[3] = t; r9[4] = de; r9[5] = ae; r9[6] = jd.down_expand;
-        r9[7] = cam_rp[jd.frame][rp].pose.roll; r9[8] = cam_rp[jd.frame][rp].pose.pitch;
-      };
-      // columns of every flagged box, fetched with one gather + one copy per column
-      std::vector<long long> fb_src, fb_dst;
-      std::vector<int> fb_cnt, fb_range_of_job(nj, -1);
-      std::vector<double> fb_dist, fb_angle, fb_skew;
-      std::vector<int> fb_flag;
-      std::vector<long long> fb_slot;
-      {
-        long long tot = 0;
-        for (size_t q = 0; q < nb; q++)
-          if (b->h_fallback.p[q])
-            for (int h = 0; h < box_njobs[q]; h++) {
-              int j = box_job0[q] + h;
-              fb_range_of_job[j] = (int)fb_src.size();
-              fb_src.push_back(b->h_job_cbase.p[j]); fb_cnt.push_back(b->h_job_valid.p[j]); fb_dst.push_back(tot);
-              tot += b->h_job_valid.p[j];
-            }
-        if (!fb_src.empty()) {
-          size_t nr = fb_src.size();
-          ENS(b->d_fb_src, nr); ENS(b->d_fb_dst, nr); ENS(b->d_fb_cnt, nr);
-          ENS(b->d_fb_dist, tot + 1); ENS(b->d_fb_angle, tot + 1); ENS(b->d_fb_skew, tot + 1); ENS(b->d_fb_flag, tot + 1); ENS(b->d_fb_slot, tot + 1);
-          H2D(b->d_fb_src, fb_src); H2D(b->d_fb_dst, fb_dst); H2D(b->d_fb_cnt, fb_cnt);
-          cs::launch_gather_ranges(v, b->d_fb_src.p, b->d_fb_cnt.p, b->d_fb_dst.p, (int)nr, b->d_fb_dist.p, b->d_fb_angle.p, b->d_fb_skew.p, b->d_fb_flag.p, b->d_fb_slot.p, st);
-          fb_dist.resize(tot); fb_angle.resize(tot); fb_skew.resize(tot); fb_flag.resize(tot); fb_slot.resize(tot);
-          if (tot) {
-            CS_HIP_TRY(hipMemcpyAsync(fb_dist.data(), b->d_fb_dist.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            CS_HIP_TRY(hipMemcpyAsync(fb_angle.data(), b->d_fb_angle.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            CS_HIP_TRY(hipMemcpyAsync(fb_skew.data(), b->d_fb_skew.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            CS_HIP_TRY(hipMemcpyAsync(fb_flag.data(), b->d_fb_flag.p, 4 * (size_t)tot, hipMemcpyDeviceToHost, st));
-            CS_HIP_TRY(hipMemcpyAsync(fb_slot.data(), b->d_fb_slot.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-          }
-          CS_HIP_TRY(hipStreamSynchronize(st));
-        }
-      }
-      std::vector<std::vector<cs::RankWinner>> fb_winners(nb);
-      int hip_err = 0;
-      auto finish_box = [&](size_t q, int phase) -> int {
-        const int j0 = box_job0[q], nh = box_njobs[q];
-        const int f = jobs[j0].frame, bi = jobs[j0].box;
-        const FrameIn& F = b->frames[f];
-        const double* bb = &F.boxes[5 * bi];
-        std::vector<cs::RankWinner> wl;
-        // cam_pose.camera_yaw as the next box of this frame reads it (:180): the reference's last set_cam_pose() of this box is
-        // the one for the last kept proposal of the last height sample (:727-737), or, when nothing was kept, the sweep's last
-        // (roll, pitch) sample (:368-377).  (One box per frame and round: no two workers write the same entry.)
-        auto carry_yaw = [&](long long last_slot) {
-          const cs::JobDesc& jl = jobs[j0 + nh - 1];
-          if (last_slot < 0) { cur_yaw[f] = cam_rp[f].back().cam_yaw; return; }
-          const long long ry = ((last_slot - jl.slot_off) >> 1) / jl.T;
-          cur_yaw[f] = cam_rp[f][(size_t)(ry / jl.Y)].cam_yaw;
-        };
-        if (!b->h_fallback.p[q]) {
-          if (sample_rp && phase == 0) carry_yaw(b->h_last_slot.p[q]);
-          for (int r = 0; r < b->h_win_count.p[q]; r++) wl.push_back(b->h_winners.p[q * KMAX + r]);
-        } else if (phase == 1) {
-          wl = fb_winners[q];
-        } else {
-          struct HP { int h, cand; double score, skew; };
-          std::vector<HP> props;
-          std::vector<std::vector<double>> hd(nh), ha(nh), hs(nh);
-          std::vector<std::vector<int>> hf(nh);
-          std::vector<std::vector<long long>> hsl(nh);
-          for (int h = 0; h < nh; h++) {
-            int j = j0 + h;
-            int V = b->h_job_valid.p[j];
-            long long p0 = fb_dst[fb_range_of_job[j]];
-            hd[h].assign(fb_dist.begin() + p0, fb_dist.begin() + p0 + V); ha[h].assign(fb_angle.begin() + p0, fb_angle.begin() + p0 + V);
-            hs[h].assign(fb_skew.begin() + p0, fb_skew.begin() + p0 + V); hf[h].assign(fb_flag.begin() + p0, fb_flag.begin() + p0 + V);
-            hsl[h].assign(fb_slot.begin() + p0, fb_slot.begin() + p0 + V);
-            std::vector<int> keep;
-            std::vector<double> score;
-            fuse_scores(hd[h].data(), ha[h].data(), V, P.weight_vp_angle, keep, score);
-            if (sample_rp && h == nh - 1) carry_yaw(keep.empty() ? -1 : hsl[h][keep.back()]);
-            for (size_t z = 0; z < keep.size(); z++) {
-              if (hf[h][keep[z]] & cs::CAND_NEG_SCALE) continue;
-              props.push_back(HP{h, keep[z], score[z], hs[h][keep[z]]});
-            }
-          }
-          int n = (int)props.size(), kk = std::min(KMAX, n);
-          std::vector<double> comb(n);
-          for (int i = 0; i < n; i++) {
-            double skew_error = P.weight_skew_error * std::max(props[i].skew - P.nominal_skew_ratio, 0.0);
-            if (props[i].skew > P.max_cut_skew) skew_error = 100;
-            comb[i] = props[i].score + P.weight_skew_error * skew_error;
-          }
-          std::vector<int> idx(n);
-          std::iota(idx.begin(), idx.end(), 0);
-          std::partial_sort(idx.begin(), idx.begin() + kk, idx.end(), [&comb](int a, int c) { return comb[a] < comb[c]; });
-          for (int r = 0; r < kk; r++) {
-            const HP& hp = props[idx[r]];
-            cs::RankWinner w{};
-            w.slot = hsl[hp.h][hp.cand]; w.normalized_error = hp.score; w.dist_err = hd[hp.h][hp.cand]; w.angle_err = ha[hp.h][hp.cand];
-            w.flag = hf[hp.h][hp.cand] & cs::CAND_VP_MASK;
-            wl.push_back(w);  // corners fetched below, in one gather for all fallback winners
-          }
-          fb_winners[q] = wl;
-          return CS_OK;
-        }
-        for (size_t r = 0; r < wl.size(); r++) {
-          const cs::RankWinner& w = wl[r];
-          int h = 0;
-          while (h + 1 < nh && w.slot >= jobs[j0 + h + 1].slot_off) h++;
-          double r9[9];
-          int rpi = 0;
-          rows_of(jobs[j0 + h], w.slot, w.flag, w.dist_err, w.angle_err, r9, &rpi);
-          cs_cuboid& o = out[((size_t)f * MB + bi) * KMAX + r];
-          finish_cuboid(F, cam_rp[f][rpi].pose, r9, w.corners, cam_raw[f].euler, sample_rp, w.normalized_error, o);
-          o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
-        }
-        out_counts[(size_t)f * MB + bi] = (int)wl.size();
-        return CS_OK;
-      };
-      parallel_for((int)nb, NT, [&](int q) { (void)finish_box((size_t)q, 0); });  // flagged boxes: exact host ranking only
-      {
-        std::vector<long long> ws;
-        for (size_t q = 0; q < nb; q++) { if (b->h_fallback.p[q]) { tm.n_fallback_boxes++; for (auto& w : fb_winners[q]) ws.push_back(w.slot); } }
-        if (!ws.empty()) {
-          ENS(b->d_win_slots, ws.size()); ENS(b->d_win_corners, 16 * ws.size()); ENS(b->h_win_corners, 16 * ws.size());
-          H2D(b->d_win_slots, ws);
-          cs::launch_gather_corners(v, sp, b->d_win_slots.p, (int)ws.size(), b->d_win_corners.p, st);
-          CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * ws.size(), hipMemcpyDeviceToHost, st));
-          CS_HIP_TRY(hipStreamSynchronize(st));
-          size_t z = 0;
-          for (size_t q = 0; q < nb; q++)
-            if (b->h_fallback.p[q])
-              for (auto& w : fb_winners[q]) { std::memcpy(w.corners, b->h_win_corners.p + 16 * z, 128); z++; }
-        }
-        parallel_for((int)nb, NT, [&](int q) { if (b->h_fallback.p[q]) (void)finish_box((size_t)q, 1); });
-      }
-      if (hip_err) return hip_err;
-      tm.finalize_ms += now_ms() - t0;
-      continue;
-    }
-    // valid counts -> host -> size the compact arrays
-    ENS(b->h_job_valid, nj); ENS(b->h_job_cbase, nj + 1);
-    CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-    CS_HIP_TRY(hipStreamSynchronize(st));
-    if (dev_setup) for (size_t j = 0; j < nj; j++) jobs[j].m = b->h_jobs.p[j].m;
-    long long n_valid = 0;
-    for (size_t j = 0; j < nj; j++) { b->h_job_cbase.p[j] = n_valid; n_valid += b->h_job_valid.p[j]; }
-    b->h_job_cbase.p[nj] = n_valid;
-    tm.n_valid += n_valid;
-    ENS(b->d_c_slot, n_valid + 1); ENS(b->d_c_flag, n_valid + 1); ENS(b->d_c_dist, n_valid + 1); ENS(b->d_c_angle, n_valid + 1); ENS(b->d_c_skew, n_valid + 1);
-    v.c_slot = b->d_c_slot.p; v.c_flag = b->d_c_flag.p; v.c_dist = b->d_c_dist.p; v.c_angle = b->d_c_angle.p; v.c_skew = b->d_c_skew.p;
-    CS_HIP_TRY(hipEventRecord(d->ev[3], st));
-    cs::launch_scan_compact(v, st);
-    CS_HIP_TRY(hipEventRecord(d->ev[8], st));
-    cs::launch_score(v, sp, n_valid, slot_total, st);
-    CS_HIP_TRY(hipEventRecord(d->ev[4], st));
-    CS_HIP_TRY(hipGetLastError());
-    ENS(b->h_c_slot, n_valid + 1); ENS(b->h_c_flag, n_valid + 1); ENS(b->h_c_dist, n_valid + 1); ENS(b->h_c_angle, n_valid + 1); ENS(b->h_c_skew, n_valid + 1);
-    double t_d2h = now_ms();
-    if (n_valid) {
-      CS_HIP_TRY(hipMemcpyAsync(b->h_c_slot.p, b->d_c_slot.p, sizeof(long long) * n_valid, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_c_flag.p, b->d_c_flag.p, sizeof(int) * n_valid, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_c_dist.p, b->d_c_dist.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_c_angle.p, b->d_c_angle.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(b->h_c_skew.p, b->d_c_skew.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-    }
-    CS_HIP_TRY(hipStreamSynchronize(st));
-    tm.d2h_ms += now_ms() - t_d2h;
-    {
-      float ms = 0;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
-      tm.cand_kernel_launches += 1;
-      // algorithmic bytes of the candidate kernel: maps + line arrays + vp/bound read once,
-      // 200 B written per valid proposal, 4 B flag per slot
-      // algorithmic bytes: as above
-      tm.cand_kernel_bytes += 48LL * vp_total + 4LL * slot_total;
-      long long sbytes = 96LL * vp_total + (28LL + 8LL + 4LL) * n_valid;
-      for (size_t j = 0; j < nj; j++) sbytes += 4LL * jobs[j].map_w * (jobs[j].g.eb - jobs[j].g.et);
-      tm.score_kernel_bytes += sbytes;
-    }
-
-    // ------------------------------------------------------------------ rank (host) ----------
-    t0 = now_ms();
-    size_t res_base = b->results.size();
-    b->results.resize(res_base + nj);
-    parallel_for((int)nj, NT, [&](int j) {
-      const cs::JobDesc& jd = jobs[j];
-      JobResult& R = b->results[res_base + j];
-      R.frame = jd.frame; R.box = jd.box; R.hid = jd.hid;
-      long long c0 = b->h_job_cbase.p[j];
-      int V = b->h_job_valid.p[j];
-      R.n_valid = V;
-      R.rows9.resize(9 * (size_t)V);
-      R.slots.assign(b->h_c_slot.p + c0, b->h_c_slot.p + c0 + V);
-      R.rp_idx.resize(V);
-      const cs::RpPose* rpp = nullptr;
-      for (int i = 0; i < V; i++) {
-        long long local = R.slots[i] - jd.slot_off;
-        int cfg = (int)(local & 1) + 1;
-        long long rest = local >> 1;
-        int t = (int)(rest % jd.T);
-        int ry = (int)(rest / jd.T);
-        int rp = ry / jd.Y, y = ry - rp * jd.Y;
-        rpp = &cam_rp[jd.frame][rp].pose;
-        R.rp_idx[i] = rp;
-        double* r9 = &R.rows9[9 * (size_t)i];
-        r9[0] = cfg; r9[1] = b->h_c_flag.p[c0 + i] & cs::CAND_VP_MASK; r9[2] = yaw[jd.yaw_off + y]; r9[3] = t;
-        r9[4] = b->h_c_dist.p[c0 + i]; r9[5] = b->h_c_angle.p[c0 + i]; r9[6] = jd.down_expand;
-        r9[7] = rpp->roll; r9[8] = rpp->pitch;
-      }
-      fuse_scores(b->h_c_dist.p + c0, b->h_c_angle.p + c0, V, P.weight_vp_angle, R.keep, R.score);
-    });
-    for (size_t j = 0; j < nj; j++) b->job_index[((size_t)jobs[j].frame * MB + jobs[j].box) * 3 + jobs[j].hid] = (int)(res_base + j);
-
-    // per box: proposals over its height samples (in order), final ranking (:804-838)
-    std::vector<std::pair<int, int>> round_boxes;  // (frame, box)
-    for (size_t j = 0; j < nj; j++)
-      if (jobs[j].hid == 0) round_boxes.emplace_back(jobs[j].frame, jobs[j].box);
-    std::vector<std::vector<Winner>> win_per_box(round_boxes.size());
-    parallel_for((int)round_boxes.size(), NT, [&](int q) {
-      int f = round_boxes[q].first, bi = round_boxes[q].second;
-      const FrameIn& F = b->frames[f];
-      std::vector<Proposal> props;
-      int last_ri = -1;
-      for (int k = 0; k < F.n_heights[bi]; k++) {
-        int ri = b->job_index[((size_t)f * MB + bi) * 3 + k];
-        if (ri < 0) continue;
-        last_ri = ri;
-        const JobResult& R = b->results[ri];
-        long long c0 = b->h_job_cbase.p[ri - res_base];
-        for (size_t q2 = 0; q2 < R.keep.size(); q2++) {
-          int cand = R.keep[q2];
-          if (b->h_c_flag.p[c0 + cand] & cs::CAND_NEG_SCALE) continue;  // :766
-          props.push_back(Proposal{ri, cand, R.score[q2], b->h_c_skew.p[c0 + cand]});
-        }
-      }
-      if (sample_rp && last_ri >= 0) {
-        // cam_pose.camera_yaw as the next box of this frame reads it (:180): the reference's last
-        // set_cam_pose() of this box is the one for the last kept proposal of the last height sample
-        // (:727-737), or, when nothing was kept, the sweep's last (roll, pitch) sample (:368-377).
-        const JobResult& R = b->results[last_ri];
-        if (!R.keep.empty()) cur_yaw[f] = cam_rp[f][R.rp_idx[R.keep.back()]].cam_yaw;
-        else cur_yaw[f] = cam_rp[f].back().cam_yaw;
-      }
-      int n = (int)props.size();
-      int kk = std::min(KMAX, n);
-      std::vector<double> comb(n);
-      for (int i = 0; i < n; i++) {
-        double skew_error = P.weight_skew_error * std::max(props[i].skew - P.nominal_skew_ratio, 0.0);
-        if (props[i].skew > P.max_cut_skew) skew_error = 100;
-        comb[i] = props[i].normalized_error + P.weight_skew_error * skew_error;  // weight applied twice (:813,:820)
-      }
-      std::vector<int> idx(n);
-      std::iota(idx.begin(), idx.end(), 0);
-      std::partial_sort(idx.begin(), idx.begin() + kk, idx.end(), [&comb](int a, int c) { return comb[a] < comb[c]; });
-      for (int r = 0; r < kk; r++) {
-        const Proposal& p = props[idx[r]];
-        win_per_box[q].push_back(Winner{f, bi, r, p.res_idx, p.cand, p.normalized_error, p.skew});
-      }
-    });
-    size_t w0 = winners.size();
-    for (auto& wv : win_per_box) winners.insert(winners.end(), wv.begin(), wv.end());
-    tm.rank_host_ms += now_ms() - t0;
-
-    // ------------------------------------------------------------------ finish ---------------
-    t0 = now_ms();
-    size_t nw = winners.size() - w0;
-    std::vector<long long> wslots(nw);
-    for (size_t i = 0; i < nw; i++) wslots[i] = b->results[winners[w0 + i].res_idx].slots[winners[w0 + i].cand];
-    // debug: corners of every valid candidate of this round
-    size_t n_gather = nw + (b->debug ? (size_t)n_valid : 0);
-    if (b->debug) wslots.insert(wslots.end(), b->h_c_slot.p, b->h_c_slot.p + n_valid);
-    if (n_gather) {
-      ENS(b->d_win_slots, n_gather); ENS(b->d_win_corners, 16 * n_gather); ENS(b->h_win_corners, 16 * n_gather);
-      CS_HIP_TRY(hipMemcpyAsync(b->d_win_slots.p, wslots.data(), sizeof(long long) * n_gather, hipMemcpyHostToDevice, st));
-      cs::launch_gather_corners(v, sp, b->d_win_slots.p, (int)n_gather, b->d_win_corners.p, st);
-      CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * n_gather, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipStreamSynchronize(st));
-    }
-    for (size_t i = 0; i < nw; i++) {
-      const Winner& w = winners[w0 + i];
-      const JobResult& R = b->results[w.res_idx];
-      const FrameIn& F = b->frames[w.frame];
-      const double* r9 = &R.rows9[9 * (size_t)w.cand];
-      const cs::RpPose* pose = &cam_rp[w.frame][R.rp_idx[w.cand]].pose;
-      cs_cuboid& o = out[((size_t)w.frame * MB + w.box) * KMAX + w.rank];
-      finish_cuboid(F, *pose, r9, b->h_win_corners.p + 16 * i, cam_raw[w.frame].euler, sample_rp, w.normalized_error, o);
-      const double* bb = &F.boxes[5 * w.box];
-      o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
-      out_counts[(size_t)w.frame * MB + w.box] = std::max(out_counts[(size_t)w.frame * MB + w.box], w.rank + 1);
-    }
-    if (b->debug) {
-      for (size_t j = 0; j < nj; j++) {
-        JobResult& R = b->results[res_base + j];
-        long long c0 = b->h_job_cbase.p[j];
-        R.corners.assign(b->h_win_corners.p + 16 * (nw + c0), b->h_win_corners.p + 16 * (nw + c0 + R.n_valid));
-      }
-    }
-    tm.finalize_ms += now_ms() - t0;
+    RoundTables T;
+    if ((rc = round_setup(X, round, T))) return rc;
+    if (T.nj == 0) continue;
+    if ((rc = round_upload(X, T)) || (rc = round_sweep(X, T)) || (rc = device_rank ? round_rank_device(X, T) : round_rank_host(X, T))) return rc;
   }
   tm.total_ms = now_ms() - t_begin;
   b->timing = tm;
@@ -2826,7 +2536,6 @@ int cs_edge_distance_maps_multi(cs_detector* d, const unsigned char* const* gray
       CS_HIP_TRY(hipMemcpyAsync(out_maps[k], d_map.p + er[k].map_off, sizeof(float) * (size_t)er[k].w * er[k].h, hipMemcpyDeviceToHost, st));
   CS_HIP_TRY(hipStreamSynchronize(st));
   if (kernel_ms) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); *kernel_ms = ms; }
-  d_gray.release(); d_cls.release(); d_rois.release(); d_map.release();
   return CS_OK;
   CS_GUARD_END("cs_edge_distance_maps")
 }

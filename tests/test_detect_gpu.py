@@ -385,6 +385,34 @@ def test_roll_pitch_rounds_queued_at_once_equal_the_round_by_round_path(heights,
     lean.close(); ref.close(); det.close()
 
 
+@pytest.mark.parametrize("sample_rp", [0, 1])
+def test_every_caller_of_the_exact_ranking_agrees_on_the_same_ties(sample_rp):
+    """The exact host ranking (exact_rank_box, detect_rank_host.h) has four callers: the lean pipeline's tie boxes, the lean roll/pitch
+    path's, the round path's device-ranked tie boxes and the round path's host ranking of every box.  Two frames whose maps are all zero
+    (every cut of every box a tie: the order std::partial_sort leaves decides the records) and an ordinary frame go through all of them:
+    the same bytes, two cuboids per box."""
+    frames = []
+    for s in range(2):
+        fr = synth.make_frame(9100 + s, n_boxes=3, n_lines=200)
+        fr["maps"] = [[np.zeros_like(m) for m in mm] for mm in fr["maps"]]
+        frames.append(fr)
+    frames.append(synth.make_frame(9102, n_boxes=3, n_lines=200))
+    det = capi.Detector(capi.default_params(whether_sample_cam_roll_pitch=sample_rp, yaw_step_deg=6.0, max_cuboid_num=2))
+    modes = [dict(), dict(force_no_pipeline=True), dict(force_host_rank=True)] + ([] if sample_rp else [dict(pipeline_chunks=2)])
+    ref = None
+    for kw in modes:
+        bat = capi.Batch(det, frames, **kw)
+        bat.run()
+        got = (bat.raw_out_bytes(), bat.counts_bytes())
+        if "force_host_rank" not in kw:
+            assert bat.timing()["n_fallback_boxes"] >= 6, kw
+        bat.close()
+        if ref is None:
+            ref = got
+        assert got[0] == ref[0] and got[1] == ref[1], kw
+    det.close()
+
+
 def test_full_size_c2_batch_against_oracle_sample_and_properties():
     """BASELINE.json's C2 at the bench's full batch size (1000 frames x 8 boxes x 181 yaw x ~400 segments, 31.5 M
     proposal slots per run): (a) 48 frames drawn from the batch are bit-identical to the oracle's records,
