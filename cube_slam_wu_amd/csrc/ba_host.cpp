@@ -12,13 +12,11 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <limits>
 #include <memory>
 #include <string>
@@ -29,6 +27,7 @@
 
 #include "../../include/cubeslam_hip.h"
 #include "ba_edge_class.h"
+#include "ba_structure.h"
 #include "ba_types.h"
 #include "band_solver.h"
 #include "cs_hip_util.h"
@@ -127,7 +126,6 @@ struct DBuf {
     return CS_OK;
   }
   int upload(const std::vector<T>& h) { return upload_ptr(h.data(), h.size()); }
-  int upload_staged(const std::vector<T>& h, StageArena& stage, hipStream_t st) { return upload_ptr_staged(h.data(), h.size(), stage, st); }
   int upload_ptr_staged(const T* h, size_t count, StageArena& stage, hipStream_t st) {   // up to 1 MB: through the pinned arena, queued on st (a blocking copy from pageable memory costs 50-100 us)
     const size_t bytes = count * sizeof(T);
     void* pin = (bytes && bytes <= (1u << 20)) ? stage.take(bytes) : nullptr;
@@ -170,25 +168,7 @@ struct DBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; cap = 0; }
 };
 
-// Host scratch of the structure phase: UNINITIALISED storage (std::vector<int>(n) zero-fills on the constructing thread, which takes the
-// page faults of a fresh multi-megabyte array one by one; the worker threads that fill these arrays then fault their own ranges side by side)
-template <class T>
-struct UBuf {
-  std::unique_ptr<T[]> p;
-  size_t n = 0, cap = 0;
-  UBuf() {}
-  explicit UBuf(size_t m) : p(new T[std::max<size_t>(1, m)]), n(m), cap(std::max<size_t>(1, m)) {}
-  // a buffer kept on the handle between structure phases: the same (already faulted-in) memory again, grown with head room -- a fresh
-  // 400 KB array is ~100 page faults, 0.1-0.2 ms on the thread that fills it; contents are NOT kept when it grows
-  void ensure(size_t m) { if (m > cap || !p) { cap = m + m / 4 + 1024; p.reset(new T[cap]); } n = m; }
-  T& operator[](size_t i) { return p[i]; }
-  const T& operator[](size_t i) const { return p[i]; }
-  T* begin() { return p.get(); }
-  const T* begin() const { return p.get(); }
-  T* data() { return p.get(); }
-  const T* data() const { return p.get(); }
-  size_t size() const { return n; }
-};
+using cs::UBuf;    // (host scratch of the structure phase: ba_structure.h)
 
 }  // namespace
 
@@ -366,120 +346,18 @@ struct cs_ba {
 
 namespace {
 
-// The structure phase's threaded loops (seven or eight short bursts of <= 8 items): a process-wide set of seven parked threads instead of
-// 8 x std::thread per burst (20-30 us each to create and join: over a millisecond of the phase at a million edges).  One user at a time;
-// a second handle building its structure at the same moment (the sharded tests' rank threads) falls back to plain threads.
-class StructPool {
- public:
-  static StructPool& get() { static StructPool p; return p; }
-  bool try_run(int n, const std::function<void(int)>& fn) {
-    std::unique_lock<std::mutex> use(use_, std::try_to_lock);
-    if (!use.owns_lock()) return false;
-    if (th_.empty()) for (int i = 0; i < 7; i++) th_.emplace_back([this] { loop(); });
-    fn_ = &fn; n_ = n; next_.store(0); pending_.store((int)th_.size());
-    gen_.fetch_add(1);                                   // (publishes fn_ / n_ / next_ / pending_ to the workers)
-    if (sleepers_.load() > 0) { std::lock_guard<std::mutex> lk(m_); cv_.notify_all(); }
-    work();
-    // every worker acknowledges the burst (fn must outlive their last look at it): the hot ones within a microsecond, a parked one after its wake-up
-    for (int spins = 0; pending_.load(std::memory_order_acquire) != 0; spins++) { if (spins < 2000) cpu_relax(); else std::this_thread::yield(); }
-    fn_ = nullptr;
-    return true;
-  }
-  ~StructPool() {
-    stop_.store(true); gen_.fetch_add(1);
-    { std::lock_guard<std::mutex> lk(m_); cv_.notify_all(); }
-    for (auto& t : th_) t.join();
-  }
- private:
-  static void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#else
-    std::this_thread::yield();
-#endif
-  }
-  void work() { for (;;) { const int i = next_.fetch_add(1); if (i >= n_) break; (*fn_)(i); } }
-  // A worker can stay hot for SPIN_US after a burst (CS_BA_POOL_SPIN_US; the structure phase is seven or eight bursts inside 1-2 ms, and
-  // waking a parked thread is 20-40 us of the calling thread's wait each time) before it parks on the condition variable.  Default 0: on the
-  // measurement boxes (a 16-CPU cgroup quota) seven spinning threads bought nothing -- 1.2 ms per appended frame at 200 cameras either way --
-  // and their burnt quota came back as 5 ms throttling stalls in one frame out of ten.
-  void loop() {
-    unsigned long long seen = 0;
-    for (;;) {
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int spins = 0; gen_.load(std::memory_order_acquire) == seen; spins++) {
-        cpu_relax();
-        if ((spins & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(SPIN_US)) {
-          std::unique_lock<std::mutex> lk(m_);
-          sleepers_.fetch_add(1);                        // (seq_cst against try_run's gen_ increment + sleepers_ read: one of the two sees the other)
-          cv_.wait(lk, [&] { return gen_.load() != seen; });
-          sleepers_.fetch_sub(1);
-          break;
-        }
-      }
-      seen = gen_.load(std::memory_order_acquire);
-      if (stop_.load()) return;
-      work();
-      pending_.fetch_sub(1, std::memory_order_release);
-    }
-  }
-  const int SPIN_US = [] { const char* e = getenv("CS_BA_POOL_SPIN_US"); return e ? atoi(e) : 0; }();
-  std::vector<std::thread> th_;
-  std::mutex use_, m_;
-  std::condition_variable cv_;
-  const std::function<void(int)>* fn_ = nullptr;
-  std::atomic<int> next_{0}, pending_{0}, sleepers_{0};
-  int n_ = 0;
-  std::atomic<unsigned long long> gen_{0};
-  std::atomic<bool> stop_{false};
-};
-// threads of a structure-phase burst: min(8, hardware threads), or fewer with CS_BA_STRUCT_THREADS (= 1: every loop on the calling thread --
-// tests hold the threaded tables to the sequential ones, cs_ba_structure_digest)
-inline int struct_threads() {
-  static const int cap = [] { const char* e = getenv("CS_BA_STRUCT_THREADS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
-  return (int)std::max(1u, std::min((unsigned)cap, std::thread::hardware_concurrency()));
-}
-// items 0 .. n - 1 side by side (n <= 8 in the structure phase)
-inline void run_items(int n, const std::function<void(int)>& fn) {
-  if (n <= 1) { if (n == 1) fn(0); return; }
-  if (StructPool::get().try_run(n, fn)) return;
-  std::vector<std::thread> th;
-  for (int t = 0; t < n; t++) th.emplace_back(fn, t);
-  for (auto& t : th) t.join();
-}
+using cs::cam_rank;
+using cs::landmark_owners;
+using cs::run_items;
+using cs::struct_threads;
 
-// std::sort on chunks in a few host threads, then pairwise merges (the structure phase's large sorts)
-template <class It, class Cmp>
-void parallel_sort(It b, It e, Cmp cmp, int nt) {
-  const size_t n = (size_t)(e - b);
-  if (nt <= 1 || n < 50000) { std::sort(b, e, cmp); return; }
-  std::vector<size_t> cut(nt + 1);
-  for (int t = 0; t <= nt; t++) cut[t] = n * t / nt;
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++) th.emplace_back([&, t] { std::sort(b + cut[t], b + cut[t + 1], cmp); });
-    for (auto& t : th) t.join();
-  }
-  for (int step = 1; step < nt; step *= 2) {
-    std::vector<std::thread> th;
-    for (int t = 0; t + step < nt; t += 2 * step)
-      th.emplace_back([&, t] { std::inplace_merge(b + cut[t], b + cut[t + step], b + cut[std::min(nt, t + 2 * step)], cmp); });
-    for (auto& t : th) t.join();
-  }
-}
+// `call` returns a CS_* code: pass a failure on
+#define CS_TRY(call) do { if (int _rc = (call)) return _rc; } while (0)
 
-// camera -> rank (contiguous subsequences), landmark -> rank of the subsequence of its lowest-index observing camera
-inline int cam_rank(int cam, int n_cams, int n_ranks) { return (int)(((long long)cam * n_ranks) / std::max(1, n_cams)); }
 // The per-landmark camera lists of the last structure phase (st_cams_of / st_edge_of, st_cam_cnt) stay valid only while the projection edges
 // [0, st_lists_edges) and the landmark count they were built for are untouched -- cs_ba_append_* only adds behind them.  EVERY entry point that
 // rewrites e_pt / e_cam or the vertex arrays calls this, so that the next phase checks every edge's indices again and rebuilds the lists.
 inline void proj_edge_lists_invalidate(cs_ba* B) { B->st_lists_edges = 0; B->st_cam_cnt.clear(); }
-void landmark_owners(int n_ranks, int n_cams, int n_points, int n_proj, const int* e_pt, const int* e_cam, std::vector<int>& owner) {
-  std::vector<int> first(n_points, 0x7fffffff);
-  for (int k = 0; k < n_proj; k++) if (e_pt[k] >= 0 && e_pt[k] < n_points) first[e_pt[k]] = std::min(first[e_pt[k]], e_cam[k]);
-  owner.assign(n_points, 0);
-  for (int p = 0; p < n_points; p++) owner[p] = (first[p] == 0x7fffffff) ? 0 : cam_rank(first[p], n_cams, n_ranks);
-}
 
 // the host's level vectors from the device's bytes, after a classification there (the layout is that of the structure phase that filled d_lvl)
 int refresh_levels_host(cs_ba* B) {
@@ -522,482 +400,41 @@ void fold_pose_levels(const cs_ba* B, std::vector<int>& ca, std::vector<int>& oa
   for (size_t k = 0; k < oa.size(); k++) if (k < lo.size() && lo[k]) oa[k] = 0;
 }
 
-int finalize_structure(cs_ba* B) {
-  if (!B->structure_dirty) return CS_OK;
-  struct Clock { cs_ba* b; double t0; ~Clock() { b->tm.structure_ms += now_ms() - t0; } } clock{B, now_ms()};
-  CS_HIP_TRY(hipSetDevice(B->device));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));             // nothing of an earlier call may still read the buffers (or the staging arena) reused below
-  { const int rl = refresh_levels_host(B); if (rl) return rl; }      // (levels a classification left on the device survive this phase through the host's copy)
-  B->pm_cm_valid = false;
-  { const int rc0 = B->stage.begin((size_t)8 << 20); if (rc0) return rc0; }
-  static const bool prof = getenv("CS_BA_PROF") != nullptr;   // diagnostics: host phase clock of the structure phase
+// diagnostics (CS_BA_PROF): host phase clock of the structure phase, with the device allocations so far
+struct PhaseMarks {
+  const bool on = [] { static const bool prof = getenv("CS_BA_PROF") != nullptr; return prof; }();
   double t_ph = now_ms();
-  auto mark = [&](const char* what) { if (prof) { double t = now_ms(); fprintf(stderr, "[ba structure] %-28s %8.2f ms   (%d device allocations so far)\n", what, t - t_ph, g_dbuf_reallocs); t_ph = t; } };
-  const int nc = B->nc, no = B->no, np = B->np;
-  // camera-cuboid edges of both kinds as one list: EdgeSE3Cuboid first, then EdgeSE3CuboidProj
-  const cs::EdgeClassHost &c3 = B->pose_class(CS_EDGE_CUBOID), &cp = B->pose_class(CS_EDGE_CUBOID_PROJ), &od = B->pose_class(CS_EDGE_ODOM);
-  const std::vector<int>&oe_i = od.a, &oe_j = od.b;
-  B->ce_cam = c3.a; B->ce_cam.insert(B->ce_cam.end(), cp.a.begin(), cp.a.end());
-  B->ce_cub = c3.b; B->ce_cub.insert(B->ce_cub.end(), cp.b.begin(), cp.b.end());
-  B->n_cub3 = c3.size();
-  B->n_cub = (int)B->ce_cam.size();
-  B->n_odom = od.size();
-  // ---- index mapping (sparse_optimizer.cpp:166-190): non-marginalised vertices by id, then the points
-  B->cam_col_ref.assign(nc, -1); B->cub_col_ref.assign(no, -1); B->pt_lm.assign(np, -1);
-  {
-    int col = 0;
-    auto do_cams = [&]() { for (int i = 0; i < nc; i++) if (!B->cam_fixed[i]) { B->cam_col_ref[i] = col; col += 6; } };
-    auto do_cubs = [&]() { for (int i = 0; i < no; i++) if (!B->cub_fixed[i]) { B->cub_col_ref[i] = col; col += 9; } };
-    if (B->cuboids_first) { do_cubs(); do_cams(); } else { do_cams(); do_cubs(); }
-    B->n_pose = col;
-  }
-  // ---- the free landmarks grouped by the set of cameras that see them.  cams_of: every landmark's cameras sorted by id;
-  // gorder: free landmarks with >= 1 edge sorted by (number of cameras, camera list); run_first: where each distinct set starts
-  // (edges that an earlier phase of this handle has seen were checked then, and append only raises nc / np)
-  for (int k = std::min(B->st_lists_edges, B->n_proj); k < B->n_proj; k++)
-    if (B->e_pt[k] < 0 || B->e_pt[k] >= np || B->e_cam[k] < 0 || B->e_cam[k] >= nc) { cs_set_error("projection edge index out of range"); return CS_ERR_INVALID_ARG; }
-  mark("  checks, index mapping");
-  std::vector<int> cam_cnt(np + 1, 0), gorder, run_first;
-  // edges grouped by landmark: camera (sorted by id) and caller edge index
-  const int st_nb = 1 - B->st_cur;
-  UBuf<int>& cams_of = B->st_cams_of[st_nb]; UBuf<int>& edge_of = B->st_edge_of[st_nb];
-  cams_of.ensure((size_t)B->n_proj); edge_of.ensure((size_t)B->n_proj);
-  {
-    {   // a counting sort of the edges by landmark (the edge order inside a landmark stays the caller's), then every landmark's camera list
-        // sorted, its edges with it.  Threaded in two levels: the edges are first dealt into landmark ranges (thread t walks its share of the
-        // edges and appends to its own list per range), then range r's thread counts, fills and sorts from the lists of its range only --
-        // every edge is read three times in all, every write (and the page faults of the two fresh arrays) is partitioned.  (First form: one
-        // thread counted all edges, then every thread scanned ALL edges for those of its landmarks -- 5.9 ms at a million edges.)
-      // A graph that was only APPENDED to since the last structure phase (cs_ba_append_*): the lists of that phase are kept on the handle, every
-      // landmark's old list is copied, its new edges follow in the caller's order, and the same stable insertion sort runs over the landmarks
-      // that got edges -- the same lists as the counting sort below gives (old edges precede new ones in the caller's order), in one linear
-      // pass instead of three (200 cameras / 100 k edges, a frame of 500 edges appended: 0.28 -> 0.08 ms).
-      const int E0 = B->st_lists_edges, np0 = (int)B->st_cam_cnt.size() - 1;
-      const bool grown = E0 > 0 && np0 >= 0 && np0 <= np && E0 <= B->n_proj && (B->n_proj - E0) <= E0 / 4 && B->st_cams_of[B->st_cur].size() == (size_t)E0 && B->st_edge_of[B->st_cur].size() == (size_t)E0;
-      const int NT = grown ? 0 : (B->n_proj > 20000 ? struct_threads() : 1);   // (200 cameras / 100 k edges: 0.67 -> 0.35 ms)
-      auto sort_lists = [&](int p0, int p1) {
-        for (int p = p0; p < p1; p++) {
-          const int a0 = cam_cnt[p], a1 = cam_cnt[p + 1];
-          for (int a = a0 + 1; a < a1; a++) {      // insertion sort (a handful of edges; stable: caller order among equal cameras)
-            const int c = cams_of[a], e = edge_of[a];
-            int q = a;
-            while (q > a0 && cams_of[q - 1] > c) { cams_of[q] = cams_of[q - 1]; edge_of[q] = edge_of[q - 1]; q--; }
-            cams_of[q] = c; edge_of[q] = e;
-          }
-        }
-      };
-      if (grown) {
-        std::vector<int> add(np + 1, 0), used(np, 0);
-        for (int k = E0; k < B->n_proj; k++) add[B->e_pt[k] + 1]++;
-        for (int p = 0; p < np; p++) add[p + 1] += add[p];                          // new edges of the landmarks before p
-        for (int p = 0; p <= np; p++) cam_cnt[p] = (p <= np0 ? B->st_cam_cnt[p] : E0) + add[p];
-        const int* oc = B->st_cams_of[B->st_cur].data(); const int* oe = B->st_edge_of[B->st_cur].data();
-        const int NTc = B->n_proj > 20000 ? struct_threads() : 1;                   // (the old lists are out of cache by now: the copy is a burst of misses)
-        run_items(NTc, [&](int t) {
-          const int p0 = (int)((long long)np0 * t / NTc), p1 = (int)((long long)np0 * (t + 1) / NTc);
-          if (p1 <= p0) return;
-          // (the landmarks of a range that got no edge in between move as one block: runs are copied whole)
-          int p = p0;
-          while (p < p1) {
-            int q = p + 1;
-            while (q < p1 && add[q] == add[p]) q++;                                 // landmarks p .. q - 1: the same shift (only the last may have new edges)
-            const int a0 = B->st_cam_cnt[p], a1 = B->st_cam_cnt[q], d0 = cam_cnt[p];
-            std::memcpy(&cams_of[d0], oc + a0, sizeof(int) * (size_t)(a1 - a0));
-            std::memcpy(&edge_of[d0], oe + a0, sizeof(int) * (size_t)(a1 - a0));
-            p = q;
-          }
-        });
-        for (int k = E0; k < B->n_proj; k++) {
-          const int p = B->e_pt[k], m_old = p < np0 ? B->st_cam_cnt[p + 1] - B->st_cam_cnt[p] : 0, q = cam_cnt[p] + m_old + used[p]++;
-          cams_of[q] = B->e_cam[k]; edge_of[q] = k;
-        }
-        for (int k = E0; k < B->n_proj; k++) sort_lists(B->e_pt[k], B->e_pt[k] + 1);
-      } else if (NT == 1) {
-        for (int k = 0; k < B->n_proj; k++) cam_cnt[B->e_pt[k] + 1]++;
-        for (int i = 0; i < np; i++) cam_cnt[i + 1] += cam_cnt[i];
-        std::vector<int> fill(cam_cnt.begin(), cam_cnt.end() - 1);
-        for (int k = 0; k < B->n_proj; k++) { const int q = fill[B->e_pt[k]]++; cams_of[q] = B->e_cam[k]; edge_of[q] = k; }
-        sort_lists(0, np);
-      } else {
-        auto range_of = [&](int p) { return (int)(((long long)p * NT) / np); };                    // landmark -> range
-        auto range_lo = [&](int r) { return (int)(((long long)r * np + NT - 1) / NT); };            // first landmark of range r (inverse of range_of)
-        std::vector<std::vector<int>> dealt((size_t)NT * NT);                                      // [dealing thread][range]: edge indices, ascending
-        run_items(NT, [&](int t) {
-          const int k0 = (int)((long long)B->n_proj * t / NT), k1 = (int)((long long)B->n_proj * (t + 1) / NT);
-          for (int r = 0; r < NT; r++) dealt[(size_t)t * NT + r].reserve((size_t)(k1 - k0) / NT + 64);
-          for (int k = k0; k < k1; k++) dealt[(size_t)t * NT + range_of(B->e_pt[k])].push_back(k);
-        });
-        std::vector<int> range_edges(NT + 1, 0);       // where a range's edges start in the grouped arrays
-        for (int r = 0; r < NT; r++) { size_t m = 0; for (int t = 0; t < NT; t++) m += dealt[(size_t)t * NT + r].size(); range_edges[r + 1] = range_edges[r] + (int)m; }
-        run_items(NT, [&](int r) {       // (cam_cnt[p + 1] of the range's landmarks is this thread's alone: count, then end offset)
-          const int p0 = range_lo(r), p1 = r + 1 < NT ? range_lo(r + 1) : np;
-          for (int t = 0; t < NT; t++) for (int k : dealt[(size_t)t * NT + r]) cam_cnt[B->e_pt[k] + 1]++;
-          std::vector<int> fill((size_t)(p1 - p0));
-          int at = range_edges[r];
-          for (int p = p0; p < p1; p++) { fill[p - p0] = at; at += cam_cnt[p + 1]; cam_cnt[p + 1] = at; }
-          for (int t = 0; t < NT; t++) for (int k : dealt[(size_t)t * NT + r]) { const int q = fill[B->e_pt[k] - p0]++; cams_of[q] = B->e_cam[k]; edge_of[q] = k; }
-          // (the lists' bounds: cam_cnt[p0] belongs to the range before -- its value is range_edges[r])
-          for (int p = p0; p < p1; p++) {
-            const int a0 = p == p0 ? range_edges[r] : cam_cnt[p], a1 = cam_cnt[p + 1];
-            for (int a = a0 + 1; a < a1; a++) {
-              const int c = cams_of[a], e = edge_of[a];
-              int q = a;
-              while (q > a0 && cams_of[q - 1] > c) { cams_of[q] = cams_of[q - 1]; edge_of[q] = edge_of[q - 1]; q--; }
-              cams_of[q] = c; edge_of[q] = e;
-            }
-          }
-        });
-      }
-    }
-    mark("  camera lists (count, fill, sort)");
-    for (int p = 0; p < np; p++) {
-      for (int a = cam_cnt[p] + 1; a < cam_cnt[p + 1]; a++)
-        if (cams_of[a] == cams_of[a - 1]) { cs_set_error("two projection edges between the same point and camera"); return CS_ERR_INVALID_ARG; }
-      if (!B->pt_fixed[p] && cam_cnt[p + 1] > cam_cnt[p]) gorder.push_back(p);
-    }
-    mark("  duplicate check");
-    // Group the landmarks by camera set.  A KITTI-shaped problem has ~70x fewer distinct sets than landmarks (2 862 for 200 k at C4), so
-    // instead of sorting the landmarks (9.6 ms of comparisons at C4) every thread hashes its range of landmarks into its own table of
-    // sets, the tables are merged, the few DISTINCT sets are sorted by (number of cameras, camera list), and the landmarks are laid
-    // out group by group -- in landmark order inside a group, because every thread walks its range in order and the ranges are laid
-    // down in order.  Same gorder / run_first as the sort produced.
-    {
-      const int NTg = (gorder.size() > 5000) ? struct_threads() : 1;
-      struct LGroup { int rep; std::vector<int> members; };
-      std::vector<std::vector<LGroup>> local(NTg);
-      auto set_hash = [&](int p) {
-        unsigned long long h = 1469598103934665603ull;
-        for (int a = cam_cnt[p]; a < cam_cnt[p + 1]; a++) { h ^= (unsigned)cams_of[a] + 0x9e3779b9u; h *= 1099511628211ull; }
-        return h ^ (h >> 29);
-      };
-      auto same_set = [&](int p, int q) {
-        const int kp = cam_cnt[p + 1] - cam_cnt[p];
-        return kp == cam_cnt[q + 1] - cam_cnt[q] && std::equal(cams_of.begin() + cam_cnt[p], cams_of.begin() + cam_cnt[p + 1], cams_of.begin() + cam_cnt[q]);
-      };
-      auto group_range = [&](int t) {
-        const size_t i0 = gorder.size() * t / NTg, i1 = gorder.size() * (t + 1) / NTg;
-        std::vector<LGroup>& G = local[t];
-        size_t cap = 1024;
-        std::vector<int> table(cap, -1);
-        for (size_t i = i0; i < i1; i++) {
-          const int p = gorder[i];
-          if ((G.size() + 1) * 2 > cap) {            // grow: re-insert the groups' representatives
-            cap *= 4; table.assign(cap, -1);
-            for (size_t g = 0; g < G.size(); g++) { size_t s = set_hash(G[g].rep) & (cap - 1); while (table[s] >= 0) s = (s + 1) & (cap - 1); table[s] = (int)g; }
-          }
-          size_t s = set_hash(p) & (cap - 1);
-          while (table[s] >= 0 && !same_set(G[table[s]].rep, p)) s = (s + 1) & (cap - 1);
-          if (table[s] < 0) { table[s] = (int)G.size(); G.push_back(LGroup{p, {}}); }
-          G[table[s]].members.push_back(p);
-        }
-      };
-      run_items(NTg, group_range);
-      // merge: global groups = distinct sets over all threads
-      struct GGroup { int rep; std::vector<std::pair<int, int>> parts; };     // (thread, local group), thread order = landmark order
-      std::vector<GGroup> GG;
-      {
-        size_t cap = 4096;
-        std::vector<int> table(cap, -1);
-        for (int t = 0; t < NTg; t++)
-          for (size_t g = 0; g < local[t].size(); g++) {
-            const int p = local[t][g].rep;
-            if ((GG.size() + 1) * 2 > cap) {
-              cap *= 4; table.assign(cap, -1);
-              for (size_t q = 0; q < GG.size(); q++) { size_t s = set_hash(GG[q].rep) & (cap - 1); while (table[s] >= 0) s = (s + 1) & (cap - 1); table[s] = (int)q; }
-            }
-            size_t s = set_hash(p) & (cap - 1);
-            while (table[s] >= 0 && !same_set(GG[table[s]].rep, p)) s = (s + 1) & (cap - 1);
-            if (table[s] < 0) { table[s] = (int)GG.size(); GG.push_back(GGroup{p, {}}); }
-            GG[table[s]].parts.push_back({t, (int)g});
-          }
-      }
-      std::vector<int> gidx(GG.size());
-      for (size_t q = 0; q < GG.size(); q++) gidx[q] = (int)q;
-      std::sort(gidx.begin(), gidx.end(), [&](int x, int y) {
-        const int p = GG[x].rep, q = GG[y].rep;
-        const int kp = cam_cnt[p + 1] - cam_cnt[p], kq = cam_cnt[q + 1] - cam_cnt[q];
-        if (kp != kq) return kp < kq;
-        return std::lexicographical_compare(cams_of.begin() + cam_cnt[p], cams_of.begin() + cam_cnt[p + 1], cams_of.begin() + cam_cnt[q], cams_of.begin() + cam_cnt[q + 1]);
-      });
-      std::vector<int> sorted;
-      sorted.reserve(gorder.size());
-      for (int q : gidx) {
-        run_first.push_back((int)sorted.size());
-        for (auto& pt : GG[q].parts) { const std::vector<int>& m = local[pt.first][pt.second].members; sorted.insert(sorted.end(), m.begin(), m.end()); }
-      }
-      run_first.push_back((int)sorted.size());
-      gorder.swap(sorted);
-    }
-    mark("  group by camera set");
-  }
-  mark("camera sets");
-  // ---- cuboid / odometry edge indices are used below: check them first
-  for (int k = 0; k < B->n_cub; k++)
-    if (B->ce_cam[k] < 0 || B->ce_cam[k] >= nc || B->ce_cub[k] < 0 || B->ce_cub[k] >= no) { cs_set_error("cuboid edge index out of range"); return CS_ERR_INVALID_ARG; }
-  for (int k = 0; k < B->n_odom; k++)
-    if (oe_i[k] < 0 || oe_i[k] >= nc || oe_j[k] < 0 || oe_j[k] >= nc) { cs_set_error("odometry edge index out of range"); return CS_ERR_INVALID_ARG; }
-  // ---- solver ordering of the pose vertices: reverse Cuthill-McKee on the block graph of the reduced system
-  // (camera-camera through shared landmarks and odometry edges, camera-cuboid through cuboid edges), so that S is
-  // banded for trajectory-shaped graphs.  The ordering only permutes the linear system; g2o's order is kept for x/b
-  // inspection (cam_col_ref).
-  // Two candidate systems.  (a) g2o's: cameras and cuboids (only the points are marginalised).  (b) The cuboids eliminated as
-  // well: a cuboid is coupled to the cameras that observe it and to nothing else, exactly like a landmark with a 9 x 9 block, so
-  // S_cc -= H_co D_oo^-1 H_co^T is the same exact block elimination -- a different elimination order of one Cholesky
-  // factorisation, not a different system -- and the reduced system shrinks to the cameras (C4: 10 494 -> 5 994 unknowns,
-  // bandwidth 182 -> 119: a cuboid couples the ~20 consecutive cameras that see it, which the landmarks' band nearly contains).
-  // The one with the cheaper banded factorisation (n bw^2) is taken; (b) needs the fused Schur schedule and at most
-  // BA_ELIM_MAX_SLOTS cameras per cuboid; sharded, a cuboid's edges then all live on ONE rank (that of its lowest-index observing
-  // camera) so that its block is complete where it is eliminated, and the cuboids' increments are summed over the ranks after the
-  // back-substitution (zero on every rank but the owner).  CS_BA_KEEP_CUBOIDS=1 forces (a).
-  B->cam_col.assign(nc, -1); B->cub_col.assign(no, -1);
-  // external (host-evaluated) edges: indices, and what their pattern means for the choices below
-  bool ext_binary_on_cuboid = false;
-  for (int k = 0; k < B->ext_n; k++) {
-    const int ci = B->ext_e4[4 * k], ii = B->ext_e4[4 * k + 1], cj = B->ext_e4[4 * k + 2], ij = B->ext_e4[4 * k + 3];
-    auto bad = [&](int c, int i) { return c < 0 || c > 2 || i < 0 || i >= (c == 0 ? nc : c == 1 ? no : np); };
-    if (bad(ci, ii) || (ij >= 0 && bad(cj, ij))) { cs_set_error("external edge: vertex class / index out of range"); return CS_ERR_INVALID_ARG; }
-    if (ij >= 0 && (ci == 2 || cj == 2)) { cs_set_error("external edge: a binary edge may join cameras and cuboids only (a marginalised point takes unary terms only: its coupling to a pose would change the Schur structure)"); return CS_ERR_INVALID_ARG; }
-    if (ij >= 0 && ci == cj && ii == ij) { cs_set_error("external edge: both ends are the same vertex"); return CS_ERR_INVALID_ARG; }
-    if (ij >= 0 && (ci == 1 || cj == 1)) ext_binary_on_cuboid = true;
-  }
-  if (B->shard_n > 1 && (B->ext_n > 0 || B->ext_fn || B->ext_terms_set)) { cs_set_error("external (host-evaluated) edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
-  std::vector<std::vector<int>> cub_cams(no);     // free cameras observing a free cuboid, distinct, by camera id
-  int max_slots = 0, n_free_cub = 0;
-  for (int k = 0; k < B->n_cub; k++) if (!B->cub_fixed[B->ce_cub[k]] && !B->cam_fixed[B->ce_cam[k]]) cub_cams[B->ce_cub[k]].push_back(B->ce_cam[k]);
-  for (int o = 0; o < no; o++) {
-    std::sort(cub_cams[o].begin(), cub_cams[o].end());
-    cub_cams[o].erase(std::unique(cub_cams[o].begin(), cub_cams[o].end()), cub_cams[o].end());
-    max_slots = std::max(max_slots, (int)cub_cams[o].size());
-    if (!B->cub_fixed[o]) n_free_cub++;
-  }
-  bool fused_ok = getenv("CS_BA_SCHUR_PAIRS") == nullptr;
-  {
-    // (tracks of more than BA_FUSED_KMAX views go through the segments' plain multiply-add kernel: meant for the tail of a map -- when a
-    // quarter of the landmarks are such tracks the pair-major path is the faster build again, measured at C4's size with 20 views each)
-    size_t n_long = 0;
-    for (int p : gorder) {
-      const int kk = cam_cnt[p + 1] - cam_cnt[p];
-      if (kk > cs::BA_LONG_KMAX) { fused_ok = false; break; }
-      if (kk > cs::BA_FUSED_KMAX) n_long++;
-    }
-    if (4 * n_long > gorder.size()) fused_ok = false;
-  }
-  mark("  cuboid cameras, track lengths");
-  struct Ordering { std::vector<int> cam_col, cub_col; int n_red = 0, bw = 0; std::vector<std::vector<int>> adj; std::vector<int> free_ids; };
-  auto make_ordering = [&](bool elim) -> Ordering {
-    Ordering O;
-    O.cam_col.assign(nc, -1); O.cub_col.assign(no, -1);
-    const int NV = nc + no;
-    std::vector<std::vector<int>> adj(NV);
-    auto is_free = [&](int v) { return v < nc ? !B->cam_fixed[v] : (!elim && !B->cub_fixed[v - nc]); };
-    // (up to 8 192 vertices the links are collected as bits -- a camera pair is linked by many camera sets and, cuboids eliminated, by
-    // every cuboid both see: 0.2 M pushes + a sort and unique per vertex were 4 ms of this phase at 1 000 cameras -- and read out in order)
-    const bool as_bits = NV <= 8192;
-    const size_t Wd = as_bits ? (size_t)(NV + 63) / 64 : 0;
-    std::vector<unsigned long long> bits(as_bits ? (size_t)NV * Wd : 0, 0ull);
-    auto link = [&](int a, int b) {
-      if (a == b || !is_free(a) || !is_free(b)) return;
-      if (as_bits) { bits[(size_t)a * Wd + (b >> 6)] |= 1ull << (b & 63); bits[(size_t)b * Wd + (a >> 6)] |= 1ull << (a & 63); }
-      else { adj[a].push_back(b); adj[b].push_back(a); }
-    };
-    // landmarks couple the cameras that see them: one clique per DISTINCT camera set (the landmarks were grouped by camera set
-    // above; KITTI-shaped problems have ~100x fewer sets than landmarks)
-    for (size_t r = 0; r + 1 < run_first.size(); r++) {
-      const int p = gorder[run_first[r]];
-      for (int a = cam_cnt[p]; a < cam_cnt[p + 1]; a++) for (int b = a + 1; b < cam_cnt[p + 1]; b++) link(cams_of[a], cams_of[b]);
-    }
-    for (int k = 0; k < B->n_odom; k++) link(oe_i[k], oe_j[k]);
-    for (int k = 0; k < B->ext_n; k++) if (B->ext_e4[4 * k + 3] >= 0) link((B->ext_e4[4 * k] ? nc : 0) + B->ext_e4[4 * k + 1], (B->ext_e4[4 * k + 2] ? nc : 0) + B->ext_e4[4 * k + 3]);
-    if (!elim) { for (int k = 0; k < B->n_cub; k++) link(B->ce_cam[k], nc + B->ce_cub[k]); }
-    else for (int o = 0; o < no; o++) if (!B->cub_fixed[o]) for (size_t a = 0; a < cub_cams[o].size(); a++) for (size_t b = a + 1; b < cub_cams[o].size(); b++) link(cub_cams[o][a], cub_cams[o][b]);
-    if (as_bits) {
-      for (int v = 0; v < NV; v++) {
-        const unsigned long long* r = bits.data() + (size_t)v * Wd;
-        for (size_t w = 0; w < Wd; w++) for (unsigned long long m = r[w]; m; m &= m - 1) adj[v].push_back((int)(64 * w) + __builtin_ctzll(m));
-      }
-    } else {
-      for (auto& a : adj) { std::sort(a.begin(), a.end()); a.erase(std::unique(a.begin(), a.end()), a.end()); }
-    }
-    std::vector<int> order;  // Cuthill-McKee, component by component, starting from a minimum-degree vertex
-    std::vector<char> seen(NV, 0);
-    std::vector<int> by_deg;
-    for (int v = 0; v < NV; v++) if (is_free(v)) by_deg.push_back(v);
-    std::stable_sort(by_deg.begin(), by_deg.end(), [&](int a, int b) { return adj[a].size() < adj[b].size(); });
-    for (int s0 : by_deg) {
-      if (seen[s0]) continue;
-      // pseudo-peripheral start: two BFS sweeps from the minimum-degree vertex of the component
-      int start = s0;
-      for (int sweep = 0; sweep < 2; sweep++) {
-        std::vector<int> q{start}, dist(NV, -1);
-        dist[start] = 0;
-        for (size_t h = 0; h < q.size(); h++) for (int w : adj[q[h]]) if (dist[w] < 0) { dist[w] = dist[q[h]] + 1; q.push_back(w); }
-        int far = q.back();
-        for (int v : q) if (dist[v] == dist[far] && adj[v].size() < adj[far].size()) far = v;
-        start = far;
-      }
-      size_t head = order.size();
-      order.push_back(start); seen[start] = 1;
-      for (; head < order.size(); head++) {
-        std::vector<int> nb;
-        for (int w : adj[order[head]]) if (!seen[w]) { seen[w] = 1; nb.push_back(w); }
-        std::stable_sort(nb.begin(), nb.end(), [&](int a, int b) { return adj[a].size() < adj[b].size(); });
-        order.insert(order.end(), nb.begin(), nb.end());
-      }
-    }
-    std::reverse(order.begin(), order.end());
-    int col = 0;
-    for (int v : order) { if (v < nc) { O.cam_col[v] = col; col += 6; } else { O.cub_col[v - nc] = col; col += 9; } }
-    O.n_red = col;
-    if (elim) for (int o = 0; o < no; o++) if (!B->cub_fixed[o]) { O.cub_col[o] = col; col += 9; }   // increments of the eliminated cuboids: behind the reduced system's
-    auto vcol = [&](int v) { return v < nc ? O.cam_col[v] : O.cub_col[v - nc]; };
-    auto vdim = [&](int v) { return v < nc ? 6 : 9; };
-    int bw = 0;
-    for (int v : order) {
-      bw = std::max(bw, vdim(v) - 1);
-      for (int w : adj[v]) { int lo = std::min(vcol(v), vcol(w)); int hi = (vcol(v) > vcol(w)) ? vcol(v) + vdim(v) - 1 : vcol(w) + vdim(w) - 1; bw = std::max(bw, hi - lo); }
-    }
-    O.bw = bw;
-    O.free_ids = order;          // (for the sparse plan: the block graph of the free vertices)
-    O.adj = std::move(adj);
-    return O;
-  };
-  // banded path only where the persistent kernel's team is guaranteed to be resident on THIS device (occupancy query x CUs:
-  // 256 CUs admit bandwidths up to ~1900; a partitioned or smaller device proportionally less); dense rocSOLVER otherwise
-  auto band_ok = [&](const Ordering& O) { return !B->force_dense && O.n_red > 128 && O.bw + 1 <= O.n_red / 2 && cs::ba_band_fits_device(O.n_red, O.bw + 1); };
-  auto cost = [&](const Ordering& O) { return band_ok(O) ? (double)O.n_red * (O.bw + 1.0) * (O.bw + 1.0) : (double)O.n_red * O.n_red * O.n_red / 3.0; };
-  {
-    // (an external binary edge on a cuboid couples it to something besides its observing cameras: the cuboids then stay in the system)
-    B->elim_max_slots = std::max(1, std::min(max_slots, (int)cs::BA_ELIM_MAX_SLOTS));
-    const bool try_elim = fused_ok && n_free_cub > 0 && max_slots <= cs::BA_ELIM_MAX_SLOTS && getenv("CS_BA_KEEP_CUBOIDS") == nullptr && !ext_binary_on_cuboid;
-    // (the two candidate orderings only read shared data: g2o's system on a second thread while this one orders the cameras-only system)
-    Ordering keep_o, elim_o;
-    if (try_elim && nc + no > 64) {
-      run_items(2, [&](int t) { if (t == 0) elim_o = make_ordering(true); else keep_o = make_ordering(false); });
-    } else {
-      keep_o = make_ordering(false);
-      if (try_elim) elim_o = make_ordering(true);
-    }
-    // (an ordering without unknowns -- every camera fixed, the driver's frame-0 graph -- is not a candidate: nothing would be
-    // factorised and the cuboids' elimination / back-substitution hang off the reduced solve)
-    mark("  two orderings");
-    B->elim = try_elim && elim_o.n_red > 0 && cost(elim_o) < cost(keep_o);
-    const Ordering& O = B->elim ? elim_o : keep_o;
-    B->cam_col = O.cam_col; B->cub_col = O.cub_col; B->n_red = O.n_red;
-    B->band_ld = band_ok(O) ? O.bw + 1 : 0;
-    // A general sparse factorisation (fill-reducing order of the block graph, ba_sparse.h) where it is the fastest of the three.  The
-    // estimates are fits to measurements on MI355X (tools/ba_mesh_quick.py): banded -- 1.15 n / 64 dependent steps of
-    // (10 + 0.043 bw) us; dense rocSOLVER potrf -- n^3 / 3 at 11 Tflop/s + 1 ms; sparse -- 25 us per level of the elimination tree +
-    // 1.5 ms per Gflop + the dense tail's n^3 / 3 at 3 Tflop/s (rocSOLVER at 1-2 k unknowns) + the dense assembly's extra cost (1 ms + the
-    // n x n fill).  The plan (an O(N^2) minimum-degree sweep) is only built when the alternative costs more than 5 ms.  CS_BA_SPARSE=0 never, =1 whenever the plan fits.
-    mark("  band fits device");
-    B->sparse = false; B->S_clean = false;
-    {
-      const char* e = getenv("CS_BA_SPARSE");
-      const int mode = e ? atoi(e) : -1;
-      const double nn = (double)O.n_red;
-      double est_band = B->band_ld ? 1.15 * nn / 64.0 * (10.0 + 0.043 * (B->band_ld - 1)) * 1e-3 : 1e30;
-      // (wide bands: the line above was fitted on bandwidths of 100-200; the 1 920-camera survey mesh -- 11 514 unknowns, bandwidth 1 121 -- takes the banded
-      // kernels 14.2 ms where it says 12.0 (bench.py, ba.solver_paths: 17.2 ms per damped solve against 14.8 through the sparse path, ~3 ms of either the reduce))
-      if (B->band_ld > 128) est_band *= 1.0 + 0.00018 * (B->band_ld - 128);
-      const double est_dense = nn * nn * nn / 3.0 / 11e12 * 1e3 + 1.0;
-      // block cyclic reduction where the band is narrow enough for 128-unknown blocks and its few levels beat the banded kernels' chain of steps
-      B->use_bcr = false;
-      if (B->band_ld && cs::ba_bcr_ok(O.n_red, B->band_ld)) {
-        const double est_bcr = cs::ba_bcr_estimate_ms(O.n_red);
-        const char* eb = getenv("CS_BAND_BCR");
-        if (est_bcr < est_band || (eb && atoi(eb) == 2)) { B->use_bcr = true; est_band = est_bcr; }
-      }
-      const double est_other = std::min(est_band, est_dense);
-      const bool consider = mode != 0 && !B->force_dense && B->shard_n == 1 && O.n_red >= 256 && (mode == 1 || est_other > 5.0);
-      if (consider) {
-        std::vector<int> dim(nc + no, 0), col(nc + no, 0);
-        for (int v : O.free_ids) { dim[v] = v < nc ? 6 : 9; col[v] = v < nc ? O.cam_col[v] : O.cub_col[v - nc]; }
-        const bool fits = B->solver.build(O.adj, O.free_ids, dim, col, 0.35, getenv("CS_BA_SPARSE_NO_TAIL") ? 0 : (getenv("CS_BA_SPARSE_TAIL_MAX") ? atoi(getenv("CS_BA_SPARSE_TAIL_MAX")) : 9000));
-        const cs::SparsePlan& plan = B->solver.plan;      // (the handle's own: a plan that is not taken is not uploaded, and B->sparse stays false)
-        const double nt = (double)plan.n_tail;
-        const double est_sparse = 0.025 * plan.levels + 1.5 * plan.flops * 2e-9 + (nt > 0 ? nt * nt * nt / 3.0 / 3e12 * 1e3 + 1.0 : 0.0) + 1.0 + nn * nn * 8.0 / 2e12 * 1e3
-                                  + 0.3;   // (the sparse solve is not deferrable: its trials take cs_ba_optimize's synchronising flow -- four more host round trips than the stream flow of the band)
-        if (prof && fits) fprintf(stderr, "[ba structure] sparse plan: %d vertices, %d levels, %lld values (%.1f%% of the dense triangle), largest panel %d, %.2f Gflop + a dense tail of %d unknowns; estimates ms: sparse %.1f, band %.1f, dense %.1f\n",
-                                  plan.N, plan.levels, plan.nvals, 100.0 * plan.nvals / (0.5 * nn * nn), plan.max_panel, plan.flops * 2e-9, plan.n_tail, est_sparse, est_band < 1e29 ? est_band : -1.0, est_dense);
-        if (fits && (mode == 1 || est_sparse < est_other)) { B->sparse = true; B->band_ld = 0; B->use_bcr = false; }
-      }
-    }
-  }
-  // ---- sharded: the column cut (separator mode) and who owns what
-  mark("ordering (RCM)");
-  B->sep_mode = false; B->cut.clear(); B->sepw.clear(); B->sep_off.clear(); B->n_sep = 0; B->w_max = 0; B->msg_doubles = 0;
-  B->int_c = B->int_n = B->zl = B->wl = B->zr = B->wr = 0;
-  const int R = B->shard_n;
-  if (R > 1 && B->band_ld > 0 && getenv("CS_BA_SHARD_ALLREDUCE") == nullptr) {
-    struct Blk { int col, dim; };
-    std::vector<Blk> blks;
-    for (int i = 0; i < nc; i++) if (B->cam_col[i] >= 0) blks.push_back(Blk{B->cam_col[i], 6});
-    for (int i = 0; i < no; i++) if (B->cub_col[i] >= 0 && B->cub_col[i] < B->n_red) blks.push_back(Blk{B->cub_col[i], 9});
-    std::sort(blks.begin(), blks.end(), [](const Blk& a, const Blk& b) { return a.col < b.col; });
-    const int bw = B->band_ld - 1;
-    std::vector<int> cut(R + 1, 0), sepw(R, 0);
-    cut[R] = B->n_red;
-    bool ok = true;
-    for (int r = 1; r < R && ok; r++) {
-      const long long target = (long long)B->n_red * r / R;
-      size_t q = 0;
-      while (q < blks.size() && blks[q].col < target) q++;
-      if (q >= blks.size()) { ok = false; break; }
-      cut[r] = blks[q].col;
-      int w = 0;
-      while (q < blks.size() && w < bw) { w += blks[q].dim; q++; }
-      if (w < bw) { ok = false; break; }
-      sepw[r] = w;
-    }
-    for (int r = 0; r < R && ok; r++) {
-      const int ni = cut[r + 1] - cut[r] - sepw[r];
-      if (ni < 129 || ni <= B->band_ld) ok = false;     // (also: interiors further apart than the bandwidth, the regime the band kernels are tested in)
-    }
-    if (ok) {   // the separator system (block tridiagonal, blocks <= w_max: a band of 2 w_max) goes through the same persistent kernels
-      int wm = 0, nsep = 0;
-      for (int k = 1; k < R; k++) { wm = std::max(wm, sepw[k]); nsep += sepw[k]; }
-      // the interiors go through the ONE-SIDED kernel (grid = team + 1), whose residency depends on LD only: every rank decides alike
-      int ni_max = 0;
-      for (int r = 0; r < R; r++) ni_max = std::max(ni_max, cut[r + 1] - cut[r] - sepw[r]);
-      if (!cs::ba_band_fits_device(nsep, 2 * wm) || !cs::ba_band_fits_device(ni_max, B->band_ld, true)) ok = false;
-    }
-    if (ok) {
-      B->sep_mode = true; B->cut = cut; B->sepw = sepw;
-      B->sep_off.assign(R + 1, 0);
-      for (int k = 1; k < R; k++) { B->sep_off[k + 1] = B->sep_off[k] + sepw[k]; B->w_max = std::max(B->w_max, sepw[k]); }
-      B->n_sep = B->sep_off[R];
-      B->msg_doubles = 3 * (size_t)B->w_max * B->w_max + 2 * (size_t)B->w_max;
-      const int r = B->shard_rank;
-      B->zl = cut[r]; B->wl = sepw[r]; B->int_c = cut[r] + sepw[r]; B->int_n = cut[r + 1] - B->int_c;
-      B->zr = cut[r + 1]; B->wr = (r + 1 < R) ? sepw[r + 1] : 0;
-    }
-  }
-  auto rank_of_col = [&](int col) { int r = 0; while (r + 1 < R && col >= B->cut[r + 1]) r++; return r; };
-  std::vector<int> owner;
-  if (B->sep_mode) {   // a landmark goes to the rank that owns the lowest column among its free cameras (none: rank 0)
-    owner.assign(np, 0);
-    for (int p = 0; p < np; p++) {
-      int lo = 0x7fffffff;
-      for (int a = cam_cnt[p]; a < cam_cnt[p + 1]; a++) { const int c = B->cam_col[cams_of[a]]; if (c >= 0) lo = std::min(lo, c); }
-      if (lo != 0x7fffffff) owner[p] = rank_of_col(lo);
-    }
-  } else if (B->shard_n > 1) {
-    landmark_owners(B->shard_n, nc, np, B->n_proj, B->e_pt.data(), B->e_cam.data(), owner);
-  } else {
-    owner.assign(np, 0);
-  }
-  B->lm_owner = owner;
-  int nl = 0;
-  std::vector<int> pt_free(np);
-  for (int i = 0; i < np; i++) { pt_free[i] = B->pt_fixed[i] ? 0 : 1; if (pt_free[i]) B->pt_lm[i] = nl++; }
-  B->n_lm = nl;
-  int rc;
-  // (the ~80 small uploads of a structure phase likewise: staged in the pinned arena, copied by one kernel per group of up to 48 tables at
-  // the end of the phase -- nothing launched inside the phase reads them.  CS_BA_UPLOAD_KERNEL=0: one hipMemcpyAsync per table, as before.)
+  void operator()(const char* what) { if (on) { double t = now_ms(); fprintf(stderr, "[ba structure] %-28s %8.2f ms   (%d device allocations so far)\n", what, t - t_ph, g_dbuf_reallocs); t_ph = t; } }
+};
+
+// The structure phase's uploads and zero fills, queued on the handle's stream.
+// (the ~80 small uploads of a structure phase: staged in the pinned arena, copied by one kernel per group of up to 48 tables at
+// the end of the phase -- nothing launched inside the phase reads them.  CS_BA_UPLOAD_KERNEL=0: one hipMemcpyAsync per table, as before.)
+// (the ~50 zero fills of a structure phase -- one hipMemsetAsync each, 4-6 us of host time apiece, a third of an appended frame's phase --
+// are collected and go out as one kernel per group of up to 48 buffers: zflush() where the order against other device work matters)
+struct StructureUploads {
+  cs_ba* B;
   std::vector<cs::BaCopyItem> copy_list;
+  std::vector<std::pair<void*, size_t>> zero_list;
   const bool upload_kernel = [] { const char* e = getenv("CS_BA_UPLOAD_KERNEL"); return !e || atoi(e) != 0; }();
+  explicit StructureUploads(cs_ba* b) : B(b) {}
+  template <class T>
+  int up(DBuf<T>& buf, const T* h, size_t n) {
+    CS_TRY(upload_kernel ? buf.upload_ptr_deferred(h, n, B->stage, copy_list, B->st) : buf.upload_ptr_staged(h, n, B->stage, B->st));
+    return flush(false);
+  }
+  template <class T>
+  int up(DBuf<T>& buf, const std::vector<T>& v) { return up(buf, v.data(), v.size()); }
+  template <class T>
+  int alloc_zeroed(DBuf<T>& buf, size_t n) { return buf.alloc_deferred(n, zero_list); }
+  int zflush() {
+    for (size_t i = 0; i < zero_list.size(); i += 48) cs::ba_launch_multi_zero(zero_list.data() + i, (int)std::min<size_t>(48, zero_list.size() - i), B->st);
+    zero_list.clear();
+    CS_HIP_TRY(hipGetLastError());
+    return CS_OK;
+  }
   // (a launch per 24 tables or 2 MB staged, so that a large graph's transfers run beside the host work that follows them)
-  auto cflush = [&](bool all) -> int {
+  int flush(bool all) {
     size_t bytes = 0;
     for (const cs::BaCopyItem& c : copy_list) bytes += c.bytes;
     if (!all && copy_list.size() < 24 && bytes < ((size_t)2 << 20)) return CS_OK;
@@ -1005,531 +442,347 @@ int finalize_structure(cs_ba* B) {
     copy_list.clear();
     CS_HIP_TRY(hipGetLastError());
     return CS_OK;
+  }
+};
+
+// ---- index mapping (sparse_optimizer.cpp:166-190): non-marginalised vertices by id, then the points
+void reference_columns(cs_ba* B) {
+  const int nc = B->nc, no = B->no;
+  B->cam_col_ref.assign(nc, -1); B->cub_col_ref.assign(no, -1); B->pt_lm.assign(B->np, -1);
+  int col = 0;
+  auto do_cams = [&]() { for (int i = 0; i < nc; i++) if (!B->cam_fixed[i]) { B->cam_col_ref[i] = col; col += 6; } };
+  auto do_cubs = [&]() { for (int i = 0; i < no; i++) if (!B->cub_fixed[i]) { B->cub_col_ref[i] = col; col += 9; } };
+  if (B->cuboids_first) { do_cubs(); do_cams(); } else { do_cams(); do_cubs(); }
+  B->n_pose = col;
+}
+
+// external (host-evaluated) edges: indices, and what their pattern means for the solver choice
+int check_external_edges(const cs_ba* B, bool& binary_on_cuboid) {
+  const int nc = B->nc, no = B->no, np = B->np;
+  binary_on_cuboid = false;
+  for (int k = 0; k < B->ext_n; k++) {
+    const int ci = B->ext_e4[4 * k], ii = B->ext_e4[4 * k + 1], cj = B->ext_e4[4 * k + 2], ij = B->ext_e4[4 * k + 3];
+    auto bad = [&](int c, int i) { return c < 0 || c > 2 || i < 0 || i >= (c == 0 ? nc : c == 1 ? no : np); };
+    if (bad(ci, ii) || (ij >= 0 && bad(cj, ij))) { cs_set_error("external edge: vertex class / index out of range"); return CS_ERR_INVALID_ARG; }
+    if (ij >= 0 && (ci == 2 || cj == 2)) { cs_set_error("external edge: a binary edge may join cameras and cuboids only (a marginalised point takes unary terms only: its coupling to a pose would change the Schur structure)"); return CS_ERR_INVALID_ARG; }
+    if (ij >= 0 && ci == cj && ii == ij) { cs_set_error("external edge: both ends are the same vertex"); return CS_ERR_INVALID_ARG; }
+    if (ij >= 0 && (ci == 1 || cj == 1)) binary_on_cuboid = true;
+  }
+  if (B->shard_n > 1 && (B->ext_n > 0 || B->ext_fn || B->ext_terms_set)) { cs_set_error("external (host-evaluated) edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
+  return CS_OK;
+}
+// ... their records, and the binary ones grouped by the unordered pair of vertices they join (stable: the caller's order inside a group)
+int upload_external_edges(cs_ba* B, StructureUploads& U) {
+  { std::vector<int> e4(B->ext_e4); if (e4.empty()) e4.assign(4, 0); CS_TRY(U.up(B->d_ext_e4, e4)); }
+  std::vector<int> order, gptr(1, 0);
+  auto key = [&](int k) {
+    const long long a = ((long long)B->ext_e4[4 * k] << 32) | (unsigned)B->ext_e4[4 * k + 1], b = ((long long)B->ext_e4[4 * k + 2] << 32) | (unsigned)B->ext_e4[4 * k + 3];
+    return std::make_pair(std::min(a, b), std::max(a, b));
   };
-#define UP(buf, vec) do { rc = upload_kernel ? (buf).upload_ptr_deferred((vec).data(), (vec).size(), B->stage, copy_list, B->st) : (buf).upload_staged(vec, B->stage, B->st); if (!rc) rc = cflush(false); if (rc) return rc; } while (0)
-  // (the ~50 zero fills of a structure phase -- one hipMemsetAsync each, 4-6 us of host time apiece, a third of an appended frame's phase --
-  // are collected and go out as one kernel per group of up to 48 buffers: ZFLUSH() where the order against other device work matters)
-  std::vector<std::pair<void*, size_t>> zero_list;
-  auto zflush = [&]() -> int {
-    for (size_t i = 0; i < zero_list.size(); i += 48) cs::ba_launch_multi_zero(zero_list.data() + i, (int)std::min<size_t>(48, zero_list.size() - i), B->st);
-    zero_list.clear();
-    CS_HIP_TRY(hipGetLastError());
-    return CS_OK;
-  };
-#define AL(buf, n) do { rc = (buf).alloc_deferred(n, zero_list); if (rc) return rc; } while (0)
-#define ZFLUSH() do { rc = zflush(); if (rc) return rc; } while (0)
-#define UPB(buf, ub) do { rc = upload_kernel ? (buf).upload_ptr_deferred((ub).data(), (ub).size(), B->stage, copy_list, B->st) : (buf).upload_ptr_staged((ub).data(), (ub).size(), B->stage, B->st); if (!rc) rc = cflush(false); if (rc) return rc; } while (0)
-  UP(B->d_cam_col, B->cam_col); UP(B->d_cub_col, B->cub_col); UP(B->d_pt_free, pt_free);
-  { std::vector<int> e4(B->ext_e4); if (e4.empty()) e4.assign(4, 0); UP(B->d_ext_e4, e4); }
-  {  // the host-evaluated binary edges grouped by the unordered pair of vertices they join (stable: the caller's order inside a group)
-    std::vector<int> order, gptr(1, 0);
-    auto key = [&](int k) {
-      const long long a = ((long long)B->ext_e4[4 * k] << 32) | (unsigned)B->ext_e4[4 * k + 1], b = ((long long)B->ext_e4[4 * k + 2] << 32) | (unsigned)B->ext_e4[4 * k + 3];
-      return std::make_pair(std::min(a, b), std::max(a, b));
-    };
-    for (int k = 0; k < B->ext_n; k++) if (B->ext_e4[4 * k + 3] >= 0) order.push_back(k);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return key(x) < key(y); });
-    for (size_t q = 0; q < order.size(); q++) if (q + 1 == order.size() || key(order[q]) != key(order[q + 1])) gptr.push_back((int)q + 1);
-    B->ext_groups = (int)gptr.size() - 1;
-    if (order.empty()) order.push_back(0);
-    UP(B->d_ext_order, order); UP(B->d_ext_gptr, gptr);
+  for (int k = 0; k < B->ext_n; k++) if (B->ext_e4[4 * k + 3] >= 0) order.push_back(k);
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return key(x) < key(y); });
+  for (size_t q = 0; q < order.size(); q++) if (q + 1 == order.size() || key(order[q]) != key(order[q + 1])) gptr.push_back((int)q + 1);
+  B->ext_groups = (int)gptr.size() - 1;
+  if (order.empty()) order.push_back(0);
+  CS_TRY(U.up(B->d_ext_order, order)); CS_TRY(U.up(B->d_ext_gptr, gptr));
+  return CS_OK;
+}
+
+// The elimination / band / BCR / sparse decision between two candidate systems.  (a) g2o's: cameras and cuboids (only the points are
+// marginalised).  (b) The cuboids eliminated as
+// well: a cuboid is coupled to the cameras that observe it and to nothing else, exactly like a landmark with a 9 x 9 block, so
+// S_cc -= H_co D_oo^-1 H_co^T is the same exact block elimination -- a different elimination order of one Cholesky
+// factorisation, not a different system -- and the reduced system shrinks to the cameras (C4: 10 494 -> 5 994 unknowns,
+// bandwidth 182 -> 119: a cuboid couples the ~20 consecutive cameras that see it, which the landmarks' band nearly contains).
+// The one with the cheaper banded factorisation (n bw^2) is taken; (b) needs the fused Schur schedule and at most
+// BA_ELIM_MAX_SLOTS cameras per cuboid; sharded, a cuboid's edges then all live on ONE rank (that of its lowest-index observing
+// camera) so that its block is complete where it is eliminated, and the cuboids' increments are summed over the ranks after the
+// back-substitution (zero on every rank but the owner).  CS_BA_KEEP_CUBOIDS=1 forces (a).
+// The ordering only permutes the linear system; g2o's order is kept for x/b inspection (cam_col_ref).
+void choose_reduced_solver(cs_ba* B, const cs::Ordering& keep_o, const cs::Ordering& elim_o, bool try_elim, PhaseMarks& mark) {
+  const int nc = B->nc, no = B->no;
+  // banded path only where the persistent kernel's team is guaranteed to be resident on THIS device (occupancy query x CUs:
+  // 256 CUs admit bandwidths up to ~1900; a partitioned or smaller device proportionally less); dense rocSOLVER otherwise
+  auto band_ok = [&](const cs::Ordering& O) { return !B->force_dense && O.n_red > 128 && O.bw + 1 <= O.n_red / 2 && cs::ba_band_fits_device(O.n_red, O.bw + 1); };
+  auto cost = [&](const cs::Ordering& O) { return band_ok(O) ? (double)O.n_red * (O.bw + 1.0) * (O.bw + 1.0) : (double)O.n_red * O.n_red * O.n_red / 3.0; };
+  // (an ordering without unknowns -- every camera fixed, the driver's frame-0 graph -- is not a candidate: nothing would be
+  // factorised and the cuboids' elimination / back-substitution hang off the reduced solve)
+  B->elim = try_elim && elim_o.n_red > 0 && cost(elim_o) < cost(keep_o);
+  const cs::Ordering& O = B->elim ? elim_o : keep_o;
+  B->cam_col = O.cam_col; B->cub_col = O.cub_col; B->n_red = O.n_red;
+  B->band_ld = band_ok(O) ? O.bw + 1 : 0;
+  // A general sparse factorisation (fill-reducing order of the block graph, ba_sparse.h) where it is the fastest of the three.  The
+  // estimates are fits to measurements on MI355X (tools/ba_mesh_quick.py): banded -- 1.15 n / 64 dependent steps of
+  // (10 + 0.043 bw) us; dense rocSOLVER potrf -- n^3 / 3 at 11 Tflop/s + 1 ms; sparse -- 25 us per level of the elimination tree +
+  // 1.5 ms per Gflop + the dense tail's n^3 / 3 at 3 Tflop/s (rocSOLVER at 1-2 k unknowns) + the dense assembly's extra cost (1 ms + the
+  // n x n fill).  The plan (an O(N^2) minimum-degree sweep) is only built when the alternative costs more than 5 ms.  CS_BA_SPARSE=0 never, =1 whenever the plan fits.
+  mark("  band fits device");
+  B->sparse = false; B->S_clean = false;
+  const char* e = getenv("CS_BA_SPARSE");
+  const int mode = e ? atoi(e) : -1;
+  const double nn = (double)O.n_red;
+  double est_band = B->band_ld ? 1.15 * nn / 64.0 * (10.0 + 0.043 * (B->band_ld - 1)) * 1e-3 : 1e30;
+  // (wide bands: the line above was fitted on bandwidths of 100-200; the 1 920-camera survey mesh -- 11 514 unknowns, bandwidth 1 121 -- takes the banded
+  // kernels 14.2 ms where it says 12.0 (bench.py, ba.solver_paths: 17.2 ms per damped solve against 14.8 through the sparse path, ~3 ms of either the reduce))
+  if (B->band_ld > 128) est_band *= 1.0 + 0.00018 * (B->band_ld - 128);
+  const double est_dense = nn * nn * nn / 3.0 / 11e12 * 1e3 + 1.0;
+  // block cyclic reduction where the band is narrow enough for 128-unknown blocks and its few levels beat the banded kernels' chain of steps
+  B->use_bcr = false;
+  if (B->band_ld && cs::ba_bcr_ok(O.n_red, B->band_ld)) {
+    const double est_bcr = cs::ba_bcr_estimate_ms(O.n_red);
+    const char* eb = getenv("CS_BAND_BCR");
+    if (est_bcr < est_band || (eb && atoi(eb) == 2)) { B->use_bcr = true; est_band = est_bcr; }
   }
-  // ---- projection edges: point-major order (sorted by pose column inside a point), camera-major copy.  The edges are already
-  // grouped by landmark with their cameras sorted by id (cams_of / edge_of above); a rank's point-major table is its own landmarks'
-  // groups, each re-ordered by (column, camera id) -- k <= a handful of entries -- in a few host threads on disjoint ranges.
-  std::vector<int> pt_ptr(np + 1, 0);
-  for (int p = 0; p < np; p++) pt_ptr[p + 1] = pt_ptr[p] + (owner[p] == B->shard_rank ? cam_cnt[p + 1] - cam_cnt[p] : 0);
-  const int E = pt_ptr[np];   // local edges
-  if (B->slot_src_cap < (size_t)E) { B->slot_src_cap = (size_t)E + (B->slot_src ? (size_t)E / 4 : 0) + 1; B->slot_src.reset(new int[B->slot_src_cap]); }
-  B->slot_src_n = E;
-  int* const src_of_slot = B->slot_src.get();
-  UBuf<int>& pm_pt = B->st_pm_pt; UBuf<int>& pm_cam = B->st_pm_cam;
-  pm_pt.ensure((size_t)E); pm_cam.ensure((size_t)E);
-  const int NTH = (E > 20000) ? struct_threads() : 1;
-  {
-    auto build_points = [&](int p0, int p1) {
-      for (int p = p0; p < p1; p++) {
-        if (owner[p] != B->shard_rank) continue;
-        const int a0 = cam_cnt[p], k = cam_cnt[p + 1] - a0, s0 = pt_ptr[p];
-        for (int a = 0; a < k; a++) { pm_cam[s0 + a] = cams_of[a0 + a]; src_of_slot[s0 + a] = edge_of[a0 + a]; pm_pt[s0 + a] = p; }
-        for (int a = 1; a < k; a++) {     // by (column, camera id): fixed cameras (column -1) first, by id; stable
-          const int c = pm_cam[s0 + a], e = src_of_slot[s0 + a], col = B->cam_col[c];
-          int q = a;
-          while (q > 0 && (B->cam_col[pm_cam[s0 + q - 1]] > col || (B->cam_col[pm_cam[s0 + q - 1]] == col && pm_cam[s0 + q - 1] > c))) {
-            pm_cam[s0 + q] = pm_cam[s0 + q - 1]; src_of_slot[s0 + q] = src_of_slot[s0 + q - 1]; q--;
-          }
-          pm_cam[s0 + q] = c; src_of_slot[s0 + q] = e;
-        }
-      }
-    };
-    run_items(NTH, [&](int t) { build_points((int)((long long)np * t / NTH), (int)((long long)np * (t + 1) / NTH)); });
+  const double est_other = std::min(est_band, est_dense);
+  const bool consider = mode != 0 && !B->force_dense && B->shard_n == 1 && O.n_red >= 256 && (mode == 1 || est_other > 5.0);
+  if (!consider) return;
+  std::vector<int> dim(nc + no, 0), col(nc + no, 0);
+  for (int v : O.free_ids) { dim[v] = v < nc ? 6 : 9; col[v] = v < nc ? O.cam_col[v] : O.cub_col[v - nc]; }
+  const bool fits = B->solver.build(O.adj, O.free_ids, dim, col, 0.35, getenv("CS_BA_SPARSE_NO_TAIL") ? 0 : (getenv("CS_BA_SPARSE_TAIL_MAX") ? atoi(getenv("CS_BA_SPARSE_TAIL_MAX")) : 9000));
+  const cs::SparsePlan& plan = B->solver.plan;      // (the handle's own: a plan that is not taken is not uploaded, and B->sparse stays false)
+  const double nt = (double)plan.n_tail;
+  const double est_sparse = 0.025 * plan.levels + 1.5 * plan.flops * 2e-9 + (nt > 0 ? nt * nt * nt / 3.0 / 3e12 * 1e3 + 1.0 : 0.0) + 1.0 + nn * nn * 8.0 / 2e12 * 1e3
+                            + 0.3;   // (the sparse solve is not deferrable: its trials take cs_ba_optimize's synchronising flow -- four more host round trips than the stream flow of the band)
+  if (mark.on && fits) fprintf(stderr, "[ba structure] sparse plan: %d vertices, %d levels, %lld values (%.1f%% of the dense triangle), largest panel %d, %.2f Gflop + a dense tail of %d unknowns; estimates ms: sparse %.1f, band %.1f, dense %.1f\n",
+                               plan.N, plan.levels, plan.nvals, 100.0 * plan.nvals / (0.5 * nn * nn), plan.max_panel, plan.flops * 2e-9, plan.n_tail, est_sparse, est_band < 1e29 ? est_band : -1.0, est_dense);
+  if (fits && (mode == 1 || est_sparse < est_other)) { B->sparse = true; B->band_ld = 0; B->use_bcr = false; }
+}
+
+// ---- sharded: the column cut (separator mode) where the band admits one and the device holds the kernels' teams
+void choose_sharding(cs_ba* B) {
+  B->sep_mode = false; B->cut.clear(); B->sepw.clear(); B->sep_off.clear(); B->n_sep = 0; B->w_max = 0; B->msg_doubles = 0;
+  B->int_c = B->int_n = B->zl = B->wl = B->zr = B->wr = 0;
+  const int R = B->shard_n;
+  if (R <= 1 || B->band_ld <= 0 || getenv("CS_BA_SHARD_ALLREDUCE") != nullptr) return;
+  std::vector<int> cut, sepw;
+  if (!cs::separator_cut(B->cam_col, B->cub_col, B->n_red, B->band_ld, R, cut, sepw)) return;
+  // the separator system (block tridiagonal, blocks <= w_max: a band of 2 w_max) goes through the same persistent kernels
+  int wm = 0, nsep = 0;
+  for (int k = 1; k < R; k++) { wm = std::max(wm, sepw[k]); nsep += sepw[k]; }
+  // the interiors go through the ONE-SIDED kernel (grid = team + 1), whose residency depends on LD only: every rank decides alike
+  int ni_max = 0;
+  for (int r = 0; r < R; r++) ni_max = std::max(ni_max, cut[r + 1] - cut[r] - sepw[r]);
+  if (!cs::ba_band_fits_device(nsep, 2 * wm) || !cs::ba_band_fits_device(ni_max, B->band_ld, true)) return;
+  B->sep_mode = true; B->cut = cut; B->sepw = sepw;
+  B->sep_off.assign(R + 1, 0);
+  for (int k = 1; k < R; k++) { B->sep_off[k + 1] = B->sep_off[k] + sepw[k]; B->w_max = std::max(B->w_max, sepw[k]); }
+  B->n_sep = B->sep_off[R];
+  B->msg_doubles = 3 * (size_t)B->w_max * B->w_max + 2 * (size_t)B->w_max;
+  const int r = B->shard_rank;
+  B->zl = cut[r]; B->wl = sepw[r]; B->int_c = cut[r] + sepw[r]; B->int_n = cut[r + 1] - B->int_c;
+  B->zr = cut[r + 1]; B->wr = (r + 1 < R) ? sepw[r + 1] : 0;
+}
+
+// stereo edges: which records are the same for every edge (the structure is unsharded here: cs_ba_set_shard refuses a stereo graph, so E = n_proj)
+int decide_stereo_uniform(cs_ba* B, int E, int nM, int nS) {
+  if (nS <= 0) return CS_OK;
+  if (B->shard_n > 1 || E != B->n_proj) { cs_set_error("stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
+  const char* env = getenv("CS_BA_UNIFORM");
+  const bool on = !env || atoi(env) != 0;
+  if (nM == 0) std::memcpy(B->uni8 + 4, B->h_se_intr.data(), 32);      // (no mono edge: the first stereo edge's intrinsics are the reference record)
+  B->intr_uniform_all = nM > 0 ? B->intr_uniform : on;
+  B->sinfo_uniform = on;
+  for (int s = 0; s < nS && (B->intr_uniform_all || B->sinfo_uniform); s++) {
+    if (B->intr_uniform_all && std::memcmp(&B->h_se_intr[4 * (size_t)s], B->uni8 + 4, 32) != 0) B->intr_uniform_all = false;
+    if (B->sinfo_uniform && std::memcmp(&B->h_se_sinfo[10 * (size_t)s], B->h_se_sinfo.data(), 80) != 0) B->sinfo_uniform = false;
   }
-  mark("  point-major order");
-  // camera-major: a stable counting sort of the point-major slots by camera, the slots cut into NTH ranges (per-range histograms)
-  UBuf<int>& cm_pm = B->st_cm_pm; UBuf<int>& cm_pt = B->st_cm_pt;
-  cm_pm.ensure((size_t)E); cm_pt.ensure((size_t)E);
-  std::vector<int> cam_ptr(nc + 1, 0);
-  {
-    std::vector<std::vector<int>> hist(NTH, std::vector<int>(nc, 0));
-    auto count = [&](int t) { for (int sl = (int)((long long)E * t / NTH), s1 = (int)((long long)E * (t + 1) / NTH); sl < s1; sl++) hist[t][pm_cam[sl]]++; };
-    auto fillr = [&](int t) { std::vector<int>& h = hist[t]; for (int sl = (int)((long long)E * t / NTH), s1 = (int)((long long)E * (t + 1) / NTH); sl < s1; sl++) { const int q = h[pm_cam[sl]]++; cm_pm[q] = sl; cm_pt[q] = pm_pt[sl]; } };
-    auto run_threads = [&](const std::function<void(int)>& fn) {
-      run_items(NTH, fn);
-    };
-    run_threads(count);
-    int run = 0;
-    for (int c = 0; c < nc; c++) {
-      cam_ptr[c] = run;
-      for (int t = 0; t < NTH; t++) { const int v = hist[t][c]; hist[t][c] = run; run += v; }    // where range t starts writing camera c
-    }
-    cam_ptr[nc] = run;
-    run_threads(fillr);
-  }
-  mark("  index arrays (point-major, camera-major)");
-  // The edge tables go to the device from a second host thread while this one builds the Schur schedule (host work only): five
-  // arrays of E ints through blocking copies (0.3-0.4 ms each at a million edges, from pageable memory), the zero-fills and the eight
-  // gathers that put the caller's measurement rows into both edge orders.  Everything is queued on B->st; the phase's one wait is
-  // at its end.  (The staging arena is this thread's: the helper copies directly.)
-  // stereo edges: which records are the same for every edge (the structure is unsharded here: cs_ba_set_shard refuses a stereo graph, so E = n_proj)
-  const int nS = B->n_stereo, nM = B->n_proj - nS;
+  return CS_OK;
+}
+
+// The edge tables go to the device from a second host thread while the caller's builds the Schur schedule (host work only): five
+// arrays of E ints through blocking copies (0.3-0.4 ms each at a million edges, from pageable memory), the zero-fills and the eight
+// gathers that put the caller's measurement rows into both edge orders.  Everything is queued on B->st; the phase's one wait is
+// at its end.  (The staging arena is the caller's thread's: this one copies directly.)
+int upload_edge_tables(cs_ba* B, const cs::EdgeOrders& O, int nM, int nS) {
+  CS_HIP_TRY(hipSetDevice(B->device));
+  const int E = O.E;
+  const size_t Ez = (size_t)E;
+  CS_TRY(B->cm_pm.upload_ptr(O.cm_pm, Ez)); CS_TRY(B->d_src.upload_ptr(O.src_of_slot, Ez));
+  // (the information / intrinsics records in the two edge orders only when they differ between edges: BaView::info_u / intr_u otherwise)
+  bool per_info = !B->info_uniform, per_intr = !B->intr_uniform, have_hub = B->have_huber;
+  const double* src_uv = B->raw_uv.p; const double* src_info = B->raw_info.p; const double* src_intr = B->raw_intr.p; const double* src_huber = B->raw_huber.p;
   if (nS > 0) {
-    if (B->shard_n > 1 || E != B->n_proj) { cs_set_error("stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
-    const char* env = getenv("CS_BA_UNIFORM");
-    const bool on = !env || atoi(env) != 0;
-    if (nM == 0) std::memcpy(B->uni8 + 4, B->h_se_intr.data(), 32);      // (no mono edge: the first stereo edge's intrinsics are the reference record)
-    B->intr_uniform_all = nM > 0 ? B->intr_uniform : on;
-    B->sinfo_uniform = on;
-    for (int s = 0; s < nS && (B->intr_uniform_all || B->sinfo_uniform); s++) {
-      if (B->intr_uniform_all && std::memcmp(&B->h_se_intr[4 * (size_t)s], B->uni8 + 4, 32) != 0) B->intr_uniform_all = false;
-      if (B->sinfo_uniform && std::memcmp(&B->h_se_sinfo[10 * (size_t)s], B->h_se_sinfo.data(), 80) != 0) B->sinfo_uniform = false;
-    }
-  }
-  int edge_rc = CS_OK;
-  std::thread edge_th([&]() {
-    edge_rc = [&]() -> int {
-      CS_HIP_TRY(hipSetDevice(B->device));
-      int r;
-      const size_t Ez = (size_t)E;
-#define ER(call) do { r = (call); if (r) return r; } while (0)
-      ER(B->cm_pm.upload_ptr(cm_pm.data(), Ez)); ER(B->d_src.upload_ptr(src_of_slot, Ez));
-      // (the information / intrinsics records in the two edge orders only when they differ between edges: BaView::info_u / intr_u otherwise)
-      bool per_info = !B->info_uniform, per_intr = !B->intr_uniform, have_hub = B->have_huber;
-      const double* src_uv = B->raw_uv.p; const double* src_info = B->raw_info.p; const double* src_intr = B->raw_intr.p; const double* src_huber = B->raw_huber.p;
-      if (nS > 0) {
-        // A stereo graph: the gathers below index rows in e_pt's order -- the mono edges' rows (on the device since they were set), then the stereo
-        // edges' (on the host) -- so the two are put behind each other first.  A mono edge's slot of a stereo-only field stays zero and the reverse.
-        const size_t Mz = (size_t)nM, Sz = (size_t)nS;
-        auto rows = [&](DBuf<double>& comb, int w, const double* mono_dev, const double* mono_rec4, const double* st_host) -> int {
-          int rr = comb.reserve((size_t)w * (Mz + Sz)); if (rr) return rr;
-          comb.n = (size_t)w * (Mz + Sz);
-          if (Mz && mono_dev) CS_HIP_TRY(hipMemcpyAsync(comb.p, mono_dev, 8 * (size_t)w * Mz, hipMemcpyDeviceToDevice, B->st));
-          else if (Mz && mono_rec4) cs::ba_launch_fill_rows4(comb.p, mono_rec4, nM, B->st);
-          else if (Mz) CS_HIP_TRY(hipMemsetAsync(comb.p, 0, 8 * (size_t)w * Mz, B->st));
-          if (st_host) CS_HIP_TRY(hipMemcpy(comb.p + (size_t)w * Mz, st_host, 8 * (size_t)w * Sz, hipMemcpyHostToDevice));
-          else CS_HIP_TRY(hipMemsetAsync(comb.p + (size_t)w * Mz, 0, 8 * (size_t)w * Sz, B->st));
-          return CS_OK;
-        };
-        per_info = nM > 0 && !B->info_uniform; per_intr = !B->intr_uniform_all; have_hub = B->have_huber || !B->h_se_huber.empty();
-        ER(rows(B->comb_uv, 2, B->raw_uv.p, nullptr, B->h_se_uv.data())); src_uv = B->comb_uv.p;
-        if (per_info) { ER(rows(B->comb_info, 4, B->raw_info.p, nullptr, nullptr)); src_info = B->comb_info.p; }
-        if (per_intr) { ER(rows(B->comb_intr, 4, B->raw_intr_virtual ? nullptr : B->raw_intr.p, B->uni8 + 4, B->h_se_intr.data())); src_intr = B->comb_intr.p; }
-        if (have_hub) { ER(rows(B->comb_huber, 1, B->have_huber ? B->raw_huber.p : nullptr, nullptr, B->h_se_huber.empty() ? nullptr : B->h_se_huber.data())); src_huber = B->comb_huber.p; }
-        // the stereo-only fields in both orders, built here from the host rows
-        const bool per_sinfo = !B->sinfo_uniform;
-        std::vector<int> pk(Ez), ck(Ez);
-        std::vector<double> pu(Ez), cu(Ez), ps(per_sinfo ? 10 * Ez : 0), cs10(per_sinfo ? 10 * Ez : 0);
-        for (size_t sl = 0; sl < Ez; sl++) {
-          const int s = src_of_slot[sl] - nM;
-          pk[sl] = s >= 0; pu[sl] = s >= 0 ? B->h_se_ur[s] : 0.0;
-          if (per_sinfo) { if (s >= 0) std::memcpy(&ps[10 * sl], &B->h_se_sinfo[10 * (size_t)s], 80); else std::memset(&ps[10 * sl], 0, 80); }
-        }
-        for (size_t q = 0; q < Ez; q++) {
-          const size_t sl = (size_t)cm_pm[q];
-          ck[q] = pk[sl]; cu[q] = pu[sl];
-          if (per_sinfo) std::memcpy(&cs10[10 * q], &ps[10 * sl], 80);
-        }
-        ER(B->d_pm_kind.upload(pk)); ER(B->d_cm_kind.upload(ck)); ER(B->d_pm_ur.upload(pu)); ER(B->d_cm_ur.upload(cu));
-        if (per_sinfo) { ER(B->d_pm_sinfo.upload(ps)); ER(B->d_cm_sinfo.upload(cs10)); }
-      }
-      ER(B->pm_uv.alloc(2 * Ez, B->st)); ER(B->pm_huber.alloc(Ez, B->st)); ER(B->cm_uv.alloc(2 * Ez, B->st)); ER(B->cm_huber.alloc(Ez, B->st));
-      if (per_info) { ER(B->pm_info.alloc(4 * Ez, B->st)); ER(B->cm_info.alloc(4 * Ez, B->st)); }
-      if (per_intr) { ER(B->pm_intr.alloc(4 * Ez, B->st)); ER(B->cm_intr.alloc(4 * Ez, B->st)); }
-      cs::ba_launch_gather_rows(src_uv, B->d_src.p, E, 2, B->pm_uv.p, B->st);
-      if (per_info) cs::ba_launch_gather_rows(src_info, B->d_src.p, E, 4, B->pm_info.p, B->st);
-      if (per_intr) cs::ba_launch_gather_rows(src_intr, B->d_src.p, E, 4, B->pm_intr.p, B->st);
-      // the width records: widths <= 0 (no kernel) as +0.0, the sign bit = the edge's level (ba_kernels.hip: edge_off); levels exist -> their
-      // bytes in e_pt's order go up first (the only per-edge upload a level costs, and only here)
-      const unsigned char* lvl_dev = nullptr;
-      {
-        std::vector<unsigned char> lv;
-        B->lvl_on_device = combined_proj_levels(B, nM, nS, lv);
-        if (B->lvl_on_device) { ER(B->d_lvl.upload(lv)); lvl_dev = B->d_lvl.p; B->lvl_nM = nM; B->lvl_nS = nS; }
-      }
-      if (have_hub || lvl_dev) cs::ba_launch_gather_widths(have_hub ? src_huber : nullptr, B->d_src.p, lvl_dev, E, B->pm_huber.p, B->st);   // (else: zeros from the allocation)
-      cs::ba_launch_gather_rows(B->pm_uv.p, B->cm_pm.p, E, 2, B->cm_uv.p, B->st);
-      if (per_info) cs::ba_launch_gather_rows(B->pm_info.p, B->cm_pm.p, E, 4, B->cm_info.p, B->st);
-      if (per_intr) cs::ba_launch_gather_rows(B->pm_intr.p, B->cm_pm.p, E, 4, B->cm_intr.p, B->st);
-      cs::ba_launch_gather_rows(B->pm_huber.p, B->cm_pm.p, E, 1, B->cm_huber.p, B->st);
-      CS_HIP_TRY(hipGetLastError());
-      ER(B->pm_pt.upload_ptr(pm_pt.data(), Ez)); ER(B->pm_cam.upload_ptr(pm_cam.data(), Ez)); ER(B->cm_pt.upload_ptr(cm_pt.data(), Ez));
-#undef ER
+    // A stereo graph: the gathers below index rows in e_pt's order -- the mono edges' rows (on the device since they were set), then the stereo
+    // edges' (on the host) -- so the two are put behind each other first.  A mono edge's slot of a stereo-only field stays zero and the reverse.
+    const size_t Mz = (size_t)nM, Sz = (size_t)nS;
+    auto rows = [&](DBuf<double>& comb, int w, const double* mono_dev, const double* mono_rec4, const double* st_host) -> int {
+      CS_TRY(comb.reserve((size_t)w * (Mz + Sz)));
+      comb.n = (size_t)w * (Mz + Sz);
+      if (Mz && mono_dev) CS_HIP_TRY(hipMemcpyAsync(comb.p, mono_dev, 8 * (size_t)w * Mz, hipMemcpyDeviceToDevice, B->st));
+      else if (Mz && mono_rec4) cs::ba_launch_fill_rows4(comb.p, mono_rec4, nM, B->st);
+      else if (Mz) CS_HIP_TRY(hipMemsetAsync(comb.p, 0, 8 * (size_t)w * Mz, B->st));
+      if (st_host) CS_HIP_TRY(hipMemcpy(comb.p + (size_t)w * Mz, st_host, 8 * (size_t)w * Sz, hipMemcpyHostToDevice));
+      else CS_HIP_TRY(hipMemsetAsync(comb.p + (size_t)w * Mz, 0, 8 * (size_t)w * Sz, B->st));
       return CS_OK;
-    }();
-  });
-  struct JoinEdge { std::thread& t; ~JoinEdge() { if (t.joinable()) t.join(); } } join_edge{edge_th};
-  UP(B->pt_ptr, pt_ptr);
-  {   // kernel kinds of the projection edges in both orders -- only if some edge has a kernel other than Huber
-    bool generic = false;
-    for (int kd : B->rk_proj) if (kd != cs::RK_NONE && kd != cs::RK_HUBER) { generic = true; break; }
-    for (int kd : B->rk_stereo) if (kd != cs::RK_NONE && kd != cs::RK_HUBER) { generic = true; break; }
-    if (generic && nS > 0) {
-      // (a class without a kind list has Huber wherever its delta is positive: with a kind array on the device every edge is looked up in it)
-      std::vector<double> hub_m;
-      if (B->rk_proj.empty() && B->have_huber && nM > 0) { hub_m.resize((size_t)nM); CS_HIP_TRY(hipMemcpy(hub_m.data(), B->raw_huber.p, 8 * (size_t)nM, hipMemcpyDeviceToHost)); }
-      auto kind_of = [&](int src) -> int {
-        if (src < nM) return !B->rk_proj.empty() ? B->rk_proj[src] : (!hub_m.empty() && hub_m[src] > 0 ? cs::RK_HUBER : cs::RK_NONE);
-        const int s2 = src - nM;
-        return !B->rk_stereo.empty() ? B->rk_stereo[s2] : (!B->h_se_huber.empty() && B->h_se_huber[s2] > 0 ? cs::RK_HUBER : cs::RK_NONE);
-      };
-      std::vector<int> pk(std::max(1, E), 0), ck(std::max(1, E), 0);
-      for (int sl = 0; sl < E; sl++) pk[sl] = kind_of(src_of_slot[sl]);
-      for (int q = 0; q < E; q++) ck[q] = pk[cm_pm[q]];
-      UP(B->d_pm_rk, pk); UP(B->d_cm_rk, ck);
-    } else if (generic) {
-      std::vector<int> pk(std::max(1, E), 0), ck(std::max(1, E), 0);
-      for (int sl = 0; sl < E; sl++) pk[sl] = B->rk_proj[src_of_slot[sl]];
-      for (int q = 0; q < E; q++) ck[q] = pk[cm_pm[q]];
-      UP(B->d_pm_rk, pk); UP(B->d_cm_rk, ck);
-    } else { B->d_pm_rk.release(); B->d_cm_rk.release(); }
+    };
+    per_info = nM > 0 && !B->info_uniform; per_intr = !B->intr_uniform_all; have_hub = B->have_huber || !B->h_se_huber.empty();
+    CS_TRY(rows(B->comb_uv, 2, B->raw_uv.p, nullptr, B->h_se_uv.data())); src_uv = B->comb_uv.p;
+    if (per_info) { CS_TRY(rows(B->comb_info, 4, B->raw_info.p, nullptr, nullptr)); src_info = B->comb_info.p; }
+    if (per_intr) { CS_TRY(rows(B->comb_intr, 4, B->raw_intr_virtual ? nullptr : B->raw_intr.p, B->uni8 + 4, B->h_se_intr.data())); src_intr = B->comb_intr.p; }
+    if (have_hub) { CS_TRY(rows(B->comb_huber, 1, B->have_huber ? B->raw_huber.p : nullptr, nullptr, B->h_se_huber.empty() ? nullptr : B->h_se_huber.data())); src_huber = B->comb_huber.p; }
+    // the stereo-only fields in both orders, built here from the host rows
+    const bool per_sinfo = !B->sinfo_uniform;
+    std::vector<int> pk(Ez), ck(Ez);
+    std::vector<double> pu(Ez), cu(Ez), ps(per_sinfo ? 10 * Ez : 0), cs10(per_sinfo ? 10 * Ez : 0);
+    for (size_t sl = 0; sl < Ez; sl++) {
+      const int s = O.src_of_slot[sl] - nM;
+      pk[sl] = s >= 0; pu[sl] = s >= 0 ? B->h_se_ur[s] : 0.0;
+      if (per_sinfo) { if (s >= 0) std::memcpy(&ps[10 * sl], &B->h_se_sinfo[10 * (size_t)s], 80); else std::memset(&ps[10 * sl], 0, 80); }
+    }
+    for (size_t q = 0; q < Ez; q++) {
+      const size_t sl = (size_t)O.cm_pm[q];
+      ck[q] = pk[sl]; cu[q] = pu[sl];
+      if (per_sinfo) std::memcpy(&cs10[10 * q], &ps[10 * sl], 80);
+    }
+    CS_TRY(B->d_pm_kind.upload(pk)); CS_TRY(B->d_cm_kind.upload(ck)); CS_TRY(B->d_pm_ur.upload(pu)); CS_TRY(B->d_cm_ur.upload(cu));
+    if (per_sinfo) { CS_TRY(B->d_pm_sinfo.upload(ps)); CS_TRY(B->d_cm_sinfo.upload(cs10)); }
   }
-  UP(B->cam_ptr, cam_ptr);
-  mark("edge orderings + upload");
-  // ---- Schur pattern (block_solver.hpp:262-292).  Fused path: segments of landmarks with one camera set + the destination
-  // schedule of their partial blocks (BaView::fused).  It needs every landmark to be seen by <= BA_LONG_KMAX cameras; otherwise
-  // (or with CS_BA_SCHUR_PAIRS=1, diagnostics) the pair-major path: (landmark, i1 <= i2) entries grouped by camera pair.
-  B->fused = fused_ok;        // (CS_BA_SCHUR_PAIRS unset, no track beyond BA_LONG_KMAX views, long tracks a minority: decided with the orderings above)
-  for (int p : gorder) if (owner[p] == B->shard_rank && cam_cnt[p + 1] - cam_cnt[p] > cs::BA_LONG_KMAX) { B->fused = false; break; }
-  B->n_seg = 0; B->n_gpairs = 0; B->seg_class[0] = B->seg_class[1] = B->seg_class[2] = B->seg_class[3] = B->seg_class[4] = 0;
-  B->schur_entries = 0;
-  for (int p : gorder) if (owner[p] == B->shard_rank) { const long long k = cam_cnt[p + 1] - cam_cnt[p]; B->schur_entries += k * (k + 1) / 2; }
-  if (B->fused) {
-    std::vector<int> run_lm, seg_ptr{0}, seg_k, seg_tile, seg_slot, run_e0, seg_cam;
-    struct Dst { int a, b, id; };
-    std::vector<Dst> dst;                      // (destination block = its two columns, partial block id), in creation order: ids grow
-    std::vector<std::pair<int, int>> cdst;     // (camera, partial vector id)
-    const long long NP = std::max(1, B->n_pose);
-    int n_tiles = 0, n_slots = 0;
-    // Two passes over the runs (camera sets), both threaded: what a run contributes to every table is a function of its size and its cameras
-    // alone -- count, prefix over the runs, then every run writes its own ranges.  (Round 6; one thread appending to ten vectors was 2.5-3.3 ms
-    // at C4.  Same tables, entry for entry: the no-GPU digest test holds the threaded build to the sequential one.)
-    {
-      const size_t R = run_first.size() > 0 ? run_first.size() - 1 : 0;
-      struct RunCnt { int m, k, f, dps; };       // owned landmarks, cameras, free cameras, destination blocks per segment
-      std::vector<RunCnt> rc_(R);
-      std::vector<int> slot_cam_all;             // every run's cameras in slot order (by column, then id), run after run
-      std::vector<size_t> sc_off(R + 1, 0);
-      for (size_t r = 0; r < R; r++) { const int p0 = gorder[run_first[r]]; sc_off[r + 1] = sc_off[r] + (size_t)(cam_cnt[p0 + 1] - cam_cnt[p0]); }
-      slot_cam_all.resize(sc_off[R]);
-      const int NTs = R > 256 ? struct_threads() : 1;
-      run_items(NTs, [&](int t) {
-        for (size_t r = R * t / NTs, r1 = R * (t + 1) / NTs; r < r1; r++) {
-          const int p0 = gorder[run_first[r]], k = cam_cnt[p0 + 1] - cam_cnt[p0];
-          int* sc = slot_cam_all.data() + sc_off[r];
-          std::copy(cams_of.begin() + cam_cnt[p0], cams_of.begin() + cam_cnt[p0 + 1], sc);
-          std::sort(sc, sc + k, [&](int x, int y) { return B->cam_col[x] != B->cam_col[y] ? B->cam_col[x] < B->cam_col[y] : x < y; });
-          int m = 0, f = 0, dps = 0;
-          for (int q = run_first[r]; q < run_first[r + 1]; q++) m += owner[gorder[q]] == B->shard_rank ? 1 : 0;
-          for (int a2 = 0; a2 < k; a2++) if (B->cam_col[sc[a2]] >= 0) { f++; dps += k - a2; }
-          rc_[r] = RunCnt{m, k, f, dps};
-        }
-      });
-      // where every run starts in every table
-      std::vector<size_t> o_lm(R + 1, 0), o_seg(R + 1, 0), o_cam(R + 1, 0), o_dst(R + 1, 0), o_cd(R + 1, 0);
-      std::vector<int> o_tile(R + 1, 0), o_slot(R + 1, 0);
-      for (size_t r = 0; r < R; r++) {
-        const int ns = (rc_[r].m + cs::BA_SEG_LM - 1) / cs::BA_SEG_LM, k = rc_[r].k;
-        o_lm[r + 1] = o_lm[r] + rc_[r].m; o_seg[r + 1] = o_seg[r] + ns; o_cam[r + 1] = o_cam[r] + (size_t)ns * k;
-        o_dst[r + 1] = o_dst[r] + (size_t)ns * rc_[r].dps; o_cd[r + 1] = o_cd[r] + (size_t)ns * rc_[r].f;
-        o_tile[r + 1] = o_tile[r] + ns * (k * (k + 1) / 2); o_slot[r + 1] = o_slot[r] + ns * k;
-      }
-      run_lm.resize(o_lm[R]); run_e0.resize(o_lm[R]); seg_ptr.assign(o_seg[R] + 1, 0); seg_k.resize(o_seg[R]); seg_tile.resize(o_seg[R]); seg_slot.resize(o_seg[R]);
-      seg_cam.resize(o_cam[R]);
-      {   // (room for what the eliminated cuboids append below: without it their first push_back copies the whole table)
-        size_t cub_dst = 0, cub_cd = 0;
-        if (B->elim) for (int o = 0; o < no; o++) if (!B->cub_fixed[o]) { const size_t kc = cub_cams[o].size(); cub_dst += kc * (kc + 1) / 2; cub_cd += kc; }
-        dst.reserve(o_dst[R] + cub_dst); cdst.reserve(o_cd[R] + cub_cd);
-      }
-      dst.resize(o_dst[R]); cdst.resize(o_cd[R]);
-      run_items(NTs, [&](int t) {
-        for (size_t r = R * t / NTs, r1 = R * (t + 1) / NTs; r < r1; r++) {
-          const int k = rc_[r].k;
-          const int* sc = slot_cam_all.data() + sc_off[r];
-          size_t lm = o_lm[r], sg = o_seg[r], cm = o_cam[r], ds = o_dst[r], cd = o_cd[r];
-          int tiles = o_tile[r], slots = o_slot[r], in_seg = 0;
-          for (int q = run_first[r]; q < run_first[r + 1]; q++) {
-            const int p = gorder[q];
-            if (owner[p] != B->shard_rank) continue;
-            if (in_seg == 0) {   // open a segment
-              seg_k[sg] = k; seg_tile[sg] = tiles; seg_slot[sg] = slots;
-              for (int a2 = 0; a2 < k; a2++) seg_cam[cm++] = sc[a2];      // (= pm_cam[pt_ptr[p] + a]: the point-major order of a landmark's edges is this slot order)
-              for (int a2 = 0; a2 < k; a2++) {
-                const int ca = B->cam_col[sc[a2]];
-                if (ca < 0) continue;
-                cdst[cd++] = {sc[a2], slots + a2};
-                for (int b2 = a2; b2 < k; b2++) dst[ds++] = Dst{ca, B->cam_col[sc[b2]], tiles + a2 * k - a2 * (a2 - 1) / 2 + (b2 - a2)};
-              }
-              tiles += k * (k + 1) / 2; slots += k;
-            }
-            run_lm[lm] = p; run_e0[lm] = pt_ptr[p]; lm++;
-            if (++in_seg == cs::BA_SEG_LM) { seg_ptr[++sg] = (int)lm; in_seg = 0; }
-          }
-          if (in_seg) seg_ptr[++sg] = (int)lm;
-        }
-      });
-      n_tiles = R ? o_tile[R] : 0; n_slots = R ? o_slot[R] : 0;
-    }
-    mark("  segments of the runs");
-    // the eliminated cuboids join the destination schedule: per free cuboid one slot per observing camera (by column), the upper
-    // triangle of slot pairs as partial blocks, one partial vector per slot
-    std::vector<int> cubS_ptr(no + 1, 0), cubS_cam, ce_slot(B->n_cub, -1), cub_tile(no, 0), cub_coef(no, 0);
-    if (B->elim) {
-      for (int o = 0; o < no; o++) {
-        cubS_ptr[o] = (int)cubS_cam.size();
-        if (B->cub_fixed[o]) continue;
-        std::vector<int> sc = cub_cams[o];
-        std::sort(sc.begin(), sc.end(), [&](int a, int b) { return B->cam_col[a] != B->cam_col[b] ? B->cam_col[a] < B->cam_col[b] : a < b; });
-        const int k = (int)sc.size();
-        cub_tile[o] = n_tiles; cub_coef[o] = n_slots;
-        for (int a = 0; a < k; a++) {
-          cubS_cam.push_back(sc[a]);
-          cdst.push_back({sc[a], n_slots + a});
-          for (int b = a; b < k; b++) dst.push_back(Dst{B->cam_col[sc[a]], B->cam_col[sc[b]], n_tiles + a * k - a * (a - 1) / 2 + (b - a)});
-        }
-        n_tiles += k * (k + 1) / 2; n_slots += k;
-      }
-      cubS_ptr[no] = (int)cubS_cam.size();
-      for (int k = 0; k < B->n_cub; k++) {
-        const int o = B->ce_cub[k], c = B->ce_cam[k];
-        if (B->cub_fixed[o] || B->cam_fixed[c]) continue;
-        for (int q = cubS_ptr[o]; q < cubS_ptr[o + 1]; q++) if (cubS_cam[q] == c) { ce_slot[k] = q; break; }
-      }
-    } else {
-      for (int o = 0; o <= no; o++) cubS_ptr[o] = 0;
-    }
-    // edges of a slot, in edge order (a camera may hold an EdgeSE3Cuboid and an EdgeSE3CuboidProj to one cuboid)
-    std::vector<int> slotE_ptr(cubS_cam.size() + 1, 0), slotE_idx;
-    {
-      for (int k = 0; k < B->n_cub; k++) if (ce_slot[k] >= 0) slotE_ptr[ce_slot[k] + 1]++;
-      for (size_t q = 0; q < cubS_cam.size(); q++) slotE_ptr[q + 1] += slotE_ptr[q];
-      slotE_idx.assign(std::max(1, slotE_ptr.back()), 0);
-      std::vector<int> fill(slotE_ptr.begin(), slotE_ptr.end() - 1);
-      for (int k = 0; k < B->n_cub; k++) if (ce_slot[k] >= 0) slotE_idx[fill[ce_slot[k]]++] = k;
-    }
-    UP(B->d_slotE_ptr, slotE_ptr); UP(B->d_slotE_idx, slotE_idx);
-    if (cubS_cam.empty()) cubS_cam.push_back(0);
-    if (ce_slot.empty()) ce_slot.push_back(-1);
-    if (cub_tile.empty()) { cub_tile.push_back(0); cub_coef.push_back(0); }
-    UP(B->d_cubS_ptr, cubS_ptr); UP(B->d_cubS_cam, cubS_cam); UP(B->d_ce_slot, ce_slot); UP(B->d_cub_tile, cub_tile); UP(B->d_cub_coef, cub_coef);
-    AL(B->cub_M, 54 * cubS_cam.size()); AL(B->cub_Dinv, 81 * (size_t)std::max(1, no)); AL(B->d_elim_fail, 1); ZFLUSH();
-    B->n_seg = (int)seg_k.size();
-    for (int sgi = 0; sgi < B->n_seg; sgi++) {   // segments are sorted by k
-      if (seg_k[sgi] <= 2) B->seg_class[0] = sgi + 1;
-      if (seg_k[sgi] <= 5) B->seg_class[1] = sgi + 1;
-      if (seg_k[sgi] <= 7) B->seg_class[2] = sgi + 1;
-      if (seg_k[sgi] <= 10) B->seg_class[3] = sgi + 1;
-      if (seg_k[sgi] <= cs::BA_FUSED_KMAX) B->seg_class[4] = sgi + 1;
-    }
-    mark("  cuboid slots");
-    // by destination block, the partial blocks of one destination in creation (= segment) order: ids grow with creation, so (key, id) is the stable order
-    // (two stable counting passes over the columns -- second column, then first -- instead of a comparison sort: 0.66 -> 0.06 ms at 200 cameras,
-    // a third of this phase at 1 000)
-    {
-      std::vector<Dst> tmp(dst.size());
-      std::vector<int> cnt((size_t)NP + 2);
-      auto pass = [&](const std::vector<Dst>& in, std::vector<Dst>& out, bool by_b) {
-        std::fill(cnt.begin(), cnt.end(), 0);
-        for (const Dst& e : in) cnt[(by_b ? e.b : e.a) + 1]++;
-        for (size_t c = 0; c + 1 < cnt.size(); c++) cnt[c + 1] += cnt[c];
-        for (const Dst& e : in) out[cnt[by_b ? e.b : e.a]++] = e;
-      };
-      pass(dst, tmp, true);
-      pass(tmp, dst, false);
-    }
-    mark("  destination sort");
-    std::vector<int> gp_ptr, gp_i1, gp_i2, gtile(dst.size());
-    for (size_t i = 0; i < dst.size(); i++) {
-      if (i == 0 || dst[i].a != dst[i - 1].a || dst[i].b != dst[i - 1].b) { gp_ptr.push_back((int)i); gp_i1.push_back(dst[i].a); gp_i2.push_back(dst[i].b); }
-      gtile[i] = dst[i].id;
-    }
-    gp_ptr.push_back((int)dst.size());
-    B->n_gpairs = (int)gp_i1.size();
-    std::vector<int> gcam_ptr(nc + 1, 0), gslot(cdst.size());
-    for (auto& e : cdst) gcam_ptr[e.first + 1]++;
-    for (int i = 0; i < nc; i++) gcam_ptr[i + 1] += gcam_ptr[i];
-    { std::vector<int> fill(gcam_ptr.begin(), gcam_ptr.end() - 1); for (auto& e : cdst) gslot[fill[e.first]++] = e.second; }
-    mark("  destination lists");
-    UP(B->d_run_lm, run_lm); UP(B->d_seg_ptr, seg_ptr); UP(B->d_seg_k, seg_k); UP(B->d_seg_tile, seg_tile); UP(B->d_seg_slot, seg_slot);
-    UP(B->d_run_e0, run_e0); UP(B->d_seg_cam, seg_cam);
-    UP(B->d_gp_ptr, gp_ptr); UP(B->d_gp_i1, gp_i1); UP(B->d_gp_i2, gp_i2); UP(B->d_gtile, gtile); UP(B->d_gcam_ptr, gcam_ptr); UP(B->d_gslot, gslot);
-    AL(B->part_tiles, 36 * (size_t)n_tiles); AL(B->part_coef, 6 * (size_t)n_slots); ZFLUSH();
-    B->n_pairs = 0;
-    std::vector<int> none(1, 0);
-    UP(B->pair_ptr, none); UP(B->pair_i1, none); UP(B->pair_i2, none); UP(B->ent_a, none); UP(B->ent_b, none);
-  } else {
-    struct Ent { long long key; int a, b; };
-    std::vector<Ent> ents;
-    const long long NP = std::max(1, B->n_pose);
-    for (int p = 0; p < np; p++) {
-      if (!pt_free[p]) continue;
-      for (int a = pt_ptr[p]; a < pt_ptr[p + 1]; a++) {
-        int ca = B->cam_col[pm_cam[a]];
-        if (ca < 0) continue;
-        for (int b = a; b < pt_ptr[p + 1]; b++) {
-          int cb = B->cam_col[pm_cam[b]];
-          if (cb < 0) continue;
-          ents.push_back(Ent{(long long)ca * NP + cb, a, b});
-        }
-      }
-    }
-    std::stable_sort(ents.begin(), ents.end(), [](const Ent& x, const Ent& y) { return x.key < y.key; });
-    std::vector<int> pair_ptr, pair_i1, pair_i2, ent_a(ents.size()), ent_b(ents.size());
-    for (size_t i = 0; i < ents.size(); i++) {
-      if (i == 0 || ents[i].key != ents[i - 1].key) {
-        pair_ptr.push_back((int)i);
-        pair_i1.push_back((int)(ents[i].key / NP));
-        pair_i2.push_back((int)(ents[i].key % NP));
-      }
-      ent_a[i] = ents[i].a; ent_b[i] = ents[i].b;
-    }
-    pair_ptr.push_back((int)ents.size());
-    B->n_pairs = (int)pair_i1.size();
-    UP(B->pair_ptr, pair_ptr); UP(B->pair_i1, pair_i1); UP(B->pair_i2, pair_i2); UP(B->ent_a, ent_a); UP(B->ent_b, ent_b);
-    std::vector<int> none(1, 0);
-    UP(B->d_run_lm, none); UP(B->d_seg_ptr, none); UP(B->d_seg_k, none); UP(B->d_seg_tile, none); UP(B->d_seg_slot, none); UP(B->d_run_e0, none); UP(B->d_seg_cam, none);
-    UP(B->d_gp_ptr, none); UP(B->d_gp_i1, none); UP(B->d_gp_i2, none); UP(B->d_gtile, none); UP(B->d_gcam_ptr, none); UP(B->d_gslot, none);
-    AL(B->part_tiles, 1); AL(B->part_coef, 1); ZFLUSH();
-    std::vector<int> zp(no + 1, 0);
-    UP(B->d_slotE_ptr, none); UP(B->d_slotE_idx, none);
-    UP(B->d_cubS_ptr, zp); UP(B->d_cubS_cam, none); UP(B->d_ce_slot, none); UP(B->d_cub_tile, none); UP(B->d_cub_coef, none);
-    AL(B->cub_M, 1); AL(B->cub_Dinv, 1); AL(B->d_elim_fail, 1); ZFLUSH();
-  }
-  mark("Schur schedule");
-  // ---- cuboid / odometry edges and their vertex adjacency
-  auto csr = [&](int nv, const std::vector<int>& owner, std::vector<int>& ptr, std::vector<int>& idx) {
-    ptr.assign(nv + 1, 0);
-    for (int o : owner) ptr[o + 1]++;
-    for (int i = 0; i < nv; i++) ptr[i + 1] += ptr[i];
-    idx.resize(owner.size());
-    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-    for (size_t k = 0; k < owner.size(); k++) idx[fill[owner[k]]++] = (int)k;
-  };
-  std::vector<int> p1, i1, p2, i2, p3, i3, p4, i4;
-  csr(nc, B->ce_cam, p1, i1); csr(nc, oe_i, p2, i2); csr(nc, oe_j, p3, i3); csr(no, B->ce_cub, p4, i4);
-  UP(B->cam_ce_ptr, p1); UP(B->cam_ce_idx, i1); UP(B->cam_oei_ptr, p2); UP(B->cam_oei_idx, i2);
-  UP(B->cam_oej_ptr, p3); UP(B->cam_oej_idx, i3); UP(B->cub_ce_ptr, p4); UP(B->cub_ce_idx, i4);
-  UP(B->d_ce_cam, B->ce_cam); UP(B->d_ce_cub, B->ce_cub); UP(B->d_oe_i, oe_i); UP(B->d_oe_j, oe_j);
+  CS_TRY(B->pm_uv.alloc(2 * Ez, B->st)); CS_TRY(B->pm_huber.alloc(Ez, B->st)); CS_TRY(B->cm_uv.alloc(2 * Ez, B->st)); CS_TRY(B->cm_huber.alloc(Ez, B->st));
+  if (per_info) { CS_TRY(B->pm_info.alloc(4 * Ez, B->st)); CS_TRY(B->cm_info.alloc(4 * Ez, B->st)); }
+  if (per_intr) { CS_TRY(B->pm_intr.alloc(4 * Ez, B->st)); CS_TRY(B->cm_intr.alloc(4 * Ez, B->st)); }
+  cs::ba_launch_gather_rows(src_uv, B->d_src.p, E, 2, B->pm_uv.p, B->st);
+  if (per_info) cs::ba_launch_gather_rows(src_info, B->d_src.p, E, 4, B->pm_info.p, B->st);
+  if (per_intr) cs::ba_launch_gather_rows(src_intr, B->d_src.p, E, 4, B->pm_intr.p, B->st);
+  // the width records: widths <= 0 (no kernel) as +0.0, the sign bit = the edge's level (ba_kernels.hip: edge_off); levels exist -> their
+  // bytes in e_pt's order go up first (the only per-edge upload a level costs, and only here)
+  const unsigned char* lvl_dev = nullptr;
   {
-    std::vector<int> ca(B->n_cub), oa(B->n_odom);
-    // cuboid edges: with their camera's rank, or -- cuboids eliminated -- all edges of a cuboid with the rank of its lowest-index camera.
-    // Separator mode: by the lowest column among the free vertices involved (an eliminated cuboid: among its observing cameras).
-    std::vector<int> cub_owner(no, 0);
-    if (B->sep_mode) {
-      for (int o = 0; o < no; o++) {
-        int lo = 0x7fffffff;
-        for (int c : cub_cams[o]) lo = std::min(lo, B->cam_col[c]);
-        cub_owner[o] = lo == 0x7fffffff ? 0 : rank_of_col(lo);
-      }
-      for (int k = 0; k < B->n_cub; k++) {
-        const int o = B->ce_cub[k], c = B->ce_cam[k];
-        int own = 0;
-        if (B->elim && !B->cub_fixed[o]) own = cub_owner[o];
-        else {
-          int lo = 0x7fffffff;
-          if (B->cam_col[c] >= 0) lo = std::min(lo, B->cam_col[c]);
-          if (B->cub_col[o] >= 0 && B->cub_col[o] < B->n_red) lo = std::min(lo, B->cub_col[o]);
-          own = lo == 0x7fffffff ? 0 : rank_of_col(lo);
-        }
-        ca[k] = own == B->shard_rank;
-      }
-      for (int k = 0; k < B->n_odom; k++) {
-        int lo = 0x7fffffff;
-        if (B->cam_col[oe_i[k]] >= 0) lo = std::min(lo, B->cam_col[oe_i[k]]);
-        if (B->cam_col[oe_j[k]] >= 0) lo = std::min(lo, B->cam_col[oe_j[k]]);
-        oa[k] = (lo == 0x7fffffff ? 0 : rank_of_col(lo)) == B->shard_rank;
-      }
-    } else {
-      std::vector<int> first(no, 0x7fffffff);
-      for (int k = 0; k < B->n_cub; k++) first[B->ce_cub[k]] = std::min(first[B->ce_cub[k]], B->ce_cam[k]);
-      for (int o = 0; o < no; o++) cub_owner[o] = first[o] == 0x7fffffff ? 0 : cam_rank(first[o], nc, B->shard_n);
-      for (int k = 0; k < B->n_cub; k++) ca[k] = (B->elim ? cub_owner[B->ce_cub[k]] : cam_rank(B->ce_cam[k], nc, B->shard_n)) == B->shard_rank;
-      for (int k = 0; k < B->n_odom; k++) oa[k] = cam_rank(oe_j[k], nc, B->shard_n) == B->shard_rank;
-    }
-    {
-      std::vector<int> mine(std::max(1, no), 0);
-      for (int o = 0; o < no; o++) mine[o] = cub_owner[o] == B->shard_rank;
-      UP(B->d_cub_mine, mine);
-    }
-    B->h_ce_shard = ca; B->h_oe_shard = oa;
-    for (cs::EdgeClassHost& c : B->ec) c.lvl.resize(any_level(c.lvl) ? (size_t)c.size() : 0);
-    fold_pose_levels(B, ca, oa);      // (a level-1 edge gives zero blocks and no chi2, like an edge of another rank)
-    UP(B->d_ce_active, ca); UP(B->d_oe_active, oa);
+    std::vector<unsigned char> lv;
+    B->lvl_on_device = combined_proj_levels(B, nM, nS, lv);
+    if (B->lvl_on_device) { CS_TRY(B->d_lvl.upload(lv)); lvl_dev = B->d_lvl.p; B->lvl_nM = nM; B->lvl_nS = nS; }
   }
-  {   // kernels of the camera-cuboid edges (EdgeSE3Cuboid list, then EdgeSE3CuboidProj list) and of the odometry edges
-    auto any_kernel = [](const std::vector<int>& kinds) { for (int kd : kinds) if (kd != 0) return true; return false; };
-    const std::vector<int> kc = combined_cuboid(B, &cs::EdgeClassHost::rk, 1);
-    if (any_kernel(kc)) {
-      const std::vector<double> dc = combined_cuboid(B, &cs::EdgeClassHost::rd, 1);
-      UP(B->d_ce_rk, kc); UP(B->d_ce_rdelta, dc);
-    } else { B->d_ce_rk.release(); B->d_ce_rdelta.release(); }
-    if (any_kernel(od.rk)) {
-      std::vector<int> kk(od.rk); std::vector<double> dd(od.rd);
-      kk.resize(std::max(1, B->n_odom), 0); dd.resize(std::max(1, B->n_odom), 0.0);
-      UP(B->d_oe_rk, kk); UP(B->d_oe_rdelta, dd);
-    } else { B->d_oe_rk.release(); B->d_oe_rdelta.release(); }
+  if (have_hub || lvl_dev) cs::ba_launch_gather_widths(have_hub ? src_huber : nullptr, B->d_src.p, lvl_dev, E, B->pm_huber.p, B->st);   // (else: zeros from the allocation)
+  cs::ba_launch_gather_rows(B->pm_uv.p, B->cm_pm.p, E, 2, B->cm_uv.p, B->st);
+  if (per_info) cs::ba_launch_gather_rows(B->pm_info.p, B->cm_pm.p, E, 4, B->cm_info.p, B->st);
+  if (per_intr) cs::ba_launch_gather_rows(B->pm_intr.p, B->cm_pm.p, E, 4, B->cm_intr.p, B->st);
+  cs::ba_launch_gather_rows(B->pm_huber.p, B->cm_pm.p, E, 1, B->cm_huber.p, B->st);
+  CS_HIP_TRY(hipGetLastError());
+  CS_TRY(B->pm_pt.upload_ptr(O.pm_pt, Ez)); CS_TRY(B->pm_cam.upload_ptr(O.pm_cam, Ez)); CS_TRY(B->cm_pt.upload_ptr(O.cm_pt, Ez));
+  return CS_OK;
+}
+
+// kernel kinds of the projection edges in both orders -- only if some edge has a kernel other than Huber
+int upload_proj_kinds(cs_ba* B, StructureUploads& U, const cs::EdgeOrders& O, int nM) {
+  bool generic = false;
+  for (int kd : B->rk_proj) if (kd != cs::RK_NONE && kd != cs::RK_HUBER) { generic = true; break; }
+  for (int kd : B->rk_stereo) if (kd != cs::RK_NONE && kd != cs::RK_HUBER) { generic = true; break; }
+  if (!generic) { B->d_pm_rk.release(); B->d_cm_rk.release(); return CS_OK; }
+  // (a class without a kind list has Huber wherever its delta is positive: with a kind array on the device every edge is looked up in it)
+  std::vector<double> hub_m;
+  if (B->rk_proj.empty() && B->have_huber && nM > 0) { hub_m.resize((size_t)nM); CS_HIP_TRY(hipMemcpy(hub_m.data(), B->raw_huber.p, 8 * (size_t)nM, hipMemcpyDeviceToHost)); }
+  std::vector<int> pk, ck;
+  cs::proj_kind_tables(O, [&](int src) -> int {
+    if (src < nM) return !B->rk_proj.empty() ? B->rk_proj[src] : (!hub_m.empty() && hub_m[src] > 0 ? cs::RK_HUBER : cs::RK_NONE);
+    const int s2 = src - nM;
+    return !B->rk_stereo.empty() ? B->rk_stereo[s2] : (!B->h_se_huber.empty() && B->h_se_huber[s2] > 0 ? cs::RK_HUBER : cs::RK_NONE);
+  }, pk, ck);
+  CS_TRY(U.up(B->d_pm_rk, pk)); CS_TRY(U.up(B->d_cm_rk, ck));
+  return CS_OK;
+}
+
+// The Schur schedules' tables, each group written once; a schedule that is not in use goes up as constructed (its placeholder).
+int upload_elim_tables(cs_ba* B, StructureUploads& U, const cs::FusedSchedule& F) {
+  CS_TRY(U.up(B->d_slotE_ptr, F.slotE_ptr)); CS_TRY(U.up(B->d_slotE_idx, F.slotE_idx));
+  CS_TRY(U.up(B->d_cubS_ptr, F.cubS_ptr)); CS_TRY(U.up(B->d_cubS_cam, F.cubS_cam)); CS_TRY(U.up(B->d_ce_slot, F.ce_slot)); CS_TRY(U.up(B->d_cub_tile, F.cub_tile)); CS_TRY(U.up(B->d_cub_coef, F.cub_coef));
+  CS_TRY(U.alloc_zeroed(B->cub_M, B->fused ? 54 * F.cubS_cam.size() : 1)); CS_TRY(U.alloc_zeroed(B->cub_Dinv, B->fused ? 81 * (size_t)std::max(1, B->no) : 1)); CS_TRY(U.alloc_zeroed(B->d_elim_fail, 1));
+  return U.zflush();
+}
+int upload_segment_tables(cs_ba* B, StructureUploads& U, const cs::FusedSchedule& F) {
+  CS_TRY(U.up(B->d_run_lm, F.run_lm)); CS_TRY(U.up(B->d_seg_ptr, F.seg_ptr)); CS_TRY(U.up(B->d_seg_k, F.seg_k)); CS_TRY(U.up(B->d_seg_tile, F.seg_tile)); CS_TRY(U.up(B->d_seg_slot, F.seg_slot));
+  CS_TRY(U.up(B->d_run_e0, F.run_e0)); CS_TRY(U.up(B->d_seg_cam, F.seg_cam));
+  CS_TRY(U.up(B->d_gp_ptr, F.gp_ptr)); CS_TRY(U.up(B->d_gp_i1, F.gp_i1)); CS_TRY(U.up(B->d_gp_i2, F.gp_i2)); CS_TRY(U.up(B->d_gtile, F.gtile)); CS_TRY(U.up(B->d_gcam_ptr, F.gcam_ptr)); CS_TRY(U.up(B->d_gslot, F.gslot));
+  CS_TRY(U.alloc_zeroed(B->part_tiles, B->fused ? 36 * (size_t)F.n_tiles : 1)); CS_TRY(U.alloc_zeroed(B->part_coef, B->fused ? 6 * (size_t)F.n_slots : 1));
+  return U.zflush();
+}
+int upload_pair_tables(cs_ba* B, StructureUploads& U, const cs::PairSchedule& Q) {
+  CS_TRY(U.up(B->pair_ptr, Q.pair_ptr)); CS_TRY(U.up(B->pair_i1, Q.pair_i1)); CS_TRY(U.up(B->pair_i2, Q.pair_i2)); CS_TRY(U.up(B->ent_a, Q.ent_a)); CS_TRY(U.up(B->ent_b, Q.ent_b));
+  return CS_OK;
+}
+
+// ---- cuboid / odometry edges: their vertex adjacency, ends, owners (with the levels folded in) and kernels
+int upload_pose_edge_lists(cs_ba* B, StructureUploads& U, const cs::PoseEdgeEnds& P, cs::PoseEdgeOwners& W) {
+  const cs::EdgeClassHost& od = B->pose_class(CS_EDGE_ODOM);
+  const cs::VertexEdges c1 = cs::vertex_edge_csr(B->nc, P.ce_cam, P.n_cub), c2 = cs::vertex_edge_csr(B->nc, P.oe_i, P.n_odom),
+                        c3 = cs::vertex_edge_csr(B->nc, P.oe_j, P.n_odom), c4 = cs::vertex_edge_csr(B->no, P.ce_cub, P.n_cub);
+  CS_TRY(U.up(B->cam_ce_ptr, c1.ptr)); CS_TRY(U.up(B->cam_ce_idx, c1.idx)); CS_TRY(U.up(B->cam_oei_ptr, c2.ptr)); CS_TRY(U.up(B->cam_oei_idx, c2.idx));
+  CS_TRY(U.up(B->cam_oej_ptr, c3.ptr)); CS_TRY(U.up(B->cam_oej_idx, c3.idx)); CS_TRY(U.up(B->cub_ce_ptr, c4.ptr)); CS_TRY(U.up(B->cub_ce_idx, c4.idx));
+  CS_TRY(U.up(B->d_ce_cam, B->ce_cam)); CS_TRY(U.up(B->d_ce_cub, B->ce_cub)); CS_TRY(U.up(B->d_oe_i, od.a)); CS_TRY(U.up(B->d_oe_j, od.b));
+  {
+    std::vector<int> mine(std::max(1, B->no), 0);
+    for (int o = 0; o < B->no; o++) mine[o] = W.cub_owner[o] == B->shard_rank;
+    CS_TRY(U.up(B->d_cub_mine, mine));
   }
-  mark("  pose edge lists");
-  UP(B->ce_meas, c3.meas); UP(B->ce_info, c3.info); UP(B->oe_meas, od.meas); UP(B->oe_info, od.info);
-  UP(B->pe_meas, cp.meas); UP(B->pe_info, cp.info); UP(B->pe_K, cp.extra);
-  AL(B->ce_Hcc, 36 * (size_t)B->n_cub); AL(B->ce_Hoo, 81 * (size_t)B->n_cub); AL(B->ce_Hco, 54 * (size_t)B->n_cub); AL(B->ce_bc, 6 * (size_t)B->n_cub); AL(B->ce_bo, 9 * (size_t)B->n_cub);
-  AL(B->oe_Hii, 36 * (size_t)B->n_odom); AL(B->oe_Hjj, 36 * (size_t)B->n_odom); AL(B->oe_Hij, 36 * (size_t)B->n_odom); AL(B->oe_bi, 6 * (size_t)B->n_odom); AL(B->oe_bj, 6 * (size_t)B->n_odom);
-  mark("  pose edge measurements");
-  // ---- linear system storage
-  AL(B->Hcam, 36 * (size_t)nc); AL(B->bcam, 6 * (size_t)nc); AL(B->Hcub, 81 * (size_t)no); AL(B->bcub, 9 * (size_t)no);
-  AL(B->Hll, 9 * (size_t)np); AL(B->bl, 3 * (size_t)np); AL(B->W, 18 * (size_t)E); AL(B->WD, 18 * (size_t)E);
-  AL(B->Dinv, 9 * (size_t)np); AL(B->dbl, 3 * (size_t)np); B->s_doubles = (size_t)B->n_red * (B->band_ld ? B->band_ld : B->n_red);
-  AL(B->S, B->s_doubles + B->n_pose);   // [S | rhs]: one buffer, one all-reduce in the sharded solve
-  AL(B->xl, 3 * (size_t)np);
-  AL(B->d_band_info, cs::BAND_INFO_WORDS);  // the solver's status words (band_solver.h)
-  AL(B->band_linv, B->band_ld ? std::max(cs::ba_band_workspace_doubles(B->n_red, B->band_ld), B->use_bcr ? cs::ba_bcr_workspace_doubles(B->n_red, 128) : (size_t)1) : 1);   // inverted diagonal blocks (+ the separator's rows in the nested order)
+  B->h_ce_shard = W.ca; B->h_oe_shard = W.oa;
+  for (cs::EdgeClassHost& c : B->ec) c.lvl.resize(any_level(c.lvl) ? (size_t)c.size() : 0);
+  fold_pose_levels(B, W.ca, W.oa);      // (a level-1 edge gives zero blocks and no chi2, like an edge of another rank)
+  CS_TRY(U.up(B->d_ce_active, W.ca)); CS_TRY(U.up(B->d_oe_active, W.oa));
+  // kernels of the camera-cuboid edges (EdgeSE3Cuboid list, then EdgeSE3CuboidProj list) and of the odometry edges
+  auto any_kernel = [](const std::vector<int>& kinds) { for (int kd : kinds) if (kd != 0) return true; return false; };
+  const std::vector<int> kc = combined_cuboid(B, &cs::EdgeClassHost::rk, 1);
+  if (any_kernel(kc)) {
+    const std::vector<double> dc = combined_cuboid(B, &cs::EdgeClassHost::rd, 1);
+    CS_TRY(U.up(B->d_ce_rk, kc)); CS_TRY(U.up(B->d_ce_rdelta, dc));
+  } else { B->d_ce_rk.release(); B->d_ce_rdelta.release(); }
+  if (any_kernel(od.rk)) {
+    std::vector<int> kk(od.rk); std::vector<double> dd(od.rd);
+    kk.resize(std::max(1, B->n_odom), 0); dd.resize(std::max(1, B->n_odom), 0.0);
+    CS_TRY(U.up(B->d_oe_rk, kk)); CS_TRY(U.up(B->d_oe_rdelta, dd));
+  } else { B->d_oe_rk.release(); B->d_oe_rdelta.release(); }
+  return CS_OK;
+}
+// ... their measurements, and the blocks their kernels write
+int upload_pose_edge_payload(cs_ba* B, StructureUploads& U) {
+  const cs::EdgeClassHost &c3 = B->pose_class(CS_EDGE_CUBOID), &cp = B->pose_class(CS_EDGE_CUBOID_PROJ), &od = B->pose_class(CS_EDGE_ODOM);
+  const size_t n_cub = (size_t)B->n_cub, n_odom = (size_t)B->n_odom;
+  CS_TRY(U.up(B->ce_meas, c3.meas)); CS_TRY(U.up(B->ce_info, c3.info)); CS_TRY(U.up(B->oe_meas, od.meas)); CS_TRY(U.up(B->oe_info, od.info));
+  CS_TRY(U.up(B->pe_meas, cp.meas)); CS_TRY(U.up(B->pe_info, cp.info)); CS_TRY(U.up(B->pe_K, cp.extra));
+  CS_TRY(U.alloc_zeroed(B->ce_Hcc, 36 * n_cub)); CS_TRY(U.alloc_zeroed(B->ce_Hoo, 81 * n_cub)); CS_TRY(U.alloc_zeroed(B->ce_Hco, 54 * n_cub)); CS_TRY(U.alloc_zeroed(B->ce_bc, 6 * n_cub)); CS_TRY(U.alloc_zeroed(B->ce_bo, 9 * n_cub));
+  CS_TRY(U.alloc_zeroed(B->oe_Hii, 36 * n_odom)); CS_TRY(U.alloc_zeroed(B->oe_Hjj, 36 * n_odom)); CS_TRY(U.alloc_zeroed(B->oe_Hij, 36 * n_odom)); CS_TRY(U.alloc_zeroed(B->oe_bi, 6 * n_odom)); CS_TRY(U.alloc_zeroed(B->oe_bj, 6 * n_odom));
+  return CS_OK;
+}
+
+// ---- linear system storage (E: this rank's projection edges)
+int allocate_system_storage(cs_ba* B, int E, StructureUploads& U) {
+  const size_t nc = (size_t)B->nc, no = (size_t)B->no, np = (size_t)B->np;
+  const int R = B->shard_n;
+  CS_TRY(U.alloc_zeroed(B->Hcam, 36 * nc)); CS_TRY(U.alloc_zeroed(B->bcam, 6 * nc)); CS_TRY(U.alloc_zeroed(B->Hcub, 81 * no)); CS_TRY(U.alloc_zeroed(B->bcub, 9 * no));
+  CS_TRY(U.alloc_zeroed(B->Hll, 9 * np)); CS_TRY(U.alloc_zeroed(B->bl, 3 * np)); CS_TRY(U.alloc_zeroed(B->W, 18 * (size_t)E)); CS_TRY(U.alloc_zeroed(B->WD, 18 * (size_t)E));
+  CS_TRY(U.alloc_zeroed(B->Dinv, 9 * np)); CS_TRY(U.alloc_zeroed(B->dbl, 3 * np));
+  B->s_doubles = (size_t)B->n_red * (B->band_ld ? B->band_ld : B->n_red);
+  CS_TRY(U.alloc_zeroed(B->S, B->s_doubles + B->n_pose));   // [S | rhs]: one buffer, one all-reduce in the sharded solve
+  CS_TRY(U.alloc_zeroed(B->xl, 3 * np));
+  CS_TRY(U.alloc_zeroed(B->d_band_info, cs::BAND_INFO_WORDS));  // the solver's status words (band_solver.h)
+  CS_TRY(U.alloc_zeroed(B->band_linv, B->band_ld ? std::max(cs::ba_band_workspace_doubles(B->n_red, B->band_ld), B->use_bcr ? cs::ba_bcr_workspace_doubles(B->n_red, 128) : (size_t)1) : 1));   // inverted diagonal blocks (+ the separator's rows in the nested order)
   B->nb_chi = cs::ba_chi2_blocks(E);
   B->n_chi_partials = B->nb_chi + (B->n_cub + B->n_odom + 63) / 64;
-  AL(B->chi_partial, B->n_chi_partials);
-  AL(B->scale_partial, (size_t)cs::ba_scale_blocks());
-  AL(B->d_info, 1);
-  if (B->sparse) { rc = B->solver.upload(B->st); if (rc) return rc; }      // (one queued copy; this phase's closing wait is the one it asks for)
+  CS_TRY(U.alloc_zeroed(B->chi_partial, B->n_chi_partials));
+  CS_TRY(U.alloc_zeroed(B->scale_partial, (size_t)cs::ba_scale_blocks()));
+  CS_TRY(U.alloc_zeroed(B->d_info, 1));
+  if (B->sparse) CS_TRY(B->solver.upload(B->st));      // (one queued copy; this phase's closing wait is the one it asks for)
   if (B->sep_mode) {
-    AL(B->sepY, (size_t)(B->wl + B->wr) * B->int_n);
-    AL(B->sep_msgs, B->msg_doubles * (size_t)R);
-    AL(B->sepS, (size_t)B->n_sep * 2 * B->w_max + B->n_sep);   // [S_sep (band of 2 w_max) | rhs_sep]
-    AL(B->sep_work, std::max(cs::ba_band_workspace_doubles(B->n_sep, 2 * B->w_max), cs::ba_bcr_sep_ok(B->w_max, B->shard_n) ? cs::ba_bcr_sep_workspace_doubles(B->shard_n) : (size_t)1));
-    AL(B->d_sep_info, cs::BAND_INFO_WORDS);
-    AL(B->int_work, cs::ba_band_workspace_doubles(B->int_n, B->band_ld));
-    AL(B->d_int_info, cs::BAND_INFO_WORDS);
+    CS_TRY(U.alloc_zeroed(B->sepY, (size_t)(B->wl + B->wr) * B->int_n));
+    CS_TRY(U.alloc_zeroed(B->sep_msgs, B->msg_doubles * (size_t)R));
+    CS_TRY(U.alloc_zeroed(B->sepS, (size_t)B->n_sep * 2 * B->w_max + B->n_sep));   // [S_sep (band of 2 w_max) | rhs_sep]
+    CS_TRY(U.alloc_zeroed(B->sep_work, std::max(cs::ba_band_workspace_doubles(B->n_sep, 2 * B->w_max), cs::ba_bcr_sep_ok(B->w_max, B->shard_n) ? cs::ba_bcr_sep_workspace_doubles(B->shard_n) : (size_t)1)));
+    CS_TRY(U.alloc_zeroed(B->d_sep_info, cs::BAND_INFO_WORDS));
+    CS_TRY(U.alloc_zeroed(B->int_work, cs::ba_band_workspace_doubles(B->int_n, B->band_ld)));
+    CS_TRY(U.alloc_zeroed(B->d_int_info, cs::BAND_INFO_WORDS));
     std::vector<int> sep_col(R + 1, 0);
     for (int k = 1; k < R; k++) sep_col[k] = B->cut[k];
-    UP(B->d_sep_off, B->sep_off); UP(B->d_sep_col, sep_col);
+    CS_TRY(U.up(B->d_sep_off, B->sep_off)); CS_TRY(U.up(B->d_sep_col, sep_col));
     // what this rank contributes to the collectives of one LM trial: its separator message, the solution vector, three scalars
     B->bytes_per_trial = 8 * ((long long)B->msg_doubles + B->n_pose + 3);
   } else {
-    AL(B->sepY, 1); AL(B->sep_msgs, 1); AL(B->sepS, 1); AL(B->int_work, 1); AL(B->d_int_info, cs::BAND_INFO_WORDS); AL(B->sep_work, 1); AL(B->d_sep_info, cs::BAND_INFO_WORDS);
+    CS_TRY(U.alloc_zeroed(B->sepY, 1)); CS_TRY(U.alloc_zeroed(B->sep_msgs, 1)); CS_TRY(U.alloc_zeroed(B->sepS, 1)); CS_TRY(U.alloc_zeroed(B->int_work, 1));
+    CS_TRY(U.alloc_zeroed(B->d_int_info, cs::BAND_INFO_WORDS)); CS_TRY(U.alloc_zeroed(B->sep_work, 1)); CS_TRY(U.alloc_zeroed(B->d_sep_info, cs::BAND_INFO_WORDS));
     std::vector<int> none1(1, 0);
-    UP(B->d_sep_off, none1); UP(B->d_sep_col, none1);
+    CS_TRY(U.up(B->d_sep_off, none1)); CS_TRY(U.up(B->d_sep_col, none1));
     B->bytes_per_trial = R > 1 ? 8 * ((long long)B->s_doubles + B->n_pose + 3 + (B->elim ? B->n_pose - B->n_red : 0)) : 0;
   }
   B->bytes_per_trial_allreduce = 8 * ((long long)B->s_doubles + B->n_pose + 3 + (B->elim ? B->n_pose - B->n_red : 0));
   {
     const size_t need = std::max<size_t>(16, (size_t)B->n_pose + 2);
-    AL(B->d_scalars, need);
+    CS_TRY(U.alloc_zeroed(B->d_scalars, need));
     if (B->scalars_cap < need) {     // (with head room: a graph that grows by a camera per frame would re-pin this buffer every frame, ~0.1 ms)
       if (B->h_scalars) (void)hipHostFree(B->h_scalars);
       B->h_scalars = nullptr;
@@ -1538,23 +791,17 @@ int finalize_structure(cs_ba* B) {
       B->scalars_cap = want;
     }
   }
-  AL(B->cams_bak, 7 * (size_t)nc); AL(B->points_bak, 3 * (size_t)np); AL(B->cubes_bak, 10 * (size_t)no);
-  {
-    std::vector<double> u8(B->uni8, B->uni8 + 8);
-    if (nS > 0) u8.insert(u8.end(), B->h_se_sinfo.begin(), B->h_se_sinfo.begin() + 10);      // (a stereo graph: the stereo edges' reference record behind the mono one)
-    UP(B->d_uni, u8);
-  }
-#undef UP
-#undef AL
-#undef UPB
-  // (the helper thread allocates the edge tables' device buffers: their addresses are final only once it is done)
-  mark("  pose edge tables staged");
-  edge_th.join();
-  mark("  edge-table thread joined");
-  if (edge_rc) return edge_rc;
+  CS_TRY(U.alloc_zeroed(B->cams_bak, 7 * nc)); CS_TRY(U.alloc_zeroed(B->points_bak, 3 * np)); CS_TRY(U.alloc_zeroed(B->cubes_bak, 10 * no));
+  std::vector<double> u8(B->uni8, B->uni8 + 8);
+  if (B->n_stereo > 0) u8.insert(u8.end(), B->h_se_sinfo.begin(), B->h_se_sinfo.begin() + 10);      // (a stereo graph: the stereo edges' reference record behind the mono one)
+  return U.up(B->d_uni, u8);
+}
+
+// the kernels' view of the handle (every table is in place: the edge tables' helper thread has been joined)
+void fill_view(cs_ba* B, int E, int nM, int nS) {
   cs::BaView& v = B->view;
   v.cams = B->cams.p; v.points = B->points.p; v.cubes = B->cubes.p; v.cam_col = B->d_cam_col.p; v.cub_col = B->d_cub_col.p; v.pt_free = B->d_pt_free.p;
-  v.nc = nc; v.np = np; v.no = no; v.n_pose = B->n_pose; v.n_red = B->n_red; v.elim = B->elim ? 1 : 0; v.elim_max_slots = B->elim_max_slots;
+  v.nc = B->nc; v.np = B->np; v.no = B->no; v.n_pose = B->n_pose; v.n_red = B->n_red; v.elim = B->elim ? 1 : 0; v.elim_max_slots = B->elim_max_slots;
   v.cubS_ptr = B->d_cubS_ptr.p; v.cubS_cam = B->d_cubS_cam.p; v.ce_slot = B->d_ce_slot.p; v.cub_tile = B->d_cub_tile.p; v.cub_coef = B->d_cub_coef.p;
   v.cub_mine = B->d_cub_mine.p;
   v.cub_M = B->cub_M.p; v.cub_Dinv = B->cub_Dinv.p; v.elim_fail = B->d_elim_fail.p; v.slotE_ptr = B->d_slotE_ptr.p; v.slotE_idx = B->d_slotE_idx.p;
@@ -1590,12 +837,183 @@ int finalize_structure(cs_ba* B) {
   v.n_gpairs = B->n_gpairs; v.gpair_ptr = B->d_gp_ptr.p; v.gpair_i1 = B->d_gp_i1.p; v.gpair_i2 = B->d_gp_i2.p; v.gtile = B->d_gtile.p;
   v.gcam_ptr = B->d_gcam_ptr.p; v.gslot = B->d_gslot.p;
   v.chi_partial = B->chi_partial.p;
+}
+
+// The structure phase: the passes of ba_structure.h in order, everything for the device queued on B->st, one wait at the end.
+int finalize_structure(cs_ba* B) {
+  if (!B->structure_dirty) return CS_OK;
+  struct Clock { cs_ba* b; double t0; ~Clock() { b->tm.structure_ms += now_ms() - t0; } } clock{B, now_ms()};
+  CS_HIP_TRY(hipSetDevice(B->device));
+  CS_HIP_TRY(hipStreamSynchronize(B->st));             // nothing of an earlier call may still read the buffers (or the staging arena) reused below
+  CS_TRY(refresh_levels_host(B));                      // (levels a classification left on the device survive this phase through the host's copy)
+  B->pm_cm_valid = false;
+  CS_TRY(B->stage.begin((size_t)8 << 20));
+  PhaseMarks mark;
+  const int nc = B->nc, no = B->no, np = B->np;
+  // ---- checks.  Camera-cuboid edges of both kinds as one list: EdgeSE3Cuboid first, then EdgeSE3CuboidProj
+  const cs::EdgeClassHost &c3 = B->pose_class(CS_EDGE_CUBOID), &cp = B->pose_class(CS_EDGE_CUBOID_PROJ), &od = B->pose_class(CS_EDGE_ODOM);
+  B->ce_cam = c3.a; B->ce_cam.insert(B->ce_cam.end(), cp.a.begin(), cp.a.end());
+  B->ce_cub = c3.b; B->ce_cub.insert(B->ce_cub.end(), cp.b.begin(), cp.b.end());
+  B->n_cub3 = c3.size();
+  B->n_cub = (int)B->ce_cam.size();
+  B->n_odom = od.size();
+  reference_columns(B);
+  // (edges that an earlier phase of this handle has seen were checked then, and append only raises nc / np)
+  for (int k = std::min(B->st_lists_edges, B->n_proj); k < B->n_proj; k++)
+    if (B->e_pt[k] < 0 || B->e_pt[k] >= np || B->e_cam[k] < 0 || B->e_cam[k] >= nc) { cs_set_error("projection edge index out of range"); return CS_ERR_INVALID_ARG; }
+  mark("  checks, index mapping");
+  // ---- lists: every landmark's cameras (the lists of the last phase are kept on the handle: a graph that was only appended to extends them)
+  const int st_nb = 1 - B->st_cur;
+  cs::CameraLists L;
+  B->st_cams_of[st_nb].ensure((size_t)B->n_proj); B->st_edge_of[st_nb].ensure((size_t)B->n_proj);
+  L.cams_of = B->st_cams_of[st_nb].data(); L.edge_of = B->st_edge_of[st_nb].data();
+  {
+    const int E0 = B->st_lists_edges, np0 = (int)B->st_cam_cnt.size() - 1;
+    const bool grown = E0 > 0 && np0 >= 0 && np0 <= np && E0 <= B->n_proj && (B->n_proj - E0) <= E0 / 4 && B->st_cams_of[B->st_cur].size() == (size_t)E0 && B->st_edge_of[B->st_cur].size() == (size_t)E0;
+    const cs::PrevLists prev{E0, &B->st_cam_cnt, B->st_cams_of[B->st_cur].data(), B->st_edge_of[B->st_cur].data()};
+    cs::landmark_camera_lists(np, B->n_proj, B->e_pt.data(), B->e_cam.data(), grown ? &prev : nullptr, B->n_proj > 20000 ? struct_threads() : 1, L);   // (200 cameras / 100 k edges: 0.67 -> 0.35 ms)
+  }
+  mark("  camera lists (count, fill, sort)");
+  std::vector<int> seen;
+  if (!cs::check_lists_collect_seen(L, np, B->pt_fixed.data(), seen)) { cs_set_error("two projection edges between the same point and camera"); return CS_ERR_INVALID_ARG; }
+  mark("  duplicate check");
+  // ---- sets: the free landmarks grouped by the set of cameras that see them
+  const cs::CameraSets S = cs::group_by_camera_set(L, seen, seen.size() > 5000 ? struct_threads() : 1);
+  mark("  group by camera set");
+  mark("camera sets");
+  // ---- cuboid / odometry edge indices are used below: check them first
+  for (int k = 0; k < B->n_cub; k++)
+    if (B->ce_cam[k] < 0 || B->ce_cam[k] >= nc || B->ce_cub[k] < 0 || B->ce_cub[k] >= no) { cs_set_error("cuboid edge index out of range"); return CS_ERR_INVALID_ARG; }
+  for (int k = 0; k < B->n_odom; k++)
+    if (od.a[k] < 0 || od.a[k] >= nc || od.b[k] < 0 || od.b[k] >= nc) { cs_set_error("odometry edge index out of range"); return CS_ERR_INVALID_ARG; }
+  B->cam_col.assign(nc, -1); B->cub_col.assign(no, -1);
+  bool ext_binary_on_cuboid = false;
+  CS_TRY(check_external_edges(B, ext_binary_on_cuboid));
+  const cs::Vertices V{nc, no, np, B->cam_fixed.data(), B->cub_fixed.data(), B->pt_fixed.data()};
+  const cs::PoseEdgeEnds P{B->n_cub, B->ce_cam.data(), B->ce_cub.data(), B->n_odom, od.a.data(), od.b.data(), B->ext_n, B->ext_e4.data()};
+  const std::vector<std::vector<int>> cub_cams = cs::cuboid_camera_lists(V, P);
+  int max_slots = 0, n_free_cub = 0;
+  for (int o = 0; o < no; o++) { max_slots = std::max(max_slots, (int)cub_cams[o].size()); if (!B->cub_fixed[o]) n_free_cub++; }
+  bool fused_ok = getenv("CS_BA_SCHUR_PAIRS") == nullptr;
+  {
+    // (tracks of more than BA_FUSED_KMAX views go through the segments' plain multiply-add kernel: meant for the tail of a map -- when a
+    // quarter of the landmarks are such tracks the pair-major path is the faster build again, measured at C4's size with 20 views each)
+    size_t n_long = 0;
+    for (int p : S.gorder) {
+      const int kk = L.count(p);
+      if (kk > cs::BA_LONG_KMAX) { fused_ok = false; break; }
+      if (kk > cs::BA_FUSED_KMAX) n_long++;
+    }
+    if (4 * n_long > S.gorder.size()) fused_ok = false;
+  }
+  mark("  cuboid cameras, track lengths");
+  // ---- orderings and the solver choice
+  {
+    // (an external binary edge on a cuboid couples it to something besides its observing cameras: the cuboids then stay in the system)
+    B->elim_max_slots = std::max(1, std::min(max_slots, (int)cs::BA_ELIM_MAX_SLOTS));
+    const bool try_elim = fused_ok && n_free_cub > 0 && max_slots <= cs::BA_ELIM_MAX_SLOTS && getenv("CS_BA_KEEP_CUBOIDS") == nullptr && !ext_binary_on_cuboid;
+    cs::PoseGraph G; G.V = V; G.L = &L; G.S = &S; G.P = P; G.cub_cams = &cub_cams;
+    // (the two candidate orderings only read shared data: g2o's system on a second thread while this one orders the cameras-only system)
+    cs::Ordering keep_o, elim_o;
+    if (try_elim && nc + no > 64) {
+      run_items(2, [&](int t) { if (t == 0) elim_o = cs::rcm_ordering(G, true); else keep_o = cs::rcm_ordering(G, false); });
+    } else {
+      keep_o = cs::rcm_ordering(G, false);
+      if (try_elim) elim_o = cs::rcm_ordering(G, true);
+    }
+    mark("  two orderings");
+    choose_reduced_solver(B, keep_o, elim_o, try_elim, mark);
+  }
+  mark("ordering (RCM)");
+  // ---- sharding: the column cut (separator mode) and who owns what
+  choose_sharding(B);
+  const cs::Sharding sh{B->shard_rank, B->shard_n, &B->cut};
+  std::vector<int> owner;
+  if (B->sep_mode) owner = cs::landmark_owners_by_column(L, np, B->cam_col, B->cut);   // the rank that owns the lowest column among its free cameras (none: rank 0)
+  else if (B->shard_n > 1) landmark_owners(B->shard_n, nc, np, B->n_proj, B->e_pt.data(), B->e_cam.data(), owner);
+  else owner.assign(np, 0);
+  B->lm_owner = owner;
+  int nl = 0;
+  std::vector<int> pt_free(np);
+  for (int i = 0; i < np; i++) { pt_free[i] = B->pt_fixed[i] ? 0 : 1; if (pt_free[i]) B->pt_lm[i] = nl++; }
+  B->n_lm = nl;
+  StructureUploads U(B);
+  CS_TRY(U.up(B->d_cam_col, B->cam_col)); CS_TRY(U.up(B->d_cub_col, B->cub_col)); CS_TRY(U.up(B->d_pt_free, pt_free));
+  CS_TRY(upload_external_edges(B, U));
+  // ---- orders: the projection edges point-major and camera-major (host scratch kept on the handle for its memory only)
+  cs::EdgeOrders O;
+  cs::landmark_slot_ranges(L, np, owner, B->shard_rank, O);
+  const int E = O.E;   // local edges
+  if (B->slot_src_cap < (size_t)E) { B->slot_src_cap = (size_t)E + (B->slot_src ? (size_t)E / 4 : 0) + 1; B->slot_src.reset(new int[B->slot_src_cap]); }
+  B->slot_src_n = E;
+  B->st_pm_pt.ensure((size_t)E); B->st_pm_cam.ensure((size_t)E); B->st_cm_pm.ensure((size_t)E); B->st_cm_pt.ensure((size_t)E);
+  O.src_of_slot = B->slot_src.get(); O.pm_pt = B->st_pm_pt.data(); O.pm_cam = B->st_pm_cam.data(); O.cm_pm = B->st_cm_pm.data(); O.cm_pt = B->st_cm_pt.data();
+  const int NTH = (E > 20000) ? struct_threads() : 1;
+  cs::point_major_order(L, np, owner, B->shard_rank, B->cam_col, NTH, O);
+  mark("  point-major order");
+  cs::camera_major_order(nc, NTH, O);
+  mark("  index arrays (point-major, camera-major)");
+  const int nS = B->n_stereo, nM = B->n_proj - nS;
+  CS_TRY(decide_stereo_uniform(B, E, nM, nS));
+  int edge_rc = CS_OK;
+  std::thread edge_th([&]() { edge_rc = upload_edge_tables(B, O, nM, nS); });
+  struct JoinEdge { std::thread& t; ~JoinEdge() { if (t.joinable()) t.join(); } } join_edge{edge_th};
+  CS_TRY(U.up(B->pt_ptr, O.pt_ptr));
+  CS_TRY(upload_proj_kinds(B, U, O, nM));
+  CS_TRY(U.up(B->cam_ptr, O.cam_ptr));
+  mark("edge orderings + upload");
+  // ---- schedule: the Schur pattern.  Fused path: it needs every landmark to be seen by <= BA_LONG_KMAX cameras; otherwise
+  // (or with CS_BA_SCHUR_PAIRS=1, diagnostics) the pair-major path.
+  B->fused = fused_ok;        // (CS_BA_SCHUR_PAIRS unset, no track beyond BA_LONG_KMAX views, long tracks a minority: decided with the orderings above)
+  for (int p : S.gorder) if (owner[p] == B->shard_rank && L.count(p) > cs::BA_LONG_KMAX) { B->fused = false; break; }
+  B->schur_entries = 0;
+  for (int p : S.gorder) if (owner[p] == B->shard_rank) { const long long k = L.count(p); B->schur_entries += k * (k + 1) / 2; }
+  cs::FusedSchedule F(no);
+  cs::PairSchedule Q;
+  if (B->fused) {
+    cs::SchurInput in;
+    in.V = V; in.L = &L; in.S = &S; in.owner = &owner; in.rank = B->shard_rank; in.cam_col = &B->cam_col; in.pt_ptr = &O.pt_ptr; in.n_pose = B->n_pose;
+    in.elim = B->elim; in.cub_cams = &cub_cams; in.P = P; in.seg_lm = cs::BA_SEG_LM; in.fused_kmax = cs::BA_FUSED_KMAX;
+    cs::fused_segments(in, S.runs() > 256 ? struct_threads() : 1, F);
+    mark("  segments of the runs");
+    cs::fused_cuboid_slots(in, F);
+    CS_TRY(upload_elim_tables(B, U, F));
+    mark("  cuboid slots");
+    cs::fused_destination_sort(in, F);
+    mark("  destination sort");
+    cs::fused_destination_lists(in, F);
+    mark("  destination lists");
+    CS_TRY(upload_segment_tables(B, U, F));
+    CS_TRY(upload_pair_tables(B, U, Q));
+  } else {
+    Q = cs::schur_pairs(np, pt_free, O, B->cam_col, B->n_pose);
+    CS_TRY(upload_pair_tables(B, U, Q));
+    CS_TRY(upload_segment_tables(B, U, F));
+    CS_TRY(upload_elim_tables(B, U, F));
+  }
+  B->n_seg = F.n_seg; B->n_gpairs = F.n_gpairs; B->n_pairs = Q.n_pairs;
+  for (int q = 0; q < 5; q++) B->seg_class[q] = F.seg_class[q];
+  mark("Schur schedule");
+  // ---- pose edges
+  cs::PoseEdgeOwners W = cs::pose_edge_owners(V, P, cub_cams, B->cam_col, B->cub_col, B->n_red, B->elim, sh);
+  CS_TRY(upload_pose_edge_lists(B, U, P, W));
+  mark("  pose edge lists");
+  CS_TRY(upload_pose_edge_payload(B, U));
+  mark("  pose edge measurements");
+  // ---- storage
+  CS_TRY(allocate_system_storage(B, E, U));
+  // (the helper thread allocates the edge tables' device buffers: their addresses are final only once it is done)
+  mark("  pose edge tables staged");
+  edge_th.join();
+  mark("  edge-table thread joined");
+  if (edge_rc) return edge_rc;
+  fill_view(B, E, nM, nS);
   // the allocations above are zeroed on B->st (one batched fill, one wait here); uploads went through blocking copies
-  ZFLUSH();
-  rc = cflush(true); if (rc) return rc;
+  CS_TRY(U.zflush());
+  CS_TRY(U.flush(true));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   B->append_stage.off = 0;           // (the appended rows have arrived)
-  B->st_lists_edges = B->n_proj; B->st_cam_cnt = std::move(cam_cnt); B->st_cur = st_nb;   // (for a grown graph's next phase)
+  B->st_lists_edges = B->n_proj; B->st_cam_cnt = std::move(L.cam_cnt); B->st_cur = st_nb;   // (for a grown graph's next phase)
   mark("pose edges + allocations");
   B->structure_dirty = false;
   B->have_system = false;
