@@ -1133,6 +1133,100 @@ def pose_optimize_batch(batch, params=None, device=0):
     return out
 
 
+# ------------------------------------------------------------------ Sim(3) alignment of keyframe pairs, batched ----------
+class CsSim3PairParams(C.Structure):
+    _fields_ = [("iterations_first", C.c_int), ("iterations_more_clean", C.c_int), ("iterations_more_outliers", C.c_int), ("robust_second_round", C.c_int),
+                ("min_inliers", C.c_int), ("th2", C.c_double), ("huber_delta", C.c_double)]
+
+
+DECLARED_SYMBOLS += ["cs_sim3_pair_default_params", "cs_sim3_optimize_pairs", "cs_sim3_pairs_create", "cs_sim3_pairs_destroy", "cs_sim3_pairs_optimize",
+                     "cs_sim3_pairs_last_timing", "cs_sim3_pairs_linearize"]
+
+
+def sim3_pair_default_params(**kw):
+    """cs_sim3_pair_default_params with overrides."""
+    p = CsSim3PairParams()
+    lib().cs_sim3_pair_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _sim3_pair_inputs(batch):
+    """A batch dict (synth_sim3_pairs.synth_sim3_pairs layout: S12, intr, fix_scale, match_ptr, P1, P2, obs1, obs2, info12, info21) as C arguments."""
+    S = _f64(batch["S12"], (-1, 8)); n = len(S)
+    intr, ptr = _f64(batch["intr"], (n, 8)), _i32(batch["match_ptr"])
+    if len(ptr) != n + 1:
+        raise ValueError("match_ptr must hold n_pairs + 1 entries")
+    fs = np.ascontiguousarray(np.asarray(batch["fix_scale"]).ravel().astype(np.uint8))
+    if len(fs) != n:
+        raise ValueError("fix_scale must hold one entry per pair")
+    N = int(ptr[-1]) if n else 0
+    P1, P2, o1, o2 = _f64(batch["P1"], (N, 3)), _f64(batch["P2"], (N, 3)), _f64(batch["obs1"], (N, 2)), _f64(batch["obs2"], (N, 2))
+    W12 = _f64(batch["info12"], (N, 4)) if batch.get("info12") is not None else None
+    W21 = _f64(batch["info21"], (N, 4)) if batch.get("info21") is not None else None
+    keep = (S, intr, ptr, fs, P1, P2, o1, o2, W12, W21)
+    return n, N, keep, (_dp(S), _dp(intr), _u8p(fs), _ip(ptr), _dp(P1), _dp(P2), _dp(o1), _dp(o2))
+
+
+def _sim3_pair_call(fn, head, batch, params):
+    p = params if params is not None else sim3_pair_default_params()
+    n, N, keep, args = _sim3_pair_inputs(batch)
+    W12, W21 = keep[8], keep[9]
+    S_out, inl, n_in = np.zeros((n, 8)), np.zeros(N, np.uint8), np.zeros(n, np.int32)
+    chi2, iters = np.zeros((n, 2)), np.zeros((n, 2), np.int32)
+    rc = fn(*head, C.byref(p), n, *args, _dp(W12) if W12 is not None else None, _dp(W21) if W21 is not None else None,
+            _dp(S_out), _u8p(inl), _ip(n_in), _dp(chi2), _ip(iters))
+    return rc, dict(S12=S_out, inlier=inl, n_inliers=n_in, chi2=chi2, iterations=iters)
+
+
+class Sim3Pairs:
+    """cs_sim3_pairs handle: keeps its stream and device buffers between optimize() calls."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _chk(lib().cs_sim3_pairs_create(int(device), C.byref(self.h)), "cs_sim3_pairs_create")
+
+    def optimize(self, batch, params=None):
+        """-> dict: S12 (n, 8), inlier (N, uint8), n_inliers (n), chi2 and iterations (n, 2)."""
+        rc, out = _sim3_pair_call(lib().cs_sim3_pairs_optimize, (self.h,), batch, params)
+        _chk(rc, "cs_sim3_pairs_optimize")
+        return out
+
+    def timing(self):
+        k, h = C.c_double(), C.c_double()
+        _chk(lib().cs_sim3_pairs_last_timing(self.h, C.byref(k), C.byref(h)), "cs_sim3_pairs_last_timing")
+        return {"kernel_ms": k.value, "host_ms": h.value}
+
+    def close(self):
+        if self.h:
+            lib().cs_sim3_pairs_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sim3_optimize_pairs(batch, params=None, device=0):
+    """cs_sim3_optimize_pairs: the one-shot form."""
+    rc, out = _sim3_pair_call(lib().cs_sim3_optimize_pairs, (int(device),), batch, params)
+    _chk(rc, "cs_sim3_optimize_pairs")
+    return out
+
+
+def sim3_pairs_linearize(batch, device=0):
+    """cs_sim3_pairs_linearize -> (err (N, 4): e12 e21, jac (N, 2, 2, 7): edge, error component, update dimension) at batch["S12"]."""
+    n, N, keep, args = _sim3_pair_inputs(batch)
+    err, jac = np.zeros((N, 4)), np.zeros((N, 2, 2, 7))
+    _chk(lib().cs_sim3_pairs_linearize(int(device), n, *args, _dp(err), _dp(jac)), "cs_sim3_pairs_linearize")
+    return err, jac
+
+
 DECLARED_SYMBOLS += ["cs_pgo_create", "cs_pgo_destroy", "cs_pgo_set_vertices", "cs_pgo_set_estimates", "cs_pgo_set_edges", "cs_pgo_set_lm_params", "cs_pgo_chi2",
                      "cs_pgo_linearize_edges", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
 

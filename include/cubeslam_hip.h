@@ -717,6 +717,76 @@ int  cs_pgo_solver_path(cs_pgo* g, int* path, double* sparse_fill);
  * trials (assembly, factorisation, substitution, update, chi2 of the new state, the record's copy), total_ms = the call.          */
 int  cs_pgo_last_timing(cs_pgo* g, double* linearize_ms, double* solve_ms, double* total_ms);
 
+/* ------------------------------------------------------------------ Path B''': Sim(3) alignment of keyframe pairs, batched -- */
+/* Replaces, for many keyframe pairs at once, the g2o graph an ORB-SLAM2-derived loop closer optimises once per loop candidate
+ * (Optimizer::OptimizeSim3, NOT IN THE REFERENCE; the g2o types it uses are): ONE free VertexSim3Expmap with its two cameras
+ * (types/types_seven_dof_expmap.h:48-94; cam_map1 / cam_map2 :74-88; oplusImpl :60-69: update[6] = 0 under _fix_scale, estimate =
+ * exp(update) * estimate) and, per match, two binary edges whose other vertex is a FIXED VertexSBAPointXYZ:
+ *   EdgeSim3ProjectXYZ          types_seven_dof_expmap.h:130-149   e12 = obs1 - cam_map1(project(S.map(P2)))
+ *   EdgeInverseSim3ProjectXYZ   types_seven_dof_expmap.h:152-171   e21 = obs2 - cam_map2(project(S^-1.map(P1)))
+ * over Sim3 (types/sim3.h:41-285, never renormalised -- as cs_pgo).  Both edges have linearizeOplus commented out (:147, :169): the
+ * Jacobians are BaseBinaryEdge::linearizeOplus's numeric default (core/base_binary_edge.hpp:130-205: column d =
+ * (e(+delta e_d) - e(-delta e_d)) * (1 / (2 delta)), delta = 1e-9, through oplusImpl -- a fix_scale pair gets an exactly zero seventh
+ * column).  The quadratic form and the rho' weighting are BaseBinaryEdge::constructQuadraticForm's (:55-120), the kernel is
+ * RobustKernelHuber with its single-precision delta^2 (core/robust_kernel_impl.h:86; cs_robust.h: huber_rho).  Each round is
+ * SparseOptimizer::optimize (core/sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg
+ * (core/optimization_algorithm_levenberg.cpp:61-189) in the arithmetic of cs_lm.h, stated on the device as pose_kernels.hip states it:
+ * EACH optimize() call re-initialises lambda (tau * max |H_jj|, tau = 1e-5), ni and nBad; at most 10 trials per iteration; the second
+ * round continues from the state the first ended on.  The 7 x 7 system H + lambda I goes through an LDL^T without pivoting, and a
+ * pivot that is not positive makes the trial a failed one (LinearSolverDense, solvers/linear_solver_dense.h:104-111).  A depth of zero
+ * or a negative depth is not tested, as in g2o.
+ *
+ * The schedule and the classification are ORB-SLAM2's, NOT IN THE REFERENCE: optimize(iterations_first); every match with plain
+ * e^T Omega e > th2 on EITHER edge loses BOTH edges (optimizer.removeEdge) and is not looked at again; with fewer than min_inliers
+ * matches left the pair is given up: no second round, 0 inliers, every flag 0, S12_out = the state the first round ended on; otherwise
+ * optimize(iterations_more_outliers) if a match was removed and optimize(iterations_more_clean) if none was, and the inlier flags are
+ * taken the same way once more.  Both classifications are evaluated AT THE STATE THE ROUND ENDED ON -- the stance cs_pose takes; g2o's
+ * stored _error after a rejected last trial would be the rejected state's (computeActiveErrors is not repeated after the pop).
+ *
+ * All pairs of a call are optimised by ONE kernel launch, one wavefront per pair; a pair's result does not depend on its
+ * position in the batch or on the batch's size.  Every argument is checked on the host before anything is launched -- every value
+ * finite, s > 0, match_ptr[0] = 0 and non-decreasing, counts within int range, iteration counts 0..100 -- and a refused call leaves the
+ * outputs untouched; no input makes the kernel read out of bounds, and no loop in it is unbounded (trials <= 10, iterations <= 100). */
+typedef struct cs_sim3_pair_params {
+  int    iterations_first;          /* LM iterations of the first optimize() (5)                                    */
+  int    iterations_more_clean;     /* ... of the second one when the first classification removed no match (5)     */
+  int    iterations_more_outliers;  /* ... when it removed one (10)                                                 */
+  int    robust_second_round;       /* 1: the Huber kernel stays on in the second round (1)                         */
+  int    min_inliers;               /* fewer matches left after the first classification: the pair is given up (10) */
+  double th2;                       /* classification threshold on e^T Omega e (10.0)                               */
+  double huber_delta;               /* RobustKernelHuber::delta of both edges, <= 0: no kernel (sqrt(th2))          */
+} cs_sim3_pair_params;
+void cs_sim3_pair_default_params(cs_sim3_pair_params* p);
+/* Pair f owns matches match_ptr[f] .. match_ptr[f + 1] - 1.  S12 maps camera-2 coordinates to camera-1 coordinates.  Per match: P1 / P2
+ * the match's point in camera-1 / camera-2 coordinates (the two fixed VertexSBAPointXYZ), obs1 / obs2 its keypoint in image 1 / image 2,
+ * info12 / info21 the row-major 2 x 2 information of e12 / e21 (NULL: identity for every match).
+ * Outputs: S12_out n_pairs x 8; inlier_out one byte per match; n_inliers_out n_pairs (what OptimizeSim3 returns); chi2_out and
+ * iterations_done n_pairs x 2 (either may be NULL): activeRobustChi2 over the round's matches at the state round r ended on, and what
+ * optimize() returned for round r (0 and 0 for a round that did not run).                                                          */
+int cs_sim3_optimize_pairs(int device, const cs_sim3_pair_params* p, int n_pairs,
+      const double* S12_in,             /* n_pairs x 8: qx qy qz qw tx ty tz s (Sim3::operator[] order), s > 0          */
+      const double* intr8,              /* n_pairs x 8: fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2                                 */
+      const unsigned char* fix_scale,   /* n_pairs: VertexSim3Expmap::_fix_scale                                        */
+      const int* match_ptr,             /* n_pairs + 1                                                                  */
+      const double* P1, const double* P2, const double* obs1, const double* obs2, const double* info12, const double* info21,
+      double* S12_out, unsigned char* inlier_out, int* n_inliers_out, double* chi2_out, int* iterations_done);
+/* The same with a handle that keeps its stream and its device / pinned buffers between calls (they grow on demand and never shrink).
+ * Same arguments, same bits as the one-shot form.  Calls on one handle must not overlap.                                           */
+typedef struct cs_sim3_pairs cs_sim3_pairs;
+int cs_sim3_pairs_create(int device, cs_sim3_pairs** out);
+void cs_sim3_pairs_destroy(cs_sim3_pairs* b);
+int cs_sim3_pairs_optimize(cs_sim3_pairs* b, const cs_sim3_pair_params* p, int n_pairs, const double* S12_in, const double* intr8, const unsigned char* fix_scale,
+      const int* match_ptr, const double* P1, const double* P2, const double* obs1, const double* obs2, const double* info12, const double* info21,
+      double* S12_out, unsigned char* inlier_out, int* n_inliers_out, double* chi2_out, int* iterations_done);
+/* Of the handle's last call that passed its argument checks (a refused call leaves the figures of the one before): kernel_ms = the one
+ * kernel, from hipEvents on the handle's stream; host_ms = the whole call on a monotonic clock (checking, packing, the two copies and
+ * the kernel included).                                                                                                            */
+int cs_sim3_pairs_last_timing(const cs_sim3_pairs* b, double* kernel_ms, double* host_ms);
+/* Inspection: what computeError + linearizeOplus leave in _error and _jacobianOplusXj of every match's two edges at S12_in.
+ * err4 = n_matches x 4 (e12, then e21); jac28 = n_matches x 2 x 2 x 7 (edge, error component, update dimension).                    */
+int cs_sim3_pairs_linearize(int device, int n_pairs, const double* S12_in, const double* intr8, const unsigned char* fix_scale, const int* match_ptr,
+      const double* P1, const double* P2, const double* obs1, const double* obs2, double* err4, double* jac28);
+
 #ifdef __cplusplus
 }
 #endif
