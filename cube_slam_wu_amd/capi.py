@@ -1096,27 +1096,22 @@ def _pose_call(fn, head, batch, params):
     return rc, dict(Tcw=T_out, inlier=inl, chi2=chi2, iterations=iters)
 
 
-class PoseBatch:
-    """cs_pose_batch handle: keeps its stream and device buffers between optimize() calls."""
+class _BatchHandle:
+    """What the batch handles share: <_SYM>_create, _last_timing and _destroy of a handle that keeps its stream and device buffers between calls."""
+    _SYM = None
 
     def __init__(self, device=0):
         self.h = C.c_void_p()
-        _chk(lib().cs_pose_batch_create(int(device), C.byref(self.h)), "cs_pose_batch_create")
-
-    def optimize(self, batch, params=None):
-        """-> dict: Tcw (n, 7), inlier (N, uint8), chi2 and iterations (n, n_rounds)."""
-        rc, out = _pose_call(lib().cs_pose_batch_optimize, (self.h,), batch, params)
-        _chk(rc, "cs_pose_batch_optimize")
-        return out
+        _chk(getattr(lib(), self._SYM + "_create")(int(device), C.byref(self.h)), self._SYM + "_create")
 
     def timing(self):
         k, h = C.c_double(), C.c_double()
-        _chk(lib().cs_pose_batch_last_timing(self.h, C.byref(k), C.byref(h)), "cs_pose_batch_last_timing")
+        _chk(getattr(lib(), self._SYM + "_last_timing")(self.h, C.byref(k), C.byref(h)), self._SYM + "_last_timing")
         return {"kernel_ms": k.value, "host_ms": h.value}
 
     def close(self):
         if self.h:
-            lib().cs_pose_batch_destroy(self.h)
+            getattr(lib(), self._SYM + "_destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -1124,6 +1119,18 @@ class PoseBatch:
             self.close()
         except Exception:
             pass
+
+
+class PoseBatch(_BatchHandle):
+    """cs_pose_batch handle: keeps its stream and device buffers between optimize() calls."""
+
+    _SYM = "cs_pose_batch"
+
+    def optimize(self, batch, params=None):
+        """-> dict: Tcw (n, 7), inlier (N, uint8), chi2 and iterations (n, n_rounds)."""
+        rc, out = _pose_call(lib().cs_pose_batch_optimize, (self.h,), batch, params)
+        _chk(rc, "cs_pose_batch_optimize")
+        return out
 
 
 def pose_optimize_batch(batch, params=None, device=0):
@@ -1182,34 +1189,16 @@ def _sim3_pair_call(fn, head, batch, params):
     return rc, dict(S12=S_out, inlier=inl, n_inliers=n_in, chi2=chi2, iterations=iters)
 
 
-class Sim3Pairs:
+class Sim3Pairs(_BatchHandle):
     """cs_sim3_pairs handle: keeps its stream and device buffers between optimize() calls."""
 
-    def __init__(self, device=0):
-        self.h = C.c_void_p()
-        _chk(lib().cs_sim3_pairs_create(int(device), C.byref(self.h)), "cs_sim3_pairs_create")
+    _SYM = "cs_sim3_pairs"
 
     def optimize(self, batch, params=None):
         """-> dict: S12 (n, 8), inlier (N, uint8), n_inliers (n), chi2 and iterations (n, 2)."""
         rc, out = _sim3_pair_call(lib().cs_sim3_pairs_optimize, (self.h,), batch, params)
         _chk(rc, "cs_sim3_pairs_optimize")
         return out
-
-    def timing(self):
-        k, h = C.c_double(), C.c_double()
-        _chk(lib().cs_sim3_pairs_last_timing(self.h, C.byref(k), C.byref(h)), "cs_sim3_pairs_last_timing")
-        return {"kernel_ms": k.value, "host_ms": h.value}
-
-    def close(self):
-        if self.h:
-            lib().cs_sim3_pairs_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def sim3_optimize_pairs(batch, params=None, device=0):

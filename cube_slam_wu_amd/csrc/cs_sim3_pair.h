@@ -7,29 +7,18 @@
 // Both have linearizeOplus commented out (:147, :169): the Jacobian is BaseBinaryEdge's numeric default (core/base_binary_edge.hpp:130-205),
 // central differences with delta = 1e-9 through VertexSim3Expmap::oplusImpl (cs_sim3.h: sim3_oplus).  The quadratic form is
 // BaseBinaryEdge::constructQuadraticForm's (:55-120) with the point fixed, the kernel RobustKernelHuber (cs_robust.h), the optimiser
-// OptimizationAlgorithmLevenberg (core/optimization_algorithm_levenberg.cpp:61-189) in the arithmetic of cs_lm.h, stated here once more
-// because it has to run on the device (as pose_kernels.hip states it); the 7 x 7 system goes through an LDL^T without pivoting whose "all
-// pivots positive" test is LinearSolverDense's (solvers/linear_solver_dense.h:104-111).  The two-round schedule with the classification
-// between the rounds is ORB-SLAM2's Optimizer::OptimizeSim3, which is NOT IN THE REFERENCE.
+// cs_dense_lm.h's dense_lm_round with N = 7: OptimizationAlgorithmLevenberg in the policy of cs_lm.h over a 7 x 7 LDL^T, the loop
+// pose_kernels.hip runs with N = 6.  The two-round schedule with the classification between the rounds is ORB-SLAM2's
+// Optimizer::OptimizeSim3, which is NOT IN THE REFERENCE.
 //
 // sim3_pair_optimize is written over a "wave" W: `lane` of `stride` workers share a pair's matches (worker l owns matches l, l + stride,
 // ...), W::sum adds one value per worker and hands every worker the same total, W::load reads a match record, W::put / W::get / W::sync publish the 15 states of a
 // linearisation (W::reread, once per match: the states are read again, not kept in registers over the loop).  sim3_pair_kernels.hip runs it with 64 lanes, a butterfly and LDS; tools/hostonly/sim3_pair_host_check.cpp with one
 // worker and an array.  FP64, -ffp-contract=off.
 #pragma once
-#include <float.h>
-#include <math.h>
-
+#include "cs_dense_lm.h"
 #include "cs_robust.h"
 #include "cs_sim3.h"
-
-#if defined(__HIPCC__)
-#define CS_UNROLL _Pragma("unroll")      // constant trip counts: every array below has to stay in registers on the device
-#define CS_NOUNROLL _Pragma("nounroll")
-#else
-#define CS_UNROLL
-#define CS_NOUNROLL
-#endif
 
 namespace cs {
 
@@ -144,53 +133,6 @@ CS_HD void sim3_pair_quadratic_form(const double* J, const double* Wm, const dou
   }
 }
 
-// (H + lambda I) x = b by LDL^T without pivoting; false when a pivot is not positive (solvers/linear_solver_dense.h:104-111)
-CS_HD bool solve7(const double* H, double lambda, const double* b, double* x) {
-  double A[49], D[7], y[7];
-  {
-    int k = 0;
-    CS_UNROLL
-    for (int i = 0; i < 7; i++)
-      CS_UNROLL
-      for (int j = i; j < 7; j++, k++) { A[7 * i + j] = H[k]; A[7 * j + i] = H[k]; }
-  }
-  CS_UNROLL
-  for (int i = 0; i < 7; i++) A[8 * i] += lambda;
-  bool ok = true;
-  CS_UNROLL
-  for (int j = 0; j < 7; j++) {
-    double d = A[8 * j];
-    CS_UNROLL
-    for (int k = 0; k < j; k++) d -= A[7 * j + k] * A[7 * j + k] * D[k];
-    if (!(d > 0)) ok = false;
-    D[j] = d;
-    CS_UNROLL
-    for (int i = j + 1; i < 7; i++) {
-      double s = A[7 * i + j];
-      CS_UNROLL
-      for (int k = 0; k < j; k++) s -= A[7 * i + k] * A[7 * j + k] * D[k];
-      A[7 * i + j] = s / d;
-    }
-  }
-  CS_UNROLL
-  for (int i = 0; i < 7; i++) {
-    double s = b[i];
-    CS_UNROLL
-    for (int k = 0; k < i; k++) s -= A[7 * i + k] * y[k];
-    y[i] = s;
-  }
-  CS_UNROLL
-  for (int i = 0; i < 7; i++) y[i] /= D[i];
-  CS_UNROLL
-  for (int i = 6; i >= 0; i--) {
-    double s = y[i];
-    CS_UNROLL
-    for (int k = i + 1; k < 7; k++) s -= A[7 * k + i] * x[k];
-    x[i] = s;
-  }
-  return ok;
-}
-
 // The 15 states of a linearisation at S, one per worker, published through W.
 template <class W>
 CS_HD void sim3_pair_publish_states(W& w, const Sim3& S, bool fix_scale) {
@@ -282,62 +224,22 @@ CS_HD void sim3_pair_inspect(W& w, const Sim3PairProblem& F, const Sim3& S, doub
   }
 }
 
-// SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg::solve (:61-163) on the pair's active matches, from S.
-// The arithmetic of a trial is cs_lm.h's lm_begin / lm_trial / lm_again / lm_stop.  Returns what optimize() returns; chi = the
-// activeRobustChi2 the state it ends on has.  No loop is unbounded: iterations <= SIM3_PAIR_MAX_ITERATIONS (the host refuses more), trials <= 10.
+// The pair as cs_dense_lm.h's problem: one free VertexSim3Expmap under the pair's active matches
+template <class W>
+struct Sim3PairLm {
+  W& w;
+  const Sim3PairProblem& F;
+  const unsigned char* level;
+  double huber;
+  CS_HD_MEMBER void linearize(const Sim3& S, double* H, double* b, double& chi) const { sim3_pair_linearize(w, F, level, S, huber, H, b, chi); }
+  CS_HD_MEMBER double chi2(const Sim3& S) const { return sim3_pair_active_chi2(w, F, level, S, huber); }
+  CS_HD_MEMBER Sim3 oplus(const Sim3& S, const double* x) const { return sim3_oplus(S, x, F.fix_scale); }
+};
+
+// optimize(iterations) on the pair's active matches, from S (cs_dense_lm.h).  iterations <= SIM3_PAIR_MAX_ITERATIONS: the host refuses more.
 template <class W>
 CS_HD int sim3_pair_round(W& w, const Sim3PairProblem& F, const unsigned char* level, Sim3& S, double huber, int iterations, double& currentChi) {
-  int done = 0;
-  if (iterations <= 0) { currentChi = sim3_pair_active_chi2(w, F, level, S, huber); return 0; }
-  double lambda = 0.0, ni = 2.0;
-  int nBad = 0;
-  for (int it = 0; it < iterations; it++) {
-    double H[28], b[7];
-    sim3_pair_linearize(w, F, level, S, huber, H, b, currentChi);
-    if (it == 0) {                                   // computeLambdaInit (:166-180): tau * max |H_jj|, tau = 1e-5
-      double md = 0.0;
-      int k = 0;
-      CS_UNROLL
-      for (int j = 0; j < 7; k += 7 - j, j++) md = fmax(fabs(H[k]), md);
-      lambda = 1e-5 * md;
-      ni = 2.0; nBad = 0;
-    }
-    const double iniChi = currentChi;
-    double rho = 0.0;
-    int qmax = 0;
-    do {
-      double x[7];
-      const bool solved = solve7(H, lambda, b, x);
-      double tempChi = DBL_MAX, scale = 0.0;         // a failed factorisation: :126-127, and no scale term (cs_lm.h: lm_trial)
-      Sim3 Sn = S;
-      if (solved) {
-        Sn = sim3_oplus(S, x, F.fix_scale);
-        tempChi = sim3_pair_active_chi2(w, F, level, Sn, huber);
-        CS_UNROLL
-        for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + b[j]);      // computeScale (:182-189)
-      }
-      rho = currentChi - tempChi;
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - pow(2 * rho - 1, 3.0);
-        alpha = fmin(alpha, 2. / 3.);
-        lambda *= fmax(1. / 3., alpha);
-        ni = 2.0;
-        currentChi = tempChi;
-        S = Sn;
-      } else {
-        lambda *= ni;
-        ni *= 2;
-      }
-      qmax++;
-    } while (rho < 0 && qmax < SIM3_PAIR_MAX_TRIALS);
-    done++;
-    if (qmax == SIM3_PAIR_MAX_TRIALS || rho == 0) break;
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-    if (nBad >= 3) break;
-  }
-  return done;
+  return dense_lm_round<7>(Sim3PairLm<W>{w, F, level, huber}, S, iterations, SIM3_PAIR_MAX_TRIALS, currentChi);
 }
 
 // The classification between and after the rounds: an active match with e^T Omega e > th2 on either edge loses both edges

@@ -6,31 +6,23 @@
 //   constructQuadraticForm (rho' weights Omega and -Omega e)      core/base_unary_edge.hpp:42-72
 //   RobustKernelHuber with its single-precision delta^2           cs_robust.h
 //   VertexSE3Expmap::oplusImpl (exp(update) * estimate)           types_six_dof_expmap.h:73-76, cs_se3.h
-// driven round by round through SparseOptimizer::optimize (core/sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg
-// (core/optimization_algorithm_levenberg.cpp:61-189); the 6 x 6 system goes through an LDL^T without pivoting whose "all pivots positive"
-// test is LinearSolverDense's isPositive() (solvers/linear_solver_dense.h:104-111).
+// driven round by round through cs_dense_lm.h's dense_lm_round with N = 6: SparseOptimizer::optimize with OptimizationAlgorithmLevenberg
+// over a 6 x 6 LDL^T without pivoting (the g2o lines are cited there and in cs_lm.h).
 //
 // Shape: one wavefront per frame, the whole optimisation -- every round, iteration and trial -- inside one launch.  Lane l owns the frame's
 // observations l, l + 64, ...: it keeps their share of the 21 upper entries of H, of b and of chi2 in registers; the 64 shares are summed
-// by a butterfly over the lanes (lane ^ 32, ^ 16, ... ^ 1: a fixed order, and -- both partners add the same two numbers -- the same bits in
-// every lane).  Every lane therefore holds the same H and b, and every lane runs the 6 x 6 factorisation on them: on a SIMD machine that
+// by cs_wave.h's wave_sum_all (a butterfly over the lanes: a fixed order, and the same bits in every lane).  Every lane therefore holds the same H and b, and every lane runs the 6 x 6 factorisation on them: on a SIMD machine that
 // costs what one lane costs, and the increment needs no broadcast.  All LM scalars are wave-uniform, so the control flow never diverges.
 // A frame's result depends on its own data only: the same bits at any position in any batch.  FP64, -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
-
+#include "cs_dense_lm.h"
 #include "cs_robust.h"
+#include "cs_wave.h"
 #include "pose_types.h"
 
 namespace cs {
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 struct Obs {
   double X[3], m[3], W[9];
@@ -38,11 +30,8 @@ struct Obs {
 };
 
 __device__ __forceinline__ Obs obs_load(const double* __restrict__ rec) {
-  // 128 bytes, 16-byte aligned (the host packs the records behind a 256-byte aligned base)
-  const double2* p = reinterpret_cast<const double2*>(rec);
   double v[POSE_OBS_DOUBLES];
-#pragma unroll
-  for (int k = 0; k < POSE_OBS_DOUBLES / 2; k++) { const double2 t = p[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
+  load_record<POSE_OBS_DOUBLES>(rec, v);             // 128 bytes
   Obs o;
 #pragma unroll
   for (int k = 0; k < 3; k++) { o.X[k] = v[k]; o.m[k] = v[3 + k]; }
@@ -98,7 +87,7 @@ __device__ __forceinline__ double frame_chi2(const Frame& F, const Pose& T, bool
     huber_rho(c, robust ? (o.stereo ? F.huber_stereo : F.huber_mono) : 0.0, r0, r1);
     acc += r0;
   }
-  return wave_sum(acc);
+  return wave_sum_all(acc);
 }
 
 // computeActiveErrors + linearizeOplus + constructQuadraticForm of every level-0 edge: H (21 upper entries, row by row), b, chi2
@@ -159,58 +148,38 @@ __device__ __forceinline__ void frame_linearize(const Frame& F, const Pose& T, b
     }
   }
 #pragma unroll
-  for (int k = 0; k < 21; k++) H[k] = wave_sum(h[k]);
+  for (int k = 0; k < 21; k++) H[k] = wave_sum_all(h[k]);
 #pragma unroll
-  for (int k = 0; k < 6; k++) b[k] = wave_sum(g[k]);
-  chi = wave_sum(acc);
+  for (int k = 0; k < 6; k++) b[k] = wave_sum_all(g[k]);
+  chi = wave_sum_all(acc);
 }
 
-// (H + lambda I) x = b by LDL^T without pivoting; false when a pivot is not positive
-__device__ __forceinline__ bool solve6(const double* H, double lambda, const double* b, double* x) {
-  double A[36], D[6], y[6];
-  {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-      for (int j = i; j < 6; j++, k++) { A[6 * i + j] = H[k]; A[6 * j + i] = H[k]; }
+// The caller's classification between two optimize() calls: every observation, current outliers included, by its plain chi2.
+// Returns the observations left at level 0, the same number in every lane.
+__device__ __forceinline__ int frame_classify(const Frame& F, const Pose& T, double chi2_mono, double chi2_stereo, int lane) {
+  int left = 0;
+  for (int i = lane; i < F.n; i += 64) {
+    const Obs o = obs_load(F.obs + (size_t)i * POSE_OBS_DOUBLES);
+    double e[3], pc[3], We[3];
+    obs_error(T, F.intr, o, e, pc);
+    const double c = obs_chi2(o, e, We);
+    const double thr = o.stereo ? chi2_stereo : chi2_mono;
+    const unsigned char in = (thr > 0 && c > thr) ? 0 : 1;
+    F.level[i] = in;
+    left += in;
   }
-#pragma unroll
-  for (int i = 0; i < 6; i++) A[7 * i] += lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = A[7 * j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= A[6 * j + k] * A[6 * j + k] * D[k];
-    if (!(d > 0)) ok = false;
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double s = A[6 * i + j];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= A[6 * i + k] * A[6 * j + k] * D[k];
-      A[6 * i + j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= A[6 * i + k] * y[k];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] /= D[i];
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) s -= A[6 * k + i] * x[k];
-    x[i] = s;
-  }
-  return ok;
+  return wave_sum_all(left);
 }
+
+// The frame as cs_dense_lm.h's problem: one free VertexSE3Expmap under the frame's level-0 edges
+struct FrameLm {
+  const Frame& F;
+  bool robust;
+  int lane;
+  __device__ __forceinline__ void linearize(const Pose& T, double* H, double* b, double& chi) const { frame_linearize(F, T, robust, lane, H, b, chi); }
+  __device__ __forceinline__ double chi2(const Pose& T) const { return frame_chi2(F, T, robust, lane); }
+  __device__ __forceinline__ Pose oplus(const Pose& T, const double* x) const { return cam_oplus(T, x); }
+};
 
 __global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(const PoseLaunch a) {
   const int lane = threadIdx.x & 63;
@@ -229,81 +198,19 @@ __global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(c
   Pose T = T0;
   // every edge starts at level 0.  A lane reads back only what it wrote itself (observation i belongs to lane i & 63 throughout).
   for (int i = lane; i < F.n; i += 64) F.level[i] = 1;
+  int n_act = F.n;                                   // level-0 edges, the same in every lane
 
   for (int r = 0; r < a.n_rounds; r++) {
     if (a.restart_each_round) T = T0;
     const bool robust = r < a.robust_rounds;
-    int n_act = 0;
-    for (int i = lane; i < F.n; i += 64) n_act += F.level[i];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) n_act += __shfl_xor(n_act, m, 64);
     int done = 0;
     double currentChi = 0.0;
-    if (n_act > 0) {
-      const int iterations = a.iterations[r];
-      if (iterations <= 0) currentChi = frame_chi2(F, T, robust, lane);
-      double lambda = 0.0, ni = 2.0;
-      int nBad = 0;
-      for (int it = 0; it < iterations; it++) {
-        double H[21], b[6];
-        frame_linearize(F, T, robust, lane, H, b, currentChi);
-        if (it == 0) {                               // computeLambdaInit (:166-180): tau * max |H_jj|, tau = 1e-5
-          double md = 0.0;
-          int k = 0;
-#pragma unroll
-          for (int j = 0; j < 6; k += 6 - j, j++) md = fmax(fabs(H[k]), md);
-          lambda = 1e-5 * md;
-          ni = 2.0; nBad = 0;
-        }
-        const double iniChi = currentChi;
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-          double x[6];
-          const bool ok2 = solve6(H, lambda, b, x);
-          double tempChi = DBL_MAX, scale = 0.0;
-          Pose Tn = T;
-          if (ok2) {
-            Tn = cam_oplus(T, x);
-            tempChi = frame_chi2(F, Tn, robust, lane);
-#pragma unroll
-            for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);      // computeScale (:182-189)
-          }
-          rho = currentChi - tempChi;
-          scale += 1e-3;
-          rho /= scale;
-          if (rho > 0 && isfinite(tempChi)) {
-            double alpha = 1. - pow(2 * rho - 1, 3.0);
-            alpha = fmin(alpha, 2. / 3.);
-            lambda *= fmax(1. / 3., alpha);
-            ni = 2.0;
-            currentChi = tempChi;
-            T = Tn;
-          } else {
-            lambda *= ni;
-            ni *= 2;
-          }
-          qmax++;
-        } while (rho < 0 && qmax < 10);
-        done++;
-        if (qmax == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        if (nBad >= 3) break;
-      }
-    }
+    if (n_act > 0) done = dense_lm_round<6>(FrameLm{F, robust, lane}, T, a.iterations[r], 10, currentChi);
     if (lane == 0) {
       a.iters_out[f * a.n_rounds + r] = done;
       a.chi2_out[f * a.n_rounds + r] = currentChi;
     }
-    // the caller's classification between two optimize() calls: every observation, current outliers included, by its plain chi2
-    for (int i = lane; i < F.n; i += 64) {
-      const Obs o = obs_load(F.obs + (size_t)i * POSE_OBS_DOUBLES);
-      double e[3], pc[3], We[3];
-      obs_error(T, F.intr, o, e, pc);
-      const double c = obs_chi2(o, e, We);
-      const double thr = o.stereo ? a.chi2_stereo : a.chi2_mono;
-      F.level[i] = (thr > 0 && c > thr) ? 0 : 1;
-    }
+    n_act = frame_classify(F, T, a.chi2_mono, a.chi2_stereo, lane);
   }
   if (lane == 0) pose_store(T, a.T_out + 7 * f);
 }

@@ -15,23 +15,13 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
-#include "cs_hip_util.h"
+#include "cs_batch_handle.h"
 #include "sim3_pair_types.h"
 
-struct cs_sim3_pairs {
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  cs::DevBuf<unsigned char> d_in;      // [S0 | intr | records | match_ptr | fix_scale], one upload
-  cs::DevBuf<unsigned char> d_out;     // [S_out | chi2 | iterations | n_inliers | inlier] or [err | jac], one download
-  cs::PinBuf<unsigned char> h_in, h_out;     // pinned staging of the two
-  double kernel_ms = 0, host_ms = 0;
-  bool ran = false;
-};
+// d_in = [S0 | intr | records | match_ptr | fix_scale], d_out = [S_out | chi2 | iterations | n_inliers | inlier] or [err | jac]
+struct cs_sim3_pairs : cs::BatchHandle {};
 
 namespace {
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 bool all_finite(const double* v, size_t n) {
   for (size_t i = 0; i < n; i++)
@@ -53,10 +43,7 @@ int check_pairs(const char* who, int n_pairs, const double* S12_in, const double
                 const double* P1, const double* P2, const double* obs1, const double* obs2, const double* info12, const double* info21, size_t* n_matches) {
   auto fail = [&](const char* what) { cs_set_error((std::string(who) + ": " + what).c_str()); return CS_ERR_INVALID_ARG; };
   if (!S12_in || !intr8 || !fix_scale || !match_ptr) return fail("NULL argument");
-  // the kernel indexes the records by match_ptr alone: it must be a non-decreasing partition of [0, n_matches)
-  if (match_ptr[0] != 0) return fail("match_ptr[0] must be 0");
-  for (int f = 0; f < n_pairs; f++)
-    if (match_ptr[f + 1] < match_ptr[f]) return fail("match_ptr must not decrease");
+  if (int rc = cs::check_partition(std::string(who) + ": match_ptr", match_ptr, n_pairs)) return rc;
   const size_t n = (size_t)match_ptr[n_pairs];
   if (n > (size_t)INT_MAX / 28) return fail("too many matches for one call");      // every index the kernel forms, the Jacobians' included, fits an int
   if (n > 0 && (!P1 || !P2 || !obs1 || !obs2)) return fail("NULL match array");
@@ -72,13 +59,14 @@ int check_pairs(const char* who, int n_pairs, const double* S12_in, const double
 struct InLayout { size_t S, intr, rec, ptr, fs, bytes; };
 
 InLayout in_layout(size_t np, size_t n) {
+  cs::Layout in;
   InLayout L;
-  L.S = 0;
-  L.intr = align256(L.S + 8 * np * 8);
-  L.rec = align256(L.intr + 8 * np * 8);
-  L.ptr = align256(L.rec + n * cs::SIM3_PAIR_MATCH_DOUBLES * 8);
-  L.fs = align256(L.ptr + (np + 1) * 4);
-  L.bytes = align256(L.fs + np);
+  L.S = in.add(8 * np * 8);
+  L.intr = in.add(8 * np * 8);
+  L.rec = in.add(n * cs::SIM3_PAIR_MATCH_DOUBLES * 8);
+  L.ptr = in.add((np + 1) * 4);
+  L.fs = in.add(np);
+  L.bytes = in.bytes;
   return L;
 }
 
@@ -126,33 +114,9 @@ void cs_sim3_pair_default_params(cs_sim3_pair_params* p) {
   p->min_inliers = 10;
 }
 
-int cs_sim3_pairs_create(int device, cs_sim3_pairs** out) {
-  if (!out) return CS_ERR_INVALID_ARG;
-  *out = nullptr;
-  { const int rc = cs::check_device(device); if (rc) return rc; }
-  cs_sim3_pairs* B = new (std::nothrow) cs_sim3_pairs();
-  if (!B) return CS_ERR_CAPACITY;
-  struct Guard { cs_sim3_pairs* b; ~Guard() { if (b) cs_sim3_pairs_destroy(b); } } g{B};
-  B->device = device;
-  CS_HIP_TRY(hipSetDevice(device));
-  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
-  CS_HIP_TRY(hipEventCreate(&B->ev0));
-  CS_HIP_TRY(hipEventCreate(&B->ev1));
-  g.b = nullptr;
-  *out = B;
-  return CS_OK;
-}
+int cs_sim3_pairs_create(int device, cs_sim3_pairs** out) { return cs::batch_create(device, out); }
 
-void cs_sim3_pairs_destroy(cs_sim3_pairs* B) {
-  if (!B) return;
-  (void)hipSetDevice(B->device);
-  if (B->st) (void)hipStreamSynchronize(B->st);
-  B->d_in.release(); B->d_out.release(); B->h_in.release(); B->h_out.release();
-  if (B->ev0) (void)hipEventDestroy(B->ev0);
-  if (B->ev1) (void)hipEventDestroy(B->ev1);
-  if (B->st) (void)hipStreamDestroy(B->st);
-  delete B;
-}
+void cs_sim3_pairs_destroy(cs_sim3_pairs* B) { cs::batch_destroy(B); }
 
 int cs_sim3_pairs_optimize(cs_sim3_pairs* B, const cs_sim3_pair_params* p, int n_pairs, const double* S12_in, const double* intr8, const unsigned char* fix_scale,
                            const int* match_ptr, const double* P1, const double* P2, const double* obs1, const double* obs2, const double* info12, const double* info21,
@@ -167,56 +131,37 @@ int cs_sim3_pairs_optimize(cs_sim3_pairs* B, const cs_sim3_pair_params* p, int n
   B->ran = false;                                      // (a refused call leaves the last run's timing in place; one that fails from here on does not)
   const size_t np = (size_t)n_pairs;
 
-  // ---- layout of the two buffers (every part 256-byte aligned)
+  // ---- layout of the two buffers
   const InLayout L = in_layout(np, n);
-  const size_t out_S = 0, out_chi = align256(out_S + 8 * np * 8), out_it = align256(out_chi + 2 * np * 8), out_ni = align256(out_it + 2 * np * 4),
-               out_lv = align256(out_ni + np * 4), out_bytes = align256(out_lv + n);
-  CS_HIP_TRY(hipSetDevice(B->device));
-  rc = B->d_in.ensure(L.bytes); if (rc) return rc;
-  rc = B->d_out.ensure(out_bytes); if (rc) return rc;
-  rc = B->h_in.ensure(L.bytes); if (rc) return rc;
-  rc = B->h_out.ensure(out_bytes); if (rc) return rc;
-  pack_inputs(B->h_in.p, L, np, n, S12_in, intr8, fix_scale, match_ptr, P1, P2, obs1, obs2, info12, info21);
+  cs::Layout out;
+  const size_t out_S = out.add(8 * np * 8), out_chi = out.add(2 * np * 8), out_it = out.add(2 * np * 4), out_ni = out.add(np * 4), out_lv = out.add(n);
 
   cs::Sim3PairLaunch a;
-  set_inputs(a, B->d_in.p, L, n_pairs);
-  a.sched.iterations_first = p->iterations_first; a.sched.iterations_more_clean = p->iterations_more_clean; a.sched.iterations_more_outliers = p->iterations_more_outliers;
-  a.sched.robust_second_round = p->robust_second_round ? 1 : 0; a.sched.min_inliers = p->min_inliers;
-  a.sched.th2 = p->th2; a.sched.huber_delta = p->huber_delta;
-  a.S_out = reinterpret_cast<double*>(B->d_out.p + out_S);
-  a.chi2_out = reinterpret_cast<double*>(B->d_out.p + out_chi);
-  a.iters_out = reinterpret_cast<int*>(B->d_out.p + out_it);
-  a.n_inliers = reinterpret_cast<int*>(B->d_out.p + out_ni);
-  a.inlier = B->d_out.p + out_lv;
-
-  CS_HIP_TRY(hipMemcpyAsync(B->d_in.p, B->h_in.p, L.bytes, hipMemcpyHostToDevice, B->st));
-  CS_HIP_TRY(hipEventRecord(B->ev0, B->st));
-  cs::sim3_pair_launch(a, B->st);
-  CS_HIP_TRY(hipGetLastError());
-  CS_HIP_TRY(hipEventRecord(B->ev1, B->st));
-  CS_HIP_TRY(hipMemcpyAsync(B->h_out.p, B->d_out.p, out_bytes, hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
-  float ms = 0;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+  auto pack = [&] {
+    pack_inputs(B->h_in.p, L, np, n, S12_in, intr8, fix_scale, match_ptr, P1, P2, obs1, obs2, info12, info21);
+    set_inputs(a, B->d_in.p, L, n_pairs);
+    a.sched.iterations_first = p->iterations_first; a.sched.iterations_more_clean = p->iterations_more_clean; a.sched.iterations_more_outliers = p->iterations_more_outliers;
+    a.sched.robust_second_round = p->robust_second_round ? 1 : 0; a.sched.min_inliers = p->min_inliers;
+    a.sched.th2 = p->th2; a.sched.huber_delta = p->huber_delta;
+    a.S_out = reinterpret_cast<double*>(B->d_out.p + out_S);
+    a.chi2_out = reinterpret_cast<double*>(B->d_out.p + out_chi);
+    a.iters_out = reinterpret_cast<int*>(B->d_out.p + out_it);
+    a.n_inliers = reinterpret_cast<int*>(B->d_out.p + out_ni);
+    a.inlier = B->d_out.p + out_lv;
+  };
+  rc = cs::batch_round_trip(*B, L.bytes, out.bytes, true, pack, [&] { cs::sim3_pair_launch(a, B->st); }); if (rc) return rc;
 
   std::memcpy(S12_out, B->h_out.p + out_S, 8 * np * 8);
   if (chi2_out) std::memcpy(chi2_out, B->h_out.p + out_chi, 2 * np * 8);
   if (iterations_done) std::memcpy(iterations_done, B->h_out.p + out_it, 2 * np * 4);
   std::memcpy(n_inliers_out, B->h_out.p + out_ni, np * 4);
   if (n) std::memcpy(inlier_out, B->h_out.p + out_lv, n);
-  B->kernel_ms = ms;
   B->host_ms = cs::now_ms() - t_begin;
   B->ran = true;
   return CS_OK;
 }
 
-int cs_sim3_pairs_last_timing(const cs_sim3_pairs* B, double* kernel_ms, double* host_ms) {
-  if (!B) return CS_ERR_INVALID_ARG;
-  if (!B->ran) return CS_ERR_NOT_RUN;
-  if (kernel_ms) *kernel_ms = B->kernel_ms;
-  if (host_ms) *host_ms = B->host_ms;
-  return CS_OK;
-}
+int cs_sim3_pairs_last_timing(const cs_sim3_pairs* B, double* kernel_ms, double* host_ms) { return cs::batch_last_timing(B, kernel_ms, host_ms); }
 
 int cs_sim3_optimize_pairs(int device, const cs_sim3_pair_params* p, int n_pairs, const double* S12_in, const double* intr8, const unsigned char* fix_scale,
                            const int* match_ptr, const double* P1, const double* P2, const double* obs1, const double* obs2, const double* info12, const double* info21,
@@ -244,21 +189,16 @@ int cs_sim3_pairs_linearize(int device, int n_pairs, const double* S12_in, const
   struct Guard { cs_sim3_pairs* b; ~Guard() { cs_sim3_pairs_destroy(b); } } g{B};
   const size_t np = (size_t)n_pairs;
   const InLayout L = in_layout(np, n);
-  const size_t out_err = 0, out_jac = align256(out_err + 4 * n * 8), out_bytes = align256(out_jac + 28 * n * 8);
-  rc = B->d_in.ensure(L.bytes); if (rc) return rc;
-  rc = B->d_out.ensure(out_bytes); if (rc) return rc;
-  rc = B->h_in.ensure(L.bytes); if (rc) return rc;
-  rc = B->h_out.ensure(out_bytes); if (rc) return rc;
-  pack_inputs(B->h_in.p, L, np, n, S12_in, intr8, fix_scale, match_ptr, P1, P2, obs1, obs2, nullptr, nullptr);
+  cs::Layout out;
+  const size_t out_err = out.add(4 * n * 8), out_jac = out.add(28 * n * 8);
   cs::Sim3PairLaunch a;
-  set_inputs(a, B->d_in.p, L, n_pairs);
-  a.err = reinterpret_cast<double*>(B->d_out.p + out_err);
-  a.jac = reinterpret_cast<double*>(B->d_out.p + out_jac);
-  CS_HIP_TRY(hipMemcpyAsync(B->d_in.p, B->h_in.p, L.bytes, hipMemcpyHostToDevice, B->st));
-  cs::sim3_pair_launch_linearize(a, B->st);
-  CS_HIP_TRY(hipGetLastError());
-  CS_HIP_TRY(hipMemcpyAsync(B->h_out.p, B->d_out.p, out_bytes, hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
+  auto pack = [&] {
+    pack_inputs(B->h_in.p, L, np, n, S12_in, intr8, fix_scale, match_ptr, P1, P2, obs1, obs2, nullptr, nullptr);
+    set_inputs(a, B->d_in.p, L, n_pairs);
+    a.err = reinterpret_cast<double*>(B->d_out.p + out_err);
+    a.jac = reinterpret_cast<double*>(B->d_out.p + out_jac);
+  };
+  rc = cs::batch_round_trip(*B, L.bytes, out.bytes, false, pack, [&] { cs::sim3_pair_launch_linearize(a, B->st); }); if (rc) return rc;
   std::memcpy(err4, B->h_out.p + out_err, 4 * n * 8);
   std::memcpy(jac28, B->h_out.p + out_jac, 28 * n * 8);
   return CS_OK;

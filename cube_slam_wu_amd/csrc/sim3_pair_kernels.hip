@@ -3,8 +3,7 @@
 // The arithmetic and the control flow are cs_sim3_pair.h's sim3_pair_optimize (the g2o lines it restates are cited there); this file
 // gives it its wave: one wavefront per pair, the whole optimisation -- both rounds, every iteration and trial -- inside one launch, as
 // pose_kernels.hip does for a frame.  Lane l owns the pair's matches l, l + 64, ...; its share of the 28 upper entries of H, of b and of
-// chi2 is summed over the lanes by pose_kernels.hip's butterfly (lane ^ 32, ^ 16, ... ^ 1: a fixed order, and -- both partners add the
-// same two numbers -- the same bits in every lane), so every lane holds the same system, runs the same 7 x 7 factorisation and takes the
+// chi2 is summed over the lanes by cs_wave.h's wave_sum_all (a butterfly: a fixed order, and the same bits in every lane), so every lane holds the same system, runs the same 7 x 7 factorisation and takes the
 // same LM decisions: the control flow never diverges, and a pair's result is the same bits at any position in any batch.
 //
 // The 15 states of a linearisation (S, S (+) +-delta e_d, each with its inverse: 240 doubles) are wave-uniform.  Lanes 0..14 build one
@@ -13,6 +12,7 @@
 // leaves at once.  FP64, -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
+#include "cs_wave.h"
 #include "sim3_pair_types.h"
 
 namespace cs {
@@ -24,27 +24,14 @@ enum { STATE_PITCH = SIM3_PAIR_STATE_DOUBLES + 1, WAVE_LDS_DOUBLES = SIM3_PAIR_S
 struct Wave64 {
   int lane, stride;
   double* st;                    // this wave's WAVE_LDS_DOUBLES of LDS
-  __device__ __forceinline__ double sum(double v) const {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-  }
-  __device__ __forceinline__ int sum(int v) const {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-  }
+  __device__ __forceinline__ double sum(double v) const { return wave_sum_all(v); }
+  __device__ __forceinline__ int sum(int v) const { return wave_sum_all(v); }
   __device__ __forceinline__ void put(int k, const double* v) {
 #pragma unroll
     for (int j = 0; j < SIM3_PAIR_STATE_DOUBLES; j++) st[STATE_PITCH * k + j] = v[j];
   }
   __device__ __forceinline__ const double* get(int k) const { return st + STATE_PITCH * k; }
-  // 144 bytes, 16-byte aligned (the host packs the records behind a 256-byte aligned base)
-  __device__ __forceinline__ void load(const double* __restrict__ rec, double* v) const {
-    const double2* p = reinterpret_cast<const double2*>(rec);
-#pragma unroll
-    for (int k = 0; k < SIM3_PAIR_MATCH_DOUBLES / 2; k++) { const double2 t = p[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
-  }
+  __device__ __forceinline__ void load(const double* __restrict__ rec, double* v) const { load_record<SIM3_PAIR_MATCH_DOUBLES>(rec, v); }      // 144 bytes
   // one wave, program order: the fence keeps the compiler from moving LDS accesses across it
   // 240 doubles are not to live in VGPRs across the match loop: behind this fence the compiler reads the states from LDS again
   __device__ __forceinline__ void reread() const { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }

@@ -730,7 +730,7 @@ int  cs_pgo_last_timing(cs_pgo* g, double* linearize_ms, double* solve_ms, doubl
  * column).  The quadratic form and the rho' weighting are BaseBinaryEdge::constructQuadraticForm's (:55-120), the kernel is
  * RobustKernelHuber with its single-precision delta^2 (core/robust_kernel_impl.h:86; cs_robust.h: huber_rho).  Each round is
  * SparseOptimizer::optimize (core/sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg
- * (core/optimization_algorithm_levenberg.cpp:61-189) in the arithmetic of cs_lm.h, stated on the device as pose_kernels.hip states it:
+ * (core/optimization_algorithm_levenberg.cpp:61-189) in the policy of cs_lm.h, run on the device by cs_dense_lm.h's loop as for cs_pose_*:
  * EACH optimize() call re-initialises lambda (tau * max |H_jj|, tau = 1e-5), ni and nBad; at most 10 trials per iteration; the second
  * round continues from the state the first ended on.  The 7 x 7 system H + lambda I goes through an LDL^T without pivoting, and a
  * pivot that is not positive makes the trial a failed one (LinearSolverDense, solvers/linear_solver_dense.h:104-111).  A depth of zero
