@@ -14,6 +14,8 @@
 //   finish  (host, threaded)  cs_cuboid records of the winners (:740-798, object_3d_util.cpp:941-1011); the few boxes whose
 //                             ties could reach the output are fetched and ranked with the exact std::partial_sort.
 // The same stages exist as a general round-based path (debug getters, host ranking / host line setup on request).
+// What the paths share is stated once: the rules in front of the kernels in detect_jobs_host.h, those behind them in detect_rank_host.h,
+// the device tables and the view over them in SweepBuffers, the tie boxes' pass in TiePass.
 // With whether_sample_cam_roll_pitch the reference carries cam_pose.camera_yaw from one box to the next
 // (:180 reads what :374/:734 left behind), so boxes of a frame are processed in rounds (round r = box r of
 // every frame), each ranked on the device; without it all boxes of all frames go through the sweep in one launch.
@@ -40,6 +42,7 @@
 #include "../../include/cubeslam_hip.h"
 #include "cs_hip_util.h"
 #include "detect_hooks.h"
+#include "detect_jobs_host.h"
 #include "detect_rank_host.h"
 #include "detect_types.h"
 #include "edge_types.h"
@@ -47,7 +50,7 @@
 thread_local std::string g_cs_err;  // shared by every path (cs_hip_util.h: cs_set_error)
 void cs_set_error(const std::string& s) { g_cs_err = s; }
 
-using namespace cs_dh;   // detect_rank_host.h: FrameIn, the slot decode, the exact ranking, the record writers
+using namespace cs_dh;   // detect_jobs_host.h: the job-table rules; detect_rank_host.h: FrameIn, the slot decode, the exact ranking, the record writers
 
 namespace {
 
@@ -190,15 +193,6 @@ void make_cam(const double* K, const double* R, const double* t, CamCache& c) {
   c.pose.plane[3] = ((t[0] * 0.0 + t[1] * 0.0) + t[2] * 1.0) + 1.0 * 0.0;
   c.pose.roll = c.euler[0];
   c.pose.pitch = c.euler[1];
-}
-
-template <class T>
-void linespace(T a, T b, T step, std::vector<T>& out) {  // matrix_utils.cpp:368-380
-  while (a <= b) {
-    out.push_back(a);
-    a += step;
-    if (out.size() > 1000) break;
-  }
 }
 
 // merge_break_lines (object_3d_util.cpp:431-543) on a row-major n x 4 array.
@@ -425,20 +419,46 @@ struct JobResult {        // rank-stage products retained for cs_batch_debug_*
   std::vector<double> corners;   // V x 16 when debug is on
 };
 
+// The device tables of one sweep with their pinned companions, for all three paths (a PipeSlot holds one, the round path's is the batch's).
+// What only one path needs (flag, bound3, the fb_* pool of the lean roll/pitch path) that path grows itself.
+struct cs_batch;
+struct SweepBuffers {
+  DevBuf<cs::JobDesc> jobs;
+  DevBuf<long long> slot_prefix, job_cbase, c_slot, fb_slot;
+  DevBuf<int> vp_prefix, top_x, flag, job_valid, c_flag, box_job0, box_njobs, win_count, fallback, fb_flag;
+  DevBuf<double> mid_x, mid_y, ang, yaw, yaw_c, yaw_s, vp, bound, bound3, c_dist, c_angle, c_skew, fb_dist, fb_angle, fb_skew;
+  DevBuf<cs::RankWinner> winners;
+  PinBuf<long long> h_job_cbase, h_fb_src, h_fb_dst, h_fb_slot, h_win_slots;      // h_fb_*, h_win_*: what the tie boxes' gather kernels read and write
+  PinBuf<int> h_job_valid, h_win_count, h_fallback, h_fb_cnt, h_fb_flag;
+  PinBuf<double> h_fb_dist, h_fb_angle, h_fb_skew, h_win_corners;
+  // nj jobs, n_prefix prefix entries (nj + 1; lean roll/pitch: one more per round), pooled line / yaw / top-sample entries, (rp, yaw) samples, nb boxes
+  int ensure_tables(size_t nj, size_t n_prefix, size_t n_lines, size_t n_yaw, size_t n_top, size_t vp_total, size_t nb, int kmax) {
+    CS_ENSURE(jobs, nj); CS_ENSURE(slot_prefix, n_prefix); CS_ENSURE(vp_prefix, n_prefix); CS_ENSURE(job_valid, nj); CS_ENSURE(job_cbase, n_prefix);
+    CS_ENSURE(mid_x, n_lines + 1); CS_ENSURE(mid_y, n_lines + 1); CS_ENSURE(ang, n_lines + 1); CS_ENSURE(yaw, n_yaw + 1); CS_ENSURE(yaw_c, n_yaw + 1); CS_ENSURE(yaw_s, n_yaw + 1);
+    CS_ENSURE(top_x, n_top + 1); CS_ENSURE(vp, 6 * vp_total + 6); CS_ENSURE(bound, 6 * vp_total + 6);
+    CS_ENSURE(box_job0, nb + 1); CS_ENSURE(box_njobs, nb + 1); CS_ENSURE(win_count, nb + 1); CS_ENSURE(fallback, nb + 1); CS_ENSURE(winners, nb * (size_t)kmax + 1);
+    CS_ENSURE(h_win_count, nb + 1); CS_ENSURE(h_fallback, nb + 1); CS_ENSURE(h_job_valid, nj); CS_ENSURE(h_job_cbase, n_prefix);
+    return CS_OK;
+  }
+  int ensure_slots(long long rows) {      // the compacted columns
+    return c_slot.ensure(rows + 1) || c_flag.ensure(rows + 1) || c_dist.ensure(rows + 1) || c_angle.ensure(rows + 1) || c_skew.ensure(rows + 1) ? CS_ERR_HIP : CS_OK;
+  }
+  // The view over n_jobs jobs from job j0, prefix entry p0 on (io: a small production call's tables lie in its I/O block, laid out as A).
+  // Pointers of buffers a path never grew are null or stale; its kernels do not read them.
+  void bind(cs::DetectDeviceView& v, const cs_batch& b, size_t n_jobs, size_t j0 = 0, size_t p0 = 0, unsigned char* io = nullptr, const SmallCallArena* A = nullptr) const;
+  // one height sample's rows [p0, p0 + V) of the fetched tie columns
+  HeightCols fb_cols(long long p0, int V) const { return HeightCols{h_fb_dist.p + p0, h_fb_angle.p + p0, h_fb_skew.p + p0, h_fb_flag.p + p0, h_fb_slot.p + p0, V}; }
+};
+
 // One of the two in-flight chunks of the pipelined production path (pipe_launch / pipe_finish).  Its buffers free themselves.
 struct PipeSlot {
-  DevBuf<cs::JobDesc> jobs;
+  SweepBuffers sb;
   DevBuf<unsigned char> tab_arena;       // a small call's tables in one block: one upload instead of ten (single-frame latency)
   PinBuf<unsigned char> h_tab_arena;
   bool merged_io = false;                // this slot's call went through the block: its results are unpacked from h_tab_arena in pipe_finish
-  size_t o_jobs = 0, o_rec = 0, o_wc = 0, o_fb = 0, o_jv = 0, o_cb = 0, o_end = 0;
-  DevBuf<long long> slot_prefix, job_cbase, c_slot, fb_slot;
-  DevBuf<int> vp_prefix, top_x, flag, job_valid, c_flag, box_job0, box_njobs, win_count, fallback, fb_flag;
-  DevBuf<double> bound3;
+  SmallCallArena arena;                  // ... laid out like this
   DevBuf<int> ls_order, blk_info, ls_crowded;
   PinBuf<int> h_ls_order;
-  DevBuf<double> mid_x, mid_y, ang, yaw, yaw_c, yaw_s, vp, bound, c_dist, c_angle, c_skew, fb_dist, fb_angle, fb_skew;
-  DevBuf<cs::RankWinner> winners;
   DevBuf<cs_cuboid> records;        // the winners' records of the device-ranked boxes (record_kernel)
   PinBuf<cs_cuboid> h_records;
   // lean roll/pitch path (rp_launch / rp_finish): all rounds of the batch queued at once
@@ -458,12 +478,9 @@ struct PipeSlot {
   int rp_NT = 0, rp_YCAP = 0;
   std::vector<hipEvent_t> rp_ev;     // 5 per round: start, corners + compaction, VP support, scorer, ranking + records
   PinBuf<cs::JobDesc> h_jobs_in, h_jobs_out;
-  PinBuf<long long> h_slot_prefix, h_job_cbase;
-  PinBuf<int> h_vp_prefix, h_top_x, h_box_job0, h_box_njobs, h_win_count, h_fallback, h_job_valid;
+  PinBuf<long long> h_slot_prefix;
+  PinBuf<int> h_vp_prefix, h_top_x, h_box_job0, h_box_njobs;
   PinBuf<double> h_yaw, h_yaw_c, h_yaw_s;
-  PinBuf<long long> h_fb_src, h_fb_dst, h_fb_slot, h_win_slots;
-  PinBuf<int> h_fb_cnt, h_fb_flag;
-  PinBuf<double> h_fb_dist, h_fb_angle, h_fb_skew, h_win_corners;
   hipEvent_t done = nullptr, ev[13] = {};   // 0-6: phase marks on the main stream; 7: inputs resident; 8-11: second stream (corner construction); 12: line setup of the crowded ROIs done (third stream)
   cs::DetectDeviceView view{};
   int f0 = 0, f1 = 0, vp_total = 0;
@@ -509,26 +526,18 @@ struct cs_batch {
   DevBuf<int> d_frame_line_ptr;
   bool device_setup = false;   // every frame's segment count fits the line-setup kernel's LDS table
   bool force_host_setup = false;
-  // per-round device pools
-  DevBuf<cs::JobDesc> d_jobs;
-  DevBuf<long long> d_slot_prefix, d_job_cbase, d_c_slot, d_win_slots;
-  DevBuf<int> d_vp_prefix, d_top_x, d_flag, d_job_valid, d_c_flag;
-  DevBuf<double> d_mid_x, d_mid_y, d_ang, d_yaw, d_yaw_c, d_yaw_s, d_vp, d_bound, d_c_dist, d_c_angle, d_c_skew, d_win_corners;
-  DevBuf<cs::RpPose> d_rp;
-  PinBuf<long long> h_c_slot, h_job_cbase;
-  PinBuf<int> h_c_flag, h_job_valid;
-  PinBuf<double> h_c_dist, h_c_angle, h_c_skew, h_win_corners;
-  DevBuf<int> d_box_job0, d_box_njobs, d_win_count, d_fallback;
+  DevBuf<cs::RpPose> d_rp;      // the frames' roll/pitch sample poses, all paths
+  // round path: the device tables of the round in flight, and what only this path brings back (every compacted column for the host
+  // ranking, the device's winners with their corners, the carried proposal, the job table)
+  SweepBuffers round;
+  PinBuf<long long> h_c_slot;
+  PinBuf<int> h_c_flag;
+  PinBuf<double> h_c_dist, h_c_angle, h_c_skew;
   DevBuf<long long> d_last_slot;
   PinBuf<long long> h_last_slot;
-  DevBuf<cs::RankWinner> d_winners;
-  DevBuf<long long> d_fb_src, d_fb_dst, d_fb_slot;
-  DevBuf<int> d_fb_cnt, d_fb_flag;
-  DevBuf<double> d_fb_dist, d_fb_angle, d_fb_skew;
   PinBuf<cs::RankWinner> h_winners;
-  PinBuf<int> h_win_count, h_fallback;
   PinBuf<cs::JobDesc> h_jobs;
-  PinBuf<unsigned char> h_tables, h_tables2;   // the job tables of one round, staged in pinned memory: their uploads are asynchronous and back to back
+  PinBuf<unsigned char> h_tables;   // the job tables of one round, staged in pinned memory: their uploads are asynchronous and back to back
   bool force_host_rank = false;
   bool force_round_path = false;   // roll/pitch sampling through the round-by-round path (the lean path's redo of frames with tie boxes)
   // state
@@ -544,6 +553,18 @@ struct cs_batch {
     for (auto& e : ev_edge_done) if (e) (void)hipEventDestroy(e);
   }
 };
+
+void SweepBuffers::bind(cs::DetectDeviceView& v, const cs_batch& b, size_t n_jobs, size_t j0, size_t p0, unsigned char* io, const SmallCallArena* A) const {
+  v = cs::DetectDeviceView{};
+  v.jobs = jobs.p + j0; v.n_jobs = (int)n_jobs; v.slot_prefix = slot_prefix.p + p0; v.vp_prefix = vp_prefix.p + p0; v.maps = b.d_maps.p;
+  v.mid_x = mid_x.p; v.mid_y = mid_y.p; v.line_angle = ang.p; v.yaw = yaw.p; v.yaw_cos = yaw_c.p; v.yaw_sin = yaw_s.p; v.top_x = top_x.p;
+  v.rp = b.d_rp.p; v.invK = b.d_invK.p; v.vp = vp.p; v.bound = bound.p; v.bound3 = bound3.p; v.flag = flag.p; v.job_valid = job_valid.p + j0;
+  v.job_cbase = job_cbase.p + p0; v.c_slot = c_slot.p; v.c_flag = c_flag.p; v.c_dist = c_dist.p; v.c_angle = c_angle.p; v.c_skew = c_skew.p;
+  if (!io) return;
+  v.jobs = reinterpret_cast<cs::JobDesc*>(io + A->o_jobs); v.slot_prefix = reinterpret_cast<long long*>(io + A->o_sp); v.vp_prefix = reinterpret_cast<int*>(io + A->o_vp);
+  v.yaw = reinterpret_cast<double*>(io + A->o_y); v.yaw_cos = reinterpret_cast<double*>(io + A->o_yc); v.yaw_sin = reinterpret_cast<double*>(io + A->o_ys);
+  v.top_x = reinterpret_cast<int*>(io + A->o_tx); v.job_valid = reinterpret_cast<int*>(io + A->o_jv); v.job_cbase = reinterpret_cast<long long*>(io + A->o_cb);
+}
 
 
 // The C ABI is the trust boundary: a 2D box must lie inside the image (its far edges are pixel coordinates the sweep
@@ -909,12 +930,7 @@ static int batch_layout(cs_detector* d, cs_batch* b) {
       int nj = 0;
       for (int bi = 0; bi < F.n_boxes; bi++) {
         nj += F.n_heights[bi];
-        const double* bb = &F.boxes[5 * bi];
-        int left = bb[0], w = bb[2], right = left + bb[2];
-        int res = (int)std::round(std::min(20, w / 10));
-        std::vector<int> tops;
-        if (res >= 1) linespace<int>(left + 5, right - 5, res, tops);   // :215-219: the count depends on the box alone
-        b->top_base.push_back(b->top_base.back() + (int)tops.size());
+        b->top_base.push_back(b->top_base.back() + top_samples(&F.boxes[5 * bi], nullptr));   // :215-219: the count depends on the box alone
       }
       b->job_base[f + 1] = b->job_base[f] + nj;
       b->box_base[f + 1] = b->box_base[f] + F.n_boxes;
@@ -1060,6 +1076,55 @@ static int g_runs = 0;
 static const bool g_prof = getenv("CS_DETECT_PROF") != nullptr;   // diagnostics: host phase clock of the lean path
 #define MARK(k, t_ref) do { if (g_prof) { double t_now = now_ms(); g_mark[k] += t_now - (t_ref); (t_ref) = t_now; } } while (0)
 
+// The tie boxes of a finished sweep (B.h_fallback; B.h_job_cbase / h_job_valid say where their columns lie) get the exact ranking on the
+// host: enqueue_columns, wait, rank(q) per box on any thread, enqueue_corners, wait, corners(q, r) -- enqueue and wait apart, so that a
+// caller can work while something travels.  The gather kernels read the lists from, and write the rows to, B's pinned host pools themselves
+// (coalesced rows; no copy engine between the device and a host that is waiting for a few kilobytes).
+struct TiePass {
+  SweepBuffers& B; const cs::DetectDeviceView& v; hipStream_t st;
+  const int *box_job0, *box_njobs;                   // the sweep's box table, on the host
+  std::vector<int> boxes;                            // the flagged boxes
+  std::vector<long long> col0_of_job;                // first fetched row of a flagged box's job
+  std::vector<std::vector<ExactWinner>> winners;     // per box of the sweep (filled for the flagged ones)
+  std::vector<size_t> corner0;                       // per box: first of its winners in h_win_corners
+  TiePass(SweepBuffers& B_, const cs::DetectDeviceView& v_, hipStream_t st_, const int* job0, const int* njobs, size_t nj, size_t nb)
+      : B(B_), v(v_), st(st_), box_job0(job0), box_njobs(njobs), col0_of_job(nj, -1), winners(nb), corner0(nb, 0) {
+    for (size_t q = 0; q < nb; q++) if (B.h_fallback.p[q]) boxes.push_back((int)q);
+  }
+  int enqueue_columns() {
+    size_t nr = 0, z = 0;
+    long long tot = 0;
+    for (int q : boxes) nr += (size_t)box_njobs[q];
+    if (boxes.empty()) return CS_OK;
+    CS_ENSURE(B.h_fb_src, nr); CS_ENSURE(B.h_fb_dst, nr); CS_ENSURE(B.h_fb_cnt, nr);
+    for (int q : boxes)
+      for (int j = box_job0[q]; j < box_job0[q] + box_njobs[q]; j++, z++) {
+        B.h_fb_src.p[z] = B.h_job_cbase.p[j]; B.h_fb_cnt.p[z] = B.h_job_valid.p[j]; B.h_fb_dst.p[z] = col0_of_job[j] = tot;
+        tot += B.h_job_valid.p[j];
+      }
+    CS_ENSURE(B.h_fb_dist, tot + 1); CS_ENSURE(B.h_fb_angle, tot + 1); CS_ENSURE(B.h_fb_skew, tot + 1); CS_ENSURE(B.h_fb_flag, tot + 1); CS_ENSURE(B.h_fb_slot, tot + 1);
+    cs::launch_gather_ranges(v, B.h_fb_src.p, B.h_fb_cnt.p, B.h_fb_dst.p, (int)nr, B.h_fb_dist.p, B.h_fb_angle.p, B.h_fb_skew.p, B.h_fb_flag.p, B.h_fb_slot.p, st);
+    return CS_OK;
+  }
+  int wait() { if (!boxes.empty()) { CS_HIP_TRY(hipGetLastError()); CS_HIP_TRY(hipStreamSynchronize(st)); } return CS_OK; }      // (no tie box: no call into the runtime)
+  // the exact winners of flagged box q into winners[q]; returns the last kept slot of its last height sample (exact_rank_box)
+  long long rank(size_t q, const RankWeights& RW, int kmax) {
+    HeightCols cols[3];
+    for (int h = 0; h < box_njobs[q]; h++) cols[h] = B.fb_cols(col0_of_job[box_job0[q] + h], B.h_job_valid.p[box_job0[q] + h]);
+    return exact_rank_box(cols, box_njobs[q], RW, kmax, winners[q]);
+  }
+  int enqueue_corners(const cs::SweepParams& sp) {
+    size_t nw = 0;
+    for (int q : boxes) { corner0[q] = nw; nw += winners[q].size(); }
+    if (nw == 0) return CS_OK;
+    CS_ENSURE(B.h_win_slots, nw); CS_ENSURE(B.h_win_corners, 16 * nw);
+    for (int q : boxes) for (size_t r = 0; r < winners[q].size(); r++) B.h_win_slots.p[corner0[q] + r] = winners[q][r].slot;
+    cs::launch_gather_corners(v, sp, B.h_win_slots.p, (int)nw, B.h_win_corners.p, st);
+    return CS_OK;
+  }
+  const double* corners(size_t q, size_t r) const { return B.h_win_corners.p + 16 * (corner0[q] + r); }
+};
+
 int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   cs_detector* d = C.d; cs_batch* b = C.b;
   const cs_detect_params& P = d->prm;
@@ -1076,7 +1141,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   const int jb0 = b->job_base[f0], bx0 = b->box_base[f0], tp0 = b->top_base[bx0];
   const long long ln0 = b->line_base[f0];
   const size_t nj = (size_t)(b->job_base[f1] - jb0), n_lines = (size_t)(b->line_base[f1] - ln0);
-  const int YCAP = (int)(2.0 * P.yaw_range_deg / std::max(1e-9, P.yaw_step_deg)) + 3;
+  const int YCAP = yaw_list_capacity(P.yaw_range_deg, P.yaw_step_deg);
   const size_t n_yaw = (size_t)nf * YCAP, n_top = (size_t)(b->top_base[b->box_base[f1]] - tp0);
   if ((long long)nj * 1 > 0x7fffffffLL || (long long)n_lines > 0x7fffffffLL) { cs_set_error("chunk too large"); return CS_ERR_CAPACITY; }
   S.nj = nj;
@@ -1092,27 +1157,17 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     int nY = -1, ji = 0;
     for (int bi = 0; bi < F.n_boxes; bi++) {
       const double* bb = &F.boxes[5 * bi];
-      int left = bb[0], w = bb[2];
-      int right = left + bb[2];
-      int res = (int)std::round(std::min(20, w / 10));
-      const int tb = b->top_base[b->box_base[f] + bi] - tp0, tcap = b->top_base[b->box_base[f] + bi + 1] - tp0 - tb;
-      int nT = 0;
-      if (res >= 1) {
-        if (nY < 0) {  // cam_pose never changes without roll/pitch sampling: one yaw list per frame (:180-184)
-          double yaw_init = (*C.cam_raw)[f].cam_yaw - 90.0 / 180.0 * CS_PI;
-          std::vector<double> yl;
-          linespace<double>(yaw_init - P.yaw_range_deg / 180.0 * CS_PI, yaw_init + P.yaw_range_deg / 180.0 * CS_PI, P.yaw_step_deg / 180.0 * CS_PI, yl);
-          nY = (int)yl.size();
-          if (nY > YCAP) { overflow = 1; nY = 0; }
-          for (int y = 0; y < nY; y++) { yw[y] = yl[y]; yc[y] = h_cos(yl[y]); ys[y] = h_sin(yl[y]); }
-        }
-        int* tx = S.h_top_x.p + tb;
-        for (int x = left + 5; x <= right - 5 && nT < tcap; x += res) tx[nT++] = x;   // linespace<int> (matrix_utils.cpp:368-380)
+      const bool swept = top_sample_step(bb) >= 1;
+      const int tb = b->top_base[b->box_base[f] + bi] - tp0;
+      if (swept && nY < 0) {  // cam_pose never changes without roll/pitch sampling: one yaw list per frame (:180-184)
+        nY = fill_yaw_list((*C.cam_raw)[f].cam_yaw, P.yaw_range_deg, P.yaw_step_deg, YCAP, yw, yc, ys);
+        if (nY < 0) { overflow = 1; nY = 0; }
       }
+      const int nT = top_samples(bb, S.h_top_x.p + tb);      // (as many as batch_layout reserved: top_base counts them by the same rule)
       for (int k = 0; k < F.n_heights[bi]; k++) {
         cs::JobDesc jd;
         fill_job_geometry(jd, F, bi, k, (*C.rp_off)[f]);
-        jd.frame = f; jd.Y = (res >= 1) ? std::max(nY, 0) : 0; jd.T = nT; jd.RP = 1;
+        jd.frame = f; jd.Y = swept ? nY : 0; jd.T = nT; jd.RP = 1;
         jd.yaw_off = q * YCAP; jd.top_off = tb;
         jd.line_off = (int)(b->line_base[f] - ln0) + ji * F.n_lines;
         jout[ji++] = jd;
@@ -1125,33 +1180,18 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   size_t nb = 0;
   long long real_slots = 0;      // proposals (the slot space itself is padded per job)
   {
-    long long so = 0, vo = 0;
-    real_slots = 0;
+    JobSpan at{0, 0};
     for (size_t j = 0; j < nj; j++) {
       cs::JobDesc& jd = S.h_jobs_in.p[j];
-      jd.slot_off = so; jd.vp_off = (int)vo;
-      S.h_slot_prefix.p[j] = so; S.h_vp_prefix.p[j] = (int)vo;
-      // (a job's slots in multiples of 256: its compacted rows start there -- candidate_compact_kernel's capacity layout -- and a scorer
-      // workgroup never straddles two jobs)
-      real_slots += (long long)jd.Y * jd.T * 2;
-      so += ((long long)jd.Y * jd.T * 2 + 255) & ~255LL; vo += (jd.Y + 63) & ~63;   // whole waves per job: a wave of the VP kernels then reads one job (scalar loads)
-      if (jd.hid == 0 && jd.Y > 0 && jd.T > 0) { S.h_box_job0.p[nb] = (int)j; S.h_box_njobs.p[nb] = b->frames[jd.frame].n_heights[jd.box]; nb++; }
+      const JobSpan own = span_padded(jd);
+      jd.slot_off = S.h_slot_prefix.p[j] = at.slots; jd.vp_off = S.h_vp_prefix.p[j] = (int)at.vps;
+      real_slots += span_exact(jd).slots; at.slots += own.slots; at.vps += own.vps;
+      // (the null jobs of a box the reference skips open no box)
+      if (jd.hid == 0 && jd.Y > 0 && jd.T > 0) { S.h_box_job0.p[nb] = (int)j; S.h_box_njobs.p[nb++] = b->frames[jd.frame].n_heights[jd.box]; }
     }
-    S.h_slot_prefix.p[nj] = so; S.h_vp_prefix.p[nj] = (int)vo;
-    S.slot_total = so; S.vp_total = (int)vo;
-    // launch order of the line setup: jobs with the largest ROI x segment count first (a counting sort on that proxy of
-    // their sequential merge work), so that the kernel's tail is not a late-started long job
-    {
-      enum { NBK = 64 };
-      long long wmax = 1;
-      for (size_t j = 0; j < nj; j++) { const cs::JobDesc& jd = S.h_jobs_in.p[j]; wmax = std::max(wmax, (long long)(jd.g.er - jd.g.el) * (jd.g.eb - jd.g.et) * b->frames[jd.frame].n_lines); }
-      int cnt[NBK + 1] = {0};
-      auto bucket = [&](const cs::JobDesc& jd) { return NBK - 1 - (int)(((long long)(jd.g.er - jd.g.el) * (jd.g.eb - jd.g.et) * b->frames[jd.frame].n_lines) * (NBK - 1) / wmax); };
-      for (size_t j = 0; j < nj; j++) cnt[bucket(S.h_jobs_in.p[j]) + 1]++;
-      for (int q = 0; q < NBK; q++) cnt[q + 1] += cnt[q];
-      for (size_t j = 0; j < nj; j++) S.h_ls_order.p[cnt[bucket(S.h_jobs_in.p[j])]++] = (int)j;
-    }
-    if (vo > 0x7fffffffLL) { cs_set_error("too many yaw samples in one chunk"); return CS_ERR_CAPACITY; }
+    S.h_slot_prefix.p[nj] = S.slot_total = at.slots; S.h_vp_prefix.p[nj] = S.vp_total = (int)at.vps;
+    line_setup_order(S.h_jobs_in.p, nj, b->frames, S.h_ls_order.p);
+    if (at.vps > 0x7fffffffLL) { cs_set_error("too many yaw samples in one chunk"); return CS_ERR_CAPACITY; }
   }
   S.nb = nb;
   MARK(1, tq);   // prefixes + box table
@@ -1159,63 +1199,48 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   C.tm->n_jobs += (long long)nj; C.tm->n_slots += real_slots;
   // ---- device buffers, H2D, kernels, D2H: all asynchronous on the detector's stream
   const long long slot_total = S.slot_total;
-  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.jobs, nj); CS_ENSURE(S.slot_prefix, nj + 1); CS_ENSURE(S.vp_prefix, nj + 1); CS_ENSURE(S.job_valid, nj); CS_ENSURE(S.job_cbase, nj + 1);
-  CS_ENSURE(S.mid_x, n_lines + 1); CS_ENSURE(S.mid_y, n_lines + 1); CS_ENSURE(S.ang, n_lines + 1); CS_ENSURE(S.yaw, n_yaw + 1); CS_ENSURE(S.yaw_c, n_yaw + 1); CS_ENSURE(S.yaw_s, n_yaw + 1);
-  CS_ENSURE(S.top_x, n_top + 1); CS_ENSURE(S.vp, 6 * (size_t)S.vp_total + 6); CS_ENSURE(S.bound, 6 * (size_t)S.vp_total + 6); CS_ENSURE(S.bound3, nj * (size_t)cs::vp3_table_doubles_per_job());
-  CS_ENSURE(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2);
-  CS_ENSURE(S.c_slot, slot_total + 1); CS_ENSURE(S.c_flag, slot_total + 1); CS_ENSURE(S.c_dist, slot_total + 1);
-  CS_ENSURE(S.c_angle, slot_total + 1); CS_ENSURE(S.c_skew, slot_total + 1); CS_ENSURE(S.box_job0, nb + 1); CS_ENSURE(S.box_njobs, nb + 1); CS_ENSURE(S.win_count, nb + 1);
-  CS_ENSURE(S.fallback, nb + 1); CS_ENSURE(S.winners, nb * KMAX + 1); CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1);
-  CS_ENSURE(S.h_win_count, nb + 1); CS_ENSURE(S.h_fallback, nb + 1); CS_ENSURE(S.h_job_valid, nj); CS_ENSURE(S.h_job_cbase, nj + 1); CS_ENSURE(S.h_jobs_out, nj);
+  SweepBuffers& B = S.sb;
+  int rc;
+  if ((rc = B.ensure_tables(nj, nj + 1, n_lines, n_yaw, n_top, (size_t)S.vp_total, nb, KMAX)) || (rc = B.ensure_slots(slot_total))) return rc;
+  CS_ENSURE(B.bound3, nj * (size_t)cs::vp3_table_doubles_per_job());
+  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2);
+  CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1); CS_ENSURE(S.h_jobs_out, nj);
   // the tables' device addresses: the slot's own buffers, or -- a call of a frame or two, where ten copies of a few hundred bytes cost ten
   // launch latencies (~150 us of a 0.46 ms call) -- pieces of ONE block that goes up in one copy
-  int* p_ls_order = S.ls_order.p; cs::JobDesc* p_jobs = S.jobs.p; long long* p_slot_prefix = S.slot_prefix.p; int* p_vp_prefix = S.vp_prefix.p;
-  double *p_yaw = S.yaw.p, *p_yaw_c = S.yaw_c.p, *p_yaw_s = S.yaw_s.p;
-  int *p_top_x = S.top_x.p, *p_box_job0 = S.box_job0.p, *p_box_njobs = S.box_njobs.p;
-  cs_cuboid* p_records = S.records.p; int *p_win_count = S.win_count.p, *p_fallback = S.fallback.p, *p_job_valid = S.job_valid.p; long long* p_job_cbase = S.job_cbase.p;
+  cs::DetectDeviceView& v = S.view;
+  cs::RankView rv{};
+  rv.box_job0 = B.box_job0.p; rv.box_njobs = B.box_njobs.p; rv.n_boxes = (int)nb; rv.winners = B.winners.p; rv.win_count = B.win_count.p; rv.fallback = B.fallback.p;
+  int* p_ls_order = S.ls_order.p; cs_cuboid* p_records = S.records.p;
   // from the first launch to the `done` record: this batch's launches, back to back in the shared streams (StreamSet::enqueue_mu; asynchronous
   // calls only)
   std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);
-  S.merged_io = nj <= 256;
+  S.merged_io = nj <= SMALL_CALL_JOBS;
   if (S.merged_io) {
-    // layout: [inputs | the job table (in and out) | outputs] -- one copy up ([0, end of the job table)), one copy back (from the job table on)
-    size_t need = 0;
-    auto room = [&](size_t bytes) { const size_t at = need; need += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_ls = room(sizeof(int) * nj), o_sp = room(sizeof(long long) * (nj + 1)), o_vp = room(sizeof(int) * (nj + 1));
-    const size_t o_y = room(8 * n_yaw), o_yc = room(8 * n_yaw), o_ys = room(8 * n_yaw), o_tx = room(sizeof(int) * n_top), o_b0 = room(sizeof(int) * nb), o_bn = room(sizeof(int) * nb);
-    const size_t o_jobs = room(sizeof(cs::JobDesc) * nj), in_end = need;
-    S.o_jobs = o_jobs; S.o_rec = room(sizeof(cs_cuboid) * nb * KMAX); S.o_wc = room(sizeof(int) * nb); S.o_fb = room(sizeof(int) * nb); S.o_jv = room(sizeof(int) * nj);
-    S.o_cb = room(sizeof(long long) * (nj + 1)); S.o_end = need;
-    CS_ENSURE(S.tab_arena, need + 256); CS_ENSURE(S.h_tab_arena, need + 256);
+    const SmallCallArena& A = S.arena = SmallCallArena(nj, n_yaw, n_top, nb, KMAX);
+    CS_ENSURE(S.tab_arena, A.o_end + 256); CS_ENSURE(S.h_tab_arena, A.o_end + 256);
     unsigned char *hb = S.h_tab_arena.p, *db = S.tab_arena.p;
-    memcpy(hb + o_ls, S.h_ls_order.p, sizeof(int) * nj); memcpy(hb + o_jobs, S.h_jobs_in.p, sizeof(cs::JobDesc) * nj);
-    memcpy(hb + o_sp, S.h_slot_prefix.p, sizeof(long long) * (nj + 1)); memcpy(hb + o_vp, S.h_vp_prefix.p, sizeof(int) * (nj + 1));
-    if (n_yaw) { memcpy(hb + o_y, S.h_yaw.p, 8 * n_yaw); memcpy(hb + o_yc, S.h_yaw_c.p, 8 * n_yaw); memcpy(hb + o_ys, S.h_yaw_s.p, 8 * n_yaw); }
-    if (n_top) memcpy(hb + o_tx, S.h_top_x.p, sizeof(int) * n_top);
-    if (nb) { memcpy(hb + o_b0, S.h_box_job0.p, sizeof(int) * nb); memcpy(hb + o_bn, S.h_box_njobs.p, sizeof(int) * nb); }
+    memcpy(hb + A.o_ls, S.h_ls_order.p, sizeof(int) * nj); memcpy(hb + A.o_jobs, S.h_jobs_in.p, sizeof(cs::JobDesc) * nj);
+    memcpy(hb + A.o_sp, S.h_slot_prefix.p, sizeof(long long) * (nj + 1)); memcpy(hb + A.o_vp, S.h_vp_prefix.p, sizeof(int) * (nj + 1));
+    if (n_yaw) { memcpy(hb + A.o_y, S.h_yaw.p, 8 * n_yaw); memcpy(hb + A.o_yc, S.h_yaw_c.p, 8 * n_yaw); memcpy(hb + A.o_ys, S.h_yaw_s.p, 8 * n_yaw); }
+    if (n_top) memcpy(hb + A.o_tx, S.h_top_x.p, sizeof(int) * n_top);
+    if (nb) { memcpy(hb + A.o_b0, S.h_box_job0.p, sizeof(int) * nb); memcpy(hb + A.o_bn, S.h_box_njobs.p, sizeof(int) * nb); }
     if (!d->streams->own_streams) enqueue.lock();
-    CS_HIP_TRY(hipMemcpyAsync(db, hb, in_end, hipMemcpyHostToDevice, st));
-    p_ls_order = reinterpret_cast<int*>(db + o_ls); p_jobs = reinterpret_cast<cs::JobDesc*>(db + o_jobs); p_slot_prefix = reinterpret_cast<long long*>(db + o_sp);
-    p_vp_prefix = reinterpret_cast<int*>(db + o_vp); p_yaw = reinterpret_cast<double*>(db + o_y); p_yaw_c = reinterpret_cast<double*>(db + o_yc); p_yaw_s = reinterpret_cast<double*>(db + o_ys);
-    p_top_x = reinterpret_cast<int*>(db + o_tx); p_box_job0 = reinterpret_cast<int*>(db + o_b0); p_box_njobs = reinterpret_cast<int*>(db + o_bn);
-    p_records = reinterpret_cast<cs_cuboid*>(db + S.o_rec); p_win_count = reinterpret_cast<int*>(db + S.o_wc); p_fallback = reinterpret_cast<int*>(db + S.o_fb);
-    p_job_valid = reinterpret_cast<int*>(db + S.o_jv); p_job_cbase = reinterpret_cast<long long*>(db + S.o_cb);
+    CS_HIP_TRY(hipMemcpyAsync(db, hb, A.in_end, hipMemcpyHostToDevice, st));
+    B.bind(v, *b, nj, 0, 0, db, &A);
+    p_ls_order = reinterpret_cast<int*>(db + A.o_ls); p_records = reinterpret_cast<cs_cuboid*>(db + A.o_rec);
+    rv.box_job0 = reinterpret_cast<int*>(db + A.o_b0); rv.box_njobs = reinterpret_cast<int*>(db + A.o_bn);
+    rv.win_count = reinterpret_cast<int*>(db + A.o_wc); rv.fallback = reinterpret_cast<int*>(db + A.o_fb);
   } else {
     // a batch's tables: one kernel reads all ten out of the pinned staging pools (no copy-engine ring in the sweep: see multi_copy_kernel)
     cs::CopySegs cp{};
-    cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, S.jobs, S.h_jobs_in, nj); cs::add_copy(cp, S.slot_prefix, S.h_slot_prefix, nj + 1);
-    cs::add_copy(cp, S.vp_prefix, S.h_vp_prefix, nj + 1); cs::add_copy(cp, S.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, S.yaw_c, S.h_yaw_c, n_yaw);
-    cs::add_copy(cp, S.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, S.top_x, S.h_top_x, n_top); cs::add_copy(cp, S.box_job0, S.h_box_job0, nb);
-    cs::add_copy(cp, S.box_njobs, S.h_box_njobs, nb);
+    cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, B.jobs, S.h_jobs_in, nj); cs::add_copy(cp, B.slot_prefix, S.h_slot_prefix, nj + 1);
+    cs::add_copy(cp, B.vp_prefix, S.h_vp_prefix, nj + 1); cs::add_copy(cp, B.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, B.yaw_c, S.h_yaw_c, n_yaw);
+    cs::add_copy(cp, B.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, B.top_x, S.h_top_x, n_top); cs::add_copy(cp, B.box_job0, S.h_box_job0, nb);
+    cs::add_copy(cp, B.box_njobs, S.h_box_njobs, nb);
     if (!d->streams->own_streams) enqueue.lock();
     cs::launch_multi_copy(cp, st);
+    B.bind(v, *b, nj);
   }
-  cs::DetectDeviceView& v = S.view;
-  v = cs::DetectDeviceView{};
-  v.jobs = p_jobs; v.n_jobs = (int)nj; v.slot_prefix = p_slot_prefix; v.vp_prefix = p_vp_prefix; v.maps = b->d_maps.p;
-  v.mid_x = S.mid_x.p; v.mid_y = S.mid_y.p; v.line_angle = S.ang.p; v.yaw = p_yaw; v.yaw_cos = p_yaw_c; v.yaw_sin = p_yaw_s; v.top_x = p_top_x;
-  v.rp = b->d_rp.p; v.invK = b->d_invK.p; v.vp = S.vp.p; v.bound = S.bound.p; v.bound3 = S.bound3.p; v.job_valid = p_job_valid;
-  v.job_cbase = p_job_cbase; v.c_slot = S.c_slot.p; v.c_flag = S.c_flag.p; v.c_dist = S.c_dist.p; v.c_angle = S.c_angle.p; v.c_skew = S.c_skew.p;
   // The corner construction needs the vanishing points but not the segments: it runs on the second stream (where this block has one:
   // otherwise stB == st and the cross-stream waits are not enqueued) beside line
   // setup + VP support (a latency-bound and an ALU-bound kernel), and the scorer waits for both.
@@ -1234,7 +1259,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   CS_HIP_TRY(hipEventRecord(S.ev[9], stB));
   CS_HIP_TRY(hipEventRecord(S.ev[10], stB));
   CS_HIP_TRY(hipEventRecord(S.ev[0], st));
-  cs::launch_line_setup_listed(p_jobs, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
+  cs::launch_line_setup_listed(const_cast<cs::JobDesc*>(v.jobs), (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, B.mid_x.p, B.mid_y.p, B.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, p_ls_order,
                                stC, S.ev[0], S.ev[12], S.ls_crowded.p);
   CS_HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::launch_vp_support_only(v, C.sp, S.vp_total, st, 1);      // (this path's jobs have one roll/pitch sample: jd.RP = 1 above)
@@ -1243,19 +1268,17 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   CS_HIP_TRY(hipEventRecord(S.ev[4], st));
   cs::launch_score(v, C.sp, slot_total, slot_total, st);
   CS_HIP_TRY(hipEventRecord(S.ev[5], st));
-  cs::RankView rv{};
-  rv.box_job0 = p_box_job0; rv.box_njobs = p_box_njobs; rv.n_boxes = (int)nb; rv.winners = S.winners.p; rv.win_count = p_win_count; rv.fallback = p_fallback;
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
   cs::launch_rank(v, rv, rkp, st, 0, false);          // (the host reads no winner of the device: record_kernel rebuilds their corners)
   cs::launch_records(v, rv, KMAX, p_records, st, nullptr, rkp.short_sq_bound);     // the records of the boxes the device ranked: only they come back
   CS_HIP_TRY(hipEventRecord(S.ev[6], st));
   CS_HIP_TRY(hipGetLastError());
   if (S.merged_io) {
-    CS_HIP_TRY(hipMemcpyAsync(S.h_tab_arena.p + S.o_jobs, S.tab_arena.p + S.o_jobs, S.o_end - S.o_jobs, hipMemcpyDeviceToHost, st));   // unpacked in pipe_finish
+    CS_HIP_TRY(hipMemcpyAsync(S.h_tab_arena.p + S.arena.o_jobs, S.tab_arena.p + S.arena.o_jobs, S.arena.o_end - S.arena.o_jobs, hipMemcpyDeviceToHost, st));   // unpacked in pipe_finish
   } else {   // the results: written to the pinned host pools by one kernel
     cs::CopySegs cp{};
-    cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, S.h_win_count, S.win_count, nb); cs::add_copy(cp, S.h_fallback, S.fallback, nb);
-    cs::add_copy(cp, S.h_job_valid, S.job_valid, nj); cs::add_copy(cp, S.h_job_cbase, S.job_cbase, nj + 1);      // (the job table itself is not read back: pipe_finish works from the host's own copy)
+    cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, B.h_win_count, B.win_count, nb); cs::add_copy(cp, B.h_fallback, B.fallback, nb);
+    cs::add_copy(cp, B.h_job_valid, B.job_valid, nj); cs::add_copy(cp, B.h_job_cbase, B.job_cbase, nj + 1);      // (the job table itself is not read back: pipe_finish works from the host's own copy)
     cs::launch_multi_copy(cp, st);
   }
   CS_HIP_TRY(hipEventRecord(S.done, st));
@@ -1277,11 +1300,13 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   S.in_flight = false;
   const size_t nj = S.nj, nb = S.nb;
   if (nj == 0) return CS_OK;
+  SweepBuffers& B = S.sb;
   if (S.merged_io) {     // a small call's results came back in one block (pipe_launch): to the places the rest of this function reads
     const unsigned char* hb = S.h_tab_arena.p;
-    memcpy(S.h_jobs_out.p, hb + S.o_jobs, sizeof(cs::JobDesc) * nj);
-    if (nb) { memcpy(S.h_records.p, hb + S.o_rec, sizeof(cs_cuboid) * nb * KMAX); memcpy(S.h_win_count.p, hb + S.o_wc, sizeof(int) * nb); memcpy(S.h_fallback.p, hb + S.o_fb, sizeof(int) * nb); }
-    memcpy(S.h_job_valid.p, hb + S.o_jv, sizeof(int) * nj); memcpy(S.h_job_cbase.p, hb + S.o_cb, sizeof(long long) * (nj + 1));
+    const SmallCallArena& A = S.arena;
+    memcpy(S.h_jobs_out.p, hb + A.o_jobs, sizeof(cs::JobDesc) * nj);
+    if (nb) { memcpy(S.h_records.p, hb + A.o_rec, sizeof(cs_cuboid) * nb * KMAX); memcpy(B.h_win_count.p, hb + A.o_wc, sizeof(int) * nb); memcpy(B.h_fallback.p, hb + A.o_fb, sizeof(int) * nb); }
+    memcpy(B.h_job_valid.p, hb + A.o_jv, sizeof(int) * nj); memcpy(B.h_job_cbase.p, hb + A.o_cb, sizeof(long long) * (nj + 1));
   }
   double t0 = now_ms();
   {
@@ -1294,7 +1319,7 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[5], S.ev[6])); tm.rank_kernel_ms += ms;
     tm.cand_kernel_launches += 1;
     long long n_valid = 0;      // (the capacity layout has no running total: job_cbase[j] = slot_prefix[j])
-    for (size_t j = 0; j < nj; j++) n_valid += S.h_job_valid.p[j];
+    for (size_t j = 0; j < nj; j++) n_valid += B.h_job_valid.p[j];
     tm.n_valid += n_valid;
     // algorithmic bytes of the corner construction: the vanishing points it writes (48 B each) + 12 bytes (slot id, flag) per VALID proposal
     tm.cand_kernel_bytes += 48LL * S.vp_total + 12LL * n_valid;
@@ -1303,100 +1328,60 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
     tm.score_kernel_bytes += sbytes;
   }
   const cs::JobDesc* jobs = S.h_jobs_in.p;
-  hipStream_t st2 = d->stream_hi;
   MARK(4, tq);   // wait for the GPU + timing bookkeeping
   // ---- boxes the kernel flagged (a tie at a cut or at the top): exact std::partial_sort ranking on the host.  Their
   // columns are fetched on the high-priority stream: the host waits for them while other sweeps (the next chunk's, or another
   // batch's of the same process) fill the device, and these few small kernels should not queue behind those.
-  std::vector<long long> fb_src, fb_dst;
-  std::vector<int> fb_cnt, fb_range_of_job(nj, -1);
-  long long tot = 0;
-  for (size_t q = 0; q < nb; q++)
-    if (S.h_fallback.p[q])
-      for (int h = 0; h < S.h_box_njobs.p[q]; h++) {
-        int j = S.h_box_job0.p[q] + h;
-        fb_range_of_job[j] = (int)fb_src.size();
-        fb_src.push_back(S.h_job_cbase.p[j]); fb_cnt.push_back(S.h_job_valid.p[j]); fb_dst.push_back(tot);
-        tot += S.h_job_valid.p[j];
-      }
-  if (!fb_src.empty()) {
-    size_t nr = fb_src.size();
-    CS_ENSURE(S.h_fb_src, nr); CS_ENSURE(S.h_fb_dst, nr); CS_ENSURE(S.h_fb_cnt, nr);
-    CS_ENSURE(S.h_fb_dist, tot + 1); CS_ENSURE(S.h_fb_angle, tot + 1); CS_ENSURE(S.h_fb_skew, tot + 1); CS_ENSURE(S.h_fb_flag, tot + 1); CS_ENSURE(S.h_fb_slot, tot + 1);
-    std::copy(fb_src.begin(), fb_src.end(), S.h_fb_src.p); std::copy(fb_dst.begin(), fb_dst.end(), S.h_fb_dst.p); std::copy(fb_cnt.begin(), fb_cnt.end(), S.h_fb_cnt.p);
-    // the range lists are read from, and the columns written to, the pinned host pools by the gather kernel itself (coalesced rows; no
-    // copy engine between the device and a host that is waiting for a few kilobytes)
-    cs::launch_gather_ranges(S.view, S.h_fb_src.p, S.h_fb_cnt.p, S.h_fb_dst.p, (int)nr, S.h_fb_dist.p, S.h_fb_angle.p, S.h_fb_skew.p, S.h_fb_flag.p, S.h_fb_slot.p, st2);
-    CS_HIP_TRY(hipGetLastError());
-  }
+  TiePass tie(B, S.view, d->stream_hi, S.h_box_job0.p, S.h_box_njobs.p, nj, nb);
+  int rc;
+  if ((rc = tie.enqueue_columns())) return rc;
   MARK(5, tq);   // tie lists + gather enqueue
   // ---- records of the winners.  The boxes the device ranked are written while the tie boxes' columns travel.
-  std::vector<std::vector<ExactWinner>> fb_winners(nb);
-  std::vector<size_t> fb_corner0(nb, 0);      // first of a tie box's winners in h_win_corners
+  const std::vector<int>& fbq = tie.boxes;
   auto write_box = [&](size_t q) {
     const int j0 = S.h_box_job0.p[q];
-    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = (int)fb_winners[q].size();
+    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = (int)tie.winners[q].size();
     for (int r = 0; r < nw; r++) {
-      const ExactWinner& w = fb_winners[q][r];
+      const ExactWinner& w = tie.winners[q][r];
       const cs::JobDesc& jd = jobs[j0 + w.h];
       const SlotRef s = decode_slot(jd, w.slot);
-      write_winner_record(b->frames[f], jd, s, w.flag, w.dist, w.angle, S.h_yaw.p[jd.yaw_off + s.y], cam_rp[f][s.rp].pose, S.h_win_corners.p + 16 * (fb_corner0[q] + r),
+      write_winner_record(b->frames[f], jd, s, w.flag, w.dist, w.angle, S.h_yaw.p[jd.yaw_off + s.y], cam_rp[f][s.rp].pose, tie.corners(q, r),
                           (*C.cam_raw)[f].euler, false, w.score, C.out[((size_t)f * MB + bi) * KMAX + r]);
     }
     C.out_counts[(size_t)f * MB + bi] = nw;
   };
   const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
-  auto rank_on_host = [&](size_t q) {
-    const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q];
-    HeightCols cols[3];
-    for (int h = 0; h < nh; h++) {
-      const long long p0 = fb_dst[fb_range_of_job[j0 + h]];
-      cols[h] = HeightCols{S.h_fb_dist.p + p0, S.h_fb_angle.p + p0, S.h_fb_skew.p + p0, S.h_fb_flag.p + p0, S.h_fb_slot.p + p0, S.h_job_valid.p[j0 + h]};
-    }
-    (void)exact_rank_box(cols, nh, RW, KMAX, fb_winners[q]);
-  };
-  std::vector<int> fbq;
-  for (size_t q = 0; q < nb; q++) if (S.h_fallback.p[q]) fbq.push_back((int)q);
   tm.n_fallback_boxes += (int)fbq.size();
   auto records = [&](int qi) {      // a device-ranked box: its records are complete but for the caller's rectangle
     const size_t q = (size_t)qi;
-    if (S.h_fallback.p[q]) return;
+    if (B.h_fallback.p[q]) return;
     const int j0 = S.h_box_job0.p[q];
-    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = S.h_win_count.p[q];
+    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = B.h_win_count.p[q];
     for (int r = 0; r < nw; r++) copy_device_record(b->frames[f], bi, S.h_records.p[q * KMAX + r], C.out[((size_t)f * MB + bi) * KMAX + r]);
     C.out_counts[(size_t)f * MB + bi] = nw;
   };
   if (fbq.size() <= 64) {
     // a handful of tie boxes (the usual case): their columns are a few kilobytes and already here; their exact ranking
     // (tens of microseconds each) rides in the same parallel pass as the records of the other boxes, first in the queue
-    if (!fb_src.empty()) CS_HIP_TRY(hipStreamSynchronize(st2));
+    if ((rc = tie.wait())) return rc;
     MARK(7, tq);   // wait for the tie columns
     const int nfb = (int)fbq.size();
     constexpr int RCH = 256;           // records are a 400-byte copy each: hand them out in chunks
     const int nch = ((int)nb + RCH - 1) / RCH;
     d->pool->run(nfb + nch, [&](int z) {
-      if (z < nfb) { rank_on_host((size_t)fbq[z]); return; }
+      if (z < nfb) { (void)tie.rank((size_t)fbq[z], RW, KMAX); return; }
       for (int q = (z - nfb) * RCH, q1 = std::min((int)nb, q + RCH); q < q1; q++) records(q);
     });
     MARK(6, tq);   // records of the device-ranked boxes (+ exact ranking of the tie boxes)
   } else {
     d->pool->run((int)nb, records);
     MARK(6, tq);   // records of the device-ranked boxes, written while the tie boxes' columns travel
-    if (!fb_src.empty()) CS_HIP_TRY(hipStreamSynchronize(st2));
+    if ((rc = tie.wait())) return rc;
     MARK(7, tq);   // wait for the tie columns
-    d->pool->run((int)fbq.size(), [&](int z) { rank_on_host((size_t)fbq[z]); });
+    d->pool->run((int)fbq.size(), [&](int z) { (void)tie.rank((size_t)fbq[z], RW, KMAX); });
   }
   MARK(8, tq);   // exact ranking of the tie boxes
-  {
-    size_t nw = 0;
-    for (int q : fbq) { fb_corner0[q] = nw; nw += fb_winners[q].size(); }
-    if (nw) {
-      CS_ENSURE(S.h_win_slots, nw); CS_ENSURE(S.h_win_corners, 16 * nw);
-      for (int q : fbq) for (size_t r = 0; r < fb_winners[q].size(); r++) S.h_win_slots.p[fb_corner0[q] + r] = fb_winners[q][r].slot;
-      cs::launch_gather_corners(S.view, C.sp, S.h_win_slots.p, (int)nw, S.h_win_corners.p, st2);     // (pinned host memory on both sides)
-      CS_HIP_TRY(hipStreamSynchronize(st2));
-    }
-  }
+  if ((rc = tie.enqueue_corners(C.sp)) || (rc = tie.wait())) return rc;
   MARK(9, tq);   // corners of the tie winners
   if (fbq.size() <= 24) { for (int q : fbq) write_box((size_t)q); }
   else d->pool->run((int)fbq.size(), [&](int z) { write_box((size_t)fbq[z]); });
@@ -1427,7 +1412,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   int max_rp = 1;
   for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)cam_rp[f].size());
   const int NT = 1 + max_rp;
-  const int YCAP = (int)(2.0 * P.yaw_range_deg / std::max(1e-9, P.yaw_step_deg)) + 3;
+  const int YCAP = yaw_list_capacity(P.yaw_range_deg, P.yaw_step_deg);
   const size_t n_yaw = (size_t)NF * NT * YCAP;
   if (n_yaw > 0x7fffffffULL) { cs_set_error("too many yaw samples"); return CS_ERR_CAPACITY; }
   CS_ENSURE(S.h_yaw, n_yaw + 1); CS_ENSURE(S.h_yaw_c, n_yaw + 1); CS_ENSURE(S.h_yaw_s, n_yaw + 1); CS_ENSURE(S.h_rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.h_rp_raw_euler, 3 * (size_t)NF + 1);
@@ -1440,13 +1425,10 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     *cnt = 0;
     if (i > nrp) return;
     const double cam_yaw = i == 0 ? (*C.cam_raw)[f].cam_yaw : cam_rp[f][i - 1].cam_yaw;
-    const double yaw_init = cam_yaw - 90.0 / 180.0 * CS_PI;
-    std::vector<double> yl;
-    linespace<double>(yaw_init - P.yaw_range_deg / 180.0 * CS_PI, yaw_init + P.yaw_range_deg / 180.0 * CS_PI, P.yaw_step_deg / 180.0 * CS_PI, yl);
-    if ((int)yl.size() > YCAP) { overflow = 1; return; }
-    double* yw = S.h_yaw.p + ((size_t)f * NT + i) * YCAP; double* yc = S.h_yaw_c.p + ((size_t)f * NT + i) * YCAP; double* ys = S.h_yaw_s.p + ((size_t)f * NT + i) * YCAP;
-    for (size_t y = 0; y < yl.size(); y++) { yw[y] = yl[y]; yc[y] = h_cos(yl[y]); ys[y] = h_sin(yl[y]); }
-    *cnt = (int)yl.size();
+    const size_t at = ((size_t)f * NT + i) * YCAP;
+    const int n = fill_yaw_list(cam_yaw, P.yaw_range_deg, P.yaw_step_deg, YCAP, S.h_yaw.p + at, S.h_yaw_c.p + at, S.h_yaw_s.p + at);
+    if (n < 0) { overflow = 1; return; }
+    *cnt = n;
   });
   if (overflow) { cs_set_error("yaw sample list exceeds its capacity"); return CS_ERR_CAPACITY; }
   for (int f = 0; f < NF; f++) {
@@ -1454,7 +1436,6 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     for (int e = 0; e < 3; e++) S.h_rp_raw_euler.p[3 * f + e] = (*C.cam_raw)[f].euler[e];
   }
   // ---- jobs of all rounds: (round, frame, height sample); per round its own slot / vanishing-point numbering
-  const int tp0 = 0;
   size_t nj_tot = 0, nb_tot = 0;
   for (int f = 0; f < NF; f++) for (int bi = 0; bi < b->frames[f].n_boxes; bi++) nj_tot += b->frames[f].n_heights[bi];
   const size_t n_top = (size_t)b->top_base[b->box_base[NF]];
@@ -1469,7 +1450,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   for (int r = 0; r < MB; r++) {
     PipeSlot::RpRound& Rr = S.rp_rounds[r];
     Rr.j0 = ji; Rr.b0 = nb_tot;
-    long long so = 0, vo = 0;
+    JobSpan at{0, 0};
     int* box_of = S.h_rp_maps.p + (size_t)(3 * r) * NF; int* job0_of = box_of + NF; int* njobs_of = job0_of + NF;
     for (int f = 0; f < NF; f++) {
       box_of[f] = -1; job0_of[f] = -1; njobs_of[f] = 0;
@@ -1477,18 +1458,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       if (r >= F.n_boxes) continue;
       const int bi = r;
       const double* bb = &F.boxes[5 * bi];
-      const int left = bb[0], w = bb[2], right = left + bb[2];
-      const int res = (int)std::round(std::min(20, w / 10));
-      if (res < 1) continue;              // :215: the box is skipped and leaves the carried yaw alone
-      const int tb = b->top_base[b->box_base[f] + bi] - tp0, tcap = b->top_base[b->box_base[f] + bi + 1] - tp0 - tb;
-      int nT = 0;
-      int* tx = S.h_top_x.p + tb;
-      for (int x = left + 5; x <= right - 5 && nT < tcap; x += res) tx[nT++] = x;
+      if (top_sample_step(bb) < 1) continue;              // :215: the box is skipped and leaves the carried yaw alone
+      const int tb = b->top_base[b->box_base[f] + bi];
+      const int nT = top_samples(bb, S.h_top_x.p + tb);     // (as many as batch_layout reserved: top_base counts them by the same rule)
       const int nrp = (int)cam_rp[f].size();
       box_of[f] = (int)(nb_tot - Rr.b0); job0_of[f] = (int)(ji - Rr.j0); njobs_of[f] = F.n_heights[bi];
-      S.h_box_job0.p[nb_tot] = (int)(ji - Rr.j0); S.h_box_njobs.p[nb_tot] = F.n_heights[bi];
+      S.h_box_job0.p[nb_tot] = (int)(ji - Rr.j0); S.h_box_njobs.p[nb_tot++] = F.n_heights[bi];
       S.rp_box_frame.push_back(f); S.rp_box_index.push_back(bi);
-      nb_tot++;
       for (int k = 0; k < F.n_heights[bi]; k++) {
         cs::JobDesc jd;
         fill_job_geometry(jd, F, bi, k, (*C.rp_off)[f]);
@@ -1497,14 +1473,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
         jd.yaw_off = (int)(((size_t)f * NT) * YCAP);
         jd.top_off = tb;
         jd.line_off = (int)n_lines; n_lines += F.n_lines;
-        jd.slot_off = so; jd.vp_off = (int)vo;
-        S.h_slot_prefix.p[ji + r] = so; S.h_vp_prefix.p[ji + r] = (int)vo;
-        so += (long long)nrp * ycap_f[f] * nT * 2;
-        max_job_slots = std::max(max_job_slots, (long long)nrp * ycap_f[f] * nT * 2);
-        vo += ((long long)nrp * ycap_f[f] + 63) & ~63LL;
+        const JobSpan own = span_longest_list(jd, ycap_f[f]);
+        jd.slot_off = S.h_slot_prefix.p[ji + r] = at.slots; jd.vp_off = S.h_vp_prefix.p[ji + r] = (int)at.vps;
+        max_job_slots = std::max(max_job_slots, own.slots); at.slots += own.slots; at.vps += own.vps;
         S.h_jobs_in.p[ji++] = jd;
       }
     }
+    const long long so = at.slots, vo = at.vps;
     Rr.nj = ji - Rr.j0; Rr.nb = nb_tot - Rr.b0; Rr.slot_cap = so; Rr.vp_cap = (int)vo;
     S.h_slot_prefix.p[ji + r] = so; S.h_vp_prefix.p[ji + r] = (int)vo;
     if (vo > 0x7fffffffLL || so > 0x7fffffff00LL) { cs_set_error("too many samples in one round"); return CS_ERR_CAPACITY; }
@@ -1519,20 +1494,18 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   C.tm->n_jobs += (long long)nj;
   if (nj == 0) { S.in_flight = true; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
   // ---- device buffers; the per-round arrays are sized for the largest round and reused from round to round (one stream: in order)
-  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.jobs, nj); CS_ENSURE(S.slot_prefix, nj + MB + 1); CS_ENSURE(S.vp_prefix, nj + MB + 1); CS_ENSURE(S.job_valid, nj); CS_ENSURE(S.job_cbase, nj + MB + 1);
+  SweepBuffers& B = S.sb;
+  int rc;
+  if ((rc = B.ensure_tables(nj, nj + MB + 1, (size_t)n_lines, n_yaw, n_top, (size_t)vp_cap_max, nb, KMAX)) || (rc = B.ensure_slots(slot_cap_max))) return rc;
+  CS_ENSURE(B.flag, slot_cap_max + 1); CS_ENSURE(B.bound3, nj_round_max * (size_t)cs::vp3_table_doubles_per_job() + 1);
   const int max_trips = (int)std::min<long long>((max_job_slots + 4095) / 4096, 1 << 20);      // compaction trips of the largest job (4096 slots each)
   CS_ENSURE(S.rp_trip_cnt, (size_t)nj_round_max * (size_t)std::max(1, max_trips) + 1);
-  CS_ENSURE(S.mid_x, (size_t)n_lines + 1); CS_ENSURE(S.mid_y, (size_t)n_lines + 1); CS_ENSURE(S.ang, (size_t)n_lines + 1); CS_ENSURE(S.yaw, n_yaw + 1); CS_ENSURE(S.yaw_c, n_yaw + 1); CS_ENSURE(S.yaw_s, n_yaw + 1);
-  CS_ENSURE(S.top_x, n_top + 1); CS_ENSURE(S.vp, 6 * (size_t)vp_cap_max + 6); CS_ENSURE(S.bound, 6 * (size_t)vp_cap_max + 6); CS_ENSURE(S.bound3, nj_round_max * (size_t)cs::vp3_table_doubles_per_job() + 1);
-  CS_ENSURE(S.flag, slot_cap_max + 1); CS_ENSURE(S.c_slot, slot_cap_max + 1); CS_ENSURE(S.c_flag, slot_cap_max + 1); CS_ENSURE(S.c_dist, slot_cap_max + 1); CS_ENSURE(S.c_angle, slot_cap_max + 1); CS_ENSURE(S.c_skew, slot_cap_max + 1);
-  CS_ENSURE(S.box_job0, nb + 1); CS_ENSURE(S.box_njobs, nb + 1); CS_ENSURE(S.win_count, nb + 1); CS_ENSURE(S.fallback, nb + 1); CS_ENSURE(S.rp_last_slot, nb + 1);
-  CS_ENSURE(S.winners, nb * KMAX + 1); CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1); CS_ENSURE(S.h_win_count, nb + 1); CS_ENSURE(S.h_fallback, nb + 1);
-  CS_ENSURE(S.h_job_cbase, nj + MB + 1);
+  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2); CS_ENSURE(S.rp_last_slot, nb + 1);
+  CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1);
   S.rp_NT = NT; S.rp_YCAP = YCAP;
   S.rp_pool_cap = std::max<long long>(1 << 18, slots_all / 64);        // columns of the flagged boxes (about one box in a hundred)
-  CS_ENSURE(S.fb_dist, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_angle, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_skew, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_flag, (size_t)S.rp_pool_cap + 1); CS_ENSURE(S.fb_slot, (size_t)S.rp_pool_cap + 1);
-  CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2);
-  CS_ENSURE(S.rp_box_base, nb + 1); CS_ENSURE(S.rp_pool_used, 1); CS_ENSURE(S.h_rp_box_base, nb + 1); CS_ENSURE(S.h_rp_pool_used, 1); CS_ENSURE(S.h_rp_last_slot, nb + 1); CS_ENSURE(S.h_job_valid, nj + 1); CS_ENSURE(S.h_jobs_out, nj + 1);
+  CS_ENSURE(B.fb_dist, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_angle, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_skew, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_flag, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_slot, (size_t)S.rp_pool_cap + 1);
+  CS_ENSURE(S.rp_box_base, nb + 1); CS_ENSURE(S.rp_pool_used, 1); CS_ENSURE(S.h_rp_box_base, nb + 1); CS_ENSURE(S.h_rp_pool_used, 1); CS_ENSURE(S.h_rp_last_slot, nb + 1); CS_ENSURE(S.h_jobs_out, nj + 1);
   CS_ENSURE(S.rp_cur_idx, (size_t)NF + 1); CS_ENSURE(S.rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.rp_maps, 3 * (size_t)MB * NF + 1); CS_ENSURE(S.rp_raw_euler, 3 * (size_t)NF + 1);
   while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; CS_HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
   std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);      // all rounds of this batch back to back in the shared streams (see pipe_launch)
@@ -1542,18 +1515,18 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   CS_HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
   {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
     cs::CopySegs cp{};
-    cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, S.jobs, S.h_jobs_in, nj); cs::add_copy(cp, S.slot_prefix, S.h_slot_prefix, nj + MB);
-    cs::add_copy(cp, S.vp_prefix, S.h_vp_prefix, nj + MB); cs::add_copy(cp, S.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, S.yaw_c, S.h_yaw_c, n_yaw);
-    cs::add_copy(cp, S.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, S.top_x, S.h_top_x, n_top); cs::add_copy(cp, S.box_job0, S.h_box_job0, nb);
-    cs::add_copy(cp, S.box_njobs, S.h_box_njobs, nb); cs::add_copy(cp, S.rp_tab_count, S.h_rp_tab_count, (long long)NF * NT);
+    cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, B.jobs, S.h_jobs_in, nj); cs::add_copy(cp, B.slot_prefix, S.h_slot_prefix, nj + MB);
+    cs::add_copy(cp, B.vp_prefix, S.h_vp_prefix, nj + MB); cs::add_copy(cp, B.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, B.yaw_c, S.h_yaw_c, n_yaw);
+    cs::add_copy(cp, B.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, B.top_x, S.h_top_x, n_top); cs::add_copy(cp, B.box_job0, S.h_box_job0, nb);
+    cs::add_copy(cp, B.box_njobs, S.h_box_njobs, nb); cs::add_copy(cp, S.rp_tab_count, S.h_rp_tab_count, (long long)NF * NT);
     cs::add_copy(cp, S.rp_maps, S.h_rp_maps, 3LL * MB * NF); cs::add_copy(cp, S.rp_raw_euler, S.h_rp_raw_euler, 3LL * NF);
     cs::launch_multi_copy(cp, st);
   }
-  CS_HIP_TRY(hipMemsetAsync(S.job_valid.p, 0, sizeof(int) * nj, st));
+  CS_HIP_TRY(hipMemsetAsync(B.job_valid.p, 0, sizeof(int) * nj, st));
   CS_HIP_TRY(hipMemsetAsync(S.rp_cur_idx.p, 0, sizeof(int) * NF, st));
   CS_HIP_TRY(hipEventRecord(S.ev[0], st));
   // ---- line setup of every job of the batch at once (it depends on the box and the frame's segments only)
-  cs::launch_line_setup_listed(S.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, S.mid_x.p, S.mid_y.p, S.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
+  cs::launch_line_setup_listed(B.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, B.mid_x.p, B.mid_y.p, B.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
                                stC, S.ev[0], S.ev[12], S.ls_crowded.p);
   CS_HIP_TRY(hipEventRecord(S.ev[1], st));
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
@@ -1561,11 +1534,8 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     const PipeSlot::RpRound& Rr = S.rp_rounds[r];
     if (Rr.nj == 0) continue;
     hipEvent_t* re = &S.rp_ev[5 * (size_t)r];
-    cs::DetectDeviceView v{};
-    v.jobs = S.jobs.p + Rr.j0; v.n_jobs = (int)Rr.nj; v.slot_prefix = S.slot_prefix.p + Rr.j0 + r; v.vp_prefix = S.vp_prefix.p + Rr.j0 + r; v.maps = b->d_maps.p;
-    v.mid_x = S.mid_x.p; v.mid_y = S.mid_y.p; v.line_angle = S.ang.p; v.yaw = S.yaw.p; v.yaw_cos = S.yaw_c.p; v.yaw_sin = S.yaw_s.p; v.top_x = S.top_x.p;
-    v.rp = b->d_rp.p; v.invK = b->d_invK.p; v.vp = S.vp.p; v.bound = S.bound.p; v.bound3 = S.bound3.p; v.flag = S.flag.p; v.job_valid = S.job_valid.p + Rr.j0;
-    v.job_cbase = S.job_cbase.p + Rr.j0 + r; v.c_slot = S.c_slot.p; v.c_flag = S.c_flag.p; v.c_dist = S.c_dist.p; v.c_angle = S.c_angle.p; v.c_skew = S.c_skew.p;
+    cs::DetectDeviceView v;
+    B.bind(v, *b, Rr.nj, Rr.j0, Rr.j0 + r);      // (the prefixes carry one closing entry per earlier round)
     if (r > 0) {      // the carried yaw: this round's jobs get the list the previous round's result selects
       // (the previous round WITH jobs decides for the frames it held a box of; a frame without a box there keeps its list)
       int rq = r - 1;
@@ -1574,10 +1544,10 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       cs::RpCarryView c{};
       c.n_frames = NF; c.NT = NT; c.YCAP = YCAP;
       c.prev_box_of_frame = Rq.nj ? S.rp_maps.p + (size_t)(3 * rq) * NF : nullptr;
-      c.prev_last_slot = S.rp_last_slot.p + Rq.b0; c.prev_jobs = S.jobs.p + Rq.j0; c.prev_box_job0 = S.box_job0.p + Rq.b0; c.prev_box_njobs = S.box_njobs.p + Rq.b0;
+      c.prev_last_slot = S.rp_last_slot.p + Rq.b0; c.prev_jobs = B.jobs.p + Rq.j0; c.prev_box_job0 = B.box_job0.p + Rq.b0; c.prev_box_njobs = B.box_njobs.p + Rq.b0;
       c.job0_of_frame = S.rp_maps.p + (size_t)(3 * r + 1) * NF; c.njobs_of_frame = S.rp_maps.p + (size_t)(3 * r + 2) * NF;
       c.tab_count = S.rp_tab_count.p; c.cur_idx = S.rp_cur_idx.p;
-      cs::launch_rp_carry(c, S.jobs.p + Rr.j0, st);
+      cs::launch_rp_carry(c, B.jobs.p + Rr.j0, st);
     }
     CS_HIP_TRY(hipEventRecord(re[0], st));
     cs::launch_vp_points(v, Rr.vp_cap, st);
@@ -1589,14 +1559,14 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     cs::launch_score(v, C.sp, Rr.slot_cap, Rr.slot_cap, st);
     CS_HIP_TRY(hipEventRecord(re[3], st));
     cs::RankView rv{};
-    rv.box_job0 = S.box_job0.p + Rr.b0; rv.box_njobs = S.box_njobs.p + Rr.b0; rv.n_boxes = (int)Rr.nb; rv.winners = S.winners.p + Rr.b0 * KMAX;
-    rv.win_count = S.win_count.p + Rr.b0; rv.fallback = S.fallback.p + Rr.b0; rv.last_slot = S.rp_last_slot.p + Rr.b0;
+    rv.box_job0 = B.box_job0.p + Rr.b0; rv.box_njobs = B.box_njobs.p + Rr.b0; rv.n_boxes = (int)Rr.nb; rv.winners = B.winners.p + Rr.b0 * KMAX;
+    rv.win_count = B.win_count.p + Rr.b0; rv.fallback = B.fallback.p + Rr.b0; rv.last_slot = S.rp_last_slot.p + Rr.b0;
     cs::launch_rank(v, rv, rkp, st, Rr.nb ? (long long)(Rr.slot_cap / (long long)Rr.nb) : 0, false);      // (average slots per box of the round: which instance ranks)
     cs::launch_records(v, rv, KMAX, S.records.p + Rr.b0 * KMAX, st, S.rp_raw_euler.p, rkp.short_sq_bound);
     {   // the flagged boxes' columns, before the next round reuses the arrays
       cs::RpSaveView sv{};
       sv.fallback = rv.fallback; sv.box_job0 = rv.box_job0; sv.box_njobs = rv.box_njobs; sv.n_boxes = rv.n_boxes; sv.pool_used = S.rp_pool_used.p; sv.pool_cap = S.rp_pool_cap;
-      sv.box_base = S.rp_box_base.p + Rr.b0; sv.p_dist = S.fb_dist.p; sv.p_angle = S.fb_angle.p; sv.p_skew = S.fb_skew.p; sv.p_flag = S.fb_flag.p; sv.p_slot = S.fb_slot.p;
+      sv.box_base = S.rp_box_base.p + Rr.b0; sv.p_dist = B.fb_dist.p; sv.p_angle = B.fb_angle.p; sv.p_skew = B.fb_skew.p; sv.p_flag = B.fb_flag.p; sv.p_slot = B.fb_slot.p;
       cs::launch_rp_save_fallback(v, sv, st);
     }
     CS_HIP_TRY(hipEventRecord(re[4], st));
@@ -1605,8 +1575,8 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   CS_HIP_TRY(hipEventRecord(S.ev[6], st));
   {
     cs::CopySegs cp{};
-    cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, S.h_win_count, S.win_count, nb); cs::add_copy(cp, S.h_fallback, S.fallback, nb);
-    cs::add_copy(cp, S.h_job_cbase, S.job_cbase, nj + MB); cs::add_copy(cp, S.h_job_valid, S.job_valid, nj); cs::add_copy(cp, S.h_jobs_out, S.jobs, nj);
+    cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, B.h_win_count, B.win_count, nb); cs::add_copy(cp, B.h_fallback, B.fallback, nb);
+    cs::add_copy(cp, B.h_job_cbase, B.job_cbase, nj + MB); cs::add_copy(cp, B.h_job_valid, B.job_valid, nj); cs::add_copy(cp, S.h_jobs_out, B.jobs, nj);
     cs::add_copy(cp, S.h_rp_last_slot, S.rp_last_slot, nb); cs::add_copy(cp, S.h_rp_box_base, S.rp_box_base, nb); cs::add_copy(cp, S.h_rp_pool_used, S.rp_pool_used, 1);
     cs::launch_multi_copy(cp, st);
   }
@@ -1641,7 +1611,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
       tm.cand_kernel_launches += 1;
     }
     tm.n_slots += S.slot_total;
-    for (int r = 0; r < MB; r++) if (S.rp_rounds[r].nj) tm.n_valid += S.h_job_cbase.p[S.rp_rounds[r].j0 + r + S.rp_rounds[r].nj];
+    for (int r = 0; r < MB; r++) if (S.rp_rounds[r].nj) tm.n_valid += S.sb.h_job_cbase.p[S.rp_rounds[r].j0 + r + S.rp_rounds[r].nj];
   }
   // ---- the flagged boxes: exact ranking on the host from their saved columns.  A frame is only redone when the exact ranking
   // carries a different camera yaw to the frame's next box than the device assumed (or the columns did not fit the pool).
@@ -1649,16 +1619,16 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   std::vector<char> host_done(S.nb, 0);     // box written from the host ranking
   int n_redo = 0;
   size_t n_fb = 0;
-  for (size_t q = 0; q < S.nb; q++) n_fb += S.h_fallback.p[q] ? 1 : 0;
+  for (size_t q = 0; q < S.nb; q++) n_fb += S.sb.h_fallback.p[q] ? 1 : 0;
   tm.n_fallback_boxes += (int)n_fb;
   if (n_fb) {
     hipStream_t st2 = d->stream_hi;
     const size_t used = (size_t)std::min<unsigned long long>(*S.h_rp_pool_used.p, (unsigned long long)S.rp_pool_cap);
-    CS_ENSURE(S.h_fb_dist, used + 1); CS_ENSURE(S.h_fb_angle, used + 1); CS_ENSURE(S.h_fb_skew, used + 1); CS_ENSURE(S.h_fb_flag, used + 1); CS_ENSURE(S.h_fb_slot, used + 1);
+    CS_ENSURE(S.sb.h_fb_dist, used + 1); CS_ENSURE(S.sb.h_fb_angle, used + 1); CS_ENSURE(S.sb.h_fb_skew, used + 1); CS_ENSURE(S.sb.h_fb_flag, used + 1); CS_ENSURE(S.sb.h_fb_slot, used + 1);
     if (used) {
       cs::CopySegs cp{};
-      cs::add_copy(cp, S.h_fb_dist, S.fb_dist, used); cs::add_copy(cp, S.h_fb_angle, S.fb_angle, used); cs::add_copy(cp, S.h_fb_skew, S.fb_skew, used);
-      cs::add_copy(cp, S.h_fb_flag, S.fb_flag, used); cs::add_copy(cp, S.h_fb_slot, S.fb_slot, used);
+      cs::add_copy(cp, S.sb.h_fb_dist, S.sb.fb_dist, used); cs::add_copy(cp, S.sb.h_fb_angle, S.sb.fb_angle, used); cs::add_copy(cp, S.sb.h_fb_skew, S.sb.fb_skew, used);
+      cs::add_copy(cp, S.sb.h_fb_flag, S.sb.fb_flag, used); cs::add_copy(cp, S.sb.h_fb_slot, S.sb.fb_slot, used);
       cs::launch_multi_copy(cp, st2);
       CS_HIP_TRY(hipStreamSynchronize(st2));
     }
@@ -1669,25 +1639,25 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
     auto carry_idx = [](const cs::JobDesc& jl, long long last) { return last < 0 ? jl.RP : 1 + decode_slot(jl, last).rp; };
     const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
     std::vector<int> fb_frames;
-    for (int f = 0; f < NF; f++) { bool any = false; for (size_t q : boxes_of[f]) any = any || S.h_fallback.p[q]; if (any) fb_frames.push_back(f); }
+    for (int f = 0; f < NF; f++) { bool any = false; for (size_t q : boxes_of[f]) any = any || S.sb.h_fallback.p[q]; if (any) fb_frames.push_back(f); }
     d->pool->run((int)fb_frames.size(), [&](int z) {
       const int f = fb_frames[z];
       const FrameIn& F = b->frames[f];
       for (size_t bq = 0; bq < boxes_of[f].size(); bq++) {
         const size_t q = boxes_of[f][bq];
-        if (!S.h_fallback.p[q]) continue;
+        if (!S.sb.h_fallback.p[q]) continue;
         const long long base = S.h_rp_box_base.p[q];
         if (base < 0) { redo[f] = 1; return; }
         // which round the box belongs to: its jobs are relative to that round's first job
         size_t r = 0;
         while (r + 1 < S.rp_rounds.size() && q >= S.rp_rounds[r + 1].b0) r++;
         const cs::JobDesc* jobs = S.h_jobs_out.p + S.rp_rounds[r].j0;
-        const int* jvalid = S.h_job_valid.p + S.rp_rounds[r].j0;
+        const int* jvalid = S.sb.h_job_valid.p + S.rp_rounds[r].j0;
         const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q], bi = S.rp_box_index[q];
         HeightCols cols[3];
         long long run = base;
         for (int h = 0; h < nh; h++) {
-          cols[h] = HeightCols{S.h_fb_dist.p + run, S.h_fb_angle.p + run, S.h_fb_skew.p + run, S.h_fb_flag.p + run, S.h_fb_slot.p + run, jvalid[j0 + h]};
+          cols[h] = S.sb.fb_cols(run, jvalid[j0 + h]);
           run += jvalid[j0 + h];
         }
         std::vector<ExactWinner> wl;
@@ -1730,7 +1700,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
     for (size_t q = (size_t)z * RCH, q1 = std::min(S.nb, q + RCH); q < q1; q++) {
       const int f = S.rp_box_frame[q], bi = S.rp_box_index[q];
       if (redo[f] || host_done[q]) continue;
-      const int nw = S.h_win_count.p[q];
+      const int nw = S.sb.h_win_count.p[q];
       for (int r = 0; r < nw; r++) copy_device_record(b->frames[f], bi, S.h_records.p[q * KMAX + r], C.out[((size_t)f * MB + bi) * KMAX + r]);
       C.out_counts[(size_t)f * MB + bi] = nw;
     }
@@ -1909,20 +1879,6 @@ void round_write_winner(const RoundRun& X, const RoundTables& T, const cs::JobDe
                       normalized_error, C.out[((size_t)f * C.b->max_boxes + jd.box) * C.d->prm.max_cuboid_num + rank]);
 }
 
-// a table to the device: through the pinned block `hb` (asynchronous, back to back with its neighbours), or from where it lies
-template <class T>
-int upload_staged(DevBuf<T>& dst, const std::vector<T>& vec, unsigned char* hb, size_t off, hipStream_t st) {
-  if (vec.empty()) return CS_OK;
-  memcpy(hb + off, vec.data(), sizeof(T) * vec.size());
-  CS_HIP_TRY(hipMemcpyAsync(dst.p, hb + off, sizeof(T) * vec.size(), hipMemcpyHostToDevice, st));
-  return CS_OK;
-}
-template <class T>
-int upload_pageable(DevBuf<T>& dst, const std::vector<T>& vec, hipStream_t st) {
-  CS_HIP_TRY(hipMemcpyAsync(dst.p, vec.data(), sizeof(T) * vec.size(), hipMemcpyHostToDevice, st));
-  return CS_OK;
-}
-
 // ---- setup (host): the round's jobs per frame, then packed into pooled tables
 int round_setup(RoundRun& X, int round, RoundTables& T) {
   cs_detector* d = X.C.d; cs_batch* b = X.C.b;
@@ -1941,23 +1897,18 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
     int shared_yoff = -1, shared_Y = 0;  // without roll/pitch sampling cam_pose never changes: every box of the frame sweeps the same yaw list (:180-184)
     for (int bi = b0; bi < b1; bi++) {
       const double* bb = &F.boxes[5 * bi];
-      int left = bb[0], w = bb[2];
-      int right = left + bb[2];
-      int res = (int)std::round(std::min(20, w / 10));
-      if (res < 1) continue;  // :215 break (same for every height sample)
+      if (top_sample_step(bb) < 1) continue;  // :215 break (same for every height sample)
       // yaw samples (:180-184)
       int yoff, nY;
       if (shared_yoff >= 0) { yoff = shared_yoff; nY = shared_Y; }
       else {
-        double yaw_init = X.cur_yaw[f] - 90.0 / 180.0 * CS_PI;
-        std::vector<double> yaws;
-        linespace<double>(yaw_init - P.yaw_range_deg / 180.0 * CS_PI, yaw_init + P.yaw_range_deg / 180.0 * CS_PI, P.yaw_step_deg / 180.0 * CS_PI, yaws);
-        yoff = (int)R.yaw.size(); nY = (int)yaws.size();
-        for (double y : yaws) { R.yaw.push_back(y); R.yaw_c.push_back(h_cos(y)); R.yaw_s.push_back(h_sin(y)); }
+        double yl[LINESPACE_MAX], yc[LINESPACE_MAX], ys[LINESPACE_MAX];      // (no list is longer: this path's tables have no other capacity)
+        yoff = (int)R.yaw.size(); nY = std::max(0, fill_yaw_list(X.cur_yaw[f], P.yaw_range_deg, P.yaw_step_deg, LINESPACE_MAX, yl, yc, ys));
+        R.yaw.insert(R.yaw.end(), yl, yl + nY); R.yaw_c.insert(R.yaw_c.end(), yc, yc + nY); R.yaw_s.insert(R.yaw_s.end(), ys, ys + nY);
         if (!sample_rp) { shared_yoff = yoff; shared_Y = nY; }
       }
-      std::vector<int> tops;
-      linespace<int>(left + 5, right - 5, res, tops);
+      std::vector<int> tops(LINESPACE_MAX);
+      tops.resize((size_t)top_samples(bb, tops.data()));
       for (int k = 0; k < F.n_heights[bi]; k++) {
         cs::JobDesc jd;
         fill_job_geometry(jd, F, bi, k, rp_off[f]);
@@ -1991,14 +1942,14 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
   std::vector<long long> f_slot(NF + 1, 0), f_vp(NF + 1, 0);
   for (int f = 0; f < NF; f++) {
     size_t nl = 0, nt = 0;
-    long long ns = 0, nv = 0;
+    JobSpan fs{0, 0};
     for (size_t q = 0; q < fr[f].jobs.size(); q++) {
-      const cs::JobDesc& jd = fr[f].jobs[q];
+      const JobSpan s = span_exact(fr[f].jobs[q]);
       nl += fr[f].jh[q].line_cap; nt += fr[f].jh[q].tops.size();
-      nv += (long long)jd.RP * jd.Y; ns += (long long)jd.RP * jd.Y * jd.T * 2;
+      fs.slots += s.slots; fs.vps += s.vps;
     }
     f_job[f + 1] = f_job[f] + fr[f].jobs.size(); f_line[f + 1] = f_line[f] + nl; f_yaw[f + 1] = f_yaw[f] + fr[f].yaw.size();
-    f_top[f + 1] = f_top[f] + nt; f_slot[f + 1] = f_slot[f] + ns; f_vp[f + 1] = f_vp[f] + nv;
+    f_top[f + 1] = f_top[f] + nt; f_slot[f + 1] = f_slot[f] + fs.slots; f_vp[f + 1] = f_vp[f] + fs.vps;
   }
   const size_t nj = f_job[NF];
   T.nj = nj; T.n_lines = f_line[NF];
@@ -2011,7 +1962,7 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
   d->pool->run(NF, [&](int f) {
     FrameRound& R = fr[f];
     size_t ji = f_job[f], lo = f_line[f], yo = f_yaw[f], to = f_top[f];
-    long long so = f_slot[f], vo = f_vp[f];
+    JobSpan at{f_slot[f], f_vp[f]};
     std::copy(R.yaw.begin(), R.yaw.end(), T.yaw.begin() + yo);
     std::copy(R.yaw_c.begin(), R.yaw_c.end(), T.yaw_c.begin() + yo);
     std::copy(R.yaw_s.begin(), R.yaw_s.end(), T.yaw_s.begin() + yo);
@@ -2019,7 +1970,6 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
       cs::JobDesc& jd = R.jobs[q];
       const JobHost& jh = R.jh[q];
       jd.line_off = (int)lo; jd.yaw_off = (int)(yo + jh.yaw_off_local); jd.top_off = (int)to;
-      jd.vp_off = (int)vo; jd.slot_off = so;
       if (!dev_setup) {
         std::copy(jh.mids_x.begin(), jh.mids_x.end(), T.mid_x.begin() + lo);
         std::copy(jh.mids_y.begin(), jh.mids_y.end(), T.mid_y.begin() + lo);
@@ -2027,15 +1977,14 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
       }
       std::copy(jh.tops.begin(), jh.tops.end(), T.top_x.begin() + to);
       lo += jh.line_cap; to += jh.tops.size();
-      T.slot_prefix[ji] = so; T.vp_prefix[ji] = (int)vo;
-      vo += (long long)jd.RP * jd.Y;
-      so += (long long)jd.RP * jd.Y * jd.T * 2;
+      jd.slot_off = T.slot_prefix[ji] = at.slots; jd.vp_off = T.vp_prefix[ji] = (int)at.vps;
+      at.slots += span_exact(jd).slots; at.vps += span_exact(jd).vps;
       T.jobs[ji] = jd;
     }
   });
   T.slot_prefix[nj] = f_slot[NF]; T.vp_prefix[nj] = (int)f_vp[NF];
   T.slot_total = T.slot_prefix[nj]; T.vp_total = T.vp_prefix[nj];
-  for (size_t j = 0; j < nj; j++)
+  for (size_t j = 0; j < nj; j++)      // (every job here belongs to a swept box; a box whose yaw list came out empty is still listed)
     if (T.jobs[j].hid == 0) { T.box_job0.push_back((int)j); T.box_njobs.push_back(b->frames[T.jobs[j].frame].n_heights[T.jobs[j].box]); }
   tm.setup_host_ms += now_ms() - t0;
   tm.n_jobs += (long long)nj; tm.n_slots += T.slot_total;
@@ -2047,28 +1996,26 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
 // and the host does not wait (the round's results are awaited before the block is written again).
 int round_upload(RoundRun& X, RoundTables& T) {
   cs_batch* b = X.C.b;
+  SweepBuffers& B = b->round;
   hipStream_t st = X.C.d->stream;
   const double t0 = now_ms();
-  const size_t nj = T.nj, n_lines = T.n_lines, n_yaw = T.yaw.size(), n_top = T.top_x.size();
-  CS_ENSURE(b->d_jobs, nj); CS_ENSURE(b->d_slot_prefix, nj + 1); CS_ENSURE(b->d_vp_prefix, nj + 1); CS_ENSURE(b->d_job_valid, nj); CS_ENSURE(b->d_job_cbase, nj + 1);
-  CS_ENSURE(b->d_mid_x, n_lines + 1); CS_ENSURE(b->d_mid_y, n_lines + 1); CS_ENSURE(b->d_ang, n_lines + 1);
-  CS_ENSURE(b->d_yaw, n_yaw + 1); CS_ENSURE(b->d_yaw_c, n_yaw + 1); CS_ENSURE(b->d_yaw_s, n_yaw + 1); CS_ENSURE(b->d_top_x, n_top + 1);
-  CS_ENSURE(b->d_vp, 6 * (size_t)T.vp_total + 6); CS_ENSURE(b->d_bound, 6 * (size_t)T.vp_total + 6);
-  CS_ENSURE(b->d_flag, T.slot_total + 1);
-  size_t need = 0;
-  auto room = [&](size_t bytes) { const size_t at = need; need += (bytes + 63) & ~(size_t)63; return at; };
-  const size_t o_jobs = room(sizeof(cs::JobDesc) * T.jobs.size()), o_sp = room(sizeof(long long) * T.slot_prefix.size()), o_vp = room(sizeof(int) * T.vp_prefix.size());
-  const size_t o_mx = room(8 * T.mid_x.size()), o_my = room(8 * T.mid_y.size()), o_an = room(8 * T.ang.size());
-  const size_t o_y = room(8 * T.yaw.size()), o_yc = room(8 * T.yaw_c.size()), o_ys = room(8 * T.yaw_s.size()), o_tx = room(sizeof(int) * T.top_x.size());
+  const size_t nj = T.nj;
+  int rc;
+  if ((rc = B.ensure_tables(nj, nj + 1, T.n_lines, T.yaw.size(), T.top_x.size(), (size_t)T.vp_total, T.box_job0.size(), X.C.d->prm.max_cuboid_num))) return rc;
+  CS_ENSURE(B.flag, T.slot_total + 1);
+  struct Tab { void* dst; const void* src; size_t bytes; };
+  auto tab = [](auto& dst, const auto& vec) { return Tab{dst.p, vec.data(), sizeof(vec[0]) * vec.size()}; };
+  const Tab tabs[] = {tab(B.jobs, T.jobs), tab(B.slot_prefix, T.slot_prefix), tab(B.vp_prefix, T.vp_prefix), tab(B.mid_x, T.mid_x), tab(B.mid_y, T.mid_y), tab(B.ang, T.ang),
+                      tab(B.yaw, T.yaw), tab(B.yaw_c, T.yaw_c), tab(B.yaw_s, T.yaw_s), tab(B.top_x, T.top_x), tab(B.box_job0, T.box_job0), tab(B.box_njobs, T.box_njobs)};
+  size_t need = 0;      // every table on a 64-byte boundary of the block
+  for (const Tab& t : tabs) need += (size_t)whole_waves((long long)t.bytes);
   CS_ENSURE(b->h_tables, need + 64);
   unsigned char* hb = b->h_tables.p;
-  int rc;
-  if ((rc = upload_staged(b->d_jobs, T.jobs, hb, o_jobs, st)) || (rc = upload_staged(b->d_slot_prefix, T.slot_prefix, hb, o_sp, st)) || (rc = upload_staged(b->d_vp_prefix, T.vp_prefix, hb, o_vp, st)) ||
-      (rc = upload_staged(b->d_mid_x, T.mid_x, hb, o_mx, st)) || (rc = upload_staged(b->d_mid_y, T.mid_y, hb, o_my, st)) || (rc = upload_staged(b->d_ang, T.ang, hb, o_an, st)) ||
-      (rc = upload_staged(b->d_yaw, T.yaw, hb, o_y, st)) || (rc = upload_staged(b->d_yaw_c, T.yaw_c, hb, o_yc, st)) || (rc = upload_staged(b->d_yaw_s, T.yaw_s, hb, o_ys, st)) ||
-      (rc = upload_staged(b->d_top_x, T.top_x, hb, o_tx, st)))
-    return rc;
-  CS_HIP_TRY(hipMemsetAsync(b->d_job_valid.p, 0, sizeof(int) * nj, st));
+  for (const Tab& t : tabs) {
+    if (t.bytes) { memcpy(hb, t.src, t.bytes); CS_HIP_TRY(hipMemcpyAsync(t.dst, hb, t.bytes, hipMemcpyHostToDevice, st)); }
+    hb += whole_waves((long long)t.bytes);
+  }
+  CS_HIP_TRY(hipMemsetAsync(B.job_valid.p, 0, sizeof(int) * nj, st));
   X.C.tm->h2d_ms += now_ms() - t0;
   return CS_OK;
 }
@@ -2076,25 +2023,22 @@ int round_upload(RoundRun& X, RoundTables& T) {
 // ---- sweep (HIP): line setup, VP support, corner construction
 int round_sweep(RoundRun& X, RoundTables& T) {
   cs_detector* d = X.C.d; cs_batch* b = X.C.b;
+  SweepBuffers& B = b->round;
   const cs_detect_params& P = d->prm;
   hipStream_t st = d->stream;
   const size_t nj = T.nj;
   cs::DetectDeviceView& v = T.v;
-  v.jobs = b->d_jobs.p; v.n_jobs = (int)nj; v.slot_prefix = b->d_slot_prefix.p; v.vp_prefix = b->d_vp_prefix.p;
-  v.maps = b->d_maps.p; v.mid_x = b->d_mid_x.p; v.mid_y = b->d_mid_y.p; v.line_angle = b->d_ang.p;
-  v.yaw = b->d_yaw.p; v.yaw_cos = b->d_yaw_c.p; v.yaw_sin = b->d_yaw_s.p; v.top_x = b->d_top_x.p; v.rp = b->d_rp.p; v.invK = b->d_invK.p;
-  v.vp = b->d_vp.p; v.bound = b->d_bound.p; v.flag = b->d_flag.p;
-  v.job_valid = b->d_job_valid.p; v.job_cbase = b->d_job_cbase.p;
+  B.bind(v, *b, nj);      // (the c_* columns: bound again once they are sized, round_compact_score)
   CS_HIP_TRY(hipEventRecord(d->ev[6], st));
   if (X.dev_setup) {
-    cs::launch_line_setup(b->d_jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, b->d_mid_x.p, b->d_mid_y.p, b->d_ang.p,
+    cs::launch_line_setup(B.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, B.mid_x.p, B.mid_y.p, B.ang.p,
                           P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st);
   }
   CS_HIP_TRY(hipEventRecord(d->ev[7], st));
   if (X.dev_setup) {
     // the merged segment counts come back with the results (byte accounting, debug getters)
     CS_ENSURE(b->h_jobs, nj);
-    CS_HIP_TRY(hipMemcpyAsync(b->h_jobs.p, b->d_jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_jobs.p, B.jobs.p, sizeof(cs::JobDesc) * nj, hipMemcpyDeviceToHost, st));
   }
   CS_HIP_TRY(hipEventRecord(d->ev[0], st));
   cs::launch_vp_support(v, X.C.sp, T.vp_total, st);
@@ -2108,10 +2052,11 @@ int round_sweep(RoundRun& X, RoundTables& T) {
 // compaction into the c_* columns (`rows` of them) and the scorer
 int round_compact_score(RoundRun& X, RoundTables& T, long long rows) {
   cs_detector* d = X.C.d; cs_batch* b = X.C.b;
+  SweepBuffers& B = b->round;
   hipStream_t st = d->stream;
   cs::DetectDeviceView& v = T.v;
-  CS_ENSURE(b->d_c_slot, rows + 1); CS_ENSURE(b->d_c_flag, rows + 1); CS_ENSURE(b->d_c_dist, rows + 1); CS_ENSURE(b->d_c_angle, rows + 1); CS_ENSURE(b->d_c_skew, rows + 1);
-  v.c_slot = b->d_c_slot.p; v.c_flag = b->d_c_flag.p; v.c_dist = b->d_c_dist.p; v.c_angle = b->d_c_angle.p; v.c_skew = b->d_c_skew.p;
+  if (int rc = B.ensure_slots(rows)) return rc;
+  B.bind(v, *b, T.nj);
   CS_HIP_TRY(hipEventRecord(d->ev[3], st));
   cs::launch_scan_compact(v, st);
   CS_HIP_TRY(hipEventRecord(d->ev[8], st));
@@ -2145,6 +2090,7 @@ int account_sweep(cs_detector* d, cs_detect_timing& tm, const RoundTables& T, lo
 int round_rank_device(RoundRun& X, RoundTables& T) {
   PipeCtx& C = X.C;
   cs_detector* d = C.d; cs_batch* b = C.b;
+  SweepBuffers& B = b->round;
   const cs_detect_params& P = d->prm;
   const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
   hipStream_t st = d->stream;
@@ -2153,79 +2099,44 @@ int round_rank_device(RoundRun& X, RoundTables& T) {
   const size_t nj = T.nj, nb = T.box_job0.size();
   int rc;
   if ((rc = round_compact_score(X, T, T.slot_total))) return rc;   // the exact number of valid proposals stays on the device
-  CS_ENSURE(b->d_box_job0, nb); CS_ENSURE(b->d_box_njobs, nb); CS_ENSURE(b->d_win_count, nb); CS_ENSURE(b->d_fallback, nb); CS_ENSURE(b->d_winners, nb * KMAX);
-  CS_ENSURE(b->h_winners, nb * KMAX); CS_ENSURE(b->h_win_count, nb); CS_ENSURE(b->h_fallback, nb); CS_ENSURE(b->h_job_valid, nj); CS_ENSURE(b->h_job_cbase, nj + 1);
-  CS_ENSURE(b->h_tables2, 2 * sizeof(int) * nb + 128);
-  if ((rc = upload_staged(b->d_box_job0, T.box_job0, b->h_tables2.p, 0, st)) || (rc = upload_staged(b->d_box_njobs, T.box_njobs, b->h_tables2.p, (sizeof(int) * nb + 63) & ~(size_t)63, st))) return rc;
+  CS_ENSURE(b->h_winners, nb * KMAX);
   cs::RankView rv{};
-  rv.box_job0 = b->d_box_job0.p; rv.box_njobs = b->d_box_njobs.p; rv.n_boxes = (int)nb;
-  rv.winners = b->d_winners.p; rv.win_count = b->d_win_count.p; rv.fallback = b->d_fallback.p;
+  rv.box_job0 = B.box_job0.p; rv.box_njobs = B.box_njobs.p; rv.n_boxes = (int)nb; rv.winners = B.winners.p; rv.win_count = B.win_count.p; rv.fallback = B.fallback.p;
   if (X.sample_rp) { CS_ENSURE(b->d_last_slot, nb); CS_ENSURE(b->h_last_slot, nb); rv.last_slot = b->d_last_slot.p; }
   cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
   cs::launch_rank(v, rv, rkp, st);
   CS_HIP_TRY(hipEventRecord(d->ev[5], st));
   CS_HIP_TRY(hipGetLastError());
   double t0 = now_ms();
-  CS_HIP_TRY(hipMemcpyAsync(b->h_winners.p, b->d_winners.p, sizeof(cs::RankWinner) * nb * KMAX, hipMemcpyDeviceToHost, st));
-  CS_HIP_TRY(hipMemcpyAsync(b->h_win_count.p, b->d_win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-  CS_HIP_TRY(hipMemcpyAsync(b->h_fallback.p, b->d_fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(b->h_winners.p, B.winners.p, sizeof(cs::RankWinner) * nb * KMAX, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(B.h_win_count.p, B.win_count.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(B.h_fallback.p, B.fallback.p, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
   if (X.sample_rp) CS_HIP_TRY(hipMemcpyAsync(b->h_last_slot.p, b->d_last_slot.p, sizeof(long long) * nb, hipMemcpyDeviceToHost, st));
-  CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
-  CS_HIP_TRY(hipMemcpyAsync(b->h_job_cbase.p, b->d_job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(B.h_job_valid.p, B.job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(B.h_job_cbase.p, B.job_cbase.p, sizeof(long long) * (nj + 1), hipMemcpyDeviceToHost, st));
   CS_HIP_TRY(hipStreamSynchronize(st));
   tm.d2h_ms += now_ms() - t0;
   if (X.dev_setup) for (size_t j = 0; j < nj; j++) T.jobs[j].m = b->h_jobs.p[j].m;
-  const long long n_valid = b->h_job_cbase.p[nj];
+  const long long n_valid = B.h_job_cbase.p[nj];
   tm.n_valid += n_valid;
   if ((rc = account_sweep(d, tm, T, n_valid, true))) return rc;
   t0 = now_ms();
-  // columns of every flagged box, fetched with one gather + one copy per column
-  std::vector<long long> fb_src, fb_dst, fb_slot;
-  std::vector<int> fb_cnt, fb_flag, fb_range_of_job(nj, -1);
-  std::vector<double> fb_dist, fb_angle, fb_skew;
-  long long tot = 0;
-  for (size_t q = 0; q < nb; q++)
-    if (b->h_fallback.p[q])
-      for (int h = 0; h < T.box_njobs[q]; h++) {
-        int j = T.box_job0[q] + h;
-        fb_range_of_job[j] = (int)fb_src.size();
-        fb_src.push_back(b->h_job_cbase.p[j]); fb_cnt.push_back(b->h_job_valid.p[j]); fb_dst.push_back(tot);
-        tot += b->h_job_valid.p[j];
-      }
-  if (!fb_src.empty()) {
-    size_t nr = fb_src.size();
-    CS_ENSURE(b->d_fb_src, nr); CS_ENSURE(b->d_fb_dst, nr); CS_ENSURE(b->d_fb_cnt, nr);
-    CS_ENSURE(b->d_fb_dist, tot + 1); CS_ENSURE(b->d_fb_angle, tot + 1); CS_ENSURE(b->d_fb_skew, tot + 1); CS_ENSURE(b->d_fb_flag, tot + 1); CS_ENSURE(b->d_fb_slot, tot + 1);
-    if ((rc = upload_pageable(b->d_fb_src, fb_src, st)) || (rc = upload_pageable(b->d_fb_dst, fb_dst, st)) || (rc = upload_pageable(b->d_fb_cnt, fb_cnt, st))) return rc;
-    cs::launch_gather_ranges(v, b->d_fb_src.p, b->d_fb_cnt.p, b->d_fb_dst.p, (int)nr, b->d_fb_dist.p, b->d_fb_angle.p, b->d_fb_skew.p, b->d_fb_flag.p, b->d_fb_slot.p, st);
-    fb_dist.resize(tot); fb_angle.resize(tot); fb_skew.resize(tot); fb_flag.resize(tot); fb_slot.resize(tot);
-    if (tot) {
-      CS_HIP_TRY(hipMemcpyAsync(fb_dist.data(), b->d_fb_dist.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(fb_angle.data(), b->d_fb_angle.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(fb_skew.data(), b->d_fb_skew.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(fb_flag.data(), b->d_fb_flag.p, 4 * (size_t)tot, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipMemcpyAsync(fb_slot.data(), b->d_fb_slot.p, 8 * (size_t)tot, hipMemcpyDeviceToHost, st));
-    }
-    CS_HIP_TRY(hipStreamSynchronize(st));
-  }
+  // the flagged boxes' columns come in one gather (this path has nothing to do meanwhile: it waits at once)
+  TiePass tie(B, v, st, T.box_job0.data(), T.box_njobs.data(), nj, nb);
+  if ((rc = tie.enqueue_columns()) || (rc = tie.wait())) return rc;
+  tm.n_fallback_boxes += (int)tie.boxes.size();
   // the boxes the device ranked: their records; the flagged ones: the exact ranking only (their corners are fetched below, in one gather)
   const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
-  std::vector<std::vector<ExactWinner>> fb_winners(nb);
   d->pool->run((int)nb, [&](int q) {
     const int j0 = T.box_job0[q], nh = T.box_njobs[q];
     const cs::JobDesc* jobs = &T.jobs[j0];
-    if (b->h_fallback.p[q]) {
-      HeightCols cols[3];
-      for (int h = 0; h < nh; h++) {
-        const long long p0 = fb_dst[fb_range_of_job[j0 + h]];
-        cols[h] = HeightCols{fb_dist.data() + p0, fb_angle.data() + p0, fb_skew.data() + p0, fb_flag.data() + p0, fb_slot.data() + p0, b->h_job_valid.p[j0 + h]};
-      }
-      const long long last = exact_rank_box(cols, nh, RW, KMAX, fb_winners[q]);
+    if (B.h_fallback.p[q]) {
+      const long long last = tie.rank((size_t)q, RW, KMAX);
       if (X.sample_rp) carry_yaw(X, jobs[nh - 1], last);
       return;
     }
     if (X.sample_rp) carry_yaw(X, jobs[nh - 1], b->h_last_slot.p[q]);
-    const int nw = b->h_win_count.p[q];
+    const int nw = B.h_win_count.p[q];
     for (int r = 0; r < nw; r++) {
       const cs::RankWinner& w = b->h_winners.p[q * KMAX + r];
       int h = 0;
@@ -2234,24 +2145,14 @@ int round_rank_device(RoundRun& X, RoundTables& T) {
     }
     C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = nw;
   });
-  std::vector<long long> ws;
-  std::vector<size_t> corner0(nb, 0);      // first of a flagged box's winners in h_win_corners
-  for (size_t q = 0; q < nb; q++)
-    if (b->h_fallback.p[q]) { tm.n_fallback_boxes++; corner0[q] = ws.size(); for (const ExactWinner& w : fb_winners[q]) ws.push_back(w.slot); }
-  if (!ws.empty()) {
-    CS_ENSURE(b->d_win_slots, ws.size()); CS_ENSURE(b->d_win_corners, 16 * ws.size()); CS_ENSURE(b->h_win_corners, 16 * ws.size());
-    if ((rc = upload_pageable(b->d_win_slots, ws, st))) return rc;
-    cs::launch_gather_corners(v, C.sp, b->d_win_slots.p, (int)ws.size(), b->d_win_corners.p, st);
-    CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * ws.size(), hipMemcpyDeviceToHost, st));
-    CS_HIP_TRY(hipStreamSynchronize(st));
-  }
-  d->pool->run((int)nb, [&](int q) {
-    if (!b->h_fallback.p[q]) return;
+  if ((rc = tie.enqueue_corners(C.sp)) || (rc = tie.wait())) return rc;
+  d->pool->run((int)tie.boxes.size(), [&](int z) {
+    const size_t q = (size_t)tie.boxes[z];
     const cs::JobDesc* jobs = &T.jobs[T.box_job0[q]];
-    const int nw = (int)fb_winners[q].size();
+    const int nw = (int)tie.winners[q].size();
     for (int r = 0; r < nw; r++) {
-      const ExactWinner& w = fb_winners[q][r];
-      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, b->h_win_corners.p + 16 * (corner0[q] + r), r);
+      const ExactWinner& w = tie.winners[q][r];
+      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, tie.corners(q, r), r);
     }
     C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = nw;
   });
@@ -2263,6 +2164,7 @@ int round_rank_device(RoundRun& X, RoundTables& T) {
 int round_rank_host(RoundRun& X, RoundTables& T) {
   PipeCtx& C = X.C;
   cs_detector* d = C.d; cs_batch* b = C.b;
+  SweepBuffers& B = b->round;
   const cs_detect_params& P = d->prm;
   const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
   hipStream_t st = d->stream;
@@ -2271,24 +2173,23 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   const size_t nj = T.nj, nb = T.box_job0.size();
   int rc;
   // valid counts -> host -> size the compact arrays
-  CS_ENSURE(b->h_job_valid, nj); CS_ENSURE(b->h_job_cbase, nj + 1);
-  CS_HIP_TRY(hipMemcpyAsync(b->h_job_valid.p, b->d_job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
+  CS_HIP_TRY(hipMemcpyAsync(B.h_job_valid.p, B.job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
   CS_HIP_TRY(hipStreamSynchronize(st));
   if (X.dev_setup) for (size_t j = 0; j < nj; j++) T.jobs[j].m = b->h_jobs.p[j].m;
   long long n_valid = 0;
-  for (size_t j = 0; j < nj; j++) { b->h_job_cbase.p[j] = n_valid; n_valid += b->h_job_valid.p[j]; }
-  b->h_job_cbase.p[nj] = n_valid;
+  for (size_t j = 0; j < nj; j++) { B.h_job_cbase.p[j] = n_valid; n_valid += B.h_job_valid.p[j]; }
+  B.h_job_cbase.p[nj] = n_valid;
   tm.n_valid += n_valid;
   if ((rc = round_compact_score(X, T, n_valid))) return rc;
   CS_HIP_TRY(hipGetLastError());
   CS_ENSURE(b->h_c_slot, n_valid + 1); CS_ENSURE(b->h_c_flag, n_valid + 1); CS_ENSURE(b->h_c_dist, n_valid + 1); CS_ENSURE(b->h_c_angle, n_valid + 1); CS_ENSURE(b->h_c_skew, n_valid + 1);
   double t0 = now_ms();
   if (n_valid) {
-    CS_HIP_TRY(hipMemcpyAsync(b->h_c_slot.p, b->d_c_slot.p, sizeof(long long) * n_valid, hipMemcpyDeviceToHost, st));
-    CS_HIP_TRY(hipMemcpyAsync(b->h_c_flag.p, b->d_c_flag.p, sizeof(int) * n_valid, hipMemcpyDeviceToHost, st));
-    CS_HIP_TRY(hipMemcpyAsync(b->h_c_dist.p, b->d_c_dist.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-    CS_HIP_TRY(hipMemcpyAsync(b->h_c_angle.p, b->d_c_angle.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
-    CS_HIP_TRY(hipMemcpyAsync(b->h_c_skew.p, b->d_c_skew.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_slot.p, B.c_slot.p, sizeof(long long) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_flag.p, B.c_flag.p, sizeof(int) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_dist.p, B.c_dist.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_angle.p, B.c_angle.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
+    CS_HIP_TRY(hipMemcpyAsync(b->h_c_skew.p, B.c_skew.p, sizeof(double) * n_valid, hipMemcpyDeviceToHost, st));
   }
   CS_HIP_TRY(hipStreamSynchronize(st));
   tm.d2h_ms += now_ms() - t0;
@@ -2302,8 +2203,8 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
     const cs::JobDesc& jd = T.jobs[j];
     JobResult& R = b->results[res_base + j];
     R.frame = jd.frame; R.box = jd.box; R.hid = jd.hid;
-    const long long c0 = b->h_job_cbase.p[j];
-    const int V = b->h_job_valid.p[j];
+    const long long c0 = B.h_job_cbase.p[j];
+    const int V = B.h_job_valid.p[j];
     R.n_valid = V;
     R.rows9.resize(9 * (size_t)V);
     R.slots.assign(b->h_c_slot.p + c0, b->h_c_slot.p + c0 + V);
@@ -2322,7 +2223,7 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
     const int j0 = T.box_job0[q], nh = T.box_njobs[q];
     HeightCols cols[3];
     for (int h = 0; h < nh; h++) {
-      const long long c0 = b->h_job_cbase.p[j0 + h];
+      const long long c0 = B.h_job_cbase.p[j0 + h];
       const JobResult& R = b->results[res_base + j0 + h];
       cols[h] = HeightCols{b->h_c_dist.p + c0, b->h_c_angle.p + c0, b->h_c_skew.p + c0, b->h_c_flag.p + c0, b->h_c_slot.p + c0, R.n_valid, &R.keep, &R.score};
     }
@@ -2339,10 +2240,10 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   if (b->debug) wslots.insert(wslots.end(), b->h_c_slot.p, b->h_c_slot.p + n_valid);
   const size_t n_gather = wslots.size();
   if (n_gather) {
-    CS_ENSURE(b->d_win_slots, n_gather); CS_ENSURE(b->d_win_corners, 16 * n_gather); CS_ENSURE(b->h_win_corners, 16 * n_gather);
-    if ((rc = upload_pageable(b->d_win_slots, wslots, st))) return rc;
-    cs::launch_gather_corners(T.v, C.sp, b->d_win_slots.p, (int)n_gather, b->d_win_corners.p, st);
-    CS_HIP_TRY(hipMemcpyAsync(b->h_win_corners.p, b->d_win_corners.p, sizeof(double) * 16 * n_gather, hipMemcpyDeviceToHost, st));
+    CS_ENSURE(B.h_win_slots, n_gather); CS_ENSURE(B.h_win_corners, 16 * n_gather);
+    std::copy(wslots.begin(), wslots.end(), B.h_win_slots.p);
+    cs::launch_gather_corners(T.v, C.sp, B.h_win_slots.p, (int)n_gather, B.h_win_corners.p, st);     // (pinned host memory on both sides, as in TiePass)
+    CS_HIP_TRY(hipGetLastError());
     CS_HIP_TRY(hipStreamSynchronize(st));
   }
   size_t i = 0;
@@ -2350,15 +2251,15 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
     const cs::JobDesc* jobs = &T.jobs[T.box_job0[q]];
     for (size_t r = 0; r < win_per_box[q].size(); r++, i++) {
       const ExactWinner& w = win_per_box[q][r];
-      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, b->h_win_corners.p + 16 * i, (int)r);
+      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, B.h_win_corners.p + 16 * i, (int)r);
     }
     C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = (int)win_per_box[q].size();
   }
   if (b->debug) {
     for (size_t j = 0; j < nj; j++) {
       JobResult& R = b->results[res_base + j];
-      const long long c0 = b->h_job_cbase.p[j];
-      R.corners.assign(b->h_win_corners.p + 16 * (nw + c0), b->h_win_corners.p + 16 * (nw + c0 + R.n_valid));
+      const long long c0 = B.h_job_cbase.p[j];
+      R.corners.assign(B.h_win_corners.p + 16 * (nw + c0), B.h_win_corners.p + 16 * (nw + c0 + R.n_valid));
     }
   }
   tm.finalize_ms += now_ms() - t0;
