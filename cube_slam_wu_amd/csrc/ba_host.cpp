@@ -1,358 +1,20 @@
-// ba_host.cpp -- host side of path B (g2o bundle adjustment) behind the C ABI of include/cubeslam_hip.h.
+// ba_host.cpp -- host side of path B (g2o bundle adjustment) behind the C ABI of include/cubeslam_hip.h: the handle's life, graph input, the
+// structure phase and its uploads, edge levels and classification, inspection, dump / load.  The numeric steps and the LM loop are ba_lm.cpp's.
 //
 // Mirrors, step for step, what g2o's BlockSolver + OptimizationAlgorithmLevenberg do
 // (object_slam/Thirdparty/g2o/g2o/core/block_solver.hpp, optimization_algorithm_levenberg.cpp): the
 // structure phase (index mapping, edge orderings, Schur pattern) runs once on the host when the edges are
 // set; every numeric step is a HIP kernel on resident data; the LM control flow (lambda schedule, accept /
-// reject, termination) is scalar host code fed by one chi2 read-back per trial.  The reduced camera/cuboid
-// system is dense and factorised with rocSOLVER potrf/potrs (the reference's LinearSolverDense uses a dense
-// Eigen::LDLT, solvers/linear_solver_dense.h:104-111).  There is no CPU fallback.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <string>
-#include <mutex>
-#include <thread>
-#include <map>
-#include <vector>
-
-#include "../../include/cubeslam_hip.h"
-#include "ba_edge_class.h"
-#include "ba_structure.h"
-#include "ba_types.h"
-#include "band_solver.h"
-#include "cs_hip_util.h"
-#include "cs_lm.h"
-#include "cs_sparse_solver.h"
+// reject, termination) is scalar host code fed by one chi2 read-back per trial.  There is no CPU fallback.
+#include "ba_handle.h"
 
 namespace {
 
 using cs::now_ms;
-
-// a phase mark on the handle's stream -- only while the stage split is asked for (cs_ba_set_stage_timing)
-#define BA_MARK(B, e) do { if ((B)->stage_timing) CS_HIP_TRY(hipEventRecord((e), (B)->st)); } while (0)
-#define BA_NCCL(expr)                                                          \
-  do {                                                                         \
-    ncclResult_t _r = (expr);                                                  \
-    if (_r != ncclSuccess) {                                                   \
-      cs_set_error(std::string(#expr) + ": " + ncclGetErrorString(_r));     \
-      return CS_ERR_HIP;                                                       \
-    }                                                                          \
-  } while (0)
-
-// Pinned staging for the structure phase's many small uploads: a blocking hipMemcpy from pageable memory costs ~40 us whatever its
-// size, and the phase makes a few dozen; through this arena they are queued on the handle's stream and waited for once.
-struct StageArena {
-  char* p = nullptr;
-  size_t cap = 0, off = 0;
-  void* take(size_t bytes) {          // nullptr: no room (the caller copies directly)
-    const size_t at = (off + 63) & ~(size_t)63;
-    if (!p || at + bytes > cap) return nullptr;
-    off = at + bytes;
-    return p + at;
-  }
-  int begin(size_t want) {            // at the start of a structure phase, the stream idle
-    off = 0;
-    if (p && cap >= want) return CS_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    CS_HIP_TRY(hipHostMalloc((void**)&p, want));
-    cap = want;
-    return CS_OK;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = off = 0; }
-};
-
-static int g_dbuf_reallocs = 0;     // (diagnostics: device (re)allocations, printed with the structure phase's clock under CS_BA_PROF)
-template <class T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0, cap = 0;       // entries in use / allocated (grow-only: a graph that is extended frame by frame re-runs the structure phase,
-                               // and ~100 hipFree + hipMalloc pairs were a quarter of it at 200 cameras)
-  int reserve(size_t count) {
-    count = std::max<size_t>(1, count);
-    if (p && count <= cap) return CS_OK;
-    // (a buffer that has to grow belongs to a graph that is being extended: a quarter of head room, so that the next frames fit --
-    // without it every appended frame re-allocated every buffer whose size follows the edges or the points, ~60 of them)
-    const size_t want = p ? count + count / 4 + 64 : count;
-    g_dbuf_reallocs++;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    CS_HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
-    cap = want;
-    return CS_OK;
-  }
-  int upload_ptr(const T* h, size_t count) {   // from the caller's memory
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    if (n) CS_HIP_TRY(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return CS_OK;
-  }
-  int append_ptr(const T* h, size_t count) {   // the old contents stay where they are on the device, `count` new entries follow
-    if (!count) return CS_OK;
-    if (!p || n + count > cap) {               // (with head room: the next frames append in place)
-      const size_t want = std::max(n + count, cap + cap / 2 + 16);
-      T* q = nullptr;
-      CS_HIP_TRY(hipMalloc((void**)&q, want * sizeof(T)));
-      if (n) CS_HIP_TRY(hipMemcpy(q, p, n * sizeof(T), hipMemcpyDeviceToDevice));
-      if (p) (void)hipFree(p);
-      p = q; cap = want;
-    }
-    CS_HIP_TRY(hipMemcpy(p + n, h, count * sizeof(T), hipMemcpyHostToDevice));
-    n += count;
-    return CS_OK;
-  }
-  // the same through a pinned arena, queued on st (a frame's appends: a dozen blocking copies from pageable memory were 0.3-0.5 ms); the
-  // arena's contents must stay until st has run (the handle rewinds it after the next structure phase's wait)
-  int append_ptr_staged(const T* h, size_t count, StageArena& stage, hipStream_t st) {
-    if (!count) return CS_OK;
-    const size_t bytes = count * sizeof(T);
-    void* pin = (p && n + count <= cap && bytes <= (256u << 10)) ? stage.take(bytes) : nullptr;
-    if (!pin) {                                   // growing (the old contents are copied: nothing may still be writing them) or no room
-      CS_HIP_TRY(hipStreamSynchronize(st));
-      return append_ptr(h, count);
-    }
-    std::memcpy(pin, h, bytes);
-    CS_HIP_TRY(hipMemcpyAsync(p + n, pin, bytes, hipMemcpyHostToDevice, st));
-    n += count;
-    return CS_OK;
-  }
-  int upload(const std::vector<T>& h) { return upload_ptr(h.data(), h.size()); }
-  int upload_ptr_staged(const T* h, size_t count, StageArena& stage, hipStream_t st) {   // up to 1 MB: through the pinned arena, queued on st (a blocking copy from pageable memory costs 50-100 us)
-    const size_t bytes = count * sizeof(T);
-    void* pin = (bytes && bytes <= (1u << 20)) ? stage.take(bytes) : nullptr;
-    if (!pin) return upload_ptr(h, count);
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    std::memcpy(pin, h, bytes);
-    CS_HIP_TRY(hipMemcpyAsync(p, pin, bytes, hipMemcpyHostToDevice, st));
-    return CS_OK;
-  }
-  // like upload_ptr_staged, but the copy itself is left to the caller's batched launch (cs::ba_launch_multi_copy): destination, staged
-  // source and size are appended to the list.  No room in the arena: a blocking copy now.
-  // Tables of more than 64 KB keep their own hipMemcpyAsync (the copy engine moves a large table faster than a kernel reads it over the link:
-  // at a million edges the all-kernel form cost the phase 1.5 ms).
-  int upload_ptr_deferred(const T* h, size_t count, StageArena& stage, std::vector<cs::BaCopyItem>& list, hipStream_t st) {
-    const size_t bytes = count * sizeof(T);
-    if (bytes > (64u << 10)) return upload_ptr_staged(h, count, stage, st);
-    void* pin = bytes ? stage.take(bytes) : nullptr;
-    if (!pin) return upload_ptr(h, count);
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    std::memcpy(pin, h, bytes);
-    list.push_back(cs::BaCopyItem{p, pin, bytes});
-    return CS_OK;
-  }
-  int alloc(size_t count, hipStream_t st = nullptr) {   // zeroed; st: queued on that stream instead of a blocking call per buffer
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    if (st) CS_HIP_TRY(hipMemsetAsync(p, 0, std::max<size_t>(1, n) * sizeof(T), st));
-    else CS_HIP_TRY(hipMemset(p, 0, std::max<size_t>(1, n) * sizeof(T)));
-    return CS_OK;
-  }
-  // zeroed like alloc(), but the fill is left to the caller's batched launch (cs::ba_launch_multi_zero): ptr / bytes are appended to the list
-  int alloc_deferred(size_t count, std::vector<std::pair<void*, size_t>>& zero_list) {
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    zero_list.emplace_back((void*)p, std::max<size_t>(1, n) * sizeof(T));
-    return CS_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; cap = 0; }
-};
-
-using cs::UBuf;    // (host scratch of the structure phase: ba_structure.h)
-
-}  // namespace
-
-struct cs_ba {
-  int device = 0;
-  hipStream_t st = nullptr;
-  StageArena stage;                          // pinned staging of the structure phase's small uploads
-  // the landmarks' camera lists of the last structure phase (host): a graph that is only appended to extends them instead of re-sorting all edges
-  int st_lists_edges = 0, st_cur = 0; std::vector<int> st_cam_cnt; UBuf<int> st_cams_of[2], st_edge_of[2];   // (two sets: a phase reads the last one's and fills the other)
-  UBuf<int> st_pm_pt, st_pm_cam, st_cm_pm, st_cm_pt;   // host scratch of the edge orders, kept for its memory only
-  StageArena append_stage;                   // ... and of cs_ba_append_*'s rows (queued on st, rewound by the structure phase)
-  hipStream_t st2 = nullptr;                 // side stream of the reduce phase (cuboid elimination beside the landmark segments)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipStream_t st3 = nullptr;                 // third stream of the linearisation: the landmark kernel beside the camera kernel (which fills a fraction of the CUs)
-  hipEvent_t ev_join3 = nullptr;
-  rocblas_handle blas = nullptr;
-  hipEvent_t ev[8] = {};   // phase marks on the stream (linearise: 0-1; solve: 2 reduce 3 factor 4 back-substitution 5)
-  hipEvent_t sev[4] = {};  // separator mode, inside [3, 4]: interior factorised, separator message formed, messages gathered, separator system solved
-  double sep_ms[5] = {0, 0, 0, 0, 0};   // accumulated: interior factorisation, message (Y, T, t), gather, separator solve, interior back-substitution
-  bool lin_pending = false;  // ev[0..1] recorded but not yet read
-  int* h_status = nullptr;   // pinned: [status of the (interior's) factorisation, a cuboid block failed, status of the separator system's factorisation -- sparse: [2], [3] are the solver's two words]
-  // sharded BA over RCCL (cs_ba_comm_init): the collectives are issued from here, on this handle's stream
-  ncclComm_t comm = nullptr;
-  DBuf<double> d_scalars;    // [chi2, LM scale term] of a trial; lambda_0's diagonal on iteration 0
-  // lambda of the current trial lives in device memory (d_lam: [lambda, lambda of the pose diagonals in LM's scale term]), copied from
-  // the pinned h_lam at the head of a trial's launch sequence: the sequence itself never changes
-  double* h_lam = nullptr;
-  DBuf<double> d_lam;
-  double* h_scalars = nullptr;   // pinned mirror
-  // the trial's [chi2, scale term, failure flag, sequence number], written by the trial's last kernel itself (ba_sum2_flag_kernel) and polled by
-  // cs_ba_optimize: pinned, device-visible
-  double* h_trial = nullptr;
-  double trial_seq = 0.0;
-  // G2OBatchStatistics-like stage split (core/batch_stats.h:48-62): like g2o's setComputeBatchStatistics it is OFF unless asked for
-  // (cs_ba_set_stage_timing) -- every phase mark is an event on the stream, ~6 us of dispatch gap each, eight per LM trial
-  bool stage_timing = false;
-  // OptimizationAlgorithmLevenberg's two properties (optimization_algorithm_levenberg.cpp:50-51, setters :191-199): cs_ba_set_lm_params
-  double user_lambda_init = 0.0;      // "initialLambda": > 0 replaces tau * max |H_jj| (computeLambdaInit :168-169)
-  int max_trials_after_failure = 10;  // "maxTrialsAfterFailure": trials of one iteration (:149-151)
-  hipEvent_t ev_upd = nullptr;     // recorded behind a trial's update kernel when the next linearisation is speculated: its side streams fork there
-  size_t scalars_cap = 0;
-  // host copy of the problem description
-  int nc = 0, no = 0, np = 0, cuboids_first = 0;
-  std::vector<int> cam_fixed, cub_fixed, pt_fixed, cam_col, cub_col, pt_lm;  // pt_lm: landmark index among free points or -1
-  std::vector<int> cam_col_ref, cub_col_ref;  // columns in g2o's sort-by-id order (inspection only); cam_col / cub_col are in solver (RCM) order
-  int band_ld = 0;                            // 0 = dense reduced system
-  bool use_bcr = false;
-  int force_dense = 0;
-  // sharded BA: landmarks (with all their projection edges) are dealt to ranks by the camera subsequence of their
-  // first observation; cuboid / odometry edges follow their camera.  Every rank keeps all vertices.
-  int shard_rank = 0, shard_n = 1;
-  // Separator mode of the sharded solve (shard_n > 1, banded system, every rank's interior wide enough): rank r owns the columns
-  // [cut[r], cut[r + 1]) of the band -- its first sepw[r] >= bandwidth columns are the separator Z_r (sepw[0] = 0), the rest its interior
-  // -- and everything whose lowest column falls into that range (landmarks with their projection edges, cuboids, odometry edges).
-  // What a rank builds then lies in its own columns and in the diagonal block of the next separator; it factorises its interior only,
-  // the ranks exchange the separators' Schur complements (3 w^2 + 2 w doubles each) and the interiors' solutions.  Otherwise
-  // (sep_mode == false) the whole [S | b] is summed over the ranks and every rank factorises it.
-  bool sep_mode = false;
-  std::vector<int> cut, sepw, sep_off, lm_owner;   // sep_off[k]: row of separator k in the separator system (k = 1 .. R - 1; sep_off[R] = n_sep)
-  int n_sep = 0, w_max = 0;
-  size_t msg_doubles = 0;                          // one rank's message: [LL | RL | RR | tL | tR]
-  int int_c = 0, int_n = 0, zl = 0, wl = 0, zr = 0, wr = 0;   // this rank's interior and its two separators
-  DBuf<double> sepY, sep_msgs, sepS, int_work, sep_work;
-  DBuf<int> d_sep_off, d_sep_col, d_int_info, d_sep_info;
-  long long bytes_per_trial = 0, bytes_per_trial_allreduce = 0;   // payload this rank contributes to the collectives of one LM trial; what the all-reduce of [S | b] would be
-  size_t s_doubles = 0;                       // size of S; rhs follows it in the same allocation (one all-reduce)
-  int n_pose = 0, n_lm = 0;
-  int n_red = 0;            // dimension of the system the solver factorises: n_pose, or the cameras' part when the cuboids are eliminated too
-  bool elim = false;        // free cuboids eliminated like landmarks (single rank, fused Schur schedule)
-  int elim_max_slots = 1;   // observing cameras of the widest free cuboid
-  // general sparse Cholesky of the reduced system (cs_sparse_solver.h): graphs the ordering cannot band
-  bool sparse = false;         // this structure's solves go through `solver` (its plan was built, accepted and uploaded)
-  bool S_clean = false;        // sparse: S holds nothing outside the plan's pattern (set by the first trial's full clear)
-  cs::SparseSolver solver;
-  DBuf<int> d_cub_mine;     // sharded + eliminated cuboids: 1 = this rank owns the cuboid (holds all its edges)
-  DBuf<int> d_cubS_ptr, d_cubS_cam, d_ce_slot, d_cub_tile, d_cub_coef, d_elim_fail, d_slotE_ptr, d_slotE_idx;
-  DBuf<double> cub_M, cub_Dinv;
-  // The three pose-edge classes as the caller gave them (ba_edge_class.h): endpoints, payload, kernels and levels of EdgeSE3Cuboid,
-  // EdgeSE3CuboidProj and EdgeSE3Expmap, kept until the structure phase puts them on the device.
-  cs::EdgeClassHost ec[3] = {{cs::kPoseEdgeDims[0]}, {cs::kPoseEdgeDims[1]}, {cs::kPoseEdgeDims[2]}};
-  cs::EdgeClassHost& pose_class(int edge_class) { return ec[edge_class - CS_EDGE_CUBOID]; }
-  const cs::EdgeClassHost& pose_class(int edge_class) const { return ec[edge_class - CS_EDGE_CUBOID]; }
-  int n_proj = 0, n_cub = 0, n_odom = 0;   // n_cub = EdgeSE3Cuboid + EdgeSE3CuboidProj edges (the combined list ce_cam / ce_cub); n_cub, n_cub3 and n_odom are written by finalize_structure only
-  int n_cub3 = 0;                          // of which EdgeSE3Cuboid (they come first)
-  DBuf<double> pe_meas, pe_info, pe_K;
-  std::vector<int> e_pt, e_cam;      // projection edges, caller order: the mono edges [0, n_proj - n_stereo), the stereo edges behind them (g2o's edge order)
-  // stereo projection edges (EdgeStereoSE3ProjectXYZ; cs_ba_set_edges_proj_stereo): counted in n_proj, their payload in the caller's order on the
-  // host until the structure phase puts it beside the mono edges' in the two edge orders
-  int n_stereo = 0;
-  std::vector<double> h_se_uv, h_se_ur, h_se_intr, h_se_sinfo, h_se_huber;   // 2, 1, 4 (fx fy cx cy), 10 (information 3 x 3, bf), 1 (empty: no kernel) per edge
-  std::vector<int> rk_stereo;                                                // kernel kinds (cs_ba_set_robust_kernels), empty: Huber from the deltas
-  bool intr_uniform_all = false, sinfo_uniform = false;                      // decided by the structure phase: BaView::intr_u over both classes, sinfo_u
-  DBuf<double> comb_uv, comb_info, comb_intr, comb_huber;                    // a stereo graph's rows of both classes in e_pt's order (the gathers' source)
-  DBuf<double> d_pm_ur, d_cm_ur, d_pm_sinfo, d_cm_sinfo;
-  DBuf<int> d_pm_kind, d_cm_kind;
-  DBuf<int> d_src;                   // device copy of slot_src (the gathers of the structure phase)
-  std::unique_ptr<int[]> slot_src;   // point-major slot -> caller edge (uninitialised storage with head room: kept across structure phases)
-  size_t slot_src_cap = 0; int slot_src_n = 0;
-  std::vector<int> ce_cam, ce_cub;
-  bool structure_dirty = true;
-  // device buffers
-  DBuf<double> cams, points, cubes, cams_bak, points_bak, cubes_bak;
-  DBuf<int> d_cam_col, d_cub_col, d_pt_free;
-  DBuf<int> pm_pt, pm_cam, pt_ptr, cm_pm, cm_pt, cam_ptr;
-  DBuf<double> pm_uv, pm_info, pm_intr, pm_huber, cm_uv, cm_info, cm_intr, cm_huber;
-  DBuf<int> d_ce_cam, d_ce_cub, d_oe_i, d_oe_j, d_ce_active, d_oe_active;
-  DBuf<double> ce_meas, ce_info, ce_Hcc, ce_Hoo, ce_Hco, ce_bc, ce_bo, oe_meas, oe_info, oe_Hii, oe_Hjj, oe_Hij, oe_bi, oe_bj;
-  DBuf<int> cam_ce_ptr, cam_ce_idx, cam_oei_ptr, cam_oei_idx, cam_oej_ptr, cam_oej_idx, cub_ce_ptr, cub_ce_idx;
-  DBuf<double> Hcam, bcam, Hcub, bcub, Hll, bl, W, WD, Dinv, dbl, S, rhs, xl, chi_partial, band_linv, scale_partial;
-  DBuf<int> pair_ptr, pair_i1, pair_i2, ent_a, ent_b;
-  // fused Schur schedule (BaView::fused)
-  bool fused = false;
-  int n_seg = 0, n_gpairs = 0, seg_class[5] = {0, 0, 0, 0, 0};
-  DBuf<int> d_run_lm, d_seg_ptr, d_seg_k, d_seg_tile, d_seg_slot, d_gp_ptr, d_gp_i1, d_gp_i2, d_gtile, d_gcam_ptr, d_gslot;
-  DBuf<int> d_run_e0, d_seg_cam;     // round 6: a run entry's first point-major edge (= pt_ptr[run_lm]) and a segment slot's camera (= pm_cam of the segment's first landmark): two dependent loads less at the head of ba_lin_schur_kernel
-  DBuf<double> part_tiles, part_coef;
-  DBuf<rocblas_int> d_info;
-  DBuf<int> d_band_info;
-  int n_pairs = 0, nb_chi = 1, n_chi_partials = 1;
-  long long schur_entries = 0;
-  // the projection edges' payload (88 bytes per edge) goes straight to the device when the edges are set, in the caller's order;
-  // the structure phase permutes it there (ba_gather_rows_kernel)
-  DBuf<double> raw_uv, raw_info, raw_intr, raw_huber;
-  // every projection edge with the same information matrix / intrinsics (decided by comparing the caller's records when they are set or
-  // appended): the kernels then read these 4 + 4 doubles instead of the per-edge records (BaView::info_u / intr_u).  CS_BA_UNIFORM=0: never.
-  bool info_uniform = false, intr_uniform = false;
-  // the per-edge records are not stored while every edge carries the handle's reference record (uni8): 64 bytes per edge that no kernel would
-  // read -- a third of a C4 problem's upload; they are written out from the reference record the moment an appended edge brings another one
-  bool raw_info_virtual = false, raw_intr_virtual = false;
-  double uni8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  DBuf<double> d_uni;
-  bool have_huber = false;
-  // robust kernels (cs_ba_set_robust_kernels; cs_robust.h): kinds per edge in the caller's order, empty = none of the class has one.
-  // The projection edges' deltas live in raw_huber (Huber is the fast path: kinds all 0 / 1 -> no kind array on the device).
-  std::vector<int> rk_proj;
-  DBuf<int> d_pm_rk, d_cm_rk, d_ce_rk, d_oe_rk;
-  DBuf<double> d_ce_rdelta, d_oe_rdelta;
-  int rk_off = 0;                    // cs_ba_set_kernels_enabled: bit (1 << cs_edge_class) set = the class's kernels are switched off (BaView::rk_off)
-  // Edge levels (OptimizableGraph::Edge::setLevel; cs_ba_set_edge_levels / cs_ba_classify_edges).  The master copy per class, in the caller's edge
-  // order; empty = every edge of the class at level 0.  On the device a projection edge's level is the sign of its width record in both edge orders
-  // (ba_kernels.hip: edge_off) plus d_lvl, one byte per edge in e_pt's order (mono edges, then stereo), which exists only once a level may be 1; a
-  // cuboid / odometry edge's level is folded into d_ce_active / d_oe_active (h_ce_shard / h_oe_shard keep the sharding's own words).
-  // lvl_host_stale: cs_ba_classify_edges wrote d_lvl on the device and the host vectors have not been refreshed from it yet.
-  std::vector<unsigned char> lvl_mono, lvl_stereo;      // (the pose classes' levels: ec[].lvl)
-  DBuf<unsigned char> d_lvl;
-  bool lvl_on_device = false, lvl_host_stale = false;
-  int lvl_nM = 0, lvl_nS = 0;        // d_lvl's layout: the class counts of the structure phase that filled it
-  std::vector<int> h_ce_shard, h_oe_shard;
-  DBuf<int> d_pm_cm, d_cls_counts;   // point-major -> camera-major slot (the inverse of cm_pm, built for the first classification of a structure); [mono, stereo] outlier counters
-  bool pm_cm_valid = false;
-  DBuf<double> d_cls_chi;            // the classification's per-edge plain chi2, when the caller asks for it
-  // external (host-evaluated) edges: the coupling pattern of the binary ones (structure), the terms of the current linearisation
-  int ext_n = 0;
-  std::vector<int> ext_e4;                       // (class_i, idx_i, class_j, idx_j) per edge; idx_j < 0: unary
-  DBuf<int> d_ext_e4, d_ext_order, d_ext_gptr;   // (+ the binary ones grouped by destination pair: ba_ext_offdiag_kernel)
-  int ext_groups = 0;
-  DBuf<double> ext_cam36, ext_cam6, ext_cub81, ext_cub9, ext_pt9, ext_pt3, ext_Hij;
-  std::vector<double> h_ext_Hij;                 // host copy (cs_ba_get_system's dense H_pp)
-  bool ext_has_cam = false, ext_has_cub = false, ext_has_pt = false, ext_terms_set = false;
-  double ext_chi2 = 0;
-  cs_external_fn ext_fn = nullptr; void* ext_ctx = nullptr;
-  // last solution / rhs on the host (for LM's scale term and for inspection)
-  std::vector<double> h_b, h_x;
-  // The linear system in device memory is ONE linearisation of the current graph: set by build_system_device, cleared by the structure phase, by new
-  // estimates or external terms, and by every optimize call that ran an iteration (what that leaves behind is blocks of up to three states: H_pl of
-  // its first iteration, pose blocks of the speculated linearisation, landmark blocks of the trial before).
-  bool have_system = false;
-  // cams_bak / points_bak / cubes_bak hold what cs_ba_push saved (one level).  Dead after the structure phase, cs_ba_set_estimates, an optimize call
-  // that ran an iteration (its update kernel saves every trial's estimates there) and after cs_ba_pop has restored it.
-  bool backup_live = false;
-  cs_ba_timing tm{};
-  cs::BaView view{};
-};
-
-
-namespace {
-
 using cs::cam_rank;
 using cs::landmark_owners;
 using cs::run_items;
 using cs::struct_threads;
-
-// `call` returns a CS_* code: pass a failure on
-#define CS_TRY(call) do { if (int _rc = (call)) return _rc; } while (0)
 
 // The per-landmark camera lists of the last structure phase (st_cams_of / st_edge_of, st_cam_cnt) stay valid only while the projection edges
 // [0, st_lists_edges) and the landmark count they were built for are untouched -- cs_ba_append_* only adds behind them.  EVERY entry point that
@@ -839,6 +501,8 @@ void fill_view(cs_ba* B, int E, int nM, int nS) {
   v.chi_partial = B->chi_partial.p;
 }
 
+}  // namespace
+
 // The structure phase: the passes of ba_structure.h in order, everything for the device queued on B->st, one wait at the end.
 int finalize_structure(cs_ba* B) {
   if (!B->structure_dirty) return CS_OK;
@@ -1021,340 +685,10 @@ int finalize_structure(cs_ba* B) {
   return CS_OK;
 }
 
-}  // namespace
-static void debug_nan_scan(cs_ba* B, const char* where);
-static bool debug_nan_enabled();
-namespace {
-
-int chi2_device(cs_ba* B, double* chi) {
-  cs::ba_launch_chi2(B->view, B->nb_chi, B->st);
-  CS_HIP_TRY(hipGetLastError());
-  std::vector<double> part(B->n_chi_partials);
-  CS_HIP_TRY(hipMemcpyAsync(part.data(), B->chi_partial.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
-  double s = 0;
-  for (double p : part) s += p;  // fixed order
-  *chi = s;
-  return CS_OK;
-}
-
-// b (poses then landmarks) to the host: LM's scale term needs it (optimization_algorithm_levenberg.cpp:182-189)
-int fetch_b(cs_ba* B) {
-  B->h_b.assign(B->n_pose + 3 * (size_t)B->n_lm, 0.0);
-  std::vector<double> bc(6 * (size_t)B->nc), bo(9 * (size_t)B->no), bl(3 * (size_t)B->np);
-  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(bc.data(), B->bcam.p, 8 * bc.size(), hipMemcpyDeviceToHost, B->st));
-  if (B->no) CS_HIP_TRY(hipMemcpyAsync(bo.data(), B->bcub.p, 8 * bo.size(), hipMemcpyDeviceToHost, B->st));
-  if (B->np) CS_HIP_TRY(hipMemcpyAsync(bl.data(), B->bl.p, 8 * bl.size(), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
-  for (int i = 0; i < B->nc; i++) if (B->cam_col[i] >= 0) std::memcpy(&B->h_b[B->cam_col[i]], &bc[6 * (size_t)i], 48);
-  for (int i = 0; i < B->no; i++) if (B->cub_col[i] >= 0) std::memcpy(&B->h_b[B->cub_col[i]], &bo[9 * (size_t)i], 72);
-  for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) std::memcpy(&B->h_b[B->n_pose + 3 * (size_t)B->pt_lm[i]], &bl[3 * (size_t)i], 24);
-  return CS_OK;
-}
-
-int fetch_x(cs_ba* B) {
-  B->h_x.assign(B->n_pose + 3 * (size_t)B->n_lm, 0.0);
-  std::vector<double> xl(3 * (size_t)B->np);
-  if (B->n_pose) CS_HIP_TRY(hipMemcpyAsync(B->h_x.data(), B->view.rhs, 8 * (size_t)B->n_pose, hipMemcpyDeviceToHost, B->st));
-  if (B->np) CS_HIP_TRY(hipMemcpyAsync(xl.data(), B->xl.p, 8 * xl.size(), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
-  for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) std::memcpy(&B->h_x[B->n_pose + 3 * (size_t)B->pt_lm[i]], &xl[3 * (size_t)i], 24);
-  return CS_OK;
-}
-
-// phase times come from events read after the next stream synchronisation, so that no phase boundary stalls the host
-int collect_lin_time(cs_ba* B) {
-  if (!B->stage_timing) { B->lin_pending = false; return CS_OK; }
-  if (!B->lin_pending) return CS_OK;
-  float ms = 0;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[0], B->ev[1]));
-  B->tm.linearize_ms += ms;
-  B->lin_pending = false;
-  return CS_OK;
-}
-
-int build_system_device(cs_ba* B, hipEvent_t ev_pre = nullptr) {
-  BA_MARK(B, B->ev[0]);
-  cs::ba_launch_linearize(B->view, B->st, B->st2, B->ev_fork, B->ev_join, B->st3, B->ev_join3, ev_pre);
-  if (B->ext_terms_set) {
-    if (B->ext_cam36.n != 36 * (size_t)B->nc || B->ext_cub81.n != 81 * (size_t)B->no || B->ext_pt9.n != 9 * (size_t)B->np) { cs_set_error("external terms were set for a graph of another size: call cs_ba_set_external_terms again"); return CS_ERR_INVALID_ARG; }
-    cs::ba_launch_ext_add(B->view, B->ext_has_cam ? B->ext_cam36.p : nullptr, B->ext_cam6.p, B->ext_has_cub ? B->ext_cub81.p : nullptr, B->ext_cub9.p,
-                          B->ext_has_pt ? B->ext_pt9.p : nullptr, B->ext_pt3.p, B->st);
-  }
-  CS_HIP_TRY(hipGetLastError());
-  BA_MARK(B, B->ev[1]);
-  B->lin_pending = true;
-  B->tm.n_linearizations++;
-  B->have_system = true;
-  return CS_OK;
-}
-
-// setLambda + solve + restoreDiagonal (block_solver.hpp:353-486, :563-604): lambda is applied while the
-// reduced system is assembled, so the stored blocks are never modified and nothing needs restoring.
-// The banded factorisation is a persistent kernel whose workgroups wait for each other: all of them must be resident.
-// One such kernel fits many times over, but an unbounded number of concurrent solves (handles on different streams of
-// one process) would not; they take turns.
-static std::mutex& g_coop_mutex = cs::coop_mutex();   // (cs_hip_util.h: the pose-graph handle's sparse solve takes the same turn)
-// The turn is held across the collectives of a trial when they are queued on the stream (RCCL): two communicator handles in one
+// The persistent solver kernels' turn (ba_lm.cpp) is held across the collectives of a trial when they are queued on the stream (RCCL): two communicator handles in one
 // process would wait for each other (one holds the turn inside a collective, the other needs the turn to enqueue its side).  One
 // process per GPU is the contract; cs_ba_comm_init enforces it.
 static std::atomic<int> g_comm_handles{0};
-
-// phase times of the last solve, read once the stream has been synchronised
-int collect_solve_times(cs_ba* B) {
-  if (!B->stage_timing) { B->lin_pending = false; return CS_OK; }
-  float ms = 0;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[2], B->ev[3])); B->tm.reduce_ms += ms;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[3], B->ev[4])); B->tm.factor_ms += ms;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[4], B->ev[5])); B->tm.backsub_ms += ms;
-  if (B->sep_mode && B->shard_n > 1) {
-    hipEvent_t seq[6] = {B->ev[3], B->sev[0], B->sev[1], B->sev[2], B->sev[3], B->ev[4]};
-    for (int i = 0; i < 5; i++) { CS_HIP_TRY(hipEventElapsedTime(&ms, seq[i], seq[i + 1])); B->sep_ms[i] += ms; }
-  }
-  return collect_lin_time(B);
-}
-
-// collectives of the sharded solve: RCCL on the handle's stream (queued, no host round trip), or the caller's callback (which is
-// host-synchronous: the stream is drained first)
-int coll_allreduce(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* d, size_t n) {
-  if (fn) {
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, d, n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
-  } else if (B->comm) {
-    BA_NCCL(ncclAllReduce(d, d, n, ncclDouble, ncclSum, B->comm, B->st));
-  }
-  return CS_OK;
-}
-// in place: rank r's part sits at buf + r * per_rank.  Through the callback an all-gather is the sum of the zero-padded buffers
-// (the caller zeroes the other ranks' slots first).
-int coll_allgather(cs_ba* B, cs_allreduce_fn fn, void* ctx, double* buf, size_t per_rank) {
-  if (fn) {
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (fn(ctx, buf, per_rank * (size_t)B->shard_n, 1, 0) != 0) { cs_set_error("all-reduce callback failed"); return CS_ERR_HIP; }
-  } else if (B->comm) {
-    BA_NCCL(ncclAllGather(buf + (size_t)B->shard_rank * per_rank, buf, per_rank, ncclDouble, B->comm, B->st));
-  }
-  return CS_OK;
-}
-
-// Sharded with the cuboids eliminated: a cuboid's increment is computed by the rank that owns it (zero elsewhere); every rank updates
-// all vertices, so the increments (9 doubles per free cuboid, behind the reduced system's in `rhs`) are summed over the ranks.
-int share_cuboid_increments(cs_ba* B, cs_allreduce_fn fn, void* ctx) {
-  if (!B->elim || B->shard_n <= 1 || B->n_pose <= B->n_red) return CS_OK;
-  return coll_allreduce(B, fn, ctx, B->view.rhs + B->n_red, (size_t)(B->n_pose - B->n_red));
-}
-
-// A workgroup of a persistent factorisation waited ~1 s for its team (band_wait_ge): the device is shared with another persistent kernel.
-// h_status[0]: the band's / the interior's word; with_sep: h_status[2], the separator system's, counts too.
-int check_band_timeout(const cs_ba* B, bool with_sep) {
-  if (B->h_status[0] != cs::BAND_TIMEOUT_INFO && !(with_sep && B->h_status[2] == cs::BAND_TIMEOUT_INFO)) return CS_OK;
-  cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device");
-  return CS_ERR_HIP;
-}
-
-// defer != nullptr (banded path only): everything is queued and the function returns WITHOUT synchronising; *defer then holds the
-// persistent-kernel turn, and the caller synchronises, reads *h_status, calls collect_solve_times() and releases the turn.
-// lambda of the damped solve that is about to be queued: into the pinned word and, queued on the stream, into device memory.  (Inside a
-// captured trial the copy is a node of the graph: every replay reads whatever the host left in h_lam.)
-int put_lambda(cs_ba* B, double lambda) {
-  B->h_lam[0] = lambda;
-  B->h_lam[1] = B->shard_rank == 0 ? lambda : 0.0;      // x^T (lambda x + b): the poses' lambda x^2 is counted once, on rank 0
-  CS_HIP_TRY(hipMemcpyAsync(B->d_lam.p, B->h_lam, 2 * sizeof(double), hipMemcpyHostToDevice, B->st));
-  return CS_OK;
-}
-int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void* ctx, std::unique_lock<std::mutex>* defer);
-
-int solve_device(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn = nullptr, void* ctx = nullptr, std::unique_lock<std::mutex>* defer = nullptr) {
-  const int n = B->n_red;
-  *ok = true;
-  if (B->sep_mode && B->shard_n > 1) return solve_device_sep(B, lambda, ok, fn, ctx, defer);
-  if (n > 0) {
-    const bool lean_head = B->band_ld > 0 && !B->sparse;      // (banded path: one prologue kernel instead of a copy and three fills)
-    // (the prologue's launch is ba_launch_reduce's when nothing reads the phase marks and no host-evaluated edge writes S in between: it then
-    // runs on the side stream, beside the landmark segments -- BaSidePrologue)
-    cs::BaSidePrologue side_pro{};
-    const bool pro_in_reduce = lean_head && defer != nullptr && !B->stage_timing && B->shard_n == 1 && !(B->ext_n > 0 && B->ext_terms_set);
-    if (lean_head) {
-      B->h_lam[0] = lambda; B->h_lam[1] = B->shard_rank == 0 ? lambda : 0.0;
-      side_pro = cs::BaSidePrologue{B->d_lam.p, B->h_lam[0], B->h_lam[1], B->d_band_info.p, B->d_elim_fail.p, B->S.p, B->s_doubles + (size_t)B->n_pose};
-      if (!pro_in_reduce) cs::ba_launch_trial_prologue(B->d_lam.p, B->h_lam[0], B->h_lam[1], B->d_band_info.p, B->d_elim_fail.p, B->S.p, B->s_doubles + (size_t)B->n_pose, B->st);   // (+ [S | rhs] cleared: no fill of its own)
-    } else { int rcl = put_lambda(B, lambda); if (rcl) return rcl; }
-    BA_MARK(B, B->ev[2]);
-    if (lean_head) {
-    } else if (B->sparse && B->S_clean) {
-      // (sparse path: S was cleared by the structure phase and only the plan's pattern is ever written -- the pattern and the right-hand side)
-      cs::launch_sparse_zero_pattern(B->solver.view(B->S.p, B->view.rhs, n), B->S.p, B->st);
-      CS_HIP_TRY(hipMemsetAsync(B->S.p + B->s_doubles, 0, sizeof(double) * B->n_pose, B->st));
-    } else {
-      CS_HIP_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
-      B->S_clean = B->sparse;
-    }
-    if (!lean_head) CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
-    cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join, pro_in_reduce ? &side_pro : nullptr);
-    if (B->ext_n > 0 && B->ext_terms_set) cs::ba_launch_ext_offdiag(B->view, B->ext_groups, B->d_ext_gptr.p, B->d_ext_order.p, B->d_ext_e4.p, B->ext_Hij.p, B->st);
-    // (block cyclic reduction in a deferred trial: no kernel of it waits for another -- no time-out word to read --, and the two failure words
-    // reach the host folded into the trial's scalars by the caller's sum kernel: the two 4-byte copies, a blit launch each, stay away)
-    const bool status_in_scalars = defer != nullptr && B->band_ld > 0 && B->use_bcr;
-    if (status_in_scalars) { B->h_status[0] = 0; B->h_status[1] = 0; }
-    else CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-    CS_HIP_TRY(hipGetLastError());
-    if ((fn && B->shard_n > 1) || (!fn && B->comm)) {  // sum the ranks' partial reduced systems: [S | rhs] in one message
-      int rc2 = coll_allreduce(B, fn, ctx, B->S.p, B->s_doubles + B->n_pose); if (rc2) return rc2;
-    }
-    BA_MARK(B, B->ev[3]);
-    if (B->band_ld) {
-      // banded: factorisation, both substitutions and the landmark back-substitution are queued back to back; the
-      // pivot flag comes home with the single synchronisation (a failed factorisation just leaves garbage increments
-      // that the caller discards)
-      std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-      if (B->use_bcr) cs::ba_launch_bcr(B->S.p, B->band_linv.p, n, B->band_ld, 128, B->view.rhs, B->d_band_info.p, B->st);
-      else cs::ba_launch_band_cholesky(B->S.p, B->band_linv.p, n, B->band_ld, B->view.rhs, B->d_band_info.p, true, B->st);
-      CS_HIP_TRY(hipGetLastError());
-      BA_MARK(B, B->ev[4]);
-      // (Round 5 tried clearing the band for the NEXT trial on the side stream here -- block cyclic reduction is done with it after its first
-      // level -- to take the 10 us fill off the head of a trial: the event record / wait / fill / record sequence stalled the host's enqueue of the
-      // kernels behind it by 35-60 us each, profiles/r5_ba_timeline_prezero.txt; the fill stays at the head.)
-      cs::ba_launch_backsub(B->view, B->st);
-      CS_HIP_TRY(hipGetLastError());
-      if (fn && B->elim && B->shard_n > 1) {   // the callback waits for the other ranks: the persistent kernel's turn must be free by then
-        CS_HIP_TRY(hipStreamSynchronize(B->st));
-        coop_turn.unlock();
-      }
-      { int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
-      BA_MARK(B, B->ev[5]);
-      if (!status_in_scalars) CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_band_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-      if (defer) { *defer = std::move(coop_turn); B->tm.n_solves++; return CS_OK; }   // (the caller's sum kernel folds the two status words into the trial's scalars)
-      cs::ba_launch_fail_flag(B->d_band_info.p, B->d_elim_fail.p, nullptr, B->d_scalars.p + 2, B->st);
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-      { int rc2 = check_band_timeout(B, false); if (rc2) return rc2; }
-      if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
-    } else if (B->sparse) {
-      // general sparse: the pattern's blocks are gathered from the dense S by the factorisation itself (sparse_kernels.hip)
-      std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-      const cs::SparseSolver& sv = B->solver; const int rs = B->solver.solve(B->blas, B->S.p, B->view.rhs, n, B->st);
-      if (rs == cs::SparseSolver::CHOL_NOT_LAUNCHED) { cs_set_error("sparse solver: the factorisation could not be launched (grid " + std::to_string(sv.grids.chol) + " for " + std::to_string(sv.plan.N) + " vertices)"); return CS_ERR_HIP; }
-      if (rs == cs::SparseSolver::BACK_NOT_LAUNCHED) { cs_set_error("sparse solver: the substitution could not be launched (grid " + std::to_string(sv.grids.back) + " for " + std::to_string(sv.plan.N) + " vertices)"); return CS_ERR_HIP; }
-      if (rs) return rs;
-      BA_MARK(B, B->ev[4]);
-      cs::ba_launch_backsub(B->view, B->st);
-      CS_HIP_TRY(hipGetLastError());
-      { int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
-      BA_MARK(B, B->ev[5]);
-      { int rc2 = B->solver.queue_status(B->h_status + 2, B->st); if (rc2) return rc2; }
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-      const cs::SparseVerdict verdict = cs::sparse_verdict(B->h_status + 2);     // (the factorisation's word and the dense tail's pivot)
-      if (verdict == cs::SPARSE_TIMEOUT) {
-        cs_set_error("sparse solver: grid not co-resident (wait timed out); set CS_BA_SPARSE=0 on a shared device");
-        return CS_ERR_HIP;
-      }
-      if (verdict != cs::SPARSE_OK || B->h_status[1] != 0) *ok = false;
-    } else {
-      // dense: the lower triangle of the row-major S is the upper triangle of the column-major matrix rocSOLVER sees
-      CS_ROC_TRY(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, B->S.p, n, B->d_info.p));
-      CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-      if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
-      else CS_ROC_TRY(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, 1, B->S.p, n, B->view.rhs, n));
-      BA_MARK(B, B->ev[4]);
-      // (sharded: the collective is issued whether or not THIS rank's factorisation went through -- the ranks decide together, below)
-      if (*ok || B->shard_n > 1) { cs::ba_launch_backsub(B->view, B->st); CS_HIP_TRY(hipGetLastError()); int rc2 = share_cuboid_increments(B, fn, ctx); if (rc2) return rc2; }
-      BA_MARK(B, B->ev[5]);
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-    }
-    int rc = collect_solve_times(B); if (rc) return rc;
-  }
-  B->tm.n_solves++;
-  return CS_OK;
-}
-
-// The damped solve in separator mode (cs_ba::sep_mode; kernels: "sharded reduced solve" in band_kernels.hip).  What is built here lies
-// in this rank's columns and in the next separator's diagonal block; only the interior is factorised here.  Collectives per solve:
-// one all-gather of the separator messages (3 w^2 + 2 w doubles per rank) and one all-reduce of the solution vector (n_pose doubles:
-// every rank contributes its interior's increments and those of the cuboids it eliminated).  block_solver.hpp:385-485 for what a
-// shard builds and solves.
-int solve_device_sep(cs_ba* B, double lambda, bool* ok, cs_allreduce_fn fn, void* ctx, std::unique_lock<std::mutex>* defer) {
-  *ok = true;
-  // Without a collective the separator system would be assembled from the other ranks' stale / zero messages and "solve" to a
-  // meaningless x that reports positive_definite = 1 (the low-level path cs_ba_solve -> solve_device has neither callback nor, possibly,
-  // a communicator).  A sharded handle solves only through cs_ba_optimize_sharded or after cs_ba_comm_init.
-  if (!fn && !B->comm) { cs_set_error("sharded handle in separator mode: the damped solve needs the ranks' separator messages -- use cs_ba_optimize_sharded (callback) or cs_ba_comm_init (RCCL); cs_ba_solve alone cannot"); return CS_ERR_INVALID_ARG; }
-  const int R = B->shard_n, LD = B->band_ld, ns = B->n_sep;
-  double* rhs = B->view.rhs;
-  const int LDs = 2 * B->w_max;
-  double* rsep = B->sepS.p + (size_t)ns * LDs;
-  { int rcl = put_lambda(B, lambda); if (rcl) return rcl; }
-  BA_MARK(B, B->ev[2]);
-  CS_HIP_TRY(hipMemsetAsync(B->S.p, 0, sizeof(double) * (B->s_doubles + B->n_pose), B->st));
-  CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
-  if (fn) CS_HIP_TRY(hipMemsetAsync(B->sep_msgs.p, 0, sizeof(double) * B->msg_doubles * (size_t)R, B->st));
-  cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join);
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipGetLastError());
-  BA_MARK(B, B->ev[3]);
-  std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
-  CS_HIP_TRY(hipMemsetAsync(B->d_int_info.p, 0, cs::BAND_INFO_WORDS * sizeof(int), B->st));
-  // the interior: L L^T = S(I, I), y = L^-1 b_I in place (one-sided order, right-hand side riding along)
-  cs::ba_launch_band_cholesky(B->S.p + (size_t)B->int_c * LD, B->int_work.p, B->int_n, LD, rhs + B->int_c, B->d_int_info.p, false, B->st, true);
-  CS_HIP_TRY(hipGetLastError());
-  BA_MARK(B, B->sev[0]);
-  if (fn) {   // the callback waits for the other ranks (threads of this process in the tests): the persistent kernel's turn must be free by then
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    coop_turn.unlock();
-  }
-  cs::ba_launch_sep_reduce(B->S.p, LD, B->int_work.p, B->int_c, B->int_n, B->zl, B->wl, B->zr, B->wr, B->sepY.p, rhs, B->sep_msgs.p + (size_t)B->shard_rank * B->msg_doubles, B->w_max, B->st);
-  CS_HIP_TRY(hipGetLastError());
-  BA_MARK(B, B->sev[1]);
-  { int rc = coll_allgather(B, fn, ctx, B->sep_msgs.p, B->msg_doubles); if (rc) return rc; }
-  BA_MARK(B, B->sev[2]);
-  // every rank assembles and solves the (small) separator system: nothing to broadcast afterwards.  Block tridiagonal = a band of
-  // 2 w_max: the persistent banded Cholesky again (two fronts at 7 separators: 18 dependent steps)
-  if (cs::ba_bcr_sep_ok(B->w_max, R)) {
-    // ... by block cyclic reduction, straight from the messages' blocks (bcr_kernels.hip): 7 separators = 3 levels instead of 18 dependent steps
-    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, cs::BAND_INFO_WORDS * sizeof(int), B->st));
-    cs::ba_launch_bcr_sep(B->sep_msgs.p, B->msg_doubles, B->w_max, R, B->d_sep_off.p, B->d_sep_col.p, ns, B->sep_work.p, rhs, B->d_sep_info.p, B->st);
-    CS_HIP_TRY(hipGetLastError());
-  } else {
-    cs::ba_launch_sep_assemble(B->sep_msgs.p, B->msg_doubles, B->w_max, R, B->d_sep_off.p, ns, LDs, B->sepS.p, rsep, B->st);
-    CS_HIP_TRY(hipGetLastError());
-    if (!coop_turn.owns_lock()) coop_turn.lock();
-    CS_HIP_TRY(hipMemsetAsync(B->d_sep_info.p, 0, cs::BAND_INFO_WORDS * sizeof(int), B->st));
-    cs::ba_launch_band_cholesky(B->sepS.p, B->sep_work.p, ns, LDs, rsep, B->d_sep_info.p, true, B->st);
-    CS_HIP_TRY(hipGetLastError());
-    if (fn) {
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-      coop_turn.unlock();
-    }
-    cs::ba_launch_sep_scatter(rsep, ns, R, B->d_sep_off.p, B->d_sep_col.p, rhs, B->st);
-  }
-  BA_MARK(B, B->sev[3]);
-  cs::ba_launch_sep_backsolve(B->S.p, LD, B->int_work.p, B->int_c, B->int_n, B->zl, B->wl, B->zr, B->wr, B->sepY.p, rhs, B->d_int_info.p, B->st);
-  CS_HIP_TRY(hipGetLastError());
-  BA_MARK(B, B->ev[4]);
-  cs::ba_launch_backsub(B->view, B->st);   // this rank's landmarks and cuboids see its own columns and the next separator only
-  CS_HIP_TRY(hipGetLastError());
-  // the solution vector: every rank contributes ITS columns (its separator as it solved it, its interior) and its cuboids' increments
-  // behind the reduced system, zeros elsewhere -- every entry then has one source, so all ranks end with the same bits
-  if (B->zl > 0) CS_HIP_TRY(hipMemsetAsync(rhs, 0, sizeof(double) * (size_t)B->zl, B->st));
-  if (B->int_c + B->int_n < B->n_red) CS_HIP_TRY(hipMemsetAsync(rhs + B->int_c + B->int_n, 0, sizeof(double) * (size_t)(B->n_red - B->int_c - B->int_n), B->st));
-  { int rc = coll_allreduce(B, fn, ctx, rhs, (size_t)B->n_pose); if (rc) return rc; }
-  BA_MARK(B, B->ev[5]);
-  cs::ba_launch_fail_flag(B->d_int_info.p, B->d_elim_fail.p, B->d_sep_info.p, B->d_scalars.p + 2, B->st);
-  // both persistent factorisations of the trial report their own time-out (a team that was not co-resident): the interior's and the
-  // separator system's -- the latter must not be mistaken for "not positive definite" (LM would raise lambda and retry, ~1 s a trial)
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_int_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status + 2, B->d_sep_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipGetLastError());
-  B->tm.n_solves++;
-  if (defer) { if (coop_turn.owns_lock()) *defer = std::move(coop_turn); return CS_OK; }
-  CS_HIP_TRY(hipMemcpyAsync(B->h_scalars + 2, B->d_scalars.p + 2, sizeof(double), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
-  if (coop_turn.owns_lock()) coop_turn.unlock();
-  { int rc = check_band_timeout(B, true); if (rc) return rc; }
-  if (B->h_scalars[2] != 0.0) *ok = false;
-  return collect_solve_times(B);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -1778,7 +1112,6 @@ int cs_ba_set_robust_kernels(cs_ba* B, int edge_class, int n, const int* kind, c
   CS_GUARD_END("cs_ba_set_robust_kernels")
 }
 
-static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap);
 // ---- edge levels, kernels switched in place, classification, rounds: ORB-SLAM2's LocalBundleAdjustment / BundleAdjustment on the device ----------
 static int levels_refuse_shard(const cs_ba* B, const char* who) {
   if (B->shard_n <= 1) return CS_OK;
@@ -1910,117 +1243,6 @@ int cs_ba_optimize_rounds(cs_ba* B, const cs_ba_round* rounds, int n_rounds, int
   CS_GUARD_END("cs_ba_optimize_rounds")
 }
 
-static int cs_ba_compute_errors_impl(cs_ba* B, double* chi2) {
-  if (!B || !chi2) return CS_ERR_INVALID_ARG;
-  CS_HIP_TRY(hipSetDevice(B->device));
-  int rc = finalize_structure(B); if (rc) return rc;
-  double t0 = now_ms();
-  rc = chi2_device(B, chi2);
-  if (B->ext_terms_set) *chi2 += B->ext_chi2;      // the host-evaluated edges' share (cs_ba_set_external_terms / _chi2)
-  B->tm.errors_ms += now_ms() - t0;
-  return rc;
-}
-int cs_ba_compute_errors(cs_ba* B, double* chi2) {
-  CS_GUARD_BEGIN
-  return cs_ba_compute_errors_impl(B, chi2);
-  CS_GUARD_END("cs_ba_compute_errors")
-}
-
-static int cs_ba_build_system_impl(cs_ba* B) {
-  if (!B) return CS_ERR_INVALID_ARG;
-  CS_HIP_TRY(hipSetDevice(B->device));
-  int rc = finalize_structure(B); if (rc) return rc;
-  rc = build_system_device(B); if (rc) return rc;
-  rc = fetch_b(B); if (rc) return rc;
-  debug_nan_scan(B, "after cs_ba_build_system");
-  return CS_OK;
-}
-int cs_ba_build_system(cs_ba* B) {
-  CS_GUARD_BEGIN
-  return cs_ba_build_system_impl(B);
-  CS_GUARD_END("cs_ba_build_system")
-}
-
-// The guard of every call that reads the linear system (see cs_ba::have_system).
-static int need_system(cs_ba* B, const char* who) {
-  if (!B->structure_dirty && B->have_system) return CS_OK;
-  cs_set_error(std::string(who) + ": no linear system on the handle (none was built, or the graph, the estimates or the external terms changed, or cs_ba_optimize ran "
-               "since): call cs_ba_compute_errors + cs_ba_build_system first");
-  return CS_ERR_NOT_RUN;
-}
-
-static int cs_ba_solve_impl(cs_ba* B, double lambda, int* pd) {
-  if (!B) return CS_ERR_INVALID_ARG;
-  CS_HIP_TRY(hipSetDevice(B->device));
-  if (int rn = need_system(B, "cs_ba_solve")) return rn;
-  bool ok = false;
-  int rc = solve_device(B, lambda, &ok); if (rc) return rc;
-  if (ok) debug_nan_scan(B, "after cs_ba_solve");
-  if (pd) *pd = ok ? 1 : 0;
-  return ok ? fetch_x(B) : CS_OK;
-}
-int cs_ba_solve(cs_ba* B, double lambda, int* pd) {
-  CS_GUARD_BEGIN
-  return cs_ba_solve_impl(B, lambda, pd);
-  CS_GUARD_END("cs_ba_solve")
-}
-
-int cs_ba_update(cs_ba* B) {
-  if (!B) return CS_ERR_INVALID_ARG;
-  CS_GUARD_BEGIN
-  if (int rn = need_system(B, "cs_ba_update (no solution to apply; cs_ba_solve comes after them)")) return rn;
-  CS_HIP_TRY(hipSetDevice(B->device));
-  double t0 = now_ms();
-  cs::ba_launch_update(B->view, B->st);
-  CS_HIP_TRY(hipGetLastError());
-  CS_HIP_TRY(hipStreamSynchronize(B->st));
-  B->tm.update_ms += now_ms() - t0;
-  debug_nan_scan(B, "after cs_ba_update");
-  return CS_OK;
-  CS_GUARD_END("cs_ba_update")
-}
-
-// The estimates into / out of the backup buffers, queued on the handle's stream: what cs_ba_push / cs_ba_pop do once their guards have passed, and
-// what cs_ba_optimize's own trials use (its rollback of a rejected trial is not the caller's pop and goes through no guard).
-static int save_estimates(cs_ba* B) {
-  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams_bak.p, B->cams.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
-  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points_bak.p, B->points.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
-  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes_bak.p, B->cubes.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
-  return CS_OK;
-}
-static int restore_estimates(cs_ba* B) {
-  if (B->nc) CS_HIP_TRY(hipMemcpyAsync(B->cams.p, B->cams_bak.p, 56 * (size_t)B->nc, hipMemcpyDeviceToDevice, B->st));
-  if (B->np) CS_HIP_TRY(hipMemcpyAsync(B->points.p, B->points_bak.p, 24 * (size_t)B->np, hipMemcpyDeviceToDevice, B->st));
-  if (B->no) CS_HIP_TRY(hipMemcpyAsync(B->cubes.p, B->cubes_bak.p, 80 * (size_t)B->no, hipMemcpyDeviceToDevice, B->st));
-  return CS_OK;
-}
-
-int cs_ba_push(cs_ba* B) {
-  if (!B) return CS_ERR_INVALID_ARG;
-  CS_GUARD_BEGIN
-  CS_HIP_TRY(hipSetDevice(B->device));
-  int rc = finalize_structure(B); if (rc) return rc;
-  rc = save_estimates(B); if (rc) return rc;
-  B->backup_live = true;
-  return CS_OK;
-  CS_GUARD_END("cs_ba_push")
-}
-
-int cs_ba_pop(cs_ba* B) {
-  if (!B) return CS_ERR_INVALID_ARG;
-  CS_GUARD_BEGIN
-  if (B->structure_dirty || !B->backup_live) {
-    cs_set_error("cs_ba_pop: no backup to restore (cs_ba_push has not run since the graph changed, since cs_ba_set_estimates, since a cs_ba_optimize call or since the last cs_ba_pop)");
-    return CS_ERR_NOT_RUN;
-  }
-  CS_HIP_TRY(hipSetDevice(B->device));
-  int rc = restore_estimates(B); if (rc) return rc;
-  B->backup_live = false;        // (one level, and spent once restored)
-  return CS_OK;
-  CS_GUARD_END("cs_ba_pop")
-}
-
-// optimization_algorithm_levenberg.cpp:61-163 + sparse_optimizer.cpp:354-419
 int cs_ba_set_shard(cs_ba* B, int rank, int n_ranks) {
   if (!B || n_ranks < 1 || rank < 0 || rank >= n_ranks) return CS_ERR_INVALID_ARG;
   if (B->n_stereo > 0 && n_ranks > 1) { cs_set_error("cs_ba_set_shard: stereo projection edges are not supported on a sharded handle"); return CS_ERR_INVALID_ARG; }
@@ -2038,255 +1260,6 @@ int cs_ba_shard_landmark_owners(int n_ranks, int n_cams, int n_points, int n_pro
   landmark_owners(n_ranks, n_cams, n_points, n_proj, e_pt, e_cam, owner);
   std::copy(owner.begin(), owner.end(), owner_out);
   return CS_OK;
-}
-
-int cs_ba_optimize(cs_ba* B, int iterations, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap) {
-  return cs_ba_optimize_sharded(B, iterations, nullptr, nullptr, iterations_done, chi_hist, lambda_hist, trials_hist, cap);
-}
-
-static int cs_ba_optimize_sharded_impl(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap) {
-  if (!B || iterations < 0) return CS_ERR_INVALID_ARG;
-  if (B->shard_n > 1 && !fn && !B->comm) { cs_set_error("sharded problem needs cs_ba_comm_init() (RCCL) or an all-reduce callback"); return CS_ERR_INVALID_ARG; }
-  const bool cb = fn && B->shard_n > 1;          // collectives through the caller's callback (CPU / gloo tests, ranks as threads)
-  const bool rccl = !fn && B->comm != nullptr;   // collectives issued here, on this handle's stream
-  CS_HIP_TRY(hipSetDevice(B->device));
-  int rc = finalize_structure(B); if (rc) return rc;
-  // host scalars: sum / max over the ranks
-  auto reduce_host = [&](double* v, size_t n, int op) -> int {
-    if (cb) return fn(ctx, v, n, 0, op);
-    if (rccl) {
-      if (n > B->scalars_cap) return 1;
-      std::memcpy(B->h_scalars, v, n * sizeof(double));
-      if (hipMemcpyAsync(B->d_scalars.p, B->h_scalars, n * sizeof(double), hipMemcpyHostToDevice, B->st) != hipSuccess) return 1;
-      if (ncclAllReduce(B->d_scalars.p, B->d_scalars.p, n, ncclDouble, op == 0 ? ncclSum : ncclMax, B->comm, B->st) != ncclSuccess) return 1;
-      if (hipMemcpyAsync(B->h_scalars, B->d_scalars.p, n * sizeof(double), hipMemcpyDeviceToHost, B->st) != hipSuccess) return 1;
-      if (hipStreamSynchronize(B->st) != hipSuccess) return 1;
-      std::memcpy(v, B->h_scalars, n * sizeof(double));
-    }
-    return 0;
-  };
-  // One trial entirely on the stream (banded solver, no callback): damped solve, LM scale term, update, chi2 of the new state and --
-  // sharded -- ONE RCCL all-reduce of the pair [chi2, scale] are queued back to back; the host synchronises once per trial.
-  const bool stream_flow = !cb && B->band_ld > 0 && B->n_red > 0;
-  double t_begin = now_ms();
-  if (B->shard_n > 1) {
-    // every rank decides the solver layout from its own structure phase (and device query): the collectives below only match if
-    // they all decided alike
-    const double q[5] = {(double)B->n_red, (double)B->band_ld, B->elim ? 1.0 : 0.0, B->sep_mode ? 1.0 : 0.0, (double)B->n_sep};
-    double v[10];
-    for (int i = 0; i < 5; i++) { v[i] = q[i]; v[5 + i] = -q[i]; }
-    if (reduce_host(v, 10, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-    for (int i = 0; i < 5; i++)
-      if (v[i] != q[i] || v[5 + i] != -q[i]) { cs_set_error("sharded BA: the ranks disagree on the solver layout (reduced size / bandwidth / cuboid elimination / separator mode); check CS_BA_* environment variables and devices"); return CS_ERR_INVALID_ARG; }
-  }
-  // external (host-evaluated) edges: their terms depend on the state, so the caller's callback re-evaluates them before every
-  // linearisation (want_system = 1: cs_ba_set_external_terms) and after every trial's update (want_system = 0: cs_ba_set_external_chi2)
-  const bool ext_active = B->ext_n > 0 || B->ext_terms_set || B->ext_fn;
-  if (ext_active && !B->ext_fn) { cs_set_error("cs_ba_optimize: the graph has external (host-evaluated) edges but no cs_ba_set_external_callback; drive the stepwise calls instead"); return CS_ERR_NOT_RUN; }
-  auto ext_refresh = [&](int want_system) -> int {
-    if (!ext_active) return CS_OK;
-    CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (B->ext_fn(B->ext_ctx, B, want_system) != 0) { cs_set_error("external-edge callback failed"); return CS_ERR_INVALID_ARG; }
-    if (!B->ext_terms_set) { cs_set_error("external-edge callback did not call cs_ba_set_external_terms"); return CS_ERR_NOT_RUN; }
-    return CS_OK;
-  };
-  const bool fuse_lin_env = [] { const char* e = getenv("CS_BA_FUSE_LIN"); return !e || atoi(e) != 0; }();     // (read per call: the tests hold the two paths to each other in one process)
-  const bool fuse_lin_ok = fuse_lin_env && stream_flow && B->fused && B->shard_n == 1 && !ext_active && B->n_proj > 0 &&
-                           B->n_seg == std::max(std::max(std::max(B->seg_class[0], B->seg_class[1]), std::max(B->seg_class[2], B->seg_class[3])), B->seg_class[4]) &&
-                           getenv("CS_BA_DEBUG_NAN") == nullptr;
-  struct FuseLinGuard { cs_ba* b; ~FuseLinGuard() { b->view.fuse_lin = 0; } } fuse_lin_guard{B};   // (every other entry point linearises with the classic kernels)
-  // Once an iteration has started, whatever way this call returns: no linear system for the stepwise and inspection calls (see cs_ba::have_system), and
-  // the caller's pushed estimates are gone (the trials below save theirs in the same buffers).  Two host flags: nothing is queued for them.
-  struct LeftoverGuard { cs_ba* b; bool ran; ~LeftoverGuard() { if (ran) { b->have_system = false; b->backup_live = false; } } } leftover_guard{B, false};
-  // The NEXT iteration's linearisation is queued right behind a trial, before the host has the trial's verdict: nearly every trial is accepted, and
-  // the ~70 us the host needs to read the scalars, decide and queue again then pass while the device linearises (the timeline showed the device
-  // idle for exactly that long after every trial).  A rejected trial pops the estimates and linearises the restored state once more -- the same
-  // kernels on the same state: the same bits as the system the speculation overwrote.  Off whenever something else must see the stream between
-  // trials: external (host-evaluated) edges, sharded runs, the NaN scans, the stage split's phase marks.
-  const bool can_spec = stream_flow && B->shard_n == 1 && !ext_active && !B->stage_timing && !debug_nan_enabled();
-  bool spec_lin = false;         // this iteration's system is already queued (speculated behind the last iteration's accepted trial)
-  // a trial's scalars straight from its last kernel into pinned memory, polled here (single rank: no collective behind the kernel)
-  const bool direct_scalars = stream_flow && !rccl && B->h_trial != nullptr;
-  auto wait_trial = [&](double seq) -> int {
-    volatile double* h = B->h_trial;
-    const double t_w = now_ms();
-    unsigned spins = 0;
-    while (h[3] != seq) {
-      if ((++spins & 0xfffu) == 0 && now_ms() - t_w > 5000.0) {      // five seconds without the word: ask the runtime what happened
-        CS_HIP_TRY(hipStreamSynchronize(B->st));
-        if (h[3] != seq) { cs_set_error("cs_ba_optimize: the trial's scalars never arrived in pinned memory"); return CS_ERR_HIP; }
-        break;
-      }
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return CS_OK;
-  };
-  cs::LmState lm;      // lambda, ni, the bad-iteration count: the policy is cs_lm.h's (set by the first iteration)
-  int done = 0;
-  double carriedChi = 0;
-  bool have_carried = false;     // chi2 of the current state is known from the previous iteration's last trial
-  for (int it = 0; it < iterations; it++) {
-    leftover_guard.ran = true;
-    double currentChi = 0;
-    double t0 = now_ms();
-    rc = ext_refresh(1); if (rc) return rc;        // (the terms of this iteration's linearisation, and the chi2 share at the current state)
-    if (have_carried) {
-      // computeActiveErrors + activeRobustChi2 at the top of an iteration (:67-69) would re-evaluate the state the last trial left:
-      // the accepted trial's chi2 (same kernels, same state, fixed-shape sums: the same bits), or -- after ten rejections --
-      // the popped state's, which is the previous currentChi
-      currentChi = carriedChi;
-    } else {
-      rc = chi2_device(B, &currentChi); if (rc) return rc;
-      if (ext_active) currentChi += B->ext_chi2;
-      if (reduce_host(&currentChi, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-      B->tm.errors_ms += now_ms() - t0;
-    }
-    double tempChi = currentChi, iniChi = currentChi;
-    // From the second iteration on the landmark side of the projection edges is linearised inside the trial's Schur kernels
-    // (ba_lin_schur_kernel: one pass over the edges, H_pl never read back); the first iteration needs H_ll for lambda's initial value
-    // before any trial.  Same bits either way (CS_BA_FUSE_LIN=0: the classic pair of kernels throughout).
-    B->view.fuse_lin = (it > 0 && fuse_lin_ok) ? 1 : 0;
-    if (!spec_lin) { rc = build_system_device(B); if (rc) return rc; }
-    spec_lin = false;
-    debug_nan_scan(B, "cs_ba_optimize: after the linearisation");
-    if (it == 0 && B->shard_n == 1) {  // computeLambdaInit (:166-180): tau * max |H_jj| over all non-fixed vertices, landmarks included
-      // one rank: the maximum is taken where the blocks are (ba_max_diag_kernel) and eight bytes come back, instead of every H_cc / H_oo / H_ll
-      // block (14 MB at C4, 0.6 ms of every cs_ba_optimize call)
-      CS_HIP_TRY(hipMemsetAsync(B->d_scalars.p, 0, sizeof(double), B->st));
-      cs::ba_launch_max_diag(B->view, B->d_scalars.p, B->st);
-      CS_HIP_TRY(hipGetLastError());
-      CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, sizeof(double), hipMemcpyDeviceToHost, B->st));
-      CS_HIP_TRY(hipStreamSynchronize(B->st));
-      cs::lm_begin(lm, B->user_lambda_init, B->h_scalars[0]);
-    } else if (it == 0) {
-      CS_HIP_TRY(hipStreamSynchronize(B->st));   // the copies below run on the NULL stream, which B->st does not order with
-      std::vector<double> hc(36 * (size_t)B->nc), ho(81 * (size_t)B->no), hl(9 * (size_t)B->np);
-      if (B->nc) CS_HIP_TRY(hipMemcpy(hc.data(), B->Hcam.p, 8 * hc.size(), hipMemcpyDeviceToHost));
-      if (B->no) CS_HIP_TRY(hipMemcpy(ho.data(), B->Hcub.p, 8 * ho.size(), hipMemcpyDeviceToHost));
-      if (B->np) CS_HIP_TRY(hipMemcpy(hl.data(), B->Hll.p, 8 * hl.size(), hipMemcpyDeviceToHost));
-      // pose diagonals are partial sums on every rank: sum them before taking the maximum
-      std::vector<double> pd(std::max(1, B->n_pose), 0.0);
-      for (int i = 0; i < B->nc; i++) if (B->cam_col[i] >= 0) for (int d = 0; d < 6; d++) pd[B->cam_col[i] + d] = hc[36 * (size_t)i + 7 * d];
-      for (int i = 0; i < B->no; i++) if (B->cub_col[i] >= 0) for (int d = 0; d < 9; d++) pd[B->cub_col[i] + d] = ho[81 * (size_t)i + 10 * d];
-      if (reduce_host(pd.data(), pd.size(), 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-      double md = 0;
-      for (int i = 0; i < B->n_pose; i++) md = std::max(std::fabs(pd[i]), md);
-      for (int i = 0; i < B->np; i++) if (B->pt_lm[i] >= 0) for (int d = 0; d < 3; d++) md = std::max(std::fabs(hl[9 * (size_t)i + 4 * d]), md);
-      if (reduce_host(&md, 1, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-      cs::lm_begin(lm, B->user_lambda_init, md);
-    }
-    double rho = 0;
-    int qmax = 0;
-    do {
-      if (!stream_flow) { rc = save_estimates(B); if (rc) return rc; }      // (stream flow: the update kernel below saves the estimates it replaces)
-      bool ok2 = true;
-      bool spec_now = false;
-      double scale = 0;
-      if (stream_flow) {
-        std::unique_lock<std::mutex> turn;
-        // x^T (lambda x + b): b is a per-rank partial sum, x is replicated for the poses -- their lambda x^2 term is counted once
-        // (rank 0); a landmark's terms live on exactly one rank.  A failed factorisation leaves garbage in x; the update below then
-        // writes garbage estimates, which the pop restores (the decision is taken after the synchronisation).
-        // [chi2, scale term, "a factorisation failed somewhere"]: one message; every rank takes the same accept / reject branch.
-        auto enqueue_trial = [&](std::unique_lock<std::mutex>* t) -> int {
-          bool okq = true;
-          int rq = solve_device(B, lm.lambda, &okq, nullptr, nullptr, t); if (rq) return rq;
-          cs::ba_launch_scale_update(B->view, B->d_lam.p, B->scale_partial.p, B->st, B->cams_bak.p, B->points_bak.p, B->cubes_bak.p);
-          if (spec_now) CS_HIP_TRY(hipEventRecord(B->ev_upd, B->st));      // the state the next linearisation reads is final from here
-          BA_MARK(B, B->ev[6]);
-          cs::ba_launch_chi2(B->view, B->nb_chi, B->st);
-          if (B->sep_mode && B->shard_n > 1) cs::ba_launch_sum2(B->chi_partial.p, B->n_chi_partials, B->scale_partial.p, cs::ba_scale_blocks(), B->d_scalars.p, B->st);   // (separator mode set its flag itself: three status words)
-          else cs::ba_launch_sum2_flag(B->chi_partial.p, B->n_chi_partials, B->scale_partial.p, cs::ba_scale_blocks(), B->d_band_info.p, B->d_elim_fail.p, B->d_scalars.p, B->st,
-                                       direct_scalars ? B->h_trial : nullptr, direct_scalars ? (B->trial_seq += 1.0) : 0.0);
-          CS_HIP_TRY(hipGetLastError());
-          if (rccl) BA_NCCL(ncclAllReduce(B->d_scalars.p, B->d_scalars.p, 3, ncclDouble, ncclSum, B->comm, B->st));
-          if (!direct_scalars) CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, 3 * sizeof(double), hipMemcpyDeviceToHost, B->st));
-          BA_MARK(B, B->ev[7]);
-          return CS_OK;
-        };
-        // (The sequence is the same ~30 launches, fills and copies for every trial of a structure -- lambda is read from device memory -- and was
-        // replayed as one hipGraph in round 4: measured no faster on MI355X / ROCm 7.0 and +0.8 ms of instantiation per structure, DESIGN.md section 3;
-        // removed in round 5.)
-        spec_now = can_spec && direct_scalars && it + 1 < iterations;
-        rc = enqueue_trial(&turn); if (rc) return rc;
-        if (spec_now) {      // the next iteration's linearisation (it + 1 > 0: the fused form where the graph allows it), queued before the verdict
-          const int fl = B->view.fuse_lin;
-          B->view.fuse_lin = fuse_lin_ok ? 1 : 0;
-          rc = build_system_device(B, B->ev_upd);      // (its numeric-Jacobian edges start behind the update, beside this trial's chi2 kernels)
-          B->view.fuse_lin = fl;       // (a retry of THIS iteration reduces the way this iteration linearised)
-          if (rc) return rc;
-        }
-        const double* hs = B->h_scalars;
-        if (direct_scalars) { rc = wait_trial(B->trial_seq); if (rc) return rc; hs = B->h_trial; }
-        else CS_HIP_TRY(hipStreamSynchronize(B->st));
-        turn.unlock();
-        rc = check_band_timeout(B, B->sep_mode && B->shard_n > 1); if (rc) return rc;
-        ok2 = hs[2] == 0.0;
-        tempChi = hs[0];
-        scale = hs[1];
-        if (B->stage_timing) {
-          if (direct_scalars) CS_HIP_TRY(hipStreamSynchronize(B->st));     // (the phase marks are read below: the last one must have passed)
-          rc = collect_solve_times(B); if (rc) return rc;
-          float ms = 0;
-          CS_HIP_TRY(hipEventElapsedTime(&ms, B->ev[6], B->ev[7])); B->tm.errors_ms += ms;
-        }
-        if (ext_active && ok2) { rc = ext_refresh(0); if (rc) return rc; tempChi += B->ext_chi2; }
-      } else {
-        rc = solve_device(B, lm.lambda, &ok2, fn, ctx); if (rc) return rc;
-        if (B->shard_n > 1) {   // a failed factorisation on one rank is everybody's rejected trial
-          double ff = ok2 ? 0.0 : 1.0;
-          if (reduce_host(&ff, 1, 1)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-          ok2 = ff == 0.0;
-        }
-        if (ok2) {
-          const int nsb = cs::ba_scale_blocks();
-          std::vector<double> sp(nsb);
-          cs::ba_launch_scale(B->view, B->d_lam.p, B->scale_partial.p, B->st);     // (d_lam still holds this trial's lambda: put_lambda in solve_device)
-          CS_HIP_TRY(hipGetLastError());
-          CS_HIP_TRY(hipMemcpyAsync(sp.data(), B->scale_partial.p, sizeof(double) * nsb, hipMemcpyDeviceToHost, B->st));
-          rc = cs_ba_update(B); if (rc) return rc;   // synchronises the stream
-          for (double p : sp) scale += p;
-        }
-        t0 = now_ms();
-        rc = chi2_device(B, &tempChi); if (rc) return rc;
-        if (ext_active && ok2) { rc = ext_refresh(0); if (rc) return rc; tempChi += B->ext_chi2; }
-        if (reduce_host(&tempChi, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-        B->tm.errors_ms += now_ms() - t0;
-        if (reduce_host(&scale, 1, 0)) { cs_set_error("all-reduce failed"); return CS_ERR_HIP; }
-      }
-      if (ok2) debug_nan_scan(B, "cs_ba_optimize: after a trial's solve + update");
-      if (cs::lm_trial(lm, currentChi, tempChi, scale, ok2, rho)) {
-        spec_lin = spec_now;       // the system of the state this trial left is already on the stream
-      } else {
-        rc = restore_estimates(B); if (rc) return rc;
-        if (spec_now) {            // the speculation linearised the rejected state: the restored one again, as this iteration linearises
-          rc = build_system_device(B); if (rc) return rc;
-        }
-      }
-      qmax++;
-    } while (cs::lm_again(rho, qmax, B->max_trials_after_failure));
-    if (!spec_lin) CS_HIP_TRY(hipStreamSynchronize(B->st));
-    if (done < cap) {
-      if (chi_hist) chi_hist[done] = currentChi;
-      if (lambda_hist) lambda_hist[done] = lm.lambda;
-      if (trials_hist) trials_hist[done] = qmax;
-    }
-    done++;
-    carriedChi = currentChi; have_carried = true;
-    if (cs::lm_stop(lm, rho, qmax, B->max_trials_after_failure, iniChi, currentChi)) break;
-  }
-  if (spec_lin) CS_HIP_TRY(hipStreamSynchronize(B->st));      // (a stopping rule ended the loop behind an accepted trial: its speculated system is the current state's)
-  if (iterations_done) *iterations_done = done;
-  B->tm.total_ms += now_ms() - t_begin;
-  return CS_OK;
-}
-int cs_ba_optimize_sharded(cs_ba* B, int iterations, cs_allreduce_fn fn, void* ctx, int* iterations_done, double* chi_hist, double* lambda_hist, int* trials_hist, int cap) {
-  CS_GUARD_BEGIN
-  return cs_ba_optimize_sharded_impl(B, iterations, fn, ctx, iterations_done, chi_hist, lambda_hist, trials_hist, cap);
-  CS_GUARD_END("cs_ba_optimize_sharded")
 }
 
 // ---- RCCL: one process per GPU, the library issues the collectives itself (ncclAllReduce on the handle's stream)
@@ -2743,8 +1716,8 @@ int cs_ba_check_finite(cs_ba* B, int* n_bad, char* report, int report_cap) {
   return check_finite_impl(B, report, report_cap, n_bad);
   CS_GUARD_END("cs_ba_check_finite")
 }
-static bool debug_nan_enabled() { static const bool on = [] { const char* e = getenv("CS_BA_DEBUG_NAN"); return e && atoi(e) != 0; }(); return on; }
-static void debug_nan_scan(cs_ba* B, const char* where) {
+bool debug_nan_enabled() { static const bool on = [] { const char* e = getenv("CS_BA_DEBUG_NAN"); return e && atoi(e) != 0; }(); return on; }
+void debug_nan_scan(cs_ba* B, const char* where) {
   if (!debug_nan_enabled()) return;
   char rep[2048]; int n = 0;
   if (check_finite_impl(B, rep, (int)sizeof(rep), &n) == CS_OK && n > 0) fprintf(stderr, "[cs_ba CS_BA_DEBUG_NAN] %s:\n%s", where, rep);

@@ -34,7 +34,7 @@ void cs_set_error(const std::string& s);
 
 namespace cs {
 
-// the turn of the persistent solver kernels whose workgroups wait for each other (ba_host.cpp, pgo_host.cpp): one such kernel at a time per process
+// the turn of the persistent solver kernels whose workgroups wait for each other (ba_lm.cpp, pgo_host.cpp): one such kernel at a time per process
 inline std::mutex& coop_mutex() { static std::mutex m; return m; }
 
 // the first check of every cs_*_create: a device is visible and `device` names one

@@ -1,6 +1,6 @@
 // cs_lm.h -- the Levenberg-Marquardt policy of g2o's OptimizationAlgorithmLevenberg::solve (core/optimization_algorithm_levenberg.cpp:61-163),
 // stated once, for host and device: lambda's first value, a trial's accept / reject arithmetic, the retry and stop rules.  The host loops of
-// cs_ba_optimize (ba_host.cpp) and cs_pgo_optimize (pgo_host.cpp) call it, and so does the per-wavefront loop of cs_dense_lm.h that
+// cs_ba_optimize (ba_lm.cpp) and cs_pgo_optimize (pgo_host.cpp) call it, and so does the per-wavefront loop of cs_dense_lm.h that
 // pose_kernels.hip and sim3_pair_kernels.hip run.  What a loop DOES on either verdict stays with the loop.  (Compiled with
 // -ffp-contract=off, like all of them.)
 #pragma once

@@ -1,6 +1,6 @@
 // cs_sparse_solver.h -- the host side of the general sparse Cholesky (plan: ba_sparse.h, kernels: sparse_kernels.hip), owned once: the
 // plan and its launch grids, the plan's tables on the device, the workspace, the status words, and the sequence a damped solve queues.
-// The bundle adjustment's reduced system (ba_host.cpp) and the pose graph's H + lambda I (pgo_host.cpp) each hold one.
+// The bundle adjustment's reduced system (ba_lm.cpp) and the pose graph's H + lambda I (pgo_host.cpp) each hold one.
 #pragma once
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>

@@ -1,6 +1,6 @@
 """Every factorisation of the reduced pose system against an exact float64 solve of the system the device factorised (tests/ba_numpy_ref.py).
 
-The paths (csrc/ba_host.cpp: the choice in the structure phase, the solves in solve_device): the persistent banded Cholesky in its nested,
+The paths (csrc/ba_host.cpp: the choice in the structure phase; csrc/ba_lm.cpp: the solves in solve_device): the persistent banded Cholesky in its nested,
 two-front and one-sided orders; block cyclic reduction (bcr_kernels.hip); the general sparse Cholesky (ba_sparse.h + sparse_kernels.hip)
 with the default dense tail, a small one and none; dense rocSOLVER.  Per case, at lambda 1e-3 and 30:
   (a) cs_ba_get_reduced_system equals the numpy reduced matrix permuted to solver order (1e-12 of max |S|);

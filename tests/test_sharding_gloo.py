@@ -121,7 +121,7 @@ def _worker(rank, port, out):
 
 
 def _sep_worker(rank, world, port, out):
-    """Separator mode of the sharded solve (include/cubeslam_hip.h, ba_host.cpp solve_device_sep) restated in numpy, one process
+    """Separator mode of the sharded solve (include/cubeslam_hip.h, ba_lm.cpp solve_device_sep) restated in numpy, one process
     per rank: ownership by lowest column, the rank's partial system in its own columns + the next separator's diagonal block,
     interior Cholesky, the message [LL | RL | RR | tL | tR], one all-gather, the separator system solved by every rank, interior
     back-substitution, one all-reduce of the solution vector."""
