@@ -1,4 +1,4 @@
-// ba_handle.h -- the bundle-adjustment handle (struct cs_ba) with the device / pinned buffer types it is made of, the three macros of its host
+// ba_handle.h -- the bundle-adjustment handle (struct cs_ba; its buffer types are ba_dbuf.h's), the two macros of its host
 // code, and the few functions that cross between ba_host.cpp (graph input, structure phase, inspection, dump / load) and ba_lm.cpp (the
 // stepwise calls, the damped solve, the LM loop).  Host code only: included by those two files and nothing else.
 #pragma once
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "ba_dbuf.h"
 #include "ba_edge_class.h"
 #include "ba_structure.h"
 #include "ba_types.h"
@@ -43,156 +44,39 @@
     }                                                                          \
   } while (0)
 
-// Pinned staging for the structure phase's many small uploads: a blocking hipMemcpy from pageable memory costs ~40 us whatever its
-// size, and the phase makes a few dozen; through this arena they are queued on the handle's stream and waited for once.
-struct StageArena {
-  char* p = nullptr;
-  size_t cap = 0, off = 0;
-  void* take(size_t bytes) {          // nullptr: no room (the caller copies directly)
-    const size_t at = (off + 63) & ~(size_t)63;
-    if (!p || at + bytes > cap) return nullptr;
-    off = at + bytes;
-    return p + at;
-  }
-  int begin(size_t want) {            // at the start of a structure phase, the stream idle
-    off = 0;
-    if (p && cap >= want) return CS_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    CS_HIP_TRY(hipHostMalloc((void**)&p, want));
-    cap = want;
-    return CS_OK;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = off = 0; }
-};
-
-inline int g_dbuf_reallocs = 0;     // (diagnostics: device (re)allocations, printed with the structure phase's clock under CS_BA_PROF)
-template <class T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0, cap = 0;       // entries in use / allocated (grow-only: a graph that is extended frame by frame re-runs the structure phase,
-                               // and ~100 hipFree + hipMalloc pairs were a quarter of it at 200 cameras)
-  int reserve(size_t count) {
-    count = std::max<size_t>(1, count);
-    if (p && count <= cap) return CS_OK;
-    // (a buffer that has to grow belongs to a graph that is being extended: a quarter of head room, so that the next frames fit --
-    // without it every appended frame re-allocated every buffer whose size follows the edges or the points, ~60 of them)
-    const size_t want = p ? count + count / 4 + 64 : count;
-    g_dbuf_reallocs++;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    CS_HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
-    cap = want;
-    return CS_OK;
-  }
-  int upload_ptr(const T* h, size_t count) {   // from the caller's memory
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    if (n) CS_HIP_TRY(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return CS_OK;
-  }
-  int append_ptr(const T* h, size_t count) {   // the old contents stay where they are on the device, `count` new entries follow
-    if (!count) return CS_OK;
-    if (!p || n + count > cap) {               // (with head room: the next frames append in place)
-      const size_t want = std::max(n + count, cap + cap / 2 + 16);
-      T* q = nullptr;
-      CS_HIP_TRY(hipMalloc((void**)&q, want * sizeof(T)));
-      if (n) CS_HIP_TRY(hipMemcpy(q, p, n * sizeof(T), hipMemcpyDeviceToDevice));
-      if (p) (void)hipFree(p);
-      p = q; cap = want;
-    }
-    CS_HIP_TRY(hipMemcpy(p + n, h, count * sizeof(T), hipMemcpyHostToDevice));
-    n += count;
-    return CS_OK;
-  }
-  // the same through a pinned arena, queued on st (a frame's appends: a dozen blocking copies from pageable memory were 0.3-0.5 ms); the
-  // arena's contents must stay until st has run (the handle rewinds it after the next structure phase's wait)
-  int append_ptr_staged(const T* h, size_t count, StageArena& stage, hipStream_t st) {
-    if (!count) return CS_OK;
-    const size_t bytes = count * sizeof(T);
-    void* pin = (p && n + count <= cap && bytes <= (256u << 10)) ? stage.take(bytes) : nullptr;
-    if (!pin) {                                   // growing (the old contents are copied: nothing may still be writing them) or no room
-      CS_HIP_TRY(hipStreamSynchronize(st));
-      return append_ptr(h, count);
-    }
-    std::memcpy(pin, h, bytes);
-    CS_HIP_TRY(hipMemcpyAsync(p + n, pin, bytes, hipMemcpyHostToDevice, st));
-    n += count;
-    return CS_OK;
-  }
-  int upload(const std::vector<T>& h) { return upload_ptr(h.data(), h.size()); }
-  int upload_ptr_staged(const T* h, size_t count, StageArena& stage, hipStream_t st) {   // up to 1 MB: through the pinned arena, queued on st (a blocking copy from pageable memory costs 50-100 us)
-    const size_t bytes = count * sizeof(T);
-    void* pin = (bytes && bytes <= (1u << 20)) ? stage.take(bytes) : nullptr;
-    if (!pin) return upload_ptr(h, count);
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    std::memcpy(pin, h, bytes);
-    CS_HIP_TRY(hipMemcpyAsync(p, pin, bytes, hipMemcpyHostToDevice, st));
-    return CS_OK;
-  }
-  // like upload_ptr_staged, but the copy itself is left to the caller's batched launch (cs::ba_launch_multi_copy): destination, staged
-  // source and size are appended to the list.  No room in the arena: a blocking copy now.
-  // Tables of more than 64 KB keep their own hipMemcpyAsync (the copy engine moves a large table faster than a kernel reads it over the link:
-  // at a million edges the all-kernel form cost the phase 1.5 ms).
-  int upload_ptr_deferred(const T* h, size_t count, StageArena& stage, std::vector<cs::BaCopyItem>& list, hipStream_t st) {
-    const size_t bytes = count * sizeof(T);
-    if (bytes > (64u << 10)) return upload_ptr_staged(h, count, stage, st);
-    void* pin = bytes ? stage.take(bytes) : nullptr;
-    if (!pin) return upload_ptr(h, count);
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    std::memcpy(pin, h, bytes);
-    list.push_back(cs::BaCopyItem{p, pin, bytes});
-    return CS_OK;
-  }
-  int alloc(size_t count, hipStream_t st = nullptr) {   // zeroed; st: queued on that stream instead of a blocking call per buffer
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    if (st) CS_HIP_TRY(hipMemsetAsync(p, 0, std::max<size_t>(1, n) * sizeof(T), st));
-    else CS_HIP_TRY(hipMemset(p, 0, std::max<size_t>(1, n) * sizeof(T)));
-    return CS_OK;
-  }
-  // zeroed like alloc(), but the fill is left to the caller's batched launch (cs::ba_launch_multi_zero): ptr / bytes are appended to the list
-  int alloc_deferred(size_t count, std::vector<std::pair<void*, size_t>>& zero_list) {
-    int rc = reserve(count); if (rc) return rc;
-    n = count;
-    zero_list.emplace_back((void*)p, std::max<size_t>(1, n) * sizeof(T));
-    return CS_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; cap = 0; }
-};
-
 using cs::UBuf;    // (host scratch of the structure phase: ba_structure.h)
 
 struct cs_ba {
+  // Every device resource below is an owner type that gives itself back, and members die in reverse declaration order.  So: the three
+  // streams first -- they die last, after everything that was queued on them -- the BLAS handle behind its stream, then buffers, events and
+  // pinned words in any order.  cs_ba_destroy waits for the streams, closes the communicator and deletes: nothing is named there.
   int device = 0;
-  hipStream_t st = nullptr;
+  cs::Stream st;
+  cs::Stream st2;                            // side stream of the reduce phase (cuboid elimination beside the landmark segments)
+  cs::Stream st3;                            // third stream of the linearisation: the landmark kernel beside the camera kernel (which fills a fraction of the CUs)
+  cs::BlasHandle blas;
   StageArena stage;                          // pinned staging of the structure phase's small uploads
   // the landmarks' camera lists of the last structure phase (host): a graph that is only appended to extends them instead of re-sorting all edges
   int st_lists_edges = 0, st_cur = 0; std::vector<int> st_cam_cnt; UBuf<int> st_cams_of[2], st_edge_of[2];   // (two sets: a phase reads the last one's and fills the other)
   UBuf<int> st_pm_pt, st_pm_cam, st_cm_pm, st_cm_pt;   // host scratch of the edge orders, kept for its memory only
   StageArena append_stage;                   // ... and of cs_ba_append_*'s rows (queued on st, rewound by the structure phase)
-  hipStream_t st2 = nullptr;                 // side stream of the reduce phase (cuboid elimination beside the landmark segments)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipStream_t st3 = nullptr;                 // third stream of the linearisation: the landmark kernel beside the camera kernel (which fills a fraction of the CUs)
-  hipEvent_t ev_join3 = nullptr;
-  rocblas_handle blas = nullptr;
-  hipEvent_t ev[8] = {};   // phase marks on the stream (linearise: 0-1; solve: 2 reduce 3 factor 4 back-substitution 5)
-  hipEvent_t sev[4] = {};  // separator mode, inside [3, 4]: interior factorised, separator message formed, messages gathered, separator system solved
+  cs::Event ev_fork, ev_join, ev_join3;      // the side streams' fork and their two joins
+  cs::Event ev[8];   // phase marks on the stream (linearise: 0-1; solve: 2 reduce 3 factor 4 back-substitution 5)
+  cs::Event sev[4];  // separator mode, inside [3, 4]: interior factorised, separator message formed, messages gathered, separator system solved
   double sep_ms[5] = {0, 0, 0, 0, 0};   // accumulated: interior factorisation, message (Y, T, t), gather, separator solve, interior back-substitution
   bool lin_pending = false;  // ev[0..1] recorded but not yet read
-  int* h_status = nullptr;   // pinned: [status of the (interior's) factorisation, a cuboid block failed, status of the separator system's factorisation -- sparse: [2], [3] are the solver's two words]
+  cs::PinBuf<int> h_status;  // pinned: [status of the (interior's) factorisation, a cuboid block failed, status of the separator system's factorisation -- sparse: [2], [3] are the solver's two words]
   // sharded BA over RCCL (cs_ba_comm_init): the collectives are issued from here, on this handle's stream
   ncclComm_t comm = nullptr;
   DBuf<double> d_scalars;    // [chi2, LM scale term] of a trial; lambda_0's diagonal on iteration 0
   // lambda of the current trial lives in device memory (d_lam: [lambda, lambda of the pose diagonals in LM's scale term]), copied from
   // the pinned h_lam at the head of a trial's launch sequence: the sequence itself never changes
-  double* h_lam = nullptr;
+  cs::PinBuf<double> h_lam;
   DBuf<double> d_lam;
-  double* h_scalars = nullptr;   // pinned mirror
+  cs::PinBuf<double> h_scalars;  // pinned mirror
   // the trial's [chi2, scale term, failure flag, sequence number], written by the trial's last kernel itself (ba_sum2_flag_kernel) and polled by
   // cs_ba_optimize: pinned, device-visible
-  double* h_trial = nullptr;
+  cs::PinBuf<double> h_trial;
   double trial_seq = 0.0;
   // G2OBatchStatistics-like stage split (core/batch_stats.h:48-62): like g2o's setComputeBatchStatistics it is OFF unless asked for
   // (cs_ba_set_stage_timing) -- every phase mark is an event on the stream, ~6 us of dispatch gap each, eight per LM trial
@@ -200,8 +84,7 @@ struct cs_ba {
   // OptimizationAlgorithmLevenberg's two properties (optimization_algorithm_levenberg.cpp:50-51, setters :191-199): cs_ba_set_lm_params
   double user_lambda_init = 0.0;      // "initialLambda": > 0 replaces tau * max |H_jj| (computeLambdaInit :168-169)
   int max_trials_after_failure = 10;  // "maxTrialsAfterFailure": trials of one iteration (:149-151)
-  hipEvent_t ev_upd = nullptr;     // recorded behind a trial's update kernel when the next linearisation is speculated: its side streams fork there
-  size_t scalars_cap = 0;
+  cs::Event ev_upd;                // recorded behind a trial's update kernel when the next linearisation is speculated: its side streams fork there
   // host copy of the problem description
   int nc = 0, no = 0, np = 0, cuboids_first = 0;
   std::vector<int> cam_fixed, cub_fixed, pt_fixed, cam_col, cub_col, pt_lm;  // pt_lm: landmark index among free points or -1
@@ -334,9 +217,6 @@ struct cs_ba {
   cs_ba_timing tm{};
   cs::BaView view{};
 };
-
-// `call` returns a CS_* code: pass a failure on
-#define CS_TRY(call) do { if (int _rc = (call)) return _rc; } while (0)
 
 // ---- across the two files
 // ba_host.cpp: the structure phase (a no-op on a clean handle); CS_BA_DEBUG_NAN's scan of estimates, errors and blocks after a step

@@ -445,13 +445,7 @@ int allocate_system_storage(cs_ba* B, int E, StructureUploads& U) {
   {
     const size_t need = std::max<size_t>(16, (size_t)B->n_pose + 2);
     CS_TRY(U.alloc_zeroed(B->d_scalars, need));
-    if (B->scalars_cap < need) {     // (with head room: a graph that grows by a camera per frame would re-pin this buffer every frame, ~0.1 ms)
-      if (B->h_scalars) (void)hipHostFree(B->h_scalars);
-      B->h_scalars = nullptr;
-      const size_t want = need + need / 4 + 256;
-      CS_HIP_TRY(hipHostMalloc((void**)&B->h_scalars, want * sizeof(double)));
-      B->scalars_cap = want;
-    }
+    if (B->h_scalars.cap < need) CS_ENSURE(B->h_scalars, need + need / 4 + 256);     // (with head room: a graph that grows by a camera per frame would re-pin this buffer every frame, ~0.1 ms)
   }
   CS_TRY(U.alloc_zeroed(B->cams_bak, 7 * nc)); CS_TRY(U.alloc_zeroed(B->points_bak, 3 * np)); CS_TRY(U.alloc_zeroed(B->cubes_bak, 10 * no));
   std::vector<double> u8(B->uni8, B->uni8 + 8);
@@ -697,75 +691,38 @@ int cs_ba_create(int device, cs_ba** out) {
   *out = nullptr;
   { const int rc = cs::check_device(device); if (rc) return rc; }
   CS_GUARD_BEGIN
-  struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{new cs_ba()};   // freed on every early return
-  cs_ba* B = g.b;
+  cs::Guard<cs_ba> g(new cs_ba(), cs_ba_destroy);   // freed on every early return
+  cs_ba* B = g.h;
   B->device = device;
   { const char* e = getenv("CS_BA_FORCE_DENSE"); B->force_dense = (e && atoi(e)) ? 1 : 0; }  // diagnostics: rocSOLVER dense path
   CS_HIP_TRY(hipSetDevice(device));
-  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
-  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st2, hipStreamNonBlocking));   // (a high-priority side stream was measured in round 5: no effect on the kernels that run beside a device-filling one)
-  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_fork, hipEventDisableTiming));
-  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_join, hipEventDisableTiming));
-  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st3, hipStreamNonBlocking));
-  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_join3, hipEventDisableTiming));
-  CS_HIP_TRY(hipEventCreateWithFlags(&B->ev_upd, hipEventDisableTiming));
-  for (auto& e : B->ev) CS_HIP_TRY(hipEventCreate(&e));
-  for (auto& e : B->sev) CS_HIP_TRY(hipEventCreate(&e));
-  CS_HIP_TRY(hipHostMalloc((void**)&B->h_lam, 2 * sizeof(double)));
-  B->h_lam[0] = B->h_lam[1] = 0.0;
-  { int rc0 = B->d_lam.alloc(2); if (rc0) return rc0; }
-  CS_HIP_TRY(hipHostMalloc((void**)&B->h_trial, 8 * sizeof(double)));
-  for (int i = 0; i < 8; i++) B->h_trial[i] = 0.0;
-  CS_HIP_TRY(hipHostMalloc((void**)&B->h_status, 4 * sizeof(int)));
-  B->h_status[0] = B->h_status[1] = B->h_status[2] = B->h_status[3] = 0;
-  CS_ROC_TRY(rocblas_create_handle(&B->blas));
-  CS_ROC_TRY(rocblas_set_stream(B->blas, B->st));
-  *out = B;
-  g.b = nullptr;
+  CS_TRY(B->st.create(hipStreamNonBlocking));
+  CS_TRY(B->st2.create(hipStreamNonBlocking));   // (a high-priority side stream was measured in round 5: no effect on the kernels that run beside a device-filling one)
+  CS_TRY(B->st3.create(hipStreamNonBlocking));
+  for (cs::Event* e : {&B->ev_fork, &B->ev_join, &B->ev_join3, &B->ev_upd}) CS_TRY(e->create(hipEventDisableTiming));
+  for (auto& e : B->ev) CS_TRY(e.create());
+  for (auto& e : B->sev) CS_TRY(e.create());
+  CS_ENSURE(B->h_lam, 2); CS_ENSURE(B->h_trial, 8); CS_ENSURE(B->h_status, 4);
+  std::fill_n(B->h_lam.p, 2, 0.0); std::fill_n(B->h_trial.p, 8, 0.0); std::fill_n(B->h_status.p, 4, 0);
+  CS_TRY(B->d_lam.alloc(2));
+  CS_TRY(B->blas.create(B->st));
+  *out = g.disarm();
   return CS_OK;
   CS_GUARD_END("cs_ba_create")
 }
 
+// (every member gives itself back, the streams last: see the head of struct cs_ba)
 void cs_ba_destroy(cs_ba* B) {
   if (!B) return;
   (void)hipSetDevice(B->device);
-  DBuf<double>* dd[] = {&B->cams, &B->points, &B->cubes, &B->cams_bak, &B->points_bak, &B->cubes_bak, &B->pm_uv, &B->pm_info, &B->pm_intr, &B->pm_huber,
-                        &B->cm_uv, &B->cm_info, &B->cm_intr, &B->cm_huber, &B->ce_meas, &B->ce_info, &B->ce_Hcc, &B->ce_Hoo, &B->ce_Hco, &B->ce_bc, &B->ce_bo,
-                        &B->oe_meas, &B->oe_info, &B->oe_Hii, &B->oe_Hjj, &B->oe_Hij, &B->oe_bi, &B->oe_bj, &B->Hcam, &B->bcam, &B->Hcub, &B->bcub, &B->Hll, &B->bl,
-                        &B->W, &B->WD, &B->Dinv, &B->dbl, &B->S, &B->rhs, &B->xl, &B->chi_partial, &B->band_linv, &B->scale_partial, &B->pe_meas, &B->pe_info, &B->pe_K, &B->part_tiles, &B->part_coef, &B->cub_M, &B->cub_Dinv, &B->raw_uv, &B->raw_info, &B->raw_intr, &B->raw_huber, &B->sepY, &B->sep_msgs, &B->sepS, &B->int_work, &B->sep_work, &B->d_ce_rdelta, &B->d_oe_rdelta, &B->ext_cam36, &B->ext_cam6, &B->ext_cub81, &B->ext_cub9, &B->ext_pt9, &B->ext_pt3, &B->ext_Hij, &B->comb_uv, &B->comb_info, &B->comb_intr, &B->comb_huber, &B->d_pm_ur, &B->d_cm_ur, &B->d_pm_sinfo, &B->d_cm_sinfo};
-  for (auto* d : dd) d->release();
-  B->stage.release(); B->append_stage.release();
-  DBuf<int>* di[] = {&B->d_ce_active, &B->d_oe_active, &B->d_cam_col, &B->d_cub_col, &B->d_pt_free, &B->pm_pt, &B->pm_cam, &B->pt_ptr, &B->cm_pm, &B->cm_pt, &B->cam_ptr, &B->d_ce_cam, &B->d_ce_cub,
-                     &B->d_oe_i, &B->d_oe_j, &B->cam_ce_ptr, &B->cam_ce_idx, &B->cam_oei_ptr, &B->cam_oei_idx, &B->cam_oej_ptr, &B->cam_oej_idx, &B->cub_ce_ptr,
-                     &B->cub_ce_idx, &B->pair_ptr, &B->pair_i1, &B->pair_i2, &B->ent_a, &B->ent_b, &B->d_run_lm, &B->d_seg_ptr, &B->d_seg_k, &B->d_seg_tile, &B->d_seg_slot, &B->d_run_e0, &B->d_seg_cam,
-                     &B->d_gp_ptr, &B->d_gp_i1, &B->d_gp_i2, &B->d_gtile, &B->d_gcam_ptr, &B->d_gslot, &B->d_cubS_ptr, &B->d_cubS_cam, &B->d_ce_slot, &B->d_cub_tile, &B->d_cub_coef,
-                     &B->d_elim_fail, &B->d_slotE_ptr, &B->d_slotE_idx, &B->d_cub_mine, &B->d_sep_off, &B->d_sep_col, &B->d_int_info, &B->d_sep_info, &B->d_pm_rk, &B->d_cm_rk, &B->d_ce_rk, &B->d_oe_rk, &B->d_ext_e4, &B->d_ext_order, &B->d_ext_gptr, &B->d_src, &B->d_pm_kind, &B->d_cm_kind};
-  for (auto* d : di) d->release();
-  B->d_lvl.release(); B->d_pm_cm.release(); B->d_cls_counts.release(); B->d_cls_chi.release();
-  B->solver.release();
-  B->d_info.release(); B->d_band_info.release();
-  for (auto& e : B->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : B->sev) if (e) (void)hipEventDestroy(e);
-  if (B->h_lam) (void)hipHostFree(B->h_lam);
-  B->d_lam.release();
-  if (B->h_status) (void)hipHostFree(B->h_status);
-  if (B->h_trial) (void)hipHostFree(B->h_trial);
-  if (B->h_scalars) (void)hipHostFree(B->h_scalars);
+  for (const cs::Stream* s : {&B->st, &B->st2, &B->st3}) if (s->s) (void)hipStreamSynchronize(*s);
   if (B->comm) { (void)ncclCommDestroy(B->comm); g_comm_handles--; }
-  B->d_scalars.release();
-  if (B->blas) rocblas_destroy_handle(B->blas);
-  if (B->ev_fork) (void)hipEventDestroy(B->ev_fork);
-  if (B->ev_join) (void)hipEventDestroy(B->ev_join);
-  if (B->st2) (void)hipStreamDestroy(B->st2);
-  if (B->st3) (void)hipStreamDestroy(B->st3);
-  if (B->ev_join3) (void)hipEventDestroy(B->ev_join3);
-  if (B->ev_upd) (void)hipEventDestroy(B->ev_upd);
-  if (B->st) (void)hipStreamDestroy(B->st);
   delete B;
 }
 
-static int cs_ba_set_vertices_impl(cs_ba* B, const double* cams7, const int* cam_fixed, int nc, const double* cuboids10, const int* cub_fixed, int no,
+int cs_ba_set_vertices(cs_ba* B, const double* cams7, const int* cam_fixed, int nc, const double* cuboids10, const int* cub_fixed, int no,
                        const double* points3, const int* pt_fixed, int np, int cuboids_first) {
+  CS_GUARD_BEGIN
   if (!B || nc < 0 || no < 0 || np < 0 || (nc && (!cams7 || !cam_fixed)) || (no && (!cuboids10 || !cub_fixed)) || (np && (!points3 || !pt_fixed))) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way: cs_ba_append_* queues them on st)
@@ -780,11 +737,6 @@ static int cs_ba_set_vertices_impl(cs_ba* B, const double* cams7, const int* cam
   rc = B->points.upload(std::vector<double>(points3, points3 + 3 * (size_t)np)); if (rc) return rc;
   B->structure_dirty = true;
   return CS_OK;
-}
-int cs_ba_set_vertices(cs_ba* B, const double* cams7, const int* cam_fixed, int nc, const double* cuboids10, const int* cub_fixed, int no,
-                       const double* points3, const int* pt_fixed, int np, int cuboids_first) {
-  CS_GUARD_BEGIN
-  return cs_ba_set_vertices_impl(B, cams7, cam_fixed, nc, cuboids10, cub_fixed, no, points3, pt_fixed, np, cuboids_first);
   CS_GUARD_END("cs_ba_set_vertices")
 }
 
@@ -797,8 +749,9 @@ static int append_arena(cs_ba* B) {
   if (B->append_stage.p) return CS_OK;
   return B->append_stage.begin((size_t)1 << 20);
 }
-static int cs_ba_append_vertices_impl(cs_ba* B, const double* cams7, const int* cam_fixed, int n_cams, const double* cuboids10, const int* cub_fixed, int n_cub,
-                                      const double* points3, const int* pt_fixed, int n_pts) {
+int cs_ba_append_vertices(cs_ba* B, const double* cams7, const int* cam_fixed, int n_cams, const double* cuboids10, const int* cub_fixed, int n_cub,
+                          const double* points3, const int* pt_fixed, int n_pts) {
+  CS_GUARD_BEGIN
   if (!B || n_cams < 0 || n_cub < 0 || n_pts < 0 || (n_cams && (!cams7 || !cam_fixed)) || (n_cub && (!cuboids10 || !cub_fixed)) || (n_pts && (!points3 || !pt_fixed))) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
@@ -814,11 +767,6 @@ static int cs_ba_append_vertices_impl(cs_ba* B, const double* cams7, const int* 
   B->nc += n_cams; B->no += n_cub; B->np += n_pts;
   B->structure_dirty = true;
   return CS_OK;
-}
-int cs_ba_append_vertices(cs_ba* B, const double* cams7, const int* cam_fixed, int n_cams, const double* cuboids10, const int* cub_fixed, int n_cub,
-                          const double* points3, const int* pt_fixed, int n_pts) {
-  CS_GUARD_BEGIN
-  return cs_ba_append_vertices_impl(B, cams7, cam_fixed, n_cams, cuboids10, cub_fixed, n_cub, points3, pt_fixed, n_pts);
   CS_GUARD_END("cs_ba_append_vertices")
 }
 // are the n new records all equal to the handle's reference record (the first record ever set)?  A few threads over the caller's arrays.
@@ -908,7 +856,8 @@ int cs_ba_append_edges_odom(cs_ba* B, int n, const int* ci, const int* cj, const
   CS_GUARD_END("cs_ba_append_edges_odom")
 }
 
-static int cs_ba_set_estimates_impl(cs_ba* B, const double* cams7, const double* cuboids10, const double* points3) {
+int cs_ba_set_estimates(cs_ba* B, const double* cams7, const double* cuboids10, const double* points3) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));       // (appended rows may still be on their way)
@@ -922,14 +871,11 @@ static int cs_ba_set_estimates_impl(cs_ba* B, const double* cams7, const double*
   B->have_system = false;
   B->backup_live = false;
   return CS_OK;
-}
-int cs_ba_set_estimates(cs_ba* B, const double* cams7, const double* cuboids10, const double* points3) {
-  CS_GUARD_BEGIN
-  return cs_ba_set_estimates_impl(B, cams7, cuboids10, points3);
   CS_GUARD_END("cs_ba_set_estimates")
 }
 
-static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
+int cs_ba_set_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
+  CS_GUARD_BEGIN
   if (!B || n < 0 || (n && (!pt || !cam || !uv || !info4 || !intr4))) return CS_ERR_INVALID_ARG;
   {   // the mono edges are replaced; the stereo edges behind them stay
     const std::vector<int> sp(B->e_pt.end() - B->n_stereo, B->e_pt.end()), sc(B->e_cam.end() - B->n_stereo, B->e_cam.end());
@@ -953,10 +899,6 @@ static int cs_ba_set_edges_proj_impl(cs_ba* B, int n, const int* pt, const int* 
   if (huber) { rc = B->raw_huber.upload_ptr(huber, (size_t)n); if (rc) return rc; } else B->raw_huber.release();
   B->structure_dirty = true;
   return CS_OK;
-}
-int cs_ba_set_edges_proj(cs_ba* B, int n, const int* pt, const int* cam, const double* uv, const double* info4, const double* intr4, const double* huber) {
-  CS_GUARD_BEGIN
-  return cs_ba_set_edges_proj_impl(B, n, pt, cam, uv, info4, intr4, huber);
   CS_GUARD_END("cs_ba_set_edges_proj")
 }
 
@@ -1032,8 +974,9 @@ int cs_ba_set_external_edges(cs_ba* B, int n, const int* class_i, const int* idx
   return CS_OK;
   CS_GUARD_END("cs_ba_set_external_edges")
 }
-static int cs_ba_set_external_terms_impl(cs_ba* B, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3,
-                                         const double* Hij81, double chi2) {
+int cs_ba_set_external_terms(cs_ba* B, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3,
+                             const double* Hij81, double chi2) {
+  CS_GUARD_BEGIN
   if (!B || (cam36 && !cam6) || (cub81 && !cub9) || (pt9 && !pt3) || (B->ext_n > 0 && !Hij81)) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));     // the previous linearisation may still read the buffers
@@ -1049,11 +992,6 @@ static int cs_ba_set_external_terms_impl(cs_ba* B, const double* cam36, const do
   B->ext_terms_set = true;
   B->have_system = false;
   return CS_OK;
-}
-int cs_ba_set_external_terms(cs_ba* B, const double* cam36, const double* cam6, const double* cub81, const double* cub9, const double* pt9, const double* pt3,
-                             const double* Hij81, double chi2) {
-  CS_GUARD_BEGIN
-  return cs_ba_set_external_terms_impl(B, cam36, cam6, cub81, cub9, pt9, pt3, Hij81, chi2);
   CS_GUARD_END("cs_ba_set_external_terms")
 }
 int cs_ba_set_external_chi2(cs_ba* B, double chi2) {
@@ -1084,7 +1022,8 @@ static bool any_class_level(cs_ba* B) { for (int c : kEdgeClasses) if (any_level
 
 // Robust kernels of one edge class (OptimizableGraph::Edge::setRobustKernel, core/optimizable_graph.h:419-423; the kernels:
 // core/robust_kernel_impl.cpp:78-165).  Replaces the class's kernels; n = the class's edge count.
-static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const int* kind, const double* delta) {
+int cs_ba_set_robust_kernels(cs_ba* B, int edge_class, int n, const int* kind, const double* delta) {
+  CS_GUARD_BEGIN
   if (!B || n < 0 || (n && kind && !delta)) return CS_ERR_INVALID_ARG;
   const EdgeClassRef cls = edge_class_ref(B, edge_class);
   if (cls.count < 0) { cs_set_error("cs_ba_set_robust_kernels: unknown edge class"); return CS_ERR_INVALID_ARG; }
@@ -1105,10 +1044,6 @@ static int cs_ba_set_robust_kernels_impl(cs_ba* B, int edge_class, int n, const 
   *cls.kinds = kk;
   B->structure_dirty = true;
   return CS_OK;
-}
-int cs_ba_set_robust_kernels(cs_ba* B, int edge_class, int n, const int* kind, const double* delta) {
-  CS_GUARD_BEGIN
-  return cs_ba_set_robust_kernels_impl(B, edge_class, n, kind, delta);
   CS_GUARD_END("cs_ba_set_robust_kernels")
 }
 
@@ -1142,7 +1077,8 @@ static int push_pose_levels(cs_ba* B) {
   if (!oa.empty()) CS_HIP_TRY(hipMemcpy(B->d_oe_active.p, oa.data(), sizeof(int) * oa.size(), hipMemcpyHostToDevice));
   return CS_OK;
 }
-static int cs_ba_set_edge_levels_impl(cs_ba* B, int edge_class, int n, const unsigned char* level) {
+int cs_ba_set_edge_levels(cs_ba* B, int edge_class, int n, const unsigned char* level) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   if (int rs = levels_refuse_shard(B, "cs_ba_set_edge_levels")) return rs;
   const EdgeClassRef cls = edge_class_ref(B, edge_class);
@@ -1156,10 +1092,6 @@ static int cs_ba_set_edge_levels_impl(cs_ba* B, int edge_class, int n, const uns
   B->have_system = false;          // (the system on the device is the old active set's)
   if (B->structure_dirty) return CS_OK;      // (the structure phase that is due applies them)
   return (edge_class == CS_EDGE_PROJ || edge_class == CS_EDGE_PROJ_STEREO) ? push_proj_levels(B) : push_pose_levels(B);
-}
-int cs_ba_set_edge_levels(cs_ba* B, int edge_class, int n, const unsigned char* level) {
-  CS_GUARD_BEGIN
-  return cs_ba_set_edge_levels_impl(B, edge_class, n, level);
   CS_GUARD_END("cs_ba_set_edge_levels")
 }
 int cs_ba_get_edge_levels(cs_ba* B, int edge_class, int n, unsigned char* level) {
@@ -1329,30 +1261,24 @@ int cs_ba_get_state(cs_ba* B, double* cams7, double* cuboids10, double* points3)
   CS_GUARD_END("cs_ba_get_state")
 }
 
-static int cs_ba_sizes_impl(cs_ba* B, int* size_pose, int* size_lm) {
+int cs_ba_sizes(cs_ba* B, int* size_pose, int* size_lm) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   int rc = finalize_structure(B); if (rc) return rc;
   if (size_pose) *size_pose = B->n_pose;
   if (size_lm) *size_lm = 3 * B->n_lm;
   return CS_OK;
-}
-int cs_ba_sizes(cs_ba* B, int* size_pose, int* size_lm) {
-  CS_GUARD_BEGIN
-  return cs_ba_sizes_impl(B, size_pose, size_lm);
   CS_GUARD_END("cs_ba_sizes")
 }
 
-static int cs_ba_solver_layout_impl(cs_ba* B, int* band_ld, int* team) {
+int cs_ba_solver_layout(cs_ba* B, int* band_ld, int* team) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   int rc = finalize_structure(B); if (rc) return rc;
   int rw = 0;
   if (band_ld) *band_ld = B->band_ld;
   if (team) *team = B->band_ld ? cs::ba_band_team(B->band_ld, &rw) : 0;
   return CS_OK;
-}
-int cs_ba_solver_layout(cs_ba* B, int* band_ld, int* team) {
-  CS_GUARD_BEGIN
-  return cs_ba_solver_layout_impl(B, band_ld, team);
   CS_GUARD_END("cs_ba_solver_layout")
 }
 
@@ -1422,7 +1348,8 @@ int cs_ba_get_system(cs_ba* B, double* Hpp, double* Hll9, double* Hpl18, double*
 // g2o's index order (as cs_ba_get_system), factorised by rocSOLVER, and the columns of the requested j-vertices are solved for: a call for
 // inspection and for covariance queries of a handful of vertices, not a per-iteration path.  Returns CS_ERR_NOT_RUN before cs_ba_build_system,
 // CS_ERR_INVALID_ARG for a fixed vertex or a point, *positive_definite = 0 (and CS_OK) when the factorisation fails (g2o: false).
-static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite) {
+int cs_ba_pose_marginals(cs_ba* B, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite) {
+  CS_GUARD_BEGIN
   if (!B || n_pairs < 0 || (n_pairs && (!class_i || !idx_i || !class_j || !idx_j || !out))) return CS_ERR_INVALID_ARG;
   if (positive_definite) *positive_definite = 1;
   if (int rn = need_system(B, "cs_ba_pose_marginals")) return rn;
@@ -1457,7 +1384,6 @@ static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, 
     for (int d = 0; d < col_dim[q]; d++) E[(c0 + d) * (size_t)n + col_base[q] + d] = 1.0;
   DBuf<double> dH, dE;
   DBuf<int> dinfo;
-  struct Rel { DBuf<double>&a, &b; DBuf<int>& c; ~Rel() { a.release(); b.release(); c.release(); } } rel{dH, dE, dinfo};
   int rc;
   if ((rc = dH.reserve((size_t)n * n)) || (rc = dE.reserve((size_t)n * m)) || (rc = dinfo.reserve(1))) return rc;
   CS_HIP_TRY(hipMemcpyAsync(dH.p, H.data(), 8 * H.size(), hipMemcpyHostToDevice, B->st));
@@ -1479,10 +1405,6 @@ static int cs_ba_pose_marginals_impl(cs_ba* B, int n_pairs, const int* class_i, 
     for (int r = 0; r < di; r++) for (int c = 0; c < dj; c++) out[o++] = E[(size_t)(rhs_of_pair[k] + c) * n + ci + r];
   }
   return CS_OK;
-}
-int cs_ba_pose_marginals(cs_ba* B, int n_pairs, const int* class_i, const int* idx_i, const int* class_j, const int* idx_j, double* out, int* positive_definite) {
-  CS_GUARD_BEGIN
-  return cs_ba_pose_marginals_impl(B, n_pairs, class_i, idx_i, class_j, idx_j, out, positive_definite);
   CS_GUARD_END("cs_ba_pose_marginals")
 }
 
@@ -1490,7 +1412,8 @@ int cs_ba_pose_marginals(cs_ba* B, int n_pairs, const int* class_i, const int* i
 // (n_red = cs_ba_reduced_size), its right-hand side, and the column of every camera / cuboid in it (solver order = reverse
 // Cuthill-McKee; -1: fixed; a cuboid column >= n_red: the cuboid was eliminated and is not part of S).  Runs the Schur-complement build
 // (block_solver.hpp:373-439) at `lambda` on the current linearisation; no factorisation.
-static int cs_ba_get_reduced_system_impl(cs_ba* B, double lambda, double* S_dense, double* rhs, int* cam_col, int* cub_col) {
+int cs_ba_get_reduced_system(cs_ba* B, double lambda, double* S_dense, double* rhs, int* cam_col, int* cub_col) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   if (int rn = need_system(B, "cs_ba_get_reduced_system")) return rn;
   if (B->shard_n > 1) { cs_set_error("cs_ba_get_reduced_system: not on a sharded handle (a rank holds a partial system)"); return CS_ERR_INVALID_ARG; }
@@ -1519,10 +1442,6 @@ static int cs_ba_get_reduced_system_impl(cs_ba* B, double lambda, double* S_dens
     }
   }
   return CS_OK;
-}
-int cs_ba_get_reduced_system(cs_ba* B, double lambda, double* S_dense, double* rhs, int* cam_col, int* cub_col) {
-  CS_GUARD_BEGIN
-  return cs_ba_get_reduced_system_impl(B, lambda, S_dense, rhs, cam_col, cub_col);
   CS_GUARD_END("cs_ba_get_reduced_system")
 }
 
@@ -1659,11 +1578,9 @@ static int check_finite_impl(cs_ba* B, char* report, int report_cap, int* n_bad_
   const cs::BaView& v = B->view;
   const int E = v.n_proj, n_edges = E + B->n_cub + B->n_odom;
   DBuf<double> chi; DBuf<int> out;
-  struct Free { DBuf<double>* a; DBuf<int>* b; ~Free() { a->release(); b->release(); } } guard{&chi, &out};
   if ((rc = chi.alloc(std::max(1, n_edges), B->st))) return rc;
   // (level-0 edges only: a level-1 edge is outside the active set and may well be non-finite)
   DBuf<unsigned char> lce, loe;
-  struct FreeL { DBuf<unsigned char>* a; DBuf<unsigned char>* b; ~FreeL() { a->release(); b->release(); } } guard_l{&lce, &loe};
   { const std::vector<unsigned char> l = combined_cuboid(B, &cs::EdgeClassHost::lvl); if (any_level(l) && (rc = lce.upload(l))) return rc; }
   if (any_level(B->pose_class(CS_EDGE_ODOM).lvl)) { std::vector<unsigned char> l(B->pose_class(CS_EDGE_ODOM).lvl); l.resize((size_t)B->n_odom, 0); if ((rc = loe.upload(l))) return rc; }
   cs::ba_launch_edge_chi(v, chi.p, B->st, lce.p, loe.p);
@@ -1734,7 +1651,8 @@ struct LevelTrailer { char magic[8]; int rk_off; int n[5]; };      // optional, 
 template <class T> bool wr(FILE* f, const std::vector<T>& a) { return a.empty() || fwrite(a.data(), sizeof(T), a.size(), f) == a.size(); }
 template <class T> bool rd(FILE* f, std::vector<T>& a, size_t n) { a.resize(n); return n == 0 || fread(a.data(), sizeof(T), n, f) == n; }
 }  // namespace
-static int cs_ba_dump_impl(cs_ba* B, const char* path) {
+int cs_ba_dump(cs_ba* B, const char* path) {
+  CS_GUARD_BEGIN
   if (!B || !path) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
@@ -1778,13 +1696,10 @@ static int cs_ba_dump_impl(cs_ba* B, const char* path) {
   ok = (fclose(f) == 0) && ok;
   if (!ok) { cs_set_error(std::string("cs_ba_dump: write to ") + path + " failed"); return CS_ERR_INVALID_ARG; }
   return CS_OK;
-}
-int cs_ba_dump(cs_ba* B, const char* path) {
-  CS_GUARD_BEGIN
-  return cs_ba_dump_impl(B, path);
   CS_GUARD_END("cs_ba_dump")
 }
-static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
+int cs_ba_load(const char* path, int device, cs_ba** out) {
+  CS_GUARD_BEGIN
   if (!path || !out) return CS_ERR_INVALID_ARG;
   *out = nullptr;
   FILE* f = fopen(path, "rb");
@@ -1818,7 +1733,7 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
   if (!ok || (nrks && nrks != nst) || (nrk && nrk != npe)) { cs_set_error("cs_ba_load: truncated or inconsistent file"); return CS_ERR_INVALID_ARG; }
   cs_ba* B = nullptr;
   int rc = cs_ba_create(device, &B); if (rc) return rc;
-  struct Guard { cs_ba* b; ~Guard() { if (b) cs_ba_destroy(b); } } g{B};
+  cs::Guard<cs_ba> g(B, cs_ba_destroy);
   if ((rc = cs_ba_set_vertices(B, cams.data(), camf.data(), nc, cubs.data(), cubf.data(), no, pts.data(), ptf.data(), np, cf))) return rc;
   // (the setters normalise quaternions; the dumped ones are normalised already and must come back with their exact bits)
   if (nc) CS_HIP_TRY(hipMemcpy(B->cams.p, cams.data(), 56 * (size_t)nc, hipMemcpyHostToDevice));
@@ -1845,12 +1760,7 @@ static int cs_ba_load_impl(const char* path, int device, cs_ba** out) {
       if ((LT.rk_off >> kEdgeClasses[i]) & 1) { if ((rc = cs_ba_set_kernels_enabled(B, kEdgeClasses[i], 0))) return rc; }
     }
   }
-  *out = B;
-  g.b = nullptr;
+  *out = g.disarm();
   return CS_OK;
-}
-int cs_ba_load(const char* path, int device, cs_ba** out) {
-  CS_GUARD_BEGIN
-  return cs_ba_load_impl(path, device, out);
   CS_GUARD_END("cs_ba_load")
 }

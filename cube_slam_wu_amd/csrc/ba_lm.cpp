@@ -88,7 +88,7 @@ cs::TrialFacts trial_facts(const cs_ba* B, cs_allreduce_fn fn) {
   f.seg_classes_full = B->n_seg == *std::max_element(B->seg_class, B->seg_class + 5);
   f.ext_edges = B->ext_n > 0; f.ext_terms_set = B->ext_terms_set; f.ext_fn_set = B->ext_fn != nullptr;
   f.stage_timing = B->stage_timing;
-  f.h_trial_present = B->h_trial != nullptr;
+  f.h_trial_present = B->h_trial.p != nullptr;
   { const char* e = getenv("CS_BA_FUSE_LIN"); f.fuse_lin_env = !e || atoi(e) != 0; }     // (read per call: the tests hold the two paths to each other in one process)
   f.nan_env_present = getenv("CS_BA_DEBUG_NAN") != nullptr;
   f.nan_scans_on = debug_nan_enabled();
@@ -146,13 +146,13 @@ struct Collectives {
   int reduce_scalars(double* v, size_t n, int op) {      // 0: done
     if (kind == cs::CollKind::callback) return fn(ctx, v, n, 0, op);
     if (kind == cs::CollKind::rccl) {
-      if (n > B->scalars_cap) return 1;
-      std::memcpy(B->h_scalars, v, n * sizeof(double));
-      if (hipMemcpyAsync(B->d_scalars.p, B->h_scalars, n * sizeof(double), hipMemcpyHostToDevice, B->st) != hipSuccess) return 1;
+      if (n > B->h_scalars.cap) return 1;
+      std::memcpy(B->h_scalars.p, v, n * sizeof(double));
+      if (hipMemcpyAsync(B->d_scalars.p, B->h_scalars.p, n * sizeof(double), hipMemcpyHostToDevice, B->st) != hipSuccess) return 1;
       if (ncclAllReduce(B->d_scalars.p, B->d_scalars.p, n, ncclDouble, op == 0 ? ncclSum : ncclMax, B->comm, B->st) != ncclSuccess) return 1;
-      if (hipMemcpyAsync(B->h_scalars, B->d_scalars.p, n * sizeof(double), hipMemcpyDeviceToHost, B->st) != hipSuccess) return 1;
+      if (hipMemcpyAsync(B->h_scalars.p, B->d_scalars.p, n * sizeof(double), hipMemcpyDeviceToHost, B->st) != hipSuccess) return 1;
       if (hipStreamSynchronize(B->st) != hipSuccess) return 1;
-      std::memcpy(v, B->h_scalars, n * sizeof(double));
+      std::memcpy(v, B->h_scalars.p, n * sizeof(double));
     }
     return 0;
   }
@@ -168,7 +168,7 @@ int share_cuboid_increments(cs_ba* B, Collectives& coll) {
 // A workgroup of a persistent factorisation waited ~1 s for its team (band_wait_ge): the device is shared with another persistent kernel.
 // h_status[0]: the band's / the interior's word; with_sep: h_status[2], the separator system's, counts too.
 int check_band_timeout(const cs_ba* B, bool with_sep) {
-  if (B->h_status[0] != cs::BAND_TIMEOUT_INFO && !(with_sep && B->h_status[2] == cs::BAND_TIMEOUT_INFO)) return CS_OK;
+  if (B->h_status.p[0] != cs::BAND_TIMEOUT_INFO && !(with_sep && B->h_status.p[2] == cs::BAND_TIMEOUT_INFO)) return CS_OK;
   cs_set_error("banded solver: team not co-resident (wait timed out); set CS_BA_FORCE_DENSE=1 on a shared device");
   return CS_ERR_HIP;
 }
@@ -178,9 +178,9 @@ int check_band_timeout(const cs_ba* B, bool with_sep) {
 int queue_reduce(cs_ba* B, Collectives& coll, const cs::SolveHead& head, double lambda) {
   cs::BaSidePrologue side_pro{};
   if (head.lean_head) {
-    B->h_lam[0] = lambda; B->h_lam[1] = B->shard_rank == 0 ? lambda : 0.0;
-    side_pro = cs::BaSidePrologue{B->d_lam.p, B->h_lam[0], B->h_lam[1], B->d_band_info.p, B->d_elim_fail.p, B->S.p, B->s_doubles + (size_t)B->n_pose};
-    if (!head.pro_in_reduce) cs::ba_launch_trial_prologue(B->d_lam.p, B->h_lam[0], B->h_lam[1], B->d_band_info.p, B->d_elim_fail.p, B->S.p, B->s_doubles + (size_t)B->n_pose, B->st);   // (+ [S | rhs] cleared: no fill of its own)
+    B->h_lam.p[0] = lambda; B->h_lam.p[1] = B->shard_rank == 0 ? lambda : 0.0;
+    side_pro = cs::BaSidePrologue{B->d_lam.p, B->h_lam.p[0], B->h_lam.p[1], B->d_band_info.p, B->d_elim_fail.p, B->S.p, B->s_doubles + (size_t)B->n_pose};
+    if (!head.pro_in_reduce) cs::ba_launch_trial_prologue(B->d_lam.p, B->h_lam.p[0], B->h_lam.p[1], B->d_band_info.p, B->d_elim_fail.p, B->S.p, B->s_doubles + (size_t)B->n_pose, B->st);   // (+ [S | rhs] cleared: no fill of its own)
   } else CS_TRY(put_lambda(B, lambda));
   BA_MARK(B, B->ev[2]);
   if (!head.lean_head) {
@@ -196,8 +196,8 @@ int queue_reduce(cs_ba* B, Collectives& coll, const cs::SolveHead& head, double 
   }
   cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join, head.pro_in_reduce ? &side_pro : nullptr);
   if (B->ext_n > 0 && B->ext_terms_set) cs::ba_launch_ext_offdiag(B->view, B->ext_groups, B->d_ext_gptr.p, B->d_ext_order.p, B->d_ext_e4.p, B->ext_Hij.p, B->st);
-  if (head.status_in_scalars) { B->h_status[0] = 0; B->h_status[1] = 0; }
-  else CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  if (head.status_in_scalars) { B->h_status.p[0] = 0; B->h_status.p[1] = 0; }
+  else CS_HIP_TRY(hipMemcpyAsync(B->h_status.p + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipGetLastError());
   if (head.sum_ranks) CS_TRY(coll.device_allreduce(B->S.p, B->s_doubles + B->n_pose));      // [S | rhs] in one message
   BA_MARK(B, B->ev[3]);
@@ -226,12 +226,12 @@ int solve_banded(cs_ba* B, Collectives& coll, const cs::SolveHead& head, bool* o
   }
   CS_TRY(share_cuboid_increments(B, coll));
   BA_MARK(B, B->ev[5]);
-  if (!head.status_in_scalars) CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_band_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  if (!head.status_in_scalars) CS_HIP_TRY(hipMemcpyAsync(B->h_status.p, B->d_band_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
   if (turn_out) { *turn_out = std::move(coop_turn); return CS_OK; }   // (the caller's sum kernel folds the two status words into the trial's scalars)
   cs::ba_launch_fail_flag(B->d_band_info.p, B->d_elim_fail.p, nullptr, B->d_scalars.p + 2, B->st);
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   CS_TRY(check_band_timeout(B, false));
-  if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
+  if (B->h_status.p[0] != 0 || B->h_status.p[1] != 0) *ok = false;
   return CS_OK;
 }
 
@@ -247,14 +247,14 @@ int solve_sparse(cs_ba* B, Collectives& coll, bool* ok) {
   CS_HIP_TRY(hipGetLastError());
   CS_TRY(share_cuboid_increments(B, coll));
   BA_MARK(B, B->ev[5]);
-  CS_TRY(B->solver.queue_status(B->h_status + 2, B->st));
+  CS_TRY(B->solver.queue_status(B->h_status.p + 2, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
-  const cs::SparseVerdict verdict = cs::sparse_verdict(B->h_status + 2);     // (the factorisation's word and the dense tail's pivot)
+  const cs::SparseVerdict verdict = cs::sparse_verdict(B->h_status.p + 2);     // (the factorisation's word and the dense tail's pivot)
   if (verdict == cs::SPARSE_TIMEOUT) {
     cs_set_error("sparse solver: grid not co-resident (wait timed out); set CS_BA_SPARSE=0 on a shared device");
     return CS_ERR_HIP;
   }
-  if (verdict != cs::SPARSE_OK || B->h_status[1] != 0) *ok = false;
+  if (verdict != cs::SPARSE_OK || B->h_status.p[1] != 0) *ok = false;
   return CS_OK;
 }
 
@@ -262,9 +262,9 @@ int solve_sparse(cs_ba* B, Collectives& coll, bool* ok) {
 int solve_dense(cs_ba* B, Collectives& coll, bool* ok) {
   const int n = B->n_red;
   CS_ROC_TRY(rocsolver_dpotrf(B->blas, rocblas_fill_upper, n, B->S.p, n, B->d_info.p));
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status.p, B->d_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
-  if (B->h_status[0] != 0 || B->h_status[1] != 0) *ok = false;
+  if (B->h_status.p[0] != 0 || B->h_status.p[1] != 0) *ok = false;
   else CS_ROC_TRY(rocsolver_dpotrs(B->blas, rocblas_fill_upper, n, 1, B->S.p, n, B->view.rhs, n));
   BA_MARK(B, B->ev[4]);
   // (sharded: the collective is issued whether or not THIS rank's factorisation went through -- the ranks decide together, in the loop)
@@ -321,7 +321,7 @@ int solve_device_sep(cs_ba* B, Collectives& coll, double lambda, bool* ok, std::
   CS_HIP_TRY(hipMemsetAsync(B->d_elim_fail.p, 0, sizeof(int), B->st));
   if (through_callback) CS_HIP_TRY(hipMemsetAsync(B->sep_msgs.p, 0, sizeof(double) * B->msg_doubles * (size_t)R, B->st));
   cs::ba_launch_reduce(B->view, B->d_lam.p, B->st, B->st2, B->ev_fork, B->ev_join);
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status.p + 1, B->d_elim_fail.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipGetLastError());
   BA_MARK(B, B->ev[3]);
   std::unique_lock<std::mutex> coop_turn(g_coop_mutex);
@@ -374,16 +374,16 @@ int solve_device_sep(cs_ba* B, Collectives& coll, double lambda, bool* ok, std::
   cs::ba_launch_fail_flag(B->d_int_info.p, B->d_elim_fail.p, B->d_sep_info.p, B->d_scalars.p + 2, B->st);
   // both persistent factorisations of the trial report their own time-out (a team that was not co-resident): the interior's and the
   // separator system's -- the latter must not be mistaken for "not positive definite" (LM would raise lambda and retry, ~1 s a trial)
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status, B->d_int_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
-  CS_HIP_TRY(hipMemcpyAsync(B->h_status + 2, B->d_sep_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status.p, B->d_int_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_status.p + 2, B->d_sep_info.p, sizeof(int), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipGetLastError());
   B->tm.n_solves++;
   if (turn_out) { if (coop_turn.owns_lock()) *turn_out = std::move(coop_turn); return CS_OK; }
-  CS_HIP_TRY(hipMemcpyAsync(B->h_scalars + 2, B->d_scalars.p + 2, sizeof(double), hipMemcpyDeviceToHost, B->st));
+  CS_HIP_TRY(hipMemcpyAsync(B->h_scalars.p + 2, B->d_scalars.p + 2, sizeof(double), hipMemcpyDeviceToHost, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   if (coop_turn.owns_lock()) coop_turn.unlock();
   CS_TRY(check_band_timeout(B, true));
-  if (B->h_scalars[2] != 0.0) *ok = false;
+  if (B->h_scalars.p[2] != 0.0) *ok = false;
   return collect_solve_times(B, true);
 }
 
@@ -414,15 +414,16 @@ int need_system(cs_ba* B, const char* who) {
 
 // lambda of the damped solve that is about to be queued: into the pinned word and, queued on the stream, into device memory.
 int put_lambda(cs_ba* B, double lambda) {
-  B->h_lam[0] = lambda;
-  B->h_lam[1] = B->shard_rank == 0 ? lambda : 0.0;      // x^T (lambda x + b): the poses' lambda x^2 is counted once, on rank 0
-  CS_HIP_TRY(hipMemcpyAsync(B->d_lam.p, B->h_lam, 2 * sizeof(double), hipMemcpyHostToDevice, B->st));
+  B->h_lam.p[0] = lambda;
+  B->h_lam.p[1] = B->shard_rank == 0 ? lambda : 0.0;      // x^T (lambda x + b): the poses' lambda x^2 is counted once, on rank 0
+  CS_HIP_TRY(hipMemcpyAsync(B->d_lam.p, B->h_lam.p, 2 * sizeof(double), hipMemcpyHostToDevice, B->st));
   return CS_OK;
 }
 
 extern "C" {
 
-static int cs_ba_compute_errors_impl(cs_ba* B, double* chi2) {
+int cs_ba_compute_errors(cs_ba* B, double* chi2) {
+  CS_GUARD_BEGIN
   if (!B || !chi2) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
@@ -431,14 +432,11 @@ static int cs_ba_compute_errors_impl(cs_ba* B, double* chi2) {
   if (B->ext_terms_set) *chi2 += B->ext_chi2;      // the host-evaluated edges' share (cs_ba_set_external_terms / _chi2)
   B->tm.errors_ms += now_ms() - t0;
   return rc;
-}
-int cs_ba_compute_errors(cs_ba* B, double* chi2) {
-  CS_GUARD_BEGIN
-  return cs_ba_compute_errors_impl(B, chi2);
   CS_GUARD_END("cs_ba_compute_errors")
 }
 
-static int cs_ba_build_system_impl(cs_ba* B) {
+int cs_ba_build_system(cs_ba* B) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   int rc = finalize_structure(B); if (rc) return rc;
@@ -446,14 +444,11 @@ static int cs_ba_build_system_impl(cs_ba* B) {
   rc = fetch_b(B); if (rc) return rc;
   debug_nan_scan(B, "after cs_ba_build_system");
   return CS_OK;
-}
-int cs_ba_build_system(cs_ba* B) {
-  CS_GUARD_BEGIN
-  return cs_ba_build_system_impl(B);
   CS_GUARD_END("cs_ba_build_system")
 }
 
-static int cs_ba_solve_impl(cs_ba* B, double lambda, int* pd) {
+int cs_ba_solve(cs_ba* B, double lambda, int* pd) {
+  CS_GUARD_BEGIN
   if (!B) return CS_ERR_INVALID_ARG;
   CS_HIP_TRY(hipSetDevice(B->device));
   if (int rn = need_system(B, "cs_ba_solve")) return rn;
@@ -463,10 +458,6 @@ static int cs_ba_solve_impl(cs_ba* B, double lambda, int* pd) {
   if (ok) debug_nan_scan(B, "after cs_ba_solve");
   if (pd) *pd = ok ? 1 : 0;
   return ok ? fetch_x(B) : CS_OK;
-}
-int cs_ba_solve(cs_ba* B, double lambda, int* pd) {
-  CS_GUARD_BEGIN
-  return cs_ba_solve_impl(B, lambda, pd);
   CS_GUARD_END("cs_ba_solve")
 }
 
@@ -563,9 +554,9 @@ int lambda_init(LmRun& R) {
     CS_HIP_TRY(hipMemsetAsync(B->d_scalars.p, 0, sizeof(double), B->st));
     cs::ba_launch_max_diag(B->view, B->d_scalars.p, B->st);
     CS_HIP_TRY(hipGetLastError());
-    CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, sizeof(double), hipMemcpyDeviceToHost, B->st));
+    CS_HIP_TRY(hipMemcpyAsync(B->h_scalars.p, B->d_scalars.p, sizeof(double), hipMemcpyDeviceToHost, B->st));
     CS_HIP_TRY(hipStreamSynchronize(B->st));
-    cs::lm_begin(R.lm, B->user_lambda_init, B->h_scalars[0]);
+    cs::lm_begin(R.lm, B->user_lambda_init, B->h_scalars.p[0]);
     return CS_OK;
   }
   CS_HIP_TRY(hipStreamSynchronize(B->st));   // the copies below run on the NULL stream, which B->st does not order with
@@ -605,17 +596,17 @@ int queue_trial(LmRun& R, bool spec, std::unique_lock<std::mutex>* turn) {
   cs::ba_launch_chi2(B->view, B->nb_chi, B->st);
   if (R.plan.sharded_sep) cs::ba_launch_sum2(B->chi_partial.p, B->n_chi_partials, B->scale_partial.p, cs::ba_scale_blocks(), B->d_scalars.p, B->st);   // (separator mode set its flag itself: three status words)
   else cs::ba_launch_sum2_flag(B->chi_partial.p, B->n_chi_partials, B->scale_partial.p, cs::ba_scale_blocks(), B->d_band_info.p, B->d_elim_fail.p, B->d_scalars.p, B->st,
-                               direct ? B->h_trial : nullptr, direct ? (B->trial_seq += 1.0) : 0.0);
+                               direct ? B->h_trial.p : nullptr, direct ? (B->trial_seq += 1.0) : 0.0);
   CS_HIP_TRY(hipGetLastError());
   if (R.plan.coll == cs::CollKind::rccl) BA_NCCL(ncclAllReduce(B->d_scalars.p, B->d_scalars.p, 3, ncclDouble, ncclSum, B->comm, B->st));
-  if (!direct) CS_HIP_TRY(hipMemcpyAsync(B->h_scalars, B->d_scalars.p, 3 * sizeof(double), hipMemcpyDeviceToHost, B->st));
+  if (!direct) CS_HIP_TRY(hipMemcpyAsync(B->h_scalars.p, B->d_scalars.p, 3 * sizeof(double), hipMemcpyDeviceToHost, B->st));
   BA_MARK(B, B->ev[7]);
   return CS_OK;
 }
 
 // the trial's scalars in pinned memory, written by its last kernel: polled, no runtime call
 int await_trial(cs_ba* B, double seq) {
-  volatile double* h = B->h_trial;
+  volatile double* h = B->h_trial.p;
   const double t_w = now_ms();
   unsigned spins = 0;
   while (h[3] != seq) {
@@ -645,8 +636,8 @@ int trial_on_stream(LmRun& R, bool spec, Trial& t) {
     B->view.fuse_lin = fl;       // (a retry of THIS iteration reduces the way this iteration linearised)
     if (rc) return rc;
   }
-  const double* hs = B->h_scalars;
-  if (R.plan.direct_scalars) { CS_TRY(await_trial(B, B->trial_seq)); hs = B->h_trial; }
+  const double* hs = B->h_scalars.p;
+  if (R.plan.direct_scalars) { CS_TRY(await_trial(B, B->trial_seq)); hs = B->h_trial.p; }
   else CS_HIP_TRY(hipStreamSynchronize(B->st));
   turn.unlock();
   CS_TRY(check_band_timeout(B, R.plan.sharded_sep));

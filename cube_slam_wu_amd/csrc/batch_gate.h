@@ -37,9 +37,14 @@ struct ChunkGate {
   }
 };
 
-// grow-only set of events of a producer's scratch: `done` (blocking sync, no timing) and a timed pair per chunk around its kernels
+// grow-only set of events of a producer's scratch: `done` (blocking sync, no timing) and a timed pair per chunk around its kernels.
+// Destroyed with the scratch; not copyable.  (Raw handles side by side: ChunkGate::watch walks `done` as an array.)
 struct ChunkEvents {
   std::vector<hipEvent_t> done, k0, k1;
+  ChunkEvents() = default;
+  ChunkEvents(const ChunkEvents&) = delete;
+  ChunkEvents& operator=(const ChunkEvents&) = delete;
+  ~ChunkEvents() { release(); }
   hipError_t reserve(int n) {
     while ((int)done.size() < n) {
       hipEvent_t a = nullptr, b = nullptr, c = nullptr;

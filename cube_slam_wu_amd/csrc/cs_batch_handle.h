@@ -12,8 +12,8 @@ namespace cs {
 
 struct BatchHandle {
   int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Stream st;                               // (first: it dies last, after the buffers its copies use)
+  Event ev0, ev1;
   DevBuf<unsigned char> d_in, d_out;       // one upload, one download
   PinBuf<unsigned char> h_in, h_out;       // pinned staging of the two
   double kernel_ms = 0, host_ms = 0;
@@ -32,10 +32,6 @@ void batch_destroy(H* B) {
   if (!B) return;
   (void)hipSetDevice(B->device);
   if (B->st) (void)hipStreamSynchronize(B->st);
-  B->d_in.release(); B->d_out.release(); B->h_in.release(); B->h_out.release();
-  if (B->ev0) (void)hipEventDestroy(B->ev0);
-  if (B->ev1) (void)hipEventDestroy(B->ev1);
-  if (B->st) (void)hipStreamDestroy(B->st);
   delete B;
 }
 
@@ -46,14 +42,13 @@ int batch_create(int device, H** out) {
   { const int rc = check_device(device); if (rc) return rc; }
   H* B = new (std::nothrow) H();
   if (!B) return CS_ERR_CAPACITY;
-  struct Guard { H* b; ~Guard() { if (b) batch_destroy(b); } } g{B};
+  Guard<H> g(B, batch_destroy<H>);
   B->device = device;
   CS_HIP_TRY(hipSetDevice(device));
-  CS_HIP_TRY(hipStreamCreateWithFlags(&B->st, hipStreamNonBlocking));
-  CS_HIP_TRY(hipEventCreate(&B->ev0));
-  CS_HIP_TRY(hipEventCreate(&B->ev1));
-  g.b = nullptr;
-  *out = B;
+  CS_TRY(B->st.create(hipStreamNonBlocking));
+  CS_TRY(B->ev0.create());
+  CS_TRY(B->ev1.create());
+  *out = g.disarm();
   return CS_OK;
 }
 

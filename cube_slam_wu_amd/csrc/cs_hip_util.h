@@ -23,8 +23,10 @@ void cs_set_error(const std::string& s);
     }                                                                          \
   } while (0)
 
+// `call` returns a CS_* code: pass a failure on
+#define CS_TRY(call) do { if (int _rc = (call)) return _rc; } while (0)
 // grow a DevBuf / PinBuf (below) inside a function that returns a CS_* code
-#define CS_ENSURE(buf, n) do { if (int _rc = (buf).ensure(n)) return _rc; } while (0)
+#define CS_ENSURE(buf, n) CS_TRY((buf).ensure(n))
 
 // No C++ exception may cross the C boundary (std::bad_alloc / std::length_error from a host buffer would terminate the caller).
 #define CS_GUARD_BEGIN try {
@@ -84,6 +86,40 @@ struct PinBuf {
     return CS_OK;
   }
   void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+// One stream / one event, destroyed with its holder; not copyable.  Each converts to the raw handle, so the HIP calls take it as written.
+// A holder declares its streams BEFORE everything that is queued on them: members die in reverse order, the streams last.
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  int create(unsigned flags) { CS_HIP_TRY(hipStreamCreateWithFlags(&s, flags)); return CS_OK; }
+  int create(unsigned flags, int priority) { CS_HIP_TRY(hipStreamCreateWithPriority(&s, flags, priority)); return CS_OK; }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  int create(unsigned flags = hipEventDefault) { CS_HIP_TRY(hipEventCreateWithFlags(&e, flags)); return CS_OK; }
+  operator hipEvent_t() const { return e; }
+};
+
+// What a create function has made so far: given back through the handle's own destroy function on every early return, kept by disarm().
+template <class H>
+struct Guard {
+  H* h;
+  void (*destroy)(H*);
+  Guard(H* h_, void (*destroy_)(H*)) : h(h_), destroy(destroy_) {}
+  Guard(const Guard&) = delete;
+  Guard& operator=(const Guard&) = delete;
+  ~Guard() { if (h) destroy(h); }
+  H* disarm() { H* r = h; h = nullptr; return r; }
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device's instance of a kernel: a handle on a second GPU of the

@@ -12,6 +12,17 @@
 #define CS_ROC_TRY(expr) do { rocblas_status _s = (expr); if (_s != rocblas_status_success) { cs_set_error(std::string(#expr) + ": rocblas status " + std::to_string((int)_s)); return CS_ERR_HIP; } } while (0)
 
 namespace cs {
+// a rocBLAS handle bound to one stream, destroyed with its holder (which declares it behind that stream); not copyable
+struct BlasHandle {
+  rocblas_handle h = nullptr;
+  BlasHandle() = default;
+  BlasHandle(const BlasHandle&) = delete;
+  BlasHandle& operator=(const BlasHandle&) = delete;
+  ~BlasHandle() { if (h) (void)rocblas_destroy_handle(h); }
+  int create(hipStream_t st) { CS_ROC_TRY(rocblas_create_handle(&h)); CS_ROC_TRY(rocblas_set_stream(h, st)); return CS_OK; }
+  operator rocblas_handle() const { return h; }
+};
+
 struct SparseSolver {
   SparsePlan plan; SparseGrids grids{0, 0};
   enum { NDIM, NCOL, SPTR, SROW, SROFF, PROW, RBASE, RENT, RPTR, RCOL, RPOS, ORDER, TCOL, N_TABLES };
@@ -71,7 +82,6 @@ struct SparseSolver {
     return CS_OK;
   }
   double fill(int n) const { return (double)plan.nvals / (0.5 * (double)n * (double)n); }
-  void release() { h_tab.release(); tab.release(); info.release(); L.release(); xs.release(); T.release(); done.release(); xdone.release(); }
 };
 
 // the two words of queue_status() (pgo_host.cpp's dense path feeds [0, rocSOLVER's info]); PIVOT: not positive definite, a failed trial; TIMEOUT: the grid was not co-resident

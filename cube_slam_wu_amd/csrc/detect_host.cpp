@@ -33,6 +33,7 @@
 #include <limits>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <numeric>
 #include <string>
@@ -365,7 +366,7 @@ struct cs_detector {
   hipStream_t stream2 = nullptr;   // vanishing points + corner construction: beside the line setup, or -- few queues -- the chain's stream
   hipStream_t stream3 = nullptr;   // line setup of the crowded ROIs: beside the line setup of all the others, or the chain's stream
   hipStream_t stream_hi = nullptr; // high priority: the small fetches of the tie boxes, which the host waits for while another batch's sweep owns the device
-  hipEvent_t ev[12] = {};
+  cs::Event ev[12];
   int n_threads = 1;
   int cpu_grant = 1;          // CPUs this process may use at once (cgroup quota, else the hardware threads)
   std::unique_ptr<WorkerPool> pool;
@@ -450,7 +451,7 @@ struct SweepBuffers {
   HeightCols fb_cols(long long p0, int V) const { return HeightCols{h_fb_dist.p + p0, h_fb_angle.p + p0, h_fb_skew.p + p0, h_fb_flag.p + p0, h_fb_slot.p + p0, V}; }
 };
 
-// One of the two in-flight chunks of the pipelined production path (pipe_launch / pipe_finish).  Its buffers free themselves.
+// One of the two in-flight chunks of the pipelined production path (pipe_launch / pipe_finish).  Its buffers and events free themselves.
 struct PipeSlot {
   SweepBuffers sb;
   DevBuf<unsigned char> tab_arena;       // a small call's tables in one block: one upload instead of ten (single-frame latency)
@@ -476,37 +477,32 @@ struct PipeSlot {
   PinBuf<unsigned long long> h_rp_pool_used;
   long long rp_pool_cap = 0;
   int rp_NT = 0, rp_YCAP = 0;
-  std::vector<hipEvent_t> rp_ev;     // 5 per round: start, corners + compaction, VP support, scorer, ranking + records
+  std::deque<cs::Event> rp_ev;       // (a deque: it grows without moving an event)  5 per round: start, corners + compaction, VP support, scorer, ranking + records
   PinBuf<cs::JobDesc> h_jobs_in, h_jobs_out;
   PinBuf<long long> h_slot_prefix;
   PinBuf<int> h_vp_prefix, h_top_x, h_box_job0, h_box_njobs;
   PinBuf<double> h_yaw, h_yaw_c, h_yaw_s;
-  hipEvent_t done = nullptr, ev[13] = {};   // 0-6: phase marks on the main stream; 7: inputs resident; 8-11: second stream (corner construction); 12: line setup of the crowded ROIs done (third stream)
+  cs::Event done, ev[13];                   // 0-6: phase marks on the main stream; 7: inputs resident; 8-11: second stream (corner construction); 12: line setup of the crowded ROIs done (third stream)
   cs::DetectDeviceView view{};
   int f0 = 0, f1 = 0, vp_total = 0;
   size_t nj = 0, nb = 0;
   long long slot_total = 0;
   bool in_flight = false;
   bool counted_busy = false;      // this sweep is in the detector's and the stream set's `busy` counts
-  ~PipeSlot() {
-    if (done) (void)hipEventDestroy(done);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : rp_ev) if (e) (void)hipEventDestroy(e);
-  }
 };
 
 struct BatchRunState;   // what a submitted (not yet collected) sweep keeps alive: camera caches, timing, the caller's output arrays
 struct cs_batch {
   cs_detector* det = nullptr;
   BatchRunState* run_state = nullptr;
+  cs::Stream copy_stream;                   // cs_batch_refill_gray's upload stream (first among the device resources: it dies after the image buffers it fills)
   PinBuf<cs::RpPose> h_rp;
   DevBuf<unsigned char> d_gray, d_cls;      // image input: gray images and Canny's class bytes (kept: a refilled batch reuses them)
   DevBuf<cs::EdgeRoi> d_edge_rois;
   // cs_batch_refill_gray: a second image buffer (the upload of the next images runs on copy_stream beside the sweep over the current maps),
   // what launch_edge_maps needs again, and the events that order copy -> front end -> the buffer's next upload
   DevBuf<unsigned char> d_gray2;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_edge_done[2] = {nullptr, nullptr};
+  cs::Event ev_copied[2], ev_edge_done[2];
   int gray_cur = 0, gray_w = 0, gray_h = 0, edge_n_rois = 0, edge_max_w = 1;
   long long edge_max_px = 1;
   bool gray_batch = false;
@@ -547,11 +543,7 @@ struct cs_batch {
   cs_detect_timing timing{};
   // (the caller has made the device current.)  The upload stream first: nothing may still be writing the image buffers when the
   // members -- every device and pinned buffer above -- free themselves after this body
-  ~cs_batch() {
-    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
-    for (auto& e : ev_copied) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_edge_done) if (e) (void)hipEventDestroy(e);
-  }
+  ~cs_batch() { if (copy_stream) (void)hipStreamSynchronize(copy_stream); }
 };
 
 void SweepBuffers::bind(cs::DetectDeviceView& v, const cs_batch& b, size_t n_jobs, size_t j0, size_t p0, unsigned char* io, const SmallCallArena* A) const {
@@ -704,8 +696,8 @@ int cs_detector_create(const cs_detect_params* params, int device, cs_detector**
   *out = nullptr;
   { const int rc = cs::check_device(device); if (rc) return rc; }
   CS_GUARD_BEGIN
-  struct Guard { cs_detector* d; ~Guard() { if (d) cs_detector_destroy(d); } } g{new cs_detector()};   // freed on every early return
-  cs_detector* d = g.d;
+  cs::Guard<cs_detector> g(new cs_detector(), cs_detector_destroy);   // freed on every early return
+  cs_detector* d = g.h;
   if (params) d->prm = *params; else cs_detect_default_params(&d->prm);
   if (d->prm.max_cuboid_num < 1 || !(d->prm.yaw_step_deg > 0) || !(d->prm.yaw_range_deg >= 0)) { cs_set_error("bad params"); return CS_ERR_INVALID_ARG; }
   d->device = device;
@@ -728,7 +720,7 @@ int cs_detector_create(const cs_detect_params* params, int device, cs_detector**
       d->stream = st4[0]; d->stream2 = st4[1]; d->stream3 = st4[2]; d->stream_hi = st4[3];
     }
   }
-  for (auto& e : d->ev) CS_HIP_TRY(hipEventCreate(&e));
+  for (auto& e : d->ev) CS_TRY(e.create());
   int hc = (int)std::thread::hardware_concurrency();
   // default worker count: 64 on an unrestricted 256-thread EPYC (beats 32 and 128); under a cgroup CPU quota three threads
   // per granted CPU (measured under a 16-CPU quota: 48 threads 187 k frames/s, 32: 184 k, 64: 171-181 k, 16: 166-172 k --
@@ -745,8 +737,7 @@ int cs_detector_create(const cs_detect_params* params, int device, cs_detector**
   }
   d->n_threads = d->prm.host_threads > 0 ? d->prm.host_threads : dflt;
   d->pool.reset(new WorkerPool(d->n_threads - 1));
-  *out = d;
-  g.d = nullptr;
+  *out = g.disarm();
   return CS_OK;
   CS_GUARD_END("cs_detector_create")
 }
@@ -754,14 +745,15 @@ int cs_detector_create(const cs_detect_params* params, int device, cs_detector**
 void cs_detector_destroy(cs_detector* d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
+  // (the streams are shared: what this detector queued outside a batch -- a front end, a segment producer's tail -- is waited for here,
+  // before the resident batch and the producers' scratch go)
+  if (d->stream) (void)hipStreamSynchronize(d->stream);
   if (d->single) { cs_batch_destroy(d->single); d->single = nullptr; }
   if (d->lines_scratch && d->lines_free) { d->lines_free(d->lines_scratch); d->lines_scratch = nullptr; }
   if (d->lsd_scratch && d->lsd_free) { d->lsd_free(d->lsd_scratch); d->lsd_scratch = nullptr; }
   if (d->lbd_scratch && d->lbd_free) { d->lbd_free(d->lbd_scratch); d->lbd_scratch = nullptr; }
-  for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
   if (d->streams) {
-    // (the streams are shared: what this detector queued outside a batch -- a front end, a segment producer's tail -- is waited for here)
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    // the five working streams are this detector's own or the shared set's, so they stay raw and go here
     if (d->streams->own_streams)
       for (hipStream_t st : {d->stream, d->stream2, d->stream3, d->stream_idle, d->stream_hi}) if (st) (void)hipStreamDestroy(st);
     stream_set_release(d->streams, d->stream_slot);
@@ -784,12 +776,11 @@ static int batch_create_impl(cs_detector* d, const cs_frame_desc* fr, const unsi
   *out = nullptr;
   CS_GUARD_BEGIN
   CS_HIP_TRY(hipSetDevice(d->device));
-  struct Guard { cs_batch* b; ~Guard() { if (b) cs_batch_destroy(b); } } g{new cs_batch()};   // freed on every early return
-  g.b->det = d;
-  int rc = batch_fill(d, g.b, fr, grays, n_frames);
+  cs::Guard<cs_batch> g(new cs_batch(), cs_batch_destroy);   // freed on every early return
+  g.h->det = d;
+  int rc = batch_fill(d, g.h, fr, grays, n_frames);
   if (rc) return rc;
-  *out = g.b;
-  g.b = nullptr;
+  *out = g.disarm();
   return CS_OK;
   CS_GUARD_END("cs_batch_create")
 }
@@ -967,9 +958,9 @@ int cs_batch_refill_gray(cs_detector* d, cs_batch* b, const unsigned char* const
     // (lowest priority: bulk traffic, and a hardware queue of its own)
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    CS_HIP_TRY(hipStreamCreateWithPriority(&b->copy_stream, hipStreamNonBlocking, prio_least));
-    for (auto& e : b->ev_copied) CS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : b->ev_edge_done) CS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    CS_TRY(b->copy_stream.create(hipStreamNonBlocking, prio_least));
+    for (auto& e : b->ev_copied) CS_TRY(e.create(hipEventDisableTiming));
+    for (auto& e : b->ev_edge_done) CS_TRY(e.create(hipEventDisableTiming));
     CS_HIP_TRY(hipEventRecord(b->ev_edge_done[0], d->stream));      // buffer 0's reader so far: the front end of cs_batch_create_gray (finished)
     CS_HIP_TRY(hipEventRecord(b->ev_edge_done[1], d->stream));
   }
@@ -1131,7 +1122,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   hipStream_t st = d->stream;
   const int KMAX = P.max_cuboid_num;
   double t0 = now_ms(), tq = t0;
-  if (!S.done) { CS_HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) CS_HIP_TRY(hipEventCreate(&e)); }
+  if (!S.done) { CS_TRY(S.done.create()); for (auto& e : S.ev) CS_TRY(e.create()); }
   S.f0 = f0; S.f1 = f1;
   const int nf = f1 - f0;
   // ---- per frame, in parallel and straight into the pinned staging pools: job descriptors + sample lists (everything
@@ -1406,7 +1397,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   hipStream_t st = d->stream;
   const int KMAX = P.max_cuboid_num, NF = b->n_frames, MB = b->max_boxes;
   double t0 = now_ms();
-  if (!S.done) { CS_HIP_TRY(hipEventCreate(&S.done)); for (auto& e : S.ev) CS_HIP_TRY(hipEventCreate(&e)); }
+  if (!S.done) { CS_TRY(S.done.create()); for (auto& e : S.ev) CS_TRY(e.create()); }
   S.f0 = 0; S.f1 = NF;
   // ---- yaw lists: NT = 1 + max RP per frame, YCAP samples each
   int max_rp = 1;
@@ -1507,7 +1498,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   CS_ENSURE(B.fb_dist, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_angle, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_skew, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_flag, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_slot, (size_t)S.rp_pool_cap + 1);
   CS_ENSURE(S.rp_box_base, nb + 1); CS_ENSURE(S.rp_pool_used, 1); CS_ENSURE(S.h_rp_box_base, nb + 1); CS_ENSURE(S.h_rp_pool_used, 1); CS_ENSURE(S.h_rp_last_slot, nb + 1); CS_ENSURE(S.h_jobs_out, nj + 1);
   CS_ENSURE(S.rp_cur_idx, (size_t)NF + 1); CS_ENSURE(S.rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.rp_maps, 3 * (size_t)MB * NF + 1); CS_ENSURE(S.rp_raw_euler, 3 * (size_t)NF + 1);
-  while (S.rp_ev.size() < 5 * (size_t)MB) { hipEvent_t e = nullptr; CS_HIP_TRY(hipEventCreate(&e)); S.rp_ev.push_back(e); }
+  while (S.rp_ev.size() < 5 * (size_t)MB) { S.rp_ev.emplace_back(); if (int rc = S.rp_ev.back().create()) { S.rp_ev.pop_back(); return rc; } }
   std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);      // all rounds of this batch back to back in the shared streams (see pipe_launch)
   if (!d->streams->own_streams) enqueue.lock();
   hipStream_t stB = nullptr, stC = nullptr;      // (corner construction stays on the chain here: stB is not used)
@@ -1533,7 +1524,7 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   for (int r = 0; r < MB; r++) {
     const PipeSlot::RpRound& Rr = S.rp_rounds[r];
     if (Rr.nj == 0) continue;
-    hipEvent_t* re = &S.rp_ev[5 * (size_t)r];
+    const auto re = S.rp_ev.begin() + 5 * (size_t)r;
     cs::DetectDeviceView v;
     B.bind(v, *b, Rr.nj, Rr.j0, Rr.j0 + r);      // (the prefixes carry one closing entry per earlier round)
     if (r > 0) {      // the carried yaw: this round's jobs get the list the previous round's result selects
@@ -1603,7 +1594,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
     CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
     for (int r = 0; r < MB; r++) {
       if (S.rp_rounds[r].nj == 0) continue;
-      hipEvent_t* re = &S.rp_ev[5 * (size_t)r];
+      const auto re = S.rp_ev.begin() + 5 * (size_t)r;
       CS_HIP_TRY(hipEventElapsedTime(&ms, re[0], re[1])); tm.cand_kernel_ms += ms;      // vanishing points, corners, compaction
       CS_HIP_TRY(hipEventElapsedTime(&ms, re[1], re[2])); tm.vp_kernel_ms += ms;
       CS_HIP_TRY(hipEventElapsedTime(&ms, re[2], re[3])); tm.score_kernel_ms += ms;

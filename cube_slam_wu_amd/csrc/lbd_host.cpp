@@ -35,28 +35,20 @@ struct LbdScratch {
   bool weights_up = false;
   cs::DevBuf<unsigned> d_q, d_t;
   cs::DevBuf<int> d_ptr, d_out;                          // q_ptr | t_ptr; train_idx | dist | dist2
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  cs::Event ev0, ev1;
   double describe_ms = -1, match_ms = -1;
   std::vector<cs::LbdLine> lines;
   std::vector<unsigned char> desc;
   std::vector<int> out;
 };
-void lbd_scratch_free(void* p) {
-  LbdScratch* S = (LbdScratch*)p;
-  if (!S) return;
-  S->d_gray.release(); S->d_p3.release(); S->d_desc32.release(); S->d_desc72.release(); S->d_lines.release(); S->d_w.release();
-  S->d_q.release(); S->d_t.release(); S->d_ptr.release(); S->d_out.release();
-  if (S->ev0) (void)hipEventDestroy(S->ev0);
-  if (S->ev1) (void)hipEventDestroy(S->ev1);
-  delete S;
-}
+void lbd_scratch_free(void* p) { delete (LbdScratch*)p; }      // (cs_detector_destroy has made the device current and waited for the stream)
 LbdScratch& scratch_of(cs_detector* d) {
   void** slot = cs_internal_detector_lbd_slot(d, lbd_scratch_free);
   if (!*slot) *slot = new LbdScratch();
   return *(LbdScratch*)*slot;
 }
 int events_of(LbdScratch& S) {
-  if (!S.ev0) { CS_HIP_TRY(hipEventCreate(&S.ev0)); CS_HIP_TRY(hipEventCreate(&S.ev1)); }
+  if (!S.ev0) { CS_TRY(S.ev0.create()); CS_TRY(S.ev1.create()); }
   return CS_OK;
 }
 

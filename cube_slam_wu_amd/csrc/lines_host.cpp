@@ -242,19 +242,11 @@ struct LinesScratch {
   cs::PinBuf<unsigned char> h_in;    // the batch's images side by side (one upload)
   size_t cap = 0;                    // pixels x images the four hold (they grow together)
   cs::ChunkEvents chunks;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  cs::Event ev0, ev1;
   double device_ms = 0, host_ms = 0, total_ms = 0;
   int n_images = 0;
 };
-void lines_scratch_free(void* p) {
-  LinesScratch* S = (LinesScratch*)p;
-  if (!S) return;
-  S->d_gray.release(); S->d_pk.release(); S->h_pin.release(); S->h_in.release();
-  S->chunks.release();
-  if (S->ev0) (void)hipEventDestroy(S->ev0);
-  if (S->ev1) (void)hipEventDestroy(S->ev1);
-  delete S;
-}
+void lines_scratch_free(void* p) { delete (LinesScratch*)p; }      // (cs_detector_destroy has made the device current and waited for the stream)
 
 // the sequential half of one image: routing, fitting, validation, end points (all of it independent of the other images)
 // extra (optional, cap records): each kept segment's lineDirection_ and numOfPixels (OctaveKeyLines :1081-1082), what the descriptor needs beside the end points
@@ -352,7 +344,7 @@ extern "C" int cs_internal_detect_lines_batch(cs_detector* d, const unsigned cha
       if (rc) return rc;
       S.cap = need;
     }
-    if (!S.ev0) { CS_HIP_TRY(hipEventCreate(&S.ev0)); CS_HIP_TRY(hipEventCreate(&S.ev1)); }
+    if (!S.ev0) { CS_TRY(S.ev0.create()); CS_TRY(S.ev1.create()); }
     int k[3];
     cs::lines_blur_taps(k);
     const cs::LineMaps dm{S.d_pk.p};

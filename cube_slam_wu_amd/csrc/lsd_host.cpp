@@ -462,18 +462,10 @@ struct LsdScratch {
   size_t cap_in = 0, cap_out = 0;   // input pixels x images (d_gray, d_blur, h_in grow together); bytes of the planes (d_out, h_out)
   cs::ChunkEvents chunks;
   int tab_w = 0, tab_h = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  cs::Event ev0, ev1;
   double device_ms = 0, host_ms = 0, total_ms = 0;
 };
-void lsd_scratch_free(void* p) {
-  LsdScratch* S = (LsdScratch*)p;
-  if (!S) return;
-  S->d_gray.release(); S->d_blur.release(); S->d_out.release(); S->d_tab.release(); S->h_out.release(); S->h_in.release();
-  S->chunks.release();
-  if (S->ev0) (void)hipEventDestroy(S->ev0);
-  if (S->ev1) (void)hipEventDestroy(S->ev1);
-  delete S;
-}
+void lsd_scratch_free(void* p) { delete (LsdScratch*)p; }      // (cs_detector_destroy has made the device current and waited for the stream)
 
 }  // namespace
 
@@ -510,7 +502,7 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
       if (rc) return rc;
       S.cap_out = out_stride * (size_t)n_images;
     }
-    if (!S.ev0) { CS_HIP_TRY(hipEventCreate(&S.ev0)); CS_HIP_TRY(hipEventCreate(&S.ev1)); }
+    if (!S.ev0) { CS_TRY(S.ev0.create()); CS_TRY(S.ev1.create()); }
     // resize's tables for this size: source offset and the two float weights per scaled column / row (pixel centres, INTER_LINEAR)
     const size_t tab_bytes = (size_t)(Ws + Hs) * (sizeof(int) + 2 * sizeof(float));
     if (S.tab_w != img_w || S.tab_h != img_h) {

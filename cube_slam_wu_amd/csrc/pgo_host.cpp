@@ -28,8 +28,8 @@ static const size_t PGO_DENSE_BUDGET_BYTES = (size_t)4 << 30;
 
 struct cs_pgo {
   int device = 0;
-  hipStream_t st = nullptr;
-  rocblas_handle blas = nullptr;
+  cs::Stream st;            // (first: it dies last, after the BLAS handle bound to it and every buffer its work uses)
+  cs::BlasHandle blas;
   int nv = 0, ne = 0, n = 0;
   bool have_vertices = false, have_edges = false, ran = false;
   std::vector<unsigned char> fixed, fix_scale;
@@ -190,14 +190,12 @@ int cs_pgo_create(int device, cs_pgo** out) {
   { const int rc = cs::check_device(device); if (rc) return rc; }
   cs_pgo* G = new (std::nothrow) cs_pgo();
   if (!G) return CS_ERR_CAPACITY;
-  struct Guard { cs_pgo* g; ~Guard() { if (g) cs_pgo_destroy(g); } } guard{G};
+  cs::Guard<cs_pgo> guard(G, cs_pgo_destroy);
   G->device = device;
   CS_HIP_TRY(hipSetDevice(device));
-  CS_HIP_TRY(hipStreamCreateWithFlags(&G->st, hipStreamNonBlocking));
-  CS_ROC_TRY(rocblas_create_handle(&G->blas));
-  CS_ROC_TRY(rocblas_set_stream(G->blas, G->st));
-  guard.g = nullptr;
-  *out = G;
+  CS_TRY(G->st.create(hipStreamNonBlocking));
+  CS_TRY(G->blas.create(G->st));
+  *out = guard.disarm();
   return CS_OK;
 }
 
@@ -205,15 +203,6 @@ void cs_pgo_destroy(cs_pgo* G) {
   if (!G) return;
   (void)hipSetDevice(G->device);
   if (G->st) (void)hipStreamSynchronize(G->st);
-  if (G->blas) (void)rocblas_destroy_handle(G->blas);
-  cs::DevBuf<double>* dd[] = {&G->est, &G->est_init, &G->est_bak, &G->meas, &G->info, &G->err, &G->Ji, &G->Jj, &G->Hii, &G->Hij, &G->Hjj, &G->bi, &G->bj, &G->chi2_each,
-                              &G->S, &G->b, &G->x, &G->diag, &G->rec, &G->io};
-  for (auto* d : dd) d->release();
-  cs::DevBuf<int>* di[] = {&G->vcol, &G->ei, &G->ej, &G->inc_ptr, &G->inc_edge, &G->d_info, &G->io_i};
-  for (auto* d : di) d->release();
-  G->d_fix_scale.release(); G->inc_side.release(); G->solver.release();
-  G->h_rec.release(); G->h_status.release();
-  if (G->st) (void)hipStreamDestroy(G->st);
   delete G;
 }
 

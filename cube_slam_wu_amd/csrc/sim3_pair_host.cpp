@@ -186,7 +186,7 @@ int cs_sim3_pairs_linearize(int device, int n_pairs, const double* S12_in, const
   cs_sim3_pairs* B = nullptr;
   rc = cs_sim3_pairs_create(device, &B);
   if (rc) return rc;
-  struct Guard { cs_sim3_pairs* b; ~Guard() { cs_sim3_pairs_destroy(b); } } g{B};
+  cs::Guard<cs_sim3_pairs> g(B, cs_sim3_pairs_destroy);     // (this call's own handle: never disarmed)
   const size_t np = (size_t)n_pairs;
   const InLayout L = in_layout(np, n);
   cs::Layout out;
