@@ -32,213 +32,31 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
+#include "ba_proj_edge.h"
 #include "ba_types.h"
 #include "band_solver.h"
 #include "cs_wave.h"
 
 namespace cs {
 
-// rho, rho' of a projection edge's squared error (cs_robust.h): Huber-or-none from the delta alone, any kernel through the kind array
-// (off: the class's kernels are switched off in place, cs_ba_set_kernels_enabled -- the RK_NONE branch, whatever the records hold)
-__device__ __forceinline__ void proj_rho(const int* rk, int k, double delta, bool off, double e, double& rho0, double& rho1) {
-  if (off) { rho0 = e; rho1 = 1.0; }
-  else if (rk) robust_rho(rk[k], delta, e, rho0, rho1);
-  else huber_rho(e, delta, rho0, rho1);
-}
-// An edge's level (OptimizableGraph::Edge::setLevel, core/optimizable_graph.h) rides in the SIGN BIT of its kernel-width record (pm_huber /
-// cm_huber, widths are >= +0.0 otherwise): the kernels already read that record, so a graph without a level-1 edge reads nothing more and computes
-// what it always did.  A level-1 edge is outside the active set: every site that evaluates an edge SELECTS zeros for it before the projection is
-// used -- its point may sit at depth 0 or behind the camera, and 0 * inf must not reach a sum.
-__device__ __forceinline__ bool edge_off(double width_record) { return __double2hiint(width_record) < 0; }
-// The select of the linearising sites (proj_linearize / proj_linearize_any): a level-1 edge's camera-frame point is replaced by (0, 0, 1) BEFORE it is
-// projected, so its error and Jacobians are finite whatever the estimates are, and its rho' and chi2 are then selected to zero -- Omega and -Omega e are
-// weighted by an exact 0 and every product the callers form from the ProjLin is an exact (signed) zero.  Selects, not an early return with a zeroed
-// ProjLin: a second exit made the compiler keep the camera-frame point in scratch memory in every kernel that inlines these functions, and zeroing the
-// error as well cost ba_lin_schur_kernel<1, true> and <5, false> a wavefront of occupancy (169 and 257 registers against the steps at 168 and 256).
-__device__ __forceinline__ void level1_point(bool off, double* pc) { if (off) { pc[0] = 0.0; pc[1] = 0.0; pc[2] = 1.0; } }
-
-struct ProjLin {
-  double e[2];     // error
-  double Jp[6];    // 2x3  d e / d point
-  double Jc[12];   // 2x6  d e / d camera (rot 0..2, trans 3..5)
-  double Wm[4];    // rho' * Omega
-  double r[2];     // -rho' * Omega e
-  double chi;      // rho0
-};
-
-__device__ __forceinline__ void proj_linearize(const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k, int rk_off, ProjLin& L) {
-  // (proj_error's arithmetic, with the level's select between its two steps)
-  double pc[3];
-  pose_map(T, X, pc);
-  const bool off = edge_off(huber);
-  level1_point(off, pc);
-  L.e[0] = uv[0] - (pc[0] / pc[2] * intr[0] + intr[2]);
-  L.e[1] = uv[1] - (pc[1] / pc[2] * intr[1] + intr[3]);
-  double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z, fx = intr[0], fy = intr[1];
-  double tmp[6] = {fx, 0, -x / z * fx, 0, fy, -y / z * fy};
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      double s = 0;
-#pragma unroll
-      for (int q = 0; q < 3; q++) s += (-1. / z * tmp[3 * i + q]) * R[3 * q + j];
-      L.Jp[3 * i + j] = s;
-    }
-  L.Jc[0] = x * y / z_2 * fx; L.Jc[1] = -(1 + (x * x / z_2)) * fx; L.Jc[2] = y / z * fx; L.Jc[3] = -1. / z * fx; L.Jc[4] = 0; L.Jc[5] = x / z_2 * fx;
-  L.Jc[6] = (1 + y * y / z_2) * fy; L.Jc[7] = -x * y / z_2 * fy; L.Jc[8] = -x / z * fy; L.Jc[9] = 0; L.Jc[10] = -1. / z * fy; L.Jc[11] = y / z_2 * fy;
-  double c = L.e[0] * (info[0] * L.e[0] + info[1] * L.e[1]) + L.e[1] * (info[2] * L.e[0] + info[3] * L.e[1]);
-  double rho1;
-  proj_rho(rk, k, huber, (rk_off & RK_OFF_MONO) != 0, c, L.chi, rho1);
-  if (off) { rho1 = 0.0; L.chi = 0.0; }
-#pragma unroll
-  for (int i = 0; i < 4; i++) L.Wm[i] = rho1 * info[i];
-  L.r[0] = -(info[0] * L.e[0] + info[1] * L.e[1]) * rho1;
-  L.r[1] = -(info[2] * L.e[0] + info[3] * L.e[1]) * rho1;
-}
-
-// ---- stereo projection edges (EdgeStereoSE3ProjectXYZ) ----------------------------------------------------------------------------
-// Every kernel that evaluates a projection edge has a STEREO instantiation, launched for graphs that hold a stereo edge (v.pm_kind != nullptr);
-// a graph without one runs the STEREO = false code, which is the mono code above and nothing else.  Inside a stereo instantiation a lane
-// branches on its edge's kind while it linearises; both kinds then share one set of 3-row products -- a mono edge fills rows 0 and 1 and
-// leaves row 2 (error, Jacobians, information) zero, which adds exact zeros to the sums the mono code forms.
-struct ProjLin3 {
-  double e[3];     // error (u_left, v, u_right)
-  double Jp[9];    // 3x3  d e / d point
-  double Jc[18];   // 3x6  d e / d camera
-  double Wm[9];    // rho' * Omega
-  double r[3];     // -rho' * Omega e
-  double chi;      // rho0
-};
-// a stereo edge's record beyond the mono one: 3 x 3 information + bf, the graph's one record or the edge's own
-__device__ __forceinline__ const double* stereo_rec(const double* sinfo_u, const double* sinfo, size_t k) { return sinfo_u ? sinfo_u : sinfo + 10 * k; }
-__device__ __forceinline__ double quad3(const double* e, const double* info) {
-  return e[0] * ((info[0] * e[0] + info[1] * e[1]) + info[2] * e[2]) + e[1] * ((info[3] * e[0] + info[4] * e[1]) + info[5] * e[2]) + e[2] * ((info[6] * e[0] + info[7] * e[1]) + info[8] * e[2]);
-}
-// Either kind of edge of a stereo graph in the 3-row form, from the fields both kinds have (uv, info: the mono edge's 2 x 2; intr: fx fy cx cy)
-// and the stereo ones (u_right; srec = 3 x 3 information, bf).  What the two kinds share is formed once, in front of the per-lane branch: the
-// camera-frame point and rows 0 and 1 of the camera Jacobian, which both linearizeOplus write alike (types_six_dof_expmap.cpp:171-183, :259-271).
-// Stereo: the error with its single-precision invz / bf (cs_se3.h), the point Jacobian in ITS form (:247-257: -fx R(0,j) / z + fx x R(2,j) / z^2,
-// not the mono edge's -1/z * tmp * R), row 2 of both Jacobians (:255-257, :273-278), all double.  Mono: proj_linearize's arithmetic, row 2 zero.
-// Then the weights of constructQuadraticForm (base_binary_edge.hpp:54-120).
-__device__ __forceinline__ void proj_linearize_any(bool stereo, const Pose& T, const double* R, const double* X, const double* uv, const double* info, const double* intr, double huber, const int* rk, int k, int rk_off,
-                                                   double ur, const double* srec, ProjLin3& L) {
-  double pc[3];
-  pose_map(T, X, pc);
-  const bool off = edge_off(huber);
-  level1_point(off, pc);
-  const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z, fx = intr[0], fy = intr[1];
-  L.Jc[0] = x * y / z_2 * fx; L.Jc[1] = -(1 + (x * x / z_2)) * fx; L.Jc[2] = y / z * fx; L.Jc[3] = -1. / z * fx; L.Jc[4] = 0; L.Jc[5] = x / z_2 * fx;
-  L.Jc[6] = (1 + y * y / z_2) * fy; L.Jc[7] = -x * y / z_2 * fy; L.Jc[8] = -x / z * fy; L.Jc[9] = 0; L.Jc[10] = -1. / z * fy; L.Jc[11] = y / z_2 * fy;
-  double e0, e1, e2, c, W[9], jp[9], jc2[6];
-  if (stereo) {
-    const double bf = srec[9];
-    double e[3];
-    stereo_cam_project_error(pc, uv, ur, intr, bf, e);
-    e0 = e[0]; e1 = e[1]; e2 = e[2];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      jp[j] = -fx * R[j] / z + fx * x * R[6 + j] / z_2;
-      jp[3 + j] = -fy * R[3 + j] / z + fy * y * R[6 + j] / z_2;
-      jp[6 + j] = jp[j] - bf * R[6 + j] / z_2;
-    }
-    jc2[0] = L.Jc[0] - bf * y / z_2; jc2[1] = L.Jc[1] + bf * x / z_2; jc2[2] = L.Jc[2]; jc2[3] = L.Jc[3]; jc2[4] = 0; jc2[5] = L.Jc[5] - bf / z_2;
-#pragma unroll
-    for (int i = 0; i < 9; i++) W[i] = srec[i];
-  } else {
-    e0 = uv[0] - (x / z * fx + intr[2]);
-    e1 = uv[1] - (y / z * fy + intr[3]);
-    e2 = 0;
-    const double tmp[6] = {fx, 0, -x / z * fx, 0, fy, -y / z * fy};
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        double s = 0;
-#pragma unroll
-        for (int q = 0; q < 3; q++) s += (-1. / z * tmp[3 * i + q]) * R[3 * q + j];
-        jp[3 * i + j] = s;
-      }
-    jp[6] = 0; jp[7] = 0; jp[8] = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) jc2[i] = 0;
-    W[0] = info[0]; W[1] = info[1]; W[2] = 0; W[3] = info[2]; W[4] = info[3]; W[5] = 0; W[6] = 0; W[7] = 0; W[8] = 0;
-  }
-  L.e[0] = e0; L.e[1] = e1; L.e[2] = e2;
-#pragma unroll
-  for (int i = 0; i < 9; i++) L.Jp[i] = jp[i];
-#pragma unroll
-  for (int i = 0; i < 6; i++) L.Jc[12 + i] = jc2[i];
-  // (a mono edge: the zeros of row / column 2 add nothing -- e^T Omega e, rho' Omega and -rho' Omega e are the 2 x 2 ones)
-  c = quad3(L.e, W);
-  double rho1;
-  proj_rho(rk, k, huber, (rk_off & (stereo ? RK_OFF_STEREO : RK_OFF_MONO)) != 0, c, L.chi, rho1);
-  if (off) { rho1 = 0.0; L.chi = 0.0; }
-#pragma unroll
-  for (int i = 0; i < 9; i++) L.Wm[i] = rho1 * W[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++) L.r[i] = -((W[3 * i] * L.e[0] + W[3 * i + 1] * L.e[1]) + W[3 * i + 2] * L.e[2]) * rho1;
-}
-// the products of constructQuadraticForm on the 3-row form, written as the mono sites write theirs (row sums left to right)
-__device__ __forceinline__ void lin3_cam_terms(const ProjLin3& L, double* A21, double* b6) {   // A_ii (upper triangle) += J_c^T W J_c, b_i += J_c^T r
-  int q = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    const double jw0 = (L.Jc[i] * L.Wm[0] + L.Jc[6 + i] * L.Wm[3]) + L.Jc[12 + i] * L.Wm[6];
-    const double jw1 = (L.Jc[i] * L.Wm[1] + L.Jc[6 + i] * L.Wm[4]) + L.Jc[12 + i] * L.Wm[7];
-    const double jw2 = (L.Jc[i] * L.Wm[2] + L.Jc[6 + i] * L.Wm[5]) + L.Jc[12 + i] * L.Wm[8];
-#pragma unroll
-    for (int j = i; j < 6; j++) A21[q++] += (jw0 * L.Jc[j] + jw1 * L.Jc[6 + j]) + jw2 * L.Jc[12 + j];
-    b6[i] += (L.Jc[i] * L.r[0] + L.Jc[6 + i] * L.r[1]) + L.Jc[12 + i] * L.r[2];
-  }
-}
-__device__ __forceinline__ void lin3_point_terms(const ProjLin3& L, double* H6, double* b3) {   // J_p^T W J_p (upper triangle), J_p^T r
-  double pw[9];  // Jp^T W (3x3)
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) pw[3 * i + d] = (L.Jp[i] * L.Wm[d] + L.Jp[3 + i] * L.Wm[3 + d]) + L.Jp[6 + i] * L.Wm[6 + d];
-  int q = 0;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-#pragma unroll
-    for (int j = i; j < 3; j++) H6[q++] = (pw[3 * i] * L.Jp[j] + pw[3 * i + 1] * L.Jp[3 + j]) + pw[3 * i + 2] * L.Jp[6 + j];
-    b3[i] = (L.Jp[i] * L.r[0] + L.Jp[3 + i] * L.r[1]) + L.Jp[6 + i] * L.r[2];
-  }
-}
-__device__ __forceinline__ double lin3_hpl(const ProjLin3& L, int i, int j) {   // (J_c^T W J_p)(i, j)
-  const double jw0 = (L.Jc[i] * L.Wm[0] + L.Jc[6 + i] * L.Wm[3]) + L.Jc[12 + i] * L.Wm[6];
-  const double jw1 = (L.Jc[i] * L.Wm[1] + L.Jc[6 + i] * L.Wm[4]) + L.Jc[12 + i] * L.Wm[7];
-  const double jw2 = (L.Jc[i] * L.Wm[2] + L.Jc[6 + i] * L.Wm[5]) + L.Jc[12 + i] * L.Wm[8];
-  return (jw0 * L.Jp[j] + jw1 * L.Jp[3 + j]) + jw2 * L.Jp[6 + j];
-}
+// A projection edge -- its records, its plain chi2, its linearisation and the products of its quadratic form -- is stated in ba_proj_edge.h;
+// the kernels below hold what is theirs: which edges a lane takes, where the sums go.  STEREO picks the 3-row form (ROWS) and the table's
+// stereo arrays; there is no second wording of anything beside it.
 
 // ---------------------------------------------------------------------------------------------------
 // (device bodies with the block index / block count as arguments: ba_chi2_kernel below runs both kinds of block in ONE launch)
 template <bool STEREO>
 __device__ __forceinline__ void chi2_proj_block(const BaView& v, int bid, int nblocks, double* ws) {
+  const ProjTable<STEREO> E(v, PointMajor{});
   double acc = 0;
   for (int k = bid * 256 + threadIdx.x; k < v.n_proj; k += nblocks * 256) {
-    if (edge_off(v.pm_huber[k])) continue;      // level 1: no share in chi2, its error never formed
-    Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
-    if constexpr (STEREO) {
-      if (v.pm_kind[k]) {
-        double e3[3], pc3[3], rho0, rho1;
-        const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
-        stereo_proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.pm_ur[k], v.intr_u ? v.intr_u : v.pm_intr + 4 * k, srec[9], e3, pc3);
-        proj_rho(v.pm_rk, k, v.pm_huber[k], (v.rk_off & RK_OFF_STEREO) != 0, quad3(e3, srec), rho0, rho1);
-        acc += rho0;
-        continue;
-      }
-    }
-    double e[2], pc[3];
-    proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, e, pc);
-    const double* info = v.info_u ? v.info_u : v.pm_info + 4 * k;
-    double c = e[0] * (info[0] * e[0] + info[1] * e[1]) + e[1] * (info[2] * e[0] + info[3] * e[1]);
-    double rho0, rho1;
-    proj_rho(v.pm_rk, k, v.pm_huber[k], (v.rk_off & RK_OFF_MONO) != 0, c, rho0, rho1);
+    if (edge_off(E.width[k])) continue;      // level 1: no share in chi2, its error never formed
+    double pc[3], rho0, rho1;
+    const double c = proj_edge_chi(E, k, pc);
+    proj_rho(E.rk, k, E.width[k], E.kernels_off(E.stereo(k)), c, rho0, rho1);
     acc += rho0;
   }
   acc = wave_sum(acc);
@@ -351,26 +169,11 @@ __global__ __launch_bounds__(256) void ba_lin_cam_kernel(BaView v) {
 #pragma unroll
   for (int i = 0; i < 6; i++) b[i] = 0;
   int e0 = v.cam_ptr[c], e1 = v.cam_ptr[c + 1];
+  const ProjTable<STEREO> E(v, CameraMajor{});
   for (int k = e0 + threadIdx.x; k < e1; k += 256) {
-    if constexpr (STEREO) {
-      ProjLin3 L3;
-      proj_linearize_any(v.cm_kind[k] != 0, T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k, v.rk_off,
-                         v.cm_ur[k], stereo_rec(v.sinfo_u, v.cm_sinfo, (size_t)k), L3);
-      lin3_cam_terms(L3, A, b);
-      continue;
-    }
-    ProjLin L;
-    proj_linearize(T, R, v.points + 3 * v.cm_pt[k], v.cm_uv + 2 * k, v.info_u ? v.info_u : v.cm_info + 4 * k, v.intr_u ? v.intr_u : v.cm_intr + 4 * k, v.cm_huber[k], v.cm_rk, k, v.rk_off, L);
-    // JW = Jc^T W (6x2)
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-      double jw0 = L.Jc[i] * L.Wm[0] + L.Jc[6 + i] * L.Wm[2];
-      double jw1 = L.Jc[i] * L.Wm[1] + L.Jc[6 + i] * L.Wm[3];
-#pragma unroll
-      for (int j = i; j < 6; j++) A[q++] += jw0 * L.Jc[j] + jw1 * L.Jc[6 + j];
-      b[i] += L.Jc[i] * L.r[0] + L.Jc[6 + i] * L.r[1];
-    }
+    ProjLinT<STEREO ? 3 : 2> L;
+    proj_linearize(E, k, T, R, E.point_of(k), L);
+    lin_cam_terms(L, A, b);
   }
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -407,43 +210,12 @@ __device__ __forceinline__ void lin_pt_edge(const BaView& v, int k, bool free_pt
   Pose T = pose_load(v.cams + 7 * c);
   double R[9];
   pose_rotmat(T, R);
-  if constexpr (STEREO) {
-    ProjLin3 L3;
-    proj_linearize_any(v.pm_kind[k] != 0, T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k, v.rk_off,
-                       v.pm_ur[k], stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k), L3);
-    lin3_point_terms(L3, H6, b3);
-    double* Wk3 = v.W + 18 * (size_t)k;
-    const bool both3 = free_pt && v.cam_col[c] >= 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) Wk3[3 * i + j] = both3 ? lin3_hpl(L3, i, j) : 0.0;
-    return;
-  }
-  ProjLin L;
-  proj_linearize(T, R, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.info_u ? v.info_u : v.pm_info + 4 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, v.pm_huber[k], v.pm_rk, k, v.rk_off, L);
-  double pw[6];  // Jp^T W (3x2)
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    pw[2 * i] = L.Jp[i] * L.Wm[0] + L.Jp[3 + i] * L.Wm[2];
-    pw[2 * i + 1] = L.Jp[i] * L.Wm[1] + L.Jp[3 + i] * L.Wm[3];
-  }
-  int q = 0;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-#pragma unroll
-    for (int j = i; j < 3; j++) H6[q++] = pw[2 * i] * L.Jp[j] + pw[2 * i + 1] * L.Jp[3 + j];
-    b3[i] = L.Jp[i] * L.r[0] + L.Jp[3 + i] * L.r[1];
-  }
+  const ProjTable<STEREO> E(v, PointMajor{});
+  ProjLinT<STEREO ? 3 : 2> L;
+  proj_linearize(E, k, T, R, E.point_of(k), L);
+  lin_point_terms(L, H6, b3);
   double* Wk = v.W + 18 * (size_t)k;
-  const bool both = free_pt && v.cam_col[c] >= 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    const double jw0 = L.Jc[i] * L.Wm[0] + L.Jc[6 + i] * L.Wm[2];
-    const double jw1 = L.Jc[i] * L.Wm[1] + L.Jc[6 + i] * L.Wm[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) Wk[3 * i + j] = both ? (jw0 * L.Jp[j] + jw1 * L.Jp[3 + j]) : 0.0;
-  }
+  lin_hpl(L, free_pt && v.cam_col[c] >= 0, [&](int i, int j) -> double& { return Wk[3 * i + j]; });
 }
 
 template <bool STEREO>
@@ -1022,6 +794,7 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
   // (a stereo graph's record adds the edge's kind and u_right; the 3 x 3 information and bf are read where a stereo lane linearises -- ten more
   // doubles in the record would be held across the chunk's products by every lane, mono ones included)
   struct EdgeRec { double X[3], uv[2], info[4], intr[4], huber; int p, e; double ur; int kind; };
+  const ProjTable<STEREO> E(v, PointMajor{});
   auto fetch = [&](int c0) {
     EdgeRec r;
     const int ncl = min(C, n - c0);
@@ -1032,9 +805,9 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
 #pragma unroll
     for (int q = 0; q < 2; q++) r.uv[q] = v.pm_uv[2 * (size_t)r.e + q];
 #pragma unroll
-    for (int q = 0; q < 4; q++) { r.info[q] = v.info_u ? v.info_u[q] : v.pm_info[4 * (size_t)r.e + q]; r.intr[q] = v.intr_u ? v.intr_u[q] : v.pm_intr[4 * (size_t)r.e + q]; }
+    for (int q = 0; q < 4; q++) { r.info[q] = E.info_at(r.e, q); r.intr[q] = E.intr_at(r.e, q); }
     r.huber = v.pm_huber[r.e];
-    if constexpr (STEREO) { r.ur = v.pm_ur[r.e]; r.kind = v.pm_kind[r.e]; } else { r.ur = 0.0; r.kind = 0; }
+    r.ur = E.ur(r.e); r.kind = E.kind_of(r.e);
     return r;
   };
   EdgeRec rec = fetch(0);
@@ -1047,33 +820,9 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
       const int p = rec.p, e = rec.e;
 #pragma unroll
       for (int q = 0; q < 9; q++) h9[q] = 0.0;
-      if constexpr (STEREO) {
-        if (lc < ncl) {
-          ProjLin3 L3;
-          proj_linearize_any(rec.kind != 0, T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, v.rk_off, rec.ur, stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)e), L3);
-          lin3_point_terms(L3, h9, h9 + 6);
-          const bool both3 = cam_free && v.pt_free[p] != 0;
-#pragma unroll
-          for (int q = 0; q < 6; q++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) Wl[3 * q + j][lane] = both3 ? lin3_hpl(L3, q, j) : 0.0;
-        }
-      } else if (lc < ncl) {
-        ProjLin L;
-        proj_linearize(T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, v.pm_rk, e, v.rk_off, L);
-        double pw[6];  // Jp^T W (3x2)
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-          pw[2 * q] = L.Jp[q] * L.Wm[0] + L.Jp[3 + q] * L.Wm[2];
-          pw[2 * q + 1] = L.Jp[q] * L.Wm[1] + L.Jp[3 + q] * L.Wm[3];
-        }
-        int o = 0;
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-#pragma unroll
-          for (int j = q; j < 3; j++) h9[o++] = pw[2 * q] * L.Jp[j] + pw[2 * q + 1] * L.Jp[3 + j];
-          h9[6 + q] = L.Jp[q] * L.r[0] + L.Jp[3 + q] * L.r[1];
-        }
+      if (lc < ncl) {
+        ProjLinT<STEREO ? 3 : 2> L;
+        proj_linearize(T, R, rec.X, rec.uv, rec.info, rec.intr, rec.huber, E.rk, e, E.rk_off, rec.kind != 0, rec.ur, E.srec(e), L);
         // (H_pl goes out as 18 eight-byte stores per lane.  Round 5 measured the alternative -- the chunk's records through LDS as runs of 18 k
         // contiguous doubles, 64 consecutive doubles per store instruction --: the same HBM traffic by the counters (251 MB read, 227 MB written per
         // launch at C4: L2 merges the partial lines either way) and a kernel 7 % slower for the index arithmetic; dropped.  What the kernel
@@ -1085,14 +834,17 @@ __device__ __forceinline__ void ba_lin_schur_segment(const BaView& v, double lam
         const bool both = cam_free && v.pt_free[p] != 0;
 #pragma unroll
         for (int q = 0; q < 6; q++) {
-          const double jw0 = L.Jc[q] * L.Wm[0] + L.Jc[6 + q] * L.Wm[2];
-          const double jw1 = L.Jc[q] * L.Wm[1] + L.Jc[6 + q] * L.Wm[3];
+          double h3[3];
+          lin_hpl_row(L, q, h3);
 #pragma unroll
           for (int j = 0; j < 3; j++) {
-            const double w = both ? (jw0 * L.Jp[j] + jw1 * L.Jp[3 + j]) : 0.0;
+            const double w = both ? h3[j] : 0.0;
             Wl[3 * q + j][lane] = w;
           }
         }
+        // (behind the H_pl rows, not in front of them: in front, the 2-row form's <5> instance needs 137 registers beside its 120 accumulator
+        // registers -- one more than two wavefronts per SIMD allow; here 131)
+        lin_point_terms(L, h9, h9 + 6);
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1473,11 +1225,12 @@ __device__ __forceinline__ void backsub_point(const BaView& v, int p) {
 }
 
 // The same with H_pl formed on the spot (the fused linearise-in-Schur trials, which never write it): per edge the camera, the point, the
-// measurement -- proj_linearize and the J_c^T (rho' Omega) J_p product exactly as ba_lin_schur_segment / lin_pt_edge form them, then the same
+// measurement -- the proj_linearize and the lin_hpl that ba_lin_schur_segment / lin_pt_edge call (ba_proj_edge.h), then the same
 // sums in the same order as the kernel above: the same x_l bit for bit (tests/test_ba_gpu.py holds the LM run to the classic pair).
 template <bool STEREO>
 __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
   if (p >= v.np) return;
+  const ProjTable<STEREO> E(v, PointMajor{});
   double cl[3] = {v.bl[3 * p], v.bl[3 * p + 1], v.bl[3 * p + 2]};
   const bool free_pt = v.pt_free[p] != 0;
   const double X[3] = {v.points[3 * (size_t)p], v.points[3 * (size_t)p + 1], v.points[3 * (size_t)p + 2]};
@@ -1489,25 +1242,9 @@ __device__ __forceinline__ void backsub_lin_point(const BaView& v, int p) {
     double R[9];
     pose_rotmat(T, R);
     double Wk[18];
-    if constexpr (STEREO) {
-      ProjLin3 L3;
-      proj_linearize_any(v.pm_kind[k] != 0, T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k, v.rk_off,
-                         v.pm_ur[k], stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k), L3);
-#pragma unroll
-      for (int q = 0; q < 6; q++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Wk[3 * q + j] = free_pt ? lin3_hpl(L3, q, j) : 0.0;
-    } else {
-    ProjLin L;
-    proj_linearize(T, R, X, v.pm_uv + 2 * (size_t)k, v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k, v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k, v.pm_huber[k], v.pm_rk, k, v.rk_off, L);
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-      const double jw0 = L.Jc[q] * L.Wm[0] + L.Jc[6 + q] * L.Wm[2];
-      const double jw1 = L.Jc[q] * L.Wm[1] + L.Jc[6 + q] * L.Wm[3];
-#pragma unroll
-      for (int j = 0; j < 3; j++) Wk[3 * q + j] = free_pt ? (jw0 * L.Jp[j] + jw1 * L.Jp[3 + j]) : 0.0;      // (the camera is free here)
-    }
-    }
+    ProjLinT<STEREO ? 3 : 2> L;
+    proj_linearize(E, k, T, R, X, L);
+    lin_hpl(L, free_pt, [&](int q, int j) -> double& { return Wk[3 * q + j]; });      // (the camera is free here)
     const double* xp = v.rhs + col;
 #pragma unroll
     for (int cc = 0; cc < 3; cc++) {
@@ -1609,10 +1346,13 @@ void ba_launch_gather_rows(const double* src, const int* idx, int n, int width, 
 
 int ba_chi2_blocks(int n_proj) { int nb = (n_proj + 255) / 256; return nb < 1 ? 1 : (nb > 2048 ? 2048 : nb); }
 
+// which instantiation of a projection-edge kernel a graph runs: f(std::true_type) where it holds a stereo edge, f(std::false_type) where not
+template <class F>
+static void with_edge_kinds(const BaView& v, F&& f) { if (v.pm_kind) f(std::true_type{}); else f(std::false_type{}); }
+
 void ba_launch_chi2(const BaView& v, int nb_proj, hipStream_t st) {
   const int ne = v.n_cub + v.n_odom, nb_pose = (ne + 63) / 64;
-  if (v.pm_kind) hipLaunchKernelGGL(ba_chi2_kernel<true>, dim3(nb_proj + (nb_pose + 3) / 4), dim3(256), 0, st, v, nb_proj, nb_pose);
-  else hipLaunchKernelGGL(ba_chi2_kernel<false>, dim3(nb_proj + (nb_pose + 3) / 4), dim3(256), 0, st, v, nb_proj, nb_pose);
+  with_edge_kinds(v, [&](auto stereo) { hipLaunchKernelGGL(ba_chi2_kernel<decltype(stereo)::value>, dim3(nb_proj + (nb_pose + 3) / 4), dim3(256), 0, st, v, nb_proj, nb_pose); });
 }
 // the numeric-Jacobian edges (cuboid, odometry: few edges, long dependent chains) run beside the projection edges (many edges, short
 // chains) on a second stream; ba_accum_pose_kernel needs both
@@ -1637,20 +1377,16 @@ void ba_launch_linearize(const BaView& v, hipStream_t st, hipStream_t st2, hipEv
   // stream -- rounds 3-4 -- they waited for wave slots beside the cuboid edges for 112 us, behind them they lengthen the main stream's chain)
   if (v.n_odom > 0 && ob == 0) hipLaunchKernelGGL(ba_odom_edge_kernel, dim3((v.n_odom + 3) / 4), dim3(64), 0, se, v);
   if (side) (void)hipEventRecord(ev_join, st2);
+  auto launch_lin_pt = [&](hipStream_t s) {
+    with_edge_kinds(v, [&](auto stereo) { hipLaunchKernelGGL(ba_lin_pt_kernel<decltype(stereo)::value>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, s, v); });
+  };
   if (side3) {
     (void)hipStreamWaitEvent(st3, ev_fork, 0);
-    if (v.pm_kind) hipLaunchKernelGGL(ba_lin_pt_kernel<true>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st3, v);
-    else hipLaunchKernelGGL(ba_lin_pt_kernel<false>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st3, v);
+    launch_lin_pt(st3);
     (void)hipEventRecord(ev_join3, st3);
   }
-  if (v.n_proj > 0 || v.nc > 0) {
-    if (v.pm_kind) hipLaunchKernelGGL(ba_lin_cam_kernel<true>, dim3(v.nc), dim3(256), 0, st, v);
-    else hipLaunchKernelGGL(ba_lin_cam_kernel<false>, dim3(v.nc), dim3(256), 0, st, v);
-  }
-  if (!side3 && lin_pt) {
-    if (v.pm_kind) hipLaunchKernelGGL(ba_lin_pt_kernel<true>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st, v);
-    else hipLaunchKernelGGL(ba_lin_pt_kernel<false>, dim3((v.np + LIN_PT_GROUP - 1) / LIN_PT_GROUP), dim3(256), 0, st, v);
-  }
+  if (v.n_proj > 0 || v.nc > 0) with_edge_kinds(v, [&](auto stereo) { hipLaunchKernelGGL(ba_lin_cam_kernel<decltype(stereo)::value>, dim3(v.nc), dim3(256), 0, st, v); });
+  if (!side3 && lin_pt) launch_lin_pt(st);
   if (side) (void)hipStreamWaitEvent(st, ev_join, 0);
   if (side3) (void)hipStreamWaitEvent(st, ev_join3, 0);
   hipLaunchKernelGGL(ba_accum_pose_kernel, dim3(v.nc + v.no), dim3(128), 0, st, v, 0);
@@ -1689,13 +1425,11 @@ void ba_launch_reduce(const BaView& v, const double* lambda, hipStream_t st, hip
         if (c1 > c0) c0 = 0;
         const int cb[6] = {0, c0, c1, c2, c3, c4};
         auto launch = [&](auto kern, int lo, int hi) { if (hi > lo) hipLaunchKernelGGL(kern, dim3((hi - lo + 3) / 4), dim3(256), 0, st, v, lin_lamp, lo, hi, lin_lam); };
-        if (v.pm_kind) {
-          launch(ba_lin_schur_kernel<1, true>, cb[0], cb[1]); launch(ba_lin_schur_kernel<2, true>, cb[1], cb[2]); launch(ba_lin_schur_kernel<3, true>, cb[2], cb[3]);
-          launch(ba_lin_schur_kernel<4, true>, cb[3], cb[4]); launch(ba_lin_schur_kernel<5, true>, cb[4], cb[5]);
-        } else {
-          launch(ba_lin_schur_kernel<1, false>, cb[0], cb[1]); launch(ba_lin_schur_kernel<2, false>, cb[1], cb[2]); launch(ba_lin_schur_kernel<3, false>, cb[2], cb[3]);
-          launch(ba_lin_schur_kernel<4, false>, cb[3], cb[4]); launch(ba_lin_schur_kernel<5, false>, cb[4], cb[5]);
-        }
+        with_edge_kinds(v, [&](auto stereo) {
+          constexpr bool S = decltype(stereo)::value;
+          launch(ba_lin_schur_kernel<1, S>, cb[0], cb[1]); launch(ba_lin_schur_kernel<2, S>, cb[1], cb[2]); launch(ba_lin_schur_kernel<3, S>, cb[2], cb[3]);
+          launch(ba_lin_schur_kernel<4, S>, cb[3], cb[4]); launch(ba_lin_schur_kernel<5, S>, cb[4], cb[5]);
+        });
       } else {
         if (c0 > 0) hipLaunchKernelGGL(ba_schur_fused_kernel<1>, dim3((c0 + 3) / 4), dim3(256), 0, st, v, lambda, 0, c0);
         if (c1 > c0) hipLaunchKernelGGL(ba_schur_fused_kernel<2>, dim3((c1 - c0 + 3) / 4), dim3(256), 0, st, v, lambda, c0, c1);
@@ -1748,20 +1482,8 @@ __global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out,
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k < v.n_proj) {
     if (edge_off(v.pm_huber[k])) { out[k] = 0.0; return; }
-    Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
-    if constexpr (STEREO) {
-      if (v.pm_kind[k]) {
-        double e3[3], pc3[3];
-        const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
-        stereo_proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.pm_ur[k], v.intr_u ? v.intr_u : v.pm_intr + 4 * k, srec[9], e3, pc3);
-        out[k] = quad3(e3, srec);
-        return;
-      }
-    }
-    double e[2], pc[3];
-    proj_error(T, v.points + 3 * v.pm_pt[k], v.pm_uv + 2 * k, v.intr_u ? v.intr_u : v.pm_intr + 4 * k, e, pc);
-    const double* info = v.info_u ? v.info_u : v.pm_info + 4 * k;
-    out[k] = e[0] * (info[0] * e[0] + info[1] * e[1]) + e[1] * (info[2] * e[0] + info[3] * e[1]);
+    double pc[3];
+    out[k] = proj_edge_chi(ProjTable<STEREO>(v, PointMajor{}), k, pc);
     return;
   }
   const int q = k - v.n_proj;
@@ -1785,8 +1507,7 @@ __global__ __launch_bounds__(256) void ba_edge_chi_kernel(BaView v, double* out,
 void ba_launch_edge_chi(const BaView& v, double* out, hipStream_t st, const unsigned char* lvl_ce, const unsigned char* lvl_oe) {
   const int n = v.n_proj + v.n_cub + v.n_odom;
   if (n <= 0) return;
-  if (v.pm_kind) hipLaunchKernelGGL(ba_edge_chi_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, v, out, lvl_ce, lvl_oe);
-  else hipLaunchKernelGGL(ba_edge_chi_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, v, out, lvl_ce, lvl_oe);
+  with_edge_kinds(v, [&](auto stereo) { hipLaunchKernelGGL(ba_edge_chi_kernel<decltype(stereo)::value>, dim3((n + 255) / 256), dim3(256), 0, st, v, out, lvl_ce, lvl_oe); });
 }
 
 // ---- edge levels (OptimizableGraph::Edge::setLevel) of the projection edges: see edge_off ------------------------------------------------
@@ -1831,27 +1552,16 @@ void ba_launch_invert_perm(const int* perm, int n, int* inv, hipStream_t st) {
 template <bool STEREO>
 __global__ __launch_bounds__(256) void ba_classify_kernel(BaView v, BaClassify a) {
   const int k = blockIdx.x * 256 + threadIdx.x;
+  const ProjTable<STEREO> E(v, PointMajor{});
   bool stereo = false, out = false;
   if (k < v.n_proj) {
-    if constexpr (STEREO) stereo = v.pm_kind[k] != 0;
+    stereo = E.stereo(k);
     const double h = a.pm_huber[k], thr = stereo ? a.thr_stereo : a.thr_mono;
     const bool was = edge_off(h), test = thr > 0 && !(a.sticky && was);
     out = was;
     if (test || a.chi_out) {
-      const Pose T = pose_load(v.cams + 7 * v.pm_cam[k]);
-      const double* intr = v.intr_u ? v.intr_u : v.pm_intr + 4 * (size_t)k;
-      double chi, pc[3];
-      if (stereo) {
-        double e3[3];
-        const double* srec = stereo_rec(v.sinfo_u, v.pm_sinfo, (size_t)k);
-        stereo_proj_error(T, v.points + 3 * (size_t)v.pm_pt[k], v.pm_uv + 2 * (size_t)k, v.pm_ur[k], intr, srec[9], e3, pc);
-        chi = quad3(e3, srec);
-      } else {
-        double e[2];
-        proj_error(T, v.points + 3 * (size_t)v.pm_pt[k], v.pm_uv + 2 * (size_t)k, intr, e, pc);
-        const double* info = v.info_u ? v.info_u : v.pm_info + 4 * (size_t)k;
-        chi = e[0] * (info[0] * e[0] + info[1] * e[1]) + e[1] * (info[2] * e[0] + info[3] * e[1]);
-      }
+      double pc[3];
+      const double chi = proj_edge_chi(E, k, pc);
       const int s = a.src[k];
       if (a.chi_out) a.chi_out[s] = chi;
       if (test) {
@@ -1873,8 +1583,7 @@ __global__ __launch_bounds__(256) void ba_classify_kernel(BaView v, BaClassify a
 }
 void ba_launch_classify(const BaView& v, const BaClassify& a, hipStream_t st) {
   if (v.n_proj <= 0) return;
-  if (v.pm_kind) hipLaunchKernelGGL(ba_classify_kernel<true>, dim3((unsigned)((v.n_proj + 255) / 256)), dim3(256), 0, st, v, a);
-  else hipLaunchKernelGGL(ba_classify_kernel<false>, dim3((unsigned)((v.n_proj + 255) / 256)), dim3(256), 0, st, v, a);
+  with_edge_kinds(v, [&](auto stereo) { hipLaunchKernelGGL(ba_classify_kernel<decltype(stereo)::value>, dim3((unsigned)((v.n_proj + 255) / 256)), dim3(256), 0, st, v, a); });
 }
 
 // ---- external (host-evaluated) edges: cs_ba_set_external_edges / cs_ba_set_external_terms ---------------------------------------
@@ -2079,9 +1788,8 @@ void ba_launch_scale(const BaView& v, const double* lambda, double* partial, hip
 void ba_launch_backsub(const BaView& v, hipStream_t st) {
   const int ncb = (v.elim && v.no > 0) ? (v.no + 3) / 4 : 0, npb = (v.np + 255) / 256;
   if (ncb + npb <= 0) return;
-  if (v.fuse_lin && v.pm_kind) hipLaunchKernelGGL((ba_backsub_all_kernel<true, true>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);
-  else if (v.fuse_lin) hipLaunchKernelGGL((ba_backsub_all_kernel<true, false>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);      // (the trial's Schur kernels did not write H_pl)
-  else hipLaunchKernelGGL((ba_backsub_all_kernel<false, false>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);
+  if (!v.fuse_lin) hipLaunchKernelGGL((ba_backsub_all_kernel<false, false>), dim3(ncb + npb), dim3(256), 0, st, v, ncb);
+  else with_edge_kinds(v, [&](auto stereo) { hipLaunchKernelGGL((ba_backsub_all_kernel<true, decltype(stereo)::value>), dim3(ncb + npb), dim3(256), 0, st, v, ncb); });      // (the trial's Schur kernels did not write H_pl)
 }
 void ba_launch_scale_update(const BaView& v, const double* lambda, double* partial, hipStream_t st, double* bak_cams, double* bak_points, double* bak_cubes) {
   const int n = v.np + v.nc + v.no;

@@ -202,6 +202,80 @@ def test_all_stereo_and_all_mono_graphs():
     A.close(); B.close()
 
 
+def _two_components(seed=5):
+    """Component A: cameras 0..11 (0 fixed), landmarks 0..59, mono edges only -- landmarks 0..47 seen by all 12 cameras (576 edges in the first
+    group of 48 landmarks: more than ba_lin_pt_kernel stages, so the group walks its edges per landmark), landmarks 48..59 with tracks of 2..5 views.
+    Component B: cameras 12..14 (12 fixed), landmarks 60..65, stereo edges only, every landmark seen by the three cameras.  No shared vertex."""
+    rng = np.random.default_rng(seed)
+    nc, n_pts = 15, 66
+    cams = np.zeros((nc, 7)); cams[:, 6] = 1.0
+    cams[:, :3] = rng.uniform(-0.3, 0.3, (nc, 3))
+    q = np.concatenate([rng.uniform(-0.03, 0.03, (nc, 3)), np.ones((nc, 1))], axis=1)
+    cams[:, 3:] = q / np.linalg.norm(q, axis=1, keepdims=True)
+    pts = np.concatenate([rng.uniform(-2, 2, (n_pts, 2)), rng.uniform(4, 8, (n_pts, 1))], axis=1)
+    fx, fy, cx, cy, bf = 520.0, 515.0, 320.0, 240.0, 40.0
+
+    def project(c, p):
+        x, y, z, w = cams[c, 3:]
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        pc = R @ pts[p] + cams[c, :3]
+        u = fx * pc[0] / pc[2] + cx
+        return u, fy * pc[1] / pc[2] + cy, u - bf / pc[2]
+
+    m_pt, m_cam = [], []
+    for p in range(48):
+        m_pt += [p] * 12; m_cam += list(range(12))
+    for p in range(48, 60):
+        seen = np.sort(rng.choice(12, 2 + (p - 48) % 4, replace=False))
+        m_pt += [p] * len(seen); m_cam += seen.tolist()
+    s_pt = np.repeat(np.arange(60, 66), 3); s_cam = np.tile(np.arange(12, 15), 6)
+    m_pt, m_cam = np.array(m_pt, np.int32), np.array(m_cam, np.int32)
+    m_uv = np.array([project(c, p)[:2] for p, c in zip(m_pt, m_cam)]) + rng.normal(0, 1.5, (len(m_pt), 2))      # (1.5 px at unit information: a good part beyond Huber's width)
+    s_uvr = np.array([project(c, p) for p, c in zip(s_pt, s_cam)]) + rng.normal(0, 1.5, (len(s_pt), 3))
+    cam_fixed = np.zeros(nc, np.int32); cam_fixed[[0, 12]] = 1
+    return dict(cams=cams, points=pts, cam_fixed=cam_fixed, pt_fixed=np.zeros(n_pts, np.int32),
+                mono=(m_pt, m_cam, m_uv, np.tile(np.array([1.3, 0.2, 0.2, 0.9]), (len(m_pt), 1)), np.tile(np.array([fx, fy, cx, cy]), (len(m_pt), 1))),
+                stereo=(s_pt.astype(np.int32), s_cam.astype(np.int32), s_uvr, np.tile(np.eye(3).ravel(), (len(s_pt), 1)), np.tile(np.array([fx, fy, cx, cy, bf]), (len(s_pt), 1))))
+
+
+def test_mono_edges_in_a_stereo_graph_equal_the_mono_graph_bitwise():
+    """A graph that holds a stereo edge runs the kernels' 3-row instantiations for ALL its edges; a mono edge fills rows 0 and 1 there and 'adds
+    exact zeros to the sums the mono code forms' (ba_proj_edge.h).  Held here: component A (mono) together with component B (stereo, no shared
+    vertex) against A alone, after compute_errors + build_system -- every A camera's 6 x 6 block, every A landmark's 3 x 3 block, every A edge's
+    H_pl block and A's part of b, np.array_equal (which takes -0 for +0, as intended).  Without kernels, with Huber widths, with three A edges at level 1."""
+    t = _two_components()
+    mono, stereo = t["mono"], t["stereo"]
+    n_m, n_a_cams, n_a_pts = len(mono[0]), 12, 60
+    assert n_m > 576 and np.count_nonzero(mono[0] < 48) == 576      # the first group's edges: beyond LIN_PT_CAP
+    levels = np.zeros(n_m, np.uint8); levels[[5, 300, n_m - 2]] = 1
+    for what, huber, lvl in (("no kernel", None, None), ("Huber", HUB, None), ("three edges at level 1", HUB, levels)):
+        U = capi.BaProblem(t["cams"], t["cam_fixed"], None, None, t["points"], t["pt_fixed"])
+        A = capi.BaProblem(t["cams"][:n_a_cams], t["cam_fixed"][:n_a_cams], None, None, t["points"][:n_a_pts], t["pt_fixed"][:n_a_pts])
+        hm = np.full(n_m, huber[0]) if huber is not None else None
+        U.set_edges_proj(*mono, hm); A.set_edges_proj(*mono, hm)
+        U.set_edges_proj_stereo(*stereo, np.full(len(stereo[0]), huber[1]) if huber is not None else None)
+        if lvl is not None:
+            U.set_edge_levels(capi.EDGE_PROJ, lvl); A.set_edge_levels(capi.EDGE_PROJ, lvl)
+        U.compute_errors(); A.compute_errors()
+        _, _, Hpl_u, b_u = U.build_system()
+        _, _, Hpl_a, b_a = A.build_system()
+        hc_u, _, hp_u = U.vertex_hessians()
+        hc_a, _, hp_a = A.vertex_hessians()
+        assert np.abs(hc_a[1:]).min(axis=(1, 2)).max() > 0 and np.abs(Hpl_a).max() > 0, what
+        assert np.array_equal(hc_u[:n_a_cams], hc_a), what
+        assert np.array_equal(hp_u[:n_a_pts], hp_a), what
+        assert np.array_equal(Hpl_u[:n_m], Hpl_a), what
+        # b in g2o's order: free cameras by id (A's eleven in front of B's two), then the landmarks by id (A's sixty in front of B's six)
+        n_u, n_a = U.sizes()[0], A.sizes()[0]
+        assert (n_u, n_a) == (6 * 13, 6 * 11) and len(b_a) == n_a + 3 * n_a_pts and np.abs(b_a).min() > 0, what
+        assert np.array_equal(b_u[:n_a], b_a[:n_a]), what
+        assert np.array_equal(b_u[n_u:n_u + 3 * n_a_pts], b_a[n_a:]), what
+        if lvl is not None:
+            assert np.all(Hpl_a[lvl == 1] == 0) and np.all(Hpl_u[:n_m][lvl == 1] == 0)
+        U.close(); A.close()
+
+
 def test_append_and_dump_load(fam, tmp_path):
     """A frame's stereo edges appended to an optimised graph = the graph built in one go at the same estimates; dump -> load -> the same run."""
     s = fam["stereo"]

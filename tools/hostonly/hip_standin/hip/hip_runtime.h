@@ -1,6 +1,7 @@
-// hip/hip_runtime.h -- a counting stand-in for the HIP runtime, for tools/hostonly/owners_check.cpp alone (its directory goes first on the
-// include path).  Device and pinned memory are malloc, copies are memcpy, streams and events are tokens; everything made is kept in a set
-// of what is live, and a free or destroy of something that is not live aborts.  Only what cs_hip_util.h and ba_dbuf.h call exists.
+// hip/hip_runtime.h -- a counting stand-in for the HIP runtime, for tools/hostonly/owners_check.cpp and ba_proj_edge_check.cpp alone (its
+// directory goes first on the include path).  Device and pinned memory are malloc, copies are memcpy, streams and events are tokens; everything
+// made is kept in a set of what is live, and a free or destroy of something that is not live aborts.  Only what cs_hip_util.h and ba_dbuf.h call
+// exists, and the two handle types that ba_types.h's launcher declarations name.
 #pragma once
 #include <cstddef>
 #include <cstdio>
