@@ -1059,7 +1059,8 @@ class CsPoseParams(C.Structure):
                 ("huber_mono", C.c_double), ("huber_stereo", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double)]
 
 
-DECLARED_SYMBOLS += ["cs_pose_default_params", "cs_pose_optimize_batch", "cs_pose_batch_create", "cs_pose_batch_destroy", "cs_pose_batch_optimize", "cs_pose_batch_last_timing"]
+DECLARED_SYMBOLS += ["cs_pose_default_params", "cs_pose_optimize_batch", "cs_pose_batch_create", "cs_pose_batch_destroy", "cs_pose_batch_optimize", "cs_pose_batch_last_timing",
+                     "cs_pose_linearize_batch"]
 
 
 def pose_default_params(**kw):
@@ -1077,9 +1078,8 @@ def pose_default_params(**kw):
     return p
 
 
-def _pose_call(fn, head, batch, params):
-    """Marshals a batch dict (synth_pose.synth_pose_batch layout: Tcw, intr, obs_ptr, Xw, meas, info, is_stereo) into one C call."""
-    p = params if params is not None else pose_default_params()
+def _pose_inputs(batch):
+    """A batch dict (synth_pose.synth_pose_batch layout: Tcw, intr, obs_ptr, Xw, meas, info, is_stereo) as C arguments."""
     T = _f64(batch["Tcw"], (-1, 7)); n = len(T)
     intr, ptr = _f64(batch["intr"], (n, 5)), _i32(batch["obs_ptr"])
     if len(ptr) != n + 1:
@@ -1089,10 +1089,17 @@ def _pose_call(fn, head, batch, params):
     st = np.ascontiguousarray(np.asarray(batch["is_stereo"]).ravel().astype(np.uint8))
     if len(st) != N:
         raise ValueError("is_stereo must hold one entry per observation")
+    keep = (T, intr, ptr, X, m, W, st)
+    return n, N, keep, (n, _dp(T), _dp(intr), _ip(ptr), _dp(X), _dp(m), _dp(W), st.ctypes.data_as(C.POINTER(C.c_ubyte)))
+
+
+def _pose_call(fn, head, batch, params):
+    """Marshals a batch dict into one optimize call."""
+    p = params if params is not None else pose_default_params()
+    n, N, keep, args = _pose_inputs(batch)
     T_out, inl = np.zeros((n, 7)), np.zeros(N, np.uint8)
     chi2, iters = np.zeros((n, p.n_rounds)), np.zeros((n, p.n_rounds), np.int32)
-    ub = lambda a: a.ctypes.data_as(C.POINTER(C.c_ubyte))
-    rc = fn(*head, C.byref(p), n, _dp(T), _dp(intr), _ip(ptr), _dp(X), _dp(m), _dp(W), ub(st), _dp(T_out), ub(inl), _dp(chi2), _ip(iters))
+    rc = fn(*head, C.byref(p), *args, _dp(T_out), inl.ctypes.data_as(C.POINTER(C.c_ubyte)), _dp(chi2), _ip(iters))
     return rc, dict(Tcw=T_out, inlier=inl, chi2=chi2, iterations=iters)
 
 
@@ -1138,6 +1145,17 @@ def pose_optimize_batch(batch, params=None, device=0):
     rc, out = _pose_call(lib().cs_pose_optimize_batch, (int(device),), batch, params)
     _chk(rc, "cs_pose_optimize_batch")
     return out
+
+
+def pose_linearize_batch(batch, robust=True, huber_mono=None, huber_stereo=None, device=0):
+    """cs_pose_linearize_batch -> (H (n, 21): the upper entries row by row, b (n, 6), chi2 (n)) at batch["Tcw"] over all observations;
+    the Huber widths default to cs_pose_default_params'."""
+    d = pose_default_params()
+    hm, hs = (d.huber_mono if huber_mono is None else huber_mono), (d.huber_stereo if huber_stereo is None else huber_stereo)
+    n, N, keep, args = _pose_inputs(batch)
+    H, b, chi2 = np.zeros((n, 21)), np.zeros((n, 6)), np.zeros(n)
+    _chk(lib().cs_pose_linearize_batch(int(device), int(bool(robust)), C.c_double(hm), C.c_double(hs), *args, _dp(H), _dp(b), _dp(chi2)), "cs_pose_linearize_batch")
+    return H, b, chi2
 
 
 # ------------------------------------------------------------------ Sim(3) alignment of keyframe pairs, batched ----------

@@ -181,10 +181,8 @@ struct FrameLm {
   __device__ __forceinline__ Pose oplus(const Pose& T, const double* x) const { return cam_oplus(T, x); }
 };
 
-__global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(const PoseLaunch a) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * POSE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
-  if (f >= a.n_frames) return;                       // (a whole wavefront leaves: there is no barrier in this kernel)
+// frame f of a launch
+__device__ __forceinline__ Frame frame_of(const PoseLaunch& a, int f) {
   Frame F;
   const int o0 = a.obs_ptr[f];
   F.n = a.obs_ptr[f + 1] - o0;
@@ -193,6 +191,14 @@ __global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(c
 #pragma unroll
   for (int k = 0; k < 5; k++) F.intr[k] = a.intr[5 * f + k];
   F.huber_mono = a.huber_mono; F.huber_stereo = a.huber_stereo;
+  return F;
+}
+
+__global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(const PoseLaunch a) {
+  const int lane = threadIdx.x & 63;
+  const int f = blockIdx.x * POSE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  if (f >= a.n_frames) return;                       // (a whole wavefront leaves: there is no barrier in this kernel)
+  const Frame F = frame_of(a, f);
   Pose T0 = pose_load(a.T0 + 7 * f);
   pose_normalize(T0);                                // SE3Quat(const Vector7d&) normalises (types/se3quat.h:67-70)
   Pose T = T0;
@@ -215,12 +221,40 @@ __global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_batch_kernel(c
   if (lane == 0) pose_store(T, a.T_out + 7 * f);
 }
 
+// Inspection (cs_pose_linearize_batch): frame_linearize, the routine every iteration above starts with, once per frame at its normalised
+// T0 with every observation at level 0.  Lane 0 stores H (21), b (6) and chi2 (every lane holds the same sums).
+__global__ void __launch_bounds__(64 * POSE_WAVES_PER_BLOCK) pose_linearize_kernel(const PoseLaunch a) {
+  const int lane = threadIdx.x & 63;
+  const int f = blockIdx.x * POSE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  if (f >= a.n_frames) return;
+  const Frame F = frame_of(a, f);
+  Pose T = pose_load(a.T0 + 7 * f);
+  pose_normalize(T);
+  for (int i = lane; i < F.n; i += 64) F.level[i] = 1;      // (read back by the lane that wrote it, as above)
+  double H[21], b[6], chi;
+  frame_linearize(F, T, a.robust_rounds != 0, lane, H, b, chi);
+  if (lane == 0) {
+    double* out = a.system_out + (size_t)f * POSE_SYSTEM_DOUBLES;
+#pragma unroll
+    for (int k = 0; k < 21; k++) out[k] = H[k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) out[21 + k] = b[k];
+    out[27] = chi;
+  }
+}
+
 }  // namespace
 
 void pose_launch(const PoseLaunch& a, hipStream_t st) {
   if (a.n_frames <= 0) return;
   const int blocks = (a.n_frames + POSE_WAVES_PER_BLOCK - 1) / POSE_WAVES_PER_BLOCK;
   hipLaunchKernelGGL(pose_batch_kernel, dim3(blocks), dim3(64 * POSE_WAVES_PER_BLOCK), 0, st, a);
+}
+
+void pose_launch_linearize(const PoseLaunch& a, hipStream_t st) {
+  if (a.n_frames <= 0) return;
+  const int blocks = (a.n_frames + POSE_WAVES_PER_BLOCK - 1) / POSE_WAVES_PER_BLOCK;
+  hipLaunchKernelGGL(pose_linearize_kernel, dim3(blocks), dim3(64 * POSE_WAVES_PER_BLOCK), 0, st, a);
 }
 
 }  // namespace cs

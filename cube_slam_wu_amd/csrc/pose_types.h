@@ -7,7 +7,8 @@ namespace cs {
 // One observation as the kernel reads it: 16 doubles = 128 bytes, one cache line per lane.
 //   [0..2] Xw   [3..5] measurement (u, v, u_r; mono: u, v, 0)   [6..14] information, row-major 3 x 3 (mono: the upper-left 2 x 2, zeros elsewhere)
 //   [15] 1.0 = EdgeStereoSE3ProjectXYZOnlyPose, 0.0 = EdgeSE3ProjectXYZOnlyPose
-enum { POSE_OBS_DOUBLES = 16, POSE_MAX_ROUNDS = 8, POSE_WAVES_PER_BLOCK = 4 };
+// POSE_SYSTEM_DOUBLES: what the inspection entry stores per frame -- H (21 upper entries, row by row), b (6), activeRobustChi2 (1)
+enum { POSE_OBS_DOUBLES = 16, POSE_MAX_ROUNDS = 8, POSE_WAVES_PER_BLOCK = 4, POSE_SYSTEM_DOUBLES = 28 };
 
 struct PoseLaunch {
   int n_frames, n_rounds;
@@ -22,8 +23,12 @@ struct PoseLaunch {
   double* chi2_out;        // n_frames x n_rounds
   int* iters_out;          // n_frames x n_rounds
   unsigned char* inlier;   // obs_ptr[n_frames]: the level of every observation between the rounds, and the result
+  double* system_out;      // pose_launch_linearize only: n_frames x POSE_SYSTEM_DOUBLES
 };
 
 void pose_launch(const PoseLaunch& a, hipStream_t st);
+// Inspection (cs_pose_linearize_batch): the system of every frame at its normalised T0 over all its observations.  Of the schedule it
+// reads robust_rounds alone (!= 0: the Huber kernel is on) with the two widths; it writes system_out, and inlier (all ones).
+void pose_launch_linearize(const PoseLaunch& a, hipStream_t st);
 
 }  // namespace cs

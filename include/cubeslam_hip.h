@@ -653,6 +653,12 @@ int cs_pose_batch_optimize(cs_pose_batch* b, const cs_pose_params* p, int n_fram
 /* Of the handle's last call: kernel_ms = the one kernel, from hipEvents on the handle's stream; host_ms = the whole call on a monotonic
  * clock (packing, the two copies and the kernel included).                                                                          */
 int cs_pose_batch_last_timing(const cs_pose_batch* b, double* kernel_ms, double* host_ms);
+/* Inspection: the system an iteration starts from -- computeActiveErrors + buildSystem of every frame at its normalised Tcw7_in with all
+ * its observations at level 0.  robust != 0: the Huber kernel with the two widths.  H21 = n_frames x 21 (the upper entries of the 6 x 6
+ * H, row by row), b6 = n_frames x 6, chi2 = n_frames (activeRobustChi2).  The inputs are cs_pose_optimize_batch's.                 */
+int cs_pose_linearize_batch(int device, int robust, double huber_mono, double huber_stereo, int n_frames, const double* Tcw7_in, const double* intr5,
+      const int* obs_ptr, const double* Xw3, const double* meas3, const double* info9, const unsigned char* is_stereo,
+      double* H21, double* b6, double* chi2);
 
 /* ------------------------------------------------------------------ Path B'': pose-graph optimisation over Sim(3) keyframe vertices -- */
 /* Replaces the g2o graph an ORB-SLAM2-derived pipeline optimises after a loop closure (Optimizer::OptimizeEssentialGraph, NOT IN THE

@@ -13,8 +13,13 @@ Written from the reference's lines:
 The round schedule and the classification between the rounds are the caller's (ORB-SLAM2's Optimizer::PoseOptimization pattern): after
 each round every observation -- current outliers included -- is tested by its plain chi2 at the round's final pose.
 
-optimize_frame() also records what the tests' condition on the inputs needs: every LM trial's rho and, at every classification point,
-how close any observation's chi2 came to its threshold.
+errors(), jacobians() and _Graph.linearize() take a dtype: float64 or np.longdouble.  In either, the stereo edge's 1 / z goes through a
+float32 and so does Huber's delta^2, as in the reference: the long double run is the same function with finer rounding, and the
+difference of the two is the reference's own rounding error.
+
+optimize_frame() also records what the tests' condition on the inputs needs: every LM trial's rho, at every classification point how
+close any observation's chi2 came to its threshold, and every pivot of every factorisation relative to the largest diagonal entry of
+H + lambda I (a pivot that close to zero is given its sign by rounding).
 """
 from __future__ import annotations
 
@@ -37,7 +42,9 @@ def _qmul(a, b):
 def _normalize(q):
     if q[3] < 0:
         q = -q
-    return q / np.sqrt(q @ q)
+    # (the four squares added from the left, written out: q @ q leaves the order to the BLAS, and on a quaternion that is not of unit length
+    # already the last bit of the norm -- hence of the result -- depends on it)
+    return q / np.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3])
 
 
 def _rot(q):
@@ -100,18 +107,19 @@ def se3_from_vector(v):
 
 
 # ---- the two edges, all observations of a frame at once
-def errors(T, intr, Xw, meas, stereo):
+def errors(T, intr, Xw, meas, stereo, dtype=np.float64):
     """computeError of both classes: (n, 3) errors (a mono row's third entry is 0) and the points in the camera frame."""
-    fx, fy, cx, cy, bf = intr
+    T, Xw, meas = np.asarray(T, dtype), np.asarray(Xw, dtype), np.asarray(meas, dtype)
+    fx, fy, cx, cy, bf = np.asarray(intr, dtype)
     pc = Xw @ _rot(T[3:]).T + T[:3]
-    e = np.zeros((len(Xw), 3))
+    e = np.zeros((len(Xw), 3), dtype)
     m = ~stereo
     # EdgeSE3ProjectXYZOnlyPose::cam_project: project2d, then * f + c
     e[m, 0] = meas[m, 0] - (pc[m, 0] / pc[m, 2] * fx + cx)
     e[m, 1] = meas[m, 1] - (pc[m, 1] / pc[m, 2] * fy + cy)
     # EdgeStereoSE3ProjectXYZOnlyPose::cam_project: `const float invz = 1.0f / trans_xyz[2]`, bf the double member
     s = stereo
-    invz = (1.0 / pc[s, 2]).astype(np.float32).astype(np.float64)
+    invz = (1.0 / pc[s, 2]).astype(np.float32).astype(dtype)
     u = pc[s, 0] * invz * fx + cx
     e[s, 0] = meas[s, 0] - u
     e[s, 1] = meas[s, 1] - (pc[s, 1] * invz * fy + cy)
@@ -119,13 +127,14 @@ def errors(T, intr, Xw, meas, stereo):
     return e, pc
 
 
-def jacobians(pc, intr, stereo):
+def jacobians(pc, intr, stereo, dtype=np.float64):
     """linearizeOplus of both classes: (n, 3, 6); a mono edge's third row is 0."""
-    fx, fy, _, _, bf = intr
+    pc = np.asarray(pc, dtype)
+    fx, fy, _, _, bf = np.asarray(intr, dtype)
     x, y = pc[:, 0], pc[:, 1]
     invz = 1.0 / pc[:, 2]
     invz_2 = invz * invz
-    J = np.zeros((len(pc), 3, 6))
+    J = np.zeros((len(pc), 3, 6), dtype)
     J[:, 0, 0] = x * y * invz_2 * fx
     J[:, 0, 1] = -(1 + (x * x * invz_2)) * fx
     J[:, 0, 2] = y * invz * fx
@@ -155,20 +164,26 @@ def omega3(info9, stereo):
 
 def huber(e2, delta):
     """RobustKernelHuber::robustify: rho and rho' of the squared errors e2 (delta per edge; <= 0 = no kernel)."""
+    e2 = np.asarray(e2)
     delta = np.broadcast_to(np.asarray(delta, np.float64), e2.shape)
     dsqr = (delta * delta).astype(np.float32).astype(np.float64)
     on = (delta > 0) & (e2 > dsqr)
-    sq = np.sqrt(np.where(on, e2, 1.0))
-    return np.where(on, 2 * sq * delta - dsqr, e2), np.where(on, delta / sq, 1.0)
+    one = e2.dtype.type(1)
+    sq = np.sqrt(np.where(on, e2, one))
+    return np.where(on, 2 * sq * delta - dsqr, e2), np.where(on, delta / sq, one)
 
 
-def ldlt_solve(A, b):
-    """LDL^T without pivoting; None when a pivot is not positive (LDLT::isPositive)."""
+def ldlt_solve(A, b, pivots=None):
+    """LDL^T without pivoting; None when a pivot is not positive (LDLT::isPositive).  pivots: a list that takes every pivot met, the
+    failing one included, relative to the largest diagonal entry of A."""
     n = len(b)
     L = np.eye(n)
     D = np.zeros(n)
+    top = np.abs(np.diag(A)).max()
     for j in range(n):
         d = A[j, j] - (L[j, :j] * L[j, :j]) @ D[:j]
+        if pivots is not None:
+            pivots.append(d / top)
         if not d > 0:
             return None
         D[j] = d
@@ -187,25 +202,30 @@ def ldlt_solve(A, b):
 class _Graph:
     """One free VertexSE3Expmap and the level-0 edges of a frame."""
 
-    def __init__(self, intr, Xw, meas, W, stereo, delta):
-        self.intr, self.Xw, self.meas, self.W, self.stereo, self.delta = intr, Xw, meas, W, stereo, delta
+    def __init__(self, intr, Xw, meas, W, stereo, delta, dtype=np.float64):
+        self.intr, self.Xw, self.meas, self.W, self.stereo, self.delta, self.dtype = intr, Xw, meas, np.asarray(W, dtype), stereo, delta, dtype
 
     def chi2_each(self, T):
-        e, pc = errors(T, self.intr, self.Xw, self.meas, self.stereo)
+        e, pc = errors(T, self.intr, self.Xw, self.meas, self.stereo, self.dtype)
         We = np.einsum("nij,nj->ni", self.W, e)
         return np.einsum("ni,ni->n", e, We), e, We, pc
 
     def robust_chi2(self, T):
         c, _, _, _ = self.chi2_each(T)
-        return huber(c, self.delta)[0].sum()
+        return float(huber(c, self.delta)[0].sum())
 
     def linearize(self, T):
         c, e, We, pc = self.chi2_each(T)
         rho0, rho1 = huber(c, self.delta)
-        J = jacobians(pc, self.intr, self.stereo)
+        J = jacobians(pc, self.intr, self.stereo, self.dtype)
         b = -np.einsum("n,nia,ni->a", rho1, J, We)
         H = np.einsum("n,nia,nij,njb->ab", rho1, J, self.W, J)
         return H, b, rho0.sum()
+
+    def system64(self, T):
+        """linearize(), rounded to float64: what the LM loop, float64 whatever the edges' dtype, is handed."""
+        H, b, chi = self.linearize(T)
+        return np.asarray(H, np.float64), np.asarray(b, np.float64), float(chi)
 
 
 def lm_optimize(G, T, iterations, log):
@@ -213,14 +233,14 @@ def lm_optimize(G, T, iterations, log):
     lam, ni, n_bad, done, trials = 0.0, 2.0, 0, 0, []
     current = G.robust_chi2(T)
     for it in range(iterations):
-        H, b, current = G.linearize(T)
+        H, b, current = G.system64(T)
         if it == 0:
             lam = 1e-5 * np.abs(np.diag(H)).max()
             ni, n_bad = 2.0, 0
         ini = current
         rho, qmax = 0.0, 0
         while True:
-            x = ldlt_solve(H + lam * np.eye(6), b)
+            x = ldlt_solve(H + lam * np.eye(6), b, log["pivots"])
             if x is not None:
                 Tn = se3_mul(se3_exp(x), T)
                 temp = G.robust_chi2(Tn)
@@ -228,7 +248,8 @@ def lm_optimize(G, T, iterations, log):
             else:
                 log["not_pd_trials"] += 1
                 Tn, temp, scale = T, np.finfo(np.float64).max, 0.0
-            rho = (current - temp) / (scale + 1e-3)
+            with np.errstate(over="ignore"):      # (a failed trial: -DBL_MAX / 1e-3 = -inf)
+                rho = (current - temp) / (scale + 1e-3)
             log["rho"].append(rho)
             if rho > 0 and np.isfinite(temp):
                 alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
@@ -251,9 +272,11 @@ def lm_optimize(G, T, iterations, log):
     return T, done, current, trials
 
 
-def optimize_frame(T0, intr, Xw, meas, info9, stereo, params=None):
-    """All rounds of one frame.  Returns a dict: pose (7), inlier (n, bool), chi2 / iterations (n_rounds), trials (list per round),
-    rho (every LM trial's rho), margin (smallest |chi2 / threshold - 1| met at a classification point), not_pd_trials."""
+def optimize_frame(T0, intr, Xw, meas, info9, stereo, params=None, dtype=np.float64):
+    """All rounds of one frame; dtype = the precision the edges are evaluated in (errors, Jacobians, the sums of H, b and chi2), the LM loop
+    and the pose staying float64.  Returns a dict: pose (7), inlier (n, bool), chi2 / iterations (n_rounds), trials (list per round),
+    rho (every LM trial's rho), margin (smallest |chi2 / threshold - 1| met at a classification point), not_pd_trials, pivot_margin (the
+    smallest |pivot| of any factorisation, relative to the largest diagonal entry of its H + lambda I; inf when none was run)."""
     p = dict(DEFAULTS, **(params or {}))
     Xw = np.asarray(Xw, np.float64).reshape(-1, 3)
     meas = np.asarray(meas, np.float64).reshape(-1, 3)
@@ -265,7 +288,7 @@ def optimize_frame(T0, intr, Xw, meas, info9, stereo, params=None):
     T0 = se3_from_vector(T0)
     T = T0
     level0 = np.ones(n, bool)
-    log = dict(rho=[], not_pd_trials=0)
+    log = dict(rho=[], not_pd_trials=0, pivots=[])
     chi2, iters, trials, margin = [], [], [], np.inf
     for r in range(p["n_rounds"]):
         if p["restart_each_round"]:
@@ -273,26 +296,44 @@ def optimize_frame(T0, intr, Xw, meas, info9, stereo, params=None):
         delta = np.where(stereo, p["huber_stereo"], p["huber_mono"]) if r < p["robust_rounds"] else np.zeros(n)
         a = level0
         if a.any():
-            G = _Graph(intr, Xw[a], meas[a], W[a], stereo[a], delta[a])
+            G = _Graph(intr, Xw[a], meas[a], W[a], stereo[a], delta[a], dtype)
             T, done, c, tr = lm_optimize(G, T, p["iterations"][r], log)
         else:
             done, c, tr = 0, 0.0, []
         chi2.append(c); iters.append(done); trials.append(tr)
         if n:
-            each = _Graph(intr, Xw, meas, W, stereo, np.zeros(n)).chi2_each(T)[0]
+            each = np.asarray(_Graph(intr, Xw, meas, W, stereo, np.zeros(n), dtype).chi2_each(T)[0], np.float64)
             on = thr > 0
             if on.any():
                 margin = min(margin, np.abs(each[on] / thr[on] - 1).min())
             level0 = ~(on & (each > thr))
     return dict(pose=T, inlier=level0, chi2=np.array(chi2), iterations=np.array(iters, np.int32), trials=trials,
-                rho=np.array(log["rho"]), margin=margin, not_pd_trials=log["not_pd_trials"])
+                rho=np.array(log["rho"]), margin=margin, not_pd_trials=log["not_pd_trials"],
+                pivot_margin=float(np.abs(log["pivots"]).min()) if log["pivots"] else np.inf)
 
 
-def optimize_batch(batch, params=None):
+def linearize_batch(batch, robust=True, params=None, dtype=np.float64):
+    """What cs_pose_linearize_batch hands out: per frame H (21 upper entries, row by row), b (6) and the active robust chi2 at the normalised
+    input pose over all observations, in `dtype`."""
+    p = dict(DEFAULTS, **(params or {}))
+    ptr = batch["obs_ptr"]
+    iu = np.triu_indices(6)
+    H, b, chi = [], [], []
+    for f in range(len(batch["Tcw"])):
+        s = slice(ptr[f], ptr[f + 1])
+        stereo = np.asarray(batch["is_stereo"][s]).astype(bool)
+        delta = np.where(stereo, p["huber_stereo"], p["huber_mono"]) if robust else np.zeros(len(stereo))
+        G = _Graph(batch["intr"][f], batch["Xw"][s], batch["meas"][s], omega3(batch["info"][s], stereo), stereo, delta, dtype)
+        Hf, bf, cf = G.linearize(se3_from_vector(batch["Tcw"][f]))
+        H.append(Hf[iu]); b.append(bf); chi.append(cf)
+    return np.array(H, dtype).reshape(-1, 21), np.array(b, dtype).reshape(-1, 6), np.array(chi, dtype)
+
+
+def optimize_batch(batch, params=None, dtype=np.float64):
     """optimize_frame over a batch dict (cube_slam_wu_amd.synth_pose layout); a list of per-frame results."""
     out = []
     ptr = batch["obs_ptr"]
     for f in range(len(batch["Tcw"])):
         s = slice(ptr[f], ptr[f + 1])
-        out.append(optimize_frame(batch["Tcw"][f], batch["intr"][f], batch["Xw"][s], batch["meas"][s], batch["info"][s], batch["is_stereo"][s], params))
+        out.append(optimize_frame(batch["Tcw"][f], batch["intr"][f], batch["Xw"][s], batch["meas"][s], batch["info"][s], batch["is_stereo"][s], params, dtype))
     return out

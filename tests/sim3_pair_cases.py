@@ -1,6 +1,11 @@
 """The batches tests/test_sim3_pair_gpu.py runs and their reference results (tests/sim3_pair_ref.py), built once per process.
 tests/test_sim3_pair_ref.py asserts, without a GPU, the conditions under which a float64 reference may be compared at all -- for every
-pair of every batch here, none dropped: the seeds below are ones for which the reference alone meets them."""
+pair of every batch here, none dropped: the seeds below are ones for which the reference alone meets them.
+
+cube_slam_wu_amd/synth_sim3_pairs.py gives every pair the same two cameras, each with fx == fy, and every edge a scalar times the identity
+as its information: reading pair 0's intrinsics for every pair, fx for fy, camera 1 for camera 2, or dropping an off-diagonal entry of
+Omega changes little or nothing there.  with_distinct_intrinsics and with_dense_information take those symmetries away (dense_batch,
+dense_edge_batch); the generator's defaults are not touched."""
 import functools
 
 import numpy as np
@@ -12,7 +17,8 @@ COUNTS = (12, 20, 63, 64, 65, 100, 128, 129, 300)      # the lane-stride boundar
 START = (0.05, 0.1, 0.05)
 SHORT = dict(iterations_first=3, iterations_more_clean=2, iterations_more_outliers=2)      # the schedule at which trial counts can be compared
 
-MAIN_SEED, DEFAULT_SEED, VARIANT_SEED, EDGE_SEED = 2, 4, 11, 3
+MAIN_SEED, DEFAULT_SEED, VARIANT_SEED, EDGE_SEED, DENSE_SEED = 2, 4, 11, 3, 31
+DENSE = dict(SHORT, min_inliers=8)      # dense information upweights some residuals: more matches go after round one than in main_batch
 
 VARIANTS = {
     "no_kernel": dict(SHORT, huber_delta=0.0),
@@ -59,11 +65,78 @@ def edge_batch():
     return sp.synth_sim3_pairs(4, 12, 0.1, EDGE_SEED, START, fix_scale=[0, 1, 0, 0])
 
 
+def _copy(batch):
+    return {k: np.array(v, copy=True) for k, v in batch.items()}
+
+
+def _cam(P, K):
+    return np.stack([P[:, 0] / P[:, 2] * K[0] + K[2], P[:, 1] / P[:, 2] * K[1] + K[3]], 1)
+
+
+def with_distinct_intrinsics(batch, seed):
+    """Every pair its own two cameras: fx within 5 % of the generator's, fy 2 .. 6 % off fx to either side, cx and cy moved by up to 8 and 5
+    pixels, drawn per camera.  Every keypoint is moved by what the new camera changes in the projection of its stored point, so its noise
+    and the outliers stay what they were."""
+    rng = np.random.default_rng(seed)
+    out = _copy(batch)
+    n = len(batch["S12"])
+    for c in (0, 4):
+        fx = batch["intr"][:, c] * rng.uniform(0.95, 1.05, n)
+        out["intr"][:, c] = fx
+        out["intr"][:, c + 1] = fx * (1 + rng.choice([-1.0, 1.0], n) * rng.uniform(0.02, 0.06, n))
+        out["intr"][:, c + 2] += rng.uniform(-8, 8, n)
+        out["intr"][:, c + 3] += rng.uniform(-5, 5, n)
+    ptr = batch["match_ptr"]
+    for f in range(n):
+        s = slice(ptr[f], ptr[f + 1])
+        out["obs1"][s] += _cam(batch["P1"][s], out["intr"][f, :4]) - _cam(batch["P1"][s], batch["intr"][f, :4])
+        out["obs2"][s] += _cam(batch["P2"][s], out["intr"][f, 4:]) - _cam(batch["P2"][s], batch["intr"][f, 4:])
+    assert np.all(np.abs(out["intr"][:, [1, 5]] / out["intr"][:, [0, 4]] - 1) >= 0.02)
+    assert all(len(np.unique(out["intr"][:, k])) == n for k in range(8)) and np.all(out["intr"][:, :4] != out["intr"][:, 4:])
+    return out
+
+
+def with_dense_information(batch, seed):
+    """Every edge its own dense 2 x 2 information Q diag(d) Q^T, symmetric to the last bit and positive definite: Q a random rotation, d the
+    edge's level weight times factors of 1 / sqrt(5) .. sqrt(5) (eigenvalue ratio up to 5); info12 and info21 drawn independently."""
+    rng = np.random.default_rng(seed)
+    out = _copy(batch)
+    N = len(batch["P1"])
+    for key in ("info12", "info21"):
+        w = batch[key][:, 0]
+        d = w[:, None] * np.exp(rng.uniform(-0.5 * np.log(5.0), 0.5 * np.log(5.0), (N, 2)))
+        ang = rng.uniform(0, 2 * np.pi, N)
+        c, s = np.cos(ang), np.sin(ang)
+        off = c * s * (d[:, 0] - d[:, 1])
+        out[key] = np.stack([c * c * d[:, 0] + s * s * d[:, 1], off, off, s * s * d[:, 0] + c * c * d[:, 1]], 1)
+    return out
+
+
+def told_apart(batch, seed):
+    return with_dense_information(with_distinct_intrinsics(batch, seed + 100), seed + 200)
+
+
+@functools.lru_cache(None)
+def dense_batch(seed=DENSE_SEED):
+    """24 pairs over COUNTS, every second pair fix_scale, 10 % outliers, each pair with its own cameras and each edge with its own dense information."""
+    rng = np.random.default_rng(seed)
+    counts = np.concatenate([np.array(COUNTS), np.array(COUNTS), rng.choice(COUNTS, 24 - 2 * len(COUNTS))])
+    return told_apart(sp.synth_sim3_pairs(24, counts, 0.1, seed, START), seed)
+
+
+@functools.lru_cache(None)
+def dense_edge_batch():
+    """edge_batch() with per-pair, per-camera intrinsics (cs_sim3_pairs_linearize takes no information: its blocks are the errors and Jacobians)."""
+    return told_apart(edge_batch(), EDGE_SEED)
+
+
 @functools.lru_cache(None)
 def run(name, long_double=False, seed=None):
-    """Reference results of a named case: 'main', 'default', or a key of VARIANTS (seed: another batch of the same make, for choosing seeds)."""
+    """Reference results of a named case: 'main', 'default', 'dense', or a key of VARIANTS (seed: another batch of the same make, for choosing seeds)."""
     dtype = np.longdouble if long_double else np.float64
     kw = {} if seed is None else dict(seed=seed)
+    if name == "dense":
+        return ref.optimize_batch(dense_batch(**kw), ref.params(**DENSE), dtype)
     if name == "main":
         return ref.optimize_batch(main_batch(**kw), ref.params(**SHORT), dtype)
     if name == "default":
@@ -72,9 +145,9 @@ def run(name, long_double=False, seed=None):
 
 
 @functools.lru_cache(None)
-def edge_blocks(long_double=False):
-    """(err (48, 4), jac (48, 2, 2, 7)) of edge_batch() at its start states."""
-    b = edge_batch()
+def edge_blocks(long_double=False, dense=False):
+    """(err (48, 4), jac (48, 2, 2, 7)) of edge_batch() -- dense: of dense_edge_batch() -- at its start states."""
+    b = dense_edge_batch() if dense else edge_batch()
     dtype = np.longdouble if long_double else np.float64
     errs, jacs = [], []
     for f in range(len(b["S12"])):

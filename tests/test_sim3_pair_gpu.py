@@ -55,6 +55,33 @@ def test_edge_blocks():
     assert not failures, failures
 
 
+def test_edge_blocks_with_distinct_intrinsics():
+    """The same 48 matches with every pair's two cameras its own and fx != fy (tests/sim3_pair_cases.py: dense_edge_batch), under the
+    tolerance rule of test_edge_blocks, unchanged.  Reference's own deviation: errors 1.2e-14, Jacobians 1.4e-7."""
+    b = pc.dense_edge_batch()
+    (e64, j64), (eld, jld) = pc.edge_blocks(False, True), pc.edge_blocks(True, True)
+    err, jac = capi.sim3_pairs_linearize(b)
+    fs = np.repeat(b["fix_scale"].astype(bool), np.diff(b["match_ptr"]))
+    assert np.isfinite(err).all() and np.isfinite(jac).all() and np.all(jac[fs][..., 6] == 0)
+    failures = []
+    for nm, got, r64, rld, factor, floor in (("err", err, e64, eld, 100, 1e-13), ("jac", jac, j64, jld, 10, 0.0)):
+        ref_dev, dev = ref.block_deviation(r64, rld).max(), ref.block_deviation(got, r64).max()
+        tol = max(factor * ref_dev, floor)
+        print("%s: device %.3g, reference's own %.3g, tolerance %.3g" % (nm, dev, ref_dev, tol))
+        if not dev <= tol:
+            failures.append((nm, dev, tol))
+    assert not failures, failures
+
+
+def test_dense_information_and_distinct_intrinsics_against_numpy_reference():
+    """24 pairs over the lane-stride counts at schedule (3, 2), every pair with its own two cameras (fx != fy) and every edge with its own
+    dense 2 x 2 information; min_inliers 8, under which 21 of the 24 run a second round (asserted in tests/test_sim3_pair_ref.py)."""
+    b = pc.dense_batch()
+    got = capi.sim3_optimize_pairs(b, _prm(**pc.DENSE))
+    pc.compare_with_reference(got, pc.run("dense"), "device dense")
+    assert 2 * int((got["iterations"][:, 1] > 0).sum()) >= 24
+
+
 def test_batch_against_numpy_reference():
     """96 pairs at schedule (3, 2), match counts on the lane-stride boundaries, every second pair fix_scale.  Measured on an MI355X:
     states within 3.4e-7, chi2 within 7.9e-9 of the float64 reference (whose own long double spread is 4.4e-7 on the states)."""
