@@ -68,7 +68,7 @@ DECLARED_SYMBOLS = [
     "cs_detector_destroy", "cs_detect_cuboids", "cs_batch_create", "cs_batch_max_boxes", "cs_batch_run", "cs_batch_submit", "cs_batch_collect",
     "cs_bgr_to_gray", "cs_edge_distance_maps", "cs_edge_distance_maps_multi", "cs_detect_cuboids_gray", "cs_batch_create_gray", "cs_batch_refill_gray", "cs_batch_refill_wait", "cs_batch_destroy", "cs_batch_last_timing", "cs_batch_debug_candidates", "cs_batch_debug_kept", "cs_batch_set_debug", "cs_batch_set_pipeline_chunks", "cs_detect_lines_gray", "cs_detect_lines_batch", "cs_detect_lines_last_timing", "cs_detect_lsd_gray", "cs_detect_lsd_batch", "cs_detect_lsd_last_timing",
     "cs_lbd_describe_gray", "cs_detect_descrip_lines_gray", "cs_detect_descrip_lines_batch", "cs_lbd_match", "cs_lbd_match_batch", "cs_lbd_last_timing",
-    "cs_check_score_atan2", "cs_check_score_sample_index",
+    "cs_check_score_atan2", "cs_check_score_sample_index", "cs_check_line_setup",
 ]
 
 # cs_keyline (one octave: start / end point, direction, length of the support region in pixels)
@@ -135,6 +135,23 @@ def check_score_sample_index(sy, sx, map_w, a, b):
     if rc != 0:
         raise RuntimeError("cs_check_score_sample_index failed (%d): %s" % (rc, last_error()))
     return idx, probe
+
+
+def check_line_setup(lines, rois, yt, dist_thre=20.0, angle_thre_deg=5.0, len_thre=30.0):
+    """The line setup on its own: one frame's segments (n x 4) against r expanded ROIs (r x 4 inclusive integer bounds) with yaw / top-edge
+    sample counts yt (r x 2).  Returns (device, host), each a dict of m (r) and angle, mid_x, mid_y (r x n, zero behind the m[k] entries)."""
+    lines = np.ascontiguousarray(lines, np.float64).reshape(-1, 4)
+    rois, yt = np.ascontiguousarray(rois, np.int32).reshape(-1, 4), np.ascontiguousarray(yt, np.int32).reshape(-1, 2)
+    if len(rois) != len(yt):
+        raise ValueError("rois and yt must have one row per ROI")
+    n, r = len(lines), len(rois)
+    ip = C.POINTER(C.c_int)
+    m, tab = [np.zeros(r, np.int32) for _ in range(2)], [np.zeros((3, r, n)) for _ in range(2)]
+    rc = lib().cs_check_line_setup(_dp(lines), n, rois.ctypes.data_as(ip), yt.ctypes.data_as(ip), r, C.c_double(dist_thre), C.c_double(angle_thre_deg), C.c_double(len_thre),
+                                   m[0].ctypes.data_as(ip), _dp(tab[0]), m[1].ctypes.data_as(ip), _dp(tab[1]))
+    if rc != 0:
+        raise RuntimeError("cs_check_line_setup failed (%d): %s" % (rc, last_error()))
+    return tuple({"m": m[q], "angle": tab[q][0], "mid_x": tab[q][1], "mid_y": tab[q][2]} for q in range(2))
 
 
 def box_rois(box5, img_w, img_h, sample_height=False):

@@ -6,7 +6,7 @@
 //                             :344-355)  ->  JobDesc + pooled SoA arrays in pinned memory, one H2D copy;
 //   sweep   (HIP)             line setup (ROI filter + merge_break_lines) and VP support, vanishing points + corner
 //                             construction + ordered compaction, the crowded ROIs' line setup; the scorer joins them
-//                             (detect_kernels.hip).  On three streams of the process's stream set with eight hardware
+//                             (detect_kernels.hip, line_setup_kernels.hip).  On three streams of the process's stream set with eight hardware
 //                             queues or more, on one stream per detector with fewer (StreamSet below);
 //   rank    (HIP)             fuse_normalize_scores_v2 (object_3d_util.cpp:726-837) and the final skew-weighted ranking
 //                             (box_proposal_detail.cpp:766-838) on the compacted (dist, angle, skew) columns; only the
@@ -526,6 +526,7 @@ struct cs_batch {
   // round path: the device tables of the round in flight, and what only this path brings back (every compacted column for the host
   // ranking, the device's winners with their corners, the carried proposal, the job table)
   SweepBuffers round;
+  DevBuf<int> round_ls_lists;       // the line setup's two lists of crowded jobs: 2 (nj + 1) ints
   PinBuf<long long> h_c_slot;
   PinBuf<int> h_c_flag;
   PinBuf<double> h_c_dist, h_c_angle, h_c_skew;
@@ -634,6 +635,60 @@ int cs_check_score_sample_index(const double* sy, const double* sx, const int* m
   };
   if (rc == CS_OK) rc = run();
   return rc;
+}
+
+int cs_check_line_setup(const double* lines, int n, const int* rois, const int* yt, int r, double dist_thre, double angle_thre_deg, double len_thre,
+                        int* dev_m, double* dev_tab, int* host_m, double* host_tab) {
+  if (n < 0 || r < 0 || (n > 0 && !lines) || (r > 0 && (!rois || !yt || !dev_m || !dev_tab || !host_m || !host_tab))) { cs_set_error("cs_check_line_setup: null array"); return CS_ERR_INVALID_ARG; }
+  if (n > cs::line_setup_capacity()) { cs_set_error("cs_check_line_setup: more segments than the line setup's rows"); return CS_ERR_CAPACITY; }
+  if (r > (1 << 16)) { cs_set_error("cs_check_line_setup: more than 2^16 ROIs"); return CS_ERR_CAPACITY; }
+  if (int rc = cs::check_device(0)) return rc;
+  if (r == 0) return CS_OK;
+  CS_GUARD_BEGIN
+  CS_HIP_TRY(hipSetDevice(0));
+  const size_t N = (size_t)n, R = (size_t)r, plane = R * N;
+  std::vector<cs::JobDesc> jobs(R);
+  std::memset(jobs.data(), 0, sizeof(cs::JobDesc) * R);
+  std::fill(host_tab, host_tab + 3 * plane, 0.0);
+  for (size_t k = 0; k < R; k++) {
+    cs::JobDesc& jd = jobs[k];
+    jd.g.el = rois[4 * k]; jd.g.et = rois[4 * k + 1]; jd.g.er = rois[4 * k + 2]; jd.g.eb = rois[4 * k + 3];
+    jd.Y = yt[2 * k]; jd.T = yt[2 * k + 1]; jd.line_off = (int)(k * N);
+    // the host's tables: what the sweep computes under force_host_setup (a skipped job has no segments)
+    host_m[k] = 0;
+    if (jd.Y == 0 || jd.T == 0) continue;
+    std::vector<double> in;
+    for (size_t e = 0; e < N; e++) {
+      const double* l = lines + 4 * e;
+      if (cs::inside_box(cs::v2(l[0], l[1]), jd.g.el, jd.g.et, jd.g.er, jd.g.eb) && cs::inside_box(cs::v2(l[2], l[3]), jd.g.el, jd.g.et, jd.g.er, jd.g.eb)) in.insert(in.end(), l, l + 4);
+    }
+    merge_lines(in, dist_thre, angle_thre_deg, len_thre);
+    host_m[k] = (int)(in.size() / 4);
+    for (size_t i = 0; i < in.size() / 4; i++) {
+      host_tab[k * N + i] = cs::cs_atan2(in[4 * i + 3] - in[4 * i + 1], in[4 * i + 2] - in[4 * i]);
+      host_tab[plane + k * N + i] = (in[4 * i] + in[4 * i + 2]) / 2;
+      host_tab[2 * plane + k * N + i] = (in[4 * i + 1] + in[4 * i + 3]) / 2;
+    }
+  }
+  // the device's: the production launcher, everything on the null stream
+  DevBuf<cs::JobDesc> d_jobs;
+  DevBuf<double> d_lines, d_tab;      // d_tab: angle, mid x, mid y planes of r x n
+  DevBuf<int> d_ptr, d_lists;
+  cs::Event fork, join;
+  CS_ENSURE(d_jobs, R); CS_ENSURE(d_lines, 4 * N + 4); CS_ENSURE(d_tab, 3 * plane + 1); CS_ENSURE(d_ptr, 2); CS_ENSURE(d_lists, 2 * (R + 1));
+  CS_TRY(fork.create()); CS_TRY(join.create());
+  const int ptr[2] = {0, n};
+  CS_HIP_TRY(hipMemcpy(d_jobs.p, jobs.data(), sizeof(cs::JobDesc) * R, hipMemcpyHostToDevice));
+  if (n) CS_HIP_TRY(hipMemcpy(d_lines.p, lines, sizeof(double) * 4 * N, hipMemcpyHostToDevice));
+  CS_HIP_TRY(hipMemcpy(d_ptr.p, ptr, sizeof(ptr), hipMemcpyHostToDevice));
+  CS_HIP_TRY(hipMemset(d_tab.p, 0, sizeof(double) * (3 * plane + 1)));
+  cs::launch_line_setup_listed(d_jobs.p, r, d_lines.p, d_ptr.p, d_tab.p + plane, d_tab.p + 2 * plane, d_tab.p, dist_thre, angle_thre_deg, len_thre, nullptr, nullptr, nullptr, fork, join, d_lists.p);
+  CS_HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipMemcpy(jobs.data(), d_jobs.p, sizeof(cs::JobDesc) * R, hipMemcpyDeviceToHost));
+  if (plane) CS_HIP_TRY(hipMemcpy(dev_tab, d_tab.p, sizeof(double) * 3 * plane, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < R; k++) dev_m[k] = jobs[k].m;
+  return CS_OK;
+  CS_GUARD_END("cs_check_line_setup")
 }
 
 void cs_detect_default_params(cs_detect_params* p) {
@@ -1126,7 +1181,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   S.f0 = f0; S.f1 = f1;
   const int nf = f1 - f0;
   // ---- per frame, in parallel and straight into the pinned staging pools: job descriptors + sample lists (everything
-  // else of the setup happens in line_setup_kernel).  The pools use a capacity layout fixed by the inputs (a frame's
+  // else of the setup happens in the line setup kernels).  The pools use a capacity layout fixed by the inputs (a frame's
   // jobs, yaw samples and top-edge samples have known upper bounds), so no frame waits for another one's counts; a
   // box the reference skips (:215) leaves null jobs (Y = T = 0) that own no slots.
   const int jb0 = b->job_base[f0], bx0 = b->box_base[f0], tp0 = b->top_base[bx0];
@@ -1906,7 +1961,7 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
         jd.frame = f; jd.Y = nY; jd.T = (int)tops.size(); jd.RP = (int)cam_rp[f].size();
         JobHost jh;
         jh.frame = f; jh.box = bi; jh.hid = k; jh.yaw_off_local = yoff; jh.tops = tops;
-        // ROI line filter (:271-283) + merge (:288-296) + angles/midpoints (:309-315): line_setup_kernel, or here
+        // ROI line filter (:271-283) + merge (:288-296) + angles/midpoints (:309-315): the line setup kernels, or here
         if (dev_setup) { jd.m = 0; jh.line_cap = F.n_lines; R.jobs.push_back(jd); R.jh.push_back(std::move(jh)); continue; }
         std::vector<double> in;
         for (int e = 0; e < F.n_lines; e++) {
@@ -2021,9 +2076,10 @@ int round_sweep(RoundRun& X, RoundTables& T) {
   cs::DetectDeviceView& v = T.v;
   B.bind(v, *b, nj);      // (the c_* columns: bound again once they are sized, round_compact_score)
   CS_HIP_TRY(hipEventRecord(d->ev[6], st));
-  if (X.dev_setup) {
-    cs::launch_line_setup(B.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, B.mid_x.p, B.mid_y.p, B.ang.p,
-                          P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st);
+  if (X.dev_setup) {      // (one stream in both roles: the crowded ROIs' instances in stream order, between the classification and the others)
+    CS_ENSURE(b->round_ls_lists, 2 * (nj + 1));
+    cs::launch_line_setup_listed(B.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, B.mid_x.p, B.mid_y.p, B.ang.p,
+                                 P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, nullptr, st, d->ev[9], d->ev[10], b->round_ls_lists.p);
   }
   CS_HIP_TRY(hipEventRecord(d->ev[7], st));
   if (X.dev_setup) {

@@ -1,9 +1,11 @@
-// detect_types.h -- what detect_host.cpp hands to detect_kernels.hip: the device data layout of the proposal sweep
+// detect_types.h -- what detect_host.cpp hands to detect_kernels.hip and line_setup_kernels.hip: the device data layout of the proposal sweep
 // (see DESIGN.md "Path A: data layout in HBM") and the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 #include "../../include/cubeslam_hip.h"
 #include "cs_geom.h"
@@ -124,7 +126,19 @@ struct RpCarryView {
   int* cur_idx;                     // [n_frames] list in force
 };
 
-// ---- launchers (detect_kernels.hip)
+// ---- launchers (detect_kernels.hip; the line setup's: line_setup_kernels.hip)
+// diagnostics: CS_DETECT_SKIP=<names> leaves the named kernels out of the sweep, to measure their marginal cost in the saturated
+// pipeline (the results are then meaningless; never set outside a timing experiment)
+// Compiled in only with -DCS_DIAG (make DIAG=1): the shipped library has no switch that changes results, cs_diag_build() says which
+// build is loaded and bench.py refuses a diagnostic one.
+#ifdef CS_DIAG
+static bool skip_kernel(const char* name) {
+  static const char* e = getenv("CS_DETECT_SKIP");
+  return e && strstr(e, name) != nullptr;
+}
+#else
+static constexpr bool skip_kernel(const char*) { return false; }
+#endif
 void launch_vp_support(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st);
 void launch_vp_support_only(const DetectDeviceView& v, const SweepParams& sp, int vp_total, hipStream_t st, int rp_max = 0);      // rp_max: the jobs' largest roll/pitch sample count (0: unknown)
 void launch_vp_points(const DetectDeviceView& v, int vp_total, hipStream_t st);
@@ -141,8 +155,6 @@ void launch_rank(const DetectDeviceView& v, const RankView& rv, const RankParams
 void launch_records(const DetectDeviceView& v, const RankView& rv, int kmax, cs_cuboid* out, hipStream_t st, const double* raw_euler = nullptr, double rebuild_short_sq_bound = -1.0);
 void launch_rp_carry(const RpCarryView& c, JobDesc* jobs, hipStream_t st);
 void launch_rp_save_fallback(const DetectDeviceView& v, const RpSaveView& s, hipStream_t st);
-void launch_line_setup(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
-                       double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st);
 void launch_line_setup_listed(JobDesc* jobs, int n_jobs, const double* frame_lines, const int* frame_line_ptr, double* mid_x, double* mid_y, double* line_angle,
                               double dist_thre, double angle_thre_deg, double len_thre, hipStream_t st, const int* order, hipStream_t st_crowded, hipEvent_t fork, hipEvent_t join, int* crowded);
 int line_setup_capacity();

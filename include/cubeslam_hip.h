@@ -248,7 +248,7 @@ typedef struct cs_detect_timing {
   int n_fallback_boxes;              /* boxes whose ranking hit a tie and was redone on the host  */
   int n_redo_frames;                 /* roll/pitch sampling, lean path: frames redone round by round because of such a box */
   double rank_kernel_ms;
-  double line_setup_ms;              /* line_setup_kernel (ROI filter + merge_break_lines on the device)  */
+  double line_setup_ms;              /* the line setup kernels (ROI filter + merge_break_lines on the device)  */
   double score_kernel_ms;            /* score_kernel: distance + angle errors of the valid proposals       */
   long long score_kernel_bytes;      /* its algorithmic bytes                                   */
 } cs_detect_timing;
@@ -285,6 +285,15 @@ int cs_check_score_atan2(const double* y, const double* x, int n, double* out, i
  * a = 1 and b = 1.5 * 2^-53 the sum is 1 + 2^-52 under round-to-nearest and 1 under round-toward-zero, which tells whether the
  * lane's rounding mode is what the rest of the scorer's arithmetic assumes.  Runs on device 0. */
 int cs_check_score_sample_index(const double* sy, const double* sx, const int* map_w, const double* a, const double* b, int n, int* index, double* probe);
+/* A check of the line setup on its own: one frame's n segments (lines: n x 4 doubles x1 y1 x2 y2; n above the line setup's capacity of
+ * 512 rows is refused with CS_ERR_CAPACITY) against r expanded ROIs (rois: r x 4 ints, the inclusive bounds left top right bottom; yt:
+ * r x 2 ints, the job's yaw and top-edge sample counts -- a job with either at 0 is one the sweep skips and comes back with m = 0) and the
+ * three thresholds of merge_break_lines (gap in pixels, angle in degrees, length in pixels).  dev_m[k] and dev_tab = what the sweep's own
+ * launcher writes for ROI k -- the classification, both lists and every instance of the kernels --, host_m[k] and host_tab = what the
+ * host's line setup computes for it.  A table is three planes of r x n doubles, angle, mid x, mid y; row k holds m[k] entries, the rest
+ * is 0.  Runs on device 0. */
+int cs_check_line_setup(const double* lines, int n, const int* rois, const int* yt, int r, double dist_thre, double angle_thre_deg, double len_thre,
+                        int* dev_m, double* dev_tab, int* host_m, double* host_tab);
 
 
 /* ------------------------------------------------------------------ Path B: g2o bundle adjustment -- */

@@ -1,5 +1,5 @@
 """The device kernels take some of the reference's comparisons in a cheaper form and fall back to the exact evaluation inside a
-margin (cube_slam_wu_amd/csrc/detect_kernels.hip: atan2_float, vp_step, vp_support_multi pass 1, ls_pair_pass; cs_geom.h:
+margin (cube_slam_wu_amd/csrc: cs_atan2_float.h, detect_kernels.hip vp_step and vp_support_multi pass 1, line_setup_kernels.hip; cs_geom.h:
 sqrt_lt_bound / sqrt_le_bound).  The GPU parity tests show the results are unchanged on their inputs; these tests pin the error
 bounds the margins are built on, on the CPU, from the constants in the source."""
 import os
@@ -11,12 +11,13 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "cube_slam_wu_amd", "csrc", "detect_kernels.hip")
+SRC_ATAN2_FLOAT = os.path.join(ROOT, "cube_slam_wu_amd", "csrc", "cs_atan2_float.h")
+SRC_LINE_SETUP = os.path.join(ROOT, "cube_slam_wu_amd", "csrc", "line_setup_kernels.hip")
 
 
 def _atan2_float_coefficients():
     """The polynomial of atan2_float, read from the source (highest power first)."""
-    text = open(SRC).read()
+    text = open(SRC_ATAN2_FLOAT).read()
     body = text[text.index("__device__ __forceinline__ float atan2_float("):]
     body = body[: body.index("return at;")]
     first = re.search(r"float at = (-?[0-9.]+)f;", body).group(1)
@@ -335,7 +336,7 @@ def test_line_pair_test_decisions_equal_the_exact_evaluation():
     including pairs built to sit on the thresholds.  The margin is read from the source."""
     rng = np.random.default_rng(31)
     f32 = np.float32
-    text = open(SRC).read()
+    text = open(SRC_LINE_SETUP).read()
     margin = f32(float(re.search(r"#define LS_MARGIN ([0-9.e+-]+)f", text).group(1)))
     assert margin == f32(1.5e-5)
     PI_F = f32(3.14159274)
