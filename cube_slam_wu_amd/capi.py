@@ -1252,7 +1252,7 @@ def sim3_pairs_linearize(batch, device=0):
 
 
 DECLARED_SYMBOLS += ["cs_pgo_create", "cs_pgo_destroy", "cs_pgo_set_vertices", "cs_pgo_set_estimates", "cs_pgo_set_edges", "cs_pgo_set_lm_params", "cs_pgo_chi2",
-                     "cs_pgo_linearize_edges", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
+                     "cs_pgo_linearize_edges", "cs_pgo_edge_terms", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
 
 
 def _u8p(a):
@@ -1305,6 +1305,13 @@ class PoseGraph:
         e, ji, jj = np.zeros((self.ne, 7)), np.zeros((self.ne, 7, 7)), np.zeros((self.ne, 7, 7))
         _chk(lib().cs_pgo_linearize_edges(self.h, _dp(e), _dp(ji), _dp(jj)), "cs_pgo_linearize_edges")
         return e, ji, jj
+
+    def edge_terms(self):
+        """Per edge, at the current estimates: dict Hii, Hij, Hjj (E, 7, 7), bi, bj (E, 7), chi2 (E) -- cs_pgo_edge_terms."""
+        E = self.ne
+        t = dict(Hii=np.zeros((E, 7, 7)), Hij=np.zeros((E, 7, 7)), Hjj=np.zeros((E, 7, 7)), bi=np.zeros((E, 7)), bj=np.zeros((E, 7)), chi2=np.zeros(E))
+        _chk(lib().cs_pgo_edge_terms(self.h, *(_dp(t[k]) for k in ("Hii", "Hij", "Hjj", "bi", "bj", "chi2"))), "cs_pgo_edge_terms")
+        return t
 
     def optimize(self, iters, cap=64):
         done = C.c_int()

@@ -297,6 +297,19 @@ int cs_pgo_linearize_edges(cs_pgo* G, double* err7, double* Ji49, double* Jj49) 
   return CS_OK;
 }
 
+int cs_pgo_edge_terms(cs_pgo* G, double* Hii49, double* Hij49, double* Hjj49, double* bi7, double* bj7, double* chi2_each) {
+  int rc = need(G, "cs_pgo_edge_terms", true); if (rc) return rc;
+  CS_HIP_TRY(hipSetDevice(G->device));
+  rc = linearize(G); if (rc) return rc;
+  const size_t E = (size_t)G->ne;
+  const struct { double* dst; const double* src; size_t n; } out[6] = {{Hii49, G->Hii.p, 49 * E}, {Hij49, G->Hij.p, 49 * E}, {Hjj49, G->Hjj.p, 49 * E},
+                                                                      {bi7, G->bi.p, 7 * E}, {bj7, G->bj.p, 7 * E}, {chi2_each, G->chi2_each.p, E}};
+  for (const auto& o : out)
+    if (o.dst) CS_HIP_TRY(hipMemcpyAsync(o.dst, o.src, o.n * sizeof(double), hipMemcpyDeviceToHost, G->st));
+  CS_HIP_TRY(hipStreamSynchronize(G->st));
+  return CS_OK;
+}
+
 // optimization_algorithm_levenberg.cpp:61-163 (the policy: cs_lm.h) + sparse_optimizer.cpp:354-419
 int cs_pgo_optimize(cs_pgo* G, int iterations, int* iterations_done, double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap) {
   int rc = need(G, "cs_pgo_optimize", true); if (rc) return rc;

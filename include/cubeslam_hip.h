@@ -703,8 +703,11 @@ int  cs_pgo_set_vertices(cs_pgo* g, int n, const double* sim8, const unsigned ch
 int  cs_pgo_set_estimates(cs_pgo* g, const double* sim8);
 /* optimizer.addEdge(EdgeSim3) n >= 1 times, replacing the handle's edges: vertices (vi, vj), setMeasurement(meas8) in the vertices'
  * layout, setInformation(info49) row-major 7 x 7 (NULL: identity for every edge).  Refused: an index out of range, vi == vj, a repeated
- * pair, a non-positive or non-finite measurement, a system above the budget.  A vertex without an edge keeps its estimate; an edge
- * between two fixed vertices counts in chi2 only.                                                                                  */
+ * pair, a non-positive or non-finite measurement, a non-finite information entry, a system above the budget.  A vertex without an edge
+ * keeps its estimate; an edge between two fixed vertices counts in chi2 only.
+ * THE INFORMATION IS TAKEN AS SYMMETRIC and is not checked for it: the assembly stores the LOWER triangle of each diagonal block
+ * J^T Omega J, g2o's solver reads the upper one, and the two agree only for a symmetric Omega.  (The per-edge products of
+ * cs_pgo_edge_terms are well defined for any matrix; an optimisation with an asymmetric one is not g2o's.)                          */
 int  cs_pgo_set_edges(cs_pgo* g, int n, const int* vi, const int* vj, const double* meas8, const double* info49);
 /* OptimizationAlgorithmLevenberg's two properties, as cs_ba_set_lm_params: ORB-SLAM2 calls setUserLambdaInit(1e-16).               */
 int  cs_pgo_set_lm_params(cs_pgo* g, double user_lambda_init, int max_trials_after_failure);
@@ -715,6 +718,11 @@ int  cs_pgo_chi2(cs_pgo* g, double* chi2, double* chi2_each);
  * estimates -- what computeError + linearizeOplus leave in _error, _jacobianOplusXi, _jacobianOplusXj; a zero block for a fixed
  * vertex.  Any of the three may be NULL.                                                                                           */
 int  cs_pgo_linearize_edges(cs_pgo* g, double* err7, double* Ji49, double* Jj49);
+/* Inspection: every edge's terms of the quadratic form at the current estimates, as constructQuadraticForm forms them
+ * (core/base_binary_edge.hpp:55-120, no robust kernel): J_i^T Omega J_i, J_i^T Omega J_j, J_j^T Omega J_j (n_edges x 49 each, row-major),
+ * -J_i^T Omega e, -J_j^T Omega e (n_edges x 7) and e^T Omega e (n_edges), with the Jacobians cs_pgo_linearize_edges gives; zero blocks for a
+ * fixed vertex.  These are the buffers the assembly gathers H and b from.  Any of the six may be NULL.                               */
+int  cs_pgo_edge_terms(cs_pgo* g, double* Hii49, double* Hij49, double* Hjj49, double* bi7, double* bj7, double* chi2_each);
 /* SparseOptimizer::optimize(iterations) (sparse_optimizer.cpp:354-419) with OptimizationAlgorithmLevenberg; *iterations_done and the
  * history arrays as cs_ba_optimize.  CS_ERR_NOT_RUN before cs_pgo_set_edges.                                                       */
 int  cs_pgo_optimize(cs_pgo* g, int iterations, int* iterations_done, double* chi2_hist, double* lambda_hist, int* trials_hist, int hist_cap);

@@ -22,6 +22,20 @@ Quaterniond(R)'s three diagonal branches cannot be reached through cs_pgo_linear
 whatever the error's rotation); test_big_rotation_update reaches them through the first update of a graph 2.6 rad off.
 
 The rejected-trial graph: chi2 within 10 x the 3.2e-6 that test_pgo_ref.py measures between the two precisions.
+
+Edge information.  Every graph above has Omega = I.  pgo_cases' fixscale_w, free_w and layout_w are the same graphs with a dense, per-edge
+Q diag(w) Q^T on every edge (test_trajectory, test_layout_weighted -- whose per-edge chi2 is the one direct check of pgo_error_kernel's
+Omega e), under the same contract; their optima lie 8e-3 .. 9e-2 from the unweighted ones (asserted in test_pgo_ref.py), so a kernel that
+reads another edge's Omega, or none, cannot pass.  Measured on an MI355X: states 8.1e-8 .. 1.7e-7, chi2 3.4e-8 .. 4.7e-7, lambda <= 2e-16.
+test_edge_terms holds cs_pgo_edge_terms' six products per edge to long-double products of the device's OWN e and J, within a rounding
+bound (measured: at most 0.11 of it); half of its matrices are asymmetric, the only place where a transposed read of info49 shows.
+Checked once on copies of the kernel: reading v.info[t] instead of v.info[49 k + t] fails test_edge_terms, both weighted trajectories,
+both weighted layouts and both mesh runs; reading W[7 c + r] fails test_edge_terms alone.
+
+The mesh (test_mesh, test_back_ends_mesh): 320 edges and 812 unknowns -- PGO_REDUCE_T = 256: the reductions' strided loops go round more
+than once -- and the one sparse plan here with a dense tail (27 positions, 189 unknowns; tests/test_pgo_plan_cpu.py asserts it from the
+host-only plan).  Measured: states 4.4e-7 and 3.6e-7, chi2 4.2e-10 and 4.5e-11, lambda 1.3e-9; sparse against dense after one iteration
+1.7e-14, against a tolerance of 4.9e-13.
 """
 import os
 
@@ -86,11 +100,53 @@ def test_edge_blocks():
     assert not failures, failures
 
 
-@pytest.mark.parametrize("name,lam", list(pc.TRAJECTORIES), ids=lambda v: str(v))
+def test_edge_terms():
+    """cs_pgo_edge_terms on the 46 hand-placed edges with dense information, every second matrix asymmetric (pgo_cases.edge_terms_case):
+    the six products formed in long double from the DEVICE's own e, J_i, J_j, entry by entry.  The numeric Jacobians' noise cancels this
+    way, so the bound is rounding's: 32 * 2^-53 * (|J|^T |Omega| |J|) per entry, likewise with |e| (two nested 7-term sums).  Another
+    edge's Omega, the identity, or a transposed read of info49 are errors of the entries' own size (test_pgo_ref.py: > 1e6 bounds).
+    Measured on an MI355X: the worst entry at 0.11 of its bound."""
+    g = pc.edge_terms_case()
+    G = capi.pose_graph_from_dict(g)
+    e, ji, jj = G.linearize_edges()
+    got = G.edge_terms()
+    G.close()
+    want = pc.edge_terms_expected(g["info49"], e, ji, jj)
+    fx_i, fx_j = g["fixed"][g["vi"]].astype(bool), g["fixed"][g["vj"]].astype(bool)
+    assert fx_i.any() and fx_j.any() and (~fx_i & ~fx_j).any()
+    for nm, m in (("Hii", fx_i), ("bi", fx_i), ("Hij", fx_i | fx_j), ("Hjj", fx_j), ("bj", fx_j)):
+        assert np.all(got[nm][m] == 0), nm                                         # a fixed vertex: exactly zero blocks
+    assert np.all(np.abs(got["Hii"][~fx_i]).max(axis=(1, 2)) > 0) and np.all(np.abs(got["Hjj"][~fx_j]).max(axis=(1, 2)) > 0)
+    failures = []
+    for nm in ("Hii", "Hij", "Hjj", "bi", "bj", "chi2"):
+        val, bound = want[nm]
+        assert got[nm].shape == val.shape and np.isfinite(got[nm]).all(), nm
+        err = np.abs(np.asarray(got[nm], np.longdouble) - val)
+        worst = float((err / np.where(bound > 0, bound, 1)).max())
+        print("%s: worst error / bound %.3g (largest entry %.3g)" % (nm, worst, float(np.abs(val).max())))
+        if not np.all(err <= bound):
+            failures.append((nm, worst, np.flatnonzero((err > bound).reshape(len(err), -1).any(-1)).tolist()))
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("name,lam", list(pc.TRAJECTORIES) + list(pc.WEIGHTED_TRAJECTORIES), ids=lambda v: str(v))
 def test_trajectory(name, lam):
-    it = pc.TRAJECTORIES[(name, lam)]
+    it = pc.TRAJECTORIES[(name, lam)] if (name, lam) in pc.TRAJECTORIES else pc.WEIGHTED_TRAJECTORIES[(name, lam)]
     G, done = _run(pc.graph(name), lam, it)
     _compare(G, done, pc.ref_run(name, lam, it), "%s lambda %g" % (name, lam))
+    G.close()
+
+
+@pytest.mark.parametrize("lam", [0.0, 1e-16])
+def test_mesh(lam):
+    """pgo_cases.mesh_graph: 320 edges and 812 unknowns (the reductions' strided loops go round more than once) on the sparse path WITH a
+    dense tail (27 positions, 189 unknowns: tests/test_pgo_plan_cpu.py) -- tail assembly, its rocSOLVER factorisation, the substitution
+    that skips tail columns, on 7-wide blocks."""
+    G, done = _run(pc.graph("mesh"), lam, pc.MESH_ITERATIONS)
+    assert G.solver_path()[0] == "sparse"
+    _compare(G, done, pc.ref_run("mesh", lam, pc.MESH_ITERATIONS), "mesh lambda %g" % lam)
+    fixed = list(pc.MESH_FIXED)
+    assert np.array_equal(G.vertices()[fixed], pc.graph("mesh")["sim8"][fixed])
     G.close()
 
 
@@ -103,17 +159,27 @@ def test_rejected_trials():
     G.close()
 
 
-@pytest.mark.parametrize("lam", [0.0, 1e-16])
-def test_layout(lam):
-    G, done = _run(pc.graph("layout"), lam, pc.LAYOUT_ITERATIONS)
-    R = pc.ref_run("layout", lam, pc.LAYOUT_ITERATIONS)
-    _compare(G, done, R, "layout lambda %g" % lam)
-    assert np.array_equal(G.vertices()[20], pc.graph("layout")["sim8"][20])        # the vertex without an edge keeps its estimate
-    assert np.array_equal(G.vertices()[[0, 33, 34]], pc.graph("layout")["sim8"][[0, 33, 34]])
-    c, each = G.chi2(each=True)
+def _layout(name, lam):
+    G, done = _run(pc.graph(name), lam, pc.LAYOUT_ITERATIONS)
+    R = pc.ref_run(name, lam, pc.LAYOUT_ITERATIONS)
+    _compare(G, done, R, "%s lambda %g" % (name, lam))
+    assert np.array_equal(G.vertices()[20], pc.graph(name)["sim8"][20])            # the vertex without an edge keeps its estimate
+    assert np.array_equal(G.vertices()[[0, 33, 34]], pc.graph(name)["sim8"][[0, 33, 34]])
+    c, each = G.chi2(each=True)                                                    # (pgo_error_kernel's own Omega e, per edge)
     rc, reach = R.chi2()
     assert abs(c - float(rc)) < 1e-5 * float(rc) and np.abs(each - reach).max() < 1e-5 * float(reach.max())
     G.close()
+
+
+@pytest.mark.parametrize("lam", [0.0, 1e-16])
+def test_layout(lam):
+    _layout("layout", lam)
+
+
+@pytest.mark.parametrize("lam", [0.0, 1e-16])
+def test_layout_weighted(lam):
+    """The layout graph with dense information on every edge; the per-edge chi2 is the one direct check of pgo_error_kernel's Omega product."""
+    _layout(pc.WEIGHTED_LAYOUT[0], lam)
 
 
 def test_back_ends(monkeypatch):
@@ -127,6 +193,30 @@ def test_back_ends(monkeypatch):
     assert ps == "sparse" and 0 < fill <= 0.35 and pd == "dense" and fill_d == 0
     _compare(Gs, done_s, R, "layout, sparse")
     _compare(Gd, done_d, R, "layout, dense")
+    Gs.close(); Gd.close()
+
+
+def test_back_ends_mesh(monkeypatch):
+    """The mesh after ONE iteration on the sparse path (dense tail) and on rocSOLVER's: both factorise the same bits of H + lambda I, so
+    the states differ by factorisation rounding alone.  Tolerance: 100 x what three float64 factorisations of the reference's system
+    differ by (pgo_cases.mesh_factorisation_deviation, 4.9e-15; asserted below 1e-10 in test_pgo_ref.py) -- 100 x because the device's
+    orders (minimum degree with a dense tail; rocSOLVER's blocked one) are further from the reference's than its two are from each other.
+    Measured on an MI355X: 1.7e-14 against the tolerance of 4.9e-13."""
+    tol = 100 * pc.mesh_factorisation_deviation()
+    g = pc.graph("mesh")
+    monkeypatch.delenv("CS_PGO_FORCE_DENSE", raising=False)
+    Gs, done_s = _run(g, 0.0, 1)
+    monkeypatch.setenv("CS_PGO_FORCE_DENSE", "1")
+    Gd, done_d = _run(g, 0.0, 1)
+    monkeypatch.delenv("CS_PGO_FORCE_DENSE")
+    (ps, fill), (pd, fill_d) = Gs.solver_path(), Gd.solver_path()
+    assert ps == "sparse" and 0 < fill <= 0.35 and pd == "dense" and fill_d == 0
+    assert done_s == done_d == 1 and Gs.history()[2].tolist() == Gd.history()[2].tolist() == [1]
+    dev = pgo_ref.state_deviation(Gs.vertices(), Gd.vertices())
+    moved = pgo_ref.state_deviation(Gs.vertices(), g["sim8"])
+    print("mesh, one iteration, sparse against dense: states %.3g (tolerance %.3g; the step itself %.3g)" % (dev, tol, moved))
+    assert moved > 1e-3                                                            # (the step was taken)
+    assert dev <= tol, (dev, tol)
     Gs.close(); Gd.close()
 
 
@@ -206,7 +296,14 @@ def test_argument_errors():
     bad = np.tile([0, 0, 0, 1, 0, 0, 0, 1.0], (2, 1)); bad[1, 7] = 0.0
     assert rc_edges([0, 1], [1, 2], bad) == INVALID and "scale" in capi.last_error()         # a non-positive scale
     assert rc_edges([], []) == INVALID
+    for bad_value in (np.nan, np.inf):                                                       # a non-finite information entry, in the last edge
+        W = np.ascontiguousarray(np.tile(np.eye(7).ravel(), (2, 1))); W[1, 48] = bad_value
+        m = np.ascontiguousarray(np.tile([0, 0, 0, 1, 0, 0, 0, 1.0], (2, 1)))
+        two = np.array([0, 1], np.int32), np.array([1, 2], np.int32)
+        assert L.cs_pgo_set_edges(G.h, 2, capi._ip(two[0]), capi._ip(two[1]), capi._dp(m), capi._dp(W)) == INVALID
+        assert "information of edge 1 is not finite" in capi.last_error()
     assert L.cs_pgo_optimize(G.h, 1, None, None, None, None, 0) == NOT_RUN                   # every refusal left the handle without edges
+    assert L.cs_pgo_edge_terms(G.h, None, None, None, None, None, None) == NOT_RUN
     s = g["sim8"].copy(); s[5, 7] = -1.0
     with pytest.raises(RuntimeError, match="non-positive scale"):
         G.set_estimates(s)

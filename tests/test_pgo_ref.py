@@ -8,7 +8,15 @@
       the kind and size float64 differs from long double by, so the reference's own share must leave the other half.  With seed 1 the
       far graph's lambda differed by 1.1e-5 between the two precisions; pgo_cases.SEED = 2 is a seed where it does not.
 Measured (float64 against long double): state deviations 4e-8 .. 2.5e-7, chi2 1.2e-7 .. 1.8e-6 (the far graph), lambda <= 1.2e-7; the
-rejected-trial graph: trials [1, 6], states 1.1e-7, chi2 3.2e-6."""
+rejected-trial graph: trials [1, 6], states 1.1e-7, chi2 3.2e-6.
+
+The graphs with dense edge information (pgo_cases: fixscale_w, free_w, layout_w) and the 11 x 11 mesh go through the same four rules:
+states 4.2e-8 .. 9.9e-8 (mesh 2.6e-7, 4.4e-7), chi2 1.2e-7 .. 2.8e-6 (fixscale_w; mesh 5e-8), lambda <= 2.2e-7, min |rho| 1.9e-5 (free_w,
+lambda 1e-16).  Besides: the weighted optima lie more than 1e-3 from the unweighted ones (8e-3 .. 9e-2), so ignoring Omega cannot pass the
+1e-5 contract; the information generator and the mesh are what they claim; the rounding bound of test_pgo_gpu.py's test_edge_terms
+holds for float64 products and tells another edge's Omega, the identity and a transposed Omega; and the mesh's state after one step
+differs by 4.9e-15 between three float64 factorisations, the yardstick of the back ends' comparison there.  That the mesh keeps a
+dense tail in the sparse plan is tests/test_pgo_plan_cpu.py's."""
 import numpy as np
 import pytest
 
@@ -37,6 +45,87 @@ def test_conditions_of_the_gpu_comparisons(name, lam, iterations):
     else:
         assert a.stats.get("quirk", 0) == 0 and b.stats.get("quirk", 0) == 0                       # (c)
         assert _rel(a.chi2_hist, b.chi2_hist) < 5e-6 and _rel(a.lambda_hist, b.lambda_hist) < 5e-6  # (d)
+
+
+@pytest.mark.parametrize("name,lam,iterations", pc.weighted_runs(), ids=lambda v: str(v))
+def test_weighted_optimum_is_not_the_unweighted_one(name, lam, iterations):
+    """What makes the weighted runs a test of Omega: the same graph without information ends somewhere else -- 8e-3 (fixscale) to 9e-2
+    (layout) in state, against the 1e-5 contract.  A generator that drifts toward the identity is noticed here."""
+    a, b = pc.ref_run(name, lam, iterations), pc.ref_run(name[:-2], lam, iterations)
+    sep = pgo_ref.state_deviation(a.est, b.est)
+    print("%s lambda %g: weighted against unweighted %.3g" % (name, lam, sep))
+    assert sep > 1e-3
+
+
+def test_edge_information_is_what_it_claims():
+    W = pc.edge_information(40, pc.INFO_SEED).reshape(-1, 7, 7)
+    assert np.array_equal(W, W.transpose(0, 2, 1))                                                 # symmetric exactly
+    ev = np.linalg.eigvalsh(W)
+    assert ev.min() > 0.099 and ev.max() < 31.7 and (ev.max(-1) / ev.min(-1)).min() > 3            # 10 ** U(-1, 1.5) per axis, far from a multiple of I
+    off = W * (1 - np.eye(7))
+    assert np.abs(off).max(axis=(1, 2)).min() > 0.1                                                # every matrix has off-diagonal weight
+    assert min(np.abs(W[a] - W[b]).max() for a in range(40) for b in range(a)) > 0.1               # another matrix for every edge
+    for name in ("layout_w", "mesh"):
+        g = pc.graph(name)
+        assert g["info49"].shape == (len(g["vi"]), 49)
+    # the per-edge products' matrices: every second one asymmetric, the others not
+    T = pc.edge_terms_case()["info49"].reshape(-1, 7, 7)
+    asym = np.abs(T - T.transpose(0, 2, 1)).max(axis=(1, 2))
+    assert len(T) == 46 and np.all(asym[1::2] > 0.1) and np.all(asym[0::2] == 0)
+
+
+def test_edge_terms_bound_holds_for_float64_products_and_tells_a_wrong_omega():
+    """pgo_cases.edge_terms_expected, the yardstick of test_pgo_gpu.py's test_edge_terms, on the reference's own e, J_i, J_j: plain float64
+    products (numpy's order, not the kernel's) stay inside the rounding bound; the same products with the NEXT edge's Omega, with the
+    identity, or with Omega transposed do not -- the transposed one on the asymmetric matrices only."""
+    g = pc.edge_terms_case()
+    (e, Ji, Jj), _ = pc.edge_block_refs()
+    W = g["info49"].reshape(-1, 7, 7)
+    want = pc.edge_terms_expected(g["info49"], e, Ji, Jj)
+
+    def worst(Wk):
+        """Per edge: the largest error / bound over the six products formed in float64 with Wk (0 where both vanish)."""
+        got = dict(Hii=np.einsum("kra,krc,kcb->kab", Ji, Wk, Ji), Hij=np.einsum("kra,krc,kcb->kab", Ji, Wk, Jj), Hjj=np.einsum("kra,krc,kcb->kab", Jj, Wk, Jj),
+                   bi=-np.einsum("kra,krc,kc->ka", Ji, Wk, e), bj=-np.einsum("kra,krc,kc->ka", Jj, Wk, e), chi2=np.einsum("kr,krc,kc->k", e, Wk, e))
+        out = np.zeros(len(Wk))
+        for nm, (val, bound) in want.items():
+            err = np.abs(got[nm].astype(np.longdouble) - val).reshape(len(Wk), -1)
+            b = bound.reshape(len(Wk), -1)
+            assert np.all(err[b == 0] == 0)
+            out = np.maximum(out, (err / np.where(b > 0, b, 1)).max(-1).astype(float))
+        return out
+
+    assert worst(W).max() <= 1.0
+    live = np.abs(e).max(-1) > 0                   # (the exactly zero error between two identities has J != 0 and still tells)
+    assert worst(np.roll(W, -1, axis=0)).min() > 1e6 and worst(np.broadcast_to(np.eye(7), W.shape))[live].min() > 1e6
+    t = worst(W.transpose(0, 2, 1))
+    both_fixed = (g["fixed"][g["vi"]] & g["fixed"][g["vj"]]).astype(bool)      # (no Jacobian at all: e^T Omega e alone, which a transpose keeps)
+    asym = np.arange(len(W)) % 2 == 1
+    assert both_fixed.sum() == 1 and t[asym & ~both_fixed].min() > 1e6 and t[~asym | both_fixed].max() <= 1.0
+
+
+def test_mesh_graph_is_what_it_claims():
+    g = pc.mesh_graph()
+    w = pc.MESH_SIDE
+    pairs = list(zip(g["vi"].tolist(), g["vj"].tolist()))
+    assert len(g["sim8"]) == 121 and len(pairs) == 320 and len({(min(p), max(p)) for p in pairs}) == 320
+    assert sorted(np.flatnonzero(g["fixed"]).tolist()) == [0, 10, 60, 110, 120]
+    assert np.array_equal(np.flatnonzero(g["fix_scale"]), np.arange(2, 121, 5))
+    step = sorted({abs(i - j) for i, j in pairs})
+    assert step == [1, w, w + 1]                                                                   # right, down, one diagonal
+    straight = [(i, j) for i, j in pairs if abs(i - j) in (1, w)]
+    assert all(((i % w) + (i // w)) % 2 == 0 for i, j in straight) and any(i > j for i, j in straight) and any(i < j for i, j in straight)
+    G = pc.make_ref(g)
+    assert len(pairs) > 256 and G.n == 7 * 116 > 256                                               # PGO_REDUCE_T
+
+
+def test_mesh_factorisation_yardstick():
+    """The mesh's states after one step from three float64 factorisations of the reference's system (pgo_cases.mesh_factorisation_deviation;
+    measured 4.9e-15): 100 x this is the tolerance of test_pgo_gpu.py's test_back_ends_mesh.  After more iterations the deviation is
+    carried through the numeric Jacobians and no longer a factorisation's (a similar mesh: 5e-6 after three), hence one iteration there."""
+    dev = pc.mesh_factorisation_deviation()
+    print("mesh, one step, three float64 factorisations: state deviation %.3g" % dev)
+    assert 0 < dev < 1e-10
 
 
 def test_big_rotation_update_reaches_every_quaternion_branch():

@@ -106,6 +106,34 @@ def test_pgo_smaller_plan_inside_a_larger_buffer():
     _same_pgo(got, A, "the ring after layout")
 
 
+@functools.lru_cache(maxsize=None)
+def _mesh_alone():
+    G = capi.pose_graph_from_dict(pc.graph("mesh"))
+    try:
+        return _pgo_result(G, pc.MESH_ITERATIONS)
+    finally:
+        G.close()
+
+
+def test_pgo_a_plan_with_a_dense_tail_between_two_without():
+    """layout (no tail), the mesh (a dense tail of 189 unknowns: the tail's block and tcol come and go), layout again, on one handle."""
+    A, M = _pgo_alone("layout"), _mesh_alone()
+    assert A["path"] == "sparse" and M["path"] == "sparse"
+    B = capi.pose_graph_from_dict(pc.graph("layout"))
+    try:
+        first = _pgo_result(B, pc.LAYOUT_ITERATIONS)
+        _set_graph(B, pc.graph("mesh"))
+        mesh = _pgo_result(B, pc.MESH_ITERATIONS)
+        _set_graph(B, pc.graph("layout"))
+        again = _pgo_result(B, pc.LAYOUT_ITERATIONS)
+    finally:
+        B.close()
+    assert first["path"] == mesh["path"] == again["path"] == "sparse"
+    _same_pgo(first, A, "layout on a fresh handle")
+    _same_pgo(mesh, M, "the mesh after layout")
+    _same_pgo(again, A, "layout after the mesh")
+
+
 def test_ba_sparse_again_after_another_path():
     path0, x0 = _ba_alone()
     assert path0 == "sparse"
