@@ -374,13 +374,8 @@ struct cs_detector {
   // call to call (a batch built and torn down per frame spent most of the call in hipMalloc / hipFree)
   cs_batch* single = nullptr;
   std::mutex single_mu;
-  // the line-segment producer's resident scratch (lines_host.cpp owns its type; freed through lines_free)
-  void* lines_scratch = nullptr;
-  void (*lines_free)(void*) = nullptr;
-  void* lsd_scratch = nullptr;          // the same for the LSD branch (lsd_host.cpp)
-  void (*lsd_free)(void*) = nullptr;
-  void* lbd_scratch = nullptr;          // and for the line descriptors / matching (lbd_host.cpp)
-  void (*lbd_free)(void*) = nullptr;
+  // the resident scratch of the segment producers and the descriptor path, one slot each (cs::ScratchSlot; the holder owns the type, `free` gives it back)
+  struct { void* p = nullptr; void (*free)(void*) = nullptr; } scratch[cs::N_SCRATCH_SLOTS];
   std::mutex lines_mu;
 };
 
@@ -736,10 +731,8 @@ int cs_cam_euler_zyx(const double T_wc[16], double euler3[3]) {
 
 // internal (not in the public header): the line-segment producer (lines_host.cpp) runs on the detector's stream
 void* cs_internal_detector_stream(cs_detector* d) { return (void*)d->stream; }
-// lines_host.cpp: the producer's scratch slot, its lock, and the detector's worker pool
-void** cs_internal_detector_lines_slot(cs_detector* d, void (*deleter)(void*)) { d->lines_free = deleter; return &d->lines_scratch; }
-void** cs_internal_detector_lsd_slot(cs_detector* d, void (*deleter)(void*)) { d->lsd_free = deleter; return &d->lsd_scratch; }
-void** cs_internal_detector_lbd_slot(cs_detector* d, void (*deleter)(void*)) { d->lbd_free = deleter; return &d->lbd_scratch; }
+// the scratch slots (detect_hooks.h), their holders' lock, and the detector's worker pool
+void** cs_internal_detector_scratch_slot(cs_detector* d, int which, void (*deleter)(void*)) { d->scratch[which].free = deleter; return &d->scratch[which].p; }
 void* cs_internal_detector_lines_mutex(cs_detector* d) { return (void*)&d->lines_mu; }
 void cs_internal_detector_parallel(cs_detector* d, int n, void (*fn)(int, void*), void* ctx) { d->pool->run(n, [&](int i) { fn(i, ctx); }); }
 // (for the segment producers' image-long items: two threads per granted CPU at most, see cs_detector_create)
@@ -804,9 +797,7 @@ void cs_detector_destroy(cs_detector* d) {
   // before the resident batch and the producers' scratch go)
   if (d->stream) (void)hipStreamSynchronize(d->stream);
   if (d->single) { cs_batch_destroy(d->single); d->single = nullptr; }
-  if (d->lines_scratch && d->lines_free) { d->lines_free(d->lines_scratch); d->lines_scratch = nullptr; }
-  if (d->lsd_scratch && d->lsd_free) { d->lsd_free(d->lsd_scratch); d->lsd_scratch = nullptr; }
-  if (d->lbd_scratch && d->lbd_free) { d->lbd_free(d->lbd_scratch); d->lbd_scratch = nullptr; }
+  for (auto& s : d->scratch) if (s.p && s.free) { s.free(s.p); s.p = nullptr; }      // (EDLines, LSD, descriptors)
   if (d->streams) {
     // the five working streams are this detector's own or the shared set's, so they stay raw and go here
     if (d->streams->own_streams)

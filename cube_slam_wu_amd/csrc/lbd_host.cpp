@@ -6,7 +6,8 @@
 // The descriptor reads the Sobel derivatives of the blurred image, which are exactly what the EDLines producer's device stage leaves resident
 // (lines_kernels.hip: BinaryDescriptor::computeSobel, binary_descriptor.cpp:352-402, is the same GaussianBlur 5 x 5 sigma 1 + Sobel 16S), so detect +
 // describe costs one more kernel over the maps that are already there.  The arithmetic and its contract: cs_lbd.h; the kernels: lbd_kernels.hip.
-// Everything that launches them is here (lines_host.cpp knows none of it: tools/hostonly/lines_host_check.cpp builds that file alone).
+// Everything that launches them is here (lines_host.cpp knows none of it: tools/hostonly/lines_host_check.cpp builds that file alone).  Its scratch
+// lives in the detector's third slot (detect_hooks.h: cs::SCRATCH_LBD), under the same lock as the two producers'.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,7 +44,7 @@ struct LbdScratch {
 };
 void lbd_scratch_free(void* p) { delete (LbdScratch*)p; }      // (cs_detector_destroy has made the device current and waited for the stream)
 LbdScratch& scratch_of(cs_detector* d) {
-  void** slot = cs_internal_detector_lbd_slot(d, lbd_scratch_free);
+  void** slot = cs_internal_detector_scratch_slot(d, cs::SCRATCH_LBD, lbd_scratch_free);
   if (!*slot) *slot = new LbdScratch();
   return *(LbdScratch*)*slot;
 }

@@ -10,6 +10,8 @@
 //   validation      (LineValidation_ :2793-2874, nfa descriptor.hpp:764-848), end points, start / end order (OctaveKeyLines :1074-1143)
 // The arithmetic follows the reference operation for operation (same types: float normal-equation terms, double solve, float end points);
 // tests/test_lines_gpu.py holds it to the CPU restatement of the same detector bit for bit.  No CPU fallback for the device stages.
+// How a batch of images goes through the device and the worker pool is cs_image_batch.h's business (shared with lsd_host.cpp): this file supplies
+// the scratch, what to launch for a run of images, and the host stage of one image.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,8 +24,8 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
-#include "batch_gate.h"
 #include "cs_hip_util.h"
+#include "cs_image_batch.h"
 #include "cs_nfa.h"
 #include "detect_hooks.h"
 #include "lines_types.h"
@@ -234,17 +236,10 @@ struct Extractor {
   }
 };
 
-// Resident scratch of a detector's line producer: device maps and pinned host copies for `cap_images` images of `cap_pixels` pixels
-// (grows only).  A call used to pay three hipMalloc / hipFree pairs and five copies into pageable vectors.
-struct LinesScratch {
-  cs::DevBuf<unsigned char> d_gray, d_pk;
+// Resident scratch of a detector's line producer (grows only): beside the driver's, the packed maps on the device and their pinned copy
+struct LinesScratch : cs::ImageBatchScratch {
+  cs::DevBuf<unsigned char> d_pk;
   cs::PinBuf<unsigned char> h_pin;   // per image: the packed map, 3 bytes per pixel (+ 4 bytes of pad behind the last image)
-  cs::PinBuf<unsigned char> h_in;    // the batch's images side by side (one upload)
-  size_t cap = 0;                    // pixels x images the four hold (they grow together)
-  cs::ChunkEvents chunks;
-  cs::Event ev0, ev1;
-  double device_ms = 0, host_ms = 0, total_ms = 0;
-  int n_images = 0;
 };
 void lines_scratch_free(void* p) { delete (LinesScratch*)p; }      // (cs_detector_destroy has made the device current and waited for the stream)
 
@@ -313,12 +308,11 @@ int lines_host_stage(const Maps& M, const EdParams& P, double length_thres, floa
 
 }  // namespace
 
-// n_images gray images of one size: the per-pixel stages of all of them on the device (one kernel per image, queued back to back, the
-// maps copied into pinned staging), then the sequential halves side by side on the detector's worker pool.  lines4[i] receives image
-// i's segments (cap rows of 4), n_lines[i] their number.
+// n_images gray images of one size: the per-pixel stages on the device, the packed maps copied into pinned staging, the sequential halves side by
+// side on the detector's worker pool (cs::run_image_batch).  lines4[i] receives image i's segments (cap rows of 4), n_lines[i] their number.
 // The entry behind cs_detect_lines_batch, with two optional extras for the descriptor path (lbd_host.cpp; detect_hooks.h): extra[i] receives image i's
-// per-segment direction / pixel count, and `then` runs after the host stages, still under the producer's lock, with the batch's packed maps resident
-// on the device (image i's at d_p3 + 3 N i) and the detector's stream idle.
+// per-segment direction / pixel count, and `then` runs after the host stages and only if every image succeeded, still under the producers' lock,
+// with the batch's packed maps resident on the device (image i's at d_p3 + 3 N i) and the detector's stream idle.
 extern "C" int cs_internal_detect_lines_batch(cs_detector* d, const unsigned char* const* grays, int n_images, int img_w, int img_h, double length_thres, float* const* lines4, int cap,
                                               int* n_lines, cs::LineExtra* const* extra, int (*then)(void* ctx, const unsigned char* d_p3), void* then_ctx) {
   if (!d || n_images < 0 || (n_images && (!grays || !n_lines || (cap && !lines4))) || img_w < 3 || img_h < 3 || cap < 0) return CS_ERR_INVALID_ARG;
@@ -329,85 +323,26 @@ extern "C" int cs_internal_detect_lines_batch(cs_detector* d, const unsigned cha
     std::lock_guard<std::mutex> lk(*(std::mutex*)cs_internal_detector_lines_mutex(d));
     CS_HIP_TRY(hipSetDevice(cs_internal_detector_device(d)));
     hipStream_t st = (hipStream_t)cs_internal_detector_stream(d);
-    void** slot = cs_internal_detector_lines_slot(d, lines_scratch_free);
+    void** slot = cs_internal_detector_scratch_slot(d, cs::SCRATCH_EDLINES, lines_scratch_free);
     if (!*slot) *slot = new LinesScratch();
     LinesScratch& S = *(LinesScratch*)*slot;
     const double t_begin = cs::now_ms();
     const EdParams P;
     const size_t N = (size_t)img_w * img_h, need = N * (size_t)n_images;
-    if (need > S.cap) {
-      S.cap = 0;
-      int rc = S.d_gray.ensure(need);
-      if (!rc) rc = S.d_pk.ensure(3 * need + 4);
-      if (!rc) rc = S.h_pin.ensure(3 * need + 4);
-      if (!rc) rc = S.h_in.ensure(need);
-      if (rc) return rc;
-      S.cap = need;
-    }
-    if (!S.ev0) { CS_TRY(S.ev0.create()); CS_TRY(S.ev1.create()); }
+    CS_ENSURE(S.d_gray, need);
+    CS_ENSURE(S.d_pk, 3 * need + 4);
+    CS_ENSURE(S.h_pin, 3 * need + 4);
+    CS_ENSURE(S.h_in, need);
     int k[3];
     cs::lines_blur_taps(k);
-    const cs::LineMaps dm{S.d_pk.p};
-    struct Ctx {
-      const unsigned char* h_pk; int W, H; size_t N; const EdParams* P; double thr; float* const* lines4; int cap; int* n_lines; std::vector<int> rc;
-      cs::ChunkGate gate; int device; const hipEvent_t* done; int n_chunks, n_images;
-      const unsigned char* const* grays; unsigned char* h_in; cs::LineExtra* const* extra;
-    } ctx{S.h_pin.p, img_w, img_h, N, &P, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in.p, extra};
-    auto one = [](int i, void* vp) {
-      Ctx& c = *(Ctx*)vp;
-      Maps M; M.W = c.W; M.H = c.H; M.grad_thr = c.P->grad_thr; M.p3 = c.h_pk + 3 * c.N * (size_t)i;
-      try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i], c.extra ? c.extra[i] : nullptr); }
-      catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
+    auto launch = [&](int i0, int ni) {
+      cs::launch_lines_maps(S.d_gray.p + (size_t)i0 * N, img_w, img_h, cs::LineMaps{S.d_pk.p + 3 * N * (size_t)i0}, k, P.grad_thr, P.anchor_thr, P.scan, st, ni);
     };
-    double t_host;
-    if (n_images == 1) {
-      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, grays[0], N, hipMemcpyHostToDevice, st));
-      CS_HIP_TRY(hipEventRecord(S.ev0, st));
-      cs::launch_lines_maps(S.d_gray.p, img_w, img_h, dm, k, P.grad_thr, P.anchor_thr, P.scan, st, 1);
-      CS_HIP_TRY(hipGetLastError());
-      CS_HIP_TRY(hipEventRecord(S.ev1, st));
-      CS_HIP_TRY(hipMemcpyAsync(S.h_pin.p, S.d_pk.p, 3 * N, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipStreamSynchronize(st));
-      float ms = 0;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
-      S.device_ms = ms;
-      t_host = cs::now_ms();
-      one(0, &ctx);
-    } else {
-      // a batch: the images gathered into pinned memory by the pool (the caller's buffers are pageable), one upload, then chunk by chunk
-      // [kernel | copy back | event], all queued before the pool starts on the first chunk's images (batch_gate.h)
-      cs_internal_detector_parallel(d, n_images, [](int i, void* vp) { Ctx& c = *(Ctx*)vp; std::memcpy(c.h_in + c.N * (size_t)i, c.grays[i], c.N); }, &ctx);
-      const int CH = cs::BATCH_CHUNK, n_chunks = (n_images + CH - 1) / CH;
-      CS_HIP_TRY(S.chunks.reserve(n_chunks));
-      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, S.h_in.p, N * (size_t)n_images, hipMemcpyHostToDevice, st));
-      for (int c = 0; c < n_chunks; c++) {
-        const int i0 = c * CH, ni = std::min(CH, n_images - i0);
-        const cs::LineMaps mi{dm.p3 + 3 * (size_t)i0 * N};
-        CS_HIP_TRY(hipEventRecord(S.chunks.k0[c], st));
-        cs::launch_lines_maps(S.d_gray.p + (size_t)i0 * N, img_w, img_h, mi, k, P.grad_thr, P.anchor_thr, P.scan, st, ni);
-        CS_HIP_TRY(hipGetLastError());
-        CS_HIP_TRY(hipEventRecord(S.chunks.k1[c], st));
-        CS_HIP_TRY(hipMemcpyAsync(S.h_pin.p + 3 * N * (size_t)i0, S.d_pk.p + 3 * N * (size_t)i0, 3 * N * (size_t)ni, hipMemcpyDeviceToHost, st));
-        CS_HIP_TRY(hipEventRecord(S.chunks.done[c], st));
-      }
-      ctx.done = S.chunks.done.data(); ctx.n_chunks = n_chunks;
-      t_host = cs::now_ms();
-      cs_internal_detector_parallel_long(d, n_images + 1, [](int t, void* vp) {
-        Ctx& c = *(Ctx*)vp;
-        if (t == 0) { c.gate.watch(c.device, c.done, c.n_chunks, cs::BATCH_CHUNK, c.n_images); return; }
-        const int i = t - 1;
-        if (!c.gate.wait_for(i)) { c.rc[i] = CS_ERR_HIP; return; }
-        Maps M; M.W = c.W; M.H = c.H; M.grad_thr = c.P->grad_thr; M.p3 = c.h_pk + 3 * c.N * (size_t)i;
-        try { c.rc[i] = lines_host_stage(M, *c.P, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i], c.extra ? c.extra[i] : nullptr); }
-        catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
-      }, &ctx);
-      CS_HIP_TRY(hipStreamSynchronize(st));
-      double dev = 0;
-      for (int c = 0; c < n_chunks; c++) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, S.chunks.k0[c], S.chunks.k1[c])); dev += ms; }
-      S.device_ms = dev;
-    }
-    S.host_ms = cs::now_ms() - t_host; S.total_ms = cs::now_ms() - t_begin; S.n_images = n_images;
-    for (int r : ctx.rc) if (r) return r;
+    auto stage = [&](int i) {
+      Maps M; M.W = img_w; M.H = img_h; M.grad_thr = P.grad_thr; M.p3 = S.h_pin.p + 3 * N * (size_t)i;
+      return lines_host_stage(M, P, length_thres, lines4 ? lines4[i] : nullptr, cap, &n_lines[i], extra ? extra[i] : nullptr);
+    };
+    CS_TRY(cs::run_image_batch(d, S, t_begin, grays, n_images, N, S.d_pk.p, S.h_pin.p, 3 * N, 3 * N, launch, stage));
     return then ? then(then_ctx, S.d_pk.p) : CS_OK;
   } catch (const std::exception& ex) {
     cs_set_error(std::string("cs_detect_lines_batch: ") + ex.what());
@@ -425,13 +360,8 @@ extern "C" int cs_detect_lines_batch(cs_detector* d, const unsigned char* const*
 extern "C" int cs_detect_lines_last_timing(cs_detector* d, double* device_ms, double* host_ms, double* total_ms) {
   if (!d) return CS_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(*(std::mutex*)cs_internal_detector_lines_mutex(d));
-  void** slot = cs_internal_detector_lines_slot(d, lines_scratch_free);
-  const LinesScratch* S = (const LinesScratch*)*slot;
-  if (!S) return CS_ERR_NOT_RUN;
-  if (device_ms) *device_ms = S->device_ms;
-  if (host_ms) *host_ms = S->host_ms;
-  if (total_ms) *total_ms = S->total_ms;
-  return CS_OK;
+  const LinesScratch* S = (const LinesScratch*)*cs_internal_detector_scratch_slot(d, cs::SCRATCH_EDLINES, lines_scratch_free);
+  return S ? cs::batch_last_timing(*S, device_ms, host_ms, total_ms) : CS_ERR_NOT_RUN;
 }
 
 extern "C" int cs_detect_lines_gray(cs_detector* d, const unsigned char* gray, int img_w, int img_h, double length_thres, float* lines4, int cap, int* n_lines) {

@@ -12,6 +12,8 @@
 //                                  the second slopes -- and the binomial tail of cs_nfa.h (first term n + 1, as :1107 has it)
 // The arithmetic follows the reference operation for operation; tests/test_lines_gpu.py holds the result to the CPU restatement
 // (itself pinned on the reference's saved segments) bit for bit.  No CPU fallback for the device stages.
+// How a batch of images goes through the device and the worker pool is cs_image_batch.h's business (shared with lines_host.cpp): this file
+// supplies the scratch, the resize tables and Gaussian taps, what to launch for a run of images, and the host stage of one image.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,9 +26,9 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
-#include "batch_gate.h"
 #include "cs_fast_atan.h"
 #include "cs_hip_util.h"
+#include "cs_image_batch.h"
 #include "cs_nfa.h"
 #include "detect_hooks.h"
 #include "lsd_types.h"
@@ -454,16 +456,11 @@ int lsd_host_stage(int img_w, int img_h, int Ws, int Hs, const float* deg, const
   return CS_OK;
 }
 
-// Resident scratch of a detector's LSD producer (grows only)
-struct LsdScratch {
-  cs::DevBuf<unsigned char> d_gray; cs::DevBuf<double> d_blur; cs::DevBuf<char> d_out, d_tab;
+// Resident scratch of a detector's LSD producer (grows only): beside the driver's, the blurred images, the planes and the resize tables
+struct LsdScratch : cs::ImageBatchScratch {
+  cs::DevBuf<double> d_blur; cs::DevBuf<char> d_out, d_tab;
   cs::PinBuf<char> h_out;           // per image [modulus (double) | angle (float degrees)]
-  cs::PinBuf<unsigned char> h_in;   // the batch's images side by side (one upload)
-  size_t cap_in = 0, cap_out = 0;   // input pixels x images (d_gray, d_blur, h_in grow together); bytes of the planes (d_out, h_out)
-  cs::ChunkEvents chunks;
   int tab_w = 0, tab_h = 0;
-  cs::Event ev0, ev1;
-  double device_ms = 0, host_ms = 0, total_ms = 0;
 };
 void lsd_scratch_free(void* p) { delete (LsdScratch*)p; }      // (cs_detector_destroy has made the device current and waited for the stream)
 
@@ -479,7 +476,7 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
     std::lock_guard<std::mutex> lk(*(std::mutex*)cs_internal_detector_lines_mutex(d));
     CS_HIP_TRY(hipSetDevice(cs_internal_detector_device(d)));
     hipStream_t st = (hipStream_t)cs_internal_detector_stream(d);
-    void** slot = cs_internal_detector_lsd_slot(d, lsd_scratch_free);
+    void** slot = cs_internal_detector_scratch_slot(d, cs::SCRATCH_LSD, lsd_scratch_free);
     if (!*slot) *slot = new LsdScratch();
     LsdScratch& S = *(LsdScratch*)*slot;
     const double t_begin = cs::now_ms();
@@ -487,22 +484,11 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
     const int Ws = (int)std::lrint(img_w * kScale), Hs = (int)std::lrint(img_h * kScale);
     const size_t N = (size_t)img_w * img_h, Ns = (size_t)Ws * Hs;
     const size_t out_stride = 8 * Ns + 4 * ((Ns + 1) & ~(size_t)1);       // per image: Ns doubles, Ns floats (padded to a multiple of 8 bytes)
-    if (N * (size_t)n_images > S.cap_in) {
-      S.cap_in = 0;
-      int rc = S.d_gray.ensure(N * (size_t)n_images);
-      if (!rc) rc = S.h_in.ensure(N * (size_t)n_images);
-      if (!rc) rc = S.d_blur.ensure(N * (size_t)n_images);
-      if (rc) return rc;
-      S.cap_in = N * (size_t)n_images;
-    }
-    if (out_stride * (size_t)n_images > S.cap_out) {
-      S.cap_out = 0;
-      int rc = S.d_out.ensure(out_stride * (size_t)n_images);
-      if (!rc) rc = S.h_out.ensure(out_stride * (size_t)n_images);
-      if (rc) return rc;
-      S.cap_out = out_stride * (size_t)n_images;
-    }
-    if (!S.ev0) { CS_TRY(S.ev0.create()); CS_TRY(S.ev1.create()); }
+    CS_ENSURE(S.d_gray, N * (size_t)n_images);
+    CS_ENSURE(S.h_in, N * (size_t)n_images);
+    CS_ENSURE(S.d_blur, N * (size_t)n_images);
+    CS_ENSURE(S.d_out, out_stride * (size_t)n_images);
+    CS_ENSURE(S.h_out, out_stride * (size_t)n_images);
     // resize's tables for this size: source offset and the two float weights per scaled column / row (pixel centres, INTER_LINEAR)
     const size_t tab_bytes = (size_t)(Ws + Hs) * (sizeof(int) + 2 * sizeof(float));
     if (S.tab_w != img_w || S.tab_h != img_h) {
@@ -527,8 +513,7 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
         yo[i] = s; ya[2 * i] = 1.f - f; ya[2 * i + 1] = f;
       }
       S.tab_w = S.tab_h = 0;
-      const int rc = S.d_tab.ensure(tab_bytes);
-      if (rc) return rc;
+      CS_ENSURE(S.d_tab, tab_bytes);
       CS_HIP_TRY(hipMemcpy(S.d_tab.p, host.data(), tab_bytes, hipMemcpyHostToDevice));
       S.tab_w = img_w; S.tab_h = img_h;
     }
@@ -545,66 +530,14 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
       for (int i = 0; i < 7; i++) G.k[i] *= sum;
     }
     const double rho = kQuant / std::sin(kPi * kAngTh / 180);
-    struct Ctx {
-      const char* h; size_t out_stride; int w, h0, Ws, Hs; size_t Ns; double thr; float* const* lines4; int cap; int* n_lines; std::vector<int> rc;
-      cs::ChunkGate gate; int device; const hipEvent_t* done; int n_chunks, n_images;
-      const unsigned char* const* grays; unsigned char* h_in; size_t N;
-    } ctx{S.h_out.p, out_stride, img_w, img_h, Ws, Hs, Ns, length_thres, lines4, cap, n_lines, std::vector<int>(n_images, 0), {}, cs_internal_detector_device(d), nullptr, 0, n_images, grays, S.h_in.p, N};
-    auto one = [](int i, void* vp) {
-      Ctx& c = *(Ctx*)vp;
-      const double* mod = (const double*)(c.h + c.out_stride * (size_t)i);
-      try { c.rc[i] = lsd_host_stage(c.w, c.h0, c.Ws, c.Hs, (const float*)(mod + c.Ns), mod, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i]); }
-      catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
+    auto launch = [&](int i0, int ni) {
+      cs::launch_lsd_maps(S.d_gray.p + (size_t)i0 * N, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur.p + (size_t)i0 * N, S.d_out.p + out_stride * (size_t)i0, out_stride, st, ni);
     };
-    double t_host;
-    if (n_images == 1) {
-      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, grays[0], N, hipMemcpyHostToDevice, st));
-      CS_HIP_TRY(hipEventRecord(S.ev0, st));
-      cs::launch_lsd_maps(S.d_gray.p, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur.p, S.d_out.p, out_stride, st, 1);
-      CS_HIP_TRY(hipGetLastError());
-      CS_HIP_TRY(hipEventRecord(S.ev1, st));
-      CS_HIP_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, out_stride, hipMemcpyDeviceToHost, st));
-      CS_HIP_TRY(hipStreamSynchronize(st));
-      float ms = 0;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
-      S.device_ms = ms;
-      t_host = cs::now_ms();
-      one(0, &ctx);
-    } else {
-      // a batch: the images gathered into pinned memory by the pool (the caller's buffers are pageable: 64 staged copies otherwise), one
-      // upload, then chunk by chunk [kernels | copy back | event] -- all queued before the pool starts on the first chunk (batch_gate.h)
-      cs_internal_detector_parallel(d, n_images, [](int i, void* vp) { Ctx& c = *(Ctx*)vp; std::memcpy(c.h_in + c.N * (size_t)i, c.grays[i], c.N); }, &ctx);
-      const int CH = cs::BATCH_CHUNK, n_chunks = (n_images + CH - 1) / CH;
-      CS_HIP_TRY(S.chunks.reserve(n_chunks));
-      CS_HIP_TRY(hipMemcpyAsync(S.d_gray.p, S.h_in.p, N * (size_t)n_images, hipMemcpyHostToDevice, st));
-      for (int c = 0; c < n_chunks; c++) {
-        const int i0 = c * CH, ni = std::min(CH, n_images - i0);
-        CS_HIP_TRY(hipEventRecord(S.chunks.k0[c], st));
-        cs::launch_lsd_maps(S.d_gray.p + (size_t)i0 * N, img_w, img_h, Ws, Hs, G, T, rho, S.d_blur.p + (size_t)i0 * N, S.d_out.p + out_stride * (size_t)i0, out_stride, st, ni);
-        CS_HIP_TRY(hipGetLastError());
-        CS_HIP_TRY(hipEventRecord(S.chunks.k1[c], st));
-        CS_HIP_TRY(hipMemcpyAsync(S.h_out.p + out_stride * (size_t)i0, S.d_out.p + out_stride * (size_t)i0, out_stride * (size_t)ni, hipMemcpyDeviceToHost, st));
-        CS_HIP_TRY(hipEventRecord(S.chunks.done[c], st));
-      }
-      ctx.done = S.chunks.done.data(); ctx.n_chunks = n_chunks;
-      t_host = cs::now_ms();
-      cs_internal_detector_parallel_long(d, n_images + 1, [](int t, void* vp) {
-        Ctx& c = *(Ctx*)vp;
-        if (t == 0) { c.gate.watch(c.device, c.done, c.n_chunks, cs::BATCH_CHUNK, c.n_images); return; }
-        const int i = t - 1;
-        if (!c.gate.wait_for(i)) { c.rc[i] = CS_ERR_HIP; return; }
-        const double* mod = (const double*)(c.h + c.out_stride * (size_t)i);
-        try { c.rc[i] = lsd_host_stage(c.w, c.h0, c.Ws, c.Hs, (const float*)(mod + c.Ns), mod, c.thr, c.lines4 ? c.lines4[i] : nullptr, c.cap, &c.n_lines[i]); }
-        catch (const std::exception&) { c.rc[i] = CS_ERR_CAPACITY; }
-      }, &ctx);
-      CS_HIP_TRY(hipStreamSynchronize(st));          // (every chunk's event has been waited for; this also surfaces a late error)
-      double dev = 0;
-      for (int c = 0; c < n_chunks; c++) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, S.chunks.k0[c], S.chunks.k1[c])); dev += ms; }
-      S.device_ms = dev;
-    }
-    S.host_ms = cs::now_ms() - t_host; S.total_ms = cs::now_ms() - t_begin;
-    for (int r : ctx.rc) if (r) return r;
-    return CS_OK;
+    auto stage = [&](int i) {
+      const double* mod = (const double*)(S.h_out.p + out_stride * (size_t)i);
+      return lsd_host_stage(img_w, img_h, Ws, Hs, (const float*)(mod + Ns), mod, length_thres, lines4 ? lines4[i] : nullptr, cap, &n_lines[i]);
+    };
+    return cs::run_image_batch(d, S, t_begin, grays, n_images, N, S.d_out.p, S.h_out.p, out_stride, out_stride, launch, stage);
   } catch (const std::exception& ex) {
     cs_set_error(std::string("cs_detect_lsd_batch: ") + ex.what());
     return CS_ERR_CAPACITY;
@@ -614,13 +547,8 @@ extern "C" int cs_detect_lsd_batch(cs_detector* d, const unsigned char* const* g
 extern "C" int cs_detect_lsd_last_timing(cs_detector* d, double* device_ms, double* host_ms, double* total_ms) {
   if (!d) return CS_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(*(std::mutex*)cs_internal_detector_lines_mutex(d));
-  void** slot = cs_internal_detector_lsd_slot(d, lsd_scratch_free);
-  const LsdScratch* S = (const LsdScratch*)*slot;
-  if (!S) return CS_ERR_NOT_RUN;
-  if (device_ms) *device_ms = S->device_ms;
-  if (host_ms) *host_ms = S->host_ms;
-  if (total_ms) *total_ms = S->total_ms;
-  return CS_OK;
+  const LsdScratch* S = (const LsdScratch*)*cs_internal_detector_scratch_slot(d, cs::SCRATCH_LSD, lsd_scratch_free);
+  return S ? cs::batch_last_timing(*S, device_ms, host_ms, total_ms) : CS_ERR_NOT_RUN;
 }
 
 extern "C" int cs_detect_lsd_gray(cs_detector* d, const unsigned char* gray, int img_w, int img_h, double length_thres, float* lines4, int cap, int* n_lines) {

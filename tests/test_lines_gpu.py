@@ -171,3 +171,31 @@ def test_lsd_batch_equals_single_calls_and_reports_errors():
     with pytest.raises(RuntimeError):
         det.detect_lines(np.zeros((4, 4), np.uint8), 15.0, use_lsd=True)
     det.close()
+
+
+@pytest.mark.parametrize("n_images", [2, 4, 5, 8])
+def test_batches_at_the_chunk_edges_equal_the_single_image_calls(n_images):
+    """The batch driver queues the images in chunks of four: a partial chunk, exactly one, one image over, exactly two.  Both producers and the
+    descriptor path, batch against one call per image (which the tests above pin to the oracles), bit for bit.  Small images need not have
+    segments one by one; every case compares some (oracle/edlines_oracle_py and lsd_oracle_py on these seeds: 13 to 52 EDLines and 25 to 114
+    LSD segments per case, no image without one)."""
+    rng = np.random.default_rng(9000 + n_images)
+    grays = [_synthetic(rng, 97, 131) for _ in range(n_images)]
+    det = capi.Detector(capi.default_params())
+    compared = 0
+    for use_lsd in (False, True):
+        got = det.detect_lines_batch(grays, 15.0, use_lsd=use_lsd)
+        assert len(got) == n_images
+        for a, g in zip(got, grays):
+            b = det.detect_lines(g, 15.0, use_lsd=use_lsd)
+            assert a.shape == b.shape and np.array_equal(a, b)
+            compared += len(b)
+    got = det.detect_descrip_lines_batch(grays, 15.0)
+    assert len(got) == n_images
+    for (kl_a, d_a), g in zip(got, grays):
+        kl_b, d_b = det.detect_descrip_lines(g, 15.0)
+        assert kl_a.shape == kl_b.shape and all(np.array_equal(kl_a[f], kl_b[f]) for f in kl_b.dtype.names)
+        assert d_a.shape == d_b.shape and np.array_equal(d_a, d_b)
+        compared += len(kl_b)
+    assert compared > 0
+    det.close()

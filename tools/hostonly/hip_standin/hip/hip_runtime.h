@@ -1,7 +1,7 @@
-// hip/hip_runtime.h -- a counting stand-in for the HIP runtime, for tools/hostonly/owners_check.cpp and ba_proj_edge_check.cpp alone (its
-// directory goes first on the include path).  Device and pinned memory are malloc, copies are memcpy, streams and events are tokens; everything
-// made is kept in a set of what is live, and a free or destroy of something that is not live aborts.  Only what cs_hip_util.h and ba_dbuf.h call
-// exists, and the two handle types that ba_types.h's launcher declarations name.
+// hip/hip_runtime.h -- a counting stand-in for the HIP runtime, for tools/hostonly/owners_check.cpp, ba_proj_edge_check.cpp and
+// image_batch_check.cpp alone (its directory goes first on the include path).  Device and pinned memory are malloc, copies are memcpy, streams and events are tokens; everything
+// made is kept in a set of what is live, and a free or destroy of something that is not live aborts.  Only what cs_hip_util.h, ba_dbuf.h and
+// cs_image_batch.h call exists, and the two handle types that ba_types.h's launcher declarations name.
 #pragma once
 #include <cstddef>
 #include <cstdio>
@@ -10,7 +10,7 @@
 #include <set>
 
 typedef int hipError_t;
-enum { hipSuccess = 0 };
+enum { hipSuccess = 0, hipErrorUnknown = 999 };
 enum { hipHostMallocDefault = 0, hipStreamNonBlocking = 1, hipEventDefault = 0, hipEventBlockingSync = 1, hipEventDisableTiming = 2 };
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
@@ -31,6 +31,8 @@ inline hipError_t drop(int kind, void* p) {
   std::free(p);
   return hipSuccess;
 }
+// the knob: the k-th hipEventSynchronize from now (1 = the next) returns an error; 0 = none does
+inline int& event_sync_fails_in() { static int k = 0; return k; }
 }  // namespace hip_standin
 
 inline const char* hipGetErrorString(hipError_t) { return "stand-in error"; }
@@ -53,3 +55,7 @@ inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) { return hip_standin::drop(hip_standin::STREAM, s); }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hip_standin::make(hip_standin::EVENT, (void**)e, sizeof(hipStandinToken)); }
 inline hipError_t hipEventDestroy(hipEvent_t e) { return hip_standin::drop(hip_standin::EVENT, e); }
+inline hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDefault); }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+inline hipError_t hipEventSynchronize(hipEvent_t) { int& k = hip_standin::event_sync_fails_in(); return k > 0 && --k == 0 ? hipErrorUnknown : hipSuccess; }
+inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.25f; return hipSuccess; }

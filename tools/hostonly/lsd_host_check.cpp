@@ -10,7 +10,7 @@
 void cs_set_error(const std::string& s) { fprintf(stderr, "%s\n", s.c_str()); }
 extern "C" void* cs_internal_detector_stream(cs_detector*) { return nullptr; }
 extern "C" int cs_internal_detector_device(cs_detector*) { return 0; }
-extern "C" void** cs_internal_detector_lsd_slot(cs_detector*, void (*)(void*)) { return nullptr; }
+extern "C" void** cs_internal_detector_scratch_slot(cs_detector*, int, void (*)(void*)) { return nullptr; }
 extern "C" void* cs_internal_detector_lines_mutex(cs_detector*) { return nullptr; }
 extern "C" void cs_internal_detector_parallel(cs_detector*, int, void (*)(int, void*), void*) {}
 extern "C" void cs_internal_detector_parallel_long(cs_detector*, int, void (*)(int, void*), void*) {}
