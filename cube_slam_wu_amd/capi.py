@@ -1251,6 +1251,85 @@ def sim3_pairs_linearize(batch, device=0):
     return err, jac
 
 
+# ------------------------------------------------------------------ Sim(3) RANSAC of keyframe pairs, batched ----------
+class CsSim3RansacParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int), ("max_iterations", C.c_int)]
+
+
+DECLARED_SYMBOLS += ["cs_sim3_ransac_default_params", "cs_sim3_ransac_pairs", "cs_sim3_ransac_create", "cs_sim3_ransac_destroy", "cs_sim3_ransac_run",
+                     "cs_sim3_ransac_last_timing", "cs_sim3_ransac_triplets", "cs_sim3_ransac_hypotheses"]
+
+
+def sim3_ransac_default_params(**kw):
+    """cs_sim3_ransac_default_params with overrides."""
+    p = CsSim3RansacParams()
+    lib().cs_sim3_ransac_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _sim3_ransac_inputs(batch):
+    """A batch dict (synth_sim3_ransac layout: intr, fix_scale, seed, match_ptr, P1, P2, max_err1, max_err2) as C arguments."""
+    intr = _f64(batch["intr"], (-1, 8)); n = len(intr)
+    ptr = _i32(batch["match_ptr"])
+    if len(ptr) != n + 1:
+        raise ValueError("match_ptr must hold n_pairs + 1 entries")
+    fs = np.ascontiguousarray(np.asarray(batch["fix_scale"]).ravel().astype(np.uint8))
+    seed = np.ascontiguousarray(np.asarray(batch["seed"]).ravel().astype(np.uint64))
+    if len(fs) != n or len(seed) != n:
+        raise ValueError("fix_scale and seed must hold one entry per pair")
+    N = int(ptr[-1]) if n else 0
+    P1, P2, t1, t2 = _f64(batch["P1"], (N, 3)), _f64(batch["P2"], (N, 3)), _f64(batch["max_err1"], (N,)), _f64(batch["max_err2"], (N,))
+    keep = (intr, fs, seed, ptr, P1, P2, t1, t2)
+    return n, N, keep, (_dp(intr), _u8p(fs), seed.ctypes.data_as(C.POINTER(C.c_ulonglong)), _ip(ptr), _dp(P1), _dp(P2), _dp(t1), _dp(t2))
+
+
+def _sim3_ransac_call(fn, head, batch, params):
+    p = params if params is not None else sim3_ransac_default_params()
+    n, N, keep, args = _sim3_ransac_inputs(batch)
+    found, hyp, its, n_in = (np.zeros(n, np.int32) for _ in range(4))
+    S_out, inl = np.zeros((n, 8)), np.zeros(N, np.uint8)
+    rc = fn(*head, C.byref(p), n, *args, _ip(found), _ip(hyp), _ip(its), _dp(S_out), _u8p(inl), _ip(n_in))
+    return rc, dict(found=found, hyp=hyp, iterations=its, S12=S_out, inlier=inl, n_inliers=n_in)
+
+
+class Sim3Ransac(_BatchHandle):
+    """cs_sim3_ransac handle: keeps its stream and device buffers between run() calls."""
+
+    _SYM = "cs_sim3_ransac"
+
+    def run(self, batch, params=None):
+        """-> dict: found, hyp, iterations, n_inliers (n), S12 (n, 8), inlier (N, uint8)."""
+        rc, out = _sim3_ransac_call(lib().cs_sim3_ransac_run, (self.h,), batch, params)
+        _chk(rc, "cs_sim3_ransac_run")
+        return out
+
+
+def sim3_ransac_pairs(batch, params=None, device=0):
+    """cs_sim3_ransac_pairs: the one-shot form."""
+    rc, out = _sim3_ransac_call(lib().cs_sim3_ransac_pairs, (int(device),), batch, params)
+    _chk(rc, "cs_sim3_ransac_pairs")
+    return out
+
+
+def sim3_ransac_triplets(seed, n_matches, n_hyp):
+    """cs_sim3_ransac_triplets -> (n_hyp, 3) match indices; runs without a device."""
+    out = np.zeros((int(n_hyp), 3), np.int32)
+    _chk(lib().cs_sim3_ransac_triplets(C.c_ulonglong(int(seed)), int(n_matches), int(n_hyp), _ip(out)), "cs_sim3_ransac_triplets")
+    return out
+
+
+def sim3_ransac_hypotheses(batch, n_hyp, device=0):
+    """cs_sim3_ransac_hypotheses -> (S12 (n, n_hyp, 8), count (n, n_hyp)): every hypothesis of every pair; a refused one has count -1."""
+    n, N, keep, args = _sim3_ransac_inputs(batch)
+    S, cnt = np.zeros((n, int(n_hyp), 8)), np.zeros((n, int(n_hyp)), np.int32)
+    _chk(lib().cs_sim3_ransac_hypotheses(int(device), n, *args, int(n_hyp), _dp(S), _ip(cnt)), "cs_sim3_ransac_hypotheses")
+    return S, cnt
+
+
 DECLARED_SYMBOLS += ["cs_pgo_create", "cs_pgo_destroy", "cs_pgo_set_vertices", "cs_pgo_set_estimates", "cs_pgo_set_edges", "cs_pgo_set_lm_params", "cs_pgo_chi2",
                      "cs_pgo_linearize_edges", "cs_pgo_edge_terms", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
 

@@ -810,6 +810,81 @@ int cs_sim3_pairs_last_timing(const cs_sim3_pairs* b, double* kernel_ms, double*
 int cs_sim3_pairs_linearize(int device, int n_pairs, const double* S12_in, const double* intr8, const unsigned char* fix_scale, const int* match_ptr,
       const double* P1, const double* P2, const double* obs1, const double* obs2, double* err4, double* jac28);
 
+/* ------------------------------------------------------------------ Path B'''': Sim(3) RANSAC of keyframe pairs, batched -- */
+/* Produces, for many keyframe pairs at once, the start S12 and the set of matches that cs_sim3_optimize_pairs takes: what an
+ * ORB-SLAM2-derived loop closer computes per loop candidate with Sim3Solver inside LoopClosing::ComputeSim3 (SetRansacParameters,
+ * iterate called until it succeeds or says bNoMore, ComputeSim3, CheckInliers; NOT IN THE REFERENCE).  The statement, which
+ * csrc/cs_sim3_ransac.h carries for host and device:
+ *   image points   p1 = proj1(P1), p2 = proj2(P2): the projections of the stored points themselves, as in Sim3Solver, not the
+ *                  keypoints; proj(P) = (fx P.x (1 / P.z) + cx, fy P.y (1 / P.z) + cy); no depth test.
+ *   budget         N = the pair's match count.  N < max(3, min_inliers): the pair is not run -- found 0, hyp -1, 0 iterations, 0
+ *                  inliers, every flag 0, S12_out the identity (0,0,0,1, 0,0,0, 1).  Otherwise eps = min_inliers / N, its = 1 if
+ *                  eps >= 1, else ceil(log(1 - probability) / log(1 - eps^3)) (max_iterations where log(1 - eps^3) rounds to 0),
+ *                  max_its = max(1, min(its, max_iterations)); worked out on the host in double.
+ *   draws          hypothesis h uses three distinct matches, drawn as Sim3Solver draws them: from the list 0 .. N-1 pick position r
+ *                  among the remaining entries, take it, overwrite it with the last entry, shrink.  r = splitmix64(seed + (3 h + k) *
+ *                  0x9E3779B97F4A7C15) modulo the remaining count, k = 0, 1, 2 (splitmix64's output function: z ^= z >> 30,
+ *                  z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31).  Counter-based: a lane computes its
+ *                  own triple, in closed form, without the list.
+ *   hypothesis     Horn 1987 as Sim3Solver::ComputeSim3: centroids O1, O2, centred triples Pr1, Pr2, M = Pr2 Pr1^T, the symmetric 4 x 4
+ *                    N11 = M00+M11+M22  N12 = M12-M21  N13 = M20-M02  N14 = M01-M10   N22 = M00-M11-M22  N23 = M01+M10
+ *                    N24 = M20+M02   N33 = -M00+M11-M22  N34 = M12+M21   N44 = -M00-M11+M22
+ *                  whose eigenvector of the largest eigenvalue is the quaternion (w, x, y, z), computed by 12 sweeps of cyclic Jacobi
+ *                  rotations, normalised, its sign flipped so that w >= 0 (w == 0: the first non-zero of x, y, z is positive).  R12 is
+ *                  built from the unit quaternion DIRECTLY: ORB-SLAM2 goes through atan2 and cv::Rodrigues to the same rotation; going
+ *                  direct needs no libm and has no 0 / 0 at the identity.  s = 1 under fix_scale, else sum(Pr1 . (R Pr2)) /
+ *                  sum((R Pr2)^2); t12 = O1 - s R O2; the inverse map is R^T / s, -R^T t / s.  A hypothesis whose s is not finite and
+ *                  positive (a repeated triple, coincident points) counts 0 inliers and is never stored.
+ *   inliers        a match is an inlier iff |p1 - proj1(s R P2 + t)|^2 < max_err1 AND |p2 - proj2(R^T (P1 - t) / s)|^2 < max_err2; a
+ *                  NaN or inf error is not an inlier.
+ *   selection      the sequential semantics of Sim3Solver::iterate: h = 0 .. max_its - 1; a hypothesis with count >= best becomes the
+ *                  stored best (>=: the LAST of equals is stored); the first with count > min_inliers (strict) ends the search,
+ *                  found = 1.  When nothing was found the stored best's transform, count and flags are handed out with found = 0
+ *                  (ORB-SLAM2 returns an empty matrix there); when nothing was stored, hyp = -1, the identity and no inlier.
+ *
+ * All pairs of a call are run by ONE kernel launch, one wavefront per pair, one lane per hypothesis, 64 hypotheses at a time
+ * (DESIGN.md section 14); a pair's outputs are the same bits at any position in any batch.  Every argument is checked on the host before
+ * anything is launched -- every value finite, thresholds >= 0, 0 < probability < 1, min_inliers >= 0, 1 <= max_iterations <= 1024,
+ * match_ptr[0] = 0 and non-decreasing, counts within int range -- and a refused call leaves the outputs untouched; no input makes the
+ * kernel read out of bounds, and every loop in it is bounded by max_iterations or by the pair's match count.                       */
+typedef struct cs_sim3_ransac_params {
+  double probability;               /* SetRansacParameters' probability (0.99)                                        */
+  int    min_inliers;               /* ... minInliers: more than this many inliers end the search (20)                */
+  int    max_iterations;            /* ... maxIterations, 1 .. 1024 (300)                                             */
+} cs_sim3_ransac_params;
+void cs_sim3_ransac_default_params(cs_sim3_ransac_params* p);
+/* Pair f owns matches match_ptr[f] .. match_ptr[f + 1] - 1.  Per match: P1 / P2 the matched map point in camera-1 / camera-2
+ * coordinates, max_err1 / max_err2 the squared pixel thresholds in image 1 / image 2 (ORB-SLAM2: 9.210 * sigma2 of the keypoint's octave).
+ * Outputs per pair: found_out; hyp_out the index of the hypothesis handed out (the winner, the stored best when nothing was found, or
+ * -1); iterations_out (hyp + 1 when found, else max_its); S12_out n_pairs x 8 in Sim3::operator[] order qx qy qz qw tx ty tz s, what
+ * cs_sim3_optimize_pairs takes as S12_in; n_inliers_out; inlier_out one byte per match.  hyp_out and iterations_out may be NULL.     */
+int cs_sim3_ransac_pairs(int device, const cs_sim3_ransac_params* p, int n_pairs,
+      const double* intr8,              /* n_pairs x 8: fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2                                 */
+      const unsigned char* fix_scale,   /* n_pairs                                                                      */
+      const unsigned long long* seed,   /* n_pairs: the pair's draws depend on nothing else                             */
+      const int* match_ptr,             /* n_pairs + 1                                                                  */
+      const double* P1, const double* P2, const double* max_err1, const double* max_err2,
+      int* found_out, int* hyp_out, int* iterations_out, double* S12_out, unsigned char* inlier_out, int* n_inliers_out);
+/* The same with a handle that keeps its stream and its device / pinned buffers between calls (they grow on demand and never shrink).
+ * Same arguments, same bits as the one-shot form.  Calls on one handle must not overlap.                                           */
+typedef struct cs_sim3_ransac cs_sim3_ransac;
+int cs_sim3_ransac_create(int device, cs_sim3_ransac** out);
+void cs_sim3_ransac_destroy(cs_sim3_ransac* b);
+int cs_sim3_ransac_run(cs_sim3_ransac* b, const cs_sim3_ransac_params* p, int n_pairs, const double* intr8, const unsigned char* fix_scale,
+      const unsigned long long* seed, const int* match_ptr, const double* P1, const double* P2, const double* max_err1, const double* max_err2,
+      int* found_out, int* hyp_out, int* iterations_out, double* S12_out, unsigned char* inlier_out, int* n_inliers_out);
+/* Of the handle's last call that passed its argument checks: kernel_ms = the one kernel, from hipEvents on the handle's stream;
+ * host_ms = the whole call on a monotonic clock (checking, packing, the two copies and the kernel included).                       */
+int cs_sim3_ransac_last_timing(const cs_sim3_ransac* b, double* kernel_ms, double* host_ms);
+/* Inspection.  The draws of hypotheses 0 .. n_hyp - 1 among n_matches >= 3 matches: out3 = n_hyp x 3 match indices.  Host only: it runs
+ * without a device.                                                                                                                */
+int cs_sim3_ransac_triplets(unsigned long long seed, int n_matches, int n_hyp, int* out3);
+/* Inspection: EVERY hypothesis 0 .. n_hyp - 1 (1 <= n_hyp <= 1024) of every pair, without budget or selection: S12_each = n_pairs x
+ * n_hyp x 8, count_each = n_pairs x n_hyp its inlier count.  A refused hypothesis (and every one of a pair with fewer than three
+ * matches) has the identity and count -1.                                                                                          */
+int cs_sim3_ransac_hypotheses(int device, int n_pairs, const double* intr8, const unsigned char* fix_scale, const unsigned long long* seed, const int* match_ptr,
+      const double* P1, const double* P2, const double* max_err1, const double* max_err2, int n_hyp, double* S12_each, int* count_each);
+
 #ifdef __cplusplus
 }
 #endif
