@@ -1330,6 +1330,84 @@ def sim3_ransac_hypotheses(batch, n_hyp, device=0):
     return S, cnt
 
 
+# ------------------------------------------------------------------ two-view triangulation of new map points, batched ----------
+class CsTriangulateParams(C.Structure):
+    _fields_ = [("min_baseline_ratio", C.c_double), ("max_cos_parallax", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double),
+                ("ratio_factor", C.c_double), ("scale_range", C.c_double)]
+
+
+DECLARED_SYMBOLS += ["cs_triangulate_default_params", "cs_triangulate_pairs", "cs_triangulate_create", "cs_triangulate_destroy", "cs_triangulate_run",
+                     "cs_triangulate_last_timing", "cs_triangulate_inspect"]
+
+# cs_triangulate_status / cs_triangulate_route
+TRI_STATUS = {"OK": 0, "PAIR_NOT_RUN": 1, "LOW_PARALLAX": 2, "W_ZERO": 3, "DEPTH1": 4, "DEPTH2": 5, "REPROJ1": 6, "REPROJ2": 7, "ZERO_DIST": 8, "SCALE": 9}
+TRI_ROUTE = {"NONE": 0, "TRIANGULATED": 1, "STEREO1": 2, "STEREO2": 3}
+
+
+def triangulate_default_params(**kw):
+    """cs_triangulate_default_params with overrides."""
+    p = CsTriangulateParams()
+    lib().cs_triangulate_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _triangulate_inputs(batch):
+    """A batch dict (synth_triangulate layout: Tcw1, Tcw2, cam1, cam2, median_depth2, match_ptr, kp1, kp2) as C arguments."""
+    T1 = _f64(batch["Tcw1"], (-1, 7)); n = len(T1)
+    T2, c1, c2, md = _f64(batch["Tcw2"], (n, 7)), _f64(batch["cam1"], (n, 6)), _f64(batch["cam2"], (n, 6)), _f64(batch["median_depth2"], (n,))
+    ptr = _i32(batch["match_ptr"])
+    if len(ptr) != n + 1:
+        raise ValueError("match_ptr must hold n_pairs + 1 entries")
+    N = int(ptr[-1]) if n else 0
+    k1, k2 = _f64(batch["kp1"], (N, 6)), _f64(batch["kp2"], (N, 6))
+    keep = (T1, T2, c1, c2, md, ptr, k1, k2)
+    return n, N, keep, (_dp(T1), _dp(T2), _dp(c1), _dp(c2), _dp(md), _ip(ptr), _dp(k1), _dp(k2))
+
+
+def _triangulate_call(fn, head, batch, params, inspect=False):
+    p = params if params is not None else triangulate_default_params()
+    n, N, keep, args = _triangulate_inputs(batch)
+    X, nrm, dmin, dmax = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros(N), np.zeros(N)
+    status, route, ran, n_acc = np.zeros(N, np.uint8), np.zeros(N, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+    out = dict(X=X, normal=nrm, min_distance=dmin, max_distance=dmax, status=status, route=route, ran=ran, n_accepted=n_acc)
+    tail = ()
+    if inspect:
+        out["cos3"] = np.zeros((N, 3))
+        tail = (_dp(out["cos3"]),)
+    rc = fn(*head, C.byref(p), n, *args, _dp(X), _dp(nrm), _dp(dmin), _dp(dmax), _u8p(status), _u8p(route), _u8p(ran), _ip(n_acc), *tail)
+    return rc, out
+
+
+class Triangulate(_BatchHandle):
+    """cs_triangulate handle: keeps its stream and device buffers between run() calls."""
+
+    _SYM = "cs_triangulate"
+
+    def run(self, batch, params=None):
+        """-> dict: X, normal (N, 3), min_distance, max_distance (N), status, route (N, uint8), ran (n, uint8), n_accepted (n)."""
+        rc, out = _triangulate_call(lib().cs_triangulate_run, (self.h,), batch, params)
+        _chk(rc, "cs_triangulate_run")
+        return out
+
+
+def triangulate_pairs(batch, params=None, device=0):
+    """cs_triangulate_pairs: the one-shot form."""
+    rc, out = _triangulate_call(lib().cs_triangulate_pairs, (int(device),), batch, params)
+    _chk(rc, "cs_triangulate_pairs")
+    return out
+
+
+def triangulate_inspect(batch, params=None, device=0):
+    """cs_triangulate_inspect: triangulate_pairs' outputs plus cos3 (N, 3) = cosRays, cosS1, cosS2 of every match."""
+    rc, out = _triangulate_call(lib().cs_triangulate_inspect, (int(device),), batch, params, inspect=True)
+    _chk(rc, "cs_triangulate_inspect")
+    return out
+
+
 DECLARED_SYMBOLS += ["cs_pgo_create", "cs_pgo_destroy", "cs_pgo_set_vertices", "cs_pgo_set_estimates", "cs_pgo_set_edges", "cs_pgo_set_lm_params", "cs_pgo_chi2",
                      "cs_pgo_linearize_edges", "cs_pgo_edge_terms", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
 

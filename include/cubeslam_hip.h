@@ -885,6 +885,87 @@ int cs_sim3_ransac_triplets(unsigned long long seed, int n_matches, int n_hyp, i
 int cs_sim3_ransac_hypotheses(int device, int n_pairs, const double* intr8, const unsigned char* fix_scale, const unsigned long long* seed, const int* match_ptr,
       const double* P1, const double* P2, const double* max_err1, const double* max_err2, int n_hyp, double* S12_each, int* count_each);
 
+/* ------------------------------------------------------------------ Path B''''': two-view triangulation of new map points, batched -- */
+/* Replaces, for the current keyframe and all of its covisible neighbours at once, the geometric part of
+ * LocalMapping::CreateNewMapPoints of an ORB-SLAM2-derived local mapper (with KeyFrame::UnprojectStereo, and
+ * MapPoint::UpdateNormalAndDepth for the two observations a new point has; NOT IN THE REFERENCE): per match the parallax decision,
+ * linear triangulation or a stereo back-projection in its place, two depth tests, two reprojection gates and the scale-consistency
+ * test.  ORB-SLAM2 computes them in float32 with OpenCV's SVD; this is FP64.  Pair f is (keyframe 1 = the current keyframe,
+ * keyframe 2 = a neighbour) and owns matches match_ptr[f] .. match_ptr[f + 1] - 1.  The statement, which csrc/cs_triangulate.h
+ * carries for host and device (its top comment gives every formula and the order of every sum):
+ *   per pair       R_i = the rotation of Tcw_i's quaternion (normalised), O_i = -R_i^T t_i, baseline = |O2 - O1|.
+ *                  median_depth2 > 0 (monocular): not run when baseline / median_depth2 < min_baseline_ratio;
+ *                  median_depth2 <= 0 (stereo): not run when baseline < b2.  Every match of such a pair: CS_TRI_PAIR_NOT_RUN.
+ *   per match      the first test that fails gives the status:
+ *   1 rays         xn_i = ((u_i - cx_i) / fx_i, (v_i - cy_i) / fy_i, 1), ray_i = R_i^T xn_i, cosRays their cosine; stereo_i = ur_i >= 0;
+ *                  cosS1 = cosS2 = cosRays + 1; if stereo1: cosS1 = (d1^2 - b1^2 / 4) / (d1^2 + b1^2 / 4) [= cos(2 atan2(b / 2, d))];
+ *                  ELSE if stereo2: the same for side 2 (the else is ORB-SLAM2's own); cosS = min(cosS1, cosS2).
+ *   2 route        cosRays < cosS && cosRays > 0 && (stereo1 || stereo2 || cosRays < max_cos_parallax): CS_TRI_ROUTE_TRIANGULATED,
+ *                  the right singular vector of the smallest singular value of the 4 x 4 DLT matrix by 8 sweeps of a one-sided
+ *                  (Hestenes) Jacobi; w == 0 or a coordinate not finite: CS_TRI_W_ZERO.  Otherwise stereo1 && cosS1 < cosS2: side 1's
+ *                  back-projection (KeyFrame::UnprojectStereo), CS_TRI_ROUTE_STEREO1; otherwise stereo2 && cosS2 < cosS1:
+ *                  CS_TRI_ROUTE_STEREO2; otherwise CS_TRI_LOW_PARALLAX, route CS_TRI_ROUTE_NONE.
+ *   3 depths       z of the point in camera 1 <= 0: CS_TRI_DEPTH1; in camera 2: CS_TRI_DEPTH2.
+ *   4 reprojection side 1 then side 2, squared pixel error (with the right-image term where ur_i >= 0) above chi2_mono sigma2_i
+ *                  (chi2_stereo sigma2_i): CS_TRI_REPROJ1 / CS_TRI_REPROJ2; a NaN error is a rejection.
+ *   5 scale        dist_i = |X - O_i|; one of them zero: CS_TRI_ZERO_DIST; ratioDist = dist2 / dist1, ratioOctave = scale1 / scale2;
+ *                  ratioDist ratio_factor < ratioOctave || ratioDist > ratioOctave ratio_factor: CS_TRI_SCALE.
+ *   6 accepted     CS_TRI_OK: normal = ((X - O1) / dist1 + (X - O2) / dist2) / 2 (not renormalised, as in ORB-SLAM2),
+ *                  max_distance = dist1 scale1, min_distance = max_distance / scale_range.
+ *
+ * All matches of a call are run by ONE kernel launch, one lane per match, one wavefront per chunk of at most 64 matches of one pair
+ * (DESIGN.md section 15); a match's outputs are the same bits at any position in any batch.  Every argument is checked on the host
+ * before anything is launched -- no NULL, n_pairs >= 0, match_ptr[0] = 0 and non-decreasing, every value finite, a quaternion of
+ * non-zero norm, fx fy sigma2 scale > 0, depth > 0 where ur >= 0, every parameter finite and positive -- and a refused call
+ * (CS_ERR_INVALID_ARG) leaves the outputs untouched.  n_pairs == 0 and pairs without matches are valid.                              */
+typedef enum cs_triangulate_status {
+  CS_TRI_OK = 0, CS_TRI_PAIR_NOT_RUN = 1, CS_TRI_LOW_PARALLAX = 2, CS_TRI_W_ZERO = 3, CS_TRI_DEPTH1 = 4, CS_TRI_DEPTH2 = 5,
+  CS_TRI_REPROJ1 = 6, CS_TRI_REPROJ2 = 7, CS_TRI_ZERO_DIST = 8, CS_TRI_SCALE = 9
+} cs_triangulate_status;
+typedef enum cs_triangulate_route {
+  CS_TRI_ROUTE_NONE = 0, CS_TRI_ROUTE_TRIANGULATED = 1, CS_TRI_ROUTE_STEREO1 = 2, CS_TRI_ROUTE_STEREO2 = 3
+} cs_triangulate_route;
+typedef struct cs_triangulate_params {
+  double min_baseline_ratio;        /* CreateNewMapPoints: ratioBaselineDepth < 0.01 skips a monocular neighbour (0.01)      */
+  double max_cos_parallax;          /* ... cosParallaxRays < 0.9998 for a match without stereo (0.9998)                      */
+  double chi2_mono;                 /* ... 5.991 * sigma2 (5.991)                                                            */
+  double chi2_stereo;               /* ... 7.8 * sigma2 (7.8)                                                                */
+  double ratio_factor;              /* ... 1.5 * the keyframe's scale factor (1.5 * 1.2)                                     */
+  double scale_range;               /* UpdateNormalAndDepth: scale factor to the power (levels - 1), max / min distance (1.2^7) */
+} cs_triangulate_params;
+/* CreateNewMapPoints' constants for ORB-SLAM2's default pyramid (scale factor 1.2, 8 levels). */
+void cs_triangulate_default_params(cs_triangulate_params* p);
+/* LocalMapping::CreateNewMapPoints over n_pairs (current keyframe, neighbour) pairs, one shot.  Outputs per match: X3_out the point in
+ * world coordinates (zeros when none was computed: CS_TRI_PAIR_NOT_RUN, CS_TRI_LOW_PARALLAX, CS_TRI_W_ZERO), normal3_out, min_distance_out
+ * and max_distance_out (zeros unless CS_TRI_OK), status_out, route_out; per pair: ran_out (0 = not run) and n_accepted_out, the number of
+ * CS_TRI_OK matches.                                                                                                                */
+int cs_triangulate_pairs(int device, const cs_triangulate_params* p, int n_pairs,
+      const double* Tcw1, const double* Tcw2,   /* n_pairs x 7 each, world-to-camera, SE3Quat::toVector order x y z qx qy qz qw   */
+      const double* cam1, const double* cam2,   /* n_pairs x 6 each: fx fy cx cy bf b (b = the stereo baseline in metres)          */
+      const double* median_depth2,              /* n_pairs: the neighbour's median scene depth; <= 0 selects the stereo rule       */
+      const int* match_ptr,                     /* n_pairs + 1                                                                     */
+      const double* kp1, const double* kp2,     /* n_matches x 6 each: u v ur depth sigma2 scale (ur < 0: none, depth not read)    */
+      double* X3_out, double* normal3_out, double* min_distance_out, double* max_distance_out,
+      unsigned char* status_out, unsigned char* route_out, unsigned char* ran_out, int* n_accepted_out);
+/* The same with a handle that keeps its stream and its device / pinned buffers between calls (they grow on demand and never shrink).
+ * Same arguments, same bits as the one-shot form.  Calls on one handle must not overlap.                                           */
+typedef struct cs_triangulate cs_triangulate;
+int cs_triangulate_create(int device, cs_triangulate** out);
+void cs_triangulate_destroy(cs_triangulate* b);
+int cs_triangulate_run(cs_triangulate* b, const cs_triangulate_params* p, int n_pairs, const double* Tcw1, const double* Tcw2, const double* cam1,
+      const double* cam2, const double* median_depth2, const int* match_ptr, const double* kp1, const double* kp2,
+      double* X3_out, double* normal3_out, double* min_distance_out, double* max_distance_out,
+      unsigned char* status_out, unsigned char* route_out, unsigned char* ran_out, int* n_accepted_out);
+/* Of the handle's last call that passed its argument checks: kernel_ms = the one kernel, from hipEvents on the handle's stream;
+ * host_ms = the whole call on a monotonic clock (checking, packing, the two copies and the kernel included).                       */
+int cs_triangulate_last_timing(const cs_triangulate* b, double* kernel_ms, double* host_ms);
+/* Inspection: CreateNewMapPoints' decision quantities beside its outcome.  As cs_triangulate_pairs, plus cos3_out = n_matches x 3:
+ * cosRays (cosParallaxRays), cosS1, cosS2 (cosParallaxStereo1 / 2) of every match of a pair that is run, zeros otherwise.          */
+int cs_triangulate_inspect(int device, const cs_triangulate_params* p, int n_pairs, const double* Tcw1, const double* Tcw2, const double* cam1,
+      const double* cam2, const double* median_depth2, const int* match_ptr, const double* kp1, const double* kp2,
+      double* X3_out, double* normal3_out, double* min_distance_out, double* max_distance_out,
+      unsigned char* status_out, unsigned char* route_out, unsigned char* ran_out, int* n_accepted_out, double* cos3_out);
+
 #ifdef __cplusplus
 }
 #endif
