@@ -14,8 +14,11 @@
 //   finish  (host, threaded)  cs_cuboid records of the winners (:740-798, object_3d_util.cpp:941-1011); the few boxes whose
 //                             ties could reach the output are fetched and ranked with the exact std::partial_sort.
 // The same stages exist as a general round-based path (debug getters, host ranking / host line setup on request).
-// What the paths share is stated once: the rules in front of the kernels in detect_jobs_host.h, those behind them in detect_rank_host.h,
-// the device tables and the view over them in SweepBuffers, the tie boxes' pass in TiePass.
+// What the paths share is stated once: the rules in front of the kernels in detect_jobs_host.h, those behind them in detect_rank_host.h
+// (the exact ranking, the host's corner rebuild, the record writers over the caller's output: OutView, write_exact_winners,
+// write_device_records), the camera cache in detect_cam_host.h, the device tables and the view over them in SweepBuffers, the tie boxes'
+// pass in TiePass, the launch / collect protocol of a lean path's slot in PipeSlot (begin, mark_in_flight, wait).  The worker pool of the
+// host stages is cs_worker_pool.h.
 // With whether_sample_cam_roll_pitch the reference carries cam_pose.camera_yaw from one box to the next
 // (:180 reads what :374/:734 left behind), so boxes of a frame are processed in rounds (round r = box r of
 // every frame), each ranked on the device; without it all boxes of all frames go through the sweep in one launch.
@@ -25,176 +28,36 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <memory>
 #include <mutex>
 #include <chrono>
 #include <cmath>
-#include <limits>
 #include <cstdio>
 #include <cstring>
 #include <deque>
-#include <functional>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
 #include "cs_hip_util.h"
+#include "cs_worker_pool.h"
+#include "detect_cam_host.h"      // (with detect_jobs_host.h and detect_rank_host.h)
 #include "detect_hooks.h"
-#include "detect_jobs_host.h"
-#include "detect_rank_host.h"
 #include "detect_types.h"
 #include "edge_types.h"
 
 thread_local std::string g_cs_err;  // shared by every path (cs_hip_util.h: cs_set_error)
 void cs_set_error(const std::string& s) { g_cs_err = s; }
 
-using namespace cs_dh;   // detect_jobs_host.h: the job-table rules; detect_rank_host.h: FrameIn, the slot decode, the exact ranking, the record writers
+using namespace cs_dh;   // detect_jobs_host.h: the job-table rules; detect_rank_host.h: FrameIn, the slot decode, the exact ranking, the record writers; detect_cam_host.h: the camera cache
 
 namespace {
 
 using cs::DevBuf;
 using cs::PinBuf;
+using cs::WorkerPool;
 using cs::now_ms;
-
-// Persistent worker pool for the host stages (one per detector; the calling thread takes part).
-class WorkerPool {
- public:
-  explicit WorkerPool(int n_workers) {
-    for (int i = 0; i < n_workers; i++) th_.emplace_back([this]() { loop(); });
-  }
-  ~WorkerPool() {
-    { std::lock_guard<std::mutex> lk(m_); stop_ = true; gen_++; }
-    cv_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-  // max_threads: at most this many threads (the caller included) take items -- for items that run for milliseconds, where more
-  // runnable threads than the CPU quota tolerates only get the process throttled
-  void run(int n, const std::function<void(int)>& fn, int max_threads = 0x7fffffff) {
-    if (n <= 0) return;
-    if (th_.empty() || n == 1) { for (int i = 0; i < n; i++) fn(i); return; }
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      fn_ = &fn; n_ = n; next_.store(0); joined_.store(0); limit_ = std::max(1, max_threads); pending_ = (int)th_.size(); gen_++;
-    }
-    cv_.notify_all();
-    work();
-    std::unique_lock<std::mutex> lk(m_);
-    done_.wait(lk, [this]() { return pending_ == 0; });
-    fn_ = nullptr;
-  }
- private:
-  void work() {
-    if (joined_.fetch_add(1) >= limit_) return;
-    for (;;) {
-      int i = next_.fetch_add(1);
-      if (i >= n_) break;
-      (*fn_)(i);
-    }
-  }
-  void loop() {
-    unsigned long long seen = 0;
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&]() { return gen_ != seen; });
-        seen = gen_;
-        if (stop_) return;
-      }
-      work();
-      {
-        std::lock_guard<std::mutex> lk(m_);
-        if (--pending_ == 0) done_.notify_all();
-      }
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex m_;
-  std::condition_variable cv_, done_;
-  const std::function<void(int)>* fn_ = nullptr;
-  std::atomic<int> next_{0}, joined_{0};
-  int n_ = 0, pending_ = 0, limit_ = 0x7fffffff;
-  unsigned long long gen_ = 0;
-  bool stop_ = false;
-};
-
-// ---------------------------------------------------------------- camera cache (set_cam_pose) ---
-struct M3 { double m[9]; };
-
-inline double cof3(const double* a, int i, int j) {
-  int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-  return a[3 * i1 + j1] * a[3 * i2 + j2] - a[3 * i1 + j2] * a[3 * i2 + j1];
-}
-// 3x3 inverse in cofactor form, the algorithm Eigen's Matrix3d::inverse() uses.
-void inv3(const double* a, double* r) {
-  double c0 = cof3(a, 0, 0), c1 = cof3(a, 1, 0), c2 = cof3(a, 2, 0);
-  double det = (c0 * a[0] + c1 * a[3]) + c2 * a[6];
-  double id = 1.0 / det;
-  r[0] = c0 * id; r[1] = c1 * id; r[2] = c2 * id;
-  r[3] = cof3(a, 0, 1) * id; r[4] = cof3(a, 1, 1) * id; r[5] = cof3(a, 2, 1) * id;
-  r[6] = cof3(a, 0, 2) * id; r[7] = cof3(a, 1, 2) * id; r[8] = cof3(a, 2, 2) * id;
-}
-void mul3(const double* a, const double* b, double* r) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) r[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
-}
-// Rotation matrix -> quaternion (Shoemake, as Eigen::Quaterniond(Matrix3d)) -> ZYX Euler angles
-// (matrix_utils.cpp:38-49).
-void rot_to_euler(const double* R, double e[3]) {
-  double w, q[3];
-  double t = R[0] + R[4] + R[8];
-  if (t > 0.0) {
-    t = std::sqrt(t + 1.0);
-    w = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[4 * i]) i = 2;
-    int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = std::sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
-    q[i] = 0.5 * t;
-    t = 0.5 / t;
-    w = (R[3 * k + j] - R[3 * j + k]) * t;
-    q[j] = (R[3 * j + i] + R[3 * i + j]) * t;
-    q[k] = (R[3 * k + i] + R[3 * i + k]) * t;
-  }
-  double qx = q[0], qy = q[1], qz = q[2];
-  e[0] = std::atan2(2 * (w * qx + qy * qz), 1 - 2 * (qx * qx + qy * qy));
-  e[1] = std::asin(2 * (w * qy - qz * qx));
-  e[2] = std::atan2(2 * (w * qz + qx * qy), 1 - 2 * (qy * qy + qz * qz));
-}
-// matrix_utils.cpp:81-96
-void euler_to_rot(double roll, double pitch, double yaw, double* R) {
-  double cp = h_cos(pitch), sp = h_sin(pitch), sr = h_sin(roll), cr = h_cos(roll), sy = h_sin(yaw), cy = h_cos(yaw);
-  R[0] = cp * cy; R[1] = (sr * sp * cy) - (cr * sy); R[2] = (cr * sp * cy) + (sr * sy);
-  R[3] = cp * sy; R[4] = (sr * sp * sy) + (cr * cy); R[5] = (cr * sp * sy) - (sr * cy);
-  R[6] = -sp; R[7] = sr * cp; R[8] = cr * cp;
-}
-
-struct CamCache {
-  cs::RpPose pose;  // KinvR, R, t, ground plane, roll, pitch
-  double euler[3];
-  double cam_yaw;
-};
-// set_cam_pose (box_proposal_detail.cpp:45-56) for rotation R (row-major 3x3) and position t.
-void make_cam(const double* K, const double* R, const double* t, CamCache& c) {
-  std::memcpy(c.pose.R, R, 9 * sizeof(double));
-  std::memcpy(c.pose.t, t, 3 * sizeof(double));
-  rot_to_euler(R, c.euler);
-  double invR[9];
-  inv3(R, invR);
-  mul3(K, invR, c.pose.KinvR);
-  c.cam_yaw = c.euler[2];
-  // ground plane in the sensor frame: T_wc^T (0,0,1,0)  (:130-131)
-  for (int i = 0; i < 3; i++) c.pose.plane[i] = ((R[0 + i] * 0.0 + R[3 + i] * 0.0) + R[6 + i] * 1.0) + 0.0 * 0.0;
-  c.pose.plane[3] = ((t[0] * 0.0 + t[1] * 0.0) + t[2] * 1.0) + 1.0 * 0.0;
-  c.pose.roll = c.euler[0];
-  c.pose.pitch = c.euler[1];
-}
 
 // merge_break_lines (object_3d_util.cpp:431-543) on a row-major n x 4 array.
 void merge_lines(std::vector<double>& L, double dist_thre, double angle_thre_deg, double len_thre) {
@@ -377,6 +240,10 @@ struct cs_detector {
   // the resident scratch of the segment producers and the descriptor path, one slot each (cs::ScratchSlot; the holder owns the type, `free` gives it back)
   struct { void* p = nullptr; void (*free)(void*) = nullptr; } scratch[cs::N_SCRATCH_SLOTS];
   std::mutex lines_mu;
+  // CS_DETECT_PROF (diagnostics): the host phase clock of this detector's lean-path runs, reported every eighth run (prof_report)
+  const bool prof = getenv("CS_DETECT_PROF") != nullptr;
+  double prof_mark[16] = {};
+  int prof_runs = 0;
 };
 
 // The side streams of one enqueue block (call it under enqueue_mu): the detector's own; or, with one stream per slot and no OTHER detector's
@@ -393,7 +260,6 @@ static void sweep_side_streams(const cs_detector* d, hipStream_t* corners, hipSt
 }
 
 struct JobHost {          // host-side companion of a JobDesc of the current round
-  int frame, box, hid;
   int yaw_off_local;
   std::vector<double> mids_x, mids_y, angs;
   std::vector<int> tops;
@@ -407,7 +273,7 @@ struct FrameRound {       // setup products of one frame in one round
 };
 
 struct JobResult {        // rank-stage products retained for cs_batch_debug_*
-  int frame, box, hid, n_valid;
+  int n_valid;
   std::vector<double> rows9;     // V x 9
   std::vector<long long> slots;  // V
   std::vector<int> keep;
@@ -457,33 +323,52 @@ struct PipeSlot {
   PinBuf<int> h_ls_order;
   DevBuf<cs_cuboid> records;        // the winners' records of the device-ranked boxes (record_kernel)
   PinBuf<cs_cuboid> h_records;
-  // lean roll/pitch path (rp_launch / rp_finish): all rounds of the batch queued at once
-  struct RpRound { size_t j0 = 0, nj = 0, b0 = 0, nb = 0; long long slot_cap = 0; int vp_cap = 0; };
-  std::vector<RpRound> rp_rounds;
-  std::vector<int> rp_box_frame, rp_box_index;      // per box (all rounds): frame, box of the frame
-  DevBuf<int> rp_trip_cnt;                           // valid slots per (job of a round, compaction trip)
-  DevBuf<int> rp_cur_idx, rp_tab_count, rp_maps;    // per frame: list in force; (frame, list) -> samples; per round: box / first job / jobs of a frame
-  DevBuf<long long> rp_last_slot, rp_box_base;
-  DevBuf<unsigned long long> rp_pool_used;
-  DevBuf<double> rp_raw_euler;
-  PinBuf<int> h_rp_tab_count, h_rp_maps;
-  PinBuf<double> h_rp_raw_euler;
-  PinBuf<long long> h_rp_last_slot, h_rp_box_base;
-  PinBuf<unsigned long long> h_rp_pool_used;
-  long long rp_pool_cap = 0;
-  int rp_NT = 0, rp_YCAP = 0;
-  std::deque<cs::Event> rp_ev;       // (a deque: it grows without moving an event)  5 per round: start, corners + compaction, VP support, scorer, ranking + records
   PinBuf<cs::JobDesc> h_jobs_in, h_jobs_out;
   PinBuf<long long> h_slot_prefix;
   PinBuf<int> h_vp_prefix, h_top_x, h_box_job0, h_box_njobs;
   PinBuf<double> h_yaw, h_yaw_c, h_yaw_s;
   cs::Event done, ev[13];                   // 0-6: phase marks on the main stream; 7: inputs resident; 8-11: second stream (corner construction); 12: line setup of the crowded ROIs done (third stream)
   cs::DetectDeviceView view{};
-  int f0 = 0, f1 = 0, vp_total = 0;
+  int vp_total = 0;
   size_t nj = 0, nb = 0;
   long long slot_total = 0;
   bool in_flight = false;
   bool counted_busy = false;      // this sweep is in the detector's and the stream set's `busy` counts
+  // ---- the slot protocol of both lean paths: begin (launch), ... enqueue ..., mark_in_flight (launch), wait (finish)
+  int begin() { if (!done) { CS_TRY(done.create()); for (auto& e : ev) CS_TRY(e.create()); } return CS_OK; }      // the events, on first use
+  // `done` closes the sweep queued on st; from here it counts as in flight for sweep_side_streams (a launch that queued kernels calls it still under enqueue_mu)
+  int mark_in_flight(cs_detector* d, hipStream_t st) {
+    CS_HIP_TRY(hipEventRecord(done, st));
+    in_flight = counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
+    return CS_OK;
+  }
+  void uncount(cs_detector* d) { if (counted_busy) { counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); } }
+  // the host collects the sweep.  The counts go down BEFORE the wait: an error return must not leave them up
+  int wait(cs_detector* d, cs_detect_timing& tm) {
+    const double tw = now_ms();
+    uncount(d);
+    CS_HIP_TRY(hipEventSynchronize(done));
+    tm.d2h_ms += now_ms() - tw;   // time the host actually waited for the GPU
+    in_flight = false;
+    return CS_OK;
+  }
+};
+
+// The lean roll/pitch path's own state (rp_launch / rp_finish: all rounds of the batch queued at once), once per batch beside pipe[0]
+struct RpLean {
+  struct Round { size_t j0 = 0, nj = 0, b0 = 0, nb = 0; long long slot_cap = 0; int vp_cap = 0; };
+  std::vector<Round> rounds;
+  std::vector<int> box_frame, box_index;      // per box (all rounds): frame, box of the frame
+  DevBuf<int> trip_cnt, cur_idx, tab_count, maps;   // valid slots per (job of a round, compaction trip); per frame: list in force; (frame, list) -> samples; per round: box / first job / jobs of a frame
+  DevBuf<long long> last_slot, box_base;
+  DevBuf<unsigned long long> pool_used;
+  DevBuf<double> raw_euler;
+  PinBuf<int> h_tab_count, h_maps;
+  PinBuf<double> h_raw_euler;
+  PinBuf<long long> h_last_slot, h_box_base;
+  PinBuf<unsigned long long> h_pool_used;
+  long long pool_cap = 0;
+  std::deque<cs::Event> ev;       // (a deque: it grows without moving an event)  5 per round: start, corners + compaction, VP support, scorer, ranking + records
 };
 
 struct BatchRunState;   // what a submitted (not yet collected) sweep keeps alive: camera caches, timing, the caller's output arrays
@@ -504,6 +389,7 @@ struct cs_batch {
   int refill_q[2] = {-1, -1}, n_refill = 0;   // image buffers whose upload is on its way, oldest first; the next submit queues the oldest one's front end
   PinBuf<float> h_maps_stage;               // map upload staging
   PipeSlot pipe[2];
+  std::unique_ptr<RpLean> rp;               // created by the first rp_launch
   // capacity layout of the lean path's staging pools (from the inputs alone): first job / first box of a frame, first
   // merged-segment row of a frame's jobs, first top-edge sample of a box
   std::vector<int> job_base, box_base, top_base;
@@ -513,6 +399,7 @@ struct cs_batch {
   int n_frames = 0, max_boxes = 0;
   std::vector<FrameIn> frames;
   DevBuf<float> d_maps;
+  const float* maps = nullptr;   // the map pool the sweep reads: d_maps.p (batch_fill), or -- the lean roll/pitch path's redo batch -- the parent batch's
   DevBuf<double> d_invK, d_frame_lines;
   DevBuf<int> d_frame_line_ptr;
   bool device_setup = false;   // every frame's segment count fits the line-setup kernel's LDS table
@@ -544,7 +431,7 @@ struct cs_batch {
 
 void SweepBuffers::bind(cs::DetectDeviceView& v, const cs_batch& b, size_t n_jobs, size_t j0, size_t p0, unsigned char* io, const SmallCallArena* A) const {
   v = cs::DetectDeviceView{};
-  v.jobs = jobs.p + j0; v.n_jobs = (int)n_jobs; v.slot_prefix = slot_prefix.p + p0; v.vp_prefix = vp_prefix.p + p0; v.maps = b.d_maps.p;
+  v.jobs = jobs.p + j0; v.n_jobs = (int)n_jobs; v.slot_prefix = slot_prefix.p + p0; v.vp_prefix = vp_prefix.p + p0; v.maps = b.maps;
   v.mid_x = mid_x.p; v.mid_y = mid_y.p; v.line_angle = ang.p; v.yaw = yaw.p; v.yaw_cos = yaw_c.p; v.yaw_sin = yaw_s.p; v.top_x = top_x.p;
   v.rp = b.d_rp.p; v.invK = b.d_invK.p; v.vp = vp.p; v.bound = bound.p; v.bound3 = bound3.p; v.flag = flag.p; v.job_valid = job_valid.p + j0;
   v.job_cbase = job_cbase.p + p0; v.c_slot = c_slot.p; v.c_flag = c_flag.p; v.c_dist = c_dist.p; v.c_angle = c_angle.p; v.c_skew = c_skew.p;
@@ -882,6 +769,7 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
   // upload the distance maps (zero padded) and the per-frame invK
   int rc = b->d_maps.ensure(map_floats + 1);
   if (rc) { return rc; }
+  b->maps = b->d_maps.p;
   {
     if (!grays) {
       // small pools (a frame, a few frames) go through pinned staging kept by the batch and a queued copy; a large batch's pool is
@@ -941,12 +829,10 @@ static int batch_fill(cs_detector* d, cs_batch* b, const cs_frame_desc* fr, cons
 // Second half of describing a batch: per-frame invK, the pooled line segments, the capacity layout of the staging pools.
 static int batch_layout(cs_detector* d, cs_batch* b) {
   const int n_frames = b->n_frames;
-  int rc;
   {
     std::vector<double> ik(9 * (size_t)std::max(1, n_frames));
     for (int f = 0; f < n_frames; f++) std::memcpy(&ik[9 * f], b->frames[f].invK, 9 * sizeof(double));
-    rc = b->d_invK.ensure(ik.size());
-    if (rc) { return rc; }
+    CS_ENSURE(b->d_invK, ik.size());
     CS_HIP_TRY(hipMemcpy(b->d_invK.p, ik.data(), sizeof(double) * ik.size(), hipMemcpyHostToDevice));
     // line segments (already left-to-right aligned), pooled, for the device-side line setup
     std::vector<int> lp(n_frames + 1, 0);
@@ -954,8 +840,7 @@ static int batch_layout(cs_detector* d, cs_batch* b) {
     for (int f = 0; f < n_frames; f++) { lp[f + 1] = lp[f] + b->frames[f].n_lines; if (b->frames[f].n_lines > cs::line_setup_capacity()) b->device_setup = false; }
     std::vector<double> fl(4 * (size_t)std::max(1, lp[n_frames]));
     for (int f = 0; f < n_frames; f++) if (b->frames[f].n_lines) std::memcpy(&fl[4 * (size_t)lp[f]], b->frames[f].lines.data(), 32 * (size_t)b->frames[f].n_lines);
-    rc = b->d_frame_lines.ensure(fl.size()); if (rc) { return rc; }
-    rc = b->d_frame_line_ptr.ensure(lp.size()); if (rc) { return rc; }
+    CS_ENSURE(b->d_frame_lines, fl.size()); CS_ENSURE(b->d_frame_line_ptr, lp.size());
     CS_HIP_TRY(hipMemcpy(b->d_frame_lines.p, fl.data(), 8 * fl.size(), hipMemcpyHostToDevice));
     CS_HIP_TRY(hipMemcpy(b->d_frame_line_ptr.p, lp.data(), 4 * lp.size(), hipMemcpyHostToDevice));
   }
@@ -1066,7 +951,7 @@ void cs_batch_destroy(cs_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->det->device);
   if (b->run_state) { (void)hipDeviceSynchronize(); batch_drop_run_state(b); }   // a submitted sweep that was never collected
-  for (PipeSlot& S : b->pipe) if (S.counted_busy) { S.counted_busy = false; b->det->busy.fetch_sub(1); b->det->streams->busy.fetch_sub(1); }
+  for (PipeSlot& S : b->pipe) S.uncount(b->det);
   delete b;
 }
 
@@ -1089,7 +974,7 @@ int cs_batch_set_debug(cs_batch* b, int enable) {
 namespace {
 
 struct PipeCtx {
-  cs_detector* d; cs_batch* b; cs_cuboid* out; int* out_counts;
+  cs_detector* d; cs_batch* b; OutView O;
   const std::vector<CamCache>* cam_raw; const std::vector<int>* rp_off;
   cs::SweepParams sp; cs_detect_timing* tm;
   const std::vector<std::vector<CamCache>>* cam_rp_all = nullptr;
@@ -1103,15 +988,14 @@ struct BatchRunState {
   cs_detect_timing tm{};
   double t_begin = 0;
   PipeCtx C{};
-  bool deferred = false;    // pipe_launch done, pipe_finish pending (cs_batch_collect)
   bool rp_lean = false;     // ... of the lean roll/pitch path (rp_launch / rp_finish)
 };
 namespace {
 
-static double g_mark[16];
-static int g_runs = 0;
-static const bool g_prof = getenv("CS_DETECT_PROF") != nullptr;   // diagnostics: host phase clock of the lean path
-#define MARK(k, t_ref) do { if (g_prof) { double t_now = now_ms(); g_mark[k] += t_now - (t_ref); (t_ref) = t_now; } } while (0)
+// CS_DETECT_PROF: phase k of detector d's host clock (cs_detector::prof_mark)
+// the device time between two events of a finished sweep, onto a timing field
+int add_elapsed(double& field, hipEvent_t a, hipEvent_t b) { float ms = 0; CS_HIP_TRY(hipEventElapsedTime(&ms, a, b)); field += ms; return CS_OK; }
+#define MARK(k, t_ref) do { if (d->prof) { double t_now = now_ms(); d->prof_mark[k] += t_now - (t_ref); (t_ref) = t_now; } } while (0)
 
 // The tie boxes of a finished sweep (B.h_fallback; B.h_job_cbase / h_job_valid say where their columns lie) get the exact ranking on the
 // host: enqueue_columns, wait, rank(q) per box on any thread, enqueue_corners, wait, corners(q, r) -- enqueue and wait apart, so that a
@@ -1168,8 +1052,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   hipStream_t st = d->stream;
   const int KMAX = P.max_cuboid_num;
   double t0 = now_ms(), tq = t0;
-  if (!S.done) { CS_TRY(S.done.create()); for (auto& e : S.ev) CS_TRY(e.create()); }
-  S.f0 = f0; S.f1 = f1;
+  CS_TRY(S.begin());
   const int nf = f1 - f0;
   // ---- per frame, in parallel and straight into the pinned staging pools: job descriptors + sample lists (everything
   // else of the setup happens in the line setup kernels).  The pools use a capacity layout fixed by the inputs (a frame's
@@ -1182,7 +1065,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   const size_t n_yaw = (size_t)nf * YCAP, n_top = (size_t)(b->top_base[b->box_base[f1]] - tp0);
   if ((long long)nj * 1 > 0x7fffffffLL || (long long)n_lines > 0x7fffffffLL) { cs_set_error("chunk too large"); return CS_ERR_CAPACITY; }
   S.nj = nj;
-  if (nj == 0) { S.nb = 0; S.slot_total = 0; S.vp_total = 0; S.in_flight = true; C.tm->setup_host_ms += now_ms() - t0; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
+  if (nj == 0) { S.nb = 0; S.slot_total = 0; S.vp_total = 0; C.tm->setup_host_ms += now_ms() - t0; return S.mark_in_flight(d, st); }
   CS_ENSURE(S.h_jobs_in, nj); CS_ENSURE(S.h_slot_prefix, nj + 1); CS_ENSURE(S.h_vp_prefix, nj + 1); CS_ENSURE(S.h_yaw, n_yaw + 1); CS_ENSURE(S.h_yaw_c, n_yaw + 1); CS_ENSURE(S.h_yaw_s, n_yaw + 1);
   CS_ENSURE(S.h_top_x, n_top + 1); CS_ENSURE(S.h_box_job0, nj); CS_ENSURE(S.h_box_njobs, nj); CS_ENSURE(S.h_ls_order, nj);
   std::atomic<int> overflow{0};
@@ -1237,8 +1120,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   // ---- device buffers, H2D, kernels, D2H: all asynchronous on the detector's stream
   const long long slot_total = S.slot_total;
   SweepBuffers& B = S.sb;
-  int rc;
-  if ((rc = B.ensure_tables(nj, nj + 1, n_lines, n_yaw, n_top, (size_t)S.vp_total, nb, KMAX)) || (rc = B.ensure_slots(slot_total))) return rc;
+  CS_TRY(B.ensure_tables(nj, nj + 1, n_lines, n_yaw, n_top, (size_t)S.vp_total, nb, KMAX)); CS_TRY(B.ensure_slots(slot_total));
   CS_ENSURE(B.bound3, nj * (size_t)cs::vp3_table_doubles_per_job());
   CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.blk_info, 2 * (size_t)(slot_total >> 8) + 4); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2);
   CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1); CS_ENSURE(S.h_jobs_out, nj);
@@ -1305,7 +1187,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
   CS_HIP_TRY(hipEventRecord(S.ev[4], st));
   cs::launch_score(v, C.sp, slot_total, slot_total, st);
   CS_HIP_TRY(hipEventRecord(S.ev[5], st));
-  cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
+  const cs::RankParams rkp = rank_params(P, C.sp);
   cs::launch_rank(v, rv, rkp, st, 0, false);          // (the host reads no winner of the device: record_kernel rebuilds their corners)
   cs::launch_records(v, rv, KMAX, p_records, st, nullptr, rkp.short_sq_bound);     // the records of the boxes the device ranked: only they come back
   CS_HIP_TRY(hipEventRecord(S.ev[6], st));
@@ -1318,9 +1200,7 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
     cs::add_copy(cp, B.h_job_valid, B.job_valid, nj); cs::add_copy(cp, B.h_job_cbase, B.job_cbase, nj + 1);      // (the job table itself is not read back: pipe_finish works from the host's own copy)
     cs::launch_multi_copy(cp, st);
   }
-  CS_HIP_TRY(hipEventRecord(S.done, st));
-  S.in_flight = true;
-  S.counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
+  CS_TRY(S.mark_in_flight(d, st));
   MARK(3, tq);   // allocations + enqueue of copies and kernels
   return CS_OK;
 }
@@ -1328,13 +1208,10 @@ int pipe_launch(PipeCtx& C, PipeSlot& S, int f0, int f1) {
 int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>& cam_rp) {
   cs_detector* d = C.d; cs_batch* b = C.b;
   const cs_detect_params& P = d->prm;
-  const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
+  const int KMAX = P.max_cuboid_num;
   cs_detect_timing& tm = *C.tm;
-  double tw = now_ms(), tq = tw;
-  if (S.counted_busy) { S.counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); }      // (before the wait: an error return must not leave the counts up)
-  CS_HIP_TRY(hipEventSynchronize(S.done));
-  tm.d2h_ms += now_ms() - tw;   // time the host actually waited for the GPU
-  S.in_flight = false;
+  double tq = now_ms();
+  CS_TRY(S.wait(d, tm));
   const size_t nj = S.nj, nb = S.nb;
   if (nj == 0) return CS_OK;
   SweepBuffers& B = S.sb;
@@ -1347,13 +1224,12 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   }
   double t0 = now_ms();
   {
-    float ms = 0;
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[1], S.ev[2])); tm.vp_kernel_ms += ms;
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[8], S.ev[9])); tm.cand_kernel_ms += ms;    // second stream: vanishing points + corners
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[9], S.ev[10])); tm.compact_ms += ms;
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[4], S.ev[5])); tm.score_kernel_ms += ms;
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[5], S.ev[6])); tm.rank_kernel_ms += ms;
+    CS_TRY(add_elapsed(tm.line_setup_ms, S.ev[0], S.ev[1]));
+    CS_TRY(add_elapsed(tm.vp_kernel_ms, S.ev[1], S.ev[2]));
+    CS_TRY(add_elapsed(tm.cand_kernel_ms, S.ev[8], S.ev[9]));    // second stream: vanishing points + corners
+    CS_TRY(add_elapsed(tm.compact_ms, S.ev[9], S.ev[10]));
+    CS_TRY(add_elapsed(tm.score_kernel_ms, S.ev[4], S.ev[5]));
+    CS_TRY(add_elapsed(tm.rank_kernel_ms, S.ev[5], S.ev[6]));
     tm.cand_kernel_launches += 1;
     long long n_valid = 0;      // (the capacity layout has no running total: job_cbase[j] = slot_prefix[j])
     for (size_t j = 0; j < nj; j++) n_valid += B.h_job_valid.p[j];
@@ -1370,37 +1246,27 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   // columns are fetched on the high-priority stream: the host waits for them while other sweeps (the next chunk's, or another
   // batch's of the same process) fill the device, and these few small kernels should not queue behind those.
   TiePass tie(B, S.view, d->stream_hi, S.h_box_job0.p, S.h_box_njobs.p, nj, nb);
-  int rc;
-  if ((rc = tie.enqueue_columns())) return rc;
+  CS_TRY(tie.enqueue_columns());
   MARK(5, tq);   // tie lists + gather enqueue
   // ---- records of the winners.  The boxes the device ranked are written while the tie boxes' columns travel.
   const std::vector<int>& fbq = tie.boxes;
   auto write_box = [&](size_t q) {
-    const int j0 = S.h_box_job0.p[q];
-    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = (int)tie.winners[q].size();
-    for (int r = 0; r < nw; r++) {
-      const ExactWinner& w = tie.winners[q][r];
-      const cs::JobDesc& jd = jobs[j0 + w.h];
-      const SlotRef s = decode_slot(jd, w.slot);
-      write_winner_record(b->frames[f], jd, s, w.flag, w.dist, w.angle, S.h_yaw.p[jd.yaw_off + s.y], cam_rp[f][s.rp].pose, tie.corners(q, r),
-                          (*C.cam_raw)[f].euler, false, w.score, C.out[((size_t)f * MB + bi) * KMAX + r]);
-    }
-    C.out_counts[(size_t)f * MB + bi] = nw;
+    const cs::JobDesc* bj = jobs + S.h_box_job0.p[q];
+    const int f = bj[0].frame;
+    write_exact_winners(C.O, b->frames[f], bj, tie.winners[q], S.h_yaw.p, cam_rp[f], (*C.cam_raw)[f].euler, false, corners_at(tie.corners(q, 0)));
   };
-  const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
+  const RankWeights RW = rank_weights(P);
   tm.n_fallback_boxes += (int)fbq.size();
   auto records = [&](int qi) {      // a device-ranked box: its records are complete but for the caller's rectangle
     const size_t q = (size_t)qi;
     if (B.h_fallback.p[q]) return;
-    const int j0 = S.h_box_job0.p[q];
-    const int f = jobs[j0].frame, bi = jobs[j0].box, nw = B.h_win_count.p[q];
-    for (int r = 0; r < nw; r++) copy_device_record(b->frames[f], bi, S.h_records.p[q * KMAX + r], C.out[((size_t)f * MB + bi) * KMAX + r]);
-    C.out_counts[(size_t)f * MB + bi] = nw;
+    const cs::JobDesc& j0 = jobs[S.h_box_job0.p[q]];
+    write_device_records(C.O, b->frames[j0.frame], j0.frame, j0.box, S.h_records.p + q * KMAX, B.h_win_count.p[q]);
   };
   if (fbq.size() <= 64) {
     // a handful of tie boxes (the usual case): their columns are a few kilobytes and already here; their exact ranking
     // (tens of microseconds each) rides in the same parallel pass as the records of the other boxes, first in the queue
-    if ((rc = tie.wait())) return rc;
+    CS_TRY(tie.wait());
     MARK(7, tq);   // wait for the tie columns
     const int nfb = (int)fbq.size();
     constexpr int RCH = 256;           // records are a 400-byte copy each: hand them out in chunks
@@ -1413,12 +1279,12 @@ int pipe_finish(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>
   } else {
     d->pool->run((int)nb, records);
     MARK(6, tq);   // records of the device-ranked boxes, written while the tie boxes' columns travel
-    if ((rc = tie.wait())) return rc;
+    CS_TRY(tie.wait());
     MARK(7, tq);   // wait for the tie columns
     d->pool->run((int)fbq.size(), [&](int z) { (void)tie.rank((size_t)fbq[z], RW, KMAX); });
   }
   MARK(8, tq);   // exact ranking of the tie boxes
-  if ((rc = tie.enqueue_corners(C.sp)) || (rc = tie.wait())) return rc;
+  CS_TRY(tie.enqueue_corners(C.sp)); CS_TRY(tie.wait());
   MARK(9, tq);   // corners of the tie winners
   if (fbq.size() <= 24) { for (int q : fbq) write_box((size_t)q); }
   else d->pool->run((int)fbq.size(), [&](int z) { write_box((size_t)fbq[z]); });
@@ -1443,8 +1309,9 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   hipStream_t st = d->stream;
   const int KMAX = P.max_cuboid_num, NF = b->n_frames, MB = b->max_boxes;
   double t0 = now_ms();
-  if (!S.done) { CS_TRY(S.done.create()); for (auto& e : S.ev) CS_TRY(e.create()); }
-  S.f0 = 0; S.f1 = NF;
+  CS_TRY(S.begin());
+  if (!b->rp) b->rp.reset(new RpLean());
+  RpLean& R = *b->rp;
   // ---- yaw lists: NT = 1 + max RP per frame, YCAP samples each
   int max_rp = 1;
   for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)cam_rp[f].size());
@@ -1452,13 +1319,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   const int YCAP = yaw_list_capacity(P.yaw_range_deg, P.yaw_step_deg);
   const size_t n_yaw = (size_t)NF * NT * YCAP;
   if (n_yaw > 0x7fffffffULL) { cs_set_error("too many yaw samples"); return CS_ERR_CAPACITY; }
-  CS_ENSURE(S.h_yaw, n_yaw + 1); CS_ENSURE(S.h_yaw_c, n_yaw + 1); CS_ENSURE(S.h_yaw_s, n_yaw + 1); CS_ENSURE(S.h_rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.h_rp_raw_euler, 3 * (size_t)NF + 1);
+  CS_ENSURE(S.h_yaw, n_yaw + 1); CS_ENSURE(S.h_yaw_c, n_yaw + 1); CS_ENSURE(S.h_yaw_s, n_yaw + 1); CS_ENSURE(R.h_tab_count, (size_t)NF * NT + 1); CS_ENSURE(R.h_raw_euler, 3 * (size_t)NF + 1);
   std::atomic<int> overflow{0};
   std::vector<int> ycap_f(NF, 0);     // longest list of the frame: its boxes' slots are laid out for it
   d->pool->run(NF * NT, [&](int z) {
     const int f = z / NT, i = z % NT;
     const int nrp = (int)cam_rp[f].size();
-    int* cnt = S.h_rp_tab_count.p + (size_t)f * NT + i;
+    int* cnt = R.h_tab_count.p + (size_t)f * NT + i;
     *cnt = 0;
     if (i > nrp) return;
     const double cam_yaw = i == 0 ? (*C.cam_raw)[f].cam_yaw : cam_rp[f][i - 1].cam_yaw;
@@ -1469,26 +1336,26 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   });
   if (overflow) { cs_set_error("yaw sample list exceeds its capacity"); return CS_ERR_CAPACITY; }
   for (int f = 0; f < NF; f++) {
-    for (int i = 0; i < NT; i++) ycap_f[f] = std::max(ycap_f[f], S.h_rp_tab_count.p[(size_t)f * NT + i]);
-    for (int e = 0; e < 3; e++) S.h_rp_raw_euler.p[3 * f + e] = (*C.cam_raw)[f].euler[e];
+    for (int i = 0; i < NT; i++) ycap_f[f] = std::max(ycap_f[f], R.h_tab_count.p[(size_t)f * NT + i]);
+    for (int e = 0; e < 3; e++) R.h_raw_euler.p[3 * f + e] = (*C.cam_raw)[f].euler[e];
   }
   // ---- jobs of all rounds: (round, frame, height sample); per round its own slot / vanishing-point numbering
   size_t nj_tot = 0, nb_tot = 0;
   for (int f = 0; f < NF; f++) for (int bi = 0; bi < b->frames[f].n_boxes; bi++) nj_tot += b->frames[f].n_heights[bi];
   const size_t n_top = (size_t)b->top_base[b->box_base[NF]];
   CS_ENSURE(S.h_jobs_in, nj_tot + 1); CS_ENSURE(S.h_slot_prefix, nj_tot + MB + 1); CS_ENSURE(S.h_vp_prefix, nj_tot + MB + 1); CS_ENSURE(S.h_top_x, n_top + 1);
-  CS_ENSURE(S.h_box_job0, nj_tot + 1); CS_ENSURE(S.h_box_njobs, nj_tot + 1); CS_ENSURE(S.h_ls_order, nj_tot + 1); CS_ENSURE(S.h_rp_maps, 3 * (size_t)MB * NF + 1);
-  S.rp_rounds.assign(MB, PipeSlot::RpRound{});
-  S.rp_box_frame.clear(); S.rp_box_index.clear();
+  CS_ENSURE(S.h_box_job0, nj_tot + 1); CS_ENSURE(S.h_box_njobs, nj_tot + 1); CS_ENSURE(S.h_ls_order, nj_tot + 1); CS_ENSURE(R.h_maps, 3 * (size_t)MB * NF + 1);
+  R.rounds.assign(MB, RpLean::Round{});
+  R.box_frame.clear(); R.box_index.clear();
   size_t ji = 0;
   long long n_lines = 0, slot_cap_max = 0, slots_all = 0, max_job_slots = 0;
   int vp_cap_max = 0;
   size_t nj_round_max = 0;
   for (int r = 0; r < MB; r++) {
-    PipeSlot::RpRound& Rr = S.rp_rounds[r];
+    RpLean::Round& Rr = R.rounds[r];
     Rr.j0 = ji; Rr.b0 = nb_tot;
     JobSpan at{0, 0};
-    int* box_of = S.h_rp_maps.p + (size_t)(3 * r) * NF; int* job0_of = box_of + NF; int* njobs_of = job0_of + NF;
+    int* box_of = R.h_maps.p + (size_t)(3 * r) * NF; int* job0_of = box_of + NF; int* njobs_of = job0_of + NF;
     for (int f = 0; f < NF; f++) {
       box_of[f] = -1; job0_of[f] = -1; njobs_of[f] = 0;
       const FrameIn& F = b->frames[f];
@@ -1501,12 +1368,12 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
       const int nrp = (int)cam_rp[f].size();
       box_of[f] = (int)(nb_tot - Rr.b0); job0_of[f] = (int)(ji - Rr.j0); njobs_of[f] = F.n_heights[bi];
       S.h_box_job0.p[nb_tot] = (int)(ji - Rr.j0); S.h_box_njobs.p[nb_tot++] = F.n_heights[bi];
-      S.rp_box_frame.push_back(f); S.rp_box_index.push_back(bi);
+      R.box_frame.push_back(f); R.box_index.push_back(bi);
       for (int k = 0; k < F.n_heights[bi]; k++) {
         cs::JobDesc jd;
         fill_job_geometry(jd, F, bi, k, (*C.rp_off)[f]);
         jd.frame = f; jd.T = nT; jd.RP = nrp;
-        jd.Y = S.h_rp_tab_count.p[(size_t)f * NT];            // list 0 (the raw pose) until rp_carry_kernel says otherwise
+        jd.Y = R.h_tab_count.p[(size_t)f * NT];            // list 0 (the raw pose) until rp_carry_kernel says otherwise
         jd.yaw_off = (int)(((size_t)f * NT) * YCAP);
         jd.top_off = tb;
         jd.line_off = (int)n_lines; n_lines += F.n_lines;
@@ -1529,67 +1396,65 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
   for (size_t j = 0; j < nj; j++) S.h_ls_order.p[j] = (int)j;
   C.tm->setup_host_ms += now_ms() - t0;
   C.tm->n_jobs += (long long)nj;
-  if (nj == 0) { S.in_flight = true; CS_HIP_TRY(hipEventRecord(S.done, st)); return CS_OK; }
+  if (nj == 0) return S.mark_in_flight(d, st);
   // ---- device buffers; the per-round arrays are sized for the largest round and reused from round to round (one stream: in order)
   SweepBuffers& B = S.sb;
-  int rc;
-  if ((rc = B.ensure_tables(nj, nj + MB + 1, (size_t)n_lines, n_yaw, n_top, (size_t)vp_cap_max, nb, KMAX)) || (rc = B.ensure_slots(slot_cap_max))) return rc;
+  CS_TRY(B.ensure_tables(nj, nj + MB + 1, (size_t)n_lines, n_yaw, n_top, (size_t)vp_cap_max, nb, KMAX)); CS_TRY(B.ensure_slots(slot_cap_max));
   CS_ENSURE(B.flag, slot_cap_max + 1); CS_ENSURE(B.bound3, nj_round_max * (size_t)cs::vp3_table_doubles_per_job() + 1);
   const int max_trips = (int)std::min<long long>((max_job_slots + 4095) / 4096, 1 << 20);      // compaction trips of the largest job (4096 slots each)
-  CS_ENSURE(S.rp_trip_cnt, (size_t)nj_round_max * (size_t)std::max(1, max_trips) + 1);
-  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2); CS_ENSURE(S.rp_last_slot, nb + 1);
+  CS_ENSURE(R.trip_cnt, (size_t)nj_round_max * (size_t)std::max(1, max_trips) + 1);
+  CS_ENSURE(S.ls_order, nj); CS_ENSURE(S.ls_crowded, 2 * (nj + 1) + 2); CS_ENSURE(R.last_slot, nb + 1);
   CS_ENSURE(S.records, nb * KMAX + 1); CS_ENSURE(S.h_records, nb * KMAX + 1);
-  S.rp_NT = NT; S.rp_YCAP = YCAP;
-  S.rp_pool_cap = std::max<long long>(1 << 18, slots_all / 64);        // columns of the flagged boxes (about one box in a hundred)
-  CS_ENSURE(B.fb_dist, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_angle, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_skew, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_flag, (size_t)S.rp_pool_cap + 1); CS_ENSURE(B.fb_slot, (size_t)S.rp_pool_cap + 1);
-  CS_ENSURE(S.rp_box_base, nb + 1); CS_ENSURE(S.rp_pool_used, 1); CS_ENSURE(S.h_rp_box_base, nb + 1); CS_ENSURE(S.h_rp_pool_used, 1); CS_ENSURE(S.h_rp_last_slot, nb + 1); CS_ENSURE(S.h_jobs_out, nj + 1);
-  CS_ENSURE(S.rp_cur_idx, (size_t)NF + 1); CS_ENSURE(S.rp_tab_count, (size_t)NF * NT + 1); CS_ENSURE(S.rp_maps, 3 * (size_t)MB * NF + 1); CS_ENSURE(S.rp_raw_euler, 3 * (size_t)NF + 1);
-  while (S.rp_ev.size() < 5 * (size_t)MB) { S.rp_ev.emplace_back(); if (int rc = S.rp_ev.back().create()) { S.rp_ev.pop_back(); return rc; } }
+  R.pool_cap = std::max<long long>(1 << 18, slots_all / 64);        // columns of the flagged boxes (about one box in a hundred)
+  CS_ENSURE(B.fb_dist, (size_t)R.pool_cap + 1); CS_ENSURE(B.fb_angle, (size_t)R.pool_cap + 1); CS_ENSURE(B.fb_skew, (size_t)R.pool_cap + 1); CS_ENSURE(B.fb_flag, (size_t)R.pool_cap + 1); CS_ENSURE(B.fb_slot, (size_t)R.pool_cap + 1);
+  CS_ENSURE(R.box_base, nb + 1); CS_ENSURE(R.pool_used, 1); CS_ENSURE(R.h_box_base, nb + 1); CS_ENSURE(R.h_pool_used, 1); CS_ENSURE(R.h_last_slot, nb + 1); CS_ENSURE(S.h_jobs_out, nj + 1);
+  CS_ENSURE(R.cur_idx, (size_t)NF + 1); CS_ENSURE(R.tab_count, (size_t)NF * NT + 1); CS_ENSURE(R.maps, 3 * (size_t)MB * NF + 1); CS_ENSURE(R.raw_euler, 3 * (size_t)NF + 1);
+  while (R.ev.size() < 5 * (size_t)MB) { R.ev.emplace_back(); if (int rc = R.ev.back().create()) { R.ev.pop_back(); return rc; } }
   std::unique_lock<std::mutex> enqueue(d->streams->enqueue_mu, std::defer_lock);      // all rounds of this batch back to back in the shared streams (see pipe_launch)
   if (!d->streams->own_streams) enqueue.lock();
   hipStream_t stB = nullptr, stC = nullptr;      // (corner construction stays on the chain here: stB is not used)
   sweep_side_streams(d, &stB, &stC);
-  CS_HIP_TRY(hipMemsetAsync(S.rp_pool_used.p, 0, sizeof(unsigned long long), st));
+  CS_HIP_TRY(hipMemsetAsync(R.pool_used.p, 0, sizeof(unsigned long long), st));
   {     // (one kernel reads all thirteen tables out of the pinned pools: multi_copy_kernel)
     cs::CopySegs cp{};
     cs::add_copy(cp, S.ls_order, S.h_ls_order, nj); cs::add_copy(cp, B.jobs, S.h_jobs_in, nj); cs::add_copy(cp, B.slot_prefix, S.h_slot_prefix, nj + MB);
     cs::add_copy(cp, B.vp_prefix, S.h_vp_prefix, nj + MB); cs::add_copy(cp, B.yaw, S.h_yaw, n_yaw); cs::add_copy(cp, B.yaw_c, S.h_yaw_c, n_yaw);
     cs::add_copy(cp, B.yaw_s, S.h_yaw_s, n_yaw); cs::add_copy(cp, B.top_x, S.h_top_x, n_top); cs::add_copy(cp, B.box_job0, S.h_box_job0, nb);
-    cs::add_copy(cp, B.box_njobs, S.h_box_njobs, nb); cs::add_copy(cp, S.rp_tab_count, S.h_rp_tab_count, (long long)NF * NT);
-    cs::add_copy(cp, S.rp_maps, S.h_rp_maps, 3LL * MB * NF); cs::add_copy(cp, S.rp_raw_euler, S.h_rp_raw_euler, 3LL * NF);
+    cs::add_copy(cp, B.box_njobs, S.h_box_njobs, nb); cs::add_copy(cp, R.tab_count, R.h_tab_count, (long long)NF * NT);
+    cs::add_copy(cp, R.maps, R.h_maps, 3LL * MB * NF); cs::add_copy(cp, R.raw_euler, R.h_raw_euler, 3LL * NF);
     cs::launch_multi_copy(cp, st);
   }
   CS_HIP_TRY(hipMemsetAsync(B.job_valid.p, 0, sizeof(int) * nj, st));
-  CS_HIP_TRY(hipMemsetAsync(S.rp_cur_idx.p, 0, sizeof(int) * NF, st));
+  CS_HIP_TRY(hipMemsetAsync(R.cur_idx.p, 0, sizeof(int) * NF, st));
   CS_HIP_TRY(hipEventRecord(S.ev[0], st));
   // ---- line setup of every job of the batch at once (it depends on the box and the frame's segments only)
   cs::launch_line_setup_listed(B.jobs.p, (int)nj, b->d_frame_lines.p, b->d_frame_line_ptr.p, B.mid_x.p, B.mid_y.p, B.ang.p, P.pre_merge_dist_thre, P.pre_merge_angle_thre, P.edge_length_threshold, st, S.ls_order.p,
                                stC, S.ev[0], S.ev[12], S.ls_crowded.p);
   CS_HIP_TRY(hipEventRecord(S.ev[1], st));
-  cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
+  const cs::RankParams rkp = rank_params(P, C.sp);
   for (int r = 0; r < MB; r++) {
-    const PipeSlot::RpRound& Rr = S.rp_rounds[r];
+    const RpLean::Round& Rr = R.rounds[r];
     if (Rr.nj == 0) continue;
-    const auto re = S.rp_ev.begin() + 5 * (size_t)r;
+    const auto re = R.ev.begin() + 5 * (size_t)r;
     cs::DetectDeviceView v;
     B.bind(v, *b, Rr.nj, Rr.j0, Rr.j0 + r);      // (the prefixes carry one closing entry per earlier round)
     if (r > 0) {      // the carried yaw: this round's jobs get the list the previous round's result selects
       // (the previous round WITH jobs decides for the frames it held a box of; a frame without a box there keeps its list)
       int rq = r - 1;
-      while (rq > 0 && S.rp_rounds[rq].nj == 0) rq--;
-      const PipeSlot::RpRound& Rq = S.rp_rounds[rq];
+      while (rq > 0 && R.rounds[rq].nj == 0) rq--;
+      const RpLean::Round& Rq = R.rounds[rq];
       cs::RpCarryView c{};
       c.n_frames = NF; c.NT = NT; c.YCAP = YCAP;
-      c.prev_box_of_frame = Rq.nj ? S.rp_maps.p + (size_t)(3 * rq) * NF : nullptr;
-      c.prev_last_slot = S.rp_last_slot.p + Rq.b0; c.prev_jobs = B.jobs.p + Rq.j0; c.prev_box_job0 = B.box_job0.p + Rq.b0; c.prev_box_njobs = B.box_njobs.p + Rq.b0;
-      c.job0_of_frame = S.rp_maps.p + (size_t)(3 * r + 1) * NF; c.njobs_of_frame = S.rp_maps.p + (size_t)(3 * r + 2) * NF;
-      c.tab_count = S.rp_tab_count.p; c.cur_idx = S.rp_cur_idx.p;
+      c.prev_box_of_frame = Rq.nj ? R.maps.p + (size_t)(3 * rq) * NF : nullptr;
+      c.prev_last_slot = R.last_slot.p + Rq.b0; c.prev_jobs = B.jobs.p + Rq.j0; c.prev_box_job0 = B.box_job0.p + Rq.b0; c.prev_box_njobs = B.box_njobs.p + Rq.b0;
+      c.job0_of_frame = R.maps.p + (size_t)(3 * r + 1) * NF; c.njobs_of_frame = R.maps.p + (size_t)(3 * r + 2) * NF;
+      c.tab_count = R.tab_count.p; c.cur_idx = R.cur_idx.p;
       cs::launch_rp_carry(c, B.jobs.p + Rr.j0, st);
     }
     CS_HIP_TRY(hipEventRecord(re[0], st));
     cs::launch_vp_points(v, Rr.vp_cap, st);
     cs::launch_candidates(v, C.sp, Rr.slot_cap, st);
-    cs::launch_scan_compact_trips(v, S.rp_trip_cnt.p, max_trips, st);
+    cs::launch_scan_compact_trips(v, R.trip_cnt.p, max_trips, st);
     CS_HIP_TRY(hipEventRecord(re[1], st));
     cs::launch_vp_support_only(v, C.sp, Rr.vp_cap, st);
     CS_HIP_TRY(hipEventRecord(re[2], st));
@@ -1597,13 +1462,13 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     CS_HIP_TRY(hipEventRecord(re[3], st));
     cs::RankView rv{};
     rv.box_job0 = B.box_job0.p + Rr.b0; rv.box_njobs = B.box_njobs.p + Rr.b0; rv.n_boxes = (int)Rr.nb; rv.winners = B.winners.p + Rr.b0 * KMAX;
-    rv.win_count = B.win_count.p + Rr.b0; rv.fallback = B.fallback.p + Rr.b0; rv.last_slot = S.rp_last_slot.p + Rr.b0;
+    rv.win_count = B.win_count.p + Rr.b0; rv.fallback = B.fallback.p + Rr.b0; rv.last_slot = R.last_slot.p + Rr.b0;
     cs::launch_rank(v, rv, rkp, st, Rr.nb ? (long long)(Rr.slot_cap / (long long)Rr.nb) : 0, false);      // (average slots per box of the round: which instance ranks)
-    cs::launch_records(v, rv, KMAX, S.records.p + Rr.b0 * KMAX, st, S.rp_raw_euler.p, rkp.short_sq_bound);
+    cs::launch_records(v, rv, KMAX, S.records.p + Rr.b0 * KMAX, st, R.raw_euler.p, rkp.short_sq_bound);
     {   // the flagged boxes' columns, before the next round reuses the arrays
       cs::RpSaveView sv{};
-      sv.fallback = rv.fallback; sv.box_job0 = rv.box_job0; sv.box_njobs = rv.box_njobs; sv.n_boxes = rv.n_boxes; sv.pool_used = S.rp_pool_used.p; sv.pool_cap = S.rp_pool_cap;
-      sv.box_base = S.rp_box_base.p + Rr.b0; sv.p_dist = B.fb_dist.p; sv.p_angle = B.fb_angle.p; sv.p_skew = B.fb_skew.p; sv.p_flag = B.fb_flag.p; sv.p_slot = B.fb_slot.p;
+      sv.fallback = rv.fallback; sv.box_job0 = rv.box_job0; sv.box_njobs = rv.box_njobs; sv.n_boxes = rv.n_boxes; sv.pool_used = R.pool_used.p; sv.pool_cap = R.pool_cap;
+      sv.box_base = R.box_base.p + Rr.b0; sv.p_dist = B.fb_dist.p; sv.p_angle = B.fb_angle.p; sv.p_skew = B.fb_skew.p; sv.p_flag = B.fb_flag.p; sv.p_slot = B.fb_slot.p;
       cs::launch_rp_save_fallback(v, sv, st);
     }
     CS_HIP_TRY(hipEventRecord(re[4], st));
@@ -1614,12 +1479,32 @@ int rp_launch(PipeCtx& C, PipeSlot& S, const std::vector<std::vector<CamCache>>&
     cs::CopySegs cp{};
     cs::add_copy(cp, S.h_records, S.records, nb * KMAX); cs::add_copy(cp, B.h_win_count, B.win_count, nb); cs::add_copy(cp, B.h_fallback, B.fallback, nb);
     cs::add_copy(cp, B.h_job_cbase, B.job_cbase, nj + MB); cs::add_copy(cp, B.h_job_valid, B.job_valid, nj); cs::add_copy(cp, S.h_jobs_out, B.jobs, nj);
-    cs::add_copy(cp, S.h_rp_last_slot, S.rp_last_slot, nb); cs::add_copy(cp, S.h_rp_box_base, S.rp_box_base, nb); cs::add_copy(cp, S.h_rp_pool_used, S.rp_pool_used, 1);
+    cs::add_copy(cp, R.h_last_slot, R.last_slot, nb); cs::add_copy(cp, R.h_box_base, R.box_base, nb); cs::add_copy(cp, R.h_pool_used, R.pool_used, 1);
     cs::launch_multi_copy(cp, st);
   }
-  CS_HIP_TRY(hipEventRecord(S.done, st));
-  S.in_flight = true;
-  S.counted_busy = true; d->busy.fetch_add(1); d->streams->busy.fetch_add(1);
+  return S.mark_in_flight(d, st);
+}
+
+// The lean roll/pitch path's redo: frames `ids` of C's batch again, as a small batch through the round-by-round path (force_round_path) that
+// reads the parent's map pool at the same offsets; its records and counts go to the parent's output.
+int rp_redo_frames(PipeCtx& C, const std::vector<int>& ids) {
+  cs_detector* d = C.d; const cs_batch* b = C.b;
+  cs_batch sub;
+  sub.det = d; sub.force_round_path = true; sub.maps = b->maps; sub.n_frames = (int)ids.size();
+  for (int f : ids) { sub.frames.push_back(b->frames[f]); sub.max_boxes = std::max(sub.max_boxes, b->frames[f].n_boxes); }
+  CS_TRY(batch_layout(d, &sub));
+  std::vector<cs_cuboid> o2(ids.size() * std::max(1, sub.max_boxes) * C.O.kmax);
+  std::vector<int> c2(ids.size() * std::max(1, sub.max_boxes), 0);
+  const OutView O2{o2.data(), c2.data(), sub.max_boxes, C.O.kmax};
+  CS_TRY(batch_run_impl(d, &sub, O2.out, O2.out_counts, false));
+  for (size_t z = 0; z < ids.size(); z++) {
+    const int f = ids[z];
+    for (int bi = 0; bi < b->frames[f].n_boxes; bi++) {
+      const int nw = O2.count((int)z, bi);
+      C.O.count(f, bi) = nw;
+      for (int r = 0; r < nw; r++) C.O.rec(f, bi, r) = O2.rec((int)z, bi, r);
+    }
+  }
   return CS_OK;
 }
 
@@ -1628,27 +1513,23 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   const cs_detect_params& P = d->prm;
   const int KMAX = P.max_cuboid_num, MB = b->max_boxes, NF = b->n_frames;
   cs_detect_timing& tm = *C.tm;
-  double tw = now_ms();
-  if (S.counted_busy) { S.counted_busy = false; d->busy.fetch_sub(1); d->streams->busy.fetch_sub(1); }      // (before the wait: an error return must not leave the counts up)
-  CS_HIP_TRY(hipEventSynchronize(S.done));
-  tm.d2h_ms += now_ms() - tw;
-  S.in_flight = false;
+  CS_TRY(S.wait(d, tm));
   if (S.nj == 0) return CS_OK;
+  RpLean& R = *b->rp;
   double t0 = now_ms();
   {
-    float ms = 0;
-    CS_HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1])); tm.line_setup_ms += ms;
+    CS_TRY(add_elapsed(tm.line_setup_ms, S.ev[0], S.ev[1]));
     for (int r = 0; r < MB; r++) {
-      if (S.rp_rounds[r].nj == 0) continue;
-      const auto re = S.rp_ev.begin() + 5 * (size_t)r;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, re[0], re[1])); tm.cand_kernel_ms += ms;      // vanishing points, corners, compaction
-      CS_HIP_TRY(hipEventElapsedTime(&ms, re[1], re[2])); tm.vp_kernel_ms += ms;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, re[2], re[3])); tm.score_kernel_ms += ms;
-      CS_HIP_TRY(hipEventElapsedTime(&ms, re[3], re[4])); tm.rank_kernel_ms += ms;      // ranking, records, the flagged boxes' columns
+      if (R.rounds[r].nj == 0) continue;
+      const auto re = R.ev.begin() + 5 * (size_t)r;
+      CS_TRY(add_elapsed(tm.cand_kernel_ms, re[0], re[1]));      // vanishing points, corners, compaction
+      CS_TRY(add_elapsed(tm.vp_kernel_ms, re[1], re[2]));
+      CS_TRY(add_elapsed(tm.score_kernel_ms, re[2], re[3]));
+      CS_TRY(add_elapsed(tm.rank_kernel_ms, re[3], re[4]));      // ranking, records, the flagged boxes' columns
       tm.cand_kernel_launches += 1;
     }
     tm.n_slots += S.slot_total;
-    for (int r = 0; r < MB; r++) if (S.rp_rounds[r].nj) tm.n_valid += S.sb.h_job_cbase.p[S.rp_rounds[r].j0 + r + S.rp_rounds[r].nj];
+    for (int r = 0; r < MB; r++) if (R.rounds[r].nj) tm.n_valid += S.sb.h_job_cbase.p[R.rounds[r].j0 + r + R.rounds[r].nj];
   }
   // ---- the flagged boxes: exact ranking on the host from their saved columns.  A frame is only redone when the exact ranking
   // carries a different camera yaw to the frame's next box than the device assumed (or the columns did not fit the pool).
@@ -1660,7 +1541,7 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   tm.n_fallback_boxes += (int)n_fb;
   if (n_fb) {
     hipStream_t st2 = d->stream_hi;
-    const size_t used = (size_t)std::min<unsigned long long>(*S.h_rp_pool_used.p, (unsigned long long)S.rp_pool_cap);
+    const size_t used = (size_t)std::min<unsigned long long>(*R.h_pool_used.p, (unsigned long long)R.pool_cap);
     CS_ENSURE(S.sb.h_fb_dist, used + 1); CS_ENSURE(S.sb.h_fb_angle, used + 1); CS_ENSURE(S.sb.h_fb_skew, used + 1); CS_ENSURE(S.sb.h_fb_flag, used + 1); CS_ENSURE(S.sb.h_fb_slot, used + 1);
     if (used) {
       cs::CopySegs cp{};
@@ -1672,9 +1553,9 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
     const std::vector<std::vector<CamCache>>& cam_rp = *C.cam_rp_all;
     // boxes of a frame in round order
     std::vector<std::vector<size_t>> boxes_of(NF);
-    for (size_t q = 0; q < S.nb; q++) boxes_of[S.rp_box_frame[q]].push_back(q);
+    for (size_t q = 0; q < S.nb; q++) boxes_of[R.box_frame[q]].push_back(q);
     auto carry_idx = [](const cs::JobDesc& jl, long long last) { return last < 0 ? jl.RP : 1 + decode_slot(jl, last).rp; };
-    const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
+    const RankWeights RW = rank_weights(P);
     std::vector<int> fb_frames;
     for (int f = 0; f < NF; f++) { bool any = false; for (size_t q : boxes_of[f]) any = any || S.sb.h_fallback.p[q]; if (any) fb_frames.push_back(f); }
     d->pool->run((int)fb_frames.size(), [&](int z) {
@@ -1683,14 +1564,14 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
       for (size_t bq = 0; bq < boxes_of[f].size(); bq++) {
         const size_t q = boxes_of[f][bq];
         if (!S.sb.h_fallback.p[q]) continue;
-        const long long base = S.h_rp_box_base.p[q];
+        const long long base = R.h_box_base.p[q];
         if (base < 0) { redo[f] = 1; return; }
         // which round the box belongs to: its jobs are relative to that round's first job
         size_t r = 0;
-        while (r + 1 < S.rp_rounds.size() && q >= S.rp_rounds[r + 1].b0) r++;
-        const cs::JobDesc* jobs = S.h_jobs_out.p + S.rp_rounds[r].j0;
-        const int* jvalid = S.sb.h_job_valid.p + S.rp_rounds[r].j0;
-        const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q], bi = S.rp_box_index[q];
+        while (r + 1 < R.rounds.size() && q >= R.rounds[r + 1].b0) r++;
+        const cs::JobDesc* jobs = S.h_jobs_out.p + R.rounds[r].j0;
+        const int* jvalid = S.sb.h_job_valid.p + R.rounds[r].j0;
+        const int j0 = S.h_box_job0.p[q], nh = S.h_box_njobs.p[q];
         HeightCols cols[3];
         long long run = base;
         for (int h = 0; h < nh; h++) {
@@ -1699,34 +1580,15 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
         }
         std::vector<ExactWinner> wl;
         const long long exact_last = exact_rank_box(cols, nh, RW, KMAX, wl);
-        const int kk = (int)wl.size();
-        for (int w = 0; w < kk; w++) {
-          const cs::JobDesc& jd = jobs[j0 + wl[w].h];
-          const SlotRef s = decode_slot(jd, wl[w].slot);
-          // the winner's corners: the vanishing points (vp_points_kernel's arithmetic) and build_corners, on the host
-          const double* A = cam_rp[f][s.rp].pose.KinvR;
-          const double cy = S.h_yaw_c.p[jd.yaw_off + s.y], sy = S.h_yaw_s.p[jd.yaw_off + s.y];
-          const double dd[3][3] = {{cy, sy, 0.0}, {-sy, cy, 0.0}, {0.0, 0.0, 1.0}};
-          cs::V2 vp[3];
-          for (int k = 0; k < 3; k++) {
-            const double h0 = (A[0] * dd[k][0] + A[1] * dd[k][1]) + A[2] * dd[k][2];
-            const double h1 = (A[3] * dd[k][0] + A[4] * dd[k][1]) + A[5] * dd[k][2];
-            const double h2 = (A[6] * dd[k][0] + A[7] * dd[k][1]) + A[8] * dd[k][2];
-            vp[k] = cs::v2(h0 / h2, h1 / h2);
-          }
-          cs::V2 c8[8];
-          for (auto& c : c8) c = cs::v2(0.0, 0.0);
-          (void)cs::build_corners(jd.g, vp[0], vp[1], vp[2], (double)S.h_top_x.p[jd.top_off + s.t], s.cfg, C.sp.short_sq_bound, c8);
-          double c16[16];
-          for (int k = 0; k < 8; k++) { c16[k] = c8[k].x; c16[8 + k] = c8[k].y; }
-          write_winner_record(F, jd, s, wl[w].flag, wl[w].dist, wl[w].angle, S.h_yaw.p[jd.yaw_off + s.y], cam_rp[f][s.rp].pose, c16, (*C.cam_raw)[f].euler, true, wl[w].score,
-                              C.out[((size_t)f * MB + bi) * KMAX + w]);
-        }
-        C.out_counts[(size_t)f * MB + bi] = kk;
+        double c16[16];      // the winner's corners, rebuilt on the host
+        write_exact_winners(C.O, F, jobs + j0, wl, S.h_yaw.p, cam_rp[f], (*C.cam_raw)[f].euler, true, [&](size_t, const cs::JobDesc& jd, const SlotRef& s) {
+          host_corners16(cam_rp[f][s.rp].pose.KinvR, S.h_yaw_c.p[jd.yaw_off + s.y], S.h_yaw_s.p[jd.yaw_off + s.y], jd, s, (double)S.h_top_x.p[jd.top_off + s.t], C.sp.short_sq_bound, c16);
+          return (const double*)c16;
+        });
         host_done[q] = 1;
         // does the frame's next box start from the yaw the device assumed?
         const cs::JobDesc& jl = jobs[j0 + nh - 1];
-        if (bq + 1 < boxes_of[f].size() && carry_idx(jl, exact_last) != carry_idx(jl, S.h_rp_last_slot.p[q])) { redo[f] = 1; return; }
+        if (bq + 1 < boxes_of[f].size() && carry_idx(jl, exact_last) != carry_idx(jl, R.h_last_slot.p[q])) { redo[f] = 1; return; }
       }
     });
     for (int f = 0; f < NF; f++) n_redo += redo[f] ? 1 : 0;
@@ -1735,41 +1597,15 @@ int rp_finish(PipeCtx& C, PipeSlot& S) {
   const int nch = ((int)S.nb + RCH - 1) / RCH;
   d->pool->run(nch, [&](int z) {
     for (size_t q = (size_t)z * RCH, q1 = std::min(S.nb, q + RCH); q < q1; q++) {
-      const int f = S.rp_box_frame[q], bi = S.rp_box_index[q];
+      const int f = R.box_frame[q], bi = R.box_index[q];
       if (redo[f] || host_done[q]) continue;
-      const int nw = S.sb.h_win_count.p[q];
-      for (int r = 0; r < nw; r++) copy_device_record(b->frames[f], bi, S.h_records.p[q * KMAX + r], C.out[((size_t)f * MB + bi) * KMAX + r]);
-      C.out_counts[(size_t)f * MB + bi] = nw;
+      write_device_records(C.O, b->frames[f], f, bi, S.h_records.p + q * KMAX, S.sb.h_win_count.p[q]);
     }
   });
   if (n_redo) {
-    // a small batch of those frames, sharing this batch's map pool (same offsets), through the round-by-round path
-    cs_batch sub;
-    sub.det = d;
-    sub.force_round_path = true;
     std::vector<int> ids;
     for (int f = 0; f < NF; f++) if (redo[f]) ids.push_back(f);
-    sub.n_frames = (int)ids.size();
-    sub.frames.resize(ids.size());
-    sub.max_boxes = 0;
-    for (size_t z = 0; z < ids.size(); z++) { sub.frames[z] = b->frames[ids[z]]; sub.max_boxes = std::max(sub.max_boxes, sub.frames[z].n_boxes); }
-    sub.d_maps.p = b->d_maps.p; sub.d_maps.cap = b->d_maps.cap;           // borrowed
-    struct Unborrow { cs_batch* s; ~Unborrow() { s->d_maps.p = nullptr; s->d_maps.cap = 0; } } ub{&sub};      // (destroyed before `sub`)
-    int rc = batch_layout(d, &sub);
-    if (rc) return rc;
-    const int MBs = sub.max_boxes;
-    std::vector<cs_cuboid> o2((size_t)ids.size() * std::max(1, MBs) * KMAX);
-    std::vector<int> c2((size_t)ids.size() * std::max(1, MBs), 0);
-    rc = batch_run_impl(d, &sub, o2.data(), c2.data(), false);
-    if (rc) return rc;
-    for (size_t z = 0; z < ids.size(); z++) {
-      const int f = ids[z];
-      for (int bi = 0; bi < b->frames[f].n_boxes; bi++) {
-        const int nw = c2[z * MBs + bi];
-        for (int r = 0; r < nw; r++) C.out[((size_t)f * MB + bi) * KMAX + r] = o2[(z * MBs + bi) * KMAX + r];
-        C.out_counts[(size_t)f * MB + bi] = nw;
-      }
-    }
+    CS_TRY(rp_redo_frames(C, ids));
     tm.n_redo_frames += n_redo;
   }
   tm.finalize_ms += now_ms() - t0;
@@ -1784,7 +1620,6 @@ extern "C" int cs_batch_set_pipeline_chunks(cs_batch* b, int n_chunks) {
   return CS_OK;
 }
 
-static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_counts, bool defer);
 static int batch_collect_impl(cs_detector* d, cs_batch* b);
 extern "C" int cs_batch_run(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_counts) {
   CS_GUARD_BEGIN
@@ -1807,25 +1642,23 @@ extern "C" int cs_batch_collect(cs_detector* d, cs_batch* b) {
 }
 static void batch_drop_run_state(cs_batch* b) { delete b->run_state; b->run_state = nullptr; }
 // CS_DETECT_PROF: the host phase clock of the lean path, every eighth run
-static void prof_report(double total_ms) {
-  if (!g_prof || (++g_runs % 8) != 0) return;
+static void prof_report(cs_detector* d, double total_ms) {
+  if (!d->prof || (++d->prof_runs % 8) != 0) return;
   const char* nm[11] = {"jobs+samples", "prefix+pack", nullptr, "alloc+enqueue", "gpu wait", "tie lists", "records", "tie wait", "tie rank", "tie corners", "tie records"};
   fprintf(stderr, "[detect] host ms/run:");
-  for (int k = 0; k < 11; k++) { if (nm[k]) fprintf(stderr, " %s %.3f", nm[k], g_mark[k] / 8); g_mark[k] = 0; }
-  fprintf(stderr, " | pre %.3f total %.3f\n", g_mark[11] / 8, total_ms); g_mark[11] = 0;
+  for (int k = 0; k < 11; k++) { if (nm[k]) fprintf(stderr, " %s %.3f", nm[k], d->prof_mark[k] / 8); d->prof_mark[k] = 0; }
+  fprintf(stderr, " | pre %.3f total %.3f\n", d->prof_mark[11] / 8, total_ms); d->prof_mark[11] = 0;
 }
 static int batch_collect_impl(cs_detector* d, cs_batch* b) {
   if (!b->run_state) return CS_OK;                        // nothing outstanding (or the sweep ran to completion inside submit)
   std::unique_ptr<BatchRunState> rs(b->run_state);
   b->run_state = nullptr;
-  if (!rs->deferred) return CS_OK;
   CS_HIP_TRY(hipSetDevice(d->device));
-  int rc = rs->rp_lean ? rp_finish(rs->C, b->pipe[0]) : pipe_finish(rs->C, b->pipe[0], rs->cam_rp);
-  if (rc) return rc;
+  CS_TRY(rs->rp_lean ? rp_finish(rs->C, b->pipe[0]) : pipe_finish(rs->C, b->pipe[0], rs->cam_rp));
   rs->tm.total_ms = now_ms() - rs->t_begin;
   b->timing = rs->tm;
   b->ran = true;
-  prof_report(rs->tm.total_ms);
+  prof_report(d, rs->tm.total_ms);
   return CS_OK;
 }
 
@@ -1839,22 +1672,8 @@ static int build_camera_caches(cs_detector* d, cs_batch* b, BatchRunState* rs, b
   d->pool->run(NF, [&](int f) {
     const FrameIn& F = b->frames[f];
     make_cam(F.K, F.R, F.t, cam_raw[f]);
-    if (sample_rp) {
-      std::vector<double> rolls, pitches;
-      linespace<double>(cam_raw[f].euler[0] - 6.0 / 180.0 * CS_PI, cam_raw[f].euler[0] + 6.0 / 180.0 * CS_PI, 3.0 / 180.0 * CS_PI, rolls);
-      linespace<double>(cam_raw[f].euler[1] - 6.0 / 180.0 * CS_PI, cam_raw[f].euler[1] + 6.0 / 180.0 * CS_PI, 3.0 / 180.0 * CS_PI, pitches);
-      for (double r : rolls)
-        for (double p : pitches) {
-          double Rn[9];
-          euler_to_rot(r, p, cam_raw[f].euler[2], Rn);
-          CamCache c;
-          make_cam(F.K, Rn, F.t, c);
-          c.pose.roll = r; c.pose.pitch = p;  // the row stores the *sample* angles (:686)
-          cam_rp[f].push_back(c);
-        }
-    } else {
-      cam_rp[f].push_back(cam_raw[f]);
-    }
+    if (sample_rp) sample_rp_poses(F.K, F.t, cam_raw[f], cam_rp[f]);
+    else cam_rp[f].push_back(cam_raw[f]);
   });
   std::vector<int>& rp_off = rs->rp_off; rp_off.assign(NF + 1, 0);
   for (int f = 0; f < NF; f++) rp_off[f + 1] = rp_off[f] + (int)cam_rp[f].size();
@@ -1906,14 +1725,11 @@ void carry_yaw(RoundRun& X, const cs::JobDesc& jl, long long last_slot) {
   X.cur_yaw[jl.frame] = last_slot < 0 ? rp.back().cam_yaw : rp[(size_t)decode_slot(jl, last_slot).rp].cam_yaw;
 }
 
-// the record of winner `rank` of job jd's box
-void round_write_winner(const RoundRun& X, const RoundTables& T, const cs::JobDesc& jd, long long slot, int flag, double dist_err, double angle_err, double normalized_error,
-                        const double* corners16, int rank) {
+// the exact winners wl of the box whose jobs start at `jobs`, their corners one after the other from corners16
+void round_write_exact(const RoundRun& X, const RoundTables& T, const cs::JobDesc* jobs, const std::vector<ExactWinner>& wl, const double* corners16) {
   const PipeCtx& C = X.C;
-  const int f = jd.frame;
-  const SlotRef s = decode_slot(jd, slot);
-  write_winner_record(C.b->frames[f], jd, s, flag, dist_err, angle_err, T.yaw[jd.yaw_off + s.y], (*C.cam_rp_all)[f][s.rp].pose, corners16, (*C.cam_raw)[f].euler, X.sample_rp,
-                      normalized_error, C.out[((size_t)f * C.b->max_boxes + jd.box) * C.d->prm.max_cuboid_num + rank]);
+  const int f = jobs[0].frame;
+  write_exact_winners(C.O, C.b->frames[f], jobs, wl, T.yaw.data(), (*C.cam_rp_all)[f], (*C.cam_raw)[f].euler, X.sample_rp, corners_at(corners16));
 }
 
 // ---- setup (host): the round's jobs per frame, then packed into pooled tables
@@ -1951,7 +1767,7 @@ int round_setup(RoundRun& X, int round, RoundTables& T) {
         fill_job_geometry(jd, F, bi, k, rp_off[f]);
         jd.frame = f; jd.Y = nY; jd.T = (int)tops.size(); jd.RP = (int)cam_rp[f].size();
         JobHost jh;
-        jh.frame = f; jh.box = bi; jh.hid = k; jh.yaw_off_local = yoff; jh.tops = tops;
+        jh.yaw_off_local = yoff; jh.tops = tops;
         // ROI line filter (:271-283) + merge (:288-296) + angles/midpoints (:309-315): the line setup kernels, or here
         if (dev_setup) { jd.m = 0; jh.line_cap = F.n_lines; R.jobs.push_back(jd); R.jh.push_back(std::move(jh)); continue; }
         std::vector<double> in;
@@ -2037,8 +1853,7 @@ int round_upload(RoundRun& X, RoundTables& T) {
   hipStream_t st = X.C.d->stream;
   const double t0 = now_ms();
   const size_t nj = T.nj;
-  int rc;
-  if ((rc = B.ensure_tables(nj, nj + 1, T.n_lines, T.yaw.size(), T.top_x.size(), (size_t)T.vp_total, T.box_job0.size(), X.C.d->prm.max_cuboid_num))) return rc;
+  CS_TRY(B.ensure_tables(nj, nj + 1, T.n_lines, T.yaw.size(), T.top_x.size(), (size_t)T.vp_total, T.box_job0.size(), X.C.d->prm.max_cuboid_num));
   CS_ENSURE(B.flag, T.slot_total + 1);
   struct Tab { void* dst; const void* src; size_t bytes; };
   auto tab = [](auto& dst, const auto& vec) { return Tab{dst.p, vec.data(), sizeof(vec[0]) * vec.size()}; };
@@ -2108,13 +1923,12 @@ int round_compact_score(RoundRun& X, RoundTables& T, long long rows) {
 // the VP support table once per (job, rp, yaw) + per valid proposal 12 B read (slot id, flag) and 28 B of scores written.
 // ranked: the round was ranked on the device (events 4 -> 5).
 int account_sweep(cs_detector* d, cs_detect_timing& tm, const RoundTables& T, long long n_valid, bool ranked) {
-  float ms = 0;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1])); tm.vp_kernel_ms += ms;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[1], d->ev[2])); tm.cand_kernel_ms += ms;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[3], d->ev[8])); tm.compact_ms += ms;
-  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[8], d->ev[4])); tm.score_kernel_ms += ms;
-  if (ranked) { CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[4], d->ev[5])); tm.rank_kernel_ms += ms; }
-  CS_HIP_TRY(hipEventElapsedTime(&ms, d->ev[6], d->ev[7])); tm.line_setup_ms += ms;
+  CS_TRY(add_elapsed(tm.vp_kernel_ms, d->ev[0], d->ev[1]));
+  CS_TRY(add_elapsed(tm.cand_kernel_ms, d->ev[1], d->ev[2]));
+  CS_TRY(add_elapsed(tm.compact_ms, d->ev[3], d->ev[8]));
+  CS_TRY(add_elapsed(tm.score_kernel_ms, d->ev[8], d->ev[4]));
+  if (ranked) { CS_TRY(add_elapsed(tm.rank_kernel_ms, d->ev[4], d->ev[5])); }
+  CS_TRY(add_elapsed(tm.line_setup_ms, d->ev[6], d->ev[7]));
   tm.cand_kernel_launches += 1;
   tm.cand_kernel_bytes += 48LL * T.vp_total + 4LL * T.slot_total;
   long long sbytes = 96LL * T.vp_total + (28LL + 8LL + 4LL) * n_valid;
@@ -2130,19 +1944,17 @@ int round_rank_device(RoundRun& X, RoundTables& T) {
   cs_detector* d = C.d; cs_batch* b = C.b;
   SweepBuffers& B = b->round;
   const cs_detect_params& P = d->prm;
-  const int KMAX = P.max_cuboid_num, MB = b->max_boxes;
+  const int KMAX = P.max_cuboid_num;
   hipStream_t st = d->stream;
   cs_detect_timing& tm = *C.tm;
   const cs::DetectDeviceView& v = T.v;
   const size_t nj = T.nj, nb = T.box_job0.size();
-  int rc;
-  if ((rc = round_compact_score(X, T, T.slot_total))) return rc;   // the exact number of valid proposals stays on the device
+  CS_TRY(round_compact_score(X, T, T.slot_total));   // the exact number of valid proposals stays on the device
   CS_ENSURE(b->h_winners, nb * KMAX);
   cs::RankView rv{};
   rv.box_job0 = B.box_job0.p; rv.box_njobs = B.box_njobs.p; rv.n_boxes = (int)nb; rv.winners = B.winners.p; rv.win_count = B.win_count.p; rv.fallback = B.fallback.p;
   if (X.sample_rp) { CS_ENSURE(b->d_last_slot, nb); CS_ENSURE(b->h_last_slot, nb); rv.last_slot = b->d_last_slot.p; }
-  cs::RankParams rkp{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, KMAX, C.sp.short_sq_bound};
-  cs::launch_rank(v, rv, rkp, st);
+  cs::launch_rank(v, rv, rank_params(P, C.sp), st);
   CS_HIP_TRY(hipEventRecord(d->ev[5], st));
   CS_HIP_TRY(hipGetLastError());
   double t0 = now_ms();
@@ -2157,17 +1969,18 @@ int round_rank_device(RoundRun& X, RoundTables& T) {
   if (X.dev_setup) for (size_t j = 0; j < nj; j++) T.jobs[j].m = b->h_jobs.p[j].m;
   const long long n_valid = B.h_job_cbase.p[nj];
   tm.n_valid += n_valid;
-  if ((rc = account_sweep(d, tm, T, n_valid, true))) return rc;
+  CS_TRY(account_sweep(d, tm, T, n_valid, true));
   t0 = now_ms();
   // the flagged boxes' columns come in one gather (this path has nothing to do meanwhile: it waits at once)
   TiePass tie(B, v, st, T.box_job0.data(), T.box_njobs.data(), nj, nb);
-  if ((rc = tie.enqueue_columns()) || (rc = tie.wait())) return rc;
+  CS_TRY(tie.enqueue_columns()); CS_TRY(tie.wait());
   tm.n_fallback_boxes += (int)tie.boxes.size();
   // the boxes the device ranked: their records; the flagged ones: the exact ranking only (their corners are fetched below, in one gather)
-  const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
+  const RankWeights RW = rank_weights(P);
   d->pool->run((int)nb, [&](int q) {
     const int j0 = T.box_job0[q], nh = T.box_njobs[q];
     const cs::JobDesc* jobs = &T.jobs[j0];
+    const int f = jobs[0].frame, bi = jobs[0].box;
     if (B.h_fallback.p[q]) {
       const long long last = tie.rank((size_t)q, RW, KMAX);
       if (X.sample_rp) carry_yaw(X, jobs[nh - 1], last);
@@ -2175,24 +1988,22 @@ int round_rank_device(RoundRun& X, RoundTables& T) {
     }
     if (X.sample_rp) carry_yaw(X, jobs[nh - 1], b->h_last_slot.p[q]);
     const int nw = B.h_win_count.p[q];
+    const cs::RankWinner* wq = b->h_winners.p + (size_t)q * KMAX;      // the box's winners as the device ranked them
     for (int r = 0; r < nw; r++) {
-      const cs::RankWinner& w = b->h_winners.p[q * KMAX + r];
+      const cs::RankWinner& w = wq[r];
       int h = 0;
       while (h + 1 < nh && w.slot >= jobs[h + 1].slot_off) h++;
-      round_write_winner(X, T, jobs[h], w.slot, w.flag, w.dist_err, w.angle_err, w.normalized_error, w.corners, r);
+      const cs::JobDesc& jd = jobs[h];
+      const SlotRef s = decode_slot(jd, w.slot);
+      write_winner_record(b->frames[f], jd, s, w.flag, w.dist_err, w.angle_err, T.yaw[jd.yaw_off + s.y], (*C.cam_rp_all)[f][s.rp].pose, w.corners, (*C.cam_raw)[f].euler, X.sample_rp,
+                          w.normalized_error, C.O.rec(f, bi, r));
     }
-    C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = nw;
+    C.O.count(f, bi) = nw;
   });
-  if ((rc = tie.enqueue_corners(C.sp)) || (rc = tie.wait())) return rc;
+  CS_TRY(tie.enqueue_corners(C.sp)); CS_TRY(tie.wait());
   d->pool->run((int)tie.boxes.size(), [&](int z) {
     const size_t q = (size_t)tie.boxes[z];
-    const cs::JobDesc* jobs = &T.jobs[T.box_job0[q]];
-    const int nw = (int)tie.winners[q].size();
-    for (int r = 0; r < nw; r++) {
-      const ExactWinner& w = tie.winners[q][r];
-      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, tie.corners(q, r), r);
-    }
-    C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = nw;
+    round_write_exact(X, T, &T.jobs[T.box_job0[q]], tie.winners[q], tie.corners(q, 0));
   });
   tm.finalize_ms += now_ms() - t0;
   return CS_OK;
@@ -2209,7 +2020,6 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   cs_detect_timing& tm = *C.tm;
   const std::vector<std::vector<CamCache>>& cam_rp = *C.cam_rp_all;
   const size_t nj = T.nj, nb = T.box_job0.size();
-  int rc;
   // valid counts -> host -> size the compact arrays
   CS_HIP_TRY(hipMemcpyAsync(B.h_job_valid.p, B.job_valid.p, sizeof(int) * nj, hipMemcpyDeviceToHost, st));
   CS_HIP_TRY(hipStreamSynchronize(st));
@@ -2218,7 +2028,7 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   for (size_t j = 0; j < nj; j++) { B.h_job_cbase.p[j] = n_valid; n_valid += B.h_job_valid.p[j]; }
   B.h_job_cbase.p[nj] = n_valid;
   tm.n_valid += n_valid;
-  if ((rc = round_compact_score(X, T, n_valid))) return rc;
+  CS_TRY(round_compact_score(X, T, n_valid));
   CS_HIP_TRY(hipGetLastError());
   CS_ENSURE(b->h_c_slot, n_valid + 1); CS_ENSURE(b->h_c_flag, n_valid + 1); CS_ENSURE(b->h_c_dist, n_valid + 1); CS_ENSURE(b->h_c_angle, n_valid + 1); CS_ENSURE(b->h_c_skew, n_valid + 1);
   double t0 = now_ms();
@@ -2231,7 +2041,7 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   }
   CS_HIP_TRY(hipStreamSynchronize(st));
   tm.d2h_ms += now_ms() - t0;
-  if ((rc = account_sweep(d, tm, T, n_valid, false))) return rc;
+  CS_TRY(account_sweep(d, tm, T, n_valid, false));
 
   // per job: the candidate rows and fuse_normalize_scores_v2, retained
   t0 = now_ms();
@@ -2240,7 +2050,6 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   d->pool->run((int)nj, [&](int j) {
     const cs::JobDesc& jd = T.jobs[j];
     JobResult& R = b->results[res_base + j];
-    R.frame = jd.frame; R.box = jd.box; R.hid = jd.hid;
     const long long c0 = B.h_job_cbase.p[j];
     const int V = B.h_job_valid.p[j];
     R.n_valid = V;
@@ -2255,7 +2064,7 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   });
   for (size_t j = 0; j < nj; j++) b->job_index[((size_t)T.jobs[j].frame * MB + T.jobs[j].box) * 3 + T.jobs[j].hid] = (int)(res_base + j);
   // per box: proposals over its height samples (in order), final ranking (:804-838)
-  const RankWeights RW{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew};
+  const RankWeights RW = rank_weights(P);
   std::vector<std::vector<ExactWinner>> win_per_box(nb);
   d->pool->run((int)nb, [&](int q) {
     const int j0 = T.box_job0[q], nh = T.box_njobs[q];
@@ -2286,12 +2095,8 @@ int round_rank_host(RoundRun& X, RoundTables& T) {
   }
   size_t i = 0;
   for (size_t q = 0; q < nb; q++) {
-    const cs::JobDesc* jobs = &T.jobs[T.box_job0[q]];
-    for (size_t r = 0; r < win_per_box[q].size(); r++, i++) {
-      const ExactWinner& w = win_per_box[q][r];
-      round_write_winner(X, T, jobs[w.h], w.slot, w.flag, w.dist, w.angle, w.score, B.h_win_corners.p + 16 * i, (int)r);
-    }
-    C.out_counts[(size_t)jobs[0].frame * MB + jobs[0].box] = (int)win_per_box[q].size();
+    round_write_exact(X, T, &T.jobs[T.box_job0[q]], win_per_box[q], B.h_win_corners.p + 16 * i);
+    i += win_per_box[q].size();
   }
   if (b->debug) {
     for (size_t j = 0; j < nj; j++) {
@@ -2331,32 +2136,30 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
   sp.short_sq_bound = cs::sqrt_lt_bound(P.shorted_edge_thre);
   sp.consider_config_1 = P.consider_config_1; sp.consider_config_2 = P.consider_config_2;
 
-  int rc = build_camera_caches(d, b, rs, sample_rp);
-  if (rc) return rc;
-  rs->C = PipeCtx{d, b, out, out_counts, &rs->cam_raw, &rs->rp_off, sp, &rs->tm, &rs->cam_rp};
+  CS_TRY(build_camera_caches(d, b, rs, sample_rp));
+  rs->C = PipeCtx{d, b, OutView{out, out_counts, MB, KMAX}, &rs->cam_raw, &rs->rp_off, sp, &rs->tm, &rs->cam_rp};
   PipeCtx& C = rs->C;
-  if (g_prof) g_mark[11] += now_ms() - t_begin;   // camera caches + pose pool upload
+  if (d->prof) d->prof_mark[11] += now_ms() - t_begin;   // camera caches + pose pool upload
 
   // ---- production path: chunked two-slot pipeline (host packs chunk k+1 / finishes chunk k-1 while the GPU sweeps k)
   if (!sample_rp && lean_path_allowed(b, KMAX)) {
     const int n_chunks = std::max(1, std::min(NF, b->pipe_chunks));
     if (n_chunks == 1) {    // the usual shape: one launch, one finish -- the finish may be left to cs_batch_collect
-      if ((rc = pipe_launch(C, b->pipe[0], 0, NF))) return rc;
-      rs->deferred = true;
+      CS_TRY(pipe_launch(C, b->pipe[0], 0, NF));
       b->run_state = rs_owner.release();
       return defer ? CS_OK : batch_collect_impl(d, b);
     }
     for (int k = 0; k <= n_chunks; k++) {
       if (k < n_chunks) {
         int f0 = (int)((long long)NF * k / n_chunks), f1 = (int)((long long)NF * (k + 1) / n_chunks);
-        if ((rc = pipe_launch(C, b->pipe[k & 1], f0, f1))) return rc;
+        CS_TRY(pipe_launch(C, b->pipe[k & 1], f0, f1));
       }
-      if (k >= 1 && (rc = pipe_finish(C, b->pipe[(k - 1) & 1], rs->cam_rp))) return rc;
+      if (k >= 1) CS_TRY(pipe_finish(C, b->pipe[(k - 1) & 1], rs->cam_rp));
     }
     tm.total_ms = now_ms() - t_begin;
     b->timing = tm;
     b->ran = true;
-    prof_report(tm.total_ms);
+    prof_report(d, tm.total_ms);
     return CS_OK;
   }
 
@@ -2364,8 +2167,8 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
   int max_rp = 0;
   for (int f = 0; f < NF; f++) max_rp = std::max(max_rp, (int)rs->cam_rp[f].size());
   if (sample_rp && lean_path_allowed(b, KMAX) && !b->force_round_path && max_rp <= cs::vp3_table_doubles_per_job() / 2) {
-    if ((rc = rp_launch(C, b->pipe[0], rs->cam_rp))) return rc;
-    rs->deferred = true; rs->rp_lean = true;
+    CS_TRY(rp_launch(C, b->pipe[0], rs->cam_rp));
+    rs->rp_lean = true;
     b->run_state = rs_owner.release();
     return defer ? CS_OK : batch_collect_impl(d, b);
   }
@@ -2377,9 +2180,9 @@ static int batch_run_impl(cs_detector* d, cs_batch* b, cs_cuboid* out, int* out_
   const int n_rounds = sample_rp ? MB : (MB > 0 ? 1 : 0);
   for (int round = 0; round < n_rounds; round++) {
     RoundTables T;
-    if ((rc = round_setup(X, round, T))) return rc;
+    CS_TRY(round_setup(X, round, T));
     if (T.nj == 0) continue;
-    if ((rc = round_upload(X, T)) || (rc = round_sweep(X, T)) || (rc = device_rank ? round_rank_device(X, T) : round_rank_host(X, T))) return rc;
+    CS_TRY(round_upload(X, T)); CS_TRY(round_sweep(X, T)); CS_TRY(device_rank ? round_rank_device(X, T) : round_rank_host(X, T));
   }
   tm.total_ms = now_ms() - t_begin;
   b->timing = tm;

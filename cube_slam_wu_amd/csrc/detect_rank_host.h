@@ -1,6 +1,7 @@
 // detect_rank_host.h -- the rules every sweep path of detect_host.cpp shares, once each: the slot numbering's inverse, the 9-value
 // candidate row, fuse_normalize_scores_v2 and the exact final ranking of a box (tie order is part of the contract: the output is
-// byte-identical to the reference), the geometry of a job descriptor, and the cs_cuboid record of a winner.
+// byte-identical to the reference), the geometry of a job descriptor, the cs_cuboid record of a winner, the host's rebuild of a winner's
+// corners, and the writers of a box's records and count into the caller's output (OutView).
 // Plain C++: nothing here launches a kernel or calls a HIP function (tests/test_detect_rank_host_cpu.py builds it with the host compiler).
 #pragma once
 #include <algorithm>
@@ -105,6 +106,11 @@ struct HeightCols {
   const std::vector<double>* score = nullptr;
 };
 struct RankWeights { double w_angle, w_skew, nominal_skew, max_cut_skew; };   // weight_vp_angle, weight_skew_error, nominal_skew_ratio, max_cut_skew
+// the ranking's parameters out of the detector's: the host's and the kernels' form
+inline RankWeights rank_weights(const cs_detect_params& P) { return RankWeights{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew}; }
+inline cs::RankParams rank_params(const cs_detect_params& P, const cs::SweepParams& sp) {
+  return cs::RankParams{P.weight_vp_angle, P.weight_skew_error, P.nominal_skew_ratio, P.max_cut_skew, P.max_cuboid_num, sp.short_sq_bound};
+}
 struct ExactWinner {
   long long slot;
   int h, cand;             // height sample, candidate index inside it
@@ -208,6 +214,21 @@ inline void finish_cuboid(const FrameIn& F, const cs::RpPose& pose, const double
   }
 }
 
+// The corners of proposal s of job jd, rebuilt on the host (the lean roll/pitch path's tie winners): the vanishing points of pose matrix
+// A = KinvR and the yaw sample's (cos, sin) -- vp_points_kernel's arithmetic, operation for operation -- then build_corners at top-edge sample top_x.
+inline void host_corners16(const double* A, double cy, double sy, const cs::JobDesc& jd, const SlotRef& s, double top_x, double short_sq_bound, double c16[16]) {
+  const double dd[3][3] = {{cy, sy, 0.0}, {-sy, cy, 0.0}, {0.0, 0.0, 1.0}};
+  cs::V2 vp[3], c8[8];
+  for (int k = 0; k < 3; k++) {
+    double h[3];
+    for (int i = 0; i < 3; i++) h[i] = (A[3 * i] * dd[k][0] + A[3 * i + 1] * dd[k][1]) + A[3 * i + 2] * dd[k][2];
+    vp[k] = cs::v2(h[0] / h[2], h[1] / h[2]);
+  }
+  for (auto& c : c8) c = cs::v2(0.0, 0.0);
+  (void)cs::build_corners(jd.g, vp[0], vp[1], vp[2], top_x, s.cfg, short_sq_bound, c8);
+  for (int k = 0; k < 8; k++) { c16[k] = c8[k].x; c16[8 + k] = c8[k].y; }
+}
+
 inline void set_caller_rect(const FrameIn& F, int box, cs_cuboid& o) {
   const double* bb = &F.boxes[5 * box];
   o.rect_detect_2d[0] = (int)bb[0]; o.rect_detect_2d[1] = (int)bb[1]; o.rect_detect_2d[2] = (int)bb[2]; o.rect_detect_2d[3] = (int)bb[3];
@@ -227,6 +248,36 @@ inline void write_winner_record(const FrameIn& F, const cs::JobDesc& jd, const S
 inline void copy_device_record(const FrameIn& F, int box, const cs_cuboid& rec, cs_cuboid& o) {
   o = rec;
   set_caller_rect(F, box, o);
+}
+
+// ---- the caller's output: KMAX records and one count per (frame, box of max_boxes) ---------------------------------------------------
+struct OutView {
+  cs_cuboid* out = nullptr; int* out_counts = nullptr; int max_boxes = 0, kmax = 0;
+  cs_cuboid& rec(int f, int box, int r) const { return out[((size_t)f * max_boxes + box) * kmax + r]; }
+  int& count(int f, int box) const { return out_counts[(size_t)f * max_boxes + box]; }
+};
+
+// The exact winners `wl` of a box into its records and count.  jobs: the box's jobs (one per height sample); yaw: the path's yaw table
+// (jd.yaw_off indexes it); cams[rp].pose: the frame's roll/pitch sample poses; corners_of(r, jd, s): the 16 corner doubles of winner r.
+template <class Cams, class CornersOf>
+inline void write_exact_winners(const OutView& O, const FrameIn& F, const cs::JobDesc* jobs, const std::vector<ExactWinner>& wl, const double* yaw, const Cams& cams,
+                                const double raw_euler[3], bool sample_rp, CornersOf corners_of) {
+  const int f = jobs[0].frame, box = jobs[0].box;
+  for (size_t r = 0; r < wl.size(); r++) {
+    const ExactWinner& w = wl[r];
+    const cs::JobDesc& jd = jobs[w.h];
+    const SlotRef s = decode_slot(jd, w.slot);
+    write_winner_record(F, jd, s, w.flag, w.dist, w.angle, yaw[jd.yaw_off + s.y], cams[s.rp].pose, corners_of(r, jd, s), raw_euler, sample_rp, w.score, O.rec(f, box, (int)r));
+  }
+  O.count(f, box) = (int)wl.size();
+}
+// the corner source of winners whose corners lie one after the other from corners16
+inline auto corners_at(const double* corners16) { return [corners16](size_t r, const cs::JobDesc&, const SlotRef&) { return corners16 + 16 * r; }; }
+
+// The nw records record_kernel wrote for box `box` of frame f, and the count
+inline void write_device_records(const OutView& O, const FrameIn& F, int f, int box, const cs_cuboid* recs, int nw) {
+  for (int r = 0; r < nw; r++) copy_device_record(F, box, recs[r], O.rec(f, box, r));
+  O.count(f, box) = nw;
 }
 
 }  // namespace cs_dh

@@ -385,6 +385,29 @@ def test_roll_pitch_rounds_queued_at_once_equal_the_round_by_round_path(heights,
     lean.close(); ref.close(); det.close()
 
 
+def test_roll_pitch_saved_column_pool_overflow_redoes_frames():
+    """The lean roll/pitch path's redo, asserted to happen: sixteen frames of three boxes whose maps are all zero, so every box is a tie box and
+    all its columns go to the saved-column pool (max(2^18, slots / 64) rows: 2^18 here).  The flagged boxes' valid proposals exceed the pool
+    (the test's own precondition: at least twice 2^18 of them -- four frames of 32 to 35 thousand each, four times over), the boxes that
+    find it full get no rows, and their frames are redone through the round-by-round path on the parent batch's map pool: the same bytes
+    as the round path alone, and at least one frame redone."""
+    uniq = []
+    for seed in (9302, 9307, 9350, 9357):
+        fr = synth.make_frame(seed, n_boxes=3, n_lines=150)
+        fr["maps"] = [[np.zeros_like(m) for m in mm] for mm in fr["maps"]]
+        uniq.append(fr)
+    frames = [uniq[i % 4] for i in range(16)]
+    det = capi.Detector(capi.default_params(whether_sample_cam_roll_pitch=1, yaw_step_deg=0.5, max_cuboid_num=2))
+    ref = capi.Batch(det, frames, force_no_pipeline=True); ref.run()
+    lean = capi.Batch(det, frames); lean.run()
+    tl = lean.timing()
+    print("n_valid %d, n_slots %d, fallback boxes %d, frames redone %d, lean %.2f ms" % (tl["n_valid"], tl["n_slots"], tl["n_fallback_boxes"], tl["n_redo_frames"], tl["total_ms"]))
+    assert tl["n_valid"] >= 2 * 2**18
+    assert lean.raw_out_bytes() == ref.raw_out_bytes() and lean.counts_bytes() == ref.counts_bytes()
+    assert tl["n_redo_frames"] >= 1
+    lean.close(); ref.close(); det.close()
+
+
 @pytest.mark.parametrize("sample_rp", [0, 1])
 def test_every_caller_of_the_exact_ranking_agrees_on_the_same_ties(sample_rp):
     """The exact host ranking (exact_rank_box, detect_rank_host.h) has four callers: the lean pipeline's tie boxes, the lean roll/pitch

@@ -5,7 +5,14 @@ against the header with the host compiler, under the address and undefined-behav
   * exact_rank_box -- the one copy of the exact final ranking all four sweep paths call -- to its properties (min(KMAX, proposals) winners, comb
     non-decreasing, no flagged candidate, every winner in its height sample's keep list, the last kept slot of the last height sample or -1) for
     V = 0, V <= 4, V = 30 with all-equal distance keys, a height sample with every candidate flagged, KMAX above the number of proposals and three
-    height samples, with and without precomputed keep / score lists.
+    height samples, with and without precomputed keep / score lists;
+  * the camera cache (detect_cam_host.h): rot_to_euler(euler_to_rot(r, p, y)) = (r, p, y) over a grid that takes the positive-trace branch and each
+    of the three largest-diagonal branches of the quaternion step; make_cam's KinvR against K R^-1 in long double and its ground-plane row; the
+    roll/pitch sample poses, roll-major, each storing its sample angles (25 for a camera whose lists close at +6 degrees, 20 for a forward-looking
+    one whose roll list rounds past it -- the count linespace's loop gives, restated);
+  * host_corners16 to build_corners on the vanishing points restated in the program, bit for bit, with at least one accepted proposal;
+  * the record writers (write_exact_winners with corners from a callback and from corners_at, write_device_records) to writing the records and count of rec(f, box, r) / count(f, box)
+    of a 2-frame, 3-box, KMAX = 2 output and no element beside them; rank_weights / rank_params to the detector's parameters.
 That the four callers then write the same bytes is tests/test_detect_gpu.py's business."""
 import os
 import shutil
