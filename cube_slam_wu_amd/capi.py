@@ -1408,6 +1408,120 @@ def triangulate_inspect(batch, params=None, device=0):
     return out
 
 
+# ------------------------------------------------------------------ guided ORB matching by projection, batched -----------------
+class CsOrbSearchParams(C.Structure):
+    _fields_ = [("min_dist_factor", C.c_double), ("max_dist_factor", C.c_double), ("view_cos", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double),
+                ("grid_cols", C.c_int), ("grid_rows", C.c_int)]
+
+
+DECLARED_SYMBOLS += ["cs_orb_search_default_params", "cs_orb_search_create", "cs_orb_search_destroy", "cs_orb_search_set_frames", "cs_orb_search_run",
+                     "cs_orb_search_last_timing", "cs_orb_search_jobs", "cs_orb_search_inspect", "cs_orb_search_mutual"]
+
+# cs_orb_search_status / cs_orb_search_flags
+ORB_STATUS = {"OK": 0, "SKIPPED": 1, "BEHIND": 2, "OUT_OF_IMAGE": 3, "OUT_OF_RANGE": 4, "VIEW_ANGLE": 5, "NO_CANDIDATE": 6, "TOO_FAR": 7}
+ORB_FLAGS = {"CHECK_VIEW": 1, "CHECK_REPROJ": 2}
+
+
+def orb_search_default_params(**kw):
+    """cs_orb_search_default_params with overrides."""
+    p = CsOrbSearchParams()
+    lib().cs_orb_search_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _u8(a, shape):
+    return np.ascontiguousarray(np.asarray(a, np.uint8).reshape(shape))
+
+
+def _orb_frame_inputs(batch):
+    """The frames of a batch dict (synth_orb_search layout: kp_ptr, kp, octave, desc, cam, bounds, scale_factor, n_levels) as C arguments."""
+    cam = _f64(batch["cam"], (-1, 5)); n = len(cam)
+    bounds, sf, nl = _f64(batch["bounds"], (n, 4)), _f64(batch["scale_factor"], (n,)), _i32(batch["n_levels"])
+    ptr = _i32(batch["kp_ptr"])
+    if len(ptr) != n + 1 or len(nl) != n:
+        raise ValueError("kp_ptr must hold n_frames + 1 entries and n_levels n_frames")
+    N = int(ptr[-1]) if n else 0
+    kp, octave, desc = _f64(batch["kp"], (N, 3)), _i32(batch["octave"]), _u8(batch["desc"], (N, 32))
+    if len(octave) != N:
+        raise ValueError("octave must hold one entry per keypoint")
+    keep = (ptr, kp, octave, desc, cam, bounds, sf, nl)
+    return n, N, keep, (_ip(ptr), _dp(kp), _ip(octave), _u8p(desc), _dp(cam), _dp(bounds), _dp(sf), _ip(nl))
+
+
+def _orb_job_inputs(batch):
+    """The jobs of a batch dict (frame_of_job, pose8, th, max_hamming, flags, query_ptr, X, normal, dist_range, qdesc, skip) as C arguments."""
+    pose = _f64(batch["pose8"], (-1, 8)); n = len(pose)
+    fj, th, mh, fl, ptr = _i32(batch["frame_of_job"]), _f64(batch["th"], (n,)), _i32(batch["max_hamming"]), _i32(batch["flags"]), _i32(batch["query_ptr"])
+    if len(ptr) != n + 1 or len(fj) != n or len(mh) != n or len(fl) != n:
+        raise ValueError("query_ptr must hold n_jobs + 1 entries; frame_of_job, max_hamming and flags n_jobs")
+    Q = int(ptr[-1]) if n else 0
+    X, nrm, dr, qd, skip = _f64(batch["X"], (Q, 3)), _f64(batch["normal"], (Q, 3)), _f64(batch["dist_range"], (Q, 2)), _u8(batch["qdesc"], (Q, 32)), _u8(batch["skip"], (Q,))
+    keep = (fj, pose, th, mh, fl, ptr, X, nrm, dr, qd, skip)
+    return n, Q, keep, (_ip(fj), _dp(pose), _dp(th), _ip(mh), _ip(fl), _ip(ptr), _dp(X), _dp(nrm), _dp(dr), _u8p(qd), _u8p(skip))
+
+
+def _orb_outputs(n, Q, inspect=False):
+    out = dict(status=np.zeros(Q, np.uint8), best_idx=np.zeros(Q, np.int32), best_dist=np.zeros(Q, np.int32), level=np.zeros(Q, np.uint8), n_ok=np.zeros(n, np.int32))
+    args = (_u8p(out["status"]), _ip(out["best_idx"]), _ip(out["best_dist"]), _u8p(out["level"]), _ip(out["n_ok"]))
+    if inspect:
+        out.update(insp5=np.zeros((Q, 5)), n_window=np.zeros(Q, np.int32), n_candidates=np.zeros(Q, np.int32))
+        args += (_dp(out["insp5"]), _ip(out["n_window"]), _ip(out["n_candidates"]))
+    return out, args
+
+
+class OrbSearch(_BatchHandle):
+    """cs_orb_search handle: keeps its stream, its buffers and a set of frames on the device between run() calls."""
+
+    _SYM = "cs_orb_search"
+
+    def set_frames(self, batch, params=None):
+        """Checks, packs (each frame's grid is built here) and uploads the frames of `batch`; they replace the set the handle held."""
+        p = params if params is not None else orb_search_default_params()
+        n, N, keep, args = _orb_frame_inputs(batch)
+        _chk(lib().cs_orb_search_set_frames(self.h, C.byref(p), n, *args), "cs_orb_search_set_frames")
+
+    def run(self, batch):
+        """The jobs of `batch` against the handle's frames -> dict: status, level (Q, uint8), best_idx, best_dist (Q), n_ok (n_jobs)."""
+        n, Q, keep, args = _orb_job_inputs(batch)
+        out, outs = _orb_outputs(n, Q)
+        _chk(lib().cs_orb_search_run(self.h, n, *args, *outs), "cs_orb_search_run")
+        return out
+
+
+def _orb_one_shot(name, batch, params, device, inspect):
+    p = params if params is not None else orb_search_default_params()
+    nf, N, keep_f, fargs = _orb_frame_inputs(batch)
+    nj, Q, keep_j, jargs = _orb_job_inputs(batch)
+    out, outs = _orb_outputs(nj, Q, inspect)
+    _chk(getattr(lib(), name)(int(device), C.byref(p), nf, *fargs, nj, *jargs, *outs), name)
+    return out
+
+
+def orb_search_jobs(batch, params=None, device=0):
+    """cs_orb_search_jobs: the one-shot form, frames and jobs in one call."""
+    return _orb_one_shot("cs_orb_search_jobs", batch, params, device, False)
+
+
+def orb_search_inspect(batch, params=None, device=0):
+    """cs_orb_search_inspect: orb_search_jobs' outputs plus insp5 (Q, 5) = u v ur dist radius, n_window and n_candidates of every query."""
+    return _orb_one_shot("cs_orb_search_inspect", batch, params, device, True)
+
+
+def orb_search_mutual(best12, status12, best21, status21):
+    """cs_orb_search_mutual -> match12 (n1): j where i -> j and j -> i are both OK, -1 otherwise; runs without a device."""
+    b12, b21, s12, s21 = _i32(best12), _i32(best21), _u8(status12, (-1,)), _u8(status21, (-1,))
+    if len(b12) != len(s12) or len(b21) != len(s21):
+        raise ValueError("one status per best index")
+    out, n = np.zeros(len(b12), np.int32), C.c_int()
+    _chk(lib().cs_orb_search_mutual(len(b12), _ip(b12), _u8p(s12), len(b21), _ip(b21), _u8p(s21), _ip(out), C.byref(n)), "cs_orb_search_mutual")
+    assert n.value == int((out >= 0).sum())
+    return out
+
+
 DECLARED_SYMBOLS += ["cs_pgo_create", "cs_pgo_destroy", "cs_pgo_set_vertices", "cs_pgo_set_estimates", "cs_pgo_set_edges", "cs_pgo_set_lm_params", "cs_pgo_chi2",
                      "cs_pgo_linearize_edges", "cs_pgo_edge_terms", "cs_pgo_optimize", "cs_pgo_get_vertices", "cs_pgo_get_se3", "cs_pgo_correct_points", "cs_pgo_solver_path", "cs_pgo_last_timing"]
 

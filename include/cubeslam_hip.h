@@ -966,6 +966,102 @@ int cs_triangulate_inspect(int device, const cs_triangulate_params* p, int n_pai
       double* X3_out, double* normal3_out, double* min_distance_out, double* max_distance_out,
       unsigned char* status_out, unsigned char* route_out, unsigned char* ran_out, int* n_accepted_out, double* cos3_out);
 
+/* ------------------------------------------------------------------ Path B'''''': guided ORB matching by projection, batched -------- */
+/* Replaces, for many (map points -> keyframe) jobs at once, the guided matcher an ORB-SLAM2-derived back end runs between its geometric
+ * steps (NOT IN THE REFERENCE): ORBmatcher::Fuse(pKF, vpMapPoints, th) of LocalMapping::SearchInNeighbors,
+ * ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse and ORBmatcher::SearchBySim3 of
+ * LoopClosing::ComputeSim3, with KeyFrame::GetFeaturesInArea and MapPoint::PredictScale.  In these a query's result depends on that
+ * query alone.  ORBmatcher::SearchByProjection (tracking) and SearchForTriangulation assign keypoints while they loop and are NOT
+ * covered.  ORB-SLAM2 computes in float32; this is FP64.  csrc/cs_orb_search.h carries the statement for host and device (its top
+ * comment gives every formula and the order of every sum):
+ *   frame     keypoints (u v ur; ur < 0: no right-image coordinate), an octave and 32 descriptor bytes each, cam = fx fy cx cy bf,
+ *             bounds = min_x max_x min_y max_y, scale_factor, n_levels; scale[l] = scale[l-1] scale_factor, inv_sigma2[l] = 1 / scale[l]^2.
+ *             A keypoint lies in grid cell (floor((u - min_x) cols / (max_x - min_x) + 0.5), likewise for v); one whose cell is outside
+ *             the grid is in no cell and is never matched (ORB-SLAM2's behaviour at the right and bottom border).
+ *   job       a frame, Xc = s R X + t (pose8 = x y z qx qy qz qw s), th, max_hamming, flags.
+ *   query     the first step that fails gives the status: skip: SKIPPED; Xc.z <= 0: BEHIND (ORB-SLAM2: < 0); the projection outside
+ *             [min_x, max_x) x [min_y, max_y): OUT_OF_IMAGE; |Xc| outside [min_dist_factor min_distance, max_dist_factor max_distance]:
+ *             OUT_OF_RANGE; with CHECK_VIEW, Xc . (R normal) < view_cos |Xc|: VIEW_ANGLE; level = the smallest l with
+ *             scale[l] >= max_distance / |Xc| (at most n_levels - 1), radius = th scale[level]; over the cells of GetFeaturesInArea's
+ *             window, columns outermost, rows inside, keypoints in ascending index: a keypoint with |du| < radius, |dv| < radius,
+ *             level - 1 <= octave <= level and (with CHECK_REPROJ) e2 inv_sigma2[octave] <= chi2_mono / chi2_stereo is a candidate; the
+ *             smallest Hamming distance wins, AMONG EQUALS THE FIRST IN THAT ORDER; none: NO_CANDIDATE; a best distance above
+ *             max_hamming: TOO_FAR (index and distance are still handed out); otherwise OK.
+ *
+ * All queries of a call are run by ONE kernel launch, one lane per query, one wavefront per chunk of at most 64 queries of one job
+ * (DESIGN.md section 16); a query's outputs are the same bits at any position in any batch.  Every argument is checked on the host
+ * before anything is launched and a refused call (CS_ERR_INVALID_ARG) writes no output.  Empty batches, jobs without queries and frames
+ * without keypoints are valid.                                                                                                      */
+typedef enum cs_orb_search_status {
+  CS_ORB_OK = 0, CS_ORB_SKIPPED = 1, CS_ORB_BEHIND = 2, CS_ORB_OUT_OF_IMAGE = 3, CS_ORB_OUT_OF_RANGE = 4, CS_ORB_VIEW_ANGLE = 5,
+  CS_ORB_NO_CANDIDATE = 6, CS_ORB_TOO_FAR = 7
+} cs_orb_search_status;
+typedef enum cs_orb_search_flags { CS_ORB_CHECK_VIEW = 1, CS_ORB_CHECK_REPROJ = 2 } cs_orb_search_flags;
+typedef struct cs_orb_search_params {
+  double min_dist_factor;           /* Fuse: dist3D < 0.8 * minDistance (0.8)                                                 */
+  double max_dist_factor;           /* ... dist3D > 1.2 * maxDistance (1.2)                                                   */
+  double view_cos;                  /* ... PO.dot(Pn) < 0.5 * dist3D (0.5)                                                    */
+  double chi2_mono;                 /* ... e2 * invSigma2 > 5.99 (5.99)                                                       */
+  double chi2_stereo;               /* ... e2 * invSigma2 > 7.8 (7.8)                                                         */
+  int grid_cols;                    /* FRAME_GRID_COLS (64), 1 .. 128                                                         */
+  int grid_rows;                    /* FRAME_GRID_ROWS (48), 1 .. 128                                                         */
+} cs_orb_search_params;
+/* ORBmatcher::Fuse's constants and ORB-SLAM2's 64 x 48 grid. */
+void cs_orb_search_default_params(cs_orb_search_params* p);
+/* A handle that keeps its stream, its buffers AND a set of frames on the device between calls: SearchInNeighbors and SearchBySim3 search
+ * the same keyframes twice, once in each direction.  Calls on one handle must not overlap.                                         */
+typedef struct cs_orb_search cs_orb_search;
+int cs_orb_search_create(int device, cs_orb_search** out);
+void cs_orb_search_destroy(cs_orb_search* b);
+/* Checks every argument, builds each frame's grid (a stable counting sort by cell) while packing, uploads once.  Replaces the set the
+ * handle held; a refused call leaves that set in place.                                                                            */
+int cs_orb_search_set_frames(cs_orb_search* b, const cs_orb_search_params* p, int n_frames,
+      const int* kp_ptr,                        /* n_frames + 1: frame f owns keypoints kp_ptr[f] .. kp_ptr[f + 1] - 1             */
+      const double* kp,                         /* n_keypoints x 3: u v ur (ur < 0: none)                                          */
+      const int* octave,                        /* n_keypoints, 0 .. n_levels - 1 of the keypoint's frame                          */
+      const unsigned char* desc,                /* n_keypoints x 32                                                                */
+      const double* cam,                        /* n_frames x 5: fx fy cx cy bf                                                    */
+      const double* bounds,                     /* n_frames x 4: min_x max_x min_y max_y                                           */
+      const double* scale_factor,               /* n_frames, > 1                                                                   */
+      const int* n_levels);                     /* n_frames, 1 .. 16                                                               */
+/* Ships only jobs and queries; the frames are the handle's.  Refused before cs_orb_search_set_frames and for a frame index outside
+ * the set.  Outputs per query: status_out, best_idx_out (the keypoint's index within its frame, -1: none), best_dist_out (-1: none),
+ * level_out (255: not reached); per job: n_ok_out, the number of CS_ORB_OK queries.                                                 */
+int cs_orb_search_run(cs_orb_search* b, int n_jobs,
+      const int* frame_of_job,                  /* n_jobs                                                                          */
+      const double* pose8,                      /* n_jobs x 8: x y z qx qy qz qw s; Xc = s R X + t                                 */
+      const double* th,                         /* n_jobs: the radius factor                                                       */
+      const int* max_hamming,                   /* n_jobs: 0 .. 256 (TH_LOW = 50 for Fuse, TH_HIGH = 100 for SearchBySim3)         */
+      const int* flags,                         /* n_jobs: CS_ORB_CHECK_VIEW | CS_ORB_CHECK_REPROJ                                 */
+      const int* query_ptr,                     /* n_jobs + 1                                                                      */
+      const double* X, const double* normal,    /* n_queries x 3 each, world coordinates                                           */
+      const double* dist_range,                 /* n_queries x 2: min_distance max_distance, as cs_triangulate hands them out      */
+      const unsigned char* qdesc,               /* n_queries x 32                                                                  */
+      const unsigned char* skip,                /* n_queries: non-zero = isBad / IsInKeyFrame / already matched                    */
+      unsigned char* status_out, int* best_idx_out, int* best_dist_out, unsigned char* level_out, int* n_ok_out);
+/* Of the handle's last cs_orb_search_run that passed its argument checks: kernel_ms = the one kernel, from hipEvents on the handle's
+ * stream; host_ms = the whole call on a monotonic clock.                                                                            */
+int cs_orb_search_last_timing(const cs_orb_search* b, double* kernel_ms, double* host_ms);
+/* One shot: frames and jobs in one call.  Same bits as the handle's.                                                                */
+int cs_orb_search_jobs(int device, const cs_orb_search_params* p, int n_frames, const int* kp_ptr, const double* kp, const int* octave,
+      const unsigned char* desc, const double* cam, const double* bounds, const double* scale_factor, const int* n_levels,
+      int n_jobs, const int* frame_of_job, const double* pose8, const double* th, const int* max_hamming, const int* flags,
+      const int* query_ptr, const double* X, const double* normal, const double* dist_range, const unsigned char* qdesc,
+      const unsigned char* skip, unsigned char* status_out, int* best_idx_out, int* best_dist_out, unsigned char* level_out, int* n_ok_out);
+/* Inspection: as cs_orb_search_jobs, plus per query insp5_out = u v ur dist radius (zeros before the step that computes them),
+ * n_window_out = the keypoints that pass the two |d| < radius tests, n_candidates_out = those that also pass the level and
+ * reprojection gates.                                                                                                               */
+int cs_orb_search_inspect(int device, const cs_orb_search_params* p, int n_frames, const int* kp_ptr, const double* kp, const int* octave,
+      const unsigned char* desc, const double* cam, const double* bounds, const double* scale_factor, const int* n_levels,
+      int n_jobs, const int* frame_of_job, const double* pose8, const double* th, const int* max_hamming, const int* flags,
+      const int* query_ptr, const double* X, const double* normal, const double* dist_range, const unsigned char* qdesc,
+      const unsigned char* skip, unsigned char* status_out, int* best_idx_out, int* best_dist_out, unsigned char* level_out, int* n_ok_out,
+      double* insp5_out, int* n_window_out, int* n_candidates_out);
+/* SearchBySim3's agreement step, plain host code (no device): match12_out[i] = j iff best12[i] = j with status12[i] = CS_ORB_OK and
+ * best21[j] = i with status21[j] = CS_ORB_OK, otherwise -1; *n_out = the number of matches.                                          */
+int cs_orb_search_mutual(int n1, const int* best12, const unsigned char* status12, int n2, const int* best21, const unsigned char* status21,
+      int* match12_out, int* n_out);
+
 #ifdef __cplusplus
 }
 #endif
