@@ -100,14 +100,28 @@ def last_error():
     return lib().cs_last_error().decode()
 
 
-def default_params(**kw):
-    p = CsDetectParams()
-    lib().cs_detect_default_params(C.byref(p))
+def _default_params(struct_type, symbol, kw, hook=None):
+    """A parameter struct as <symbol> fills it, with the overrides `kw`; hook(p, k, v) -> True where it has set field k itself."""
+    p = struct_type()
+    getattr(lib(), symbol)(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise KeyError(k)
-        setattr(p, k, v)
+        if hook is None or not hook(p, k, v):
+            setattr(p, k, v)
     return p
+
+
+def _ptr_array(batch, key, n, what):
+    """batch[key] as int32, which must hold n + 1 entries (`what` names the n) -> (the array, its last entry = the number of items)."""
+    ptr = _i32(batch[key])
+    if len(ptr) != n + 1:
+        raise ValueError("%s must hold %s + 1 entries" % (key, what))
+    return ptr, (int(ptr[-1]) if n else 0)
+
+
+def default_params(**kw):
+    return _default_params(CsDetectParams, "cs_detect_default_params", kw)
 
 
 def check_score_atan2(y, x):
@@ -1082,26 +1096,18 @@ DECLARED_SYMBOLS += ["cs_pose_default_params", "cs_pose_optimize_batch", "cs_pos
 
 def pose_default_params(**kw):
     """cs_pose_default_params with overrides; `iterations` takes a list of n_rounds counts."""
-    p = CsPoseParams()
-    lib().cs_pose_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
+    def iterations(p, k, v):
         if k == "iterations":
             for r, n in enumerate(v):
                 p.iterations[r] = int(n)
-        else:
-            setattr(p, k, v)
-    return p
+        return k == "iterations"
+    return _default_params(CsPoseParams, "cs_pose_default_params", kw, iterations)
 
 
 def _pose_inputs(batch):
     """A batch dict (synth_pose.synth_pose_batch layout: Tcw, intr, obs_ptr, Xw, meas, info, is_stereo) as C arguments."""
     T = _f64(batch["Tcw"], (-1, 7)); n = len(T)
-    intr, ptr = _f64(batch["intr"], (n, 5)), _i32(batch["obs_ptr"])
-    if len(ptr) != n + 1:
-        raise ValueError("obs_ptr must hold n_frames + 1 entries")
-    N = int(ptr[-1]) if n else 0
+    intr, (ptr, N) = _f64(batch["intr"], (n, 5)), _ptr_array(batch, "obs_ptr", n, "n_frames")
     X, m, W = _f64(batch["Xw"], (N, 3)), _f64(batch["meas"], (N, 3)), _f64(batch["info"], (N, 9))
     st = np.ascontiguousarray(np.asarray(batch["is_stereo"]).ravel().astype(np.uint8))
     if len(st) != N:
@@ -1187,25 +1193,16 @@ DECLARED_SYMBOLS += ["cs_sim3_pair_default_params", "cs_sim3_optimize_pairs", "c
 
 def sim3_pair_default_params(**kw):
     """cs_sim3_pair_default_params with overrides."""
-    p = CsSim3PairParams()
-    lib().cs_sim3_pair_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _default_params(CsSim3PairParams, "cs_sim3_pair_default_params", kw)
 
 
 def _sim3_pair_inputs(batch):
     """A batch dict (synth_sim3_pairs.synth_sim3_pairs layout: S12, intr, fix_scale, match_ptr, P1, P2, obs1, obs2, info12, info21) as C arguments."""
     S = _f64(batch["S12"], (-1, 8)); n = len(S)
-    intr, ptr = _f64(batch["intr"], (n, 8)), _i32(batch["match_ptr"])
-    if len(ptr) != n + 1:
-        raise ValueError("match_ptr must hold n_pairs + 1 entries")
+    intr, (ptr, N) = _f64(batch["intr"], (n, 8)), _ptr_array(batch, "match_ptr", n, "n_pairs")
     fs = np.ascontiguousarray(np.asarray(batch["fix_scale"]).ravel().astype(np.uint8))
     if len(fs) != n:
         raise ValueError("fix_scale must hold one entry per pair")
-    N = int(ptr[-1]) if n else 0
     P1, P2, o1, o2 = _f64(batch["P1"], (N, 3)), _f64(batch["P2"], (N, 3)), _f64(batch["obs1"], (N, 2)), _f64(batch["obs2"], (N, 2))
     W12 = _f64(batch["info12"], (N, 4)) if batch.get("info12") is not None else None
     W21 = _f64(batch["info21"], (N, 4)) if batch.get("info21") is not None else None
@@ -1262,26 +1259,17 @@ DECLARED_SYMBOLS += ["cs_sim3_ransac_default_params", "cs_sim3_ransac_pairs", "c
 
 def sim3_ransac_default_params(**kw):
     """cs_sim3_ransac_default_params with overrides."""
-    p = CsSim3RansacParams()
-    lib().cs_sim3_ransac_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _default_params(CsSim3RansacParams, "cs_sim3_ransac_default_params", kw)
 
 
 def _sim3_ransac_inputs(batch):
     """A batch dict (synth_sim3_ransac layout: intr, fix_scale, seed, match_ptr, P1, P2, max_err1, max_err2) as C arguments."""
     intr = _f64(batch["intr"], (-1, 8)); n = len(intr)
-    ptr = _i32(batch["match_ptr"])
-    if len(ptr) != n + 1:
-        raise ValueError("match_ptr must hold n_pairs + 1 entries")
+    ptr, N = _ptr_array(batch, "match_ptr", n, "n_pairs")
     fs = np.ascontiguousarray(np.asarray(batch["fix_scale"]).ravel().astype(np.uint8))
     seed = np.ascontiguousarray(np.asarray(batch["seed"]).ravel().astype(np.uint64))
     if len(fs) != n or len(seed) != n:
         raise ValueError("fix_scale and seed must hold one entry per pair")
-    N = int(ptr[-1]) if n else 0
     P1, P2, t1, t2 = _f64(batch["P1"], (N, 3)), _f64(batch["P2"], (N, 3)), _f64(batch["max_err1"], (N,)), _f64(batch["max_err2"], (N,))
     keep = (intr, fs, seed, ptr, P1, P2, t1, t2)
     return n, N, keep, (_dp(intr), _u8p(fs), seed.ctypes.data_as(C.POINTER(C.c_ulonglong)), _ip(ptr), _dp(P1), _dp(P2), _dp(t1), _dp(t2))
@@ -1346,23 +1334,14 @@ TRI_ROUTE = {"NONE": 0, "TRIANGULATED": 1, "STEREO1": 2, "STEREO2": 3}
 
 def triangulate_default_params(**kw):
     """cs_triangulate_default_params with overrides."""
-    p = CsTriangulateParams()
-    lib().cs_triangulate_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _default_params(CsTriangulateParams, "cs_triangulate_default_params", kw)
 
 
 def _triangulate_inputs(batch):
     """A batch dict (synth_triangulate layout: Tcw1, Tcw2, cam1, cam2, median_depth2, match_ptr, kp1, kp2) as C arguments."""
     T1 = _f64(batch["Tcw1"], (-1, 7)); n = len(T1)
     T2, c1, c2, md = _f64(batch["Tcw2"], (n, 7)), _f64(batch["cam1"], (n, 6)), _f64(batch["cam2"], (n, 6)), _f64(batch["median_depth2"], (n,))
-    ptr = _i32(batch["match_ptr"])
-    if len(ptr) != n + 1:
-        raise ValueError("match_ptr must hold n_pairs + 1 entries")
-    N = int(ptr[-1]) if n else 0
+    ptr, N = _ptr_array(batch, "match_ptr", n, "n_pairs")
     k1, k2 = _f64(batch["kp1"], (N, 6)), _f64(batch["kp2"], (N, 6))
     keep = (T1, T2, c1, c2, md, ptr, k1, k2)
     return n, N, keep, (_dp(T1), _dp(T2), _dp(c1), _dp(c2), _dp(md), _ip(ptr), _dp(k1), _dp(k2))
@@ -1424,13 +1403,7 @@ ORB_FLAGS = {"CHECK_VIEW": 1, "CHECK_REPROJ": 2}
 
 def orb_search_default_params(**kw):
     """cs_orb_search_default_params with overrides."""
-    p = CsOrbSearchParams()
-    lib().cs_orb_search_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _default_params(CsOrbSearchParams, "cs_orb_search_default_params", kw)
 
 
 def _u8(a, shape):

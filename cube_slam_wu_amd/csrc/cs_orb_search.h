@@ -47,6 +47,7 @@
 #include <math.h>
 
 #include "cs_dense_lm.h"      // CS_HD, CS_UNROLL, CS_NOUNROLL
+#include "cs_se3.h"           // quat_rotmat
 
 namespace cs {
 
@@ -101,11 +102,7 @@ CS_HD void orb_frame_record(const double* cam5, const double* bounds4, double sc
 // pose8: x y z qx qy qz qw s
 CS_HD void orb_job_record(const double* pose8, double th, int frame, int max_hamming, int flags, OrbJob& J) {
   const double n = sqrt(pose8[3] * pose8[3] + pose8[4] * pose8[4] + pose8[5] * pose8[5] + pose8[6] * pose8[6]);
-  const double x = pose8[3] / n, y = pose8[4] / n, z = pose8[5] / n, w = pose8[6] / n;
-  double* R = J.R;
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+  quat_rotmat(pose8[6] / n, pose8[3] / n, pose8[4] / n, pose8[5] / n, J.R);
   CS_UNROLL
   for (int i = 0; i < 3; i++) J.t[i] = pose8[i];
   J.s = pose8[7]; J.th = th;

@@ -81,6 +81,14 @@ CS_HD void pose_rotmat(const Pose& p, double* R) {  // Eigen toRotationMatrix
   R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
   R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
+// R (row-major) of the unit quaternion (w, x, y, z) with every product and sum as written: what cs_sim3_ransac.h, cs_triangulate.h and
+// cs_orb_search.h, held bit for bit to their float64 references, use.  pose_rotmat above doubles x, y, z FIRST (2x y - 2z w, not
+// 2 (x y - w z)): another sequence of operations, the bundle adjustment's, and it stays what it is.
+CS_HD void quat_rotmat(double w, double x, double y, double z, double* R) {
+  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
 CS_HD void quat_from_rotmat(const double* R, Pose& p) {  // Eigen Quaterniond(Matrix3d)
   double t = R[0] + R[4] + R[8];
   if (t > 0.0) {

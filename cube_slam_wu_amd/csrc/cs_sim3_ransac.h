@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "cs_dense_lm.h"      // CS_HD, CS_UNROLL, CS_NOUNROLL
+#include "cs_se3.h"           // quat_rotmat
 
 namespace cs {
 
@@ -150,10 +151,7 @@ CS_HD void sim3_ransac_top_eigenvector(const double* n10, double* q) {
 
 // The rotation matrix (row-major) of the unit quaternion (w, x, y, z)
 CS_HD void sim3_ransac_rotation(const double* q, double* R) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+  quat_rotmat(q[0], q[1], q[2], q[3], R);
 }
 
 // A hypothesis as it is kept and handed out: the unit quaternion (w, x, y, z), t12 and s.

@@ -46,6 +46,7 @@
 #include <math.h>
 
 #include "cs_dense_lm.h"      // CS_HD, CS_UNROLL, CS_NOUNROLL
+#include "cs_se3.h"           // quat_rotmat
 
 namespace cs {
 
@@ -80,10 +81,7 @@ CS_HD bool tri_finite(double x) { return fabs(x) <= DBL_MAX; }      // (a NaN co
 // R (row-major) of q / |q|, t and O = -R^T t from 7 doubles x y z qx qy qz qw
 CS_HD void triangulate_camera(const double* Tcw, double* R, double* t, double* O) {
   const double n = sqrt(Tcw[3] * Tcw[3] + Tcw[4] * Tcw[4] + Tcw[5] * Tcw[5] + Tcw[6] * Tcw[6]);
-  const double x = Tcw[3] / n, y = Tcw[4] / n, z = Tcw[5] / n, w = Tcw[6] / n;
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+  quat_rotmat(Tcw[6] / n, Tcw[3] / n, Tcw[4] / n, Tcw[5] / n, R);
   CS_UNROLL
   for (int i = 0; i < 3; i++) t[i] = Tcw[i];
   CS_UNROLL

@@ -31,25 +31,23 @@ struct cs_orb_search : cs::BatchHandle {
   bool has_frames = false;
   int n_frames = 0;
   cs::OrbParams prm = {};
-  size_t at_frame = 0, at_start = 0, at_kp4 = 0, at_orig = 0, at_desc = 0;
+  cs::Part<cs::OrbFrame> set_frame;        // the parts of d_set
+  cs::Part<int> set_start, set_orig;
+  cs::Part<double> set_kp4;
+  cs::Part<unsigned> set_desc;
 };
 
 namespace {
 
-bool all_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
-bool positive(double x) { return std::isfinite(x) && x > 0; }
+using cs::all_finite;
+using cs::positive;
 
 int check_params(const char* who, const cs_orb_search_params* p) {
-  auto fail = [&](const char* what) { cs_set_error((std::string(who) + ": " + what).c_str()); return CS_ERR_INVALID_ARG; };
-  if (!p) return fail("NULL parameters");
+  const cs::Refuse refuse{who};
+  if (!p) return refuse("NULL parameters");
   if (!positive(p->min_dist_factor) || !positive(p->max_dist_factor) || !std::isfinite(p->view_cos) || !positive(p->chi2_mono) || !positive(p->chi2_stereo))
-    return fail("the distance factors and chi2 gates must be finite and positive, view_cos finite");
-  if (p->grid_cols < 1 || p->grid_cols > cs::ORB_MAX_GRID || p->grid_rows < 1 || p->grid_rows > cs::ORB_MAX_GRID) return fail("grid_cols and grid_rows must be in 1 .. 128");
+    return refuse("the distance factors and chi2 gates must be finite and positive, view_cos finite");
+  if (p->grid_cols < 1 || p->grid_cols > cs::ORB_MAX_GRID || p->grid_rows < 1 || p->grid_rows > cs::ORB_MAX_GRID) return refuse("grid_cols and grid_rows must be in 1 .. 128");
   return CS_OK;
 }
 
@@ -81,193 +79,171 @@ struct Outputs {
 
 // What cs_orb_search_set_frames checks before anything is packed.  *n_keypoints = kp_ptr[n_frames].
 int check_frames(const char* who, const cs_orb_search_params* p, int n_frames, const Frames& in, size_t* n_keypoints) {
-  auto fail = [&](const char* what) { cs_set_error((std::string(who) + ": " + what).c_str()); return CS_ERR_INVALID_ARG; };
+  const cs::Refuse refuse{who};
   *n_keypoints = 0;
   if (n_frames == 0) return CS_OK;
-  if (!in.kp_ptr || !in.cam || !in.bounds || !in.scale_factor || !in.n_levels) return fail("NULL argument");
+  if (!in.kp_ptr || !in.cam || !in.bounds || !in.scale_factor || !in.n_levels) return refuse("NULL argument");
   if (int rc = cs::check_partition(std::string(who) + ": kp_ptr", in.kp_ptr, n_frames)) return rc;
   const size_t nf = (size_t)n_frames, n = (size_t)in.kp_ptr[n_frames];
-  if (n > (size_t)INT_MAX / 8 || nf * ((size_t)p->grid_cols * p->grid_rows + 1) > (size_t)INT_MAX / 4) return fail("too many keypoints or frames for one set");
-  if (n > 0 && (!in.kp || !in.octave || !in.desc)) return fail("NULL keypoint array");
-  if (!all_finite(in.cam, 5 * nf) || !all_finite(in.bounds, 4 * nf) || !all_finite(in.scale_factor, nf)) return fail("an intrinsic, a bound or a scale factor is not finite");
+  if (n > (size_t)INT_MAX / 8 || nf * ((size_t)p->grid_cols * p->grid_rows + 1) > (size_t)INT_MAX / 4) return refuse("too many keypoints or frames for one set");
+  if (n > 0 && (!in.kp || !in.octave || !in.desc)) return refuse("NULL keypoint array");
+  if (!all_finite(in.cam, 5 * nf) || !all_finite(in.bounds, 4 * nf) || !all_finite(in.scale_factor, nf)) return refuse("an intrinsic, a bound or a scale factor is not finite");
   for (size_t f = 0; f < nf; f++) {
     const double *c = in.cam + 5 * f, *b = in.bounds + 4 * f;
-    if (!(c[0] > 0 && c[1] > 0)) return fail("fx and fy must be positive");
-    if (!(b[1] > b[0] && b[3] > b[2])) return fail("max_x > min_x and max_y > min_y are required");
-    if (!std::isfinite(p->grid_cols / (b[1] - b[0])) || !std::isfinite(p->grid_rows / (b[3] - b[2]))) return fail("the image bounds are too narrow for the grid");
-    if (!(in.scale_factor[f] > 1)) return fail("scale_factor must be greater than 1");
-    if (in.n_levels[f] < 1 || in.n_levels[f] > cs::ORB_MAX_LEVELS) return fail("n_levels must be in 1 .. 16");
+    if (!(c[0] > 0 && c[1] > 0)) return refuse("fx and fy must be positive");
+    if (!(b[1] > b[0] && b[3] > b[2])) return refuse("max_x > min_x and max_y > min_y are required");
+    if (!std::isfinite(p->grid_cols / (b[1] - b[0])) || !std::isfinite(p->grid_rows / (b[3] - b[2]))) return refuse("the image bounds are too narrow for the grid");
+    if (!(in.scale_factor[f] > 1)) return refuse("scale_factor must be greater than 1");
+    if (in.n_levels[f] < 1 || in.n_levels[f] > cs::ORB_MAX_LEVELS) return refuse("n_levels must be in 1 .. 16");
     double sc = 1.0;
     for (int l = 1; l < in.n_levels[f]; l++) sc = sc * in.scale_factor[f];
-    if (!std::isfinite(sc * sc)) return fail("the level table overflows");
+    if (!std::isfinite(sc * sc)) return refuse("the level table overflows");
     for (int i = in.kp_ptr[f]; i < in.kp_ptr[f + 1]; i++)
-      if (in.octave[i] < 0 || in.octave[i] >= in.n_levels[f]) return fail("an octave is outside 0 .. n_levels - 1");
+      if (in.octave[i] < 0 || in.octave[i] >= in.n_levels[f]) return refuse("an octave is outside 0 .. n_levels - 1");
   }
-  if (!all_finite(in.kp, 3 * n)) return fail("a keypoint coordinate is not finite");
+  if (!all_finite(in.kp, 3 * n)) return refuse("a keypoint coordinate is not finite");
   *n_keypoints = n;
   return CS_OK;
 }
 
 // What cs_orb_search_run checks before anything is launched.  *n_queries = query_ptr[n_jobs].
 int check_jobs(const char* who, int n_frames, int n_jobs, const Jobs& in, size_t* n_queries) {
-  auto fail = [&](const char* what) { cs_set_error((std::string(who) + ": " + what).c_str()); return CS_ERR_INVALID_ARG; };
-  if (!in.frame_of_job || !in.pose8 || !in.th || !in.max_hamming || !in.flags || !in.query_ptr) return fail("NULL argument");
+  const cs::Refuse refuse{who};
+  if (!in.frame_of_job || !in.pose8 || !in.th || !in.max_hamming || !in.flags || !in.query_ptr) return refuse("NULL argument");
   if (int rc = cs::check_partition(std::string(who) + ": query_ptr", in.query_ptr, n_jobs)) return rc;
   const size_t nj = (size_t)n_jobs, n = (size_t)in.query_ptr[n_jobs];
-  if (n > (size_t)INT_MAX / 8) return fail("too many queries for one call");
-  if (n > 0 && (!in.X || !in.normal || !in.dist_range || !in.qdesc || !in.skip)) return fail("NULL query array");
-  if (!all_finite(in.pose8, 8 * nj)) return fail("a pose is not finite");
+  if (n > (size_t)INT_MAX / 8) return refuse("too many queries for one call");
+  if (n > 0 && (!in.X || !in.normal || !in.dist_range || !in.qdesc || !in.skip)) return refuse("NULL query array");
+  if (!all_finite(in.pose8, 8 * nj)) return refuse("a pose is not finite");
   for (size_t j = 0; j < nj; j++) {
     const double* T = in.pose8 + 8 * j;
-    if (in.frame_of_job[j] < 0 || in.frame_of_job[j] >= n_frames) return fail("a frame index is outside the handle's frame set");
-    if (!positive(std::sqrt(T[3] * T[3] + T[4] * T[4] + T[5] * T[5] + T[6] * T[6]))) return fail("a quaternion has zero norm or overflows");
-    if (!(T[7] > 0)) return fail("the scale s must be positive");
-    if (!positive(in.th[j])) return fail("th must be finite and positive");
-    if (in.max_hamming[j] < 0 || in.max_hamming[j] > 256) return fail("max_hamming must be in 0 .. 256");
-    if (in.flags[j] & ~(cs::ORB_CHECK_VIEW | cs::ORB_CHECK_REPROJ)) return fail("unknown flag bits");
+    if (in.frame_of_job[j] < 0 || in.frame_of_job[j] >= n_frames) return refuse("a frame index is outside the handle's frame set");
+    if (!cs::quaternion_norm_ok(T + 3)) return refuse("a quaternion has zero norm or overflows");
+    if (!(T[7] > 0)) return refuse("the scale s must be positive");
+    if (!positive(in.th[j])) return refuse("th must be finite and positive");
+    if (in.max_hamming[j] < 0 || in.max_hamming[j] > 256) return refuse("max_hamming must be in 0 .. 256");
+    if (in.flags[j] & ~(cs::ORB_CHECK_VIEW | cs::ORB_CHECK_REPROJ)) return refuse("unknown flag bits");
   }
-  if (!all_finite(in.X, 3 * n) || !all_finite(in.normal, 3 * n)) return fail("a point or a normal is not finite");
+  if (!all_finite(in.X, 3 * n) || !all_finite(in.normal, 3 * n)) return refuse("a point or a normal is not finite");
   for (size_t i = 0; i < n; i++) {
     const double lo = in.dist_range[2 * i], hi = in.dist_range[2 * i + 1];
-    if (!(positive(lo) && std::isfinite(hi) && lo <= hi)) return fail("0 < min_distance <= max_distance, both finite, are required");
+    if (!(positive(lo) && std::isfinite(hi) && lo <= hi)) return refuse("0 < min_distance <= max_distance, both finite, are required");
   }
   *n_queries = n;
   return CS_OK;
 }
 
 int set_frames(cs_orb_search* B, const char* who, const cs_orb_search_params* p, int n_frames, const Frames& in) {
-  auto fail = [&](const char* what) { cs_set_error((std::string(who) + ": " + what).c_str()); return CS_ERR_INVALID_ARG; };
-  if (!B || n_frames < 0) return fail("no handle or a negative frame count");
+  const cs::Refuse refuse{who};
+  if (!B || n_frames < 0) return refuse("no handle or a negative frame count");
   int rc = check_params(who, p); if (rc) return rc;
   size_t n = 0;
   rc = check_frames(who, p, n_frames, in, &n); if (rc) return rc;
   const size_t nf = (size_t)n_frames, cells = (size_t)p->grid_cols * p->grid_rows;
 
   cs::Layout l;
-  const size_t at_frame = l.add(nf * sizeof(cs::OrbFrame)), at_start = l.add(nf * (cells + 1) * sizeof(int)), at_kp4 = l.add(n * cs::ORB_KP_DOUBLES * 8),
-               at_orig = l.add(n * sizeof(int)), at_desc = l.add(n * cs::ORB_DESC_WORDS * sizeof(unsigned));
-  l.add(16);                                           // (a set without a frame still has a buffer)
+  const auto at_frame = l.add<cs::OrbFrame>(nf);
+  const auto at_start = l.add<int>(nf * (cells + 1));
+  const auto at_kp4 = l.add<double>(n * cs::ORB_KP_DOUBLES);
+  const auto at_orig = l.add<int>(n);
+  const auto at_desc = l.add<unsigned>(n * cs::ORB_DESC_WORDS);
+  l.add<unsigned char>(16);                            // (a set without a frame still has a buffer)
   CS_HIP_TRY(hipSetDevice(B->device));
   B->has_frames = false;                               // (from here on the set the handle held is gone)
   CS_ENSURE(B->d_set, l.bytes);
   CS_ENSURE(B->h_set, l.bytes);
   unsigned char* h = B->h_set.p;
-  cs::OrbFrame* frame = reinterpret_cast<cs::OrbFrame*>(h + at_frame);
+  cs::OrbFrame* frame = at_frame.at(h);
   for (size_t f = 0; f < nf; f++) {
     const int first = in.kp_ptr[f], count = in.kp_ptr[f + 1] - first;
     cs::orb_frame_record(in.cam + 5 * f, in.bounds + 4 * f, in.scale_factor[f], in.n_levels[f], p->grid_cols, p->grid_rows, first, (int)(f * (cells + 1)), frame[f]);
     frame[f].n_sorted = cs::orb_pack_frame(frame[f], count, in.kp + 3 * (size_t)first, in.octave + first, in.desc + 32 * (size_t)first,
-                                           reinterpret_cast<int*>(h + at_start) + f * (cells + 1), reinterpret_cast<double*>(h + at_kp4) + cs::ORB_KP_DOUBLES * (size_t)first,
-                                           reinterpret_cast<int*>(h + at_orig) + first, reinterpret_cast<unsigned*>(h + at_desc) + cs::ORB_DESC_WORDS * (size_t)first);
+                                           at_start.at(h) + f * (cells + 1), at_kp4.at(h) + cs::ORB_KP_DOUBLES * (size_t)first, at_orig.at(h) + first,
+                                           at_desc.at(h) + cs::ORB_DESC_WORDS * (size_t)first);
   }
   CS_HIP_TRY(hipMemcpyAsync(B->d_set.p, h, l.bytes, hipMemcpyHostToDevice, B->st));
   CS_HIP_TRY(hipStreamSynchronize(B->st));
   B->prm.min_dist_factor = p->min_dist_factor; B->prm.max_dist_factor = p->max_dist_factor; B->prm.view_cos = p->view_cos; B->prm.chi2_mono = p->chi2_mono;
   B->prm.chi2_stereo = p->chi2_stereo; B->prm.grid_cols = p->grid_cols; B->prm.grid_rows = p->grid_rows;
-  B->at_frame = at_frame; B->at_start = at_start; B->at_kp4 = at_kp4; B->at_orig = at_orig; B->at_desc = at_desc;
+  B->set_frame = at_frame; B->set_start = at_start; B->set_kp4 = at_kp4; B->set_orig = at_orig; B->set_desc = at_desc;
   B->n_frames = n_frames;
   B->has_frames = true;
   return CS_OK;
 }
 
 int run(cs_orb_search* B, const char* who, int n_jobs, const Jobs& in, const Outputs& out, bool inspect) {
-  auto fail = [&](const char* what) { cs_set_error((std::string(who) + ": " + what).c_str()); return CS_ERR_INVALID_ARG; };
-  if (!B || n_jobs < 0) return fail("no handle or a negative job count");
-  if (!B->has_frames) return fail("the handle holds no frame set (cs_orb_search_set_frames)");
-  if (n_jobs == 0) { B->kernel_ms = B->host_ms = 0; B->ran = true; return CS_OK; }
-  const double t_begin = cs::now_ms();
+  const cs::Refuse refuse{who};
+  if (!B || n_jobs < 0) return refuse("no handle or a negative job count");
+  if (!B->has_frames) return refuse("the handle holds no frame set (cs_orb_search_set_frames)");
+  cs::BatchCall call(*B);
+  if (n_jobs == 0) return call.empty();
   size_t n = 0;
   int rc = check_jobs(who, B->n_frames, n_jobs, in, &n); if (rc) return rc;
-  if (!out.n_ok) return fail("NULL output");
-  if (n > 0 && (!out.status || !out.best_idx || !out.best_dist || !out.level || (inspect && (!out.insp5 || !out.n_window || !out.n_candidates)))) return fail("NULL output");
-  B->ran = false;                                      // (a refused call leaves the last run's timing in place; one that fails from here on does not)
-  const size_t nj = (size_t)n_jobs;
-  size_t n_chunks = 0;
-  for (size_t j = 0; j < nj; j++) n_chunks += ((size_t)(in.query_ptr[j + 1] - in.query_ptr[j]) + cs::ORB_CHUNK - 1) / cs::ORB_CHUNK;
+  if (!out.n_ok) return refuse("NULL output");
+  if (n > 0 && (!out.status || !out.best_idx || !out.best_dist || !out.level || (inspect && (!out.insp5 || !out.n_window || !out.n_candidates)))) return refuse("NULL output");
+  call.point_of_no_return();                           // (behind the checks: cs_batch_handle.h, BatchCall)
+  const size_t nj = (size_t)n_jobs, n_chunks = cs::chunk_count(in.query_ptr, nj, cs::ORB_CHUNK);
 
   cs::Layout li, lo;
-  const size_t in_job = li.add(nj * sizeof(cs::OrbJob)), in_q = li.add(n * cs::ORB_QUERY_DOUBLES * 8), in_qd = li.add(n * cs::ORB_DESC_WORDS * sizeof(unsigned)), in_skip = li.add(n),
-               in_chunk = li.add(n_chunks * sizeof(cs::OrbChunk));
-  const size_t out_idx = lo.add(n * sizeof(int)), out_dist = lo.add(n * sizeof(int)), out_st = lo.add(n), out_lv = lo.add(n),
-               out_insp = lo.add(inspect ? n * cs::ORB_INSPECT_DOUBLES * 8 : 0), out_nw = lo.add(inspect ? n * sizeof(int) : 0), out_nc = lo.add(inspect ? n * sizeof(int) : 0);
-  lo.add(16);                                          // (a batch without a query still has an output buffer)
+  const auto in_job = li.add<cs::OrbJob>(nj);
+  const auto in_q = li.add<double>(n * cs::ORB_QUERY_DOUBLES);
+  const auto in_qd = li.add<unsigned>(n * cs::ORB_DESC_WORDS);
+  const auto in_skip = li.add<unsigned char>(n);
+  const auto in_chunk = li.add<cs::Chunk>(n_chunks);
+  const auto out_idx = lo.add<int>(n), out_dist = lo.add<int>(n);
+  const auto out_st = lo.add<unsigned char>(n), out_lv = lo.add<unsigned char>(n);
+  const auto out_insp = lo.add<double>(inspect ? n * cs::ORB_INSPECT_DOUBLES : 0);
+  const auto out_nw = lo.add<int>(inspect ? n : 0), out_nc = lo.add<int>(inspect ? n : 0);
+  lo.add<unsigned char>(16);                           // (a batch without a query still has an output buffer)
 
   cs::OrbLaunch a;
   auto pack = [&] {
-    unsigned char* h = B->h_in.p;
-    cs::OrbJob* job = reinterpret_cast<cs::OrbJob*>(h + in_job);
-    cs::OrbChunk* chunk = reinterpret_cast<cs::OrbChunk*>(h + in_chunk);
-    size_t c = 0;
-    for (size_t j = 0; j < nj; j++) {
-      cs::orb_job_record(in.pose8 + 8 * j, in.th[j], in.frame_of_job[j], in.max_hamming[j], in.flags[j], job[j]);
-      for (int first = in.query_ptr[j]; first < in.query_ptr[j + 1]; first += cs::ORB_CHUNK, c++) {
-        const int left = in.query_ptr[j + 1] - first;
-        chunk[c].job = (int)j; chunk[c].first = first; chunk[c].count = left < cs::ORB_CHUNK ? left : (int)cs::ORB_CHUNK; chunk[c].pad = 0;
-      }
-    }
-    double* q = reinterpret_cast<double*>(h + in_q);
-    unsigned* qd = reinterpret_cast<unsigned*>(h + in_qd);
+    cs::OrbJob* job = in_job.at(B->h_in.p);
+    for (size_t j = 0; j < nj; j++) cs::orb_job_record(in.pose8 + 8 * j, in.th[j], in.frame_of_job[j], in.max_hamming[j], in.flags[j], job[j]);
+    cs::chunk_fill(in.query_ptr, nj, cs::ORB_CHUNK, in_chunk.at(B->h_in.p));
+    double* q = in_q.at(B->h_in.p);
+    unsigned* qd = in_qd.at(B->h_in.p);
     for (size_t i = 0; i < n; i++, q += cs::ORB_QUERY_DOUBLES, qd += cs::ORB_DESC_WORDS) {
       std::memcpy(q, in.X + 3 * i, 3 * 8);
       std::memcpy(q + 3, in.normal + 3 * i, 3 * 8);
       std::memcpy(q + 6, in.dist_range + 2 * i, 2 * 8);
       cs::orb_pack_descriptor(in.qdesc + 32 * i, qd);
     }
-    if (n) std::memcpy(h + in_skip, in.skip, n);
+    if (n) cs::copy_in(in_skip, B->h_in, in.skip);
     std::memset(&a, 0, sizeof(a));
     a.n_chunks = (int)n_chunks;
     a.prm = B->prm;
-    a.frame = reinterpret_cast<const cs::OrbFrame*>(B->d_set.p + B->at_frame);
-    a.start = reinterpret_cast<const int*>(B->d_set.p + B->at_start);
-    a.kp4 = reinterpret_cast<const double*>(B->d_set.p + B->at_kp4);
-    a.orig = reinterpret_cast<const int*>(B->d_set.p + B->at_orig);
-    a.desc = reinterpret_cast<const unsigned*>(B->d_set.p + B->at_desc);
-    a.chunk = reinterpret_cast<const cs::OrbChunk*>(B->d_in.p + in_chunk);
-    a.job = reinterpret_cast<const cs::OrbJob*>(B->d_in.p + in_job);
-    a.q8 = reinterpret_cast<const double*>(B->d_in.p + in_q);
-    a.qdesc = reinterpret_cast<const unsigned*>(B->d_in.p + in_qd);
-    a.skip = B->d_in.p + in_skip;
-    a.status = B->d_out.p + out_st;
-    a.level = B->d_out.p + out_lv;
-    a.best_idx = reinterpret_cast<int*>(B->d_out.p + out_idx);
-    a.best_dist = reinterpret_cast<int*>(B->d_out.p + out_dist);
-    a.insp5 = inspect ? reinterpret_cast<double*>(B->d_out.p + out_insp) : nullptr;
-    a.n_window = inspect ? reinterpret_cast<int*>(B->d_out.p + out_nw) : nullptr;
-    a.n_candidates = inspect ? reinterpret_cast<int*>(B->d_out.p + out_nc) : nullptr;
+    unsigned char *ds = B->d_set.p, *di = B->d_in.p, *dout = B->d_out.p;
+    a.frame = B->set_frame.at(ds); a.start = B->set_start.at(ds); a.kp4 = B->set_kp4.at(ds); a.orig = B->set_orig.at(ds); a.desc = B->set_desc.at(ds);
+    a.chunk = in_chunk.at(di); a.job = in_job.at(di); a.q8 = in_q.at(di); a.qdesc = in_qd.at(di); a.skip = in_skip.at(di);
+    a.status = out_st.at(dout); a.level = out_lv.at(dout); a.best_idx = out_idx.at(dout); a.best_dist = out_dist.at(dout);
+    a.insp5 = inspect ? out_insp.at(dout) : nullptr;
+    a.n_window = inspect ? out_nw.at(dout) : nullptr;
+    a.n_candidates = inspect ? out_nc.at(dout) : nullptr;
   };
   rc = cs::batch_round_trip(*B, li.bytes, lo.bytes, true, pack, [&] { cs::orb_search_launch(a, inspect, B->st); }); if (rc) return rc;
 
   if (n) {
-    const unsigned char* h = B->h_out.p;
-    std::memcpy(out.status, h + out_st, n);
-    std::memcpy(out.level, h + out_lv, n);
-    std::memcpy(out.best_idx, h + out_idx, n * sizeof(int));
-    std::memcpy(out.best_dist, h + out_dist, n * sizeof(int));
+    cs::copy_out(out_st, B->h_out, out.status);
+    cs::copy_out(out_lv, B->h_out, out.level);
+    cs::copy_out(out_idx, B->h_out, out.best_idx);
+    cs::copy_out(out_dist, B->h_out, out.best_dist);
     if (inspect) {
-      std::memcpy(out.insp5, h + out_insp, n * cs::ORB_INSPECT_DOUBLES * 8);
-      std::memcpy(out.n_window, h + out_nw, n * sizeof(int));
-      std::memcpy(out.n_candidates, h + out_nc, n * sizeof(int));
+      cs::copy_out(out_insp, B->h_out, out.insp5);
+      cs::copy_out(out_nw, B->h_out, out.n_window);
+      cs::copy_out(out_nc, B->h_out, out.n_candidates);
     }
   }
-  for (size_t j = 0; j < nj; j++) {
-    int ok = 0;
-    for (int i = in.query_ptr[j]; i < in.query_ptr[j + 1]; i++) ok += out.status[i] == CS_ORB_OK ? 1 : 0;
-    out.n_ok[j] = ok;
-  }
-  B->host_ms = cs::now_ms() - t_begin;
-  B->ran = true;
-  return CS_OK;
+  cs::count_status(in.query_ptr, nj, out.status, CS_ORB_OK, out.n_ok);
+  return call.done();
 }
 
 int one_shot(const char* who, int device, const cs_orb_search_params* p, int n_frames, const Frames& fr, int n_jobs, const Jobs& jb, const Outputs& out, bool inspect) {
-  if (n_frames < 0 || n_jobs < 0) { cs_set_error(std::string(who) + ": a negative frame or job count"); return CS_ERR_INVALID_ARG; }
-  cs_orb_search* B = nullptr;
-  int rc = cs_orb_search_create(device, &B);
-  if (rc) return rc;
-  rc = set_frames(B, who, p, n_frames, fr);
-  if (!rc) rc = run(B, who, n_jobs, jb, out, inspect);
-  cs_orb_search_destroy(B);
-  return rc;
+  if (n_frames < 0 || n_jobs < 0) return cs::Refuse{who}("a negative frame or job count");
+  return cs::batch_one_shot<cs_orb_search>(device, [&](cs_orb_search* B) -> int {
+    if (int rc = set_frames(B, who, p, n_frames, fr)) return rc;
+    return run(B, who, n_jobs, jb, out, inspect);
+  });
 }
 
 }  // namespace
@@ -328,10 +304,8 @@ int cs_orb_search_inspect(int device, const cs_orb_search_params* p, int n_frame
 }
 
 int cs_orb_search_mutual(int n1, const int* best12, const unsigned char* status12, int n2, const int* best21, const unsigned char* status21, int* match12_out, int* n_out) {
-  if (n1 < 0 || n2 < 0 || !n_out || (n1 > 0 && (!best12 || !status12 || !match12_out)) || (n2 > 0 && (!best21 || !status21))) {
-    cs_set_error("cs_orb_search_mutual: a negative count or a NULL argument");
-    return CS_ERR_INVALID_ARG;
-  }
+  if (n1 < 0 || n2 < 0 || !n_out || (n1 > 0 && (!best12 || !status12 || !match12_out)) || (n2 > 0 && (!best21 || !status21)))
+    return cs::Refuse{"cs_orb_search_mutual"}("a negative count or a NULL argument");
   int n = 0;
   for (int i = 0; i < n1; i++) {
     const int j = best12[i];

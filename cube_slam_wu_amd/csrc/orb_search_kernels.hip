@@ -26,17 +26,14 @@ namespace cs {
 namespace {
 
 static_assert(ORB_CHUNK == 64, "one query per lane");
-static_assert(sizeof(OrbFrame) % 16 == 0 && sizeof(OrbJob) % 16 == 0 && sizeof(OrbChunk) == 16, "records behind aligned addresses");
+static_assert(sizeof(OrbFrame) % 16 == 0 && sizeof(OrbJob) % 16 == 0 && sizeof(Chunk) == 16, "records behind aligned addresses");
 
 template <bool INSPECT>
 __global__ void __launch_bounds__(64 * ORB_WAVES_PER_BLOCK) orb_search_kernel(const OrbLaunch a) {
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int c = blockIdx.x * ORB_WAVES_PER_BLOCK + wave;
-  if (c >= a.n_chunks) return;                       // (a whole wavefront leaves: there is no barrier in this kernel)
-  const OrbChunk ch = a.chunk[c];
-  const int lane = threadIdx.x & 63;
-  if (lane >= ch.count) return;
-  const OrbJob& J = a.job[ch.job];                   // wave-uniform
+  Chunk ch;
+  int lane;
+  if (!wave_chunk<ORB_WAVES_PER_BLOCK>(a.chunk, a.n_chunks, ch, lane)) return;      // (a whole wavefront, or a lane past the count: there is no barrier in this kernel)
+  const OrbJob& J = a.job[ch.owner];                 // wave-uniform
   const OrbFrame& F = a.frame[J.frame];              // wave-uniform
   const size_t i = (size_t)ch.first + lane;
 

@@ -2,17 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cs_chunk.h"
 #include "cs_orb_search.h"
 
 namespace cs {
 
 // ORB_CHUNK: queries of ONE job a wave handles, one per lane
 enum { ORB_WAVES_PER_BLOCK = 4, ORB_CHUNK = 64 };
-
-// A wave's work: `count` (1 .. ORB_CHUNK) queries of job `job`, from query `first` on (an index into the whole batch)
-struct OrbChunk {
-  int job, first, count, pad;
-};
 
 struct OrbLaunch {
   int n_chunks;
@@ -24,7 +20,7 @@ struct OrbLaunch {
   const int* orig;                 // ... their index in their frame
   const unsigned* desc;            // ... their ORB_DESC_WORDS words, behind a 256-byte aligned base
   // the call's
-  const OrbChunk* chunk;           // n_chunks, built by the host from query_ptr
+  const Chunk* chunk;              // n_chunks (cs_chunk.h; owner = the job), built by the host from query_ptr
   const OrbJob* job;               // n_jobs (orb_job_record)
   const double* q8;                // n_queries x ORB_QUERY_DOUBLES, behind a 256-byte aligned base
   const unsigned* qdesc;           // n_queries x ORB_DESC_WORDS, behind a 256-byte aligned base

@@ -23,41 +23,39 @@ struct cs_pose_batch : cs::BatchHandle {};
 namespace {
 
 int check_params(const cs_pose_params* p) {
-  if (!p || p->n_rounds < 1 || p->n_rounds > cs::POSE_MAX_ROUNDS) { cs_set_error("cs_pose: n_rounds must be 1..8"); return CS_ERR_INVALID_ARG; }
+  const cs::Refuse refuse{"cs_pose"};
+  if (!p || p->n_rounds < 1 || p->n_rounds > cs::POSE_MAX_ROUNDS) return refuse("n_rounds must be 1..8");
   for (int r = 0; r < p->n_rounds; r++)
-    if (p->iterations[r] < 0) { cs_set_error("cs_pose: negative iteration count"); return CS_ERR_INVALID_ARG; }
+    if (p->iterations[r] < 0) return refuse("negative iteration count");
   return CS_OK;
 }
 
 // What both entries check of their inputs.  *n_obs = obs_ptr[n_frames].
-int check_frames(const std::string& who, int n_frames, const double* Tcw7_in, const double* intr5, const int* obs_ptr, const double* Xw3, const double* meas3,
+int check_frames(const char* who, int n_frames, const double* Tcw7_in, const double* intr5, const int* obs_ptr, const double* Xw3, const double* meas3,
                  const double* info9, const unsigned char* is_stereo, size_t* n_obs) {
-  if (!Tcw7_in || !intr5 || !obs_ptr) { cs_set_error(who + ": NULL argument"); return CS_ERR_INVALID_ARG; }
-  if (int rc = cs::check_partition(who + ": obs_ptr", obs_ptr, n_frames)) return rc;
+  const cs::Refuse refuse{who};
+  if (!Tcw7_in || !intr5 || !obs_ptr) return refuse("NULL argument");
+  if (int rc = cs::check_partition(std::string(who) + ": obs_ptr", obs_ptr, n_frames)) return rc;
   *n_obs = (size_t)obs_ptr[n_frames];
-  if (*n_obs > 0 && (!Xw3 || !meas3 || !info9 || !is_stereo)) { cs_set_error(who + ": NULL observation array"); return CS_ERR_INVALID_ARG; }
+  if (*n_obs > 0 && (!Xw3 || !meas3 || !info9 || !is_stereo)) return refuse("NULL observation array");
   return CS_OK;
 }
 
-struct InLayout { size_t T, intr, obs, ptr, bytes; };
+// the parts of d_in, in their order
+struct InLayout {
+  cs::Layout all;
+  cs::Part<double> T, intr, obs;
+  cs::Part<int> ptr;
+  InLayout(size_t nf, size_t n_obs)
+      : T(all.add<double>(7 * nf)), intr(all.add<double>(5 * nf)), obs(all.add<double>(n_obs * cs::POSE_OBS_DOUBLES)), ptr(all.add<int>(nf + 1)) {}
+};
 
-InLayout in_layout(size_t nf, size_t n_obs) {
-  cs::Layout in;
-  InLayout L;
-  L.T = in.add(7 * nf * 8);
-  L.intr = in.add(5 * nf * 8);
-  L.obs = in.add(n_obs * cs::POSE_OBS_DOUBLES * 8);
-  L.ptr = in.add((nf + 1) * 4);
-  L.bytes = in.bytes;
-  return L;
-}
-
-void pack_inputs(unsigned char* h, const InLayout& L, size_t nf, size_t n_obs, const double* Tcw7_in, const double* intr5, const int* obs_ptr,
+void pack_inputs(cs::PinBuf<unsigned char>& h, const InLayout& L, size_t n_obs, const double* Tcw7_in, const double* intr5, const int* obs_ptr,
                  const double* Xw3, const double* meas3, const double* info9, const unsigned char* is_stereo) {
-  std::memcpy(h + L.T, Tcw7_in, 7 * nf * 8);
-  std::memcpy(h + L.intr, intr5, 5 * nf * 8);
-  std::memcpy(h + L.ptr, obs_ptr, (nf + 1) * 4);
-  double* rec = reinterpret_cast<double*>(h + L.obs);
+  cs::copy_in(L.T, h, Tcw7_in);
+  cs::copy_in(L.intr, h, intr5);
+  cs::copy_in(L.ptr, h, obs_ptr);
+  double* rec = L.obs.at(h.p);
   for (size_t i = 0; i < n_obs; i++, rec += cs::POSE_OBS_DOUBLES) {
     const double *X = Xw3 + 3 * i, *m = meas3 + 3 * i, *W = info9 + 9 * i;
     rec[0] = X[0]; rec[1] = X[1]; rec[2] = X[2];
@@ -76,10 +74,7 @@ void pack_inputs(unsigned char* h, const InLayout& L, size_t nf, size_t n_obs, c
 void set_inputs(cs::PoseLaunch& a, unsigned char* d, const InLayout& L, int n_frames) {
   std::memset(&a, 0, sizeof(a));
   a.n_frames = n_frames;
-  a.T0 = reinterpret_cast<const double*>(d + L.T);
-  a.intr = reinterpret_cast<const double*>(d + L.intr);
-  a.obs = reinterpret_cast<const double*>(d + L.obs);
-  a.obs_ptr = reinterpret_cast<const int*>(d + L.ptr);
+  a.T0 = L.T.at(d); a.intr = L.intr.at(d); a.obs = L.obs.at(d); a.obs_ptr = L.ptr.at(d);
 }
 
 }  // namespace
@@ -106,42 +101,40 @@ int cs_pose_batch_optimize(cs_pose_batch* B, const cs_pose_params* p, int n_fram
                            double* Tcw7_out, unsigned char* inlier_out, double* chi2_out, int* iterations_done) {
   if (!B || n_frames < 0) return CS_ERR_INVALID_ARG;
   int rc = check_params(p); if (rc) return rc;
-  B->ran = false;
-  if (n_frames == 0) { B->kernel_ms = B->host_ms = 0; B->ran = true; return CS_OK; }
-  if (!Tcw7_out) { cs_set_error("cs_pose_batch_optimize: NULL argument"); return CS_ERR_INVALID_ARG; }
-  const double t_begin = cs::now_ms();
+  const cs::Refuse refuse{"cs_pose_batch_optimize"};
+  cs::BatchCall call(*B);
+  call.point_of_no_return();                           // (before the checks: cs_batch_handle.h, BatchCall)
+  if (n_frames == 0) return call.empty();
+  if (!Tcw7_out) return refuse("NULL argument");
   size_t n_obs = 0;
   rc = check_frames("cs_pose_batch_optimize", n_frames, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo, &n_obs); if (rc) return rc;
-  if (n_obs > 0 && !inlier_out) { cs_set_error("cs_pose_batch_optimize: NULL observation array"); return CS_ERR_INVALID_ARG; }
+  if (n_obs > 0 && !inlier_out) return refuse("NULL observation array");
   const size_t R = (size_t)p->n_rounds, nf = (size_t)n_frames;
 
   // ---- layout of the two buffers
-  const InLayout L = in_layout(nf, n_obs);
+  const InLayout L(nf, n_obs);
   cs::Layout out;
-  const size_t out_T = out.add(7 * nf * 8), out_chi = out.add(nf * R * 8), out_it = out.add(nf * R * 4), out_lv = out.add(n_obs);
+  const auto out_T = out.add<double>(7 * nf), out_chi = out.add<double>(nf * R);
+  const auto out_it = out.add<int>(nf * R);
+  const auto out_lv = out.add<unsigned char>(n_obs);
 
   cs::PoseLaunch a;
   auto pack = [&] {
-    pack_inputs(B->h_in.p, L, nf, n_obs, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo);
+    pack_inputs(B->h_in, L, n_obs, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo);
     set_inputs(a, B->d_in.p, L, n_frames);
     a.n_rounds = p->n_rounds;
     for (int r = 0; r < cs::POSE_MAX_ROUNDS; r++) a.iterations[r] = r < p->n_rounds ? p->iterations[r] : 0;
     a.robust_rounds = p->robust_rounds; a.restart_each_round = p->restart_each_round ? 1 : 0;
     a.huber_mono = p->huber_mono; a.huber_stereo = p->huber_stereo; a.chi2_mono = p->chi2_mono; a.chi2_stereo = p->chi2_stereo;
-    a.T_out = reinterpret_cast<double*>(B->d_out.p + out_T);
-    a.chi2_out = reinterpret_cast<double*>(B->d_out.p + out_chi);
-    a.iters_out = reinterpret_cast<int*>(B->d_out.p + out_it);
-    a.inlier = B->d_out.p + out_lv;
+    a.T_out = out_T.at(B->d_out.p); a.chi2_out = out_chi.at(B->d_out.p); a.iters_out = out_it.at(B->d_out.p); a.inlier = out_lv.at(B->d_out.p);
   };
-  rc = cs::batch_round_trip(*B, L.bytes, out.bytes, true, pack, [&] { cs::pose_launch(a, B->st); }); if (rc) return rc;
+  rc = cs::batch_round_trip(*B, L.all.bytes, out.bytes, true, pack, [&] { cs::pose_launch(a, B->st); }); if (rc) return rc;
 
-  std::memcpy(Tcw7_out, B->h_out.p + out_T, 7 * nf * 8);
-  if (chi2_out) std::memcpy(chi2_out, B->h_out.p + out_chi, nf * R * 8);
-  if (iterations_done) std::memcpy(iterations_done, B->h_out.p + out_it, nf * R * 4);
-  if (n_obs) std::memcpy(inlier_out, B->h_out.p + out_lv, n_obs);
-  B->host_ms = cs::now_ms() - t_begin;
-  B->ran = true;
-  return CS_OK;
+  cs::copy_out(out_T, B->h_out, Tcw7_out);
+  if (chi2_out) cs::copy_out(out_chi, B->h_out, chi2_out);
+  if (iterations_done) cs::copy_out(out_it, B->h_out, iterations_done);
+  if (n_obs) cs::copy_out(out_lv, B->h_out, inlier_out);
+  return call.done();
 }
 
 int cs_pose_batch_last_timing(const cs_pose_batch* B, double* kernel_ms, double* host_ms) { return cs::batch_last_timing(B, kernel_ms, host_ms); }
@@ -149,47 +142,43 @@ int cs_pose_batch_last_timing(const cs_pose_batch* B, double* kernel_ms, double*
 int cs_pose_optimize_batch(int device, const cs_pose_params* p, int n_frames, const double* Tcw7_in, const double* intr5, const int* obs_ptr,
                            const double* Xw3, const double* meas3, const double* info9, const unsigned char* is_stereo,
                            double* Tcw7_out, unsigned char* inlier_out, double* chi2_out, int* iterations_done) {
-  cs_pose_batch* B = nullptr;
-  int rc = cs_pose_batch_create(device, &B);
-  if (rc) return rc;
-  rc = cs_pose_batch_optimize(B, p, n_frames, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo, Tcw7_out, inlier_out, chi2_out, iterations_done);
-  cs_pose_batch_destroy(B);
-  return rc;
+  return cs::batch_one_shot<cs_pose_batch>(device, [&](cs_pose_batch* B) -> int {
+    return cs_pose_batch_optimize(B, p, n_frames, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo, Tcw7_out, inlier_out, chi2_out, iterations_done);
+  });
 }
 
 int cs_pose_linearize_batch(int device, int robust, double huber_mono, double huber_stereo, int n_frames, const double* Tcw7_in, const double* intr5,
                             const int* obs_ptr, const double* Xw3, const double* meas3, const double* info9, const unsigned char* is_stereo,
                             double* H21, double* b6, double* chi2) {
-  if (n_frames < 0) { cs_set_error("cs_pose_linearize_batch: a negative frame count"); return CS_ERR_INVALID_ARG; }
+  const cs::Refuse refuse{"cs_pose_linearize_batch"};
+  if (n_frames < 0) return refuse("a negative frame count");
   if (n_frames == 0) return CS_OK;
   size_t n_obs = 0;
   int rc = check_frames("cs_pose_linearize_batch", n_frames, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo, &n_obs); if (rc) return rc;
-  if (!H21 || !b6 || !chi2) { cs_set_error("cs_pose_linearize_batch: NULL output"); return CS_ERR_INVALID_ARG; }
-  cs_pose_batch* B = nullptr;
-  rc = cs_pose_batch_create(device, &B);
-  if (rc) return rc;
-  cs::Guard<cs_pose_batch> g(B, cs_pose_batch_destroy);     // (this call's own handle: never disarmed)
-  const size_t nf = (size_t)n_frames;
-  const InLayout L = in_layout(nf, n_obs);
-  cs::Layout out;
-  const size_t out_sys = out.add(nf * cs::POSE_SYSTEM_DOUBLES * 8), out_lv = out.add(n_obs);
-  cs::PoseLaunch a;
-  auto pack = [&] {
-    pack_inputs(B->h_in.p, L, nf, n_obs, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo);
-    set_inputs(a, B->d_in.p, L, n_frames);
-    a.robust_rounds = robust ? 1 : 0;
-    a.huber_mono = huber_mono; a.huber_stereo = huber_stereo;
-    a.system_out = reinterpret_cast<double*>(B->d_out.p + out_sys);
-    a.inlier = B->d_out.p + out_lv;
-  };
-  rc = cs::batch_round_trip(*B, L.bytes, out.bytes, false, pack, [&] { cs::pose_launch_linearize(a, B->st); }); if (rc) return rc;
-  const double* sys = reinterpret_cast<const double*>(B->h_out.p + out_sys);
-  for (size_t f = 0; f < nf; f++, sys += cs::POSE_SYSTEM_DOUBLES) {
-    std::memcpy(H21 + 21 * f, sys, 21 * 8);
-    std::memcpy(b6 + 6 * f, sys + 21, 6 * 8);
-    chi2[f] = sys[27];
-  }
-  return CS_OK;
+  if (!H21 || !b6 || !chi2) return refuse("NULL output");
+  return cs::batch_one_shot<cs_pose_batch>(device, [&](cs_pose_batch* B) -> int {
+    const size_t nf = (size_t)n_frames;
+    const InLayout L(nf, n_obs);
+    cs::Layout out;
+    const auto out_sys = out.add<double>(nf * cs::POSE_SYSTEM_DOUBLES);
+    const auto out_lv = out.add<unsigned char>(n_obs);
+    cs::PoseLaunch a;
+    auto pack = [&] {
+      pack_inputs(B->h_in, L, n_obs, Tcw7_in, intr5, obs_ptr, Xw3, meas3, info9, is_stereo);
+      set_inputs(a, B->d_in.p, L, n_frames);
+      a.robust_rounds = robust ? 1 : 0;
+      a.huber_mono = huber_mono; a.huber_stereo = huber_stereo;
+      a.system_out = out_sys.at(B->d_out.p); a.inlier = out_lv.at(B->d_out.p);
+    };
+    rc = cs::batch_round_trip(*B, L.all.bytes, out.bytes, false, pack, [&] { cs::pose_launch_linearize(a, B->st); }); if (rc) return rc;
+    const double* sys = out_sys.at(B->h_out.p);
+    for (size_t f = 0; f < nf; f++, sys += cs::POSE_SYSTEM_DOUBLES) {
+      std::memcpy(H21 + 21 * f, sys, 21 * 8);
+      std::memcpy(b6 + 6 * f, sys + 21, 6 * 8);
+      chi2[f] = sys[27];
+    }
+    return CS_OK;
+  });
 }
 
 }  // extern "C"

@@ -19,17 +19,14 @@ namespace cs {
 namespace {
 
 static_assert(TRI_CHUNK == 64, "one match per lane");
-static_assert(sizeof(TriPair) % 16 == 0 && sizeof(TriChunk) == 16, "records behind aligned addresses");
+static_assert(sizeof(TriPair) % 16 == 0 && sizeof(Chunk) == 16, "records behind aligned addresses");
 
 template <bool INSPECT>
 __global__ void __launch_bounds__(64 * TRI_WAVES_PER_BLOCK) triangulate_kernel(const TriLaunch a) {
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int c = blockIdx.x * TRI_WAVES_PER_BLOCK + wave;
-  if (c >= a.n_chunks) return;                       // (a whole wavefront leaves: there is no barrier in this kernel)
-  const TriChunk ch = a.chunk[c];
-  const int lane = threadIdx.x & 63;
-  if (lane >= ch.count) return;
-  const TriPair& P = a.pair[ch.pair];                // wave-uniform
+  Chunk ch;
+  int lane;
+  if (!wave_chunk<TRI_WAVES_PER_BLOCK>(a.chunk, a.n_chunks, ch, lane)) return;      // (a whole wavefront, or a lane past the count: there is no barrier in this kernel)
+  const TriPair& P = a.pair[ch.owner];               // wave-uniform
   const size_t i = (size_t)ch.first + lane;
 
   double m[TRI_MATCH_DOUBLES];

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cs_chunk.h"
 #include "cs_triangulate.h"
 
 namespace cs {
@@ -9,15 +10,10 @@ namespace cs {
 // TRI_CHUNK: matches of ONE pair a wave handles, one per lane
 enum { TRI_WAVES_PER_BLOCK = 4, TRI_CHUNK = 64 };
 
-// A wave's work: `count` (1 .. TRI_CHUNK) matches of pair `pair`, from match `first` on (an index into the whole batch)
-struct TriChunk {
-  int pair, first, count, pad;
-};
-
 struct TriLaunch {
   int n_chunks;
   TriParams prm;
-  const TriChunk* chunk;           // n_chunks, built by the host from match_ptr
+  const Chunk* chunk;              // n_chunks (cs_chunk.h; owner = the pair), built by the host from match_ptr
   const TriPair* pair;             // n_pairs (cs_triangulate.h: triangulate_pair_record)
   const double* rec;               // n_matches x TRI_MATCH_DOUBLES, behind a 256-byte aligned base
   double* out8;                    // n_matches x TRI_OUT_DOUBLES, behind a 256-byte aligned base

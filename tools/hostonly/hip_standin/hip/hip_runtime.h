@@ -1,6 +1,6 @@
-// hip/hip_runtime.h -- a counting stand-in for the HIP runtime, for tools/hostonly/owners_check.cpp, ba_proj_edge_check.cpp and
-// image_batch_check.cpp alone (its directory goes first on the include path).  Device and pinned memory are malloc, copies are memcpy, streams and events are tokens; everything
-// made is kept in a set of what is live, and a free or destroy of something that is not live aborts.  Only what cs_hip_util.h, ba_dbuf.h and
+// hip/hip_runtime.h -- a counting stand-in for the HIP runtime, for tools/hostonly/owners_check.cpp, ba_proj_edge_check.cpp,
+// image_batch_check.cpp and batch_handle_check.cpp alone (its directory goes first on the include path).  Device and pinned memory are malloc, copies are memcpy, streams and events are tokens; everything
+// made is kept in a set of what is live and counted (made, dropped), and a free or destroy of something that is not live aborts.  Only what cs_hip_util.h, ba_dbuf.h and
 // cs_image_batch.h call exists, and the two handle types that ba_types.h's launcher declarations name.
 #pragma once
 #include <cstddef>
@@ -21,14 +21,18 @@ typedef hipStandinToken* hipEvent_t;
 namespace hip_standin {
 enum Kind { DEVICE, PINNED, STREAM, EVENT, N_KINDS };
 inline std::set<void*>& live(int kind) { static std::set<void*> s[N_KINDS]; return s[kind]; }
+inline long& made(int kind) { static long n[N_KINDS]; return n[kind]; }
+inline long& dropped(int kind) { static long n[N_KINDS]; return n[kind]; }
 inline hipError_t make(int kind, void** out, size_t bytes) {
   *out = std::malloc(bytes ? bytes : 1);
+  made(kind)++;
   live(kind).insert(*out);
   return hipSuccess;
 }
 inline hipError_t drop(int kind, void* p) {
   if (!live(kind).erase(p)) { std::fprintf(stderr, "hip stand-in: kind %d: %p given back but not live\n", kind, p); std::abort(); }
   std::free(p);
+  dropped(kind)++;
   return hipSuccess;
 }
 // the knob: the k-th hipEventSynchronize from now (1 = the next) returns an error; 0 = none does
