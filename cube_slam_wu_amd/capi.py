@@ -68,7 +68,7 @@ DECLARED_SYMBOLS = [
     "cs_detector_destroy", "cs_detect_cuboids", "cs_batch_create", "cs_batch_max_boxes", "cs_batch_run", "cs_batch_submit", "cs_batch_collect",
     "cs_bgr_to_gray", "cs_edge_distance_maps", "cs_edge_distance_maps_multi", "cs_detect_cuboids_gray", "cs_batch_create_gray", "cs_batch_refill_gray", "cs_batch_refill_wait", "cs_batch_destroy", "cs_batch_last_timing", "cs_batch_debug_candidates", "cs_batch_debug_kept", "cs_batch_set_debug", "cs_batch_set_pipeline_chunks", "cs_detect_lines_gray", "cs_detect_lines_batch", "cs_detect_lines_last_timing", "cs_detect_lsd_gray", "cs_detect_lsd_batch", "cs_detect_lsd_last_timing",
     "cs_lbd_describe_gray", "cs_detect_descrip_lines_gray", "cs_detect_descrip_lines_batch", "cs_lbd_match", "cs_lbd_match_batch", "cs_lbd_last_timing",
-    "cs_check_score_atan2", "cs_check_score_sample_index", "cs_check_line_setup",
+    "cs_check_score_atan2", "cs_check_score_sample_index", "cs_check_line_setup", "cs_check_vp_support",
 ]
 
 # cs_keyline (one octave: start / end point, direction, length of the support region in pixels)
@@ -134,6 +134,21 @@ def check_score_atan2(y, x):
     if rc != 0:
         raise RuntimeError("cs_check_score_atan2 failed (%d): %s" % (rc, last_error()))
     return out, acc.astype(bool)
+
+
+def check_vp_support(mid_x, mid_y, angle, vp_x, vp_y, thre, swapped=False, form=0):
+    """The vanishing-point support of one segment table against the points (vp_x, vp_y): (device, host), each (n, 2) bounding segment angles
+    (NaN = no inlier).  form 0 = staged wavefront form on pairs of points, 1 = unstaged on pairs, 2 = unstaged on single points."""
+    mid_x, mid_y, angle = (np.ascontiguousarray(a, np.float64) for a in (mid_x, mid_y, angle))
+    vp_x, vp_y = np.ascontiguousarray(vp_x, np.float64), np.ascontiguousarray(vp_y, np.float64)
+    if not (mid_x.ndim == 1 and mid_x.shape == mid_y.shape == angle.shape) or vp_x.ndim != 1 or vp_x.shape != vp_y.shape:
+        raise ValueError("mid_x, mid_y, angle must be 1-D of one length, vp_x and vp_y 1-D of one length")
+    n = len(vp_x)
+    dev, host = np.zeros((n, 2)), np.zeros((n, 2))
+    rc = lib().cs_check_vp_support(_dp(mid_x), _dp(mid_y), _dp(angle), len(mid_x), _dp(vp_x), _dp(vp_y), n, C.c_double(thre), int(bool(swapped)), int(form), _dp(dev), _dp(host))
+    if rc != 0:
+        raise RuntimeError("cs_check_vp_support failed (%d): %s" % (rc, last_error()))
+    return dev, host
 
 
 def check_score_sample_index(sy, sx, map_w, a, b):

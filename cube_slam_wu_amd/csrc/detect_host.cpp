@@ -573,6 +573,62 @@ int cs_check_line_setup(const double* lines, int n, const int* rois, const int* 
   CS_GUARD_END("cs_check_line_setup")
 }
 
+// VP_support_edge_infos (object_3d_util.cpp:548-619) for one point, written plainly: the angle of every segment, the inlier test, the
+// unwrap against the first inlier, strict first-occurrence extremes.  What cs_check_vp_support sets the device's decisions against.
+static void vp_support_reference(const double* mx, const double* my, const double* la, int m, double vpx, double vpy, double thre, bool swapped, double* out2) {
+  bool have = false;
+  double base = 0, hi = 0, lo = 0;
+  int i_hi = -1, i_lo = -1;
+  for (int i = 0; i < m; i++) {
+    const double raw = cs::cs_atan2(my[i] - vpy, mx[i] - vpx);
+    const double nrm = cs::normalize_to_pi(raw);
+    double d = cs::dabs(la[i] - nrm);
+    d = cs::dmin(d, CS_PI - d);
+    if (!(d < thre)) continue;
+    if (!have) { have = true; base = hi = lo = raw; i_hi = i_lo = i; continue; }
+    double sh = raw;
+    if ((raw - base) < -CS_PI) sh = raw + 2 * CS_PI;
+    else if ((raw - base) > CS_PI) sh = raw - 2 * CS_PI;
+    if (sh > hi) { hi = sh; i_hi = i; }
+    if (sh < lo) { lo = sh; i_lo = i; }
+  }
+  const double NaN = __builtin_nan("");
+  const double a_hi = have ? la[i_hi] : NaN, a_lo = have ? la[i_lo] : NaN;
+  out2[0] = swapped ? a_lo : a_hi;
+  out2[1] = swapped ? a_hi : a_lo;
+}
+
+int cs_check_vp_support(const double* mid_x, const double* mid_y, const double* angle, int m, const double* vp_x, const double* vp_y, int n, double thre, int swapped, int form,
+                        double* dev, double* host) {
+  if (m < 0 || n < 0 || (m > 0 && (!mid_x || !mid_y || !angle)) || (n > 0 && (!vp_x || !vp_y || !dev || !host))) { cs_set_error("cs_check_vp_support: null array"); return CS_ERR_INVALID_ARG; }
+  if (form < 0 || form > 2) { cs_set_error("cs_check_vp_support: form must be 0, 1 or 2"); return CS_ERR_INVALID_ARG; }
+  if (m > (1 << 20) || n > (1 << 20)) { cs_set_error("cs_check_vp_support: more than 2^20 segments or points"); return CS_ERR_CAPACITY; }
+  if (int rc = cs::check_device(0)) return rc;
+  if (n == 0) return CS_OK;
+  CS_GUARD_BEGIN
+  CS_HIP_TRY(hipSetDevice(0));
+  for (int p = 0; p < n; p++) vp_support_reference(mid_x, mid_y, angle, m, vp_x[p], vp_y[p], thre, swapped != 0, host + 2 * (size_t)p);
+  const size_t M = (size_t)m, N = (size_t)n;
+  DevBuf<double> d;       // mid x, mid y, angle | vp x, vp y | out
+  CS_ENSURE(d, 3 * M + 4 * N + 1);
+  double* seg = d.p;
+  double* pts = d.p + 3 * M;
+  double* out = pts + 2 * N;
+  if (m) {
+    CS_HIP_TRY(hipMemcpy(seg, mid_x, sizeof(double) * M, hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(seg + M, mid_y, sizeof(double) * M, hipMemcpyHostToDevice));
+    CS_HIP_TRY(hipMemcpy(seg + 2 * M, angle, sizeof(double) * M, hipMemcpyHostToDevice));
+  }
+  CS_HIP_TRY(hipMemcpy(pts, vp_x, sizeof(double) * N, hipMemcpyHostToDevice));
+  CS_HIP_TRY(hipMemcpy(pts + N, vp_y, sizeof(double) * N, hipMemcpyHostToDevice));
+  CS_HIP_TRY(hipMemset(out, 0, sizeof(double) * 2 * N));
+  cs::launch_vp_support_check(seg, seg + M, seg + 2 * M, m, pts, pts + N, n, thre, swapped != 0, form, out, nullptr);
+  CS_HIP_TRY(hipGetLastError());
+  CS_HIP_TRY(hipMemcpy(dev, out, sizeof(double) * 2 * N, hipMemcpyDeviceToHost));
+  return CS_OK;
+  CS_GUARD_END("cs_check_vp_support")
+}
+
 void cs_detect_default_params(cs_detect_params* p) {
   if (!p) return;
   p->consider_config_1 = 1; p->consider_config_2 = 1;

@@ -29,7 +29,7 @@
 #include "../../include/cubeslam_hip.h"
 #include "detect_types.h"
 #include "cs_atan2_lean.h"
-#include "cs_atan2_float.h"
+#include "cs_vp_support.h"
 
 namespace cs {
 
@@ -73,123 +73,60 @@ __device__ __forceinline__ long long xcd_virtual_block() {
 //
 // The reference evaluates atan2 for every segment, keeps those whose direction is within `thre` of the segment's own angle,
 // unwraps the kept angles against the first one (smooth_jump_angles, :278-302) and returns the segment angles at the arg-max and
-// arg-min.  Only DECISIONS leave this function (which segments are inliers, which one is the extreme), so the angles are
-// evaluated in float (|error| < 2.5e-6 rad over all quadrants, tests/test_device_decisions.py) and every decision that falls
-// within a margin of its threshold -- a few per million -- is re-decided with the exact cs_atan2 values of the segments
-// involved.  Error budget of a float angle: conversion of the double differences 1e-7, quotient (__fdividef) 3e-7, polynomial
-// 2e-6, pi constants and the +-2 pi shift 7e-7; of a difference of two of them twice that.  Margins: 1e-5 on the inlier test,
-// 2e-5 on the unwrap decision and on the comparisons against the running extremes.  Each decision therefore equals the
-// reference's, including ties (equal angles keep the first occurrence, :609-614 maxCoeff / minCoeff).
+// arg-min.  Only DECISIONS leave this function (which segments are inliers, which one is the extreme), and cs_vp_support.h states
+// how they are reached without an angle: a cross/dot classification in float (out for sure, in for sure, undecided) and the order
+// of the inliers from double cross products, with the exact cs_atan2 values of the segments involved wherever a margin is hit --
+// a few per ten thousand.  Each decision therefore equals the reference's, including ties (equal angles keep the first
+// occurrence, :609-614 maxCoeff / minCoeff).
 // out[0], out[1] = the two bounding segment angles (NaN = none): (max, min) for vp 1, swapped for vp 2, 3 (:609-614).
-__device__ __attribute__((noinline)) double vp_exact_raw(double dy, double dx) { return cs_atan2(dy, dx); }
-
-// exact unwrapped angle of segment i against the first inlier `ib` (both re-evaluated: this runs a few times per million segments)
-__device__ __forceinline__ double vp_exact_unwrapped(const double* __restrict__ mx, const double* __restrict__ my, int i, int ib, double vpxk, double vpyk) {
-  const double raw = vp_exact_raw(my[i] - vpyk, mx[i] - vpxk);
-  if (i == ib) return raw;
-  const double base = vp_exact_raw(my[ib] - vpyk, mx[ib] - vpxk);
-  if ((raw - base) < -CS_PI) return raw + 2 * CS_PI;
-  if ((raw - base) > CS_PI) return raw - 2 * CS_PI;
-  return raw;
-}
 // the rarely taken exact decisions, out of line so that the sweep's loop body stays small
-__device__ __attribute__((noinline)) float vp_rare_unwrapped_f(const double* mx, const double* my, int i, int ib, double vpxk, double vpyk) {
-  return (float)vp_exact_unwrapped(mx, my, i, ib, vpxk, vpyk);
-}
 __device__ __attribute__((noinline)) bool vp_rare_greater(const double* mx, const double* my, int i, int i_ref, int ib, double vpxk, double vpyk) {
   return vp_exact_unwrapped(mx, my, i, ib, vpxk, vpyk) > vp_exact_unwrapped(mx, my, i_ref, ib, vpxk, vpyk);
 }
 __device__ __attribute__((noinline)) bool vp_rare_less(const double* mx, const double* my, int i, int i_ref, int ib, double vpxk, double vpyk) {
   return vp_exact_unwrapped(mx, my, i, ib, vpxk, vpyk) < vp_exact_unwrapped(mx, my, i_ref, ib, vpxk, vpyk);
 }
-// exact inlier test of one segment, with its angle as a float (returned by value: a callee that stores through a pointer would
-// make the compiler assume the segment arrays may change, and their loads could no longer be scalar)
-struct VpExactInlier { float at; int inl; };
-__device__ __attribute__((noinline)) VpExactInlier vp_rare_inlier(double dyd, double dxd, double lai, double thre) {
-  const double raw = cs_atan2(dyd, dxd);
-  const double nrm = normalize_to_pi(raw);
-  double d = dabs(lai - nrm);
-  d = dmin(d, CS_PI - d);
-  return VpExactInlier{(float)raw, d < thre ? 1 : 0};
-}
-
-struct VpRun {               // running state of one vanishing point's sweep over the segments
-  bool have;
-  int ib, i_hi, i_lo;        // first inlier, running arg-max / arg-min of the unwrapped angle
-  float base_f, hi_f, lo_f;  // their float angles
-  double hx, hy, lx, ly;     // mid point - vanishing point of the two running extremes
+__device__ __attribute__((noinline)) bool vp_rare_inlier(double dyd, double dxd, double lai, double thre) { return vp_exact_inlier(dyd, dxd, lai, thre); }
+// (All three return by value: a callee that stores through a pointer would make the compiler assume the segment arrays may change,
+// and their loads could no longer be scalar.)  The order step's view of the two comparisons:
+struct VpRareOrder {
+  const double* mx; const double* my; double vpx, vpy;
+  __device__ __forceinline__ bool greater(int i, int i_ref, int ib) const { return vp_rare_greater(mx, my, i, i_ref, ib, vpx, vpy); }
+  __device__ __forceinline__ bool less(int i, int i_ref, int ib) const { return vp_rare_less(mx, my, i, i_ref, ib, vpx, vpy); }
 };
 
-// one segment (mid point mxi, myi; angle lai) against one vanishing point
-__device__ __forceinline__ void vp_step(const double* __restrict__ mx, const double* __restrict__ my, int i, double mxi, double myi, double lai,
-                                        double vpxk, double vpyk, double thre, float thre_f, VpRun& R) {
-  const float PI_F = 3.14159274f, HPI_F = 1.57079637f, M_IN = 1.0e-5f, M_ORD = 2.0e-5f;
-  const double dyd = myi - vpyk, dxd = mxi - vpxk;
-  bool usable;
-  float at = atan2_float((float)dyd, (float)dxd, &usable);
-  float nr = at;                           // normalize_to_pi: the distance below is circular, so which side of the fold a float lands on does not matter
-  if (at > HPI_F) nr = at - PI_F; else if (at < -HPI_F) nr = at + PI_F;
-  float df = fabsf((float)lai - nr);
-  df = fminf(df, PI_F - df);
-  bool inl = usable && df < thre_f - M_IN;              // (zero or non-finite differences are decided exactly)
-  if (!(inl || (usable && df > thre_f + M_IN))) { const VpExactInlier x = vp_rare_inlier(dyd, dxd, lai, thre); inl = x.inl != 0; at = x.at; }
-  if (inl) {
-    if (!R.have) {  // first inlier: base of smooth_jump_angles (:278-302), and initial arg-max / arg-min
-      R.have = true; R.ib = i; R.i_hi = i; R.i_lo = i; R.base_f = at; R.hi_f = at; R.lo_f = at; R.hx = dxd; R.hy = dyd; R.lx = dxd; R.ly = dyd;
-    } else {
-      const float d = at - R.base_f;
-      float sh = d < -PI_F ? at + 2.0f * PI_F : d > PI_F ? at - 2.0f * PI_F : at;
-      if (fabsf(fabsf(d) - PI_F) < M_ORD) sh = vp_rare_unwrapped_f(mx, my, i, R.ib, vpxk, vpyk);
-      // Against the running extremes.  Far vanishing points see all segments within a fraction of a milliradian, closer than the
-      // float angles resolve; inside the margin the order comes from the cross product of the two (double) difference vectors:
-      // its sign is the order of the true angles (both unwrapped angles lie within the margin of each other, far from the
-      // +-pi fold), reliable when it exceeds its rounding error -- 1e-12 of the product of the 1-norms, i.e. an angle
-      // difference above 1e-12 rad, thousands of ulps of the rounded atan2 values.  Below that (equal or nearly equal
-      // directions): the exact values decide, including the tie rule.
-      if (sh > R.hi_f + M_ORD) { R.hi_f = sh; R.i_hi = i; R.hx = dxd; R.hy = dyd; }                 // maxCoeff: first occurrence, strict
-      else if (sh > R.hi_f - M_ORD) {
-        const double c = R.hx * dyd - R.hy * dxd, lim = 1.0e-12 * ((dabs(dxd) + dabs(dyd)) * (dabs(R.hx) + dabs(R.hy)));
-        const bool greater = c > lim ? true : c < -lim ? false : vp_rare_greater(mx, my, i, R.i_hi, R.ib, vpxk, vpyk);
-        if (greater) { R.hi_f = sh; R.i_hi = i; R.hx = dxd; R.hy = dyd; }
-      }
-      if (sh < R.lo_f - M_ORD) { R.lo_f = sh; R.i_lo = i; R.lx = dxd; R.ly = dyd; }                 // minCoeff
-      else if (sh < R.lo_f + M_ORD) {
-        const double c = R.lx * dyd - R.ly * dxd, lim = 1.0e-12 * ((dabs(dxd) + dabs(dyd)) * (dabs(R.lx) + dabs(R.ly)));
-        const bool less = c < -lim ? true : c > lim ? false : vp_rare_less(mx, my, i, R.i_lo, R.ib, vpxk, vpyk);
-        if (less) { R.lo_f = sh; R.i_lo = i; R.lx = dxd; R.ly = dyd; }
-      }
-    }
-  }
+// one segment (mid point - vanishing point dxd, dyd; angle lai) with its classification: survivor = not out for sure
+__device__ __forceinline__ void vp_step(const double* __restrict__ mx, const double* __restrict__ my, int i, double dxd, double dyd, double lai, bool survivor, bool in_for_sure,
+                                        double vpxk, double vpyk, double thre, VpRun& R) {
+  bool inlier = in_for_sure;
+  if (survivor && !in_for_sure) inlier = vp_rare_inlier(dyd, dxd, lai, thre);      // (rare: the band between the two tests is 2e-4 rad wide)
+  vp_order_step(R, i, dxd, dyd, inlier, VpRareOrder{mx, my, vpxk, vpyk});
 }
 
 // One wave's staging area for a chunk of 64 segments (the wave sits inside one job: every lane sweeps the same segments).
 struct VpChunk {
   double2 xy[64];   // mid point
   double ang[64];   // segment angle
-  float2 dir[64];   // unit direction (cosf, sinf: 2 ulp)
+  float2 dir[64];   // unit direction (sincosf: 2 ulp)
 };
 
 // K vanishing points swept together over the job's segments, 64 segments per chunk.
 //   staging: lane u loads segment u of the chunk (one coalesced load per array) and its direction into LDS; both passes read
 //     from there (pass 1: every lane the same address = broadcast; pass 2: a gather), not from global memory.
-//   pass 1 (every segment, branch-free, ~10 instructions per vanishing point): drop what is certainly not an inlier.  With u the
-//     segment's unit direction and d = mid point - vanishing point, the circular angle between them is below thre exactly
-//     when |u x d| < tan(thre) |u . d|; in float, with thre widened by 1e-4 rad and 2e-6 (|dx| + |dy|) of slack for the
-//     roundings (error budget: direction 3e-7 rad, each product / sum 6e-8 relative), no true inlier fails the test.
-//     The survivors (about a fifth of the segments) are a bit mask per lane.
-//   pass 2 (survivors, in order): vp_step -- float angle, the inlier decision, the running extremes, exact where a margin is hit.
-// UNIFORM = false (a wave that spans jobs; only the round-based path produces those): no staging, every segment goes to vp_step.
+//   pass 1 (every segment, branch-free): the three-way classification of cs_vp_support.h on the float difference and the staged
+//     direction.  It leaves two bit masks per lane and vanishing point: the survivors (not out for sure, about a fifth of the
+//     segments) and, among them, those that are in for sure.  The few undecided ones get the exact inlier test right behind it.
+//   pass 2 (inliers, in order): vp_order_step on the double difference.
+// UNIFORM = false (a wave that spans jobs; only the round-based path produces those; and vp3_support_kernel's single lanes): no
+//   staging, the same classification per segment with the direction computed in place, the same step for what it does not drop.
 // out[2k], out[2k+1] = the two bounding segment angles of vanishing point k (NaN = none): (max, min) when !swapped[k], else (min, max) (:609-614)
 template <int K, bool UNIFORM>
 __device__ __forceinline__ void vp_support_multi(const double* __restrict__ mx, const double* __restrict__ my, const double* __restrict__ la, int m, VpChunk* ch,
                                                  const double* vpx, const double* vpy, const double* thre, const bool* swapped, bool lane_on, double* out) {
   VpRun R[K];
-  float thre_f[K], tan_f[K];
+  VpTan tn[K];
 #pragma unroll
-  for (int k = 0; k < K; k++) {
-    R[k] = VpRun{false, 0, 0, 0, 0.f, 0.f, 0.f, 0., 0., 0., 0.}; thre_f[k] = (float)thre[k];
-    tan_f[k] = thre_f[k] < 1.5f ? tanf(thre_f[k] + 1.0e-4f) : __builtin_huge_valf();      // (a threshold near 90 degrees keeps everything)
-  }
+  for (int k = 0; k < K; k++) { R[k] = vp_run_empty(); tn[k] = vp_tan_bounds((float)thre[k]); }
   if (UNIFORM) {
     const int lane = threadIdx.x & 63;
     for (int c0 = 0; c0 < m; c0 += 64) {
@@ -199,44 +136,68 @@ __device__ __forceinline__ void vp_support_multi(const double* __restrict__ mx, 
         const double a = la[c0 + lane];
         ch->xy[lane] = make_double2(mx[c0 + lane], my[c0 + lane]);
         ch->ang[lane] = a;
-        ch->dir[lane] = make_float2(cosf((float)a), sinf((float)a));
+        float ux, uy;
+        sincosf((float)a, &uy, &ux);
+        ch->dir[lane] = make_float2(ux, uy);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      unsigned long long mask[K];
+      // pass 1: one bit per segment and test, gathered in 32-bit words (the segment index is uniform, so a bit is one select of a scalar and an OR)
+      unsigned keep[K][2], sure[K][2];
 #pragma unroll
-      for (int k = 0; k < K; k++) mask[k] = 0;
+      for (int k = 0; k < K; k++) { keep[k][0] = keep[k][1] = 0u; sure[k][0] = sure[k][1] = 0u; }
+#pragma unroll
+      for (int w = 0; w < 2; w++) {
+        const int u1 = min(n, 32 * w + 32);
 #pragma unroll 4
-      for (int u = 0; u < n; u++) {
-        const double2 P = ch->xy[u];
-        const float2 ud = ch->dir[u];
+        for (int u = 32 * w; u < u1; u++) {
+          const double2 P = ch->xy[u];
+          const float2 ud = ch->dir[u];
+          const unsigned bit = 1u << (u & 31);
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-          const float fx = (float)(P.x - vpx[k]), fy = (float)(P.y - vpy[k]);
-          const float cr = fabsf(__builtin_fmaf(fx, ud.y, -(fy * ud.x))), dt = fabsf(__builtin_fmaf(fx, ud.x, fy * ud.y));
-          const bool out_for_sure = cr > __builtin_fmaf(tan_f[k], dt, 2.0e-6f * (fabsf(fx) + fabsf(fy)));      // (false for NaN / inf: those go on)
-          mask[k] |= (unsigned long long)(out_for_sure ? 0 : 1) << u;
+          for (int k = 0; k < K; k++) {
+            const VpSure s = vp_classify_sure((float)(P.x - vpx[k]), (float)(P.y - vpy[k]), ud.x, ud.y, tn[k]);
+            keep[k][w] |= s.out ? 0u : bit;
+            sure[k][w] |= s.in ? bit : 0u;
+          }
         }
       }
 #pragma unroll
       for (int k = 0; k < K; k++) {
-        unsigned long long mk = lane_on ? mask[k] : 0ull;
-        while (__any(mk != 0)) {
-          if (mk != 0) {
-            const int u = __ffsll((long long)mk) - 1;
-            mk &= mk - 1;
+        unsigned long long mk = lane_on ? ((unsigned long long)keep[k][1] << 32) | keep[k][0] : 0ull;
+        // the undecided survivors (the band between the two tests is 2e-4 rad wide: a lane in a hundred has one) are settled exactly first ...
+        unsigned long long und = mk & ~(((unsigned long long)sure[k][1] << 32) | sure[k][0]);
+        while (__any(und != 0)) {
+          if (und != 0) {
+            const int u = __ffsll((long long)und) - 1;
             const double2 P = ch->xy[u];
-            vp_step(mx, my, c0 + u, P.x, P.y, ch->ang[u], vpx[k], vpy[k], thre[k], thre_f[k], R[k]);
+            if (!vp_rare_inlier(P.y - vpy[k], P.x - vpx[k], ch->ang[u], thre[k])) mk &= ~(und & -und);
+            und &= und - 1;
           }
         }
+        // ... so that pass 2 walks inliers only.  (No branch on the lane's own mask: a lane that has run out goes through the step switched off.)
+        const VpRareOrder exact{mx, my, vpx[k], vpy[k]};
+        if (__any(mk != 0)) do {
+          const bool active = mk != 0;
+          const int u = active ? __ffsll((long long)mk) - 1 : 0;
+          mk &= mk - 1;
+          const double2 P = ch->xy[u];
+          vp_order_step(R[k], c0 + u, P.x - vpx[k], P.y - vpy[k], active, exact);
+        } while (__any(mk != 0));
       }
     }
   } else {
     const int mm = lane_on ? m : 0;
     for (int i = 0; i < mm; i++) {
       const double X = mx[i], Y = my[i], A = la[i];
+      float ux, uy;
+      sincosf((float)A, &uy, &ux);
 #pragma unroll
-      for (int k = 0; k < K; k++) vp_step(mx, my, i, X, Y, A, vpx[k], vpy[k], thre[k], thre_f[k], R[k]);
+      for (int k = 0; k < K; k++) {
+        const double dxd = X - vpx[k], dyd = Y - vpy[k];
+        const VpSure s = vp_classify_sure((float)dxd, (float)dyd, ux, uy, tn[k]);
+        vp_step(mx, my, i, dxd, dyd, A, !s.out, s.in, vpx[k], vpy[k], thre[k], R[k]);
+      }
     }
   }
   const double NaN = __builtin_nan("");
@@ -328,6 +289,40 @@ __global__ __launch_bounds__(64) void vp3_support_kernel(DetectDeviceView v, Swe
   const bool swapped3 = true;
   vp_support_multi<1, false>(v.mid_x + jd.line_off, v.mid_y + jd.line_off, v.line_angle + jd.line_off, on ? jd.m : 0, nullptr, &vx, &vy, &sp.vp3_thre_rad, &swapped3, on, o2);
   if (on) { double* t3 = v.bound3 + 2 * ((size_t)j * VP3_RPCAP + rp); t3[0] = o2[0]; t3[1] = o2[1]; }
+}
+
+// cs_check_vp_support: vp_support_multi on its own, one segment table against n points.  FORM 0: the staged <2, true> form, a lane per
+// pair of points (2q, 2q + 1), whole wavefronts (the staging needs every lane; the surplus lanes are off); FORM 1: <2, false>, a lane per
+// pair; FORM 2: <1, false>, a lane per point.  The second point of the last pair of an odd n repeats the first and is not written.
+template <int FORM>
+__global__ __launch_bounds__(64) void vp_support_check_kernel(const double* __restrict__ mx, const double* __restrict__ my, const double* __restrict__ la, int m,
+                                                              const double* __restrict__ px, const double* __restrict__ py, int n, double thre, bool swapped, double* __restrict__ out) {
+  constexpr int K = FORM == 2 ? 1 : 2;
+  const int q = blockIdx.x * 64 + threadIdx.x, p0 = q * K;
+  const bool on = p0 < n;
+  if (FORM != 0 && !on) return;
+  __shared__ VpChunk chunk;
+  double vx[K], vy[K], th[K], o[2 * K];
+  bool sw[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const int p = on ? (p0 + k < n ? p0 + k : p0) : 0;
+    vx[k] = on ? px[p] : 0.0; vy[k] = on ? py[p] : 0.0; th[k] = thre; sw[k] = swapped;
+  }
+  vp_support_multi<K, FORM == 0>(mx, my, la, m, &chunk, vx, vy, th, sw, on, o);
+  if (!on) return;
+#pragma unroll
+  for (int k = 0; k < K; k++)
+    if (p0 + k < n) { out[2 * (p0 + k)] = o[2 * k]; out[2 * (p0 + k) + 1] = o[2 * k + 1]; }
+}
+void launch_vp_support_check(const double* mx, const double* my, const double* la, int m, const double* px, const double* py, int n, double thre, bool swapped, int form,
+                             double* out, hipStream_t st) {
+  if (n <= 0) return;
+  const int lanes = form == 2 ? n : (n + 1) / 2;
+  const dim3 grid((lanes + 63) / 64), block(64);
+  if (form == 0) hipLaunchKernelGGL(vp_support_check_kernel<0>, grid, block, 0, st, mx, my, la, m, px, py, n, thre, swapped, out);
+  else if (form == 1) hipLaunchKernelGGL(vp_support_check_kernel<1>, grid, block, 0, st, mx, my, la, m, px, py, n, thre, swapped, out);
+  else hipLaunchKernelGGL(vp_support_check_kernel<2>, grid, block, 0, st, mx, my, la, m, px, py, n, thre, swapped, out);
 }
 
 // getVanishingPoints (object_3d_util.cpp:928-937) alone: the same arithmetic as the head of vp_support_kernel

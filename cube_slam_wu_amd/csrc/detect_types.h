@@ -149,6 +149,8 @@ void launch_scan_compact(const DetectDeviceView& v, hipStream_t st);
 void launch_scan_compact_trips(const DetectDeviceView& v, int* cnt, int max_trips, hipStream_t st);
 void launch_score(const DetectDeviceView& v, const SweepParams& sp, long long n_valid_bound, long long slot_total, hipStream_t st);
 void launch_score_atan2_check(const double* y, const double* x, int n, double* out, int* accepted, hipStream_t st);      // (cs_check_score_atan2)
+void launch_vp_support_check(const double* mx, const double* my, const double* la, int m, const double* px, const double* py, int n, double thre, bool swapped, int form,
+                             double* out, hipStream_t st);      // (cs_check_vp_support)
 void launch_score_sample_index_check(const double* sy, const double* sx, const int* map_w, const double* a, const double* b, int n, int* index, double* probe, hipStream_t st);      // (cs_check_score_sample_index)
 void launch_gather_corners(const DetectDeviceView& v, const SweepParams& sp, const long long* slots, int n, double* out, hipStream_t st);
 void launch_rank(const DetectDeviceView& v, const RankView& rv, const RankParams& rp, hipStream_t st, long long max_slots_per_box = 0, bool with_corners = true);

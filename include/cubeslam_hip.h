@@ -285,6 +285,14 @@ int cs_check_score_atan2(const double* y, const double* x, int n, double* out, i
  * a = 1 and b = 1.5 * 2^-53 the sum is 1 + 2^-52 under round-to-nearest and 1 under round-toward-zero, which tells whether the
  * lane's rounding mode is what the rest of the scorer's arithmetic assumes.  Runs on device 0. */
 int cs_check_score_sample_index(const double* sy, const double* sx, const int* map_w, const double* a, const double* b, int n, int* index, double* probe);
+/* A check of the vanishing-point support on its own: one table of m segments (mid points, angles in [-pi/2, pi/2]) against n points
+ * (n <= 2^20, m <= 2^20) with one threshold `thre` (radians).  form selects the device procedure: 0 = the staged wavefront form, points taken
+ * in pairs, one pair per lane; 1 = the unstaged form, one pair per lane; 2 = the unstaged form, one point per lane.  dev[2p], dev[2p+1]
+ * = the two bounding segment angles of point p as the device decides them, host[2p], host[2p+1] = the same from the reference's loop
+ * evaluated plainly on the host (atan2 of every segment, the unwrap, strict first-occurrence extremes): (max, min), or (min, max) when
+ * swapped != 0; NaN, NaN where no segment is an inlier.  Runs on device 0. */
+int cs_check_vp_support(const double* mid_x, const double* mid_y, const double* angle, int m, const double* vp_x, const double* vp_y, int n, double thre, int swapped, int form,
+                        double* dev, double* host);
 /* A check of the line setup on its own: one frame's n segments (lines: n x 4 doubles x1 y1 x2 y2; n above the line setup's capacity of
  * 512 rows is refused with CS_ERR_CAPACITY) against r expanded ROIs (rois: r x 4 ints, the inclusive bounds left top right bottom; yt:
  * r x 2 ints, the job's yaw and top-edge sample counts -- a job with either at 0 is one the sweep skips and comes back with m = 0) and the
